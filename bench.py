@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- the contract benchmark: f32 CSR SpMV, 10M rows x 32 nnz/row per GPU (BASELINE C2/C5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+At N = 1 a plain run sets up, warms up, times the K steps and prints the headline; `roofline` then holds what the timed steps'
+own HIP events give.  Everything else at N = 1 -- the PMC traffic passes, the cold launches, `other_pattern`, `inspector`,
+`cpu_baseline` with its parity gate and BASELINE configs C3 / C4 (`configs`) -- runs only with --full.  An N > 1 line carries its
+exchange self-check and legs either way.  --dump-outputs DIR writes y as the last timed step left it to DIR/y.npy (f32; rank 0's
+rows; larger than 64 MB: DIR/y_sample.npy, a fixed seeded sample of them), before anything else touches it.
 
 A "step" is one pass of the hot path over the resident matrix: y = A.x with A, x, y in HBM.
   N = 1  BASELINE configs[1]: SparseMatCRS<f32,u32>, 10,000,000 rows, 32 nnz/row, SURVEY 8d's primary pattern
@@ -63,6 +69,9 @@ CALIB_SUBSTR = "k_ew"       # the element-wise kernel the PMC child pass runs fo
 CALIB_N = 1 << 26           # x += y on 2^26 f32: reads 2 x 256 MiB, writes 256 MiB, 16 B per lane
 FLUSH_BYTES = 512 << 20
 WATCHDOG_EXIT = 3           # exit status of every rank when an optional N > 1 leg hung (the headline line is still printed)
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: y whole up to this size, else a seeded sample of DUMP_SAMPLE entries
+DUMP_SAMPLE = 8 << 20
+DUMP_SEED = 0x5EED0D0
 
 
 def algorithmic_bytes(rows, nnz, x_ref):
@@ -507,6 +516,18 @@ def extra_configs(args, lib, check, sm, synth, np, stream, sync):
 
 
 
+def dump_outputs(out_dir, np, y):
+    """--dump-outputs: y of the last timed step as DIR/y.npy (f32), or, when larger than DUMP_MAX_BYTES, the entries at a fixed
+    seeded set of rows (sorted, the same for the same arguments) as DIR/y_sample.npy -- so two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if y.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "y.npy"), y)
+        return
+    rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, len(y), DUMP_SAMPLE))
+    np.save(os.path.join(out_dir, "y_sample.npy"), y[rows])
+
+
 def stats(ts):
     s = sorted(ts)
     return {"mean": sum(s) / len(s), "median": s[len(s) // 2], "min": s[0], "max": s[-1], "launches": len(s)}
@@ -662,6 +683,11 @@ def main():
                     help="column pattern of the synthetic matrix: 'window' = SURVEY 8d's primary workload to the letter (32 distinct "
                          "columns drawn without replacement from [i-4096, i+4096], stored ascending); 'stratified' = the easier-to-plan "
                          "subset of it the rounds before measured (one column per 256-wide stratum)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also the PMC traffic passes, the cold launches, the other column pattern, the "
+                         "inspectors' cost, the CPU baselines with their parity gate and BASELINE configs C3 / C4 (see --configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write y as the last timed step left it to DIR/y.npy (f32; DIR/y_sample.npy, a fixed seeded sample, above 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # rocprofv3 --pmc child pass
@@ -669,7 +695,7 @@ def main():
                     help="bare --gpus N > 1: ONE process owns all N blocks (ncclCommInitAll / peer reads) instead of the default, N child "
                          "processes of this one, one per GPU (ncclCommInitRank) -- every block's work is then issued by one host thread")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="N = 1: append BASELINE configs[2] (C3) and configs[3] (C4 SpMV, C4 CG) to the line as `configs` "
+                    help="N = 1, with --full: append BASELINE configs[2] (C3) and configs[3] (C4 SpMV, C4 CG) to the line as `configs` "
                          "(auto: when --rows is the BASELINE size)")
     ap.add_argument("--rccl-probe", action="store_true", help=argparse.SUPPRESS)  # short N > 1 run with RCCL's own log switched on (see rccl_report)
     ap.add_argument("--c3-rows", type=int, default=10_000_000, help=argparse.SUPPRESS)
@@ -696,7 +722,7 @@ def main():
     one_process = not launched and n_gpus > 1  # bare `bench.py --gpus N`: this process owns all N blocks
 
     traffic, traffic_note, calibration = None, "skipped", None
-    if n_gpus == 1 and not launched and not args.child and not args.no_traffic:
+    if args.full and n_gpus == 1 and not launched and not args.child and not args.no_traffic:
         traffic, traffic_note, calibration = pmc_traffic(args)  # before this process initialises the GPU
 
     import numpy as np
@@ -729,7 +755,7 @@ def main():
     force_par = os.environ.get("SMH_BENCH_FORCE_PAR") == "1"
     if n_gpus == 1 and not force_par:
         check(lib.smh_set_device(local_rank if launched else 0))
-        if not args.child:
+        if args.full and not args.child:
             warm_inspectors(synth, np)  # (so that prepare_ms below is the matrix's own set-up, not the process's first kernel loads)
         mat = synth.crs_fixed(synth.SEED_MATRIX, pattern, n, NNZ_PER_ROW, np.float32)
         blocks = [mat]
@@ -821,6 +847,13 @@ def main():
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.max(elapsed)
+    if args.dump_outputs and rank == 0:
+        if par is None:
+            y_out = ybuf.download(np.float32, n)
+        else:  # (the rows of this process's blocks: all of y unless it is one rank of several)
+            y_out = y.download()[par.block(0)[0]:par.block(par.n_local_blocks() - 1)[1]]
+        dump_outputs(args.dump_outputs, np, y_out)
+        del y_out
     kernel = stats(ev.times_ms())
     step_events = None
     if par is not None:
@@ -859,7 +892,7 @@ def main():
 
     # cold: the same launch after 512 MiB of stores flushed L2 and the Infinity Cache (N = 1 only)
     cold = cold_reads = None
-    if n_gpus == 1:
+    if args.full and n_gpus == 1:
         flush = synth.DeviceBuffer(FLUSH_BYTES)
         cev = Events(lib, check, 20)
         for i in range(20):
@@ -886,7 +919,7 @@ def main():
     # rides along (N = 1, plain path): the other column pattern on the same box in the same process -- the rounds before this
     # one put the headline on the stratified subset of SURVEY 8d's window matrices; both numbers stay visible
     other = None
-    if n_gpus == 1 and par is None and os.environ.get("SMH_BENCH_NO_OTHER_PATTERN") != "1":
+    if args.full and n_gpus == 1 and par is None and os.environ.get("SMH_BENCH_NO_OTHER_PATTERN") != "1":
         o_name = "stratified" if args.pattern == "window" else "window"
         o_mat = synth.crs_fixed(synth.SEED_MATRIX, synth.PATTERN_BANDED if args.pattern == "window" else synth.PATTERN_WINDOW,
                                 n, NNZ_PER_ROW, np.float32)
@@ -976,7 +1009,7 @@ def main():
         # communicators (ncclCommInitAll) live inside the library's blocks and are not asked
         result["rccl"] = rccl_report(comm, sm) if backend == "rccl" else {"note": "exchange backend '%s': no RCCL call in this run" % backend}
         result["ranks_seen"] = result["rccl"].get("ranks_seen") if comm is not None else None
-    if head_prepare is not None and not args.child:
+    if args.full and head_prepare is not None and not args.child:
         result["inspector"] = inspector_cost(mat, args.variant, xptr, n, yptr, stream, lib, check, sync, kernel_ms)
         if not args.no_cpu_baseline:  # (the plain kernels wrote y: the headline matrix's product again for the parity gate)
             spmv()
@@ -1065,7 +1098,7 @@ def main():
     # (decided identically on every rank: rank 0 runs the probe, the others wait for it on the host)
     probe_wanted = bool(n_gpus > 1 and launched and backend == "rccl" and rdzv_path and os.environ.get("SMH_BENCH_RCCL_PROBE", "0" if share else "1") == "1")
     if rank == 0:
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             if par is None:
                 x_host, y_host = xbuf.download(np.float32, n), ybuf.download(np.float32, n)
             else:  # (SMH_BENCH_FORCE_PAR: the partitioned path with one block)
@@ -1074,7 +1107,7 @@ def main():
             result["cpu_baseline"], result["cpu_baseline_all_cores"] = one, allc
         else:
             result["cpu_baseline"] = None
-        want_configs = args.configs == "on" or (args.configs == "auto" and rows == ROWS_PER_GPU)
+        want_configs = args.full and (args.configs == "on" or (args.configs == "auto" and rows == ROWS_PER_GPU))
         if n_gpus == 1 and par is None and want_configs:
             # the other single-GPU BASELINE configs, after the headline is complete; the headline's buffers go first
             del mat, blocks, xbuf, ybuf

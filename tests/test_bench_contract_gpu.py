@@ -1,12 +1,17 @@
-"""bench.py as the driver runs it, at small sizes: ONE JSON line on stdout with the contract's keys, `roofline` and `cpu_baseline`
-at N = 1; the N > 1 code path (one process, blocks sharing the device) with its exchange self-check -- which must fail when
-the exchange is skipped; and the one-process-per-GPU launch with a lone rank under torch.distributed.run."""
+"""bench.py as the driver runs it, at small sizes: ONE JSON line on stdout with the contract's keys; at N = 1 the plain line and its
+--dump-outputs, and with --full `roofline`'s extra legs, `cpu_baseline` and the other configs; the N > 1 code path (one process,
+blocks sharing the device) with its exchange self-check -- which must fail when the exchange is skipped; and the
+one-process-per-GPU launch with a lone rank under torch.distributed.run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+import oracle
+from sparsemat_amd import synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,8 +28,8 @@ def run_bench(args, env=None, launcher=None, expect_rc=0):
 
 
 def test_single_gpu_line(gpu):
-    d = run_bench(["--rows", "1000000", "--steps", "7", "--warmup", "2", "--no-traffic", "--configs", "on", "--c3-rows", "600000", "--c4-grid", "96",
-                   "--cg-iters", "20"])
+    d = run_bench(["--rows", "1000000", "--steps", "7", "--warmup", "2", "--full", "--no-traffic", "--configs", "on", "--c3-rows", "600000",
+                   "--c4-grid", "96", "--cg-iters", "20"])
     for k in CONTRACT:
         assert k in d, k
     assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"], d["scaling"], d["vs_baseline"]) == (1, 7, 2, "f32", "weak", None)
@@ -57,6 +62,28 @@ def test_single_gpu_line(gpu):
     assert c["C3"]["dtype"] == "f64" and c["C3"]["parity"]["tol"] == 1e-12 and c["C3"]["launches"] == 20 and c["C3"]["inspector"]["prepare_ms"] > 0
     assert c["C4_spmv"]["parity"]["bit_exact"] is True and c["C4_spmv"]["algorithmic_bytes"] > 0
     assert c["C4_cg"]["iterations_per_solve"] == 20 and c["C4_cg"]["algorithmic_bytes"] == c["C4_spmv"]["algorithmic_bytes"] + 9 * 96 ** 3 * 4
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_its_product(gpu, tmp_path):
+    """Without --full the N = 1 line is the timed steps and nothing else; --dump-outputs writes the y of the last timed step,
+    which is the product of the seeded inputs (the oracle generates the same matrix and x itself)."""
+    rows = 1000000
+    d = run_bench(["--rows", str(rows), "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    for k in CONTRACT:
+        assert k in d, k
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"]) == (1, 6, 2, "f32") and d["ms_per_step"] > 0
+    r = d["roofline"]
+    assert r["launches"] == 6 and r["kernel_ms"] <= d["ms_per_step"] * 1.02
+    assert r["traffic"] is None and r["cold"] is None and r["cold_after_reads"] is None and d["cpu_baseline"] is None
+    for k in ("other_pattern", "inspector", "configs", "cpu_baseline_all_cores"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["y.npy"]
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (rows,)
+    off, col, val = oracle.gen_fixed(synth.SEED_MATRIX, synth.PATTERN_WINDOW, rows, 32, np.float32)
+    x = oracle.gen_x(synth.SEED_X, rows, np.float32)
+    err = np.abs(y.astype(np.float64) - oracle.spmv(off, col, val, x)) / np.maximum(oracle.spmv_abs(off, col, val, x), 1e-300)
+    assert err.max() <= 1e-5, err.max()
 
 
 def test_n_gpus_rehearsal_checks_its_exchange(gpu):

@@ -118,3 +118,20 @@ def test_laplace3d_rows_is_the_full_generator_cut(tmp_path):
             o2, c2, v2 = oracle.laplace3d_rows(11, 7, 5, rb, re, dtype)
             lo, hi = int(off[rb]), int(off[re])
             assert np.array_equal(o2, off[rb:re + 1] - lo) and np.array_equal(c2, col[lo:hi]) and np.array_equal(v2, val[lo:hi])
+
+
+def test_dumped_outputs_are_whole_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: y whole as f32 while it fits the size limit; above it, the entries at a seeded set of rows, the same set
+    from run to run (two builds are compared output for output)."""
+    small = np.arange(1000, dtype=np.float64) / 7
+    bench.dump_outputs(str(tmp_path / "a"), np, small)
+    assert os.listdir(tmp_path / "a") == ["y.npy"]
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = np.arange(bench.DUMP_MAX_BYTES // 4 + 1, dtype=np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), np, big)
+        assert os.listdir(tmp_path / d) == ["y_sample.npy"]
+    b, c = np.load(tmp_path / "b" / "y_sample.npy"), np.load(tmp_path / "c" / "y_sample.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, c) and b.nbytes <= bench.DUMP_MAX_BYTES
+    assert len(b) > bench.DUMP_SAMPLE // 2 and np.isin(b, big).all()

@@ -22,6 +22,6 @@ run "assembly" python3 tests/bench/assemble_bench.py &&
 run "transpose, column tables" python3 tests/bench/transpose_bench.py &&
 run "prod" python3 tests/bench/prod_bench.py &&
 run "single-process SparseMatPar (blocks on one device)" python3 tests/bench/par_local_bench.py &&
-run "bench.py" python3 bench.py
+run "bench.py" python3 bench.py --full
 grep -v "amdgpu.ids" "$out" > "$out.tmp" && mv "$out.tmp" "$out"
 tail -5 "$out"
