@@ -167,6 +167,48 @@ class SparseMatCRS {
         detail::check(smh_crs_prod(h_, rhs.h_, &c.h_));
         return c;
     }
+    // #[derive(Clone)] (sparsemat_crs.rs:8): an independent library-owned copy (the copy constructor stays deleted: copies
+    // of device matrices are explicit)
+    SparseMatCRS clone() const {
+        SparseMatCRS c;
+        detail::check(smh_crs_clone(h_, &c.h_));
+        return c;
+    }
+    // SparseMatrix::add / sub (sparsematrix.rs:123-143), in place: `*get_mut(i, j) += val` (-=) for every entry of rhs in
+    // storage order -- new columns pushed to the start of their row, folds into the first occurrence, bit for bit.  rhs may
+    // be *this.  The operators of sparsemat_ops! (:370-433): +=, -=, *= T, and +, -, * T on a clone.
+    void add(const SparseMatCRS &rhs) { detail::check(smh_crs_add_assign(h_, rhs.h_)); }
+    void sub(const SparseMatCRS &rhs) { detail::check(smh_crs_sub_assign(h_, rhs.h_)); }
+    SparseMatCRS &operator+=(const SparseMatCRS &rhs) { add(rhs); return *this; }
+    SparseMatCRS &operator-=(const SparseMatCRS &rhs) { sub(rhs); return *this; }
+    SparseMatCRS &operator*=(T a) { scale(a); return *this; }
+    friend SparseMatCRS operator+(const SparseMatCRS &a, const SparseMatCRS &b) {
+        SparseMatCRS c;
+        detail::check(smh_crs_add(a.h_, b.h_, &c.h_));
+        return c;
+    }
+    friend SparseMatCRS operator-(const SparseMatCRS &a, const SparseMatCRS &b) {
+        SparseMatCRS c;
+        detail::check(smh_crs_sub(a.h_, b.h_, &c.h_));
+        return c;
+    }
+    friend SparseMatCRS operator*(const SparseMatCRS &a, T s) {
+        SparseMatCRS c = a.clone();
+        c.scale(s);
+        return c;
+    }
+    size_t orphans() const { return smh_crs_orphans(h_); }  // see smh_crs_orphans
+    // SparseMatrix::get (sparsemat_crs.rs:54-67 via find_index): the first match in the row, zero when absent.  Downloads
+    // the arrays: meant for spot checks, as in the reference's tests.
+    T get(size_t i, size_t j) const {
+        if (i >= n_rows()) return T(0);
+        std::vector<uint32_t> off, col;
+        std::vector<T> val;
+        raw_parts(off, col, val);
+        for (uint32_t k = off[i]; k < off[i + 1]; ++k)
+            if (col[k] == j) return val[k];
+        return T(0);
+    }
     bool is_symmetric() const {  // sparsematrix.rs:212-222
         int out = 0;
         detail::check(smh_crs_is_symmetric(h_, &out));

@@ -57,6 +57,13 @@ extern "C" {
     pub fn smh_last_transpose_route() -> c_int;  // 0 general (device-wide sort), 1 two bucketed passes: diagnostics only
     pub fn smh_crs_orphans(m: *const smh_crs) -> usize;
     pub fn smh_crs_prod(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
+    // #[derive(Clone)] and SparseMatrix::add / sub (src/sparsematrix.rs:123-143) with the operators of sparsemat_ops! (:370-433)
+    pub fn smh_crs_clone(a: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_add(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_sub(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_add_assign(a: *mut smh_crs, b: *const smh_crs) -> c_int;
+    pub fn smh_crs_sub_assign(a: *mut smh_crs, b: *const smh_crs) -> c_int;
+    pub fn smh_last_add_route() -> c_int;  // 0 general, 1 short rows, 2 structure unchanged, 3 same pattern: diagnostics only
     pub fn smh_crs_is_symmetric(m: *const smh_crs, out: *mut c_int) -> c_int;
     pub fn smh_crs_is_sorted(m: *const smh_crs, out: *mut c_int) -> c_int;
     pub fn smh_crs_column_info(m: *const smh_crs, rows: *mut u32, col_ptr: *mut u32, entries: *mut u32) -> c_int;

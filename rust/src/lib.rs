@@ -179,6 +179,53 @@ impl<T: HipValue> TripletStream<T> {
     }
 }
 
+/// `#[derive(Clone)]` (src/sparsemat_crs.rs:8): an independent device copy (dims, arrays, orphans, kernel settings).
+impl Clone for DeviceCrs {
+    fn clone(&self) -> Self {
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { ffi::smh_crs_clone(self.handle, &mut handle) });
+        DeviceCrs { handle, n_rows: self.n_rows }
+    }
+}
+
+impl DeviceCrs {
+    /// `SparseMatrix::add` (src/sparsematrix.rs:123-133): `*self.get_mut(i, j) += val` for every entry of `rhs` in storage
+    /// order -- new columns pushed to the start of their row, folds into the first occurrence; bit for bit.
+    pub fn add(&mut self, rhs: &DeviceCrs) {
+        check(unsafe { ffi::smh_crs_add_assign(self.handle, rhs.handle) });
+        self.n_rows = unsafe { ffi::smh_crs_n_rows(self.handle) };
+    }
+    /// `SparseMatrix::sub` (src/sparsematrix.rs:135-143).
+    pub fn sub(&mut self, rhs: &DeviceCrs) {
+        check(unsafe { ffi::smh_crs_sub_assign(self.handle, rhs.handle) });
+        self.n_rows = unsafe { ffi::smh_crs_n_rows(self.handle) };
+    }
+}
+
+// the operators of sparsemat_ops! (src/sparsematrix.rs:370-419); `+` / `-` work on a clone of self inside the library
+impl std::ops::AddAssign for DeviceCrs {
+    fn add_assign(&mut self, rhs: Self) { self.add(&rhs); }
+}
+impl std::ops::SubAssign for DeviceCrs {
+    fn sub_assign(&mut self, rhs: Self) { self.sub(&rhs); }
+}
+impl std::ops::Add for DeviceCrs {
+    type Output = Self;
+    fn add(self, rhs: Self) -> Self {
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { ffi::smh_crs_add(self.handle, rhs.handle, &mut handle) });
+        DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
+    }
+}
+impl std::ops::Sub for DeviceCrs {
+    type Output = Self;
+    fn sub(self, rhs: Self) -> Self {
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { ffi::smh_crs_sub(self.handle, rhs.handle, &mut handle) });
+        DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
+    }
+}
+
 impl Drop for DeviceCrs {
     fn drop(&mut self) {
         unsafe { ffi::smh_crs_destroy(self.handle) };

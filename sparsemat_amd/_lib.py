@@ -47,6 +47,12 @@ SIGNATURES = {
     "smh_crs_column_info": (_int, [_vp, _vp, _vp, _vp]),
     "smh_crs_column_info_dev": (_int, [_vp, _vp, _vp, _vp]),
     "smh_crs_prod": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "smh_crs_clone": (_int, [_vp, C.POINTER(_vp)]),
+    "smh_crs_add": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "smh_crs_sub": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "smh_crs_add_assign": (_int, [_vp, _vp]),
+    "smh_crs_sub_assign": (_int, [_vp, _vp]),
+    "smh_last_add_route": (_int, []),
     "smh_crs_is_symmetric": (_int, [_vp, C.POINTER(_int)]),
     "smh_crs_is_sorted": (_int, [_vp, C.POINTER(_int)]),
     "smh_crs_sort_rows": (_int, [_vp]),

@@ -1325,6 +1325,143 @@ int smh_crs_prod(const smh_crs *a, const smh_crs *b, smh_crs **out) {
     return SMH_OK;
 }
 
+// ---- #[derive(Clone)] (sparsemat_crs.rs:8) and SparseMatrix::add / sub (sparsematrix.rs:123-143, matadd.hip) ------------------
+static thread_local int g_add_route = 2;
+int smh_last_add_route(void) { return g_add_route; }
+
+// the smh_crs_set_* settings a clone (and a handle updated in place) carries
+static void copy_knobs(smh_crs *dst, const smh_crs *src) {
+    dst->forced_lanes = src->forced_lanes;
+    dst->forced_chunks = src->forced_chunks;
+    dst->stream_rows_per_thread = src->stream_rows_per_thread;
+    dst->cb_forced_shift = src->cb_forced_shift;
+    dst->use_ring = src->use_ring;
+    dst->use_stream_xs = src->use_stream_xs;
+    dst->use_stream_direct = src->use_stream_direct;
+    dst->use_stream_vdict = src->use_stream_vdict;
+    dst->use_col16 = src->use_col16;
+}
+
+// a fresh handle over device arrays (owned: freed with it, also on failure), with `like`'s settings and the create-time inspection done
+static int wrap_arrays(const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, size_t orphans, uint32_t *off, uint32_t *col, void *val,
+                       bool owns, smh_crs **out) {
+    smh_crs *m = new (std::nothrow) smh_crs();
+    if (!m) {
+        if (owns) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); }
+        return fail(SMH_ERR_OOM, "host allocation failed");
+    }
+    m->dtype = like->dtype; m->device = current_device(); m->owns = owns;
+    m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz; m->orphans = orphans;
+    m->d_off = off; m->d_col = col; m->d_val = val;
+    copy_knobs(m, like);
+    const int rc = finish_create(m, 0);
+    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
+    *out = m;
+    return SMH_OK;
+}
+
+// in place: `a` takes the fresh handle's state, and every form derived from the old one (merge tiles, K1s codes and value
+// dictionary, K1r plan, K2c / K2f / K2s / K2t copies, statistics) goes with the old state.  keep_arrays: the fresh handle
+// works on the old handle's arrays (values updated where they are), so the old state must not free them.
+static void replace_state(smh_crs *a, smh_crs *fresh, bool keep_arrays) {
+    std::swap(*a, *fresh);
+    if (keep_arrays) fresh->owns = false;
+    (void)smh_crs_destroy(fresh);
+}
+
+int smh_crs_clone(const smh_crs *a, smh_crs **out) {
+    if (!a || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    const size_t vs = dtype_size(a->dtype);
+    uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;
+    auto go = [&]() -> int {
+        SMH_HIP(hipMalloc((void **)&off, (a->n_rows + 1) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc((void **)&col, (a->nnz + 4) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc(&val, (a->nnz + 4) * vs));
+        SMH_HIP(hipMemcpy(off, a->d_off, (a->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+        if (a->nnz) {
+            SMH_HIP(hipMemcpy(col, a->d_col, a->nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            SMH_HIP(hipMemcpy(val, a->d_val, a->nnz * vs, hipMemcpyDeviceToDevice));
+        }
+        return SMH_OK;
+    };
+    const int rc = go();
+    if (rc != SMH_OK) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return rc; }
+    return wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, off, col, val, true, out);
+}
+
+// a_mut != NULL: a += b in place (a_mut == a); else *out = a.clone() + b
+static int add_common(smh_crs *a_mut, const smh_crs *a, const smh_crs *b, bool subtract, smh_crs **out) {
+    if (!a || !b || (!a_mut && !out)) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (out) *out = nullptr;
+    if (a->dtype != b->dtype) return fail(SMH_ERR_INVALID, "operands differ in value type");
+    if (a->device != b->device) return fail(SMH_ERR_INVALID, "operands live on different devices");
+    if (a->n_rows == 0 && a->orphans)
+        return fail(SMH_ERR_INVALID, "add / sub: the left operand has no rows but an orphaned entry -- the reference's hidden offset_rows "
+                                     "length decides whether it comes back to life, and the handle does not keep it");
+    SMH_HIP(hipStreamSynchronize(b->stream));  // b's reads come after whatever b's stream still has to do
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    g_add_route = 2;
+    if (b->nnz == 0) {  // nothing visited: a unchanged (b's orphan is not reached by any row)
+        if (a_mut) return SMH_OK;
+        return smh_crs_clone(a, out);
+    }
+    smh_crs *fresh = nullptr;
+    if (a->n_rows == 0) {
+        // SparseMatCRS::new() (no offset_rows): the replay of b's entries as add_to operations, first-push quirk included
+        g_add_route = 0;
+        const size_t vs = dtype_size(a->dtype);
+        uint32_t *rows = nullptr;
+        void *neg = nullptr;
+        auto go = [&]() -> int {
+            SMH_HIP(hipMalloc((void **)&rows, b->nnz * sizeof(uint32_t)));
+            SMH_TRY(expand_rows(b->d_off, b->n_rows, rows, nullptr));
+            if (subtract) {  // 0 - v == 0 + (-v) in IEEE 754, signed zeros included
+                SMH_HIP(hipMalloc(&neg, (b->nnz + 4) * vs));
+                SMH_HIP(hipMemcpy(neg, b->d_val, b->nnz * vs, hipMemcpyDeviceToDevice));
+                SMH_TRY(launch_scale_values(a->dtype, neg, b->nnz, -1.0, nullptr));
+            }
+            SMH_HIP(hipStreamSynchronize(nullptr));
+            return assemble_common((smh_dtype)a->dtype, b->nnz, rows, b->d_col, subtract ? neg : b->d_val, nullptr, true, true, &fresh);
+        };
+        const int rc = go();
+        (void)hipFree(rows);
+        (void)hipFree(neg);
+        SMH_TRY(rc);
+        if (fresh->n_cols < a->n_cols) fresh->n_cols = a->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
+        copy_knobs(fresh, a);
+        if (a_mut) replace_state(a_mut, fresh, false);
+        else *out = fresh;
+        return SMH_OK;
+    }
+    AddOperand oa, ob;
+    oa.off = a->d_off; oa.col = a->d_col; oa.val = a->d_val;
+    oa.n_rows = a->n_rows; oa.n_cols = a->n_cols; oa.nnz = a->nnz; oa.orphans = a->orphans;
+    oa.max_row_len = a->max_row_len; oa.max_col = a->max_col;
+    ob.off = b->d_off; ob.col = b->d_col; ob.val = b->d_val;
+    ob.n_rows = b->n_rows; ob.n_cols = b->n_cols; ob.nnz = b->nnz; ob.orphans = b->orphans;
+    ob.max_row_len = b->max_row_len; ob.max_col = b->max_col;
+    const bool force_general = getenv("SMH_ADD_FAST") && atoi(getenv("SMH_ADD_FAST")) == 0;
+    AddResult r;
+    SMH_TRY(add_crs(a->dtype, subtract, oa, ob, a_mut != nullptr, a == b, force_general, &r, a->stream));
+    g_add_route = r.route;
+    if (r.values_only) {  // (borrowed by the fresh handle until it has been built: a failure must not free a's arrays)
+        SMH_TRY(wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, a->d_off, a->d_col, a->d_val, false, &fresh));
+        fresh->owns = a->owns;
+    } else
+        SMH_TRY(wrap_arrays(a, r.n_rows, r.n_cols, r.nnz, a->orphans, r.off, r.col, r.val, true, &fresh));
+    if (a_mut) replace_state(a_mut, fresh, r.values_only);
+    else *out = fresh;
+    return SMH_OK;
+}
+
+int smh_crs_add(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_common(nullptr, a, b, false, out); }
+int smh_crs_sub(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_common(nullptr, a, b, true, out); }
+int smh_crs_add_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, false, nullptr); }
+int smh_crs_sub_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, true, nullptr); }
+
 int smh_crs_is_symmetric(const smh_crs *m, int *out) {
     if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
     return crs_is_symmetric(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, out, m->stream);

@@ -153,6 +153,22 @@ int crs_is_symmetric(int dtype, const uint32_t *off, const uint32_t *col, const 
 int prod_crs(int dtype, const uint32_t *a_off, const uint32_t *a_col, const void *a_val, size_t a_rows, size_t a_nnz, uint32_t a_max_col,
              const uint32_t *b_off, const uint32_t *b_col, const void *b_val, size_t b_rows, size_t *n_rows_out, size_t *n_cols_out,
              size_t *nnz_out, uint32_t **off_out, uint32_t **col_out, void **val_out, hipStream_t s);
+// SparseMatrix::add / sub (matadd.hip).  Device pointers; operands with at least one row (a) / one entry (b).
+struct AddOperand {
+    const uint32_t *off = nullptr, *col = nullptr;
+    const void *val = nullptr;
+    size_t n_rows = 0, n_cols = 0, nnz = 0, orphans = 0;
+    uint32_t max_row_len = 0, max_col = 0;
+};
+struct AddResult {
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    uint32_t *off = nullptr, *col = nullptr;  // new arrays (the caller owns them); all null when values_only
+    void *val = nullptr;
+    int route = 0;             // smh_last_add_route
+    bool values_only = false;  // in_place and no new entry: a's values were updated where they are
+};
+int add_crs(int dtype, bool subtract, const AddOperand &a, const AddOperand &b, bool in_place, bool alias, bool force_general, AddResult *res,
+            hipStream_t s);
 // K1r (LDS x-ring): inspector, host plan, kernel
 struct RingPhase {
     uint32_t row_begin, row_end;  // rows of this phase (row_begin is a multiple of 64)

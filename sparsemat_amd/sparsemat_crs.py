@@ -6,6 +6,7 @@ them to HBM once.  ``mvp`` / ``*`` run the hand-written HIP kernels.  Assembly
 (``add_to``/``set``/``get_mut``) stays with the reference's own containers -- out of scope here.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 
@@ -127,6 +128,54 @@ class SparseMatCRS:
         h = C.c_void_p()
         check(lib().smh_crs_prod(self._h, rhs._h, C.byref(h)))
         return type(self)(h, self.dtype)
+
+    def clone(self):
+        """#[derive(Clone)] (sparsemat_crs.rs:8): an independent library-owned copy (dims, arrays, orphans, kernel settings)."""
+        h = C.c_void_p()
+        check(lib().smh_crs_clone(self._h, C.byref(h)))
+        return type(self)(h, self.dtype)
+
+    def add(self, rhs):
+        """SparseMatrix::add (sparsematrix.rs:123-133), in place like the reference's ``&mut self``: ``*get_mut(i, j) += val``
+        for every entry of ``rhs`` in storage order -- new columns pushed to the start of their row, folds into the first
+        occurrence; bit for bit (``smh_crs_add_assign``).  ``rhs`` may be ``self``."""
+        check(lib().smh_crs_add_assign(self._h, rhs._h))
+
+    def sub(self, rhs):
+        """SparseMatrix::sub (sparsematrix.rs:135-143): as ``add`` with ``-=``."""
+        check(lib().smh_crs_sub_assign(self._h, rhs._h))
+
+    def __iadd__(self, rhs):  # AddAssign (sparsematrix.rs:372-378)
+        if not isinstance(rhs, SparseMatCRS):
+            return NotImplemented
+        self.add(rhs)
+        return self
+
+    def __isub__(self, rhs):  # SubAssign (:380-386)
+        if not isinstance(rhs, SparseMatCRS):
+            return NotImplemented
+        self.sub(rhs)
+        return self
+
+    def __add__(self, rhs):  # Add: self.clone() += rhs (:397-407)
+        if not isinstance(rhs, SparseMatCRS):
+            return NotImplemented
+        h = C.c_void_p()
+        check(lib().smh_crs_add(self._h, rhs._h, C.byref(h)))
+        return type(self)(h, self.dtype)
+
+    def __sub__(self, rhs):  # Sub: self.clone() -= rhs (:409-419)
+        if not isinstance(rhs, SparseMatCRS):
+            return NotImplemented
+        h = C.c_void_p()
+        check(lib().smh_crs_sub(self._h, rhs._h, C.byref(h)))
+        return type(self)(h, self.dtype)
+
+    @staticmethod
+    def last_add_route():
+        """How this thread's last add / sub was carried out (``smh_last_add_route``): "general", "short_rows",
+        "structure_unchanged" or "same_pattern"."""
+        return ("general", "short_rows", "structure_unchanged", "same_pattern")[lib().smh_last_add_route()]
 
     def is_symmetric(self):  # sparsematrix.rs:212-222
         out = C.c_int(0)
@@ -399,7 +448,18 @@ class SparseMatCRS:
         return y
 
     def __mul__(self, rhs):
+        """``A * v`` (sparsematrix.rs:435-443): mvp; ``A * s`` for a scalar s (Mul<T>, :422-432): a scaled clone."""
+        if isinstance(rhs, numbers.Real):
+            ret = self.clone()
+            ret.scale(rhs)
+            return ret
         return self.mvp(rhs)
+
+    def __imul__(self, rhs):  # MulAssign<T> (:389-395): scale in place
+        if isinstance(rhs, numbers.Real):
+            self.scale(rhs)
+            return self
+        return NotImplemented
 
     def inner_prod(self, lhs, rhs, variant="auto"):
         """SparseMatrix::inner_prod (sparsematrix.rs:161-171): lhs^T A rhs as a Python float."""
