@@ -198,16 +198,39 @@ class SparseMatCRS {
         return c;
     }
     size_t orphans() const { return smh_crs_orphans(h_); }  // see smh_crs_orphans
-    // SparseMatrix::get (sparsemat_crs.rs:54-67 via find_index): the first match in the row, zero when absent.  Downloads
-    // the arrays: meant for spot checks, as in the reference's tests.
+    // SparseMatrix::get (sparsemat_crs.rs:136-142 via find_index :54-67): the first match in the row, zero when absent
+    // (smh_crs_get: one query on the device; get_many for batches).
     T get(size_t i, size_t j) const {
-        if (i >= n_rows()) return T(0);
-        std::vector<uint32_t> off, col;
-        std::vector<T> val;
-        raw_parts(off, col, val);
-        for (uint32_t k = off[i]; k < off[i + 1]; ++k)
-            if (col[k] == j) return val[k];
-        return T(0);
+        T out = T(0);
+        detail::check(smh_crs_get(h_, i, j, &out));
+        return out;
+    }
+    std::vector<T> get_many(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols) const {
+        if (rows.size() != cols.size()) throw Panic(SMH_ERR_INVALID, "rows and cols differ in length");
+        std::vector<T> out(rows.size(), T(0));
+        detail::check(smh_crs_get_many(h_, rows.size(), rows.data(), cols.data(), out.data()));
+        return out;
+    }
+    // SparseMatrix::set / add_to (sparsematrix.rs:226-233) on this container: one device call each -- correct, but batch a
+    // stream into apply() (smh_crs_apply: ops[k] != 0 is set, an empty ops vector means all add_to)
+    void set(size_t i, size_t j, T val) { apply({index(i)}, {index(j)}, {val}, {1}); }
+    void add_to(size_t i, size_t j, T val) { apply({index(i)}, {index(j)}, {val}, {}); }
+    void apply(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, const std::vector<T> &vals,
+               const std::vector<uint8_t> &ops = {}) {
+        if (rows.size() != vals.size() || cols.size() != vals.size() || (!ops.empty() && ops.size() != vals.size()))
+            throw Panic(SMH_ERR_INVALID, "rows, cols, values and ops differ in length");
+        detail::check(smh_crs_apply(h_, vals.size(), rows.data(), cols.data(), vals.data(), ops.empty() ? nullptr : ops.data()));
+    }
+    // SparseMatCRS::new() (sparsemat_crs.rs:47-49) and SparseMatrix::eye (sparsematrix.rs:91-98)
+    static SparseMatCRS new_empty() {
+        SparseMatCRS m;
+        detail::check(smh_crs_replay(detail::dtype_of<T>::value, 0, nullptr, nullptr, nullptr, nullptr, &m.h_));
+        return m;
+    }
+    static SparseMatCRS eye(size_t dim) {
+        SparseMatCRS m;
+        detail::check(smh_crs_eye(detail::dtype_of<T>::value, dim, &m.h_));
+        return m;
     }
     bool is_symmetric() const {  // sparsematrix.rs:212-222
         int out = 0;
@@ -242,6 +265,11 @@ class SparseMatCRS {
   private:
     template <typename U> friend class SparseMatIndexList;
     SparseMatCRS() = default;
+    // a row or column index of Index = u32: larger ones are refused, never truncated
+    static uint32_t index(size_t i) {
+        if (i > 0xFFFFFFFFull) throw Panic(SMH_ERR_INVALID, "index does not fit the u32 index type");
+        return (uint32_t)i;
+    }
     smh_crs *h_ = nullptr;
 };
 

@@ -201,6 +201,53 @@ int smh_crs_sub_assign(smh_crs *a, const smh_crs *b);
  * empty b), 3 same pattern (b entry k lands on a entry k: element-wise).  Same bits on every route.  SMH_ADD_FAST=0
  * (environment) keeps every call on the general route. */
 int smh_last_add_route(void);
+/* SparseMatrix::get (sparsemat_crs.rs:136-142 via find_index :54-67): *value_out = the FIRST entry of row i whose column is
+ * j, or zero (+0) when there is none or i >= n_rows (an orphan is never reached).  value_out holds one value of the handle's
+ * dtype.  smh_crs_get_many: the same for n queries (rows[k], cols[k]) -> values_out[k], host arrays; _dev: device arrays on
+ * the handle's device (SMH_ERR_INVALID otherwise).  The _dev forms wait for all work on the device before they read the
+ * arrays and have written the results when they return, as smh_crs_assemble_dev does.  NULL arrays with n > 0:
+ * SMH_ERR_INVALID. */
+int smh_crs_get(const smh_crs *m, size_t i, size_t j, void *value_out);
+int smh_crs_get_many(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out);
+int smh_crs_get_many_dev(const smh_crs *m, size_t n, const uint32_t *rows_dev, const uint32_t *cols_dev, void *values_out_dev);
+/* A stream of set / add_to calls on an existing handle, in stream order (sparsematrix.rs:224-233): m.add_to(rows[k], cols[k],
+ * values[k]) when ops is NULL or ops[k] == 0, m.set(...) when ops[k] != 0 -- get_mut = find_index (the FIRST match in the
+ * row) or else push (inserts at the START of the row, sparsemat_crs.rs:71-92).  Bit for bit the reference's result; for a
+ * handle with rows:
+ *   - n_rows = max(m.n_rows, 1 + largest row of any operation) (an operation on a row >= m.n_rows always creates an entry);
+ *   - n_cols = max(m.n_cols, 1 + largest column that created a NEW entry);
+ *   - row i = its new columns in REVERSE order of first appearance among the stream's operations on row i, then m's row i
+ *     unchanged;
+ *   - an operation whose (row, column) exists in m's row goes to the first occurrence (later repeats in m are left alone);
+ *   - every target is the left fold of its operations in stream order, from m's value or from +0 for a new entry: add_to is
+ *     acc + v (one rounding), set is v.  So add_to(-0.0) on a new entry gives +0, set(-0.0) gives -0;
+ *   - m's orphan stays (smh_crs_orphans unchanged).
+ * A handle without rows and without an orphan (SparseMatCRS::new()): the result is smh_crs_replay of the stream, first-push
+ * quirk included, with n_cols at least m.n_cols.  A handle without rows but with one orphan -- the state the first push
+ * leaves, made by a one-operation replay / transpose / add-to-empty and smh_crs_eye(1), which keep that operation on the
+ * handle (smh_crs_clone copies it, smh_crs_scale scales its value as it scales stored values) -- continues the same way: the replay of (that operation ++ the stream).  Such a handle
+ * without the operation: SMH_ERR_INVALID, m untouched.  Entries plus orphans reaching u32::MAX: SMH_ERR_CAPACITY, decided
+ * before anything is allocated or written; n_ops == 0 leaves m untouched.  NULL arrays with n_ops > 0: SMH_ERR_INVALID.
+ * Derived forms: when every operation lands on an existing entry, the values are folded in place (a borrowed value array,
+ * smh_crs_create_dev, is written where it is and stays borrowed); every form derived from the structure stays and the
+ * value-derived ones are refreshed as smh_crs_update_values(m, NULL) does.  Otherwise the handle is rebuilt on
+ * library-owned arrays as smh_crs_add_assign rebuilds it (derived forms rebuilt on next use, smh_crs_set_* settings kept,
+ * lent arrays not written).  Every target's operations are folded by one GPU thread in stream order, so a stream piling very
+ * many operations onto one entry is folded serially.  _dev: device arrays (ops may be NULL) under smh_crs_get_many_dev's rules.  Not under a stream
+ * capture. */
+int smh_crs_apply(smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops);
+int smh_crs_apply_dev(smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev, const void *values_dev,
+                      const uint8_t *ops_dev);
+/* Diagnostics: how this thread's last smh_crs_apply[_dev] was carried out (csrc/matupdate.hip) -- 0 the general route (the
+ * operations split into those with a target and those creating entries, both sorted; the handle is rebuilt), 1 values only
+ * (every operation lands on an existing entry: sorted by target and folded in place; also n_ops == 0), 2 replay (a handle
+ * without rows).  Same bits on every route.  SMH_APPLY_FAST=0 (environment) sends every handle with rows to the general
+ * route. */
+int smh_last_apply_route(void);
+/* SparseMatrix::eye (sparsematrix.rs:91-98) on a SparseMatCRS, i.e. set(i, i, 1) for i < dim: dim 0 the empty matrix; dim 1
+ * no rows, one orphan, n_cols 1 (the first-push quirk; the operation is kept as for a one-operation replay); dim >= 2 the
+ * identity (built directly, without a sort). */
+int smh_crs_eye(smh_dtype dtype, size_t dim, smh_crs **out);
 /* is_symmetric (sparsematrix.rs:212-222: get(j, i) != val for some stored entry -> false; get takes
  * the first match in storage order) and is_sorted (:251-271): *out = 1 / 0. */
 int smh_crs_is_symmetric(const smh_crs *m, int *out);

@@ -64,6 +64,17 @@ extern "C" {
     pub fn smh_crs_add_assign(a: *mut smh_crs, b: *const smh_crs) -> c_int;
     pub fn smh_crs_sub_assign(a: *mut smh_crs, b: *const smh_crs) -> c_int;
     pub fn smh_last_add_route() -> c_int;  // 0 general, 1 short rows, 2 structure unchanged, 3 same pattern: diagnostics only
+    // SparseMatrix::get / set / add_to / eye (src/sparsematrix.rs:91-98, 224-233; src/sparsemat_crs.rs:54-92, 136-150)
+    pub fn smh_crs_get(m: *const smh_crs, i: usize, j: usize, value_out: *mut c_void) -> c_int;
+    pub fn smh_crs_get_many(m: *const smh_crs, n: usize, rows: *const u32, cols: *const u32, values_out: *mut c_void) -> c_int;
+    pub fn smh_crs_get_many_dev(m: *const smh_crs, n: usize, rows_dev: *const u32, cols_dev: *const u32,
+                                values_out_dev: *mut c_void) -> c_int;
+    pub fn smh_crs_apply(m: *mut smh_crs, n_ops: usize, rows: *const u32, cols: *const u32, values: *const c_void,
+                         ops: *const u8) -> c_int;
+    pub fn smh_crs_apply_dev(m: *mut smh_crs, n_ops: usize, rows_dev: *const u32, cols_dev: *const u32,
+                             values_dev: *const c_void, ops_dev: *const u8) -> c_int;
+    pub fn smh_last_apply_route() -> c_int;  // 0 general, 1 values only, 2 replay: diagnostics only
+    pub fn smh_crs_eye(dtype: c_int, dim: usize, out: *mut *mut smh_crs) -> c_int;
     pub fn smh_crs_is_symmetric(m: *const smh_crs, out: *mut c_int) -> c_int;
     pub fn smh_crs_is_sorted(m: *const smh_crs, out: *mut c_int) -> c_int;
     pub fn smh_crs_column_info(m: *const smh_crs, rows: *mut u32, col_ptr: *mut u32, entries: *mut u32) -> c_int;
@@ -105,6 +116,7 @@ extern "C" {
     pub fn smh_par_create_rank_split(comm: *mut smh_comm, n_rows: usize, block: *mut smh_crs, row_begin: usize, out: *mut *mut smh_par) -> c_int;
     pub fn smh_crs_n_rows(m: *const smh_crs) -> usize;
     pub fn smh_crs_n_cols(m: *const smh_crs) -> usize;
+    pub fn smh_crs_dtype(m: *const smh_crs) -> c_int;
     pub fn smh_crs_nnz(m: *const smh_crs) -> usize;
     pub fn smh_crs_download(m: *const smh_crs, offset_rows: *mut u32, columns: *mut u32, values: *mut c_void) -> c_int;
 }

@@ -202,6 +202,63 @@ impl DeviceCrs {
     }
 }
 
+/// A row or column index of `Index = u32`: larger ones are refused, never truncated.
+fn index(i: usize) -> u32 {
+    u32::try_from(i).expect("index does not fit the u32 index type")
+}
+
+impl DeviceCrs {
+    /// `SparseMatrix::eye` (src/sparsematrix.rs:91-98) on a SparseMatCRS: `set(i, i, 1)` for i < dim (dim 1 keeps the
+    /// container's first-push quirk: no rows, one orphan).
+    pub fn eye<T: HipValue>(dim: usize) -> Self {
+        check_abi();
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { ffi::smh_crs_eye(T::DTYPE, dim, &mut handle) });
+        DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
+    }
+    /// The library reads and writes values of the handle's own type: `T` must be it.
+    fn assert_dtype<T: HipValue>(&self) {
+        assert_eq!(unsafe { ffi::smh_crs_dtype(self.handle) }, T::DTYPE, "value type differs from the matrix's");
+    }
+    /// `SparseMatrix::get` (src/sparsemat_crs.rs:136-142): the first entry of row i with column j, zero when absent.
+    pub fn get<T: HipValue + Default>(&self, i: usize, j: usize) -> T {
+        self.assert_dtype::<T>();
+        let mut out = T::default();
+        check(unsafe { ffi::smh_crs_get(self.handle, i, j, &mut out as *mut T as *mut c_void) });
+        out
+    }
+    /// `get` for every (rows[k], cols[k]) at once.
+    pub fn get_many<T: HipValue + Default>(&self, rows: &[u32], cols: &[u32]) -> Vec<T> {
+        assert_eq!(rows.len(), cols.len());
+        self.assert_dtype::<T>();
+        let mut out = vec![T::default(); rows.len()];
+        check(unsafe {
+            ffi::smh_crs_get_many(self.handle, rows.len(), rows.as_ptr(), cols.as_ptr(), out.as_mut_ptr() as *mut c_void)
+        });
+        out
+    }
+    /// `add_to(rows[k], cols[k], values[k])` (`ops[k] != 0`: `set`) for every k in stream order, bit for bit; an empty
+    /// `ops` means all `add_to`.  `T` must be the handle's value type.
+    pub fn apply<T: HipValue>(&mut self, rows: &[u32], cols: &[u32], values: &[T], ops: &[u8]) {
+        assert!(rows.len() == values.len() && cols.len() == values.len() && (ops.is_empty() || ops.len() == values.len()));
+        self.assert_dtype::<T>();
+        check(unsafe {
+            ffi::smh_crs_apply(self.handle, values.len(), rows.as_ptr(), cols.as_ptr(), values.as_ptr() as *const c_void,
+                               if ops.is_empty() { std::ptr::null() } else { ops.as_ptr() })
+        });
+        self.n_rows = unsafe { ffi::smh_crs_n_rows(self.handle) };
+    }
+    /// `SparseMatrix::set` (src/sparsematrix.rs:226-228): one device call -- batch a stream into `apply`.
+    pub fn set<T: HipValue>(&mut self, i: usize, j: usize, val: T) { self.apply(&[index(i)], &[index(j)], &[val], &[1]); }
+    /// `SparseMatrix::add_to` (src/sparsematrix.rs:231-233): one device call -- batch a stream into `apply`.
+    pub fn add_to<T: HipValue>(&mut self, i: usize, j: usize, val: T) { self.apply(&[index(i)], &[index(j)], &[val], &[]); }
+    /// `SparseMatrix::sparsity` (src/sparsematrix.rs:243-246).
+    pub fn sparsity(&self) -> f64 {
+        let (nnz, n_cols) = unsafe { (ffi::smh_crs_nnz(self.handle), ffi::smh_crs_n_cols(self.handle)) };
+        1.0 - nnz as f64 / (self.n_rows * n_cols) as f64
+    }
+}
+
 // the operators of sparsemat_ops! (src/sparsematrix.rs:370-419); `+` / `-` work on a clone of self inside the library
 impl std::ops::AddAssign for DeviceCrs {
     fn add_assign(&mut self, rhs: Self) { self.add(&rhs); }

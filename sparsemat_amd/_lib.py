@@ -53,6 +53,13 @@ SIGNATURES = {
     "smh_crs_add_assign": (_int, [_vp, _vp]),
     "smh_crs_sub_assign": (_int, [_vp, _vp]),
     "smh_last_add_route": (_int, []),
+    "smh_crs_get": (_int, [_vp, _sz, _sz, _vp]),
+    "smh_crs_get_many": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "smh_crs_get_many_dev": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "smh_crs_apply": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "smh_crs_apply_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "smh_last_apply_route": (_int, []),
+    "smh_crs_eye": (_int, [_int, _sz, C.POINTER(_vp)]),
     "smh_crs_is_symmetric": (_int, [_vp, C.POINTER(_int)]),
     "smh_crs_is_sorted": (_int, [_vp, C.POINTER(_int)]),
     "smh_crs_sort_rows": (_int, [_vp]),

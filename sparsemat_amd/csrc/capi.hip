@@ -1160,7 +1160,20 @@ static int assemble_common(smh_dtype dtype, size_t n_ops, const uint32_t *rows, 
             SMH_HIP(hipMemcpy(&v0, values, vs, kind));
             if (transposing) op0 = 1;
             else if (ops) SMH_HIP(hipMemcpy(&op0, ops, 1, kind));
-            if (n_ops == 1) { m->orphans = 1; return no_rows((size_t)c01[0] + 1); }
+            if (n_ops == 1) {
+                // push(i, j, zero) then `=` or `+=` (sparsematrix.rs:226-233): kept on the handle so that smh_crs_apply can
+                // continue the replay; nothing else reads it
+                if (!op0) {
+                    if (dtype == SMH_F64) { double v; memcpy(&v, &v0, 8); v = 0.0 + v; memcpy(&v0, &v, 8); }
+                    else { float v; memcpy(&v, &v0, 4); v = 0.0f + v; memcpy(&v0, &v, 4); }
+                }
+                m->has_first_op = true;
+                m->first_row = r01[0];
+                m->first_col = c01[0];
+                memcpy(&m->first_val_bits, &v0, 8);
+                m->orphans = 1;
+                return no_rows((size_t)c01[0] + 1);
+            }
             if (r01[1] < r01[0]) { skip = 1; min_cols = (size_t)c01[0] + 1; m->orphans = 1; }
             else if (r01[1] == r01[0] && c01[1] == c01[0]) { skip = 1; twin = true; }
         }
@@ -1389,7 +1402,12 @@ int smh_crs_clone(const smh_crs *a, smh_crs **out) {
     };
     const int rc = go();
     if (rc != SMH_OK) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return rc; }
-    return wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, off, col, val, true, out);
+    SMH_TRY(wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, off, col, val, true, out));
+    (*out)->has_first_op = a->has_first_op;
+    (*out)->first_row = a->first_row;
+    (*out)->first_col = a->first_col;
+    (*out)->first_val_bits = a->first_val_bits;
+    return SMH_OK;
 }
 
 // a_mut != NULL: a += b in place (a_mut == a); else *out = a.clone() + b
@@ -1461,6 +1479,195 @@ int smh_crs_add(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_
 int smh_crs_sub(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_common(nullptr, a, b, true, out); }
 int smh_crs_add_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, false, nullptr); }
 int smh_crs_sub_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, true, nullptr); }
+
+// ---- SparseMatrix::get / set / add_to / eye (sparsematrix.rs:91-98, 224-233; sparsemat_crs.rs:54-92, 136-150; matupdate.hip) ------
+static thread_local int g_apply_route = 1;
+int smh_last_apply_route(void) { return g_apply_route; }
+
+// a device array of the caller must live on the handle's device (where the runtime can tell)
+static int check_dev_array(const void *p, int device, const char *what) {
+    if (!p) return SMH_OK;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return SMH_OK; }
+    if (a.type == hipMemoryTypeDevice && a.device != device)
+        return fail(SMH_ERR_INVALID, "%s lives on device %d, the handle on device %d", what, a.device, device);
+    return SMH_OK;
+}
+
+// device copies of host operation arrays (freed with the object)
+struct DevArrays {
+    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~DevArrays() { for (void *q : p) (void)hipFree(q); }
+    int up(int i, const void *host, size_t bytes, const void **dev) {
+        if (!host) { *dev = nullptr; return SMH_OK; }
+        SMH_HIP(hipMalloc(&p[i], bytes ? bytes : 16));
+        if (bytes) SMH_HIP(hipMemcpy(p[i], host, bytes, hipMemcpyHostToDevice));
+        *dev = p[i];
+        return SMH_OK;
+    }
+};
+
+static UpdMatrix upd_view(const smh_crs *m) {
+    UpdMatrix u;
+    u.off = m->d_off; u.col = m->d_col; u.val = m->d_val;
+    u.n_rows = m->n_rows; u.n_cols = m->n_cols; u.nnz = m->nnz; u.orphans = m->orphans;
+    u.max_row_len = m->max_row_len;
+    return u;
+}
+
+static int get_many_common(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols || !values_out)) return fail(SMH_ERR_INVALID, "NULL query array");
+    if (n == 0) return SMH_OK;
+    const size_t vs = dtype_size(m->dtype);
+    if (on_device) {
+        SMH_TRY(check_dev_array(rows, m->device, "rows"));
+        SMH_TRY(check_dev_array(cols, m->device, "cols"));
+        SMH_TRY(check_dev_array(values_out, m->device, "values_out"));
+        SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the arrays come first
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    if (m->n_rows == 0) {  // find_index needs i < n_rows (sparsemat_crs.rs:54-67): every answer is zero
+        if (on_device) SMH_HIP(hipMemset(values_out, 0, n * vs));
+        else memset(values_out, 0, n * vs);
+        return SMH_OK;
+    }
+    DevArrays st;
+    const void *d_rows = rows, *d_cols = cols;
+    void *d_out = values_out;
+    if (!on_device) {
+        SMH_TRY(st.up(0, rows, n * sizeof(uint32_t), &d_rows));
+        SMH_TRY(st.up(1, cols, n * sizeof(uint32_t), &d_cols));
+        SMH_HIP(hipMalloc(&st.p[2], n * vs));
+        d_out = st.p[2];
+    }
+    SMH_TRY(crs_get_many(m->dtype, upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_out, m->stream));
+    if (!on_device) SMH_HIP(hipMemcpy(values_out, d_out, n * vs, hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_get(const smh_crs *m, size_t i, size_t j, void *value_out) {
+    if (!m || !value_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (i >= m->n_rows || j > 0xFFFFFFFFull) {  // no row i, or a column no entry can have
+        memset(value_out, 0, dtype_size(m->dtype));
+        return SMH_OK;
+    }
+    const uint32_t r = (uint32_t)i, c = (uint32_t)j;
+    return get_many_common(m, 1, &r, &c, value_out, false);
+}
+int smh_crs_get_many(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out) {
+    return get_many_common(m, n, rows, cols, values_out, false);
+}
+int smh_crs_get_many_dev(const smh_crs *m, size_t n, const uint32_t *rows_dev, const uint32_t *cols_dev, void *values_out_dev) {
+    return get_many_common(m, n, rows_dev, cols_dev, values_out_dev, true);
+}
+
+static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols || !values)) return fail(SMH_ERR_INVALID, "NULL operation array");
+    if (n >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    if (n == 0) {  // nothing applied: m untouched
+        g_apply_route = 1;
+        return SMH_OK;
+    }
+    if (m->n_rows == 0 && m->orphans && !m->has_first_op)
+        return fail(SMH_ERR_INVALID, "apply: the handle has no rows but an orphaned entry whose operation it does not know");
+    const size_t vs = dtype_size(m->dtype);
+    if (on_device) {
+        SMH_TRY(check_dev_array(rows, m->device, "rows"));
+        SMH_TRY(check_dev_array(cols, m->device, "cols"));
+        SMH_TRY(check_dev_array(values, m->device, "values"));
+        SMH_TRY(check_dev_array(ops, m->device, "ops"));
+        SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the arrays come first
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    DevArrays st;
+    const void *d_rows = rows, *d_cols = cols, *d_vals = values, *d_ops = ops;
+    if (!on_device) {
+        SMH_TRY(st.up(0, rows, n * sizeof(uint32_t), &d_rows));
+        SMH_TRY(st.up(1, cols, n * sizeof(uint32_t), &d_cols));
+        SMH_TRY(st.up(2, values, n * vs, &d_vals));
+        SMH_TRY(st.up(3, ops, n, &d_ops));
+    }
+    smh_crs *fresh = nullptr;
+    if (m->n_rows == 0) {
+        // SparseMatCRS::new(), or the state its first push leaves (sparsemat_crs.rs:75-76): the replay of (that push ++ the stream)
+        g_apply_route = 2;
+        if (!m->has_first_op) {
+            SMH_TRY(assemble_common((smh_dtype)m->dtype, n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_vals, (const uint8_t *)d_ops, true,
+                                    true, &fresh));
+        } else {
+            DevArrays cat;
+            auto go = [&]() -> int {
+                for (int i = 0; i < 3; ++i) SMH_HIP(hipMalloc(&cat.p[i], (n + 1) * (i < 2 ? sizeof(uint32_t) : vs)));
+                SMH_HIP(hipMalloc(&cat.p[3], n + 1));
+                const uint8_t set = 1;  // the recorded value is already folded: `set` it
+                SMH_HIP(hipMemcpy(cat.p[0], &m->first_row, sizeof(uint32_t), hipMemcpyHostToDevice));
+                SMH_HIP(hipMemcpy(cat.p[1], &m->first_col, sizeof(uint32_t), hipMemcpyHostToDevice));
+                SMH_HIP(hipMemcpy(cat.p[2], &m->first_val_bits, vs, hipMemcpyHostToDevice));
+                SMH_HIP(hipMemcpy(cat.p[3], &set, 1, hipMemcpyHostToDevice));
+                SMH_HIP(hipMemcpy((uint32_t *)cat.p[0] + 1, d_rows, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+                SMH_HIP(hipMemcpy((uint32_t *)cat.p[1] + 1, d_cols, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+                SMH_HIP(hipMemcpy((char *)cat.p[2] + vs, d_vals, n * vs, hipMemcpyDeviceToDevice));
+                if (d_ops) SMH_HIP(hipMemcpy((uint8_t *)cat.p[3] + 1, d_ops, n, hipMemcpyDeviceToDevice));
+                else SMH_HIP(hipMemset((uint8_t *)cat.p[3] + 1, 0, n));
+                return assemble_common((smh_dtype)m->dtype, n + 1, (const uint32_t *)cat.p[0], (const uint32_t *)cat.p[1], cat.p[2],
+                                       (const uint8_t *)cat.p[3], true, true, &fresh);
+            };
+            SMH_TRY(go());
+        }
+        if (fresh->n_cols < m->n_cols) fresh->n_cols = m->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
+        copy_knobs(fresh, m);
+        replace_state(m, fresh, false);
+        return SMH_OK;
+    }
+    const bool force_general = getenv("SMH_APPLY_FAST") && atoi(getenv("SMH_APPLY_FAST")) == 0;
+    UpdResult r;
+    SMH_TRY(crs_apply(m->dtype, upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_vals, (const uint8_t *)d_ops, force_general, &r,
+                      m->stream));
+    g_apply_route = r.route;
+    if (r.values_only)  // structure unchanged: every form derived from it stays, the value-derived ones are refreshed
+        return smh_crs_update_values(m, nullptr);
+    SMH_TRY(wrap_arrays(m, r.n_rows, r.n_cols, r.nnz, m->orphans, r.off, r.col, r.val, true, &fresh));
+    replace_state(m, fresh, false);
+    return SMH_OK;
+}
+
+int smh_crs_apply(smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops) {
+    return apply_common(m, n_ops, rows, cols, values, ops, false);
+}
+int smh_crs_apply_dev(smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev, const void *values_dev, const uint8_t *ops_dev) {
+    return apply_common(m, n_ops, rows_dev, cols_dev, values_dev, ops_dev, true);
+}
+
+int smh_crs_eye(smh_dtype dtype, size_t dim, smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
+    *out = nullptr;
+    if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
+    if (dim >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    SMH_TRY(require_device());
+    if (dim <= 1) {  // no rows (dim 0); the first push alone: no rows, one orphan, n_cols 1 (dim 1)
+        const uint32_t zero = 0;
+        const uint8_t set = 1;
+        const double one64 = 1.0;
+        const float one32 = 1.0f;
+        return assemble_common(dtype, dim, &zero, &zero, dtype == SMH_F64 ? (const void *)&one64 : (const void *)&one32, &set, false, true, out);
+    }
+    const size_t vs = dtype_size(dtype);
+    uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;
+    auto go = [&]() -> int {
+        SMH_HIP(hipMalloc((void **)&off, (dim + 1) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc((void **)&col, (dim + 4) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc(&val, (dim + 4) * vs));
+        return build_eye(dtype, dim, off, col, val, nullptr);
+    };
+    const int rc = go();
+    if (rc != SMH_OK) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return rc; }
+    smh_crs like;  // default settings
+    like.dtype = dtype;
+    return wrap_arrays(&like, dim, dim, dim, 0, off, col, val, true, out);
+}
 
 int smh_crs_is_symmetric(const smh_crs *m, int *out) {
     if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
@@ -1547,6 +1754,22 @@ int smh_crs_col_range(const smh_crs *m, uint32_t *min_out, uint32_t *max_out) {
 int smh_crs_scale(smh_crs *m, double a) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(launch_scale_values(m->dtype, m->d_val, m->nnz, a, m->stream));
+    if (m->has_first_op) {
+        // the reference scales every stored value (sparsemat_crs.rs:153-157), the orphaned first push included, and smh_crs_apply
+        // brings that value back: scale the kept copy by the same kernel, so that it rounds exactly as a stored value does
+        void *d = nullptr;
+        SMH_HIP(hipMalloc(&d, 16));
+        auto go = [&]() -> int {
+            SMH_HIP(hipMemcpyAsync(d, &m->first_val_bits, 8, hipMemcpyHostToDevice, m->stream));
+            SMH_TRY(launch_scale_values(m->dtype, d, 1, a, m->stream));
+            SMH_HIP(hipMemcpyAsync(&m->first_val_bits, d, 8, hipMemcpyDeviceToHost, m->stream));
+            SMH_HIP(hipStreamSynchronize(m->stream));
+            return SMH_OK;
+        };
+        const int rc = go();
+        (void)hipFree(d);
+        SMH_TRY(rc);
+    }
     // (K1s XD-V: every entry is its dictionary value times a, rounded as the entry itself is: the indices in the codes stay right)
     if (m->d_stream_dict && m->stream_dict_state == 1) SMH_TRY(launch_scale_values(m->dtype, m->d_stream_dict, 32, a, m->stream));
     if (m->cb_built) SMH_TRY(launch_scale_values(m->dtype, m->d_cb_val, m->nnz, a, m->stream));

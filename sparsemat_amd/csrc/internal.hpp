@@ -169,6 +169,24 @@ struct AddResult {
 };
 int add_crs(int dtype, bool subtract, const AddOperand &a, const AddOperand &b, bool in_place, bool alias, bool force_general, AddResult *res,
             hipStream_t s);
+// SparseMatrix::get / set / add_to in batches (matupdate.hip).  Device pointers; m with at least one row.
+struct UpdMatrix {
+    const uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;  // written in place by the values-only route
+    size_t n_rows = 0, n_cols = 0, nnz = 0, orphans = 0;
+    uint32_t max_row_len = 0;
+};
+struct UpdResult {
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    uint32_t *off = nullptr, *col = nullptr;  // new arrays (the caller owns them); all null when values_only
+    void *val = nullptr;
+    int route = 0;             // smh_last_apply_route
+    bool values_only = false;  // no new entry: m's values were updated where they are
+};
+int crs_get_many(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out, hipStream_t s);
+int crs_apply(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
+              bool force_general, UpdResult *res, hipStream_t s);
+int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hipStream_t s);
 // K1r (LDS x-ring): inspector, host plan, kernel
 struct RingPhase {
     uint32_t row_begin, row_end;  // rows of this phase (row_begin is a multiple of 64)
@@ -236,6 +254,11 @@ struct smh_crs {
     int device = 0;
     size_t n_rows = 0, n_cols = 0, nnz = 0;
     size_t orphans = 0;  // entries the reference's container still holds but no row reaches (first-push quirk of a replay): 0 or 1
+    // the single operation of a handle without rows but with its orphan (the one-operation replay, smh_crs_eye(1)): row, column
+    // and folded value (f32 / f64 bits), so that smh_crs_apply can continue the replay as the reference does
+    bool has_first_op = false;
+    uint32_t first_row = 0, first_col = 0;
+    uint64_t first_val_bits = 0;
     uint32_t *d_off = nullptr;
     uint32_t *d_col = nullptr;
     void *d_val = nullptr;

@@ -1,0 +1,483 @@
+// matupdate.hip -- element access of a SparseMatCRS on the device, gfx950: a batched SparseMatrix::get (sparsemat_crs.rs:136-142)
+// and a batched stream of `set` / `add_to` calls (sparsematrix.rs:224-233) on an existing handle.
+//
+// What it replaces.  `m.add_to(i, j, v)` is `*m.get_mut(i, j) += v`, `m.set(i, j, v)` is `*m.get_mut(i, j) = v`; get_mut is
+// find_index (the FIRST match in row i, sparsemat_crs.rs:54-67) or else push, which inserts at the START of the row (:71-92).  On
+// the host that is a row scan per call plus a Vec::insert per new entry.  For a handle with rows the result of a whole stream is
+// fixed in closed form (tests/update_model.py restates it):
+//   * row i = its new columns in REVERSE order of first appearance among the stream's operations on row i, then m's row i;
+//   * an operation whose (row, column) exists in m's row goes to the first occurrence; a new (row, column) is one new entry;
+//   * every target's value is the left fold of its operations in stream order, from m's value or from +0 for a new entry
+//     (add_to: acc + v, one rounding; set: v);
+//   * n_rows = max(m.n_rows, 1 + largest row of any operation), n_cols = max(m.n_cols, 1 + largest column of a new entry).
+// Device formulation (integer structure and values bit for bit, no float atomics: the fold order is the contract):
+//   1. lookup: every operation's target in m -- the first match in its row, or absent (rows past the end are absent without a
+//      load).  Rows are unsorted and may repeat columns, so this is a scan of the row: one thread per operation for rows of at
+//      most kUpdShortRow entries, else a lane group per operation whose ballot names the first hit;
+//   2. VALUES ONLY (every operation lands on an existing entry -- the re-assembly of a fixed pattern): a stable radix sort of the
+//      operations by target (rocPRIM; the value and the op ride as payload), then one thread per run of equal targets folds it
+//      in stream order from the stored value and writes the value back in place.  Structure and everything derived from it stay;
+//   3. GENERAL (some operation creates an entry; SMH_APPLY_FAST=0 sends every stream here): the operations are split stably into
+//      present and absent ones; the present ones are sorted by target as in 2., the absent ones by (row, column) -- a run is one
+//      new entry, its head the first appearance.  The heads, sorted by (row, first appearance), give the per-row counts; the
+//      device scan turns them into offsets (and decides the capacity error before the result arrays are allocated); m's
+//      entries move behind their row's new ones, new entries are written reversed, and every run is folded by one thread.
+// The batched get is step 1 with the stored value (or +0) as its output.
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "internal.hpp"
+
+namespace smh {
+
+int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
+
+constexpr uint32_t kUpdShortRow = 64;      // longest row of m the one-thread-per-operation lookup takes
+constexpr uint32_t kAbsent = 0xFFFFFFFFu;  // lookup: no entry of the row has the column
+
+static unsigned upd_grid(uint64_t n) {
+    uint64_t b = (n + kBlock - 1) / kBlock;
+    if (b > 16384) b = 16384;
+    return (unsigned)(b ? b : 1);
+}
+
+static unsigned upd_bits_for(uint64_t v) {
+    unsigned b = 1;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
+
+struct UpdInfo {
+    uint32_t n_absent;     // operations without a target in m
+    uint32_t max_row;      // largest row of any operation
+    uint32_t max_new_col;  // largest column of an absent operation (valid when n_absent > 0)
+    uint32_t pad;
+};
+
+__device__ __forceinline__ uint32_t upd_wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t w = (uint32_t)__shfl_xor((int)v, o, kWave);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t upd_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
+    return v;
+}
+
+template <typename T> __device__ __forceinline__ T upd_add(T a, T b) {  // one rounding, never contracted
+    if constexpr (sizeof(T) == 4) return __fadd_rn(a, b);
+    else return __dadd_rn(a, b);
+}
+
+// ---- 1. lookup -------------------------------------------------------------------------------------------------------------
+// G lanes per query (a power of two dividing the wavefront); the group walks the row G entries at a time and stops at the first
+// chunk holding a hit, whose lowest hit lane is the first match.  VALUES: val_out[q] = stored value or +0 (get); otherwise
+// idx_out[q] = entry index or kAbsent, and the info words (apply).
+template <int G, typename T, bool VALUES>
+__global__ void __launch_bounds__(kBlock)
+k_upd_lookup(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val, uint64_t n_rows,
+             const uint32_t *__restrict__ q_row, const uint32_t *__restrict__ q_col, uint64_t n, uint32_t *__restrict__ idx_out,
+             T *__restrict__ val_out, UpdInfo *info) {
+    const uint32_t lane = threadIdx.x & (G - 1);
+    const uint32_t wbase = (threadIdx.x & (kWave - 1)) & ~(uint32_t)(G - 1);
+    const uint64_t gmask = G == 64 ? ~0ull : ((1ull << G) - 1);
+    const uint64_t stride = (uint64_t)gridDim.x * (blockDim.x / G);
+    uint32_t n_absent = 0, max_row = 0, max_new_col = 0;
+    for (uint64_t q = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G; q < n; q += stride) {
+        const uint32_t i = q_row[q], c = q_col[q];
+        uint32_t found = kAbsent;
+        if (i < n_rows) {
+            const uint32_t a0 = off[i], a1 = off[i + 1];
+            for (uint32_t base = a0; base < a1; base += G) {
+                const uint32_t p = base + lane;
+                const bool hit = p < a1 && col[p] == c;
+                if constexpr (G == 1) {
+                    if (hit) { found = p; break; }
+                } else {
+                    const uint64_t m = ((uint64_t)__ballot(hit) >> wbase) & gmask;  // the same in every lane of the group
+                    if (m) { found = base + (uint32_t)__builtin_ctzll(m); break; }
+                }
+            }
+        }
+        if (lane == 0) {
+            if constexpr (VALUES) {
+                val_out[q] = found == kAbsent ? T(0) : val[found];
+            } else {
+                idx_out[q] = found;
+                max_row = i > max_row ? i : max_row;
+                if (found == kAbsent) {
+                    ++n_absent;
+                    max_new_col = c > max_new_col ? c : max_new_col;
+                }
+            }
+        }
+    }
+    if constexpr (!VALUES) {
+        n_absent = upd_wave_sum(n_absent);
+        max_row = upd_wave_max(max_row);
+        max_new_col = upd_wave_max(max_new_col);
+        if ((threadIdx.x & (kWave - 1)) == 0) {
+            if (n_absent) atomicAdd(&info->n_absent, n_absent);
+            atomicMax(&info->max_row, max_row);
+            atomicMax(&info->max_new_col, max_new_col);
+        }
+    }
+}
+
+template <typename T, bool VALUES>
+static int launch_lookup(uint32_t max_row_len, const uint32_t *off, const uint32_t *col, const T *val, uint64_t n_rows, const uint32_t *q_row,
+                         const uint32_t *q_col, uint64_t n, uint32_t *idx_out, T *val_out, UpdInfo *info, hipStream_t s) {
+    // lane groups sized from the longest row (as K1 sizes its sub-wave groups): one thread per query on short rows
+    const int g = max_row_len <= kUpdShortRow ? 1 : max_row_len <= 512 ? 8 : 32;
+    const unsigned grid = upd_grid(n * (uint64_t)g);
+    if (g == 1)
+        hipLaunchKernelGGL((k_upd_lookup<1, T, VALUES>), dim3(grid), dim3(kBlock), 0, s, off, col, val, n_rows, q_row, q_col, n, idx_out, val_out, info);
+    else if (g == 8)
+        hipLaunchKernelGGL((k_upd_lookup<8, T, VALUES>), dim3(grid), dim3(kBlock), 0, s, off, col, val, n_rows, q_row, q_col, n, idx_out, val_out, info);
+    else
+        hipLaunchKernelGGL((k_upd_lookup<32, T, VALUES>), dim3(grid), dim3(kBlock), 0, s, off, col, val, n_rows, q_row, q_col, n, idx_out, val_out, info);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
+// ---- 2. / 3. folds and structure -------------------------------------------------------------------------------------------
+// an operation as the payload of the sort by target: its value and whether it is a `set` (8 bytes f32, 16 bytes f64), so that
+// the fold reads the sorted runs in order instead of gathering by stream position
+template <typename T> struct UpdOp {
+    T v;
+    uint32_t set;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_upd_payload(const T *__restrict__ vals, const uint8_t *__restrict__ ops, uint64_t n, UpdOp<T> *__restrict__ pay) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+        UpdOp<T> o;
+        o.v = vals[k];
+        o.set = ops && ops[k] ? 1u : 0u;
+        pay[k] = o;
+    }
+}
+
+// one thread per run of equal targets (key sorted stably: the run is in stream order) folds it from src_val[t] and writes
+// dst_val[newpos ? newpos[t] : t].  src_val may be dst_val (in place: each run reads and writes its own entry only).  A run is
+// folded serially: a stream piling n operations onto one entry costs one thread n steps.
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_upd_fold(const uint32_t *__restrict__ key, const UpdOp<T> *__restrict__ pay, uint64_t n, const T *src_val, T *dst_val,
+           const uint32_t *__restrict__ newpos) {
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t t = key[q];
+        if (q > 0 && key[q - 1] == t) continue;  // folded by its run's head
+        T acc = src_val[t];
+        for (uint64_t q2 = q; q2 < n && key[q2] == t; ++q2) {
+            const UpdOp<T> o = pay[q2];
+            acc = o.set ? o.v : upd_add(acc, o.v);
+        }
+        dst_val[newpos ? newpos[t] : t] = acc;
+    }
+}
+
+// flag[k] = 1 for an operation without a target (the caller scans the flags: pos = absent operations before k)
+__global__ void __launch_bounds__(kBlock)
+k_upd_absent_flags(const uint32_t *__restrict__ tgt, uint64_t n, uint32_t *__restrict__ flag) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x)
+        flag[k] = tgt[k] == kAbsent ? 1u : 0u;
+}
+
+// stable split: present operations -> (target, value and op), absent ones -> ((row << cbits) | column, k)
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_upd_split(const uint32_t *__restrict__ tgt, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ cols, const T *__restrict__ vals,
+            const uint8_t *__restrict__ ops, uint64_t n, const uint32_t *__restrict__ pos, unsigned cbits, uint32_t *__restrict__ pkey,
+            UpdOp<T> *__restrict__ ppay, uint64_t *__restrict__ akey, uint32_t *__restrict__ asrc) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t a = pos[k];
+        if (pos[k + 1] != a) {
+            akey[a] = ((uint64_t)rows[k] << cbits) | cols[k];
+            asrc[a] = (uint32_t)k;
+        } else {
+            const uint64_t p = k - a;
+            pkey[p] = tgt[k];
+            UpdOp<T> o;
+            o.v = vals[k];
+            o.set = ops && ops[k] ? 1u : 0u;
+            ppay[p] = o;
+        }
+    }
+}
+
+// flag[q] = 1 at the head of a run of equal (row, column) among the sorted absent operations: one new entry each
+__global__ void __launch_bounds__(kBlock)
+k_upd_head_flags(const uint64_t *__restrict__ akey, uint64_t n, uint32_t *__restrict__ flag) {
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (uint64_t)gridDim.x * blockDim.x)
+        flag[q] = (q == 0 || akey[q - 1] != akey[q]) ? 1u : 0u;
+}
+
+// new entry h (= hpos[q] of its head q) -> key (row << kbits) | first stream position, payload q
+__global__ void __launch_bounds__(kBlock)
+k_upd_heads(const uint64_t *__restrict__ akey, const uint32_t *__restrict__ asrc, uint64_t n, const uint32_t *__restrict__ hpos, unsigned cbits,
+            unsigned kbits, uint64_t *__restrict__ hkey, uint32_t *__restrict__ hsrc) {
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t h = hpos[q];
+        if (hpos[q + 1] == h) continue;
+        hkey[h] = ((akey[q] >> cbits) << kbits) | asrc[q];  // stable sort: the head holds the smallest stream position
+        hsrc[h] = (uint32_t)q;
+    }
+}
+
+// cnt[row] = new entries of the row (the heads sorted by (row, first appearance): a row's new entries are contiguous)
+__global__ void __launch_bounds__(kBlock)
+k_upd_count_rows(const uint64_t *__restrict__ hkey, uint64_t n_new, unsigned kbits, uint32_t *__restrict__ cnt) {
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_new; p += (uint64_t)gridDim.x * blockDim.x)
+        atomicAdd(&cnt[hkey[p] >> kbits], 1u);  // integer counts: exact whatever the order
+}
+
+// r_off[i] = m's offset + new entries before row i, i <= n_rows (rows past m's end start at m's nnz)
+__global__ void __launch_bounds__(kBlock)
+k_upd_offsets(const uint32_t *__restrict__ m_off, uint64_t m_rows, const uint32_t *__restrict__ nb, uint64_t n_rows, uint32_t *__restrict__ r_off) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_rows; i += (uint64_t)gridDim.x * blockDim.x)
+        r_off[i] = m_off[i < m_rows ? i : m_rows] + nb[i];
+}
+
+// m's entries behind their row's new ones; rows_newpos[p] (the row of entry p on entry) becomes p's place in the result
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_upd_move_old(const uint32_t *__restrict__ m_off, const uint32_t *__restrict__ m_col, const T *__restrict__ m_val, uint64_t nnz,
+               const uint32_t *__restrict__ nb, const uint32_t *__restrict__ r_off, uint32_t *__restrict__ rows_newpos, uint32_t *__restrict__ r_col,
+               T *__restrict__ r_val) {
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = rows_newpos[p];
+        const uint32_t dst = r_off[i] + (nb[i + 1] - nb[i]) + ((uint32_t)p - m_off[i]);
+        r_col[dst] = m_col[p];
+        r_val[dst] = m_val[p];
+        rows_newpos[p] = dst;
+    }
+}
+
+// new entry p (row-major, by first appearance inside the row): written reversed (push prepends), its run folded from +0
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_upd_emit_new(const uint64_t *__restrict__ hkey, const uint32_t *__restrict__ hsrc, uint64_t n_new, unsigned kbits, const uint64_t *__restrict__ akey,
+               const uint32_t *__restrict__ asrc, uint64_t n_absent, uint64_t cmask, const T *__restrict__ vals, const uint8_t *__restrict__ ops,
+               const uint32_t *__restrict__ nb, const uint32_t *__restrict__ r_off, uint32_t *__restrict__ r_col, T *__restrict__ r_val) {
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_new; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)(hkey[p] >> kbits);
+        const uint32_t n_row = nb[i + 1] - nb[i];
+        const uint32_t rank = (uint32_t)p - nb[i];
+        const uint32_t dst = r_off[i] + n_row - 1 - rank;
+        const uint64_t q = hsrc[p], key = akey[q];
+        T acc = T(0);
+        for (uint64_t q2 = q; q2 < n_absent && akey[q2] == key; ++q2) {
+            const uint32_t k = asrc[q2];
+            const T v = vals[k];
+            acc = (ops && ops[k]) ? v : upd_add(acc, v);
+        }
+        r_col[dst] = (uint32_t)(key & cmask);
+        r_val[dst] = acc;
+    }
+}
+
+// ---- driver ----------------------------------------------------------------------------------------------------------------
+struct UpdScratch {
+    void *p[20] = {};
+    int n = 0;
+    template <typename U> int alloc(U **out, size_t count) {
+        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
+        p[n++] = *out;
+        return SMH_OK;
+    }
+    ~UpdScratch() { for (int i = 0; i < n; ++i) (void)hipFree(p[i]); }
+};
+
+#define SMH_UPD_ROCPRIM(call_with_tmp)                                 \
+    do {                                                               \
+        size_t bytes = 0;                                              \
+        void *tmp = nullptr;                                           \
+        SMH_HIP(call_with_tmp);                                        \
+        SMH_HIP(hipMalloc(&tmp, bytes ? bytes : 16));                  \
+        const hipError_t e1 = (call_with_tmp);                         \
+        const hipError_t e2 = hipStreamSynchronize(s);                 \
+        (void)hipFree(tmp);                                            \
+        SMH_HIP(e1);                                                   \
+        SMH_HIP(e2);                                                   \
+    } while (0)
+
+// stable sort of (target, operation) pairs by target, bits [0, bits)
+template <typename P>
+static int sort_by_target(uint32_t *key_in, uint32_t *key_out, P *src_in, P *src_out, uint64_t n, unsigned bits, hipStream_t s) {
+    if (n == 0) return SMH_OK;
+    SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, key_in, key_out, src_in, src_out, (size_t)n, 0u, bits, s));
+    return SMH_OK;
+}
+
+template <typename T>
+static int get_many_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const uint32_t *cols, T *out, hipStream_t s) {
+    return launch_lookup<T, true>(m.max_row_len, m.off, m.col, (const T *)m.val, m.n_rows, rows, cols, n, nullptr, out, nullptr, s);
+}
+
+int crs_get_many(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out, hipStream_t s) {
+    if (n == 0) return SMH_OK;
+    if (dtype == SMH_F64) SMH_TRY(get_many_t<double>(m, n, rows, cols, (double *)values_out, s));
+    else SMH_TRY(get_many_t<float>(m, n, rows, cols, (float *)values_out, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    return SMH_OK;
+}
+
+template <typename T>
+static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const uint32_t *cols, const T *vals, const uint8_t *ops, bool force_general,
+                   UpdResult *res, hipStream_t s) {
+    UpdScratch scr;
+    UpdInfo *d_info = nullptr, h_info;
+    uint32_t *tgt = nullptr;
+    SMH_TRY(scr.alloc(&d_info, 1));
+    SMH_TRY(scr.alloc(&tgt, n));
+    SMH_HIP(hipMemsetAsync(d_info, 0, sizeof(UpdInfo), s));
+    SMH_TRY((launch_lookup<T, false>(m.max_row_len, m.off, m.col, (const T *)m.val, m.n_rows, rows, cols, n, tgt, nullptr, d_info, s)));
+    SMH_HIP(hipMemcpyAsync(&h_info, d_info, sizeof h_info, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    const uint64_t n_rows = (uint64_t)h_info.max_row + 1 > m.n_rows ? (uint64_t)h_info.max_row + 1 : m.n_rows;
+    if (n_rows >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "n_rows does not fit the u32 index type");
+    const unsigned tbits = upd_bits_for(m.nnz);
+    if (h_info.n_absent == 0 && !force_general) {
+        // 2. values only: sort by target, fold in place
+        res->route = 1;
+        res->values_only = true;
+        uint32_t *key = nullptr;
+        UpdOp<T> *src_in = nullptr, *src = nullptr;
+        SMH_TRY(scr.alloc(&key, n));
+        SMH_TRY(scr.alloc(&src_in, n));
+        SMH_TRY(scr.alloc(&src, n));
+        hipLaunchKernelGGL((k_upd_payload<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, vals, ops, n, src_in);
+        SMH_HIP(hipGetLastError());
+        SMH_TRY(sort_by_target(tgt, key, src_in, src, n, tbits, s));
+        hipLaunchKernelGGL((k_upd_fold<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, key, (const UpdOp<T> *)src, n, (const T *)m.val, (T *)m.val,
+                           (const uint32_t *)nullptr);
+        SMH_HIP(hipGetLastError());
+        SMH_HIP(hipStreamSynchronize(s));
+        return SMH_OK;
+    }
+    // 3. general
+    res->route = 0;
+    const uint64_t n_absent = h_info.n_absent, n_present = n - n_absent;
+    uint32_t *pos = nullptr, *pkey_in = nullptr, *pkey = nullptr, *asrc_in = nullptr, *asrc = nullptr;
+    UpdOp<T> *psrc_in = nullptr, *psrc = nullptr;
+    uint64_t *akey_in = nullptr, *akey = nullptr;
+    SMH_TRY(scr.alloc(&pos, n + 1));
+    hipLaunchKernelGGL(k_upd_absent_flags, dim3(upd_grid(n)), dim3(kBlock), 0, s, tgt, n, pos);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemsetAsync(pos + n, 0, sizeof(uint32_t), s));
+    uint64_t total = 0;
+    SMH_TRY(device_exclusive_scan_u32(pos, n + 1, s, &total));
+    SMH_TRY(scr.alloc(&pkey_in, n_present));
+    SMH_TRY(scr.alloc(&psrc_in, n_present));
+    SMH_TRY(scr.alloc(&pkey, n_present));
+    SMH_TRY(scr.alloc(&psrc, n_present));
+    SMH_TRY(scr.alloc(&akey_in, n_absent));
+    SMH_TRY(scr.alloc(&asrc_in, n_absent));
+    SMH_TRY(scr.alloc(&akey, n_absent));
+    SMH_TRY(scr.alloc(&asrc, n_absent));
+    const unsigned cbits = upd_bits_for(h_info.max_new_col), rbits = upd_bits_for(h_info.max_row), kbits = upd_bits_for(n);
+    hipLaunchKernelGGL((k_upd_split<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, tgt, rows, cols, vals, ops, n, pos, cbits, pkey_in, psrc_in, akey_in,
+                       asrc_in);
+    SMH_HIP(hipGetLastError());
+    SMH_TRY(sort_by_target(pkey_in, pkey, psrc_in, psrc, n_present, tbits, s));
+    if (n_absent)
+        SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, akey_in, akey, asrc_in, asrc, (size_t)n_absent, 0u, rbits + cbits, s));
+    // new entries: heads of the (row, column) runs, sorted by (row, first appearance)
+    uint32_t *hpos = nullptr, *hsrc_in = nullptr, *hsrc = nullptr, *nb = nullptr;
+    uint64_t *hkey_in = nullptr, *hkey = nullptr, n_new = 0;
+    SMH_TRY(scr.alloc(&hpos, n_absent + 1));
+    SMH_TRY(scr.alloc(&nb, n_rows + 1));
+    SMH_HIP(hipMemsetAsync(nb, 0, (n_rows + 1) * sizeof(uint32_t), s));
+    if (n_absent) {
+        hipLaunchKernelGGL(k_upd_head_flags, dim3(upd_grid(n_absent)), dim3(kBlock), 0, s, akey, n_absent, hpos);
+        SMH_HIP(hipGetLastError());
+        SMH_HIP(hipMemsetAsync(hpos + n_absent, 0, sizeof(uint32_t), s));
+        SMH_TRY(device_exclusive_scan_u32(hpos, n_absent + 1, s, &n_new));
+        SMH_TRY(scr.alloc(&hkey_in, n_new));
+        SMH_TRY(scr.alloc(&hkey, n_new));
+        SMH_TRY(scr.alloc(&hsrc_in, n_new));
+        SMH_TRY(scr.alloc(&hsrc, n_new));
+        hipLaunchKernelGGL(k_upd_heads, dim3(upd_grid(n_absent)), dim3(kBlock), 0, s, akey, asrc, n_absent, hpos, cbits, kbits, hkey_in, hsrc_in);
+        SMH_HIP(hipGetLastError());
+        SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, hkey_in, hkey, hsrc_in, hsrc, (size_t)n_new, 0u, rbits + kbits, s));
+        hipLaunchKernelGGL(k_upd_count_rows, dim3(upd_grid(n_new)), dim3(kBlock), 0, s, hkey, n_new, kbits, nb);
+        SMH_HIP(hipGetLastError());
+    }
+    uint64_t n_new2 = 0;
+    SMH_TRY(device_exclusive_scan_u32(nb, n_rows + 1, s, &n_new2));
+    if (n_new2 != n_new) return fail(SMH_ERR_HIP, "apply: new-entry counts disagree (%llu vs %llu)", (unsigned long long)n_new2, (unsigned long long)n_new);
+    // capacity: entries plus orphans below u32::MAX (sparsemat_crs.rs:82-84), decided before the result is allocated or written
+    const uint64_t nnz = (uint64_t)m.nnz + n_new;
+    if (nnz + m.orphans >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    res->n_rows = n_rows;
+    const uint64_t new_cols = n_new ? (uint64_t)h_info.max_new_col + 1 : 0;
+    res->n_cols = m.n_cols > new_cols ? m.n_cols : new_cols;
+    res->nnz = nnz;
+    uint32_t *rows_newpos = nullptr;
+    SMH_TRY(scr.alloc(&rows_newpos, m.nnz));
+    SMH_TRY(expand_rows(m.off, m.n_rows, rows_newpos, s));
+    uint32_t *r_off = nullptr, *r_col = nullptr;
+    T *r_val = nullptr;
+    auto alloc_out = [&]() -> int {
+        SMH_HIP(hipMalloc((void **)&r_off, (n_rows + 1) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc((void **)&r_col, (nnz + 4) * sizeof(uint32_t)));
+        SMH_HIP(hipMalloc((void **)&r_val, (nnz + 4) * sizeof(T)));
+        return SMH_OK;
+    };
+    const int rc = alloc_out();
+    if (rc != SMH_OK) { (void)hipFree(r_off); (void)hipFree(r_col); (void)hipFree(r_val); return rc; }
+    res->off = r_off; res->col = r_col; res->val = r_val;  // owned by the caller from here on
+    hipLaunchKernelGGL(k_upd_offsets, dim3(upd_grid(n_rows + 1)), dim3(kBlock), 0, s, m.off, (uint64_t)m.n_rows, nb, n_rows, r_off);
+    SMH_HIP(hipGetLastError());
+    if (m.nnz) {
+        hipLaunchKernelGGL((k_upd_move_old<T>), dim3(upd_grid(m.nnz)), dim3(kBlock), 0, s, m.off, m.col, (const T *)m.val, (uint64_t)m.nnz, nb, r_off,
+                           rows_newpos, r_col, r_val);
+        SMH_HIP(hipGetLastError());
+    }
+    if (n_new) {
+        hipLaunchKernelGGL((k_upd_emit_new<T>), dim3(upd_grid(n_new)), dim3(kBlock), 0, s, hkey, hsrc, n_new, kbits, akey, asrc, n_absent,
+                           (cbits >= 64 ? ~0ull : ((1ull << cbits) - 1)), vals, ops, nb, r_off, r_col, r_val);
+        SMH_HIP(hipGetLastError());
+    }
+    if (n_present) {
+        hipLaunchKernelGGL((k_upd_fold<T>), dim3(upd_grid(n_present)), dim3(kBlock), 0, s, pkey, (const UpdOp<T> *)psrc, n_present, (const T *)m.val, r_val,
+                           (const uint32_t *)rows_newpos);
+        SMH_HIP(hipGetLastError());
+    }
+    SMH_HIP(hipStreamSynchronize(s));
+    return SMH_OK;
+}
+
+int crs_apply(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
+              bool force_general, UpdResult *res, hipStream_t s) {
+    *res = UpdResult();
+    if (dtype == SMH_F64) return apply_t<double>(m, n, rows, cols, (const double *)vals, ops, force_general, res, s);
+    return apply_t<float>(m, n, rows, cols, (const float *)vals, ops, force_general, res, s);
+}
+
+// SparseMatrix::eye (sparsematrix.rs:91-98) for dim >= 2: offsets 0..dim, columns 0..dim-1, ones
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_upd_eye(uint32_t *__restrict__ off, uint32_t *__restrict__ col, T *__restrict__ val, uint64_t dim) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= dim; i += (uint64_t)gridDim.x * blockDim.x) {
+        off[i] = (uint32_t)i;
+        if (i < dim) {
+            col[i] = (uint32_t)i;
+            val[i] = T(1);
+        }
+    }
+}
+
+int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hipStream_t s) {
+    if (dtype == SMH_F64) hipLaunchKernelGGL((k_upd_eye<double>), dim3(upd_grid(dim + 1)), dim3(kBlock), 0, s, off, col, (double *)val, (uint64_t)dim);
+    else hipLaunchKernelGGL((k_upd_eye<float>), dim3(upd_grid(dim + 1)), dim3(kBlock), 0, s, off, col, (float *)val, (uint64_t)dim);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
+    return SMH_OK;
+}
+
+}  // namespace smh

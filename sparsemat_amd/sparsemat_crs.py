@@ -2,8 +2,10 @@
 the SpMV hot path, backed by a device-resident ``smh_crs``.
 
 The host owns the CRS arrays (``offset_rows``, ``columns``, ``values``); ``from_raw_parts`` copies
-them to HBM once.  ``mvp`` / ``*`` run the hand-written HIP kernels.  Assembly
-(``add_to``/``set``/``get_mut``) stays with the reference's own containers -- out of scope here.
+them to HBM once.  ``mvp`` / ``*`` run the hand-written HIP kernels.  Element access runs on the device too:
+``get`` / ``get_many`` (SparseMatrix::get) and ``set`` / ``add_to`` / ``apply`` (a whole stream of set / add_to calls at
+once, bit for bit the reference's get_mut placement and folds, see ``smh_crs_apply`` in the header).  One call per
+operation is correct but slow: batch the stream into one ``apply``.
 """
 import ctypes as C
 import numbers
@@ -13,6 +15,14 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .densevec import DenseVec
+
+
+def _index(i):
+    """A row or column index of Index = u32: larger (or negative) ones are refused, never truncated."""
+    i = int(i)
+    if not 0 <= i <= 0xFFFFFFFF:
+        raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "index %d does not fit the u32 index type" % i)
+    return i
 
 
 class SparseMatCRS:
@@ -86,6 +96,21 @@ class SparseMatCRS:
         fn = lib().smh_crs_replay_dev if into_crs else lib().smh_crs_assemble_dev
         check(fn(_lib.dtype_code(dtype), n_ops, C.c_void_p(rows_ptr), C.c_void_p(cols_ptr), C.c_void_p(vals_ptr),
                  C.c_void_p(ops_ptr or 0), C.byref(h)))
+        return cls(h, dtype)
+
+    @classmethod
+    def new(cls, dtype=np.float32):
+        """SparseMatCRS::new() (sparsemat_crs.rs:47-49): no rows, no entries."""
+        h = C.c_void_p()
+        check(lib().smh_crs_replay(_lib.dtype_code(np.dtype(dtype)), 0, None, None, None, None, C.byref(h)))
+        return cls(h, dtype)
+
+    @classmethod
+    def eye(cls, dim, dtype=np.float32):
+        """SparseMatrix::eye (sparsematrix.rs:91-98) on a SparseMatCRS: ``set(i, i, 1)`` for i < dim.  dim 1 keeps the
+        container's first-push quirk (no rows, one orphan); dim >= 2 is the identity."""
+        h = C.c_void_p()
+        check(lib().smh_crs_eye(_lib.dtype_code(np.dtype(dtype)), int(dim), C.byref(h)))
         return cls(h, dtype)
 
     def transpose(self):
@@ -177,6 +202,67 @@ class SparseMatCRS:
         "structure_unchanged" or "same_pattern"."""
         return ("general", "short_rows", "structure_unchanged", "same_pattern")[lib().smh_last_add_route()]
 
+    # ---- element access (sparsematrix.rs:224-233, sparsemat_crs.rs:54-92, 136-150) ----------------
+    def get(self, i, j):
+        """SparseMatrix::get: the first entry of row i with column j, zero when absent or i >= n_rows."""
+        out = np.zeros(1, self._dtype)
+        check(lib().smh_crs_get(self._h, int(i), int(j), out.ctypes.data))
+        return out[0]
+
+    def get_many(self, rows, cols):
+        """``get`` for every (rows[k], cols[k]) at once -> numpy array of the value type."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        if len(rows) != len(cols):
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "rows and cols differ in length")
+        n = len(rows)
+        out = np.zeros(n, self._dtype)
+        check(lib().smh_crs_get_many(self._h, n, rows.ctypes.data if n else None, cols.ctypes.data if n else None,
+                                     out.ctypes.data if n else None))
+        return out
+
+    def get_many_dev(self, n, rows_ptr, cols_ptr, out_ptr):
+        """``get_many`` on raw device pointers (u32 rows / cols, values of the handle's dtype)."""
+        check(lib().smh_crs_get_many_dev(self._h, int(n), C.c_void_p(rows_ptr), C.c_void_p(cols_ptr), C.c_void_p(out_ptr)))
+
+    def apply(self, rows, cols, values, ops=None):
+        """``add_to(rows[k], cols[k], values[k])`` (``ops[k] == 1``: ``set``) for every k in stream order, in place, bit for
+        bit (``smh_crs_apply``).  Re-assembly into the handle's own pattern updates the values where they are.  A float array
+        of the other value type is refused (no silent rounding)."""
+        values = np.asarray(values)
+        if values.dtype.kind == "f" and values.dtype != self._dtype:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "values are %s, the matrix holds %s" % (values.dtype, self._dtype))
+        values = np.ascontiguousarray(values, dtype=self._dtype)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        n = len(values)
+        if len(rows) != n or len(cols) != n:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "rows, cols and values differ in length")
+        ops_a = None if ops is None else np.ascontiguousarray(ops, dtype=np.uint8)
+        if ops_a is not None and len(ops_a) != n:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "ops and values differ in length")
+        check(lib().smh_crs_apply(self._h, n, rows.ctypes.data if n else None, cols.ctypes.data if n else None,
+                                  values.ctypes.data if n else None, ops_a.ctypes.data if (ops_a is not None and n) else None))
+
+    def apply_dev(self, n_ops, rows_ptr, cols_ptr, vals_ptr, ops_ptr=None):
+        """``apply`` over operation arrays that already live in HBM (raw device pointers; ``ops_ptr`` may be None)."""
+        check(lib().smh_crs_apply_dev(self._h, int(n_ops), C.c_void_p(rows_ptr), C.c_void_p(cols_ptr), C.c_void_p(vals_ptr),
+                                      C.c_void_p(ops_ptr or 0)))
+
+    def set(self, i, j, value):
+        """SparseMatrix::set (sparsematrix.rs:226-228): one ``apply`` -- correct, but a device round trip per call."""
+        self.apply([_index(i)], [_index(j)], np.array([value], self._dtype), [1])
+
+    def add_to(self, i, j, value):
+        """SparseMatrix::add_to (sparsematrix.rs:231-233): one ``apply`` -- correct, but a device round trip per call."""
+        self.apply([_index(i)], [_index(j)], np.array([value], self._dtype))
+
+    @staticmethod
+    def last_apply_route():
+        """How this thread's last ``apply`` was carried out (``smh_last_apply_route``): "general", "values_only" or
+        "replay"."""
+        return ("general", "values_only", "replay")[lib().smh_last_apply_route()]
+
     def is_symmetric(self):  # sparsematrix.rs:212-222
         out = C.c_int(0)
         check(lib().smh_crs_is_symmetric(self._h, C.byref(out)))
@@ -224,6 +310,9 @@ class SparseMatCRS:
 
     def density(self):  # sparsematrix.rs:237-241
         return self.n_non_zero_entries() / (self.n_rows() * self.n_cols())
+
+    def sparsity(self):  # sparsematrix.rs:243-246
+        return 1.0 - self.density()
 
     def raw_parts(self):
         off = np.empty(self.n_rows() + 1, dtype=np.uint32)
