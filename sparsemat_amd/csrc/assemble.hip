@@ -42,14 +42,6 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
-static unsigned grid_for(uint64_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > 16384) b = 16384;
-    return (unsigned)(b ? b : 1);
-}
-
 // sort key (row), payload (column << 32 | stream position) + the matrix dimensions (integer max: exact)
 __global__ void __launch_bounds__(kBlock)
 k_asm_keys(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ cols, uint64_t n, uint32_t *__restrict__ row_key,
@@ -367,38 +359,6 @@ k_asm_emit_val(const uint32_t *__restrict__ row_s, const uint32_t *__restrict__ 
     }
 }
 
-static unsigned bits_for(uint64_t v) {  // bits needed to hold v
-    unsigned b = 1;
-    while (b < 64 && (v >> b)) ++b;
-    return b;
-}
-
-// rocPRIM calls: query the temporary storage, allocate, run, synchronise, free
-#define SMH_ROCPRIM(call_with_tmp)                                     \
-    do {                                                               \
-        size_t bytes = 0;                                              \
-        void *tmp = nullptr;                                           \
-        SMH_HIP(call_with_tmp);                                        \
-        SMH_HIP(hipMalloc(&tmp, bytes ? bytes : 16));                  \
-        const hipError_t e1 = (call_with_tmp);                         \
-        const hipError_t e2 = hipStreamSynchronize(s);                 \
-        (void)hipFree(tmp);                                            \
-        SMH_HIP(e1);                                                   \
-        SMH_HIP(e2);                                                   \
-    } while (0)
-
-// device buffers freed on scope exit
-struct Scratch {
-    void *p[20] = {};
-    int n = 0;
-    template <typename U> int alloc(U **out, size_t count) {
-        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
-        p[n++] = *out;
-        return SMH_OK;
-    }
-    ~Scratch() { for (int i = 0; i < n; ++i) (void)hipFree(p[i]); }
-};
-
 template <typename T>
 static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, const T *vals, const uint8_t *ops, bool reverse,
                       bool all_set, bool repeats_adjacent,
@@ -416,6 +376,14 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
     };
     if (all_set) ops = nullptr;  // every operation is `set`: no array to consult
     static const bool allow_value_payload = !(getenv("SMH_ASSEMBLE_VALUE_PAYLOAD") && atoi(getenv("SMH_ASSEMBLE_VALUE_PAYLOAD")) == 0);
+    // the result (padded like smh_crs_create's) goes to the caller when every step succeeded
+    CrsArrays res;
+    uint64_t nnz = n;
+    auto hand_over = [&](uint64_t n_rows, uint64_t n_cols) {
+        *n_rows_out = (size_t)n_rows; *n_cols_out = (size_t)n_cols; *nnz_out = (size_t)nnz;
+        res.release(off_out, col_out, val_out);
+        return SMH_OK;
+    };
     if (all_set && repeats_adjacent && allow_value_payload && n > 0) {
         // Transposition-shaped streams: sort (row) -> (column, value) and emit -- unless two neighbours turn out to name
         // the same (row, column), in which case the general route below starts over with stream positions.
@@ -428,49 +396,34 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
         SMH_TRY(bufs.alloc(&row_s, n));
         SMH_TRY(bufs.alloc(&pay, n));
         SMH_TRY(bufs.alloc(&pay_s, n));
-        hipLaunchKernelGGL((k_asm_keys_val<T>), dim3(grid_for(n) < 4096u ? grid_for(n) : 4096u), dim3(kBlock), 0, s, rows, cols, vals, n, row_key,
-                           pay, dims);
+        hipLaunchKernelGGL((k_asm_keys_val<T>), dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, rows, cols, vals, n, row_key, pay, dims);
         SMH_HIP(hipGetLastError());
         uint32_t h_dims[2];
         SMH_HIP(hipMemcpyAsync(h_dims, dims, sizeof h_dims, hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         lap("keys (value payload)");
         const uint64_t n_rows = (uint64_t)h_dims[0] + 1, n_cols = (uint64_t)h_dims[1] + 1;
-        SMH_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, row_key, row_s, pay, pay_s, (size_t)n, 0u, bits_for(h_dims[0]), s));
+        SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, row_key, row_s, pay, pay_s, (size_t)n, 0u, bits_for(h_dims[0]), s));
         lap("sort by row (value payload)");
         SMH_TRY(bufs.alloc(&seg, n_rows + 1));
-        hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, n, n_rows, seg);
+        hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, n, n_rows, seg);
         uint32_t repeats = 0;
         SMH_HIP(hipMemsetAsync(dims, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL((k_asm_adjacent_repeats_val<T>), dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, pay_s, n, dims);
+        hipLaunchKernelGGL((k_asm_adjacent_repeats_val<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, pay_s, n, dims);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemcpyAsync(&repeats, dims, sizeof repeats, hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         lap("segments, repeats");
         if (!repeats) {
-            uint32_t *off = nullptr, *col = nullptr;
-            T *val = nullptr;
-            auto go = [&]() -> int {
-                SMH_HIP(hipMalloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
-                SMH_HIP(hipMalloc((void **)&col, (n + 4) * sizeof(uint32_t)));
-                SMH_HIP(hipMalloc((void **)&val, (n + 4) * sizeof(T)));
-                SMH_HIP(hipMemcpyAsync(off, seg, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                SMH_HIP(hipMemsetAsync(col + n, 0, 4 * sizeof(uint32_t), s));
-                SMH_HIP(hipMemsetAsync(val + n, 0, 4 * sizeof(T), s));
-                hipLaunchKernelGGL((k_asm_emit_val<T>), dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, seg, pay_s, n, reverse, col, val);
-                SMH_HIP(hipGetLastError());
-                SMH_HIP(hipStreamSynchronize(s));
-                lap("emit (value payload)");
-                return SMH_OK;
-            };
-            const int rc = go();
-            if (rc != SMH_OK) {
-                (void)hipFree(off); (void)hipFree(col); (void)hipFree(val);
-                return rc;
-            }
-            *n_rows_out = (size_t)n_rows; *n_cols_out = (size_t)n_cols; *nnz_out = (size_t)n;
-            *off_out = off; *col_out = col; *val_out = val;
-            return SMH_OK;
+            SMH_TRY(res.alloc(n_rows, n, sizeof(T)));
+            SMH_HIP(hipMemcpyAsync(res.off, seg, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            SMH_TRY(res.zero_padding(n, sizeof(T), s));
+            hipLaunchKernelGGL((k_asm_emit_val<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, seg, pay_s, n, reverse, res.col,
+                               (T *)res.val);
+            SMH_HIP(hipGetLastError());
+            SMH_HIP(hipStreamSynchronize(s));
+            lap("emit (value payload)");
+            return hand_over(n_rows, n_cols);
         }
     }
     Scratch tmp_bufs;
@@ -483,7 +436,7 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
     SMH_TRY(tmp_bufs.alloc(&row_key, n));
     SMH_TRY(tmp_bufs.alloc(&cp, n));
     lap("scratch allocation");
-    hipLaunchKernelGGL(k_asm_keys, dim3(grid_for(n) < 4096u ? grid_for(n) : 4096u), dim3(kBlock), 0, s, rows, cols, n, row_key, cp, dims);
+    hipLaunchKernelGGL(k_asm_keys, dim3(grid_for(n, 4096)), dim3(kBlock), 0, s, rows, cols, n, row_key, cp, dims);
     SMH_HIP(hipGetLastError());
     lap("keys");
     uint32_t h_dims[3];
@@ -500,12 +453,12 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
     } else {
         SMH_TRY(tmp_bufs.alloc(&row_s, n));
         SMH_TRY(tmp_bufs.alloc(&cp_s, n));
-        SMH_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, row_key, row_s, cp, cp_s, (size_t)n, 0u, bits_for(h_dims[0]), s));
+        SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, row_key, row_s, cp, cp_s, (size_t)n, 0u, bits_for(h_dims[0]), s));
         lap("sort by row");
     }
     // 2. inside every row by (column, stream position); output back into `cp`
     SMH_TRY(tmp_bufs.alloc(&seg, n_rows + 1));
-    hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, n, n_rows, seg);
+    hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, n, n_rows, seg);
     SMH_HIP(hipGetLastError());
     // longest row (in operations) decides the route
     uint32_t max_ops = 0;
@@ -517,36 +470,21 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
     if (repeats_adjacent && allow_direct) {
         uint32_t repeats = 0;
         SMH_HIP(hipMemsetAsync(dims, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_asm_adjacent_repeats, dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, cp_s, n, dims);
+        hipLaunchKernelGGL(k_asm_adjacent_repeats, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, cp_s, n, dims);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemcpyAsync(&repeats, dims, sizeof repeats, hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         lap("segments, longest row, repeats");
         if (!repeats) {  // every operation is an entry: offsets = segments, entries = the sorted operations
-            uint32_t *off = nullptr, *col = nullptr;
-            T *val = nullptr;
-            auto go = [&]() -> int {
-                SMH_HIP(hipMalloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
-                SMH_HIP(hipMalloc((void **)&col, (n + 4) * sizeof(uint32_t)));
-                SMH_HIP(hipMalloc((void **)&val, (n + 4) * sizeof(T)));
-                SMH_HIP(hipMemcpyAsync(off, seg, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                SMH_HIP(hipMemsetAsync(col + n, 0, 4 * sizeof(uint32_t), s));
-                SMH_HIP(hipMemsetAsync(val + n, 0, 4 * sizeof(T), s));
-                hipLaunchKernelGGL((k_asm_direct_emit<T>), dim3(grid_for(n_rows)), dim3(kBlock), 0, s, seg, cp_s, vals, ops, all_set, n_rows,
-                                   reverse, col, val);
-                SMH_HIP(hipGetLastError());
-                SMH_HIP(hipStreamSynchronize(s));
-                lap("direct emit");
-                return SMH_OK;
-            };
-            const int rc = go();
-            if (rc != SMH_OK) {
-                (void)hipFree(off); (void)hipFree(col); (void)hipFree(val);
-                return rc;
-            }
-            *n_rows_out = (size_t)n_rows; *n_cols_out = (size_t)n_cols; *nnz_out = (size_t)n;
-            *off_out = off; *col_out = col; *val_out = val;
-            return SMH_OK;
+            SMH_TRY(res.alloc(n_rows, n, sizeof(T)));
+            SMH_HIP(hipMemcpyAsync(res.off, seg, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            SMH_TRY(res.zero_padding(n, sizeof(T), s));
+            hipLaunchKernelGGL((k_asm_direct_emit<T>), dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, seg, cp_s, vals, ops, all_set, n_rows,
+                               reverse, res.col, (T *)res.val);
+            SMH_HIP(hipGetLastError());
+            SMH_HIP(hipStreamSynchronize(s));
+            lap("direct emit");
+            return hand_over(n_rows, n_cols);
         }
     }
     if (allow_rowwise && max_ops <= kRowwiseMaxOps) {
@@ -554,89 +492,58 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
         uint32_t *lcol = row_key;  // dead after the sort
         T *lval = nullptr;
         SMH_TRY(tmp_bufs.alloc(&lval, n));
-        uint32_t *off = nullptr, *col = nullptr;
-        T *val = nullptr;
-        uint64_t n_entries = 0;
         lap("segments, longest row");
-        auto go = [&]() -> int {
-            SMH_HIP(hipMalloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
-            hipLaunchKernelGGL((k_asm_rowwise<T>), dim3((unsigned)((n_rows + kRowBlock - 1) / kRowBlock)), dim3(kRowBlock), 0, s, seg, cp_s,
-                               vals, ops, all_set, n_rows, lcol, lval, off);
-            SMH_HIP(hipGetLastError());
-            lap("row replay");
-            SMH_TRY(device_exclusive_scan_u32(off, n_rows + 1, s, &n_entries));  // counts -> CRS offsets
-            SMH_HIP(hipMalloc((void **)&col, (n_entries + 4) * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc((void **)&val, (n_entries + 4) * sizeof(T)));
-            SMH_HIP(hipMemsetAsync(col + n_entries, 0, 4 * sizeof(uint32_t), s));
-            SMH_HIP(hipMemsetAsync(val + n_entries, 0, 4 * sizeof(T), s));
-            lap("offsets, result allocation");
-            hipLaunchKernelGGL((k_asm_row_emit<T>), dim3(grid_for(n_rows)), dim3(kBlock), 0, s, seg, off, lcol, lval, n_rows, reverse, col, val);
-            SMH_HIP(hipGetLastError());
-            SMH_HIP(hipStreamSynchronize(s));
-            lap("emit");
-            return SMH_OK;
-        };
-        const int rc = go();
-        if (rc != SMH_OK) {
-            (void)hipFree(off); (void)hipFree(col); (void)hipFree(val);
-            return rc;
-        }
-        *n_rows_out = (size_t)n_rows; *n_cols_out = (size_t)n_cols; *nnz_out = (size_t)n_entries;
-        *off_out = off; *col_out = col; *val_out = val;
-        return SMH_OK;
+        SMH_TRY(res.alloc_off(n_rows));
+        hipLaunchKernelGGL((k_asm_rowwise<T>), dim3((unsigned)((n_rows + kRowBlock - 1) / kRowBlock)), dim3(kRowBlock), 0, s, seg, cp_s,
+                           vals, ops, all_set, n_rows, lcol, lval, res.off);
+        SMH_HIP(hipGetLastError());
+        lap("row replay");
+        SMH_TRY(device_exclusive_scan_u32(res.off, n_rows + 1, s, &nnz));  // counts -> CRS offsets
+        SMH_TRY(res.alloc_entries(nnz, sizeof(T)));
+        SMH_TRY(res.zero_padding(nnz, sizeof(T), s));
+        lap("offsets, result allocation");
+        hipLaunchKernelGGL((k_asm_row_emit<T>), dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, seg, res.off, lcol, lval, n_rows, reverse,
+                           res.col, (T *)res.val);
+        SMH_HIP(hipGetLastError());
+        SMH_HIP(hipStreamSynchronize(s));
+        lap("emit");
+        return hand_over(n_rows, n_cols);
     }
     // long rows: segmented sorts (rocPRIM takes long segments in several passes)
     uint64_t *runs_buf = cp;
     if (cp_s == cp) SMH_TRY(tmp_bufs.alloc(&runs_buf, n));  // (presorted stream: cp is the sort's input, not a free buffer)
-    SMH_ROCPRIM(rocprim::segmented_radix_sort_keys(tmp, bytes, cp_s, runs_buf, (unsigned)n, (unsigned)n_rows, seg, seg + 1, 0u,
-                                                   32u + bits_for(h_dims[1]), s));
+    SMH_ROCPRIM(s, rocprim::segmented_radix_sort_keys(tmp, bytes, cp_s, runs_buf, (unsigned)n, (unsigned)n_rows, seg, seg + 1, 0u,
+                                                      32u + bits_for(h_dims[1]), s));
     const uint64_t *runs = runs_buf;  // (row_s[k], runs[k]) ascending in (row, column, stream position)
     // 3. runs -> entries
     SMH_TRY(tmp_bufs.alloc(&head, n));
     SMH_TRY(tmp_bufs.alloc(&vals_s, n));
     if (ops) SMH_TRY(tmp_bufs.alloc(&ops_s, n));
-    hipLaunchKernelGGL((k_asm_heads<T>), dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, runs, vals, ops, n, vals_s, ops_s, head);
+    hipLaunchKernelGGL((k_asm_heads<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, runs, vals, ops, n, vals_s, ops_s, head);
     SMH_HIP(hipGetLastError());
-    uint64_t n_entries = 0;
-    SMH_TRY(device_exclusive_scan_u32(head, n, s, &n_entries));
+    SMH_TRY(device_exclusive_scan_u32(head, n, s, &nnz));
     uint32_t *first_pos = nullptr, *first_pos_s = nullptr, *uidx = nullptr, *uidx_s = nullptr, *ucol = nullptr;
     T *uval = nullptr;
-    SMH_TRY(tmp_bufs.alloc(&first_pos, n_entries));
-    SMH_TRY(tmp_bufs.alloc(&first_pos_s, n_entries));
-    SMH_TRY(tmp_bufs.alloc(&uidx, n_entries));
-    SMH_TRY(tmp_bufs.alloc(&uidx_s, n_entries));
-    SMH_TRY(tmp_bufs.alloc(&ucol, n_entries));
-    SMH_TRY(tmp_bufs.alloc(&uval, n_entries));
-    hipLaunchKernelGGL((k_asm_fold<T>), dim3(grid_for(n)), dim3(kBlock), 0, s, row_s, runs, vals_s, ops_s, head, n, reverse, all_set, first_pos,
-                       uidx, ucol, uval);
+    SMH_TRY(tmp_bufs.alloc(&first_pos, nnz));
+    SMH_TRY(tmp_bufs.alloc(&first_pos_s, nnz));
+    SMH_TRY(tmp_bufs.alloc(&uidx, nnz));
+    SMH_TRY(tmp_bufs.alloc(&uidx_s, nnz));
+    SMH_TRY(tmp_bufs.alloc(&ucol, nnz));
+    SMH_TRY(tmp_bufs.alloc(&uval, nnz));
+    hipLaunchKernelGGL((k_asm_fold<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, row_s, runs, vals_s, ops_s, head, n, reverse, all_set,
+                       first_pos, uidx, ucol, uval);
     SMH_HIP(hipGetLastError());
-    // result arrays (owned by the caller; padded like smh_crs_create's)
-    uint32_t *off = nullptr, *col = nullptr;
-    T *val = nullptr;
-    auto finish = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&col, (n_entries + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&val, (n_entries + 4) * sizeof(T)));
-        SMH_HIP(hipMemsetAsync(col + n_entries, 0, 4 * sizeof(uint32_t), s));
-        SMH_HIP(hipMemsetAsync(val + n_entries, 0, 4 * sizeof(T), s));
-        hipLaunchKernelGGL(k_asm_offsets, dim3(grid_for(n_rows + 1)), dim3(kBlock), 0, s, seg, head, n, n_rows, (uint32_t)n_entries, off);
-        SMH_HIP(hipGetLastError());
-        // 4. first-appearance order inside every row
-        SMH_ROCPRIM(rocprim::segmented_radix_sort_pairs(tmp, bytes, first_pos, first_pos_s, uidx, uidx_s, (unsigned)n_entries,
-                                                        (unsigned)n_rows, off, off + 1, 0u, bits_for(n - 1), s));
-        hipLaunchKernelGGL((k_asm_emit<T>), dim3(grid_for(n_entries)), dim3(kBlock), 0, s, uidx_s, ucol, uval, n_entries, col, val);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = finish();
-    if (rc != SMH_OK) {
-        (void)hipFree(off); (void)hipFree(col); (void)hipFree(val);
-        return rc;
-    }
-    *n_rows_out = (size_t)n_rows; *n_cols_out = (size_t)n_cols; *nnz_out = (size_t)n_entries;
-    *off_out = off; *col_out = col; *val_out = val;
-    return SMH_OK;
+    SMH_TRY(res.alloc(n_rows, nnz, sizeof(T)));
+    SMH_TRY(res.zero_padding(nnz, sizeof(T), s));
+    hipLaunchKernelGGL(k_asm_offsets, dim3(grid_for(n_rows + 1, kBuildGrid)), dim3(kBlock), 0, s, seg, head, n, n_rows, (uint32_t)nnz, res.off);
+    SMH_HIP(hipGetLastError());
+    // 4. first-appearance order inside every row
+    SMH_ROCPRIM(s, rocprim::segmented_radix_sort_pairs(tmp, bytes, first_pos, first_pos_s, uidx, uidx_s, (unsigned)nnz, (unsigned)n_rows, res.off,
+                                                       res.off + 1, 0u, bits_for(n - 1), s));
+    hipLaunchKernelGGL((k_asm_emit<T>), dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, uidx_s, ucol, uval, nnz, res.col, (T *)res.val);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
+    return hand_over(n_rows, n_cols);
 }
 
 // rows/cols/vals/ops: DEVICE arrays of n operations (ops may be null: all add_to).  n >= 1.
@@ -679,16 +586,16 @@ int sort_rows(int dtype, const uint32_t *off, uint32_t *col, void *val, size_t n
     SMH_TRY(tmp_bufs.alloc(&idx, nnz));
     SMH_TRY(tmp_bufs.alloc(&idx_s, nnz));
     SMH_TRY(tmp_bufs.alloc(&val_s, nnz * vs));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz)), dim3(kBlock), 0, s, idx, (uint64_t)nnz);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, idx, (uint64_t)nnz);
     SMH_HIP(hipGetLastError());
     // the CRS offsets are the segments; stable, so duplicates of a column keep their storage order
-    SMH_ROCPRIM(rocprim::segmented_radix_sort_pairs(tmp, bytes, col, col_s, idx, idx_s, (unsigned)nnz, (unsigned)n_rows, off, off + 1,
-                                                    0u, bits_for(max_col), s));
+    SMH_ROCPRIM(s, rocprim::segmented_radix_sort_pairs(tmp, bytes, col, col_s, idx, idx_s, (unsigned)nnz, (unsigned)n_rows, off, off + 1,
+                                                       0u, bits_for(max_col), s));
     if (dtype == SMH_F64)
-        hipLaunchKernelGGL((k_sortrows_gather<double>), dim3(grid_for(nnz)), dim3(kBlock), 0, s, idx_s, (const double *)val,
+        hipLaunchKernelGGL((k_sortrows_gather<double>), dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, idx_s, (const double *)val,
                            (uint64_t)nnz, (double *)val_s);
     else
-        hipLaunchKernelGGL((k_sortrows_gather<float>), dim3(grid_for(nnz)), dim3(kBlock), 0, s, idx_s, (const float *)val,
+        hipLaunchKernelGGL((k_sortrows_gather<float>), dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, idx_s, (const float *)val,
                            (uint64_t)nnz, (float *)val_s);
     SMH_HIP(hipGetLastError());
     SMH_HIP(hipMemcpyAsync(col, col_s, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
@@ -725,7 +632,7 @@ k_expand_rows(const uint32_t *__restrict__ off, uint64_t n_rows, uint32_t *__res
 
 int expand_rows(const uint32_t *off, size_t n_rows, uint32_t *rows_out, hipStream_t s) {
     if (n_rows == 0) return SMH_OK;
-    hipLaunchKernelGGL(k_expand_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, s, off, (uint64_t)n_rows, rows_out);
+    hipLaunchKernelGGL(k_expand_rows, dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, off, (uint64_t)n_rows, rows_out);
     SMH_HIP(hipGetLastError());
     return SMH_OK;
 }
@@ -744,32 +651,28 @@ int append_to_row(int dtype, uint32_t *off, uint32_t **col, void **val, size_t n
     uint32_t p = 0;
     SMH_HIP(hipMemcpyAsync(&p, off + row + 1, sizeof p, hipMemcpyDeviceToHost, s));
     SMH_HIP(hipStreamSynchronize(s));
+    Scratch fresh;
     uint32_t *ncol = nullptr;
     char *nval = nullptr;
-    SMH_HIP(hipMalloc((void **)&ncol, (n + 1 + 4) * sizeof(uint32_t)));
-    if (hipMalloc((void **)&nval, (n + 1 + 4) * vs) != hipSuccess) { (void)hipFree(ncol); return fail(SMH_ERR_OOM, "hipMalloc failed"); }
-    auto go = [&]() -> int {
-        SMH_HIP(hipMemsetAsync(ncol + n + 1, 0, 4 * sizeof(uint32_t), s));
-        SMH_HIP(hipMemsetAsync(nval + (n + 1) * vs, 0, 4 * vs, s));
-        if (p) {
-            SMH_HIP(hipMemcpyAsync(ncol, *col, (size_t)p * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            SMH_HIP(hipMemcpyAsync(nval, *val, (size_t)p * vs, hipMemcpyDeviceToDevice, s));
-        }
-        SMH_HIP(hipMemcpyAsync(ncol + p, &column, sizeof column, hipMemcpyHostToDevice, s));
-        SMH_HIP(hipMemcpyAsync(nval + (size_t)p * vs, value_host, vs, hipMemcpyHostToDevice, s));
-        if (n > p) {
-            SMH_HIP(hipMemcpyAsync(ncol + p + 1, *col + p, (n - p) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            SMH_HIP(hipMemcpyAsync(nval + ((size_t)p + 1) * vs, (const char *)*val + (size_t)p * vs, (n - p) * vs, hipMemcpyDeviceToDevice, s));
-        }
-        hipLaunchKernelGGL(k_bump_offsets, dim3(grid_for(n_rows - row)), dim3(kBlock), 0, s, off, (uint64_t)row + 1, (uint64_t)n_rows);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = go();
-    if (rc != SMH_OK) { (void)hipFree(ncol); (void)hipFree(nval); return rc; }
+    SMH_TRY(fresh.alloc(&ncol, n + 1 + 4));
+    SMH_TRY(fresh.alloc(&nval, (n + 1 + 4) * vs));
+    SMH_HIP(hipMemsetAsync(ncol + n + 1, 0, 4 * sizeof(uint32_t), s));
+    SMH_HIP(hipMemsetAsync(nval + (n + 1) * vs, 0, 4 * vs, s));
+    if (p) {
+        SMH_HIP(hipMemcpyAsync(ncol, *col, (size_t)p * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        SMH_HIP(hipMemcpyAsync(nval, *val, (size_t)p * vs, hipMemcpyDeviceToDevice, s));
+    }
+    SMH_HIP(hipMemcpyAsync(ncol + p, &column, sizeof column, hipMemcpyHostToDevice, s));
+    SMH_HIP(hipMemcpyAsync(nval + (size_t)p * vs, value_host, vs, hipMemcpyHostToDevice, s));
+    if (n > p) {
+        SMH_HIP(hipMemcpyAsync(ncol + p + 1, *col + p, (n - p) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        SMH_HIP(hipMemcpyAsync(nval + ((size_t)p + 1) * vs, (const char *)*val + (size_t)p * vs, (n - p) * vs, hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(k_bump_offsets, dim3(grid_for(n_rows - row, kBuildGrid)), dim3(kBlock), 0, s, off, (uint64_t)row + 1, (uint64_t)n_rows);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
     (void)hipFree(*col); (void)hipFree(*val);
-    *col = ncol; *val = nval; *nnz = n + 1;
+    *col = fresh.release(ncol); *val = fresh.release(nval); *nnz = n + 1;
     return SMH_OK;
 }
 
@@ -799,10 +702,10 @@ int column_info(const uint32_t *off, const uint32_t *col, size_t n_rows, size_t 
     uint32_t *col_s = nullptr, *idx = nullptr;
     SMH_TRY(tmp_bufs.alloc(&col_s, nnz));
     SMH_TRY(tmp_bufs.alloc(&idx, nnz));
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz)), dim3(kBlock), 0, s, idx, (uint64_t)nnz);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, idx, (uint64_t)nnz);
     SMH_HIP(hipGetLastError());
-    SMH_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, col, col_s, idx, entries, nnz, 0u, bits_for(max_col), s));
-    hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(nnz)), dim3(kBlock), 0, s, col_s, (uint64_t)nnz, (uint64_t)n_cols, col_ptr);
+    SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, col, col_s, idx, entries, nnz, 0u, bits_for(max_col), s));
+    hipLaunchKernelGGL(k_asm_segments, dim3(grid_for(nnz, kBuildGrid)), dim3(kBlock), 0, s, col_s, (uint64_t)nnz, (uint64_t)n_cols, col_ptr);
     SMH_HIP(hipGetLastError());
     SMH_HIP(hipStreamSynchronize(s));
     return SMH_OK;

@@ -471,6 +471,46 @@ static int ensure_colfused(smh_crs *m) {
 // K2s: the row-length split, once per matrix (split_ok == false afterwards: not worth it / not possible -> K2c)
 constexpr uint32_t kSplitMinLong = 64;  // rows of this many entries and more form the LONG part
 static int finish_create(smh_crs *m, int validate);
+// the smh_crs_set_* settings a clone (and a handle updated in place) carries
+static void copy_knobs(smh_crs *dst, const smh_crs *src) {
+    dst->forced_lanes = src->forced_lanes;
+    dst->forced_chunks = src->forced_chunks;
+    dst->stream_rows_per_thread = src->stream_rows_per_thread;
+    dst->cb_forced_shift = src->cb_forced_shift;
+    dst->use_ring = src->use_ring;
+    dst->use_stream_xs = src->use_stream_xs;
+    dst->use_stream_direct = src->use_stream_direct;
+    dst->use_stream_vdict = src->use_stream_vdict;
+    dst->use_col16 = src->use_col16;
+}
+
+// Every handle is made here: a fresh handle on the current device over device arrays, with the create-time inspection done
+// (finish_create).  like (optional): the settings it takes, else the defaults.  Owned arrays go with the handle, also on failure;
+// borrowed ones are never freed by it.
+static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, uint32_t *off, uint32_t *col, void *val,
+                       bool owns, int validate, smh_crs **out) {
+    smh_crs *m = new (std::nothrow) smh_crs();
+    if (!m) {
+        if (owns) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); }
+        return fail(SMH_ERR_OOM, "host allocation failed");
+    }
+    m->dtype = dtype; m->device = current_device(); m->owns = owns;
+    m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
+    m->d_off = off; m->d_col = col; m->d_val = val;
+    if (like) copy_knobs(m, like);
+    const int rc = finish_create(m, validate);
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)smh_crs_destroy(m); });
+    *out = m;
+    return SMH_OK;
+}
+// ... the handle takes the arrays of `arrays`
+static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, CrsArrays &arrays, int validate, smh_crs **out) {
+    uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;
+    arrays.release(&off, &col, &val);
+    return wrap_arrays(dtype, like, n_rows, n_cols, nnz, off, col, val, true, validate, out);
+}
+
 static int ensure_split(smh_crs *m) {
     if (m->split_built) return SMH_OK;
     SMH_TRY(columns_within_n_cols(m, "row-length split"));
@@ -478,34 +518,27 @@ static int ensure_split(smh_crs *m) {
     m->split_ok = false;
     if (m->no_split || m->n_rows == 0 || m->nnz == 0) return SMH_OK;
     size_t n_long = 0, nnz_long = 0;
-    uint32_t *rows = nullptr, *off_l = nullptr, *col_l = nullptr, *off_s = nullptr, *col_s = nullptr;
-    void *val_l = nullptr, *val_s = nullptr;
-    SMH_TRY(build_colsplit(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, kSplitMinLong, &n_long, &nnz_long, &rows, &off_l, &col_l,
-                           &val_l, &off_s, &col_s, &val_s, m->stream));
-    auto wrap = [&](size_t n_rows, size_t nnz, uint32_t *off, uint32_t *col, void *val, uint32_t shift, smh_crs **out) -> int {
-        smh_crs *p = new (std::nothrow) smh_crs();
-        if (!p) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return fail(SMH_ERR_OOM, "host allocation failed"); }
-        p->dtype = m->dtype; p->device = m->device; p->n_rows = n_rows; p->n_cols = m->n_cols; p->nnz = nnz;
-        p->d_off = off; p->d_col = col; p->d_val = val; p->owns = true;
-        p->no_split = true;
-        p->cb_forced_shift = shift;
-        const int rc = finish_create(p, 0);
-        if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(p); return fail(rc, "%s", keep); }
-        *out = p;
-        return SMH_OK;
-    };
+    uint32_t *rows = nullptr;
+    CrsArrays long_part, short_part;
+    SMH_TRY(build_colsplit(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, kSplitMinLong, &n_long, &nnz_long, &rows, &long_part.off,
+                           &long_part.col, &long_part.val, &short_part.off, &short_part.col, &short_part.val, m->stream));
     // worth it when the long rows are a minority that holds a good part of the entries
     const bool worth = n_long > 0 && n_long * 4 <= m->n_rows && nnz_long * 4 >= m->nnz;
     if (!worth) {
-        (void)hipFree(rows); (void)hipFree(off_l); (void)hipFree(col_l); (void)hipFree(val_l); (void)hipFree(off_s); (void)hipFree(col_s); (void)hipFree(val_s);
+        (void)hipFree(rows);
         return SMH_OK;
     }
     m->d_split_rows = rows;
     m->split_n_long = n_long;
+    auto part = [&](size_t n_rows, size_t nnz, CrsArrays &arrays, uint32_t shift, smh_crs **out) -> int {
+        SMH_TRY(wrap_arrays(m->dtype, nullptr, n_rows, m->n_cols, nnz, arrays, 0, out));
+        (*out)->no_split = true;
+        (*out)->cb_forced_shift = shift;
+        return SMH_OK;
+    };
     // LONG: K2c with 2^18-column blocks (1.93 against 2.03 ms with 2^19 on C3's long part); SHORT: its own AUTO with 2^19
-    int rc = wrap(n_long, nnz_long, off_l, col_l, val_l, 18u, &m->split_long);
-    if (rc == SMH_OK) rc = wrap(m->n_rows, m->nnz - nnz_long, off_s, col_s, val_s, 19u, &m->split_short);
-    else { (void)hipFree(off_s); (void)hipFree(col_s); (void)hipFree(val_s); }
+    int rc = part(n_long, nnz_long, long_part, 18u, &m->split_long);
+    if (rc == SMH_OK) rc = part(m->n_rows, m->nnz - nnz_long, short_part, 19u, &m->split_short);
     if (rc == SMH_OK) {
         hipError_t e = hipMalloc(&m->d_split_y, (n_long ? n_long : 1) * dtype_size(m->dtype));
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->split_stream, hipStreamNonBlocking);
@@ -513,13 +546,12 @@ static int ensure_split(smh_crs *m) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&m->split_join, hipEventDisableTiming);
         if (e != hipSuccess) rc = hip_fail(e, "split workspace", __FILE__, __LINE__);
     }
-    if (rc != SMH_OK) {
-        char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0;
-        (void)smh_crs_destroy(m->split_long); (void)smh_crs_destroy(m->split_short);
-        m->split_long = m->split_short = nullptr;
-        (void)hipFree(m->d_split_rows); m->d_split_rows = nullptr;
-        return fail(rc, "%s", keep);
-    }
+    if (rc != SMH_OK)
+        return keep_error(rc, [&] {
+            (void)smh_crs_destroy(m->split_long); (void)smh_crs_destroy(m->split_short);
+            m->split_long = m->split_short = nullptr;
+            (void)hipFree(m->d_split_rows); m->d_split_rows = nullptr;
+        });
     m->split_ok = true;
     return SMH_OK;
 }
@@ -1006,8 +1038,8 @@ static int vec_check_pair(const smh_vec *x, const smh_vec *y) {
 }
 
 // scratch for reductions of the vector API: per thread, per device
-struct ReduceScratch { void *d = nullptr; int device = -1; };
-static thread_local ReduceScratch g_red;
+struct ReduceBuffer { void *d = nullptr; int device = -1; };
+static thread_local ReduceBuffer g_red;
 static int reduce_scratch(void **out) {
     const int dev = current_device();
     if (!g_red.d || g_red.device != dev) {
@@ -1071,28 +1103,16 @@ int smh_crs_create(smh_dtype dtype, size_t n_rows, size_t n_cols, size_t nnz, co
                    const uint32_t *columns, const void *values, int validate, smh_crs **out) {
     SMH_TRY(check_create_args(dtype, n_rows, nnz, offset_rows, columns, values, out));
     SMH_TRY(require_device());
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) return fail(SMH_ERR_OOM, "host allocation failed");
-    m->dtype = dtype; m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz; m->owns = true;
-    m->device = current_device();
     const size_t vs = dtype_size(dtype);
-    int rc = SMH_OK;
-    auto go = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&m->d_off, (n_rows + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&m->d_col, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&m->d_val, (nnz + 4) * vs));
-        if (n_rows > 0) SMH_HIP(hipMemcpy(m->d_off, offset_rows, (n_rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        else SMH_HIP(hipMemset(m->d_off, 0, sizeof(uint32_t)));
-        if (nnz > 0) {
-            SMH_HIP(hipMemcpy(m->d_col, columns, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-            SMH_HIP(hipMemcpy(m->d_val, values, nnz * vs, hipMemcpyHostToDevice));
-        }
-        return finish_create(m, validate);
-    };
-    rc = go();
-    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
-    *out = m;
-    return SMH_OK;
+    CrsArrays arrays;
+    SMH_TRY(arrays.alloc(n_rows, nnz, vs));
+    if (n_rows > 0) SMH_HIP(hipMemcpy(arrays.off, offset_rows, (n_rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    else SMH_HIP(hipMemset(arrays.off, 0, sizeof(uint32_t)));
+    if (nnz > 0) {
+        SMH_HIP(hipMemcpy(arrays.col, columns, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+        SMH_HIP(hipMemcpy(arrays.val, values, nnz * vs, hipMemcpyHostToDevice));
+    }
+    return wrap_arrays(dtype, nullptr, n_rows, n_cols, nnz, arrays, validate, out);
 }
 
 int smh_crs_create_dev(smh_dtype dtype, size_t n_rows, size_t n_cols, size_t nnz, const uint32_t *offset_rows_dev,
@@ -1101,16 +1121,18 @@ int smh_crs_create_dev(smh_dtype dtype, size_t n_rows, size_t n_cols, size_t nnz
     SMH_TRY(require_device());
     if (((uintptr_t)columns_dev & 15u) || ((uintptr_t)values_dev & 15u))
         return fail(SMH_ERR_INVALID, "columns/values device pointers must be 16-byte aligned");
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) return fail(SMH_ERR_OOM, "host allocation failed");
-    m->dtype = dtype; m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz; m->owns = false;
-    m->device = current_device();
-    m->d_off = const_cast<uint32_t *>(offset_rows_dev);
-    m->d_col = const_cast<uint32_t *>(columns_dev);
-    m->d_val = const_cast<void *>(values_dev);
-    int rc = finish_create(m, validate);
-    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
-    *out = m;
+    return wrap_arrays(dtype, nullptr, n_rows, n_cols, nnz, const_cast<uint32_t *>(offset_rows_dev), const_cast<uint32_t *>(columns_dev),
+                       const_cast<void *>(values_dev), false, validate, out);
+}
+
+// a device copy of a host array (none of a null one), freed with `scr`
+static int upload(Scratch &scr, const void *host, size_t bytes, const void **dev) {
+    *dev = nullptr;
+    if (!host) return SMH_OK;
+    char *d = nullptr;
+    SMH_TRY(scr.alloc(&d, bytes));
+    if (bytes) SMH_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+    *dev = d;
     return SMH_OK;
 }
 
@@ -1130,86 +1152,63 @@ static int assemble_common(smh_dtype dtype, size_t n_ops, const uint32_t *rows, 
     if (n_ops && (!rows || !cols || !values)) return fail(SMH_ERR_INVALID, "NULL operation array");
     if (n_ops >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
     SMH_TRY(require_device());
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) return fail(SMH_ERR_OOM, "host allocation failed");
-    m->dtype = dtype; m->owns = true;
-    m->device = current_device();
     const size_t vs = dtype_size(dtype);
-    void *d_in[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto no_rows = [&](size_t n_cols) -> int {  // SparseMatCRS::new() (sparsemat_crs.rs:47-49): no rows at all
-        SMH_HIP(hipMalloc((void **)&m->d_off, sizeof(uint32_t)));
-        SMH_HIP(hipMemset(m->d_off, 0, sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&m->d_col, 4 * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&m->d_val, 4 * vs));
-        m->n_cols = n_cols;
-        return finish_create(m, 0);
+    // the first two operations decide the SparseMatCRS quirk
+    size_t skip = 0, min_cols = 0, orphans = 0;
+    bool twin = false;
+    uint32_t r01[2] = {0, 0}, c01[2] = {0, 0};
+    double v0 = 0.0;  // (holds an f32 or an f64 bit pattern)
+    uint8_t op0 = 0;
+    auto fold_v0 = [&]() {  // push(i, j, zero) then `=` or `+=` (sparsematrix.rs:226-233)
+        if (op0) return;
+        if (dtype == SMH_F64) { double v; memcpy(&v, &v0, 8); v = 0.0 + v; memcpy(&v0, &v, 8); }
+        else { float v; memcpy(&v, &v0, 4); v = 0.0f + v; memcpy(&v0, &v, 4); }
     };
-    auto go = [&]() -> int {
-        if (n_ops == 0) return no_rows(0);
-        // the first two operations decide the SparseMatCRS quirk
-        size_t skip = 0, min_cols = 0;
-        bool twin = false;
-        uint32_t r01[2] = {0, 0}, c01[2] = {0, 0};
-        double v0 = 0.0;  // (holds an f32 or an f64 bit pattern)
-        uint8_t op0 = 0;
-        if (into_crs) {
-            const size_t k = n_ops < 2 ? n_ops : 2;
-            const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
-            SMH_HIP(hipMemcpy(r01, rows, k * sizeof(uint32_t), kind));
-            SMH_HIP(hipMemcpy(c01, cols, k * sizeof(uint32_t), kind));
-            SMH_HIP(hipMemcpy(&v0, values, vs, kind));
-            if (transposing) op0 = 1;
-            else if (ops) SMH_HIP(hipMemcpy(&op0, ops, 1, kind));
-            if (n_ops == 1) {
-                // push(i, j, zero) then `=` or `+=` (sparsematrix.rs:226-233): kept on the handle so that smh_crs_apply can
-                // continue the replay; nothing else reads it
-                if (!op0) {
-                    if (dtype == SMH_F64) { double v; memcpy(&v, &v0, 8); v = 0.0 + v; memcpy(&v0, &v, 8); }
-                    else { float v; memcpy(&v, &v0, 4); v = 0.0f + v; memcpy(&v0, &v, 4); }
-                }
-                m->has_first_op = true;
-                m->first_row = r01[0];
-                m->first_col = c01[0];
-                memcpy(&m->first_val_bits, &v0, 8);
-                m->orphans = 1;
-                return no_rows((size_t)c01[0] + 1);
-            }
-            if (r01[1] < r01[0]) { skip = 1; min_cols = (size_t)c01[0] + 1; m->orphans = 1; }
-            else if (r01[1] == r01[0] && c01[1] == c01[0]) { skip = 1; twin = true; }
-        }
-        const uint32_t *d_rows = rows, *d_cols = cols;
-        const void *d_vals = values;
-        const uint8_t *d_ops = ops;
+    if (into_crs && n_ops) {
+        const size_t k = n_ops < 2 ? n_ops : 2;
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+        SMH_HIP(hipMemcpy(r01, rows, k * sizeof(uint32_t), kind));
+        SMH_HIP(hipMemcpy(c01, cols, k * sizeof(uint32_t), kind));
+        SMH_HIP(hipMemcpy(&v0, values, vs, kind));
+        if (transposing) op0 = 1;
+        else if (ops) SMH_HIP(hipMemcpy(&op0, ops, 1, kind));
+        if (n_ops == 1) { fold_v0(); orphans = 1; }
+        else if (r01[1] < r01[0]) { skip = 1; min_cols = (size_t)c01[0] + 1; orphans = 1; }
+        else if (r01[1] == r01[0] && c01[1] == c01[0]) { skip = 1; twin = true; }
+    }
+    Scratch in;  // device copies of host operation arrays
+    CrsArrays arrays;
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    const bool single = into_crs && n_ops == 1;
+    if (n_ops == 0 || single) {  // SparseMatCRS::new() (sparsemat_crs.rs:47-49): no rows at all
+        SMH_TRY(arrays.alloc(0, 0, vs));
+        SMH_HIP(hipMemset(arrays.off, 0, sizeof(uint32_t)));
+        n_cols = single ? (size_t)c01[0] + 1 : 0;
+    } else {
+        const void *d_rows = rows, *d_cols = cols, *d_vals = values, *d_ops = ops;
         if (!on_device) {
-            SMH_HIP(hipMalloc(&d_in[0], n_ops * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc(&d_in[1], n_ops * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc(&d_in[2], n_ops * vs));
-            SMH_HIP(hipMemcpy(d_in[0], rows, n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
-            SMH_HIP(hipMemcpy(d_in[1], cols, n_ops * sizeof(uint32_t), hipMemcpyHostToDevice));
-            SMH_HIP(hipMemcpy(d_in[2], values, n_ops * vs, hipMemcpyHostToDevice));
-            if (ops) {
-                SMH_HIP(hipMalloc(&d_in[3], n_ops));
-                SMH_HIP(hipMemcpy(d_in[3], ops, n_ops, hipMemcpyHostToDevice));
-            }
-            d_rows = (const uint32_t *)d_in[0]; d_cols = (const uint32_t *)d_in[1]; d_vals = d_in[2]; d_ops = (const uint8_t *)d_in[3];
+            SMH_TRY(upload(in, rows, n_ops * sizeof(uint32_t), &d_rows));
+            SMH_TRY(upload(in, cols, n_ops * sizeof(uint32_t), &d_cols));
+            SMH_TRY(upload(in, values, n_ops * vs, &d_vals));
+            SMH_TRY(upload(in, ops, n_ops, &d_ops));
         }
-        SMH_TRY(assemble_triplets(dtype, n_ops - skip, d_rows + skip, d_cols + skip, (const char *)d_vals + skip * vs,
-                                  d_ops ? d_ops + skip : nullptr, into_crs, transposing, transposing, &m->n_rows, &m->n_cols, &m->nnz, &m->d_off, &m->d_col,
-                                  &m->d_val, nullptr));
-        if (min_cols > m->n_cols) m->n_cols = min_cols;
-        if (twin) {  // the first operation's own entry: push(i, j, zero) then `=` or `+=` (sparsematrix.rs:226-233)
-            if (!op0) {
-                if (dtype == SMH_F64) { double v; memcpy(&v, &v0, 8); v = 0.0 + v; memcpy(&v0, &v, 8); }
-                else { float v; memcpy(&v, &v0, 4); v = 0.0f + v; memcpy(&v0, &v, 4); }
-            }
-            SMH_TRY(append_to_row(dtype, m->d_off, &m->d_col, &m->d_val, m->n_rows, &m->nnz, r01[0], c01[0], &v0, nullptr));
+        SMH_TRY(assemble_triplets(dtype, n_ops - skip, (const uint32_t *)d_rows + skip, (const uint32_t *)d_cols + skip, (const char *)d_vals + skip * vs,
+                                  d_ops ? (const uint8_t *)d_ops + skip : nullptr, into_crs, transposing, transposing, &n_rows, &n_cols, &nnz,
+                                  &arrays.off, &arrays.col, &arrays.val, nullptr));
+        if (min_cols > n_cols) n_cols = min_cols;
+        if (twin) {  // the first operation's own entry
+            fold_v0();
+            SMH_TRY(append_to_row(dtype, arrays.off, &arrays.col, &arrays.val, n_rows, &nnz, r01[0], c01[0], &v0, nullptr));
         }
-        return finish_create(m, 0);
-    };
-    const int rc = go();
-    for (void *p : d_in) (void)hipFree(p);
-    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
-    *out = m;
+    }
+    SMH_TRY(wrap_arrays(dtype, nullptr, n_rows, n_cols, nnz, arrays, 0, out));
+    (*out)->orphans = orphans;
+    if (single) {  // push(i, j, zero) then `=` or `+=`: kept on the handle so that smh_crs_apply can continue the replay; nothing else reads it
+        (*out)->has_first_op = true;
+        (*out)->first_row = r01[0];
+        (*out)->first_col = c01[0];
+        memcpy(&(*out)->first_val_bits, &v0, 8);
+    }
     return SMH_OK;
 }
 
@@ -1251,37 +1250,24 @@ int smh_crs_transpose(const smh_crs *a, smh_crs **out) {
         uint32_t c01[2] = {0, 0};
         SMH_HIP(hipMemcpy(c01, a->d_col, sizeof c01, hipMemcpyDeviceToHost));
         if (c01[1] >= c01[0]) {
-            uint32_t *t_off = nullptr, *t_col = nullptr;
-            void *t_val = nullptr;
+            CrsArrays t;
             size_t t_rows = 0, t_cols = 0;
             bool done = false;
-            SMH_TRY(transpose_bucketed(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, &t_off, &t_col, &t_val, &t_rows, &t_cols, &done,
+            SMH_TRY(transpose_bucketed(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, &t.off, &t.col, &t.val, &t_rows, &t_cols, &done,
                                        nullptr));
             if (done) {
-                smh_crs *m = new (std::nothrow) smh_crs();
-                if (!m) { (void)hipFree(t_off); (void)hipFree(t_col); (void)hipFree(t_val); return fail(SMH_ERR_OOM, "host allocation failed"); }
-                m->dtype = a->dtype; m->owns = true;
-                m->device = current_device();
-                m->d_off = t_off; m->d_col = t_col; m->d_val = t_val;
-                m->n_rows = t_rows; m->n_cols = t_cols; m->nnz = a->nnz;
-                const int rc = finish_create(m, 0);
-                if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
+                SMH_TRY(wrap_arrays(a->dtype, nullptr, t_rows, t_cols, a->nnz, t, 0, out));
                 g_transpose_route = 1;
-                *out = m;
                 return SMH_OK;
             }
         }
     }
+    Scratch scr;
     uint32_t *d_rowof = nullptr;
-    SMH_HIP(hipMalloc((void **)&d_rowof, a->nnz * sizeof(uint32_t)));
-    auto go = [&]() -> int {
-        SMH_TRY(expand_rows(a->d_off, a->n_rows, d_rowof, nullptr));
-        SMH_HIP(hipStreamSynchronize(nullptr));
-        return assemble_common((smh_dtype)a->dtype, a->nnz, a->d_col, d_rowof, a->d_val, nullptr, true, true, out, true);
-    };
-    const int rc = go();
-    (void)hipFree(d_rowof);
-    return rc;
+    SMH_TRY(scr.alloc(&d_rowof, a->nnz));
+    SMH_TRY(expand_rows(a->d_off, a->n_rows, d_rowof, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return assemble_common((smh_dtype)a->dtype, a->nnz, a->d_col, d_rowof, a->d_val, nullptr, true, true, out, true);
 }
 
 static int column_info_common(const smh_crs *m, uint32_t *rows, uint32_t *col_ptr, uint32_t *entries, bool on_device) {
@@ -1290,20 +1276,16 @@ static int column_info_common(const smh_crs *m, uint32_t *rows, uint32_t *col_pt
         return fail(SMH_ERR_INDEX_RANGE, "column %u out of range for %zu columns", m->max_col, m->n_cols);
     SMH_HIP(hipStreamSynchronize(m->stream));
     if (on_device) return column_info(m->d_off, m->d_col, m->n_rows, m->n_cols, m->nnz, m->max_col, rows, col_ptr, entries, m->stream);
+    Scratch scr;
     uint32_t *d[3] = {nullptr, nullptr, nullptr};
-    auto go = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&d[0], (m->nnz ? m->nnz : 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&d[1], (m->n_cols + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&d[2], (m->nnz ? m->nnz : 1) * sizeof(uint32_t)));
-        SMH_TRY(column_info(m->d_off, m->d_col, m->n_rows, m->n_cols, m->nnz, m->max_col, d[0], d[1], d[2], m->stream));
-        if (m->nnz) SMH_HIP(hipMemcpy(rows, d[0], m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        SMH_HIP(hipMemcpy(col_ptr, d[1], (m->n_cols + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (m->nnz) SMH_HIP(hipMemcpy(entries, d[2], m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return SMH_OK;
-    };
-    const int rc = go();
-    for (uint32_t *p : d) (void)hipFree(p);
-    return rc;
+    SMH_TRY(scr.alloc(&d[0], m->nnz));
+    SMH_TRY(scr.alloc(&d[1], m->n_cols + 1));
+    SMH_TRY(scr.alloc(&d[2], m->nnz));
+    SMH_TRY(column_info(m->d_off, m->d_col, m->n_rows, m->n_cols, m->nnz, m->max_col, d[0], d[1], d[2], m->stream));
+    if (m->nnz) SMH_HIP(hipMemcpy(rows, d[0], m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SMH_HIP(hipMemcpy(col_ptr, d[1], (m->n_cols + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (m->nnz) SMH_HIP(hipMemcpy(entries, d[2], m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
 }
 
 int smh_crs_column_info(const smh_crs *m, uint32_t *rows, uint32_t *col_ptr, uint32_t *entries) {
@@ -1323,55 +1305,16 @@ int smh_crs_prod(const smh_crs *a, const smh_crs *b, smh_crs **out) {
         return fail(SMH_ERR_INDEX_RANGE, "column %u out of range for %zu columns", a->max_col, a->n_cols);
     SMH_HIP(hipStreamSynchronize(a->stream));
     SMH_HIP(hipStreamSynchronize(b->stream));
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) return fail(SMH_ERR_OOM, "host allocation failed");
-    m->dtype = a->dtype; m->owns = true;
-    m->device = current_device();
-    auto go = [&]() -> int {
-        SMH_TRY(prod_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, b->d_off, b->d_col, b->d_val, b->n_rows,
-                         &m->n_rows, &m->n_cols, &m->nnz, &m->d_off, &m->d_col, &m->d_val, nullptr));
-        return finish_create(m, 0);
-    };
-    const int rc = go();
-    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
-    *out = m;
-    return SMH_OK;
+    CrsArrays arrays;
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    SMH_TRY(prod_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, b->d_off, b->d_col, b->d_val, b->n_rows, &n_rows, &n_cols,
+                     &nnz, &arrays.off, &arrays.col, &arrays.val, nullptr));
+    return wrap_arrays(a->dtype, nullptr, n_rows, n_cols, nnz, arrays, 0, out);
 }
 
 // ---- #[derive(Clone)] (sparsemat_crs.rs:8) and SparseMatrix::add / sub (sparsematrix.rs:123-143, matadd.hip) ------------------
 static thread_local int g_add_route = 2;
 int smh_last_add_route(void) { return g_add_route; }
-
-// the smh_crs_set_* settings a clone (and a handle updated in place) carries
-static void copy_knobs(smh_crs *dst, const smh_crs *src) {
-    dst->forced_lanes = src->forced_lanes;
-    dst->forced_chunks = src->forced_chunks;
-    dst->stream_rows_per_thread = src->stream_rows_per_thread;
-    dst->cb_forced_shift = src->cb_forced_shift;
-    dst->use_ring = src->use_ring;
-    dst->use_stream_xs = src->use_stream_xs;
-    dst->use_stream_direct = src->use_stream_direct;
-    dst->use_stream_vdict = src->use_stream_vdict;
-    dst->use_col16 = src->use_col16;
-}
-
-// a fresh handle over device arrays (owned: freed with it, also on failure), with `like`'s settings and the create-time inspection done
-static int wrap_arrays(const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, size_t orphans, uint32_t *off, uint32_t *col, void *val,
-                       bool owns, smh_crs **out) {
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) {
-        if (owns) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); }
-        return fail(SMH_ERR_OOM, "host allocation failed");
-    }
-    m->dtype = like->dtype; m->device = current_device(); m->owns = owns;
-    m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz; m->orphans = orphans;
-    m->d_off = off; m->d_col = col; m->d_val = val;
-    copy_knobs(m, like);
-    const int rc = finish_create(m, 0);
-    if (rc != SMH_OK) { char keep[512]; strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0; smh_crs_destroy(m); strncpy(g_err, keep, sizeof g_err); return rc; }
-    *out = m;
-    return SMH_OK;
-}
 
 // in place: `a` takes the fresh handle's state, and every form derived from the old one (merge tiles, K1s codes and value
 // dictionary, K1r plan, K2c / K2f / K2s / K2t copies, statistics) goes with the old state.  keep_arrays: the fresh handle
@@ -1387,22 +1330,15 @@ int smh_crs_clone(const smh_crs *a, smh_crs **out) {
     *out = nullptr;
     SMH_HIP(hipStreamSynchronize(a->stream));
     const size_t vs = dtype_size(a->dtype);
-    uint32_t *off = nullptr, *col = nullptr;
-    void *val = nullptr;
-    auto go = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&off, (a->n_rows + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&col, (a->nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&val, (a->nnz + 4) * vs));
-        SMH_HIP(hipMemcpy(off, a->d_off, (a->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-        if (a->nnz) {
-            SMH_HIP(hipMemcpy(col, a->d_col, a->nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-            SMH_HIP(hipMemcpy(val, a->d_val, a->nnz * vs, hipMemcpyDeviceToDevice));
-        }
-        return SMH_OK;
-    };
-    const int rc = go();
-    if (rc != SMH_OK) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return rc; }
-    SMH_TRY(wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, off, col, val, true, out));
+    CrsArrays arrays;
+    SMH_TRY(arrays.alloc(a->n_rows, a->nnz, vs));
+    SMH_HIP(hipMemcpy(arrays.off, a->d_off, (a->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    if (a->nnz) {
+        SMH_HIP(hipMemcpy(arrays.col, a->d_col, a->nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+        SMH_HIP(hipMemcpy(arrays.val, a->d_val, a->nnz * vs, hipMemcpyDeviceToDevice));
+    }
+    SMH_TRY(wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out));
+    (*out)->orphans = a->orphans;
     (*out)->has_first_op = a->has_first_op;
     (*out)->first_row = a->first_row;
     (*out)->first_col = a->first_col;
@@ -1431,23 +1367,18 @@ static int add_common(smh_crs *a_mut, const smh_crs *a, const smh_crs *b, bool s
         // SparseMatCRS::new() (no offset_rows): the replay of b's entries as add_to operations, first-push quirk included
         g_add_route = 0;
         const size_t vs = dtype_size(a->dtype);
+        Scratch scr;
         uint32_t *rows = nullptr;
-        void *neg = nullptr;
-        auto go = [&]() -> int {
-            SMH_HIP(hipMalloc((void **)&rows, b->nnz * sizeof(uint32_t)));
-            SMH_TRY(expand_rows(b->d_off, b->n_rows, rows, nullptr));
-            if (subtract) {  // 0 - v == 0 + (-v) in IEEE 754, signed zeros included
-                SMH_HIP(hipMalloc(&neg, (b->nnz + 4) * vs));
-                SMH_HIP(hipMemcpy(neg, b->d_val, b->nnz * vs, hipMemcpyDeviceToDevice));
-                SMH_TRY(launch_scale_values(a->dtype, neg, b->nnz, -1.0, nullptr));
-            }
-            SMH_HIP(hipStreamSynchronize(nullptr));
-            return assemble_common((smh_dtype)a->dtype, b->nnz, rows, b->d_col, subtract ? neg : b->d_val, nullptr, true, true, &fresh);
-        };
-        const int rc = go();
-        (void)hipFree(rows);
-        (void)hipFree(neg);
-        SMH_TRY(rc);
+        char *neg = nullptr;
+        SMH_TRY(scr.alloc(&rows, b->nnz));
+        SMH_TRY(expand_rows(b->d_off, b->n_rows, rows, nullptr));
+        if (subtract) {  // 0 - v == 0 + (-v) in IEEE 754, signed zeros included
+            SMH_TRY(scr.alloc(&neg, (b->nnz + 4) * vs));
+            SMH_HIP(hipMemcpy(neg, b->d_val, b->nnz * vs, hipMemcpyDeviceToDevice));
+            SMH_TRY(launch_scale_values(a->dtype, neg, b->nnz, -1.0, nullptr));
+        }
+        SMH_HIP(hipStreamSynchronize(nullptr));
+        SMH_TRY(assemble_common((smh_dtype)a->dtype, b->nnz, rows, b->d_col, subtract ? (const void *)neg : b->d_val, nullptr, true, true, &fresh));
         if (fresh->n_cols < a->n_cols) fresh->n_cols = a->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
         copy_knobs(fresh, a);
         if (a_mut) replace_state(a_mut, fresh, false);
@@ -1466,10 +1397,11 @@ static int add_common(smh_crs *a_mut, const smh_crs *a, const smh_crs *b, bool s
     SMH_TRY(add_crs(a->dtype, subtract, oa, ob, a_mut != nullptr, a == b, force_general, &r, a->stream));
     g_add_route = r.route;
     if (r.values_only) {  // (borrowed by the fresh handle until it has been built: a failure must not free a's arrays)
-        SMH_TRY(wrap_arrays(a, a->n_rows, a->n_cols, a->nnz, a->orphans, a->d_off, a->d_col, a->d_val, false, &fresh));
+        SMH_TRY(wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, a->d_off, a->d_col, a->d_val, false, 0, &fresh));
         fresh->owns = a->owns;
     } else
-        SMH_TRY(wrap_arrays(a, r.n_rows, r.n_cols, r.nnz, a->orphans, r.off, r.col, r.val, true, &fresh));
+        SMH_TRY(wrap_arrays(a->dtype, a, r.n_rows, r.n_cols, r.nnz, r.arrays, 0, &fresh));
+    fresh->orphans = a->orphans;
     if (a_mut) replace_state(a_mut, fresh, r.values_only);
     else *out = fresh;
     return SMH_OK;
@@ -1493,19 +1425,6 @@ static int check_dev_array(const void *p, int device, const char *what) {
         return fail(SMH_ERR_INVALID, "%s lives on device %d, the handle on device %d", what, a.device, device);
     return SMH_OK;
 }
-
-// device copies of host operation arrays (freed with the object)
-struct DevArrays {
-    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~DevArrays() { for (void *q : p) (void)hipFree(q); }
-    int up(int i, const void *host, size_t bytes, const void **dev) {
-        if (!host) { *dev = nullptr; return SMH_OK; }
-        SMH_HIP(hipMalloc(&p[i], bytes ? bytes : 16));
-        if (bytes) SMH_HIP(hipMemcpy(p[i], host, bytes, hipMemcpyHostToDevice));
-        *dev = p[i];
-        return SMH_OK;
-    }
-};
 
 static UpdMatrix upd_view(const smh_crs *m) {
     UpdMatrix u;
@@ -1532,14 +1451,15 @@ static int get_many_common(const smh_crs *m, size_t n, const uint32_t *rows, con
         else memset(values_out, 0, n * vs);
         return SMH_OK;
     }
-    DevArrays st;
+    Scratch st;  // device copies of host query arrays
     const void *d_rows = rows, *d_cols = cols;
     void *d_out = values_out;
     if (!on_device) {
-        SMH_TRY(st.up(0, rows, n * sizeof(uint32_t), &d_rows));
-        SMH_TRY(st.up(1, cols, n * sizeof(uint32_t), &d_cols));
-        SMH_HIP(hipMalloc(&st.p[2], n * vs));
-        d_out = st.p[2];
+        SMH_TRY(upload(st, rows, n * sizeof(uint32_t), &d_rows));
+        SMH_TRY(upload(st, cols, n * sizeof(uint32_t), &d_cols));
+        char *out_dev = nullptr;
+        SMH_TRY(st.alloc(&out_dev, n * vs));
+        d_out = out_dev;
     }
     SMH_TRY(crs_get_many(m->dtype, upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_out, m->stream));
     if (!on_device) SMH_HIP(hipMemcpy(values_out, d_out, n * vs, hipMemcpyDeviceToHost));
@@ -1581,13 +1501,13 @@ static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32
         SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the arrays come first
     }
     SMH_HIP(hipStreamSynchronize(m->stream));
-    DevArrays st;
+    Scratch st;  // device copies of host operation arrays
     const void *d_rows = rows, *d_cols = cols, *d_vals = values, *d_ops = ops;
     if (!on_device) {
-        SMH_TRY(st.up(0, rows, n * sizeof(uint32_t), &d_rows));
-        SMH_TRY(st.up(1, cols, n * sizeof(uint32_t), &d_cols));
-        SMH_TRY(st.up(2, values, n * vs, &d_vals));
-        SMH_TRY(st.up(3, ops, n, &d_ops));
+        SMH_TRY(upload(st, rows, n * sizeof(uint32_t), &d_rows));
+        SMH_TRY(upload(st, cols, n * sizeof(uint32_t), &d_cols));
+        SMH_TRY(upload(st, values, n * vs, &d_vals));
+        SMH_TRY(upload(st, ops, n, &d_ops));
     }
     smh_crs *fresh = nullptr;
     if (m->n_rows == 0) {
@@ -1597,24 +1517,25 @@ static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32
             SMH_TRY(assemble_common((smh_dtype)m->dtype, n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_vals, (const uint8_t *)d_ops, true,
                                     true, &fresh));
         } else {
-            DevArrays cat;
-            auto go = [&]() -> int {
-                for (int i = 0; i < 3; ++i) SMH_HIP(hipMalloc(&cat.p[i], (n + 1) * (i < 2 ? sizeof(uint32_t) : vs)));
-                SMH_HIP(hipMalloc(&cat.p[3], n + 1));
-                const uint8_t set = 1;  // the recorded value is already folded: `set` it
-                SMH_HIP(hipMemcpy(cat.p[0], &m->first_row, sizeof(uint32_t), hipMemcpyHostToDevice));
-                SMH_HIP(hipMemcpy(cat.p[1], &m->first_col, sizeof(uint32_t), hipMemcpyHostToDevice));
-                SMH_HIP(hipMemcpy(cat.p[2], &m->first_val_bits, vs, hipMemcpyHostToDevice));
-                SMH_HIP(hipMemcpy(cat.p[3], &set, 1, hipMemcpyHostToDevice));
-                SMH_HIP(hipMemcpy((uint32_t *)cat.p[0] + 1, d_rows, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-                SMH_HIP(hipMemcpy((uint32_t *)cat.p[1] + 1, d_cols, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-                SMH_HIP(hipMemcpy((char *)cat.p[2] + vs, d_vals, n * vs, hipMemcpyDeviceToDevice));
-                if (d_ops) SMH_HIP(hipMemcpy((uint8_t *)cat.p[3] + 1, d_ops, n, hipMemcpyDeviceToDevice));
-                else SMH_HIP(hipMemset((uint8_t *)cat.p[3] + 1, 0, n));
-                return assemble_common((smh_dtype)m->dtype, n + 1, (const uint32_t *)cat.p[0], (const uint32_t *)cat.p[1], cat.p[2],
-                                       (const uint8_t *)cat.p[3], true, true, &fresh);
-            };
-            SMH_TRY(go());
+            Scratch cat;  // that push's operation ++ the stream
+            uint32_t *c_rows = nullptr, *c_cols = nullptr;
+            char *c_vals = nullptr;
+            uint8_t *c_ops = nullptr;
+            SMH_TRY(cat.alloc(&c_rows, n + 1));
+            SMH_TRY(cat.alloc(&c_cols, n + 1));
+            SMH_TRY(cat.alloc(&c_vals, (n + 1) * vs));
+            SMH_TRY(cat.alloc(&c_ops, n + 1));
+            const uint8_t set = 1;  // the recorded value is already folded: `set` it
+            SMH_HIP(hipMemcpy(c_rows, &m->first_row, sizeof(uint32_t), hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_cols, &m->first_col, sizeof(uint32_t), hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_vals, &m->first_val_bits, vs, hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_ops, &set, 1, hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_rows + 1, d_rows, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            SMH_HIP(hipMemcpy(c_cols + 1, d_cols, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            SMH_HIP(hipMemcpy(c_vals + vs, d_vals, n * vs, hipMemcpyDeviceToDevice));
+            if (d_ops) SMH_HIP(hipMemcpy(c_ops + 1, d_ops, n, hipMemcpyDeviceToDevice));
+            else SMH_HIP(hipMemset(c_ops + 1, 0, n));
+            SMH_TRY(assemble_common((smh_dtype)m->dtype, n + 1, c_rows, c_cols, c_vals, c_ops, true, true, &fresh));
         }
         if (fresh->n_cols < m->n_cols) fresh->n_cols = m->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
         copy_knobs(fresh, m);
@@ -1628,7 +1549,8 @@ static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32
     g_apply_route = r.route;
     if (r.values_only)  // structure unchanged: every form derived from it stays, the value-derived ones are refreshed
         return smh_crs_update_values(m, nullptr);
-    SMH_TRY(wrap_arrays(m, r.n_rows, r.n_cols, r.nnz, m->orphans, r.off, r.col, r.val, true, &fresh));
+    SMH_TRY(wrap_arrays(m->dtype, m, r.n_rows, r.n_cols, r.nnz, r.arrays, 0, &fresh));
+    fresh->orphans = m->orphans;
     replace_state(m, fresh, false);
     return SMH_OK;
 }
@@ -1653,20 +1575,10 @@ int smh_crs_eye(smh_dtype dtype, size_t dim, smh_crs **out) {
         const float one32 = 1.0f;
         return assemble_common(dtype, dim, &zero, &zero, dtype == SMH_F64 ? (const void *)&one64 : (const void *)&one32, &set, false, true, out);
     }
-    const size_t vs = dtype_size(dtype);
-    uint32_t *off = nullptr, *col = nullptr;
-    void *val = nullptr;
-    auto go = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&off, (dim + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&col, (dim + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&val, (dim + 4) * vs));
-        return build_eye(dtype, dim, off, col, val, nullptr);
-    };
-    const int rc = go();
-    if (rc != SMH_OK) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); return rc; }
-    smh_crs like;  // default settings
-    like.dtype = dtype;
-    return wrap_arrays(&like, dim, dim, dim, 0, off, col, val, true, out);
+    CrsArrays arrays;
+    SMH_TRY(arrays.alloc(dim, dim, dtype_size(dtype)));
+    SMH_TRY(build_eye(dtype, dim, arrays.off, arrays.col, arrays.val, nullptr));
+    return wrap_arrays(dtype, nullptr, dim, dim, dim, arrays, 0, out);
 }
 
 int smh_crs_is_symmetric(const smh_crs *m, int *out) {
@@ -1757,18 +1669,13 @@ int smh_crs_scale(smh_crs *m, double a) {
     if (m->has_first_op) {
         // the reference scales every stored value (sparsemat_crs.rs:153-157), the orphaned first push included, and smh_crs_apply
         // brings that value back: scale the kept copy by the same kernel, so that it rounds exactly as a stored value does
-        void *d = nullptr;
-        SMH_HIP(hipMalloc(&d, 16));
-        auto go = [&]() -> int {
-            SMH_HIP(hipMemcpyAsync(d, &m->first_val_bits, 8, hipMemcpyHostToDevice, m->stream));
-            SMH_TRY(launch_scale_values(m->dtype, d, 1, a, m->stream));
-            SMH_HIP(hipMemcpyAsync(&m->first_val_bits, d, 8, hipMemcpyDeviceToHost, m->stream));
-            SMH_HIP(hipStreamSynchronize(m->stream));
-            return SMH_OK;
-        };
-        const int rc = go();
-        (void)hipFree(d);
-        SMH_TRY(rc);
+        Scratch scr;
+        char *d = nullptr;
+        SMH_TRY(scr.alloc(&d, 16));
+        SMH_HIP(hipMemcpyAsync(d, &m->first_val_bits, 8, hipMemcpyHostToDevice, m->stream));
+        SMH_TRY(launch_scale_values(m->dtype, d, 1, a, m->stream));
+        SMH_HIP(hipMemcpyAsync(&m->first_val_bits, d, 8, hipMemcpyDeviceToHost, m->stream));
+        SMH_HIP(hipStreamSynchronize(m->stream));
     }
     // (K1s XD-V: every entry is its dictionary value times a, rounded as the entry itself is: the indices in the codes stay right)
     if (m->d_stream_dict && m->stream_dict_state == 1) SMH_TRY(launch_scale_values(m->dtype, m->d_stream_dict, 32, a, m->stream));
@@ -2210,10 +2117,7 @@ static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const v
     // lhs.get(i) is evaluated inside the entry loop (sparsematrix.rs:165-168): only rows that hold entries index lhs, so a
     // short lhs is an error only if it ends before the last non-empty row (densevec.rs:41 panics there).  The kernels read
     // lhs for every row, so a short-but-legal lhs is continued with zeros in a scratch copy.
-    struct Padded {
-        void *d = nullptr;
-        ~Padded() { if (d) (void)hipFree(d); }
-    } padded;
+    Scratch scr;
     if (lhs_len < m->n_rows) {
         size_t lo = 0, hi = m->n_rows;  // smallest i with offset_rows[i] == nnz; rows i.. are empty
         while (lo < hi) {
@@ -2225,10 +2129,11 @@ static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const v
         }
         if (lhs_len < lo)  // row lo - 1 is the last one with entries
             return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %zu", lhs_len, lo - 1);
-        SMH_HIP(hipMalloc(&padded.d, m->n_rows * vs));
-        SMH_HIP(hipMemsetAsync(padded.d, 0, m->n_rows * vs, m->stream));
-        if (lhs_len) SMH_HIP(hipMemcpyAsync(padded.d, d_lhs, lhs_len * vs, hipMemcpyDeviceToDevice, m->stream));
-        d_lhs = padded.d;
+        char *padded = nullptr;
+        SMH_TRY(scr.alloc(&padded, m->n_rows * vs));
+        SMH_HIP(hipMemsetAsync(padded, 0, m->n_rows * vs, m->stream));
+        if (lhs_len) SMH_HIP(hipMemcpyAsync(padded, d_lhs, lhs_len * vs, hipMemcpyDeviceToDevice, m->stream));
+        d_lhs = padded;
     }
     void *scratch = nullptr;
     SMH_TRY(reduce_scratch(&scratch));
@@ -2279,16 +2184,12 @@ int smh_crs_inner_prod(smh_crs *m, const void *lhs_host, size_t lhs_len, const v
     const size_t vs = dtype_size(m->dtype);
     // rhs goes to the x staging; lhs to a scratch allocation of its own
     SMH_TRY(ensure_cap(&m->d_x, &m->d_x_cap, rhs_len * vs));
-    void *d_lhs = nullptr;
-    SMH_HIP(hipMalloc(&d_lhs, (lhs_len ? lhs_len : 1) * vs));
-    auto go = [&]() -> int {
-        if (rhs_len) SMH_HIP(hipMemcpyAsync(m->d_x, rhs_host, rhs_len * vs, hipMemcpyHostToDevice, m->stream));
-        if (lhs_len) SMH_HIP(hipMemcpyAsync(d_lhs, lhs_host, lhs_len * vs, hipMemcpyHostToDevice, m->stream));
-        return inner_prod_dev(m, d_lhs, lhs_len, m->d_x, rhs_len, variant, out);
-    };
-    const int rc = go();
-    (void)hipFree(d_lhs);
-    return rc;
+    Scratch scr;
+    char *d_lhs = nullptr;
+    SMH_TRY(scr.alloc(&d_lhs, (lhs_len ? lhs_len : 1) * vs));
+    if (rhs_len) SMH_HIP(hipMemcpyAsync(m->d_x, rhs_host, rhs_len * vs, hipMemcpyHostToDevice, m->stream));
+    if (lhs_len) SMH_HIP(hipMemcpyAsync(d_lhs, lhs_host, lhs_len * vs, hipMemcpyHostToDevice, m->stream));
+    return inner_prod_dev(m, d_lhs, lhs_len, m->d_x, rhs_len, variant, out);
 }
 
 int smh_vec_norm_squared(const smh_vec *x, double *out) { return smh_vec_dot(x, x, out); }
@@ -2415,16 +2316,14 @@ int smh_cg_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_
         }
         return SMH_OK;
     };
-    rc = body();
-    char keep[512];
-    strncpy(keep, g_err, sizeof keep); keep[sizeof keep - 1] = 0;
-    (void)hipStreamSynchronize(s);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipFree(r); (void)hipFree(p); (void)hipFree(ap); (void)hipFree(partials); (void)hipFree(dot_partials); (void)hipFree(sc); (void)hipFree(sc2);
-    if (h_sc) (void)hipHostFree(h_sc);
-    (void)hipGetLastError();
-    strncpy(g_err, keep, sizeof g_err);
+    rc = keep_error(body(), [&] {
+        (void)hipStreamSynchronize(s);
+        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipFree(r); (void)hipFree(p); (void)hipFree(ap); (void)hipFree(partials); (void)hipFree(dot_partials); (void)hipFree(sc); (void)hipFree(sc2);
+        if (h_sc) (void)hipHostFree(h_sc);
+        (void)hipGetLastError();
+    });
     if (rc != SMH_OK) return rc;
     if (iters_out) *iters_out = iters;
     if (rr_out) *rr_out = rr;

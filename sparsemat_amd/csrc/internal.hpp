@@ -5,7 +5,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/sparsemat_hip.h"
 
@@ -31,7 +33,123 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 int require_device();  // SMH_ERR_NO_DEVICE when no HIP device is visible
 int current_device();
 
+// cleanup() (destroying a handle, a par or a comm, a teardown) without losing the error text that goes with status rc; returns rc
+template <typename F> int keep_error(int rc, F &&cleanup) {
+    char keep[512];
+    strncpy(keep, smh_last_error(), sizeof keep);
+    keep[sizeof keep - 1] = 0;
+    cleanup();
+    set_error("%s", keep);
+    return rc;
+}
+
 inline size_t dtype_size(int dt) { return dt == SMH_F64 ? 8 : 4; }
+
+// ---- device memory goes through the caching layer of pool.hip (see there for why) ---------------------------------------
+hipError_t pool_malloc(void **out, size_t bytes);
+hipError_t pool_free(void *p);
+long long pool_thread_net_bytes();  // pooled bytes this thread has allocated minus freed so far (differences measure a build)
+
+// Device scratch of a host-side driver: any number of allocations, freed when the owner goes out of scope.  (The owners call the
+// pool directly, as the hipMalloc / hipFree macros at the end of this file do: pool.hip sees the same definitions.)
+class Scratch {
+  public:
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { for (void *q : p_) (void)pool_free(q); }
+    // (count ? count : 1) elements of U
+    template <typename U> int alloc(U **out, size_t count) {
+        SMH_HIP(pool_malloc((void **)out, (count ? count : 1) * sizeof(U)));
+        return adopt(*out);
+    }
+    int adopt(void *q) {  // frees q with the rest
+        try {
+            p_.push_back(q);
+        } catch (...) {
+            (void)pool_free(q);
+            return fail(SMH_ERR_OOM, "host allocation failed");
+        }
+        return SMH_OK;
+    }
+    void free_now(const void *q) {  // early free
+        if (!q) return;
+        for (void *&x : p_)
+            if (x == q) { (void)pool_free(x); x = nullptr; }
+    }
+    template <typename U> U *release(U *q) {  // hands q over to the caller
+        for (void *&x : p_)
+            if (x == q) x = nullptr;
+        return q;
+    }
+
+  private:
+    std::vector<void *> p_;
+};
+
+// The arrays of a new CRS matrix, padded like smh_crs_create's: off [n_rows + 1], col / val [nnz + 4].  Freed when the owner goes
+// out of scope unless they were handed over (release; a handle takes them in capi.hip's wrap_arrays).
+struct CrsArrays {
+    uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;
+    CrsArrays() = default;
+    CrsArrays(const CrsArrays &) = delete;
+    CrsArrays &operator=(const CrsArrays &) = delete;
+    CrsArrays(CrsArrays &&o) noexcept { o.release(&off, &col, &val); }
+    CrsArrays &operator=(CrsArrays &&o) noexcept {
+        if (this != &o) {
+            free_all();
+            o.release(&off, &col, &val);
+        }
+        return *this;
+    }
+    ~CrsArrays() { free_all(); }
+    int alloc_off(size_t n_rows) {
+        SMH_HIP(pool_malloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
+        return SMH_OK;
+    }
+    int alloc_entries(size_t nnz, size_t value_bytes) {
+        SMH_HIP(pool_malloc((void **)&col, (nnz + 4) * sizeof(uint32_t)));
+        SMH_HIP(pool_malloc(&val, (nnz + 4) * value_bytes));
+        return SMH_OK;
+    }
+    int alloc(size_t n_rows, size_t nnz, size_t value_bytes) {
+        SMH_TRY(alloc_off(n_rows));
+        return alloc_entries(nnz, value_bytes);
+    }
+    int zero_padding(size_t nnz, size_t value_bytes, hipStream_t s) {  // the 4 entries past nnz
+        SMH_HIP(hipMemsetAsync(col + nnz, 0, 4 * sizeof(uint32_t), s));
+        SMH_HIP(hipMemsetAsync((char *)val + nnz * value_bytes, 0, 4 * value_bytes, s));
+        return SMH_OK;
+    }
+    template <typename V> void release(uint32_t **off_out, uint32_t **col_out, V **val_out) {  // hands the arrays over to the caller
+        *off_out = off; *col_out = col; *val_out = (V *)val;
+        off = col = nullptr;
+        val = nullptr;
+    }
+
+  private:
+    void free_all() {
+        (void)pool_free(off); (void)pool_free(col); (void)pool_free(val);
+        off = col = nullptr;
+        val = nullptr;
+    }
+};
+
+// rocPRIM's two-phase calls: `call` names `tmp` and `bytes`; it is run once to size the temporary storage (bytes ? bytes : 16),
+// then on it; stream s is synchronised before the storage is freed
+#define SMH_ROCPRIM(s, call)                                           \
+    do {                                                               \
+        size_t bytes = 0;                                              \
+        void *tmp = nullptr;                                           \
+        SMH_HIP(call);                                                 \
+        SMH_HIP(::smh::pool_malloc(&tmp, bytes ? bytes : 16));         \
+        const hipError_t e1 = (call);                                  \
+        const hipError_t e2 = hipStreamSynchronize(s);                 \
+        (void)::smh::pool_free(tmp);                                   \
+        SMH_HIP(e1);                                                   \
+        SMH_HIP(e2);                                                   \
+    } while (0)
 
 constexpr int kWave = 64;           // gfx950 wavefront
 constexpr int kBlock = 256;         // 4 waves: one per SIMD
@@ -56,6 +174,26 @@ template <typename T> __device__ __forceinline__ T wave_sum_to_lane63(T v) {
     v = wave_dpp_add<0x143, 0xC>(v);
     return v;
 }
+// the largest value over the wavefront, in every lane
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t w = (uint32_t)__shfl_xor((int)v, o, kWave);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+// blocks of kBlock threads for n items of a grid-stride launch: at least one, at most cap (kBuildGrid: the cap of most build steps)
+constexpr uint64_t kBuildGrid = 16384;
+inline unsigned grid_for(uint64_t n, uint64_t cap) {
+    const uint64_t b = (n + kBlock - 1) / kBlock;
+    return (unsigned)(b == 0 ? 1 : b > cap ? cap : b);
+}
+inline unsigned bits_for(uint64_t v) {  // bits needed to hold v (radix sort key width)
+    unsigned b = 1;
+    while (b < 64 && (v >> b)) ++b;
+    return b;
+}
 constexpr int kMergeItemsPerThread = 8;
 constexpr int kMergeTile = kBlock * kMergeItemsPerThread;  // merge items (rows + nnz) per tile
 constexpr int kReducePartials = 1024;  // blocks of a stage-1 reduction
@@ -67,6 +205,8 @@ constexpr int kStreamCapSmall = 2045;  // K1s: ... when no tile holds more (two 
 constexpr int kStreamCodeWidth = 16384;  // K1s 16-bit column codes: columns per interval (14 bits) x 4 intervals
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
+// in-place exclusive scan of n u32 on the device; *total_out (optional) = their sum (spmv_colblock.hip)
+int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);
 // K1 / SEQ
 int launch_spmv_vector(int dtype, int lanes, const uint32_t *off, const uint32_t *col, const void *val,
                        const void *x, void *y, size_t n_rows, size_t nnz, hipStream_t s);
@@ -162,8 +302,7 @@ struct AddOperand {
 };
 struct AddResult {
     size_t n_rows = 0, n_cols = 0, nnz = 0;
-    uint32_t *off = nullptr, *col = nullptr;  // new arrays (the caller owns them); all null when values_only
-    void *val = nullptr;
+    CrsArrays arrays;          // the new arrays; all null when values_only
     int route = 0;             // smh_last_add_route
     bool values_only = false;  // in_place and no new entry: a's values were updated where they are
 };
@@ -178,8 +317,7 @@ struct UpdMatrix {
 };
 struct UpdResult {
     size_t n_rows = 0, n_cols = 0, nnz = 0;
-    uint32_t *off = nullptr, *col = nullptr;  // new arrays (the caller owns them); all null when values_only
-    void *val = nullptr;
+    CrsArrays arrays;          // the new arrays; all null when values_only
     int route = 0;             // smh_last_apply_route
     bool values_only = false;  // no new entry: m's values were updated where they are
 };
@@ -366,12 +504,7 @@ struct smh_vec {
     bool owns = true;
 };
 
-// ---- device memory goes through the caching layer of pool.hip (see there for why) ---------------------------------------
-namespace smh {
-hipError_t pool_malloc(void **out, size_t bytes);
-hipError_t pool_free(void *p);
-long long pool_thread_net_bytes();  // pooled bytes this thread has allocated minus freed so far (differences measure a build)
-}  // namespace smh
+// ---- every .hip file of the library but pool.hip allocates device memory through the pool (declared at the top) ----------
 #ifndef SMH_POOL_IMPL
 #define hipMalloc(p, n) ::smh::pool_malloc((void **)(p), (n))
 #define hipFree(p) ::smh::pool_free((void *)(p))

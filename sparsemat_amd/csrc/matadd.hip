@@ -30,21 +30,7 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
 constexpr uint32_t kAddShortRow = 64;  // longest row (of a or b) the one-thread-per-row passes take
-
-static unsigned add_grid(uint64_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > 16384) b = 16384;
-    return (unsigned)(b ? b : 1);
-}
-
-static unsigned add_bits_for(uint64_t v) {
-    unsigned b = 1;
-    while (b < 64 && (v >> b)) ++b;
-    return b;
-}
 
 // info words of the count passes
 struct AddInfo {
@@ -56,15 +42,6 @@ struct AddInfo {
 
 // row bounds of an operand with n rows, for any row index (rows past the end are empty)
 __device__ __forceinline__ uint32_t off_at(const uint32_t *__restrict__ off, uint64_t n, uint64_t i) { return off[i < n ? i : n]; }
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t w = (uint32_t)__shfl_xor((int)v, o, kWave);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 __device__ __forceinline__ void info_reduce(AddInfo *info, uint32_t not_same, uint32_t max_new_p1, uint32_t last_b_p1) {
     not_same = wave_max_u32(not_same);
@@ -270,35 +247,11 @@ k_add_merge_emit(const uint32_t *__restrict__ key, const uint32_t *__restrict__ 
 }
 
 // ---- driver ---------------------------------------------------------------------------------------------------------
-struct AddScratch {
-    void *p[12] = {};
-    int n = 0;
-    template <typename U> int alloc(U **out, size_t count) {
-        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
-        p[n++] = *out;
-        return SMH_OK;
-    }
-    ~AddScratch() { for (int i = 0; i < n; ++i) (void)hipFree(p[i]); }
-};
-
-#define SMH_ADD_ROCPRIM(call_with_tmp)                                 \
-    do {                                                               \
-        size_t bytes = 0;                                              \
-        void *tmp = nullptr;                                           \
-        SMH_HIP(call_with_tmp);                                        \
-        SMH_HIP(hipMalloc(&tmp, bytes ? bytes : 16));                  \
-        const hipError_t e1 = (call_with_tmp);                         \
-        const hipError_t e2 = hipStreamSynchronize(s);                 \
-        (void)hipFree(tmp);                                            \
-        SMH_HIP(e1);                                                   \
-        SMH_HIP(e2);                                                   \
-    } while (0)
-
 template <typename T, bool SUB>
 static int add_t(const AddOperand &a, const AddOperand &b, bool in_place, bool alias, bool force_general, AddResult *res, hipStream_t s) {
     const uint64_t n_rows_max = a.n_rows > b.n_rows ? a.n_rows : b.n_rows;
     const bool short_rows = !force_general && a.max_row_len <= kAddShortRow && b.max_row_len <= kAddShortRow;
-    AddScratch scr;
+    Scratch scr;
     AddInfo *d_info = nullptr, h_info;
     uint32_t *nb = nullptr;  // new entries before each row: n_rows_max + 1
     SMH_TRY(scr.alloc(&d_info, 1));
@@ -309,7 +262,7 @@ static int add_t(const AddOperand &a, const AddOperand &b, bool in_place, bool a
     uint32_t *key = nullptr, *src = nullptr, *m_off = nullptr, *m_row = nullptr, *fs = nullptr;
     uint64_t n_m = 0;
     if (short_rows) {
-        hipLaunchKernelGGL(k_add_count, dim3(add_grid(n_rows_max)), dim3(kBlock), 0, s, a.off, a.col, (uint64_t)a.n_rows, b.off, b.col,
+        hipLaunchKernelGGL(k_add_count, dim3(grid_for(n_rows_max, kBuildGrid)), dim3(kBlock), 0, s, a.off, a.col, (uint64_t)a.n_rows, b.off, b.col,
                            (uint64_t)b.n_rows, n_rows_max, nb, d_info);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemsetAsync(nb + n_rows_max, 0, sizeof(uint32_t), s));
@@ -325,7 +278,7 @@ static int add_t(const AddOperand &a, const AddOperand &b, bool in_place, bool a
         SMH_TRY(scr.alloc(&m_off, n_rows_max + 1));
         SMH_TRY(scr.alloc(&m_row, n_m));
         SMH_TRY(scr.alloc(&fs, (uint64_t)b.nnz + 1));
-        hipLaunchKernelGGL(k_add_merge_offsets, dim3(add_grid(n_rows_max + 1)), dim3(kBlock), 0, s, a.off, (uint64_t)a.n_rows, b.off,
+        hipLaunchKernelGGL(k_add_merge_offsets, dim3(grid_for(n_rows_max + 1, kBuildGrid)), dim3(kBlock), 0, s, a.off, (uint64_t)a.n_rows, b.off,
                            (uint64_t)b.n_rows, n_rows_max, m_off);
         SMH_HIP(hipGetLastError());
         // rows of the operands' entries: m_row doubles as a's, key as b's (both rewritten below)
@@ -333,21 +286,21 @@ static int add_t(const AddOperand &a, const AddOperand &b, bool in_place, bool a
         rows_b = key;
         SMH_TRY(expand_rows(a.off, a.n_rows, rows_a, s));
         SMH_TRY(expand_rows(b.off, b.n_rows, rows_b, s));
-        hipLaunchKernelGGL(k_add_merge_fill, dim3(add_grid(a.nnz)), dim3(kBlock), 0, s, a.col, rows_a, (uint64_t)a.nnz, b.off, (uint64_t)b.n_rows,
+        hipLaunchKernelGGL(k_add_merge_fill, dim3(grid_for(a.nnz, kBuildGrid)), dim3(kBlock), 0, s, a.col, rows_a, (uint64_t)a.nnz, b.off, (uint64_t)b.n_rows,
                            false, (uint32_t)a.nnz, key_in, src_in);
         SMH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_add_merge_fill, dim3(add_grid(b.nnz)), dim3(kBlock), 0, s, b.col, rows_b, (uint64_t)b.nnz, a.off, (uint64_t)a.n_rows,
+        hipLaunchKernelGGL(k_add_merge_fill, dim3(grid_for(b.nnz, kBuildGrid)), dim3(kBlock), 0, s, b.col, rows_b, (uint64_t)b.nnz, a.off, (uint64_t)a.n_rows,
                            true, (uint32_t)a.nnz, key_in, src_in);
         SMH_HIP(hipGetLastError());
         const uint32_t max_col = a.max_col > b.max_col ? a.max_col : b.max_col;
-        SMH_ADD_ROCPRIM(rocprim::segmented_radix_sort_pairs(tmp, bytes, key_in, key, src_in, src, (unsigned)n_m, (unsigned)n_rows_max, m_off,
-                                                            m_off + 1, 0u, add_bits_for(max_col), s));
+        SMH_ROCPRIM(s, rocprim::segmented_radix_sort_pairs(tmp, bytes, key_in, key, src_in, src, (unsigned)n_m, (unsigned)n_rows_max, m_off,
+                                                           m_off + 1, 0u, bits_for(max_col), s));
         SMH_TRY(expand_rows(m_off, n_rows_max, m_row, s));
         SMH_HIP(hipMemsetAsync(fs, 0, ((uint64_t)b.nnz + 1) * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_add_merge_flags, dim3(add_grid(n_m)), dim3(kBlock), 0, s, key, src, m_off, m_row, n_m, (uint32_t)a.nnz, fs, d_info);
+        hipLaunchKernelGGL(k_add_merge_flags, dim3(grid_for(n_m, kBuildGrid)), dim3(kBlock), 0, s, key, src, m_off, m_row, n_m, (uint32_t)a.nnz, fs, d_info);
         SMH_HIP(hipGetLastError());
         SMH_TRY(device_exclusive_scan_u32(fs, (uint64_t)b.nnz + 1, s, &n_new));
-        hipLaunchKernelGGL(k_add_rows_from_flags, dim3(add_grid(n_rows_max + 1)), dim3(kBlock), 0, s, b.off, (uint64_t)b.n_rows, fs, n_rows_max, nb);
+        hipLaunchKernelGGL(k_add_rows_from_flags, dim3(grid_for(n_rows_max + 1, kBuildGrid)), dim3(kBlock), 0, s, b.off, (uint64_t)b.n_rows, fs, n_rows_max, nb);
         SMH_HIP(hipGetLastError());
     }
     SMH_HIP(hipMemcpyAsync(&h_info, d_info, sizeof h_info, hipMemcpyDeviceToHost, s));
@@ -370,42 +323,29 @@ static int add_t(const AddOperand &a, const AddOperand &b, bool in_place, bool a
         SMH_HIP(hipMemcpyAsync(snap, b.val, (size_t)b.nnz * sizeof(T), hipMemcpyDeviceToDevice, s));
         b_val = snap;
     }
-    uint32_t *r_off = nullptr, *r_col = nullptr;
-    T *r_val = nullptr;
-    if (res->values_only) {
-        r_val = (T *)a.val;
-    } else {
-        int rc = SMH_OK;
-        auto alloc_out = [&]() -> int {
-            SMH_HIP(hipMalloc((void **)&r_off, (n_rows + 1) * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc((void **)&r_col, (nnz + 4) * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc((void **)&r_val, (nnz + 4) * sizeof(T)));
-            return SMH_OK;
-        };
-        rc = alloc_out();
-        if (rc != SMH_OK) { (void)hipFree(r_off); (void)hipFree(r_col); (void)hipFree(r_val); return rc; }
-        res->off = r_off; res->col = r_col; res->val = r_val;  // owned by the caller from here on
-    }
+    if (!res->values_only) SMH_TRY(res->arrays.alloc(n_rows, nnz, sizeof(T)));  // (freed with res unless the caller takes them)
+    uint32_t *r_off = res->arrays.off, *r_col = res->arrays.col;
+    T *r_val = res->values_only ? (T *)a.val : (T *)res->arrays.val;
     if (same) {
         if (!res->values_only) {
             SMH_HIP(hipMemcpyAsync(r_off, a.off, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
             if (nnz) SMH_HIP(hipMemcpyAsync(r_col, a.col, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         }
         if (nnz) {
-            hipLaunchKernelGGL((k_add_same<T, SUB>), dim3(add_grid((nnz + 16 / sizeof(T) - 1) / (16 / sizeof(T)))), dim3(kBlock), 0, s,
+            hipLaunchKernelGGL((k_add_same<T, SUB>), dim3(grid_for((nnz + 16 / sizeof(T) - 1) / (16 / sizeof(T)), kBuildGrid)), dim3(kBlock), 0, s,
                                (const T *)a.val, b_val, r_val, nnz);
             SMH_HIP(hipGetLastError());
         }
     } else {
         if (!res->values_only) {
-            hipLaunchKernelGGL(k_add_offsets, dim3(add_grid(n_rows + 1)), dim3(kBlock), 0, s, a.off, (uint64_t)a.n_rows, nb, n_rows, r_off);
+            hipLaunchKernelGGL(k_add_offsets, dim3(grid_for(n_rows + 1, kBuildGrid)), dim3(kBlock), 0, s, a.off, (uint64_t)a.n_rows, nb, n_rows, r_off);
             SMH_HIP(hipGetLastError());
         }
         if (short_rows) {
-            hipLaunchKernelGGL((k_add_emit_rows<T, SUB>), dim3(add_grid(n_rows)), dim3(kBlock), 0, s, a.off, a.col, (const T *)a.val,
+            hipLaunchKernelGGL((k_add_emit_rows<T, SUB>), dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, a.off, a.col, (const T *)a.val,
                                (uint64_t)a.n_rows, b.off, b.col, b_val, (uint64_t)b.n_rows, n_rows, nb, r_col, r_val, res->values_only);
         } else {
-            hipLaunchKernelGGL((k_add_merge_emit<T, SUB>), dim3(add_grid(n_m)), dim3(kBlock), 0, s, key, src, m_off, m_row, n_m, a.off,
+            hipLaunchKernelGGL((k_add_merge_emit<T, SUB>), dim3(grid_for(n_m, kBuildGrid)), dim3(kBlock), 0, s, key, src, m_off, m_row, n_m, a.off,
                                (uint64_t)a.n_rows, (const T *)a.val, (uint32_t)a.nnz, b.off, (uint64_t)b.n_rows, b_val, fs, nb, r_col, r_val,
                                res->values_only);
         }

@@ -26,14 +26,6 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
-static unsigned mat_grid(uint64_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > 16384) b = 16384;
-    return (unsigned)(b ? b : 1);
-}
-
 // ---- predicates ------------------------------------------------------------------------------------------------
 // is_sorted (sparsematrix.rs:251-271): no column smaller than its predecessor in the row
 __global__ void __launch_bounds__(kBlock)
@@ -79,44 +71,36 @@ k_is_symmetric(const uint32_t *__restrict__ off, const uint32_t *__restrict__ co
 }
 
 int crs_is_sorted(const uint32_t *off, const uint32_t *col, size_t n_rows, int *out, hipStream_t s) {
+    Scratch scr;
     uint32_t *flag = nullptr, h = 1;
-    SMH_HIP(hipMalloc((void **)&flag, sizeof(uint32_t)));
-    auto go = [&]() -> int {
-        SMH_HIP(hipMemcpyAsync(flag, &h, sizeof h, hipMemcpyHostToDevice, s));
-        if (n_rows) hipLaunchKernelGGL(k_is_sorted, dim3(mat_grid(n_rows)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, flag);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, s));
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = go();
-    (void)hipFree(flag);
+    SMH_TRY(scr.alloc(&flag, 1));
+    SMH_HIP(hipMemcpyAsync(flag, &h, sizeof h, hipMemcpyHostToDevice, s));
+    if (n_rows) hipLaunchKernelGGL(k_is_sorted, dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, flag);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
     *out = (int)h;
-    return rc;
+    return SMH_OK;
 }
 
 int crs_is_symmetric(int dtype, const uint32_t *off, const uint32_t *col, const void *val, size_t n_rows, int *out, hipStream_t s) {
+    Scratch scr;
     uint32_t *flag = nullptr, h = 1;
-    SMH_HIP(hipMalloc((void **)&flag, sizeof(uint32_t)));
-    auto go = [&]() -> int {
-        SMH_HIP(hipMemcpyAsync(flag, &h, sizeof h, hipMemcpyHostToDevice, s));
-        if (n_rows) {
-            if (dtype == SMH_F64)
-                hipLaunchKernelGGL((k_is_symmetric<double>), dim3(mat_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const double *)val,
-                                   (uint64_t)n_rows, flag);
-            else
-                hipLaunchKernelGGL((k_is_symmetric<float>), dim3(mat_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const float *)val,
-                                   (uint64_t)n_rows, flag);
-        }
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, s));
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = go();
-    (void)hipFree(flag);
+    SMH_TRY(scr.alloc(&flag, 1));
+    SMH_HIP(hipMemcpyAsync(flag, &h, sizeof h, hipMemcpyHostToDevice, s));
+    if (n_rows) {
+        if (dtype == SMH_F64)
+            hipLaunchKernelGGL((k_is_symmetric<double>), dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, off, col, (const double *)val,
+                               (uint64_t)n_rows, flag);
+        else
+            hipLaunchKernelGGL((k_is_symmetric<float>), dim3(grid_for(n_rows, kBuildGrid)), dim3(kBlock), 0, s, off, col, (const float *)val,
+                               (uint64_t)n_rows, flag);
+    }
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(&h, flag, sizeof h, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
     *out = (int)h;
-    return rc;
+    return SMH_OK;
 }
 
 // ---- prod ------------------------------------------------------------------------------------------------------
@@ -234,20 +218,6 @@ k_prod_compact(const uint32_t *__restrict__ off, const uint32_t *__restrict__ co
     }
 }
 
-struct DevBufs {  // device buffers freed on scope exit
-    std::vector<void *> p;
-    template <typename U> int alloc(U **out, size_t count) {
-        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
-        p.push_back(*out);
-        return SMH_OK;
-    }
-    void release(void *q) {
-        for (auto &x : p)
-            if (x == q) { (void)hipFree(x); x = nullptr; }
-    }
-    ~DevBufs() { for (void *x : p) (void)hipFree(x); }
-};
-
 template <typename T>
 static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, size_t a_rows, size_t a_nnz, uint32_t a_max_col,
                   const uint32_t *b_off, const uint32_t *b_col, const T *b_val, size_t b_rows, size_t *n_rows_out, size_t *n_cols_out,
@@ -264,7 +234,7 @@ static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, 
         fprintf(stderr, "[prod] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
     };
-    DevBufs bufs;
+    Scratch bufs;
     *n_rows_out = *n_cols_out = *nnz_out = 0;
     *off_out = *col_out = nullptr;
     *val_out = nullptr;
@@ -293,9 +263,9 @@ static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, 
     SMH_HIP(hipMemsetAsync(kept, 0, (a_rows + 1) * sizeof(uint32_t), s));
     SMH_HIP(hipMemsetAsync(dims, 0, 2 * sizeof(uint32_t), s));
     SMH_TRY(expand_rows(a_off, a_rows, row_of, s));
-    if (a_nnz) hipLaunchKernelGGL(k_prod_counts, dim3(mat_grid(a_nnz)), dim3(kBlock), 0, s, as_col, (uint64_t)a_nnz, b_off, (uint64_t)b_rows, cnt);
+    if (a_nnz) hipLaunchKernelGGL(k_prod_counts, dim3(grid_for(a_nnz, kBuildGrid)), dim3(kBlock), 0, s, as_col, (uint64_t)a_nnz, b_off, (uint64_t)b_rows, cnt);
     SMH_HIP(hipGetLastError());
-    if (a_rows) hipLaunchKernelGGL(k_prod_row_sums, dim3(mat_grid(a_rows)), dim3(kBlock), 0, s, a_off, cnt, (uint64_t)a_rows, row_sum);
+    if (a_rows) hipLaunchKernelGGL(k_prod_row_sums, dim3(grid_for(a_rows, kBuildGrid)), dim3(kBlock), 0, s, a_off, cnt, (uint64_t)a_rows, row_sum);
     SMH_HIP(hipGetLastError());
     // products per row on the host (4 bytes a row, no zero-filled staging); the entry offsets of the few batch borders are
     // fetched one by one below
@@ -303,7 +273,7 @@ static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, 
     if (!h_sum) return fail(SMH_ERR_OOM, "host allocation failed");
     if (a_rows) SMH_HIP(hipMemcpyAsync(h_sum.get(), row_sum, a_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     SMH_HIP(hipStreamSynchronize(s));
-    bufs.release(row_sum);
+    bufs.free_now(row_sum);
     lap("sorted check, counts, row sums");
     // batches of whole rows with at most `budget` products (a longer single row goes alone)
     struct Batch { size_t r0, r1; uint64_t products; uint32_t e0, e1; };
@@ -340,79 +310,69 @@ static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, 
         uint64_t products = 0;
         SMH_TRY(device_exclusive_scan_u32(base, n_e + 1, s, &products));
         if (products != bt.products) return fail(SMH_ERR_INVALID, "prod: product count changed between passes");
-        hipLaunchKernelGGL((k_prod_expand<T>), dim3(mat_grid(n_e)), dim3(kBlock), 0, s, e0, n_e, row_of, a_off, as_col, as_val, b_off, b_col,
+        hipLaunchKernelGGL((k_prod_expand<T>), dim3(grid_for(n_e, kBuildGrid)), dim3(kBlock), 0, s, e0, n_e, row_of, a_off, as_col, as_val, b_off, b_col,
                            b_val, (uint64_t)b_rows, base, (uint32_t)bt.r0, p_row, p_col, p_val);
         SMH_HIP(hipGetLastError());
         lap("expand");
         size_t nr = 0, nc = 0, nnz_b = 0;
-        uint32_t *off_b = nullptr, *col_b = nullptr;
-        void *val_b = nullptr;
-        SMH_TRY(assemble_triplets(dtype, products, p_row, p_col, p_val, nullptr, false, false, false, &nr, &nc, &nnz_b, &off_b, &col_b, &val_b, s));
-        bufs.p.push_back(off_b); bufs.p.push_back(col_b); bufs.p.push_back(val_b);
+        CrsArrays folded;  // (this batch's, freed at the end of the iteration)
+        SMH_TRY(assemble_triplets(dtype, products, p_row, p_col, p_val, nullptr, false, false, false, &nr, &nc, &nnz_b, &folded.off, &folded.col,
+                                  &folded.val, s));
+        const uint32_t *off_b = folded.off;
+        uint32_t *col_b = folded.col;
+        void *val_b = folded.val;
         lap("fold (assembly)");
         SMH_TRY(sort_rows(dtype, off_b, col_b, val_b, nr, nnz_b, (uint32_t)(nc ? nc - 1 : 0), s));
         lap("sort rows by column");
         uint32_t *rank = nullptr;
         SMH_TRY(bufs.alloc(&rank, nnz_b + 1));
-        hipLaunchKernelGGL((k_prod_flags<T>), dim3(mat_grid(nnz_b + 1)), dim3(kBlock), 0, s, (const T *)val_b, (uint64_t)nnz_b, rank);
+        hipLaunchKernelGGL((k_prod_flags<T>), dim3(grid_for(nnz_b + 1, kBuildGrid)), dim3(kBlock), 0, s, (const T *)val_b, (uint64_t)nnz_b, rank);
         SMH_HIP(hipGetLastError());
         uint64_t n_kept = 0;
         SMH_TRY(device_exclusive_scan_u32(rank, nnz_b + 1, s, &n_kept));
-        hipLaunchKernelGGL(k_prod_row_kept, dim3(mat_grid(nr)), dim3(kBlock), 0, s, off_b, rank, (uint64_t)nr, kept + bt.r0);
+        hipLaunchKernelGGL(k_prod_row_kept, dim3(grid_for(nr, kBuildGrid)), dim3(kBlock), 0, s, off_b, rank, (uint64_t)nr, kept + bt.r0);
         SMH_HIP(hipGetLastError());
         Piece pc{nullptr, nullptr, n_kept};
         if (n_kept) {
             SMH_TRY(bufs.alloc(&pc.col, n_kept));
             SMH_TRY(bufs.alloc(&pc.val, n_kept));
-            hipLaunchKernelGGL((k_prod_compact<T>), dim3(mat_grid(nr)), dim3(kBlock), 0, s, off_b, col_b, (const T *)val_b, (uint64_t)nr, rank,
+            hipLaunchKernelGGL((k_prod_compact<T>), dim3(grid_for(nr, kBuildGrid)), dim3(kBlock), 0, s, off_b, col_b, (const T *)val_b, (uint64_t)nr, rank,
                                (uint32_t)bt.r0, pc.col, pc.val, dims);
             SMH_HIP(hipGetLastError());
             pieces.push_back(pc);
             total += n_kept;
         }
         SMH_HIP(hipStreamSynchronize(s));
-        bufs.release(off_b); bufs.release(col_b); bufs.release(val_b); bufs.release(rank);
+        bufs.free_now(rank);
         lap("drop zeros, reverse");
     }
     if (total >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
     uint32_t h_dims[2] = {0, 0};
     SMH_HIP(hipMemcpyAsync(h_dims, dims, sizeof h_dims, hipMemcpyDeviceToHost, s));
     SMH_HIP(hipStreamSynchronize(s));
-    // result arrays (owned by the caller, padded like smh_crs_create's)
+    // the result (padded like smh_crs_create's) goes to the caller when every step succeeded
     const bool rowless = total <= 1;  // no set call at all, or the single push that leaves n_rows == 0
     const size_t n_rows = rowless ? 0 : h_dims[0], nnz = rowless ? 0 : (size_t)total;
-    uint32_t *off = nullptr, *col = nullptr;
-    T *val = nullptr;
-    auto finish = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&off, (n_rows + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&col, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&val, (nnz + 4) * sizeof(T)));
-        SMH_HIP(hipMemsetAsync(col + nnz, 0, 4 * sizeof(uint32_t), s));
-        SMH_HIP(hipMemsetAsync(val + nnz, 0, 4 * sizeof(T), s));
-        if (rowless) {
-            SMH_HIP(hipMemsetAsync(off, 0, sizeof(uint32_t), s));
-        } else {
-            uint64_t check = 0;
-            SMH_TRY(device_exclusive_scan_u32(kept, a_rows + 1, s, &check));  // kept[a_rows] == 0: offsets of all rows
-            if (check != total) return fail(SMH_ERR_INVALID, "prod: kept-entry count changed between passes");
-            SMH_HIP(hipMemcpyAsync(off, kept, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            uint64_t at = 0;
-            for (const Piece &pc : pieces) {
-                SMH_HIP(hipMemcpyAsync(col + at, pc.col, pc.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                SMH_HIP(hipMemcpyAsync(val + at, pc.val, pc.n * sizeof(T), hipMemcpyDeviceToDevice, s));
-                at += pc.n;
-            }
+    CrsArrays res;
+    SMH_TRY(res.alloc(n_rows, nnz, sizeof(T)));
+    SMH_TRY(res.zero_padding(nnz, sizeof(T), s));
+    if (rowless) {
+        SMH_HIP(hipMemsetAsync(res.off, 0, sizeof(uint32_t), s));
+    } else {
+        uint64_t check = 0;
+        SMH_TRY(device_exclusive_scan_u32(kept, a_rows + 1, s, &check));  // kept[a_rows] == 0: offsets of all rows
+        if (check != total) return fail(SMH_ERR_INVALID, "prod: kept-entry count changed between passes");
+        SMH_HIP(hipMemcpyAsync(res.off, kept, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        uint64_t at = 0;
+        for (const Piece &pc : pieces) {
+            SMH_HIP(hipMemcpyAsync(res.col + at, pc.col, pc.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            SMH_HIP(hipMemcpyAsync((T *)res.val + at, pc.val, pc.n * sizeof(T), hipMemcpyDeviceToDevice, s));
+            at += pc.n;
         }
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = finish();
-    if (rc != SMH_OK) {
-        (void)hipFree(off); (void)hipFree(col); (void)hipFree(val);
-        return rc;
     }
+    SMH_HIP(hipStreamSynchronize(s));
     *n_rows_out = n_rows; *n_cols_out = total ? h_dims[1] : 0; *nnz_out = nnz;
-    *off_out = off; *col_out = col; *val_out = val;
+    res.release(off_out, col_out, val_out);
     return SMH_OK;
 }
 

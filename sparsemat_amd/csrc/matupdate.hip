@@ -29,22 +29,8 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
 constexpr uint32_t kUpdShortRow = 64;      // longest row of m the one-thread-per-operation lookup takes
 constexpr uint32_t kAbsent = 0xFFFFFFFFu;  // lookup: no entry of the row has the column
-
-static unsigned upd_grid(uint64_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > 16384) b = 16384;
-    return (unsigned)(b ? b : 1);
-}
-
-static unsigned upd_bits_for(uint64_t v) {
-    unsigned b = 1;
-    while (b < 64 && (v >> b)) ++b;
-    return b;
-}
 
 struct UpdInfo {
     uint32_t n_absent;     // operations without a target in m
@@ -53,14 +39,6 @@ struct UpdInfo {
     uint32_t pad;
 };
 
-__device__ __forceinline__ uint32_t upd_wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t w = (uint32_t)__shfl_xor((int)v, o, kWave);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 __device__ __forceinline__ uint32_t upd_wave_sum(uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
@@ -117,8 +95,8 @@ k_upd_lookup(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
     }
     if constexpr (!VALUES) {
         n_absent = upd_wave_sum(n_absent);
-        max_row = upd_wave_max(max_row);
-        max_new_col = upd_wave_max(max_new_col);
+        max_row = wave_max_u32(max_row);
+        max_new_col = wave_max_u32(max_new_col);
         if ((threadIdx.x & (kWave - 1)) == 0) {
             if (n_absent) atomicAdd(&info->n_absent, n_absent);
             atomicMax(&info->max_row, max_row);
@@ -132,7 +110,7 @@ static int launch_lookup(uint32_t max_row_len, const uint32_t *off, const uint32
                          const uint32_t *q_col, uint64_t n, uint32_t *idx_out, T *val_out, UpdInfo *info, hipStream_t s) {
     // lane groups sized from the longest row (as K1 sizes its sub-wave groups): one thread per query on short rows
     const int g = max_row_len <= kUpdShortRow ? 1 : max_row_len <= 512 ? 8 : 32;
-    const unsigned grid = upd_grid(n * (uint64_t)g);
+    const unsigned grid = grid_for(n * (uint64_t)g, kBuildGrid);
     if (g == 1)
         hipLaunchKernelGGL((k_upd_lookup<1, T, VALUES>), dim3(grid), dim3(kBlock), 0, s, off, col, val, n_rows, q_row, q_col, n, idx_out, val_out, info);
     else if (g == 8)
@@ -282,35 +260,11 @@ k_upd_emit_new(const uint64_t *__restrict__ hkey, const uint32_t *__restrict__ h
 }
 
 // ---- driver ----------------------------------------------------------------------------------------------------------------
-struct UpdScratch {
-    void *p[20] = {};
-    int n = 0;
-    template <typename U> int alloc(U **out, size_t count) {
-        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
-        p[n++] = *out;
-        return SMH_OK;
-    }
-    ~UpdScratch() { for (int i = 0; i < n; ++i) (void)hipFree(p[i]); }
-};
-
-#define SMH_UPD_ROCPRIM(call_with_tmp)                                 \
-    do {                                                               \
-        size_t bytes = 0;                                              \
-        void *tmp = nullptr;                                           \
-        SMH_HIP(call_with_tmp);                                        \
-        SMH_HIP(hipMalloc(&tmp, bytes ? bytes : 16));                  \
-        const hipError_t e1 = (call_with_tmp);                         \
-        const hipError_t e2 = hipStreamSynchronize(s);                 \
-        (void)hipFree(tmp);                                            \
-        SMH_HIP(e1);                                                   \
-        SMH_HIP(e2);                                                   \
-    } while (0)
-
 // stable sort of (target, operation) pairs by target, bits [0, bits)
 template <typename P>
 static int sort_by_target(uint32_t *key_in, uint32_t *key_out, P *src_in, P *src_out, uint64_t n, unsigned bits, hipStream_t s) {
     if (n == 0) return SMH_OK;
-    SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, key_in, key_out, src_in, src_out, (size_t)n, 0u, bits, s));
+    SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, key_in, key_out, src_in, src_out, (size_t)n, 0u, bits, s));
     return SMH_OK;
 }
 
@@ -330,7 +284,7 @@ int crs_get_many(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, 
 template <typename T>
 static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const uint32_t *cols, const T *vals, const uint8_t *ops, bool force_general,
                    UpdResult *res, hipStream_t s) {
-    UpdScratch scr;
+    Scratch scr;
     UpdInfo *d_info = nullptr, h_info;
     uint32_t *tgt = nullptr;
     SMH_TRY(scr.alloc(&d_info, 1));
@@ -341,7 +295,7 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     SMH_HIP(hipStreamSynchronize(s));
     const uint64_t n_rows = (uint64_t)h_info.max_row + 1 > m.n_rows ? (uint64_t)h_info.max_row + 1 : m.n_rows;
     if (n_rows >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "n_rows does not fit the u32 index type");
-    const unsigned tbits = upd_bits_for(m.nnz);
+    const unsigned tbits = bits_for(m.nnz);
     if (h_info.n_absent == 0 && !force_general) {
         // 2. values only: sort by target, fold in place
         res->route = 1;
@@ -351,10 +305,10 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
         SMH_TRY(scr.alloc(&key, n));
         SMH_TRY(scr.alloc(&src_in, n));
         SMH_TRY(scr.alloc(&src, n));
-        hipLaunchKernelGGL((k_upd_payload<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, vals, ops, n, src_in);
+        hipLaunchKernelGGL((k_upd_payload<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, vals, ops, n, src_in);
         SMH_HIP(hipGetLastError());
         SMH_TRY(sort_by_target(tgt, key, src_in, src, n, tbits, s));
-        hipLaunchKernelGGL((k_upd_fold<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, key, (const UpdOp<T> *)src, n, (const T *)m.val, (T *)m.val,
+        hipLaunchKernelGGL((k_upd_fold<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, key, (const UpdOp<T> *)src, n, (const T *)m.val, (T *)m.val,
                            (const uint32_t *)nullptr);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipStreamSynchronize(s));
@@ -367,7 +321,7 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     UpdOp<T> *psrc_in = nullptr, *psrc = nullptr;
     uint64_t *akey_in = nullptr, *akey = nullptr;
     SMH_TRY(scr.alloc(&pos, n + 1));
-    hipLaunchKernelGGL(k_upd_absent_flags, dim3(upd_grid(n)), dim3(kBlock), 0, s, tgt, n, pos);
+    hipLaunchKernelGGL(k_upd_absent_flags, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, tgt, n, pos);
     SMH_HIP(hipGetLastError());
     SMH_HIP(hipMemsetAsync(pos + n, 0, sizeof(uint32_t), s));
     uint64_t total = 0;
@@ -380,13 +334,13 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     SMH_TRY(scr.alloc(&asrc_in, n_absent));
     SMH_TRY(scr.alloc(&akey, n_absent));
     SMH_TRY(scr.alloc(&asrc, n_absent));
-    const unsigned cbits = upd_bits_for(h_info.max_new_col), rbits = upd_bits_for(h_info.max_row), kbits = upd_bits_for(n);
-    hipLaunchKernelGGL((k_upd_split<T>), dim3(upd_grid(n)), dim3(kBlock), 0, s, tgt, rows, cols, vals, ops, n, pos, cbits, pkey_in, psrc_in, akey_in,
+    const unsigned cbits = bits_for(h_info.max_new_col), rbits = bits_for(h_info.max_row), kbits = bits_for(n);
+    hipLaunchKernelGGL((k_upd_split<T>), dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, tgt, rows, cols, vals, ops, n, pos, cbits, pkey_in, psrc_in, akey_in,
                        asrc_in);
     SMH_HIP(hipGetLastError());
     SMH_TRY(sort_by_target(pkey_in, pkey, psrc_in, psrc, n_present, tbits, s));
     if (n_absent)
-        SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, akey_in, akey, asrc_in, asrc, (size_t)n_absent, 0u, rbits + cbits, s));
+        SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, akey_in, akey, asrc_in, asrc, (size_t)n_absent, 0u, rbits + cbits, s));
     // new entries: heads of the (row, column) runs, sorted by (row, first appearance)
     uint32_t *hpos = nullptr, *hsrc_in = nullptr, *hsrc = nullptr, *nb = nullptr;
     uint64_t *hkey_in = nullptr, *hkey = nullptr, n_new = 0;
@@ -394,7 +348,7 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     SMH_TRY(scr.alloc(&nb, n_rows + 1));
     SMH_HIP(hipMemsetAsync(nb, 0, (n_rows + 1) * sizeof(uint32_t), s));
     if (n_absent) {
-        hipLaunchKernelGGL(k_upd_head_flags, dim3(upd_grid(n_absent)), dim3(kBlock), 0, s, akey, n_absent, hpos);
+        hipLaunchKernelGGL(k_upd_head_flags, dim3(grid_for(n_absent, kBuildGrid)), dim3(kBlock), 0, s, akey, n_absent, hpos);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemsetAsync(hpos + n_absent, 0, sizeof(uint32_t), s));
         SMH_TRY(device_exclusive_scan_u32(hpos, n_absent + 1, s, &n_new));
@@ -402,10 +356,10 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
         SMH_TRY(scr.alloc(&hkey, n_new));
         SMH_TRY(scr.alloc(&hsrc_in, n_new));
         SMH_TRY(scr.alloc(&hsrc, n_new));
-        hipLaunchKernelGGL(k_upd_heads, dim3(upd_grid(n_absent)), dim3(kBlock), 0, s, akey, asrc, n_absent, hpos, cbits, kbits, hkey_in, hsrc_in);
+        hipLaunchKernelGGL(k_upd_heads, dim3(grid_for(n_absent, kBuildGrid)), dim3(kBlock), 0, s, akey, asrc, n_absent, hpos, cbits, kbits, hkey_in, hsrc_in);
         SMH_HIP(hipGetLastError());
-        SMH_UPD_ROCPRIM(rocprim::radix_sort_pairs(tmp, bytes, hkey_in, hkey, hsrc_in, hsrc, (size_t)n_new, 0u, rbits + kbits, s));
-        hipLaunchKernelGGL(k_upd_count_rows, dim3(upd_grid(n_new)), dim3(kBlock), 0, s, hkey, n_new, kbits, nb);
+        SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, hkey_in, hkey, hsrc_in, hsrc, (size_t)n_new, 0u, rbits + kbits, s));
+        hipLaunchKernelGGL(k_upd_count_rows, dim3(grid_for(n_new, kBuildGrid)), dim3(kBlock), 0, s, hkey, n_new, kbits, nb);
         SMH_HIP(hipGetLastError());
     }
     uint64_t n_new2 = 0;
@@ -421,31 +375,23 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     uint32_t *rows_newpos = nullptr;
     SMH_TRY(scr.alloc(&rows_newpos, m.nnz));
     SMH_TRY(expand_rows(m.off, m.n_rows, rows_newpos, s));
-    uint32_t *r_off = nullptr, *r_col = nullptr;
-    T *r_val = nullptr;
-    auto alloc_out = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&r_off, (n_rows + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&r_col, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&r_val, (nnz + 4) * sizeof(T)));
-        return SMH_OK;
-    };
-    const int rc = alloc_out();
-    if (rc != SMH_OK) { (void)hipFree(r_off); (void)hipFree(r_col); (void)hipFree(r_val); return rc; }
-    res->off = r_off; res->col = r_col; res->val = r_val;  // owned by the caller from here on
-    hipLaunchKernelGGL(k_upd_offsets, dim3(upd_grid(n_rows + 1)), dim3(kBlock), 0, s, m.off, (uint64_t)m.n_rows, nb, n_rows, r_off);
+    SMH_TRY(res->arrays.alloc(n_rows, nnz, sizeof(T)));  // (freed with res unless the caller takes them)
+    uint32_t *r_off = res->arrays.off, *r_col = res->arrays.col;
+    T *r_val = (T *)res->arrays.val;
+    hipLaunchKernelGGL(k_upd_offsets, dim3(grid_for(n_rows + 1, kBuildGrid)), dim3(kBlock), 0, s, m.off, (uint64_t)m.n_rows, nb, n_rows, r_off);
     SMH_HIP(hipGetLastError());
     if (m.nnz) {
-        hipLaunchKernelGGL((k_upd_move_old<T>), dim3(upd_grid(m.nnz)), dim3(kBlock), 0, s, m.off, m.col, (const T *)m.val, (uint64_t)m.nnz, nb, r_off,
+        hipLaunchKernelGGL((k_upd_move_old<T>), dim3(grid_for(m.nnz, kBuildGrid)), dim3(kBlock), 0, s, m.off, m.col, (const T *)m.val, (uint64_t)m.nnz, nb, r_off,
                            rows_newpos, r_col, r_val);
         SMH_HIP(hipGetLastError());
     }
     if (n_new) {
-        hipLaunchKernelGGL((k_upd_emit_new<T>), dim3(upd_grid(n_new)), dim3(kBlock), 0, s, hkey, hsrc, n_new, kbits, akey, asrc, n_absent,
+        hipLaunchKernelGGL((k_upd_emit_new<T>), dim3(grid_for(n_new, kBuildGrid)), dim3(kBlock), 0, s, hkey, hsrc, n_new, kbits, akey, asrc, n_absent,
                            (cbits >= 64 ? ~0ull : ((1ull << cbits) - 1)), vals, ops, nb, r_off, r_col, r_val);
         SMH_HIP(hipGetLastError());
     }
     if (n_present) {
-        hipLaunchKernelGGL((k_upd_fold<T>), dim3(upd_grid(n_present)), dim3(kBlock), 0, s, pkey, (const UpdOp<T> *)psrc, n_present, (const T *)m.val, r_val,
+        hipLaunchKernelGGL((k_upd_fold<T>), dim3(grid_for(n_present, kBuildGrid)), dim3(kBlock), 0, s, pkey, (const UpdOp<T> *)psrc, n_present, (const T *)m.val, r_val,
                            (const uint32_t *)rows_newpos);
         SMH_HIP(hipGetLastError());
     }
@@ -473,8 +419,8 @@ __global__ void __launch_bounds__(kBlock) k_upd_eye(uint32_t *__restrict__ off, 
 }
 
 int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hipStream_t s) {
-    if (dtype == SMH_F64) hipLaunchKernelGGL((k_upd_eye<double>), dim3(upd_grid(dim + 1)), dim3(kBlock), 0, s, off, col, (double *)val, (uint64_t)dim);
-    else hipLaunchKernelGGL((k_upd_eye<float>), dim3(upd_grid(dim + 1)), dim3(kBlock), 0, s, off, col, (float *)val, (uint64_t)dim);
+    if (dtype == SMH_F64) hipLaunchKernelGGL((k_upd_eye<double>), dim3(grid_for(dim + 1, kBuildGrid)), dim3(kBlock), 0, s, off, col, (double *)val, (uint64_t)dim);
+    else hipLaunchKernelGGL((k_upd_eye<float>), dim3(grid_for(dim + 1, kBuildGrid)), dim3(kBlock), 0, s, off, col, (float *)val, (uint64_t)dim);
     SMH_HIP(hipGetLastError());
     SMH_HIP(hipStreamSynchronize(s));
     return SMH_OK;

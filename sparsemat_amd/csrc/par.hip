@@ -825,13 +825,7 @@ int smh_comm_create(const void *id, int n_ranks, int rank, smh_comm **out) {
         return SMH_OK;
     };
     const int rc = go();
-    if (rc != SMH_OK) {
-        char keep[512];
-        strncpy(keep, smh_last_error(), sizeof keep);
-        keep[sizeof keep - 1] = 0;
-        smh_comm_destroy(c);
-        return fail(rc, "%s", keep);
-    }
+    if (rc != SMH_OK) return keep_error(rc, [&] { smh_comm_destroy(c); });
     *out = c;
     return SMH_OK;
 }
@@ -886,12 +880,10 @@ int smh_comm_barrier(smh_comm *c) {
 
 // ---- construction ----------------------------------------------------------------------------------------------------
 static int par_fail_cleanup(smh_par *p, int rc, int prev_device) {
-    char keep[512];
-    strncpy(keep, smh_last_error(), sizeof keep);
-    keep[sizeof keep - 1] = 0;
-    smh_par_destroy(p);
-    (void)hipSetDevice(prev_device);
-    return fail(rc, "%s", keep);
+    return keep_error(rc, [&] {
+        smh_par_destroy(p);
+        (void)hipSetDevice(prev_device);
+    });
 }
 
 // nnz-balanced boundaries: block k starts at the first row whose entries begin at or beyond k nnz / n_blocks (every block keeps at
@@ -1643,13 +1635,7 @@ int smh_par_cg_solve_vec(smh_par *p, const smh_par_vec *b, smh_par_vec *x, doubl
         return sync_all(p);
     };
     const int rc = go();
-    if (rc != SMH_OK) {
-        char keep[512];
-        strncpy(keep, smh_last_error(), sizeof keep);
-        keep[sizeof keep - 1] = 0;
-        (void)sync_all(p);
-        return fail(rc, "%s", keep);
-    }
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)sync_all(p); });
     if (iters_out) *iters_out = iters;
     if (rr_out) *rr_out = rr;
     return SMH_OK;

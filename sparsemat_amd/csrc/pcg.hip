@@ -354,19 +354,17 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
     };
-    const int rc = go();
-    char keep[512];
-    strncpy(keep, smh_last_error(), sizeof keep);
-    keep[sizeof keep - 1] = 0;
-    if (s) (void)hipStreamSynchronize(s);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(d_x); (void)hipFree(d_r); (void)hipFree(d_p); (void)hipFree(d_ap); (void)hipFree(d_d); (void)hipFree(d_part);
-    (void)hipFree(d_dot); (void)hipFree(d_sc); (void)hipFree(d_bad);
-    if (h_sc) (void)hipHostFree(h_sc);
-    (void)hipGetLastError();
-    if (rc != SMH_OK) return fail(rc, "%s", keep);
+    const int rc = keep_error(go(), [&] {
+        if (s) (void)hipStreamSynchronize(s);
+        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (s) (void)hipStreamDestroy(s);
+        (void)hipFree(d_x); (void)hipFree(d_r); (void)hipFree(d_p); (void)hipFree(d_ap); (void)hipFree(d_d); (void)hipFree(d_part);
+        (void)hipFree(d_dot); (void)hipFree(d_sc); (void)hipFree(d_bad);
+        if (h_sc) (void)hipHostFree(h_sc);
+        (void)hipGetLastError();
+    });
+    if (rc != SMH_OK) return rc;
     if (iters_out) *iters_out = iters;
     if (rr_out) *rr_out = rr;
     return rc;

@@ -102,44 +102,32 @@ k_cb_scatter(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
     }
 }
 
-static unsigned rows_grid(uint64_t n_rows) {
-    uint64_t b = (n_rows + kBlock - 1) / kBlock;
-    if (b > 8192) b = 8192;
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
-
 // in-place exclusive scan of `n` u32 on the device (chunk sums folded on the host: n/4096 values)
 int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out) {
     if (total_out) *total_out = 0;
     if (n == 0) return SMH_OK;
     const uint64_t chunks = (n + kScanChunk - 1) / kScanChunk;
+    Scratch scr;
     uint32_t *d_sums = nullptr;
-    SMH_HIP(hipMalloc((void **)&d_sums, chunks * sizeof(uint32_t)));
+    SMH_TRY(scr.alloc(&d_sums, chunks));
     std::vector<uint32_t> h(chunks);
-    int rc = SMH_OK;
-    auto body = [&]() -> int {
-        hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)chunks), dim3(kBlock), 0, s, data, n, d_sums);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMemcpyAsync(h.data(), d_sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        SMH_HIP(hipStreamSynchronize(s));
-        uint64_t run = 0;
-        for (uint64_t c = 0; c < chunks; ++c) {
-            const uint32_t v = h[c];
-            h[c] = (uint32_t)run;
-            run += v;
-        }
-        if (run >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
-        if (total_out) *total_out = run;
-        SMH_HIP(hipMemcpyAsync(d_sums, h.data(), chunks * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)chunks), dim3(kBlock), 0, s, data, n, d_sums);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    rc = body();
-    (void)hipFree(d_sums);
-    return rc;
+    hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)chunks), dim3(kBlock), 0, s, data, n, d_sums);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(h.data(), d_sums, chunks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    uint64_t run = 0;
+    for (uint64_t c = 0; c < chunks; ++c) {
+        const uint32_t v = h[c];
+        h[c] = (uint32_t)run;
+        run += v;
+    }
+    if (run >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    if (total_out) *total_out = run;
+    SMH_HIP(hipMemcpyAsync(d_sums, h.data(), chunks * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)chunks), dim3(kBlock), 0, s, data, n, d_sums);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
+    return SMH_OK;
 }
 
 // Build the column-blocked copy.  Outputs (device, owned by the caller): off2 [n_blocks*(n_rows+1)] absolute
@@ -149,37 +137,29 @@ int build_colblock(int dtype, const uint32_t *off, const uint32_t *col, const vo
                    hipStream_t s) {
     const uint64_t total = (uint64_t)n_blocks * (n_rows + 1);
     const size_t vs = dtype_size(dtype);
+    Scratch scr;
     uint32_t *off2 = nullptr, *cur = nullptr, *col2 = nullptr;
-    void *val2 = nullptr;
-    auto body = [&]() -> int {
-        SMH_HIP(hipMalloc((void **)&off2, total * sizeof(uint32_t)));
-        SMH_HIP(hipMemsetAsync(off2, 0, total * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_cb_count, dim3(rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, shift, off2);
-        SMH_HIP(hipGetLastError());
-        SMH_TRY(device_exclusive_scan_u32(off2, total, s, nullptr));
-        SMH_HIP(hipMalloc((void **)&cur, total * sizeof(uint32_t)));
-        SMH_HIP(hipMemcpyAsync(cur, off2, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        SMH_HIP(hipMalloc((void **)&col2, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&val2, (nnz + 4) * vs));
-        SMH_HIP(hipMemsetAsync(col2 + nnz, 0, 4 * sizeof(uint32_t), s));
-        SMH_HIP(hipMemsetAsync((char *)val2 + nnz * vs, 0, 4 * vs, s));
-        if (dtype == SMH_F64)
-            hipLaunchKernelGGL(k_cb_scatter<double>, dim3(rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const double *)val,
-                               (uint64_t)n_rows, shift, cur, col2, (double *)val2);
-        else
-            hipLaunchKernelGGL(k_cb_scatter<float>, dim3(rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const float *)val,
-                               (uint64_t)n_rows, shift, cur, col2, (float *)val2);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = body();
-    (void)hipFree(cur);
-    if (rc != SMH_OK) {
-        (void)hipFree(off2); (void)hipFree(col2); (void)hipFree(val2);
-        return rc;
-    }
-    *off2_out = off2; *col2_out = col2; *val2_out = val2;
+    char *val2 = nullptr;
+    SMH_TRY(scr.alloc(&off2, total));
+    SMH_HIP(hipMemsetAsync(off2, 0, total * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_cb_count, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, shift, off2);
+    SMH_HIP(hipGetLastError());
+    SMH_TRY(device_exclusive_scan_u32(off2, total, s, nullptr));
+    SMH_TRY(scr.alloc(&cur, total));
+    SMH_HIP(hipMemcpyAsync(cur, off2, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    SMH_TRY(scr.alloc(&col2, nnz + 4));
+    SMH_TRY(scr.alloc(&val2, (nnz + 4) * vs));
+    SMH_HIP(hipMemsetAsync(col2 + nnz, 0, 4 * sizeof(uint32_t), s));
+    SMH_HIP(hipMemsetAsync(val2 + nnz * vs, 0, 4 * vs, s));
+    if (dtype == SMH_F64)
+        hipLaunchKernelGGL(k_cb_scatter<double>, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (const double *)val,
+                           (uint64_t)n_rows, shift, cur, col2, (double *)val2);
+    else
+        hipLaunchKernelGGL(k_cb_scatter<float>, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (const float *)val,
+                           (uint64_t)n_rows, shift, cur, col2, (float *)val2);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
+    *off2_out = scr.release(off2); *col2_out = scr.release(col2); *val2_out = scr.release(val2);
     return SMH_OK;
 }
 

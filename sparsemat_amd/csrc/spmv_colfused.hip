@@ -43,8 +43,6 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -266,13 +264,6 @@ k_spmv_colfused(const uint32_t *__restrict__ tile_row, const uint32_t *__restric
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static unsigned cf_rows_grid(uint64_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > 8192) b = 8192;
-    if (b == 0) b = 1;
-    return (unsigned)b;
-}
-
 // Build the K2f copy.  Outputs (device, owned by the caller): tile_row [n_tiles + 1], seg [n_tiles * n_blocks + 1],
 // cnt [n_tiles * n_blocks * 64 * rt] bytes, col2 / val2 [nnz + 4].  *fits_out = false (and nothing allocated) when a
 // (row, block) pair exceeds 255 entries.
@@ -283,75 +274,64 @@ int build_colfused(int dtype, const uint32_t *off, const uint32_t *col, const vo
     const size_t vs = dtype_size(dtype);
     *fits_out = false;
     *n_tiles_out = 0;
+    Scratch scr;
     uint32_t *cur = nullptr, *seg = nullptr, *col2 = nullptr, *d_over = nullptr, *tile_row = nullptr;
     uint8_t *cnt8 = nullptr;
-    void *val2 = nullptr;
-    bool fits = false;
-    uint64_t n_tiles = 0;
-    auto body = [&]() -> int {
-        // tiles of at most 1.25x the entries of a mean full-height tile
-        SMH_HIP(hipMalloc((void **)&d_over, sizeof(uint32_t)));
-        SMH_HIP(hipMemsetAsync(d_over, 0, sizeof(uint32_t), s));
-        const double mean_tile = n_rows ? (double)nnz * (double)tile_rows / (double)n_rows : 0.0;
-        uint64_t target = (uint64_t)(1.25 * mean_tile) + 1;
-        if (const char *e = getenv("SMH_COLFUSED_BALANCE")) {  // tuning knob: 0 = full-height tiles whatever they hold
-            if (atoi(e) == 0) target = ~uint64_t(0);
-        }
-        std::vector<uint32_t> h_off(n_rows + 1), h_tiles;
-        SMH_HIP(hipMemcpyAsync(h_off.data(), off, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        SMH_HIP(hipStreamSynchronize(s));
-        cf_tiles_host(h_off.data(), n_rows, rt, target, h_tiles);
-        n_tiles = h_tiles.size() - 1;
-        // (what every kernel below relies on: strictly increasing starts, at most 64 rt rows per tile, all rows covered)
-        for (uint64_t t = 0; t < n_tiles; ++t)
-            if (h_tiles[t + 1] <= h_tiles[t] || (uint64_t)h_tiles[t + 1] - h_tiles[t] > tile_rows)
-                return fail(SMH_ERR_INVALID, "fused column-blocked copy: malformed tile table at tile %llu", (unsigned long long)t);
-        if (h_tiles[0] != 0 || h_tiles[n_tiles] != n_rows) return fail(SMH_ERR_INVALID, "fused column-blocked copy: tile table does not cover the rows");
-        SMH_HIP(hipMalloc((void **)&tile_row, (n_tiles + 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMemcpyAsync(tile_row, h_tiles.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        SMH_HIP(hipStreamSynchronize(s));  // (h_tiles is a local)
-        const uint64_t n_seg = n_tiles * n_blocks, total = n_seg * tile_rows;
-        if (total >= (1ull << 34)) return fail(SMH_ERR_OOM, "fused column-blocked copy: count table too large");
-        SMH_HIP(hipMalloc((void **)&cur, (total ? total : 1) * sizeof(uint32_t)));
-        SMH_HIP(hipMemsetAsync(cur, 0, (total ? total : 1) * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_cf_count, dim3(cf_rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, shift,
-                           (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, d_over);
-        SMH_HIP(hipGetLastError());
-        uint32_t h_over = 0;
-        SMH_HIP(hipMemcpyAsync(&h_over, d_over, sizeof h_over, hipMemcpyDeviceToHost, s));
-        SMH_HIP(hipStreamSynchronize(s));
-        if (h_over) return SMH_OK;  // a (row, block) pair with more than 255 entries: not describable
-        fits = true;
-        SMH_HIP(hipMalloc((void **)&cnt8, total ? total : 1));
-        hipLaunchKernelGGL(k_cf_narrow, dim3(cf_rows_grid(total)), dim3(kBlock), 0, s, cur, total, cnt8);
-        SMH_HIP(hipGetLastError());
-        SMH_TRY(device_exclusive_scan_u32(cur, total, s, nullptr));
-        SMH_HIP(hipMalloc((void **)&seg, (n_seg + 1) * sizeof(uint32_t)));
-        hipLaunchKernelGGL(k_cf_segments, dim3(cf_rows_grid(n_seg + 1)), dim3(kBlock), 0, s, cur, n_seg, rt, (uint32_t)nnz, seg);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMalloc((void **)&col2, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc(&val2, (nnz + 4) * vs));
-        SMH_HIP(hipMemsetAsync(col2 + nnz, 0, 4 * sizeof(uint32_t), s));
-        SMH_HIP(hipMemsetAsync((char *)val2 + nnz * vs, 0, 4 * vs, s));
-        if (dtype == SMH_F64)
-            hipLaunchKernelGGL(k_cf_scatter<double>, dim3(cf_rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const double *)val,
-                               (uint64_t)n_rows, shift, (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, col2, (double *)val2);
-        else
-            hipLaunchKernelGGL(k_cf_scatter<float>, dim3(cf_rows_grid(n_rows)), dim3(kBlock), 0, s, off, col, (const float *)val,
-                               (uint64_t)n_rows, shift, (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, col2, (float *)val2);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipStreamSynchronize(s));
-        return SMH_OK;
-    };
-    const int rc = body();
-    (void)hipFree(cur);
-    (void)hipFree(d_over);
-    if (rc != SMH_OK || !fits) {
-        (void)hipFree(seg); (void)hipFree(cnt8); (void)hipFree(col2); (void)hipFree(val2); (void)hipFree(tile_row);
-        return rc;
+    char *val2 = nullptr;
+    // tiles of at most 1.25x the entries of a mean full-height tile
+    SMH_TRY(scr.alloc(&d_over, 1));
+    SMH_HIP(hipMemsetAsync(d_over, 0, sizeof(uint32_t), s));
+    const double mean_tile = n_rows ? (double)nnz * (double)tile_rows / (double)n_rows : 0.0;
+    uint64_t target = (uint64_t)(1.25 * mean_tile) + 1;
+    if (const char *e = getenv("SMH_COLFUSED_BALANCE")) {  // tuning knob: 0 = full-height tiles whatever they hold
+        if (atoi(e) == 0) target = ~uint64_t(0);
     }
+    std::vector<uint32_t> h_off(n_rows + 1), h_tiles;
+    SMH_HIP(hipMemcpyAsync(h_off.data(), off, (n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    cf_tiles_host(h_off.data(), n_rows, rt, target, h_tiles);
+    const uint64_t n_tiles = h_tiles.size() - 1;
+    // (what every kernel below relies on: strictly increasing starts, at most 64 rt rows per tile, all rows covered)
+    for (uint64_t t = 0; t < n_tiles; ++t)
+        if (h_tiles[t + 1] <= h_tiles[t] || (uint64_t)h_tiles[t + 1] - h_tiles[t] > tile_rows)
+            return fail(SMH_ERR_INVALID, "fused column-blocked copy: malformed tile table at tile %llu", (unsigned long long)t);
+    if (h_tiles[0] != 0 || h_tiles[n_tiles] != n_rows) return fail(SMH_ERR_INVALID, "fused column-blocked copy: tile table does not cover the rows");
+    SMH_TRY(scr.alloc(&tile_row, n_tiles + 1));
+    SMH_HIP(hipMemcpyAsync(tile_row, h_tiles.data(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    SMH_HIP(hipStreamSynchronize(s));  // (h_tiles is a local)
+    const uint64_t n_seg = n_tiles * n_blocks, total = n_seg * tile_rows;
+    if (total >= (1ull << 34)) return fail(SMH_ERR_OOM, "fused column-blocked copy: count table too large");
+    SMH_TRY(scr.alloc(&cur, total));
+    SMH_HIP(hipMemsetAsync(cur, 0, (total ? total : 1) * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_cf_count, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (uint64_t)n_rows, shift,
+                       (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, d_over);
+    SMH_HIP(hipGetLastError());
+    uint32_t h_over = 0;
+    SMH_HIP(hipMemcpyAsync(&h_over, d_over, sizeof h_over, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    if (h_over) return SMH_OK;  // a (row, block) pair with more than 255 entries: not describable
+    SMH_TRY(scr.alloc(&cnt8, total));
+    hipLaunchKernelGGL(k_cf_narrow, dim3(grid_for(total, 8192)), dim3(kBlock), 0, s, cur, total, cnt8);
+    SMH_HIP(hipGetLastError());
+    SMH_TRY(device_exclusive_scan_u32(cur, total, s, nullptr));
+    SMH_TRY(scr.alloc(&seg, n_seg + 1));
+    hipLaunchKernelGGL(k_cf_segments, dim3(grid_for(n_seg + 1, 8192)), dim3(kBlock), 0, s, cur, n_seg, rt, (uint32_t)nnz, seg);
+    SMH_HIP(hipGetLastError());
+    SMH_TRY(scr.alloc(&col2, nnz + 4));
+    SMH_TRY(scr.alloc(&val2, (nnz + 4) * vs));
+    SMH_HIP(hipMemsetAsync(col2 + nnz, 0, 4 * sizeof(uint32_t), s));
+    SMH_HIP(hipMemsetAsync(val2 + nnz * vs, 0, 4 * vs, s));
+    if (dtype == SMH_F64)
+        hipLaunchKernelGGL(k_cf_scatter<double>, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (const double *)val,
+                           (uint64_t)n_rows, shift, (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, col2, (double *)val2);
+    else
+        hipLaunchKernelGGL(k_cf_scatter<float>, dim3(grid_for(n_rows, 8192)), dim3(kBlock), 0, s, off, col, (const float *)val,
+                           (uint64_t)n_rows, shift, (uint32_t)n_blocks, rt, tile_row, (uint32_t)n_tiles, cur, col2, (float *)val2);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));
     *n_tiles_out = (size_t)n_tiles;
-    *tile_row_out = tile_row; *seg_out = seg; *cnt_out = cnt8; *col2_out = col2; *val2_out = val2;
+    *tile_row_out = scr.release(tile_row); *seg_out = scr.release(seg); *cnt_out = scr.release(cnt8);
+    *col2_out = scr.release(col2); *val2_out = scr.release(val2);
     *fits_out = true;
     return SMH_OK;
 }

@@ -46,8 +46,6 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
 // columns per slice and threads per pass-1 workgroup, per value type (A/B builds override them: sparsemat_amd/build.py extra_flags).
 // f32: 16384 columns = 64 KiB of x + a 16 KiB stage -> two 1024-thread workgroups per CU.  f64: 16384 columns = 128 KiB + 32 KiB: ONE
 // workgroup per CU; the alternative that gives two (8192 columns, 512 threads: 64 + 16 KiB) was measured in round 4 and lost what it
@@ -667,23 +665,6 @@ __global__ __launch_bounds__(kBlock) void k_t3_table(const uint32_t *__restrict_
     }
 }
 
-static unsigned t3_bits_for(uint64_t v) {
-    unsigned b = 1;
-    while (b < 64 && (v >> b)) ++b;
-    return b;
-}
-
-struct T3Scratch {
-    void *p[16] = {};
-    int n = 0;
-    template <typename U> int alloc(U **out, size_t count) {
-        SMH_HIP(hipMalloc((void **)out, (count ? count : 1) * sizeof(U)));
-        p[n++] = *out;
-        return SMH_OK;
-    }
-    ~T3Scratch() { for (int i = 0; i < n; ++i) (void)hipFree(p[i]); }
-};
-
 // the geometry for rows of equal length and no two entries of a row in one slice (AUTO's estimate; the build cuts the row blocks
 // by the products the rows really have)
 void tiled_geometry(size_t n_rows, size_t n_cols, size_t nnz, int dtype, uint32_t *n_cb, uint32_t *R, uint32_t *n_rb) {
@@ -719,14 +700,14 @@ static int build_t(::smh_crs *m) {
         fprintf(stderr, "[k2t build] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
     };
-    T3Scratch tmp;
+    Scratch scr;
     uint32_t *rows_e = nullptr, *key_s = nullptr;
     T3Entry<T> *ps = nullptr;  // the entries sorted by slice (inside a slice: row, storage order)
     uint64_t *d_start = nullptr;
-    SMH_TRY(tmp.alloc(&rows_e, nnz));
-    SMH_TRY(tmp.alloc(&key_s, nnz));
-    SMH_TRY(tmp.alloc(&ps, nnz));
-    SMH_TRY(tmp.alloc(&d_start, (size_t)n_cb + 1));
+    SMH_TRY(scr.alloc(&rows_e, nnz));
+    SMH_TRY(scr.alloc(&key_s, nnz));
+    SMH_TRY(scr.alloc(&ps, nnz));
+    SMH_TRY(scr.alloc(&d_start, (size_t)n_cb + 1));
     const unsigned grid = 2048;
     if (nnz) {
         SMH_TRY(expand_rows(m->d_off, m->n_rows, rows_e, s));
@@ -734,15 +715,7 @@ static int build_t(::smh_crs *m) {
         // keys and payload are READ through iterators over the CRS arrays (nothing is materialised before the first pass)
         auto keys_in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), T3LoadKey{m->d_col, kT3Slice});
         auto vals_in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), T3LoadEntry<T>{rows_e, m->d_col, (const T *)m->d_val});
-        size_t bytes = 0;
-        void *ws = nullptr;
-        SMH_HIP(rocprim::radix_sort_pairs(ws, bytes, keys_in, key_s, vals_in, ps, (size_t)nnz, 0u, t3_bits_for(n_cb - 1), s));
-        SMH_HIP(hipMalloc(&ws, bytes ? bytes : 16));
-        const hipError_t e1 = rocprim::radix_sort_pairs(ws, bytes, keys_in, key_s, vals_in, ps, (size_t)nnz, 0u, t3_bits_for(n_cb - 1), s);
-        const hipError_t e2 = hipStreamSynchronize(s);
-        (void)hipFree(ws);
-        SMH_HIP(e1);
-        SMH_HIP(e2);
+        SMH_ROCPRIM(s, rocprim::radix_sort_pairs(tmp, bytes, keys_in, key_s, vals_in, ps, (size_t)nnz, 0u, bits_for(n_cb - 1), s));
         stage("radix sort (entries as payload)");
     }
     hipLaunchKernelGGL(k_t3_bounds, dim3((n_cb + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, key_s, nnz, n_cb, d_start);
@@ -767,13 +740,13 @@ static int build_t(::smh_crs *m) {
     uint32_t group = kT3RowGroup;
     if (const char *e = getenv("SMH_TILED_GROUP")) { const int v = atoi(e); if (v >= 1 && v <= 1024) group = (uint32_t)v; }  // tuning knob (1: a count per row, round 3's cut)
     const size_t n_groups = (m->n_rows + group - 1) / group;
-    SMH_TRY(tmp.alloc(&cstart, (size_t)n_chunks));
-    SMH_TRY(tmp.alloc(&clen, (size_t)n_chunks));
-    SMH_TRY(tmp.alloc(&obase, (size_t)n_chunks + 1));
-    SMH_TRY(tmp.alloc(&preal, (size_t)n_chunks));
-    SMH_TRY(tmp.alloc(&gcount, n_groups));
+    SMH_TRY(scr.alloc(&cstart, (size_t)n_chunks));
+    SMH_TRY(scr.alloc(&clen, (size_t)n_chunks));
+    SMH_TRY(scr.alloc(&obase, (size_t)n_chunks + 1));
+    SMH_TRY(scr.alloc(&preal, (size_t)n_chunks));
+    SMH_TRY(scr.alloc(&gcount, n_groups));
     uint32_t *any_cut = nullptr;  // does any chunk boundary cut a (row, slice) pair?
-    SMH_TRY(tmp.alloc(&any_cut, 1));
+    SMH_TRY(scr.alloc(&any_cut, 1));
     SMH_HIP(hipMemsetAsync(any_cut, 0, sizeof(uint32_t), s));
     SMH_HIP(hipMalloc(&m->d_t2_val, (slots + CH) * sizeof(T)));
     SMH_HIP(hipMalloc((void **)&m->d_t2_code, (slots + CH) * sizeof(uint16_t)));
@@ -796,7 +769,7 @@ static int build_t(::smh_crs *m) {
     SMH_TRY(device_exclusive_scan_u32(obase, (uint64_t)n_chunks + 1, s, &n_prod));  // obase[c] = products before chunk c; obase[n_chunks] = all
     stage("scan");
     if (n_prod >= (1ull << 32) - 4 * CH) return fail(SMH_ERR_INVALID, "tiled variant: %llu products are too many for its 32-bit index", (unsigned long long)n_prod);
-    SMH_TRY(tmp.alloc(&prow, (size_t)n_prod));
+    SMH_TRY(scr.alloc(&prow, (size_t)n_prod));
     if (n_chunks) {
         hipLaunchKernelGGL(k_t3_prow<T>, dim3(wgrid), dim3(kBlock), 0, s, m->d_t3_cptr, n_cb, n_chunks, d_start, cstart, clen, obase, ps, m->d_t2_code, prow, preal,
                            gcount, group, (T3Chunk *)m->d_t3_chunk, any_cut);

@@ -31,8 +31,6 @@
 
 namespace smh {
 
-int device_exclusive_scan_u32(uint32_t *data, uint64_t n, hipStream_t s, uint64_t *total_out);  // spmv_colblock.hip
-
 namespace {
 
 constexpr uint32_t kTbSrcRows = 256;      // rows of a source tile (= threads of its block)
@@ -347,72 +345,62 @@ int run(const uint32_t *off, const uint32_t *col, const V *val, size_t n_rows, s
     while (shift > 0 && ((uint64_t)nnz << shift) / n_t > 4096) --shift;
     uint64_t n_b = 0;
 
-    uint32_t *d_total = nullptr, *d_cursor = nullptr, *d_src = nullptr, *d_offt = nullptr, *d_col = nullptr;
+    Scratch scr;
+    CrsArrays res;  // (the result unless INFO; handed over when done)
+    uint32_t *d_total = nullptr, *d_cursor = nullptr, *d_src = nullptr;
     uint8_t *d_t = nullptr;
-    V *d_bval = nullptr, *d_val = nullptr;
-    TbScalars *d_sc = nullptr;
-    auto cleanup = [&](bool keep_result) {
-        (void)hipFree(d_total); (void)hipFree(d_cursor); (void)hipFree(d_src); (void)hipFree(d_t); (void)hipFree(d_bval);
-        if (!keep_result && !INFO) { (void)hipFree(d_offt); (void)hipFree(d_col); (void)hipFree(d_val); }
-    };
-    auto go = [&]() -> int {
-        TbScalars sc;
-        for (int attempt = 0;; ++attempt) {
-            n_b = (n_t + (1ull << shift) - 1) >> shift;
-            (void)hipFree(d_total);
-            d_total = nullptr;
-            SMH_HIP(hipMalloc((void **)&d_total, (n_b + 1 + 4) * sizeof(uint32_t)));  // the buckets' totals / starts, then the scalars
-            d_sc = reinterpret_cast<TbScalars *>(d_total + n_b + 1);
-            SMH_HIP(hipMemsetAsync(d_total, 0, (n_b + 1 + 4) * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_tb_hist, dim3((unsigned)n_st), dim3(kTbSrcRows), 0, s, off, col, (uint64_t)n_rows, shift, d_total, d_sc);
-            SMH_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_tb_max, dim3((unsigned)std::min<uint64_t>((n_b + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, s, d_total, n_b, d_sc);
-            SMH_HIP(hipGetLastError());
-            SMH_HIP(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, s));
-            SMH_HIP(hipStreamSynchronize(s));
-            if (sc.overflow) return SMH_OK;  // columns without locality: declined
-            if (sc.max_bucket <= kTbCap) break;
-            // a bucket too large for the LDS of pass S (dense stretches of columns): halve the buckets' rows and count again
-            if (shift == 0 || attempt == 3) return SMH_OK;
-            --shift;
-        }
-        uint64_t total = 0;
-        SMH_TRY(device_exclusive_scan_u32(d_total, n_b + 1, s, &total));
-        if (total != nnz) return fail(SMH_ERR_INVALID, "bucketed transposition counted %llu of %zu entries", (unsigned long long)total, nnz);
-        SMH_HIP(hipMalloc((void **)&d_cursor, n_b * sizeof(uint32_t)));
-        SMH_HIP(hipMemcpyAsync(d_cursor, d_total, n_b * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        SMH_HIP(hipMalloc((void **)&d_src, (nnz + 4) * sizeof(uint32_t)));
-        SMH_HIP(hipMalloc((void **)&d_t, nnz + 16));
-        if (!INFO) SMH_HIP(hipMalloc((void **)&d_bval, (nnz + 4) * sizeof(V)));
-        SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tb_part<V, INFO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb_part_lds<V>()));
-        SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tb_sort<V, INFO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTbSortLds));
-        hipLaunchKernelGGL((k_tb_part<V, INFO>), dim3((unsigned)n_st), dim3(kTbPartThreads), tb_part_lds<V>(), s, off, col, val, (uint64_t)n_rows, shift, d_cursor, d_src, d_t, d_bval);
+    V *d_bval = nullptr;
+    TbScalars *d_sc = nullptr, sc;
+    for (int attempt = 0;; ++attempt) {
+        n_b = (n_t + (1ull << shift) - 1) >> shift;
+        scr.free_now(d_total);
+        SMH_TRY(scr.alloc(&d_total, n_b + 1 + 4));  // the buckets' totals / starts, then the scalars
+        d_sc = reinterpret_cast<TbScalars *>(d_total + n_b + 1);
+        SMH_HIP(hipMemsetAsync(d_total, 0, (n_b + 1 + 4) * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_tb_hist, dim3((unsigned)n_st), dim3(kTbSrcRows), 0, s, off, col, (uint64_t)n_rows, shift, d_total, d_sc);
         SMH_HIP(hipGetLastError());
-        if (INFO) {
-            d_offt = *off_out;
-            d_col = *col_out;
-        } else {
-            SMH_HIP(hipMalloc((void **)&d_offt, (n_t + 1) * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc((void **)&d_col, (nnz + 4) * sizeof(uint32_t)));
-            SMH_HIP(hipMalloc((void **)&d_val, (nnz + 4) * sizeof(V)));
-            SMH_HIP(hipMemsetAsync(d_col + nnz, 0, 4 * sizeof(uint32_t), s));
-            SMH_HIP(hipMemsetAsync(d_val + nnz, 0, 4 * sizeof(V), s));
-        }
-        const uint32_t nnz32 = (uint32_t)nnz;
-        SMH_HIP(hipMemcpyAsync(d_offt + n_t, &nnz32, sizeof nnz32, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL((k_tb_sort<V, INFO>), dim3((unsigned)n_b), dim3(kTbSortThreads), kTbSortLds, s, d_total, d_src, d_t, d_bval, n_t, shift, d_offt, d_col, d_val, d_sc);
+        hipLaunchKernelGGL(k_tb_max, dim3((unsigned)std::min<uint64_t>((n_b + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, s, d_total, n_b, d_sc);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
-        if (sc.repeats) return SMH_OK;  // a repeated (row, column) pair: `set` semantics live in the general route
-        *n_cols_out = sc.last_row_plus1;
-        *done = true;
-        return SMH_OK;
-    };
-    const int rc = go();
-    cleanup(rc == SMH_OK && *done);
-    if (rc == SMH_OK && *done && !INFO) { *off_out = d_offt; *col_out = d_col; *val_out = d_val; }
-    return rc;
+        if (sc.overflow) return SMH_OK;  // columns without locality: declined
+        if (sc.max_bucket <= kTbCap) break;
+        // a bucket too large for the LDS of pass S (dense stretches of columns): halve the buckets' rows and count again
+        if (shift == 0 || attempt == 3) return SMH_OK;
+        --shift;
+    }
+    uint64_t total = 0;
+    SMH_TRY(device_exclusive_scan_u32(d_total, n_b + 1, s, &total));
+    if (total != nnz) return fail(SMH_ERR_INVALID, "bucketed transposition counted %llu of %zu entries", (unsigned long long)total, nnz);
+    SMH_TRY(scr.alloc(&d_cursor, n_b));
+    SMH_HIP(hipMemcpyAsync(d_cursor, d_total, n_b * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    SMH_TRY(scr.alloc(&d_src, nnz + 4));
+    SMH_TRY(scr.alloc(&d_t, nnz + 16));
+    if (!INFO) SMH_TRY(scr.alloc(&d_bval, nnz + 4));
+    SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tb_part<V, INFO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb_part_lds<V>()));
+    SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tb_sort<V, INFO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTbSortLds));
+    hipLaunchKernelGGL((k_tb_part<V, INFO>), dim3((unsigned)n_st), dim3(kTbPartThreads), tb_part_lds<V>(), s, off, col, val, (uint64_t)n_rows, shift, d_cursor, d_src, d_t, d_bval);
+    SMH_HIP(hipGetLastError());
+    uint32_t *d_offt = *off_out, *d_col = *col_out;
+    V *d_val = nullptr;
+    if (!INFO) {
+        SMH_TRY(res.alloc(n_t, nnz, sizeof(V)));
+        SMH_TRY(res.zero_padding(nnz, sizeof(V), s));
+        d_offt = res.off;
+        d_col = res.col;
+        d_val = (V *)res.val;
+    }
+    const uint32_t nnz32 = (uint32_t)nnz;
+    SMH_HIP(hipMemcpyAsync(d_offt + n_t, &nnz32, sizeof nnz32, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL((k_tb_sort<V, INFO>), dim3((unsigned)n_b), dim3(kTbSortThreads), kTbSortLds, s, d_total, d_src, d_t, d_bval, n_t, shift, d_offt, d_col, d_val, d_sc);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(&sc, d_sc, sizeof sc, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    if (sc.repeats) return SMH_OK;  // a repeated (row, column) pair: `set` semantics live in the general route
+    *n_cols_out = sc.last_row_plus1;
+    *done = true;
+    if (!INFO) res.release(off_out, col_out, val_out);
+    return SMH_OK;
 }
 
 }  // namespace

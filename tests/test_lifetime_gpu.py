@@ -1,7 +1,9 @@
 """Handle lifetime: every lazily built workspace (merge table, ring plans incl. the wide and the banded ring, 16-bit
-column arrays, K1s windows and codes, K2c blocked copy, assembly scratch) is released with its handle -- device
+column arrays, K1s windows and codes, K2c blocked copy, assembly scratch) is released with its handle, and so is every
+array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay) -- device
 memory in use returns to where it started after many create / use / destroy rounds."""
 import gc
+import os
 
 import numpy as np
 import pytest
@@ -62,18 +64,83 @@ def _exercise(rng, kind):
     del m, t
 
 
+def _with_env(name, value, fn):
+    old = os.environ.get(name)
+    os.environ[name] = value
+    try:
+        return fn()
+    finally:
+        if old is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = old
+
+
+def _banded(rng, n, lo, hi):
+    """n rows of lo..hi - 1 distinct columns in a band around the diagonal (wrapping): ~(lo + hi) / 2 * n entries"""
+    lens = rng.integers(lo, hi, n)
+    off = np.zeros(n + 1, np.uint32)
+    np.cumsum(lens, out=off[1:])
+    k = np.arange(off[-1]) - np.repeat(off[:-1].astype(np.int64), lens)
+    col = ((np.repeat(np.arange(n), lens) + 7 * k - 40 + rng.integers(0, 7, len(k))) % n).astype(np.uint32)
+    val = rng.uniform(-1, 1, len(col)).astype(np.float32)
+    return sm.SparseMatCRS.from_raw_parts(n, int(col.max()) + 1, off, col, val), off, col
+
+
+def _exercise_matrix_ops(rng):
+    # ~320 k entries: the column and value arrays are pooled blocks (1 MiB and more)
+    n = 40_000
+    a, off, col = _banded(rng, n, 4, 12)
+    b, _, _ = _banded(rng, n, 2, 6)
+    t = a.transpose()
+    assert sm.SparseMatCRS.last_transpose_route() == "bucketed"
+    t2 = _with_env("SMH_TRANSPOSE_BUCKETED", "0", a.transpose)
+    assert sm.SparseMatCRS.last_transpose_route() == "general"
+    p = a.prod(t)
+    a.column_info()
+    c = a.clone()
+    s = a + c
+    assert sm.SparseMatCRS.last_add_route() == "same_pattern"
+    first = sm.SparseMatCRS.from_raw_parts(n, a.n_cols(), np.arange(n + 1, dtype=np.uint32), col[off[:-1]],
+                                           np.ones(n, np.float32))
+    c += first
+    assert sm.SparseMatCRS.last_add_route() == "structure_unchanged"
+    d = a + b
+    assert sm.SparseMatCRS.last_add_route() == "short_rows"
+    c -= b
+    e = _with_env("SMH_ADD_FAST", "0", lambda: a - b)
+    assert sm.SparseMatCRS.last_add_route() == "general"
+    pick = rng.integers(0, len(col), 100_000)
+    rows = np.searchsorted(off, pick, side="right") - 1
+    c.apply(rows, col[pick], rng.uniform(-1, 1, len(pick)).astype(np.float32), rng.integers(0, 2, len(pick)))
+    assert sm.SparseMatCRS.last_apply_route() == "values_only"
+    c.apply(rng.integers(0, n + 100, 100_000), rng.integers(0, n, 100_000), rng.uniform(-1, 1, 100_000).astype(np.float32))
+    assert sm.SparseMatCRS.last_apply_route() == "general"
+    _with_env("SMH_APPLY_FAST", "0", lambda: d.apply(rows, col[pick], np.ones(len(pick), np.float32)))
+    assert sm.SparseMatCRS.last_apply_route() == "general"
+    a.get_many(rng.integers(0, n, 300_000), rng.integers(0, n, 300_000))
+    i = sm.SparseMatCRS.eye(300_000)
+    r = sm.SparseMatCRS.from_triplets(rng.integers(0, 20_000, 300_000), rng.integers(0, 20_000, 300_000),
+                                      rng.uniform(-1, 1, 300_000).astype(np.float32), into_crs=True)
+    del a, b, t, t2, p, c, s, first, d, e, i, r
+
+
+def _round(rng):
+    for kind in range(3):
+        _exercise(rng, kind)
+    _exercise_matrix_ops(rng)
+
+
 def test_no_device_memory_is_left_behind(gpu):
     rng = np.random.default_rng(0)
-    for kind in range(3):   # first round: one-time allocations (code objects, rocPRIM state, thread-local scratch)
-        _exercise(rng, kind)
+    _round(rng)  # first round: one-time allocations (code objects, rocPRIM state, thread-local scratch)
     gc.collect()
     # the library keeps the device memory it frees (csrc/pool.hip): what it KEEPS depends on what ran before in this process, so both
     # readings are taken with the pool returned to the runtime, and the bytes the library has handed out are compared exactly
     before, live_before = _used_without_the_pool()
     for rep in range(8):
-        for kind in range(3):
-            _exercise(rng, kind)
+        _round(rng)
     gc.collect()
     after, live_after = _used_without_the_pool()
     assert live_after == live_before, "the library still holds %d bytes more than before" % (live_after - live_before)
-    assert after - before < 8 << 20, "device memory in use grew by %.1f MiB over 24 create/use/destroy rounds" % ((after - before) / 2 ** 20)
+    assert after - before < 8 << 20, "device memory in use grew by %.1f MiB over 8 create/use/destroy rounds" % ((after - before) / 2 ** 20)
