@@ -80,18 +80,24 @@ void synth_powerlaw_lengths(uint64_t seed, size_t row_begin, size_t row_end, uin
 
 static bool valid_dtype(int dt) { return dt == SMH_F32 || dt == SMH_F64; }
 
-static int ensure_cap(void **buf, size_t *cap, size_t bytes) {
-    if (*cap >= bytes && *buf) return SMH_OK;
-    if (*buf) { SMH_HIP(hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    size_t want = bytes < 256 ? 256 : bytes;
-    SMH_HIP(hipMalloc(buf, want));
-    *cap = want;
+// "Launch into a few device words, bring them to the host": launch(d) fills `count` elements at d (device scratch), which are
+// copied to `host` behind a synchronisation of s.  The second form allocates the scratch itself.
+template <typename U, typename F> static int read_back(U *d, U *host, size_t count, hipStream_t s, F &&launch) {
+    SMH_TRY(launch(d));
+    SMH_HIP(hipMemcpyAsync(host, d, count * sizeof(U), hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
     return SMH_OK;
+}
+template <typename U, typename F> static int read_back(U *host, size_t count, hipStream_t s, F &&launch) {
+    Scratch scr;
+    U *d = nullptr;
+    SMH_TRY(scr.alloc(&d, count));
+    return read_back(d, host, count, s, launch);
 }
 
 // ---- variant selection ---------------------------------------------------------------------------
-static int auto_lanes(const smh_crs *m) {
-    if (m->forced_lanes) return m->forced_lanes;
+// lanes sized to the mean row alone (the skew test of AUTO)
+static int mean_lanes(const smh_crs *m) {
     const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
     // one pass of a lane group covers 4*lanes entry slots: size the group to the mean row; short rows
     // start anywhere inside their first 16-B chunk, so they get 3 slots of slack (measured on the 7-point
@@ -99,34 +105,32 @@ static int auto_lanes(const smh_crs *m) {
     const double need = mean < 16.0 ? mean + 3.0 : mean;
     int lanes = 1;
     while (lanes < 64 && 4.0 * lanes < need) lanes <<= 1;
+    return lanes;
+}
+
+static int auto_lanes(const smh_crs *m) {
+    if (m->knobs.forced_lanes) return m->knobs.forced_lanes;
+    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
+    int lanes = mean_lanes(m);
     // Long rows in the pipelined body (contiguous-band matrices, 320 M entries, same box): rows of 128 / 256 entries
     // run in 0.313 / 0.301 ms with 16 lanes (2 / 4 passes of 64 slots) against 0.359 / 0.348 ms with one pass of 32 / 64
     // lanes; rows of 100 entries prefer one pass of 32 lanes (0.398 vs 0.500 ms).
-    if (m->use_ring != 0) {
+    if (m->knobs.use_ring != 0) {
         if (mean >= 128.0) lanes = 16;
         else if (lanes > 32) lanes = 32;
         // ... and when their columns do not fit the ring (global gathers, one cache line each) 8 lanes lose least
         // (banded +-32768, rows of 256: 1.28-1.33 ms with 4-8 lanes, 1.51 ms with 16, 1.62-1.80 ms with 64)
-        if (mean > 32.0 && m->ring_planned && m->ring_fraction < 0.5) lanes = 8;
+        if (mean > 32.0 && m->ring.state == Form::Ready && m->ring.fraction < 0.5) lanes = 8;
     }
-    return lanes;
-}
-
-// lanes sized to the mean row alone (the skew test of AUTO)
-static int mean_lanes(const smh_crs *m) {
-    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-    const double need = mean < 16.0 ? mean + 3.0 : mean;
-    int lanes = 1;
-    while (lanes < 64 && 4.0 * lanes < need) lanes <<= 1;
     return lanes;
 }
 
 // 16-B chunks each lane loads per pass (pipelined K1r body only): 4*lanes*chunks entry slots per row and pass
 static int auto_chunks(const smh_crs *m) {
     const int lanes = auto_lanes(m);
-    if (m->forced_chunks) {
-        if (lanes == 1) return m->forced_chunks;
-        if (lanes == 2) return m->forced_chunks > 2 ? 2 : m->forced_chunks;
+    if (m->knobs.forced_chunks) {
+        if (lanes == 1) return m->knobs.forced_chunks;
+        if (lanes == 2) return m->knobs.forced_chunks > 2 ? 2 : m->knobs.forced_chunks;
         return 1;
     }
     return 1;
@@ -136,41 +140,16 @@ static int auto_chunks(const smh_crs *m) {
 // 2^19 columns: 2 MiB of f32 x.  f64 takes the same width (4 MiB of x, a whole L2): measured on C3, 20 blocks of
 // 2^19 run in 3.64 ms, 39 blocks of 2^18 in 5.08 ms -- the per-block sweeps of offsets and y (12 B + 8 B per row)
 // outweigh the better hit rate (profiles/r01_colblock_sweep.log)
-static uint32_t cb_shift_for(const smh_crs *m) { return m->cb_forced_shift ? m->cb_forced_shift : 19u; }
+static uint32_t cb_shift_for(const smh_crs *m) { return m->knobs.cb_forced_shift ? m->knobs.cb_forced_shift : 19u; }
 static size_t cb_blocks_for(const smh_crs *m) {
     const uint64_t w = 1ull << cb_shift_for(m);
     const uint64_t b = ((uint64_t)m->n_cols + w - 1) / w;
     return (size_t)(b ? b : 1);
 }
-// values changed (update_values / scale): the blocked copy is rebuilt on its next use
-static void drop_colblock(smh_crs *m) {
-    tiled_free(m);
-    (void)hipFree(m->d_cb_off); (void)hipFree(m->d_cb_col); (void)hipFree(m->d_cb_val);
-    m->d_cb_off = m->d_cb_col = nullptr;
-    m->d_cb_val = nullptr;
-    m->cb_built = false;
-    (void)hipFree(m->d_cf_seg); (void)hipFree(m->d_cf_cnt); (void)hipFree(m->d_cf_col); (void)hipFree(m->d_cf_val);
-    (void)hipFree(m->d_cf_tile_row);
-    m->d_cf_seg = m->d_cf_col = m->d_cf_tile_row = nullptr;
-    m->d_cf_cnt = nullptr;
-    m->d_cf_val = nullptr;
-    m->cf_built = m->cf_ok = false;
-    (void)smh_crs_destroy(m->split_long);
-    (void)smh_crs_destroy(m->split_short);
-    m->split_long = m->split_short = nullptr;
-    (void)hipFree(m->d_split_rows); (void)hipFree(m->d_split_y);
-    m->d_split_rows = nullptr;
-    m->d_split_y = nullptr;
-    m->split_built = m->split_ok = false;
-    m->split_n_long = 0;
-    if (m->split_stream) { (void)hipStreamSynchronize(m->split_stream); (void)hipStreamDestroy(m->split_stream); m->split_stream = nullptr; }
-    if (m->split_fork) { (void)hipEventDestroy(m->split_fork); m->split_fork = nullptr; }
-    if (m->split_join) { (void)hipEventDestroy(m->split_join); m->split_join = nullptr; }
-}
 // K2f geometry: blocks of 2^18 columns (1 MiB of f32 x, 2 MiB of f64 x): its waves walk the blocks without a barrier and
 // spread over a few of them, so the L2 has to hold more than one (measured on C2-uniform, f32: 2^18 2.05 ms, 2^19 2.40 ms);
 // a forced width applies to both blocked variants
-static uint32_t cf_shift_for(const smh_crs *m) { return m->cb_forced_shift ? m->cb_forced_shift : 18u; }
+static uint32_t cf_shift_for(const smh_crs *m) { return m->knobs.cb_forced_shift ? m->knobs.cb_forced_shift : 18u; }
 static size_t cf_blocks_for(const smh_crs *m) {
     const uint64_t w = 1ull << cf_shift_for(m);
     const uint64_t b = ((uint64_t)m->n_cols + w - 1) / w;
@@ -189,7 +168,7 @@ static bool wants_colblock(const smh_crs *m) {
 // K2t is an option: not switched off, its copy was not refused, >= min_tile entries per (slice, row block) tile, a tile table of <= 1 GiB
 static bool tiled_fits(const smh_crs *m, double min_tile = 32.0) {
     static const bool tiled_off = getenv("SMH_TILED") && atoi(getenv("SMH_TILED")) == 0;  // tuning knob
-    if (tiled_off || (m->t2_built && !m->t2_ok)) return false;
+    if (tiled_off || m->tiled.state == Form::Refused) return false;
     uint32_t n_cb = 0, R = 0, n_rb = 0;
     tiled_geometry(m->n_rows, m->n_cols, m->nnz, m->dtype, &n_cb, &R, &n_rb);
     const double tile = (double)m->nnz / (double)n_cb / (double)n_rb;
@@ -201,7 +180,7 @@ static int resolve_variant(const smh_crs *m, int variant) {
     if (wants_colblock(m)) {
         // one sweep over y (K2f) unless its byte table cannot describe the matrix / it was switched off
         static const bool fused_off = getenv("SMH_COLBLOCK_FUSED") && atoi(getenv("SMH_COLBLOCK_FUSED")) == 0;  // tuning knob
-        if (fused_off || (m->cf_built && !m->cf_ok) || cf_blocks_for(m) > 255) return SMH_SPMV_COLBLOCK;
+        if (fused_off || m->cf.state == Form::Refused || cf_blocks_for(m) > 255) return SMH_SPMV_COLBLOCK;
         // K2f's waves keep their tiles for the whole sweep: that only works while they stay together, i.e. for rows of
         // similar length.  Skewed rows (BASELINE C3, power law 1..2048) let them drift over all column blocks at once
         // -- 5.2-5.6 ms against K2c's 3.25 ms, and a lock step costs more than it recovers (profiles/r02_k2f_sweep.log) --
@@ -233,7 +212,7 @@ static int resolve_variant(const smh_crs *m, int variant) {
         // f32 power law (6 blocks) 0.22 GB for 0.76 GB -> K2c stays ahead, 0.61 against 0.75 ms
         const double vs = (double)dtype_size(m->dtype);
         const double sweeps = (double)cb_blocks_for(m) * (double)m->n_rows * (4.0 + 2.0 * vs), entries = (double)m->nnz * (4.0 + vs);
-        if (!split_off && !m->no_split && !(m->split_built && !m->split_ok) && sweeps >= 0.6 * entries) return SMH_SPMV_COLSPLIT;
+        if (!split_off && !m->no_split && m->split.state != Form::Refused && sweeps >= 0.6 * entries) return SMH_SPMV_COLSPLIT;
         return SMH_SPMV_COLBLOCK;
     }
     const int lanes = mean_lanes(m);
@@ -241,28 +220,32 @@ static int resolve_variant(const smh_crs *m, int variant) {
     const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
     // ... except rows of 9-12 entries whose columns fit the LDS ring (plan taken at create time): there the ring kernel
     // with 4 lanes wins (banded, 320 M entries, rows of 12: 0.445 vs 0.637 ms; rows of 8: 0.572 vs 0.586 ms, a tie)
-    const bool short_ring_rows = mean > 8.0 && m->ring_planned && m->ring_fraction >= 0.5 && m->use_ring != 0;
+    const bool short_ring_rows = mean > 8.0 && m->ring.state == Form::Ready && m->ring.fraction >= 0.5 && m->knobs.use_ring != 0;
     if (mean <= 12.0 && m->max_row_len <= 64 && !short_ring_rows) return SMH_SPMV_STREAM;
     // skew test: the longest row needs >= 8 passes of a group sized for the mean row
     if ((uint64_t)m->max_row_len >= 8ull * 4ull * (uint64_t)lanes && m->max_row_len > 64) return SMH_SPMV_MERGE;
     // long rows whose columns do not fit the LDS ring (plan taken at create time): every kernel is then bound by one
     // cache line per gather; the dense stream kernel loses least up to ~128 entries per row (banded +-8192..32768,
     // 320 M entries: rows of 64 / 128: K1s 0.91 / 1.18 ms, lane-group kernels 1.24-1.42 / 1.34-1.69 ms)
-    if (mean > 32.0 && mean <= 128.0 && m->ring_planned && m->ring_fraction < 0.5) return SMH_SPMV_STREAM;
+    if (mean > 32.0 && mean <= 128.0 && m->ring.state == Form::Ready && m->ring.fraction < 0.5) return SMH_SPMV_STREAM;
     return SMH_SPMV_VECTOR;
 }
 
 static int ensure_merge_ws(smh_crs *m) {
-    if (m->d_tile_row) return SMH_OK;
+    if (m->merge.state == Form::Ready) return SMH_OK;
+    MergeTable t;
     const uint64_t items = (uint64_t)m->n_rows + (uint64_t)m->nnz;
-    m->n_tiles = (size_t)((items + kMergeTile - 1) / kMergeTile);
-    if (m->n_tiles == 0) return SMH_OK;
-    SMH_HIP(hipMalloc((void **)&m->d_tile_row, (m->n_tiles + 1) * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_tile_nz, (m->n_tiles + 1) * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_carry_row, m->n_tiles * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc(&m->d_carry_val, m->n_tiles * dtype_size(m->dtype)));
-    SMH_TRY(launch_merge_table(m->d_off, m->n_rows, m->nnz, m->n_tiles, m->d_tile_row, m->d_tile_nz, m->stream));
-    SMH_HIP(hipStreamSynchronize(m->stream));
+    t.n_tiles = (size_t)((items + kMergeTile - 1) / kMergeTile);
+    if (t.n_tiles) {
+        SMH_TRY(t.tile_row.alloc(t.n_tiles + 1));
+        SMH_TRY(t.tile_nz.alloc(t.n_tiles + 1));
+        SMH_TRY(t.carry_row.alloc(t.n_tiles));
+        SMH_TRY(t.carry_val.alloc(t.n_tiles * dtype_size(m->dtype)));
+        SMH_TRY(launch_merge_table(m->d_off, m->n_rows, m->nnz, t.n_tiles, t.tile_row.get(), t.tile_nz.get(), m->stream));
+        SMH_HIP(hipStreamSynchronize(m->stream));
+    }
+    t.state = Form::Ready;
+    m->merge = std::move(t);
     return SMH_OK;
 }
 
@@ -271,14 +254,10 @@ static int ensure_merge_ws(smh_crs *m) {
 // for the lane-group kernels anyway); the banded attempt -- an inspector pass, a table readback, a host pass over the
 // tiles: ~50 ms at 134 M rows -- then waits until the VECTOR family is actually used.
 static int ensure_ring_plan(smh_crs *m, bool with_bands = true) {
-    if (m->ring_planned && (!with_bands || m->ring_bands_tried)) return SMH_OK;
-    if (m->ring_planned) {  // planned without the banded attempt: plan again, completely
-        (void)hipFree(m->d_phase_ptr); (void)hipFree(m->d_phases);
-        m->d_phase_ptr = nullptr;
-        m->d_phases = nullptr;
-        m->ring_planned = false;
-    }
-    m->ring_bands_tried = with_bands;
+    if (m->ring.state == Form::Ready && (!with_bands || m->ring.bands_tried)) return SMH_OK;
+    m->ring = RingPlan();  // planned without the banded attempt: plan again, completely (the old plan goes first: no higher peak)
+    RingPlan p;
+    p.bands_tried = with_bands;
     const size_t n_tiles = (m->n_rows + 63) / 64;
     int cus = 256;
     hipDeviceProp_t prop;
@@ -296,26 +275,23 @@ static int ensure_ring_plan(smh_crs *m, bool with_bands = true) {
     blocks = (blocks + 7u) & ~7u;
     std::vector<uint32_t> cmin(n_tiles), cmax(n_tiles);
     if (n_tiles) {
+        Scratch scr;
         uint32_t *d_min = nullptr, *d_max = nullptr;
-        SMH_HIP(hipMalloc((void **)&d_min, n_tiles * sizeof(uint32_t)));
-        hipError_t e = hipMalloc((void **)&d_max, n_tiles * sizeof(uint32_t));
-        int rc = e == hipSuccess ? launch_tile_span(m->d_off, m->d_col, m->n_rows, n_tiles, d_min, d_max, m->stream)
-                                 : hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        if (rc == SMH_OK) {
-            e = hipMemcpyAsync(cmin.data(), d_min, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(cmax.data(), d_max, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-            if (e != hipSuccess) rc = hip_fail(e, "tile span readback", __FILE__, __LINE__);
-        }
-        (void)hipFree(d_min); (void)hipFree(d_max);
-        SMH_TRY(rc);
+        SMH_TRY(scr.alloc(&d_min, n_tiles));
+        SMH_TRY(scr.alloc(&d_max, n_tiles));
+        SMH_TRY(read_back(d_min, cmin.data(), n_tiles, m->stream, [&](uint32_t *) -> int {
+            SMH_TRY(launch_tile_span(m->d_off, m->d_col, m->n_rows, n_tiles, d_min, d_max, m->stream));
+            SMH_HIP(hipMemcpyAsync(cmax.data(), d_max, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+            return SMH_OK;
+        }));
     }
+    double span_fraction = 0.0;
     {  // locality statistic for AUTO: mean column span of a 64-row tile relative to n_cols
         double acc = 0.0;
         size_t used = 0;
         for (size_t t = 0; t < n_tiles; ++t)
             if (cmin[t] <= cmax[t]) { acc += (double)(cmax[t] - cmin[t]) + 1.0; ++used; }
-        m->span_fraction = used && m->n_cols ? acc / (double)used / (double)m->n_cols : 0.0;
+        span_fraction = used && m->n_cols ? acc / (double)used / (double)m->n_cols : 0.0;
     }
     std::vector<uint32_t> phase_ptr;
     std::vector<RingPhase> phases;
@@ -326,12 +302,12 @@ static int ensure_ring_plan(smh_crs *m, bool with_bands = true) {
     uint32_t noring_mode = 0;
     if (const char *e = getenv("SMH_GATHER_NT")) noring_mode = atoi(e) ? 2u : 0u;
     build_ring_plan(m->n_rows, kRingEntries, cmin.data(), cmax.data(), blocks, noring_mode, phase_ptr, phases,
-                    &m->ring_fraction);
-    m->ring_entries = kRingEntries;
+                    &p.fraction);
+    p.entries = kRingEntries;
     // f32 rows that do not fit 16384 columns but fit 32768: the wide ring (128 KiB of LDS, one 1024-thread block per CU
     // like f64, so half as many blocks).  Rows of 64 entries in a +-8192 band: 0.90 ms (K1s) -> see DESIGN.md.
     const char *wide_env = getenv("SMH_RING_WIDE");  // tuning knob: 0 = never
-    if (m->dtype == SMH_F32 && m->ring_fraction < 0.5 && !(wide_env && atoi(wide_env) == 0)) {
+    if (m->dtype == SMH_F32 && p.fraction < 0.5 && !(wide_env && atoi(wide_env) == 0)) {
         std::vector<uint32_t> phase_ptr_w;
         std::vector<RingPhase> phases_w;
         double frac_w = 0.0;
@@ -340,61 +316,53 @@ static int ensure_ring_plan(smh_crs *m, bool with_bands = true) {
         if (frac_w >= 0.5) {
             phase_ptr.swap(phase_ptr_w);
             phases.swap(phases_w);
-            m->ring_fraction = frac_w;
-            m->ring_entries = kRingEntriesWide;
+            p.fraction = frac_w;
+            p.entries = kRingEntriesWide;
             blocks = blocks_w;
         }
     }
     // Still mostly outside the ring: rows that reference a few narrow column intervals far apart (stencils on
     // structured grids) get the BANDED ring -- four bands of a quarter of the ring, one per interval of the tile.
-    m->ring_bands = 1;
     const char *band_env = getenv("SMH_RING_BANDS");  // tuning knob: 0 = never
-    if (with_bands && m->ring_fraction < 0.5 && n_tiles && m->nnz && !(band_env && atoi(band_env) == 0)) {
+    if (with_bands && p.fraction < 0.5 && n_tiles && m->nnz && !(band_env && atoi(band_env) == 0)) {
         const unsigned sizes[2] = {(unsigned)kRingEntries, (unsigned)kRingEntriesWide};
         const int n_sizes = m->dtype == SMH_F32 && !(wide_env && atoi(wide_env) == 0) ? 2 : 1;
         std::vector<uint32_t> h_win(n_tiles * 8);
-        uint32_t *d_win = nullptr, *d_count = nullptr;
-        SMH_HIP(hipMalloc((void **)&d_win, n_tiles * 8 * sizeof(uint32_t)));
-        hipError_t e = hipMalloc((void **)&d_count, sizeof(uint32_t));
-        int rc = e == hipSuccess ? SMH_OK : hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-        bool adopted = false;
-        for (int si = 0; si < n_sizes && rc == SMH_OK && !adopted; ++si) {
+        Scratch scr;
+        uint32_t *d_count = nullptr;
+        SMH_TRY(p.win.alloc(n_tiles * 8));
+        SMH_TRY(scr.alloc(&d_count, 1));
+        for (int si = 0; si < n_sizes && p.bands == 1; ++si) {
             const unsigned ring = sizes[si];
-            rc = launch_tile_intervals(m->d_off, m->d_col, m->n_rows, 64, ring / 4, d_win, d_count, m->stream);
-            if (rc == SMH_OK) {
-                e = hipMemcpyAsync(h_win.data(), d_win, n_tiles * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-                if (e != hipSuccess) rc = hip_fail(e, "tile interval readback", __FILE__, __LINE__);
-            }
-            if (rc != SMH_OK) break;
+            SMH_TRY(read_back(p.win.get(), h_win.data(), n_tiles * 8, m->stream, [&](uint32_t *d_win) {
+                return launch_tile_intervals(m->d_off, m->d_col, m->n_rows, 64, ring / 4, d_win, d_count, m->stream);
+            }));
             std::vector<uint32_t> phase_ptr_b;
             std::vector<RingPhase> phases_b;
             double frac_b = 0.0;
             const unsigned blocks_b = ring == (unsigned)kRingEntries || m->dtype == SMH_F64 ? blocks : ((blocks / 2) + 7u) & ~7u;
             build_ring_plan_banded(m->n_rows, ring, h_win.data(), blocks_b, noring_mode, phase_ptr_b, phases_b, &frac_b);
-            if (frac_b >= 0.5 && frac_b > m->ring_fraction) {
+            if (frac_b >= 0.5 && frac_b > p.fraction) {
                 phase_ptr.swap(phase_ptr_b);
                 phases.swap(phases_b);
-                m->ring_fraction = frac_b;
-                m->ring_entries = ring;
-                m->ring_bands = 4;
+                p.fraction = frac_b;
+                p.entries = ring;
+                p.bands = 4;
                 blocks = blocks_b;
-                adopted = true;
             }
         }
-        (void)hipFree(d_count);
-        if (adopted) m->d_ring_win = d_win;  // kept: the 16-bit ring slots are built from it on first use
-        else (void)hipFree(d_win);
-        SMH_TRY(rc);
+        if (p.bands != 4) p.win.reset();  // (kept with a banded plan: the 16-bit ring slots are built from it on first use)
     }
-    SMH_HIP(hipMalloc((void **)&m->d_phase_ptr, phase_ptr.size() * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_phases, (phases.size() + 1) * sizeof(RingPhase)));
-    SMH_HIP(hipMemcpy(m->d_phase_ptr, phase_ptr.data(), phase_ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SMH_TRY(p.phase_ptr.alloc(phase_ptr.size()));
+    SMH_TRY(p.phases.alloc(phases.size() + 1));
+    SMH_HIP(hipMemcpy(p.phase_ptr.get(), phase_ptr.data(), phase_ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!phases.empty())
-        SMH_HIP(hipMemcpy(m->d_phases, phases.data(), phases.size() * sizeof(RingPhase), hipMemcpyHostToDevice));
-    m->ring_blocks = blocks;
-    m->ring_n_phases = phases.size();
-    m->ring_planned = true;
+        SMH_HIP(hipMemcpy(p.phases.get(), phases.data(), phases.size() * sizeof(RingPhase), hipMemcpyHostToDevice));
+    p.blocks = blocks;
+    p.n_phases = phases.size();
+    p.state = Form::Ready;
+    m->ring = std::move(p);
+    m->span_fraction = span_fraction;
     return SMH_OK;
 }
 
@@ -409,47 +377,56 @@ int columns_within_n_cols(const smh_crs *m, const char *what) {
 
 // K2c: build the column-blocked copy, once per matrix
 static int ensure_colblock(smh_crs *m) {
-    if (m->cb_built) return SMH_OK;
+    if (m->cb.state == Form::Ready) return SMH_OK;
     SMH_TRY(columns_within_n_cols(m, "column-blocked variant"));
     const size_t blocks = cb_blocks_for(m);
     if (blocks == 0 || blocks > 128)
         return fail(SMH_ERR_INVALID, "column-blocked variant: %zu column blocks (supported: 1..128)", blocks);
     if ((uint64_t)blocks * (m->n_rows + 1) >= (1ull << 34)) return fail(SMH_ERR_OOM, "column-blocked offsets too large");
-    m->cb_shift = cb_shift_for(m);
-    SMH_TRY(build_colblock(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, m->cb_shift, blocks, &m->d_cb_off,
-                           &m->d_cb_col, &m->d_cb_val, m->stream));
-    m->cb_blocks = blocks;
+    ColBlock c;
+    c.shift = cb_shift_for(m);
+    uint32_t *off2 = nullptr, *col2 = nullptr;
+    void *val2 = nullptr;
+    SMH_TRY(build_colblock(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, c.shift, blocks, &off2, &col2, &val2, m->stream));
+    c.off.reset(off2);
+    c.col.reset(col2);
+    c.val.reset((char *)val2);
+    c.blocks = blocks;
     // tile height of the K1s launches: the tallest of 2048/1024/512/256 rows whose busiest tile fits the LDS stage
+    Scratch scr;
     uint32_t *d_max = nullptr;
-    SMH_HIP(hipMalloc((void **)&d_max, sizeof(uint32_t)));
+    SMH_TRY(scr.alloc(&d_max, 1));
     int rpt = 8;
-    int rc = SMH_OK;
     uint32_t worst = 0;
     for (; rpt >= 1; rpt >>= 1) {
         worst = 0;
-        for (size_t b = 0; b < blocks && rc == SMH_OK; ++b) {
+        for (size_t b = 0; b < blocks; ++b) {
             uint32_t h = 0;
-            rc = launch_stream_max_tile(m->d_cb_off + b * (m->n_rows + 1), m->n_rows, (size_t)kStreamRows * rpt, d_max, m->stream);
-            if (rc == SMH_OK) {
-                hipError_t e = hipMemcpyAsync(&h, d_max, sizeof h, hipMemcpyDeviceToHost, m->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-                if (e != hipSuccess) rc = hip_fail(e, "colblock tile statistic", __FILE__, __LINE__);
-            }
+            SMH_TRY(read_back(d_max, &h, 1, m->stream, [&](uint32_t *d) {
+                return launch_stream_max_tile(c.off.get() + b * (m->n_rows + 1), m->n_rows, (size_t)kStreamRows * rpt, d, m->stream);
+            }));
             worst = h > worst ? h : worst;
         }
-        if (rc != SMH_OK || worst <= (uint32_t)kStreamCap || rpt == 1) break;
+        if (worst <= (uint32_t)kStreamCap || rpt == 1) break;
     }
-    (void)hipFree(d_max);
-    SMH_TRY(rc);
-    m->cb_rpt = rpt < 1 ? 1 : rpt;
-    m->cb_single_pass = worst <= (uint32_t)kStreamCap;  // else 256-row tiles, several passes where needed
-    m->cb_built = true;
+    c.rpt = rpt < 1 ? 1 : rpt;
+    c.single_pass = worst <= (uint32_t)kStreamCap;  // else 256-row tiles, several passes where needed
+    c.state = Form::Ready;
+    m->cb = std::move(c);
     return SMH_OK;
 }
 
-// K2f: build the fused column-blocked copy, once per matrix (cf_ok == false afterwards: not describable -> K2c)
+// K2c's launches: one K1s sweep per column block, the later ones accumulating into y
+static int launch_colblock(const smh_crs *m, const void *x, void *y, hipStream_t s) {
+    for (size_t b = 0; b < m->cb.blocks; ++b)
+        SMH_TRY(launch_spmv_stream_block(m->dtype, m->cb.off.get() + b * (m->n_rows + 1), m->cb.col.get(), m->cb.val.get(), x, y,
+                                         m->n_rows, m->nnz, m->cb.rpt, m->cb.single_pass, b > 0, s));
+    return SMH_OK;
+}
+
+// K2f: build the fused column-blocked copy, once per matrix (Refused afterwards: not describable -> K2c)
 static int ensure_colfused(smh_crs *m) {
-    if (m->cf_built) return SMH_OK;
+    if (m->cf.state != Form::NotTried) return SMH_OK;
     SMH_TRY(columns_within_n_cols(m, "fused column-blocked variant"));
     const size_t blocks = cf_blocks_for(m);
     if (blocks > 255) return fail(SMH_ERR_INVALID, "fused column-blocked variant: %zu column blocks (supported: 1..255)", blocks);
@@ -457,33 +434,29 @@ static int ensure_colfused(smh_crs *m) {
     if (const char *e = getenv("SMH_COLFUSED_RT")) {  // tuning knob: rows per lane, 8 or 16
         if (atoi(e) == 8) rt = 8;
     }
+    ColFused c;
     bool fits = false;
-    SMH_TRY(build_colfused(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, cf_shift_for(m), blocks, rt, &m->cf_tiles,
-                           &m->d_cf_tile_row, &m->d_cf_seg, &m->d_cf_cnt, &m->d_cf_col, &m->d_cf_val, &fits, m->stream));
-    m->cf_shift = cf_shift_for(m);
-    m->cf_blocks = blocks;
-    m->cf_rt = rt;
-    m->cf_ok = fits;
-    m->cf_built = true;
+    uint32_t *tile_row = nullptr, *seg = nullptr, *col2 = nullptr;
+    uint8_t *cnt = nullptr;
+    void *val2 = nullptr;
+    SMH_TRY(build_colfused(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, cf_shift_for(m), blocks, rt, &c.tiles,
+                           &tile_row, &seg, &cnt, &col2, &val2, &fits, m->stream));
+    c.tile_row.reset(tile_row);
+    c.seg.reset(seg);
+    c.cnt.reset(cnt);
+    c.col.reset(col2);
+    c.val.reset((char *)val2);
+    c.shift = cf_shift_for(m);
+    c.blocks = blocks;
+    c.rt = rt;
+    c.state = fits ? Form::Ready : Form::Refused;
+    m->cf = std::move(c);
     return SMH_OK;
 }
 
-// K2s: the row-length split, once per matrix (split_ok == false afterwards: not worth it / not possible -> K2c)
+// K2s: the row-length split, once per matrix (Refused afterwards: not worth it / not possible -> K2c)
 constexpr uint32_t kSplitMinLong = 64;  // rows of this many entries and more form the LONG part
 static int finish_create(smh_crs *m, int validate);
-// the smh_crs_set_* settings a clone (and a handle updated in place) carries
-static void copy_knobs(smh_crs *dst, const smh_crs *src) {
-    dst->forced_lanes = src->forced_lanes;
-    dst->forced_chunks = src->forced_chunks;
-    dst->stream_rows_per_thread = src->stream_rows_per_thread;
-    dst->cb_forced_shift = src->cb_forced_shift;
-    dst->use_ring = src->use_ring;
-    dst->use_stream_xs = src->use_stream_xs;
-    dst->use_stream_direct = src->use_stream_direct;
-    dst->use_stream_vdict = src->use_stream_vdict;
-    dst->use_col16 = src->use_col16;
-}
-
 // Every handle is made here: a fresh handle on the current device over device arrays, with the create-time inspection done
 // (finish_create).  like (optional): the settings it takes, else the defaults.  Owned arrays go with the handle, also on failure;
 // borrowed ones are never freed by it.
@@ -497,7 +470,7 @@ static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_c
     m->dtype = dtype; m->device = current_device(); m->owns = owns;
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
     m->d_off = off; m->d_col = col; m->d_val = val;
-    if (like) copy_knobs(m, like);
+    if (like) m->knobs = like->knobs;
     const int rc = finish_create(m, validate);
     if (rc != SMH_OK) return keep_error(rc, [&] { (void)smh_crs_destroy(m); });
     *out = m;
@@ -512,155 +485,146 @@ static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_c
 }
 
 static int ensure_split(smh_crs *m) {
-    if (m->split_built) return SMH_OK;
+    if (m->split.state != Form::NotTried) return SMH_OK;
     SMH_TRY(columns_within_n_cols(m, "row-length split"));
-    m->split_built = true;
-    m->split_ok = false;
+    m->split.state = Form::Refused;  // until the build below is complete: a split that failed or does not pay is not tried again
     if (m->no_split || m->n_rows == 0 || m->nnz == 0) return SMH_OK;
-    size_t n_long = 0, nnz_long = 0;
+    RowSplit sp;
+    size_t nnz_long = 0;
     uint32_t *rows = nullptr;
     CrsArrays long_part, short_part;
-    SMH_TRY(build_colsplit(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, kSplitMinLong, &n_long, &nnz_long, &rows, &long_part.off,
+    SMH_TRY(build_colsplit(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, kSplitMinLong, &sp.n_long, &nnz_long, &rows, &long_part.off,
                            &long_part.col, &long_part.val, &short_part.off, &short_part.col, &short_part.val, m->stream));
+    sp.rows.reset(rows);
     // worth it when the long rows are a minority that holds a good part of the entries
-    const bool worth = n_long > 0 && n_long * 4 <= m->n_rows && nnz_long * 4 >= m->nnz;
-    if (!worth) {
-        (void)hipFree(rows);
-        return SMH_OK;
-    }
-    m->d_split_rows = rows;
-    m->split_n_long = n_long;
+    const bool worth = sp.n_long > 0 && sp.n_long * 4 <= m->n_rows && nnz_long * 4 >= m->nnz;
+    if (!worth) return SMH_OK;
     auto part = [&](size_t n_rows, size_t nnz, CrsArrays &arrays, uint32_t shift, smh_crs **out) -> int {
         SMH_TRY(wrap_arrays(m->dtype, nullptr, n_rows, m->n_cols, nnz, arrays, 0, out));
         (*out)->no_split = true;
-        (*out)->cb_forced_shift = shift;
+        (*out)->knobs.cb_forced_shift = shift;
         return SMH_OK;
     };
     // LONG: K2c with 2^18-column blocks (1.93 against 2.03 ms with 2^19 on C3's long part); SHORT: its own AUTO with 2^19
-    int rc = part(n_long, nnz_long, long_part, 18u, &m->split_long);
-    if (rc == SMH_OK) rc = part(m->n_rows, m->nnz - nnz_long, short_part, 19u, &m->split_short);
-    if (rc == SMH_OK) {
-        hipError_t e = hipMalloc(&m->d_split_y, (n_long ? n_long : 1) * dtype_size(m->dtype));
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->split_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->split_fork, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->split_join, hipEventDisableTiming);
-        if (e != hipSuccess) rc = hip_fail(e, "split workspace", __FILE__, __LINE__);
-    }
-    if (rc != SMH_OK)
-        return keep_error(rc, [&] {
-            (void)smh_crs_destroy(m->split_long); (void)smh_crs_destroy(m->split_short);
-            m->split_long = m->split_short = nullptr;
-            (void)hipFree(m->d_split_rows); m->d_split_rows = nullptr;
-        });
-    m->split_ok = true;
+    SMH_TRY(part(sp.n_long, nnz_long, long_part, 18u, &sp.long_part));
+    SMH_TRY(part(m->n_rows, m->nnz - nnz_long, short_part, 19u, &sp.short_part));
+    SMH_TRY(sp.y.alloc(sp.n_long * dtype_size(m->dtype)));
+    SMH_HIP(hipStreamCreateWithFlags(&sp.side, hipStreamNonBlocking));
+    SMH_HIP(hipEventCreateWithFlags(&sp.fork, hipEventDisableTiming));
+    SMH_HIP(hipEventCreateWithFlags(&sp.join, hipEventDisableTiming));
+    sp.state = Form::Ready;
+    m->split = std::move(sp);
     return SMH_OK;
+}
+// (the sub-handles go through smh_crs_destroy, like every handle)
+RowSplit::~RowSplit() {
+    (void)smh_crs_destroy(long_part);
+    (void)smh_crs_destroy(short_part);
+    rows.reset();
+    y.reset();
+    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+    if (fork) (void)hipEventDestroy(fork);
+    if (join) (void)hipEventDestroy(join);
 }
 
 // K1s: 16-bit column codes, once per matrix.  Kept only when EVERY tile has a description (stencils, bands): the kernel
 // variant then has no per-tile branch; any other matrix streams its u32 columns as before and nothing stays allocated.
 static int ensure_stream_codes(smh_crs *m) {
-    if (m->stream_coded) return SMH_OK;
-    m->stream_coded = true;
+    if (m->codes.state != Form::NotTried) return SMH_OK;
+    StreamCodes c;
+    c.state = Form::Refused;  // (nothing to describe, or some tile without a description)
     const size_t n_tiles = (m->n_rows + kStreamRows - 1) / kStreamRows;
-    if (n_tiles == 0 || m->nnz == 0) return SMH_OK;
-    uint32_t *d_count = nullptr, h_count = 0;
-    SMH_HIP(hipMalloc((void **)&m->d_stream_cwin, n_tiles * 8 * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&d_count, sizeof(uint32_t)));
-    int rc = launch_stream_windows(m->d_off, m->d_col, m->n_rows, m->d_stream_cwin, d_count, m->stream);
-    hipError_t e = hipSuccess;
-    if (rc == SMH_OK) e = hipMemcpyAsync(&h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost, m->stream);
-    if (rc == SMH_OK && e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    (void)hipFree(d_count);
-    if (rc == SMH_OK && e != hipSuccess) rc = hip_fail(e, "stream code table readback", __FILE__, __LINE__);
-    SMH_TRY(rc);
-    if ((size_t)h_count != n_tiles) {  // some tile's columns need more than 4 intervals of 16384
-        (void)hipFree(m->d_stream_cwin);
-        m->d_stream_cwin = nullptr;
-        return SMH_OK;
+    if (n_tiles && m->nnz) {
+        uint32_t h_count = 0;
+        SMH_TRY(c.cwin.alloc(n_tiles * 8));
+        SMH_TRY(read_back(&h_count, 1, m->stream, [&](uint32_t *d_count) {
+            return launch_stream_windows(m->d_off, m->d_col, m->n_rows, c.cwin.get(), d_count, m->stream);
+        }));
+        if ((size_t)h_count == n_tiles) c.state = Form::Ready;
+        else c.cwin.reset();  // some tile's columns need more than 4 intervals of 16384
     }
-    const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
-    SMH_HIP(hipMalloc((void **)&m->d_stream_code, n_out * sizeof(uint16_t)));
-    SMH_HIP(hipMemsetAsync(m->d_stream_code, 0, n_out * sizeof(uint16_t), m->stream));
-    SMH_TRY(launch_stream_codes(m->d_off, m->d_col, m->d_stream_cwin, m->n_rows, m->d_stream_code, m->stream));
-    m->stream_direct = false;
-    // ... and with rows of at most 255 entries the row boundaries shrink from a u32 offset to a byte per row
-    if (m->max_row_len <= 255u) {
-        SMH_HIP(hipMalloc((void **)&m->d_stream_len8, n_tiles * kStreamRows));
-        SMH_HIP(hipMalloc((void **)&m->d_stream_tbase, (n_tiles + 1) * sizeof(uint32_t)));
-        SMH_TRY(launch_stream_len8(m->d_off, m->n_rows, m->d_stream_len8, m->d_stream_tbase, m->stream));
-        // how much of x a tile's intervals span (decides whether the body that stages x in LDS applies)
-        uint32_t *d_xs = nullptr, h_xs[2] = {0xFFFFFFFFu, 0};
-        SMH_HIP(hipMalloc((void **)&d_xs, 2 * sizeof(uint32_t)));
-        int rc2 = launch_stream_xs_stats(m->d_stream_cwin, n_tiles, d_xs, m->stream);
-        hipError_t e2 = rc2 == SMH_OK ? hipMemcpyAsync(h_xs, d_xs, sizeof h_xs, hipMemcpyDeviceToHost, m->stream) : hipSuccess;
-        if (rc2 == SMH_OK && e2 == hipSuccess) e2 = hipStreamSynchronize(m->stream);
-        (void)hipFree(d_xs);
-        SMH_TRY(rc2);
-        if (e2 != hipSuccess) return hip_fail(e2, "stream window statistics", __FILE__, __LINE__);
-        m->stream_xs_chunks = h_xs[0];
-        m->stream_xs_end = h_xs[1];
-        // ... and how many rows have an odd length (decides whether the unskewed product stage of K1s XD applies)
-        unsigned long long *d_odd = nullptr, h_odd = 0;
-        SMH_HIP(hipMalloc((void **)&d_odd, sizeof(unsigned long long)));
-        int rc3 = launch_stream_odd_rows(m->d_stream_len8, n_tiles * kStreamRows, d_odd, m->stream);
-        hipError_t e3 = rc3 == SMH_OK ? hipMemcpyAsync(&h_odd, d_odd, sizeof h_odd, hipMemcpyDeviceToHost, m->stream) : hipSuccess;
-        if (rc3 == SMH_OK && e3 == hipSuccess) e3 = hipStreamSynchronize(m->stream);
-        (void)hipFree(d_odd);
-        SMH_TRY(rc3);
-        if (e3 != hipSuccess) return hip_fail(e3, "stream row-length statistics", __FILE__, __LINE__);
-        m->stream_odd_rows = (uint64_t)h_odd;
+    if (c.state == Form::Ready) {
+        const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
+        SMH_TRY(c.code.alloc(n_out));
+        SMH_HIP(hipMemsetAsync(c.code.get(), 0, n_out * sizeof(uint16_t), m->stream));
+        SMH_TRY(launch_stream_codes(m->d_off, m->d_col, c.cwin.get(), m->n_rows, c.code.get(), m->stream));
+        // ... and with rows of at most 255 entries the row boundaries shrink from a u32 offset to a byte per row
+        if (m->max_row_len <= 255u) {
+            SMH_TRY(c.len8.alloc(n_tiles * kStreamRows));
+            SMH_TRY(c.tbase.alloc(n_tiles + 1));
+            SMH_TRY(launch_stream_len8(m->d_off, m->n_rows, c.len8.get(), c.tbase.get(), m->stream));
+            // how much of x a tile's intervals span (decides whether the body that stages x in LDS applies)
+            uint32_t h_xs[2] = {0xFFFFFFFFu, 0};
+            SMH_TRY(read_back(h_xs, 2, m->stream, [&](uint32_t *d_xs) { return launch_stream_xs_stats(c.cwin.get(), n_tiles, d_xs, m->stream); }));
+            c.xs_chunks = h_xs[0];
+            c.xs_end = h_xs[1];
+            // ... and how many rows have an odd length (decides whether the unskewed product stage of K1s XD applies)
+            unsigned long long h_odd = 0;
+            SMH_TRY(read_back(&h_odd, 1, m->stream, [&](unsigned long long *d_odd) {
+                return launch_stream_odd_rows(c.len8.get(), n_tiles * kStreamRows, d_odd, m->stream);
+            }));
+            c.odd_rows = (uint64_t)h_odd;
+        }
+        SMH_HIP(hipStreamSynchronize(m->stream));
     }
-    SMH_HIP(hipStreamSynchronize(m->stream));
+    m->codes = std::move(c);
     return SMH_OK;
-}
-
-static void drop_stream_codes(smh_crs *m) {
-    (void)hipFree(m->d_stream_cwin); (void)hipFree(m->d_stream_code); (void)hipFree(m->d_stream_len8); (void)hipFree(m->d_stream_tbase);
-    m->d_stream_cwin = nullptr;
-    m->d_stream_code = nullptr;
-    m->d_stream_len8 = nullptr;
-    m->d_stream_tbase = nullptr;
-    m->stream_coded = false;
-    m->stream_direct = m->stream_vdict = false;
-    m->stream_vdict_xs = 0;
 }
 
 // does the VECTOR family run as K1r (LDS x-ring) for this matrix?
 static int vector_uses_ring(smh_crs *m, bool *out) {
     *out = false;
-    if (m->use_ring == 0 || m->n_rows == 0) return SMH_OK;
+    if (m->knobs.use_ring == 0 || m->n_rows == 0) return SMH_OK;
     SMH_TRY(ensure_ring_plan(m));
     // the pipelined body also wins without the ring (its global-gather phases), so it is the default
     // whenever its lane widths apply; mode 0 keeps the plain K1 kernel selectable
     *out = true;
     // 16-bit columns for the ring phases: a ring slot is `column mod 16384`, so the low half of a column is all a
     // ring phase reads -- 6 instead of 8 bytes per f32 entry from HBM.  One extra 2-byte-per-entry array, built once.
-    int want = m->use_col16;
+    int want = m->knobs.use_col16;
     if (const char *e = getenv("SMH_RING_COL16")) want = atoi(e) ? 1 : 0;  // tuning knob
     // (the banded plan cannot do without: its gathers take the ring slot from that array)
-    const bool use16 = m->ring_bands == 4 || want == 1 || (want < 0 && m->ring_fraction >= 0.25);
-    if (use16 && !m->d_col16 && m->nnz) {
+    const bool use16 = m->ring.bands == 4 || want == 1 || (want < 0 && m->ring.fraction >= 0.25);
+    if (use16 && !m->ring.col16.get() && m->nnz) {
         const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
-        SMH_HIP(hipMalloc((void **)&m->d_col16, n_out * sizeof(uint16_t)));
-        if (m->ring_bands == 4) {
-            SMH_HIP(hipMemsetAsync(m->d_col16, 0, n_out * sizeof(uint16_t), m->stream));
-            SMH_TRY(launch_ring_band_codes(m->d_off, m->d_col, m->d_ring_win, m->n_rows, m->ring_entries / 4, m->d_col16, m->stream));
+        DevArray<uint16_t> col16;
+        SMH_TRY(col16.alloc(n_out));
+        if (m->ring.bands == 4) {
+            SMH_HIP(hipMemsetAsync(col16.get(), 0, n_out * sizeof(uint16_t), m->stream));
+            SMH_TRY(launch_ring_band_codes(m->d_off, m->d_col, m->ring.win.get(), m->n_rows, m->ring.entries / 4, col16.get(), m->stream));
         } else {
-            SMH_TRY(launch_narrow_columns(m->d_col, m->nnz, m->d_col16, n_out, m->stream));
+            SMH_TRY(launch_narrow_columns(m->d_col, m->nnz, col16.get(), n_out, m->stream));
         }
         SMH_HIP(hipStreamSynchronize(m->stream));
-    } else if (!use16 && m->d_col16) {
-        (void)hipFree(m->d_col16);
-        m->d_col16 = nullptr;
+        m->ring.col16 = std::move(col16);
+    } else if (!use16) {
+        m->ring.col16.reset();
     }
     return SMH_OK;
+}
+
+// Which derived forms go when the matrix changes under them (each is rebuilt on its next use); dropping = a default-constructed form.
+enum class Changed { Values, Order, BlockWidth };  // update_values / apply's values-only route; sort_rows; set_colblock_shift
+static void invalidate(smh_crs *m, Changed what) {
+    // the column-blocked / split / tiled copies hold the values, keep storage order inside a (row, block) pair, and are cut by the block width
+    m->cb = ColBlock();
+    m->cf = ColFused();
+    m->split = RowSplit();
+    m->tiled = Tiled();
+    if (what == Changed::Values) m->dict.state = Form::NotTried;  // (the dictionary array stays: a product in flight may still read it)
+    if (what == Changed::Order) {
+        // the K1s codes and the 16-bit column array follow the storage order too; the ring plan's phases and windows stay: they
+        // depend on each tile's column set, not on order
+        m->codes = StreamCodes();
+        m->ring.col16.reset();
+    }
 }
 
 // K1s configuration of this handle
 static int stream_rpt(const smh_crs *m) {
     // rows per thread: 512-row tiles measured no better than 256-row tiles (1.86 vs 1.80 ms on the 512^3
     // Laplacian), so one row per thread unless asked (SMH_STREAM_RPT=2, tuning knob)
-    int want = m->stream_rows_per_thread;
+    int want = m->knobs.stream_rows_per_thread;
     if (const char *e = getenv("SMH_STREAM_RPT")) want = atoi(e);
     return want == 2 && m->max_tile512_entries <= (uint32_t)kStreamCap ? 2 : 1;
 }
@@ -697,13 +661,13 @@ static int stream_cfg(smh_crs *m, StreamCfg *c, bool recode = false) {
     // (single-pass tiles only: on dense multi-pass tiles -- banded C2 through K1s -- the decode costs more than
     // the bytes save, 0.83 vs 0.80 ms)
     if (!(c16_env && atoi(c16_env) == 0) && c->rpt == 1 && c->single_pass) {
-        const bool first = !m->stream_coded;
+        const bool first = m->codes.state == Form::NotTried;
         SMH_TRY(ensure_stream_codes(m));
         if (first) recode = true;  // (the build itself: allocations and synchronisations anyway)
-        c->code = m->d_stream_code;
-        c->cwin = m->d_stream_code ? m->d_stream_cwin : nullptr;
+        c->code = m->codes.code.get();
+        c->cwin = m->codes.code.get() ? m->codes.cwin.get() : nullptr;
         static const bool l8_off = getenv("SMH_STREAM_L8") && atoi(getenv("SMH_STREAM_L8")) == 0;  // tuning knob
-        if (c->cwin && !l8_off) { c->len8 = m->d_stream_len8; c->tbase = m->d_stream_tbase; }
+        if (c->cwin && !l8_off) { c->len8 = m->codes.len8.get(); c->tbase = m->codes.tbase.get(); }
         static const bool small_off = getenv("SMH_STREAM_SMALL") && atoi(getenv("SMH_STREAM_SMALL")) == 0;  // tuning knob
         c->small = !small_off && m->have_stats && m->max_tile_entries <= (uint32_t)kStreamCapSmall;
         static const bool xs_off = getenv("SMH_STREAM_XS") && atoi(getenv("SMH_STREAM_XS")) == 0;  // tuning knob
@@ -712,55 +676,62 @@ static int stream_cfg(smh_crs *m, StreamCfg *c, bool recode = false) {
         // 4096-entry stage pays on f32 only (grid planes 1024 wide, x of 17-34 MB: -7 .. -9 %; f64, LDS-limited to three blocks per
         // CU: +3 .. +10 %).  (Round 2 had 8 MB / 32 MB here: its inspector described a tile whose columns span < 16384 as ONE interval,
         // so a 64^3 .. 100^3 cube staged its whole span or nothing.)
-        const bool forced = m->use_stream_xs == 1;
+        const bool forced = m->knobs.use_stream_xs == 1;
         const size_t x_bytes = m->n_cols * dtype_size(m->dtype);
         const bool on2 = forced || x_bytes >= ((size_t)1 << 20), on4 = forced || (x_bytes >= ((size_t)8 << 20) && m->dtype == SMH_F32);
-        c->xs = (xs_off || m->use_stream_xs == 0 || !c->small || !c->len8) ? 0
-                : (m->stream_xs_chunks <= 2u * kBlock && on2) ? 2
-                : (m->stream_xs_chunks <= 4u * kBlock && on4) ? 4 : 0;
+        c->xs = (xs_off || m->knobs.use_stream_xs == 0 || !c->small || !c->len8) ? 0
+                : (m->codes.xs_chunks <= 2u * kBlock && on2) ? 2
+                : (m->codes.xs_chunks <= 4u * kBlock && on4) ? 4 : 0;
         // K1s XD: the code array as stage offsets.  The unskewed product stage it goes with collides on rows of even length, so
         // automatic = most rows odd (stencils with a diagonal)
         static const bool xd_off = getenv("SMH_STREAM_XD") && atoi(getenv("SMH_STREAM_XD")) == 0;  // tuning knob
-        const bool want_direct = c->code && c->xs != 0 && !xd_off && m->use_stream_direct != 0 &&
-                                 (m->use_stream_direct == 1 || 2 * m->stream_odd_rows >= (uint64_t)m->n_rows);
+        const bool want_direct = c->code && c->xs != 0 && !xd_off && m->knobs.use_stream_direct != 0 &&
+                                 (m->knobs.use_stream_direct == 1 || 2 * m->codes.odd_rows >= (uint64_t)m->n_rows);
         // K1s XD-V: the matrix's distinct values in a dictionary, their indices in the codes' spare bits (spmv_stream_xd.hip) -- when
         // the values allow it (at most 32 bit patterns; 16 with the 4096-entry stage).  Looked at once per matrix, and again after
         // smh_crs_update_values.
         static const bool vd_off = getenv("SMH_STREAM_VDICT") && atoi(getenv("SMH_STREAM_VDICT")) == 0;  // tuning knob
-        bool want_vdict = want_direct && !vd_off && m->use_stream_vdict != 0 && m->stream_dict_state != 0;
+        bool want_vdict = want_direct && !vd_off && m->knobs.use_stream_vdict != 0 && m->dict.state != Form::Refused;
         bool dict_rebuilt = false;  // (the indices in the codes belong to the dictionary they were made with)
-        if (recode && want_vdict && m->stream_dict_state < 0) {
-            if (!m->d_stream_dict) SMH_HIP(hipMalloc(&m->d_stream_dict, 32 * dtype_size(m->dtype)));
+        if (recode && want_vdict && m->dict.state == Form::NotTried) {
+            if (!m->dict.values.get()) SMH_TRY(m->dict.values.alloc(32 * dtype_size(m->dtype)));
             SMH_HIP(hipDeviceSynchronize());  // (a product in flight may still read the dictionary)
             uint32_t n_vals = 0;
-            SMH_TRY(stream_value_dict(m->dtype, m->d_val, m->nnz, m->d_stream_dict, &n_vals, m->stream));
-            m->stream_dict_n = n_vals;
-            m->stream_dict_state = n_vals ? 1 : 0;
+            SMH_TRY(stream_value_dict(m->dtype, m->d_val, m->nnz, m->dict.values.get(), &n_vals, m->stream));
+            m->dict.n = n_vals;
+            m->dict.state = n_vals ? Form::Ready : Form::Refused;
             dict_rebuilt = true;
         }
-        want_vdict = want_vdict && m->stream_dict_state == 1 && m->stream_dict_n <= stream_value_dict_capacity(c->xs);
-        const bool form_ok = want_direct == m->stream_direct && want_vdict == m->stream_vdict && (!want_vdict || m->stream_vdict_xs == c->xs) &&
-                             !(dict_rebuilt && (want_vdict || m->stream_vdict));
+        want_vdict = want_vdict && m->dict.state == Form::Ready && m->dict.n <= stream_value_dict_capacity(c->xs);
+        const bool form_ok = want_direct == m->codes.direct && want_vdict == m->codes.vdict && (!want_vdict || m->codes.vdict_xs == c->xs) &&
+                             !(dict_rebuilt && (want_vdict || m->codes.vdict));
         if (recode && c->code && !form_ok) {
             SMH_HIP(hipDeviceSynchronize());  // (a product enqueued on any stream may still read the array)
             if (want_direct)
-                SMH_TRY(launch_stream_stage_codes(m->d_off, m->d_col, m->d_stream_cwin, m->n_rows, (uint32_t)dtype_size(m->dtype), m->d_stream_code, m->stream));
+                SMH_TRY(launch_stream_stage_codes(m->d_off, m->d_col, m->codes.cwin.get(), m->n_rows, (uint32_t)dtype_size(m->dtype), m->codes.code.get(), m->stream));
             else
-                SMH_TRY(launch_stream_codes(m->d_off, m->d_col, m->d_stream_cwin, m->n_rows, m->d_stream_code, m->stream));
+                SMH_TRY(launch_stream_codes(m->d_off, m->d_col, m->codes.cwin.get(), m->n_rows, m->codes.code.get(), m->stream));
             if (want_vdict)
-                SMH_TRY(launch_stream_value_codes(m->dtype, m->d_val, m->nnz, m->d_stream_dict, m->stream_dict_n, c->xs, m->d_stream_code, m->stream));
+                SMH_TRY(launch_stream_value_codes(m->dtype, m->d_val, m->nnz, m->dict.values.get(), m->dict.n, c->xs, m->codes.code.get(), m->stream));
             SMH_HIP(hipStreamSynchronize(m->stream));
-            m->stream_direct = want_direct;
-            m->stream_vdict = want_vdict;
-            m->stream_vdict_xs = want_vdict ? c->xs : 0;
+            m->codes.direct = want_direct;
+            m->codes.vdict = want_vdict;
+            m->codes.vdict_xs = want_vdict ? c->xs : 0;
         }
         // (stage offsets without a stage -- xs == 0 after a setter that was not followed by a prepare cannot happen: the setters
         // recode; an x too short / misaligned for the stage is handled per call in stream_launch)
-        c->direct = c->code && m->stream_direct;
-        c->dict = c->direct && m->stream_vdict ? m->d_stream_dict : nullptr;
-        c->dict_high = c->dict && stream_value_dict_high(m->dtype, m->stream_dict_n, m->stream_vdict_xs);
+        c->direct = c->code && m->codes.direct;
+        c->dict = c->direct && m->codes.vdict ? m->dict.values.get() : nullptr;
+        c->dict_high = c->dict && stream_value_dict_high(m->dtype, m->dict.n, m->codes.vdict_xs);
     }
     return SMH_OK;
+}
+
+// a setting that decides the code array's meaning has changed: the array (if it was built) is rewritten now, not inside a later launch
+static int recode_stream(smh_crs *m) {
+    if (m->codes.state == Form::NotTried) return SMH_OK;
+    StreamCfg c;
+    return stream_cfg(m, &c, true);
 }
 
 // one K1s launch over the tiles [t0, t1) with the configuration `c`
@@ -771,7 +742,7 @@ static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x
     // 16-byte block (hence page, hence allocation granule) its valid entry lies in.  f32: the last chunk holds a valid entry when
     // x_len rounded up to 4 reaches stream_xs_end; f64: its SECOND load starts at stream_xs_end - 2 and must hold a valid entry
     // too (x_len >= stream_xs_end - 1), else the gathers stay global
-    const bool xs_ok = ((m->dtype == SMH_F64 ? x_len + 1 : ((x_len + 3) & ~(size_t)3)) >= (size_t)m->stream_xs_end) &&
+    const bool xs_ok = ((m->dtype == SMH_F64 ? x_len + 1 : ((x_len + 3) & ~(size_t)3)) >= (size_t)m->codes.xs_end) &&
                        (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
     if (c.direct) {
         if (xs_ok && c.xs)
@@ -783,6 +754,14 @@ static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x
     }
     return launch_spmv_stream(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->owns, c.rpt, c.single_pass,
                               dot_partials, c.code, c.cwin, c.len8, c.tbase, dot_lhs, s, c.small, xs_ok ? c.xs : 0, t0, t1);
+}
+
+// one K1r launch over the plan's row ranges [b0, b1) (dot_partials: the DOT form, whole plan only -- see launch_spmv_ring2)
+static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u) {
+    // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
+    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(), m->d_val, x, y, m->n_rows, m->nnz,
+                             m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
+                             m->ring.bands, s, dot_partials, b0, b1);
 }
 
 // any_lhs: the dot is taken with a vector of its own (n_rows entries; SparseMatrix::inner_prod) instead of x itself, so
@@ -807,11 +786,7 @@ int spmv_enqueue(smh_crs *m, const void *x, size_t x_len, void *y, int variant, 
         case SMH_SPMV_VECTOR: {
             bool ring = false;
             SMH_TRY(vector_uses_ring(m, &ring));
-            if (ring)
-                // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
-                return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->d_col16, m->d_val, x, y, m->n_rows,
-                                         m->nnz, m->owns || m->nnz % 4 == 0, m->ring_blocks, m->d_phase_ptr, m->d_phases,
-                                         m->ring_entries, m->ring_bands, s);
+            if (ring) return launch_ring(m, x, y, s);
             return launch_spmv_vector(m->dtype, auto_lanes(m), m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, s);
         }
         case SMH_SPMV_SEQ:
@@ -824,58 +799,50 @@ int spmv_enqueue(smh_crs *m, const void *x, size_t x_len, void *y, int variant, 
         case SMH_SPMV_COLSPLIT: {
             {
                 const int rc = ensure_split(m);
-                // AUTO chose this plan and its lazy build failed (scratch out of memory, ...): the plan is marked refused
-                // (split_built && !split_ok) and AUTO resolves again within this call -- K2c / K2f / K1 can still serve the product
-                if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE) {
-                    m->split_built = true;
-                    m->split_ok = false;
+                // AUTO chose this plan and its lazy build failed (scratch out of memory, ...): the builder has marked the plan
+                // Refused and AUTO resolves again within this call -- K2c / K2f / K1 can still serve the product
+                if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && m->split.state == Form::Refused) {
                     g_err[0] = 0;
                     return spmv_enqueue(m, x, x_len, y, variant, s, dot_partials, dot_lhs);
                 }
                 SMH_TRY(rc);
             }
-            if (m->split_ok) {
+            if (m->split.state == Form::Ready) {
                 // The two parts lean on different resources (LONG: the L2 gather path; SHORT: HBM streams and latency), which
                 // suggests running LONG on a stream of its own beside SHORT (fork and join by events).  Measured on C3, one box:
                 // 2.90 ms overlapped against 2.79 ms back to back -- K2f sizes its rounds to the whole chip and the blocks of
                 // x of the two parts evict each other -- so it is a knob, off by default (SMH_COLSPLIT_OVERLAP=1)
                 static const bool overlap = getenv("SMH_COLSPLIT_OVERLAP") && atoi(getenv("SMH_COLSPLIT_OVERLAP")) != 0;
-                hipStream_t sl = overlap ? m->split_stream : s;
+                hipStream_t sl = overlap ? m->split.side : s;
                 if (overlap) {
-                    SMH_HIP(hipEventRecord(m->split_fork, s));
-                    SMH_HIP(hipStreamWaitEvent(sl, m->split_fork, 0));
+                    SMH_HIP(hipEventRecord(m->split.fork, s));
+                    SMH_HIP(hipStreamWaitEvent(sl, m->split.fork, 0));
                 }
-                SMH_TRY(spmv_enqueue(m->split_long, x, x_len, m->d_split_y, SMH_SPMV_AUTO, sl));  // the long rows, compacted
-                if (overlap) SMH_HIP(hipEventRecord(m->split_join, sl));
-                SMH_TRY(spmv_enqueue(m->split_short, x, x_len, y, SMH_SPMV_AUTO, s));             // every row (0 for the long ones)
-                if (overlap) SMH_HIP(hipStreamWaitEvent(s, m->split_join, 0));
-                return launch_split_scatter(m->dtype, m->d_split_rows, m->d_split_y, m->split_n_long, y, s);
+                SMH_TRY(spmv_enqueue(m->split.long_part, x, x_len, m->split.y.get(), SMH_SPMV_AUTO, sl));  // the long rows, compacted
+                if (overlap) SMH_HIP(hipEventRecord(m->split.join, sl));
+                SMH_TRY(spmv_enqueue(m->split.short_part, x, x_len, y, SMH_SPMV_AUTO, s));             // every row (0 for the long ones)
+                if (overlap) SMH_HIP(hipStreamWaitEvent(s, m->split.join, 0));
+                return launch_split_scatter(m->dtype, m->split.rows.get(), m->split.y.get(), m->split.n_long, y, s);
             }
             SMH_TRY(ensure_colblock(m));  // not worth splitting: the per-block launches
-            for (size_t b = 0; b < m->cb_blocks; ++b)
-                SMH_TRY(launch_spmv_stream_block(m->dtype, m->d_cb_off + b * (m->n_rows + 1), m->d_cb_col, m->d_cb_val, x, y,
-                                                 m->n_rows, m->nnz, m->cb_rpt, m->cb_single_pass, b > 0, s));
-            return SMH_OK;
+            return launch_colblock(m, x, y, s);
         }
         case SMH_SPMV_COLFUSED: {
             SMH_TRY(ensure_colfused(m));
-            if (m->cf_ok)
-                return launch_spmv_colfused(m->dtype, m->cf_rt, m->d_cf_tile_row, m->cf_tiles, m->d_cf_seg, m->d_cf_cnt, m->d_cf_col, m->d_cf_val,
-                                            x, y, m->n_rows, m->nnz, (uint32_t)m->cf_blocks, m->device, s);
+            if (m->cf.state == Form::Ready)
+                return launch_spmv_colfused(m->dtype, m->cf.rt, m->cf.tile_row.get(), m->cf.tiles, m->cf.seg.get(), m->cf.cnt.get(), m->cf.col.get(), m->cf.val.get(),
+                                            x, y, m->n_rows, m->nnz, (uint32_t)m->cf.blocks, m->device, s);
         }
         [[fallthrough]];  // a (row, block) pair with more than 255 entries: the per-block launches
         case SMH_SPMV_COLBLOCK: {
             SMH_TRY(ensure_colblock(m));
-            for (size_t b = 0; b < m->cb_blocks; ++b)
-                SMH_TRY(launch_spmv_stream_block(m->dtype, m->d_cb_off + b * (m->n_rows + 1), m->d_cb_col, m->d_cb_val, x, y,
-                                                 m->n_rows, m->nnz, m->cb_rpt, m->cb_single_pass, b > 0, s));
-            return SMH_OK;
+            return launch_colblock(m, x, y, s);
         }
         case SMH_SPMV_TILED: {
             const int rc = tiled_build(m);
             // as above: a failed lazy build (K2t needs ~5 x 4 B x nnz of scratch, a copy of the entries and a product buffer)
-            // leaves t2_built && !t2_ok, which AUTO's rule reads as "does not fit" -- resolve again within this call
-            if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && m->t2_built && !m->t2_ok) {
+            // leaves the form Refused, which AUTO's rule reads as "does not fit" -- resolve again within this call
+            if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && m->tiled.state == Form::Refused) {
                 g_err[0] = 0;
                 return spmv_enqueue(m, x, x_len, y, variant, s, dot_partials, dot_lhs);
             }
@@ -884,8 +851,8 @@ int spmv_enqueue(smh_crs *m, const void *x, size_t x_len, void *y, int variant, 
         }
         case SMH_SPMV_MERGE:
             SMH_TRY(ensure_merge_ws(m));
-            return launch_spmv_merge(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->n_tiles,
-                                     m->d_tile_row, m->d_tile_nz, m->d_carry_row, m->d_carry_val, s);
+            return launch_spmv_merge(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->merge.n_tiles,
+                                     m->merge.tile_row.get(), m->merge.tile_nz.get(), m->merge.carry_row.get(), m->merge.carry_val.get(), s);
         default:
             return fail(SMH_ERR_INVALID, "unknown SpMV variant %d", variant);
     }
@@ -906,9 +873,9 @@ int spmv_rows_granularity(smh_crs *m, int variant, size_t *gran_out) {
     } else if (v == SMH_SPMV_VECTOR) {
         bool ring = false;
         SMH_TRY(vector_uses_ring(m, &ring));
-        if (ring && m->ring_blocks) {
+        if (ring && m->ring.blocks) {
             const size_t n_tiles = (m->n_rows + 63) / 64;
-            *gran_out = ((n_tiles + m->ring_blocks - 1) / m->ring_blocks) * 64;  // build_ring_plan: tiles per row range
+            *gran_out = ((n_tiles + m->ring.blocks - 1) / m->ring.blocks) * 64;  // build_ring_plan: tiles per row range
         }
     }
     return SMH_OK;
@@ -933,9 +900,7 @@ int spmv_enqueue_rows(smh_crs *m, const void *x, size_t x_len, void *y, int vari
         return stream_launch(m, c, x, x_len, y, s, dot_partials, dot_lhs, row0 / gran, (row1 + gran - 1) / gran);
     }
     if (dot_partials) return fail(SMH_ERR_INVALID, "a product by parts with the dot epilogue needs the CSR-stream kernel");
-    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->d_col16, m->d_val, x, y, m->n_rows, m->nnz,
-                             m->owns || m->nnz % 4 == 0, m->ring_blocks, m->d_phase_ptr, m->d_phases, m->ring_entries, m->ring_bands, s, nullptr,
-                             (unsigned)(row0 / gran), (unsigned)((row1 + gran - 1) / gran));
+    return launch_ring(m, x, y, s, nullptr, (unsigned)(row0 / gran), (unsigned)((row1 + gran - 1) / gran));
 }
 
 // The same for a SHORT run of rows (a partition block's boundary rows: a few thousand), any row0 / row1.  One ring workgroup walks its
@@ -974,30 +939,21 @@ static int finish_create(smh_crs *m, int validate) {
 static int finish_create_inner(smh_crs *m, int validate) {
     SMH_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     if (m->n_rows > 0) {
-        CrsStats *d_st = nullptr, h_st;
-        SMH_HIP(hipMalloc((void **)&d_st, sizeof(CrsStats)));
-        int rc = launch_crs_stats(m->d_off, m->d_col, m->n_rows, m->nnz, d_st, m->stream);
-        if (rc == SMH_OK) {
-            hipError_t e = hipMemcpyAsync(&h_st, d_st, sizeof h_st, hipMemcpyDeviceToHost, m->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-            // (reuse the first word of the scratch for the K1s tile statistic)
-            if (e == hipSuccess && !(h_st.bad & 1u)) {
-                uint32_t mt = 0;
-                rc = launch_stream_max_tile(m->d_off, m->n_rows, kStreamRows, &d_st->max_row_len, m->stream);
-                if (rc == SMH_OK) e = hipMemcpyAsync(&mt, &d_st->max_row_len, sizeof mt, hipMemcpyDeviceToHost, m->stream);
-                if (rc == SMH_OK && e == hipSuccess) e = hipStreamSynchronize(m->stream);
-                m->max_tile_entries = mt;
-                if (rc == SMH_OK && e == hipSuccess)
-                    rc = launch_stream_max_tile(m->d_off, m->n_rows, 2 * kStreamRows, &d_st->max_row_len, m->stream);
-                if (rc == SMH_OK && e == hipSuccess) e = hipMemcpyAsync(&mt, &d_st->max_row_len, sizeof mt, hipMemcpyDeviceToHost, m->stream);
-                if (rc == SMH_OK && e == hipSuccess) e = hipStreamSynchronize(m->stream);
-                m->max_tile512_entries = mt;
+        CrsStats h_st;
+        {
+            Scratch scr;
+            CrsStats *d_st = nullptr;
+            SMH_TRY(scr.alloc(&d_st, 1));
+            SMH_TRY(read_back(d_st, &h_st, 1, m->stream, [&](CrsStats *d) { return launch_crs_stats(m->d_off, m->d_col, m->n_rows, m->nnz, d, m->stream); }));
+            // (reuse the first word of the scratch for the K1s tile statistics: 256-row and 512-row tiles)
+            if (!(h_st.bad & 1u)) {
+                uint32_t *d_word = &d_st->max_row_len;
+                SMH_TRY(read_back(d_word, &m->max_tile_entries, 1, m->stream,
+                                  [&](uint32_t *d) { return launch_stream_max_tile(m->d_off, m->n_rows, kStreamRows, d, m->stream); }));
+                SMH_TRY(read_back(d_word, &m->max_tile512_entries, 1, m->stream,
+                                  [&](uint32_t *d) { return launch_stream_max_tile(m->d_off, m->n_rows, 2 * kStreamRows, d, m->stream); }));
             }
-            if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-            if (e != hipSuccess) rc = hip_fail(e, "crs stats readback", __FILE__, __LINE__);
         }
-        (void)hipFree(d_st);
-        SMH_TRY(rc);
         m->max_row_len = h_st.max_row_len;
         m->max_col = h_st.max_col;
         m->min_col = m->nnz ? ~h_st.min_col_inv : 0u;
@@ -1380,7 +1336,7 @@ static int add_common(smh_crs *a_mut, const smh_crs *a, const smh_crs *b, bool s
         SMH_HIP(hipStreamSynchronize(nullptr));
         SMH_TRY(assemble_common((smh_dtype)a->dtype, b->nnz, rows, b->d_col, subtract ? (const void *)neg : b->d_val, nullptr, true, true, &fresh));
         if (fresh->n_cols < a->n_cols) fresh->n_cols = a->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
-        copy_knobs(fresh, a);
+        fresh->knobs = a->knobs;
         if (a_mut) replace_state(a_mut, fresh, false);
         else *out = fresh;
         return SMH_OK;
@@ -1538,7 +1494,7 @@ static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32
             SMH_TRY(assemble_common((smh_dtype)m->dtype, n + 1, c_rows, c_cols, c_vals, c_ops, true, true, &fresh));
         }
         if (fresh->n_cols < m->n_cols) fresh->n_cols = m->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
-        copy_knobs(fresh, m);
+        fresh->knobs = m->knobs;
         replace_state(m, fresh, false);
         return SMH_OK;
     }
@@ -1594,10 +1550,7 @@ int smh_crs_is_sorted(const smh_crs *m, int *out) {
 int smh_crs_sort_rows(smh_crs *m) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(sort_rows(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, m->max_col, m->stream));
-    drop_colblock(m);  // the blocked copy keeps storage order inside a (row, block) pair
-    (void)hipFree(m->d_col16);  // the 16-bit column arrays follow the storage order too: rebuilt on next use
-    m->d_col16 = nullptr;
-    drop_stream_codes(m);
+    invalidate(m, Changed::Order);
     return SMH_OK;
 }
 
@@ -1605,17 +1558,6 @@ int smh_crs_destroy(smh_crs *m) {
     if (!m) return SMH_OK;
     if (m->stream) { (void)hipStreamSynchronize(m->stream); (void)hipStreamDestroy(m->stream); }
     if (m->owns) { (void)hipFree(m->d_off); (void)hipFree(m->d_col); (void)hipFree(m->d_val); }
-    (void)hipFree(m->d_tile_row); (void)hipFree(m->d_tile_nz); (void)hipFree(m->d_carry_row); (void)hipFree(m->d_carry_val);
-    (void)hipFree(m->d_phase_ptr); (void)hipFree(m->d_phases); (void)hipFree(m->d_col16); (void)hipFree(m->d_ring_win);
-    (void)hipFree(m->d_stream_cwin); (void)hipFree(m->d_stream_code);
-    (void)hipFree(m->d_stream_len8); (void)hipFree(m->d_stream_tbase); (void)hipFree(m->d_stream_dict);
-    (void)hipFree(m->d_cb_off); (void)hipFree(m->d_cb_col); (void)hipFree(m->d_cb_val);
-    (void)hipFree(m->d_cf_seg); (void)hipFree(m->d_cf_cnt); (void)hipFree(m->d_cf_col); (void)hipFree(m->d_cf_val);
-    (void)hipFree(m->d_cf_tile_row);
-    (void)smh_crs_destroy(m->split_long); (void)smh_crs_destroy(m->split_short);
-    (void)hipFree(m->d_split_rows); (void)hipFree(m->d_split_y);
-    tiled_free(m);
-    (void)hipFree(m->d_x); (void)hipFree(m->d_y);
     (void)hipGetLastError();
     delete m;
     return SMH_OK;
@@ -1624,11 +1566,10 @@ int smh_crs_destroy(smh_crs *m) {
 int smh_crs_update_values(smh_crs *m, const void *values_host) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL argument");
     if (m->nnz && values_host) SMH_HIP(hipMemcpy(m->d_val, values_host, m->nnz * dtype_size(m->dtype), hipMemcpyHostToDevice));
-    drop_colblock(m);
+    invalidate(m, Changed::Values);
     // the value dictionary of K1s XD-V described the OLD values: look again now (one pass over the values: nothing beside the copy above)
     // and take the indices out of the codes, or put the new ones in
-    m->stream_dict_state = -1;
-    if (m->stream_coded && m->stream_direct) {
+    if (m->codes.state != Form::NotTried && m->codes.direct) {
         StreamCfg c;
         SMH_TRY(stream_cfg(m, &c, true));
     }
@@ -1678,13 +1619,13 @@ int smh_crs_scale(smh_crs *m, double a) {
         SMH_HIP(hipStreamSynchronize(m->stream));
     }
     // (K1s XD-V: every entry is its dictionary value times a, rounded as the entry itself is: the indices in the codes stay right)
-    if (m->d_stream_dict && m->stream_dict_state == 1) SMH_TRY(launch_scale_values(m->dtype, m->d_stream_dict, 32, a, m->stream));
-    if (m->cb_built) SMH_TRY(launch_scale_values(m->dtype, m->d_cb_val, m->nnz, a, m->stream));
-    if (m->cf_built && m->cf_ok) SMH_TRY(launch_scale_values(m->dtype, m->d_cf_val, m->nnz, a, m->stream));
-    if (m->t2_built && m->t2_ok) SMH_TRY(launch_scale_values(m->dtype, m->d_t2_val, (size_t)m->t2_tot, a, m->stream));
-    if (m->split_built && m->split_ok) {
-        SMH_TRY(smh_crs_scale(m->split_long, a));
-        SMH_TRY(smh_crs_scale(m->split_short, a));
+    if (m->dict.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->dict.values.get(), 32, a, m->stream));
+    if (m->cb.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->cb.val.get(), m->nnz, a, m->stream));
+    if (m->cf.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->cf.val.get(), m->nnz, a, m->stream));
+    if (m->tiled.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->tiled.val.get(), (size_t)m->tiled.tot, a, m->stream));
+    if (m->split.state == Form::Ready) {
+        SMH_TRY(smh_crs_scale(m->split.long_part, a));
+        SMH_TRY(smh_crs_scale(m->split.short_part, a));
     }
     SMH_HIP(hipStreamSynchronize(m->stream));
     return SMH_OK;
@@ -1694,35 +1635,32 @@ int smh_crs_tiled_layout(smh_crs *m, uint32_t *n_slices_out, uint32_t *slice_col
                          size_t *copy_entries_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(tiled_build(m));
-    if (!m->t2_ok) return fail(SMH_ERR_INVALID, "the tiled copy could not be built for this matrix");
-    if (n_slices_out) *n_slices_out = m->t2_n_cb;
+    if (n_slices_out) *n_slices_out = m->tiled.n_cb;
     if (slice_columns_out) *slice_columns_out = tiled_slice_columns(m->dtype);
-    if (rows_per_block_out) *rows_per_block_out = m->t2_R;
-    if (n_row_blocks_out) *n_row_blocks_out = m->t2_n_rb;
-    if (copy_entries_out) *copy_entries_out = (size_t)m->t2_tot;
+    if (rows_per_block_out) *rows_per_block_out = m->tiled.R;
+    if (n_row_blocks_out) *n_row_blocks_out = m->tiled.n_rb;
+    if (copy_entries_out) *copy_entries_out = (size_t)m->tiled.tot;
     return SMH_OK;
 }
 
 int smh_crs_tiled_products(smh_crs *m, size_t *n_products_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(tiled_build(m));
-    if (!m->t2_ok) return fail(SMH_ERR_INVALID, "the tiled copy could not be built for this matrix");
-    if (n_products_out) *n_products_out = (size_t)m->t3_n_prod;
+    if (n_products_out) *n_products_out = (size_t)m->tiled.n_prod;
     return SMH_OK;
 }
 
 int smh_crs_tiled_array(smh_crs *m, int which, void *out, size_t capacity_bytes, size_t *bytes_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(tiled_build(m));
-    if (!m->t2_ok) return fail(SMH_ERR_INVALID, "the tiled copy could not be built for this matrix");
     return tiled_array(m, which, out, capacity_bytes, bytes_out);
 }
 
 int smh_crs_set_colblock_shift(smh_crs *m, uint32_t shift) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (shift > 31) return fail(SMH_ERR_INVALID, "column block shift must be 0 (automatic) or 1..31");
-    if (shift != m->cb_forced_shift) drop_colblock(m);
-    m->cb_forced_shift = shift;
+    if (shift != m->knobs.cb_forced_shift) invalidate(m, Changed::BlockWidth);
+    m->knobs.cb_forced_shift = shift;
     return SMH_OK;
 }
 
@@ -1731,14 +1669,14 @@ int smh_crs_colblock(smh_crs *m, uint32_t *shift_out, size_t *n_blocks_out, int 
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(ensure_ring_plan(m, false));  // the locality statistic
     SMH_TRY(ensure_colblock(m));
-    if (shift_out) *shift_out = m->cb_shift;
-    if (n_blocks_out) *n_blocks_out = m->cb_blocks;
-    if (rows_per_thread_out) *rows_per_thread_out = m->cb_rpt;
+    if (shift_out) *shift_out = m->cb.shift;
+    if (n_blocks_out) *n_blocks_out = m->cb.blocks;
+    if (rows_per_thread_out) *rows_per_thread_out = m->cb.rpt;
     if (span_fraction_out) *span_fraction_out = m->span_fraction;
     if (offsets_out)
-        SMH_HIP(hipMemcpy(offsets_out, m->d_cb_off, m->cb_blocks * (m->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->d_cb_col, m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->d_cb_val, m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
+        SMH_HIP(hipMemcpy(offsets_out, m->cb.off.get(), m->cb.blocks * (m->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->cb.col.get(), m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->cb.val.get(), m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
@@ -1747,19 +1685,19 @@ int smh_crs_colfused(smh_crs *m, int *fits_out, uint32_t *shift_out, size_t *n_b
                      void *values_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(ensure_colfused(m));
-    const size_t tile_rows = (size_t)64 * m->cf_rt, n_tiles = m->cf_ok ? m->cf_tiles : 0;
-    if (fits_out) *fits_out = m->cf_ok ? 1 : 0;
-    if (shift_out) *shift_out = m->cf_shift;
-    if (n_blocks_out) *n_blocks_out = m->cf_blocks;
-    if (rows_per_lane_out) *rows_per_lane_out = m->cf_rt;
+    const size_t tile_rows = (size_t)64 * m->cf.rt, n_tiles = (m->cf.state == Form::Ready) ? m->cf.tiles : 0;
+    if (fits_out) *fits_out = (m->cf.state == Form::Ready) ? 1 : 0;
+    if (shift_out) *shift_out = m->cf.shift;
+    if (n_blocks_out) *n_blocks_out = m->cf.blocks;
+    if (rows_per_lane_out) *rows_per_lane_out = m->cf.rt;
     if (n_tiles_out) *n_tiles_out = n_tiles;
-    if (!m->cf_ok) return SMH_OK;
+    if (m->cf.state != Form::Ready) return SMH_OK;
     SMH_HIP(hipStreamSynchronize(m->stream));
-    if (tile_rows_out) SMH_HIP(hipMemcpy(tile_rows_out, m->d_cf_tile_row, (n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (segments_out) SMH_HIP(hipMemcpy(segments_out, m->d_cf_seg, (n_tiles * m->cf_blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (counts_out && n_tiles) SMH_HIP(hipMemcpy(counts_out, m->d_cf_cnt, n_tiles * m->cf_blocks * tile_rows, hipMemcpyDeviceToHost));
-    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->d_cf_col, m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->d_cf_val, m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
+    if (tile_rows_out) SMH_HIP(hipMemcpy(tile_rows_out, m->cf.tile_row.get(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (segments_out) SMH_HIP(hipMemcpy(segments_out, m->cf.seg.get(), (n_tiles * m->cf.blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (counts_out && n_tiles) SMH_HIP(hipMemcpy(counts_out, m->cf.cnt.get(), n_tiles * m->cf.blocks * tile_rows, hipMemcpyDeviceToHost));
+    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->cf.col.get(), m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->cf.val.get(), m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
@@ -1767,13 +1705,14 @@ int smh_crs_colsplit(smh_crs *m, int *split_out, uint32_t *min_long_out, size_t 
                      smh_crs **short_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(ensure_split(m));
-    if (split_out) *split_out = m->split_ok ? 1 : 0;
+    const bool split = m->split.state == Form::Ready;
+    if (split_out) *split_out = split ? 1 : 0;
     if (min_long_out) *min_long_out = kSplitMinLong;
-    if (n_long_out) *n_long_out = m->split_ok ? m->split_n_long : 0;
-    if (long_out) *long_out = m->split_ok ? m->split_long : nullptr;
-    if (short_out) *short_out = m->split_ok ? m->split_short : nullptr;
-    if (long_rows_out && m->split_ok && m->split_n_long)
-        SMH_HIP(hipMemcpy(long_rows_out, m->d_split_rows, m->split_n_long * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_long_out) *n_long_out = split ? m->split.n_long : 0;
+    if (long_out) *long_out = split ? m->split.long_part : nullptr;
+    if (short_out) *short_out = split ? m->split.short_part : nullptr;
+    if (long_rows_out && split && m->split.n_long)
+        SMH_HIP(hipMemcpy(long_rows_out, m->split.rows.get(), m->split.n_long * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
@@ -1787,23 +1726,15 @@ int smh_crs_resolved_variant(const smh_crs *m, int *variant_out, int *lanes_out)
 int smh_crs_set_stream_xs(smh_crs *m, int mode) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic), 0 (never) or 1 (whenever the tiles allow)");
-    m->use_stream_xs = mode;
-    if (m->stream_coded) {  // the choice may flip the code array's meaning: now, not inside a later launch
-        StreamCfg c;
-        SMH_TRY(stream_cfg(m, &c, true));
-    }
-    return SMH_OK;
+    m->knobs.use_stream_xs = mode;
+    return recode_stream(m);
 }
 
 int smh_crs_set_stream_direct(smh_crs *m, int mode) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic), 0 (never) or 1 (whenever x is staged)");
-    m->use_stream_direct = mode;
-    if (m->stream_coded) {
-        StreamCfg c;
-        SMH_TRY(stream_cfg(m, &c, true));
-    }
-    return SMH_OK;
+    m->knobs.use_stream_direct = mode;
+    return recode_stream(m);
 }
 
 int smh_crs_stream_direct(smh_crs *m, int *direct_out) {
@@ -1818,9 +1749,9 @@ int smh_crs_stream_value_dict(smh_crs *m, int *n_values_out, void *values_out) {
     if (!m || !n_values_out) return fail(SMH_ERR_INVALID, "NULL argument");
     StreamCfg c;
     SMH_TRY(stream_cfg(m, &c));
-    *n_values_out = c.dict ? (int)m->stream_dict_n : 0;
+    *n_values_out = c.dict ? (int)m->dict.n : 0;
     if (c.dict && values_out) {
-        SMH_HIP(hipMemcpyAsync(values_out, m->d_stream_dict, (size_t)m->stream_dict_n * dtype_size(m->dtype), hipMemcpyDeviceToHost, m->stream));
+        SMH_HIP(hipMemcpyAsync(values_out, m->dict.values.get(), (size_t)m->dict.n * dtype_size(m->dtype), hipMemcpyDeviceToHost, m->stream));
         SMH_HIP(hipStreamSynchronize(m->stream));
     }
     return SMH_OK;
@@ -1829,12 +1760,8 @@ int smh_crs_stream_value_dict(smh_crs *m, int *n_values_out, void *values_out) {
 int smh_crs_set_stream_value_dict(smh_crs *m, int mode) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (mode < -1 || mode > 0) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic: whenever the values allow) or 0 (never)");
-    m->use_stream_vdict = mode;
-    if (m->stream_coded) {
-        StreamCfg c;
-        SMH_TRY(stream_cfg(m, &c, true));
-    }
-    return SMH_OK;
+    m->knobs.use_stream_vdict = mode;
+    return recode_stream(m);
 }
 
 int smh_crs_stream_layout(smh_crs *m, int *coded_out, int *byte_lengths_out, int *small_tiles_out, int *xs_chunks_out) {
@@ -1851,14 +1778,14 @@ int smh_crs_stream_layout(smh_crs *m, int *coded_out, int *byte_lengths_out, int
 int smh_crs_set_vector_chunks(smh_crs *m, int chunks) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (chunks < 0 || chunks > 3) return fail(SMH_ERR_INVALID, "chunks per lane must be 0 (automatic), 1, 2 or 3");
-    m->forced_chunks = chunks;
+    m->knobs.forced_chunks = chunks;
     return SMH_OK;
 }
 
 int smh_crs_set_ring(smh_crs *m, int mode) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "ring mode must be -1 (auto), 0 (plain K1) or 1 (K1r)");
-    m->use_ring = mode;
+    m->knobs.use_ring = mode;
     return SMH_OK;
 }
 
@@ -1868,30 +1795,30 @@ int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out, 
     SMH_TRY(ensure_ring_plan(m));
     bool ring = false;
     SMH_TRY(vector_uses_ring(m, &ring));
-    if (n_blocks_out) *n_blocks_out = m->ring_blocks;
-    if (n_phases_out) *n_phases_out = m->ring_n_phases;
-    if (ring_fraction_out) *ring_fraction_out = m->ring_fraction;
+    if (n_blocks_out) *n_blocks_out = m->ring.blocks;
+    if (n_phases_out) *n_phases_out = m->ring.n_phases;
+    if (ring_fraction_out) *ring_fraction_out = m->ring.fraction;
     if (active_out) *active_out = ring ? 1 : 0;
     if (phase_ptr_out)
-        SMH_HIP(hipMemcpy(phase_ptr_out, m->d_phase_ptr, (m->ring_blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (phases_out && m->ring_n_phases)
-        SMH_HIP(hipMemcpy(phases_out, m->d_phases, m->ring_n_phases * sizeof(RingPhase), hipMemcpyDeviceToHost));
+        SMH_HIP(hipMemcpy(phase_ptr_out, m->ring.phase_ptr.get(), (m->ring.blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (phases_out && m->ring.n_phases)
+        SMH_HIP(hipMemcpy(phases_out, m->ring.phases.get(), m->ring.n_phases * sizeof(RingPhase), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
 int smh_crs_ring_entries(smh_crs *m, uint32_t *out) {
     if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
     SMH_TRY(ensure_ring_plan(m));
-    *out = m->ring_entries;
+    *out = m->ring.entries;
     return SMH_OK;
 }
 
 int smh_crs_ring_bands(smh_crs *m, uint32_t *bands_out, uint32_t *intervals_out) {
     if (!m || !bands_out) return fail(SMH_ERR_INVALID, "NULL argument");
     SMH_TRY(ensure_ring_plan(m));
-    *bands_out = m->ring_bands;
-    if (intervals_out && m->ring_bands == 4 && m->d_ring_win)
-        SMH_HIP(hipMemcpy(intervals_out, m->d_ring_win, ((m->n_rows + 63) / 64) * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *bands_out = m->ring.bands;
+    if (intervals_out && m->ring.bands == 4 && m->ring.win.get())
+        SMH_HIP(hipMemcpy(intervals_out, m->ring.win.get(), ((m->n_rows + 63) / 64) * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
@@ -1899,7 +1826,7 @@ int smh_crs_set_vector_lanes(smh_crs *m, int lanes) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (lanes != 0 && (lanes < 1 || lanes > 64 || (lanes & (lanes - 1))))
         return fail(SMH_ERR_INVALID, "lanes per row must be 0 or a power of two in 1..64");
-    m->forced_lanes = lanes;
+    m->knobs.forced_lanes = lanes;
     return SMH_OK;
 }
 
@@ -1913,12 +1840,12 @@ static int prepare_inner(smh_crs *m, int variant) {
         case SMH_SPMV_COLBLOCK: return ensure_colblock(m);
         case SMH_SPMV_COLFUSED:
             SMH_TRY(ensure_colfused(m));
-            return m->cf_ok ? SMH_OK : ensure_colblock(m);
+            return (m->cf.state == Form::Ready) ? SMH_OK : ensure_colblock(m);
         case SMH_SPMV_COLSPLIT:
             SMH_TRY(ensure_split(m));
-            if (!m->split_ok) return ensure_colblock(m);
-            SMH_TRY(smh_crs_prepare(m->split_short, SMH_SPMV_AUTO));
-            return smh_crs_prepare(m->split_long, SMH_SPMV_AUTO);
+            if (m->split.state != Form::Ready) return ensure_colblock(m);
+            SMH_TRY(smh_crs_prepare(m->split.short_part, SMH_SPMV_AUTO));
+            return smh_crs_prepare(m->split.long_part, SMH_SPMV_AUTO);
         case SMH_SPMV_STREAM: {
             StreamCfg c;
             return stream_cfg(m, &c, true);  // code tables; the code array in the form the current settings ask for
@@ -1970,11 +1897,11 @@ int smh_crs_spmv(smh_crs *m, const void *x_host, size_t x_len, void *y_host, int
     if (m->n_rows == 0) return SMH_OK;
     if (!y_host || (x_len && !x_host)) return fail(SMH_ERR_INVALID, "NULL host vector");
     const size_t vs = dtype_size(m->dtype);
-    SMH_TRY(ensure_cap(&m->d_x, &m->d_x_cap, x_len * vs));
-    SMH_TRY(ensure_cap(&m->d_y, &m->d_y_cap, m->n_rows * vs));
-    if (x_len) SMH_HIP(hipMemcpyAsync(m->d_x, x_host, x_len * vs, hipMemcpyHostToDevice, m->stream));
-    SMH_TRY(spmv_enqueue(m, m->d_x, x_len, m->d_y, variant, m->stream));
-    SMH_HIP(hipMemcpyAsync(y_host, m->d_y, m->n_rows * vs, hipMemcpyDeviceToHost, m->stream));
+    SMH_TRY(m->stage_x.ensure_cap(x_len * vs));
+    SMH_TRY(m->stage_y.ensure_cap(m->n_rows * vs));
+    if (x_len) SMH_HIP(hipMemcpyAsync(m->stage_x.d.get(), x_host, x_len * vs, hipMemcpyHostToDevice, m->stream));
+    SMH_TRY(spmv_enqueue(m, m->stage_x.d.get(), x_len, m->stage_y.d.get(), variant, m->stream));
+    SMH_HIP(hipMemcpyAsync(y_host, m->stage_y.d.get(), m->n_rows * vs, hipMemcpyDeviceToHost, m->stream));
     SMH_HIP(hipStreamSynchronize(m->stream));
     return SMH_OK;
 }
@@ -1989,9 +1916,9 @@ size_t smh_crs_merge_tile_items(const smh_crs *) { return kMergeTile; }
 int smh_crs_merge_table(smh_crs *m, uint32_t *row_out, uint32_t *nnz_out) {
     if (!m || !row_out || !nnz_out) return fail(SMH_ERR_INVALID, "NULL argument");
     SMH_TRY(ensure_merge_ws(m));
-    if (m->n_tiles == 0) { row_out[0] = 0; nnz_out[0] = 0; return SMH_OK; }
-    SMH_HIP(hipMemcpy(row_out, m->d_tile_row, (m->n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SMH_HIP(hipMemcpy(nnz_out, m->d_tile_nz, (m->n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (m->merge.n_tiles == 0) { row_out[0] = 0; nnz_out[0] = 0; return SMH_OK; }
+    SMH_HIP(hipMemcpy(row_out, m->merge.tile_row.get(), (m->merge.n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SMH_HIP(hipMemcpy(nnz_out, m->merge.tile_nz.get(), (m->merge.n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SMH_OK;
 }
 
@@ -2145,21 +2072,19 @@ static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const v
         // K1r: the lanes that would store a row's sum multiply it by lhs[row] instead and the blocks leave partial sums
         if (m->nnz > 0 && (size_t)m->max_col >= rhs_len)
             return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", rhs_len, m->max_col);
-        SMH_TRY(ensure_cap(&m->d_y, &m->d_y_cap, ((size_t)m->ring_blocks + 1) * vs));
-        SMH_TRY(launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->d_col16, m->d_val, d_rhs, const_cast<void *>(d_lhs),
-                                  m->n_rows, m->nnz, m->owns || m->nnz % 4 == 0, m->ring_blocks, m->d_phase_ptr, m->d_phases, m->ring_entries,
-                                  m->ring_bands, m->stream, m->d_y));
-        SMH_TRY(launch_fold2(m->dtype, m->d_y, (size_t)m->ring_blocks + 1, scratch, res, m->stream));
+        SMH_TRY(m->stage_y.ensure_cap(((size_t)m->ring.blocks + 1) * vs));
+        SMH_TRY(launch_ring(m, d_rhs, const_cast<void *>(d_lhs), m->stream, m->stage_y.d.get()));
+        SMH_TRY(launch_fold2(m->dtype, m->stage_y.d.get(), (size_t)m->ring.blocks + 1, scratch, res, m->stream));
     } else if (n_dot) {
         // K1s: lhs_i * (A rhs)_i summed per tile in the SpMV's epilogue -- no y vector, no second pass; the tile partials
         // are folded by the two small reduction kernels
-        SMH_TRY(ensure_cap(&m->d_y, &m->d_y_cap, n_dot * vs));  // (the staging buffer holds the partials here)
-        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, nullptr, variant, m->stream, m->d_y, d_lhs));
-        SMH_TRY(launch_fold2(m->dtype, m->d_y, n_dot, scratch, res, m->stream));
+        SMH_TRY(m->stage_y.ensure_cap(n_dot * vs));  // (the staging buffer holds the partials here)
+        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, nullptr, variant, m->stream, m->stage_y.d.get(), d_lhs));
+        SMH_TRY(launch_fold2(m->dtype, m->stage_y.d.get(), n_dot, scratch, res, m->stream));
     } else {
-        SMH_TRY(ensure_cap(&m->d_y, &m->d_y_cap, m->n_rows * vs));
-        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, m->d_y, variant, m->stream));
-        SMH_TRY(launch_dot(m->dtype, d_lhs, m->d_y, m->n_rows, scratch, res, m->stream));
+        SMH_TRY(m->stage_y.ensure_cap(m->n_rows * vs));
+        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, m->stage_y.d.get(), variant, m->stream));
+        SMH_TRY(launch_dot(m->dtype, d_lhs, m->stage_y.d.get(), m->n_rows, scratch, res, m->stream));
     }
     double h64 = 0;
     float h32 = 0;
@@ -2183,13 +2108,13 @@ int smh_crs_inner_prod(smh_crs *m, const void *lhs_host, size_t lhs_len, const v
     if ((lhs_len && !lhs_host) || (rhs_len && !rhs_host)) return fail(SMH_ERR_INVALID, "NULL host vector");
     const size_t vs = dtype_size(m->dtype);
     // rhs goes to the x staging; lhs to a scratch allocation of its own
-    SMH_TRY(ensure_cap(&m->d_x, &m->d_x_cap, rhs_len * vs));
+    SMH_TRY(m->stage_x.ensure_cap(rhs_len * vs));
     Scratch scr;
     char *d_lhs = nullptr;
     SMH_TRY(scr.alloc(&d_lhs, (lhs_len ? lhs_len : 1) * vs));
-    if (rhs_len) SMH_HIP(hipMemcpyAsync(m->d_x, rhs_host, rhs_len * vs, hipMemcpyHostToDevice, m->stream));
+    if (rhs_len) SMH_HIP(hipMemcpyAsync(m->stage_x.d.get(), rhs_host, rhs_len * vs, hipMemcpyHostToDevice, m->stream));
     if (lhs_len) SMH_HIP(hipMemcpyAsync(d_lhs, lhs_host, lhs_len * vs, hipMemcpyHostToDevice, m->stream));
-    return inner_prod_dev(m, d_lhs, lhs_len, m->d_x, rhs_len, variant, out);
+    return inner_prod_dev(m, d_lhs, lhs_len, m->stage_x.d.get(), rhs_len, variant, out);
 }
 
 int smh_vec_norm_squared(const smh_vec *x, double *out) { return smh_vec_dot(x, x, out); }

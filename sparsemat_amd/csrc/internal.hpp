@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/sparsemat_hip.h"
@@ -134,6 +135,36 @@ struct CrsArrays {
         off = col = nullptr;
         val = nullptr;
     }
+};
+
+// One device array of T (char: sized in bytes), freed when the owner goes out of scope or takes another; null after a move.
+template <typename T> class DevArray {
+  public:
+    DevArray() = default;
+    DevArray(const DevArray &) = delete;
+    DevArray &operator=(const DevArray &) = delete;
+    DevArray(DevArray &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevArray &operator=(DevArray &&o) noexcept {
+        if (this != &o) {
+            reset(o.p_);
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevArray() { reset(); }
+    int alloc(size_t count) {  // exactly count elements
+        reset();
+        SMH_HIP(pool_malloc((void **)&p_, count * sizeof(T)));
+        return SMH_OK;
+    }
+    T *get() const { return p_; }
+    void reset(T *q = nullptr) {  // frees the array; q (optional, a pool allocation) is owned from here on
+        (void)pool_free(p_);
+        p_ = q;
+    }
+
+  private:
+    T *p_ = nullptr;
 };
 
 // rocPRIM's two-phase calls: `call` names `tmp` and `bytes`; it is run once to size the temporary storage (bytes ? bytes : 16),
@@ -361,10 +392,9 @@ int launch_crs_stats(const uint32_t *off, const uint32_t *col, size_t n_rows, si
 // kernel also leaves that many partial sums of x.y there (K1s epilogue; square matrices) -- CG's / PCG's p.Ap for free
 // K2t (spmv_tiled.hip)
 void tiled_geometry(size_t n_rows, size_t n_cols, size_t nnz, int dtype, uint32_t *n_cb, uint32_t *rows_per_block, uint32_t *n_rb);
-int tiled_build(::smh_crs *m);   // lazy; sets t2_ok
+int tiled_build(::smh_crs *m);   // lazy; leaves m->tiled Ready or Refused
 uint32_t tiled_slice_columns(int dtype);
 int columns_within_n_cols(const ::smh_crs *m, const char *what);  // capi.hip: SMH_ERR_INDEX_RANGE when max_col >= n_cols
-void tiled_free(::smh_crs *m);
 int tiled_array(::smh_crs *m, int which, void *out, size_t capacity_bytes, size_t *bytes_out);
 int launch_spmv_tiled(::smh_crs *m, const void *x, size_t x_len, void *y, hipStream_t s);
 size_t spmv_fused_dot_partials(::smh_crs *m, size_t x_len, int variant, bool any_lhs = false);
@@ -384,6 +414,129 @@ int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials
 int launch_fold2(int dtype, const void *in, size_t count, void *partials, void *result_dev, hipStream_t s);  // *result = sum(in)
 int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
 
+// ---- what a CRS handle derives lazily from its own arrays (built by capi.hip's ensure_* and spmv_tiled.hip's tiled_build) ----
+// Each form is filled in a local instance and move-assigned into the handle when it is complete; a default-constructed one is
+// "not built", and assigning that drops the form (the members free themselves).
+enum class Form {
+    NotTried,
+    Ready,
+    Refused,  // the build was attempted and the form does not apply to this matrix: AUTO takes its next choice, nothing is tried again
+};
+struct MergeTable {  // K2
+    Form state = Form::NotTried;
+    size_t n_tiles = 0;
+    DevArray<uint32_t> tile_row, tile_nz, carry_row;
+    DevArray<char> carry_val;
+};
+struct RingPlan {  // K1r
+    Form state = Form::NotTried;
+    bool bands_tried = false;             // the plan was built with the banded attempt allowed
+    unsigned blocks = 0;
+    double fraction = 0.0;                // share of rows whose gathers are served from the LDS ring
+    unsigned entries = kRingEntries;      // ring size the plan was built for
+    unsigned bands = 1;                   // 1: one sliding window; 4: banded ring (needs col16 = ring slots)
+    size_t n_phases = 0;
+    DevArray<uint32_t> phase_ptr;
+    DevArray<RingPhase> phases;
+    DevArray<uint32_t> win;               // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
+    DevArray<uint16_t> col16;             // 16-bit column array for the ring phases (built from the plan on first use; null: not used)
+};
+struct StreamCodes {  // K1s 16-bit column codes (Ready only when every tile has a description; Refused holds nothing)
+    Form state = Form::NotTried;
+    DevArray<uint32_t> cwin;              // 8 u32 per 256-row tile
+    DevArray<uint16_t> code;              // one u16 per entry
+    DevArray<uint8_t> len8;               // with max_row_len <= 255: one byte per row (its length) ...
+    DevArray<uint32_t> tbase;             // ... and one u32 per 256-row tile (its first entry)
+    uint32_t xs_chunks = 0xFFFFFFFFu, xs_end = 0;  // K1s XS: most x chunks a tile needs; largest x index + 1 they touch
+    uint64_t odd_rows = 0;                // rows of odd length (taken with the byte lengths)
+    bool direct = false;                  // code holds stage byte offsets (K1s XD) instead of column codes
+    // K1s XD-V: ... and, in their spare bits, indices into a dictionary of the matrix's distinct values (the value array is then not read)
+    bool vdict = false;                   // the codes carry the indices now (built for a stage of vdict_xs * 1024 entries)
+    int vdict_xs = 0;
+};
+struct StreamDict {  // K1s XD-V value dictionary: follows the values, where the codes follow the structure
+    Form state = Form::NotTried;          // NotTried: not looked at (or the values changed); Refused: too many distinct values
+    uint32_t n = 0;
+    DevArray<char> values;                // 32 values (kept across a look: a product in flight may still read it)
+};
+struct ColBlock {  // K2c column-blocked copy
+    Form state = Form::NotTried;
+    uint32_t shift = 0;                   // block width = 2^shift columns
+    size_t blocks = 0;
+    int rpt = 1;                          // rows per thread of the K1s launches (tile = 256*rpt rows)
+    bool single_pass = false;             // no tile of any block exceeds the LDS stage
+    DevArray<uint32_t> off, col;
+    DevArray<char> val;
+};
+struct ColFused {  // K2f fused column-blocked copy (Refused: the byte table cannot describe the matrix; the geometry stays readable)
+    Form state = Form::NotTried;
+    uint32_t shift = 0, rt = 0;
+    size_t blocks = 0, tiles = 0;
+    DevArray<uint32_t> seg, col, tile_row;
+    DevArray<uint8_t> cnt;
+    DevArray<char> val;
+};
+struct RowSplit {  // K2s row-length split: two sub-handles (owned) + the rows of the long one (Refused: not worth building)
+    Form state = Form::NotTried;
+    ::smh_crs *long_part = nullptr, *short_part = nullptr;
+    DevArray<uint32_t> rows;
+    DevArray<char> y;
+    size_t n_long = 0;
+    hipStream_t side = nullptr;           // the LONG part runs beside the SHORT one (fork / join by events)
+    hipEvent_t fork = nullptr, join = nullptr;
+    RowSplit() = default;
+    RowSplit(RowSplit &&o) noexcept { swap(o); }
+    RowSplit &operator=(RowSplit &&o) noexcept {
+        RowSplit old(std::move(*this));  // (dropped at the end of this scope)
+        swap(o);
+        return *this;
+    }
+    ~RowSplit();  // capi.hip: the only file that deletes handles
+    void swap(RowSplit &o) noexcept {
+        std::swap(state, o.state); std::swap(long_part, o.long_part); std::swap(short_part, o.short_part);
+        std::swap(rows, o.rows); std::swap(y, o.y); std::swap(n_long, o.n_long);
+        std::swap(side, o.side); std::swap(fork, o.fork); std::swap(join, o.join);
+    }
+};
+struct Tiled {  // K2t 2-D tiled copy (spmv_tiled.hip): entries by column slice, within a slice by row (Refused: its build failed)
+    Form state = Form::NotTried;
+    uint32_t n_cb = 0, n_rb = 0, R = 0;   // column slices, row blocks, rows of the largest block
+    uint64_t tot = 0;                     // entries of the copy (slices padded to 8)
+    DevArray<char> val, prod;             // values in copy order; the products of the last launch
+    DevArray<uint16_t> code, row;         // column within the slice; row within the row block
+    DevArray<uint32_t> tstart;            // (n_rb + 1) x n_cb tile starts, relative to the slice
+    DevArray<uint32_t> rbstart;           // first row of each row block (n_rb + 1); blocks hold equal entry counts
+    DevArray<uint32_t> cptr;              // (round 3's form) first chunk of each slice (n_cb + 1)
+    DevArray<char> chunk;                 // per chunk {where its product sums go, entries}
+    uint32_t n_chunks = 0, max_slice_chunks = 0;
+    bool dups = false;                    // a chunk boundary cuts a (row, slice) pair somewhere: pass 2 checks for equal neighbours
+    uint64_t n_prod = 0;                  // product slots (one per (row, slice, chunk), chunk shares padded to 16 bytes)
+};
+struct StageBuf {  // a staging vector of the host-pointer API (lazy, reused)
+    DevArray<char> d;
+    size_t cap = 0;
+    int ensure_cap(size_t bytes) {
+        if (cap >= bytes && d.get()) return SMH_OK;
+        cap = 0;
+        const size_t want = bytes < 256 ? 256 : bytes;
+        SMH_TRY(d.alloc(want));
+        cap = want;
+        return SMH_OK;
+    }
+};
+// the smh_crs_set_* settings a clone (and a handle updated in place) carries
+struct Knobs {
+    int forced_lanes = 0;
+    int forced_chunks = 0;
+    int stream_rows_per_thread = 0;       // 0 automatic (2 when every 512-row tile fits), 1 force one
+    uint32_t cb_forced_shift = 0;         // 0 automatic (2 MiB of x per block)
+    int use_ring = -1;                    // -1 automatic, 0 never, 1 always (when lanes <= 8), 2 always with the first K1r body
+    int use_stream_xs = -1;               // K1s XS: -1 automatic (x beyond the L2s; the 4096-entry stage on f32 only), 0 never, 1 whenever the tiles allow
+    int use_stream_direct = -1;           // K1s XD: -1 automatic (most rows of odd length), 0 never, 1 whenever x is staged
+    int use_stream_vdict = -1;            // -1 automatic (whenever the values allow), 0 never
+    int use_col16 = -1;                   // -1 automatic (when at least a quarter of the rows are ring rows), 0 never, 1 always
+};
+
 }  // namespace smh
 
 // ---- handles ------------------------------------------------------------------------------
@@ -401,6 +554,7 @@ struct smh_crs {
     uint32_t *d_col = nullptr;
     void *d_val = nullptr;
     bool owns = true;
+    bool no_split = false;  // this handle IS a part of a K2s split: never split again (not a setting: a clone does not take it)
     hipStream_t stream = nullptr;
     // statistics
     uint32_t max_row_len = 0;
@@ -409,91 +563,21 @@ struct smh_crs {
     uint32_t max_tile_entries = 0;  // most entries in any 256-row tile (K1s eligibility)
     uint32_t max_tile512_entries = 0;  // ... in any 512-row tile (K1s with two rows per thread)
     bool have_stats = false;
-    int forced_lanes = 0;
-    int forced_chunks = 0;
-    // merge-path workspace (lazy)
-    size_t n_tiles = 0;
-    uint32_t *d_tile_row = nullptr, *d_tile_nz = nullptr, *d_carry_row = nullptr;
-    void *d_carry_val = nullptr;
-    int stream_rows_per_thread = 0;    // 0 automatic (2 when every 512-row tile fits), 1 force one
-    // K1s 16-bit column codes (lazy; kept only when every tile has a description)
-    bool stream_coded = false;         // inspected
-    uint32_t *d_stream_cwin = nullptr; // 8 u32 per 256-row tile
-    uint16_t *d_stream_code = nullptr; // one u16 per entry
-    uint8_t *d_stream_len8 = nullptr;  // with codes and max_row_len <= 255: one byte per row (its length) ...
-    uint32_t *d_stream_tbase = nullptr; // ... and one u32 per 256-row tile (its first entry)
-    // K2c column-blocked copy (lazy)
-    bool cb_built = false;
-    uint32_t cb_forced_shift = 0;  // 0 automatic (2 MiB of x per block)
-    uint32_t cb_shift = 0;       // block width = 2^cb_shift columns
-    size_t cb_blocks = 0;
-    int cb_rpt = 1;              // rows per thread of the K1s launches (tile = 256*cb_rpt rows)
-    bool cb_single_pass = false; // no tile of any block exceeds the LDS stage
-    uint32_t *d_cb_off = nullptr, *d_cb_col = nullptr;
-    void *d_cb_val = nullptr;
-    double span_fraction = 0.0;  // mean column span of a 64-row tile / n_cols (1: no locality at all)
-    // K2s row-length split (lazy): two sub-handles (owned) + the rows of the long one
-    bool split_built = false, split_ok = false;  // ok: the split was worth building (few long rows holding many entries)
-    bool no_split = false;                       // this handle IS a part of a split: never split again
-    smh_crs *split_long = nullptr, *split_short = nullptr;
-    uint32_t *d_split_rows = nullptr;
-    void *d_split_y = nullptr;
-    size_t split_n_long = 0;
-    hipStream_t split_stream = nullptr;  // the LONG part runs beside the SHORT one (fork / join by events)
-    hipEvent_t split_fork = nullptr, split_join = nullptr;
-    // K2f fused column-blocked copy (lazy)
-    bool cf_built = false;       // the build was attempted (cf_ok: and the byte table could describe the matrix)
-    bool cf_ok = false;
-    uint32_t cf_shift = 0, cf_rt = 0;
-    size_t cf_blocks = 0, cf_tiles = 0;
-    uint32_t *d_cf_seg = nullptr, *d_cf_col = nullptr, *d_cf_tile_row = nullptr;
-    uint8_t *d_cf_cnt = nullptr;
-    void *d_cf_val = nullptr;
-    // K2t 2-D tiled copy (lazy; spmv_tiled.hip): entries by column slice, within a slice by row
-    bool t2_built = false, t2_ok = false;  // built: the build was attempted
-    uint32_t t2_n_cb = 0, t2_n_rb = 0, t2_R = 0;  // column slices, row blocks, rows of the largest block
-    uint64_t t2_tot = 0;                   // entries of the copy (slices padded to 8)
-    void *d_t2_val = nullptr, *d_t2_prod = nullptr;  // values in copy order; the products of the last launch
-    uint16_t *d_t2_code = nullptr, *d_t2_row = nullptr;  // column within the slice; row within the row block
-    uint32_t *d_t2_tstart = nullptr;       // (n_rb + 1) x n_cb tile starts, relative to the slice
-    uint32_t *d_t2_rbstart = nullptr;      // first row of each row block (n_rb + 1); blocks hold equal entry counts
-    uint32_t *d_t3_cptr = nullptr;         // (round 3's form) first chunk of each slice (n_cb + 1)
-    void *d_t3_chunk = nullptr;            // per chunk {where its product sums go, entries}
-    uint32_t t3_n_chunks = 0, t3_max_slice_chunks = 0;
-    bool t3_dups = false;                  // a chunk boundary cuts a (row, slice) pair somewhere: pass 2 checks for equal neighbours
-    uint64_t t3_n_prod = 0;                // product slots (one per (row, slice, chunk), chunk shares padded to 16 bytes)
-    // K1r plan (lazy)
-    bool ring_planned = false;
-    unsigned ring_blocks = 0;
-    double ring_fraction = 0.0;  // share of rows whose gathers are served from the LDS ring
-    unsigned ring_entries = smh::kRingEntries;  // ring size the plan was built for
-    unsigned ring_bands = 1;                    // 1: one sliding window; 4: banded ring (needs d_col16 = ring slots)
-    bool ring_bands_tried = false;              // the plan in place was built with the banded attempt allowed
-    uint32_t *d_ring_win = nullptr;             // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
-    size_t ring_n_phases = 0;
-    uint32_t *d_phase_ptr = nullptr;
-    smh::RingPhase *d_phases = nullptr;
-    int use_ring = -1;  // -1 automatic, 0 never, 1 always (when lanes <= 8), 2 always with the first K1r body
-    int use_stream_xs = -1;  // K1s XS: -1 automatic (x beyond the L2s; the 4096-entry stage on f32 only), 0 never, 1 whenever the tiles allow
-    uint32_t stream_xs_chunks = 0xFFFFFFFFu, stream_xs_end = 0;  // K1s XS: most x chunks a tile needs; largest x index + 1 they touch
-    bool stream_direct = false;   // d_stream_code holds stage byte offsets (K1s XD) instead of column codes
-    // K1s XD-V: ... and, in their spare bits, indices into a dictionary of the matrix's distinct values (the value array is then not read)
-    bool stream_vdict = false;    // the codes carry the indices now (built for a stage of stream_vdict_xs * 1024 entries)
-    int stream_vdict_xs = 0;
-    int stream_dict_state = -1;   // -1 not looked at (or the values changed), 0 too many distinct values, 1 d_stream_dict / stream_dict_n are valid
-    uint32_t stream_dict_n = 0;
-    void *d_stream_dict = nullptr;  // 32 values
-    int use_stream_vdict = -1;    // -1 automatic (whenever the values allow), 0 never
-    int use_stream_direct = -1;   // K1s XD: -1 automatic (most rows of odd length), 0 never, 1 whenever x is staged
-    uint64_t stream_odd_rows = 0; // rows of odd length (taken with the byte lengths)
-    uint16_t *d_col16 = nullptr;  // K1r: 16-bit column array for the ring phases (lazy; null: not used)
-    int use_col16 = -1;           // -1 automatic (when at least a quarter of the rows are ring rows), 0 never, 1 always
+    double span_fraction = 0.0;  // mean column span of a 64-row tile / n_cols (1: no locality at all); taken with the first K1r plan
+    smh::Knobs knobs;
+    // the derived forms (all lazy)
+    smh::MergeTable merge;
+    smh::RingPlan ring;
+    smh::StreamCodes codes;
+    smh::StreamDict dict;
+    smh::ColBlock cb;
+    smh::ColFused cf;
+    smh::RowSplit split;
+    smh::Tiled tiled;
+    smh::StageBuf stage_x, stage_y;
     // what the inspectors cost (smh_crs_prepare_stats): wall ms / pooled device bytes left allocated, create-time and prepare-time
     double create_ms = 0.0, prepare_ms = 0.0;
     long long create_bytes = 0, prepare_bytes = 0;
-    // staging for the host-pointer API (lazy, reused)
-    void *d_x = nullptr, *d_y = nullptr;
-    size_t d_x_cap = 0, d_y_cap = 0;
 };
 
 struct smh_vec {

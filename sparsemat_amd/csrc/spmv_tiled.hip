@@ -682,7 +682,7 @@ void tiled_geometry(size_t n_rows, size_t n_cols, size_t nnz, int dtype, uint32_
 }
 
 template <typename T>
-static int build_t(::smh_crs *m) {
+static int build_t(const ::smh_crs *m, Tiled &t) {  // fills t; the caller commits it
     hipStream_t s = m->stream;
     const uint64_t nnz = m->nnz;
     constexpr uint32_t CH = t3_chunk<T>(), STRIDE = t3_stride<T>(), kT3Slice = T3<T>::kSlice;
@@ -748,20 +748,20 @@ static int build_t(::smh_crs *m) {
     uint32_t *any_cut = nullptr;  // does any chunk boundary cut a (row, slice) pair?
     SMH_TRY(scr.alloc(&any_cut, 1));
     SMH_HIP(hipMemsetAsync(any_cut, 0, sizeof(uint32_t), s));
-    SMH_HIP(hipMalloc(&m->d_t2_val, (slots + CH) * sizeof(T)));
-    SMH_HIP(hipMalloc((void **)&m->d_t2_code, (slots + CH) * sizeof(uint16_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_t3_cptr, ((size_t)n_cb + 1) * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_t3_chunk, ((size_t)n_chunks + 1) * sizeof(T3Chunk)));
-    SMH_HIP(hipMemcpyAsync(m->d_t3_cptr, cptr.data(), cptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    SMH_TRY(t.val.alloc((slots + CH) * sizeof(T)));
+    SMH_TRY(t.code.alloc(slots + CH));
+    SMH_TRY(t.cptr.alloc((size_t)n_cb + 1));
+    SMH_TRY(t.chunk.alloc(((size_t)n_chunks + 1) * sizeof(T3Chunk)));
+    SMH_HIP(hipMemcpyAsync(t.cptr.get(), cptr.data(), cptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     SMH_HIP(hipMemsetAsync(gcount, 0, (n_groups ? n_groups : 1) * sizeof(uint32_t), s));
     SMH_HIP(hipMemsetAsync(obase, 0, ((size_t)n_chunks + 1) * sizeof(uint32_t), s));
     const unsigned wgrid = (n_chunks + kBlock / 64 - 1) / (kBlock / 64);
     if (n_chunks) {
-        hipLaunchKernelGGL(k_t3_chunk_starts<T>, dim3((n_chunks + kBlock - 1) / kBlock), dim3(kBlock), 0, s, m->d_t3_cptr, n_cb, n_chunks, d_start, ps, STRIDE, cstart);
+        hipLaunchKernelGGL(k_t3_chunk_starts<T>, dim3((n_chunks + kBlock - 1) / kBlock), dim3(kBlock), 0, s, t.cptr.get(), n_cb, n_chunks, d_start, ps, STRIDE, cstart);
         SMH_HIP(hipGetLastError());
     stage("allocs + chunk starts");
-        hipLaunchKernelGGL(k_t3_fill<T>, dim3(wgrid), dim3(kBlock), 0, s, m->d_t3_cptr, n_cb, n_chunks, d_start, cstart, ps,
-                           (T *)m->d_t2_val, m->d_t2_code, clen, obase);
+        hipLaunchKernelGGL(k_t3_fill<T>, dim3(wgrid), dim3(kBlock), 0, s, t.cptr.get(), n_cb, n_chunks, d_start, cstart, ps,
+                           (T *)t.val.get(), t.code.get(), clen, obase);
         SMH_HIP(hipGetLastError());
     stage("fill");
     }
@@ -771,8 +771,8 @@ static int build_t(::smh_crs *m) {
     if (n_prod >= (1ull << 32) - 4 * CH) return fail(SMH_ERR_INVALID, "tiled variant: %llu products are too many for its 32-bit index", (unsigned long long)n_prod);
     SMH_TRY(scr.alloc(&prow, (size_t)n_prod));
     if (n_chunks) {
-        hipLaunchKernelGGL(k_t3_prow<T>, dim3(wgrid), dim3(kBlock), 0, s, m->d_t3_cptr, n_cb, n_chunks, d_start, cstart, clen, obase, ps, m->d_t2_code, prow, preal,
-                           gcount, group, (T3Chunk *)m->d_t3_chunk, any_cut);
+        hipLaunchKernelGGL(k_t3_prow<T>, dim3(wgrid), dim3(kBlock), 0, s, t.cptr.get(), n_cb, n_chunks, d_start, cstart, clen, obase, ps, t.code.get(), prow, preal,
+                           gcount, group, (T3Chunk *)t.chunk.get(), any_cut);
         SMH_HIP(hipGetLastError());
     stage("prow");
     }
@@ -840,20 +840,20 @@ static int build_t(::smh_crs *m) {
     if (table_entries * 4 > (4ull << 30))
         return fail(SMH_ERR_INVALID, "tiled variant: %u column slices x %u row blocks need a tile table beyond 4 GiB", n_cb, n_rb);
     // (+ a round of slack: a tile's loads cover whole rounds whatever its length)
-    SMH_HIP(hipMalloc(&m->d_t2_prod, (n_prod + 2 * CH) * sizeof(T)));
-    SMH_HIP(hipMalloc((void **)&m->d_t2_row, (n_prod + 2 * CH) * sizeof(uint16_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_t2_tstart, table_entries * sizeof(uint32_t)));
-    SMH_HIP(hipMalloc((void **)&m->d_t2_rbstart, rb_start.size() * sizeof(uint32_t)));
-    SMH_HIP(hipMemcpyAsync(m->d_t2_rbstart, rb_start.data(), rb_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    SMH_HIP(hipMemsetAsync(m->d_t2_prod, 0, (n_prod + 2 * CH) * sizeof(T), s));
-    SMH_HIP(hipMemsetAsync(m->d_t2_row, 0, (n_prod + 2 * CH) * sizeof(uint16_t), s));  // (slack: the dump slot)
+    SMH_TRY(t.prod.alloc((n_prod + 2 * CH) * sizeof(T)));
+    SMH_TRY(t.row.alloc(n_prod + 2 * CH));
+    SMH_TRY(t.tstart.alloc(table_entries));
+    SMH_TRY(t.rbstart.alloc(rb_start.size()));
+    SMH_HIP(hipMemcpyAsync(t.rbstart.get(), rb_start.data(), rb_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    SMH_HIP(hipMemsetAsync(t.prod.get(), 0, (n_prod + 2 * CH) * sizeof(T), s));
+    SMH_HIP(hipMemsetAsync(t.row.get(), 0, (n_prod + 2 * CH) * sizeof(uint16_t), s));  // (slack: the dump slot)
     if (n_chunks) {
-        hipLaunchKernelGGL(k_t3_rowcode, dim3(wgrid), dim3(kBlock), 0, s, n_chunks, obase, preal, prow, m->d_t2_rbstart, n_rb, (uint32_t)sizeof(T), m->d_t2_row);
+        hipLaunchKernelGGL(k_t3_rowcode, dim3(wgrid), dim3(kBlock), 0, s, n_chunks, obase, preal, prow, t.rbstart.get(), n_rb, (uint32_t)sizeof(T), t.row.get());
         SMH_HIP(hipGetLastError());
     stage("allocs + rowcode");
     }
     // (obase of a slice's first chunk = where its products begin; empty slices have none)
-    hipLaunchKernelGGL(k_t3_table, dim3(grid), dim3(kBlock), 0, s, prow, m->d_t3_cptr, obase, n_cb, n_rb, m->d_t2_rbstart, m->d_t2_tstart);
+    hipLaunchKernelGGL(k_t3_table, dim3(grid), dim3(kBlock), 0, s, prow, t.cptr.get(), obase, n_cb, n_rb, t.rbstart.get(), t.tstart.get());
     SMH_HIP(hipGetLastError());
     SMH_HIP(hipStreamSynchronize(s));
     stage("table");
@@ -867,42 +867,31 @@ static int build_t(::smh_crs *m) {
         SMH_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10));
     // (the row codes are byte offsets into a wavefront's sums and must fit 16 bits)
     if (((uint64_t)R + 1) * sizeof(T) > 0xFFFFu) return fail(SMH_ERR_INVALID, "tiled variant: row blocks of %u rows do not fit the 16-bit row codes", R);
-    m->t2_n_cb = n_cb;
-    m->t2_n_rb = n_rb;
-    m->t2_R = R;
-    m->t2_tot = slots;
-    m->t3_n_chunks = n_chunks;
-    m->t3_max_slice_chunks = max_slice_chunks;
-    m->t3_n_prod = n_prod;
-    m->t3_dups = h_cut != 0;
+    t.n_cb = n_cb;
+    t.n_rb = n_rb;
+    t.R = R;
+    t.tot = slots;
+    t.n_chunks = n_chunks;
+    t.max_slice_chunks = max_slice_chunks;
+    t.n_prod = n_prod;
+    t.dups = h_cut != 0;
     return SMH_OK;
 }
 
 uint32_t tiled_slice_columns(int dtype) { return t3_slice(dtype); }
 
-void tiled_free(::smh_crs *m) {
-    (void)hipFree(m->d_t2_val); (void)hipFree(m->d_t2_prod); (void)hipFree(m->d_t2_code); (void)hipFree(m->d_t2_row);
-    (void)hipFree(m->d_t3_cptr); (void)hipFree(m->d_t3_chunk); (void)hipFree(m->d_t2_tstart); (void)hipFree(m->d_t2_rbstart);
-    m->d_t2_val = m->d_t2_prod = nullptr;
-    m->d_t2_code = m->d_t2_row = nullptr;
-    m->d_t3_cptr = nullptr;
-    m->d_t3_chunk = nullptr;
-    m->d_t2_tstart = m->d_t2_rbstart = nullptr;
-    m->t2_built = m->t2_ok = false;
-}
-
 int tiled_build(::smh_crs *m) {
-    if (m->t2_built) return m->t2_ok ? SMH_OK : fail(SMH_ERR_INVALID, "the tiled copy could not be built for this matrix");
+    if (m->tiled.state == Form::Ready) return SMH_OK;
+    if (m->tiled.state == Form::Refused) return fail(SMH_ERR_INVALID, "the tiled copy could not be built for this matrix");
     SMH_TRY(columns_within_n_cols(m, "tiled variant"));  // (the slice tables are sized from n_cols)
-    m->t2_built = true;
-    const int rc = m->dtype == SMH_F64 ? build_t<double>(m) : build_t<float>(m);
+    Tiled t;
+    const int rc = m->dtype == SMH_F64 ? build_t<double>(m, t) : build_t<float>(m, t);
     if (rc != SMH_OK) {
-        const std::string keep = smh_last_error();
-        tiled_free(m);
-        m->t2_built = true;  // do not try again
-        return fail(rc, "%s", keep.c_str());
+        m->tiled.state = Form::Refused;  // do not try again (what was built goes with t)
+        return rc;
     }
-    m->t2_ok = true;
+    t.state = Form::Ready;
+    m->tiled = std::move(t);
     return SMH_OK;
 }
 
@@ -912,14 +901,14 @@ int tiled_array(::smh_crs *m, int which, void *out, size_t capacity_bytes, size_
     const void *src = nullptr;
     size_t bytes = 0;
     switch (which) {
-        case 0: src = m->d_t3_cptr; bytes = ((size_t)m->t2_n_cb + 1) * 4; break;
-        case 1: src = m->d_t3_chunk; bytes = (size_t)m->t3_n_chunks * sizeof(T3Chunk); break;
-        case 2: src = m->d_t2_code; bytes = (size_t)m->t3_n_chunks * chunk_slots * 2; break;
-        case 3: src = m->d_t2_val; bytes = (size_t)m->t3_n_chunks * chunk_slots * vs; break;
-        case 4: src = m->d_t2_row; bytes = (size_t)m->t3_n_prod * 2; break;
-        case 5: src = m->d_t2_rbstart; bytes = ((size_t)m->t2_n_rb + 1) * 4; break;
-        case 6: src = m->d_t2_tstart; bytes = ((size_t)m->t2_n_rb + 1) * m->t2_n_cb * 4; break;
-        case 7: src = m->d_t2_prod; bytes = (size_t)m->t3_n_prod * vs; break;
+        case 0: src = m->tiled.cptr.get(); bytes = ((size_t)m->tiled.n_cb + 1) * 4; break;
+        case 1: src = m->tiled.chunk.get(); bytes = (size_t)m->tiled.n_chunks * sizeof(T3Chunk); break;
+        case 2: src = m->tiled.code.get(); bytes = (size_t)m->tiled.n_chunks * chunk_slots * 2; break;
+        case 3: src = m->tiled.val.get(); bytes = (size_t)m->tiled.n_chunks * chunk_slots * vs; break;
+        case 4: src = m->tiled.row.get(); bytes = (size_t)m->tiled.n_prod * 2; break;
+        case 5: src = m->tiled.rbstart.get(); bytes = ((size_t)m->tiled.n_rb + 1) * 4; break;
+        case 6: src = m->tiled.tstart.get(); bytes = ((size_t)m->tiled.n_rb + 1) * m->tiled.n_cb * 4; break;
+        case 7: src = m->tiled.prod.get(); bytes = (size_t)m->tiled.n_prod * vs; break;
         default: return fail(SMH_ERR_INVALID, "smh_crs_tiled_array: unknown array %d", which);
     }
     if (bytes_out) *bytes_out = bytes;
@@ -936,17 +925,17 @@ template <typename T>
 static int launch_t(::smh_crs *m, const void *x, size_t x_len, void *y, hipStream_t s) {
     constexpr uint32_t CH = t3_chunk<T>(), kT3Slice = T3<T>::kSlice;
     constexpr int kT3ExpandThreads = T3<T>::kThreads;
-    const size_t lds1 = ((size_t)kT3Slice + (kT3ExpandThreads / 64) * CH) * sizeof(T), lds2 = ((size_t)m->t2_R + 1) * sizeof(T);
+    const size_t lds1 = ((size_t)kT3Slice + (kT3ExpandThreads / 64) * CH) * sizeof(T), lds2 = ((size_t)m->tiled.R + 1) * sizeof(T);
     static const uint32_t xcd_map = getenv("SMH_TILED_XCD") ? (uint32_t)atoi(getenv("SMH_TILED_XCD")) : 3u;  // tuning knob: bit 0 pass 1, bit 1 pass 2
-    if (m->t3_n_chunks) {
+    if (m->tiled.n_chunks) {
         // a workgroup pays for staging its slice of x (16384 entries), so it should fold several times as many entries: ~65 000
         // (round 2's measurement, profiles/r02_tiled_pass1.log) = 16 chunks per wavefront
-        const uint64_t per_slice = (uint64_t)m->t3_n_chunks * CH / (m->t2_n_cb ? m->t2_n_cb : 1);
+        const uint64_t per_slice = (uint64_t)m->tiled.n_chunks * CH / (m->tiled.n_cb ? m->tiled.n_cb : 1);
         uint32_t parts = (uint32_t)((per_slice + 32768) / 65536);
         parts = parts < 1 ? 1 : (parts > 64 ? 64 : parts);
         // (a wavefront keeps the descriptors of its chunks in one register: at most 64 chunks each, 1024 per 16-wavefront workgroup)
         constexpr uint32_t per_wg = 64u * (uint32_t)(kT3ExpandThreads / 64);
-        const uint32_t need = (m->t3_max_slice_chunks + per_wg - 1u) / per_wg;
+        const uint32_t need = (m->tiled.max_slice_chunks + per_wg - 1u) / per_wg;
         if (parts < need) parts = need;
         static const int ahead = getenv("SMH_TILED_AHEAD") ? atoi(getenv("SMH_TILED_AHEAD")) : kT3Ahead;  // tuning knob: chunks in flight per wavefront
         auto *exp = ahead == 2 ? k_t3_expand<T, 2> : ahead == 4 ? k_t3_expand<T, 4> : k_t3_expand<T, 3>;
@@ -966,7 +955,7 @@ static int launch_t(::smh_crs *m, const void *x, size_t x_len, void *y, hipStrea
         // near the one above take the one whose items divide most evenly (611 slices x 8 parts over 512 workgroups: 10 against 9.5 on
         // average, 5 % lost; x 10 parts: 12 against 11.9 -- measured 572 against 586-601 us on f32, 1015-1044 against 1051 on f64)
         auto longest = [&](uint32_t c) {  // items of the busiest workgroup
-            const uint64_t items = (uint64_t)m->t2_n_cb * c;
+            const uint64_t items = (uint64_t)m->tiled.n_cb * c;
             return (xcd_map & 1u) ? ((items + 7) / 8 + wgs / 8 - 1) / (wgs / 8) : (items + wgs - 1) / wgs;
         };
         {
@@ -979,11 +968,11 @@ static int launch_t(::smh_crs *m, const void *x, size_t x_len, void *y, hipStrea
             parts = best;
         }
         if (const char *e = getenv("SMH_TILED_PARTS")) { const int v = atoi(e); if (v >= (int)need && v <= 64) parts = (uint32_t)v; }  // tuning knob
-        const uint32_t g1 = m->t2_n_cb * parts;  // (slice, part) items
+        const uint32_t g1 = m->tiled.n_cb * parts;  // (slice, part) items
         const uint32_t per_xcd = (xcd_map & 1u) ? (g1 + 7u) / 8u : 0u;
         if ((xcd_map & 1u) ? wgs / 8u > per_xcd : wgs > g1) wgs = (xcd_map & 1u) ? (per_xcd ? per_xcd * 8u : 8u) : (g1 ? g1 : 1u);
-        hipLaunchKernelGGL(exp, dim3(wgs), dim3(kT3ExpandThreads), lds1, s, (const T *)x, (uint64_t)x_len, (const T *)m->d_t2_val, m->d_t2_code,
-                           m->d_t3_cptr, (const T3Chunk *)m->d_t3_chunk, (T *)m->d_t2_prod, parts, g1, per_xcd);
+        hipLaunchKernelGGL(exp, dim3(wgs), dim3(kT3ExpandThreads), lds1, s, (const T *)x, (uint64_t)x_len, (const T *)m->tiled.val.get(), m->tiled.code.get(),
+                           m->tiled.cptr.get(), (const T3Chunk *)m->tiled.chunk.get(), (T *)m->tiled.prod.get(), parts, g1, per_xcd);
         SMH_HIP(hipGetLastError());
     }
     // pass 2: one wavefront per row block, and the wavefronts of ADJACENT row blocks share a workgroup and walk the slices in lock step
@@ -1003,16 +992,16 @@ static int launch_t(::smh_crs *m, const void *x, size_t x_len, void *y, hipStrea
     uint32_t waves2 = 1;
     for (uint32_t w = std::min(fit, 16u); w > 1; --w) {
         const bool packs = (uint64_t)(fit / w) * w * 10 >= (uint64_t)fit * 9;                      // workgroups of w leave at most a tenth of that unused
-        const bool spreads = ((uint64_t)m->t2_n_rb + w - 1) / w >= (uint64_t)cus * 9 / 10;          // ... and there is a workgroup for (nearly) every CU
+        const bool spreads = ((uint64_t)m->tiled.n_rb + w - 1) / w >= (uint64_t)cus * 9 / 10;          // ... and there is a workgroup for (nearly) every CU
         if (packs && spreads) { waves2 = w; break; }
     }
     if (waves2_env >= 1 && (uint32_t)waves2_env <= std::min(fit, 16u)) waves2 = (uint32_t)waves2_env;
-    const uint32_t g2 = (m->t2_n_rb + waves2 - 1u) / waves2, g2r = (xcd_map & 2u) ? (g2 + 7u) & ~7u : g2;
+    const uint32_t g2 = (m->tiled.n_rb + waves2 - 1u) / waves2, g2r = (xcd_map & 2u) ? (g2 + 7u) & ~7u : g2;
     static const int batch = getenv("SMH_TILED_BATCH") ? atoi(getenv("SMH_TILED_BATCH")) : kT3Batch;  // tuning knob: 2, 4 or 8 tiles per batch
-    auto *red = batch == 8 ? (m->t3_dups ? k_t3_reduce<T, true, 8> : k_t3_reduce<T, false, 8>)
-                : batch == 2 ? (m->t3_dups ? k_t3_reduce<T, true, 2> : k_t3_reduce<T, false, 2>)
-                             : (m->t3_dups ? k_t3_reduce<T, true, 4> : k_t3_reduce<T, false, 4>);
-    hipLaunchKernelGGL(red, dim3(g2r), dim3(64 * waves2), (size_t)waves2 * stride2, s, (const T *)m->d_t2_prod, m->d_t2_row, m->d_t2_tstart, m->t2_n_cb, m->t2_n_rb, m->d_t2_rbstart,
+    auto *red = batch == 8 ? (m->tiled.dups ? k_t3_reduce<T, true, 8> : k_t3_reduce<T, false, 8>)
+                : batch == 2 ? (m->tiled.dups ? k_t3_reduce<T, true, 2> : k_t3_reduce<T, false, 2>)
+                             : (m->tiled.dups ? k_t3_reduce<T, true, 4> : k_t3_reduce<T, false, 4>);
+    hipLaunchKernelGGL(red, dim3(g2r), dim3(64 * waves2), (size_t)waves2 * stride2, s, (const T *)m->tiled.prod.get(), m->tiled.row.get(), m->tiled.tstart.get(), m->tiled.n_cb, m->tiled.n_rb, m->tiled.rbstart.get(),
                        (T *)y, xcd_map >> 1 & 1u, stride2);
     SMH_HIP(hipGetLastError());
     return SMH_OK;

@@ -1,5 +1,6 @@
 """Handle lifetime: every lazily built workspace (merge table, ring plans incl. the wide and the banded ring, 16-bit
-column arrays, K1s windows and codes, K2c blocked copy, assembly scratch) is released with its handle, and so is every
+column arrays, K1s windows and codes, K2c / K2f / K2s / K2t copies, assembly scratch) is released with its handle -- also
+after it was dropped and built again inside the handle's life (sort_rows, update_values, scale, another block width) -- and so is every
 array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay) -- device
 memory in use returns to where it started after many create / use / destroy rounds."""
 import gc
@@ -11,7 +12,7 @@ import torch
 
 import oracle
 import sparsemat_amd as sm
-from util import random_crs
+from util import assert_spmv_close, random_crs
 
 pytestmark = pytest.mark.gpu
 
@@ -51,13 +52,27 @@ def _exercise(rng, kind):
     m = sm.SparseMatCRS.from_raw_parts(n, n_cols, off, col, val)
     x = rng.uniform(-1, 1, n_cols).astype(val.dtype)
     m.set_colblock_shift(12)  # at most 39 column blocks for these sizes
-    for variant in ("auto", "vector", "merge", "stream", "colblock", "colfused", "colsplit", "tiled", "seq"):
+    variants = ("auto", "vector", "merge", "stream", "colblock", "colfused", "colsplit", "tiled", "seq")
+    for variant in variants:
         m.mvp(x, variant=variant)
     m.set_vector_lanes(4)
     m.mvp(x, variant="vector")
     m.inner_prod(np.ones(n, val.dtype), x)
     m.sort_rows()
     m.mvp(x, variant="auto")
+    # every derived form dropped and built again, several times inside one handle's life: new values, a scale, another block width
+    s_col, _ = oracle.crs_sort_rows(off, col, val)
+    fresh = rng.uniform(-1, 1, len(val)).astype(val.dtype)
+    m.update_values(fresh)
+    for variant in variants:
+        m.mvp(x, variant=variant)
+    m.scale(0.5)  # (a power of two: the expected values below are exact)
+    for variant in variants:
+        m.mvp(x, variant=variant)
+    m.set_colblock_shift(13)
+    s_val = fresh * val.dtype.type(0.5)
+    for variant in variants:
+        assert_spmv_close(m.mvp(x, variant=variant), off, s_col, s_val, x, "kind %d, %s after sort / update / scale / shift" % (kind, variant))
     t = sm.SparseMatCRS.from_triplets(rng.integers(0, 500, 5000), rng.integers(0, 400, 5000),
                                       rng.uniform(-1, 1, 5000).astype(np.float32))
     t.sort_rows()
