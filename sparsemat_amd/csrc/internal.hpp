@@ -167,6 +167,54 @@ template <typename T> class DevArray {
     T *p_ = nullptr;
 };
 
+// A stream (non-blocking), an event (untimed) and pinned host memory: empty until create / alloc succeeds, released when the owner goes out of
+// scope or is assigned another (whose owner takes, and releases when it goes, what this one held).  Nothing synchronises a stream before it goes.
+struct Stream {
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    Stream &operator=(Stream &&o) noexcept { std::swap(s_, o.s_); return *this; }
+    ~Stream() { if (s_) (void)hipStreamDestroy(s_); }
+    int create() {
+        *this = Stream();
+        SMH_HIP(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+        return SMH_OK;
+    }
+    hipStream_t get() const { return s_; }
+
+  private:
+    hipStream_t s_ = nullptr;
+};
+struct Event {
+    Event() = default;
+    Event(Event &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    Event &operator=(Event &&o) noexcept { std::swap(e_, o.e_); return *this; }
+    ~Event() { if (e_) (void)hipEventDestroy(e_); }
+    int create() {
+        *this = Event();
+        SMH_HIP(hipEventCreateWithFlags(&e_, hipEventDisableTiming));
+        return SMH_OK;
+    }
+    hipEvent_t get() const { return e_; }
+
+  private:
+    hipEvent_t e_ = nullptr;
+};
+struct PinnedBuf {
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { std::swap(p_, o.p_); return *this; }
+    ~PinnedBuf() { if (p_) (void)hipHostFree(p_); }
+    int alloc(size_t bytes, unsigned flags) {  // flags: hipHostMalloc's
+        *this = PinnedBuf();
+        SMH_HIP(hipHostMalloc(&p_, bytes, flags));
+        return SMH_OK;
+    }
+    void *get() const { return p_; }
+
+  private:
+    void *p_ = nullptr;
+};
+
 // rocPRIM's two-phase calls: `call` names `tmp` and `bytes`; it is run once to size the temporary storage (bytes ? bytes : 16),
 // then on it; stream s is synchronised before the storage is freed
 #define SMH_ROCPRIM(s, call)                                           \

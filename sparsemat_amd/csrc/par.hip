@@ -65,11 +65,35 @@ int cg_par_p(int dtype, const void *sc_in, void *sc_out, const void *rr_vals, ui
 struct smh_comm {
     ncclComm_t comm = nullptr;
     int n_ranks = 1, rank = 0, device = 0;
-    hipStream_t s = nullptr;  // for the host-facing helpers (barrier, max)
-    void *d_scratch = nullptr;
+    Stream s;  // for the host-facing helpers (barrier, max)
+    DevArray<char> d_scratch;
 };
 
 namespace {
+
+// What a block owns beside its matrix, in three members.  The two that are built on first use are filled in a local instance and
+// move-assigned into the block when every array exists (`built`): a failed build leaves the block as it was, holding nothing.
+struct BlockQueues {  // streams and events (finish_par)
+    Stream s;
+    Stream sx;          // the exchange's stream when it runs beside the interior rows' product
+    Event fork, join;   // s -> sx (what the exchange needs is written), sx -> s (the exchange is done)
+    Event slice;        // own slice of the vector being exchanged is written
+    Event done;         // this block's pulls from its peers are complete
+    Event red[2];       // its value of fold slot 0 / 1 is written
+    Event all[2];       // (block 0) every block's value of the slot is written
+};
+struct CgWork {  // CG state (first solve; ensure_cg_state)
+    bool built = false;
+    DevArray<char> r, ap, partials;
+    DevArray<char> dotp;     // the SpMV's p.Ap partials (one per 256-row tile), folded by launch_fold2 through partials
+    size_t dotp_cap = 0;
+    DevArray<char> sc, sc2;  // the scalars are double-buffered: the alpha / update launch reads sc and writes sc2, the beta / p launch back (cg.hip)
+    DevArray<char> redv;     // RCCL backend: 2 x n_blocks values (fold slots)
+};
+struct HostStaging {  // staging of the host-vector API (smh_par_spmv)
+    bool built = false;
+    DevArray<char> x, y;
+};
 
 struct ParBlock {
     size_t index = 0;             // global block id
@@ -77,25 +101,13 @@ struct ParBlock {
     smh_crs *m = nullptr;
     bool owns_m = true;
     size_t r0 = 0, r1 = 0;        // global rows [r0, r1)
-    hipStream_t s = nullptr;
-    hipStream_t sx = nullptr;       // the exchange's stream when it runs beside the interior rows' product
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // s -> sx (what the exchange needs is written), sx -> s (the exchange is done)
     // INTERIOR rows [in0, in1) (local): no other block references them and they reference no other block's columns, so their
     // product needs nothing from the exchange and gives nothing to it (in1 <= in0: none)
     size_t in0 = 0, in1 = 0;
-    hipEvent_t ev_slice = nullptr;  // own slice of the vector being exchanged is written
-    hipEvent_t ev_done = nullptr;   // this block's pulls from its peers are complete
-    hipEvent_t ev_red[2] = {nullptr, nullptr};  // its value of fold slot 0 / 1 is written
-    hipEvent_t ev_all[2] = {nullptr, nullptr};  // (block 0) every block's value of the slot is written
     ncclComm_t comm = nullptr;    // RCCL backend: this block's rank of the communicator
-    // staging of the host-vector API (smh_par_spmv)
-    void *d_x = nullptr, *d_y = nullptr;
-    // CG state (first solve)
-    void *d_r = nullptr, *d_ap = nullptr, *d_partials = nullptr, *d_sc = nullptr;
-    void *d_sc2 = nullptr;  // the scalars are double-buffered: the alpha / update launch reads d_sc and writes d_sc2, the beta / p launch back (cg.hip)
-    void *d_dotp = nullptr;  // the SpMV's p.Ap partials (one per 256-row tile), folded by launch_fold2 through d_partials
-    size_t dotp_cap = 0;
-    void *d_redv = nullptr;       // RCCL backend: 2 x n_blocks values (fold slots)
+    BlockQueues q;
+    CgWork cg;
+    HostStaging io;
 };
 
 constexpr int kMaxPull = 32;  // segments per pull-kernel launch
@@ -182,8 +194,8 @@ struct smh_par {
     std::vector<uint8_t> needs;
     std::vector<size_t> split;      // empty: the reference's partition (R rows per block); else n_blocks + 1 row boundaries
     std::vector<uint8_t> peer_ok;   // [dst local * n_local + src local]: dst's device can read src's memory directly
-    void *h_red = nullptr;          // PEER backend: 2 x n_blocks fold slots in pinned host memory (all devices map it)
-    void *h_sc = nullptr;           // pinned copy of block 0's CG scalars
+    PinnedBuf h_red;                // PEER backend: 2 x n_blocks fold slots in pinned host memory (all devices map it)
+    PinnedBuf h_sc;                 // pinned copy of block 0's CG scalars
     smh_par_vec *cg_p = nullptr;    // the search direction of the solver (full-length per block)
     smh_par_vec *io_b = nullptr, *io_x = nullptr;  // staging of the host-vector solve
     ParPool *pool = nullptr;        // issuing threads (lazy; blocks 1 .. n_local - 1)
@@ -193,7 +205,7 @@ struct smh_par {
 struct smh_par_vec {
     smh_par *p = nullptr;
     size_t n = 0;
-    std::vector<void *> d;  // per local block, n entries on its device
+    std::vector<DevArray<char>> d;  // per local block, n entries on its device
 };
 
 namespace {
@@ -216,8 +228,8 @@ struct DeviceGuard {
 int sync_all(smh_par *p) {
     for (ParBlock &blk : p->b) {
         SMH_TRY(use(blk));
-        SMH_HIP(hipStreamSynchronize(blk.s));
-        if (blk.sx) SMH_HIP(hipStreamSynchronize(blk.sx));
+        SMH_HIP(hipStreamSynchronize(blk.q.s.get()));
+        if (blk.q.sx.get()) SMH_HIP(hipStreamSynchronize(blk.q.sx.get()));
     }
     return SMH_OK;
 }
@@ -310,6 +322,7 @@ int par_for(smh_par *p, const std::function<int(size_t)> &fn) {
 struct Part {
     size_t n_blocks, n_rows;
     const size_t *split;
+    const uint8_t *needs; const uint32_t *lo, *hi;  // the blocks' column intervals: block q references [lo[q], hi[q]] when needs[q]
 };
 
 void block_rows(const Part &pt, size_t k, size_t *r0, size_t *r1) {
@@ -320,22 +333,22 @@ void block_rows(const Part &pt, size_t k, size_t *r0, size_t *r1) {
 }
 
 // the part of block src's slice that block q's columns reference (empty: *a == *e == 0)
-void recv_range(const Part &pt, const uint8_t *needs, const uint32_t *lo, const uint32_t *hi, size_t q, size_t src, size_t *a, size_t *e) {
+void recv_range(const Part &pt, size_t q, size_t src, size_t *a, size_t *e) {
     *a = *e = 0;
-    if (q == src || !needs[q]) return;
+    if (q == src || !pt.needs[q]) return;
     size_t s0, s1;
     block_rows(pt, src, &s0, &s1);
-    const size_t x0 = lo[q] > s0 ? lo[q] : s0, x1 = (size_t)hi[q] + 1 < s1 ? (size_t)hi[q] + 1 : s1;
+    const size_t x0 = pt.lo[q] > s0 ? pt.lo[q] : s0, x1 = (size_t)pt.hi[q] + 1 < s1 ? (size_t)pt.hi[q] + 1 : s1;
     if (x0 < x1) { *a = x0; *e = x1; }
 }
 
-void plan_summary(const Part &pt, const uint8_t *needs, const uint32_t *lo, const uint32_t *hi, int *auto_mode, size_t *max_recv) {
+void plan_summary(const Part &pt, int *auto_mode, size_t *max_recv) {
     size_t worst = 0;
     for (size_t q = 0; q < pt.n_blocks; ++q) {
         size_t got = 0;
         for (size_t src = 0; src < pt.n_blocks; ++src) {
             size_t a, e;
-            recv_range(pt, needs, lo, hi, q, src, &a, &e);
+            recv_range(pt, q, src, &a, &e);
             got += e - a;
         }
         worst = got > worst ? got : worst;
@@ -344,7 +357,7 @@ void plan_summary(const Part &pt, const uint8_t *needs, const uint32_t *lo, cons
     if (auto_mode) *auto_mode = pt.n_blocks <= 1 ? SMH_EXCHANGE_NONE : (worst * 2 < pt.n_rows ? SMH_EXCHANGE_WINDOW : SMH_EXCHANGE_ALLGATHER);
 }
 
-Part part_of(const smh_par *p) { return Part{p->n_blocks, p->n_rows, p->split.empty() ? nullptr : p->split.data()}; }
+Part part_of(const smh_par *p) { return Part{p->n_blocks, p->n_rows, p->split.empty() ? nullptr : p->split.data(), p->needs.data(), p->lo.data(), p->hi.data()}; }
 
 // One block has nobody to exchange with.  SMH_PAR_EXCHANGE_SINGLE=1 (test knob) still sends a lone RANK through the RCCL
 // calls -- an in-place all-gather of one rank, an empty send/receive group, the 1-element gathers of the folds -- so that
@@ -362,7 +375,7 @@ int resolve_mode(const smh_par *p, int mode, int *out) {
     if (mode == SMH_EXCHANGE_AUTO) {
         int m = SMH_EXCHANGE_ALLGATHER;
         // a window is addressed by column AND owned by row: only meaningful when the vector is both (square matrix)
-        if (p->n_rows == p->n_cols) plan_summary(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), &m, nullptr);
+        if (p->n_rows == p->n_cols) plan_summary(part_of(p), &m, nullptr);
         *out = m;
         return SMH_OK;
     }
@@ -376,15 +389,25 @@ ncclDataType_t nccl_type(int dtype) { return dtype == SMH_F64 ? ncclDouble : ncc
 
 ncclComm_t comm_of(const smh_par *p, const ParBlock &blk) { return p->rank_comm ? p->rank_comm->comm : blk.comm; }
 
+// is every local block on a device of its own?  (*i, *j, optional: the first two blocks that share one)
+bool distinct_devices(const smh_par *p, size_t *i = nullptr, size_t *j = nullptr) {
+    for (size_t a = 0; a < p->b.size(); ++a)
+        for (size_t c = a + 1; c < p->b.size(); ++c)
+            if (p->b[a].device == p->b[c].device) {
+                if (i) { *i = a; *j = c; }
+                return false;
+            }
+    return true;
+}
+
 // RCCL backend of a one-process handle: one communicator rank per block, rank id = block id
 int ensure_comms(smh_par *p) {
     if (p->comms_ready || p->rank_comm || p->n_blocks <= 1) return SMH_OK;
+    size_t i = 0, j = 0;
+    if (!distinct_devices(p, &i, &j))
+        return fail(SMH_ERR_INVALID, "RCCL backend: blocks %zu and %zu share device %d (one device per block needed; use the PEER backend)", i, j, p->b[i].device);
     std::vector<int> devs(p->b.size());
     for (size_t k = 0; k < p->b.size(); ++k) devs[k] = p->b[k].device;
-    for (size_t i = 0; i < devs.size(); ++i)
-        for (size_t j = i + 1; j < devs.size(); ++j)
-            if (devs[i] == devs[j])
-                return fail(SMH_ERR_INVALID, "RCCL backend: blocks %zu and %zu share device %d (one device per block needed; use the PEER backend)", i, j, devs[i]);
     std::vector<ncclComm_t> comms(p->b.size(), nullptr);
     SMH_NCCL(ncclCommInitAll(comms.data(), (int)p->b.size(), devs.data()));
     for (size_t k = 0; k < p->b.size(); ++k) p->b[k].comm = comms[k];
@@ -394,7 +417,7 @@ int ensure_comms(smh_par *p) {
 
 // ---- the exchange -------------------------------------------------------------------------------------------------
 // side: on the blocks' exchange streams (sx) instead of their main ones -- the caller forks and joins them
-hipStream_t xs(const ParBlock &blk, bool side) { return side ? blk.sx : blk.s; }
+hipStream_t xs(const ParBlock &blk, bool side) { return side ? blk.q.sx.get() : blk.q.s.get(); }
 
 int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
     SMH_TRY(ensure_comms(p));
@@ -408,7 +431,7 @@ int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
             SMH_TRY(use(blk));
             for (size_t j = 0; j < nb; ++j) {
                 const size_t a = p->split[j], e = p->split[j + 1];
-                if (e > a) SMH_NCCL(ncclBroadcast((char *)v->d[k] + a * vs, (char *)v->d[k] + a * vs, e - a, dt, (int)j, comm_of(p, blk), xs(blk, side)));
+                if (e > a) SMH_NCCL(ncclBroadcast((char *)v->d[k].get() + a * vs, (char *)v->d[k].get() + a * vs, e - a, dt, (int)j, comm_of(p, blk), xs(blk, side)));
             }
         }
         SMH_NCCL(ncclGroupEnd());
@@ -420,7 +443,7 @@ int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
         for (size_t k = 0; k < p->b.size(); ++k) {
             ParBlock &blk = p->b[k];
             SMH_TRY(use(blk));
-            char *buf = (char *)v->d[k];
+            char *buf = (char *)v->d[k].get();
             SMH_NCCL(ncclAllGather(buf + blk.index * R * vs, buf, R, dt, comm_of(p, blk), xs(blk, side)));
         }
         SMH_NCCL(ncclGroupEnd());
@@ -431,7 +454,7 @@ int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
             for (size_t k = 0; k < p->b.size(); ++k) {
                 ParBlock &blk = p->b[k];
                 SMH_TRY(use(blk));
-                char *tail = (char *)v->d[k] + nb * R * vs;
+                char *tail = (char *)v->d[k].get() + nb * R * vs;
                 SMH_NCCL(ncclBroadcast(tail, tail, rem, dt, (int)(nb - 1), comm_of(p, blk), xs(blk, side)));
             }
             SMH_NCCL(ncclGroupEnd());
@@ -444,13 +467,13 @@ int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
     for (size_t k = 0; k < p->b.size(); ++k) {
         ParBlock &blk = p->b[k];
         SMH_TRY(use(blk));
-        char *buf = (char *)v->d[k];
+        char *buf = (char *)v->d[k].get();
         for (size_t q = 0; q < nb; ++q) {
             if (q == blk.index) continue;
             size_t a, e;
-            recv_range(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), blk.index, q, &a, &e);  // what I need of q's slice
+            recv_range(part_of(p), blk.index, q, &a, &e);  // what I need of q's slice
             if (a < e) SMH_NCCL(ncclRecv(buf + a * vs, e - a, dt, (int)q, comm_of(p, blk), xs(blk, side)));
-            recv_range(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), q, blk.index, &a, &e);  // what q needs of mine
+            recv_range(part_of(p), q, blk.index, &a, &e);  // what q needs of mine
             if (a < e) SMH_NCCL(ncclSend(buf + a * vs, e - a, dt, (int)q, comm_of(p, blk), xs(blk, side)));
         }
     }
@@ -464,7 +487,7 @@ int exchange_rccl(smh_par *p, smh_par_vec *v, int mode, bool side) {
 int peer_mark(smh_par *p, size_t k, bool side) {
     ParBlock &blk = p->b[k];
     SMH_TRY(use(blk));
-    SMH_HIP(hipEventRecord(blk.ev_slice, xs(blk, side)));
+    SMH_HIP(hipEventRecord(blk.q.slice.get(), xs(blk, side)));
     return SMH_OK;
 }
 // 2. block qi pulls what it needs from the owners' buffers
@@ -480,7 +503,7 @@ int peer_pull(smh_par *p, smh_par_vec *v, int mode, size_t qi, bool side, uint8_
         if (args.n == 0) return SMH_OK;
         uint64_t blocks = (words / 4 + kBlock - 1) / kBlock;
         blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-        hipLaunchKernelGGL(k_peer_pull, dim3((unsigned)blocks), dim3(kBlock), 0, xs(q, side), (uint32_t *)v->d[qi], args);
+        hipLaunchKernelGGL(k_peer_pull, dim3((unsigned)blocks), dim3(kBlock), 0, xs(q, side), (uint32_t *)v->d[qi].get(), args);
         SMH_HIP(hipGetLastError());
         args.n = 0;
         words = 0;
@@ -492,22 +515,22 @@ int peer_pull(smh_par *p, smh_par_vec *v, int mode, size_t qi, bool side, uint8_
         ParBlock &src = p->b[si];
         size_t a = src.r0, e = src.r1;
         if (mode == SMH_EXCHANGE_WINDOW)
-            recv_range(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), q.index, src.index, &a, &e);
+            recv_range(part_of(p), q.index, src.index, &a, &e);
         if (a >= e) continue;
         pulled[qi * nl + si] = 1;
-        SMH_HIP(hipStreamWaitEvent(xs(q, side), src.ev_slice, 0));
+        SMH_HIP(hipStreamWaitEvent(xs(q, side), src.q.slice.get(), 0));
         if (p->peer_ok[qi * nl + si]) {
-            args.src[args.n] = (const uint32_t *)v->d[si];
+            args.src[args.n] = (const uint32_t *)v->d[si].get();
             args.w0[args.n] = (uint64_t)a * wpe;
             args.w1[args.n] = (uint64_t)e * wpe;
             words += (uint64_t)(e - a) * wpe;
             if (++args.n == kMaxPull) SMH_TRY(flush());
         } else {  // no direct access between the two devices: the runtime stages the copy
-            SMH_HIP(hipMemcpyPeerAsync((char *)v->d[qi] + a * vs, q.device, (const char *)v->d[si] + a * vs, src.device, (e - a) * vs, xs(q, side)));
+            SMH_HIP(hipMemcpyPeerAsync((char *)v->d[qi].get() + a * vs, q.device, (const char *)v->d[si].get() + a * vs, src.device, (e - a) * vs, xs(q, side)));
         }
     }
     SMH_TRY(flush());
-    SMH_HIP(hipEventRecord(q.ev_done, xs(q, side)));
+    SMH_HIP(hipEventRecord(q.q.done.get(), xs(q, side)));
     return SMH_OK;
 }
 // 3. block si does not overwrite its slice while a peer may still be reading it
@@ -516,7 +539,7 @@ int peer_guard(smh_par *p, size_t si, bool side, const uint8_t *pulled) {
     ParBlock &src = p->b[si];
     SMH_TRY(use(src));
     for (size_t qi = 0; qi < nl; ++qi)
-        if (pulled[qi * nl + si]) SMH_HIP(hipStreamWaitEvent(xs(src, side), p->b[qi].ev_done, 0));
+        if (pulled[qi * nl + si]) SMH_HIP(hipStreamWaitEvent(xs(src, side), p->b[qi].q.done.get(), 0));
     return SMH_OK;
 }
 
@@ -544,14 +567,14 @@ int exchange(smh_par *p, smh_par_vec *v, int mode, bool side = false) {
 // rows are multiplied: fork() after what the exchange reads is written, join() before what it writes is read.
 int fork_one(ParBlock &blk) {
     SMH_TRY(use(blk));
-    SMH_HIP(hipEventRecord(blk.ev_fork, blk.s));
-    SMH_HIP(hipStreamWaitEvent(blk.sx, blk.ev_fork, 0));
+    SMH_HIP(hipEventRecord(blk.q.fork.get(), blk.q.s.get()));
+    SMH_HIP(hipStreamWaitEvent(blk.q.sx.get(), blk.q.fork.get(), 0));
     return SMH_OK;
 }
 int join_one(ParBlock &blk) {
     SMH_TRY(use(blk));
-    SMH_HIP(hipEventRecord(blk.ev_join, blk.sx));
-    SMH_HIP(hipStreamWaitEvent(blk.s, blk.ev_join, 0));
+    SMH_HIP(hipEventRecord(blk.q.join.get(), blk.q.sx.get()));
+    SMH_HIP(hipStreamWaitEvent(blk.q.s.get(), blk.q.join.get(), 0));
     return SMH_OK;
 }
 int fork_side(smh_par *p) {
@@ -594,19 +617,17 @@ int find_interiors(smh_par *p) {
         const size_t n_tiles = (n_loc + kBlock - 1) / kBlock;
         std::vector<uint8_t> dirty(n_tiles, 0);
         if (smh_crs_nnz(blk.m)) {
-            uint8_t *d_flag = nullptr;
-            SMH_HIP(hipMalloc((void **)&d_flag, n_tiles));
-            hipLaunchKernelGGL(k_par_remote_tiles, dim3((unsigned)n_tiles), dim3(kBlock), 0, blk.s, blk.m->d_off, blk.m->d_col, (uint64_t)n_loc,
-                               (uint32_t)blk.r0, (uint32_t)blk.r1, d_flag);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(dirty.data(), d_flag, n_tiles, hipMemcpyDeviceToHost, blk.s);
-            if (e == hipSuccess) e = hipStreamSynchronize(blk.s);
-            (void)hipFree(d_flag);
-            SMH_HIP(e);
+            DevArray<uint8_t> flag;
+            SMH_TRY(flag.alloc(n_tiles));
+            hipLaunchKernelGGL(k_par_remote_tiles, dim3((unsigned)n_tiles), dim3(kBlock), 0, blk.q.s.get(), blk.m->d_off, blk.m->d_col, (uint64_t)n_loc,
+                               (uint32_t)blk.r0, (uint32_t)blk.r1, flag.get());
+            SMH_HIP(hipGetLastError());
+            SMH_HIP(hipMemcpyAsync(dirty.data(), flag.get(), n_tiles, hipMemcpyDeviceToHost, blk.q.s.get()));
+            SMH_HIP(hipStreamSynchronize(blk.q.s.get()));
         }
         for (size_t q = 0; q < nb; ++q) {  // what block q references of my slice
             size_t a, e;
-            recv_range(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), q, blk.index, &a, &e);
+            recv_range(part_of(p), q, blk.index, &a, &e);
             if (a < e)
                 for (size_t t = (a - blk.r0) / kBlock; t <= (e - 1 - blk.r0) / kBlock; ++t) dirty[t] = 1;
         }
@@ -628,7 +649,7 @@ int find_interiors(smh_par *p) {
 // slot s of block blk: where ITS value goes / where all n_blocks values are read by its fold kernel
 void *red_all(const smh_par *p, const ParBlock &blk, int slot) {
     const size_t vs = dtype_size(p->dtype);
-    char *base = p->backend == SMH_PAR_BACKEND_RCCL ? (char *)blk.d_redv : (char *)p->h_red;
+    char *base = p->backend == SMH_PAR_BACKEND_RCCL ? (char *)blk.cg.redv.get() : (char *)p->h_red.get();
     return base + (size_t)slot * p->n_blocks * vs;
 }
 void *red_mine(const smh_par *p, const ParBlock &blk, int slot) { return (char *)red_all(p, blk, slot) + blk.index * dtype_size(p->dtype); }
@@ -637,20 +658,20 @@ void *red_mine(const smh_par *p, const ParBlock &blk, int slot) { return (char *
 int red_mark(smh_par *p, size_t k, int slot) {  // block k's value of the slot is written once its stream gets here
     ParBlock &blk = p->b[k];
     SMH_TRY(use(blk));
-    SMH_HIP(hipEventRecord(blk.ev_red[slot], blk.s));
+    SMH_HIP(hipEventRecord(blk.q.red[slot].get(), blk.q.s.get()));
     return SMH_OK;
 }
 int red_hub(smh_par *p, int slot) {  // block 0's stream has seen them all
     ParBlock &hub = p->b[0];
     SMH_TRY(use(hub));
-    for (size_t k = 1; k < p->b.size(); ++k) SMH_HIP(hipStreamWaitEvent(hub.s, p->b[k].ev_red[slot], 0));
-    if (p->b.size() > 1) SMH_HIP(hipEventRecord(hub.ev_all[slot], hub.s));
+    for (size_t k = 1; k < p->b.size(); ++k) SMH_HIP(hipStreamWaitEvent(hub.q.s.get(), p->b[k].q.red[slot].get(), 0));
+    if (p->b.size() > 1) SMH_HIP(hipEventRecord(hub.q.all[slot].get(), hub.q.s.get()));
     return SMH_OK;
 }
 int red_wait(smh_par *p, size_t k, int slot) {  // ... and block k's waits for that
     if (k == 0) return SMH_OK;
     SMH_TRY(use(p->b[k]));
-    SMH_HIP(hipStreamWaitEvent(p->b[k].s, p->b[0].ev_all[slot], 0));
+    SMH_HIP(hipStreamWaitEvent(p->b[k].q.s.get(), p->b[0].q.all[slot].get(), 0));
     return SMH_OK;
 }
 
@@ -662,7 +683,7 @@ int combine(smh_par *p, int slot) {
         SMH_NCCL(ncclGroupStart());
         for (ParBlock &blk : p->b) {
             SMH_TRY(use(blk));
-            SMH_NCCL(ncclAllGather(red_mine(p, blk, slot), red_all(p, blk, slot), 1, nccl_type(p->dtype), comm_of(p, blk), blk.s));
+            SMH_NCCL(ncclAllGather(red_mine(p, blk, slot), red_all(p, blk, slot), 1, nccl_type(p->dtype), comm_of(p, blk), blk.q.s.get()));
         }
         SMH_NCCL(ncclGroupEnd());
         return SMH_OK;
@@ -678,47 +699,41 @@ int combine(smh_par *p, int slot) {
 int ensure_cg_state(smh_par *p) {
     const size_t vs = dtype_size(p->dtype);
     for (ParBlock &blk : p->b) {
-        if (blk.d_sc) continue;
+        if (blk.cg.built) continue;
         SMH_TRY(use(blk));
         const size_t n_loc = blk.r1 - blk.r0;
-        SMH_HIP(hipMalloc(&blk.d_r, (n_loc ? n_loc : 1) * vs));
-        SMH_HIP(hipMalloc(&blk.d_ap, (n_loc ? n_loc : 1) * vs));
-        SMH_HIP(hipMalloc(&blk.d_partials, ((size_t)kReducePartials + 8) * vs));
-        blk.dotp_cap = (n_loc + 255) / 256 + 8;
-        SMH_HIP(hipMalloc(&blk.d_dotp, blk.dotp_cap * vs));
-        SMH_HIP(hipMalloc(&blk.d_redv, 2 * p->n_blocks * vs));
-        SMH_HIP(hipMemset(blk.d_redv, 0, 2 * p->n_blocks * vs));
-        SMH_HIP(hipMalloc(&blk.d_sc, cg_scalars_bytes(p->dtype)));
-        SMH_HIP(hipMalloc(&blk.d_sc2, cg_scalars_bytes(p->dtype)));
+        CgWork w;  // (an early return frees what it holds; the block is touched at the last line only)
+        SMH_TRY(w.r.alloc((n_loc ? n_loc : 1) * vs));
+        SMH_TRY(w.ap.alloc((n_loc ? n_loc : 1) * vs));
+        SMH_TRY(w.partials.alloc(((size_t)kReducePartials + 8) * vs));
+        w.dotp_cap = (n_loc + 255) / 256 + 8;
+        SMH_TRY(w.dotp.alloc(w.dotp_cap * vs));
+        SMH_TRY(w.redv.alloc(2 * p->n_blocks * vs));
+        SMH_HIP(hipMemset(w.redv.get(), 0, 2 * p->n_blocks * vs));
+        SMH_TRY(w.sc.alloc(cg_scalars_bytes(p->dtype)));
+        SMH_TRY(w.sc2.alloc(cg_scalars_bytes(p->dtype)));
+        w.built = true;
+        blk.cg = std::move(w);
     }
-    if (!p->h_red) {
-        SMH_HIP(hipHostMalloc(&p->h_red, 2 * p->n_blocks * sizeof(double), hipHostMallocPortable | hipHostMallocMapped));
-        memset(p->h_red, 0, 2 * p->n_blocks * sizeof(double));
+    if (!p->h_red.get()) {
+        SMH_TRY(p->h_red.alloc(2 * p->n_blocks * sizeof(double), hipHostMallocPortable | hipHostMallocMapped));
+        memset(p->h_red.get(), 0, 2 * p->n_blocks * sizeof(double));
     }
-    if (!p->h_sc) SMH_HIP(hipHostMalloc(&p->h_sc, cg_scalars_bytes(p->dtype), hipHostMallocDefault));
+    if (!p->h_sc.get()) SMH_TRY(p->h_sc.alloc(cg_scalars_bytes(p->dtype), hipHostMallocDefault));
     return SMH_OK;
 }
 
 int vec_create(smh_par *p, size_t n, smh_par_vec **out) {
+    const size_t vs = dtype_size(p->dtype);
+    std::vector<DevArray<char>> d(p->b.size());  // (an early return frees what it holds)
+    for (size_t k = 0; k < p->b.size(); ++k) {
+        SMH_TRY(use(p->b[k]));
+        SMH_TRY(d[k].alloc((n ? n : 1) * vs));
+        SMH_HIP(hipMemsetAsync(d[k].get(), 0, (n ? n : 1) * vs, p->b[k].q.s.get()));
+    }
     smh_par_vec *v = new (std::nothrow) smh_par_vec();
     if (!v) return fail(SMH_ERR_OOM, "host allocation failed");
-    v->p = p;
-    v->n = n;
-    v->d.assign(p->b.size(), nullptr);
-    const size_t vs = dtype_size(p->dtype);
-    for (size_t k = 0; k < p->b.size(); ++k) {
-        int rc = use(p->b[k]);
-        if (rc == SMH_OK) {
-            hipError_t e = hipMalloc(&v->d[k], (n ? n : 1) * vs);
-            if (e == hipSuccess) e = hipMemsetAsync(v->d[k], 0, (n ? n : 1) * vs, p->b[k].s);
-            if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(par vec)", __FILE__, __LINE__);
-        }
-        if (rc != SMH_OK) {
-            for (size_t j = 0; j <= k; ++j) { (void)hipSetDevice(p->b[j].device); (void)hipFree(v->d[j]); }
-            delete v;
-            return rc;
-        }
-    }
+    v->p = p; v->n = n; v->d = std::move(d);
     *out = v;
     return SMH_OK;
 }
@@ -727,8 +742,8 @@ void vec_destroy(smh_par_vec *v) {
     if (!v) return;
     for (size_t k = 0; k < v->d.size(); ++k) {
         (void)hipSetDevice(v->p->b[k].device);
-        (void)hipStreamSynchronize(v->p->b[k].s);
-        (void)hipFree(v->d[k]);
+        (void)hipStreamSynchronize(v->p->b[k].q.s.get());
+        v->d[k].reset();
     }
     (void)hipGetLastError();
     delete v;
@@ -745,16 +760,9 @@ int finish_par(smh_par *p) {
     const size_t nl = p->b.size();
     for (ParBlock &blk : p->b) {
         SMH_TRY(use(blk));
-        SMH_HIP(hipStreamCreateWithFlags(&blk.s, hipStreamNonBlocking));
-        SMH_HIP(hipStreamCreateWithFlags(&blk.sx, hipStreamNonBlocking));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_fork, hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_join, hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_slice, hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_done, hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_red[0], hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_red[1], hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_all[0], hipEventDisableTiming));
-        SMH_HIP(hipEventCreateWithFlags(&blk.ev_all[1], hipEventDisableTiming));
+        SMH_TRY(blk.q.s.create());
+        SMH_TRY(blk.q.sx.create());
+        for (Event *e : {&blk.q.fork, &blk.q.join, &blk.q.slice, &blk.q.done, &blk.q.red[0], &blk.q.red[1], &blk.q.all[0], &blk.q.all[1]}) SMH_TRY(e->create());
     }
     // direct device-to-device reads where the hardware offers them (xGMI)
     p->peer_ok.assign(nl * nl, 0);
@@ -769,10 +777,7 @@ int finish_par(smh_par *p) {
             }
             (void)hipGetLastError();
         }
-    bool distinct = true;
-    for (size_t a = 0; a < nl; ++a)
-        for (size_t c = a + 1; c < nl; ++c)
-            if (p->b[a].device == p->b[c].device) distinct = false;
+    const bool distinct = distinct_devices(p);
     if (p->rank_comm) {
         p->backend = SMH_PAR_BACKEND_RCCL;
     } else {
@@ -820,8 +825,8 @@ int smh_comm_create(const void *id, int n_ranks, int rank, smh_comm **out) {
         ncclUniqueId uid;
         memcpy(&uid, id, sizeof uid);
         SMH_NCCL(ncclCommInitRank(&c->comm, n_ranks, uid, rank));
-        SMH_HIP(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
-        SMH_HIP(hipMalloc(&c->d_scratch, 64));
+        SMH_TRY(c->s.create());
+        SMH_TRY(c->d_scratch.alloc(64));
         return SMH_OK;
     };
     const int rc = go();
@@ -834,11 +839,11 @@ int smh_comm_destroy(smh_comm *c) {
     if (!c) return SMH_OK;
     DeviceGuard g;
     (void)hipSetDevice(c->device);
-    if (c->s) { (void)hipStreamSynchronize(c->s); (void)hipStreamDestroy(c->s); }
-    (void)hipFree(c->d_scratch);
+    if (c->s.get()) (void)hipStreamSynchronize(c->s.get());
+    c->s = Stream();
     if (c->comm) (void)ncclCommDestroy(c->comm);
+    delete c;  // (its scratch)
     (void)hipGetLastError();
-    delete c;
     return SMH_OK;
 }
 
@@ -862,10 +867,10 @@ int smh_comm_max_f64(smh_comm *c, double *value_inout) {
     if (!c || !value_inout) return fail(SMH_ERR_INVALID, "NULL argument");
     DeviceGuard g;
     SMH_HIP(hipSetDevice(c->device));
-    SMH_HIP(hipMemcpyAsync(c->d_scratch, value_inout, sizeof(double), hipMemcpyHostToDevice, c->s));
-    SMH_NCCL(ncclAllReduce(c->d_scratch, c->d_scratch, 1, ncclDouble, ncclMax, c->comm, c->s));
-    SMH_HIP(hipMemcpyAsync(value_inout, c->d_scratch, sizeof(double), hipMemcpyDeviceToHost, c->s));
-    SMH_HIP(hipStreamSynchronize(c->s));
+    SMH_HIP(hipMemcpyAsync(c->d_scratch.get(), value_inout, sizeof(double), hipMemcpyHostToDevice, c->s.get()));
+    SMH_NCCL(ncclAllReduce(c->d_scratch.get(), c->d_scratch.get(), 1, ncclDouble, ncclMax, c->comm, c->s.get()));
+    SMH_HIP(hipMemcpyAsync(value_inout, c->d_scratch.get(), sizeof(double), hipMemcpyDeviceToHost, c->s.get()));
+    SMH_HIP(hipStreamSynchronize(c->s.get()));
     return SMH_OK;
 }
 
@@ -879,11 +884,24 @@ int smh_comm_barrier(smh_comm *c) {
 }
 
 // ---- construction ----------------------------------------------------------------------------------------------------
-static int par_fail_cleanup(smh_par *p, int rc, int prev_device) {
-    return keep_error(rc, [&] {
-        smh_par_destroy(p);
-        (void)hipSetDevice(prev_device);
-    });
+// What the three constructors share: the partition's arithmetic checked, a handle with its common fields and n_local blocks, the caller's fill step
+// (the blocks, their column intervals, finish_par), the interiors; a handle that failed is destroyed with the error text kept, the device restored.
+static int make_par(int dtype, size_t n_blocks, size_t n_local, size_t n_rows, size_t n_cols, smh_comm *rank_comm,
+                    const std::function<int(smh_par *)> &fill, smh_par **out) {
+    if (n_blocks == 0) return fail(SMH_ERR_INVALID, "SparseMatPar needs at least one block");
+    const size_t rpb = n_rows / n_blocks;  // sparsemat_par.rs:21
+    if (rpb == 0) return fail(SMH_ERR_INVALID, "fewer rows (%zu) than blocks (%zu): rows per block would be 0 (sparsemat_par.rs:21,32)", n_rows, n_blocks);
+    DeviceGuard g;
+    smh_par *p = new (std::nothrow) smh_par();
+    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
+    p->dtype = dtype; p->n_rows = n_rows; p->n_cols = n_cols; p->rows_per_block = rpb; p->n_blocks = n_blocks; p->rank_comm = rank_comm;
+    p->b.resize(n_local);
+    p->lo.assign(n_blocks, 0); p->hi.assign(n_blocks, 0); p->needs.assign(n_blocks, 0);
+    int rc = fill(p);
+    if (rc == SMH_OK) rc = find_interiors(p);
+    if (rc != SMH_OK) return keep_error(rc, [&] { smh_par_destroy(p); });
+    *out = p;
+    return SMH_OK;
 }
 
 // nnz-balanced boundaries: block k starts at the first row whose entries begin at or beyond k nnz / n_blocks (every block keeps at
@@ -923,23 +941,13 @@ int smh_par_create_split(smh_dtype dtype, size_t n_blocks, const int *device_ids
     if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
     if (split_mode != SMH_SPLIT_ROWS && split_mode != SMH_SPLIT_NNZ) return fail(SMH_ERR_INVALID, "unknown split mode %d", split_mode);
     if (dtype != SMH_F32 && dtype != SMH_F64) return fail(SMH_ERR_INVALID, "unknown dtype %d", (int)dtype);
-    if (n_blocks == 0) return fail(SMH_ERR_INVALID, "SparseMatPar needs at least one block");
-    if (!offset_rows) return fail(SMH_ERR_INVALID, "NULL offset_rows");
-    const size_t rpb = n_rows / n_blocks;  // sparsemat_par.rs:21
-    if (rpb == 0) return fail(SMH_ERR_INVALID, "fewer rows (%zu) than blocks (%zu): rows per block would be 0 (sparsemat_par.rs:21,32)", n_rows, n_blocks);
-    int n_dev = 0;
-    SMH_TRY(smh_device_count(&n_dev));
-    if (n_dev == 0) return fail(SMH_ERR_NO_DEVICE, "no HIP device visible: libsparsemat_hip has no CPU fallback");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    smh_par *p = new (std::nothrow) smh_par();
-    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
-    p->dtype = dtype; p->n_rows = n_rows; p->n_cols = n_cols; p->rows_per_block = rpb; p->n_blocks = n_blocks;
-    p->b.resize(n_blocks);
-    p->lo.assign(n_blocks, 0); p->hi.assign(n_blocks, 0); p->needs.assign(n_blocks, 0);
-    if (split_mode == SMH_SPLIT_NNZ) split_by_nnz(n_blocks, n_rows, offset_rows, p->split);
+    if (n_blocks && !offset_rows) return fail(SMH_ERR_INVALID, "NULL offset_rows");  // (no block at all: make_par's message)
     const size_t vs = dtype_size(dtype);
-    auto go = [&]() -> int {
+    return make_par(dtype, n_blocks, n_blocks, n_rows, n_cols, nullptr, [&](smh_par *p) -> int {
+        int n_dev = 0;
+        SMH_TRY(smh_device_count(&n_dev));
+        if (n_dev == 0) return fail(SMH_ERR_NO_DEVICE, "no HIP device visible: libsparsemat_hip has no CPU fallback");
+        if (split_mode == SMH_SPLIT_NNZ) split_by_nnz(n_blocks, n_rows, offset_rows, p->split);
         std::vector<uint32_t> off;
         for (size_t k = 0; k < n_blocks; ++k) {
             ParBlock &blk = p->b[k];
@@ -958,14 +966,8 @@ int smh_par_create_split(smh_dtype dtype, size_t n_blocks, const int *device_ids
                                    values ? (const char *)values + (size_t)base * vs : nullptr, validate, &blk.m));
             SMH_TRY(own_interval(blk, n_cols, &p->needs[k], &p->lo[k], &p->hi[k]));
         }
-        SMH_TRY(finish_par(p));
-        return find_interiors(p);
-    };
-    const int rc = go();
-    if (rc != SMH_OK) return par_fail_cleanup(p, rc, prev);
-    (void)hipSetDevice(prev);
-    *out = p;
-    return SMH_OK;
+        return finish_par(p);
+    }, out);
 }
 
 int smh_par_adopt(size_t n_blocks, smh_crs *const *blocks, size_t n_rows, smh_par **out) {
@@ -975,20 +977,12 @@ int smh_par_adopt(size_t n_blocks, smh_crs *const *blocks, size_t n_rows, smh_pa
 int smh_par_adopt_split(size_t n_blocks, smh_crs *const *blocks, size_t n_rows, const size_t *split_rows, smh_par **out) {
     if (!out || !blocks) return fail(SMH_ERR_INVALID, "NULL argument");
     if (split_rows && n_blocks) SMH_TRY(check_split(n_blocks, n_rows, split_rows));
-    if (n_blocks == 0) return fail(SMH_ERR_INVALID, "SparseMatPar needs at least one block");
-    const size_t rpb = n_rows / n_blocks;
-    if (rpb == 0) return fail(SMH_ERR_INVALID, "fewer rows (%zu) than blocks (%zu): rows per block would be 0 (sparsemat_par.rs:21,32)", n_rows, n_blocks);
-    for (size_t k = 0; k < n_blocks; ++k)
-        if (!blocks[k]) return fail(SMH_ERR_INVALID, "block %zu is NULL", k);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    smh_par *p = new (std::nothrow) smh_par();
-    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
-    p->dtype = blocks[0]->dtype; p->n_rows = n_rows; p->n_cols = blocks[0]->n_cols; p->rows_per_block = rpb; p->n_blocks = n_blocks;
-    p->b.resize(n_blocks);
-    p->lo.assign(n_blocks, 0); p->hi.assign(n_blocks, 0); p->needs.assign(n_blocks, 0);
-    if (split_rows) p->split.assign(split_rows, split_rows + n_blocks + 1);
-    auto go = [&]() -> int {
+    // (block 0 gives the handle its dtype and its columns; the NULL blocks are named by the fill step, after make_par's own checks)
+    const smh_crs *first = n_blocks ? blocks[0] : nullptr;
+    return make_par(first ? first->dtype : SMH_F32, n_blocks, n_blocks, n_rows, first ? first->n_cols : 0, nullptr, [&](smh_par *p) -> int {
+        for (size_t k = 0; k < n_blocks; ++k)
+            if (!blocks[k]) return fail(SMH_ERR_INVALID, "block %zu is NULL", k);
+        if (split_rows) p->split.assign(split_rows, split_rows + n_blocks + 1);
         for (size_t k = 0; k < n_blocks; ++k) {
             ParBlock &blk = p->b[k];
             blk.index = k;
@@ -1004,14 +998,8 @@ int smh_par_adopt_split(size_t n_blocks, smh_crs *const *blocks, size_t n_rows, 
             SMH_TRY(use(blk));
             SMH_TRY(own_interval(blk, p->n_cols, &p->needs[k], &p->lo[k], &p->hi[k]));
         }
-        SMH_TRY(finish_par(p));
-        return find_interiors(p);
-    };
-    const int rc = go();
-    if (rc != SMH_OK) return par_fail_cleanup(p, rc, prev);
-    (void)hipSetDevice(prev);
-    *out = p;
-    return SMH_OK;
+        return finish_par(p);
+    }, out);
 }
 
 int smh_par_create_rank(smh_comm *comm, size_t n_rows, smh_crs *block, smh_par **out) {
@@ -1025,18 +1013,8 @@ int smh_par_create_rank_split(smh_comm *comm, size_t n_rows, smh_crs *block, siz
     if (!out || !comm || !block) return fail(SMH_ERR_INVALID, "NULL argument");
     const bool own_split = row_begin != (size_t)-1;
     const size_t n_blocks = (size_t)comm->n_ranks, k = (size_t)comm->rank;
-    const size_t rpb = n_rows / n_blocks;
-    if (rpb == 0) return fail(SMH_ERR_INVALID, "fewer rows (%zu) than blocks (%zu): rows per block would be 0 (sparsemat_par.rs:21,32)", n_rows, n_blocks);
-    if (block->device != comm->device) return fail(SMH_ERR_INVALID, "the block lives on device %d, the communicator rank on device %d", block->device, comm->device);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    smh_par *p = new (std::nothrow) smh_par();
-    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
-    p->dtype = block->dtype; p->n_rows = n_rows; p->n_cols = block->n_cols; p->rows_per_block = rpb; p->n_blocks = n_blocks;
-    p->rank_comm = comm;
-    p->b.resize(1);
-    p->lo.assign(n_blocks, 0); p->hi.assign(n_blocks, 0); p->needs.assign(n_blocks, 0);
-    auto go = [&]() -> int {
+    return make_par(block->dtype, n_blocks, 1, n_rows, block->n_cols, comm, [&](smh_par *p) -> int {
+        if (block->device != comm->device) return fail(SMH_ERR_INVALID, "the block lives on device %d, the communicator rank on device %d", block->device, comm->device);
         ParBlock &blk = p->b[0];
         blk.index = k;
         blk.m = block;
@@ -1057,25 +1035,23 @@ int smh_par_create_rank_split(smh_comm *comm, size_t n_rows, smh_crs *block, siz
         };
         const int lrc = local();
         const std::string lmsg = lrc == SMH_OK ? std::string() : std::string(smh_last_error());
-        hipStream_t gs = blk.s ? blk.s : comm->s;  // (the communicator's own stream when this block's could not be made)
+        hipStream_t gs = blk.q.s.get() ? blk.q.s.get() : comm->s.get();  // (the communicator's own stream when this block's could not be made)
         // the ranks publish their column intervals and row ranges (the exchange plan is global): 9 u32 per rank, all-gathered in place
         constexpr size_t W = 9;  // needs, lo, hi, row_begin (low, high word), has its own split, row count (low, high word), local status
         std::vector<uint32_t> table(W * n_blocks, 0);
         table[W * k] = p->needs[k]; table[W * k + 1] = p->lo[k]; table[W * k + 2] = p->hi[k];
         table[W * k + 3] = (uint32_t)blk.r0; table[W * k + 4] = (uint32_t)((uint64_t)blk.r0 >> 32); table[W * k + 5] = own_split;
         table[W * k + 6] = (uint32_t)block->n_rows; table[W * k + 7] = (uint32_t)((uint64_t)block->n_rows >> 32); table[W * k + 8] = (uint32_t)lrc;
-        uint32_t *d_table = nullptr;
-        SMH_HIP(hipMalloc((void **)&d_table, W * n_blocks * sizeof(uint32_t)));
-        auto gather = [&]() -> int {
-            SMH_HIP(hipMemcpyAsync(d_table, table.data(), W * n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, gs));
-            SMH_NCCL(ncclAllGather(d_table + W * k, d_table, W, ncclUint32, comm->comm, gs));
-            SMH_HIP(hipMemcpyAsync(table.data(), d_table, W * n_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, gs));
+        auto gather = [&]() -> int {  // (the device copy of the table lives as long as this step)
+            DevArray<uint32_t> d_table;
+            SMH_TRY(d_table.alloc(W * n_blocks));
+            SMH_HIP(hipMemcpyAsync(d_table.get(), table.data(), W * n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, gs));
+            SMH_NCCL(ncclAllGather(d_table.get() + W * k, d_table.get(), W, ncclUint32, comm->comm, gs));
+            SMH_HIP(hipMemcpyAsync(table.data(), d_table.get(), W * n_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, gs));
             SMH_HIP(hipStreamSynchronize(gs));
             return SMH_OK;
         };
-        const int grc = gather();
-        (void)hipFree(d_table);
-        SMH_TRY(grc);
+        SMH_TRY(gather());
         // from here on every rank holds the same table and runs the same checks in the same order
         if (lrc != SMH_OK) return fail(lrc, "%s", lmsg.c_str());
         for (size_t q = 0; q < n_blocks; ++q)
@@ -1097,47 +1073,32 @@ int smh_par_create_rank_split(smh_comm *comm, size_t n_rows, smh_crs *block, siz
             }
             SMH_TRY(check_split(n_blocks, n_rows, p->split.data()));
         }
-        return find_interiors(p);
-    };
-    const int rc = go();
-    if (rc != SMH_OK) return par_fail_cleanup(p, rc, prev);
-    (void)hipSetDevice(prev);
-    *out = p;
-    return SMH_OK;
+        return SMH_OK;
+    }, out);
 }
 
 int smh_par_destroy(smh_par *p) {
     if (!p) return SMH_OK;
     pool_destroy(p);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
+    DeviceGuard g;
     for (ParBlock &blk : p->b) {
         (void)hipSetDevice(blk.device);
-        if (blk.s) (void)hipStreamSynchronize(blk.s);
+        if (blk.q.s.get()) (void)hipStreamSynchronize(blk.q.s.get());
     }
     vec_destroy(p->cg_p); vec_destroy(p->io_b); vec_destroy(p->io_x);
     for (ParBlock &blk : p->b) {
         (void)hipSetDevice(blk.device);
         if (blk.comm) (void)ncclCommDestroy(blk.comm);
-        if (blk.sx) { (void)hipStreamSynchronize(blk.sx); (void)hipStreamDestroy(blk.sx); }
-        if (blk.s) (void)hipStreamDestroy(blk.s);
-        if (blk.ev_fork) (void)hipEventDestroy(blk.ev_fork);
-        if (blk.ev_join) (void)hipEventDestroy(blk.ev_join);
-        if (blk.ev_slice) (void)hipEventDestroy(blk.ev_slice);
-        if (blk.ev_done) (void)hipEventDestroy(blk.ev_done);
-        if (blk.ev_red[0]) (void)hipEventDestroy(blk.ev_red[0]);
-        if (blk.ev_red[1]) (void)hipEventDestroy(blk.ev_red[1]);
-        if (blk.ev_all[0]) (void)hipEventDestroy(blk.ev_all[0]);
-        if (blk.ev_all[1]) (void)hipEventDestroy(blk.ev_all[1]);
+        if (blk.q.sx.get()) (void)hipStreamSynchronize(blk.q.sx.get());
+        blk.q.sx = Stream();
+        blk.q.s = Stream();
+        blk.q = BlockQueues();  // the events
         if (blk.owns_m) (void)smh_crs_destroy(blk.m);
-        (void)hipFree(blk.d_x); (void)hipFree(blk.d_y); (void)hipFree(blk.d_r); (void)hipFree(blk.d_ap);
-        (void)hipFree(blk.d_partials); (void)hipFree(blk.d_dotp); (void)hipFree(blk.d_sc); (void)hipFree(blk.d_sc2); (void)hipFree(blk.d_redv);
+        blk.io = HostStaging();
+        blk.cg = CgWork();
     }
-    if (p->h_red) (void)hipHostFree(p->h_red);
-    if (p->h_sc) (void)hipHostFree(p->h_sc);
+    delete p;  // (the pinned buffers)
     (void)hipGetLastError();
-    (void)hipSetDevice(prev);
-    delete p;
     return SMH_OK;
 }
 
@@ -1165,7 +1126,7 @@ int smh_par_block(const smh_par *p, size_t block, smh_crs **crs_out, size_t *row
 
 int smh_par_block_stream(const smh_par *p, size_t block, void **stream_out) {
     if (!p || !stream_out || block >= p->b.size()) return fail(SMH_ERR_INVALID, "no such block");
-    *stream_out = p->b[block].s;
+    *stream_out = p->b[block].q.s.get();
     return SMH_OK;
 }
 
@@ -1205,7 +1166,7 @@ int smh_par_scale(smh_par *p, double a) {  // sparsemat_par.rs:135-139
     DeviceGuard g;
     for (ParBlock &blk : p->b) {
         SMH_TRY(use(blk));
-        SMH_HIP(hipStreamSynchronize(blk.s));
+        SMH_HIP(hipStreamSynchronize(blk.q.s.get()));
         SMH_TRY(smh_crs_scale(blk.m, a));
     }
     return SMH_OK;
@@ -1217,10 +1178,7 @@ int smh_par_set_backend(smh_par *p, int backend) {
         if (backend == SMH_PAR_BACKEND_PEER) return fail(SMH_ERR_INVALID, "one process per GPU: the exchange is RCCL");
         return SMH_OK;
     }
-    bool distinct = true;
-    for (size_t a = 0; a < p->b.size(); ++a)
-        for (size_t c = a + 1; c < p->b.size(); ++c)
-            if (p->b[a].device == p->b[c].device) distinct = false;
+    const bool distinct = distinct_devices(p);
     if (backend == SMH_PAR_BACKEND_AUTO) backend = distinct && p->b.size() > 1 ? SMH_PAR_BACKEND_RCCL : SMH_PAR_BACKEND_PEER;
     if (backend != SMH_PAR_BACKEND_PEER && backend != SMH_PAR_BACKEND_RCCL) return fail(SMH_ERR_INVALID, "unknown backend %d", backend);
     if (backend == SMH_PAR_BACKEND_RCCL && !distinct && p->b.size() > 1)
@@ -1238,7 +1196,7 @@ int smh_par_exchange_mode(const smh_par *p, int mode, int *resolved_out, size_t 
     int m = SMH_EXCHANGE_NONE;
     SMH_TRY(resolve_mode(p, mode, &m));
     if (resolved_out) *resolved_out = m;
-    if (max_recv_out) plan_summary(part_of(p), p->needs.data(), p->lo.data(), p->hi.data(), nullptr, max_recv_out);
+    if (max_recv_out) plan_summary(part_of(p), nullptr, max_recv_out);
     return SMH_OK;
 }
 
@@ -1253,17 +1211,17 @@ int smh_par_plan_split(size_t n_blocks, size_t n_rows, const size_t *split_rows,
     if (n_blocks == 0 || (!split_rows && n_rows / n_blocks == 0)) return fail(SMH_ERR_INVALID, "rows per block would be 0 (sparsemat_par.rs:21,32)");
     if (!needs || !lo || !hi || block >= n_blocks) return fail(SMH_ERR_INVALID, "bad plan arguments");
     if (split_rows) SMH_TRY(check_split(n_blocks, n_rows, split_rows));
-    const Part pt{n_blocks, n_rows, split_rows};
+    const Part pt{n_blocks, n_rows, split_rows, needs, lo, hi};
     for (size_t q = 0; q < n_blocks; ++q) {
         size_t a, e;
-        recv_range(pt, needs, lo, hi, block, q, &a, &e);
+        recv_range(pt, block, q, &a, &e);
         if (recv_begin) recv_begin[q] = a;
         if (recv_end) recv_end[q] = e;
-        recv_range(pt, needs, lo, hi, q, block, &a, &e);
+        recv_range(pt, q, block, &a, &e);
         if (send_begin) send_begin[q] = a;
         if (send_end) send_end[q] = e;
     }
-    plan_summary(pt, needs, lo, hi, auto_mode_out, max_recv_out);
+    plan_summary(pt, auto_mode_out, max_recv_out);
     return SMH_OK;
 }
 
@@ -1289,7 +1247,7 @@ int smh_par_vec_upload(smh_par_vec *v, const void *host) {
     const size_t vs = dtype_size(p->dtype);
     for (size_t k = 0; k < p->b.size(); ++k) {
         SMH_TRY(use(p->b[k]));
-        if (v->n) SMH_HIP(hipMemcpyAsync(v->d[k], host, v->n * vs, hipMemcpyHostToDevice, p->b[k].s));
+        if (v->n) SMH_HIP(hipMemcpyAsync(v->d[k].get(), host, v->n * vs, hipMemcpyHostToDevice, p->b[k].q.s.get()));
     }
     return sync_all(p);  // the host buffer is borrowed for the call only
 }
@@ -1304,7 +1262,7 @@ int smh_par_vec_download(const smh_par_vec *v, void *host) {
         const ParBlock &blk = p->b[k];
         SMH_TRY(use(blk));
         if (blk.r1 > blk.r0)
-            SMH_HIP(hipMemcpyAsync((char *)host + blk.r0 * vs, (const char *)v->d[k] + blk.r0 * vs, (blk.r1 - blk.r0) * vs, hipMemcpyDeviceToHost, blk.s));
+            SMH_HIP(hipMemcpyAsync((char *)host + blk.r0 * vs, (const char *)v->d[k].get() + blk.r0 * vs, (blk.r1 - blk.r0) * vs, hipMemcpyDeviceToHost, blk.q.s.get()));
     }
     return sync_all(p);
 }
@@ -1314,14 +1272,14 @@ int smh_par_vec_download_block(const smh_par_vec *v, size_t local_block, void *h
     DeviceGuard g;
     const ParBlock &blk = v->p->b[local_block];
     SMH_TRY(use(blk));
-    if (v->n) SMH_HIP(hipMemcpyAsync(host, v->d[local_block], v->n * dtype_size(v->p->dtype), hipMemcpyDeviceToHost, blk.s));
-    SMH_HIP(hipStreamSynchronize(blk.s));
+    if (v->n) SMH_HIP(hipMemcpyAsync(host, v->d[local_block].get(), v->n * dtype_size(v->p->dtype), hipMemcpyDeviceToHost, blk.q.s.get()));
+    SMH_HIP(hipStreamSynchronize(blk.q.s.get()));
     return SMH_OK;
 }
 
 int smh_par_vec_ptr(const smh_par_vec *v, size_t local_block, void **dev_ptr_out) {
     if (!v || !dev_ptr_out || local_block >= v->d.size()) return fail(SMH_ERR_INVALID, "bad argument");
-    *dev_ptr_out = v->d[local_block];
+    *dev_ptr_out = v->d[local_block].get();
     return SMH_OK;
 }
 
@@ -1340,7 +1298,7 @@ int smh_par_spmv_dev(smh_par *p, const smh_par_vec *x, smh_par_vec *y, int varia
         SMH_TRY(par_for(p, [&](size_t k) -> int {
             ParBlock &blk = p->b[k];
             SMH_TRY(use(blk));
-            return smh_crs_spmv_dev(blk.m, x->d[k], x->n, (char *)y->d[k] + blk.r0 * vs, variant, blk.s);  // results at b R (:64)
+            return smh_crs_spmv_dev(blk.m, x->d[k].get(), x->n, (char *)y->d[k].get() + blk.r0 * vs, variant, blk.q.s.get());  // results at b R (:64)
         }));
         return exchange(p, y, mode);
     }
@@ -1356,19 +1314,19 @@ int smh_par_spmv_dev(smh_par *p, const smh_par_vec *x, smh_par_vec *y, int varia
         ParBlock &blk = p->b[k];
         if (ie[k] <= ia[k]) return SMH_OK;
         SMH_TRY(use(blk));
-        return spmv_enqueue_rows(blk.m, x->d[k], x->n, (char *)y->d[k] + blk.r0 * vs, variant, blk.s, ia[k], ie[k]);
+        return spmv_enqueue_rows(blk.m, x->d[k].get(), x->n, (char *)y->d[k].get() + blk.r0 * vs, variant, blk.q.s.get(), ia[k], ie[k]);
     };
     SMH_TRY(par_for(p, [&](size_t k) -> int {
         ParBlock &blk = p->b[k];
         SMH_TRY(use(blk));
         SMH_TRY(interior_for(blk, variant, &ia[k], &ie[k]));
-        char *yk = (char *)y->d[k] + blk.r0 * vs;
+        char *yk = (char *)y->d[k].get() + blk.r0 * vs;
         if (ie[k] > ia[k]) {
             SMH_TRY(fork_one(blk));  // (the side stream after everything the main one holds: x is written, y's readers are through)
-            SMH_TRY(spmv_enqueue_rows_short(blk.m, x->d[k], x->n, yk, variant, blk.sx, 0, ia[k]));
-            SMH_TRY(spmv_enqueue_rows_short(blk.m, x->d[k], x->n, yk, variant, blk.sx, ie[k], blk.r1 - blk.r0));
+            SMH_TRY(spmv_enqueue_rows_short(blk.m, x->d[k].get(), x->n, yk, variant, blk.q.sx.get(), 0, ia[k]));
+            SMH_TRY(spmv_enqueue_rows_short(blk.m, x->d[k].get(), x->n, yk, variant, blk.q.sx.get(), ie[k], blk.r1 - blk.r0));
         } else {
-            SMH_TRY(smh_crs_spmv_dev(blk.m, x->d[k], x->n, yk, variant, blk.s));
+            SMH_TRY(smh_crs_spmv_dev(blk.m, x->d[k].get(), x->n, yk, variant, blk.q.s.get()));
             SMH_TRY(fork_one(blk));
         }
         return peer ? peer_mark(p, k, true) : SMH_OK;
@@ -1438,20 +1396,23 @@ int smh_par_spmv(smh_par *p, const void *x_host, size_t x_len, void *y_host, int
     auto go = [&]() -> int {
         for (ParBlock &blk : p->b) {
             SMH_TRY(use(blk));
-            if (!blk.d_x) {
-                SMH_HIP(hipMalloc(&blk.d_x, (p->n_cols ? p->n_cols : 1) * vs));
-                SMH_HIP(hipMalloc(&blk.d_y, (blk.r1 > blk.r0 ? blk.r1 - blk.r0 : 1) * vs));
+            if (!blk.io.built) {
+                HostStaging st;  // (both arrays or neither)
+                SMH_TRY(st.x.alloc((p->n_cols ? p->n_cols : 1) * vs));
+                SMH_TRY(st.y.alloc((blk.r1 > blk.r0 ? blk.r1 - blk.r0 : 1) * vs));
+                st.built = true;
+                blk.io = std::move(st);
             }
             if (p->needs[blk.index]) {
                 const uint32_t lo = p->lo[blk.index], hi = p->hi[blk.index];
                 if ((size_t)hi >= x_len)  // rhs.get(j): densevec.rs:41
                     return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", x_len, hi);
-                SMH_HIP(hipMemcpyAsync((char *)blk.d_x + (size_t)lo * vs, (const char *)x_host + (size_t)lo * vs, ((size_t)hi - lo + 1) * vs,
-                                       hipMemcpyHostToDevice, blk.s));
+                SMH_HIP(hipMemcpyAsync((char *)blk.io.x.get() + (size_t)lo * vs, (const char *)x_host + (size_t)lo * vs, ((size_t)hi - lo + 1) * vs,
+                                       hipMemcpyHostToDevice, blk.q.s.get()));
             }
-            SMH_TRY(smh_crs_spmv_dev(blk.m, blk.d_x, x_len < p->n_cols ? x_len : p->n_cols, blk.d_y, variant, blk.s));
+            SMH_TRY(smh_crs_spmv_dev(blk.m, blk.io.x.get(), x_len < p->n_cols ? x_len : p->n_cols, blk.io.y.get(), variant, blk.q.s.get()));
             if (blk.r1 > blk.r0)
-                SMH_HIP(hipMemcpyAsync((char *)y_host + blk.r0 * vs, blk.d_y, (blk.r1 - blk.r0) * vs, hipMemcpyDeviceToHost, blk.s));
+                SMH_HIP(hipMemcpyAsync((char *)y_host + blk.r0 * vs, blk.io.y.get(), (blk.r1 - blk.r0) * vs, hipMemcpyDeviceToHost, blk.q.s.get()));
         }
         return sync_all(p);
     };
@@ -1488,16 +1449,16 @@ int smh_par_cg_solve_vec(smh_par *p, const smh_par_vec *b, smh_par_vec *x, doubl
             ParBlock &blk = p->b[k];
             SMH_TRY(use(blk));
             const size_t n_loc = blk.r1 - blk.r0;
-            SMH_TRY(smh_crs_spmv_dev(blk.m, x->d[k], n, blk.d_r, variant, blk.s));
-            SMH_TRY(launch_ew(dt, Ew::RSubInto, blk.d_r, (const char *)b->d[k] + blk.r0 * vs, n_loc, 0.0, nullptr, blk.s));
-            SMH_HIP(hipMemcpyAsync((char *)pv->d[k] + blk.r0 * vs, blk.d_r, n_loc * vs, hipMemcpyDeviceToDevice, blk.s));
-            SMH_TRY(cg_par_init(dt, blk.d_sc, tol, iter_max, blk.s));
-            SMH_TRY(launch_dot(dt, blk.d_r, blk.d_r, n_loc, blk.d_partials, red_mine(p, blk, 1), blk.s));
+            SMH_TRY(smh_crs_spmv_dev(blk.m, x->d[k].get(), n, blk.cg.r.get(), variant, blk.q.s.get()));
+            SMH_TRY(launch_ew(dt, Ew::RSubInto, blk.cg.r.get(), (const char *)b->d[k].get() + blk.r0 * vs, n_loc, 0.0, nullptr, blk.q.s.get()));
+            SMH_HIP(hipMemcpyAsync((char *)pv->d[k].get() + blk.r0 * vs, blk.cg.r.get(), n_loc * vs, hipMemcpyDeviceToDevice, blk.q.s.get()));
+            SMH_TRY(cg_par_init(dt, blk.cg.sc.get(), tol, iter_max, blk.q.s.get()));
+            SMH_TRY(launch_dot(dt, blk.cg.r.get(), blk.cg.r.get(), n_loc, blk.cg.partials.get(), red_mine(p, blk, 1), blk.q.s.get()));
         }
         SMH_TRY(combine(p, 1));
         for (ParBlock &blk : p->b) {
             SMH_TRY(use(blk));
-            SMH_TRY(cg_par_set_rr(dt, blk.d_sc, red_all(p, blk, 1), nb, blk.s));
+            SMH_TRY(cg_par_set_rr(dt, blk.cg.sc.get(), red_all(p, blk, 1), nb, blk.q.s.get()));
         }
         // ---- one iteration (:41-60) as phases: within a phase every block's calls are issued by its own host thread (par_for);
         // between phases all of them have been issued -- what a wait on another block's event needs.  Streams, events, kernels and
@@ -1519,38 +1480,38 @@ int smh_par_cg_solve_vec(smh_par *p, const smh_par_vec *b, smh_par_vec *x, doubl
             // :43 and :45 -- with the CSR-stream kernel p.Ap rides the product's epilogue (one partial per tile, lhs = this
             // block's slice of p) as in the single-matrix solver: no second pass over p and Ap
             const size_t n_dot = spmv_fused_dot_partials(blk.m, n, variant, true);
-            const bool fused = n_dot && n_dot <= blk.dotp_cap;
-            void *dotp = fused ? blk.d_dotp : nullptr;
-            const void *lhs = fused ? (const char *)pv->d[k] + blk.r0 * vs : nullptr;
-            if (part == 0) return spmv_enqueue_rows(blk.m, pv->d[k], n, blk.d_ap, variant, blk.s, ia, ie, dotp, lhs);
+            const bool fused = n_dot && n_dot <= blk.cg.dotp_cap;
+            void *dotp = fused ? blk.cg.dotp.get() : nullptr;
+            const void *lhs = fused ? (const char *)pv->d[k].get() + blk.r0 * vs : nullptr;
+            if (part == 0) return spmv_enqueue_rows(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.s.get(), ia, ie, dotp, lhs);
             if (part == 1 && split) {
                 if (!dotp) {
-                    SMH_TRY(spmv_enqueue_rows_short(blk.m, pv->d[k], n, blk.d_ap, variant, blk.sx, 0, ia));
-                    return spmv_enqueue_rows_short(blk.m, pv->d[k], n, blk.d_ap, variant, blk.sx, ie, n_loc);
+                    SMH_TRY(spmv_enqueue_rows_short(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.sx.get(), 0, ia));
+                    return spmv_enqueue_rows_short(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.sx.get(), ie, n_loc);
                 }
-                SMH_TRY(spmv_enqueue_rows(blk.m, pv->d[k], n, blk.d_ap, variant, blk.sx, 0, ia, dotp, lhs));
-                return spmv_enqueue_rows(blk.m, pv->d[k], n, blk.d_ap, variant, blk.sx, ie, n_loc, dotp, lhs);
+                SMH_TRY(spmv_enqueue_rows(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.sx.get(), 0, ia, dotp, lhs));
+                return spmv_enqueue_rows(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.sx.get(), ie, n_loc, dotp, lhs);
             }
             if (part == 1) return SMH_OK;  // (unsplit: everything in part 2, after the exchange has been joined)
             if (!split) {
-                if (fused) SMH_TRY(spmv_enqueue(blk.m, pv->d[k], n, blk.d_ap, variant, blk.s, blk.d_dotp, lhs));
-                else SMH_TRY(smh_crs_spmv_dev(blk.m, pv->d[k], n, blk.d_ap, variant, blk.s));
+                if (fused) SMH_TRY(spmv_enqueue(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.s.get(), blk.cg.dotp.get(), lhs));
+                else SMH_TRY(smh_crs_spmv_dev(blk.m, pv->d[k].get(), n, blk.cg.ap.get(), variant, blk.q.s.get()));
             }
-            if (fused) return launch_fold2(dt, blk.d_dotp, n_dot, blk.d_partials, red_mine(p, blk, 0), blk.s);
-            return launch_dot(dt, (const char *)pv->d[k] + blk.r0 * vs, blk.d_ap, n_loc, blk.d_partials, red_mine(p, blk, 0), blk.s);
+            if (fused) return launch_fold2(dt, blk.cg.dotp.get(), n_dot, blk.cg.partials.get(), red_mine(p, blk, 0), blk.q.s.get());
+            return launch_dot(dt, (const char *)pv->d[k].get() + blk.r0 * vs, blk.cg.ap.get(), n_loc, blk.cg.partials.get(), red_mine(p, blk, 0), blk.q.s.get());
         };
         auto update_xr = [&](size_t k) -> int {  // alpha, then x / r and this block's share of r.r
             ParBlock &blk = p->b[k];
             SMH_TRY(use(blk));
             uint32_t cnt = 0;
-            SMH_TRY(cg_par_update(dt, blk.d_sc, blk.d_sc2, red_all(p, blk, 0), nb, blk.d_r, blk.d_ap, blk.r1 - blk.r0, blk.d_partials, &cnt, blk.s));  // :45, :49-51
-            return cg_fold(dt, blk.d_partials, cnt, red_mine(p, blk, 1), blk.s);
+            SMH_TRY(cg_par_update(dt, blk.cg.sc.get(), blk.cg.sc2.get(), red_all(p, blk, 0), nb, blk.cg.r.get(), blk.cg.ap.get(), blk.r1 - blk.r0, blk.cg.partials.get(), &cnt, blk.q.s.get()));  // :45, :49-51
+            return cg_fold(dt, blk.cg.partials.get(), cnt, red_mine(p, blk, 1), blk.q.s.get());
         };
         auto update_p = [&](size_t k) -> int {  // beta (and the stop test before it), then p
             ParBlock &blk = p->b[k];
             SMH_TRY(use(blk));
-            return cg_par_p(dt, blk.d_sc2, blk.d_sc, red_all(p, blk, 1), nb, (char *)pv->d[k] + blk.r0 * vs, blk.d_r, (char *)x->d[k] + blk.r0 * vs,
-                            blk.r1 - blk.r0, blk.s);  // :52-56, :47, :58-59
+            return cg_par_p(dt, blk.cg.sc2.get(), blk.cg.sc.get(), red_all(p, blk, 1), nb, (char *)pv->d[k].get() + blk.r0 * vs, blk.cg.r.get(), (char *)x->d[k].get() + blk.r0 * vs,
+                            blk.r1 - blk.r0, blk.q.s.get());  // :52-56, :47, :58-59
         };
         auto iteration = [&]() -> int {
             // the entries of p a block references and another owns -- beside the product of the interior rows, which need none
@@ -1606,12 +1567,12 @@ int smh_par_cg_solve_vec(smh_par *p, const smh_par_vec *b, smh_par_vec *x, doubl
         auto poll = [&]() -> int {
             ParBlock &b0 = p->b[0];
             SMH_TRY(use(b0));
-            SMH_HIP(hipMemcpyAsync(p->h_sc, b0.d_sc, cg_scalars_bytes(dt), hipMemcpyDeviceToHost, b0.s));
+            SMH_HIP(hipMemcpyAsync(p->h_sc.get(), b0.cg.sc.get(), cg_scalars_bytes(dt), hipMemcpyDeviceToHost, b0.q.s.get()));
             // (block 0's stream alone: its scalars are every block's scalars -- all fold the same values -- and the other blocks'
             // streams keep their queues full across the poll; everything is drained once, when the solve returns)
-            SMH_HIP(hipStreamSynchronize(b0.s));
+            SMH_HIP(hipStreamSynchronize(b0.q.s.get()));
             uint64_t it64 = 0;
-            cg_read_scalars(dt, p->h_sc, &converged, &it64, &rr);
+            cg_read_scalars(dt, p->h_sc.get(), &converged, &it64, &rr);
             iters = (size_t)it64;
             return SMH_OK;
         };

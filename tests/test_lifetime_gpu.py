@@ -1,8 +1,9 @@
 """Handle lifetime: every lazily built workspace (merge table, ring plans incl. the wide and the banded ring, 16-bit
 column arrays, K1s windows and codes, K2c / K2f / K2s / K2t copies, assembly scratch) is released with its handle -- also
 after it was dropped and built again inside the handle's life (sort_rows, update_values, scale, another block width) -- and so is every
-array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay) -- device
-memory in use returns to where it started after many create / use / destroy rounds."""
+array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay), and every
+block, stream, vector and solver workspace of a partitioned matrix (SparseMatParLocal, ParVec) -- device memory in use returns to
+where it started after many create / use / destroy rounds."""
 import gc
 import os
 
@@ -140,10 +141,83 @@ def _exercise_matrix_ops(rng):
     del a, b, t, t2, p, c, s, first, d, e, i, r
 
 
+PAR_GRID = 84   # 592 704 rows in two blocks: a block's full-length vectors AND its per-block arrays (r, Ap: ~296 k entries) are
+PAR_ITERS = 5   # pooled blocks (1 MiB and more) in f32 already, so the exact comparison of live bytes sees them
+_stencils = {}
+
+
+def _stencil(dtype):
+    if dtype not in _stencils:
+        _stencils[dtype] = oracle.laplace3d(PAR_GRID, PAR_GRID, PAR_GRID, dtype)
+    return _stencils[dtype]
+
+
+def _exercise_par(rng, dtype):
+    """Two blocks on one device, cut by rows, by entries, and adopted from existing blocks; the host-vector product, the
+    device-resident one with both exchanges (overlap and issuing threads on and off), user vectors, both solvers.  Returns
+    what the oracle is asked about after the last round."""
+    off, col, val = _stencil(dtype)
+    n = PAR_GRID ** 3
+    x = rng.uniform(-1, 1, n).astype(dtype)
+    b = rng.uniform(-1, 1, n).astype(dtype)
+    by_rows = sm.SparseMatParLocal.with_sub_matrices(2, n, n, off, col, val, device_ids=[0, 0])
+    by_nnz = sm.SparseMatParLocal.with_sub_matrices(2, n, n, off, col, val, device_ids=[0, 0], split="nnz")
+    cut = by_nnz.split()
+    blocks = []
+    for k in range(2):
+        o = off[cut[k]:cut[k + 1] + 1].astype(np.int64)
+        blocks.append(sm.SparseMatCRS.from_raw_parts(cut[k + 1] - cut[k], n, (o - o[0]).astype(np.uint32), col[o[0]:o[-1]], val[o[0]:o[-1]]))
+    adopted = sm.SparseMatParLocal.adopt(blocks, n, split_rows=cut)
+    out = {"x": x, "b": b, "mvp": by_rows.mvp(x, variant="stream"), "mvp_dev": []}
+    xv, yv = by_nnz.vec(host=x), by_nnz.vec()
+    for exchange in ("allgather", "window"):
+        for overlap in (True, False):
+            for threads in (1, 0):
+                by_nnz.set_overlap(overlap)
+                by_nnz.set_threads(threads)
+                by_nnz.mvp_dev(xv, yv, variant="stream", exchange=exchange)
+                out["mvp_dev"].append(yv.download())
+    xv.close()
+    yv.close()
+    out["cg"] = np.zeros(n, dtype)
+    by_rows.cg_solve(b, out["cg"], tol=0.0, iter_max=PAR_ITERS)
+    bv, sv = adopted.vec(host=b), adopted.vec()
+    adopted.cg_solve_vec(bv, sv, tol=0.0, iter_max=PAR_ITERS, check_every=2)
+    out["cg_vec"] = sv.download()
+    bv.close()
+    sv.close()
+    for m in (by_rows, by_nnz, adopted):
+        m.close()
+    del blocks
+    return out
+
+
+def _check_par(dtype, out):
+    """The last round's products and iterates against the oracle: the round did what it says."""
+    off, col, val = _stencil(dtype)
+    n = PAR_GRID ** 3
+    assert_spmv_close(out["mvp"], off, col, val, out["x"], "partitioned mvp, %s" % np.dtype(dtype).name)
+    assert_spmv_close(out["mvp_dev"][0], off, col, val, out["x"], "partitioned mvp_dev, %s" % np.dtype(dtype).name)
+    for y in out["mvp_dev"][1:]:  # (tests/test_par_overlap_gpu.py: the exchange, the overlap and the threads do not touch a bit)
+        assert y.tobytes() == out["mvp_dev"][0].tobytes()
+    # PAR_ITERS iterations from x = 0 on both sides.  The two differ in the order of their sums only: the oracle's dot products
+    # are serial, the device's are trees over blocks.  A sum of n terms carries a relative rounding error of about sqrt(n) eps
+    # (the errors of its additions accumulate as a random walk); each iteration feeds two such sums (p.Ap, r.r) into alpha and
+    # beta, and x inherits their errors linearly.  A factor 8 on top for the products' and the vector updates' own rounding.
+    want, iters, _ = oracle.cg(n, n, off, col, val, out["b"], np.zeros(n, dtype), tol=0.0, iter_max=PAR_ITERS)
+    assert iters == PAR_ITERS
+    bound = 8 * PAR_ITERS * 2 * np.sqrt(n) * np.finfo(dtype).eps * np.abs(want).max()
+    for name in ("cg", "cg_vec"):
+        err = np.abs(out[name].astype(np.float64) - want.astype(np.float64)).max()
+        print("partitioned %s, %s: max |x - x_oracle| = %.3e (bound %.3e)" % (name, np.dtype(dtype).name, err, bound))
+        assert err <= bound, (name, err, bound)
+
+
 def _round(rng):
     for kind in range(3):
         _exercise(rng, kind)
     _exercise_matrix_ops(rng)
+    return {dtype: _exercise_par(rng, dtype) for dtype in (np.float32, np.float64)}
 
 
 def test_no_device_memory_is_left_behind(gpu):
@@ -154,8 +228,10 @@ def test_no_device_memory_is_left_behind(gpu):
     # readings are taken with the pool returned to the runtime, and the bytes the library has handed out are compared exactly
     before, live_before = _used_without_the_pool()
     for rep in range(8):
-        _round(rng)
+        last = _round(rng)
     gc.collect()
     after, live_after = _used_without_the_pool()
     assert live_after == live_before, "the library still holds %d bytes more than before" % (live_after - live_before)
     assert after - before < 8 << 20, "device memory in use grew by %.1f MiB over 8 create/use/destroy rounds" % ((after - before) / 2 ** 20)
+    for dtype, out in last.items():
+        _check_par(dtype, out)
