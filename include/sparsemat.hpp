@@ -100,6 +100,43 @@ class DenseVec {
     smh_vec *h_ = nullptr;
 };
 
+template <typename T> class SparseMatCRS;
+
+// A reusable update plan (smh_update_plan): the targets and the sorted order of one (rows, cols, ops) stream on one SparseMatCRS,
+// made by SparseMatCRS::update_plan.  execute(values) leaves what apply(rows, cols, values, ops) leaves, bit for bit, in one
+// gather-and-fold pass; from_zero folds every targeted entry from +0 ("zero, then assemble").  Move-only; a moved-from plan is
+// inert (execute does nothing).  The matrix must outlive every execute, not the plan.
+template <typename T>
+class UpdatePlan {
+  public:
+    UpdatePlan(UpdatePlan &&o) noexcept : p_(o.p_), m_(o.m_), n_(o.n_) { o.p_ = nullptr; o.m_ = nullptr; o.n_ = 0; }
+    UpdatePlan &operator=(UpdatePlan &&o) noexcept { std::swap(p_, o.p_); std::swap(m_, o.m_); std::swap(n_, o.n_); return *this; }
+    UpdatePlan(const UpdatePlan &) = delete;
+    ~UpdatePlan() { smh_update_plan_destroy(p_); }
+
+    void execute(const std::vector<T> &values, bool from_zero = false) {
+        if (!p_) return;
+        if (values.size() != n_) throw Panic(SMH_ERR_INVALID, "values and the plan's stream differ in length");
+        detail::check(smh_update_plan_execute(p_, m_, values.data(), from_zero ? 1 : 0));
+    }
+    size_t n_ops() const { return n_; }
+    size_t n_targets() const { return stat(1); }
+    size_t n_live_ops() const { return stat(2); }
+    smh_update_plan *handle() const { return p_; }
+
+  private:
+    friend class SparseMatCRS<T>;
+    UpdatePlan() = default;
+    size_t stat(int which) const {
+        size_t v[3] = {0, 0, 0};
+        if (p_) detail::check(smh_update_plan_stats(p_, &v[0], &v[1], &v[2], nullptr, nullptr, nullptr));
+        return v[which];
+    }
+    smh_update_plan *p_ = nullptr;
+    smh_crs *m_ = nullptr;
+    size_t n_ = 0;
+};
+
 template <typename T>
 class SparseMatCRS {
   public:
@@ -220,6 +257,17 @@ class SparseMatCRS {
         if (rows.size() != vals.size() || cols.size() != vals.size() || (!ops.empty() && ops.size() != vals.size()))
             throw Panic(SMH_ERR_INVALID, "rows, cols, values and ops differ in length");
         detail::check(smh_crs_apply(h_, vals.size(), rows.data(), cols.data(), vals.data(), ops.empty() ? nullptr : ops.data()));
+    }
+    // a reusable plan for re-assembling this matrix from the stream (rows, cols, ops) with new values: every operation must
+    // land on an existing entry (apply the stream once to create them, then plan); stale once the structure changes
+    UpdatePlan<T> update_plan(const std::vector<uint32_t> &rows, const std::vector<uint32_t> &cols, const std::vector<uint8_t> &ops = {}) {
+        if (rows.size() != cols.size() || (!ops.empty() && ops.size() != rows.size()))
+            throw Panic(SMH_ERR_INVALID, "rows, cols and ops differ in length");
+        UpdatePlan<T> p;
+        detail::check(smh_update_plan_create(h_, rows.size(), rows.data(), cols.data(), ops.empty() ? nullptr : ops.data(), &p.p_));
+        p.m_ = h_;
+        p.n_ = rows.size();
+        return p;
     }
     // SparseMatCRS::new() (sparsemat_crs.rs:47-49) and SparseMatrix::eye (sparsematrix.rs:91-98)
     static SparseMatCRS new_empty() {

@@ -39,7 +39,9 @@ extern "C" {
  * smh_crs_set_stream_windows and smh_crs_stream_windows (K1s's column windows are chosen by the inspector alone; the K1s-w kernel
  * they steered left the library); ADDED: smh_crs_tiled_products, smh_crs_prepare_stats,
  * smh_comm_ranks_seen, smh_rccl_version, smh_par_set_threads,
- * smh_crs_stream_value_dict, smh_crs_set_stream_value_dict.  A caller checks smh_abi_version() ==
+ * smh_crs_stream_value_dict, smh_crs_set_stream_value_dict; ADDED later without a version change (additions only):
+ * smh_update_plan_create, smh_update_plan_create_dev, smh_update_plan_execute, smh_update_plan_execute_dev,
+ * smh_update_plan_stats, smh_update_plan_destroy.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -244,6 +246,44 @@ int smh_crs_apply_dev(smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const 
  * without rows).  Same bits on every route.  SMH_APPLY_FAST=0 (environment) sends every handle with rows to the general
  * route. */
 int smh_last_apply_route(void);
+/* A reusable update plan: re-assembly on a FIXED pattern (csrc/matplan.hip).  smh_crs_apply on a stream whose operations all
+ * land on existing entries looks every target up, sorts the stream by target and folds -- and only the fold depends on the
+ * values.  A plan keeps the targets and the sorted order of one (rows, cols, ops) stream; executing it with n_ops new values
+ * is one gather-and-fold pass.
+ * Create: ops as for smh_crs_apply (NULL or ops[k] == 0: add_to, else set); _dev: device arrays under smh_crs_apply_dev's
+ * rules.  EVERY operation must land on an existing entry of m (the first match in its row, as find_index picks it);
+ * otherwise SMH_ERR_INVALID, the message giving the number of operations without one, m untouched, *out NULL.  To plan a
+ * stream that first has to create entries: call smh_crs_apply once -- its general route creates them -- and make the plan
+ * on the resulting handle.  A handle without rows: SMH_ERR_INVALID.  n_ops == 0: a valid plan whose execute does nothing.
+ * n_ops >= u32::MAX: SMH_ERR_CAPACITY.  NULL arrays with n_ops > 0: SMH_ERR_INVALID.
+ * Execute: `values` holds n_ops values of the handle's dtype in stream order (host array: uploaded through a staging buffer
+ * the plan keeps; _dev: under smh_crs_apply_dev's rules); both forms have finished when they return.  With from_zero == 0, m
+ * is afterwards what smh_crs_apply(m, n_ops, rows, cols, values, ops) leaves, bit for bit: every target the left fold of its
+ * operations in stream order from the stored value (add_to: acc + v, one rounding; set: v).  With from_zero != 0 the fold
+ * of every TARGETED entry starts from +0 instead -- the stream `set(r, c, +0)` for every distinct (row, column), then the
+ * stream itself: "zero, then assemble" without a second pass; entries the stream never targets are not touched.  Operations
+ * in front of their target's last `set` cannot reach the result and are dropped when the plan is made (n_live_ops counts the
+ * rest).  Execute allocates nothing on the device and sorts nothing.  The handle is treated as apply's values-only route
+ * treats it (smh_crs_update_values(m, NULL): structure-derived forms stay, value-derived ones are refreshed or dropped); a
+ * borrowed value array is written in place and stays borrowed.  Not under a stream capture.
+ * Binding: a plan belongs to one handle in one structure.  Executing it on another handle (a clone included), or after the
+ * handle's offsets, columns or storage order changed (smh_crs_sort_rows; an apply / add_assign / sub_assign that rebuilt the
+ * handle), is SMH_ERR_INVALID and writes nothing; smh_crs_scale, smh_crs_update_values, values-only apply / add_assign and
+ * other plans' executes leave it valid.  m may be destroyed first: the plan can then only be destroyed.  A plan and its
+ * handle follow the threading rule of a handle.
+ * Stats (any out may be NULL): operations of the stream, distinct targets, kept operations, most operations on one target
+ * (dropped ones included), the number of kept operations above which a run is folded by a workgroup of its own instead of
+ * one thread, and the bytes of device memory the plan holds. */
+typedef struct smh_update_plan smh_update_plan;
+int smh_update_plan_create(const smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const uint8_t *ops,
+                           smh_update_plan **out);
+int smh_update_plan_create_dev(const smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev,
+                               const uint8_t *ops_dev, smh_update_plan **out);
+int smh_update_plan_execute(smh_update_plan *p, smh_crs *m, const void *values, int from_zero);
+int smh_update_plan_execute_dev(smh_update_plan *p, smh_crs *m, const void *values_dev, int from_zero);
+int smh_update_plan_stats(const smh_update_plan *p, size_t *n_ops, size_t *n_targets, size_t *n_live_ops, size_t *longest_run,
+                          size_t *long_run_threshold, size_t *device_bytes);
+int smh_update_plan_destroy(smh_update_plan *p);
 /* SparseMatrix::eye (sparsematrix.rs:91-98) on a SparseMatCRS, i.e. set(i, i, 1) for i < dim: dim 0 the empty matrix; dim 1
  * no rows, one orphan, n_cols 1 (the first-push quirk; the operation is kept as for a one-operation replay); dim >= 2 the
  * identity (built directly, without a sort). */

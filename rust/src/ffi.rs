@@ -4,6 +4,7 @@ use std::os::raw::{c_char, c_double, c_int, c_void};
 
 #[repr(C)] pub struct smh_crs { _private: [u8; 0] }
 #[repr(C)] pub struct smh_vec { _private: [u8; 0] }
+#[repr(C)] pub struct smh_update_plan { _private: [u8; 0] }
 #[repr(C)] pub struct smh_par { _private: [u8; 0] }
 #[repr(C)] pub struct smh_par_vec { _private: [u8; 0] }
 #[repr(C)] pub struct smh_comm { _private: [u8; 0] }
@@ -74,6 +75,17 @@ extern "C" {
     pub fn smh_crs_apply_dev(m: *mut smh_crs, n_ops: usize, rows_dev: *const u32, cols_dev: *const u32,
                              values_dev: *const c_void, ops_dev: *const u8) -> c_int;
     pub fn smh_last_apply_route() -> c_int;  // 0 general, 1 values only, 2 replay: diagnostics only
+    // a reusable update plan: re-assembly on a fixed pattern as one gather-and-fold pass (every operation must land on an
+    // existing entry; bound to one handle in one structure; from_zero != 0 folds every targeted entry from +0)
+    pub fn smh_update_plan_create(m: *const smh_crs, n_ops: usize, rows: *const u32, cols: *const u32, ops: *const u8,
+                                  out: *mut *mut smh_update_plan) -> c_int;
+    pub fn smh_update_plan_create_dev(m: *const smh_crs, n_ops: usize, rows_dev: *const u32, cols_dev: *const u32,
+                                      ops_dev: *const u8, out: *mut *mut smh_update_plan) -> c_int;
+    pub fn smh_update_plan_execute(p: *mut smh_update_plan, m: *mut smh_crs, values: *const c_void, from_zero: c_int) -> c_int;
+    pub fn smh_update_plan_execute_dev(p: *mut smh_update_plan, m: *mut smh_crs, values_dev: *const c_void, from_zero: c_int) -> c_int;
+    pub fn smh_update_plan_stats(p: *const smh_update_plan, n_ops: *mut usize, n_targets: *mut usize, n_live_ops: *mut usize,
+                                 longest_run: *mut usize, long_run_threshold: *mut usize, device_bytes: *mut usize) -> c_int;
+    pub fn smh_update_plan_destroy(p: *mut smh_update_plan) -> c_int;
     pub fn smh_crs_eye(dtype: c_int, dim: usize, out: *mut *mut smh_crs) -> c_int;
     pub fn smh_crs_is_symmetric(m: *const smh_crs, out: *mut c_int) -> c_int;
     pub fn smh_crs_is_sorted(m: *const smh_crs, out: *mut c_int) -> c_int;

@@ -259,6 +259,50 @@ impl DeviceCrs {
     }
 }
 
+/// A reusable update plan (`smh_update_plan`): the targets and the sorted order of one (rows, cols, ops) stream on one
+/// `DeviceCrs`.  `execute` leaves what `apply(rows, cols, values, ops)` leaves, bit for bit, in one gather-and-fold pass; it is
+/// refused (panic with the library's message) on another matrix or after the matrix's structure changed.
+pub struct DeviceUpdatePlan {
+    handle: *mut ffi::smh_update_plan,
+    n_ops: usize,
+}
+
+impl DeviceCrs {
+    /// Every operation must land on an existing entry: `apply` the stream once to create them, then plan.  An empty `ops`
+    /// means all `add_to`.
+    pub fn update_plan(&self, rows: &[u32], cols: &[u32], ops: &[u8]) -> DeviceUpdatePlan {
+        assert!(rows.len() == cols.len() && (ops.is_empty() || ops.len() == rows.len()));
+        let mut handle = std::ptr::null_mut();
+        check(unsafe {
+            ffi::smh_update_plan_create(self.handle, rows.len(), rows.as_ptr(), cols.as_ptr(),
+                                        if ops.is_empty() { std::ptr::null() } else { ops.as_ptr() }, &mut handle)
+        });
+        DeviceUpdatePlan { handle, n_ops: rows.len() }
+    }
+}
+
+impl DeviceUpdatePlan {
+    /// `from_zero`: every targeted entry is folded from +0 instead of its stored value ("zero, then assemble" in one pass).
+    pub fn execute<T: HipValue>(&mut self, m: &mut DeviceCrs, values: &[T], from_zero: bool) {
+        assert_eq!(values.len(), self.n_ops);
+        m.assert_dtype::<T>();
+        check(unsafe { ffi::smh_update_plan_execute(self.handle, m.handle, values.as_ptr() as *const c_void, from_zero as c_int) });
+    }
+    /// Operations the plan kept: those at or after their target's last `set`.
+    pub fn n_live_ops(&self) -> usize {
+        let mut n = 0usize;
+        let null = std::ptr::null_mut();
+        check(unsafe { ffi::smh_update_plan_stats(self.handle, null, null, &mut n, null, null, null) });
+        n
+    }
+}
+
+impl Drop for DeviceUpdatePlan {
+    fn drop(&mut self) {
+        unsafe { ffi::smh_update_plan_destroy(self.handle) };
+    }
+}
+
 // the operators of sparsemat_ops! (src/sparsematrix.rs:370-419); `+` / `-` work on a clone of self inside the library
 impl std::ops::AddAssign for DeviceCrs {
     fn add_assign(&mut self, rhs: Self) { self.add(&rhs); }

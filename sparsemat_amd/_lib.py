@@ -59,6 +59,12 @@ SIGNATURES = {
     "smh_crs_apply": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_crs_apply_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_last_apply_route": (_int, []),
+    "smh_update_plan_create": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "smh_update_plan_create_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "smh_update_plan_execute": (_int, [_vp, _vp, _vp, _int]),
+    "smh_update_plan_execute_dev": (_int, [_vp, _vp, _vp, _int]),
+    "smh_update_plan_stats": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "smh_update_plan_destroy": (_int, [_vp]),
     "smh_crs_eye": (_int, [_int, _sz, C.POINTER(_vp)]),
     "smh_crs_is_symmetric": (_int, [_vp, C.POINTER(_int)]),
     "smh_crs_is_sorted": (_int, [_vp, C.POINTER(_int)]),

@@ -3,6 +3,7 @@
 // Host-side logic only: argument checks with the reference's panic conditions, HBM residency of
 // the CRS arrays, kernel-variant selection, the CG driver loop.  No CPU compute path exists here:
 // every entry point that computes needs a HIP device.
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -47,6 +48,11 @@ int require_device() {
         return fail(SMH_ERR_NO_DEVICE, "no HIP device visible: libsparsemat_hip has no CPU fallback");
     }
     return SMH_OK;
+}
+
+uint64_t next_crs_id() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1, std::memory_order_relaxed);
 }
 
 int current_device() {
@@ -1275,8 +1281,11 @@ int smh_last_add_route(void) { return g_add_route; }
 // in place: `a` takes the fresh handle's state, and every form derived from the old one (merge tiles, K1s codes and value
 // dictionary, K1r plan, K2c / K2f / K2s / K2t copies, statistics) goes with the old state.  keep_arrays: the fresh handle
 // works on the old handle's arrays (values updated where they are), so the old state must not free them.
+// The swap takes whole structs: `a` stays the handle it was (its id), in a new structure epoch unless only the values changed.
 static void replace_state(smh_crs *a, smh_crs *fresh, bool keep_arrays) {
     std::swap(*a, *fresh);
+    a->id = fresh->id;
+    a->epoch = fresh->epoch + (keep_arrays ? 0 : 1);
     if (keep_arrays) fresh->owns = false;
     (void)smh_crs_destroy(fresh);
 }
@@ -1518,6 +1527,112 @@ int smh_crs_apply_dev(smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const 
     return apply_common(m, n_ops, rows_dev, cols_dev, values_dev, ops_dev, true);
 }
 
+// ---- a reusable update plan: re-assembly on a fixed pattern as one gather-and-fold pass (matplan.hip) ---------------------------
+}  // extern "C"
+struct smh_update_plan {
+    uint64_t crs_id = 0, epoch = 0;  // the handle and the structure it was made for
+    UpdPlan plan;
+    StageBuf stage;  // the host form's upload of the values (lazy, reused)
+};
+extern "C" {
+
+static int plan_create_common(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, const uint8_t *ops, bool on_device,
+                              smh_update_plan **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
+    *out = nullptr;
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols)) return fail(SMH_ERR_INVALID, "NULL operation array");
+    if (n >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    if (m->n_rows == 0) return fail(SMH_ERR_INVALID, "update plan: the handle has no rows, so no operation has an entry to land on");
+    smh_update_plan *p = new (std::nothrow) smh_update_plan();
+    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
+    p->crs_id = m->id; p->epoch = m->epoch;
+    const int rc = [&]() -> int {
+        if (n == 0) return SMH_OK;  // a valid plan whose execute does nothing
+        if (on_device) {
+            SMH_TRY(check_dev_array(rows, m->device, "rows"));
+            SMH_TRY(check_dev_array(cols, m->device, "cols"));
+            SMH_TRY(check_dev_array(ops, m->device, "ops"));
+            SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the arrays come first
+        }
+        SMH_HIP(hipStreamSynchronize(m->stream));
+        Scratch st;  // device copies of host operation arrays; the sorted operations
+        const void *d_rows = rows, *d_cols = cols, *d_ops = ops;
+        if (!on_device) {
+            SMH_TRY(upload(st, rows, n * sizeof(uint32_t), &d_rows));
+            SMH_TRY(upload(st, cols, n * sizeof(uint32_t), &d_cols));
+            SMH_TRY(upload(st, ops, n, &d_ops));
+        }
+        uint32_t *key = nullptr, *src = nullptr;
+        uint64_t n_absent = 0;
+        SMH_TRY(st.alloc(&key, n));
+        SMH_TRY(st.alloc(&src, n));
+        SMH_TRY(crs_plan_targets(upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, key, src, &n_absent, m->stream));
+        if (n_absent)
+            return fail(SMH_ERR_INVALID, "update plan: %llu of %llu operations have no entry to land on (smh_crs_apply creates entries; plan afterwards)",
+                        (unsigned long long)n_absent, (unsigned long long)n);
+        return plan_build(n, key, src, (const uint8_t *)d_ops, &p->plan, m->stream);
+    }();
+    if (rc != SMH_OK) return keep_error(rc, [&] { delete p; });
+    *out = p;
+    return SMH_OK;
+}
+
+int smh_update_plan_create(const smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const uint8_t *ops, smh_update_plan **out) {
+    return plan_create_common(m, n_ops, rows, cols, ops, false, out);
+}
+int smh_update_plan_create_dev(const smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev, const uint8_t *ops_dev,
+                               smh_update_plan **out) {
+    return plan_create_common(m, n_ops, rows_dev, cols_dev, ops_dev, true, out);
+}
+
+static int plan_execute_common(smh_update_plan *p, smh_crs *m, const void *values, int from_zero, bool on_device) {
+    if (!p || !m) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (p->crs_id != m->id) return fail(SMH_ERR_INVALID, "update plan: made for another handle");
+    if (p->epoch != m->epoch) return fail(SMH_ERR_INVALID, "update plan: the handle's structure changed since the plan was made");
+    const size_t n = p->plan.n_ops;
+    if (n && !values) return fail(SMH_ERR_INVALID, "NULL value array");
+    if (n == 0) return SMH_OK;
+    const void *d_vals = values;
+    if (on_device) {
+        SMH_TRY(check_dev_array(values, m->device, "values"));
+        SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the array come first
+    } else {
+        const size_t bytes = n * dtype_size(m->dtype);
+        SMH_TRY(p->stage.ensure_cap(bytes));
+        SMH_HIP(hipMemcpy(p->stage.d.get(), values, bytes, hipMemcpyHostToDevice));
+        d_vals = p->stage.d.get();
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    SMH_TRY(plan_execute(m->dtype, p->plan, d_vals, m->d_val, from_zero != 0, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    return smh_crs_update_values(m, nullptr);  // as apply's values-only route: structure-derived forms stay, value-derived ones follow
+}
+
+int smh_update_plan_execute(smh_update_plan *p, smh_crs *m, const void *values, int from_zero) {
+    return plan_execute_common(p, m, values, from_zero, false);
+}
+int smh_update_plan_execute_dev(smh_update_plan *p, smh_crs *m, const void *values_dev, int from_zero) {
+    return plan_execute_common(p, m, values_dev, from_zero, true);
+}
+
+int smh_update_plan_stats(const smh_update_plan *p, size_t *n_ops, size_t *n_targets, size_t *n_live_ops, size_t *longest_run,
+                          size_t *long_run_threshold, size_t *device_bytes) {
+    if (!p) return fail(SMH_ERR_INVALID, "NULL plan");
+    if (n_ops) *n_ops = p->plan.n_ops;
+    if (n_targets) *n_targets = p->plan.n_targets;
+    if (n_live_ops) *n_live_ops = p->plan.n_live;
+    if (longest_run) *longest_run = p->plan.longest_run;
+    if (long_run_threshold) *long_run_threshold = kPlanLongRun;
+    if (device_bytes) *device_bytes = p->plan.device_bytes;
+    return SMH_OK;
+}
+
+int smh_update_plan_destroy(smh_update_plan *p) {
+    delete p;
+    return SMH_OK;
+}
+
 int smh_crs_eye(smh_dtype dtype, size_t dim, smh_crs **out) {
     if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
     *out = nullptr;
@@ -1551,6 +1666,7 @@ int smh_crs_sort_rows(smh_crs *m) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(sort_rows(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, m->max_col, m->stream));
     invalidate(m, Changed::Order);
+    ++m->epoch;  // storage order changed: an update plan's targets are stale
     return SMH_OK;
 }
 

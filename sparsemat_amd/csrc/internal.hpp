@@ -404,6 +404,23 @@ int crs_get_many(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, 
 int crs_apply(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
               bool force_general, UpdResult *res, hipStream_t s);
 int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hipStream_t s);
+// A reusable update plan (matplan.hip): the sorted order and the targets of one (rows, cols, ops) stream on one structure.  Runs
+// are numbered class by class: the short ones [0, n_short), then the long ones (more than kPlanLongRun kept operations).
+constexpr uint32_t kPlanLongRun = 64;  // longest run one thread of the short-run kernel folds
+struct UpdPlan {
+    size_t n_ops = 0, n_targets = 0, n_live = 0, longest_run = 0, n_short = 0, device_bytes = 0;
+    DevArray<uint32_t> pos;      // stream positions of the kept operations, grouped by run, in stream order inside a run (padded to 16 bytes)
+    DevArray<uint32_t> off;      // n_targets + 1: where each run starts in pos
+    DevArray<uint32_t> tgt;      // n_targets: the entry of m each run folds into
+    DevArray<uint32_t> setbits;  // one bit per run: its first kept operation is a `set` (the stored value is not read)
+};
+// matupdate.hip: key_out[q] = target of the q-th operation in (target, stream order), src_out[q] = its stream position (n entries
+// each); *n_absent_out = operations without a target in m (then nothing else is produced)
+int crs_plan_targets(const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, uint32_t *key_out, uint32_t *src_out,
+                     uint64_t *n_absent_out, hipStream_t s);
+int plan_build(size_t n, const uint32_t *key, const uint32_t *src, const uint8_t *ops, UpdPlan *plan, hipStream_t s);
+// one gather-and-fold pass over the plan: m_val[tgt] = fold of values[pos] from m_val[tgt] (from_zero: from +0); enqueued on s
+int plan_execute(int dtype, const UpdPlan &plan, const void *values, void *m_val, bool from_zero, hipStream_t s);
 // K1r (LDS x-ring): inspector, host plan, kernel
 struct RingPhase {
     uint32_t row_begin, row_end;  // rows of this phase (row_begin is a multiple of 64)
@@ -588,7 +605,14 @@ struct Knobs {
 }  // namespace smh
 
 // ---- handles ------------------------------------------------------------------------------
+namespace smh {
+uint64_t next_crs_id();  // capi.hip: a process-unique id for every handle ever made
+}
 struct smh_crs {
+    // what an update plan is bound to: this handle (id) in this structure (epoch: advanced whenever offsets, columns or storage
+    // order change -- replace_state, sort_rows; not by scale / update_values / a values-only apply or += / a plan execute)
+    uint64_t id = smh::next_crs_id();
+    uint64_t epoch = 0;
     int dtype = SMH_F32;
     int device = 0;
     size_t n_rows = 0, n_cols = 0, nnz = 0;

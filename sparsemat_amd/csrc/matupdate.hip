@@ -399,6 +399,32 @@ static int apply_t(const UpdMatrix &m, uint64_t n, const uint32_t *rows, const u
     return SMH_OK;
 }
 
+// stream positions 0..n-1: the payload of the plan's sort by target
+__global__ void __launch_bounds__(kBlock) k_upd_iota(uint32_t *__restrict__ out, uint64_t n) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) out[k] = (uint32_t)k;
+}
+
+// steps 1. and 2. without the values, for an update plan (matplan.hip): lookup, then the stable sort by target with the stream
+// position as payload
+int crs_plan_targets(const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, uint32_t *key_out, uint32_t *src_out,
+                     uint64_t *n_absent_out, hipStream_t s) {
+    Scratch scr;
+    UpdInfo *d_info = nullptr, h_info;
+    uint32_t *tgt = nullptr, *src_in = nullptr;
+    SMH_TRY(scr.alloc(&d_info, 1));
+    SMH_TRY(scr.alloc(&tgt, n));
+    SMH_HIP(hipMemsetAsync(d_info, 0, sizeof(UpdInfo), s));
+    SMH_TRY((launch_lookup<float, false>(m.max_row_len, m.off, m.col, (const float *)nullptr, m.n_rows, rows, cols, n, tgt, nullptr, d_info, s)));
+    SMH_HIP(hipMemcpyAsync(&h_info, d_info, sizeof h_info, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    *n_absent_out = h_info.n_absent;
+    if (h_info.n_absent) return SMH_OK;
+    SMH_TRY(scr.alloc(&src_in, n));
+    hipLaunchKernelGGL(k_upd_iota, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, src_in, (uint64_t)n);
+    SMH_HIP(hipGetLastError());
+    return sort_by_target(tgt, key_out, src_in, src_out, n, bits_for(m.nnz), s);
+}
+
 int crs_apply(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
               bool force_general, UpdResult *res, hipStream_t s) {
     *res = UpdResult();

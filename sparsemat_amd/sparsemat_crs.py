@@ -249,6 +249,30 @@ class SparseMatCRS:
         check(lib().smh_crs_apply_dev(self._h, int(n_ops), C.c_void_p(rows_ptr), C.c_void_p(cols_ptr), C.c_void_p(vals_ptr),
                                       C.c_void_p(ops_ptr or 0)))
 
+    def update_plan(self, rows, cols, ops=None):
+        """A reusable plan for re-assembling this matrix from the stream ``(rows[k], cols[k], ops[k])`` with new values
+        (``smh_update_plan_create``): every operation must land on an existing entry -- ``apply`` the stream once to create
+        them, then plan.  Valid until the structure changes (``sort_rows``, an ``apply`` / ``+=`` that adds entries)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        n = len(rows)
+        if len(cols) != n:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "rows and cols differ in length")
+        ops_a = None if ops is None else np.ascontiguousarray(ops, dtype=np.uint8)
+        if ops_a is not None and len(ops_a) != n:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "ops and rows differ in length")
+        h = C.c_void_p()
+        check(lib().smh_update_plan_create(self._h, n, rows.ctypes.data if n else None, cols.ctypes.data if n else None,
+                                           ops_a.ctypes.data if (ops_a is not None and n) else None, C.byref(h)))
+        return UpdatePlan(h, self, n)
+
+    def update_plan_dev(self, n_ops, rows_ptr, cols_ptr, ops_ptr=None):
+        """``update_plan`` over operation arrays that already live in HBM (raw device pointers; ``ops_ptr`` may be None)."""
+        h = C.c_void_p()
+        check(lib().smh_update_plan_create_dev(self._h, int(n_ops), C.c_void_p(rows_ptr), C.c_void_p(cols_ptr), C.c_void_p(ops_ptr or 0),
+                                               C.byref(h)))
+        return UpdatePlan(h, self, int(n_ops))
+
     def set(self, i, j, value):
         """SparseMatrix::set (sparsematrix.rs:226-228): one ``apply`` -- correct, but a device round trip per call."""
         self.apply([_index(i)], [_index(j)], np.array([value], self._dtype), [1])
@@ -579,3 +603,45 @@ class SparseMatCRS:
         """Asynchronous y = A.x on raw device pointers (stream: a hipStream_t value or None)."""
         check(lib().smh_crs_spmv_dev(self._h, C.c_void_p(x_ptr), x_len, C.c_void_p(y_ptr),
                                      _lib.VARIANTS[variant], C.c_void_p(stream or 0)))
+
+
+class UpdatePlan:
+    """The targets and the sorted order of one (rows, cols, ops) stream on one SparseMatCRS (``smh_update_plan``):
+    ``execute(values)`` is what ``apply(rows, cols, values, ops)`` leaves, bit for bit, in one gather-and-fold pass.  Holds its
+    matrix, so the matrix cannot be collected first."""
+
+    def __init__(self, handle, matrix, n_ops):
+        self._h = handle
+        self._m = matrix
+        self._n = n_ops
+
+    def execute(self, values, from_zero=False):
+        """Folds ``values`` (one per operation, stream order) into the matrix.  ``from_zero``: every targeted entry starts
+        from +0 instead of its stored value ("zero, then assemble" in one pass); untargeted entries are not touched."""
+        values = np.asarray(values)
+        dtype = self._m._dtype
+        if values.dtype.kind == "f" and values.dtype != dtype:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "values are %s, the matrix holds %s" % (values.dtype, dtype))
+        values = np.ascontiguousarray(values, dtype=dtype)
+        if len(values) != self._n:
+            raise _lib.SparseMatPanic(_lib.SMH_ERR_INVALID, "the plan holds %d operations, values has %d" % (self._n, len(values)))
+        check(lib().smh_update_plan_execute(self._h, self._m._h, values.ctypes.data if self._n else None, 1 if from_zero else 0))
+
+    def execute_dev(self, vals_ptr, from_zero=False):
+        """``execute`` over a value array that already lives in HBM (raw device pointer)."""
+        check(lib().smh_update_plan_execute_dev(self._h, self._m._h, C.c_void_p(vals_ptr or 0), 1 if from_zero else 0))
+
+    def stats(self):
+        """``smh_update_plan_stats`` as a dict: n_ops, n_targets, n_live_ops, longest_run, long_run_threshold, device_bytes."""
+        names = ("n_ops", "n_targets", "n_live_ops", "longest_run", "long_run_threshold", "device_bytes")
+        out = [C.c_size_t(0) for _ in names]
+        check(lib().smh_update_plan_stats(self._h, *[C.byref(o) for o in out]))
+        return {k: int(o.value) for k, o in zip(names, out)}
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                lib().smh_update_plan_destroy(h)
+            except Exception:
+                pass
