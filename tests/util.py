@@ -28,20 +28,23 @@ def random_crs(rng, n_rows, n_cols, row_lengths, dtype, sort_rows=False, dup=Fal
 def exact_row_sums(off, col, val, x):
     """Row sums of a_ij * x_j far more exactly than either side of the comparison: f32 data in f64 (the products are exact
     there, 24 + 24 bits, and a sum of L <= 2048 terms errs by L * 2^-53), f64 data in the 80-bit long double of this host
-    (2^-64 per operation).  Returned in that wide type."""
+    (2^-64 per operation).  Returned in that wide type.  (A row with a non-finite product comes out non-finite; the rows
+    beside it are untouched -- every row is its own segment.)"""
     wide = np.float64 if np.dtype(val.dtype) == np.dtype(np.float32) else np.longdouble
     n_rows = len(off) - 1
     out = np.zeros(n_rows, dtype=wide)
     if len(val) == 0:
         return out
-    prod = val.astype(wide) * np.asarray(x)[col].astype(wide)
-    lens = np.diff(off.astype(np.int64))
-    nonempty = lens > 0
-    # (the non-empty rows' starts, in order, cut the entry stream into exactly their segments)
-    out[nonempty] = np.add.reduceat(prod, off[:-1].astype(np.int64)[nonempty])
+    with np.errstate(invalid="ignore", over="ignore"):
+        prod = val.astype(wide) * np.asarray(x)[col].astype(wide)
+        lens = np.diff(off.astype(np.int64))
+        nonempty = lens > 0
+        # (the non-empty rows' starts, in order, cut the entry stream into exactly their segments)
+        out[nonempty] = np.add.reduceat(prod, off[:-1].astype(np.int64)[nonempty])
     return out
 
 
+BUCKET_LOG_FILE = True   # (tests of the gate itself turn the file off: their records are of their own making)
 BUCKETS = ((1, 8), (9, 32), (33, 128), (129, 512), (513, 1 << 31))
 
 
@@ -57,7 +60,7 @@ def _log_buckets(what, dt, lens, excess):
             rec["buckets"]["%d-%s" % (lo, hi if hi < (1 << 31) else "")] = {"rows": int(sel.sum()), "worst_excess": float(excess[sel].max())}
     print("parity buckets", json.dumps(rec))
     out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(out_dir):
+    if BUCKET_LOG_FILE and os.path.isdir(out_dir):
         try:
             with open(os.path.join(out_dir, "parity_buckets.jsonl"), "a") as f:
                 f.write(json.dumps(rec) + "\n")
@@ -66,7 +69,17 @@ def _log_buckets(what, dt, lens, excess):
 
 
 # what the suite reports at its end (tests/conftest.py): rows compared, rows that needed the looser form, worst literal ratio
-PARITY_STATS = {"comparisons": 0, "rows": 0, "fallback_rows": 0, "worst_literal": {}}
+# (finite oracle rows only); nonfinite_rows: rows in which the oracle itself is NaN / +Inf / -Inf, compared by class
+PARITY_STATS = {"comparisons": 0, "rows": 0, "fallback_rows": 0, "worst_literal": {}, "nonfinite_rows": 0}
+
+
+def value_class(a):
+    """0 finite, 1 +Inf, 2 -Inf, 3 NaN (sign and payload of a NaN are not told apart: x86 and the GPU make different ones)."""
+    a = np.asarray(a)
+    return np.where(np.isnan(a), 3, np.where(np.isposinf(a), 1, np.where(np.isneginf(a), 2, 0))).astype(np.int8)
+
+
+CLASS_NAMES = ("finite", "+Inf", "-Inf", "NaN")
 
 
 def assert_spmv_close(y, off, col, val, x, what=""):
@@ -75,39 +88,61 @@ def assert_spmv_close(y, off, col, val, x, what=""):
     further than tol * sum|a x| from the (effectively) exact row sum -- the reference's own rounding of a very long row --
     may instead satisfy |y_gpu - exact| <= |y_oracle - exact| + tol * sum|a x|: there the device is held to being no worse
     than the reference, not to reproducing its error.  Such rows are counted (PARITY_STATS; the suite prints the total) --
-    none is expected at these tolerances.  The same normwise."""
+    none is expected at these tolerances.  The same normwise.
+
+    Non-finite data: where the oracle's row is NaN, +Inf or -Inf, y must be of the same class (NaN sign / payload aside), and
+    the row takes no part in the bounds, the normwise check, the statistics' worst ratio or the bucket log.  Where the oracle's
+    row is finite, y must be finite and within the bounds.  Every test is of the form "passes only if <=", so that a NaN on
+    either side of a comparison fails it."""
     dt = np.dtype(val.dtype)
+    y = np.asarray(y)
     y_ref = oracle.spmv(off, col, val, x)
     assert y.shape == y_ref.shape, what
-    scale = oracle.spmv_abs(off, col, val, x)
-    lens = np.diff(off.astype(np.int64))
-    exact = exact_row_sums(off, col, val, x)
+    lens_all = np.diff(off.astype(np.int64))
+    cls_ref, cls_y = value_class(y_ref), value_class(y)
+    fin = cls_ref == 0
+    PARITY_STATS["comparisons"] += 1
+    PARITY_STATS["rows"] += int(len(lens_all))
+    PARITY_STATS["nonfinite_rows"] += int((~fin).sum())
+    bad = cls_y != cls_ref
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise AssertionError("%s: %d rows of another class than the oracle's (%d of them where the oracle is finite); first: row %d, "
+                             "len %d, y %r (%s), oracle %r (%s)" % (what, bad.sum(), (bad & fin).sum(), i, int(lens_all[i]), y[i],
+                                                                    CLASS_NAMES[cls_y[i]], y_ref[i], CLASS_NAMES[cls_ref[i]]))
+    # from here on: the rows in which the oracle (and hence, by now, y) is finite
+    rows = np.nonzero(fin)[0]
+    y_f, y_ref_f, lens = y[fin], y_ref[fin], lens_all[fin]
+    scale = oracle.spmv_abs(off, col, val, x)[fin]
+    exact = exact_row_sums(off, col, val, x)[fin]
     wide = exact.dtype
     tol = REL_TOL[dt]
     tiny = np.finfo(dt).tiny
-    literal = np.abs(y.astype(wide) - y_ref.astype(wide)).astype(np.float64)
-    err_gpu = np.abs(y.astype(wide) - exact).astype(np.float64)
-    err_ref = np.abs(y_ref.astype(wide) - exact).astype(np.float64)
+    literal = np.abs(y_f.astype(wide) - y_ref_f.astype(wide)).astype(np.float64)
+    err_gpu = np.abs(y_f.astype(wide) - exact).astype(np.float64)
+    err_ref = np.abs(y_ref_f.astype(wide) - exact).astype(np.float64)
+    bound = tol * scale + tiny
+    assert np.isfinite(bound).all() and np.isfinite(err_ref).all(), what + ": a finite oracle row with a non-finite sum |a x|"
+    ratio = literal / np.maximum(scale, 1e-300)
     excess = (err_gpu - err_ref) / np.maximum(scale, 1e-300)
     _log_buckets(what, dt, lens, excess)
-    fails_literal = literal > tol * scale + tiny
-    oracle_is_far = err_ref > tol * scale + tiny          # the only rows the looser form is for
-    fallback = fails_literal & oracle_is_far
-    PARITY_STATS["comparisons"] += 1
-    PARITY_STATS["rows"] += int(len(lens))
+    holds_literal = literal <= bound
+    oracle_is_near = err_ref <= bound                     # the looser form is for the other rows only
+    fallback = ~holds_literal & ~oracle_is_near
     PARITY_STATS["fallback_rows"] += int(fallback.sum())
     if len(lens):
-        w = float((literal / np.maximum(scale, 1e-300)).max())
+        w = float(ratio.max())
+        assert w == w, what  # (finite rows on both sides: no NaN can be left)
         PARITY_STATS["worst_literal"][dt.name] = max(PARITY_STATS["worst_literal"].get(dt.name, 0.0), w)
-    bad = fails_literal & ~oracle_is_far
+    bad = ~holds_literal & oracle_is_near
     assert not bad.any(), "%s: %d rows beyond |y_gpu - y_oracle| <= %g * sum|a x|, worst %g (row %d, len %d)" % (
-        what, bad.sum(), tol, float((literal / np.maximum(scale, 1e-300))[bad].max()), int(np.argmax(bad)), int(lens[np.argmax(bad)]))
-    bad = fallback & (err_gpu > err_ref + tol * scale + tiny)
+        what, bad.sum(), tol, float(ratio[bad].max()), int(rows[np.argmax(bad)]), int(lens[np.argmax(bad)]))
+    bad = fallback & ~(err_gpu <= err_ref + bound)
     assert not bad.any(), "%s: %d rows out of the excess bound, worst excess %g * sum|a x| (row %d, len %d)" % (
-        what, bad.sum(), excess.max(), int(np.argmax(excess)), int(lens[np.argmax(excess)]))
-    denom = float(np.abs(y_ref.astype(np.float64)).max()) if len(y_ref) else 0.0
+        what, bad.sum(), excess.max(), int(rows[np.argmax(excess)]), int(lens[np.argmax(excess)]))
+    denom = float(np.abs(y_ref_f.astype(np.float64)).max()) if len(y_ref_f) else 0.0
     if denom > 0:  # normwise, literal: max |y_gpu - y_oracle| <= tol * max |y_oracle| (else: no worse than the oracle against exact)
-        if literal.max() / denom > tol:
+        if not (literal.max() / denom <= tol):
             denom = float(np.abs(exact).max())
             assert err_gpu.max() / denom <= err_ref.max() / denom + tol, what
     return y_ref
