@@ -62,11 +62,8 @@ int current_device() {
 }
 
 // defined in the kernel files
-size_t cg_scalars_bytes(int dtype);
-int cg_begin(int dtype, void *sc, const void *r, size_t n, void *partials, double tol, size_t iter_max, hipStream_t s);
-int cg_iter_tail(int dtype, void *sc, void *sc2, void *x, void *r, void *p, const void *ap, size_t n, void *partials,
-                 const void *dot_partials, uint32_t dot_count, hipStream_t s);
-void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t *iters, double *rr);
+int cg_solve(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+             double *rr_out);  // cg.hip: the solve behind smh_cg_solve_vec
 int synth_x(int dtype, uint64_t seed, size_t begin, size_t n, void *x, hipStream_t s);
 int synth_fixed(int dtype, uint64_t seed, int pattern, size_t n, uint32_t k, size_t row_begin, size_t row_end,
                 uint32_t *off, uint32_t *col, void *val, hipStream_t s);
@@ -2283,92 +2280,7 @@ int smh_cg_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_
     if (m->n_rows != b->n || m->n_rows != x->n)
         return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");                            // :33-36
     if (check_every == 0) check_every = 4;
-    const size_t n = m->n_rows;
-    const size_t vs = dtype_size(m->dtype);
-    hipStream_t s = m->stream;
-    void *r = nullptr, *p = nullptr, *ap = nullptr, *partials = nullptr, *dot_partials = nullptr, *sc = nullptr, *sc2 = nullptr, *h_sc = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    int rc = SMH_OK;
-    size_t iters = 0;
-    double rr = 0.0;
-    auto body = [&]() -> int {
-        const size_t vb = (n ? n : 1) * vs;
-        SMH_HIP(hipMalloc(&r, vb));
-        SMH_HIP(hipMalloc(&p, vb));
-        SMH_HIP(hipMalloc(&ap, vb));
-        SMH_HIP(hipMalloc(&partials, (2 * kReducePartials + 16) * vs));  // (r.r partials | the dot's result | a first fold of many p.Ap partials)
-        // p.Ap: left in the SpMV epilogue when the kernel can (K1s), else a separate two-stage dot
-        const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
-        if (n_dot) SMH_HIP(hipMalloc(&dot_partials, n_dot * vs));
-        SMH_HIP(hipMalloc(&sc, cg_scalars_bytes(m->dtype)));
-        SMH_HIP(hipMalloc(&sc2, cg_scalars_bytes(m->dtype)));  // (the scalars are double-buffered within an iteration: cg.hip)
-        SMH_HIP(hipHostMalloc(&h_sc, cg_scalars_bytes(m->dtype)));
-        // r = b - A x  (:38) ; p = r.clone() (:39) ; rr = r.r (:40)
-        SMH_TRY(spmv_enqueue(m, x->d, x->n, r, variant, s));
-        SMH_TRY(launch_ew(m->dtype, Ew::RSubInto, r, b->d, n, 0.0, nullptr, s));
-        if (n) SMH_HIP(hipMemcpyAsync(p, r, n * vs, hipMemcpyDeviceToDevice, s));
-        SMH_TRY(cg_begin(m->dtype, sc, r, n, partials, tol, iter_max, s));
-        size_t launched = 0;
-        int converged = 0;
-        // A batch of `check_every` iterations (the product + 2 to 3 launches each) is captured ONCE into a hipGraph and replayed:
-        // for small systems the loop is launch-bound.  Iterations past convergence / iter_max are no-ops on the
-        // device, so whole batches can always be replayed.  (All workspaces were created by the SpMV above.)
-        if (iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            int crc = SMH_OK;
-            for (size_t i = 0; i < check_every && crc == SMH_OK; ++i) {
-                crc = spmv_enqueue(m, p, n, ap, variant, s, dot_partials);
-                if (crc == SMH_OK)
-                    crc = cg_iter_tail(m->dtype, sc, sc2, x->d, r, p, ap, n, partials, dot_partials, (uint32_t)n_dot, s);
-            }
-            hipError_t ce = hipStreamEndCapture(s, &graph);
-            if (crc != SMH_OK || ce != hipSuccess || !graph ||
-                hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-                graph_exec = nullptr;  // fall back to plain stream launches
-                (void)hipGetLastError();
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-        while (launched < iter_max) {
-            size_t batch = iter_max - launched < check_every ? iter_max - launched : check_every;
-            if (graph_exec) {
-                SMH_HIP(hipGraphLaunch(graph_exec, s));
-                batch = check_every;
-            } else {
-                for (size_t i = 0; i < batch; ++i) {
-                    SMH_TRY(spmv_enqueue(m, p, n, ap, variant, s, dot_partials));                        // :43
-                    SMH_TRY(cg_iter_tail(m->dtype, sc, sc2, x->d, r, p, ap, n, partials, dot_partials, (uint32_t)n_dot, s));  // :45-59
-                }
-            }
-            launched += batch;
-            SMH_HIP(hipMemcpyAsync(h_sc, sc, cg_scalars_bytes(m->dtype), hipMemcpyDeviceToHost, s));
-            SMH_HIP(hipStreamSynchronize(s));
-            uint64_t it64 = 0;
-            cg_read_scalars(m->dtype, h_sc, &converged, &it64, &rr);
-            iters = (size_t)it64;
-            if (converged) break;
-        }
-        if (iter_max == 0) {
-            SMH_HIP(hipMemcpyAsync(h_sc, sc, cg_scalars_bytes(m->dtype), hipMemcpyDeviceToHost, s));
-            SMH_HIP(hipStreamSynchronize(s));
-            uint64_t it64 = 0;
-            cg_read_scalars(m->dtype, h_sc, &converged, &it64, &rr);
-        }
-        return SMH_OK;
-    };
-    rc = keep_error(body(), [&] {
-        (void)hipStreamSynchronize(s);
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipFree(r); (void)hipFree(p); (void)hipFree(ap); (void)hipFree(partials); (void)hipFree(dot_partials); (void)hipFree(sc); (void)hipFree(sc2);
-        if (h_sc) (void)hipHostFree(h_sc);
-        (void)hipGetLastError();
-    });
-    if (rc != SMH_OK) return rc;
-    if (iters_out) *iters_out = iters;
-    if (rr_out) *rr_out = rr;
-    return SMH_OK;
+    return cg_solve(m, b, x, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 int smh_cg_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,

@@ -3,7 +3,7 @@
 // Restates ConjugateGradient::solve (reference linearsolver.rs:27-61) as a stream of kernels whose
 // scalars (r.r, p.Ap, alpha, beta, the stop flag, the iteration count) never leave HBM:
 //
-//   per iteration   SpMV  Ap = A p  (+ per-tile partials of p.Ap where the kernel can) (launched by the caller)  :43
+//   per iteration   SpMV  Ap = A p  (+ per-tile partials of p.Ap where the kernel can) (the matrix's own kernel)  :43
 //                   [k_sum_stage1 when more than 1024 partials came back / a two-stage dot when none did]       :45
 //                   k_cg_par_update : fold the partials, alpha = rr / pAp, decide "active" -- every workgroup for
 //                                     itself, workgroup 0 writes the scalars --; r -= round(Ap*alpha); partials r.r :45, :49-51
@@ -23,21 +23,12 @@
 // x, r, p are exactly those of the iteration in which the reference would have left its loop.
 // Element-wise updates round the product and the sum separately (bit-identical to the reference
 // for equal alpha/beta); the reductions are fixed trees (bitwise reproducible).
+//
+// The single-matrix driver (cg_solve, behind smh_cg_solve_vec) is at the end of the first half of this file; its loop over batches
+// of bodies -- the hipGraph, the polls -- is solve_in_batches (internal.hpp), which pcg.hip runs too.
 #include "internal.hpp"
 
 namespace smh {
-
-template <typename T>
-struct CgScalars {
-    T rr, rr_prev, pap, alpha, beta;
-    uint32_t converged;
-    uint32_t active;
-    uint32_t entered;  // the current loop body was entered: its x update is due (set with alpha)
-    uint32_t pad_;
-    uint64_t iters;
-    uint64_t iter_max;
-    double tol;
-};
 
 template <typename T> struct CgVec;
 template <> struct CgVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
@@ -182,7 +173,7 @@ __device__ __forceinline__ void cg_p_body(bool rebuild, T alpha, T beta, T *__re
 }
 
 
-// ---- the two launches of an iteration's tail (single matrix: cg_iter_tail; row-partitioned: par.hip) ----------------------------
+// ---- the two launches of an iteration's tail (single matrix: cg_iter_tail_t; row-partitioned: par.hip) ----------------------------
 // alpha + the x / r update in one launch, beta with the stop test + the p sweep in the other: every workgroup folds the `nb` partial
 // sums itself (the product's per-tile p.Ap partials or their first fold; the update's r.r partials; across row blocks: the blocks'
 // values) -- in exactly the order the one-workgroup kernels of rounds 1-3 folded them, so every workgroup (of every block) gets the
@@ -251,7 +242,7 @@ k_cg_par_p(const CgScalars<T> *__restrict__ in, CgScalars<T> *__restrict__ out, 
     cg_p_body<T, VEC>(was_active && !conv, in->alpha, beta, p, r, x, n);
 }
 
-// ---- host-side driver pieces (called from capi.hip) ----------------------------------------------
+// ---- host side: the launchers of the tail's two kernels, the single-matrix driver -------------------------------------------------
 unsigned reduce_blocks(size_t n);  // blas1.hip
 
 static inline bool cg_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -269,22 +260,49 @@ static int cg_begin_t(void *sc, const T *r, size_t n, T *partials, double tol, s
     return SMH_OK;
 }
 
-int cg_begin(int dtype, void *sc, const void *r, size_t n, void *partials, double tol, size_t iter_max, hipStream_t s) {
-    if (dtype == SMH_F64) return cg_begin_t<double>(sc, (const double *)r, n, (double *)partials, tol, iter_max, s);
-    return cg_begin_t<float>(sc, (const float *)r, n, (float *)partials, tol, iter_max, s);
+// The one launch of each tail kernel, for the single-matrix tail below and for the row-partitioned solver's pieces at the end of
+// this file.  The callers differ in two things, which they pass: `vec`, whether the 16-byte form may run (it sums in another order
+// than the plain one: the single matrix asks all four vectors of an iteration at once, a row block each kernel's own), and `cap`,
+// the most workgroups (the single matrix's tuning knobs; 512 for a row block).
+// p.Ap = fold(pap_vals[0..nb)); alpha; "active" (:45) -- then r -= round(Ap*alpha) on [0, n) and partials[0..*count_out) of r.r (:49-51).
+// Scalars: read from sc_in, written to sc_out (see k_cg_par_update).
+template <typename T>
+static int launch_cg_update(bool vec, unsigned cap, const void *sc_in, void *sc_out, const T *pap_vals, uint32_t nb, T *r, const T *ap, size_t n,
+                            T *partials, uint32_t *count_out, hipStream_t s) {
+    unsigned rb = reduce_blocks(n);
+    if (rb > cap) rb = cap;
+    if (vec)
+        hipLaunchKernelGGL((k_cg_par_update<T, true>), dim3(rb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, pap_vals, nb, r, ap, (uint64_t)n, partials);
+    else
+        hipLaunchKernelGGL((k_cg_par_update<T, false>), dim3(rb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, pap_vals, nb, r, ap, (uint64_t)n, partials);
+    SMH_HIP(hipGetLastError());
+    *count_out = rb;
+    return SMH_OK;
+}
+
+// r.r = fold(rr_vals[0..nb)); stop test; beta (:51-56) -- then x += round(p*alpha) (:47) and p = round(p*beta) + r (:58-59) on [0, n).
+// Scalars: read from sc_in, written to sc_out.
+template <typename T>
+static int launch_cg_p(bool vec, uint64_t cap, const void *sc_in, void *sc_out, const T *rr_vals, uint32_t nb, T *p, const T *r, T *x, size_t n,
+                       hipStream_t s) {
+    uint64_t pb = (n / CgVec<T>::N + kBlock) / kBlock;
+    if (pb > cap) pb = cap;
+    if (vec)
+        hipLaunchKernelGGL((k_cg_par_p<T, true>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, rr_vals, nb, p, r, x, (uint64_t)n);
+    else
+        hipLaunchKernelGGL((k_cg_par_p<T, false>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, rr_vals, nb, p, r, x, (uint64_t)n);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
 }
 
 // everything of one iteration AFTER the SpMV Ap = A p
 template <typename T>
-static int cg_iter_tail_t(void *scv, void *sc2v, T *x, T *r, T *p, const T *ap, size_t n, T *partials, const T *dot_partials,
-                          uint32_t dot_count, hipStream_t s) {
-    const CgScalars<T> *sc = (const CgScalars<T> *)scv;
-    CgScalars<T> *sc2 = (CgScalars<T> *)sc2v;
+static int cg_iter_tail_t(void *sc, void *sc2, T *x, T *r, T *p, const T *ap, size_t n, T *partials, const T *dot_partials, uint32_t dot_count,
+                          hipStream_t s) {
     // 2 blocks per CU for the two vector sweeps of the tail: 2.51-2.57 ms per C4 iteration against 2.66-2.69 with 1024 / 2048
     // blocks in the same call (profiles/r01_cg_grid_sweep.log)
     static const unsigned grid_cap = getenv("SMH_CG_BLOCKS") ? (unsigned)atoi(getenv("SMH_CG_BLOCKS")) : 512u;  // tuning knob
-    unsigned rb = reduce_blocks(n);
-    if (rb > grid_cap) rb = grid_cap;
+    static const uint64_t p_cap = getenv("SMH_CG_P_BLOCKS") ? (uint64_t)atoll(getenv("SMH_CG_P_BLOCKS")) : 512;  // tuning knob
     const bool vec = cg_aligned16(x) && cg_aligned16(r) && cg_aligned16(p) && cg_aligned16(ap);
     // Round 4: the two one-workgroup scalar kernels (alpha; beta with the stop test) ride the sweeps that follow them -- every workgroup
     // folds the partial sums itself, in the order the one-workgroup kernels did (same bits), the scalars double-buffered (sc -> sc2 -> sc)
@@ -310,29 +328,9 @@ static int cg_iter_tail_t(void *scv, void *sc2v, T *x, T *r, T *p, const T *ap, 
         pap_vals = partials + kReducePartials;
         pap_count = 1u;
     }
-    if (vec)
-        hipLaunchKernelGGL((k_cg_par_update<T, true>), dim3(rb), dim3(kBlock), 0, s, sc, sc2, pap_vals, pap_count, r, ap, (uint64_t)n, partials);
-    else
-        hipLaunchKernelGGL((k_cg_par_update<T, false>), dim3(rb), dim3(kBlock), 0, s, sc, sc2, pap_vals, pap_count, r, ap, (uint64_t)n, partials);
-    SMH_HIP(hipGetLastError());
-    uint64_t pb = (n / CgVec<T>::N + kBlock) / kBlock;
-    static const uint64_t p_cap = getenv("SMH_CG_P_BLOCKS") ? (uint64_t)atoll(getenv("SMH_CG_P_BLOCKS")) : 512;  // tuning knob
-    if (pb > p_cap) pb = p_cap;
-    if (vec)
-        hipLaunchKernelGGL((k_cg_par_p<T, true>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc2, (CgScalars<T> *)scv, (const T *)partials, rb, p, r, x, (uint64_t)n);
-    else
-        hipLaunchKernelGGL((k_cg_par_p<T, false>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc2, (CgScalars<T> *)scv, (const T *)partials, rb, p, r, x, (uint64_t)n);
-    SMH_HIP(hipGetLastError());
-    return SMH_OK;
-}
-
-int cg_iter_tail(int dtype, void *sc, void *sc2, void *x, void *r, void *p, const void *ap, size_t n, void *partials,
-                 const void *dot_partials, uint32_t dot_count, hipStream_t s) {
-    if (dtype == SMH_F64)
-        return cg_iter_tail_t<double>(sc, sc2, (double *)x, (double *)r, (double *)p, (const double *)ap, n, (double *)partials,
-                                      (const double *)dot_partials, dot_count, s);
-    return cg_iter_tail_t<float>(sc, sc2, (float *)x, (float *)r, (float *)p, (const float *)ap, n, (float *)partials,
-                                 (const float *)dot_partials, dot_count, s);
+    uint32_t rb = 0;
+    SMH_TRY(launch_cg_update<T>(vec, grid_cap, sc, sc2, pap_vals, pap_count, r, ap, n, partials, &rb, s));
+    return launch_cg_p<T>(vec, p_cap, sc2, sc, partials, rb, p, r, x, n, s);
 }
 
 // host view of the scalar block after a poll
@@ -344,6 +342,59 @@ void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t 
         const CgScalars<float> *h = (const CgScalars<float> *)host_copy;
         *converged = (int)h->converged; *iters = h->iters; *rr = (double)h->rr;
     }
+}
+
+// ConjugateGradient::solve (linearsolver.rs:27-61) on device vectors, on the handle's stream; the argument checks (:30-36) are the
+// entry point's (capi.hip).  check_every: bodies per poll.
+template <typename T>
+static int cg_solve_t(smh_crs *m, const T *b, T *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out, double *rr_out) {
+    const size_t n = m->n_rows;
+    hipStream_t s = m->stream;
+    Scratch ws;
+    PinnedBuf h_sc;
+    int converged = 0;
+    size_t iters = 0;
+    double rr = 0.0;
+    auto go = [&]() -> int {
+        T *r = nullptr, *p = nullptr, *ap = nullptr, *partials = nullptr, *dot_partials = nullptr;
+        CgScalars<T> *sc = nullptr, *sc2 = nullptr;  // (double-buffered within an iteration, see above)
+        SMH_TRY(ws.alloc(&r, n));
+        SMH_TRY(ws.alloc(&p, n));
+        SMH_TRY(ws.alloc(&ap, n));
+        SMH_TRY(ws.alloc(&partials, 2 * kReducePartials + 16));  // (r.r partials | the dot's result | a first fold of many p.Ap partials)
+        // p.Ap: left in the SpMV epilogue when the kernel can (K1s), else a separate two-stage dot
+        const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
+        if (n_dot) SMH_TRY(ws.alloc(&dot_partials, n_dot));
+        SMH_TRY(ws.alloc(&sc, 1));
+        SMH_TRY(ws.alloc(&sc2, 1));
+        SMH_TRY(h_sc.alloc(sizeof(CgScalars<T>), hipHostMallocDefault));
+        // r = b - A x  (:38) ; p = r.clone() (:39) ; rr = r.r (:40)
+        SMH_TRY(spmv_enqueue(m, x, n, r, variant, s));  // (before any capture: the handle's lazy workspaces exist from here on)
+        SMH_TRY(launch_ew(m->dtype, Ew::RSubInto, r, b, n, 0.0, nullptr, s));
+        if (n) SMH_HIP(hipMemcpyAsync(p, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+        SMH_TRY(cg_begin_t<T>(sc, r, n, partials, tol, iter_max, s));
+        auto body = [&]() -> int {
+            SMH_TRY(spmv_enqueue(m, p, n, ap, variant, s, dot_partials));                                    // :43
+            return cg_iter_tail_t<T>(sc, sc2, x, r, p, ap, n, partials, dot_partials, (uint32_t)n_dot, s);  // :45-59
+        };
+        return solve_in_batches(m->dtype, s, iter_max, check_every, body, sc, h_sc.get(), &converged, &iters, &rr);
+    };
+    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
+    // the solve failed half way
+    const int rc = keep_error(go(), [&] {
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+    });
+    if (rc != SMH_OK) return rc;
+    if (iters_out) *iters_out = iters;
+    if (rr_out) *rr_out = rr;
+    return SMH_OK;
+}
+
+int cg_solve(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+             double *rr_out) {
+    if (m->dtype == SMH_F64) return cg_solve_t<double>(m, (const double *)b->d, (double *)x->d, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return cg_solve_t<float>(m, (const float *)b->d, (float *)x->d, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 }  // namespace smh
@@ -367,17 +418,15 @@ int cg_fold(int dtype, const void *partials, uint32_t count, void *out, hipStrea
     return cg_fold_t<float>((const float *)partials, count, (float *)out, s);
 }
 
-#define SMH_CG_PAR_SCALAR(NAME, KERNEL)                                                                            \
-    int NAME(int dtype, void *sc, const void *vals, uint32_t nb, hipStream_t s) {                                  \
-        if (dtype == SMH_F64)                                                                                      \
-            hipLaunchKernelGGL(KERNEL<double>, dim3(1), dim3(kBlock), 0, s, (CgScalars<double> *)sc, (const double *)vals, nb); \
-        else                                                                                                       \
-            hipLaunchKernelGGL(KERNEL<float>, dim3(1), dim3(kBlock), 0, s, (CgScalars<float> *)sc, (const float *)vals, nb);    \
-        SMH_HIP(hipGetLastError());                                                                                \
-        return SMH_OK;                                                                                             \
-    }
-SMH_CG_PAR_SCALAR(cg_par_set_rr, k_cg_set_rr)  // rr = fold(vals)                         linearsolver.rs:40
-#undef SMH_CG_PAR_SCALAR
+// rr = fold(vals)   (linearsolver.rs:40)
+int cg_par_set_rr(int dtype, void *sc, const void *vals, uint32_t nb, hipStream_t s) {
+    if (dtype == SMH_F64)
+        hipLaunchKernelGGL(k_cg_set_rr<double>, dim3(1), dim3(kBlock), 0, s, (CgScalars<double> *)sc, (const double *)vals, nb);
+    else
+        hipLaunchKernelGGL(k_cg_set_rr<float>, dim3(1), dim3(kBlock), 0, s, (CgScalars<float> *)sc, (const float *)vals, nb);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
 
 int cg_par_init(int dtype, void *sc, double tol, size_t iter_max, hipStream_t s) {
     if (dtype == SMH_F64) hipLaunchKernelGGL(k_cg_init<double>, dim3(1), dim3(1), 0, s, (CgScalars<double> *)sc, tol, (uint64_t)iter_max);
@@ -386,45 +435,30 @@ int cg_par_init(int dtype, void *sc, double tol, size_t iter_max, hipStream_t s)
     return SMH_OK;
 }
 
-// p.Ap = fold(pap_vals[0..nb)); alpha; "active" (:45) -- then r -= round(Ap*alpha) on this block's rows and partials[0..*count_out)
-// of r.r (:49-51).  Scalars: read from sc_in, written to sc_out (see k_cg_par_update).
+// The tail's two launches on one block's rows (launch_cg_update / launch_cg_p above): each kernel takes the 16-byte form when its own
+// vectors allow it, at most 512 workgroups.  (Templates of their own, so that the launchers are first instantiated from the
+// single-matrix tail: the code object lists its kernels in the order of their first use.)
 template <typename T>
-static int cg_par_update_t(const void *sc_in, void *sc_out, const T *pap_vals, uint32_t nb, T *r, const T *ap, size_t n, T *partials,
+static int cg_par_update_t(const void *sc_in, void *sc_out, const void *pap_vals, uint32_t nb, void *r, const void *ap, size_t n, void *partials,
                            uint32_t *count_out, hipStream_t s) {
-    unsigned rb = reduce_blocks(n);
-    if (rb > 512u) rb = 512u;
-    if (cg_aligned16(r) && cg_aligned16(ap))
-        hipLaunchKernelGGL((k_cg_par_update<T, true>), dim3(rb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, pap_vals, nb, r, ap, (uint64_t)n, partials);
-    else
-        hipLaunchKernelGGL((k_cg_par_update<T, false>), dim3(rb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, pap_vals, nb, r, ap, (uint64_t)n, partials);
-    SMH_HIP(hipGetLastError());
-    *count_out = rb;
-    return SMH_OK;
+    return launch_cg_update<T>(cg_aligned16(r) && cg_aligned16(ap), 512u, sc_in, sc_out, (const T *)pap_vals, nb, (T *)r, (const T *)ap, n, (T *)partials,
+                               count_out, s);
 }
 
 int cg_par_update(int dtype, const void *sc_in, void *sc_out, const void *pap_vals, uint32_t nb, void *r, const void *ap, size_t n, void *partials,
                   uint32_t *count_out, hipStream_t s) {
-    if (dtype == SMH_F64) return cg_par_update_t<double>(sc_in, sc_out, (const double *)pap_vals, nb, (double *)r, (const double *)ap, n, (double *)partials, count_out, s);
-    return cg_par_update_t<float>(sc_in, sc_out, (const float *)pap_vals, nb, (float *)r, (const float *)ap, n, (float *)partials, count_out, s);
+    if (dtype == SMH_F64) return cg_par_update_t<double>(sc_in, sc_out, pap_vals, nb, r, ap, n, partials, count_out, s);
+    return cg_par_update_t<float>(sc_in, sc_out, pap_vals, nb, r, ap, n, partials, count_out, s);
 }
 
-// r.r = fold(rr_vals[0..nb)); stop test; beta (:51-56) -- then x += round(p*alpha) (:47) and p = round(p*beta) + r (:58-59) on this
-// block's rows.  Scalars: read from sc_in, written to sc_out.
 template <typename T>
-static int cg_par_p_t(const void *sc_in, void *sc_out, const T *rr_vals, uint32_t nb, T *p, const T *r, T *x, size_t n, hipStream_t s) {
-    uint64_t pb = (n / CgVec<T>::N + kBlock) / kBlock;
-    if (pb > 512) pb = 512;
-    if (cg_aligned16(p) && cg_aligned16(r) && cg_aligned16(x))
-        hipLaunchKernelGGL((k_cg_par_p<T, true>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, rr_vals, nb, p, r, x, (uint64_t)n);
-    else
-        hipLaunchKernelGGL((k_cg_par_p<T, false>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, rr_vals, nb, p, r, x, (uint64_t)n);
-    SMH_HIP(hipGetLastError());
-    return SMH_OK;
+static int cg_par_p_t(const void *sc_in, void *sc_out, const void *rr_vals, uint32_t nb, void *p, const void *r, void *x, size_t n, hipStream_t s) {
+    return launch_cg_p<T>(cg_aligned16(p) && cg_aligned16(r) && cg_aligned16(x), 512, sc_in, sc_out, (const T *)rr_vals, nb, (T *)p, (const T *)r, (T *)x, n, s);
 }
 
 int cg_par_p(int dtype, const void *sc_in, void *sc_out, const void *rr_vals, uint32_t nb, void *p, const void *r, void *x, size_t n, hipStream_t s) {
-    if (dtype == SMH_F64) return cg_par_p_t<double>(sc_in, sc_out, (const double *)rr_vals, nb, (double *)p, (const double *)r, (double *)x, n, s);
-    return cg_par_p_t<float>(sc_in, sc_out, (const float *)rr_vals, nb, (float *)p, (const float *)r, (float *)x, n, s);
+    if (dtype == SMH_F64) return cg_par_p_t<double>(sc_in, sc_out, rr_vals, nb, p, r, x, n, s);
+    return cg_par_p_t<float>(sc_in, sc_out, rr_vals, nb, p, r, x, n, s);
 }
 
 }  // namespace smh

@@ -214,6 +214,42 @@ struct PinnedBuf {
   private:
     void *p_ = nullptr;
 };
+// A captured graph and its executable form: empty until end_capture / instantiate succeeds (a failure leaves the owner empty and is
+// the caller's to handle: the solvers fall back to plain launches).  Nothing waits for a launched graph before its executable goes.
+struct Graph {
+    Graph() = default;
+    Graph(Graph &&o) noexcept : g_(o.g_) { o.g_ = nullptr; }
+    Graph &operator=(Graph &&o) noexcept { std::swap(g_, o.g_); return *this; }
+    ~Graph() { if (g_) (void)hipGraphDestroy(g_); }
+    hipError_t end_capture(hipStream_t s) {  // ends the capture that hipStreamBeginCapture began on s
+        *this = Graph();
+        hipGraph_t g = nullptr;
+        const hipError_t rc = hipStreamEndCapture(s, &g);
+        if (rc == hipSuccess) g_ = g;
+        return rc;
+    }
+    hipGraph_t get() const { return g_; }
+
+  private:
+    hipGraph_t g_ = nullptr;
+};
+struct GraphExec {
+    GraphExec() = default;
+    GraphExec(GraphExec &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    GraphExec &operator=(GraphExec &&o) noexcept { std::swap(e_, o.e_); return *this; }
+    ~GraphExec() { if (e_) (void)hipGraphExecDestroy(e_); }
+    hipError_t instantiate(hipGraph_t g) {
+        *this = GraphExec();
+        hipGraphExec_t e = nullptr;
+        const hipError_t rc = hipGraphInstantiate(&e, g, nullptr, nullptr, 0);
+        if (rc == hipSuccess) e_ = e;
+        return rc;
+    }
+    hipGraphExec_t get() const { return e_; }
+
+  private:
+    hipGraphExec_t e_ = nullptr;
+};
 
 // rocPRIM's two-phase calls: `call` names `tmp` and `bytes`; it is run once to size the temporary storage (bytes ? bytes : 16),
 // then on it; stream s is synchronised before the storage is freed
@@ -478,6 +514,73 @@ int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials
                hipStream_t s);
 int launch_fold2(int dtype, const void *in, size_t count, void *partials, void *result_dev, hipStream_t s);  // *result = sum(in)
 int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
+
+// ---- the device-resident solvers (cg.hip, pcg.hip, par.hip) ----------------------------------------------------------------------
+// The scalar block of a solve: it lives in device memory, the kernels of cg.hip advance it, the host copies it back once per batch.
+// (pcg.hip's PcgScalars has the same layout -- asserted there -- with r.z in the place of rr_prev.)
+template <typename T>
+struct CgScalars {
+    T rr, rr_prev, pap, alpha, beta;
+    uint32_t converged;
+    uint32_t active;
+    uint32_t entered;  // the current loop body was entered: its x update is due (set with alpha)
+    uint32_t pad_;
+    uint64_t iters;
+    uint64_t iter_max;
+    double tol;
+};
+size_t cg_scalars_bytes(int dtype);  // cg.hip
+// host view of a copy of the scalar block after a poll (cg.hip)
+void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t *iters, double *rr);
+
+// The loop of a single-matrix solve on stream s: up to iter_max bodies, body() enqueues one.  "active" drops on the device at the
+// stop (cg.hip), and bodies enqueued past it are no-ops there, so the host enqueues check_every bodies at a time and polls the
+// scalar block (d_sc, through the pinned h_sc) once per batch.  With more than one batch to go the batch is captured ONCE into a
+// hipGraph and replayed, always whole: for small systems the loop is launch-bound.  If the capture does not come about the bodies
+// are launched one by one.  *converged, *iters, *rr: the block as the last poll saw it.
+template <typename Body>
+int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_every, Body &&body, const void *d_sc, void *h_sc, int *converged,
+                     size_t *iters, double *rr) {
+    Graph graph;
+    GraphExec exec;
+    if (iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        int crc = SMH_OK;
+        for (size_t i = 0; i < check_every && crc == SMH_OK; ++i) crc = body();
+        const hipError_t ce = graph.end_capture(s);  // (also after a body that failed: the stream must leave capture mode)
+        if (crc != SMH_OK || ce != hipSuccess || !graph.get() || exec.instantiate(graph.get()) != hipSuccess)
+            (void)hipGetLastError();  // exec is empty: plain stream launches instead
+    } else {
+        (void)hipGetLastError();
+    }
+    auto poll = [&]() -> int {
+        SMH_HIP(hipMemcpyAsync(h_sc, d_sc, cg_scalars_bytes(dtype), hipMemcpyDeviceToHost, s));
+        SMH_HIP(hipStreamSynchronize(s));
+        uint64_t it64 = 0;
+        cg_read_scalars(dtype, h_sc, converged, &it64, rr);
+        *iters = (size_t)it64;
+        return SMH_OK;
+    };
+    auto run = [&]() -> int {
+        size_t launched = 0;
+        while (launched < iter_max) {
+            size_t batch = iter_max - launched < check_every ? iter_max - launched : check_every;
+            if (exec.get()) {
+                SMH_HIP(hipGraphLaunch(exec.get(), s));
+                batch = check_every;
+            } else {
+                for (size_t i = 0; i < batch; ++i) SMH_TRY(body());
+            }
+            launched += batch;
+            SMH_TRY(poll());
+            if (*converged) break;
+        }
+        if (iter_max == 0) SMH_TRY(poll());
+        return SMH_OK;
+    };
+    const int rc = run();
+    if (rc != SMH_OK) (void)hipStreamSynchronize(s);  // a replayed batch may still run: it ends before its graph goes
+    return rc;
+}
 
 // ---- what a CRS handle derives lazily from its own arrays (built by capi.hip's ensure_* and spmv_tiled.hip's tiled_build) ----
 // Each form is filled in a local instance and move-assigned into the handle when it is complete; a default-constructed one is

@@ -45,8 +45,6 @@ using namespace smh;
 
 namespace smh {
 // cg.hip
-size_t cg_scalars_bytes(int dtype);
-void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t *iters, double *rr);
 int cg_fold(int dtype, const void *partials, uint32_t count, void *out, hipStream_t s);
 int cg_par_init(int dtype, void *sc, double tol, size_t iter_max, hipStream_t s);
 int cg_par_set_rr(int dtype, void *sc, const void *vals, uint32_t nb, hipStream_t s);

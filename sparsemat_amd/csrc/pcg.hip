@@ -12,7 +12,7 @@
 // (p, x, r, d in; p, x out): 10 n values per iteration beside the SpMV (the plain CG moves 8 n; the two reads of d are
 // what the preconditioner costs), p.Ap out of the SpMV epilogue when the kernel offers it.  All scalars (r.r, r.z, p.Ap,
 // alpha, beta, the stop flag, the iteration count) live in device memory as in cg.hip: the host replays a hipGraph of 8
-// bodies and polls one small block per batch -- no synchronisation inside an iteration.
+// bodies and polls one small block per batch (solve_in_batches, internal.hpp: CG's loop) -- no synchronisation inside an iteration.
 // Reductions: fixed grid, per-thread strided sums, wave butterfly, LDS across waves, one block folds the partials in
 // index order -- deterministic.
 #include "internal.hpp"
@@ -78,6 +78,12 @@ struct PcgScalars {
     uint64_t iter_max;
     double tol;
 };
+// the host polls this block through CG's reader (cg_read_scalars): the two layouts agree in size and in what the host reads
+template <typename T> constexpr bool pcg_scalars_like_cg() {
+    return sizeof(PcgScalars<T>) == sizeof(CgScalars<T>) && offsetof(PcgScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
+           offsetof(PcgScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(PcgScalars<T>, iters) == offsetof(CgScalars<T>, iters);
+}
+static_assert(pcg_scalars_like_cg<float>() && pcg_scalars_like_cg<double>(), "PcgScalars and CgScalars have drifted apart");
 
 template <typename T>
 __global__ void k_pcg_init(PcgScalars<T> *sc, double tol, uint64_t iter_max) {
@@ -248,31 +254,32 @@ unsigned pcg_grid(size_t n) {
 template <typename T>
 int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
-    hipStream_t s = nullptr;
-    T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_d = nullptr, *d_part = nullptr, *d_dot = nullptr;
-    PcgScalars<T> *d_sc = nullptr, *h_sc = nullptr;
-    unsigned long long *d_bad = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    Stream own;  // the solve runs on a stream of its own
+    Scratch ws;
+    PinnedBuf h_sc;
+    int converged = 0;
     size_t iters = 0;
     double rr = 0.0;
     const unsigned grid = pcg_grid(n);
     auto go = [&]() -> int {
-        SMH_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        const size_t vb = (n ? n : 1) * sizeof(T);
-        SMH_HIP(hipMalloc((void **)&d_x, vb)); SMH_HIP(hipMalloc((void **)&d_r, vb)); SMH_HIP(hipMalloc((void **)&d_p, vb));
-        SMH_HIP(hipMalloc((void **)&d_ap, vb)); SMH_HIP(hipMalloc((void **)&d_d, vb));
-        SMH_HIP(hipMalloc((void **)&d_part, (2 * (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8) * sizeof(T)));
-        SMH_HIP(hipMalloc((void **)&d_sc, sizeof(PcgScalars<T>)));
-        SMH_HIP(hipMalloc((void **)&d_bad, sizeof(unsigned long long)));
-        SMH_HIP(hipHostMalloc((void **)&h_sc, sizeof(PcgScalars<T>), hipHostMallocDefault));
+        SMH_TRY(own.create());
+        const hipStream_t s = own.get();
+        T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_d = nullptr, *d_part = nullptr, *d_dot = nullptr;
+        PcgScalars<T> *d_sc = nullptr;
+        unsigned long long *d_bad = nullptr;
+        SMH_TRY(ws.alloc(&d_x, n)); SMH_TRY(ws.alloc(&d_r, n)); SMH_TRY(ws.alloc(&d_p, n));
+        SMH_TRY(ws.alloc(&d_ap, n)); SMH_TRY(ws.alloc(&d_d, n));
+        SMH_TRY(ws.alloc(&d_part, 2 * (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
+        SMH_TRY(ws.alloc(&d_sc, 1));
+        SMH_TRY(ws.alloc(&d_bad, 1));
+        SMH_TRY(h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
         T *part_rr = d_part, *part_rz = d_part + kPcgBlocks, *dot_scratch = d_part + 2 * kPcgBlocks, *fold_scratch = dot_scratch + kReducePartials + 8;
         // p.Ap: out of the SpMV epilogue when the kernel offers it (K1s), else a separate two-stage dot
         const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
-        if (n_dot) SMH_HIP(hipMalloc((void **)&d_dot, n_dot * sizeof(T)));
+        if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
         const uint32_t *off = m->d_off, *col = m->d_col;
         const void *val = m->d_val;
-        SMH_HIP(hipStreamSynchronize(m->stream));
+        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
         // diag(A); a zero diagonal cannot be divided by
         unsigned long long bad = ~0ull;
         SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
@@ -313,55 +320,15 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        // batches of check_every bodies, captured once into a hipGraph and replayed (bodies past the stop are no-ops on the
-        // device); the host polls the scalar block once per batch
-        const size_t check_every = 8;
-        if (iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            int crc = SMH_OK;
-            for (size_t i = 0; i < check_every && crc == SMH_OK; ++i) crc = body();
-            const hipError_t ce = hipStreamEndCapture(s, &graph);
-            if (crc != SMH_OK || ce != hipSuccess || !graph || hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-                graph_exec = nullptr;  // plain stream launches instead
-                (void)hipGetLastError();
-            }
-        } else {
-            (void)hipGetLastError();
-        }
-        size_t launched = 0;
-        bool converged = false;
-        auto poll = [&]() -> int {
-            SMH_HIP(hipMemcpyAsync(h_sc, d_sc, sizeof(PcgScalars<T>), hipMemcpyDeviceToHost, s));
-            SMH_HIP(hipStreamSynchronize(s));
-            converged = h_sc->converged != 0;
-            iters = (size_t)h_sc->iters;
-            rr = (double)h_sc->rr;
-            return SMH_OK;
-        };
-        while (launched < iter_max) {
-            size_t batch = iter_max - launched < check_every ? iter_max - launched : check_every;
-            if (graph_exec) {
-                SMH_HIP(hipGraphLaunch(graph_exec, s));
-                batch = check_every;
-            } else {
-                for (size_t i = 0; i < batch; ++i) SMH_TRY(body());
-            }
-            launched += batch;
-            SMH_TRY(poll());
-            if (converged) break;
-        }
-        if (iter_max == 0) SMH_TRY(poll());
+        SMH_TRY(solve_in_batches(dt, s, iter_max, 8, body, d_sc, h_sc.get(), &converged, &iters, &rr));
         if (n) SMH_HIP(hipMemcpyAsync(x_host, d_x, n * sizeof(T), hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
     };
+    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
+    // the solve failed half way
     const int rc = keep_error(go(), [&] {
-        if (s) (void)hipStreamSynchronize(s);
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (s) (void)hipStreamDestroy(s);
-        (void)hipFree(d_x); (void)hipFree(d_r); (void)hipFree(d_p); (void)hipFree(d_ap); (void)hipFree(d_d); (void)hipFree(d_part);
-        (void)hipFree(d_dot); (void)hipFree(d_sc); (void)hipFree(d_bad);
-        if (h_sc) (void)hipHostFree(h_sc);
+        if (own.get()) (void)hipStreamSynchronize(own.get());
         (void)hipGetLastError();
     });
     if (rc != SMH_OK) return rc;

@@ -1,9 +1,10 @@
 """Handle lifetime: every lazily built workspace (merge table, ring plans incl. the wide and the banded ring, 16-bit
 column arrays, K1s windows and codes, K2c / K2f / K2s / K2t copies, assembly scratch) is released with its handle -- also
 after it was dropped and built again inside the handle's life (sort_rows, update_values, scale, another block width) -- and so is every
-array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay), and every
-block, stream, vector and solver workspace of a partitioned matrix (SparseMatParLocal, ParVec) -- device memory in use returns to
-where it started after many create / use / destroy rounds."""
+array the matrix operations build (transpose, prod, column_info, clone, add / sub, apply, get_many, eye, replay), every
+block, stream, vector and solver workspace of a partitioned matrix (SparseMatParLocal, ParVec), and every workspace of the
+single-matrix solvers (ConjugateGradient, JacobiConjugateGradient), also of a solve that fails half way -- device memory in use
+returns to where it started after many create / use / destroy rounds."""
 import gc
 import os
 
@@ -13,6 +14,7 @@ import torch
 
 import oracle
 import sparsemat_amd as sm
+from sparsemat_amd import _lib
 from util import assert_spmv_close, random_crs
 
 pytestmark = pytest.mark.gpu
@@ -192,6 +194,40 @@ def _exercise_par(rng, dtype):
     return out
 
 
+def _exercise_solvers(rng, dtype, out):
+    """The single-matrix solvers on the same stencil and right-hand side (every vector of theirs is a pooled block): replayed
+    batches, plain launches, a solve that fails after its workspaces exist, calls that fail before anything is allocated."""
+    off, col, val = _stencil(dtype)
+    n = PAR_GRID ** 3
+    b = out["b"]
+    a = sm.SparseMatCRS.from_raw_parts(n, n, off, col, val)
+    cg = sm.ConjugateGradient(0.0, PAR_ITERS)  # 4 bodies per poll: two replayed batches
+    out["cg_single"] = cg.solve(a, b, np.zeros(n, dtype))
+    assert cg.iterations == PAR_ITERS
+    bv, xv = sm.DenseVec.from_vec(b), sm.DenseVec.zeros(n, dtype)
+    cg = sm.ConjugateGradient(0.0, PAR_ITERS, check_every=7)  # more bodies per poll than there are: plain launches
+    cg.solve(a, bv, xv)
+    assert cg.iterations == PAR_ITERS
+    out["cg_single_vec"] = xv.to_numpy()
+    pcg = sm.JacobiConjugateGradient(0.0, 9)  # a replayed batch of 8 and one more
+    pcg.solve(a, b, np.zeros(n, dtype))
+    assert pcg.iterations == 9
+    # a zero on the diagonal: found when the vectors, the scalar blocks and the stream of the solve exist
+    nd = 300_000
+    row = int(rng.integers(0, nd))
+    dval = np.ones(nd, np.float32)
+    dval[row] = 0
+    d = sm.SparseMatCRS.from_raw_parts(nd, nd, np.arange(nd + 1, dtype=np.uint32), np.arange(nd, dtype=np.uint32), dval)
+    with pytest.raises(sm.SparseMatPanic) as e:
+        sm.JacobiConjugateGradient().solve(d, np.ones(nd, np.float32), np.zeros(nd, np.float32))
+    assert str(e.value) == "Jacobi preconditioner: zero or absent diagonal entry in row %d" % row
+    for solver in (sm.ConjugateGradient(), sm.JacobiConjugateGradient()):
+        with pytest.raises(sm.SparseMatPanic) as e:   # linearsolver.rs:33-36
+            solver.solve(a, b[:-1], np.zeros(n, dtype))
+        assert e.value.status == _lib.SMH_ERR_DIM_MISMATCH and "Matrix and vector size mismatch" in str(e.value)
+    del e, a, d, bv, xv
+
+
 def _check_par(dtype, out):
     """The last round's products and iterates against the oracle: the round did what it says."""
     off, col, val = _stencil(dtype)
@@ -207,9 +243,9 @@ def _check_par(dtype, out):
     want, iters, _ = oracle.cg(n, n, off, col, val, out["b"], np.zeros(n, dtype), tol=0.0, iter_max=PAR_ITERS)
     assert iters == PAR_ITERS
     bound = 8 * PAR_ITERS * 2 * np.sqrt(n) * np.finfo(dtype).eps * np.abs(want).max()
-    for name in ("cg", "cg_vec"):
+    for name in ("cg", "cg_vec", "cg_single", "cg_single_vec"):  # (partitioned; one matrix: the same recurrence, the same bound)
         err = np.abs(out[name].astype(np.float64) - want.astype(np.float64)).max()
-        print("partitioned %s, %s: max |x - x_oracle| = %.3e (bound %.3e)" % (name, np.dtype(dtype).name, err, bound))
+        print("%s, %s: max |x - x_oracle| = %.3e (bound %.3e)" % (name, np.dtype(dtype).name, err, bound))
         assert err <= bound, (name, err, bound)
 
 
@@ -217,7 +253,11 @@ def _round(rng):
     for kind in range(3):
         _exercise(rng, kind)
     _exercise_matrix_ops(rng)
-    return {dtype: _exercise_par(rng, dtype) for dtype in (np.float32, np.float64)}
+    last = {}
+    for dtype in (np.float32, np.float64):
+        last[dtype] = _exercise_par(rng, dtype)
+        _exercise_solvers(rng, dtype, last[dtype])
+    return last
 
 
 def test_no_device_memory_is_left_behind(gpu):
