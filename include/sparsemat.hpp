@@ -100,6 +100,52 @@ class DenseVec {
     smh_vec *h_ = nullptr;
 };
 
+// k DenseVecs of one dimension held against one matrix (smh_mvec): interleaved on the device, k vectors of n entries on the host.
+// The reference has no such type -- its mvp (sparsematrix.rs:146-158) is generic over the vector and called once per right-hand
+// side; SparseMatCRS::mvp_many gives the same k results, bit for bit, from one sweep over the matrix.  Move-only.
+template <typename T>
+class MultiVec {
+  public:
+    using Value = T;
+    MultiVec(size_t n, size_t k) { detail::check(smh_mvec_create(detail::dtype_of<T>::value, n, k, &h_)); }  // zeros
+    explicit MultiVec(const std::vector<std::vector<T>> &vecs) {
+        const size_t n = vecs.empty() ? 0 : vecs[0].size();
+        std::vector<T> flat;
+        flat.reserve(n * vecs.size());
+        for (const auto &v : vecs) {
+            if (v.size() != n) throw Panic(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+            flat.insert(flat.end(), v.begin(), v.end());
+        }
+        detail::check(smh_mvec_from_host(detail::dtype_of<T>::value, n, vecs.size(), flat.data(), &h_));
+    }
+    MultiVec(MultiVec &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    MultiVec &operator=(MultiVec &&o) noexcept { std::swap(h_, o.h_); return *this; }
+    MultiVec(const MultiVec &) = delete;
+    ~MultiVec() { smh_mvec_destroy(h_); }
+
+    size_t dim() const { return smh_mvec_dim(h_); }      // every vector's dim() (densevec.rs:36-38)
+    size_t count() const { return smh_mvec_count(h_); }  // k
+    std::vector<std::vector<T>> to_vecs() const {
+        const size_t n = dim(), k = count();
+        std::vector<T> flat(n * k);
+        detail::check(smh_mvec_download(h_, flat.data()));
+        std::vector<std::vector<T>> out(k);
+        for (size_t c = 0; c < k; ++c) out[c].assign(flat.begin() + c * n, flat.begin() + (c + 1) * n);
+        return out;
+    }
+    DenseVec<T> column(size_t c) const {
+        DenseVec<T> v(dim());
+        detail::check(smh_mvec_get_column(h_, c, v.handle()));
+        return v;
+    }
+    void set_column(size_t c, const DenseVec<T> &v) { detail::check(smh_mvec_set_column(h_, c, v.handle())); }
+
+    smh_mvec *handle() const { return h_; }
+
+  private:
+    smh_mvec *h_ = nullptr;
+};
+
 template <typename T> class SparseMatCRS;
 
 // A reusable update plan (smh_update_plan): the targets and the sorted order of one (rows, cols, ops) stream on one SparseMatCRS,
@@ -178,6 +224,12 @@ class SparseMatCRS {
         std::vector<T> y(n_rows());
         detail::check(smh_crs_spmv(h_, rhs.data(), rhs.size(), y.data(), variant));
         return y;
+    }
+    // mvp for every vector of rhs in one sweep over the matrix (smh_crs_spmv_many): column c is bit for bit mvp(rhs.column(c), SMH_SPMV_SEQ)
+    MultiVec<T> mvp_many(const MultiVec<T> &rhs) const {
+        MultiVec<T> ret(n_rows(), rhs.count());
+        detail::check(smh_crs_spmv_many(h_, rhs.handle(), ret.handle()));
+        return ret;
     }
     // SparseMatrix::inner_prod (sparsematrix.rs:161-171): lhs^T A rhs
     T inner_prod(const DenseVec<T> &lhs, const DenseVec<T> &rhs) const {

@@ -87,6 +87,7 @@ typedef enum {
 
 typedef struct smh_crs smh_crs; /* device-resident SparseMatCRS<T,u32>  (sparsemat_crs.rs:9-17) */
 typedef struct smh_vec smh_vec; /* device-resident DenseVec<T>          (densevec.rs:5-7)      */
+typedef struct smh_mvec smh_mvec; /* k device-resident DenseVec<T>s of one dimension, interleaved */
 
 /* ---- library / device --------------------------------------------------------------- */
 int smh_abi_version(void);
@@ -503,6 +504,44 @@ int smh_blas_xpby_dev(smh_dtype dtype, void *p_dev, const void *b_dev, const voi
 int smh_crs_spmv_vec(smh_crs *m, const smh_vec *x, smh_vec *y, int variant);
 /* SparseMatrix::inner_prod on device vectors (sparsematrix.rs:161-171) */
 int smh_crs_inner_prod_vec(smh_crs *m, const smh_vec *lhs, const smh_vec *rhs, int variant, double *out);
+
+/* ---- k DenseVec<T>s of one dimension, held against one matrix ---------------------------------
+ * The reference has no such type: its SparseMatrix::mvp (sparsematrix.rs:146-158) is generic over the vector and is
+ * simply called once per right-hand side.  smh_mvec holds k vectors of dimension n (each what a DenseVec is,
+ * densevec.rs:5-7) INTERLEAVED on the device: element i of vector c at data[i * ld + c], ld = k rounded up to a
+ * multiple of 4; the padding columns are zero and stay zero.  `host` is always k vectors of n entries, one after the
+ * other (k DenseVecs' iter(), densevec.rs:20-22, collected back to back); both transpositions run on the device.
+ * k == 0, a bad dtype or n * ld * sizeof(T) overflowing is SMH_ERR_INVALID, reported before the device is asked for. */
+int smh_mvec_create(smh_dtype dtype, size_t n, size_t k, smh_mvec **out);      /* zeros (Vector::with_capacity, densevec.rs:24-29, k times) */
+int smh_mvec_from_host(smh_dtype dtype, size_t n, size_t k, const void *host, smh_mvec **out); /* from_vec (:31-34), k times */
+int smh_mvec_upload(smh_mvec *mv, const void *host);
+int smh_mvec_download(const smh_mvec *mv, void *host);
+int smh_mvec_destroy(smh_mvec *mv);
+size_t smh_mvec_dim(const smh_mvec *mv);   /* n: every vector's dim() (densevec.rs:36-38) */
+size_t smh_mvec_count(const smh_mvec *mv); /* k */
+size_t smh_mvec_ld(const smh_mvec *mv);    /* 4 * ceil(k / 4) */
+int smh_mvec_dtype(const smh_mvec *mv);
+void *smh_mvec_data(const smh_mvec *mv);   /* device pointer: n * ld elements, 16-byte aligned */
+/* Column c <-> a DenseVec (clone(), densevec.rs:9 derive, of one vector): SMH_ERR_DIM_MISMATCH when v.dim() != n,
+ * SMH_ERR_INVALID for c >= k or a dtype mismatch. */
+int smh_mvec_set_column(smh_mvec *mv, size_t c, const smh_vec *v);
+int smh_mvec_get_column(const smh_mvec *mv, size_t c, smh_vec *v);
+
+/* SparseMatrix::mvp (sparsematrix.rs:146-158) for k right-hand sides in ONE sweep over the matrix (kernel K1m): for every
+ * c < k, column c of y is bit for bit what smh_crs_spmv(m, x_c, ..., SMH_SPMV_SEQ) returns -- each product rounded, then added
+ * in storage order from T(0), no FMA contraction; empty rows give +0 -- for any matrix the handle can hold and every k >= 1.
+ * Padding columns of y are written as +0 whatever the data.  The kernel reads the handle's column and value arrays directly
+ * (no derived form): smh_crs_update_values, smh_crs_scale and values written in place into borrowed arrays
+ * (smh_crs_create_dev) take effect with the next product and need no refresh.
+ * Statuses, all decided on the host before any launch: SMH_ERR_INVALID (k == 0, a dtype that is not the matrix's, x and y the
+ * same storage, a device pointer that is not 16-byte aligned, ld < k or not a multiple of 4, n * ld * sizeof(T) overflowing);
+ * SMH_ERR_INDEX_RANGE (a column index >= x.dim(): the reference panics in densevec.rs:41); SMH_ERR_DIM_MISMATCH (y.dim() !=
+ * n_rows or y.count() != x.count()).
+ * _dev: asynchronous on `stream`, raw interleaved device pointers (x: x_len * ld elements, y: n_rows * ld), no allocation and
+ * no synchronisation.  _host: x_host is k x x_len and y_host k x n_rows in the host format above. */
+int smh_crs_spmv_many(smh_crs *m, const smh_mvec *x, smh_mvec *y);
+int smh_crs_spmv_many_dev(smh_crs *m, const void *x_dev, size_t x_len, void *y_dev, size_t k, size_t ld, void *stream);
+int smh_crs_spmv_many_host(smh_crs *m, const void *x_host, size_t x_len, size_t k, void *y_host);
 
 /* ---- ConjugateGradient::solve (linearsolver.rs:27-61) -----------------------------------
  * Device-resident: SpMV + fused updates + reductions, scalars (alpha, beta, r.r) stay in

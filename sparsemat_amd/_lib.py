@@ -126,6 +126,21 @@ SIGNATURES = {
     "smh_crs_spmv_vec": (_int, [_vp, _vp, _vp, _int]),
     "smh_crs_inner_prod": (_int, [_vp, _vp, _sz, _vp, _sz, _int, C.POINTER(C.c_double)]),
     "smh_crs_inner_prod_vec": (_int, [_vp, _vp, _vp, _int, C.POINTER(C.c_double)]),
+    "smh_mvec_create": (_int, [_int, _sz, _sz, C.POINTER(_vp)]),
+    "smh_mvec_from_host": (_int, [_int, _sz, _sz, _vp, C.POINTER(_vp)]),
+    "smh_mvec_upload": (_int, [_vp, _vp]),
+    "smh_mvec_download": (_int, [_vp, _vp]),
+    "smh_mvec_destroy": (_int, [_vp]),
+    "smh_mvec_dim": (_sz, [_vp]),
+    "smh_mvec_count": (_sz, [_vp]),
+    "smh_mvec_ld": (_sz, [_vp]),
+    "smh_mvec_dtype": (_int, [_vp]),
+    "smh_mvec_data": (_vp, [_vp]),
+    "smh_mvec_set_column": (_int, [_vp, _sz, _vp]),
+    "smh_mvec_get_column": (_int, [_vp, _sz, _vp]),
+    "smh_crs_spmv_many": (_int, [_vp, _vp, _vp]),
+    "smh_crs_spmv_many_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
+    "smh_crs_spmv_many_host": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "smh_cg_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                             C.POINTER(C.c_double)]),
     "smh_cg_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),

@@ -318,6 +318,7 @@ constexpr int kStreamRows = kBlock;    // K1s: rows per tile (one thread folds o
 constexpr int kStreamCap = 4096;       // K1s: entries of a tile staged in LDS
 constexpr int kStreamCapSmall = 2045;  // K1s: ... when no tile holds more (two 16-byte chunks per thread from an aligned start)
 constexpr int kStreamCodeWidth = 16384;  // K1s 16-bit column codes: columns per interval (14 bits) x 4 intervals
+constexpr int kManyCap = 2048;         // K1m: entries of a pass, per plane of the LDS product stage (KT = 8 on f64: half of it)
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
 // in-place exclusive scan of n u32 on the device; *total_out (optional) = their sum (spmv_colblock.hip)
@@ -351,6 +352,10 @@ int launch_stream_windows(const uint32_t *off, const uint32_t *col, size_t n_row
                           uint32_t *d_count, hipStream_t s);
 int launch_stream_codes(const uint32_t *off, const uint32_t *col, const uint32_t *win, size_t n_rows, uint16_t *code,
                         hipStream_t s);
+// K1m (spmv_many.hip): Y = A X on interleaved multi-vectors (element i of vector c at [i * ld + c]; ld a multiple of 4, 16-byte aligned
+// pointers, x != y: checked by the caller, mvec.hip); ceil(ld / KT) sweeps, columns at and beyond k are stored as +0
+int launch_spmv_many(int dtype, const uint32_t *off, const uint32_t *col, const void *val, const void *x, void *y, size_t n_rows, size_t nnz,
+                     bool padded, size_t k, size_t ld, hipStream_t s);
 // K1s XD (spmv_stream_xd.hip): the code array as byte offsets into the tile's LDS stage of x, an unskewed product stage
 int launch_spmv_stream_xd(int dtype, const void *val, const void *x, void *y, size_t n_rows, void *dot_partials, const uint16_t *scode,
                           const uint32_t *cwin, const uint8_t *len8, const uint32_t *tbase, const void *dot_lhs, hipStream_t s, int xs,
@@ -761,6 +766,15 @@ struct smh_vec {
     size_t n = 0;
     void *d = nullptr;
     bool owns = true;
+};
+
+// k vectors of dimension n, interleaved: element i of vector c at d[i * ld + c]; ld = k rounded up to a multiple of 4, the padding
+// columns are zero and stay zero (mvec.hip).  The storage frees itself with the handle.
+struct smh_mvec {
+    int dtype = SMH_F32;
+    int device = 0;
+    size_t n = 0, k = 0, ld = 0;
+    smh::DevArray<char> d;
 };
 
 // ---- every .hip file of the library but pool.hip allocates device memory through the pool (declared at the top) ----------

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .densevec import DenseVec
+from .multivec import MultiVec, pack_host
 
 
 def _index(i):
@@ -559,6 +560,24 @@ class SparseMatCRS:
         check(lib().smh_crs_spmv(self._h, x.ctypes.data if x.size else None, x.size,
                                  y.ctypes.data if y.size else None, var))
         return y
+
+    def mvp_many(self, rhs):
+        """Y = A.X for k right-hand sides in one sweep over the matrix (``smh_crs_spmv_many``): column c of the result is bit for bit
+        ``mvp(x_c, variant="seq")``.  A MultiVec (device resident) gives a NEW MultiVec; a 2-D array-like of shape (k, x_len) gives a
+        numpy array of shape (k, n_rows)."""
+        if isinstance(rhs, MultiVec):
+            ret = MultiVec.zeros(self.n_rows(), rhs.count(), self._dtype)
+            check(lib().smh_crs_spmv_many(self._h, rhs._h, ret._h))
+            return ret
+        x = pack_host(rhs, self._dtype)
+        y = np.zeros((x.shape[0], self.n_rows()), dtype=self._dtype)
+        check(lib().smh_crs_spmv_many_host(self._h, x.ctypes.data if x.size else None, x.shape[1], x.shape[0],
+                                           y.ctypes.data if y.size else None))
+        return y
+
+    def mvp_many_dev(self, x_ptr, x_len, y_ptr, k, ld, stream=None):
+        """Asynchronous Y = A.X on raw interleaved device pointers (16-byte aligned; ``ld`` a multiple of 4, at least ``k``)."""
+        check(lib().smh_crs_spmv_many_dev(self._h, C.c_void_p(x_ptr), x_len, C.c_void_p(y_ptr), k, ld, C.c_void_p(stream or 0)))
 
     def __mul__(self, rhs):
         """``A * v`` (sparsematrix.rs:435-443): mvp; ``A * s`` for a scalar s (Mul<T>, :422-432): a scaled clone."""
