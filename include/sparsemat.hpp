@@ -140,6 +140,30 @@ class MultiVec {
     }
     void set_column(size_t c, const DenseVec<T> &v) { detail::check(smh_mvec_set_column(h_, c, v.handle())); }
 
+    // the per-column BLAS-1 (densevec.rs:51-73, vector.rs:50-58, k times): in place, one rounding per operation; dot and
+    // norm_squared give one f64 per column, each summed in a fixed order that depends on dim() alone
+    MultiVec copy() const {  // clone() (densevec.rs:9 derive)
+        MultiVec ret(dim(), count());
+        detail::check(smh_mvec_copy(ret.h_, h_));
+        return ret;
+    }
+    void add(const MultiVec &o) { detail::check(smh_mvec_add(h_, o.h_)); }
+    void sub(const MultiVec &o) { detail::check(smh_mvec_sub(h_, o.h_)); }
+    void scale(const std::vector<double> &factors) {  // column c times T(factors[c])
+        if (factors.size() != count()) throw Panic(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+        detail::check(smh_mvec_scale(h_, factors.data()));
+    }
+    std::vector<double> dot(const MultiVec &o) const {
+        std::vector<double> out(count());
+        detail::check(smh_mvec_dot(h_, o.h_, out.data()));
+        return out;
+    }
+    std::vector<double> norm_squared() const {
+        std::vector<double> out(count());
+        detail::check(smh_mvec_norm_squared(h_, out.data()));
+        return out;
+    }
+
     smh_mvec *handle() const { return h_; }
 
   private:
@@ -518,14 +542,29 @@ class ConjugateGradient {
         detail::check(smh_par_cg_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO,
                                        &iterations_, &r_norm_squared_));
     }
+    // solve on the k columns of b and x at once (smh_cg_solve_many): column c is solve(mat, b_c, x_c) with its own alpha, beta,
+    // stop test and iteration count; all columns share one sweep over the matrix per body.  Same panics as solve.
+    template <typename T>
+    void solve_many(const SparseMatCRS<T> &mat, const MultiVec<T> &b, MultiVec<T> &x) {
+        std::vector<size_t> iters(b.count());
+        std::vector<double> rr(b.count());
+        detail::check(smh_cg_solve_many(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, 0, iters.data(), rr.data()));
+        iterations_many_ = std::move(iters);
+        r_norm_squared_many_ = std::move(rr);
+    }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }
+    // ... of the last solve_many, per column
+    const std::vector<size_t> &iterations_many() const { return iterations_many_; }
+    const std::vector<double> &r_norm_squared_many() const { return r_norm_squared_many_; }
 
   private:
     double tol_ = 1e-12;
     size_t iter_max_ = 10000;
     size_t iterations_ = 0;
     double r_norm_squared_ = 0.0;
+    std::vector<size_t> iterations_many_;
+    std::vector<double> r_norm_squared_many_;
 };
 
 }  // namespace sparsemat

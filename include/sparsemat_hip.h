@@ -526,6 +526,18 @@ void *smh_mvec_data(const smh_mvec *mv);   /* device pointer: n * ld elements, 1
  * SMH_ERR_INVALID for c >= k or a dtype mismatch. */
 int smh_mvec_set_column(smh_mvec *mv, size_t c, const smh_vec *v);
 int smh_mvec_get_column(const smh_mvec *mv, size_t c, smh_vec *v);
+/* The per-column BLAS-1 of k DenseVecs: every element-wise operation rounds once; the padding columns stay +0 whatever the
+ * data (scale keeps them by selection: an infinite or NaN factor does not reach them).  `a` and `out` are host arrays of k
+ * entries; scale multiplies column c by T(a[c]).  dot and norm_squared sum column c in a fixed tree whose order depends on
+ * n alone -- not on k, on c or on the other columns -- and return T widened to f64.
+ * Statuses, all decided on the host before any launch: SMH_ERR_DIM_MISMATCH when dim() or count() differ, SMH_ERR_INVALID for
+ * a dtype mismatch or a NULL factor / output array. */
+int smh_mvec_copy(smh_mvec *dst, const smh_mvec *src);
+int smh_mvec_add(smh_mvec *x, const smh_mvec *y);                             /* x_c += y_c  (densevec.rs:51-58, k times) */
+int smh_mvec_sub(smh_mvec *x, const smh_mvec *y);                             /* x_c -= y_c  (:60-67) */
+int smh_mvec_scale(smh_mvec *x, const double *a);                             /* x_c *= T(a[c])  (:69-73) */
+int smh_mvec_dot(const smh_mvec *x, const smh_mvec *y, double *out);          /* vector.rs:50-53 per column */
+int smh_mvec_norm_squared(const smh_mvec *x, double *out);                    /* :56-58 */
 
 /* SparseMatrix::mvp (sparsematrix.rs:146-158) for k right-hand sides in ONE sweep over the matrix (kernel K1m): for every
  * c < k, column c of y is bit for bit what smh_crs_spmv(m, x_c, ..., SMH_SPMV_SEQ) returns -- each product rounded, then added
@@ -556,6 +568,19 @@ int smh_cg_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inou
                  double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
 int smh_cg_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                      int variant, size_t check_every, size_t *iters_out, double *rr_out);
+/* ... on k right-hand sides at once (kernel K5m): for every c < k, column c of x is ConjugateGradient::solve(A, b_c, x_c) --
+ * its own alpha, beta, stop test and iteration count -- while all columns share one sweep over the matrix per body
+ * (smh_crs_spmv_many) and fused multi-vector updates.  A column that has stopped (converged, or iter_max bodies entered) keeps
+ * the bits of its stopping body; the solve ends when no column is active; no value of one column reaches another (b_c = 0
+ * runs its 0 / 0 recurrence to iter_max like the reference and leaves its neighbours alone).  x: in x0, out the solution.
+ * iters_out[c] = bodies column c entered, rr_out[c] = its last r.r as f64 (k entries each).  check_every: bodies per poll
+ * (0: default).  Statuses, all decided on the host before any launch: SMH_ERR_NOT_SQUARE, SMH_ERR_DIM_MISMATCH (b.dim() or
+ * x.dim() != n_rows, or the counts differ), SMH_ERR_INVALID (a dtype that is not the matrix's, b and x the same storage, NULL
+ * output arrays); those of smh_crs_spmv_many pass through.  _host: b_host and x_host_inout are k x n in the host format. */
+int smh_cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, size_t iter_max, size_t check_every,
+                      size_t *iters_out, double *rr_out);
+int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, void *x_host_inout, double tol,
+                           size_t iter_max, size_t *iters_out, double *rr_out);
 
 /* Jacobi-preconditioned CG -- an EXTENSION (the reference has no
  * preconditioner): the recurrence of ConjugateGradient::solve with z = r / diag(A), diag_i =

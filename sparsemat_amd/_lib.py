@@ -138,6 +138,12 @@ SIGNATURES = {
     "smh_mvec_data": (_vp, [_vp]),
     "smh_mvec_set_column": (_int, [_vp, _sz, _vp]),
     "smh_mvec_get_column": (_int, [_vp, _sz, _vp]),
+    "smh_mvec_copy": (_int, [_vp, _vp]),
+    "smh_mvec_add": (_int, [_vp, _vp]),
+    "smh_mvec_sub": (_int, [_vp, _vp]),
+    "smh_mvec_scale": (_int, [_vp, C.POINTER(C.c_double)]),
+    "smh_mvec_dot": (_int, [_vp, _vp, C.POINTER(C.c_double)]),
+    "smh_mvec_norm_squared": (_int, [_vp, C.POINTER(C.c_double)]),
     "smh_crs_spmv_many": (_int, [_vp, _vp, _vp]),
     "smh_crs_spmv_many_dev": (_int, [_vp, _vp, _sz, _vp, _sz, _sz, _vp]),
     "smh_crs_spmv_many_host": (_int, [_vp, _vp, _sz, _sz, _vp]),
@@ -145,6 +151,8 @@ SIGNATURES = {
                             C.POINTER(C.c_double)]),
     "smh_cg_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
                                 C.POINTER(C.c_double)]),
+    "smh_cg_solve_many": (_int, [_vp, _vp, _vp, C.c_double, _sz, _sz, C.POINTER(_sz), C.POINTER(C.c_double)]),
+    "smh_cg_solve_many_host": (_int, [_vp, _vp, _sz, _sz, _vp, C.c_double, _sz, C.POINTER(_sz), C.POINTER(C.c_double)]),
     "smh_pcg_jacobi_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                                     C.POINTER(C.c_double)]),
     "smh_comm_unique_id": (_int, [_vp]),

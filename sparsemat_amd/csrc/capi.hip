@@ -2298,6 +2298,37 @@ int smh_cg_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inou
     return rc;
 }
 
+// ... on k right-hand sides at once (K5m, cg_many.hip)
+int smh_cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, size_t iter_max, size_t check_every, size_t *iters_out,
+                      double *rr_out) {
+    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
+    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "multi-vector dtype differs from the matrix's");
+    if (b == x || b->d.get() == x->d.get()) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");           // :30-32
+    if (m->n_rows != b->n || m->n_rows != x->n || b->k != x->k)
+        return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");                            // :33-36
+    if (check_every == 0) check_every = 4;
+    return cg_solve_many(m, b, x, tol, iter_max, check_every, iters_out, rr_out);
+}
+
+int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, void *x_host_inout, double tol, size_t iter_max,
+                           size_t *iters_out, double *rr_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (m->n_rows != n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    smh_mvec *b = nullptr, *x = nullptr;
+    int rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, b_host, &b);
+    if (rc == SMH_OK) rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, x_host_inout, &x);
+    if (rc == SMH_OK) rc = smh_cg_solve_many(m, b, x, tol, iter_max, 0, iters_out, rr_out);
+    if (rc == SMH_OK && n) rc = smh_mvec_download(x, x_host_inout);
+    smh_mvec_destroy(b);
+    smh_mvec_destroy(x);
+    return rc;
+}
+
 // ---- synthetic workloads ---------------------------------------------------------------------------------
 int smh_synth_x(smh_dtype dtype, uint64_t seed, size_t begin, size_t n, void *x_dev, void *stream) {
     SMH_TRY(require_device());

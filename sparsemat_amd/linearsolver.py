@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 from .densevec import DenseVec
+from .multivec import MultiVec, pack_host
 
 
 class ConjugateGradient:
@@ -55,6 +56,31 @@ class ConjugateGradient:
                                      x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var,
                                      C.byref(iters), C.byref(rr)))
         self.iterations, self.r_norm_squared = iters.value, rr.value
+        return x
+
+    def solve_many(self, mat, b, x):
+        """``solve`` on k right-hand sides at once (``smh_cg_solve_many``): column c of x is ``solve(mat, b_c, x_c)`` with its
+        own alpha, beta, stop test and iteration count; all columns share one sweep over the matrix per body.  Two
+        ``MultiVec``s, or a ``(k, n)`` array-like b with a contiguous ``(k, n)`` numpy x of the matrix dtype; x is updated in
+        place.  Afterwards ``iterations`` is an integer array of k and ``r_norm_squared`` an f64 array of k.  Same panics
+        as ``solve``."""
+        if isinstance(b, MultiVec) and isinstance(x, MultiVec):
+            k = b.count()
+            iters, rr = np.zeros(max(k, 1), np.uintp), np.zeros(max(k, 1), np.float64)
+            check(lib().smh_cg_solve_many(mat._h, b._h, x._h, self.tol, self.iter_max, self.check_every,
+                                          iters.ctypes.data_as(C.POINTER(C.c_size_t)), rr.ctypes.data_as(C.POINTER(C.c_double))))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous and x.ndim == 2):
+                raise TypeError("x must be a contiguous (k, n) numpy array of the matrix dtype (updated in place)")
+            bb = pack_host(b, mat.dtype)
+            if bb.shape != x.shape:
+                raise _lib.SparseMatPanic(_lib.SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch")
+            k, n = x.shape
+            iters, rr = np.zeros(max(k, 1), np.uintp), np.zeros(max(k, 1), np.float64)
+            check(lib().smh_cg_solve_many_host(mat._h, bb.ctypes.data if bb.size else None, n, k, x.ctypes.data if x.size else None,
+                                               self.tol, self.iter_max, iters.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                               rr.ctypes.data_as(C.POINTER(C.c_double))))
+        self.iterations, self.r_norm_squared = iters[:k].astype(np.int64), rr[:k]
         return x
 
 

@@ -106,3 +106,35 @@ class MultiVec:
         if not isinstance(v, DenseVec):
             v = DenseVec.from_vec(v, self._dtype)
         check(lib().smh_mvec_set_column(self._h, c, v._h))
+
+    # ---- the per-column BLAS-1 (densevec.rs:51-73, vector.rs:50-58, k times): in place, one rounding per operation ----
+    def copy(self):
+        """A new MultiVec with the same vectors (clone(), densevec.rs:9 derive)."""
+        ret = MultiVec.zeros(self.dim(), self.count(), self._dtype)
+        check(lib().smh_mvec_copy(ret._h, self._h))
+        return ret
+
+    def add(self, other):
+        check(lib().smh_mvec_add(self._h, other._h))
+        return self
+
+    def sub(self, other):
+        check(lib().smh_mvec_sub(self._h, other._h))
+        return self
+
+    def scale(self, factors):
+        """Column c times ``factors[c]`` (k factors; a scalar scales every column)."""
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(factors, np.float64), (self.count(),)))
+        check(lib().smh_mvec_scale(self._h, a.ctypes.data_as(C.POINTER(C.c_double))))
+        return self
+
+    def dot(self, other):
+        """The k dot products of the columns, as a numpy f64 array (each summed in a fixed order that depends on dim() alone)."""
+        out = np.zeros(self.count(), np.float64)
+        check(lib().smh_mvec_dot(self._h, other._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def norm_squared(self):
+        out = np.zeros(self.count(), np.float64)
+        check(lib().smh_mvec_norm_squared(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
