@@ -567,4 +567,34 @@ class ConjugateGradient {
     std::vector<double> r_norm_squared_many_;
 };
 
+// BiCGSTAB for non-symmetric systems -- an extension, not in the reference (smh_bicgstab_solve*): device-resident like
+// ConjugateGradient, same panics and stop rule.  breakdown(): 0 none, 1 rho' == 0 or omega == 0, 2 r^.v == 0, 3 t.t == 0
+// (sparsemat_hip.h); a breakdown ends the solve without a panic.
+class BiCGStab {
+  public:
+    BiCGStab() = default;
+    BiCGStab(double tol, size_t iter_max) : tol_(tol), iter_max_(iter_max) {}
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_bicgstab_solve_vec(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0, &iterations_,
+                                             &r_norm_squared_, &breakdown_));
+    }
+    // host vectors, x updated in place
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_bicgstab_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO,
+                                         &iterations_, &r_norm_squared_, &breakdown_));
+    }
+    size_t iterations() const { return iterations_; }
+    double r_norm_squared() const { return r_norm_squared_; }
+    int breakdown() const { return breakdown_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t iter_max_ = 10000;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
+    int breakdown_ = 0;
+};
+
 }  // namespace sparsemat

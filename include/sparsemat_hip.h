@@ -591,6 +591,30 @@ int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_h
                          size_t x_len, double tol, size_t iter_max, int variant, size_t *iters_out,
                          double *rr_out);
 
+/* BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is
+ * the conjugate gradient).  Device-resident like smh_cg_solve: scalars in HBM, the stop decided on the device in every
+ * body and polled every `check_every` bodies (0: default, 8), bodies enqueued past the stop are no-ops, so x and all
+ * outputs are those of the stopping body.  One rounding per operation; the comparisons with zero are exact:
+ *   r = b - A x;  r^ = r;  p = r;  rho = r^.r;  rr = r.r          (no stop test before the first body)
+ *   body:  v = A p;  rv = r^.v;                  rv == 0: breakdown 2, stop (x untouched by this body)
+ *          alpha = rho / rv;  s = r - v*alpha;  ss = s.s
+ *                                                sqrt(f64(ss)) < tol: x += p*alpha; rr = ss; converged (half-step stop)
+ *          t = A s;  ts = t.s;  tt = t.t;        tt == 0: x += p*alpha; rr = ss; breakdown 3, stop
+ *          omega = ts / tt;  x = (x + p*alpha) + s*omega;  r = s - t*omega;  rr = r.r;  rho' = r^.r
+ *                                                sqrt(f64(rr)) < tol: converged
+ *                                                rho' == 0 or omega == 0: breakdown 1, stop (x keeps this body's update)
+ *          beta = (rho'/rho) * (alpha/omega);  rho = rho';  p = r + (p - v*omega)*beta
+ * A breakdown is not an error: the call returns SMH_OK and *breakdown_out holds 0 (none), 1, 2 or 3.  iters_out = bodies
+ * entered, rr_out = the last r.r (s.s after a half-step stop or breakdown 3) as f64; the output pointers may be NULL.
+ * Statuses, decided on the host before any launch: SMH_ERR_NOT_SQUARE, SMH_ERR_DIM_MISMATCH, SMH_ERR_INVALID (a NULL
+ * handle or vector, a vector dtype that is not the matrix's, b and x the same storage).  x: in x0, out the solution. */
+int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                       double tol, size_t iter_max, int variant,
+                       size_t *iters_out, double *rr_out, int *breakdown_out);
+int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                           int variant, size_t check_every,
+                           size_t *iters_out, double *rr_out, int *breakdown_out);
+
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;
  * integer division :21); block b = global rows [b R, (b+1) R) with local row ids and GLOBAL column

@@ -42,6 +42,14 @@ extern "C" {
     pub fn smh_pcg_jacobi_solve(m: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
                                 x_len: usize, tol: c_double, iter_max: usize, variant: c_int,
                                 iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    // extension (not in the reference): BiCGSTAB for non-symmetric systems; breakdown_out: 0 none, 1 rho' == 0 or
+    // omega == 0, 2 r^.v == 0, 3 t.t == 0 (a breakdown is a result: the status stays SMH_OK)
+    pub fn smh_bicgstab_solve(m: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                              x_len: usize, tol: c_double, iter_max: usize, variant: c_int,
+                              iters_out: *mut usize, rr_out: *mut c_double, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_bicgstab_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
+                                  variant: c_int, check_every: usize,
+                                  iters_out: *mut usize, rr_out: *mut c_double, breakdown_out: *mut c_int) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

@@ -79,6 +79,32 @@ impl DeviceCrs {
     }
 }
 
+/// BiCGSTAB for non-symmetric systems -- an extension, not in the reference (`smh_bicgstab_solve`): device-resident like
+/// `cg_solve`, same panics and stop rule.  Uncompiled like the rest of this shim.
+pub struct BiCGStab {
+    pub tol: f64,
+    pub iter_max: usize,
+}
+
+impl Default for BiCGStab {
+    fn default() -> Self {
+        BiCGStab { tol: 1e-12, iter_max: 10_000 }
+    }
+}
+
+impl BiCGStab {
+    /// `x` is updated in place; returns (bodies entered, last r.r, breakdown code: 0 none, 1 rho' == 0 or omega == 0,
+    /// 2 r^.v == 0, 3 t.t == 0).  A breakdown ends the solve without a panic.
+    pub fn solve<T: HipValue>(&self, mat: &DeviceCrs, b: &[T], x: &mut [T]) -> (usize, f64, i32) {
+        let (mut iters, mut rr, mut breakdown) = (0usize, 0f64, 0 as std::os::raw::c_int);
+        check(unsafe {
+            ffi::smh_bicgstab_solve(mat.handle, b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void,
+                                    x.len(), self.tol, self.iter_max, ffi::SMH_SPMV_AUTO, &mut iters, &mut rr, &mut breakdown)
+        });
+        (iters, rr, breakdown as i32)
+    }
+}
+
 impl DeviceCrs {
     /// `SparseMatrix::inner_prod` (src/sparsematrix.rs:161-171): lhs^T A rhs.
     pub fn inner_prod<T: HipValue>(&self, lhs: &[T], rhs: &[T]) -> f64 {

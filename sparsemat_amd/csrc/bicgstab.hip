@@ -1,0 +1,439 @@
+// bicgstab.hip -- BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems, gfx950.
+//
+// An EXTENSION: the reference's only solver is ConjugateGradient (linearsolver.rs:12-61), which needs a symmetric positive
+// definite matrix.  This is the stabilised bi-conjugate gradient recurrence in the family's conventions -- the guards of
+// linearsolver.rs:30-36, the stop rule sqrt(f64(r.r)) < tol tested before beta (:52-54), no stop test before the first body,
+// one rounding per operation (a - b*c is add(a, -mul(b, c)); nothing is contracted), products by the matrix's own kernel:
+//   r = b - A x;  r^ = r;  p = r;  rho = r^.r;  rr = r.r
+//   body:  v = A p;  rv = r^.v;                  rv == 0: breakdown 2, stop (x untouched by this body)
+//          alpha = rho / rv;  s = r - v*alpha;  ss = s.s
+//                                                sqrt(f64(ss)) < tol: x += p*alpha; rr = ss; converged ("half-step stop")
+//          t = A s;  ts = t.s;  tt = t.t;        tt == 0: x += p*alpha; rr = ss; breakdown 3, stop
+//          omega = ts / tt;  x = (x + p*alpha) + s*omega;  r = s - t*omega;  rr = r.r;  rho' = r^.r
+//                                                sqrt(f64(rr)) < tol: converged
+//                                                rho' == 0 or omega == 0: breakdown 1, stop (x keeps this body's update)
+//          beta = (rho'/rho) * (alpha/omega);  rho = rho';  p = r + (p - v*omega)*beta
+// The comparisons with zero are exact and NaN compares false, so non-finite data run to iter_max as they do in CG.
+//
+// Kernels: beside the two products a body is five sweeps -- partials of r^.v (2 n values); s and partials of s.s (3 n);
+// partials of t.s and t.t (2 n); x, r and partials of r.r and r^.r (7 n); p (4 n): 18 n values -- each followed (but the
+// last) by a one-workgroup kernel that folds the partials, takes the stage's decision and advances the scalars.  All scalars
+// live in device memory: a leading block in CgScalars' layout, which solve_in_batches (internal.hpp: CG's loop) polls once
+// per batch and whose `converged` word means STOPPED (a breakdown too), and a second block (rho, the dots, omega, the
+// breakdown code) that the host reads once after the loop.  Gate words: `active` (this body runs; dropped by the stage that
+// stops) gates every sweep after alpha; `xmode` tells the x / r sweep what is due (0 nothing, 1 x += p*alpha alone, 2 all).
+// Bodies enqueued past the stop are no-ops, so x, rr, iters and the code are the stopping body's wherever it falls in a batch.
+// Reductions: pcg.hip's tree everywhere -- a thread's strided run over 16-byte vectors and then its tail element, the
+// __shfl_down butterfly per wave, thread 0 over the four wave sums from the first one's, one workgroup over the partials the
+// same way -- deterministic, no float atomics.  One stream, one linear chain of launches.
+#include "internal.hpp"
+#include "solver_tree.hpp"
+
+#include <cmath>
+
+using namespace smh;
+
+namespace {
+
+// ---- device-resident scalars ---------------------------------------------------------------------------------------------
+// the block the host polls through CG's reader (cg_read_scalars): rr, the stop word and the body count sit where CG's do
+template <typename T>
+struct BiScalars {
+    T rr, alpha, beta, spare0_, spare1_;
+    uint32_t converged;  // STOPPED: converged, or a breakdown
+    uint32_t active;     // this body runs (not stopped, fewer than iter_max bodies entered, no stage of it has stopped yet)
+    uint32_t xmode;      // what this body's x / r sweep does: 0 nothing, 1 x += p*alpha, 2 x, r and the partials
+    uint32_t pad_;
+    uint64_t iters;
+    uint64_t iter_max;
+    double tol;
+};
+template <typename T> constexpr bool bi_scalars_like_cg() {
+    return sizeof(BiScalars<T>) == sizeof(CgScalars<T>) && offsetof(BiScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
+           offsetof(BiScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(BiScalars<T>, iters) == offsetof(CgScalars<T>, iters);
+}
+static_assert(bi_scalars_like_cg<float>() && bi_scalars_like_cg<double>(), "BiScalars and CgScalars have drifted apart");
+// the solver's further scalars: read by the host once, after the loop
+template <typename T>
+struct BiMore {
+    T rho, rv, ss, ts, tt, omega;
+    uint32_t breakdown;  // 0 none, 1 rho' == 0 or omega == 0, 2 r^.v == 0, 3 t.t == 0 (a stop with code 0 was a stop test's)
+    uint32_t pad_;
+};
+
+template <typename T>
+__global__ void k_bi_init(BiScalars<T> *sc, BiMore<T> *mo, double tol, uint64_t iter_max) {
+    sc->rr = sc->alpha = sc->beta = sc->spare0_ = sc->spare1_ = T(0);
+    sc->converged = sc->active = sc->xmode = sc->pad_ = 0;
+    sc->iters = 0;
+    sc->iter_max = iter_max;
+    sc->tol = tol;
+    mo->rho = mo->rv = mo->ss = mo->ts = mo->tt = mo->omega = T(0);
+    mo->breakdown = mo->pad_ = 0;
+}
+
+// one workgroup: the sums of part_a[0..n_parts) and part_b[0..n_parts) in out2[0], out2[1] (thread 0 writes, thread 0 reads)
+template <typename T>
+__device__ __forceinline__ void fold2(const T *__restrict__ part_a, const T *__restrict__ part_b, unsigned n_parts, T *out2) {
+    T a = T(0), b = T(0);
+    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) { a = p_add(a, part_a[k]); b = p_add(b, part_b[k]); }
+    block_sums(a, b, out2, out2 + 1);  // (one block: blockIdx.x == 0)
+}
+template <typename T>
+__device__ __forceinline__ T fold1(const T *__restrict__ part, unsigned n_parts) {
+    T a = T(0);
+    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
+    return block_sum1(a);  // (thread 0)
+}
+
+// ---- the sweeps: 16 bytes per lane and array (the workspaces are pool allocations: aligned), the last n % V elements one by one --
+#define BI_SWEEP_HEAD                                  \
+    constexpr int V = 16 / sizeof(T);                  \
+    typedef T VT __attribute__((ext_vector_type(V))); \
+    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x
+#define BI_LOAD(p, q) __builtin_nontemporal_load(reinterpret_cast<const VT *>(p) + (q))
+#define BI_STORE(v, p, q) __builtin_nontemporal_store((v), reinterpret_cast<VT *>(p) + (q))
+
+// partials of a.b (r^.v): runs when the body that follows will be entered
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_dot(const BiScalars<T> *__restrict__ sc, const T *__restrict__ a, const T *__restrict__ b, uint64_t n, T *__restrict__ part) {
+    if (sc->converged || sc->iters >= sc->iter_max) return;  // block-uniform
+    BI_SWEEP_HEAD;
+    T acc = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        const VT av = BI_LOAD(a, q), bv = BI_LOAD(b, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(av[e], bv[e]));
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) acc = p_add(acc, p_mul(a[i], b[i]));
+    const T t = block_sum1(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// partials of t.s and t.t in one sweep.  SETUP (t = s = r): the initial rho = r^.r and r.r, ungated
+template <typename T, bool SETUP>
+__global__ void __launch_bounds__(kBlock)
+k_bi_dot2(const BiScalars<T> *__restrict__ sc, const T *__restrict__ t, const T *__restrict__ s, uint64_t n, T *__restrict__ part_ts,
+          T *__restrict__ part_tt) {
+    if (!SETUP && !sc->active) return;
+    BI_SWEEP_HEAD;
+    T a_ts = T(0), a_tt = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        const VT tv = BI_LOAD(t, q), sv = BI_LOAD(s, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            a_ts = p_add(a_ts, p_mul(tv[e], sv[e]));
+            a_tt = p_add(a_tt, p_mul(tv[e], tv[e]));
+        }
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        const T ti = t[i];
+        a_ts = p_add(a_ts, p_mul(ti, s[i]));
+        a_tt = p_add(a_tt, p_mul(ti, ti));
+    }
+    block_sums(a_ts, a_tt, part_ts, part_tt);
+}
+
+// s = r - v*alpha; partials of s.s
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__restrict__ v, T *__restrict__ s, uint64_t n, T *__restrict__ part_ss) {
+    if (!sc->active) return;
+    const T alpha = sc->alpha;
+    BI_SWEEP_HEAD;
+    T acc = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT sv = BI_LOAD(r, q);
+        const VT vv = BI_LOAD(v, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            sv[e] = p_add(sv[e], -p_mul(vv[e], alpha));
+            acc = p_add(acc, p_mul(sv[e], sv[e]));
+        }
+        BI_STORE(sv, s, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        const T si = p_add(r[i], -p_mul(v[i], alpha));
+        s[i] = si;
+        acc = p_add(acc, p_mul(si, si));
+    }
+    const T t = block_sum1(acc);
+    if (threadIdx.x == 0) part_ss[blockIdx.x] = t;
+}
+
+// xmode 2: x = (x + p*alpha) + s*omega; r = s - t*omega; partials of r.r and r^.r.  xmode 1 (half-step stop, breakdown 3): x += p*alpha
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ x, const T *__restrict__ p, const T *__restrict__ s,
+        const T *__restrict__ t, const T *__restrict__ rhat, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr, T *__restrict__ part_rho) {
+    const uint32_t mode = sc->xmode;  // block-uniform
+    if (mode == 0) return;
+    const T alpha = sc->alpha;
+    BI_SWEEP_HEAD;
+    if (mode == 1) {
+        for (uint64_t q = tid; q < nv; q += nthreads) {
+            VT xv = BI_LOAD(x, q);
+            const VT pv = BI_LOAD(p, q);
+#pragma unroll
+            for (int e = 0; e < V; ++e) xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
+            BI_STORE(xv, x, q);
+        }
+        for (uint64_t i = nv * V + tid; i < n; i += nthreads) x[i] = p_add(x[i], p_mul(p[i], alpha));
+        return;
+    }
+    const T omega = mo->omega;
+    T a_rr = T(0), a_rho = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT xv = BI_LOAD(x, q);
+        const VT pv = BI_LOAD(p, q), sv = BI_LOAD(s, q), tv = BI_LOAD(t, q), hv = BI_LOAD(rhat, q);
+        VT rv;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            xv[e] = p_add(p_add(xv[e], p_mul(pv[e], alpha)), p_mul(sv[e], omega));
+            rv[e] = p_add(sv[e], -p_mul(tv[e], omega));
+            a_rr = p_add(a_rr, p_mul(rv[e], rv[e]));
+            a_rho = p_add(a_rho, p_mul(hv[e], rv[e]));
+        }
+        BI_STORE(xv, x, q);
+        BI_STORE(rv, r, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        const T si = s[i];
+        x[i] = p_add(p_add(x[i], p_mul(p[i], alpha)), p_mul(si, omega));
+        const T ri = p_add(si, -p_mul(t[i], omega));
+        r[i] = ri;
+        a_rr = p_add(a_rr, p_mul(ri, ri));
+        a_rho = p_add(a_rho, p_mul(rhat[i], ri));
+    }
+    block_sums(a_rr, a_rho, part_rr, part_rho);
+}
+
+// p = r + (p - v*omega)*beta
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ v, uint64_t n) {
+    if (!sc->active) return;
+    const T beta = sc->beta, omega = mo->omega;
+    BI_SWEEP_HEAD;
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT pv = BI_LOAD(p, q);
+        const VT rv = BI_LOAD(r, q), vv = BI_LOAD(v, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) pv[e] = p_add(rv[e], p_mul(p_add(pv[e], -p_mul(vv[e], omega)), beta));
+        BI_STORE(pv, p, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) p[i] = p_add(r[i], p_mul(p_add(p[i], -p_mul(v[i], omega)), beta));
+}
+
+// ---- the one-workgroup kernels between the sweeps -----------------------------------------------------------------------
+// rho = r^.r and rr = r.r of the initial residual
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_setup(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rho, const T *__restrict__ part_rr, unsigned n_parts) {
+    __shared__ T out2[2];
+    fold2(part_rho, part_rr, n_parts, out2);
+    if (threadIdx.x == 0) {
+        mo->rho = out2[0];
+        sc->rr = out2[1];
+    }
+}
+
+// decide whether this body runs; rv = r^.v; rv == 0: breakdown 2; else alpha = rho / rv
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_bi_alpha(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
+    const bool active = !sc->converged && sc->iters < sc->iter_max;  // (every thread reads before thread 0 writes: the fold has a barrier)
+    if (!active) {
+        if (threadIdx.x == 0) sc->active = sc->xmode = 0;
+        return;
+    }
+    const T rv = fold1(part, n_parts);
+    if (threadIdx.x == 0) {
+        sc->iters += 1;
+        sc->xmode = 0;
+        mo->rv = rv;
+        if (rv == T(0)) {
+            mo->breakdown = 2;
+            sc->converged = 1;
+            sc->active = 0;
+        } else {
+            sc->active = 1;
+            sc->alpha = p_div(mo->rho, rv);
+        }
+    }
+}
+
+// ss = s.s; the half-step stop
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_bi_half(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
+    if (!sc->active) return;
+    const T ss = fold1(part, n_parts);
+    if (threadIdx.x == 0) {
+        mo->ss = ss;
+        if (sqrt((double)ss) < sc->tol) {
+            sc->rr = ss;
+            sc->xmode = 1;
+            sc->converged = 1;
+            sc->active = 0;
+        }
+    }
+}
+
+// ts = t.s, tt = t.t; tt == 0: breakdown 3; else omega = ts / tt
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_omega(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_ts, const T *__restrict__ part_tt, unsigned n_parts) {
+    if (!sc->active) return;
+    __shared__ T out2[2];
+    fold2(part_ts, part_tt, n_parts, out2);
+    if (threadIdx.x == 0) {
+        const T ts = out2[0], tt = out2[1];
+        mo->ts = ts;
+        mo->tt = tt;
+        if (tt == T(0)) {
+            sc->rr = mo->ss;
+            sc->xmode = 1;
+            mo->breakdown = 3;
+            sc->converged = 1;
+            sc->active = 0;
+        } else {
+            mo->omega = p_div(ts, tt);
+            sc->xmode = 2;
+        }
+    }
+}
+
+// rr = r.r, rho' = r^.r; the stop test (before beta, linearsolver.rs:52-54); rho' == 0 or omega == 0: breakdown 1; else beta, rho = rho'
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_bi_beta(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rr, const T *__restrict__ part_rho, unsigned n_parts) {
+    if (!sc->active) return;
+    __shared__ T out2[2];
+    fold2(part_rr, part_rho, n_parts, out2);
+    if (threadIdx.x == 0) {
+        const T rr = out2[0], rho_new = out2[1], omega = mo->omega;
+        sc->rr = rr;
+        if (sqrt((double)rr) < sc->tol) {
+            sc->converged = 1;
+            sc->active = 0;
+        } else if (rho_new == T(0) || omega == T(0)) {
+            mo->breakdown = 1;
+            sc->converged = 1;
+            sc->active = 0;
+        } else {
+            sc->beta = p_mul(p_div(rho_new, mo->rho), p_div(sc->alpha, omega));
+            mo->rho = rho_new;
+        }
+    }
+}
+
+// b_in / x_io: n values each, in host or device memory (the copies are hipMemcpyDefault); x_io is written once, after the loop
+template <typename T>
+int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+               double *rr_out, int *breakdown_out) {
+    const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    Stream own;  // the solve runs on a stream of its own
+    Scratch ws;
+    PinnedBuf h_sc;
+    int stopped = 0;
+    size_t iters = 0;
+    double rr = 0.0;
+    int breakdown = 0;
+    const unsigned grid = pcg_grid(n);
+    auto go = [&]() -> int {
+        SMH_TRY(own.create());
+        const hipStream_t s = own.get();
+        T *x = nullptr, *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *sv = nullptr, *t = nullptr, *part = nullptr;
+        BiScalars<T> *sc = nullptr;
+        BiMore<T> *mo = nullptr;
+        SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&rhat, n)); SMH_TRY(ws.alloc(&p, n));
+        SMH_TRY(ws.alloc(&v, n)); SMH_TRY(ws.alloc(&sv, n)); SMH_TRY(ws.alloc(&t, n));
+        SMH_TRY(ws.alloc(&part, 2 * (size_t)kPcgBlocks));
+        SMH_TRY(ws.alloc(&sc, 1));
+        SMH_TRY(ws.alloc(&mo, 1));
+        SMH_TRY(h_sc.alloc(sizeof(BiScalars<T>) + sizeof(BiMore<T>), hipHostMallocDefault));
+        T *part_a = part, *part_b = part + kPcgBlocks;
+        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
+        if (n) {
+            SMH_HIP(hipMemcpyAsync(r, b_in, n * sizeof(T), hipMemcpyDefault, s));
+            SMH_HIP(hipMemcpyAsync(x, x_io, n * sizeof(T), hipMemcpyDefault, s));
+        }
+        // r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r  (before any capture: the handle's lazy workspaces exist from here on)
+        hipLaunchKernelGGL((k_bi_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max);
+        SMH_TRY(spmv_enqueue(m, x, n, v, variant, s));
+        if (n) {
+            SMH_TRY(launch_ew(dt, Ew::Sub, r, v, n, 0.0, nullptr, s));
+            SMH_HIP(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+            SMH_HIP(hipMemcpyAsync(p, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+        }
+        hipLaunchKernelGGL((k_bi_dot2<T, true>), dim3(grid), dim3(kBlock), 0, s, sc, r, r, (uint64_t)n, part_a, part_b);
+        hipLaunchKernelGGL((k_bi_setup<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
+        SMH_HIP(hipGetLastError());
+        auto body = [&]() -> int {
+            SMH_TRY(spmv_enqueue(m, p, n, v, variant, s));
+            hipLaunchKernelGGL((k_bi_dot<T>), dim3(grid), dim3(kBlock), 0, s, sc, rhat, v, (uint64_t)n, part_a);
+            hipLaunchKernelGGL((k_bi_alpha<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
+            hipLaunchKernelGGL((k_bi_s<T>), dim3(grid), dim3(kBlock), 0, s, sc, r, v, sv, (uint64_t)n, part_a);
+            hipLaunchKernelGGL((k_bi_half<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
+            SMH_HIP(hipGetLastError());
+            SMH_TRY(spmv_enqueue(m, sv, n, t, variant, s));
+            hipLaunchKernelGGL((k_bi_dot2<T, false>), dim3(grid), dim3(kBlock), 0, s, sc, t, sv, (uint64_t)n, part_a, part_b);
+            hipLaunchKernelGGL((k_bi_omega<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
+            hipLaunchKernelGGL((k_bi_xr<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, x, p, sv, t, rhat, r, (uint64_t)n, part_a, part_b);
+            hipLaunchKernelGGL((k_bi_beta<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
+            hipLaunchKernelGGL((k_bi_p<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, p, r, v, (uint64_t)n);
+            SMH_HIP(hipGetLastError());
+            return SMH_OK;
+        };
+        SMH_TRY(solve_in_batches(dt, s, iter_max, check_every, body, sc, h_sc.get(), &stopped, &iters, &rr));
+        BiMore<T> *h_mo = (BiMore<T> *)((char *)h_sc.get() + sizeof(BiScalars<T>));
+        SMH_HIP(hipMemcpyAsync(h_mo, mo, sizeof(BiMore<T>), hipMemcpyDeviceToHost, s));
+        if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
+        SMH_HIP(hipStreamSynchronize(s));
+        breakdown = (int)h_mo->breakdown;
+        return SMH_OK;
+    };
+    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
+    // the solve failed half way
+    const int rc = keep_error(go(), [&] {
+        if (own.get()) (void)hipStreamSynchronize(own.get());
+        (void)hipGetLastError();
+    });
+    if (rc != SMH_OK) return rc;
+    if (iters_out) *iters_out = iters;
+    if (rr_out) *rr_out = rr;
+    if (breakdown_out) *breakdown_out = breakdown;
+    return rc;
+}
+
+int bicgstab(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+             double *rr_out, int *breakdown_out) {
+    if (check_every == 0) check_every = 8;
+    if (m->dtype == SMH_F64)
+        return bicgstab_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    return bicgstab_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+}
+
+}  // namespace
+
+// the statuses are decided here, before any launch
+extern "C" int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
+                                      size_t *iters_out, double *rr_out, int *breakdown_out) {
+    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
+    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");                        // linearsolver.rs:30-32
+    if (m->n_rows != b->n || m->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");  // :33-36
+    return bicgstab(m, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+}
+
+extern "C" int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
+                                  int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    const size_t n = m->n_rows;
+    if (n != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    if (n && b_host == x_host_inout) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    return bicgstab(m, b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out, breakdown_out);
+}

@@ -16,6 +16,7 @@
 // Reductions: fixed grid, per-thread strided sums, wave butterfly, LDS across waves, one block folds the partials in
 // index order -- deterministic.
 #include "internal.hpp"
+#include "solver_tree.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -28,12 +29,6 @@ unsigned reduce_blocks(size_t n);  // blas1.hip
 
 namespace {
 
-constexpr int kPcgBlocks = 512;  // 2 blocks per CU (the CG tail's measured optimum)
-
-template <typename T> __device__ __forceinline__ T p_mul(T a, T b) { if constexpr (sizeof(T) == 4) return __fmul_rn(a, b); else return __dmul_rn(a, b); }
-template <typename T> __device__ __forceinline__ T p_add(T a, T b) { if constexpr (sizeof(T) == 4) return __fadd_rn(a, b); else return __dadd_rn(a, b); }
-template <typename T> __device__ __forceinline__ T p_div(T a, T b) { if constexpr (sizeof(T) == 4) return __fdiv_rn(a, b); else return __ddiv_rn(a, b); }
-
 // d[i] = get(i, i); *bad = the smallest row whose diagonal entry is zero or absent (stays ~0 when there is none)
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -45,24 +40,6 @@ k_pcg_diag(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, c
             if (col[q] == i) { v = val[q]; break; }
         d[i] = v;
         if (v == T(0)) atomicMin(bad, (unsigned long long)i);
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void block_sums(T a, T b, T *pa, T *pb) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        a = p_add(a, (T)__shfl_down(a, o, kWave));
-        b = p_add(b, (T)__shfl_down(b, o, kWave));
-    }
-    __shared__ T sa[kBlock / kWave], sb[kBlock / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) { sa[threadIdx.x / kWave] = a; sb[threadIdx.x / kWave] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        T ta = sa[0], tb = sb[0];
-        for (int w = 1; w < kBlock / kWave; ++w) { ta = p_add(ta, sa[w]); tb = p_add(tb, sb[w]); }
-        pa[blockIdx.x] = ta;
-        pb[blockIdx.x] = tb;
     }
 }
 
@@ -92,21 +69,6 @@ __global__ void k_pcg_init(PcgScalars<T> *sc, double tol, uint64_t iter_max) {
     sc->iters = 0;
     sc->iter_max = iter_max;
     sc->tol = tol;
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum1(T a) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) a = p_add(a, (T)__shfl_down(a, o, kWave));
-    __shared__ T sa1[kBlock / kWave];
-    if ((threadIdx.x & (kWave - 1)) == 0) sa1[threadIdx.x / kWave] = a;
-    __syncthreads();
-    T t = T(0);
-    if (threadIdx.x == 0) {
-        t = sa1[0];
-        for (int w = 1; w < kBlock / kWave; ++w) t = p_add(t, sa1[w]);
-    }
-    return t;  // (thread 0)
 }
 
 // out[b] = sum of block b's strided share of in[0..n): first stage of folding the SpMV epilogue's per-tile partials
@@ -243,12 +205,6 @@ k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__rest
             p[i] = FIRST ? z : p_add(p_mul(p[i], beta), z);
         }
     }
-}
-
-unsigned pcg_grid(size_t n) {
-    uint64_t b = (n + kBlock - 1) / kBlock;
-    if (b > (uint64_t)kPcgBlocks) b = kPcgBlocks;
-    return (unsigned)(b ? b : 1);
 }
 
 template <typename T>

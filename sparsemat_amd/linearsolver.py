@@ -8,7 +8,11 @@
                                all-reduces (p.Ap and r.r) on device-resident 1-element tensors; the vector
                                updates are the library's kernels with device-resident scalars
                                (``smh_blas_*_dev``), so no scalar visits the host except the stop test.
+* ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
+                               device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
 """
+import math
+
 import ctypes as C
 
 import numpy as np
@@ -104,4 +108,44 @@ class JacobiConjugateGradient:
         check(lib().smh_pcg_jacobi_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
                                          x.size, self.tol, self.iter_max, _lib.VARIANTS[self.variant], C.byref(iters), C.byref(rr)))
         self.iterations, self.r_norm_squared = iters.value, rr.value
+        return x
+
+
+class BiCGStab:
+    """BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is the
+    conjugate gradient): device-resident like ``ConjugateGradient``, the same guards, panics and stop rule
+    (``sqrt(f64(r.r)) < tol`` after the update of r, and on ``s.s`` at the half step), ``smh_bicgstab_solve*``.
+
+    After ``solve``: ``iterations`` (bodies entered), ``r_norm_squared`` (the last r.r, or s.s after a half-step stop, as
+    f64), ``breakdown`` (0 none; 1 rho' == 0 or omega == 0: x keeps that body's update; 2 r^.v == 0: x untouched by that body;
+    3 t.t == 0: x has taken p*alpha) and ``converged`` (a stop test ended the loop: neither a breakdown nor iter_max)."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
+        self.tol = float(tol)
+        self.iter_max = int(iter_max)
+        self.variant = variant
+        self.check_every = int(check_every)
+        self.iterations = None
+        self.r_norm_squared = None
+        self.breakdown = None
+        self.converged = None
+
+    def solve(self, mat, b, x):
+        """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
+        SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
+        iters, rr, brk = C.c_size_t(), C.c_double(), C.c_int()
+        var = _lib.VARIANTS[self.variant]
+        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
+            check(lib().smh_bicgstab_solve_vec(mat._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
+                                               C.byref(iters), C.byref(rr), C.byref(brk)))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
+                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
+            bb = np.ascontiguousarray(b, dtype=mat.dtype)
+            check(lib().smh_bicgstab_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size,
+                                           x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var,
+                                           C.byref(iters), C.byref(rr), C.byref(brk)))
+        self.iterations, self.r_norm_squared, self.breakdown = iters.value, rr.value, brk.value
+        # every entered body that ends without a breakdown has tested the r.r it reports: under tol means that test stopped the loop
+        self.converged = self.breakdown == 0 and self.iterations > 0 and math.sqrt(self.r_norm_squared) < self.tol
         return x
