@@ -364,6 +364,11 @@ int smh_crs_set_ring(smh_crs *m, int mode);
 /* columns the ring of this matrix's plan holds: 16384, or 32768 for f32 matrices whose rows need the
  * wider window (128 KiB of LDS, one 1024-thread block per CU) */
 int smh_crs_ring_entries(smh_crs *m, uint32_t *out);
+/* what the ring phases of the VECTOR family stream for their columns under the current settings (builds the plan and the
+ * form on first use): 0 = the 32-bit columns (also when the ring kernel is not in use), 1 = 16-bit columns, 2 = the compact
+ * form, 12 bits per column (f32 on the single-window ring of 16384 columns; SMH_RING_COL12 = auto / 0 / 1).  The form changes
+ * speed only, never a result. */
+int smh_crs_ring_column_form(smh_crs *m, int *form_out);
 /* 1: one sliding window (slot = column mod ring size).  4: banded ring for rows that reference a few narrow
  * column intervals far apart (stencils): band k holds the k-th interval of the tiles, slot = k * S +
  * column mod S, S = ring size / 4.  intervals_out (optional, banded plans only): 8 u32 per 64-row tile,

@@ -574,6 +574,45 @@ static int ensure_stream_codes(smh_crs *m) {
     return SMH_OK;
 }
 
+// K1r's compact column form: the counting pass (once per matrix and storage order) and, when the form is taken (*use: forced,
+// or few enough escapes), its arrays
+static void drop_ring_col12(smh_crs *m) {
+    m->ring.lo8.reset();
+    m->ring.hdr.reset();
+    m->ring.escapes.reset();
+}
+static int ensure_ring_col12(smh_crs *m, bool forced, bool *use) {
+    RingPlan &r = m->ring;
+    *use = forced || r.c12 == Form::Ready;
+    if (r.c12 != Form::NotTried && (!*use || r.lo8.get())) return SMH_OK;
+    Scratch scr;
+    uint32_t *jobs = nullptr;
+    unsigned long long *d_counts = nullptr, h_counts[2] = {0, 0};
+    SMH_TRY(scr.alloc(&jobs, 2 * r.n_phases));
+    SMH_TRY(scr.alloc(&d_counts, 2));
+    SMH_TRY(read_back(d_counts, h_counts, 2, m->stream, [&](unsigned long long *d) {
+        return launch_col12_count(m->d_off, m->d_col, m->nnz, r.phases.get(), r.n_phases, jobs, d, m->stream);
+    }));
+    r.c12_chunks = h_counts[0];
+    r.c12_escapes = h_counts[1];
+    r.c12 = r.c12_escapes * 1024ull <= r.c12_chunks ? Form::Ready : Form::Refused;
+    *use = forced || r.c12 == Form::Ready;
+    if (!*use) return SMH_OK;
+    const size_t n_chunks_out = ((m->nnz + 3) >> 2) + 1;  // (one chunk beyond the padded end, like col16)
+    DevArray<uint8_t> lo8;
+    DevArray<uint16_t> hdr;
+    DevArray<uint32_t> escapes;
+    SMH_TRY(lo8.alloc(n_chunks_out * 4));
+    SMH_TRY(hdr.alloc(n_chunks_out));
+    SMH_TRY(escapes.alloc(2 * (size_t)(r.c12_escapes ? r.c12_escapes : 1)));
+    SMH_TRY(launch_col12_encode(m->d_col, m->nnz, jobs, r.n_phases, n_chunks_out, lo8.get(), hdr.get(), escapes.get(), d_counts, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    r.lo8 = std::move(lo8);
+    r.hdr = std::move(hdr);
+    r.escapes = std::move(escapes);
+    return SMH_OK;
+}
+
 // does the VECTOR family run as K1r (LDS x-ring) for this matrix?
 static int vector_uses_ring(smh_crs *m, bool *out) {
     *out = false;
@@ -586,7 +625,19 @@ static int vector_uses_ring(smh_crs *m, bool *out) {
     // ring phase reads -- 6 instead of 8 bytes per f32 entry from HBM.  One extra 2-byte-per-entry array, built once.
     int want = m->knobs.use_col16;
     if (const char *e = getenv("SMH_RING_COL16")) want = atoi(e) ? 1 : 0;  // tuning knob
+    // ... or, f32 on the single-window ring of 16384 columns, the compact form of ring_col12.hpp: 5.5 bytes per entry.  Chosen
+    // by itself when col16 would be, nobody has asked for or against col16, and a counting pass (once per matrix) finds at most
+    // one chunk in 1024 that the code cannot hold; SMH_RING_COL12=1 takes it wherever it applies, however many chunks escape.
+    int want12 = m->knobs.use_col12;
+    if (const char *e = getenv("SMH_RING_COL12")) want12 = strcmp(e, "auto") == 0 ? -1 : (atoi(e) ? 1 : 0);  // tuning knob
+    const bool can12 = m->dtype == SMH_F32 && m->ring.bands == 1 && m->ring.entries == (unsigned)kRingEntries && m->nnz > 0;
+    bool use12 = can12 && (want12 == 1 || (want12 < 0 && want < 0 && m->ring.fraction >= 0.25));
+    if (use12) SMH_TRY(ensure_ring_col12(m, want12 == 1, &use12));
+    if (!use12) drop_ring_col12(m);
     // (the banded plan cannot do without: its gathers take the ring slot from that array)
+    // col16 is built by the same rule as before also when the compact form is in use, although the kernel then does not read it:
+    // tests/test_bench_contract_gpu.py pins `derived_bytes` to at least 2 bytes per entry.  Dropping it here (`!use12 &&`: 2 bytes
+    // per entry of device memory and a 0.5 ms pass less on the headline) has to go together with that assertion.
     const bool use16 = m->ring.bands == 4 || want == 1 || (want < 0 && m->ring.fraction >= 0.25);
     if (use16 && !m->ring.col16.get() && m->nnz) {
         const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
@@ -620,6 +671,8 @@ static void invalidate(smh_crs *m, Changed what) {
         // depend on each tile's column set, not on order
         m->codes = StreamCodes();
         m->ring.col16.reset();
+        drop_ring_col12(m);
+        m->ring.c12 = Form::NotTried;  // (which chunks escape depends on the order inside the rows)
     }
 }
 
@@ -762,7 +815,8 @@ static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x
 // one K1r launch over the plan's row ranges [b0, b1) (dot_partials: the DOT form, whole plan only -- see launch_spmv_ring2)
 static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u) {
     // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
-    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(), m->d_val, x, y, m->n_rows, m->nnz,
+    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(),
+                             RingCol12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get()}, m->d_val, x, y, m->n_rows, m->nnz,
                              m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
                              m->ring.bands, s, dot_partials, b0, b1);
 }
@@ -1916,6 +1970,14 @@ int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out, 
         SMH_HIP(hipMemcpy(phase_ptr_out, m->ring.phase_ptr.get(), (m->ring.blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (phases_out && m->ring.n_phases)
         SMH_HIP(hipMemcpy(phases_out, m->ring.phases.get(), m->ring.n_phases * sizeof(RingPhase), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_ring_column_form(smh_crs *m, int *form_out) {
+    if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));
+    *form_out = !ring ? 0 : m->ring.lo8.get() ? 2 : m->ring.col16.get() ? 1 : 0;
     return SMH_OK;
 }
 

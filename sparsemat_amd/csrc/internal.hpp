@@ -474,7 +474,15 @@ int launch_tile_span(const uint32_t *off, const uint32_t *col, size_t n_rows, si
                      uint32_t *cmax, hipStream_t s);
 // col16 (optional): the low halves of the columns, padded with zeros to a multiple of 4 entries plus one chunk; ring
 // phases then stream 2 instead of 4 bytes per column
-int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16,
+// c12 (optional, instead of col16; f32 on the single-window ring of kRingEntries columns): the compact form of ring_col12.hpp,
+// 1.5 bytes per column -- lo8: one byte per entry, hdr: one u16 per 4-entry chunk (both padded like col16), escapes: 2 u32 per
+// chunk the code cannot hold
+struct RingCol12 {
+    const uint8_t *lo8 = nullptr;
+    const uint16_t *hdr = nullptr;
+    const uint32_t *escapes = nullptr;
+};
+int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12,
                       const void *val, const void *x, void *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                       const uint32_t *phase_ptr, const RingPhase *phases, unsigned ring_entries, unsigned bands,
                       hipStream_t s, void *dot_partials = nullptr /* DOT form: y = lhs (read only), n_blocks + 1 partials of lhs . (A x) */,
@@ -485,6 +493,13 @@ int launch_tile_intervals(const uint32_t *off, const uint32_t *col, size_t n_row
 int launch_ring_band_codes(const uint32_t *off, const uint32_t *col, const uint32_t *win, size_t n_rows, uint32_t S,
                            uint16_t *code, hipStream_t s);
 int launch_narrow_columns(const uint32_t *col, size_t nnz, uint16_t *col16, size_t n_out, hipStream_t s);
+// the compact form's build.  count: jobs (2 u32 per phase) = the chunks each ring phase streams, counts[0] = how many those are,
+// counts[1] = how many of them the code cannot hold.  encode: lo8 / hdr (n_chunks_out chunks, all written) and the side table
+// (room for counts[1] entries of the count pass; counts[1] is reused as its allocator)
+int launch_col12_count(const uint32_t *off, const uint32_t *col, size_t nnz, const RingPhase *phases, size_t n_phases, uint32_t *jobs,
+                       unsigned long long *counts, hipStream_t s);
+int launch_col12_encode(const uint32_t *col, size_t nnz, const uint32_t *jobs, size_t n_phases, size_t n_chunks_out, uint8_t *lo8,
+                        uint16_t *hdr, uint32_t *escapes, unsigned long long *counts, hipStream_t s);
 // structure statistics / validation
 struct CrsStats {
     uint32_t max_row_len;
@@ -613,6 +628,13 @@ struct RingPlan {  // K1r
     DevArray<RingPhase> phases;
     DevArray<uint32_t> win;               // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
     DevArray<uint16_t> col16;             // 16-bit column array for the ring phases (built from the plan on first use; null: not used)
+    // the compact column form (ring_col12.hpp), which the ring phases then stream instead of col16.  c12: NotTried until the counting pass has run; Ready: at most one
+    // chunk in 1024 escapes, AUTO takes the form; Refused: AUTO keeps col16.  The arrays exist while the form is in use.
+    Form c12 = Form::NotTried;
+    uint64_t c12_chunks = 0, c12_escapes = 0;  // chunks the ring phases stream; those of them the code cannot hold
+    DevArray<uint8_t> lo8;
+    DevArray<uint16_t> hdr;
+    DevArray<uint32_t> escapes;
 };
 struct StreamCodes {  // K1s 16-bit column codes (Ready only when every tile has a description; Refused holds nothing)
     Form state = Form::NotTried;
@@ -708,6 +730,7 @@ struct Knobs {
     int use_stream_direct = -1;           // K1s XD: -1 automatic (most rows of odd length), 0 never, 1 whenever x is staged
     int use_stream_vdict = -1;            // -1 automatic (whenever the values allow), 0 never
     int use_col16 = -1;                   // -1 automatic (when at least a quarter of the rows are ring rows), 0 never, 1 always
+    int use_col12 = -1;                   // the compact form instead: -1 automatic (where it applies, few chunks escape and use_col16 is automatic too), 0 never, 1 wherever it applies
 };
 
 }  // namespace smh

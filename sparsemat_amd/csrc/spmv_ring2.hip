@@ -18,8 +18,10 @@
 //   garbage may be NaN), and the <= 3 entries of an unpadded array's final partial chunk are added by
 //   a one-thread fix-up kernel (in storage order: they are the last entries of their rows).
 #include "internal.hpp"
+#include "ring_col12.hpp"
 
 #include <atomic>
+#include <type_traits>
 
 namespace smh {
 
@@ -86,15 +88,30 @@ __device__ __forceinline__ uint32_t lane_pos(uint32_t j, int q) {
 // it: hipcc emits the saddr form `global_load_dwordx4 v, v_off, s[base]`, one address VGPR per load.  Every address is clamped to the
 // last piece that is safe to read (last_rel: the last whole 4-entry chunk of the arrays): lanes without work re-read a valid piece,
 // which the caller masks.
-// C16: colp points into the 16-bit column array (the low halves of the columns: all a ring phase needs, since the
-// ring slot of a column is `column mod 16384`) -- 4 columns are then 8 bytes (f32: one load; f64: two of 4 bytes)
-template <typename T, bool C16, int LANES>
-__device__ __forceinline__ void load_chunk_nb(const void *__restrict__ colp, const T *__restrict__ valp, uint32_t pass_rel, uint32_t j,
+// CF, the column form a phase streams:
+//   kColU32: colp points into the 32-bit column array
+//   kCol16:  ... into the 16-bit column array (the low halves of the columns: all a ring phase needs, since the ring slot of a
+//            column is `column mod 16384`) -- 4 columns are then 8 bytes (f32: one load; f64: two of 4 bytes)
+//   kCol12:  ... into the byte array of the compact form (ring_col12.hpp; f32 on the 16384-slot ring), and hdrp into its u16
+//            chunk headers -- 4 columns are 4 + 2 bytes, decoded where they are used (chunk_slots)
+enum : int { kColU32 = 0, kCol16 = 1, kCol12 = 2 };
+struct ColStream {
+    const void *colp;          // wave-uniform base of the phase's first chunk in the array of its form
+    const uint16_t *hdrp;      // kCol12: ... and in the chunk headers
+    const uint16_t *table;     // kCol12: the triple table (in LDS)
+    const u32x2 *escapes;      // kCol12: the side table
+};
+template <typename T, int CF, int LANES>
+__device__ __forceinline__ void load_chunk_nb(const ColStream &cs, const T *__restrict__ valp, uint32_t pass_rel, uint32_t j,
                                               uint32_t last_rel, uint32_t (&c)[4], T (&v)[4]) {
+    const void *colp = cs.colp;
     if constexpr (sizeof(T) == 4) {
         uint32_t rel = pass_rel + 4u * j;
         rel = rel < last_rel ? rel : last_rel;
-        if constexpr (C16) {  // kept packed: c[0], c[1] hold two columns each (unpacked where they are used, see ring_slot)
+        if constexpr (CF == kCol12) {  // c[0]: the chunk's four low bytes (or its side-table index), c[1]: its header
+            c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(rel, 1u)));
+            c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(cs.hdrp) + (SMH_R2_OFF(rel, 1u) >> 1)));
+        } else if constexpr (CF == kCol16) {  // kept packed: c[0], c[1] hold two columns each (unpacked where they are used, see chunk_slots)
             const u32x2 cc = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(
                 reinterpret_cast<const char *>(colp) + SMH_R2_OFF(rel, 2u)));
             c[0] = cc.x; c[1] = cc.y;  // (unpacking here instead measured the same: 0.343-0.345 ms either way)
@@ -111,7 +128,8 @@ __device__ __forceinline__ void load_chunk_nb(const void *__restrict__ colp, con
         uint32_t e0 = pass_rel + 2u * j, e1 = pass_rel + 2u * LANES + 2u * j;
         e0 = e0 < last_rel + 2u ? e0 : last_rel + 2u;
         e1 = e1 < last_rel + 2u ? e1 : last_rel + 2u;
-        if constexpr (C16) {
+        static_assert(CF != kCol12, "the compact column form is an f32 form");
+        if constexpr (CF == kCol16) {
             c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(e0, 2u)));
             c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(e1, 2u)));
         } else {
@@ -125,12 +143,29 @@ __device__ __forceinline__ void load_chunk_nb(const void *__restrict__ colp, con
     }
 }
 
-// ring slot of entry q of a chunk: column mod kRingEntries, from the u32 columns or from the packed 16-bit pairs
-template <bool C16, int RING>
-__device__ __forceinline__ uint32_t ring_slot(const uint32_t (&c)[4], int q) {
+// ring slots of a chunk's four entries: column mod kRingEntries, from the u32 columns, from the packed 16-bit pairs or from
+// the compact form.  There the escape is a wave-uniform branch that almost no wave takes (the form is only chosen by itself
+// for matrices with at most one escaped chunk in 1024): the lanes whose chunk escaped fetch its 8 bytes of true slots.
+template <int CF, int RING>
+__device__ __forceinline__ void chunk_slots(const uint32_t (&c)[4], const ColStream &cs, uint32_t (&slot)[4]) {
     constexpr uint32_t MASK = RING - 1;
-    if constexpr (C16) return (q & 1) ? ((c[q >> 1] >> 16) & MASK) : (c[q >> 1] & MASK);
-    else return c[q] & MASK;
+    if constexpr (CF == kCol12) {
+        static_assert(RING == (int)col12::kSlots, "the compact column form holds slots of the 16384-slot ring");
+        col12::decode_chunk(c[1], c[0], cs.table, slot);
+        const bool escaped = col12::is_escape(c[1]);
+        if (__builtin_amdgcn_ballot_w64(escaped) != 0) {
+            if (escaped) {
+                const u32x2 e = cs.escapes[c[0]];
+                col12::unpack_escape(e.x, e.y, slot);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if constexpr (CF == kCol16) slot[q] = (q & 1) ? ((c[q >> 1] >> 16) & MASK) : (c[q >> 1] & MASK);
+            else slot[q] = c[q] & MASK;
+        }
+    }
 }
 
 __device__ __forceinline__ float r2_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -164,8 +199,8 @@ __device__ __forceinline__ void row_bounds(uint32_t o0, uint32_t o1, int t, uint
 }
 
 // A lane group covers 4*LANES*CH entry slots of its row per pass: chunk (ch, j) = slots [4*(ch*LANES+j), +4)
-template <typename T, int LANES, int CH, int SB, bool C16>
-__device__ __forceinline__ void issue_unit(Unit<T, SB * CH> &u, const void *__restrict__ colp,
+template <typename T, int LANES, int CH, int SB, int CF>
+__device__ __forceinline__ void issue_unit(Unit<T, SB * CH> &u, const ColStream &cs,
                                            const T *__restrict__ valp, uint32_t kb, uint32_t nnz_lim, uint32_t last_rel,
                                            uint32_t lane) {
     const uint32_t j = lane % LANES;
@@ -177,16 +212,16 @@ __device__ __forceinline__ void issue_unit(Unit<T, SB * CH> &u, const void *__re
 #pragma unroll
         for (int ch = 0; ch < CH; ++ch) {
             // (lanes without work re-read a valid piece: clamped inside, masked when consumed)
-            load_chunk_nb<T, C16, LANES>(colp, valp, (s & ~3u) - kb + 4u * (uint32_t)(ch * LANES), j, last_rel, u.c[t * CH + ch], u.v[t * CH + ch]);
+            load_chunk_nb<T, CF, LANES>(cs, valp, (s & ~3u) - kb + 4u * (uint32_t)(ch * LANES), j, last_rel, u.c[t * CH + ch], u.v[t * CH + ch]);
         }
     }
 }
 
 // DOT (SparseMatrix::inner_prod, sparsematrix.rs:161-171): `y` then holds lhs, nothing is stored, and every lane adds
 // lhs[row] * (A x)[row] of the rows it would have stored to its *dacc
-template <typename T, int LANES, int CH, int SB, int GM, bool C16, int RING, bool DOT = false>
+template <typename T, int LANES, int CH, int SB, int GM, int CF, int RING, bool DOT = false>
 __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t base, uint64_t row_end,
-                                             const void *__restrict__ colp, const T *__restrict__ valp,
+                                             const ColStream &cs, const T *__restrict__ valp,
                                              const T *__restrict__ x, const T *ring, T *__restrict__ y, uint32_t kb,
                                              uint32_t nnz_lim, uint32_t last_rel, uint32_t lane, T *dacc = nullptr) {
     constexpr int RPS = kWave / LANES;
@@ -204,6 +239,8 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
         T sum = T(0);
 #pragma unroll
         for (int ch = 0; ch < CH; ++ch) {
+            uint32_t slot[4];
+            if constexpr (GM == 1) chunk_slots<CF, RING>(u.c[t * CH + ch], cs, slot);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint32_t rel = 4u * (uint32_t)(ch * LANES) + lane_pos<T, LANES>(j, q);
@@ -211,7 +248,7 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
                 T xv;
                 // (round 4, a build that is wrong on purpose: every lane gathering its OWN slot -- no bank conflicts -- ran exactly as
                 // fast, 0.699 against 0.698 ms on f64 and 0.353 against 0.353 on f32: the random LDS gathers are not what bounds K1r)
-                if constexpr (GM == 1) xv = ring[ring_slot<C16, RING>(u.c[t * CH + ch], q)];
+                if constexpr (GM == 1) xv = ring[slot[q]];
                 else if constexpr (GM == 2) xv = __builtin_nontemporal_load(&x[in ? u.c[t * CH + ch][q] : 0u]);
                 else xv = x[in ? u.c[t * CH + ch][q] : 0u];
                 const T f = r2_fma(u.v[t * CH + ch][q], xv, sum);
@@ -222,12 +259,14 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
         for (uint32_t pass = 4u * (uint32_t)(CH * LANES); pass + lane_pos<T, LANES>(j, 0) < len; pass += 4u * LANES) {
             uint32_t cc[4];
             T vv[4];
-            load_chunk_nb<T, C16, LANES>(colp, valp, sa - kb + pass, j, last_rel, cc, vv);
+            load_chunk_nb<T, CF, LANES>(cs, valp, sa - kb + pass, j, last_rel, cc, vv);
+            uint32_t slot[4];
+            if constexpr (GM == 1) chunk_slots<CF, RING>(cc, cs, slot);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool in = pass + lane_pos<T, LANES>(j, q) < len;
                 T xv;
-                if constexpr (GM == 1) xv = ring[ring_slot<C16, RING>(cc, q)];
+                if constexpr (GM == 1) xv = ring[slot[q]];
                 else if constexpr (GM == 2) xv = __builtin_nontemporal_load(&x[in ? cc[q] : 0u]);
                 else xv = x[in ? cc[q] : 0u];
                 const T f = r2_fma(vv[q], xv, sum);
@@ -252,9 +291,9 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
     }
 }
 
-// col: the 32-bit column array, or (C16) the 16-bit one
-template <typename T, int LANES, int CH, int GM, bool C16, int RING, bool DOT = false>
-__device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, const void *__restrict__ col,
+// cols: the arrays of the column form CF from their first element (colp: the 32-bit columns, the 16-bit ones or the compact form's bytes)
+template <typename T, int LANES, int CH, int GM, int CF, int RING, bool DOT = false>
+__device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, const ColStream &cols,
                                            const T *__restrict__ val, const T *__restrict__ x, const T *ring,
                                            T *__restrict__ y, uint64_t rb, uint64_t re, uint32_t nnz_lim,
                                            uint64_t last_chunk, uint32_t wave, uint32_t lane, T *dacc = nullptr) {
@@ -269,49 +308,55 @@ __device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, con
     uint32_t kb = __builtin_amdgcn_readfirstlane(off[rb]) & ~3u;
     kb = kb < (uint32_t)last_chunk ? kb : (uint32_t)last_chunk;
     const uint32_t last_rel = (uint32_t)last_chunk - kb;
-    const void *colp = reinterpret_cast<const char *>(col) + (size_t)kb * (C16 ? 2u : 4u);
+    ColStream cs = cols;  // ... from the phase's first chunk (kb is a multiple of 4: kb / 4 chunks)
+    cs.colp = reinterpret_cast<const char *>(cols.colp) + (size_t)kb * (CF == kCol12 ? 1u : CF == kCol16 ? 2u : 4u);
+    if constexpr (CF == kCol12) cs.hdrp = cols.hdrp + (kb >> 2);
     const T *valp = val + kb;
     Unit<T, SB * CH> A, B, N;  // N: only its offsets are used (the unit after next)
     load_offsets(A, off, base, re, lane);
     load_offsets(B, off, base + STRIDE, re, lane);
-    issue_unit<T, LANES, CH, SB, C16>(A, colp, valp, kb, nnz_lim, last_rel, lane);
+    issue_unit<T, LANES, CH, SB, CF>(A, cs, valp, kb, nnz_lim, last_rel, lane);
     for (;;) {
         if (base + STRIDE >= re) {
-            consume_unit<T, LANES, CH, SB, GM, C16, RING, DOT>(A, base, re, colp, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+            consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(A, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
             break;
         }
         // program order = age order: offsets(+2) older than chunks(+1); both stay in flight under consume
         load_offsets(N, off, base + 2 * STRIDE, re, lane);
-        issue_unit<T, LANES, CH, SB, C16>(B, colp, valp, kb, nnz_lim, last_rel, lane);
-        consume_unit<T, LANES, CH, SB, GM, C16, RING, DOT>(A, base, re, colp, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+        issue_unit<T, LANES, CH, SB, CF>(B, cs, valp, kb, nnz_lim, last_rel, lane);
+        consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(A, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
         A.o0 = N.o0; A.o1 = N.o1;
         base += STRIDE;
         if (base + STRIDE >= re) {
-            consume_unit<T, LANES, CH, SB, GM, C16, RING, DOT>(B, base, re, colp, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+            consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(B, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
             break;
         }
         load_offsets(N, off, base + 2 * STRIDE, re, lane);
-        issue_unit<T, LANES, CH, SB, C16>(A, colp, valp, kb, nnz_lim, last_rel, lane);
-        consume_unit<T, LANES, CH, SB, GM, C16, RING, DOT>(B, base, re, colp, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+        issue_unit<T, LANES, CH, SB, CF>(A, cs, valp, kb, nnz_lim, last_rel, lane);
+        consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(B, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
         B.o0 = N.o0; B.o1 = N.o1;
         base += STRIDE;
     }
 }
 
-// C16: ring phases stream the 16-bit column array `col16` (6 instead of 8 bytes per f32 entry); phases with global
-// gathers need whole columns and keep reading `col`
+// the triple table of the compact column form, as every workgroup of a kCol12 kernel copies it into LDS
+__device__ const col12::Table k_col12_table = col12::make_table();
+
+// CF: what ring phases stream for their columns -- kCol16: the 16-bit column array `col16` (6 instead of 8 bytes per f32 entry);
+// kCol12: the compact form `c12` (5.5 bytes; LDS then holds the ring and, behind it, the 2 KiB triple table); phases with
+// global gathers need whole columns and keep reading `col`
 // DOT: y holds lhs (read only) and dot_partials[blockIdx.x] = this block's share of lhs . (A x); nothing else is stored
-template <typename T, int LANES, int CH, bool C16, int RING, bool DOT = false>
+template <typename T, int LANES, int CH, int CF, int RING, bool DOT = false>
 __global__ void __launch_bounds__((Ring2Cfg<T, RING>::kThreads), (Ring2Cfg<T, RING>::kWavesPerSimd))
-k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const uint16_t *__restrict__ col16,
+k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const uint16_t *__restrict__ col16, RingCol12 c12,
              const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, uint32_t nnz_lim, uint64_t last_chunk,
              const uint32_t *__restrict__ phase_ptr, const RingPhase *__restrict__ phases, uint32_t bands,
              T *__restrict__ dot_partials, uint32_t lb0, uint32_t lb_n) {
     T dacc_v = T(0);
     T *dacc = DOT ? &dacc_v : nullptr;
-    extern __shared__ __attribute__((aligned(16))) unsigned char ring_raw[];  // RING * sizeof(T), dynamic
+    extern __shared__ __attribute__((aligned(16))) unsigned char ring_raw[];  // RING * sizeof(T) (kCol12: + the triple table), dynamic
     T *ring = reinterpret_cast<T *>(ring_raw);
-    // bands == 1: one window, slot = column mod RING.  bands == 4 (banded plan, C16 only): band k owns slots
+    // bands == 1: one window, slot = column mod RING.  bands == 4 (banded plan, kCol16 only): band k owns slots
     // [k * S, (k + 1) * S), S = RING / 4, slot = k * S + column mod S -- which is what col16 then holds
     const uint32_t MASK = (bands == 4u ? (uint32_t)RING / 4u : (uint32_t)RING) - 1u;
     constexpr int kRing2Threads = Ring2Cfg<T, RING>::kThreads;
@@ -324,6 +369,15 @@ k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t p0 = phase_ptr[lb], p1 = phase_ptr[lb + 1];
+    ColStream ring_cols = {CF == kCol16 ? (const void *)col16 : (const void *)col, nullptr, nullptr, nullptr};
+    const ColStream wide_cols = {col, nullptr, nullptr, nullptr};
+    if constexpr (CF == kCol12) {
+        static_assert(kRing2Threads * sizeof(uint32_t) == sizeof(col12::Table), "one dword of the table per thread");
+        uint16_t *table = reinterpret_cast<uint16_t *>(ring_raw + (size_t)RING * sizeof(T));
+        reinterpret_cast<uint32_t *>(table)[threadIdx.x] = reinterpret_cast<const uint32_t *>(k_col12_table.e)[threadIdx.x];
+        __syncthreads();
+        ring_cols = {c12.lo8, c12.hdr, table, reinterpret_cast<const u32x2 *>(c12.escapes)};
+    }
     for (uint32_t p = p0; p < p1; ++p) {
         const RingPhase ph = phases[p];
         const bool more = bands == 4u && (ph.band_hi[0] > ph.band_lo[0] || ph.band_hi[1] > ph.band_lo[1] || ph.band_hi[2] > ph.band_lo[2]);
@@ -342,13 +396,13 @@ k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
         // gather mode of the phase: 1 = LDS ring, 0 = L1/L2-cached global gathers, 2 = L1-bypassing (nt) global
         // gathers for phases whose columns have no locality to keep in the 32 KiB L1
         if (ph.use_ring == 1)
-            phase_rows<T, LANES, CH, 1, C16, RING, DOT>(off, C16 ? (const void *)col16 : (const void *)col, val, x, ring, y, ph.row_begin,
-                                                        ph.row_end, nnz_lim, last_chunk, wave, lane, dacc);
+            phase_rows<T, LANES, CH, 1, CF, RING, DOT>(off, ring_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
+                                                       lane, dacc);
         else if (ph.use_ring == 2)
-            phase_rows<T, LANES, CH, 2, false, RING, DOT>(off, col, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
+            phase_rows<T, LANES, CH, 2, kColU32, RING, DOT>(off, wide_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
                                                           lane, dacc);
         else
-            phase_rows<T, LANES, CH, 0, false, RING, DOT>(off, col, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
+            phase_rows<T, LANES, CH, 0, kColU32, RING, DOT>(off, wide_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
                                                           lane, dacc);
     }
     if constexpr (DOT) {  // fixed order: lanes (butterfly), waves (index order) -- bitwise reproducible
@@ -412,14 +466,103 @@ int launch_narrow_columns(const uint32_t *col, size_t nnz, uint16_t *col16, size
     return SMH_OK;
 }
 
+// ---- the compact column form (ring_col12.hpp), built once per matrix ----
+// Which chunks the ring phases stream: jobs[p] = chunks [x, y) of phase p (empty for a global-gather phase), every chunk in
+// one job only -- a chunk that two ring phases share (a phase begins inside it) goes with the earlier one.  Phases follow
+// one another in row order, so the entry before phase p's first belongs to the nearest earlier phase that has entries.
+__global__ void __launch_bounds__(kBlock)
+k_col12_jobs(const uint32_t *__restrict__ off, const RingPhase *__restrict__ phases, uint32_t n_phases, u32x2 *__restrict__ jobs,
+             unsigned long long *__restrict__ counts) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_phases) return;
+    const uint32_t e0 = off[phases[p].row_begin], e1 = off[phases[p].row_end];
+    uint32_t cb = e0 >> 2, ce = (uint32_t)(((uint64_t)e1 + 3u) >> 2);
+    if (phases[p].use_ring != 1u || e1 <= e0) {
+        cb = ce = 0;
+    } else if (e0 & 3u) {
+        uint32_t q = p;
+        while (q > 0 && off[phases[q - 1].row_begin] == e0) --q;  // (earlier phases without entries)
+        if (q > 0 && phases[q - 1].use_ring == 1u) ++cb;
+    }
+    jobs[p] = u32x2{cb, ce > cb ? ce : cb};
+    if (ce > cb) atomicAdd(&counts[0], (unsigned long long)(ce - cb));
+}
+
+// COUNT: counts[1] += the jobs' chunks the code cannot hold.  Else: the jobs' chunks are encoded; an escaped one takes the
+// next free entry of the side table (counts[1] is the allocator, from 0), so the table's order differs from run to run --
+// the slots a chunk decodes to do not.  Columns past nnz count as 0, like col16's padding.
+template <bool COUNT>
+__global__ void __launch_bounds__(kBlock)
+k_col12_encode(const uint32_t *__restrict__ col, uint64_t nnz, const u32x2 *__restrict__ jobs, uint32_t n_jobs, uint32_t *__restrict__ lo,
+               uint16_t *__restrict__ hdr, u32x2 *__restrict__ escapes, unsigned long long *__restrict__ counts) {
+    unsigned long long mine = 0;
+    for (uint32_t job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+        const u32x2 range = jobs[job];
+        for (uint64_t c = (uint64_t)range.x + threadIdx.x; c < range.y; c += kBlock) {
+            uint32_t slot[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) slot[q] = (4u * c + q < nnz ? col[4u * c + q] : 0u) & (col12::kSlots - 1u);
+            uint16_t h = 0;
+            uint32_t l = 0;
+            const bool ok = col12::encode_chunk(slot, &h, &l);
+            if constexpr (COUNT) {
+                mine += ok ? 0u : 1u;
+            } else {
+                if (!ok) {
+                    l = (uint32_t)atomicAdd(&counts[1], 1ull);
+                    h = (uint16_t)col12::kEscape;
+                    uint32_t pair[2];
+                    col12::pack_escape(slot, pair);
+                    escapes[l] = u32x2{pair[0], pair[1]};
+                }
+                lo[c] = l;
+                hdr[c] = h;
+            }
+        }
+    }
+    if constexpr (COUNT) {
+        if (mine) atomicAdd(&counts[1], mine);
+    }
+}
+
+int launch_col12_count(const uint32_t *off, const uint32_t *col, size_t nnz, const RingPhase *phases, size_t n_phases, uint32_t *jobs,
+                       unsigned long long *counts, hipStream_t s) {
+    SMH_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s));
+    if (n_phases == 0) return SMH_OK;
+    hipLaunchKernelGGL(k_col12_jobs, dim3((unsigned)((n_phases + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, off, phases, (uint32_t)n_phases,
+                       reinterpret_cast<u32x2 *>(jobs), counts);
+    SMH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_col12_encode<true>, dim3((unsigned)(n_phases < 8192 ? n_phases : 8192)), dim3(kBlock), 0, s, col, (uint64_t)nnz,
+                       reinterpret_cast<const u32x2 *>(jobs), (uint32_t)n_phases, (uint32_t *)nullptr, (uint16_t *)nullptr, (u32x2 *)nullptr, counts);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
+int launch_col12_encode(const uint32_t *col, size_t nnz, const uint32_t *jobs, size_t n_phases, size_t n_chunks_out, uint8_t *lo8,
+                        uint16_t *hdr, uint32_t *escapes, unsigned long long *counts, hipStream_t s) {
+    // chunks no ring phase streams, and the padding: header 0 -- they decode to slots inside the ring like any other
+    SMH_HIP(hipMemsetAsync(lo8, 0, n_chunks_out * 4, s));
+    SMH_HIP(hipMemsetAsync(hdr, 0, n_chunks_out * sizeof(uint16_t), s));
+    SMH_HIP(hipMemsetAsync(counts + 1, 0, sizeof(unsigned long long), s));
+    if (n_phases == 0) return SMH_OK;
+    hipLaunchKernelGGL(k_col12_encode<false>, dim3((unsigned)(n_phases < 8192 ? n_phases : 8192)), dim3(kBlock), 0, s, col, (uint64_t)nnz,
+                       reinterpret_cast<const u32x2 *>(jobs), (uint32_t)n_phases, reinterpret_cast<uint32_t *>(lo8), hdr,
+                       reinterpret_cast<u32x2 *>(escapes), counts);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
 // dot_partials != NULL: the DOT form -- `y` is lhs (read only), dot_partials[0..n_blocks] receive the blocks' shares of
 // lhs . (A x) plus, in slot n_blocks, that of an unpadded array's last partial chunk
 template <typename T, int RING>
-static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const T *val,
+static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12, const T *val,
                           const T *x, T *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                           const uint32_t *phase_ptr, const RingPhase *phases, uint32_t bands, T *dot_partials, hipStream_t s,
                           unsigned block_begin, unsigned block_end) {
     if (bands == 4u && !col16) return fail(SMH_ERR_INVALID, "banded ring plan without the 16-bit slot array");
+    constexpr bool kHasCol12 = std::is_same<T, float>::value && RING == (int)col12::kSlots;  // the compact form's only instantiation
+    if (c12.lo8 && (!kHasCol12 || bands != 1u || !c12.hdr || !c12.escapes))
+        return fail(SMH_ERR_INVALID, "ring kernel: the compact column form is for f32 on the single-window ring of 16384 columns");
     // the plan's row ranges [lb0, lb1) (default: all of them)
     const unsigned lb0 = block_begin < n_blocks ? block_begin : n_blocks, lb1 = block_end < n_blocks ? block_end : n_blocks;
     const bool whole = lb0 == 0 && lb1 == n_blocks;
@@ -434,10 +577,11 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
     } else {
         const uint64_t last_chunk = (nnz_lim - 1) & ~uint64_t(3);
         dim3 grid(((lb1 - lb0) + 7u) & ~7u), block(Ring2Cfg<T, RING>::kThreads);
-        constexpr size_t lds_bytes = (size_t)RING * sizeof(T);
+        constexpr size_t ring_bytes = (size_t)RING * sizeof(T);
         // dynamic LDS above 64 KiB must be allowed per kernel (idempotent, cheap)
 #define SMH_R2_LAUNCH2(L, C, N, D)                                                                                       \
     do {                                                                                                                 \
+        constexpr size_t lds_bytes = ring_bytes + ((N) == kCol12 ? sizeof(col12::Table) : 0);                            \
         /* once per (instantiation, DEVICE): function attributes are per device, and smh_par_* places blocks on       \
            several devices.  Bit d of the mask = device d has the opt-in; a second thread racing on the same bit only   \
            repeats an idempotent call.  (Set by the first launch, so never inside a later stream capture.) */          \
@@ -448,7 +592,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                    \
             attr_mask.fetch_or(dev_bit, std::memory_order_release);                                                      \
         }                                                                                                                \
-        hipLaunchKernelGGL((k_spmv_ring2<T, L, C, N, RING, D>), grid, block, lds_bytes, s, off, col, col16, val, x, y,   \
+        hipLaunchKernelGGL((k_spmv_ring2<T, L, C, N, RING, D>), grid, block, lds_bytes, s, off, col, col16, c12, val, x, y, \
                            (uint32_t)nnz_lim, last_chunk, phase_ptr, phases, bands, dot_partials, (uint32_t)lb0,         \
                            (uint32_t)(lb1 - lb0));                                                                       \
     } while (0)
@@ -456,9 +600,12 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
     do {                                                                                   \
         if (dot_partials) SMH_R2_LAUNCH2(L, C, N, true); else SMH_R2_LAUNCH2(L, C, N, false); \
     } while (0)
-#define SMH_R2_LAUNCH(L, C)                                            \
-    do {                                                               \
-        if (col16) SMH_R2_LAUNCH1(L, C, true); else SMH_R2_LAUNCH1(L, C, false); \
+#define SMH_R2_LAUNCH(L, C)                                                   \
+    do {                                                                      \
+        if (c12.lo8) {                                                        \
+            if constexpr (kHasCol12) SMH_R2_LAUNCH1(L, C, kCol12);            \
+        } else if (col16) SMH_R2_LAUNCH1(L, C, kCol16);                       \
+        else SMH_R2_LAUNCH1(L, C, kColU32);                                   \
     } while (0)
         switch (lanes * 16 + chunks) {
             case 1 * 16 + 1: SMH_R2_LAUNCH(1, 1); break;
@@ -492,7 +639,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
 
 // ring_entries: what the phase plan was built for (kRingEntries; kRingEntriesWide for f32 matrices that need it).
 // dot_partials != NULL (n_blocks + 1 values): the DOT form, `y` = lhs (see launch_ring2_t).
-int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16,
+int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12,
                       const void *val, const void *x, void *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                       const uint32_t *phase_ptr, const RingPhase *phases, unsigned ring_entries, unsigned bands,
                       hipStream_t s, void *dot_partials, unsigned block_begin, unsigned block_end) {
@@ -500,16 +647,16 @@ int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, con
     if (bands != 1u && bands != 4u) return fail(SMH_ERR_INVALID, "ring kernel: %u bands", bands);
     if (dtype == SMH_F64) {
         if (ring_entries != (unsigned)kRingEntries) return fail(SMH_ERR_INVALID, "f64 ring kernel: ring of %u columns", ring_entries);
-        return launch_ring2_t<double, kRingEntries>(lanes, chunks, off, col, col16, (const double *)val, (const double *)x,
+        return launch_ring2_t<double, kRingEntries>(lanes, chunks, off, col, col16, c12, (const double *)val, (const double *)x,
                                                     (double *)y, n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands,
                                                     (double *)dot_partials, s, block_begin, block_end);
     }
     if (ring_entries == (unsigned)kRingEntriesWide)
-        return launch_ring2_t<float, kRingEntriesWide>(lanes, chunks, off, col, col16, (const float *)val, (const float *)x,
+        return launch_ring2_t<float, kRingEntriesWide>(lanes, chunks, off, col, col16, c12, (const float *)val, (const float *)x,
                                                        (float *)y, n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands,
                                                        (float *)dot_partials, s, block_begin, block_end);
     if (ring_entries != (unsigned)kRingEntries) return fail(SMH_ERR_INVALID, "ring kernel: ring of %u columns", ring_entries);
-    return launch_ring2_t<float, kRingEntries>(lanes, chunks, off, col, col16, (const float *)val, (const float *)x, (float *)y,
+    return launch_ring2_t<float, kRingEntries>(lanes, chunks, off, col, col16, c12, (const float *)val, (const float *)x, (float *)y,
                                                n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands, (float *)dot_partials, s, block_begin, block_end);
 }
 

@@ -504,6 +504,13 @@ class SparseMatCRS:
         check(lib().smh_crs_ring_entries(self._h, C.byref(out)))
         return out.value
 
+    def ring_column_form(self):
+        """What K1r's ring phases stream for their columns under the current settings: "u32", "col16" or "col12" (the compact
+        12-bit form: f32 on the single-window 16384-column ring).  "u32" also when the ring kernel is not in use."""
+        out = C.c_int()
+        check(lib().smh_crs_ring_column_form(self._h, C.byref(out)))
+        return ("u32", "col16", "col12")[out.value]
+
     def ring_bands(self, intervals=False):
         """1 (one sliding window) or 4 (banded ring); with ``intervals`` also the per-tile column intervals
         [n_tiles64, 4, 2] of a banded plan (None otherwise)."""
