@@ -4,7 +4,8 @@ arithmetic is its contract.
 
 The recurrence (van der Vorst, unpreconditioned) is written once; HOW a reduction is carried out is cg_model's ``mode``
 ("sequential", "device", "wide").  Every other operation is in T with one rounding (a - b*c is a + (-(b*c)): the same
-bits), the products A p and A s come from oracle.spmv (the SEQ and K1s kernels are bit-exact against it), and every
+bits), the products A p and A s come from oracle.spmv (the SEQ and K1s kernels are bit-exact against it) or from the caller's
+``product`` (tests/test_solver_kernels_gpu.py: the device's own product of any kernel family, checked), and every
 reduction of bicgstab.hip uses pcg.hip's tree -- cg_model.device_sum(terms, pcg_grid(n), V, from_first=True), the kind
 "pcg" of cg_model.Reducer -- so in "device" mode x, the last r.r, the body count and the breakdown code are the device's bit
 for bit.
@@ -23,13 +24,16 @@ import oracle
 
 
 class Result:
-    def __init__(self, x, iterations, rr, breakdown, converged, half_step):
+    def __init__(self, x, iterations, rr, breakdown, converged, half_step, ss_list=(), rr_list=(), r=None, p=None):
         self.x, self.iterations, self.rr, self.breakdown, self.converged = x, iterations, rr, breakdown, converged
         self.half_step = half_step       # the stop was the half-step one (s.s under tol)
+        self.ss_list, self.rr_list = list(ss_list), list(rr_list)  # s.s / r.r of every body that got as far (what the stop tests saw)
+        self.r, self.p = r, p            # as the last full step left them (the device keeps them to itself)
         self.r_norm_squared = float(rr)  # what the solver reports: f64(T)
 
 
-def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
+def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device", product=None):
+    """product: where A v comes from (product(v) -> A v in T; None: oracle.spmv) -- the initial residual's, A p and A s."""
     val = np.ascontiguousarray(val)
     T = val.dtype.type
     red = cg_model.Reducer(mode)
@@ -37,8 +41,7 @@ def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
     def dot(a, c):
         return red.dot(a, c, "pcg")
 
-    def mvp(v):
-        return oracle.spmv(off, col, val, v)
+    mvp = product or (lambda v: oracle.spmv(off, col, val, v))
 
     with np.errstate(all="ignore"):
         x = np.array(x0, val.dtype, copy=True)
@@ -47,6 +50,7 @@ def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
         rhat, p = r.copy(), r.copy()
         rho, rr = dot(rhat, r), dot(r, r)
         iters, breakdown, converged, half = 0, 0, False, False
+        ss_list, rr_list = [], []
         while iters < iter_max:
             iters += 1
             v = mvp(p)
@@ -57,6 +61,7 @@ def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
             alpha = T(rho / rv)
             s = r - v * alpha
             ss = dot(s, s)
+            ss_list.append(ss)
             if math.sqrt(float(ss)) < tol:
                 x = x + p * alpha
                 rr, converged, half = ss, True, True
@@ -71,6 +76,7 @@ def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
             x = (x + p * alpha) + s * omega
             r = s - t * omega
             rr, rho_new = dot(r, r), dot(rhat, r)
+            rr_list.append(rr)
             if math.sqrt(float(rr)) < tol:
                 converged = True
                 break
@@ -80,7 +86,7 @@ def bicgstab(off, col, val, b, x0, tol, iter_max, mode="device"):
             beta = T(T(rho_new / rho) * T(alpha / omega))
             rho = rho_new
             p = r + (p - v * omega) * beta
-    return Result(x, iters, T(rr), breakdown, converged, half)
+    return Result(x, iters, T(rr), breakdown, converged, half, ss_list, rr_list, r, p)
 
 
 # ---- the test matrices ---------------------------------------------------------------------------------------------------

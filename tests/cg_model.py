@@ -10,8 +10,9 @@ Both recurrences are written once; HOW a reduction is carried out is a parameter
 
 All other arithmetic is in T with one rounding per operation (the library is built with -ffp-contract=off and every
 element-wise operation is an explicit *_rn multiply, add, subtract or divide), Ap comes from oracle.spmv (the SEQ and K1s
-products are bit-exact against it), so in "device" mode x, r, p, the r.r after every body and the iteration count are the
-device's bit for bit.
+products are bit-exact against it) or from the caller's ``product`` (tests/test_solver_kernels_gpu.py: the device's own
+product of any kernel family, checked against the oracle before it is used), so in "device" mode x, r, p, the r.r after
+every body and the iteration count are the device's bit for bit.
 
 The device's trees (kBlock = 256 threads, kWave = 64 lanes; V = 16 bytes / sizeof(T) elements per vector):
   a thread's share      vectors tid, tid + nthreads, ... (nthreads = grid * kBlock), the V elements of a vector in order,
@@ -231,23 +232,25 @@ def diagonal(off, col, val):
     return d
 
 
-def cg(off, col, val, b, x0, tol, iter_max, mode="device", aligned=True, fused=False):
+def cg(off, col, val, b, x0, tol, iter_max, mode="device", aligned=True, fused=False, product=None):
     """ConjugateGradient::solve (linearsolver.rs:27-61) as smh_cg_solve_vec carries it out.  aligned: x is 16-byte aligned
-    (else the two tail kernels run their VEC=false forms); fused: p.Ap comes out of the K1s epilogue ("device" mode only)."""
+    (else the two tail kernels run their VEC=false forms); fused: p.Ap comes out of the K1s epilogue ("device" mode only);
+    product: where A v comes from (product(v) -> A v in T; None: oracle.spmv) -- the initial residual's and every body's."""
     assert not fused or mode == "device"
     val = np.ascontiguousarray(val)
+    product = product or (lambda v: oracle.spmv(off, col, val, v))
     T = val.dtype.type
     red = Reducer(mode, aligned)
     with np.errstate(all="ignore"):  # (0 / 0 is the reference's behaviour for b = 0, not an accident)
         x = np.array(x0, val.dtype, copy=True)
         b = np.ascontiguousarray(b, val.dtype)
-        r = b - oracle.spmv(off, col, val, x)          # :38
+        r = b - product(x)          # :38
         p = r.copy()                                   # :39
         rr = red.one(red.dot(r, r, "dot"))             # :40  (launch_dot, then k_cg_set_rr)
         rr0, rr_list, iters = rr, [], 0
         while iters < iter_max:
             iters += 1
-            ap = oracle.spmv(off, col, val, p)         # :43
+            ap = product(p)         # :43
             if fused:
                 pap = fused_pap(p, ap, False)
             else:
@@ -265,17 +268,18 @@ def cg(off, col, val, b, x0, tol, iter_max, mode="device", aligned=True, fused=F
     return Result(x, r, p, iters, rr, rr_list, rr0)
 
 
-def pcg(off, col, val, b, x0, tol, iter_max, mode="device", fused=False):
-    """The same recurrence with z = r / diag(A) as smh_pcg_jacobi_solve carries it out (pcg.hip)."""
+def pcg(off, col, val, b, x0, tol, iter_max, mode="device", fused=False, product=None):
+    """The same recurrence with z = r / diag(A) as smh_pcg_jacobi_solve carries it out (pcg.hip).  product: as in cg."""
     assert not fused or mode == "device"
     val = np.ascontiguousarray(val)
+    product = product or (lambda v: oracle.spmv(off, col, val, v))
     T = val.dtype.type
     red = Reducer(mode)
     d = diagonal(off, col, val)
     with np.errstate(all="ignore"):
         x = np.array(x0, val.dtype, copy=True)
         b = np.ascontiguousarray(b, val.dtype)
-        r = b - oracle.spmv(off, col, val, x)
+        r = b - product(x)
         z = r / d
         rr = red.dot(r, r, "pcg")
         rz = red.dot(r, z, "pcg")
@@ -283,7 +287,7 @@ def pcg(off, col, val, b, x0, tol, iter_max, mode="device", fused=False):
         rr0, rr_list, iters = rr, [], 0
         while iters < iter_max:
             iters += 1
-            ap = oracle.spmv(off, col, val, p)
+            ap = product(p)
             # n == 0: the driver clears the dot's result instead of launching it (the fold of one +0 is +0 either way)
             if fused:
                 pap = fused_pap(p, ap, True)

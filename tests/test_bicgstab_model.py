@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import bicgstab_model as bm
+import oracle
 import sparsemat_amd as sm
 from sparsemat_amd import _lib
 
@@ -96,3 +97,67 @@ def test_binding_and_header_declare_both_entry_points():
     assert L.smh_bicgstab_solve(None, None, 0, None, 0, 1e-10, 5, 0, None, None, None) == _lib.SMH_ERR_INVALID
     assert L.smh_bicgstab_solve_vec(None, None, None, 1e-10, 5, 0, 0, None, None, None) == _lib.SMH_ERR_INVALID
     assert b"NULL handle" in L.smh_last_error()
+
+
+class CountedProduct:
+    """oracle.spmv as a ``product`` callable that counts its calls; bump = (c, k): in the c-th call the element of k-th largest
+    magnitude moves by one ulp."""
+
+    def __init__(self, off, col, val, bump=(None, 0)):
+        self.parts, self.bump, self.calls = (off, col, val), bump, 0
+
+    def __call__(self, v):
+        y = oracle.spmv(*self.parts, v)
+        if self.calls == self.bump[0]:
+            j = int(np.argsort(-np.abs(y), kind="stable")[self.bump[1]])
+            y[j] = np.nextafter(y[j], y.dtype.type(np.inf))
+        self.calls += 1
+        return y
+
+
+def results(r):
+    return r.x.tobytes(), r.iterations, r.rr.tobytes(), r.breakdown, r.converged, r.half_step, np.array(r.ss_list).tobytes(), np.array(r.rr_list).tobytes(), r.r.tobytes(), r.p.tobytes()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+def test_product_callable_is_what_the_model_consumes(dtype, mode):
+    """product = the oracle's own product: the default's bytes (x, the last r.r, every s.s and r.r, the body count, the breakdown
+    code), 1 + 2 * bodies calls (the initial residual's, A p and A s of every body), one less after a half-step stop, and
+    the exact cases' breakdowns.  One ulp on one element of ANY single call changes the result (x, r, p, an s.s or an r.r: one
+    ulp on one element seldom moves a dot, so the last call's shows in r and p alone): no product comes from anywhere else.
+    (It can also round away in v * alpha, so for each call the elements are tried in order of magnitude, at most eight of
+    them, until one shows.)"""
+    off, col, val, b, _ = bm.convdiff_system(12, 0.5, dtype)
+    x0 = np.random.default_rng(3).uniform(-1, 1, 144).astype(dtype)
+    bodies = 5
+    want = bm.bicgstab(off, col, val, b, x0, 0.0, bodies, mode)
+    assert want.iterations == bodies and want.breakdown == 0
+    counted = CountedProduct(off, col, val)
+    assert results(bm.bicgstab(off, col, val, b, x0, 0.0, bodies, mode, product=counted)) == results(want)
+    assert counted.calls == 1 + 2 * bodies
+    for call in range(1 + 2 * bodies):
+        for k in range(8):
+            bumped = bm.bicgstab(off, col, val, b, x0, 0.0, bodies, mode, product=CountedProduct(off, col, val, bump=(call, k)))
+            if results(bumped) != results(want):
+                break
+        else:
+            raise AssertionError("call %d of the product is not consumed" % call)
+    # a stop at the half step of body 3 (s.s_3 under tol, everything before it above) and one at its full step
+    norms = np.sqrt(np.array([[float(s), float(r)] for s, r in zip(want.ss_list, want.rr_list)])).reshape(-1)
+    for event, half in ((4, True), (5, False)):
+        lo, hi = norms[event], norms[:event].min()
+        if not lo < hi:
+            continue
+        tol = 0.5 * (lo + hi)
+        stopped = bm.bicgstab(off, col, val, b, x0, tol, bodies, mode)
+        assert stopped.iterations == 3 and stopped.converged and stopped.half_step is half
+        counted = CountedProduct(off, col, val)
+        assert results(bm.bicgstab(off, col, val, b, x0, tol, bodies, mode, product=counted)) == results(stopped)
+        assert counted.calls == 1 + 2 * 3 - (1 if half else 0)
+    for name, a, b, iters, x, rr, breakdown, converged in bm.EXACT:
+        off, col, val = bm.dense_to_crs(a, dtype)
+        counted = CountedProduct(off, col, val)
+        got = bm.bicgstab(off, col, val, np.array(b, dtype), np.zeros(len(b), dtype), 1e-6, 10, mode, product=counted)
+        assert (got.iterations, got.x.tolist(), got.r_norm_squared, got.breakdown, got.converged) == (iters, x, rr, breakdown, converged), name
+        assert counted.calls == 1 + 2 * iters - (1 if breakdown == 2 or name == "half-step stop" else 0), name

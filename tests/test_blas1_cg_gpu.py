@@ -104,7 +104,7 @@ def test_cg_laplace3d_matches_oracle(gpu, dtype, tol):
     b = oracle.spmv(off, col, val, np.ones(n, dtype))
     x_ref, it_ref, rr_ref = oracle.cg(n, n, off, col, val, b, np.zeros(n, dtype), tol=tol, iter_max=500)
     m = sm.SparseMatCRS.from_raw_parts(n, n, off, col, val)
-    for variant in ("seq", "auto", "merge"):
+    for variant in ("seq", "auto", "merge", "vector", "tiled", "colblock"):
         for check_every in (1, 7):
             x = np.zeros(n, dtype)
             xd, bd = sm.DenseVec.from_vec(x), sm.DenseVec.from_vec(b)

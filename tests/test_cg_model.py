@@ -128,3 +128,55 @@ def test_diagonal_takes_the_first_match_in_storage_order():
     col = np.array([2, 0, 0, 1, 1, 0], np.uint32)   # row 0: (2, 0, 0) -> first 0; row 1: (1, 1) -> first; row 2: no diagonal
     val = np.array([9.0, 4.0, 5.0, 6.0, 7.0, 8.0])
     assert cg_model.diagonal(off, col, val).tolist() == [4.0, 6.0, 0.0]
+
+
+class CountedProduct:
+    """oracle.spmv as a ``product`` callable that counts its calls; bump = (c, k): in the c-th call the element of k-th largest
+    magnitude moves by one ulp."""
+
+    def __init__(self, off, col, val, bump=(None, 0)):
+        self.parts, self.bump, self.calls = (off, col, val), bump, 0
+
+    def __call__(self, v):
+        y = oracle.spmv(*self.parts, v)
+        if self.calls == self.bump[0]:
+            j = int(np.argsort(-np.abs(y), kind="stable")[self.bump[1]])
+            y[j] = np.nextafter(y[j], y.dtype.type(np.inf))
+        self.calls += 1
+        return y
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("mode", ["sequential", "device", "wide"])
+@pytest.mark.parametrize("solver", ["cg", "pcg"])
+def test_product_callable_is_what_the_model_consumes(solver, mode, dtype):
+    """product = the oracle's own product: the default's bytes (x, every r.r, the body count), 1 + bodies calls (the initial
+    residual's and one per entered body; fewer bodies after a stop on tol).  One ulp on one element of ANY single call --
+    the initial residual's included -- changes the result (x, r, p or an r.r: one ulp on one element seldom moves a dot of a
+    thousand terms, so the last call's shows in r and p alone): no product is taken from anywhere else.  (It can also round
+    away in Ap * alpha, so for each call the elements are tried in order of magnitude, at most eight of them, until one
+    shows.)  The fused p.Ap reads the callable's Ap too."""
+    n, off, col, val, b, x0 = system("laplace", dtype)
+    model = cg_model.cg if solver == "cg" else cg_model.pcg
+    bodies = 5
+    for fused in ((False, True) if mode == "device" else (False,)):
+        for tol in (0.0, None):
+            want = model(off, col, val, b, x0, 0.0, bodies, mode=mode, fused=fused)
+            if tol is None:  # a stop on tol in body 3
+                tol = 0.5 * (math.sqrt(float(want.rr_list[2])) + min(math.sqrt(float(v)) for v in want.rr_list[:2]))
+                want = model(off, col, val, b, x0, tol, bodies, mode=mode, fused=fused)
+                assert want.iterations == 3
+            counted = CountedProduct(off, col, val)
+            got = model(off, col, val, b, x0, tol, bodies, mode=mode, fused=fused, product=counted)
+            assert counted.calls == 1 + want.iterations
+            assert got.iterations == want.iterations and same(got.x, want.x) and same(got.rr, want.rr)
+            assert same(np.array(got.rr_list), np.array(want.rr_list)) and same(got.r, want.r) and same(got.p, want.p)
+        plain = model(off, col, val, b, x0, 0.0, bodies, mode=mode, fused=fused)
+        for call in range(1 + bodies):
+            for k in range(8):
+                bumped = model(off, col, val, b, x0, 0.0, bodies, mode=mode, fused=fused, product=CountedProduct(off, col, val, bump=(call, k)))
+                if not all(same(u, v) for u, v in ((bumped.x, plain.x), (bumped.r, plain.r), (bumped.p, plain.p),
+                                                   (np.array(bumped.rr_list), np.array(plain.rr_list)))):
+                    break
+            else:
+                raise AssertionError("call %d of the product is not consumed (fused %s)" % (call, fused))
