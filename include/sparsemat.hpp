@@ -84,6 +84,13 @@ class DenseVec {
         return (T)out;
     }
     double norm() const { return std::sqrt((double)norm_squared()); }           // vector.rs:61-63
+    // an extension (see SparseMatCRS::permute): out[i] = (*this)[perm[i]], or with `inverse` out[perm[i]] = (*this)[i]
+    DenseVec permute(const std::vector<uint32_t> &perm, bool inverse = false) const {
+        static const uint32_t none = 0;
+        DenseVec r(dim());
+        detail::check(smh_vec_permute(r.h_, h_, perm.empty() ? &none : perm.data(), perm.size(), inverse ? 1 : 0));
+        return r;
+    }
     // operator sugar (densevec.rs:76-140)
     DenseVec &operator+=(const DenseVec &r) { add(r); return *this; }
     DenseVec &operator-=(const DenseVec &r) { sub(r); return *this; }
@@ -279,6 +286,37 @@ class SparseMatCRS {
         SparseMatCRS c;
         detail::check(smh_crs_prod(h_, rhs.h_, &c.h_));
         return c;
+    }
+    // Reordering (an extension: the reference has none; sparsemat_hip.h "reordering").  A permutation is n u32 with
+    // perm[new] = old.  permute: out[i][j] = (*this)[row_perm[i]][col_perm[j]], rows keep their entries in storage order, values
+    // bit for bit; an EMPTY vector is the identity.  permute_symmetric: P A P^T.
+    SparseMatCRS permute(const std::vector<uint32_t> &row_perm, const std::vector<uint32_t> &col_perm) const {
+        SparseMatCRS r;
+        detail::check(smh_crs_permute(h_, row_perm.empty() ? nullptr : row_perm.data(), row_perm.size(), col_perm.empty() ? nullptr : col_perm.data(),
+                                      col_perm.size(), &r.h_));
+        return r;
+    }
+    SparseMatCRS permute_symmetric(const std::vector<uint32_t> &perm) const {
+        static const uint32_t none = 0;
+        SparseMatCRS r;
+        detail::check(smh_crs_permute_symmetric(h_, perm.empty() ? &none : perm.data(), perm.size(), &r.h_));
+        return r;
+    }
+    // the reverse Cuthill-McKee ordering of the symmetrised pattern (computed on the device; one round of kernels per level)
+    struct RcmStats { size_t n_components = 0, n_levels = 0; };
+    std::vector<uint32_t> rcm(RcmStats *stats = nullptr) const {
+        std::vector<uint32_t> perm(n_rows() ? n_rows() : 1);
+        RcmStats st;
+        detail::check(smh_crs_rcm(h_, perm.data(), &st.n_components, &st.n_levels));
+        perm.resize(n_rows());
+        if (stats) *stats = st;
+        return perm;
+    }
+    // {max i - j, max j - i} over the stored entries
+    std::pair<uint32_t, uint32_t> bandwidth() const {
+        uint32_t lo = 0, hi = 0;
+        detail::check(smh_crs_bandwidth(h_, &lo, &hi));
+        return {lo, hi};
     }
     // #[derive(Clone)] (sparsemat_crs.rs:8): an independent library-owned copy (the copy constructor stays deleted: copies
     // of device matrices are explicit)

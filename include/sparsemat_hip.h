@@ -41,7 +41,9 @@ extern "C" {
  * smh_comm_ranks_seen, smh_rccl_version, smh_par_set_threads,
  * smh_crs_stream_value_dict, smh_crs_set_stream_value_dict; ADDED later without a version change (additions only):
  * smh_update_plan_create, smh_update_plan_create_dev, smh_update_plan_execute, smh_update_plan_execute_dev,
- * smh_update_plan_stats, smh_update_plan_destroy.  A caller checks smh_abi_version() ==
+ * smh_update_plan_stats, smh_update_plan_destroy; smh_crs_permute, smh_crs_permute_dev, smh_crs_permute_symmetric,
+ * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
+ * smh_crs_rcm_dev.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -168,6 +170,47 @@ int smh_crs_column_info_dev(const smh_crs *m, uint32_t *rows_dev, uint32_t *col_
  * first-push quirk).  The reference's Err("Dimension mismatch") (:188-190: a.n_rows != b.n_cols or
  * a.n_cols != b.n_rows) is SMH_ERR_DIM_MISMATCH.  No column tables are needed on rhs. */
 int smh_crs_prod(const smh_crs *a, const smh_crs *b, smh_crs **out);
+/* ---- reordering (EXTENSION: the reference has no permutation and no ordering; csrc/permute.hip, csrc/reorder.hip) -----------------
+ * A permutation is n uint32_t with perm[new] = old (scipy's convention: A[perm][:, perm]).  Every array argument carries its
+ * length: a length that is not the dimension it permutes is SMH_ERR_DIM_MISMATCH.  An entry >= n, or a value that occurs twice,
+ * is SMH_ERR_INVALID, the message naming the first offending position.  Validation runs on the device before anything is
+ * allocated for a result; on any error the operands are untouched and *out stays NULL.  The _dev forms take DEVICE arrays on the
+ * handle's device and, like smh_crs_apply_dev, wait for all work on the device before they read them; every form has finished
+ * when it returns.
+ * smh_crs_permute: out[i][j] = a[row_perm[i]][col_perm[j]] -- row i of the result is row row_perm[i] of a with the same entries in
+ * the same storage order, every column c relabelled to col_perm^-1[c], values copied bit for bit.  Unsorted and duplicate columns
+ * stay as they are: the storage-order sums of smh_crs_spmv(SEQ / STREAM) are kept.  Either permutation may be NULL (identity, its
+ * length ignored); rectangular matrices are allowed (row_perm: n_rows entries, col_perm: n_cols).  With a column permutation a
+ * stored column >= n_cols is SMH_ERR_INDEX_RANGE.  The result is a new library-owned handle with a's smh_crs_set_* settings and
+ * its own create-time statistics.  A handle holding an orphan (smh_crs_orphans) is SMH_ERR_INVALID.
+ * smh_crs_permute_symmetric: P A P^T, i.e. smh_crs_permute(a, perm, perm); a not square is SMH_ERR_NOT_SQUARE. */
+int smh_crs_permute(const smh_crs *a, const uint32_t *row_perm, size_t n_row_perm, const uint32_t *col_perm, size_t n_col_perm, smh_crs **out);
+int smh_crs_permute_dev(const smh_crs *a, const uint32_t *row_perm_dev, size_t n_row_perm, const uint32_t *col_perm_dev, size_t n_col_perm,
+                        smh_crs **out);
+int smh_crs_permute_symmetric(const smh_crs *a, const uint32_t *perm, size_t n_perm, smh_crs **out);
+int smh_crs_permute_symmetric_dev(const smh_crs *a, const uint32_t *perm_dev, size_t n_perm, smh_crs **out);
+/* max i - j (*lower_out) and max j - i (*upper_out) over the stored entries, 0 for a matrix without entries: one pass, integer
+ * max.  Either out may be NULL. */
+int smh_crs_bandwidth(const smh_crs *m, uint32_t *lower_out, uint32_t *upper_out);
+/* mean column span of a 64-row tile / n_cols: the locality statistic AUTO tests (taken on first use; also smh_crs_colblock's
+ * span_fraction_out, without building that copy) */
+int smh_crs_span_fraction(smh_crs *m, double *out);
+/* The reverse Cuthill-McKee ordering of a square pattern: perm_out[n_rows] with perm_out[new] = old, ready for
+ * smh_crs_permute_symmetric.  Not square: SMH_ERR_NOT_SQUARE; a stored column >= n_cols: SMH_ERR_INDEX_RANGE; 2^31 stored entries
+ * or more: SMH_ERR_CAPACITY.  Definition (the result equals it exactly; values are never read):
+ *   graph     vertices 0..n-1; u ~ v iff u != v and an entry (u, v) or (v, u) is stored -- stored zeros count, duplicates once;
+ *             deg(v) = number of distinct neighbours;
+ *   roots     while unvisited vertices remain, the root is the unvisited vertex with the smallest (deg, index): all isolated
+ *             vertices come first, in index order;
+ *   levels    from the root level by level: the next level is the set of unvisited neighbours of the current one; each new vertex
+ *             v has the key (position in the order of its earliest-placed parent, deg(v), v) and the level is appended in
+ *             ascending key order (Cuthill-McKee, ties broken by index);
+ *   result    that order reversed.
+ * *n_components_out counts roots, *n_levels_out levels over all components, root levels included (either may be NULL).
+ * Cost: one round of a few kernels and one small read-back per level plus one per component -- a chain of n vertices takes n
+ * rounds. */
+int smh_crs_rcm(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out);
+int smh_crs_rcm_dev(const smh_crs *m, uint32_t *perm_out_dev, size_t *n_components_out, size_t *n_levels_out);
 /* #[derive(Clone)] (sparsemat_crs.rs:8): a new handle with copies of the dims, arrays, orphans and the smh_crs_set_* settings;
  * derived forms (codes, plans, column-blocked copies) are rebuilt lazily.  The copy is library-owned even when `a` borrows. */
 int smh_crs_clone(const smh_crs *a, smh_crs **out);
@@ -482,6 +525,11 @@ size_t smh_vec_dim(const smh_vec *v);
 int smh_vec_dtype(const smh_vec *v);
 void *smh_vec_data(const smh_vec *v); /* device pointer */
 int smh_vec_copy(smh_vec *dst, const smh_vec *src);                            /* clone() */
+/* EXTENSION (see smh_crs_permute for permutations and their statuses): inverse == 0 gathers, dst[i] = src[perm[i]]; inverse != 0
+ * scatters, dst[perm[i]] = src[i] -- so x.permute(p) undoes with permute(p, inverse).  dst and src: different vectors of equal
+ * dimension (SMH_ERR_DIM_MISMATCH) and dtype (SMH_ERR_INVALID); perm has that many entries. */
+int smh_vec_permute(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse);
+int smh_vec_permute_dev(smh_vec *dst, const smh_vec *src, const uint32_t *perm_dev, size_t n_perm, int inverse);
 /* Vector::add / sub / scale (densevec.rs:51-58, :60-67, :69-73; += -= *= sugar :76-96):
  * x += y, x -= y over the first y.dim() entries; SMH_ERR_DIM_MISMATCH iff x.dim() < y.dim() */
 int smh_vec_add(smh_vec *x, const smh_vec *y);

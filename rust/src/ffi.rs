@@ -68,6 +68,19 @@ extern "C" {
     pub fn smh_crs_prod(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
     // #[derive(Clone)] and SparseMatrix::add / sub (src/sparsematrix.rs:123-143) with the operators of sparsemat_ops! (:370-433)
     pub fn smh_crs_clone(a: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
+    // reordering (an extension; a permutation is n u32 with perm[new] = old)
+    pub fn smh_crs_permute(a: *const smh_crs, row_perm: *const u32, n_row_perm: usize, col_perm: *const u32, n_col_perm: usize,
+                           out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_permute_dev(a: *const smh_crs, row_perm_dev: *const u32, n_row_perm: usize, col_perm_dev: *const u32,
+                               n_col_perm: usize, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_permute_symmetric(a: *const smh_crs, perm: *const u32, n_perm: usize, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_permute_symmetric_dev(a: *const smh_crs, perm_dev: *const u32, n_perm: usize, out: *mut *mut smh_crs) -> c_int;
+    pub fn smh_crs_bandwidth(m: *const smh_crs, lower_out: *mut u32, upper_out: *mut u32) -> c_int;
+    pub fn smh_crs_span_fraction(m: *mut smh_crs, out: *mut f64) -> c_int;
+    pub fn smh_crs_rcm(m: *const smh_crs, perm_out: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
+    pub fn smh_crs_rcm_dev(m: *const smh_crs, perm_out_dev: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
+    pub fn smh_vec_permute(dst: *mut smh_vec, src: *const smh_vec, perm: *const u32, n_perm: usize, inverse: c_int) -> c_int;
+    pub fn smh_vec_permute_dev(dst: *mut smh_vec, src: *const smh_vec, perm_dev: *const u32, n_perm: usize, inverse: c_int) -> c_int;
     pub fn smh_crs_add(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
     pub fn smh_crs_sub(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;
     pub fn smh_crs_add_assign(a: *mut smh_crs, b: *const smh_crs) -> c_int;

@@ -124,6 +124,40 @@ impl DeviceCrs {
         DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
     }
 
+    /// Reordering (an extension: the reference has none).  A permutation is n u32 with `perm[new] = old`.
+    /// `out[i][j] = self[row_perm[i]][col_perm[j]]`: rows keep their entries in storage order, values bit for bit; `None` is
+    /// the identity.  A malformed permutation panics with the library's message.
+    pub fn permute(&self, row_perm: Option<&[u32]>, col_perm: Option<&[u32]>) -> DeviceCrs {
+        let mut handle = std::ptr::null_mut();
+        let (rp, rn) = row_perm.map_or((std::ptr::null(), 0), |p| (p.as_ptr(), p.len()));
+        let (cp, cn) = col_perm.map_or((std::ptr::null(), 0), |p| (p.as_ptr(), p.len()));
+        check(unsafe { ffi::smh_crs_permute(self.handle, rp, rn, cp, cn, &mut handle) });
+        DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
+    }
+
+    /// `P A P^T` of a square matrix.
+    pub fn permute_symmetric(&self, perm: &[u32]) -> DeviceCrs {
+        let mut handle = std::ptr::null_mut();
+        check(unsafe { ffi::smh_crs_permute_symmetric(self.handle, perm.as_ptr(), perm.len(), &mut handle) });
+        DeviceCrs { handle, n_rows: unsafe { ffi::smh_crs_n_rows(handle) } }
+    }
+
+    /// The reverse Cuthill-McKee ordering of the symmetrised pattern, computed on the device: (perm, components, levels).
+    pub fn rcm(&self) -> (Vec<u32>, usize, usize) {
+        let mut perm = vec![0u32; self.n_rows.max(1)];
+        let (mut comps, mut levels) = (0usize, 0usize);
+        check(unsafe { ffi::smh_crs_rcm(self.handle, perm.as_mut_ptr(), &mut comps, &mut levels) });
+        perm.truncate(self.n_rows);
+        (perm, comps, levels)
+    }
+
+    /// (max i - j, max j - i) over the stored entries.
+    pub fn bandwidth(&self) -> (u32, u32) {
+        let (mut lo, mut hi) = (0u32, 0u32);
+        check(unsafe { ffi::smh_crs_bandwidth(self.handle, &mut lo, &mut hi) });
+        (lo, hi)
+    }
+
     /// `SparseMatrix::prod` (src/sparsematrix.rs:186-210) with the reference's `Result`: `Err("Dimension mismatch")`
     /// when `self.n_rows() != rhs.n_cols() || self.n_cols() != rhs.n_rows()`; no column tables needed on `rhs`.
     pub fn prod(&self, rhs: &DeviceCrs) -> Result<DeviceCrs, String> {

@@ -47,6 +47,16 @@ SIGNATURES = {
     "smh_crs_column_info": (_int, [_vp, _vp, _vp, _vp]),
     "smh_crs_column_info_dev": (_int, [_vp, _vp, _vp, _vp]),
     "smh_crs_prod": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "smh_crs_permute": (_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_vp)]),
+    "smh_crs_permute_dev": (_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_vp)]),
+    "smh_crs_permute_symmetric": (_int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    "smh_crs_permute_symmetric_dev": (_int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    "smh_crs_bandwidth": (_int, [_vp, _u32p, _u32p]),
+    "smh_crs_span_fraction": (_int, [_vp, C.POINTER(C.c_double)]),
+    "smh_crs_rcm": (_int, [_vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "smh_crs_rcm_dev": (_int, [_vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "smh_vec_permute": (_int, [_vp, _vp, _vp, _sz, _int]),
+    "smh_vec_permute_dev": (_int, [_vp, _vp, _vp, _sz, _int]),
     "smh_crs_clone": (_int, [_vp, C.POINTER(_vp)]),
     "smh_crs_add": (_int, [_vp, _vp, C.POINTER(_vp)]),
     "smh_crs_sub": (_int, [_vp, _vp, C.POINTER(_vp)]),

@@ -1325,6 +1325,155 @@ int smh_crs_prod(const smh_crs *a, const smh_crs *b, smh_crs **out) {
     return wrap_arrays(a->dtype, nullptr, n_rows, n_cols, nnz, arrays, 0, out);
 }
 
+// ---- reordering (EXTENSION; permute.hip, reorder.hip): a permutation is n u32 with perm[new] = old ---------------------------
+static int check_dev_array(const void *p, int device, const char *what);
+// One permutation argument of an entry point: checked for its length, brought to the device when it is a host array, validated
+// there (`inv` = its inverse afterwards).  perm == NULL: the identity, nothing to do (*d_perm stays null).
+static int take_permutation(Scratch &scr, const uint32_t *perm, size_t len, size_t n, bool on_device, int device, const char *what,
+                            const uint32_t **d_perm, uint32_t **inv) {
+    *d_perm = nullptr;
+    *inv = nullptr;
+    if (!perm) return SMH_OK;
+    if (len != n) return fail(SMH_ERR_DIM_MISMATCH, "%s has %zu entries, %zu expected", what, len, n);
+    if (n == 0) return SMH_OK;
+    if (on_device) {
+        SMH_TRY(check_dev_array(perm, device, what));
+        *d_perm = perm;
+    } else {
+        const void *d = nullptr;
+        SMH_TRY(upload(scr, perm, n * sizeof(uint32_t), &d));
+        *d_perm = (const uint32_t *)d;
+    }
+    SMH_TRY(scr.alloc(inv, n));
+    return validate_permutation(*d_perm, n, *inv, what, nullptr);
+}
+
+static int permute_common(const smh_crs *a, const uint32_t *row_perm, size_t n_row_perm, const uint32_t *col_perm, size_t n_col_perm, bool on_device,
+                          smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!a) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (a->orphans) return fail(SMH_ERR_INVALID, "a handle holding an orphaned entry cannot be permuted");
+    if (col_perm) SMH_TRY(columns_within_n_cols(a, "permute"));
+    if (on_device) SMH_HIP(hipDeviceSynchronize());  // the caller's writes to the arrays come first
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    Scratch scr;
+    const uint32_t *d_rp = nullptr, *d_cp = nullptr;
+    uint32_t *row_inv = nullptr, *col_inv = nullptr;
+    SMH_TRY(take_permutation(scr, row_perm, n_row_perm, a->n_rows, on_device, a->device, "row_perm", &d_rp, &row_inv));
+    SMH_TRY(take_permutation(scr, col_perm, n_col_perm, a->n_cols, on_device, a->device, "col_perm", &d_cp, &col_inv));
+    CrsArrays arrays;
+    SMH_TRY(permute_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, d_rp, col_inv, &arrays, nullptr));
+    return wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out);
+}
+
+int smh_crs_permute(const smh_crs *a, const uint32_t *row_perm, size_t n_row_perm, const uint32_t *col_perm, size_t n_col_perm, smh_crs **out) {
+    return permute_common(a, row_perm, n_row_perm, col_perm, n_col_perm, false, out);
+}
+int smh_crs_permute_dev(const smh_crs *a, const uint32_t *row_perm_dev, size_t n_row_perm, const uint32_t *col_perm_dev, size_t n_col_perm,
+                        smh_crs **out) {
+    return permute_common(a, row_perm_dev, n_row_perm, col_perm_dev, n_col_perm, true, out);
+}
+
+static int permute_symmetric_common(const smh_crs *a, const uint32_t *perm, size_t n_perm, bool on_device, smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!a || !perm) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (a->orphans) return fail(SMH_ERR_INVALID, "a handle holding an orphaned entry cannot be permuted");
+    SMH_TRY(columns_within_n_cols(a, "permute_symmetric"));
+    if (on_device) SMH_HIP(hipDeviceSynchronize());
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    Scratch scr;
+    const uint32_t *d_p = nullptr;
+    uint32_t *inv = nullptr;
+    SMH_TRY(take_permutation(scr, perm, n_perm, a->n_rows, on_device, a->device, "perm", &d_p, &inv));  // (validated once, one inverse)
+    CrsArrays arrays;
+    SMH_TRY(permute_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, d_p, inv, &arrays, nullptr));
+    return wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out);
+}
+
+int smh_crs_permute_symmetric(const smh_crs *a, const uint32_t *perm, size_t n_perm, smh_crs **out) {
+    return permute_symmetric_common(a, perm, n_perm, false, out);
+}
+int smh_crs_permute_symmetric_dev(const smh_crs *a, const uint32_t *perm_dev, size_t n_perm, smh_crs **out) {
+    return permute_symmetric_common(a, perm_dev, n_perm, true, out);
+}
+
+static int vec_permute_common(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse, bool on_device) {
+    SMH_TRY(vec_check_pair(dst, src));
+    if (!perm && n_perm) return fail(SMH_ERR_INVALID, "perm is NULL");
+    if (dst->n != src->n) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    if (dst == src || (dst->d && dst->d == src->d)) return fail(SMH_ERR_INVALID, "a vector cannot be permuted into itself");
+    if (n_perm != src->n) return fail(SMH_ERR_DIM_MISMATCH, "perm has %zu entries, %zu expected", n_perm, src->n);
+    if (src->n == 0) return SMH_OK;
+    SMH_HIP(hipDeviceSynchronize());  // vectors work on the null stream; the caller's writes to a device array come first
+    Scratch scr;
+    const uint32_t *d_p = nullptr;
+    uint32_t *inv = nullptr;
+    SMH_TRY(take_permutation(scr, perm, n_perm, src->n, on_device, src->device, "perm", &d_p, &inv));
+    SMH_TRY(launch_vec_permute(src->dtype, dst->d, src->d, d_p, src->n, inverse != 0, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return SMH_OK;
+}
+
+int smh_vec_permute(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse) {
+    return vec_permute_common(dst, src, perm, n_perm, inverse, false);
+}
+int smh_vec_permute_dev(smh_vec *dst, const smh_vec *src, const uint32_t *perm_dev, size_t n_perm, int inverse) {
+    return vec_permute_common(dst, src, perm_dev, n_perm, inverse, true);
+}
+
+int smh_crs_bandwidth(const smh_crs *m, uint32_t *lower_out, uint32_t *upper_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    uint32_t h[2] = {0, 0};
+    if (m->n_rows && m->nnz) {
+        SMH_HIP(hipStreamSynchronize(m->stream));
+        Scratch scr;
+        uint32_t *d = nullptr;
+        SMH_TRY(scr.alloc(&d, 2));
+        SMH_TRY(read_back(d, h, 2, m->stream, [&](uint32_t *q) { return launch_bandwidth(m->d_off, m->d_col, m->n_rows, q, m->stream); }));
+    }
+    if (lower_out) *lower_out = h[0];
+    if (upper_out) *upper_out = h[1];
+    return SMH_OK;
+}
+
+int smh_crs_span_fraction(smh_crs *m, double *out) {
+    if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m, false));  // the locality statistic is taken with the K1r inspector
+    *out = m->span_fraction;
+    return SMH_OK;
+}
+
+static int rcm_common(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (m->n_rows && !perm_out) return fail(SMH_ERR_INVALID, "perm_out is NULL");
+    SMH_TRY(columns_within_n_cols(m, "rcm"));
+    if (on_device) {
+        SMH_TRY(check_dev_array(perm_out, m->device, "perm_out"));
+        SMH_HIP(hipDeviceSynchronize());
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    Scratch scr;
+    uint32_t *d_perm = perm_out;
+    if (!on_device) SMH_TRY(scr.alloc(&d_perm, m->n_rows));
+    size_t comps = 0, levels = 0;
+    SMH_TRY(rcm_order(m->d_off, m->d_col, m->n_rows, m->nnz, d_perm, &comps, &levels, m->stream));
+    if (!on_device && m->n_rows) SMH_HIP(hipMemcpy(perm_out, d_perm, m->n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_components_out) *n_components_out = comps;
+    if (n_levels_out) *n_levels_out = levels;
+    return SMH_OK;
+}
+
+int smh_crs_rcm(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out) {
+    return rcm_common(m, perm_out, n_components_out, n_levels_out, false);
+}
+int smh_crs_rcm_dev(const smh_crs *m, uint32_t *perm_out_dev, size_t *n_components_out, size_t *n_levels_out) {
+    return rcm_common(m, perm_out_dev, n_components_out, n_levels_out, true);
+}
+
 // ---- #[derive(Clone)] (sparsemat_crs.rs:8) and SparseMatrix::add / sub (sparsematrix.rs:123-143, matadd.hip) ------------------
 static thread_local int g_add_route = 2;
 int smh_last_add_route(void) { return g_add_route; }

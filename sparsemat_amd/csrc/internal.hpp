@@ -445,6 +445,16 @@ int crs_get_many(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, 
 int crs_apply(int dtype, const UpdMatrix &m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
               bool force_general, UpdResult *res, hipStream_t s);
 int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hipStream_t s);
+// Reordering (permute.hip, reorder.hip; a permutation is n u32 with perm[new] = old).  Device pointers.
+// validate: `first` [n] is the caller's scratch and afterwards the inverse of perm; SMH_ERR_INVALID names the first offending position
+int validate_permutation(const uint32_t *perm, size_t n, uint32_t *first, const char *what, hipStream_t s);
+// out[i][j] = a[row_perm[i]][col_perm[j]] given col_inv = col_perm^-1 (either may be null: identity); storage order and values kept
+int permute_crs(int dtype, const uint32_t *a_off, const uint32_t *a_col, const void *a_val, size_t n_rows, size_t nnz, const uint32_t *row_perm,
+                const uint32_t *col_inv, CrsArrays *out, hipStream_t s);
+int launch_vec_permute(int dtype, void *dst, const void *src, const uint32_t *perm, size_t n, bool inverse, hipStream_t s);
+int launch_bandwidth(const uint32_t *off, const uint32_t *col, size_t n_rows, uint32_t *d_out2, hipStream_t s);  // {max i - j, max j - i}
+// the reverse Cuthill-McKee ordering of a square pattern whose columns are all below n (perm_out: n entries)
+int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, uint32_t *perm_out, size_t *n_components, size_t *n_levels, hipStream_t s);
 // A reusable update plan (matplan.hip): the sorted order and the targets of one (rows, cols, ops) stream on one structure.  Runs
 // are numbered class by class: the short ones [0, n_short), then the long ones (more than kPlanLongRun kept operations).
 constexpr uint32_t kPlanLongRun = 64;  // longest run one thread of the short-run kernel folds

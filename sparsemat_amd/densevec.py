@@ -87,6 +87,15 @@ class DenseVec:
         check(lib().smh_vec_copy(out._h, self._h))
         return out
 
+    def permute(self, perm, inverse=False):
+        """A new vector: ``out[i] = self[perm[i]]``, or with ``inverse`` ``out[perm[i]] = self[i]`` (an extension, see
+        ``SparseMatCRS.permute``): ``x.permute(p).permute(p, inverse=True)`` is ``x``."""
+        a = np.ascontiguousarray(perm, dtype=np.uint32)
+        keep = a if len(a) else np.zeros(1, np.uint32)
+        out = DenseVec.zeros(self.dim(), self._dtype)
+        check(lib().smh_vec_permute(out._h, self._h, keep.ctypes.data, len(a), 1 if inverse else 0))
+        return out
+
     # ---- Vector::add / sub / scale (densevec.rs:51-73) ------------------------------------------
     def add(self, rhs):
         check(lib().smh_vec_add(self._h, rhs._h))

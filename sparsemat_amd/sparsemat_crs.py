@@ -155,6 +155,53 @@ class SparseMatCRS:
         check(lib().smh_crs_prod(self._h, rhs._h, C.byref(h)))
         return type(self)(h, self.dtype)
 
+    # ---- reordering (an extension: the reference has none; csrc/permute.hip, csrc/reorder.hip) ---------------------------
+    @staticmethod
+    def _perm_arg(perm):
+        if perm is None:
+            return None, None, 0
+        a = np.ascontiguousarray(perm, dtype=np.uint32)
+        keep = a if len(a) else np.zeros(1, np.uint32)  # (a pointer even for an empty array: NULL means the identity)
+        return keep, keep.ctypes.data, len(a)
+
+    def permute(self, row_perm=None, col_perm=None):
+        """``out[i][j] = self[row_perm[i]][col_perm[j]]`` as a new matrix (``perm[new] = old``, scipy's ``A[perm][:, perm]``): rows
+        keep their entries in storage order, columns are relabelled, values are copied bit for bit.  None = identity."""
+        rk, rp, rn = self._perm_arg(row_perm)
+        ck, cp, cn = self._perm_arg(col_perm)
+        h = C.c_void_p()
+        check(lib().smh_crs_permute(self._h, rp, rn, cp, cn, C.byref(h)))
+        return type(self)(h, self.dtype)
+
+    def permute_symmetric(self, perm):
+        """``P A P^T``: ``permute(perm, perm)`` of a square matrix."""
+        keep, p, n = self._perm_arg(perm if perm is not None else [])
+        h = C.c_void_p()
+        check(lib().smh_crs_permute_symmetric(self._h, p, n, C.byref(h)))
+        return type(self)(h, self.dtype)
+
+    def rcm(self):
+        """The reverse Cuthill-McKee ordering of the (symmetrised) pattern, computed on the device: ``(perm, stats)`` with
+        ``perm`` an ``np.uint32`` array ready for ``permute_symmetric`` and ``stats = dict(n_components, n_levels)``.  One
+        round of kernels per level: a chain of n vertices takes n rounds."""
+        n = self.n_rows()
+        perm = np.zeros(max(n, 1), np.uint32)
+        comps, levels = C.c_size_t(), C.c_size_t()
+        check(lib().smh_crs_rcm(self._h, perm.ctypes.data, C.byref(comps), C.byref(levels)))
+        return perm[:n], dict(n_components=comps.value, n_levels=levels.value)
+
+    def bandwidth(self):
+        """(max i - j, max j - i) over the stored entries; (0, 0) without entries."""
+        lo, hi = C.c_uint32(), C.c_uint32()
+        check(lib().smh_crs_bandwidth(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def span_fraction(self):
+        """Mean column span of a 64-row tile / n_cols: the locality statistic AUTO tests."""
+        out = C.c_double()
+        check(lib().smh_crs_span_fraction(self._h, C.byref(out)))
+        return out.value
+
     def clone(self):
         """#[derive(Clone)] (sparsemat_crs.rs:8): an independent library-owned copy (dims, arrays, orphans, kernel settings)."""
         h = C.c_void_p()
