@@ -159,12 +159,16 @@ def stream_dot_partials(p, ap):
     return t
 
 
-def fused_pap(p, ap, from_first):
-    """p.Ap as the solvers fold the K1s partials (from_first: pcg.hip's workgroup sum)."""
-    parts = stream_dot_partials(p, ap)
+def fold_tile_partials(parts, from_first):
+    """The single-matrix solvers' fold of the K1s partials (from_first: pcg.hip's workgroup sum)."""
     if len(parts) > K_REDUCE_PARTIALS:
         return device_sum(parts, reduce_blocks(len(parts)), 1, from_first)
     return fold_partials(parts, from_first)
+
+
+def fused_pap(p, ap, from_first):
+    """p.Ap as the single-matrix solvers take it from the K1s epilogue."""
+    return fold_tile_partials(stream_dot_partials(p, ap), from_first)
 
 
 # ---- reductions by mode --------------------------------------------------------------------------------------------------

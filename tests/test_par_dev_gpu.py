@@ -4,7 +4,7 @@ multiplies against the shared vector, results at b * R, ONE exchange -- with the
 
 On the one-GPU box the blocks share device 0, so the PEER backend (pull kernel) carries the one-process tests; the RCCL
 call sequence runs with a lone rank (ncclCommInitRank, in-place all-gather, empty send/receive group, 1-element gathers of
-the CG folds; SMH_PAR_EXCHANGE_SINGLE=1).  The tests at the end need more than one device and run wherever there is one."""
+the CG folds; SMH_PAR_EXCHANGE_SINGLE=1; that solve bit for bit tests/par_cg_model.py with one block).  The tests at the end need more than one device and run wherever there is one."""
 import os
 import subprocess
 import sys
@@ -194,6 +194,20 @@ b, x = mc.vec(host=bh), mc.vec()
 iters, rr = mc.cg_solve_vec(b, x, tol=1e-10, iter_max=300)   # the folds go through 1-element ncclAllGathers
 ox, oit, _ = oracle.cg(nn, nn, off, col, val, bh, np.zeros(nn), tol=1e-10, iter_max=300)
 assert abs(iters - oit) <= 1 and np.abs(x.download() - ox).max() < 1e-9
+# ... and bit for bit the model of the block folds (tests/par_cg_model.py) with ONE block: every value passes through the 1-element
+# gathers and the one-value folds.  AUTO is K1s here (rows of 7 entries), its p.Ap fused; then the separate dot, 6 bodies from a random x0
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import par_cg_model
+assert lap.resolved_variant()[0] == "stream"
+want = par_cg_model.par_cg(off, col, val, bh, np.zeros(nn), 1e-10, 300, [0, nn], fused=True)
+assert iters == want.iterations and rr == want.r_norm_squared and x.download().tobytes() == want.x.tobytes(), (iters, want.iterations, rr, want.r_norm_squared)
+rng = np.random.default_rng(3)
+b2, x2 = rng.uniform(-1, 1, nn), rng.uniform(-1, 1, nn)
+for variant, fused in (("seq", False), ("stream", True)):
+    b, x = mc.vec(host=b2), mc.vec(host=x2)
+    got = mc.cg_solve_vec(b, x, tol=0.0, iter_max=6, variant=variant, check_every=4)
+    want = par_cg_model.par_cg(off, col, val, b2, x2, 0.0, 6, [0, nn], fused=fused)
+    assert got == (want.iterations, want.r_norm_squared) and x.download().tobytes() == want.x.tobytes(), (variant, got, want.r_norm_squared)
 try:
     m.set_backend("peer")
     raise SystemExit("a per-rank handle accepted the PEER backend")
@@ -211,6 +225,8 @@ def test_lone_rank_runs_the_rccl_call_sequence(gpu, tmp_path):
     script = tmp_path / "lone_rank.py"
     script.write_text(LONE_RANK % {"root": ROOT})
     env = dict(os.environ, SMH_PAR_EXCHANGE_SINGLE="1")
+    for knob in ("SMH_CG_FUSED_DOT", "SMH_STREAM_RPT"):  # (the script's model takes the K1s epilogue as the library does by itself)
+        env.pop(knob, None)
     r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "lone rank ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 

@@ -26,7 +26,9 @@ RANK = r"""
 import os, sys
 sys.path.insert(0, %(root)r)
 import numpy as np
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import oracle
+import par_cg_model
 import sparsemat_amd as sm
 from sparsemat_amd import _lib, synth
 
@@ -120,6 +122,19 @@ for dtype, tol in ((np.float64, 1e-10), (np.float32, 1e-4)):
     assert np.max(np.abs(got[r0:r1].astype(np.float64) - o_x[r0:r1])) < 10 * tol
     all_iters = comm.max(float(iters))
     assert all_iters == iters   # every rank took the same decision
+    # ... and bit for bit the model of the block folds (tests/par_cg_model.py): the ranks' values meet in the stand-in's all-gathers,
+    # every rank folds all of them; AUTO is K1s on these rows of 7 entries, p.Ap from its epilogue.  Each rank checks its own slice.
+    assert blk.resolved_variant()[0] == "stream"
+    cuts = [k * (n // world) for k in range(world)] + [n]
+    want = par_cg_model.par_cg(off, col, val, b_host, np.zeros(n, dtype), tol, 500, cuts, fused=True)
+    assert iters == want.iterations and rr == want.r_norm_squared, (dtype, iters, want.iterations, rr, want.r_norm_squared)
+    assert got[r0:r1].tobytes() == want.x[r0:r1].tobytes(), (dtype, "own slice of x")
+    x0_host = np.random.default_rng(12).uniform(-1, 1, n).astype(dtype)
+    b, x = par.vec(host=b_host), par.vec(host=x0_host)   # the separate dot (slices that start unaligned), 6 bodies from a random x0
+    got6 = par.cg_solve_vec(b, x, tol=0.0, iter_max=6, variant="seq", check_every=4)
+    want = par_cg_model.par_cg(off, col, val, b_host, x0_host, 0.0, 6, cuts)
+    assert got6 == (want.iterations, want.r_norm_squared), (dtype, got6, want.r_norm_squared)
+    assert x.download_block(0)[r0:r1].tobytes() == want.x[r0:r1].tobytes(), (dtype, "own slice of x, separate dot")
 # 6. SURVEY 8e's option for skewed matrices: blocks of equal ENTRY counts (power-law row lengths; every rank passes its first row),
 #    the plan, the exchanges (the all-gather becomes a group of broadcasts: unequal slices) and the solver's folds follow the split table
 n = 40_000
@@ -160,6 +175,8 @@ def test_ranks_on_one_device_through_the_mock(gpu, mock_so, world):
     procs = []
     for rank in range(world):
         env = dict(os.environ, LD_PRELOAD=mock_so, SMH_T_RANK=str(rank), SMH_T_WORLD=str(world), SMH_T_UID=uid)
+        for knob in ("SMH_CG_FUSED_DOT", "SMH_STREAM_RPT"):  # (the script's model takes the K1s epilogue as the library does by itself)
+            env.pop(knob, None)
         procs.append(subprocess.Popen([sys.executable, "-c", RANK % {"root": ROOT}], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     for rank, (p, (out, err)) in enumerate(zip(procs, outs)):
