@@ -110,6 +110,8 @@ def _declare(L):
                                                            C.POINTER(_sz), _u32p, _u32p, fp]
         getattr(L, "orc_crs_sort_rows_" + suf).argtypes = [_sz, _u32p, _u32p, fp]
         getattr(L, "orc_crs_sort_rows_" + suf).restype = None
+        getattr(L, "orc_spmv_lanes_" + suf).argtypes = [_sz, _u32p, _u32p, fp, fp, _sz, C.c_int, _sz, C.c_int, fp]
+        getattr(L, "orc_spmv_merge_" + suf).argtypes = [_sz, _u32p, _u32p, fp, fp, _sz, _sz, C.c_int, fp]
     L.orc_par_rows_per_block.argtypes = [_sz, _sz]
     L.orc_par_rows_per_block.restype = _sz
     L.orc_par_block_and_row.argtypes = [_sz, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz)]
@@ -191,6 +193,38 @@ def spmv_abs(offset_rows, columns, values, x):
     getattr(lib(), "orc_spmv_abs_" + suf)(len(off) - 1, _p(off, _u32p), _p(col, _u32p), _p(values, fp),
                                           _p(x, fp), _p(out, _f64p))
     return out
+
+
+# wrong variants of the two models below (sparsemat_oracle.h): only for showing that a test case tells them apart
+LANES_WRONG = {"muladd": 1, "row_grid": 2, "layout": 4, "butterfly": 8}
+MERGE_WRONG = {"fma": 1, "descending": 2, "assoc": 4}
+MERGE_TILE = 2048
+
+
+def spmv_lanes(offset_rows, columns, values, x, lanes, tail_from=None, wrong=0):
+    """y = A.x in the summation order of the lane-group kernels K1 / K1r with ``lanes`` lanes per row (orc_spmv_lanes).
+    tail_from (K1r on borrowed, unpadded arrays: nnz & ~3): the entries from there on are appended after the lane sums."""
+    values = np.ascontiguousarray(values)
+    suf, fp = _suf(values.dtype)
+    off, col = _c(offset_rows, np.uint32), _c(columns, np.uint32)
+    x = _c(x, values.dtype)
+    y = np.zeros(len(off) - 1, dtype=values.dtype)
+    nnz = int(off[-1])
+    _check(getattr(lib(), "orc_spmv_lanes_" + suf)(len(off) - 1, _p(off, _u32p), _p(col, _u32p), _p(values, fp), _p(x, fp), len(x),
+                                                    int(lanes), nnz if tail_from is None else int(tail_from), int(wrong), _p(y, fp)))
+    return y
+
+
+def spmv_merge(offset_rows, columns, values, x, tile_items=MERGE_TILE, wrong=0):
+    """y = A.x in the summation order of the merge-path kernel K2 (orc_spmv_merge) for tiles of ``tile_items`` merge items."""
+    values = np.ascontiguousarray(values)
+    suf, fp = _suf(values.dtype)
+    off, col = _c(offset_rows, np.uint32), _c(columns, np.uint32)
+    x = _c(x, values.dtype)
+    y = np.zeros(len(off) - 1, dtype=values.dtype)
+    _check(getattr(lib(), "orc_spmv_merge_" + suf)(len(off) - 1, _p(off, _u32p), _p(col, _u32p), _p(values, fp), _p(x, fp), len(x),
+                                                    int(tile_items), int(wrong), _p(y, fp)))
+    return y
 
 
 def mat_inner_prod(offset_rows, columns, values, lhs, rhs):

@@ -720,3 +720,185 @@ DEF_PROD(f64, double)
 
 DEF_PCG(f32, float)
 DEF_PCG(f64, double)
+
+/* ======================================================================= *
+ * Summation-order models of the device's own product kernels (they restate
+ * the BUILD, not a reference function: the reference sums a row in storage
+ * order, orc_spmv).  fmaf / fma are correctly rounded; every other operation
+ * is one IEEE operation (-ffp-contract=off).  `wrong` is 0 for the kernels'
+ * order; its bits select deliberately wrong variants, which exist only so
+ * that the tests can show that their cases tell each of them apart.
+ *
+ * Lane-group kernels (K1, spmv_vector.hip; K1r, spmv_ring2.hip), L = lanes:
+ *   - entry slots are counted from sa = s & ~3 of the row [s, e): the grid of
+ *     4-entry chunks is anchored at element 0 of the arrays;
+ *   - f32: lane j owns the chunks j, j + L, j + 2L, ... of the row;
+ *     f64: lane j owns slots 2j, 2j+1, 2L+2j, 2L+2j+1 of every 4L slots;
+ *   - a lane folds its entries in ascending order, sum = fma(val, x[col], sum)
+ *     from +0; slots outside [s, e) take no part;
+ *   - butterfly sum_j += sum_(j ^ o), o = L/2 ... 1, in all lanes; y = lane 0;
+ *   - tail_from < nnz (K1r on unpadded arrays, tail_from = nnz & ~3): the lanes
+ *     see the entries below tail_from only, the others are appended to their
+ *     rows' results one by one, y = fma(val, x[col], y), in storage order.
+ * ======================================================================= */
+#define DEF_LANES(SUF, T, FMA)                                                                      \
+    int orc_spmv_lanes_##SUF(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns,   \
+                             const T *values, const T *x, size_t x_len, int lanes,                  \
+                             size_t tail_from, int wrong, T *y) {                                   \
+        if (lanes < 1 || lanes > 64 || (lanes & (lanes - 1))) return ORC_ERR_SIZE_MISMATCH;          \
+        const size_t L = (size_t)lanes;                                                             \
+        const int pairs = (sizeof(T) == 8) != ((wrong & ORC_LANES_WRONG_LAYOUT) != 0);              \
+        for (size_t r = 0; r < n_rows; ++r) {                                                       \
+            const size_t s = offset_rows[r], e = offset_rows[r + 1];                                \
+            const size_t sl = s < tail_from ? s : tail_from, el = e < tail_from ? e : tail_from;    \
+            const size_t sa = (wrong & ORC_LANES_WRONG_GRID) ? sl : (sl & ~(size_t)3);              \
+            T sum[64];                                                                              \
+            for (size_t j = 0; j < L; ++j) sum[j] = (T)0;                                           \
+            for (size_t k = sl; k < el; ++k) {                                                      \
+                if (columns[k] >= x_len) return ORC_ERR_INDEX_OOB;                                  \
+                const size_t slot = k - sa, p = slot % (4 * L);                                     \
+                const size_t j = pairs ? (p % (2 * L)) / 2 : p / 4;                                 \
+                if (wrong & ORC_LANES_WRONG_MULADD) {                                               \
+                    const T t = values[k] * x[columns[k]];                                          \
+                    sum[j] = sum[j] + t;                                                            \
+                } else {                                                                            \
+                    sum[j] = FMA(values[k], x[columns[k]], sum[j]);                                 \
+                }                                                                                   \
+            }                                                                                       \
+            for (size_t step = L / 2; step > 0; step >>= 1) {                                       \
+                const size_t o = (wrong & ORC_LANES_WRONG_BUTTERFLY) ? (L / 2) / step : step;       \
+                T next[64];                                                                         \
+                for (size_t j = 0; j < L; ++j) next[j] = sum[j] + sum[j ^ o];                       \
+                for (size_t j = 0; j < L; ++j) sum[j] = next[j];                                    \
+            }                                                                                       \
+            T out = sum[0];                                                                         \
+            for (size_t k = s > el ? s : el; k < e; ++k) {                                          \
+                if (columns[k] >= x_len) return ORC_ERR_INDEX_OOB;                                  \
+                out = FMA(values[k], x[columns[k]], out);                                           \
+            }                                                                                       \
+            y[r] = out;                                                                             \
+        }                                                                                           \
+        return ORC_OK;                                                                              \
+    }
+
+DEF_LANES(f32, float, fmaf)
+DEF_LANES(f64, double, fma)
+
+/* ----------------------------------------------------------------------- *
+ * Merge-path kernel (K2, spmv_merge.hip).  The merge of the row ends with the
+ * entry indices is cut into tiles of tile_items items (the kernel: 2048; a
+ * multiple of 512 here), start coordinates from orc_merge_path_search.
+ *   - one thread per 8 consecutive items of a tile, 64 threads per wave,
+ *     tile_items / 512 waves;
+ *   - an item is a product val * x[col], rounded on its own and added to the
+ *     thread's running sum, or the end of a row: the running sum is the row's
+ *     (the thread's first one: without what earlier threads hold of that row)
+ *     and restarts from +0;
+ *   - the sums still open at the threads' ends go through a segmented
+ *     inclusive Hillis-Steele scan of the wave (o = 1, 2, ... 32; sv = pv + sv
+ *     where the lane has finished no row), a thread that finished a row
+ *     starts a segment; the waves' totals are chained in wave order;
+ *   - a thread's first finished row is carry_in + first_val, carry_in the
+ *     inclusive value of the thread before it;
+ *   - the row open at a tile's end keeps the last thread's inclusive value as
+ *     the tile's carry; a row's carries are folded in tile order from +0 and
+ *     added as y[r] = acc + y[r].
+ * ----------------------------------------------------------------------- */
+#define DEF_MERGE(SUF, T, FMA)                                                                      \
+    int orc_spmv_merge_##SUF(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns,   \
+                             const T *values, const T *x, size_t x_len, size_t tile_items,          \
+                             int wrong, T *y) {                                                     \
+        if (tile_items == 0 || tile_items % 512) return ORC_ERR_SIZE_MISMATCH;                      \
+        const size_t nnz = n_rows ? offset_rows[n_rows] : 0;                                        \
+        const size_t items = n_rows + nnz, n_tiles = (items + tile_items - 1) / tile_items;         \
+        const size_t threads = tile_items / 8, waves = threads / 64;                                \
+        for (size_t k = 0; k < nnz; ++k) if (columns[k] >= x_len) return ORC_ERR_INDEX_OOB;          \
+        for (size_t r = 0; r < n_rows; ++r) y[r] = (T)0;                                            \
+        if (n_tiles == 0) return ORC_OK;                                                            \
+        uint64_t *diag = (uint64_t *)malloc((n_tiles + 1) * sizeof(uint64_t));                      \
+        uint32_t *tile_row = (uint32_t *)malloc((n_tiles + 1) * sizeof(uint32_t));                  \
+        uint32_t *tile_nz = (uint32_t *)malloc((n_tiles + 1) * sizeof(uint32_t));                   \
+        uint32_t *carry_row = (uint32_t *)malloc(n_tiles * sizeof(uint32_t));                       \
+        T *carry_val = (T *)malloc(n_tiles * sizeof(T));                                            \
+        T *sv = (T *)malloc(threads * sizeof(T)), *nv = (T *)malloc(threads * sizeof(T));           \
+        T *first_val = (T *)malloc(threads * sizeof(T)), *incl = (T *)malloc(threads * sizeof(T));  \
+        int *sf = (int *)malloc(threads * sizeof(int)), *nf = (int *)malloc(threads * sizeof(int)); \
+        int *emitted = (int *)malloc(threads * sizeof(int));                                        \
+        size_t *first_row = (size_t *)malloc(threads * sizeof(size_t));                             \
+        for (size_t t = 0; t <= n_tiles; ++t) diag[t] = (uint64_t)t * tile_items;                   \
+        orc_merge_path_search(n_rows, nnz, offset_rows, n_tiles + 1, diag, tile_row, tile_nz);      \
+        for (size_t tile = 0; tile < n_tiles; ++tile) {                                             \
+            const size_t row1 = tile_row[tile + 1];                                                 \
+            const size_t n_it = (row1 - tile_row[tile]) + (tile_nz[tile + 1] - tile_nz[tile]);      \
+            size_t row = tile_row[tile], k = tile_nz[tile], it = 0;   /* the walk along the path */ \
+            for (size_t t = 0; t < threads; ++t) {                                                  \
+                T running = (T)0;                                                                   \
+                emitted[t] = 0;                                                                     \
+                first_val[t] = (T)0;                                                                \
+                first_row[t] = 0;                                                                   \
+                for (int i = 0; i < 8 && it < n_it; ++i, ++it) {                                    \
+                    if (row >= n_rows || k < offset_rows[row + 1]) {                                \
+                        if (wrong & ORC_MERGE_WRONG_FMA) {                                          \
+                            running = FMA(values[k], x[columns[k]], running);                       \
+                        } else {                                                                    \
+                            const T prod = values[k] * x[columns[k]];                               \
+                            running = running + prod;                                               \
+                        }                                                                           \
+                        ++k;                                                                        \
+                    } else {                                                                        \
+                        if (!emitted[t]) { first_val[t] = running; first_row[t] = row; emitted[t] = 1; } \
+                        else y[row] = running;                                                      \
+                        running = (T)0;                                                             \
+                        ++row;                                                                      \
+                    }                                                                               \
+                }                                                                                   \
+                sv[t] = running;                                                                    \
+                sf[t] = emitted[t];                                                                 \
+            }                                                                                       \
+            for (size_t o = 1; o < 64; o <<= 1) {                                                   \
+                for (size_t t = 0; t < threads; ++t) {                                              \
+                    nv[t] = sv[t];                                                                  \
+                    nf[t] = sf[t];                                                                  \
+                    if (t % 64 >= o) {                                                              \
+                        if (!sf[t]) nv[t] = sv[t - o] + sv[t];                                      \
+                        nf[t] = sf[t] | sf[t - o];                                                  \
+                    }                                                                               \
+                }                                                                                   \
+                memcpy(sv, nv, threads * sizeof(T));                                                \
+                memcpy(sf, nf, threads * sizeof(int));                                              \
+            }                                                                                       \
+            T prefix = (T)0;                                                                        \
+            for (size_t w = 0; w < waves; ++w) {                                                    \
+                for (size_t t = w * 64; t < w * 64 + 64; ++t) incl[t] = sf[t] ? sv[t] : prefix + sv[t]; \
+                for (size_t t = w * 64; t < w * 64 + 64; ++t) {                                     \
+                    const T carry_in = t % 64 ? incl[t - 1] : prefix;                               \
+                    if (emitted[t]) y[first_row[t]] = carry_in + first_val[t];                      \
+                }                                                                                   \
+                prefix = sf[w * 64 + 63] ? sv[w * 64 + 63] : prefix + sv[w * 64 + 63];              \
+            }                                                                                       \
+            carry_row[tile] = row1 < n_rows ? (uint32_t)row1 : ORC_UNSET;                           \
+            carry_val[tile] = incl[threads - 1];                                                    \
+        }                                                                                           \
+        for (size_t t = 0; t < n_tiles; ++t) {                                                      \
+            const uint32_t r = carry_row[t];                                                        \
+            if (r == ORC_UNSET || (t > 0 && carry_row[t - 1] == r)) continue;                       \
+            size_t u1 = t;                                                                          \
+            while (u1 < n_tiles && carry_row[u1] == r) ++u1;                                        \
+            if (wrong & ORC_MERGE_WRONG_ASSOC) {        /* c_t + (c_t+1 + (... + y)) */             \
+                T acc = y[r];                                                                       \
+                for (size_t u = u1; u-- > t;) acc = carry_val[u] + acc;                             \
+                y[r] = acc;                                                                         \
+            } else {                                                                                \
+                T acc = (T)0;                                                                       \
+                if (wrong & ORC_MERGE_WRONG_DESCENDING) for (size_t u = u1; u-- > t;) acc = acc + carry_val[u]; \
+                else for (size_t u = t; u < u1; ++u) acc = acc + carry_val[u];                      \
+                y[r] = acc + y[r];                                                                  \
+            }                                                                                       \
+        }                                                                                           \
+        free(diag); free(tile_row); free(tile_nz); free(carry_row); free(carry_val); free(sv); free(nv); \
+        free(first_val); free(incl); free(sf); free(nf); free(emitted); free(first_row);            \
+        return ORC_OK;                                                                              \
+    }
+
+DEF_MERGE(f32, float, fmaf)
+DEF_MERGE(f64, double, fma)

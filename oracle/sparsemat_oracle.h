@@ -187,6 +187,27 @@ void orc_merge_path_search(size_t n_rows, size_t nnz, const uint32_t *offset_row
                            size_t n_diagonals, const uint64_t *diagonals, uint32_t *row_out,
                            uint32_t *nnz_out);
 
+/* ---- summation-order models of the device's own product kernels (restate the build) ---- */
+/* `wrong`: 0 = the kernels' order; the bits below select deliberately wrong variants for the tests' sensitivity checks. */
+#define ORC_LANES_WRONG_MULADD 1    /* product rounded, then added, instead of one FMA */
+#define ORC_LANES_WRONG_GRID 2      /* chunk grid anchored at the row start */
+#define ORC_LANES_WRONG_LAYOUT 4    /* the other value type's slot layout */
+#define ORC_LANES_WRONG_BUTTERFLY 8 /* butterfly ascending, o = 1 ... L/2 */
+#define ORC_MERGE_WRONG_FMA 1        /* FMA instead of product, then add */
+#define ORC_MERGE_WRONG_DESCENDING 2 /* a row's carries folded in descending tile order */
+#define ORC_MERGE_WRONG_ASSOC 4      /* c_t + (c_t+1 + (... + y[r])) instead of (c_t + c_t+1 + ...) + y[r] */
+/* K1 / K1r with `lanes` (1, 2, 4, ... 64) lanes per row.  tail_from: entries from this index on are appended to their rows
+ * after the lane sums (K1r on unpadded arrays: nnz & ~3); pass nnz (or more) for none. */
+int orc_spmv_lanes_f32(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns, const float *values,
+                       const float *x, size_t x_len, int lanes, size_t tail_from, int wrong, float *y);
+int orc_spmv_lanes_f64(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns, const double *values,
+                       const double *x, size_t x_len, int lanes, size_t tail_from, int wrong, double *y);
+/* K2 with tiles of tile_items merge items (the kernel: 2048; a multiple of 512), 8 items per thread, 64 threads per wave */
+int orc_spmv_merge_f32(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns, const float *values,
+                       const float *x, size_t x_len, size_t tile_items, int wrong, float *y);
+int orc_spmv_merge_f64(size_t n_rows, const uint32_t *offset_rows, const uint32_t *columns, const double *values,
+                       const double *x, size_t x_len, size_t tile_items, int wrong, double *y);
+
 #ifdef __cplusplus
 }
 #endif

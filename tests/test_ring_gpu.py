@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import kernel_forms
 import oracle
 import sparsemat_amd as sm
 from sparsemat_amd import synth
@@ -90,24 +91,8 @@ def test_ring_plan_and_parity_generated(gpu, dtype, pattern, n, k):
 def test_ring_mixed_phases_random(gpu, dtype):
     """Blocks of narrow-band rows interleaved with wide rows, empty rows and a window that jumps
     backwards: ring phases, restarts and global-gather phases in one matrix."""
-    rng = np.random.default_rng(99)
-    n_rows, n_cols = 40_000, 300_000
-    lens = rng.integers(0, 40, size=n_rows)
-    lens[5000:5600] = 0
-    off = np.zeros(n_rows + 1, dtype=np.uint32)
-    np.cumsum(lens, out=off[1:])
-    col = np.empty(int(off[-1]), dtype=np.uint32)
-    centers = np.linspace(0, n_cols - 1, n_rows)
-    centers[20_000:30_000] = np.linspace(100_000, 0, 10_000)  # runs backwards
-    for i in range(n_rows):
-        a, b = off[i], off[i + 1]
-        if 12_000 <= i < 12_128 or i % 1777 == 0:  # wide rows: span the whole vector
-            col[a:b] = rng.integers(0, n_cols, size=b - a)
-        else:
-            lo = int(max(0, centers[i] - 1500))
-            col[a:b] = rng.integers(lo, min(n_cols, lo + 3000), size=b - a)
-    val = rng.uniform(-1, 1, size=len(col)).astype(dtype)
-    x = rng.uniform(-1, 1, size=n_cols).astype(dtype)
+    n_cols, off, col, val, x = kernel_forms.mixed_phases(dtype)  # (shared with tests/test_spmv_order_gpu.py)
+    n_rows = len(off) - 1
     m = sm.SparseMatCRS.from_raw_parts(n_rows, n_cols, off, col, val)
     frac, _ = check_plan(m, off, col)
     assert 0.5 < frac < 1.0

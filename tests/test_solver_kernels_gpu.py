@@ -3,7 +3,10 @@ the form it is named for (asserted through the handle's own getters, before and 
 bodies, f64(r.r) and BiCGSTAB's breakdown code equal tests/cg_model.py / tests/bicgstab_model.py in "device" mode, the model
 taking every product -- the initial residual's included -- from the DEVICE's eager product of the same variant on the same
 handle (device_product), which is held to the suite's parity bound against the oracle (util.assert_spmv_close) before the
-model may use it.  So the model is never anchored to the code under test alone, and no tolerance appears in this file.
+model may use it -- and, for the vector family and merge, to the oracle's CPU model of the kernel's own summation order
+(oracle.spmv_lanes / oracle.spmv_merge, pinned in tests/test_spmv_order_model.py) bit for bit in every row.  So the model is never
+anchored to the code under test alone, and no tolerance appears in this file.  The matrices and CONFIGS live in
+tests/kernel_forms.py, shared with tests/test_spmv_order_gpu.py.
 
 The statement per case: x0 random, tol = 0, iter_max = 11; check_every = 4 on the DenseVec entry points (three replays of the
 captured batch, the last body a no-op) and the default on the host entry points (CG 4; PCG and BiCGSTAB 8: one replay and three
@@ -27,10 +30,7 @@ band(20 000, 4000, 31 | 32) for K1 and the single-window K1r forms; band(48 000,
 rows the 16 384-column ring still serves 53 % of the rows and the plan keeps it); stencil7(130 x 130 x 6) for the banded ring (a
 48 x 48 x 24 grid fits one window); scattered(40 000) for merge (316 tiles), K2c (5 blocks of 8192 columns) and K2t (3 slices),
 without its hubs for K2f; arrowhead(8000) for K2s (40 long rows); 24^3 for K1s (the stage forced: x is under 1 MB)."""
-import contextlib
-import functools
 import math
-import os
 
 import numpy as np
 import pytest
@@ -40,278 +40,41 @@ import bicgstab_model as bm
 import cg_model
 import oracle
 import sparsemat_amd as sm
+from kernel_forms import CONFIGS, F32, F64, env, same
 from util import assert_spmv_close
 
 pytestmark = pytest.mark.gpu
 
-F32, F64 = np.float32, np.float64
 ITER_MAX = 11
 CHECK_EVERY = 4
 
 
-@contextlib.contextmanager
-def env(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-# ---- the matrices ------------------------------------------------------------------------------------------------------------
-def crs_from_pattern(n, rows, cols, zero, dtype, shuffle_seed=None):
-    """(off, col, val) from the distinct positions (rows[k], cols[k]) -- every diagonal position among them.  zero[k]: a stored
-    0.0.  Off-diagonal values -w(min(i, j), max(i, j)), w in (0, 1): symmetric; a_ii = 1 + sum_j |a_ij| (summed in f64 from the
-    rounded off-diagonals).  Rows ascending, or in random order (shuffle_seed)."""
-    rows, cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
-    minor = cols if shuffle_seed is None else np.random.default_rng(shuffle_seed).permutation(len(rows))
-    order = np.lexsort((minor, rows))
-    rows, cols, zero = rows[order], cols[order], np.asarray(zero, bool)[order]
-    lo, hi = np.minimum(rows, cols), np.maximum(rows, cols)
-    w = ((lo * 2654435761 + hi * 40503) % 1000003 + 1) / 1000004.0
-    val = np.where(zero | (rows == cols), 0.0, -w).astype(dtype)
-    diag = 1.0 + np.bincount(rows, weights=np.abs(val.astype(np.float64)), minlength=n)
-    on_diag = rows == cols
-    assert on_diag.sum() == n and not zero[on_diag].any()
-    val[on_diag] = diag.astype(dtype)
-    off = np.zeros(n + 1, np.uint32)
-    np.cumsum(np.bincount(rows, minlength=n), out=off[1:])
-    return off, cols.astype(np.uint32), val
-
-
-@functools.lru_cache(maxsize=None)
-def band_pattern(n, w, length):
-    rng = np.random.default_rng(n + w)
-    d = np.concatenate([[1], np.sort(rng.choice(np.arange(2, w), 13, replace=False)), [w]])
-    offs = np.concatenate([-d[::-1], [0], d])
-    taken = set(offs.tolist())
-    free = [t for k in range(2, 60) for t in (k, -k) if t not in taken]  # where the stored zeros go: next to the diagonal
-    i = np.arange(n)
-    cand = i[:, None] + offs[None, :]
-    valid = (cand >= 0) & (cand < n)
-    rows = [np.broadcast_to(i[:, None], cand.shape)[valid]]
-    cols = [cand[valid]]
-    zero = [np.zeros(int(valid.sum()), bool)]
-    need = length - valid.sum(axis=1)
-    inner = np.flatnonzero((need == 1) & (i + free[0] < n))  # (length 32: one zero per row, to the right where there is room)
-    rows.append(inner)
-    cols.append(inner + free[0])
-    zero.append(np.ones(len(inner), bool))
-    need[inner] = 0
-    pr, pc = [], []
-    for r in np.flatnonzero(need):
-        got = [r + t for t in free if 0 <= r + t < n][:need[r]]
-        assert len(got) == need[r]
-        pr += [r] * len(got)
-        pc += got
-    rows.append(np.array(pr, np.int64))
-    cols.append(np.array(pc, np.int64))
-    zero.append(np.ones(len(pr), bool))
-    return np.concatenate(rows), np.concatenate(cols), np.concatenate(zero)
-
-
-def band(n, w, length, dtype):
-    off, col, val = crs_from_pattern(n, *band_pattern(n, w, length), dtype)
-    assert (np.diff(off.astype(np.int64)) == length).all() and int(np.abs(col.astype(np.int64) - np.repeat(np.arange(n), length)).max()) == w
-    return off, col, val
-
-
-def symmetric_positions(n, r, c):
-    """the distinct positions (i, j), (j, i) of the pairs and the whole diagonal"""
-    lo, hi = np.minimum(r, c), np.maximum(r, c)
-    key = np.unique(lo[lo != hi] * n + hi[lo != hi])
-    lo, hi = key // n, key % n
-    d = np.arange(n)
-    return np.concatenate([lo, hi, d]), np.concatenate([hi, lo, d])
-
-
-@functools.lru_cache(maxsize=None)
-def scattered_pattern(n, hubs):
-    rng = np.random.default_rng(n)
-    r, c = [np.repeat(np.arange(n), 4)], [rng.integers(0, n, 4 * n)]
-    if hubs:
-        for h in range(0, n, 997):
-            r.append(np.full(3000, h))
-            c.append(rng.choice(n, 3000, replace=False))
-    return symmetric_positions(n, np.concatenate(r), np.concatenate(c))
-
-
-def scattered(n, dtype, hubs=True):
-    rows, cols = scattered_pattern(n, hubs)
-    return crs_from_pattern(n, rows, cols, np.zeros(len(rows), bool), dtype, shuffle_seed=1)
-
-
-@functools.lru_cache(maxsize=None)
-def arrowhead_pattern(n):
-    rng = np.random.default_rng(n)
-    r, c = [np.repeat(np.arange(n), 2)], [rng.integers(0, n, 2 * n)]
-    for h in range(n // 80, n, n // 40):
-        r.append(np.full(2000, h))
-        c.append(rng.choice(n, 2000, replace=False))
-    return symmetric_positions(n, np.concatenate(r), np.concatenate(c))
-
-
-def arrowhead(n, dtype):
-    rows, cols = arrowhead_pattern(n)
-    return crs_from_pattern(n, rows, cols, np.zeros(len(rows), bool), dtype, shuffle_seed=2)
-
-
-def stencil7(g, dtype):
-    off, col, _ = oracle.laplace3d(*g, dtype)
-    n = len(off) - 1
-    rows = np.repeat(np.arange(n), np.diff(off.astype(np.int64)))
-    got = crs_from_pattern(n, rows, col, np.zeros(len(col), bool), dtype)
-    assert np.array_equal(got[0], off) and np.array_equal(got[1], col)  # (the oracle's rows are ascending already)
-    return got
-
-
-# ---- the configurations ------------------------------------------------------------------------------------------------------
-class Config:
-    """build(dtype) -> (off, col, val); variant; knobs(m): the handle's setters; env: the environment knobs, set through the whole
-    case; check(m): what the getters must report (asserted after prepare and again after the solves); fused: CG and PCG take p.Ap
-    from the K1s epilogue; same_as: an "auto" case's explicitly named variant, whose solves must give the same bytes."""
-
-    def __init__(self, build, variant, check, knobs=None, env=None, dtypes=(F32, F64), fused=False, same_as=None, stop=F32):
-        self.build, self.variant, self.check, self.knobs, self.env = build, variant, check, knobs or (lambda m: None), env or {}
-        self.dtypes, self.fused, self.same_as, self.stop = dtypes, fused, same_as, stop
-
-
-NO_RING_ENV = dict(SMH_RING_COL16=None, SMH_RING_COL12=None)
-
-
-def k1(lanes):
-    def knobs(m):
-        m.set_ring(0)
-        m.set_vector_lanes(lanes)
-
-    def check(m):
-        assert m.resolved_variant() == ("vector", lanes) and not m.ring_plan()[2] and m.ring_column_form() == "u32"
-    return knobs, check
-
-
-def ring(form, entries=16384, bands=1, force=True):
-    def knobs(m):
-        if force:
-            m.set_ring(1)
-
-    def check(m):
-        assert m.ring_plan()[2] and m.ring_plan()[1] >= 0.5, m.ring_plan()[:3]   # active, and most rows served from the ring
-        assert (m.ring_column_form(), m.ring_entries(), m.ring_bands()) == (form, entries, bands)
-    return knobs, check
-
-
-def blocks13(m):
-    m.set_colblock_shift(13)
-
-
-def check_merge(m):
-    assert len(m.merge_table()[0]) - 1 > 1
-
-
-def check_colblock(m):
-    assert m.colblock(arrays=False)["n_blocks"] == 5
-
-
-def check_colfused(m):
-    cf = m.colfused(arrays=False)
-    assert cf["fits"] and cf["n_blocks"] == 5, cf  # (fits: K2f itself runs, not the fall-through to the per-block launches)
-
-
-def check_colsplit(m):
-    sp = m.colsplit()
-    assert sp["split"] and sp["n_long"] == 40 and sp["long"][0] == 40 and sp["short"][0] == m.n_rows(), (sp["split"], sp["n_long"])
-
-
-def check_tiled(m):
-    assert m.tiled_layout()["n_slices"] == 3
-
-
-def stream_form(xs, direct, n_dict):
-    def check(m):
-        lay = m.stream_layout()
-        assert lay["coded"] and (lay["xs_chunks"] in (2, 4)) == xs and lay["xs_chunks"] in (0, 2, 4), lay
-        assert m.stream_direct() == direct and len(m.stream_value_dict()) == n_dict
-    return check
-
-
-def stream_knobs(xs, direct=-1, vdict=-1):
-    def knobs(m):
-        m.set_stream_xs(xs)
-        m.set_stream_direct(direct)
-        m.set_stream_value_dict(vdict)
-    return knobs
-
-
-def resolves_to(name, then=lambda m: None):
-    def check(m):
-        assert m.resolved_variant()[0] == name
-        then(m)
-    return check
-
-
-def laplace24(dtype):
-    return oracle.laplace3d(24, 24, 24, dtype)
-
-
-B31 = functools.partial(band, 20_000, 4000, 31)
-B32 = functools.partial(band, 20_000, 4000, 32)
-S = functools.partial(scattered, 40_000)
-A = functools.partial(arrowhead, 8000)
-
-CONFIGS = {
-    # 1. K1 without the ring
-    "k1-lanes1": Config(B31, "vector", k1(1)[1], k1(1)[0], NO_RING_ENV),
-    "k1-lanes8": Config(B32, "vector", k1(8)[1], k1(8)[0], NO_RING_ENV, stop=F64),
-    "k1-lanes32": Config(B31, "vector", k1(32)[1], k1(32)[0], NO_RING_ENV),
-    # 2. K1r on one sliding window of 16384 columns, by column form (col12 forced on rows of 31: every chunk straddles two rows, so
-    #    every chunk leaves the code through the escape table)
-    "k1r-u32": Config(B32, "vector", ring("u32")[1], ring("u32")[0], dict(SMH_RING_COL16="0", SMH_RING_COL12=None), stop=F64),
-    "k1r-col16": Config(B32, "vector", ring("col16")[1], ring("col16")[0], dict(SMH_RING_COL16=None, SMH_RING_COL12="0")),
-    "k1r-col12-forced": Config(B31, "vector", ring("col12")[1], ring("col12")[0], dict(SMH_RING_COL16=None, SMH_RING_COL12="1"), (F32,)),
-    # 3. ... and the compact form taken by itself (neither variable set, the ring not forced)
-    "k1r-col12-auto": Config(B32, "vector", ring("col12")[1], ring("col12", force=False)[0], NO_RING_ENV, (F32,)),
-    # 4. the wide ring: offsets up to 10 000, 20 064 columns under a 64-row tile.  48 000 rows: near the matrix' edges the band is
-    #    cut off, 16 384 columns still hold about 16 000 rows' tiles, and the plan goes wide only where they are under half of the
-    #    rows (at 30 000 rows the 16 384-column ring serves 53 % and stays)
-    "k1r-wide": Config(functools.partial(band, 48_000, 10_000, 32), "vector", ring("col16", 32768)[1], ring("col16", 32768)[0], NO_RING_ENV, (F32,)),
-    # 5. the banded ring: planes of 130 x 130 = 16 900 rows, so a tile's three column intervals lie further apart than any single
-    #    window reaches (33 864 columns; the wide ring holds 32 768), and six planes, so that the rows of the two boundary planes,
-    #    which the wide ring does hold, are a third of all
-    "k1r-banded": Config(functools.partial(stencil7, (130, 130, 6)), "vector", ring("col16", 16384, 4)[1], ring("col16", 16384, 4)[0], NO_RING_ENV,
-                         stop=F64),
-    "merge": Config(S, "merge", check_merge),                                                   # 6.
-    "colblock": Config(S, "colblock", check_colblock, blocks13, stop=F64),                     # 7.
-    "colfused": Config(functools.partial(scattered, 40_000, hubs=False), "colfused", check_colfused, blocks13),  # 8.
-    "colsplit": Config(A, "colsplit", check_colsplit, stop=F64),                                # 9.
-    "tiled": Config(S, "tiled", check_tiled),                                                   # 10.
-    # 11. the K1s forms (x is far below the size at which the stage is automatic: forced)
-    "k1s-xdv": Config(laplace24, "stream", stream_form(True, True, 2), stream_knobs(1), fused=True),
-    "k1s-xd": Config(laplace24, "stream", stream_form(True, True, 0), stream_knobs(1, -1, 0), fused=True, stop=F64),
-    "k1s-xs": Config(laplace24, "stream", stream_form(True, False, 0), stream_knobs(1, 0), fused=True),
-    "k1s-plain": Config(laplace24, "stream", stream_form(False, False, 0), stream_knobs(0), fused=True, stop=F64),
-    # 12. what AUTO takes by itself
-    "auto-band": Config(B32, "auto", resolves_to("vector", ring("col12")[1]), env=NO_RING_ENV, dtypes=(F32,), same_as="vector"),
-    "auto-arrowhead": Config(A, "auto", resolves_to("merge", check_merge), same_as="merge"),
-    "auto-laplace": Config(laplace24, "auto", resolves_to("stream", stream_form(False, False, 0)), fused=True, same_as="stream", stop=F64),
-}
 CASES = [pytest.param(name, dt, id="%s-%s" % (name, "f32" if dt == F32 else "f64")) for name, c in CONFIGS.items() for dt in c.dtypes]
 
 
 # ---- the device's product, checked -------------------------------------------------------------------------------------------
+def order_model(m, variant, off, col, val):
+    """The CPU model of the device's own summation order for the lane-group kernels (oracle.spmv_lanes at the handle's lanes; the
+    arrays are owned, hence padded: K1r has no tail) and the merge-path kernel (oracle.spmv_merge); None for the other families,
+    which test_stream_gpu.py, test_colblock_gpu.py and test_tiled_gpu.py pin."""
+    family, lanes = m.resolved_variant()
+    if variant != "auto":
+        family = variant
+    if family == "vector":
+        return lambda v: oracle.spmv_lanes(off, col, val, v, lanes)
+    if family == "merge":
+        assert m.merge_table()[2] == oracle.MERGE_TILE
+        return lambda v: oracle.spmv_merge(off, col, val, v)
+    return None
+
+
 def device_product(m, variant, off, col, val):
     """product(v) = m.mvp(v, variant) computed eagerly on the device, handed on only after util.assert_spmv_close has held it to the
-    parity bound against the oracle's product.  (A vector met before is answered from the first, checked, product: the stop
-    cases walk the same iterates again.)"""
+    parity bound against the oracle's product and -- vector family and merge -- after it has equalled the CPU model of the kernel's
+    summation order in every row, bit for bit.  (A vector met before is answered from the first, checked, product: the stop cases
+    walk the same iterates again.)"""
     seen = {}
+    model = order_model(m, variant, off, col, val)
 
     def product(v):
         v = np.ascontiguousarray(v, val.dtype)
@@ -319,6 +82,10 @@ def device_product(m, variant, off, col, val):
         if key not in seen:
             y = m.mvp(v, variant=variant)
             assert_spmv_close(y, off, col, val, v, "solver product, variant %s" % variant)
+            if model is not None:
+                want = model(v)
+                bad = np.flatnonzero(y != want)
+                assert same(y, want), ("the device's product is not the model's", variant, len(bad), bad[:5], y[bad[:5]], want[bad[:5]])
             seen[key] = y
         return seen[key].copy()
     return product
@@ -344,16 +111,6 @@ def assert_products_reproducible(m, variant, x):
 
 
 # ---- the solvers -------------------------------------------------------------------------------------------------------------
-def same(a, b):
-    """bit equality (any NaN equals any NaN: its sign and payload are not arithmetic)"""
-    a, b = np.atleast_1d(np.asarray(a)), np.atleast_1d(np.asarray(b))
-    if a.dtype != b.dtype or a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    u = np.uint32 if a.dtype == np.float32 else np.uint64
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(u)[~na], b.view(u)[~nb]))
-
-
 def run_host(solver, a, b, x0):
     x = x0.copy()
     solver.solve(a, b, x)
