@@ -1,8 +1,8 @@
 // capi.hip -- extern "C" boundary of libsparsemat_hip.so (see include/sparsemat_hip.h).
 //
 // Host-side logic only: argument checks with the reference's panic conditions, HBM residency of
-// the CRS arrays, kernel-variant selection, the CG driver loop.  No CPU compute path exists here:
-// every entry point that computes needs a HIP device.
+// the CRS arrays, handle creation.  What a handle derives is built in crs_forms.hip; which kernel a product runs and its
+// launches are spmv_dispatch.hip's.  No CPU compute path exists here: every entry point that computes needs a HIP device.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -12,7 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "internal.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -24,6 +24,8 @@ void set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
 }
+
+void clear_error() { g_err[0] = 0; }
 
 int fail(int status, const char *fmt, ...) {
     va_list ap;
@@ -72,927 +74,12 @@ int synth_fill(int dtype, uint64_t seed, size_t n_cols, size_t row_begin, size_t
 size_t synth_laplace3d_nnz(size_t nx, size_t ny, size_t nz, size_t row_begin, size_t row_end);
 int synth_laplace3d(int dtype, size_t nx, size_t ny, size_t nz, size_t row_begin, size_t row_end, uint32_t *off,
                     uint32_t *col, void *val, hipStream_t s);
-void build_ring_plan(size_t n_rows, size_t ring_entries, const uint32_t *cmin, const uint32_t *cmax, size_t n_blocks,
-                     uint32_t noring_mode, std::vector<uint32_t> &phase_ptr, std::vector<RingPhase> &phases,
-                     double *ring_row_fraction);
-void build_ring_plan_banded(size_t n_rows, size_t ring_entries, const uint32_t *win, size_t n_blocks, uint32_t noring_mode,
-                            std::vector<uint32_t> &phase_ptr, std::vector<RingPhase> &phases, double *ring_row_fraction);
 void synth_powerlaw_cdf(uint32_t kmax, double alpha, uint32_t *cdf);
 void synth_powerlaw_lengths(uint64_t seed, size_t row_begin, size_t row_end, uint32_t kmax, const uint32_t *cdf,
                             uint32_t *lengths);
 
 static bool valid_dtype(int dt) { return dt == SMH_F32 || dt == SMH_F64; }
 
-// "Launch into a few device words, bring them to the host": launch(d) fills `count` elements at d (device scratch), which are
-// copied to `host` behind a synchronisation of s.  The second form allocates the scratch itself.
-template <typename U, typename F> static int read_back(U *d, U *host, size_t count, hipStream_t s, F &&launch) {
-    SMH_TRY(launch(d));
-    SMH_HIP(hipMemcpyAsync(host, d, count * sizeof(U), hipMemcpyDeviceToHost, s));
-    SMH_HIP(hipStreamSynchronize(s));
-    return SMH_OK;
-}
-template <typename U, typename F> static int read_back(U *host, size_t count, hipStream_t s, F &&launch) {
-    Scratch scr;
-    U *d = nullptr;
-    SMH_TRY(scr.alloc(&d, count));
-    return read_back(d, host, count, s, launch);
-}
-
-// ---- variant selection ---------------------------------------------------------------------------
-// lanes sized to the mean row alone (the skew test of AUTO)
-static int mean_lanes(const smh_crs *m) {
-    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-    // one pass of a lane group covers 4*lanes entry slots: size the group to the mean row; short rows
-    // start anywhere inside their first 16-B chunk, so they get 3 slots of slack (measured on the 7-point
-    // Laplacian: 4 lanes 2.87 ms, 2 lanes 3.68 ms, 1 lane x 3 chunks 3.11 ms)
-    const double need = mean < 16.0 ? mean + 3.0 : mean;
-    int lanes = 1;
-    while (lanes < 64 && 4.0 * lanes < need) lanes <<= 1;
-    return lanes;
-}
-
-static int auto_lanes(const smh_crs *m) {
-    if (m->knobs.forced_lanes) return m->knobs.forced_lanes;
-    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-    int lanes = mean_lanes(m);
-    // Long rows in the pipelined body (contiguous-band matrices, 320 M entries, same box): rows of 128 / 256 entries
-    // run in 0.313 / 0.301 ms with 16 lanes (2 / 4 passes of 64 slots) against 0.359 / 0.348 ms with one pass of 32 / 64
-    // lanes; rows of 100 entries prefer one pass of 32 lanes (0.398 vs 0.500 ms).
-    if (m->knobs.use_ring != 0) {
-        if (mean >= 128.0) lanes = 16;
-        else if (lanes > 32) lanes = 32;
-        // ... and when their columns do not fit the ring (global gathers, one cache line each) 8 lanes lose least
-        // (banded +-32768, rows of 256: 1.28-1.33 ms with 4-8 lanes, 1.51 ms with 16, 1.62-1.80 ms with 64)
-        if (mean > 32.0 && m->ring.state == Form::Ready && m->ring.fraction < 0.5) lanes = 8;
-    }
-    return lanes;
-}
-
-// 16-B chunks each lane loads per pass (pipelined K1r body only): 4*lanes*chunks entry slots per row and pass
-static int auto_chunks(const smh_crs *m) {
-    const int lanes = auto_lanes(m);
-    if (m->knobs.forced_chunks) {
-        if (lanes == 1) return m->knobs.forced_chunks;
-        if (lanes == 2) return m->knobs.forced_chunks > 2 ? 2 : m->knobs.forced_chunks;
-        return 1;
-    }
-    return 1;
-}
-
-// K2c geometry: column blocks of 2 MiB of x
-// 2^19 columns: 2 MiB of f32 x.  f64 takes the same width (4 MiB of x, a whole L2): measured on C3, 20 blocks of
-// 2^19 run in 3.64 ms, 39 blocks of 2^18 in 5.08 ms -- the per-block sweeps of offsets and y (12 B + 8 B per row)
-// outweigh the better hit rate (profiles/r01_colblock_sweep.log)
-static uint32_t cb_shift_for(const smh_crs *m) { return m->knobs.cb_forced_shift ? m->knobs.cb_forced_shift : 19u; }
-static size_t cb_blocks_for(const smh_crs *m) {
-    const uint64_t w = 1ull << cb_shift_for(m);
-    const uint64_t b = ((uint64_t)m->n_cols + w - 1) / w;
-    return (size_t)(b ? b : 1);
-}
-// K2f geometry: blocks of 2^18 columns (1 MiB of f32 x, 2 MiB of f64 x): its waves walk the blocks without a barrier and
-// spread over a few of them, so the L2 has to hold more than one (measured on C2-uniform, f32: 2^18 2.05 ms, 2^19 2.40 ms);
-// a forced width applies to both blocked variants
-static uint32_t cf_shift_for(const smh_crs *m) { return m->knobs.cb_forced_shift ? m->knobs.cb_forced_shift : 18u; }
-static size_t cf_blocks_for(const smh_crs *m) {
-    const uint64_t w = 1ull << cf_shift_for(m);
-    const uint64_t b = ((uint64_t)m->n_cols + w - 1) / w;
-    return (size_t)(b ? b : 1);
-}
-// x too large for the L2s AND rows whose columns span a large part of it (statistic taken at create time for
-// matrices with more than 8 MiB of x): gathers would miss L1 and L2 -> column-blocked execution
-// (tools/experiment_gather.py, 4M rows x 32 uniform columns, f32: K1 / K2c at x = 4 MiB 0.80 / 0.68 ms, 8 MiB
-// 1.25 / 0.66 ms, 16 MiB 1.76 / 0.71 ms, 64 MiB 2.35 / 1.44 ms)
-constexpr size_t kColblockMinXBytes = 4u << 20;
-static bool wants_colblock(const smh_crs *m) {
-    const size_t b = cb_blocks_for(m);
-    return m->n_cols * dtype_size(m->dtype) >= kColblockMinXBytes && m->span_fraction > 0.25 && b >= 2 && b <= 128;
-}
-
-// K2t is an option: not switched off, its copy was not refused, >= min_tile entries per (slice, row block) tile, a tile table of <= 1 GiB
-static bool tiled_fits(const smh_crs *m, double min_tile = 32.0) {
-    static const bool tiled_off = getenv("SMH_TILED") && atoi(getenv("SMH_TILED")) == 0;  // tuning knob
-    if (tiled_off || m->tiled.state == Form::Refused) return false;
-    uint32_t n_cb = 0, R = 0, n_rb = 0;
-    tiled_geometry(m->n_rows, m->n_cols, m->nnz, m->dtype, &n_cb, &R, &n_rb);
-    const double tile = (double)m->nnz / (double)n_cb / (double)n_rb;
-    return tile >= min_tile && (double)(n_rb + 1) * (double)n_cb * 4.0 <= (double)(1u << 30);
-}
-
-static int resolve_variant(const smh_crs *m, int variant) {
-    if (variant != SMH_SPMV_AUTO) return variant;
-    if (wants_colblock(m)) {
-        // one sweep over y (K2f) unless its byte table cannot describe the matrix / it was switched off
-        static const bool fused_off = getenv("SMH_COLBLOCK_FUSED") && atoi(getenv("SMH_COLBLOCK_FUSED")) == 0;  // tuning knob
-        if (fused_off || m->cf.state == Form::Refused || cf_blocks_for(m) > 255) return SMH_SPMV_COLBLOCK;
-        // K2f's waves keep their tiles for the whole sweep: that only works while they stay together, i.e. for rows of
-        // similar length.  Skewed rows (BASELINE C3, power law 1..2048) let them drift over all column blocks at once
-        // -- 5.2-5.6 ms against K2c's 3.25 ms, and a lock step costs more than it recovers (profiles/r02_k2f_sweep.log) --
-        // so those stay with the per-block launches, whose tiles the dispatcher hands out dynamically.
-        // (measured on parts of C3, profiles/r02_c3_split_probe.log: rows of up to 63 / 127 entries, mean 5.5 / 7.9, still run
-        // best through K2f -- 0.82 / 1.15 ms against K2c's 0.97 / 1.26; up to 255 entries K2c wins, 1.61 against 1.79)
-        const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-        const double similar = 2.0 * mean + 8.0 > 128.0 ? 2.0 * mean + 8.0 : 128.0;
-        if ((double)m->max_row_len <= similar) {
-            // the two streaming passes of K2t, whose gathers stay in LDS: ahead of K2f on every shape measured (1-10 M rows x 8-64
-            // entries, profiles/r02_tiled_crossover.log) -- f32 (16 B per entry against CSR's 8) by 31-66 % (C2-uniform 1.14 ms against
-            // 1.90), f64 (28 B against 12) by 13-66 % (10 M columns, rows of 8 / 16 / 32 / 64: 0.71 / 1.06 / 1.99 / 3.63 ms against 1.00 /
-            // 1.63 / 3.13 / 6.36; 4 M x 16: 0.44 against 0.50).  Needs >= 32 entries per tile (>= 12 measured on f64 with 39 blocks)
-            const size_t blocks = cf_blocks_for(m);
-            const bool pays = m->dtype == SMH_F32 ? tiled_fits(m)
-                              : m->no_split       ? false  // (the parts of a K2s split stay as measured)
-                                                  : tiled_fits(m, blocks >= 24 ? 12.0 : 32.0);
-            if (pays) return SMH_SPMV_TILED;
-            return SMH_SPMV_COLFUSED;
-        }
-        // skewed rows: K2t folds the entries a long row has in one slice inside its first pass and cuts its row blocks by product
-        // counts, so long rows cost it nothing special.  Round 3's form is ahead on both value types: C3 (f64) 1.6 ms against K2s's 2.76
-        // and K2c's 3.25; a 3M-row f32 power law (184 slices) 0.23 ms against K2c's 0.62 (tests/test_auto_choice_gpu.py)
-        if (!m->no_split && tiled_fits(m, m->dtype == SMH_F64 && cf_blocks_for(m) >= 24 ? 12.0 : 32.0)) return SMH_SPMV_TILED;  // (the parts of a K2s split stay as measured)
-        // ... and a matrix with a minority of long rows is taken apart by row length (K2s)
-        static const bool split_off = getenv("SMH_COLBLOCK_SPLIT") && atoi(getenv("SMH_COLBLOCK_SPLIT")) == 0;  // tuning knob
-        // ... when K2c's sweeps (per column block and row: one offset, y read and written) weigh as much as the entries
-        // themselves: C3 (f64, 10M rows, 20 blocks) 4.0 GB of sweeps for 3.8 GB of entries -> 2.78 against 3.26 ms; a 3M-row
-        // f32 power law (6 blocks) 0.22 GB for 0.76 GB -> K2c stays ahead, 0.61 against 0.75 ms
-        const double vs = (double)dtype_size(m->dtype);
-        const double sweeps = (double)cb_blocks_for(m) * (double)m->n_rows * (4.0 + 2.0 * vs), entries = (double)m->nnz * (4.0 + vs);
-        if (!split_off && !m->no_split && m->split.state != Form::Refused && sweeps >= 0.6 * entries) return SMH_SPMV_COLSPLIT;
-        return SMH_SPMV_COLBLOCK;
-    }
-    const int lanes = mean_lanes(m);
-    // short rows (stencils, FEM): the dense CSR-stream kernel (a tile denser than its LDS stage takes several passes)
-    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-    // ... except rows of 9-12 entries whose columns fit the LDS ring (plan taken at create time): there the ring kernel
-    // with 4 lanes wins (banded, 320 M entries, rows of 12: 0.445 vs 0.637 ms; rows of 8: 0.572 vs 0.586 ms, a tie)
-    const bool short_ring_rows = mean > 8.0 && m->ring.state == Form::Ready && m->ring.fraction >= 0.5 && m->knobs.use_ring != 0;
-    if (mean <= 12.0 && m->max_row_len <= 64 && !short_ring_rows) return SMH_SPMV_STREAM;
-    // skew test: the longest row needs >= 8 passes of a group sized for the mean row
-    if ((uint64_t)m->max_row_len >= 8ull * 4ull * (uint64_t)lanes && m->max_row_len > 64) return SMH_SPMV_MERGE;
-    // long rows whose columns do not fit the LDS ring (plan taken at create time): every kernel is then bound by one
-    // cache line per gather; the dense stream kernel loses least up to ~128 entries per row (banded +-8192..32768,
-    // 320 M entries: rows of 64 / 128: K1s 0.91 / 1.18 ms, lane-group kernels 1.24-1.42 / 1.34-1.69 ms)
-    if (mean > 32.0 && mean <= 128.0 && m->ring.state == Form::Ready && m->ring.fraction < 0.5) return SMH_SPMV_STREAM;
-    return SMH_SPMV_VECTOR;
-}
-
-static int ensure_merge_ws(smh_crs *m) {
-    if (m->merge.state == Form::Ready) return SMH_OK;
-    MergeTable t;
-    const uint64_t items = (uint64_t)m->n_rows + (uint64_t)m->nnz;
-    t.n_tiles = (size_t)((items + kMergeTile - 1) / kMergeTile);
-    if (t.n_tiles) {
-        SMH_TRY(t.tile_row.alloc(t.n_tiles + 1));
-        SMH_TRY(t.tile_nz.alloc(t.n_tiles + 1));
-        SMH_TRY(t.carry_row.alloc(t.n_tiles));
-        SMH_TRY(t.carry_val.alloc(t.n_tiles * dtype_size(m->dtype)));
-        SMH_TRY(launch_merge_table(m->d_off, m->n_rows, m->nnz, t.n_tiles, t.tile_row.get(), t.tile_nz.get(), m->stream));
-        SMH_HIP(hipStreamSynchronize(m->stream));
-    }
-    t.state = Form::Ready;
-    m->merge = std::move(t);
-    return SMH_OK;
-}
-
-// K1r: inspector pass + host plan, once per matrix
-// with_bands = false: the single-window plans only (what AUTO needs at create time from a matrix with rows too short
-// for the lane-group kernels anyway); the banded attempt -- an inspector pass, a table readback, a host pass over the
-// tiles: ~50 ms at 134 M rows -- then waits until the VECTOR family is actually used.
-static int ensure_ring_plan(smh_crs *m, bool with_bands = true) {
-    if (m->ring.state == Form::Ready && (!with_bands || m->ring.bands_tried)) return SMH_OK;
-    m->ring = RingPlan();  // planned without the banded attempt: plan again, completely (the old plan goes first: no higher peak)
-    RingPlan p;
-    p.bands_tried = with_bands;
-    const size_t n_tiles = (m->n_rows + 63) / 64;
-    int cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, m->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    // Two 512-thread blocks (64 KiB of LDS each) are resident per CU; the row range is cut into 3x as many
-    // blocks so that the hardware dispatcher evens out the tail (round 1, on C2: 2/CU 0.4245 ms, 8/CU 0.404 ms, 24/CU 0.402 ms;
-    // round 3, the final kernel: 4 / 6 / 8 / 12 / 16 per CU 0.360 / 0.357 / 0.361 / 0.364 / 0.371 ms, and 0.350-0.353 against
-    // 0.356-0.359 ms for 6 against 8 on banded and window matrices, f64 level -- profiles/r03_k1r_blocks_per_cu.log)
-    unsigned per_cu = 6;
-    if (const char *e = getenv("SMH_RING_BLOCKS_PER_CU")) {  // tuning knob
-        const int v = atoi(e);
-        if (v >= 1 && v <= 64) per_cu = (unsigned)v;
-    }
-    unsigned blocks = per_cu * (unsigned)cus;
-    blocks = (blocks + 7u) & ~7u;
-    std::vector<uint32_t> cmin(n_tiles), cmax(n_tiles);
-    if (n_tiles) {
-        Scratch scr;
-        uint32_t *d_min = nullptr, *d_max = nullptr;
-        SMH_TRY(scr.alloc(&d_min, n_tiles));
-        SMH_TRY(scr.alloc(&d_max, n_tiles));
-        SMH_TRY(read_back(d_min, cmin.data(), n_tiles, m->stream, [&](uint32_t *) -> int {
-            SMH_TRY(launch_tile_span(m->d_off, m->d_col, m->n_rows, n_tiles, d_min, d_max, m->stream));
-            SMH_HIP(hipMemcpyAsync(cmax.data(), d_max, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-            return SMH_OK;
-        }));
-    }
-    double span_fraction = 0.0;
-    {  // locality statistic for AUTO: mean column span of a 64-row tile relative to n_cols
-        double acc = 0.0;
-        size_t used = 0;
-        for (size_t t = 0; t < n_tiles; ++t)
-            if (cmin[t] <= cmax[t]) { acc += (double)(cmax[t] - cmin[t]) + 1.0; ++used; }
-        span_fraction = used && m->n_cols ? acc / (double)used / (double)m->n_cols : 0.0;
-    }
-    std::vector<uint32_t> phase_ptr;
-    std::vector<RingPhase> phases;
-    // Phases without a ring gather through L1/L2.  Bypassing L1 (nontemporal gathers, mode 2) was measured
-    // SLOWER on both kinds of such matrices (uniform columns 6.29 vs 5.48 ms, 512^3 Laplacian 3.77 vs 2.68 ms),
-    // so it stays a tuning knob.  The uniform case is bound by the per-CU L1 miss path (rocprofv3: TA busy 78 %,
-    // 71 % of wave cycles stalled on VMEM issue, ~59 G gathers/s) -- only column blocking would change that.
-    uint32_t noring_mode = 0;
-    if (const char *e = getenv("SMH_GATHER_NT")) noring_mode = atoi(e) ? 2u : 0u;
-    build_ring_plan(m->n_rows, kRingEntries, cmin.data(), cmax.data(), blocks, noring_mode, phase_ptr, phases,
-                    &p.fraction);
-    p.entries = kRingEntries;
-    // f32 rows that do not fit 16384 columns but fit 32768: the wide ring (128 KiB of LDS, one 1024-thread block per CU
-    // like f64, so half as many blocks).  Rows of 64 entries in a +-8192 band: 0.90 ms (K1s) -> see DESIGN.md.
-    const char *wide_env = getenv("SMH_RING_WIDE");  // tuning knob: 0 = never
-    if (m->dtype == SMH_F32 && p.fraction < 0.5 && !(wide_env && atoi(wide_env) == 0)) {
-        std::vector<uint32_t> phase_ptr_w;
-        std::vector<RingPhase> phases_w;
-        double frac_w = 0.0;
-        const unsigned blocks_w = ((blocks / 2) + 7u) & ~7u;
-        build_ring_plan(m->n_rows, kRingEntriesWide, cmin.data(), cmax.data(), blocks_w, noring_mode, phase_ptr_w, phases_w, &frac_w);
-        if (frac_w >= 0.5) {
-            phase_ptr.swap(phase_ptr_w);
-            phases.swap(phases_w);
-            p.fraction = frac_w;
-            p.entries = kRingEntriesWide;
-            blocks = blocks_w;
-        }
-    }
-    // Still mostly outside the ring: rows that reference a few narrow column intervals far apart (stencils on
-    // structured grids) get the BANDED ring -- four bands of a quarter of the ring, one per interval of the tile.
-    const char *band_env = getenv("SMH_RING_BANDS");  // tuning knob: 0 = never
-    if (with_bands && p.fraction < 0.5 && n_tiles && m->nnz && !(band_env && atoi(band_env) == 0)) {
-        const unsigned sizes[2] = {(unsigned)kRingEntries, (unsigned)kRingEntriesWide};
-        const int n_sizes = m->dtype == SMH_F32 && !(wide_env && atoi(wide_env) == 0) ? 2 : 1;
-        std::vector<uint32_t> h_win(n_tiles * 8);
-        Scratch scr;
-        uint32_t *d_count = nullptr;
-        SMH_TRY(p.win.alloc(n_tiles * 8));
-        SMH_TRY(scr.alloc(&d_count, 1));
-        for (int si = 0; si < n_sizes && p.bands == 1; ++si) {
-            const unsigned ring = sizes[si];
-            SMH_TRY(read_back(p.win.get(), h_win.data(), n_tiles * 8, m->stream, [&](uint32_t *d_win) {
-                return launch_tile_intervals(m->d_off, m->d_col, m->n_rows, 64, ring / 4, d_win, d_count, m->stream);
-            }));
-            std::vector<uint32_t> phase_ptr_b;
-            std::vector<RingPhase> phases_b;
-            double frac_b = 0.0;
-            const unsigned blocks_b = ring == (unsigned)kRingEntries || m->dtype == SMH_F64 ? blocks : ((blocks / 2) + 7u) & ~7u;
-            build_ring_plan_banded(m->n_rows, ring, h_win.data(), blocks_b, noring_mode, phase_ptr_b, phases_b, &frac_b);
-            if (frac_b >= 0.5 && frac_b > p.fraction) {
-                phase_ptr.swap(phase_ptr_b);
-                phases.swap(phases_b);
-                p.fraction = frac_b;
-                p.entries = ring;
-                p.bands = 4;
-                blocks = blocks_b;
-            }
-        }
-        if (p.bands != 4) p.win.reset();  // (kept with a banded plan: the 16-bit ring slots are built from it on first use)
-    }
-    SMH_TRY(p.phase_ptr.alloc(phase_ptr.size()));
-    SMH_TRY(p.phases.alloc(phases.size() + 1));
-    SMH_HIP(hipMemcpy(p.phase_ptr.get(), phase_ptr.data(), phase_ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (!phases.empty())
-        SMH_HIP(hipMemcpy(p.phases.get(), phases.data(), phases.size() * sizeof(RingPhase), hipMemcpyHostToDevice));
-    p.blocks = blocks;
-    p.n_phases = phases.size();
-    p.state = Form::Ready;
-    m->ring = std::move(p);
-    m->span_fraction = span_fraction;
-    return SMH_OK;
-}
-
-// The column-blocked / tiled builders size their tables from n_cols and index them with col >> shift (col / slice): a handle
-// created without validation (smh_crs_create_dev's default) may hold columns >= n_cols, which would walk past those tables.
-// Every such build starts here (max_col is a create-time statistic: no per-call cost).
-int columns_within_n_cols(const smh_crs *m, const char *what) {
-    if (m->nnz && (size_t)m->max_col >= m->n_cols)
-        return fail(SMH_ERR_INDEX_RANGE, "%s: column index %u >= n_cols %zu", what, m->max_col, m->n_cols);
-    return SMH_OK;
-}
-
-// K2c: build the column-blocked copy, once per matrix
-static int ensure_colblock(smh_crs *m) {
-    if (m->cb.state == Form::Ready) return SMH_OK;
-    SMH_TRY(columns_within_n_cols(m, "column-blocked variant"));
-    const size_t blocks = cb_blocks_for(m);
-    if (blocks == 0 || blocks > 128)
-        return fail(SMH_ERR_INVALID, "column-blocked variant: %zu column blocks (supported: 1..128)", blocks);
-    if ((uint64_t)blocks * (m->n_rows + 1) >= (1ull << 34)) return fail(SMH_ERR_OOM, "column-blocked offsets too large");
-    ColBlock c;
-    c.shift = cb_shift_for(m);
-    uint32_t *off2 = nullptr, *col2 = nullptr;
-    void *val2 = nullptr;
-    SMH_TRY(build_colblock(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, c.shift, blocks, &off2, &col2, &val2, m->stream));
-    c.off.reset(off2);
-    c.col.reset(col2);
-    c.val.reset((char *)val2);
-    c.blocks = blocks;
-    // tile height of the K1s launches: the tallest of 2048/1024/512/256 rows whose busiest tile fits the LDS stage
-    Scratch scr;
-    uint32_t *d_max = nullptr;
-    SMH_TRY(scr.alloc(&d_max, 1));
-    int rpt = 8;
-    uint32_t worst = 0;
-    for (; rpt >= 1; rpt >>= 1) {
-        worst = 0;
-        for (size_t b = 0; b < blocks; ++b) {
-            uint32_t h = 0;
-            SMH_TRY(read_back(d_max, &h, 1, m->stream, [&](uint32_t *d) {
-                return launch_stream_max_tile(c.off.get() + b * (m->n_rows + 1), m->n_rows, (size_t)kStreamRows * rpt, d, m->stream);
-            }));
-            worst = h > worst ? h : worst;
-        }
-        if (worst <= (uint32_t)kStreamCap || rpt == 1) break;
-    }
-    c.rpt = rpt < 1 ? 1 : rpt;
-    c.single_pass = worst <= (uint32_t)kStreamCap;  // else 256-row tiles, several passes where needed
-    c.state = Form::Ready;
-    m->cb = std::move(c);
-    return SMH_OK;
-}
-
-// K2c's launches: one K1s sweep per column block, the later ones accumulating into y
-static int launch_colblock(const smh_crs *m, const void *x, void *y, hipStream_t s) {
-    for (size_t b = 0; b < m->cb.blocks; ++b)
-        SMH_TRY(launch_spmv_stream_block(m->dtype, m->cb.off.get() + b * (m->n_rows + 1), m->cb.col.get(), m->cb.val.get(), x, y,
-                                         m->n_rows, m->nnz, m->cb.rpt, m->cb.single_pass, b > 0, s));
-    return SMH_OK;
-}
-
-// K2f: build the fused column-blocked copy, once per matrix (Refused afterwards: not describable -> K2c)
-static int ensure_colfused(smh_crs *m) {
-    if (m->cf.state != Form::NotTried) return SMH_OK;
-    SMH_TRY(columns_within_n_cols(m, "fused column-blocked variant"));
-    const size_t blocks = cf_blocks_for(m);
-    if (blocks > 255) return fail(SMH_ERR_INVALID, "fused column-blocked variant: %zu column blocks (supported: 1..255)", blocks);
-    uint32_t rt = 16;
-    if (const char *e = getenv("SMH_COLFUSED_RT")) {  // tuning knob: rows per lane, 8 or 16
-        if (atoi(e) == 8) rt = 8;
-    }
-    ColFused c;
-    bool fits = false;
-    uint32_t *tile_row = nullptr, *seg = nullptr, *col2 = nullptr;
-    uint8_t *cnt = nullptr;
-    void *val2 = nullptr;
-    SMH_TRY(build_colfused(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, cf_shift_for(m), blocks, rt, &c.tiles,
-                           &tile_row, &seg, &cnt, &col2, &val2, &fits, m->stream));
-    c.tile_row.reset(tile_row);
-    c.seg.reset(seg);
-    c.cnt.reset(cnt);
-    c.col.reset(col2);
-    c.val.reset((char *)val2);
-    c.shift = cf_shift_for(m);
-    c.blocks = blocks;
-    c.rt = rt;
-    c.state = fits ? Form::Ready : Form::Refused;
-    m->cf = std::move(c);
-    return SMH_OK;
-}
-
-// K2s: the row-length split, once per matrix (Refused afterwards: not worth it / not possible -> K2c)
-constexpr uint32_t kSplitMinLong = 64;  // rows of this many entries and more form the LONG part
-static int finish_create(smh_crs *m, int validate);
-// Every handle is made here: a fresh handle on the current device over device arrays, with the create-time inspection done
-// (finish_create).  like (optional): the settings it takes, else the defaults.  Owned arrays go with the handle, also on failure;
-// borrowed ones are never freed by it.
-static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, uint32_t *off, uint32_t *col, void *val,
-                       bool owns, int validate, smh_crs **out) {
-    smh_crs *m = new (std::nothrow) smh_crs();
-    if (!m) {
-        if (owns) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); }
-        return fail(SMH_ERR_OOM, "host allocation failed");
-    }
-    m->dtype = dtype; m->device = current_device(); m->owns = owns;
-    m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
-    m->d_off = off; m->d_col = col; m->d_val = val;
-    if (like) m->knobs = like->knobs;
-    const int rc = finish_create(m, validate);
-    if (rc != SMH_OK) return keep_error(rc, [&] { (void)smh_crs_destroy(m); });
-    *out = m;
-    return SMH_OK;
-}
-// ... the handle takes the arrays of `arrays`
-static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, CrsArrays &arrays, int validate, smh_crs **out) {
-    uint32_t *off = nullptr, *col = nullptr;
-    void *val = nullptr;
-    arrays.release(&off, &col, &val);
-    return wrap_arrays(dtype, like, n_rows, n_cols, nnz, off, col, val, true, validate, out);
-}
-
-static int ensure_split(smh_crs *m) {
-    if (m->split.state != Form::NotTried) return SMH_OK;
-    SMH_TRY(columns_within_n_cols(m, "row-length split"));
-    m->split.state = Form::Refused;  // until the build below is complete: a split that failed or does not pay is not tried again
-    if (m->no_split || m->n_rows == 0 || m->nnz == 0) return SMH_OK;
-    RowSplit sp;
-    size_t nnz_long = 0;
-    uint32_t *rows = nullptr;
-    CrsArrays long_part, short_part;
-    SMH_TRY(build_colsplit(m->dtype, m->d_off, m->d_col, m->d_val, m->n_rows, m->nnz, kSplitMinLong, &sp.n_long, &nnz_long, &rows, &long_part.off,
-                           &long_part.col, &long_part.val, &short_part.off, &short_part.col, &short_part.val, m->stream));
-    sp.rows.reset(rows);
-    // worth it when the long rows are a minority that holds a good part of the entries
-    const bool worth = sp.n_long > 0 && sp.n_long * 4 <= m->n_rows && nnz_long * 4 >= m->nnz;
-    if (!worth) return SMH_OK;
-    auto part = [&](size_t n_rows, size_t nnz, CrsArrays &arrays, uint32_t shift, smh_crs **out) -> int {
-        SMH_TRY(wrap_arrays(m->dtype, nullptr, n_rows, m->n_cols, nnz, arrays, 0, out));
-        (*out)->no_split = true;
-        (*out)->knobs.cb_forced_shift = shift;
-        return SMH_OK;
-    };
-    // LONG: K2c with 2^18-column blocks (1.93 against 2.03 ms with 2^19 on C3's long part); SHORT: its own AUTO with 2^19
-    SMH_TRY(part(sp.n_long, nnz_long, long_part, 18u, &sp.long_part));
-    SMH_TRY(part(m->n_rows, m->nnz - nnz_long, short_part, 19u, &sp.short_part));
-    SMH_TRY(sp.y.alloc(sp.n_long * dtype_size(m->dtype)));
-    SMH_HIP(hipStreamCreateWithFlags(&sp.side, hipStreamNonBlocking));
-    SMH_HIP(hipEventCreateWithFlags(&sp.fork, hipEventDisableTiming));
-    SMH_HIP(hipEventCreateWithFlags(&sp.join, hipEventDisableTiming));
-    sp.state = Form::Ready;
-    m->split = std::move(sp);
-    return SMH_OK;
-}
-// (the sub-handles go through smh_crs_destroy, like every handle)
-RowSplit::~RowSplit() {
-    (void)smh_crs_destroy(long_part);
-    (void)smh_crs_destroy(short_part);
-    rows.reset();
-    y.reset();
-    if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-    if (fork) (void)hipEventDestroy(fork);
-    if (join) (void)hipEventDestroy(join);
-}
-
-// K1s: 16-bit column codes, once per matrix.  Kept only when EVERY tile has a description (stencils, bands): the kernel
-// variant then has no per-tile branch; any other matrix streams its u32 columns as before and nothing stays allocated.
-static int ensure_stream_codes(smh_crs *m) {
-    if (m->codes.state != Form::NotTried) return SMH_OK;
-    StreamCodes c;
-    c.state = Form::Refused;  // (nothing to describe, or some tile without a description)
-    const size_t n_tiles = (m->n_rows + kStreamRows - 1) / kStreamRows;
-    if (n_tiles && m->nnz) {
-        uint32_t h_count = 0;
-        SMH_TRY(c.cwin.alloc(n_tiles * 8));
-        SMH_TRY(read_back(&h_count, 1, m->stream, [&](uint32_t *d_count) {
-            return launch_stream_windows(m->d_off, m->d_col, m->n_rows, c.cwin.get(), d_count, m->stream);
-        }));
-        if ((size_t)h_count == n_tiles) c.state = Form::Ready;
-        else c.cwin.reset();  // some tile's columns need more than 4 intervals of 16384
-    }
-    if (c.state == Form::Ready) {
-        const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
-        SMH_TRY(c.code.alloc(n_out));
-        SMH_HIP(hipMemsetAsync(c.code.get(), 0, n_out * sizeof(uint16_t), m->stream));
-        SMH_TRY(launch_stream_codes(m->d_off, m->d_col, c.cwin.get(), m->n_rows, c.code.get(), m->stream));
-        // ... and with rows of at most 255 entries the row boundaries shrink from a u32 offset to a byte per row
-        if (m->max_row_len <= 255u) {
-            SMH_TRY(c.len8.alloc(n_tiles * kStreamRows));
-            SMH_TRY(c.tbase.alloc(n_tiles + 1));
-            SMH_TRY(launch_stream_len8(m->d_off, m->n_rows, c.len8.get(), c.tbase.get(), m->stream));
-            // how much of x a tile's intervals span (decides whether the body that stages x in LDS applies)
-            uint32_t h_xs[2] = {0xFFFFFFFFu, 0};
-            SMH_TRY(read_back(h_xs, 2, m->stream, [&](uint32_t *d_xs) { return launch_stream_xs_stats(c.cwin.get(), n_tiles, d_xs, m->stream); }));
-            c.xs_chunks = h_xs[0];
-            c.xs_end = h_xs[1];
-            // ... and how many rows have an odd length (decides whether the unskewed product stage of K1s XD applies)
-            unsigned long long h_odd = 0;
-            SMH_TRY(read_back(&h_odd, 1, m->stream, [&](unsigned long long *d_odd) {
-                return launch_stream_odd_rows(c.len8.get(), n_tiles * kStreamRows, d_odd, m->stream);
-            }));
-            c.odd_rows = (uint64_t)h_odd;
-        }
-        SMH_HIP(hipStreamSynchronize(m->stream));
-    }
-    m->codes = std::move(c);
-    return SMH_OK;
-}
-
-// K1r's compact column form: the counting pass (once per matrix and storage order) and, when the form is taken (*use: forced,
-// or few enough escapes), its arrays
-static void drop_ring_col12(smh_crs *m) {
-    m->ring.lo8.reset();
-    m->ring.hdr.reset();
-    m->ring.escapes.reset();
-}
-static int ensure_ring_col12(smh_crs *m, bool forced, bool *use) {
-    RingPlan &r = m->ring;
-    *use = forced || r.c12 == Form::Ready;
-    if (r.c12 != Form::NotTried && (!*use || r.lo8.get())) return SMH_OK;
-    Scratch scr;
-    uint32_t *jobs = nullptr;
-    unsigned long long *d_counts = nullptr, h_counts[2] = {0, 0};
-    SMH_TRY(scr.alloc(&jobs, 2 * r.n_phases));
-    SMH_TRY(scr.alloc(&d_counts, 2));
-    SMH_TRY(read_back(d_counts, h_counts, 2, m->stream, [&](unsigned long long *d) {
-        return launch_col12_count(m->d_off, m->d_col, m->nnz, r.phases.get(), r.n_phases, jobs, d, m->stream);
-    }));
-    r.c12_chunks = h_counts[0];
-    r.c12_escapes = h_counts[1];
-    r.c12 = r.c12_escapes * 1024ull <= r.c12_chunks ? Form::Ready : Form::Refused;
-    *use = forced || r.c12 == Form::Ready;
-    if (!*use) return SMH_OK;
-    const size_t n_chunks_out = ((m->nnz + 3) >> 2) + 1;  // (one chunk beyond the padded end, like col16)
-    DevArray<uint8_t> lo8;
-    DevArray<uint16_t> hdr;
-    DevArray<uint32_t> escapes;
-    SMH_TRY(lo8.alloc(n_chunks_out * 4));
-    SMH_TRY(hdr.alloc(n_chunks_out));
-    SMH_TRY(escapes.alloc(2 * (size_t)(r.c12_escapes ? r.c12_escapes : 1)));
-    SMH_TRY(launch_col12_encode(m->d_col, m->nnz, jobs, r.n_phases, n_chunks_out, lo8.get(), hdr.get(), escapes.get(), d_counts, m->stream));
-    SMH_HIP(hipStreamSynchronize(m->stream));
-    r.lo8 = std::move(lo8);
-    r.hdr = std::move(hdr);
-    r.escapes = std::move(escapes);
-    return SMH_OK;
-}
-
-// does the VECTOR family run as K1r (LDS x-ring) for this matrix?
-static int vector_uses_ring(smh_crs *m, bool *out) {
-    *out = false;
-    if (m->knobs.use_ring == 0 || m->n_rows == 0) return SMH_OK;
-    SMH_TRY(ensure_ring_plan(m));
-    // the pipelined body also wins without the ring (its global-gather phases), so it is the default
-    // whenever its lane widths apply; mode 0 keeps the plain K1 kernel selectable
-    *out = true;
-    // 16-bit columns for the ring phases: a ring slot is `column mod 16384`, so the low half of a column is all a
-    // ring phase reads -- 6 instead of 8 bytes per f32 entry from HBM.  One extra 2-byte-per-entry array, built once.
-    int want = m->knobs.use_col16;
-    if (const char *e = getenv("SMH_RING_COL16")) want = atoi(e) ? 1 : 0;  // tuning knob
-    // ... or, f32 on the single-window ring of 16384 columns, the compact form of ring_col12.hpp: 5.5 bytes per entry.  Chosen
-    // by itself when col16 would be, nobody has asked for or against col16, and a counting pass (once per matrix) finds at most
-    // one chunk in 1024 that the code cannot hold; SMH_RING_COL12=1 takes it wherever it applies, however many chunks escape.
-    int want12 = m->knobs.use_col12;
-    if (const char *e = getenv("SMH_RING_COL12")) want12 = strcmp(e, "auto") == 0 ? -1 : (atoi(e) ? 1 : 0);  // tuning knob
-    const bool can12 = m->dtype == SMH_F32 && m->ring.bands == 1 && m->ring.entries == (unsigned)kRingEntries && m->nnz > 0;
-    bool use12 = can12 && (want12 == 1 || (want12 < 0 && want < 0 && m->ring.fraction >= 0.25));
-    if (use12) SMH_TRY(ensure_ring_col12(m, want12 == 1, &use12));
-    if (!use12) drop_ring_col12(m);
-    // (the banded plan cannot do without: its gathers take the ring slot from that array)
-    // col16 is built by the same rule as before also when the compact form is in use, although the kernel then does not read it:
-    // tests/test_bench_contract_gpu.py pins `derived_bytes` to at least 2 bytes per entry.  Dropping it here (`!use12 &&`: 2 bytes
-    // per entry of device memory and a 0.5 ms pass less on the headline) has to go together with that assertion.
-    const bool use16 = m->ring.bands == 4 || want == 1 || (want < 0 && m->ring.fraction >= 0.25);
-    if (use16 && !m->ring.col16.get() && m->nnz) {
-        const size_t n_out = ((m->nnz + 3) & ~size_t(3)) + 4;
-        DevArray<uint16_t> col16;
-        SMH_TRY(col16.alloc(n_out));
-        if (m->ring.bands == 4) {
-            SMH_HIP(hipMemsetAsync(col16.get(), 0, n_out * sizeof(uint16_t), m->stream));
-            SMH_TRY(launch_ring_band_codes(m->d_off, m->d_col, m->ring.win.get(), m->n_rows, m->ring.entries / 4, col16.get(), m->stream));
-        } else {
-            SMH_TRY(launch_narrow_columns(m->d_col, m->nnz, col16.get(), n_out, m->stream));
-        }
-        SMH_HIP(hipStreamSynchronize(m->stream));
-        m->ring.col16 = std::move(col16);
-    } else if (!use16) {
-        m->ring.col16.reset();
-    }
-    return SMH_OK;
-}
-
-// Which derived forms go when the matrix changes under them (each is rebuilt on its next use); dropping = a default-constructed form.
-enum class Changed { Values, Order, BlockWidth };  // update_values / apply's values-only route; sort_rows; set_colblock_shift
-static void invalidate(smh_crs *m, Changed what) {
-    // the column-blocked / split / tiled copies hold the values, keep storage order inside a (row, block) pair, and are cut by the block width
-    m->cb = ColBlock();
-    m->cf = ColFused();
-    m->split = RowSplit();
-    m->tiled = Tiled();
-    if (what == Changed::Values) m->dict.state = Form::NotTried;  // (the dictionary array stays: a product in flight may still read it)
-    if (what == Changed::Order) {
-        // the K1s codes and the 16-bit column array follow the storage order too; the ring plan's phases and windows stay: they
-        // depend on each tile's column set, not on order
-        m->codes = StreamCodes();
-        m->ring.col16.reset();
-        drop_ring_col12(m);
-        m->ring.c12 = Form::NotTried;  // (which chunks escape depends on the order inside the rows)
-    }
-}
-
-// K1s configuration of this handle
-static int stream_rpt(const smh_crs *m) {
-    // rows per thread: 512-row tiles measured no better than 256-row tiles (1.86 vs 1.80 ms on the 512^3
-    // Laplacian), so one row per thread unless asked (SMH_STREAM_RPT=2, tuning knob)
-    int want = m->knobs.stream_rows_per_thread;
-    if (const char *e = getenv("SMH_STREAM_RPT")) want = atoi(e);
-    return want == 2 && m->max_tile512_entries <= (uint32_t)kStreamCap ? 2 : 1;
-}
-
-// Can y = A x also leave the partial sums of x.y (CG's p.Ap) in its epilogue?  Only the K1s kernel does;
-// returns the number of partials it would write (0: not fused -- run a separate dot).
-// K1s configuration the STREAM variant runs with for this handle (builds the code tables on first use)
-struct StreamCfg {
-    int rpt = 1;
-    bool single_pass = false;
-    const uint16_t *code = nullptr;
-    const uint32_t *cwin = nullptr;
-    const uint8_t *len8 = nullptr;
-    const uint32_t *tbase = nullptr;
-    bool small = false; // no tile beyond kStreamCapSmall entries: the two-chunk body
-    int xs = 0;         // ... and every tile's column intervals fit an LDS stage of x: 16-byte chunks per thread (2 or 4), 0 = no
-    bool direct = false;  // `code` holds byte offsets into that stage, not column codes: only K1s XD (spmv_stream_xd.hip) reads it
-    const void *dict = nullptr;  // ... with value-dictionary indices in their spare bits (K1s XD-V): the kernel does not read the values
-    bool dict_high = false;      // ... in the high spare bits alone (few values)
-};
-// recode = false (every launch path): the configuration is READ from the handle -- the code array keeps the meaning it has.
-// recode = true (the first build, smh_crs_prepare, the setters): the code array is rewritten in place when the choice between
-// column codes and K1s XD's stage offsets has changed -- behind a device synchronisation, because a product enqueued on any
-// stream may still read it; never under a stream capture (the callers say so in the header), and a graph captured before the
-// change must be captured again.
-static int stream_cfg(smh_crs *m, StreamCfg *c, bool recode = false) {
-    *c = StreamCfg();
-    // a 512-row tiling is only chosen when every such tile fits the LDS stage; the 256-row tiling takes
-    // tiles of any density (loop-free body when the create-time statistic says that none overflows)
-    c->rpt = stream_rpt(m);
-    c->single_pass = m->have_stats && (c->rpt == 2 || m->max_tile_entries <= (uint32_t)kStreamCap);
-    // 16-bit column codes when every tile's columns fall into <= 4 intervals of <= 16384 (stencils, bands)
-    const char *c16_env = getenv("SMH_STREAM_C16");  // tuning knob: 0 = always the u32 columns
-    // (single-pass tiles only: on dense multi-pass tiles -- banded C2 through K1s -- the decode costs more than
-    // the bytes save, 0.83 vs 0.80 ms)
-    if (!(c16_env && atoi(c16_env) == 0) && c->rpt == 1 && c->single_pass) {
-        const bool first = m->codes.state == Form::NotTried;
-        SMH_TRY(ensure_stream_codes(m));
-        if (first) recode = true;  // (the build itself: allocations and synchronisations anyway)
-        c->code = m->codes.code.get();
-        c->cwin = m->codes.code.get() ? m->codes.cwin.get() : nullptr;
-        static const bool l8_off = getenv("SMH_STREAM_L8") && atoi(getenv("SMH_STREAM_L8")) == 0;  // tuning knob
-        if (c->cwin && !l8_off) { c->len8 = m->codes.len8.get(); c->tbase = m->codes.tbase.get(); }
-        static const bool small_off = getenv("SMH_STREAM_SMALL") && atoi(getenv("SMH_STREAM_SMALL")) == 0;  // tuning knob
-        c->small = !small_off && m->have_stats && m->max_tile_entries <= (uint32_t)kStreamCapSmall;
-        static const bool xs_off = getenv("SMH_STREAM_XS") && atoi(getenv("SMH_STREAM_XS")) == 0;  // tuning knob
-        // worth it from ~1 MB of x on (tools/dev/xs_threshold.py, profiles/r03_xs_threshold.log: 64^3 ... 320^3 cubes and 1000^2 / 2000^2
-        // grids, -11 .. -20 % with the 2048-entry stage, -18 .. -40 % as K1s XD, both dtypes; below that the launch dominates).  The
-        // 4096-entry stage pays on f32 only (grid planes 1024 wide, x of 17-34 MB: -7 .. -9 %; f64, LDS-limited to three blocks per
-        // CU: +3 .. +10 %).  (Round 2 had 8 MB / 32 MB here: its inspector described a tile whose columns span < 16384 as ONE interval,
-        // so a 64^3 .. 100^3 cube staged its whole span or nothing.)
-        const bool forced = m->knobs.use_stream_xs == 1;
-        const size_t x_bytes = m->n_cols * dtype_size(m->dtype);
-        const bool on2 = forced || x_bytes >= ((size_t)1 << 20), on4 = forced || (x_bytes >= ((size_t)8 << 20) && m->dtype == SMH_F32);
-        c->xs = (xs_off || m->knobs.use_stream_xs == 0 || !c->small || !c->len8) ? 0
-                : (m->codes.xs_chunks <= 2u * kBlock && on2) ? 2
-                : (m->codes.xs_chunks <= 4u * kBlock && on4) ? 4 : 0;
-        // K1s XD: the code array as stage offsets.  The unskewed product stage it goes with collides on rows of even length, so
-        // automatic = most rows odd (stencils with a diagonal)
-        static const bool xd_off = getenv("SMH_STREAM_XD") && atoi(getenv("SMH_STREAM_XD")) == 0;  // tuning knob
-        const bool want_direct = c->code && c->xs != 0 && !xd_off && m->knobs.use_stream_direct != 0 &&
-                                 (m->knobs.use_stream_direct == 1 || 2 * m->codes.odd_rows >= (uint64_t)m->n_rows);
-        // K1s XD-V: the matrix's distinct values in a dictionary, their indices in the codes' spare bits (spmv_stream_xd.hip) -- when
-        // the values allow it (at most 32 bit patterns; 16 with the 4096-entry stage).  Looked at once per matrix, and again after
-        // smh_crs_update_values.
-        static const bool vd_off = getenv("SMH_STREAM_VDICT") && atoi(getenv("SMH_STREAM_VDICT")) == 0;  // tuning knob
-        bool want_vdict = want_direct && !vd_off && m->knobs.use_stream_vdict != 0 && m->dict.state != Form::Refused;
-        bool dict_rebuilt = false;  // (the indices in the codes belong to the dictionary they were made with)
-        if (recode && want_vdict && m->dict.state == Form::NotTried) {
-            if (!m->dict.values.get()) SMH_TRY(m->dict.values.alloc(32 * dtype_size(m->dtype)));
-            SMH_HIP(hipDeviceSynchronize());  // (a product in flight may still read the dictionary)
-            uint32_t n_vals = 0;
-            SMH_TRY(stream_value_dict(m->dtype, m->d_val, m->nnz, m->dict.values.get(), &n_vals, m->stream));
-            m->dict.n = n_vals;
-            m->dict.state = n_vals ? Form::Ready : Form::Refused;
-            dict_rebuilt = true;
-        }
-        want_vdict = want_vdict && m->dict.state == Form::Ready && m->dict.n <= stream_value_dict_capacity(c->xs);
-        const bool form_ok = want_direct == m->codes.direct && want_vdict == m->codes.vdict && (!want_vdict || m->codes.vdict_xs == c->xs) &&
-                             !(dict_rebuilt && (want_vdict || m->codes.vdict));
-        if (recode && c->code && !form_ok) {
-            SMH_HIP(hipDeviceSynchronize());  // (a product enqueued on any stream may still read the array)
-            if (want_direct)
-                SMH_TRY(launch_stream_stage_codes(m->d_off, m->d_col, m->codes.cwin.get(), m->n_rows, (uint32_t)dtype_size(m->dtype), m->codes.code.get(), m->stream));
-            else
-                SMH_TRY(launch_stream_codes(m->d_off, m->d_col, m->codes.cwin.get(), m->n_rows, m->codes.code.get(), m->stream));
-            if (want_vdict)
-                SMH_TRY(launch_stream_value_codes(m->dtype, m->d_val, m->nnz, m->dict.values.get(), m->dict.n, c->xs, m->codes.code.get(), m->stream));
-            SMH_HIP(hipStreamSynchronize(m->stream));
-            m->codes.direct = want_direct;
-            m->codes.vdict = want_vdict;
-            m->codes.vdict_xs = want_vdict ? c->xs : 0;
-        }
-        // (stage offsets without a stage -- xs == 0 after a setter that was not followed by a prepare cannot happen: the setters
-        // recode; an x too short / misaligned for the stage is handled per call in stream_launch)
-        c->direct = c->code && m->codes.direct;
-        c->dict = c->direct && m->codes.vdict ? m->dict.values.get() : nullptr;
-        c->dict_high = c->dict && stream_value_dict_high(m->dtype, m->dict.n, m->codes.vdict_xs);
-    }
-    return SMH_OK;
-}
-
-// a setting that decides the code array's meaning has changed: the array (if it was built) is rewritten now, not inside a later launch
-static int recode_stream(smh_crs *m) {
-    if (m->codes.state == Form::NotTried) return SMH_OK;
-    StreamCfg c;
-    return stream_cfg(m, &c, true);
-}
-
-// one K1s launch over the tiles [t0, t1) with the configuration `c`
-static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x_len, void *y, hipStream_t s, void *dot_partials,
-                         const void *dot_lhs, uint64_t t0, uint64_t t1) {
-    // the staged chunks are groups of 4 entries of x fetched with 16-byte loads (f32: one load, f64: two, entries [g, g+2) and
-    // [g+2, g+4)); with x itself 16-byte aligned a load that holds at least one valid entry may reach past x_len but never past the
-    // 16-byte block (hence page, hence allocation granule) its valid entry lies in.  f32: the last chunk holds a valid entry when
-    // x_len rounded up to 4 reaches stream_xs_end; f64: its SECOND load starts at stream_xs_end - 2 and must hold a valid entry
-    // too (x_len >= stream_xs_end - 1), else the gathers stay global
-    const bool xs_ok = ((m->dtype == SMH_F64 ? x_len + 1 : ((x_len + 3) & ~(size_t)3)) >= (size_t)m->codes.xs_end) &&
-                       (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-    if (c.direct) {
-        if (xs_ok && c.xs)
-            return launch_spmv_stream_xd(m->dtype, m->d_val, x, y, m->n_rows, dot_partials, c.code, c.cwin, c.len8, c.tbase, dot_lhs, s,
-                                         c.xs, t0, t1, c.dict, c.dict_high);
-        // stage offsets mean nothing without the stage: this call streams the u32 columns (same arithmetic, same order)
-        return launch_spmv_stream(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->owns, c.rpt, c.single_pass,
-                                  dot_partials, nullptr, nullptr, nullptr, nullptr, dot_lhs, s, false, 0, t0, t1);
-    }
-    return launch_spmv_stream(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->owns, c.rpt, c.single_pass,
-                              dot_partials, c.code, c.cwin, c.len8, c.tbase, dot_lhs, s, c.small, xs_ok ? c.xs : 0, t0, t1);
-}
-
-// one K1r launch over the plan's row ranges [b0, b1) (dot_partials: the DOT form, whole plan only -- see launch_spmv_ring2)
-static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u) {
-    // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
-    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(),
-                             RingCol12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get()}, m->d_val, x, y, m->n_rows, m->nnz,
-                             m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
-                             m->ring.bands, s, dot_partials, b0, b1);
-}
-
-// any_lhs: the dot is taken with a vector of its own (n_rows entries; SparseMatrix::inner_prod) instead of x itself, so
-// the matrix need not be square
-size_t spmv_fused_dot_partials(smh_crs *m, size_t x_len, int variant, bool any_lhs) {
-    if (const char *e = getenv("SMH_CG_FUSED_DOT")) {  // tuning knob: 0 = always the separate dot
-        if (atoi(e) == 0) return 0;
-    }
-    if (resolve_variant(m, variant) != SMH_SPMV_STREAM) return 0;
-    if (!any_lhs && (m->n_rows != m->n_cols || x_len < m->n_rows)) return 0;
-    StreamCfg c;
-    if (stream_cfg(m, &c) != SMH_OK) return 0;
-    return stream_tiles(m->n_rows, c.rpt);
-}
-
-// enqueue y = A x on stream s (device pointers); dot_partials (optional, K1s only): see above
-int spmv_enqueue(smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, void *dot_partials, const void *dot_lhs) {
-    if (m->nnz > 0 && (size_t)m->max_col >= x_len)
-        return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", x_len, m->max_col);
-    const int v = resolve_variant(m, variant);
-    switch (v) {
-        case SMH_SPMV_VECTOR: {
-            bool ring = false;
-            SMH_TRY(vector_uses_ring(m, &ring));
-            if (ring) return launch_ring(m, x, y, s);
-            return launch_spmv_vector(m->dtype, auto_lanes(m), m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, s);
-        }
-        case SMH_SPMV_SEQ:
-            return launch_spmv_seq(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, s);
-        case SMH_SPMV_STREAM: {
-            StreamCfg c;
-            SMH_TRY(stream_cfg(m, &c));
-            return stream_launch(m, c, x, x_len, y, s, dot_partials, dot_lhs, 0, ~uint64_t(0));
-        }
-        case SMH_SPMV_COLSPLIT: {
-            {
-                const int rc = ensure_split(m);
-                // AUTO chose this plan and its lazy build failed (scratch out of memory, ...): the builder has marked the plan
-                // Refused and AUTO resolves again within this call -- K2c / K2f / K1 can still serve the product
-                if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && m->split.state == Form::Refused) {
-                    g_err[0] = 0;
-                    return spmv_enqueue(m, x, x_len, y, variant, s, dot_partials, dot_lhs);
-                }
-                SMH_TRY(rc);
-            }
-            if (m->split.state == Form::Ready) {
-                // The two parts lean on different resources (LONG: the L2 gather path; SHORT: HBM streams and latency), which
-                // suggests running LONG on a stream of its own beside SHORT (fork and join by events).  Measured on C3, one box:
-                // 2.90 ms overlapped against 2.79 ms back to back -- K2f sizes its rounds to the whole chip and the blocks of
-                // x of the two parts evict each other -- so it is a knob, off by default (SMH_COLSPLIT_OVERLAP=1)
-                static const bool overlap = getenv("SMH_COLSPLIT_OVERLAP") && atoi(getenv("SMH_COLSPLIT_OVERLAP")) != 0;
-                hipStream_t sl = overlap ? m->split.side : s;
-                if (overlap) {
-                    SMH_HIP(hipEventRecord(m->split.fork, s));
-                    SMH_HIP(hipStreamWaitEvent(sl, m->split.fork, 0));
-                }
-                SMH_TRY(spmv_enqueue(m->split.long_part, x, x_len, m->split.y.get(), SMH_SPMV_AUTO, sl));  // the long rows, compacted
-                if (overlap) SMH_HIP(hipEventRecord(m->split.join, sl));
-                SMH_TRY(spmv_enqueue(m->split.short_part, x, x_len, y, SMH_SPMV_AUTO, s));             // every row (0 for the long ones)
-                if (overlap) SMH_HIP(hipStreamWaitEvent(s, m->split.join, 0));
-                return launch_split_scatter(m->dtype, m->split.rows.get(), m->split.y.get(), m->split.n_long, y, s);
-            }
-            SMH_TRY(ensure_colblock(m));  // not worth splitting: the per-block launches
-            return launch_colblock(m, x, y, s);
-        }
-        case SMH_SPMV_COLFUSED: {
-            SMH_TRY(ensure_colfused(m));
-            if (m->cf.state == Form::Ready)
-                return launch_spmv_colfused(m->dtype, m->cf.rt, m->cf.tile_row.get(), m->cf.tiles, m->cf.seg.get(), m->cf.cnt.get(), m->cf.col.get(), m->cf.val.get(),
-                                            x, y, m->n_rows, m->nnz, (uint32_t)m->cf.blocks, m->device, s);
-        }
-        [[fallthrough]];  // a (row, block) pair with more than 255 entries: the per-block launches
-        case SMH_SPMV_COLBLOCK: {
-            SMH_TRY(ensure_colblock(m));
-            return launch_colblock(m, x, y, s);
-        }
-        case SMH_SPMV_TILED: {
-            const int rc = tiled_build(m);
-            // as above: a failed lazy build (K2t needs ~5 x 4 B x nnz of scratch, a copy of the entries and a product buffer)
-            // leaves the form Refused, which AUTO's rule reads as "does not fit" -- resolve again within this call
-            if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && m->tiled.state == Form::Refused) {
-                g_err[0] = 0;
-                return spmv_enqueue(m, x, x_len, y, variant, s, dot_partials, dot_lhs);
-            }
-            SMH_TRY(rc);
-            return launch_spmv_tiled(m, x, x_len, y, s);
-        }
-        case SMH_SPMV_MERGE:
-            SMH_TRY(ensure_merge_ws(m));
-            return launch_spmv_merge(m->dtype, m->d_off, m->d_col, m->d_val, x, y, m->n_rows, m->nnz, m->merge.n_tiles,
-                                     m->merge.tile_row.get(), m->merge.tile_nz.get(), m->merge.carry_row.get(), m->merge.carry_val.get(), s);
-        default:
-            return fail(SMH_ERR_INVALID, "unknown SpMV variant %d", variant);
-    }
-}
-
-// ---- products of a run of rows (par.hip: a block's boundary rows before / after its interior ones) --------------------------
-// The kernels whose launches decompose by rows WITHOUT changing any row's arithmetic: K1s (256-row tiles; bit-exact anyway) and
-// K1r (the plan's row ranges; a row's lanes, chunks and order do not depend on which workgroup takes it).  *gran_out = the row
-// granularity a run must respect (0: this handle's kernel for `variant` cannot be launched by parts).
-int spmv_rows_granularity(smh_crs *m, int variant, size_t *gran_out) {
-    *gran_out = 0;
-    if (m->n_rows == 0) return SMH_OK;
-    const int v = resolve_variant(m, variant);
-    if (v == SMH_SPMV_STREAM) {
-        StreamCfg c;
-        SMH_TRY(stream_cfg(m, &c));
-        *gran_out = (size_t)kStreamRows * (size_t)c.rpt;
-    } else if (v == SMH_SPMV_VECTOR) {
-        bool ring = false;
-        SMH_TRY(vector_uses_ring(m, &ring));
-        if (ring && m->ring.blocks) {
-            const size_t n_tiles = (m->n_rows + 63) / 64;
-            *gran_out = ((n_tiles + m->ring.blocks - 1) / m->ring.blocks) * 64;  // build_ring_plan: tiles per row range
-        }
-    }
-    return SMH_OK;
-}
-
-// y[row0, row1) = (A x)[row0, row1): row0 a multiple of the granularity, row1 too or == n_rows.  Same kernels, same arithmetic as
-// the whole product.  dot_partials: as spmv_enqueue (K1s only; the tiles of the run write their partials, the others are left alone)
-int spmv_enqueue_rows(smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, size_t row0, size_t row1,
-                      void *dot_partials, const void *dot_lhs) {
-    if (m->nnz > 0 && (size_t)m->max_col >= x_len)
-        return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", x_len, m->max_col);
-    if (row1 > m->n_rows) row1 = m->n_rows;
-    if (row0 >= row1) return SMH_OK;
-    size_t gran = 0;
-    SMH_TRY(spmv_rows_granularity(m, variant, &gran));
-    if (gran == 0 || row0 % gran || (row1 % gran && row1 != m->n_rows))
-        return fail(SMH_ERR_INVALID, "rows [%zu, %zu) cannot be launched on their own (granularity %zu)", row0, row1, gran);
-    const int v = resolve_variant(m, variant);
-    if (v == SMH_SPMV_STREAM) {
-        StreamCfg c;
-        SMH_TRY(stream_cfg(m, &c));
-        return stream_launch(m, c, x, x_len, y, s, dot_partials, dot_lhs, row0 / gran, (row1 + gran - 1) / gran);
-    }
-    if (dot_partials) return fail(SMH_ERR_INVALID, "a product by parts with the dot epilogue needs the CSR-stream kernel");
-    return launch_ring(m, x, y, s, nullptr, (unsigned)(row0 / gran), (unsigned)((row1 + gran - 1) / gran));
-}
-
-// The same for a SHORT run of rows (a partition block's boundary rows: a few thousand), any row0 / row1.  One ring workgroup walks its
-// ~6500 rows in ~100 us whatever else the chip does -- the ring kernel gets its rate from 512 of them at once -- so two boundary
-// launches were 200 us of a rank's 340 us step (profiles/r04_par_boundary_rows_k1.log).  The plain lane-group kernel K1 (same lanes,
-// same chunk grid and lane layout, same order of FMAs; x through L1 / L2 instead of the LDS ring) gives the ring kernel's bits in
-// both value types (tests/test_ring_gpu.py::test_k1_is_k1r_bit_for_bit, and every overlap-on / overlap-off comparison of the
-// partition tests), and a short run is a hundred small workgroups: microseconds.  Everything else goes the way of spmv_enqueue_rows.
-int spmv_enqueue_rows_short(smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, size_t row0, size_t row1) {
-    static const bool off = getenv("SMH_PAR_BOUNDARY_K1") && atoi(getenv("SMH_PAR_BOUNDARY_K1")) == 0;  // tuning knob
-    if (row1 > m->n_rows) row1 = m->n_rows;
-    if (row0 >= row1) return SMH_OK;
-    if (!off && resolve_variant(m, variant) == SMH_SPMV_VECTOR && auto_lanes(m) >= 4 && row1 - row0 <= (size_t)1 << 20) {
-        bool ring = false;
-        SMH_TRY(vector_uses_ring(m, &ring));
-        if (ring) {
-            if (m->nnz > 0 && (size_t)m->max_col >= x_len)
-                return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", x_len, m->max_col);
-            return launch_spmv_vector(m->dtype, auto_lanes(m), m->d_off + row0, m->d_col, m->d_val, x, (char *)y + row0 * dtype_size(m->dtype), row1 - row0,
-                                      m->nnz, s);
-        }
-    }
-    return spmv_enqueue_rows(m, x, x_len, y, variant, s, row0, row1, nullptr, nullptr);
-}
-
-static int finish_create_inner(smh_crs *m, int validate);
-static int finish_create(smh_crs *m, int validate) {
-    // (what the create-time inspection costs: the statistics passes and, for matrices AUTO needs it for, the K1r inspector)
-    const auto t0 = std::chrono::steady_clock::now();
-    const long long b0 = pool_thread_net_bytes();
-    const int rc = finish_create_inner(m, validate);
-    m->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    m->create_bytes = pool_thread_net_bytes() - b0;
-    return rc;
-}
 static int finish_create_inner(smh_crs *m, int validate) {
     SMH_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     if (m->n_rows > 0) {
@@ -1029,6 +116,42 @@ static int finish_create_inner(smh_crs *m, int validate) {
             SMH_TRY(ensure_ring_plan(m, lane_group_rows));
     }
     return SMH_OK;
+}
+static int finish_create(smh_crs *m, int validate) {
+    // (what the create-time inspection costs: the statistics passes and, for matrices AUTO needs it for, the K1r inspector)
+    const auto t0 = std::chrono::steady_clock::now();
+    const long long b0 = pool_thread_net_bytes();
+    const int rc = finish_create_inner(m, validate);
+    m->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    m->create_bytes = pool_thread_net_bytes() - b0;
+    return rc;
+}
+
+// Every handle is made here: a fresh handle on the current device over device arrays, with the create-time inspection done
+// (finish_create).  like (optional): the settings it takes, else the defaults.  Owned arrays go with the handle, also on failure;
+// borrowed ones are never freed by it.
+static int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, uint32_t *off, uint32_t *col, void *val,
+                       bool owns, int validate, smh_crs **out) {
+    smh_crs *m = new (std::nothrow) smh_crs();
+    if (!m) {
+        if (owns) { (void)hipFree(off); (void)hipFree(col); (void)hipFree(val); }
+        return fail(SMH_ERR_OOM, "host allocation failed");
+    }
+    m->dtype = dtype; m->device = current_device(); m->owns = owns;
+    m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
+    m->d_off = off; m->d_col = col; m->d_val = val;
+    if (like) m->knobs = like->knobs;
+    const int rc = finish_create(m, validate);
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)smh_crs_destroy(m); });
+    *out = m;
+    return SMH_OK;
+}
+// ... the handle takes the arrays of `arrays`
+int wrap_arrays(int dtype, const smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, CrsArrays &arrays, int validate, smh_crs **out) {
+    uint32_t *off = nullptr, *col = nullptr;
+    void *val = nullptr;
+    arrays.release(&off, &col, &val);
+    return wrap_arrays(dtype, like, n_rows, n_cols, nnz, off, col, val, true, validate, out);
 }
 
 static int check_create_args(int dtype, size_t n_rows, size_t nnz, const void *off, const void *col, const void *val,
@@ -2154,45 +1277,14 @@ int smh_crs_set_vector_lanes(smh_crs *m, int lanes) {
     return SMH_OK;
 }
 
-static int prepare_inner(smh_crs *m, int variant) {
-    switch (resolve_variant(m, variant)) {
-        case SMH_SPMV_VECTOR: {
-            bool ring = false;
-            return vector_uses_ring(m, &ring);  // builds the K1r phase plan when the ring is used
-        }
-        case SMH_SPMV_MERGE: return ensure_merge_ws(m);
-        case SMH_SPMV_COLBLOCK: return ensure_colblock(m);
-        case SMH_SPMV_COLFUSED:
-            SMH_TRY(ensure_colfused(m));
-            return (m->cf.state == Form::Ready) ? SMH_OK : ensure_colblock(m);
-        case SMH_SPMV_COLSPLIT:
-            SMH_TRY(ensure_split(m));
-            if (m->split.state != Form::Ready) return ensure_colblock(m);
-            SMH_TRY(smh_crs_prepare(m->split.short_part, SMH_SPMV_AUTO));
-            return smh_crs_prepare(m->split.long_part, SMH_SPMV_AUTO);
-        case SMH_SPMV_STREAM: {
-            StreamCfg c;
-            return stream_cfg(m, &c, true);  // code tables; the code array in the form the current settings ask for
-        }
-        case SMH_SPMV_TILED: return tiled_build(m);
-        case SMH_SPMV_SEQ: return SMH_OK;
-        default: return fail(SMH_ERR_INVALID, "unknown SpMV variant %d", variant);
-    }
-}
-
 int smh_crs_prepare(smh_crs *m, int variant) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     // what the inspectors cost (smh_crs_prepare_stats): wall time of the build, device-synchronised at both ends, and the
     // device memory it leaves allocated (pooled blocks: everything of 1 MiB and more; scratch freed inside the build nets out)
     const auto t0 = std::chrono::steady_clock::now();
     const long long b0 = pool_thread_net_bytes();
-    // AUTO's plan refused by its lazy build (marked so by the builder): resolve again, as the first product would
-    const int tried = resolve_variant(m, variant);
-    int rc = prepare_inner(m, variant);
-    if (rc != SMH_OK && variant == SMH_SPMV_AUTO && rc != SMH_ERR_INDEX_RANGE && resolve_variant(m, variant) != tried) {
-        g_err[0] = 0;
-        rc = prepare_inner(m, variant);
-    }
+    // (AUTO's plan refused by its lazy build: resolved again, as often as the first product would)
+    int rc = prepare_forms(m, variant);
     if (rc == SMH_OK && m->stream) {
         const hipError_t e = hipStreamSynchronize(m->stream);
         if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
@@ -2389,27 +1481,7 @@ static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const v
     void *scratch = nullptr;
     SMH_TRY(reduce_scratch(&scratch));
     char *res = (char *)scratch + kReducePartials * sizeof(double);
-    const size_t n_dot = spmv_fused_dot_partials(m, rhs_len, variant, true);
-    bool ring = false;
-    if (!n_dot && resolve_variant(m, variant) == SMH_SPMV_VECTOR) SMH_TRY(vector_uses_ring(m, &ring));
-    if (ring) {
-        // K1r: the lanes that would store a row's sum multiply it by lhs[row] instead and the blocks leave partial sums
-        if (m->nnz > 0 && (size_t)m->max_col >= rhs_len)
-            return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %u", rhs_len, m->max_col);
-        SMH_TRY(m->stage_y.ensure_cap(((size_t)m->ring.blocks + 1) * vs));
-        SMH_TRY(launch_ring(m, d_rhs, const_cast<void *>(d_lhs), m->stream, m->stage_y.d.get()));
-        SMH_TRY(launch_fold2(m->dtype, m->stage_y.d.get(), (size_t)m->ring.blocks + 1, scratch, res, m->stream));
-    } else if (n_dot) {
-        // K1s: lhs_i * (A rhs)_i summed per tile in the SpMV's epilogue -- no y vector, no second pass; the tile partials
-        // are folded by the two small reduction kernels
-        SMH_TRY(m->stage_y.ensure_cap(n_dot * vs));  // (the staging buffer holds the partials here)
-        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, nullptr, variant, m->stream, m->stage_y.d.get(), d_lhs));
-        SMH_TRY(launch_fold2(m->dtype, m->stage_y.d.get(), n_dot, scratch, res, m->stream));
-    } else {
-        SMH_TRY(m->stage_y.ensure_cap(m->n_rows * vs));
-        SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, m->stage_y.d.get(), variant, m->stream));
-        SMH_TRY(launch_dot(m->dtype, d_lhs, m->stage_y.d.get(), m->n_rows, scratch, res, m->stream));
-    }
+    SMH_TRY(spmv_inner_prod(m, d_lhs, d_rhs, rhs_len, variant, scratch, res));
     double h64 = 0;
     float h32 = 0;
     if (m->dtype == SMH_F64) SMH_HIP(hipMemcpyAsync(&h64, res, sizeof h64, hipMemcpyDeviceToHost, m->stream));

@@ -519,19 +519,19 @@ struct CrsStats {
 };
 int launch_crs_stats(const uint32_t *off, const uint32_t *col, size_t n_rows, size_t nnz, CrsStats *d_stats,
                      hipStream_t s);
-// y = A x on stream s with the handle's kernel (capi.hip).  dot_partials (optional): when spmv_fused_dot_partials() > 0 the
-// kernel also leaves that many partial sums of x.y there (K1s epilogue; square matrices) -- CG's / PCG's p.Ap for free
 // K2t (spmv_tiled.hip)
 void tiled_geometry(size_t n_rows, size_t n_cols, size_t nnz, int dtype, uint32_t *n_cb, uint32_t *rows_per_block, uint32_t *n_rb);
 int tiled_build(::smh_crs *m);   // lazy; leaves m->tiled Ready or Refused
 uint32_t tiled_slice_columns(int dtype);
-int columns_within_n_cols(const ::smh_crs *m, const char *what);  // capi.hip: SMH_ERR_INDEX_RANGE when max_col >= n_cols
+int columns_within_n_cols(const ::smh_crs *m, const char *what);  // crs_forms.hip: SMH_ERR_INDEX_RANGE when max_col >= n_cols
 int tiled_array(::smh_crs *m, int which, void *out, size_t capacity_bytes, size_t *bytes_out);
 int launch_spmv_tiled(::smh_crs *m, const void *x, size_t x_len, void *y, hipStream_t s);
 size_t spmv_fused_dot_partials(::smh_crs *m, size_t x_len, int variant, bool any_lhs = false);
+// y = A x on stream s with the handle's kernel (spmv_dispatch.hip).  dot_partials (optional): when spmv_fused_dot_partials() > 0 the
+// kernel also leaves that many partial sums of x.y there (K1s epilogue; square matrices) -- CG's / PCG's p.Ap for free
 int spmv_enqueue(::smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, void *dot_partials = nullptr,
                  const void *dot_lhs = nullptr);
-// products of a run of rows (capi.hip; used by par.hip to multiply a block's boundary rows before / after its interior ones)
+// products of a run of rows (spmv_dispatch.hip; used by par.hip to multiply a block's boundary rows before / after its interior ones)
 int spmv_rows_granularity(::smh_crs *m, int variant, size_t *gran_out);
 int spmv_enqueue_rows(::smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, size_t row0, size_t row1,
                       void *dot_partials = nullptr, const void *dot_lhs = nullptr);
@@ -612,7 +612,7 @@ int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_eve
     return rc;
 }
 
-// ---- what a CRS handle derives lazily from its own arrays (built by capi.hip's ensure_* and spmv_tiled.hip's tiled_build) ----
+// ---- what a CRS handle derives lazily from its own arrays (built by crs_forms.hip's ensure_* and spmv_tiled.hip's tiled_build) ----
 // Each form is filled in a local instance and move-assigned into the handle when it is complete; a default-constructed one is
 // "not built", and assigning that drops the form (the members free themselves).
 enum class Form {
@@ -696,7 +696,7 @@ struct RowSplit {  // K2s row-length split: two sub-handles (owned) + the rows o
         swap(o);
         return *this;
     }
-    ~RowSplit();  // capi.hip: the only file that deletes handles
+    ~RowSplit();  // crs_forms.hip; the sub-handles go through smh_crs_destroy (capi.hip), like every handle
     void swap(RowSplit &o) noexcept {
         std::swap(state, o.state); std::swap(long_part, o.long_part); std::swap(short_part, o.short_part);
         std::swap(rows, o.rows); std::swap(y, o.y); std::swap(n_long, o.n_long);

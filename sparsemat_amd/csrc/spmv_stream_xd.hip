@@ -17,7 +17,7 @@
 //   * a row's first 8 products are read with 8 independent LDS loads and added under a lane mask (rows beyond 8 entries continue in
 //     a loop); the row-length prefix sum is a DPP scan.
 // Without the skew the row sums of rows of EVEN length collide in LDS (stride 8 -> 8 lanes per bank); the handle takes this form
-// only when most rows have an odd length -- every stencil with a diagonal: 5, 7, 9, 27 points -- (capi.hip, stream_direct_choice).
+// only when most rows have an odd length -- every stencil with a diagonal: 5, 7, 9, 27 points -- (crs_forms.hip, stream_cfg).
 #include "internal.hpp"
 
 namespace smh {
@@ -58,7 +58,7 @@ static_assert(kStreamCapSmall + 3 <= kXdSlots, "a tile's entries from an aligned
 // every unweighted graph Laplacian or adjacency matrix; BASELINE C4 has two, 6 and -1 -- those bits name the entry's value in a
 // dictionary the kernel keeps in LDS, and the value array is not read at all: 2 bytes per entry leave HBM instead of 6 (f32) / 10
 // (f64).  The product is x times the very same bit pattern as before, the adds are in storage order: still bit for bit the
-// reference's result.  (capi.hip decides; k_value_dict_* below build the dictionary, exactly, or say that it does not exist.)
+// reference's result.  (stream_cfg in crs_forms.hip decides; k_value_dict_* below build the dictionary, exactly, or say that it does not exist.)
 template <typename T, int XS> struct XdBits {
     static constexpr uint32_t kLow = sizeof(T) == 8 ? 3u : 2u;                 // free low bits
     static constexpr uint32_t kIdx = XS == 4 ? 12u : 11u;                      // bits of an entry index inside the stage

@@ -1,4 +1,4 @@
-"""AUTO (the variant selection of capi.hip: thresholds on create-time statistics) on shapes it was NOT tuned on: its
+"""AUTO (the variant selection of spmv_dispatch.hip: thresholds on create-time statistics) on shapes it was NOT tuned on: its
 choice must be within 30 % of the fastest kernel family for the matrix (HIP events through the C ABI, median of 9
 launches).  The shapes differ from BASELINE's in size, row length, band width and value type; the bound is deliberately
 loose -- it catches a wrong family (typically 2-5x), not a tuning nuance."""

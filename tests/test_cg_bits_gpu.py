@@ -286,7 +286,7 @@ def test_solves_are_reproducible(gpu):
         assert p1[1] == p2[1] and same(np.float64(p1[2]), np.float64(p2[2])) and same(p1[0], p2[0])
 
 
-# The fused p.Ap (variant "stream"): a K1s tile is 256 rows (one row per thread is the default tiling, stream_rpt in capi.hip),
+# The fused p.Ap (variant "stream"): a K1s tile is 256 rows (one row per thread is the default tiling, stream_rpt in crs_forms.hip),
 # so spmv_fused_dot_partials returns ceil(n / 256): 9 for n = 2051 / 2049 -- folded by the update's workgroups themselves --
 # and 1026 > kReducePartials for n = 262 144 + 259, which enters k_sum_stage1 / k_pcg_sum_stage1.
 FUSED_SIZES = [2051, 262_144 + 259]

@@ -242,7 +242,7 @@ def test_k1_is_k1r_bit_for_bit(gpu, dtype):
     """The plain lane-group kernel (VECTOR with the ring off) and the LDS-ring kernel share lanes, chunk grid, lane layout (f64: two
     16-byte pieces per lane and pass in both) and the order of their FMAs: their results are the same bits.  The partition relies on
     it: a block's few boundary rows go through K1 (a hundred small workgroups) while the interior goes through K1r
-    (spmv_enqueue_rows_short, capi.hip)."""
+    (spmv_enqueue_rows_short, spmv_dispatch.hip)."""
     rng = np.random.default_rng(5)
     u = np.uint32 if dtype == np.float32 else np.uint64
     cases = [synth.crs_fixed(synth.SEED_MATRIX, synth.PATTERN_WINDOW, 400_000, 32, dtype),

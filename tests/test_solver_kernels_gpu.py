@@ -29,7 +29,10 @@ The shapes are the smallest at which each form engages; what the getters must re
 band(20 000, 4000, 31 | 32) for K1 and the single-window K1r forms; band(48 000, 10 000, 32) for the 32 768-column ring (at 30 000
 rows the 16 384-column ring still serves 53 % of the rows and the plan keeps it); stencil7(130 x 130 x 6) for the banded ring (a
 48 x 48 x 24 grid fits one window); scattered(40 000) for merge (316 tiles), K2c (5 blocks of 8192 columns) and K2t (3 slices),
-without its hubs for K2f; arrowhead(8000) for K2s (40 long rows); 24^3 for K1s (the stage forced: x is under 1 MB)."""
+without its hubs for K2f; arrowhead(8000) for K2s (40 long rows); 24^3 for K1s (the stage forced: x is under 1 MB).
+
+Every case above prepares its handle first.  The last test sends a fresh handle of every configuration straight into a product and
+holds it to the prepared one: same bytes, same forms, same resolution."""
 import math
 
 import numpy as np
@@ -40,7 +43,7 @@ import bicgstab_model as bm
 import cg_model
 import oracle
 import sparsemat_amd as sm
-from kernel_forms import CONFIGS, F32, F64, env, same
+from kernel_forms import CONFIGS, F32, F64, config_matrix, env, same
 from util import assert_spmv_close
 
 pytestmark = pytest.mark.gpu
@@ -225,3 +228,24 @@ def test_solvers_equal_the_model_fed_by_the_checked_device_product(gpu, name, dt
                 for g in solver.device(a, b, x0, tol, 50, cfg.variant):
                     assert_same_result(solver, g, stopped, (name, solver.name, "stop in body %d" % k))
         cfg.check(a)  # (the solves have changed no form)
+
+
+@pytest.mark.parametrize("name,dtype", CASES)
+def test_first_product_builds_what_prepare_builds(gpu, name, dtype):
+    """A fresh handle sent straight into a product (the lazy builds inside the first launch) against one that was prepared first: the
+    same bytes, the same forms (the configuration's getters) and the same resolution.  The product and smh_crs_prepare read which
+    forms a variant runs on from one table (spmv_dispatch.hip); this is the comparison that table could break."""
+    cfg = CONFIGS[name]
+    n, off, col, val, x = config_matrix(name, dtype)
+    with env(**cfg.env):
+        prepared = sm.SparseMatCRS.from_raw_parts(n, n, off, col, val)
+        cfg.knobs(prepared)
+        prepared.prepare(cfg.variant)
+        want = prepared.mvp(x, variant=cfg.variant)
+        fresh = sm.SparseMatCRS.from_raw_parts(n, n, off, col, val)
+        cfg.knobs(fresh)
+        got = fresh.mvp(x, variant=cfg.variant)
+        bad = np.flatnonzero(got != want)
+        assert same(got, want), (name, len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+        cfg.check(fresh)
+        assert fresh.resolved_variant() == prepared.resolved_variant()
