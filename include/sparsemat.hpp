@@ -312,6 +312,31 @@ class SparseMatCRS {
         if (stats) *stats = st;
         return perm;
     }
+    // Sparse triangular solves and symmetric Gauss-Seidel (extensions: the reference has neither; sparsemat_hip.h).  The triangle
+    // uplo (SMH_TRI_LOWER / SMH_TRI_UPPER) of this square matrix with the first stored (i, i) of a row as its diagonal entry, or an
+    // implied 1 (unit_diagonal); level-scheduled on the device, every operation rounded once, a row's subtractions in storage order.
+    struct TriLevels {
+        size_t n_levels = 0, n_launches = 0, small_level_rows = 0;
+        std::vector<uint32_t> level_of_row;
+    };
+    TriLevels trisolve_levels(int uplo = SMH_TRI_LOWER) const {
+        TriLevels t;
+        t.level_of_row.resize(n_rows() ? n_rows() : 1);
+        detail::check(smh_crs_trisolve_levels(h_, uplo, &t.n_levels, t.level_of_row.data(), &t.n_launches, &t.small_level_rows));
+        t.level_of_row.resize(n_rows());
+        return t;
+    }
+    std::vector<T> trisolve(const std::vector<T> &b, int uplo = SMH_TRI_LOWER, bool unit_diagonal = false) const {
+        std::vector<T> x(b.size());
+        detail::check(smh_crs_trisolve(h_, uplo, unit_diagonal ? SMH_DIAG_UNIT : SMH_DIAG_NON_UNIT, b.data(), b.size(), x.data(), x.size()));
+        return x;
+    }
+    // x may be b: in place
+    void trisolve(const DenseVec<T> &b, DenseVec<T> &x, int uplo = SMH_TRI_LOWER, bool unit_diagonal = false) const {
+        detail::check(smh_crs_trisolve_vec(h_, uplo, unit_diagonal ? SMH_DIAG_UNIT : SMH_DIAG_NON_UNIT, b.handle(), x.handle()));
+    }
+    // z = M^-1 r, M = (D + L) D^-1 (D + U); z may be r
+    void sgs_apply(const DenseVec<T> &r, DenseVec<T> &z) const { detail::check(smh_crs_sgs_apply_vec(h_, r.handle(), z.handle())); }
     // {max i - j, max j - i} over the stored entries
     std::pair<uint32_t, uint32_t> bandwidth() const {
         uint32_t lo = 0, hi = 0;
@@ -603,6 +628,33 @@ class ConjugateGradient {
     double r_norm_squared_ = 0.0;
     std::vector<size_t> iterations_many_;
     std::vector<double> r_norm_squared_many_;
+};
+
+// CG preconditioned by symmetric Gauss-Seidel -- an extension, not in the reference (smh_pcg_sgs_solve*): the recurrence of
+// ConjugateGradient::solve_jacobi with z = M^-1 r by two level-scheduled triangular solves; same panics and stop rule.
+class SGSConjugateGradient {
+  public:
+    SGSConjugateGradient() = default;
+    SGSConjugateGradient(double tol, size_t iter_max) : tol_(tol), iter_max_(iter_max) {}
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_pcg_sgs_solve_vec(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0, &iterations_,
+                                            &r_norm_squared_));
+    }
+    // host vectors, x updated in place
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_pcg_sgs_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO, &iterations_,
+                                        &r_norm_squared_));
+    }
+    size_t iterations() const { return iterations_; }
+    double r_norm_squared() const { return r_norm_squared_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t iter_max_ = 10000;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
 };
 
 // BiCGSTAB for non-symmetric systems -- an extension, not in the reference (smh_bicgstab_solve*): device-resident like

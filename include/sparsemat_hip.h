@@ -43,7 +43,8 @@ extern "C" {
  * smh_update_plan_create, smh_update_plan_create_dev, smh_update_plan_execute, smh_update_plan_execute_dev,
  * smh_update_plan_stats, smh_update_plan_destroy; smh_crs_permute, smh_crs_permute_dev, smh_crs_permute_symmetric,
  * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
- * smh_crs_rcm_dev.  A caller checks smh_abi_version() ==
+ * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
+ * smh_pcg_sgs_solve_vec.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -86,6 +87,10 @@ typedef enum {
                          /* tiled copy: products against slices of x held in LDS, then one  */
                          /* wavefront per block of rows folds them (no gather leaves a CU)  */
 } smh_spmv_variant;
+
+/* sparse triangular solves: which triangle of the stored matrix, and whether its diagonal is the stored one or an implied 1 */
+typedef enum { SMH_TRI_LOWER = 0, SMH_TRI_UPPER = 1 } smh_tri_uplo;
+typedef enum { SMH_DIAG_NON_UNIT = 0, SMH_DIAG_UNIT = 1 } smh_tri_diag;
 
 typedef struct smh_crs smh_crs; /* device-resident SparseMatCRS<T,u32>  (sparsemat_crs.rs:9-17) */
 typedef struct smh_vec smh_vec; /* device-resident DenseVec<T>          (densevec.rs:5-7)      */
@@ -643,6 +648,49 @@ int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, v
 int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout,
                          size_t x_len, double tol, size_t iter_max, int variant, size_t *iters_out,
                          double *rr_out);
+
+/* ---- sparse triangular solves and symmetric Gauss-Seidel -- EXTENSIONS (the reference has neither) ----------------------------
+ * The triangle of a square handle: for uplo = SMH_TRI_LOWER the stored entries (i, c) with c < i, for SMH_TRI_UPPER those with
+ * c > i, and the diagonal; entries of the other triangle are ignored.  The solve is level-scheduled: the dependency of row i is
+ * every stored column c in the triangle's strict part (stored zeros count, duplicates once); level(i) = 0 without one, else
+ * 1 + max level(c).  The schedule is a derived form of the handle, built on the device on first use, one per uplo: the rows of
+ * each level, and for every row the position of its diagonal entry -- the FIRST stored (i, i) in storage order, the rule of
+ * smh_crs_get and the Jacobi preconditioner.  It holds positions only: smh_crs_update_values, smh_crs_scale and a values-only
+ * smh_crs_apply leave it valid; smh_crs_sort_rows and whatever replaces the handle's arrays drop it.
+ * A level of more than R rows is one kernel launch; a run of consecutive levels of at most R rows each is ONE launch of one
+ * workgroup that walks them (a bidiagonal chain of n rows: one launch).  No kernel waits for another workgroup.
+ * smh_crs_trisolve_levels: the level count, the level of every row (n_rows entries, or NULL), the kernel launches one solve
+ * enqueues, and R.  Any out pointer may be NULL.
+ * smh_crs_trisolve: x = T^-1 b; diag = SMH_DIAG_UNIT takes the diagonal as 1 and needs none stored.  Every operation is rounded
+ * once and nothing is fused; for row i (LOWER; UPPER: c > i):
+ *     s = b[i];  for k = off[i] .. off[i+1]-1 in storage order:  c = col[k];  if c < i:  s = s - val[k] * x[c]
+ *     x[i] = NON_UNIT ? s / val[diagpos[i]] : s
+ * so duplicate off-diagonal entries are each subtracted and further stored (i, i) after the first are ignored.  A zero diagonal
+ * VALUE is not an error: the solve gives IEEE's +-Inf or NaN.  _vec: x may be b (in place).
+ * Statuses, all decided before any launch: SMH_ERR_NOT_SQUARE; SMH_ERR_DIM_MISMATCH; SMH_ERR_INDEX_RANGE (a stored column >=
+ * n); SMH_ERR_INVALID (a NULL pointer, a vector dtype that is not the matrix's, b and x overlapping in part, a bad uplo or diag,
+ * a handle that holds an orphaned entry, or -- NON_UNIT -- a row without a stored diagonal entry: the message names the first). */
+int smh_crs_trisolve_levels(smh_crs *m, int uplo, size_t *n_levels_out, uint32_t *level_of_row_out, size_t *n_launches_out,
+                            size_t *small_level_rows_out);
+int smh_crs_trisolve(smh_crs *m, int uplo, int diag, const void *b_host, size_t b_len, void *x_host, size_t x_len);
+int smh_crs_trisolve_vec(smh_crs *m, int uplo, int diag, const smh_vec *b, smh_vec *x);
+/* The symmetric Gauss-Seidel preconditioner M = (D + L) D^-1 (D + U) of a square handle (D, L, U: its diagonal as above and its
+ * strict triangles).  smh_crs_sgs_apply_vec: z = M^-1 r as  w = trisolve(LOWER, NON_UNIT, r);  u_i = w_i * d_i;  z =
+ * trisolve(UPPER, NON_UNIT, u), each operation rounded once; z may be r.  Statuses as smh_crs_trisolve_vec's.
+ * smh_pcg_sgs_solve: the recurrence of smh_pcg_jacobi_solve with that z; same guards, statuses, stop rule (on r.r, before
+ * beta) and outputs; device-resident like smh_cg_solve (bodies enqueued past the stop change nothing; check_every: bodies per
+ * poll, 0 = default, 8; a batch of many kernel launches is replayed in smaller batches or launched plainly, which changes no
+ * bit):
+ *     r = b - A x;  z = M^-1 r;  rr = r.r;  rz = r.z;  p = z
+ *     body:  ap = A p;  alpha = rz / p.ap;  r = r - ap*alpha;  rr = r.r;  x = x + p*alpha;  sqrt(f64(rr)) < tol: stop
+ *            z = M^-1 r;  rz' = r.z;  beta = rz' / rz;  rz = rz';  p = p*beta + z
+ * A zero or absent diagonal entry is SMH_ERR_INVALID (the message names the row); a stored column >= n SMH_ERR_INDEX_RANGE;
+ * _vec: additionally SMH_ERR_INVALID for a NULL vector, a dtype that is not the matrix's, b and x the same storage. */
+int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z);
+int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                      double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
+int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                          int variant, size_t check_every, size_t *iters_out, double *rr_out);
 
 /* BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is
  * the conjugate gradient).  Device-resident like smh_cg_solve: scalars in HBM, the stop decided on the device in every

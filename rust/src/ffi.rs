@@ -14,6 +14,10 @@ pub const SMH_ERR_DIM_MISMATCH: c_int = 1;
 pub const SMH_F32: c_int = 0;
 pub const SMH_F64: c_int = 1;
 pub const SMH_SPMV_AUTO: c_int = 0;
+pub const SMH_TRI_LOWER: c_int = 0;
+pub const SMH_TRI_UPPER: c_int = 1;
+pub const SMH_DIAG_NON_UNIT: c_int = 0;
+pub const SMH_DIAG_UNIT: c_int = 1;
 pub const SMH_EXCHANGE_NONE: c_int = 0;
 pub const SMH_EXCHANGE_ALLGATHER: c_int = 1;
 pub const SMH_EXCHANGE_WINDOW: c_int = 2;
@@ -50,6 +54,19 @@ extern "C" {
     pub fn smh_bicgstab_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
                                   variant: c_int, check_every: usize,
                                   iters_out: *mut usize, rr_out: *mut c_double, breakdown_out: *mut c_int) -> c_int;
+    // extensions (not in the reference): level-scheduled sparse triangular solves, the symmetric Gauss-Seidel preconditioner
+    // M = (D + L) D^-1 (D + U) built on them, and its CG (same contract as smh_pcg_jacobi_solve)
+    pub fn smh_crs_trisolve_levels(m: *mut smh_crs, uplo: c_int, n_levels_out: *mut usize, level_of_row_out: *mut u32,
+                                   n_launches_out: *mut usize, small_level_rows_out: *mut usize) -> c_int;
+    pub fn smh_crs_trisolve(m: *mut smh_crs, uplo: c_int, diag: c_int, b_host: *const c_void, b_len: usize, x_host: *mut c_void,
+                            x_len: usize) -> c_int;
+    pub fn smh_crs_trisolve_vec(m: *mut smh_crs, uplo: c_int, diag: c_int, b: *const smh_vec, x: *mut smh_vec) -> c_int;
+    pub fn smh_crs_sgs_apply_vec(m: *mut smh_crs, r: *const smh_vec, z: *mut smh_vec) -> c_int;
+    pub fn smh_pcg_sgs_solve(m: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                             x_len: usize, tol: c_double, iter_max: usize, variant: c_int,
+                             iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    pub fn smh_pcg_sgs_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
+                                 variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

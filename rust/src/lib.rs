@@ -105,6 +105,31 @@ impl BiCGStab {
     }
 }
 
+/// CG preconditioned by symmetric Gauss-Seidel -- an extension, not in the reference (`smh_pcg_sgs_solve`): the Jacobi
+/// recurrence with z = M^-1 r by two level-scheduled triangular solves.  Uncompiled like the rest of this shim.
+pub struct SgsConjugateGradient {
+    pub tol: f64,
+    pub iter_max: usize,
+}
+
+impl Default for SgsConjugateGradient {
+    fn default() -> Self {
+        SgsConjugateGradient { tol: 1e-12, iter_max: 10_000 }
+    }
+}
+
+impl SgsConjugateGradient {
+    /// `x` is updated in place; returns (bodies entered, last r.r).
+    pub fn solve<T: HipValue>(&self, mat: &DeviceCrs, b: &[T], x: &mut [T]) -> (usize, f64) {
+        let (mut iters, mut rr) = (0usize, 0f64);
+        check(unsafe {
+            ffi::smh_pcg_sgs_solve(mat.handle, b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void,
+                                   x.len(), self.tol, self.iter_max, ffi::SMH_SPMV_AUTO, &mut iters, &mut rr)
+        });
+        (iters, rr)
+    }
+}
+
 impl DeviceCrs {
     /// `SparseMatrix::inner_prod` (src/sparsematrix.rs:161-171): lhs^T A rhs.
     pub fn inner_prod<T: HipValue>(&self, lhs: &[T], rhs: &[T]) -> f64 {
@@ -114,6 +139,28 @@ impl DeviceCrs {
                                     rhs.len(), ffi::SMH_SPMV_AUTO, &mut out)
         });
         out
+    }
+
+    /// x = T^-1 b with T the lower (`upper == false`) or upper triangle of this square matrix, the first stored (i, i) of a row
+    /// as its diagonal entry (`unit_diagonal`: an implied 1) -- an extension; every operation rounded once, storage order.
+    pub fn trisolve<T: HipValue>(&self, b: &[T], x: &mut [T], upper: bool, unit_diagonal: bool) {
+        check(unsafe {
+            ffi::smh_crs_trisolve(self.handle, if upper { ffi::SMH_TRI_UPPER } else { ffi::SMH_TRI_LOWER },
+                                  if unit_diagonal { ffi::SMH_DIAG_UNIT } else { ffi::SMH_DIAG_NON_UNIT },
+                                  b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void, x.len())
+        });
+    }
+
+    /// The level schedule of a triangle: (levels, level of every row, kernel launches per solve).
+    pub fn trisolve_levels(&self, upper: bool) -> (usize, Vec<u32>, usize) {
+        let mut level = vec![0u32; self.n_rows.max(1)];
+        let (mut levels, mut launches, mut small) = (0usize, 0usize, 0usize);
+        check(unsafe {
+            ffi::smh_crs_trisolve_levels(self.handle, if upper { ffi::SMH_TRI_UPPER } else { ffi::SMH_TRI_LOWER }, &mut levels,
+                                         level.as_mut_ptr(), &mut launches, &mut small)
+        });
+        level.truncate(self.n_rows);
+        (levels, level, launches)
     }
 
     /// `SparseMatrix::transpose` (src/sparsematrix.rs:174-184) for `Self = SparseMatCRS`: the arrays the reference's

@@ -14,6 +14,9 @@ SMH_OK = 0
 SMH_ERR_DIM_MISMATCH, SMH_ERR_NOT_SQUARE, SMH_ERR_INDEX_RANGE, SMH_ERR_INVALID = 1, 2, 3, 4
 SMH_ERR_HIP, SMH_ERR_OOM, SMH_ERR_NO_DEVICE, SMH_ERR_CAPACITY, SMH_ERR_COMM = 5, 6, 7, 8, 9
 SMH_F32, SMH_F64 = 0, 1
+SMH_TRI_LOWER, SMH_TRI_UPPER = 0, 1
+SMH_DIAG_NON_UNIT, SMH_DIAG_UNIT = 0, 1
+UPLO = {"lower": SMH_TRI_LOWER, "upper": SMH_TRI_UPPER}
 EXCHANGE_NONE, EXCHANGE_ALLGATHER, EXCHANGE_WINDOW, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGES = {"none": EXCHANGE_NONE, "allgather": EXCHANGE_ALLGATHER, "window": EXCHANGE_WINDOW, "halo": EXCHANGE_WINDOW, "auto": EXCHANGE_AUTO}
 EXCHANGE_NAMES = {EXCHANGE_NONE: "none", EXCHANGE_ALLGATHER: "allgather", EXCHANGE_WINDOW: "window", EXCHANGE_AUTO: "auto"}
@@ -166,6 +169,14 @@ SIGNATURES = {
     "smh_cg_solve_many_host": (_int, [_vp, _vp, _sz, _sz, _vp, C.c_double, _sz, C.POINTER(_sz), C.POINTER(C.c_double)]),
     "smh_pcg_jacobi_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                                     C.POINTER(C.c_double)]),
+    "smh_crs_trisolve_levels": (_int, [_vp, _int, C.POINTER(_sz), _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "smh_crs_trisolve": (_int, [_vp, _int, _int, _vp, _sz, _vp, _sz]),
+    "smh_crs_trisolve_vec": (_int, [_vp, _int, _int, _vp, _vp]),
+    "smh_crs_sgs_apply_vec": (_int, [_vp, _vp, _vp]),
+    "smh_pcg_sgs_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
+                                 C.POINTER(C.c_double)]),
+    "smh_pcg_sgs_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
+                                     C.POINTER(C.c_double)]),
     "smh_bicgstab_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                                   C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_bicgstab_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),

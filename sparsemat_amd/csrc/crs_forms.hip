@@ -417,6 +417,9 @@ void invalidate(smh_crs *m, Changed what) {
         m->ring.col16.reset();
         drop_ring_col12(m);
         m->ring.c12 = Form::NotTried;  // (which chunks escape depends on the order inside the rows)
+        // the level schedules hold entry positions (the levels themselves would stay: they depend on each row's column set)
+        m->tri[0] = TriSchedule();
+        m->tri[1] = TriSchedule();
     }
 }
 

@@ -544,6 +544,11 @@ int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials
                hipStream_t s);
 int launch_fold2(int dtype, const void *in, size_t count, void *partials, void *result_dev, hipStream_t s);  // *result = sum(in)
 int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
+// Sparse triangular solves (trisolve.hip).  ensure_tri_schedule: the lazy level schedule m->tri[uplo] of a square handle whose
+// columns are all below n.  trisolve_enqueue: x = T^-1 b on s by that schedule (built before; device pointers, x may be b); scale_rhs:
+// the right-hand side is b[i] * val[diagpos[i]], rounded once; active (optional): a device flag, 0 = every launch returns at once
+int ensure_tri_schedule(::smh_crs *m, int uplo);
+int trisolve_enqueue(::smh_crs *m, int uplo, int diag, bool scale_rhs, const void *b, void *x, const uint32_t *active, hipStream_t s);
 
 // ---- the device-resident solvers (cg.hip, pcg.hip, par.hip) ----------------------------------------------------------------------
 // The scalar block of a solve: it lives in device memory, the kernels of cg.hip advance it, the host copies it back once per batch.
@@ -568,12 +573,13 @@ void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t 
 // scalar block (d_sc, through the pinned h_sc) once per batch.  With more than one batch to go the batch is captured ONCE into a
 // hipGraph and replayed, always whole: for small systems the loop is launch-bound.  If the capture does not come about the bodies
 // are launched one by one.  *converged, *iters, *rr: the block as the last poll saw it.
+// capture = false: never captured (a body of very many launches: SGS-PCG on a matrix of many levels).
 template <typename Body>
 int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_every, Body &&body, const void *d_sc, void *h_sc, int *converged,
-                     size_t *iters, double *rr) {
+                     size_t *iters, double *rr, bool capture = true) {
     Graph graph;
     GraphExec exec;
-    if (iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    if (capture && iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         int crc = SMH_OK;
         for (size_t i = 0; i < check_every && crc == SMH_OK; ++i) crc = body();
         const hipError_t ce = graph.end_capture(s);  // (also after a body that failed: the stream must leave capture mode)
@@ -717,6 +723,24 @@ struct Tiled {  // K2t 2-D tiled copy (spmv_tiled.hip): entries by column slice,
     bool dups = false;                    // a chunk boundary cuts a (row, slice) pair somewhere: pass 2 checks for equal neighbours
     uint64_t n_prod = 0;                  // product slots (one per (row, slice, chunk), chunk shares padded to 16 bytes)
 };
+struct TriSchedule {  // level schedule of a triangular solve (trisolve.hip), one per uplo: positions only, no values
+    Form state = Form::NotTried;
+    size_t n_levels = 0;
+    uint64_t first_no_diag = ~0ull;       // the first row without a stored (i, i); ~0: every row has one
+    DevArray<uint32_t> rows;              // the rows level by level, ascending inside a level (n)
+    DevArray<uint32_t> level_ptr;         // where each level starts in rows (n_levels + 1)
+    DevArray<uint32_t> level;             // level of each row (n)
+    DevArray<uint32_t> diagpos;           // first k with col[k] == i (n; ~0u: none)
+    // one kernel launch: a level of more than kTriSmallRows rows on a grid, or a run of consecutive levels of at most that many
+    // rows each walked by one workgroup (kTriSmallBlock threads) with a barrier between levels
+    struct Launch { uint32_t level_begin, level_end, row_begin, row_end; bool small; };
+    std::vector<Launch> launches;
+};
+// R: one pass of the multi-level kernel's workgroup (kTriSmallBlock threads) at the 8 lanes per row of a stencil.  Measured on the
+// natural 1024^2 five-point grid (2047 levels of 1 .. 1024 rows): with R = 1024 the whole solve was one workgroup on one CU, 19 ms
+// -- 9 us per level, several passes of dependent gathers each -- where a launch per level costs about 6 us
+constexpr uint32_t kTriSmallRows = 128;
+constexpr uint32_t kTriSmallBlock = 1024;
 struct StageBuf {  // a staging vector of the host-pointer API (lazy, reused)
     DevArray<char> d;
     size_t cap = 0;
@@ -787,6 +811,7 @@ struct smh_crs {
     smh::ColFused cf;
     smh::RowSplit split;
     smh::Tiled tiled;
+    smh::TriSchedule tri[2];  // [SMH_TRI_LOWER], [SMH_TRI_UPPER]
     smh::StageBuf stage_x, stage_y;
     // what the inspectors cost (smh_crs_prepare_stats): wall ms / pooled device bytes left allocated, create-time and prepare-time
     double create_ms = 0.0, prepare_ms = 0.0;

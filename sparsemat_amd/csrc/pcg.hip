@@ -15,10 +15,13 @@
 // bodies and polls one small block per batch (solve_in_batches, internal.hpp: CG's loop) -- no synchronisation inside an iteration.
 // Reductions: fixed grid, per-thread strided sums, wave butterfly, LDS across waves, one block folds the partials in
 // index order -- deterministic.
+// The second half of the file is the same recurrence preconditioned by symmetric Gauss-Seidel (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec):
+// z is a vector there, the result of two level-scheduled triangular solves (trisolve.hip); the scalars, k_pcg_alpha and the sums are these.
 #include "internal.hpp"
 #include "solver_tree.hpp"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 using namespace smh;
@@ -293,6 +296,218 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
     return rc;
 }
 
+
+// ---- symmetric Gauss-Seidel: M = (D + L) D^-1 (D + U), z = M^-1 r by two triangular solves (trisolve.hip) ---------------------------
+// The recurrence above with that z, which is a vector here: w = (D + L)^-1 r, then z = (D + U)^-1 (w * d) with the product formed
+// inside the upper solve.  The sums are Jacobi's (k_pcg_update's sweep and the one-workgroup fold), one at a time; p.Ap as above.
+
+// per-workgroup partials of x.y (with x == y: of r.r), gated by "active" unless ALWAYS
+template <typename T, bool ALWAYS>
+__global__ void __launch_bounds__(kBlock)
+k_sgs_dot(const PcgScalars<T> *__restrict__ sc, const T *__restrict__ x, const T *__restrict__ y, uint64_t n, T *__restrict__ part) {
+    constexpr int V = 16 / sizeof(T);
+    typedef T VT __attribute__((ext_vector_type(V)));
+    if (!ALWAYS && !sc->active) return;
+    T a = T(0);
+    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        const VT xv = *(reinterpret_cast<const VT *>(x) + q), yv = *(reinterpret_cast<const VT *>(y) + q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) a = p_add(a, p_mul(xv[e], yv[e]));
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) a = p_add(a, p_mul(x[i], y[i]));
+    const T t = block_sum1(a);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// the entered body's r -= ap*alpha and x += p*alpha in one sweep, and the partials of the new r.r
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_sgs_update(const PcgScalars<T> *__restrict__ sc, T *__restrict__ r, const T *__restrict__ ap, const T *__restrict__ p, T *__restrict__ x, uint64_t n,
+             T *__restrict__ part_rr) {
+    constexpr int V = 16 / sizeof(T);
+    typedef T VT __attribute__((ext_vector_type(V)));
+    if (!sc->active) return;  // block-uniform
+    const T alpha = sc->alpha;
+    T s_rr = T(0);
+    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT rv = *(reinterpret_cast<const VT *>(r) + q), xv = *(reinterpret_cast<const VT *>(x) + q);
+        const VT av = *(reinterpret_cast<const VT *>(ap) + q), pv = *(reinterpret_cast<const VT *>(p) + q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            rv[e] = p_add(rv[e], -p_mul(av[e], alpha));
+            xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
+            s_rr = p_add(s_rr, p_mul(rv[e], rv[e]));
+        }
+        *(reinterpret_cast<VT *>(r) + q) = rv;
+        *(reinterpret_cast<VT *>(x) + q) = xv;
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        const T ri = p_add(r[i], -p_mul(ap[i], alpha));
+        r[i] = ri;
+        x[i] = p_add(x[i], p_mul(p[i], alpha));
+        s_rr = p_add(s_rr, p_mul(ri, ri));
+    }
+    const T t = block_sum1(s_rr);
+    if (threadIdx.x == 0) part_rr[blockIdx.x] = t;
+}
+
+// one workgroup folds the partials.  WHAT 0: rr of the initial residual; 1: rr, then the stop test (before beta); 2: the first
+// r.z; 3: rz' = r.z, beta = rz' / rz, rz = rz'
+template <typename T, int WHAT>
+__global__ void __launch_bounds__(kBlock) k_sgs_fold(PcgScalars<T> *sc, const T *__restrict__ part, unsigned n_parts) {
+    if ((WHAT == 1 || WHAT == 3) && !sc->active) return;
+    T a = T(0);
+    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
+    const T v = block_sum1(a);
+    if (threadIdx.x == 0) {
+        if (WHAT == 0) {
+            sc->rr = v;
+        } else if (WHAT == 1) {
+            sc->rr = v;
+            if (sqrt((double)v) < sc->tol) {
+                sc->converged = 1;
+                sc->active = 0;
+            }
+        } else if (WHAT == 2) {
+            sc->rz = v;
+        } else {
+            sc->beta = p_div(v, sc->rz);
+            sc->rz = v;
+        }
+    }
+}
+
+// p = p*beta + z while the loop goes on.  FIRST: p = z
+template <typename T, bool FIRST>
+__global__ void __launch_bounds__(kBlock) k_sgs_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__restrict__ z, uint64_t n) {
+    if (!FIRST && !sc->active) return;
+    const T beta = FIRST ? T(0) : sc->beta;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        p[i] = FIRST ? z[i] : p_add(p_mul(p[i], beta), z[i]);
+}
+
+// most nodes of a captured batch (a linear chain): beyond it the bodies per batch go down, and a single body beyond it runs
+// uncaptured.  How the bodies reach the device changes no bit.  SMH_SGS_GRAPH_NODES: tuning knob
+size_t sgs_graph_nodes() {
+    if (const char *e = getenv("SMH_SGS_GRAPH_NODES")) return (size_t)strtoull(e, nullptr, 10);
+    return 4096;
+}
+
+// z = M^-1 r on stream s (w: n values of scratch; the schedules exist)
+template <typename T>
+int sgs_apply_enqueue(smh_crs *m, const T *r, T *w, T *z, const uint32_t *active, hipStream_t s) {
+    SMH_TRY(trisolve_enqueue(m, SMH_TRI_LOWER, SMH_DIAG_NON_UNIT, false, r, w, active, s));
+    return trisolve_enqueue(m, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, true, w, z, active, s);
+}
+
+// b_in / x_io: n values each, in host or device memory (the copies are hipMemcpyDefault); x_io is written once, after the loop
+template <typename T>
+int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+              double *rr_out) {
+    const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    Stream own;  // the solve runs on a stream of its own
+    Scratch ws;
+    PinnedBuf h_sc;
+    int converged = 0;
+    size_t iters = 0;
+    double rr = 0.0;
+    const unsigned grid = pcg_grid(n);
+    auto go = [&]() -> int {
+        SMH_TRY(columns_within_n_cols(m, "SGS preconditioner"));
+        SMH_TRY(ensure_tri_schedule(m, SMH_TRI_LOWER));
+        SMH_TRY(ensure_tri_schedule(m, SMH_TRI_UPPER));
+        SMH_TRY(own.create());
+        const hipStream_t s = own.get();
+        T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_z = nullptr, *d_w = nullptr, *d_part = nullptr, *d_dot = nullptr;
+        PcgScalars<T> *d_sc = nullptr;
+        unsigned long long *d_bad = nullptr;
+        SMH_TRY(ws.alloc(&d_x, n)); SMH_TRY(ws.alloc(&d_r, n)); SMH_TRY(ws.alloc(&d_p, n));
+        SMH_TRY(ws.alloc(&d_ap, n)); SMH_TRY(ws.alloc(&d_z, n)); SMH_TRY(ws.alloc(&d_w, n));
+        SMH_TRY(ws.alloc(&d_part, (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
+        SMH_TRY(ws.alloc(&d_sc, 1));
+        SMH_TRY(ws.alloc(&d_bad, 1));
+        SMH_TRY(h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
+        T *part = d_part, *dot_scratch = d_part + kPcgBlocks, *fold_scratch = dot_scratch + kReducePartials + 8;
+        const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
+        if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
+        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
+        // the diagonal's values are read once, here: a zero one cannot be divided by (d_w takes them and is overwritten later)
+        unsigned long long bad = ~0ull;
+        SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
+        if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, m->d_off, m->d_col, (const T *)m->d_val, (uint64_t)n, d_w, d_bad);
+        SMH_HIP(hipGetLastError());
+        SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+        if (n) {
+            SMH_HIP(hipMemcpyAsync(d_r, b_in, n * sizeof(T), hipMemcpyDefault, s));
+            SMH_HIP(hipMemcpyAsync(d_x, x_io, n * sizeof(T), hipMemcpyDefault, s));
+        }
+        SMH_HIP(hipStreamSynchronize(s));
+        if (bad != ~0ull) return fail(SMH_ERR_INVALID, "SGS preconditioner: zero or absent diagonal entry in row %llu", bad);
+        const uint32_t *active = &d_sc->active;
+        // r = b - A x; z = M^-1 r; rr, rz; p = z
+        hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
+        SMH_TRY(spmv_enqueue(m, d_x, n, d_ap, variant, s));
+        if (n) SMH_TRY(launch_ew(dt, Ew::Sub, d_r, d_ap, n, 0.0, nullptr, s));
+        SMH_TRY(sgs_apply_enqueue<T>(m, d_r, d_w, d_z, nullptr, s));
+        hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_r, (uint64_t)n, part);
+        hipLaunchKernelGGL((k_sgs_fold<T, 0>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
+        hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_z, (uint64_t)n, part);
+        hipLaunchKernelGGL((k_sgs_fold<T, 2>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
+        hipLaunchKernelGGL((k_sgs_p<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_z, (uint64_t)n);
+        SMH_HIP(hipGetLastError());
+        size_t spmv_nodes = 1;
+        auto body = [&]() -> int {
+            SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, variant, s, d_dot));
+            if (d_dot && n_dot > (size_t)kReducePartials) {
+                const unsigned fb = reduce_blocks(n_dot);
+                hipLaunchKernelGGL((k_pcg_sum_stage1<T>), dim3(fb), dim3(kBlock), 0, s, d_dot, (uint64_t)n_dot, fold_scratch);
+                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, fold_scratch, fb);
+            } else if (d_dot) {
+                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, d_dot, (uint32_t)n_dot);
+            } else {
+                if (n) SMH_TRY(launch_dot(dt, d_p, d_ap, n, dot_scratch, dot_scratch + kReducePartials, s));
+                else SMH_HIP(hipMemsetAsync(dot_scratch + kReducePartials, 0, sizeof(T), s));
+                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, dot_scratch + kReducePartials, 1u);
+            }
+            hipLaunchKernelGGL((k_sgs_update<T>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_p, d_x, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_sgs_fold<T, 1>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
+            SMH_TRY(sgs_apply_enqueue<T>(m, d_r, d_w, d_z, active, s));
+            hipLaunchKernelGGL((k_sgs_dot<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_z, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_sgs_fold<T, 3>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
+            hipLaunchKernelGGL((k_sgs_p<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_z, (uint64_t)n);
+            SMH_HIP(hipGetLastError());
+            return SMH_OK;
+        };
+        // the node budget of a captured batch: the two solves' launches, the product (a few nodes at most) and the tail of 8
+        const size_t per_body = m->tri[SMH_TRI_LOWER].launches.size() + m->tri[SMH_TRI_UPPER].launches.size() + spmv_nodes + 3 + 8;
+        const size_t budget = sgs_graph_nodes();
+        size_t bodies = check_every;
+        if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
+        SMH_TRY(solve_in_batches(dt, s, iter_max, bodies, body, d_sc, h_sc.get(), &converged, &iters, &rr, per_body <= budget));
+        if (n) SMH_HIP(hipMemcpyAsync(x_io, d_x, n * sizeof(T), hipMemcpyDefault, s));
+        SMH_HIP(hipStreamSynchronize(s));
+        return SMH_OK;
+    };
+    const int rc = keep_error(go(), [&] {
+        if (own.get()) (void)hipStreamSynchronize(own.get());
+        (void)hipGetLastError();
+    });
+    if (rc != SMH_OK) return rc;
+    if (iters_out) *iters_out = iters;
+    if (rr_out) *rr_out = rr;
+    return rc;
+}
+
+int pcg_sgs(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
+            double *rr_out) {
+    if (check_every == 0) check_every = 8;
+    if (m->orphans) return fail(SMH_ERR_INVALID, "SGS preconditioner: the handle holds an orphaned entry");
+    if (m->dtype == SMH_F64) return pcg_sgs_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return pcg_sgs_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
 }  // namespace
 
 extern "C" int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
@@ -305,4 +520,50 @@ extern "C" int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len
     if (smh_crs_dtype(m) == SMH_F64)
         return pcg_t<double>(m, (const double *)b_host, (double *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
     return pcg_t<float>(m, (const float *)b_host, (float *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
+}
+
+// ---- the symmetric Gauss-Seidel preconditioner and its CG; the statuses are decided here, before any launch -------------------------
+extern "C" int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z) {
+    if (!m || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (r->dtype != m->dtype || z->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (m->n_rows != r->n || m->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (m->orphans) return fail(SMH_ERR_INVALID, "SGS preconditioner: the handle holds an orphaned entry");
+    const size_t n = m->n_rows, bytes = n * dtype_size(m->dtype);
+    const char *pr = (const char *)r->d, *pz = (const char *)z->d;
+    if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "sgs_apply: r and z overlap in part");
+    SMH_TRY(columns_within_n_cols(m, "SGS preconditioner"));
+    SMH_TRY(ensure_tri_schedule(m, SMH_TRI_LOWER));
+    SMH_TRY(ensure_tri_schedule(m, SMH_TRI_UPPER));
+    if (m->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
+        return fail(SMH_ERR_INVALID, "SGS preconditioner: no diagonal entry stored in row %llu", (unsigned long long)m->tri[SMH_TRI_LOWER].first_no_diag);
+    Scratch scr;
+    char *w = nullptr;
+    SMH_TRY(scr.alloc(&w, bytes));
+    const hipStream_t s = m->stream;
+    int rc = trisolve_enqueue(m, SMH_TRI_LOWER, SMH_DIAG_NON_UNIT, false, r->d, w, nullptr, s);
+    if (rc == SMH_OK) rc = trisolve_enqueue(m, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, true, w, z->d, nullptr, s);
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)hipStreamSynchronize(s); (void)hipGetLastError(); });
+    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
+    return SMH_OK;
+}
+
+extern "C" int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
+                                     size_t *iters_out, double *rr_out) {
+    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
+    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");                        // linearsolver.rs:30-32
+    if (m->n_rows != b->n || m->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");  // :33-36
+    return pcg_sgs(m, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
+extern "C" int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
+                                 int variant, size_t *iters_out, double *rr_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    const size_t n = m->n_rows;
+    if (n != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    return pcg_sgs(m, b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out);
 }

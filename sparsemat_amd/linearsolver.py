@@ -8,6 +8,8 @@
                                all-reduces (p.Ap and r.r) on device-resident 1-element tensors; the vector
                                updates are the library's kernels with device-resident scalars
                                (``smh_blas_*_dev``), so no scalar visits the host except the stop test.
+* ``SGSConjugateGradient``  -- an extension: CG preconditioned by symmetric Gauss-Seidel through two level-scheduled sparse
+                               triangular solves (``smh_pcg_sgs_solve*``), device-resident like ``ConjugateGradient``.
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
                                device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
 """
@@ -107,6 +109,37 @@ class JacobiConjugateGradient:
         iters, rr = C.c_size_t(), C.c_double()
         check(lib().smh_pcg_jacobi_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
                                          x.size, self.tol, self.iter_max, _lib.VARIANTS[self.variant], C.byref(iters), C.byref(rr)))
+        self.iterations, self.r_norm_squared = iters.value, rr.value
+        return x
+
+
+class SGSConjugateGradient:
+    """CG preconditioned by symmetric Gauss-Seidel, M = (D + L) D^-1 (D + U) -- an EXTENSION: the recurrence of
+    ``JacobiConjugateGradient`` with z = M^-1 r by two level-scheduled sparse triangular solves (``smh_pcg_sgs_solve*``); same
+    guards, stop rule and panics, device-resident like ``ConjugateGradient``.  The number of levels -- hence of kernel launches
+    per body -- follows the ordering of the matrix (``SparseMatCRS.trisolve_levels``): a red-black or multicolour numbering
+    (``permute_symmetric``) has few.  x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
+        self.tol = float(tol)
+        self.iter_max = int(iter_max)
+        self.variant = variant
+        self.check_every = int(check_every)
+        self.iterations = None
+        self.r_norm_squared = None
+
+    def solve(self, mat, b, x):
+        iters, rr = C.c_size_t(), C.c_double()
+        var = _lib.VARIANTS[self.variant]
+        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
+            check(lib().smh_pcg_sgs_solve_vec(mat._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
+                                              C.byref(iters), C.byref(rr)))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
+                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
+            bb = np.ascontiguousarray(b, dtype=mat.dtype)
+            check(lib().smh_pcg_sgs_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
+                                          x.size, self.tol, self.iter_max, var, C.byref(iters), C.byref(rr)))
         self.iterations, self.r_norm_squared = iters.value, rr.value
         return x
 

@@ -190,6 +190,44 @@ class SparseMatCRS:
         check(lib().smh_crs_rcm(self._h, perm.ctypes.data, C.byref(comps), C.byref(levels)))
         return perm[:n], dict(n_components=comps.value, n_levels=levels.value)
 
+    # ---- sparse triangular solves and symmetric Gauss-Seidel (extensions; csrc/trisolve.hip, csrc/pcg.hip) ------------------
+    def trisolve_levels(self, uplo="lower"):
+        """The level schedule of the ``uplo`` triangle (``smh_crs_trisolve_levels``; built on the device on first use):
+        dict(n_levels, level_of_row (np.uint32, n_rows), n_launches -- kernel launches one solve enqueues --, small_level_rows --
+        the R up to which consecutive levels share one single-workgroup launch)."""
+        n = self.n_rows()
+        lev = np.zeros(max(n, 1), np.uint32)
+        n_levels, n_launches, small = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().smh_crs_trisolve_levels(self._h, _lib.UPLO[uplo], C.byref(n_levels), lev.ctypes.data, C.byref(n_launches), C.byref(small)))
+        return dict(n_levels=n_levels.value, level_of_row=lev[:n], n_launches=n_launches.value, small_level_rows=small.value)
+
+    def trisolve(self, b, uplo="lower", unit_diagonal=False):
+        """x = T^-1 b with T the ``uplo`` triangle of this square matrix (the first stored (i, i) of a row is its diagonal entry;
+        ``unit_diagonal``: an implied 1): level-scheduled on the device, every operation rounded once, the subtractions of a row
+        in storage order (``smh_crs_trisolve*``).  A ``DenseVec`` b gives a new ``DenseVec``; anything else a numpy array."""
+        diag = _lib.SMH_DIAG_UNIT if unit_diagonal else _lib.SMH_DIAG_NON_UNIT
+        if isinstance(b, DenseVec):
+            x = DenseVec.zeros(b.dim(), self.dtype)
+            check(lib().smh_crs_trisolve_vec(self._h, _lib.UPLO[uplo], diag, b._h, x._h))
+            return x
+        bb = np.ascontiguousarray(b, dtype=self.dtype)
+        x = np.zeros(bb.size, self.dtype)
+        check(lib().smh_crs_trisolve(self._h, _lib.UPLO[uplo], diag, bb.ctypes.data if bb.size else None, bb.size,
+                                     x.ctypes.data if x.size else None, x.size))
+        return x
+
+    def sgs_apply(self, r):
+        """z = M^-1 r with the symmetric Gauss-Seidel preconditioner M = (D + L) D^-1 (D + U) of this matrix
+        (``smh_crs_sgs_apply_vec``).  A ``DenseVec`` r gives a new ``DenseVec``; anything else a numpy array."""
+        if isinstance(r, DenseVec):
+            z = DenseVec.zeros(r.dim(), self.dtype)
+            check(lib().smh_crs_sgs_apply_vec(self._h, r._h, z._h))
+            return z
+        rv = DenseVec.from_vec(np.ascontiguousarray(r, dtype=self.dtype))
+        z = DenseVec.zeros(rv.dim(), self.dtype)
+        check(lib().smh_crs_sgs_apply_vec(self._h, rv._h, z._h))
+        return z.to_numpy()
+
     def bandwidth(self):
         """(max i - j, max j - i) over the stored entries; (0, 0) without entries."""
         lo, hi = C.c_uint32(), C.c_uint32()
