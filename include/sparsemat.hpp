@@ -312,6 +312,22 @@ class SparseMatCRS {
         if (stats) *stats = st;
         return perm;
     }
+    // a multicolour ordering of the symmetrised pattern (smh_crs_color; computed on the device): the rows sorted by (colour, index),
+    // ready for permute_symmetric, after which a triangular solve has at most n_colors levels.  colors: by ORIGINAL row
+    struct ColorStats {
+        size_t n_colors = 0, n_rounds = 0;
+        std::vector<uint32_t> colors;
+    };
+    std::vector<uint32_t> color(uint32_t seed = 0, ColorStats *stats = nullptr) const {
+        std::vector<uint32_t> perm(n_rows() ? n_rows() : 1);
+        ColorStats st;
+        st.colors.resize(perm.size());
+        detail::check(smh_crs_color(h_, seed, st.colors.data(), perm.data(), &st.n_colors, &st.n_rounds));
+        perm.resize(n_rows());
+        st.colors.resize(n_rows());
+        if (stats) *stats = std::move(st);
+        return perm;
+    }
     // Sparse triangular solves and symmetric Gauss-Seidel (extensions: the reference has neither; sparsemat_hip.h).  The triangle
     // uplo (SMH_TRI_LOWER / SMH_TRI_UPPER) of this square matrix with the first stored (i, i) of a row as its diagonal entry, or an
     // implied 1 (unit_diagonal); level-scheduled on the device, every operation rounded once, a row's subtractions in storage order.

@@ -44,7 +44,7 @@ extern "C" {
  * smh_update_plan_stats, smh_update_plan_destroy; smh_crs_permute, smh_crs_permute_dev, smh_crs_permute_symmetric,
  * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
- * smh_pcg_sgs_solve_vec.  A caller checks smh_abi_version() ==
+ * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -216,6 +216,28 @@ int smh_crs_span_fraction(smh_crs *m, double *out);
  * rounds. */
 int smh_crs_rcm(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out);
 int smh_crs_rcm_dev(const smh_crs *m, uint32_t *perm_out_dev, size_t *n_components_out, size_t *n_levels_out);
+/* A multicolour ordering of a square pattern (csrc/color.hip), for the level-scheduled triangular solves below: colors_out[n_rows] by
+ * ORIGINAL row and perm_out[n_rows] with perm_out[new] = old, ready for smh_crs_permute_symmetric; either array may be NULL, and so
+ * may either count.  Statuses as smh_crs_rcm's, in its order: not square SMH_ERR_NOT_SQUARE; a stored column >= n_cols
+ * SMH_ERR_INDEX_RANGE; 2^31 stored entries or more SMH_ERR_CAPACITY.  n_rows == 0: SMH_OK, 0 colours, 0 rounds.  The _dev form takes the
+ * two arrays on the handle's device, with the conventions of smh_crs_rcm_dev.  Definition (the result equals it exactly; values are
+ * never read):
+ *   graph     smh_crs_rcm's: vertices 0..n-1; u ~ v iff u != v and an entry (u, v) or (v, u) is stored -- stored zeros count,
+ *             duplicates once; deg(v) = number of distinct neighbours;
+ *   hash      h(v) = mix(v XOR seed) on 32 bits, mix the bijection x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ *             x ^= x >> 16, all mod 2^32 (mix(1) = 0x688990c0);
+ *   priority  the 64-bit key deg(v) << 32 | h(v): all keys are distinct; the largest degree comes first, the hash breaks ties;
+ *   colour    visiting the vertices in DESCENDING key order, each takes the smallest colour >= 0 that no neighbour of higher key
+ *             holds (sequential greedy in priority order: *n_colors_out <= max deg + 1);
+ *   rounds    round(v) = 0 when no neighbour has a higher key, else 1 + max round(w) over the neighbours w of higher key;
+ *             *n_rounds_out = 1 + max round -- the Jones-Plassmann schedule of the same colouring, which is what the device executes;
+ *   result    perm_out = the vertices sorted by (colour, index): every colour a contiguous block, the original order kept inside it.
+ * For a structurally symmetric pattern a row of colour c has a neighbour of every colour below c, so after
+ * smh_crs_permute_symmetric(perm) the LOWER schedule's level_of_row IS the colour of that row and it has n_colors levels, UPPER at
+ * most as many; for any other pattern both have at most n_colors.  Greedy with hashed ties does not find the 2 colours of a red-black
+ * ordering (a grid takes 4 .. 6).  Cost: one kernel per round, one small read-back per batch of 4 .. 64 rounds, one radix sort. */
+int smh_crs_color(const smh_crs *m, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors_out, size_t *n_rounds_out);
+int smh_crs_color_dev(const smh_crs *m, uint32_t seed, uint32_t *colors_out_dev, uint32_t *perm_out_dev, size_t *n_colors_out, size_t *n_rounds_out);
 /* #[derive(Clone)] (sparsemat_crs.rs:8): a new handle with copies of the dims, arrays, orphans and the smh_crs_set_* settings;
  * derived forms (codes, plans, column-blocked copies) are rebuilt lazily.  The copy is library-owned even when `a` borrows. */
 int smh_crs_clone(const smh_crs *a, smh_crs **out);

@@ -96,6 +96,8 @@ extern "C" {
     pub fn smh_crs_span_fraction(m: *mut smh_crs, out: *mut f64) -> c_int;
     pub fn smh_crs_rcm(m: *const smh_crs, perm_out: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
     pub fn smh_crs_rcm_dev(m: *const smh_crs, perm_out_dev: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
+    pub fn smh_crs_color(m: *const smh_crs, seed: u32, colors_out: *mut u32, perm_out: *mut u32, n_colors_out: *mut usize, n_rounds_out: *mut usize) -> c_int;
+    pub fn smh_crs_color_dev(m: *const smh_crs, seed: u32, colors_out_dev: *mut u32, perm_out_dev: *mut u32, n_colors_out: *mut usize, n_rounds_out: *mut usize) -> c_int;
     pub fn smh_vec_permute(dst: *mut smh_vec, src: *const smh_vec, perm: *const u32, n_perm: usize, inverse: c_int) -> c_int;
     pub fn smh_vec_permute_dev(dst: *mut smh_vec, src: *const smh_vec, perm_dev: *const u32, n_perm: usize, inverse: c_int) -> c_int;
     pub fn smh_crs_add(a: *const smh_crs, b: *const smh_crs, out: *mut *mut smh_crs) -> c_int;

@@ -198,6 +198,18 @@ impl DeviceCrs {
         (perm, comps, levels)
     }
 
+    /// A multicolour ordering of the symmetrised pattern, computed on the device (`smh_crs_color`): (perm, the colour of every
+    /// ORIGINAL row, colours, rounds).  `perm` lists the rows by (colour, index), ready for `permute_symmetric`.
+    pub fn color(&self, seed: u32) -> (Vec<u32>, Vec<u32>, usize, usize) {
+        let mut perm = vec![0u32; self.n_rows.max(1)];
+        let mut colors = vec![0u32; self.n_rows.max(1)];
+        let (mut n_colors, mut n_rounds) = (0usize, 0usize);
+        check(unsafe { ffi::smh_crs_color(self.handle, seed, colors.as_mut_ptr(), perm.as_mut_ptr(), &mut n_colors, &mut n_rounds) });
+        perm.truncate(self.n_rows);
+        colors.truncate(self.n_rows);
+        (perm, colors, n_colors, n_rounds)
+    }
+
     /// (max i - j, max j - i) over the stored entries.
     pub fn bandwidth(&self) -> (u32, u32) {
         let (mut lo, mut hi) = (0u32, 0u32);

@@ -58,6 +58,8 @@ SIGNATURES = {
     "smh_crs_span_fraction": (_int, [_vp, C.POINTER(C.c_double)]),
     "smh_crs_rcm": (_int, [_vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "smh_crs_rcm_dev": (_int, [_vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "smh_crs_color": (_int, [_vp, C.c_uint32, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "smh_crs_color_dev": (_int, [_vp, C.c_uint32, _vp, _vp, C.POINTER(_sz), C.POINTER(_sz)]),
     "smh_vec_permute": (_int, [_vp, _vp, _vp, _sz, _int]),
     "smh_vec_permute_dev": (_int, [_vp, _vp, _vp, _sz, _int]),
     "smh_crs_clone": (_int, [_vp, C.POINTER(_vp)]),

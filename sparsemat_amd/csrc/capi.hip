@@ -597,6 +597,42 @@ int smh_crs_rcm_dev(const smh_crs *m, uint32_t *perm_out_dev, size_t *n_componen
     return rcm_common(m, perm_out_dev, n_components_out, n_levels_out, true);
 }
 
+static int color_common(const smh_crs *m, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors_out, size_t *n_rounds_out,
+                        bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    SMH_TRY(columns_within_n_cols(m, "color"));
+    const size_t n = m->n_rows;
+    if (on_device) {
+        if (colors_out) SMH_TRY(check_dev_array(colors_out, m->device, "colors_out"));
+        if (perm_out) SMH_TRY(check_dev_array(perm_out, m->device, "perm_out"));
+        SMH_HIP(hipDeviceSynchronize());
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    Scratch scr;
+    uint32_t *d_colors = colors_out, *d_perm = perm_out;
+    if (!on_device) {
+        if (colors_out) SMH_TRY(scr.alloc(&d_colors, n));
+        if (perm_out) SMH_TRY(scr.alloc(&d_perm, n));
+    }
+    size_t colors = 0, rounds = 0;
+    SMH_TRY(color_order(m->d_off, m->d_col, n, m->nnz, seed, d_colors, d_perm, &colors, &rounds, m->stream));
+    if (!on_device && n) {
+        if (colors_out) SMH_HIP(hipMemcpy(colors_out, d_colors, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (perm_out) SMH_HIP(hipMemcpy(perm_out, d_perm, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (n_colors_out) *n_colors_out = colors;
+    if (n_rounds_out) *n_rounds_out = rounds;
+    return SMH_OK;
+}
+
+int smh_crs_color(const smh_crs *m, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors_out, size_t *n_rounds_out) {
+    return color_common(m, seed, colors_out, perm_out, n_colors_out, n_rounds_out, false);
+}
+int smh_crs_color_dev(const smh_crs *m, uint32_t seed, uint32_t *colors_out_dev, uint32_t *perm_out_dev, size_t *n_colors_out, size_t *n_rounds_out) {
+    return color_common(m, seed, colors_out_dev, perm_out_dev, n_colors_out, n_rounds_out, true);
+}
+
 // ---- #[derive(Clone)] (sparsemat_crs.rs:8) and SparseMatrix::add / sub (sparsematrix.rs:123-143, matadd.hip) ------------------
 static thread_local int g_add_route = 2;
 int smh_last_add_route(void) { return g_add_route; }

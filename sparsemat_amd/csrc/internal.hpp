@@ -455,6 +455,13 @@ int launch_vec_permute(int dtype, void *dst, const void *src, const uint32_t *pe
 int launch_bandwidth(const uint32_t *off, const uint32_t *col, size_t n_rows, uint32_t *d_out2, hipStream_t s);  // {max i - j, max j - i}
 // the reverse Cuthill-McKee ordering of a square pattern whose columns are all below n (perm_out: n entries)
 int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, uint32_t *perm_out, size_t *n_components, size_t *n_levels, hipStream_t s);
+// the graph both orderings work on (reorder.hip): u ~ v iff u != v and (u, v) or (v, u) is stored, as adj_off [n + 1] / adj_col with
+// ascending neighbour lists, owned by scr; n > 0; 2^31 stored entries or more are SMH_ERR_CAPACITY
+int symmetrised_pattern(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, Scratch &scr, uint32_t **adj_off_out, uint32_t **adj_col_out,
+                        hipStream_t s);
+// the multicolour ordering of the same pattern (color.hip): colors_out [n] by original row and perm_out [n], either may be null
+int color_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors,
+                size_t *n_rounds, hipStream_t s);
 // A reusable update plan (matplan.hip): the sorted order and the targets of one (rows, cols, ops) stream on one structure.  Runs
 // are numbered class by class: the short ones [0, n_short), then the long ones (more than kPlanLongRun kept operations).
 constexpr uint32_t kPlanLongRun = 64;  // longest run one thread of the short-run kernel folds

@@ -9,7 +9,7 @@
 // vertex v keyed by (position in the order of its earliest-placed parent, deg(v), v), appended in ascending key order.  The
 // result is that order reversed.  n_components counts roots, n_levels counts levels over all components, root levels included.
 //
-// Set-up (once): both directions of every off-diagonal entry as 64-bit keys (row << 32 | column; diagonal entries become a key
+// Set-up (once; symmetrised_pattern, which the multicolour ordering of color.hip shares): both directions of every off-diagonal entry as 64-bit keys (row << 32 | column; diagonal entries become a key
 // in row n, past every vertex), one radix sort, the distinct keys compacted by the library's scan -> the symmetrised pattern
 // adj_off / adj_col with ascending neighbour lists; the vertices sorted by (deg, index) for the root search.
 //
@@ -205,14 +205,12 @@ struct SortTmp {
 
 }  // namespace
 
-// perm_out: device array of n entries.  off / col: a square pattern of n rows whose columns are all below n (the caller's checks).
-int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, uint32_t *perm_out, size_t *n_components, size_t *n_levels, hipStream_t s) {
-    *n_components = *n_levels = 0;
-    if (n == 0) return SMH_OK;
+// The symmetrised pattern of a square pattern of n > 0 rows whose columns are all below n (the set-up at the top of this file):
+// adj_off [n + 1] / adj_col, every neighbour list ascending, both owned by scr.  The set-up arrays are gone when it returns.
+int symmetrised_pattern(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, Scratch &scr, uint32_t **adj_off_out, uint32_t **adj_col_out,
+                        hipStream_t s) {
     const uint64_t m2 = 2 * (uint64_t)nnz;
     if (m2 + 1 >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "the ordering handles fewer than 2^31 stored entries (%zu given)", nnz);
-    Scratch scr;
-    // ---- the symmetrised pattern ----
     uint32_t *adj_off = nullptr, *adj_col = nullptr;
     SMH_TRY(scr.alloc(&adj_off, n + 1));
     uint64_t m_u = 0;
@@ -243,6 +241,18 @@ int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, ui
         SMH_TRY(scr.alloc(&adj_col, 1));
         SMH_HIP(hipMemsetAsync(adj_off, 0, (n + 1) * sizeof(uint32_t), s));
     }
+    *adj_off_out = adj_off;
+    *adj_col_out = adj_col;
+    return SMH_OK;
+}
+
+// perm_out: device array of n entries.  off / col: a square pattern of n rows whose columns are all below n (the caller's checks).
+int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, uint32_t *perm_out, size_t *n_components, size_t *n_levels, hipStream_t s) {
+    *n_components = *n_levels = 0;
+    if (n == 0) return SMH_OK;
+    Scratch scr;
+    uint32_t *adj_off = nullptr, *adj_col = nullptr;
+    SMH_TRY(symmetrised_pattern(off, col, n, nnz, scr, &adj_off, &adj_col, s));
     // ---- degrees, the vertices by (deg, index), the isolated ones ----
     uint32_t *deg = nullptr, *iota = nullptr, *deg_sorted = nullptr, *by_deg = nullptr, *ctl = nullptr, *parent = nullptr, *order = nullptr;
     uint32_t *cand = nullptr, *cand_sorted = nullptr, *level = nullptr;

@@ -190,6 +190,20 @@ class SparseMatCRS:
         check(lib().smh_crs_rcm(self._h, perm.ctypes.data, C.byref(comps), C.byref(levels)))
         return perm[:n], dict(n_components=comps.value, n_levels=levels.value)
 
+    def color(self, seed=0):
+        """A multicolour ordering of the (symmetrised) pattern, computed on the device (``smh_crs_color``: greedy in the order of
+        the keys ``deg << 32 | mix(v ^ seed)``, largest first): ``(perm, stats)`` with ``perm`` an ``np.uint32`` array ready for
+        ``permute_symmetric`` -- the rows sorted by (colour, index) -- and ``stats = dict(colors (np.uint32, by ORIGINAL row),
+        n_colors, n_rounds, color_counts)``.  The triangular solves of the permuted matrix have at most ``n_colors`` levels."""
+        n = self.n_rows()
+        perm = np.zeros(max(n, 1), np.uint32)
+        colors = np.zeros(max(n, 1), np.uint32)
+        n_colors, n_rounds = C.c_size_t(), C.c_size_t()
+        check(lib().smh_crs_color(self._h, int(seed) & 0xFFFFFFFF, colors.ctypes.data, perm.ctypes.data, C.byref(n_colors), C.byref(n_rounds)))
+        colors = colors[:n]
+        return perm[:n], dict(colors=colors, n_colors=n_colors.value, n_rounds=n_rounds.value,
+                              color_counts=np.bincount(colors, minlength=n_colors.value))
+
     # ---- sparse triangular solves and symmetric Gauss-Seidel (extensions; csrc/trisolve.hip, csrc/pcg.hip) ------------------
     def trisolve_levels(self, uplo="lower"):
         """The level schedule of the ``uplo`` triangle (``smh_crs_trisolve_levels``; built on the device on first use):
