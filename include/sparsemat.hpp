@@ -353,6 +353,24 @@ class SparseMatCRS {
     }
     // z = M^-1 r, M = (D + L) D^-1 (D + U); z may be r
     void sgs_apply(const DenseVec<T> &r, DenseVec<T> &z) const { detail::check(smh_crs_sgs_apply_vec(h_, r.handle(), z.handle())); }
+    // ILU(0), the incomplete LU factorization without fill (an extension; smh_crs_ilu0): a new matrix on this one's pattern holding
+    // the unit-lower L below the diagonal and U on and above it, factored on the device level by level.  Rows strictly ascending
+    // (sort_rows), every diagonal stored.  zero_pivot (optional): the first row whose U(i, i) == 0, no_zero_pivot without one -- not
+    // an error, the values are IEEE's.
+    static constexpr size_t no_zero_pivot = (size_t)-1;
+    SparseMatCRS ilu0(size_t *zero_pivot = nullptr) const {
+        SparseMatCRS f;
+        detail::check(smh_crs_ilu0(h_, &f.h_, zero_pivot));
+        return f;
+    }
+    // this factor again from the values of a, which has the pattern the factor was made on: the bits of a.ilu0(); returns zero_pivot
+    size_t ilu0_refactor(const SparseMatCRS &a) {
+        size_t zero_pivot = no_zero_pivot;
+        detail::check(smh_crs_ilu0_refactor(h_, a.h_, &zero_pivot));
+        return zero_pivot;
+    }
+    // z = U^-1 L^-1 r with this matrix an ilu0 factor; z may be r
+    void ilu_apply(const DenseVec<T> &r, DenseVec<T> &z) const { detail::check(smh_crs_ilu_apply_vec(h_, r.handle(), z.handle())); }
     // {max i - j, max j - i} over the stored entries
     std::pair<uint32_t, uint32_t> bandwidth() const {
         uint32_t lo = 0, hi = 0;
@@ -662,6 +680,39 @@ class SGSConjugateGradient {
     void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
         detail::check(smh_pcg_sgs_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO, &iterations_,
                                         &r_norm_squared_));
+    }
+    size_t iterations() const { return iterations_; }
+    double r_norm_squared() const { return r_norm_squared_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t iter_max_ = 10000;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
+};
+
+// CG preconditioned by ILU(0) -- an extension, not in the reference (smh_pcg_ilu_solve*): SGSConjugateGradient's recurrence with
+// z = U^-1 L^-1 r by the two solves on `factor` (mat.ilu0()); the product is mat's.  Same panics and stop rule.
+class ILUConjugateGradient {
+  public:
+    ILUConjugateGradient() = default;
+    ILUConjugateGradient(double tol, size_t iter_max) : tol_(tol), iter_max_(iter_max) {}
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_pcg_ilu_solve_vec(mat.handle(), factor.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0, &iterations_,
+                                            &r_norm_squared_));
+    }
+    // host vectors, x updated in place
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_pcg_ilu_solve(mat.handle(), factor.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO,
+                                        &iterations_, &r_norm_squared_));
+    }
+    // ... factoring mat first
+    template <typename T, typename V>
+    void solve(const SparseMatCRS<T> &mat, const V &b, V &x) {
+        const SparseMatCRS<T> factor = mat.ilu0();
+        solve(mat, factor, b, x);
     }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }

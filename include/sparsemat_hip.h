@@ -44,7 +44,8 @@ extern "C" {
  * smh_update_plan_stats, smh_update_plan_destroy; smh_crs_permute, smh_crs_permute_dev, smh_crs_permute_symmetric,
  * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
- * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev.  A caller checks smh_abi_version() ==
+ * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
+ * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -712,6 +713,40 @@ int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z);
 int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
                       double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
 int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                          int variant, size_t check_every, size_t *iters_out, double *rr_out);
+
+/* The incomplete LU factorization without fill, ILU(0) -- an EXTENSION.  smh_crs_ilu0: *f_out is a new library-owned handle with
+ * a's offsets, columns, storage order and smh_crs_set_* settings; its values are the unit-lower factor L on the stored (i, c)
+ * with c < i and U on those with c >= i.  It is an ordinary handle (download, mvp, trisolve; the caller destroys it).  With w
+ * a's values and diagpos[k] the position of the stored (k, k), every operation rounded once and nothing fused:
+ *     for i = 0 .. n-1:
+ *       for kk = off[i] .. off[i+1]-1 in storage order, k = col[kk], while k < i:
+ *           w[kk] = w[kk] / w[diagpos[k]]
+ *           for jj = diagpos[k]+1 .. off[k+1]-1  (j = col[jj] > k):
+ *               if row i stores column j at position t:  w[t] = w[t] - w[kk] * w[jj]
+ * Rows are factored level by level of the LOWER schedule of the pattern (smh_crs_trisolve_levels: the same levels and launches).
+ * Statuses, checked before anything is written: SMH_ERR_NOT_SQUARE; SMH_ERR_INVALID for a handle that holds an orphan;
+ * SMH_ERR_INDEX_RANGE for a stored column >= n; SMH_ERR_INVALID for a row whose columns are not strictly ascending (unsorted, or
+ * a duplicate: smh_crs_sort_rows sorts, duplicates are not folded) and for a row without a stored (i, i), the message naming
+ * the first such row; SMH_ERR_INVALID for a NULL a or f_out.  A zero pivot is not an error: the values are IEEE's +-Inf or NaN, as
+ * in the triangular solve.  *zero_pivot_out (may be NULL): the smallest row i whose final U(i, i) compares equal to 0, SIZE_MAX
+ * without one.
+ * smh_crs_ilu0_refactor: new values on the same pattern (time stepping, Newton): a's values are copied into f and factored with
+ * f's schedule; the result is bit for bit that of smh_crs_ilu0(a).  SMH_ERR_DIM_MISMATCH when n differs; SMH_ERR_INVALID when the
+ * dtype, the device, the number of entries, the offsets or the columns differ (compared on the device) or f is a; a's statuses
+ * as above.  A refused call leaves f untouched.
+ * smh_crs_ilu_apply_vec: z = U^-1 L^-1 r as  w = trisolve(f, LOWER, UNIT, r);  z = trisolve(f, UPPER, NON_UNIT, w); z may be r.
+ * Statuses as smh_crs_trisolve_vec's.
+ * smh_pcg_ilu_solve: the recurrence of smh_pcg_sgs_solve with that z: the product (and its p.Ap) is a's, the solves are f's; same
+ * guards, stop rule, check_every and outputs.  A zero or absent diagonal entry of f is SMH_ERR_INVALID (the message names the
+ * row); a and f differing in n SMH_ERR_DIM_MISMATCH, in dtype or device SMH_ERR_INVALID, decided before any launch.  What f's
+ * values are is the caller's business: nothing ties f to a beyond these. */
+int smh_crs_ilu0(const smh_crs *a, smh_crs **f_out, size_t *zero_pivot_out);
+int smh_crs_ilu0_refactor(smh_crs *f, const smh_crs *a, size_t *zero_pivot_out);
+int smh_crs_ilu_apply_vec(smh_crs *f, const smh_vec *r, smh_vec *z);
+int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                      double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
+int smh_pcg_ilu_solve_vec(smh_crs *a, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                           int variant, size_t check_every, size_t *iters_out, double *rr_out);
 
 /* BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is

@@ -67,6 +67,14 @@ extern "C" {
                              iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_pcg_sgs_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
                                  variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    pub fn smh_crs_ilu0(a: *const smh_crs, f_out: *mut *mut smh_crs, zero_pivot_out: *mut usize) -> c_int;
+    pub fn smh_crs_ilu0_refactor(f: *mut smh_crs, a: *const smh_crs, zero_pivot_out: *mut usize) -> c_int;
+    pub fn smh_crs_ilu_apply_vec(f: *mut smh_crs, r: *const smh_vec, z: *mut smh_vec) -> c_int;
+    pub fn smh_pcg_ilu_solve(a: *mut smh_crs, f: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                             x_len: usize, tol: c_double, iter_max: usize, variant: c_int,
+                             iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    pub fn smh_pcg_ilu_solve_vec(a: *mut smh_crs, f: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
+                                 variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

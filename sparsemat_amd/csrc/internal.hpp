@@ -555,6 +555,7 @@ int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
 // columns are all below n.  trisolve_enqueue: x = T^-1 b on s by that schedule (built before; device pointers, x may be b); scale_rhs:
 // the right-hand side is b[i] * val[diagpos[i]], rounded once; active (optional): a device flag, 0 = every launch returns at once
 int ensure_tri_schedule(::smh_crs *m, int uplo);
+int tri_lanes(const ::smh_crs *m);  // lanes of the group a row gets, in the solves and in ilu.hip
 int trisolve_enqueue(::smh_crs *m, int uplo, int diag, bool scale_rhs, const void *b, void *x, const uint32_t *active, hipStream_t s);
 
 // ---- the device-resident solvers (cg.hip, pcg.hip, par.hip) ----------------------------------------------------------------------

@@ -17,6 +17,7 @@
 // index order -- deterministic.
 // The second half of the file is the same recurrence preconditioned by symmetric Gauss-Seidel (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec):
 // z is a vector there, the result of two level-scheduled triangular solves (trisolve.hip); the scalars, k_pcg_alpha and the sums are these.
+// ILU(0)-PCG (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) is that half again with the solves on a factor handle (ilu.hip): TriPrecond.
 #include "internal.hpp"
 #include "solver_tree.hpp"
 
@@ -395,17 +396,35 @@ size_t sgs_graph_nodes() {
     return 4096;
 }
 
-// z = M^-1 r on stream s (w: n values of scratch; the schedules exist)
-template <typename T>
-int sgs_apply_enqueue(smh_crs *m, const T *r, T *w, T *z, const uint32_t *active, hipStream_t s) {
-    SMH_TRY(trisolve_enqueue(m, SMH_TRI_LOWER, SMH_DIAG_NON_UNIT, false, r, w, active, s));
-    return trisolve_enqueue(m, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, true, w, z, active, s);
+// A preconditioner applied by two triangular solves on one handle: z = T_upper^-1 (scale(T_lower^-1 r)).  SGS: the matrix itself,
+// both diagonals stored, the right-hand side of the upper solve scaled by the diagonal.  ILU(0): the factor handle (ilu.hip), the
+// lower solve with the unit diagonal, no scaling.
+struct TriPrecond {
+    smh_crs *f;
+    int lower_diag;
+    bool scale_rhs;
+    const char *name;
+};
+TriPrecond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
+TriPrecond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
+
+// z = M^-1 r on stream s (w: n values of scratch; z may be r; the schedules exist)
+int precond_apply_enqueue(const TriPrecond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
+    SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.lower_diag, false, r, w, active, s));
+    return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
+}
+
+// the checks of a preconditioner handle that need the device: columns, schedules, a stored diagonal in every row
+int precond_prepare(const TriPrecond &pc) {
+    SMH_TRY(columns_within_n_cols(pc.f, pc.name));
+    SMH_TRY(ensure_tri_schedule(pc.f, SMH_TRI_LOWER));
+    return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
 }
 
 // b_in / x_io: n values each, in host or device memory (the copies are hipMemcpyDefault); x_io is written once, after the loop
 template <typename T>
-int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
-              double *rr_out) {
+int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+              size_t *iters_out, double *rr_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     Stream own;  // the solve runs on a stream of its own
     Scratch ws;
@@ -415,9 +434,7 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
     double rr = 0.0;
     const unsigned grid = pcg_grid(n);
     auto go = [&]() -> int {
-        SMH_TRY(columns_within_n_cols(m, "SGS preconditioner"));
-        SMH_TRY(ensure_tri_schedule(m, SMH_TRI_LOWER));
-        SMH_TRY(ensure_tri_schedule(m, SMH_TRI_UPPER));
+        SMH_TRY(precond_prepare(pc));
         SMH_TRY(own.create());
         const hipStream_t s = own.get();
         T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_z = nullptr, *d_w = nullptr, *d_part = nullptr, *d_dot = nullptr;
@@ -433,10 +450,11 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
         const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
         SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
+        if (pc.f != m) SMH_HIP(hipStreamSynchronize(pc.f->stream));
         // the diagonal's values are read once, here: a zero one cannot be divided by (d_w takes them and is overwritten later)
         unsigned long long bad = ~0ull;
         SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
-        if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, m->d_off, m->d_col, (const T *)m->d_val, (uint64_t)n, d_w, d_bad);
+        if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, pc.f->d_off, pc.f->d_col, (const T *)pc.f->d_val, (uint64_t)n, d_w, d_bad);
         SMH_HIP(hipGetLastError());
         SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
         if (n) {
@@ -444,13 +462,13 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
             SMH_HIP(hipMemcpyAsync(d_x, x_io, n * sizeof(T), hipMemcpyDefault, s));
         }
         SMH_HIP(hipStreamSynchronize(s));
-        if (bad != ~0ull) return fail(SMH_ERR_INVALID, "SGS preconditioner: zero or absent diagonal entry in row %llu", bad);
+        if (bad != ~0ull) return fail(SMH_ERR_INVALID, "%s: zero or absent diagonal entry in row %llu", pc.name, bad);
         const uint32_t *active = &d_sc->active;
         // r = b - A x; z = M^-1 r; rr, rz; p = z
         hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
         SMH_TRY(spmv_enqueue(m, d_x, n, d_ap, variant, s));
         if (n) SMH_TRY(launch_ew(dt, Ew::Sub, d_r, d_ap, n, 0.0, nullptr, s));
-        SMH_TRY(sgs_apply_enqueue<T>(m, d_r, d_w, d_z, nullptr, s));
+        SMH_TRY(precond_apply_enqueue(pc, d_r, d_w, d_z, nullptr, s));
         hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_r, (uint64_t)n, part);
         hipLaunchKernelGGL((k_sgs_fold<T, 0>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
         hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_z, (uint64_t)n, part);
@@ -473,7 +491,7 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
             }
             hipLaunchKernelGGL((k_sgs_update<T>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_p, d_x, (uint64_t)n, part);
             hipLaunchKernelGGL((k_sgs_fold<T, 1>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
-            SMH_TRY(sgs_apply_enqueue<T>(m, d_r, d_w, d_z, active, s));
+            SMH_TRY(precond_apply_enqueue(pc, d_r, d_w, d_z, active, s));
             hipLaunchKernelGGL((k_sgs_dot<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_z, (uint64_t)n, part);
             hipLaunchKernelGGL((k_sgs_fold<T, 3>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
             hipLaunchKernelGGL((k_sgs_p<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_z, (uint64_t)n);
@@ -481,7 +499,7 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
             return SMH_OK;
         };
         // the node budget of a captured batch: the two solves' launches, the product (a few nodes at most) and the tail of 8
-        const size_t per_body = m->tri[SMH_TRI_LOWER].launches.size() + m->tri[SMH_TRI_UPPER].launches.size() + spmv_nodes + 3 + 8;
+        const size_t per_body = pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size() + spmv_nodes + 3 + 8;
         const size_t budget = sgs_graph_nodes();
         size_t bodies = check_every;
         if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
@@ -500,12 +518,39 @@ int pcg_sgs_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t i
     return rc;
 }
 
+int pcg_tri(smh_crs *m, const TriPrecond &pc, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+            size_t *iters_out, double *rr_out) {
+    if (check_every == 0) check_every = 8;
+    if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (m->dtype == SMH_F64) return pcg_tri_t<double>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return pcg_tri_t<float>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
 int pcg_sgs(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
             double *rr_out) {
-    if (check_every == 0) check_every = 8;
-    if (m->orphans) return fail(SMH_ERR_INVALID, "SGS preconditioner: the handle holds an orphaned entry");
-    if (m->dtype == SMH_F64) return pcg_sgs_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
-    return pcg_sgs_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return pcg_tri(m, sgs_precond(m), b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
+// z = M^-1 r by the handle's stream; r and z: n values each on the device, equal or disjoint
+int precond_apply(const TriPrecond &pc, const smh_vec *r, smh_vec *z, const char *what) {
+    smh_crs *f = pc.f;
+    if (r->dtype != f->dtype || z->dtype != f->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
+    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (f->n_rows != r->n || f->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    const size_t n = f->n_rows, bytes = n * dtype_size(f->dtype);
+    const char *pr = (const char *)r->d, *pz = (const char *)z->d;
+    if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "%s: r and z overlap in part", what);
+    SMH_TRY(precond_prepare(pc));
+    if (f->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
+        return fail(SMH_ERR_INVALID, "%s: no diagonal entry stored in row %llu", pc.name, (unsigned long long)f->tri[SMH_TRI_LOWER].first_no_diag);
+    Scratch scr;
+    char *w = nullptr;
+    SMH_TRY(scr.alloc(&w, bytes));
+    const hipStream_t s = f->stream;
+    const int rc = precond_apply_enqueue(pc, r->d, w, z->d, nullptr, s);
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)hipStreamSynchronize(s); (void)hipGetLastError(); });
+    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
+    return SMH_OK;
 }
 
 }  // namespace
@@ -525,27 +570,7 @@ extern "C" int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len
 // ---- the symmetric Gauss-Seidel preconditioner and its CG; the statuses are decided here, before any launch -------------------------
 extern "C" int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z) {
     if (!m || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (r->dtype != m->dtype || z->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (m->n_rows != r->n || m->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (m->orphans) return fail(SMH_ERR_INVALID, "SGS preconditioner: the handle holds an orphaned entry");
-    const size_t n = m->n_rows, bytes = n * dtype_size(m->dtype);
-    const char *pr = (const char *)r->d, *pz = (const char *)z->d;
-    if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "sgs_apply: r and z overlap in part");
-    SMH_TRY(columns_within_n_cols(m, "SGS preconditioner"));
-    SMH_TRY(ensure_tri_schedule(m, SMH_TRI_LOWER));
-    SMH_TRY(ensure_tri_schedule(m, SMH_TRI_UPPER));
-    if (m->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
-        return fail(SMH_ERR_INVALID, "SGS preconditioner: no diagonal entry stored in row %llu", (unsigned long long)m->tri[SMH_TRI_LOWER].first_no_diag);
-    Scratch scr;
-    char *w = nullptr;
-    SMH_TRY(scr.alloc(&w, bytes));
-    const hipStream_t s = m->stream;
-    int rc = trisolve_enqueue(m, SMH_TRI_LOWER, SMH_DIAG_NON_UNIT, false, r->d, w, nullptr, s);
-    if (rc == SMH_OK) rc = trisolve_enqueue(m, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, true, w, z->d, nullptr, s);
-    if (rc != SMH_OK) return keep_error(rc, [&] { (void)hipStreamSynchronize(s); (void)hipGetLastError(); });
-    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
-    return SMH_OK;
+    return precond_apply(sgs_precond(m), r, z, "sgs_apply");
 }
 
 extern "C" int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
@@ -566,4 +591,41 @@ extern "C" int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, v
     if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
     if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
     return pcg_sgs(m, b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out);
+}
+
+// ---- ILU(0): the same recurrence and application with the solves on a factor handle (smh_crs_ilu0, ilu.hip); the product and its
+// fused p.Ap come from a ----------------------------------------------------------------------------------------------------------
+extern "C" int smh_crs_ilu_apply_vec(smh_crs *f, const smh_vec *r, smh_vec *z) {
+    if (!f || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
+    return precond_apply(ilu_precond(f), r, z, "ilu_apply");
+}
+
+// what a and f must agree in, decided before any launch
+static int ilu_check_pair(const smh_crs *a, const smh_crs *f) {
+    if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "ILU preconditioner: the factor is not square");
+    if (f->n_rows != a->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "ILU preconditioner: the factor's dimension differs from the matrix's");
+    if (f->dtype != a->dtype) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor's dtype differs from the matrix's");
+    if (f->device != a->device) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor and the matrix live on different devices");
+    return SMH_OK;
+}
+
+extern "C" int smh_pcg_ilu_solve_vec(smh_crs *a, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
+                                     size_t *iters_out, double *rr_out) {
+    if (!a || !f || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (b->dtype != a->dtype || x->dtype != a->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
+    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    SMH_TRY(ilu_check_pair(a, f));
+    if (a->n_rows != b->n || a->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    return pcg_tri(a, ilu_precond(f), b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
+extern "C" int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
+                                 int variant, size_t *iters_out, double *rr_out) {
+    if (!a || !f) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(ilu_check_pair(a, f));
+    const size_t n = a->n_rows;
+    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    return pcg_tri(a, ilu_precond(f), b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out);
 }

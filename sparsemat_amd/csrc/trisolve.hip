@@ -143,15 +143,6 @@ void tri_launch(const smh_crs *m, const TriSchedule &t, const TriSchedule::Launc
     }
 }
 
-// lanes per row: the smallest power of two that holds the mean row in one pass (smh_crs_set_vector_lanes overrides it, as for K1)
-int tri_lanes(const smh_crs *m) {
-    if (m->knobs.forced_lanes) return m->knobs.forced_lanes;
-    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
-    int lanes = 1;
-    while (lanes < kWave && (double)lanes < mean) lanes <<= 1;
-    return lanes;
-}
-
 template <typename T>
 int trisolve_t(smh_crs *m, const TriSchedule &t, int upper, int unit, int scale_rhs, const T *b, T *x, const uint32_t *active, hipStream_t s) {
     const int lanes = tri_lanes(m);
@@ -192,6 +183,15 @@ int tri_check_solve(smh_crs *m, int uplo, int diag, const char *what) {
 }  // namespace
 
 namespace smh {
+
+// lanes per row: the smallest power of two that holds the mean row in one pass (smh_crs_set_vector_lanes overrides it, as for K1)
+int tri_lanes(const smh_crs *m) {
+    if (m->knobs.forced_lanes) return m->knobs.forced_lanes;
+    const double mean = m->n_rows ? (double)m->nnz / (double)m->n_rows : 0.0;
+    int lanes = 1;
+    while (lanes < kWave && (double)lanes < mean) lanes <<= 1;
+    return lanes;
+}
 
 int ensure_tri_schedule(smh_crs *m, int uplo) {
     if (m->tri[uplo].state == Form::Ready) return SMH_OK;

@@ -10,6 +10,8 @@
                                (``smh_blas_*_dev``), so no scalar visits the host except the stop test.
 * ``SGSConjugateGradient``  -- an extension: CG preconditioned by symmetric Gauss-Seidel through two level-scheduled sparse
                                triangular solves (``smh_pcg_sgs_solve*``), device-resident like ``ConjugateGradient``.
+* ``ILUConjugateGradient``  -- an extension: CG preconditioned by ILU(0) (``SparseMatCRS.ilu0``, ``smh_pcg_ilu_solve*``): the same two
+                               solves on a factor computed on the device.
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
                                device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
 """
@@ -140,6 +142,43 @@ class SGSConjugateGradient:
             bb = np.ascontiguousarray(b, dtype=mat.dtype)
             check(lib().smh_pcg_sgs_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
                                           x.size, self.tol, self.iter_max, var, C.byref(iters), C.byref(rr)))
+        self.iterations, self.r_norm_squared = iters.value, rr.value
+        return x
+
+
+class ILUConjugateGradient:
+    """CG preconditioned by the incomplete LU factorization without fill, M = L U (``SparseMatCRS.ilu0``) -- an EXTENSION: the
+    recurrence of ``SGSConjugateGradient`` with z = U^-1 L^-1 r by a unit-lower and an upper triangular solve on the factor
+    (``smh_pcg_ilu_solve*``); the product is the matrix's.  ``solve(mat, b, x, factor=None)`` factors ``mat`` itself when no factor
+    is given (afterwards ``factor`` holds the one used and ``zero_pivot`` what its factorization reported, None for a passed
+    factor).  x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
+        self.tol = float(tol)
+        self.iter_max = int(iter_max)
+        self.variant = variant
+        self.check_every = int(check_every)
+        self.iterations = None
+        self.r_norm_squared = None
+        self.factor = None
+        self.zero_pivot = None
+
+    def solve(self, mat, b, x, factor=None):
+        self.zero_pivot = None
+        if factor is None:
+            factor, self.zero_pivot = mat.ilu0()
+        self.factor = factor
+        iters, rr = C.c_size_t(), C.c_double()
+        var = _lib.VARIANTS[self.variant]
+        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
+            check(lib().smh_pcg_ilu_solve_vec(mat._h, factor._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
+                                              C.byref(iters), C.byref(rr)))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
+                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
+            bb = np.ascontiguousarray(b, dtype=mat.dtype)
+            check(lib().smh_pcg_ilu_solve(mat._h, factor._h, bb.ctypes.data if bb.size else None, bb.size,
+                                          x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var, C.byref(iters), C.byref(rr)))
         self.iterations, self.r_norm_squared = iters.value, rr.value
         return x
 

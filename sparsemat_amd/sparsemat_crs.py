@@ -242,6 +242,37 @@ class SparseMatCRS:
         check(lib().smh_crs_sgs_apply_vec(self._h, rv._h, z._h))
         return z.to_numpy()
 
+    # ---- ILU(0) (an extension; csrc/ilu.hip, applied through csrc/pcg.hip) ------------------------------------------------
+    _NO_PIVOT = C.c_size_t(-1).value  # SIZE_MAX: no zero pivot
+
+    def ilu0(self):
+        """``(f, zero_pivot)``: the incomplete LU factorization without fill of this square matrix (``smh_crs_ilu0``), factored
+        on the device level by level of the lower schedule.  ``f`` is a new matrix on this one's pattern whose values are the
+        unit-lower L below the diagonal and U on and above it; ``zero_pivot`` is None, or the first row whose U(i, i) is 0 (not
+        an error: the values are IEEE's).  Every row must be strictly ascending (``sort_rows``) and store its diagonal."""
+        h, zp = C.c_void_p(), C.c_size_t()
+        check(lib().smh_crs_ilu0(self._h, C.byref(h), C.byref(zp)))
+        return type(self)(h, self.dtype), (None if zp.value == self._NO_PIVOT else zp.value)
+
+    def ilu0_refactor(self, a):
+        """This factor again from the values of ``a``, which has the pattern this factor was made on (``smh_crs_ilu0_refactor``):
+        the bits of ``a.ilu0()`` without a new handle or schedule.  Returns ``zero_pivot`` as ``ilu0`` does."""
+        zp = C.c_size_t()
+        check(lib().smh_crs_ilu0_refactor(self._h, a._h, C.byref(zp)))
+        return None if zp.value == self._NO_PIVOT else zp.value
+
+    def ilu_apply(self, r):
+        """z = U^-1 L^-1 r with this matrix an ``ilu0`` factor: a unit-lower and an upper triangular solve
+        (``smh_crs_ilu_apply_vec``).  A ``DenseVec`` r gives a new ``DenseVec``; anything else a numpy array."""
+        if isinstance(r, DenseVec):
+            z = DenseVec.zeros(r.dim(), self.dtype)
+            check(lib().smh_crs_ilu_apply_vec(self._h, r._h, z._h))
+            return z
+        rv = DenseVec.from_vec(np.ascontiguousarray(r, dtype=self.dtype))
+        z = DenseVec.zeros(rv.dim(), self.dtype)
+        check(lib().smh_crs_ilu_apply_vec(self._h, rv._h, z._h))
+        return z.to_numpy()
+
     def bandwidth(self):
         """(max i - j, max j - i) over the stored entries; (0, 0) without entries."""
         lo, hi = C.c_uint32(), C.c_uint32()
