@@ -448,6 +448,12 @@ int smh_crs_ring_bands(smh_crs *m, uint32_t *bands_out, uint32_t *intervals_out)
 int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out,
                       double *ring_fraction_out, int *active_out, uint32_t *phase_ptr_out,
                       uint32_t *phases_out);
+/* which phases of that plan are REGULAR (read-only; built with the plan): len_out[p], n_phases values, = L when phase p
+ * gathers from the ring (use_ring == 1), L > 0 and offsets[r] == offsets[row_begin] + (r - row_begin) * L for every r in
+ * [row_begin, row_end]; else 0.  Where every phase of the plan gathers from the ring, some phase is regular and the ring phases
+ * stream 16-bit or 12-bit columns, the ring kernel computes the row offsets of the regular phases instead of streaming them
+ * (SMH_RING_REGULAR = auto / 0: 0 = every phase loads its offsets).  The table changes speed only, never a result. */
+int smh_crs_ring_regular(smh_crs *m, uint32_t *len_out);
 
 /* K2c, the column-blocked copy (built on first use; integer structure, checked bit-exact in tests):
  * block b holds the entries with column >> shift == b, as a CSR over all rows whose offsets

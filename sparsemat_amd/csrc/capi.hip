@@ -1281,6 +1281,14 @@ int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out, 
     return SMH_OK;
 }
 
+int smh_crs_ring_regular(smh_crs *m, uint32_t *len_out) {
+    if (!m || !len_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m));
+    if (m->ring.n_phases)
+        SMH_HIP(hipMemcpy(len_out, m->ring.reg_len.get(), m->ring.n_phases * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
 int smh_crs_ring_column_form(smh_crs *m, int *form_out) {
     if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
     bool ring = false;

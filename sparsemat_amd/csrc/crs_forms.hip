@@ -142,6 +142,22 @@ int ensure_ring_plan(smh_crs *m, bool with_bands) {
     SMH_HIP(hipMemcpy(p.phase_ptr.get(), phase_ptr.data(), phase_ptr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!phases.empty())
         SMH_HIP(hipMemcpy(p.phases.get(), phases.data(), phases.size() * sizeof(RingPhase), hipMemcpyHostToDevice));
+    // which ring phases of the plan that was taken (16384 slots, 32768 slots or banded) have rows of one length: those compute their
+    // row offsets instead of streaming them (k_spmv_ring2's REG body).  One read of the offsets, here, so that no launch path builds it.
+    // The kernel that reads the table has the two ring bodies only (see there), so it applies to plans without global-gather phases.
+    SMH_TRY(p.reg_len.alloc(phases.size() + 1));
+    if (!phases.empty()) {
+        std::vector<uint32_t> h_reg(phases.size());
+        SMH_TRY(read_back(p.reg_len.get(), h_reg.data(), phases.size(), m->stream, [&](uint32_t *d_reg) {
+            return launch_ring_regular(m->d_off, p.phases.get(), phases.size(), d_reg, m->stream);
+        }));
+        bool ring_only = true, any_regular = false;
+        for (size_t i = 0; i < phases.size(); ++i) {
+            ring_only = ring_only && phases[i].use_ring == 1u;
+            any_regular = any_regular || h_reg[i] != 0u;
+        }
+        p.reg_applies = ring_only && any_regular;
+    }
     p.blocks = blocks;
     p.n_phases = phases.size();
     p.state = Form::Ready;

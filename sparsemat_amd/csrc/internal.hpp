@@ -503,7 +503,11 @@ int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, con
                       const void *val, const void *x, void *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                       const uint32_t *phase_ptr, const RingPhase *phases, unsigned ring_entries, unsigned bands,
                       hipStream_t s, void *dot_partials = nullptr /* DOT form: y = lhs (read only), n_blocks + 1 partials of lhs . (A x) */,
-                      unsigned block_begin = 0, unsigned block_end = ~0u /* the plan's row ranges [begin, end) only (default: all; not with the DOT form) */);
+                      unsigned block_begin = 0, unsigned block_end = ~0u /* the plan's row ranges [begin, end) only (default: all; not with the DOT form) */,
+                      const uint32_t *reg_len = nullptr /* RingPlan::reg_len: regular phases compute their row offsets (NULL: every phase loads them) */);
+// reg_len[p] = L when phase p gathers from the ring (use_ring == 1), L > 0 and off[r] == off[row_begin] + (r - row_begin) * L for
+// every r in [row_begin, row_end]; else 0.  One read of the offsets.
+int launch_ring_regular(const uint32_t *off, const RingPhase *phases, size_t n_phases, uint32_t *reg_len, hipStream_t s);
 // banded ring (4 bands): per-tile column intervals (the K1s inspector over 64-row tiles) and the 16-bit ring slots
 int launch_tile_intervals(const uint32_t *off, const uint32_t *col, size_t n_rows, size_t tile_rows, size_t max_width,
                           uint32_t *win, uint32_t *d_count, hipStream_t s);
@@ -650,7 +654,9 @@ struct RingPlan {  // K1r
     size_t n_phases = 0;
     DevArray<uint32_t> phase_ptr;
     DevArray<RingPhase> phases;
-    DevArray<uint32_t> win;               // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
+    DevArray<uint32_t> reg_len;           // one per phase: the row length of a ring phase whose rows are all equally long, else 0 (launch_ring_regular)
+    bool reg_applies = false;             // every phase gathers from the ring and some are regular: launches pass reg_len (k_spmv_ring2's REGK form)
+    DevArray<uint32_t> win;              // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
     DevArray<uint16_t> col16;             // 16-bit column array for the ring phases (built from the plan on first use; null: not used)
     // the compact column form (ring_col12.hpp), which the ring phases then stream instead of col16.  c12: NotTried until the counting pass has run; Ready: at most one
     // chunk in 1024 escapes, AUTO takes the form; Refused: AUTO keeps col16.  The arrays exist while the form is in use.

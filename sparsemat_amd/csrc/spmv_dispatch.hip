@@ -1,6 +1,7 @@
 // spmv_dispatch.hip -- which kernel a product runs (AUTO's rules, with the measurements behind every threshold), which derived forms
 // that kernel runs on, and its launches.  Host-side logic only; the forms themselves are built in crs_forms.hip.
 #include <cstdlib>
+#include <cstring>
 
 #include "crs_forms.hpp"
 
@@ -172,11 +173,17 @@ static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x
 
 // one K1r launch over the plan's row ranges [b0, b1) (dot_partials: the DOT form, whole plan only -- see launch_spmv_ring2)
 static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u) {
+    // regular phases compute their row offsets from the plan's table, where it applies (RingPlan::reg_applies) and the ring phases
+    // stream a narrow column form; SMH_RING_REGULAR=0 (tuning knob, read per launch like SMH_RING_COL12): no table, every phase
+    // loads its offsets
+    const char *reg_env = getenv("SMH_RING_REGULAR");
+    const bool reg_off = reg_env && strcmp(reg_env, "auto") != 0 && atoi(reg_env) == 0;
+    const uint32_t *reg_len = m->ring.reg_applies && !reg_off && (m->ring.lo8.get() || m->ring.col16.get()) ? m->ring.reg_len.get() : nullptr;
     // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
     return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(),
                              RingCol12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get()}, m->d_val, x, y, m->n_rows, m->nnz,
                              m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
-                             m->ring.bands, s, dot_partials, b0, b1);
+                             m->ring.bands, s, dot_partials, b0, b1, reg_len);
 }
 
 // Can y = A x also leave the partial sums of x.y (CG's p.Ap) in its epilogue?  Only the K1s kernel does;

@@ -17,6 +17,8 @@
 //   that is safe to read, entries outside the row are masked with selects (never multiplied in: LDS
 //   garbage may be NaN), and the <= 3 entries of an unpadded array's final partial chunk are added by
 //   a one-thread fix-up kernel (in storage order: they are the last entries of their rows).
+//   A REGULAR phase (ring gathers, every row L > 0 entries long: RingPlan::reg_len) does not stream its row offsets at all: they
+//   are off[row_begin] + i * L, computed where the other body loads them (phase_rows<..., REG>, in the REGK form of the kernel).
 #include "internal.hpp"
 #include "ring_col12.hpp"
 
@@ -181,6 +183,17 @@ __device__ __forceinline__ void load_offsets(Unit<T, NCH> &u, const uint32_t *__
     u.o1 = off[r1];
 }
 
+// ... of a REGULAR phase (rows [rb, re] all L entries apart, e0 = off[rb]: RingPlan::reg_len): the same two values without the
+// loads.  32-bit arithmetic is exact: every offset is <= nnz < 2^32.
+template <typename T, int NCH>
+__device__ __forceinline__ void regular_offsets(Unit<T, NCH> &u, uint32_t e0, uint32_t L, uint64_t rb, uint64_t base, uint64_t row_end,
+                                                uint32_t lane) {
+    // wave-uniform: the unit's first row within the phase (clamped to its end) and the rows from there to the end -- nothing can wrap
+    const uint32_t n = (uint32_t)(row_end - rb), d = base - rb < n ? (uint32_t)(base - rb) : n, left = n - d;
+    u.o0 = e0 + (d + (lane < left ? lane : left)) * L;
+    u.o1 = e0 + (d + (lane + 1u < left ? lane + 1u : left)) * L;
+}
+
 // row bounds of (step t, this lane's group), limited to the entries the kernel may touch
 template <int LANES>
 __device__ __forceinline__ void row_bounds(uint32_t o0, uint32_t o1, int t, uint32_t lane, uint32_t nnz_lim,
@@ -292,11 +305,13 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
 }
 
 // cols: the arrays of the column form CF from their first element (colp: the 32-bit columns, the 16-bit ones or the compact form's bytes)
-template <typename T, int LANES, int CH, int GM, int CF, int RING, bool DOT = false>
+// REG: the phase is regular with row length L (RingPlan::reg_len): the units' offsets are computed, the offset array is read for
+// off[rb] alone, and nothing the chunk addresses are made of waits for a load
+template <typename T, int LANES, int CH, int GM, int CF, int RING, bool DOT = false, bool REG = false>
 __device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, const ColStream &cols,
                                            const T *__restrict__ val, const T *__restrict__ x, const T *ring,
                                            T *__restrict__ y, uint64_t rb, uint64_t re, uint32_t nnz_lim,
-                                           uint64_t last_chunk, uint32_t wave, uint32_t lane, T *dacc = nullptr) {
+                                           uint64_t last_chunk, uint32_t wave, uint32_t lane, T *dacc = nullptr, uint32_t L = 0) {
     constexpr int STEPS = LANES;
     constexpr int SBMAX = sizeof(T) == 8 ? SMH_RING2_SB64 : kRing2SB;  // f64 chunks take 12 VGPRs: one step per unit (two: A/B in round 4)
     constexpr int SB = STEPS < SBMAX ? STEPS : SBMAX;
@@ -305,13 +320,42 @@ __device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, con
     uint64_t base = rb + (uint64_t)wave * RU;
     if (base >= re) return;
     // 32-bit addressing inside the phase: everything is relative to the phase's first (aligned) entry
-    uint32_t kb = __builtin_amdgcn_readfirstlane(off[rb]) & ~3u;
+    const uint32_t e0 = __builtin_amdgcn_readfirstlane(off[rb]);
+    uint32_t kb = e0 & ~3u;
     kb = kb < (uint32_t)last_chunk ? kb : (uint32_t)last_chunk;
     const uint32_t last_rel = (uint32_t)last_chunk - kb;
     ColStream cs = cols;  // ... from the phase's first chunk (kb is a multiple of 4: kb / 4 chunks)
     cs.colp = reinterpret_cast<const char *>(cols.colp) + (size_t)kb * (CF == kCol12 ? 1u : CF == kCol16 ? 2u : 4u);
     if constexpr (CF == kCol12) cs.hdrp = cols.hdrp + (kb >> 2);
     const T *valp = val + kb;
+    if constexpr (REG) {
+        Unit<T, SB * CH> A, B;
+        regular_offsets(A, e0, L, rb, base, re, lane);
+        regular_offsets(B, e0, L, rb, base + STRIDE, re, lane);
+        // the loop of the loading body below without the unit N: the offsets of the unit after next are computed where that body
+        // copies them.  (Three units in rotation, two of them in flight -- the addresses wait for no load, so it is cheap --
+        // measured no better: DESIGN.md Appendix A.)
+        issue_unit<T, LANES, CH, SB, CF>(A, cs, valp, kb, nnz_lim, last_rel, lane);
+        for (;;) {
+            if (base + STRIDE >= re) {
+                consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(A, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+                break;
+            }
+            issue_unit<T, LANES, CH, SB, CF>(B, cs, valp, kb, nnz_lim, last_rel, lane);
+            consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(A, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+            regular_offsets(A, e0, L, rb, base + 2 * STRIDE, re, lane);
+            base += STRIDE;
+            if (base + STRIDE >= re) {
+                consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(B, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+                break;
+            }
+            issue_unit<T, LANES, CH, SB, CF>(A, cs, valp, kb, nnz_lim, last_rel, lane);
+            consume_unit<T, LANES, CH, SB, GM, CF, RING, DOT>(B, base, re, cs, valp, x, ring, y, kb, nnz_lim, last_rel, lane, dacc);
+            regular_offsets(B, e0, L, rb, base + 2 * STRIDE, re, lane);
+            base += STRIDE;
+        }
+        return;
+    }
     Unit<T, SB * CH> A, B, N;  // N: only its offsets are used (the unit after next)
     load_offsets(A, off, base, re, lane);
     load_offsets(B, off, base + STRIDE, re, lane);
@@ -346,12 +390,16 @@ __device__ const col12::Table k_col12_table = col12::make_table();
 // kCol12: the compact form `c12` (5.5 bytes; LDS then holds the ring and, behind it, the 2 KiB triple table); phases with
 // global gathers need whole columns and keep reading `col`
 // DOT: y holds lhs (read only) and dot_partials[blockIdx.x] = this block's share of lhs . (A x); nothing else is stored
-template <typename T, int LANES, int CH, int CF, int RING, bool DOT = false>
+// REGK: the kernel for plans whose phases ALL gather from the ring and of which some are regular -- reg_len[p] (RingPlan::reg_len)
+// sends phase p to the body that computes its row offsets (L != 0) or to the one that loads them.  A kernel of its own and not
+// a fourth body beside the other three: the bodies' registers add up (one body of the f32 headline kernel takes 76-82 VGPRs,
+// the three of the other form all 128, a fourth spilled 92 bytes per lane), and these two take 97.
+template <typename T, int LANES, int CH, int CF, int RING, bool DOT = false, bool REGK = false>
 __global__ void __launch_bounds__((Ring2Cfg<T, RING>::kThreads), (Ring2Cfg<T, RING>::kWavesPerSimd))
 k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const uint16_t *__restrict__ col16, RingCol12 c12,
              const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, uint32_t nnz_lim, uint64_t last_chunk,
              const uint32_t *__restrict__ phase_ptr, const RingPhase *__restrict__ phases, uint32_t bands,
-             T *__restrict__ dot_partials, uint32_t lb0, uint32_t lb_n) {
+             T *__restrict__ dot_partials, uint32_t lb0, uint32_t lb_n, const uint32_t *__restrict__ reg_len) {
     T dacc_v = T(0);
     T *dacc = DOT ? &dacc_v : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char ring_raw[];  // RING * sizeof(T) (kCol12: + the triple table), dynamic
@@ -395,7 +443,16 @@ k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
         }
         // gather mode of the phase: 1 = LDS ring, 0 = L1/L2-cached global gathers, 2 = L1-bypassing (nt) global
         // gathers for phases whose columns have no locality to keep in the 32 KiB L1
-        if (ph.use_ring == 1)
+        if constexpr (REGK) {
+            static_assert(CF != kColU32, "regular phases stream one of the narrow column forms");
+            const uint32_t L = reg_len[p];  // wave-uniform
+            if (L != 0)
+                phase_rows<T, LANES, CH, 1, CF, RING, DOT, true>(off, ring_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim,
+                                                                 last_chunk, wave, lane, dacc, L);
+            else
+                phase_rows<T, LANES, CH, 1, CF, RING, DOT>(off, ring_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk,
+                                                           wave, lane, dacc);
+        } else if (ph.use_ring == 1)
             phase_rows<T, LANES, CH, 1, CF, RING, DOT>(off, ring_cols, val, x, ring, y, ph.row_begin, ph.row_end, nnz_lim, last_chunk, wave,
                                                        lane, dacc);
         else if (ph.use_ring == 2)
@@ -462,6 +519,40 @@ int launch_narrow_columns(const uint32_t *col, size_t nnz, uint16_t *col16, size
     uint64_t blocks = (n_out + kBlock - 1) / kBlock;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(k_narrow_columns, dim3((unsigned)blocks), dim3(kBlock), 0, s, col, (uint64_t)nnz, (uint64_t)n_out, col16);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
+// ---- which ring phases are regular (RingPlan::reg_len), once per plan ----
+// One workgroup per phase at a time: L = the first row's length, and every offset of rows [row_begin, row_end] is compared with
+// off[row_begin] + (r - row_begin) * L (in 64 bits: a product that wraps must not pass).  Each offset is read once, except those
+// two phases share.
+__global__ void __launch_bounds__(kBlock)
+k_ring_regular(const uint32_t *__restrict__ off, const RingPhase *__restrict__ phases, uint32_t n_phases, uint32_t *__restrict__ reg_len) {
+    __shared__ uint32_t s_bad;
+    for (uint32_t p = blockIdx.x; p < n_phases; p += gridDim.x) {
+        const uint32_t rb = phases[p].row_begin, re = phases[p].row_end;
+        const bool ring = phases[p].use_ring == 1u && re > rb;
+        if (threadIdx.x == 0) s_bad = 0u;
+        __syncthreads();
+        uint32_t L = 0;
+        if (ring) {  // (workgroup-uniform)
+            const uint32_t e0 = off[rb];
+            L = off[rb + 1] - e0;
+            bool bad = false;
+            for (uint64_t r = (uint64_t)rb + threadIdx.x; r <= re; r += kBlock) bad |= (uint64_t)off[r] != (uint64_t)e0 + (r - rb) * (uint64_t)L;
+            if (bad) s_bad = 1u;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) reg_len[p] = s_bad ? 0u : L;
+        __syncthreads();  // (s_bad is read before the next phase clears it)
+    }
+}
+
+int launch_ring_regular(const uint32_t *off, const RingPhase *phases, size_t n_phases, uint32_t *reg_len, hipStream_t s) {
+    if (n_phases == 0) return SMH_OK;
+    hipLaunchKernelGGL(k_ring_regular, dim3((unsigned)(n_phases < 8192 ? n_phases : 8192)), dim3(kBlock), 0, s, off, phases, (uint32_t)n_phases,
+                       reg_len);
     SMH_HIP(hipGetLastError());
     return SMH_OK;
 }
@@ -558,7 +649,7 @@ template <typename T, int RING>
 static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12, const T *val,
                           const T *x, T *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                           const uint32_t *phase_ptr, const RingPhase *phases, uint32_t bands, T *dot_partials, hipStream_t s,
-                          unsigned block_begin, unsigned block_end) {
+                          unsigned block_begin, unsigned block_end, const uint32_t *reg_len) {
     if (bands == 4u && !col16) return fail(SMH_ERR_INVALID, "banded ring plan without the 16-bit slot array");
     constexpr bool kHasCol12 = std::is_same<T, float>::value && RING == (int)col12::kSlots;  // the compact form's only instantiation
     if (c12.lo8 && (!kHasCol12 || bands != 1u || !c12.hdr || !c12.escapes))
@@ -579,7 +670,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
         dim3 grid(((lb1 - lb0) + 7u) & ~7u), block(Ring2Cfg<T, RING>::kThreads);
         constexpr size_t ring_bytes = (size_t)RING * sizeof(T);
         // dynamic LDS above 64 KiB must be allowed per kernel (idempotent, cheap)
-#define SMH_R2_LAUNCH2(L, C, N, D)                                                                                       \
+#define SMH_R2_LAUNCH2(L, C, N, D, R)                                                                                    \
     do {                                                                                                                 \
         constexpr size_t lds_bytes = ring_bytes + ((N) == kCol12 ? sizeof(col12::Table) : 0);                            \
         /* once per (instantiation, DEVICE): function attributes are per device, and smh_par_* places blocks on       \
@@ -588,24 +679,29 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
         static std::atomic<uint64_t> attr_mask{0};                                                                       \
         const uint64_t dev_bit = 1ull << (unsigned)(current_device() & 63);                                              \
         if (!(attr_mask.load(std::memory_order_acquire) & dev_bit)) {                                                    \
-            SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_ring2<T, L, C, N, RING, D>),               \
+            SMH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_ring2<T, L, C, N, RING, D, R>),            \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                    \
             attr_mask.fetch_or(dev_bit, std::memory_order_release);                                                      \
         }                                                                                                                \
-        hipLaunchKernelGGL((k_spmv_ring2<T, L, C, N, RING, D>), grid, block, lds_bytes, s, off, col, col16, c12, val, x, y, \
+        hipLaunchKernelGGL((k_spmv_ring2<T, L, C, N, RING, D, R>), grid, block, lds_bytes, s, off, col, col16, c12, val, x, y, \
                            (uint32_t)nnz_lim, last_chunk, phase_ptr, phases, bands, dot_partials, (uint32_t)lb0,         \
-                           (uint32_t)(lb1 - lb0));                                                                       \
+                           (uint32_t)(lb1 - lb0), reg_len);                                                              \
     } while (0)
-#define SMH_R2_LAUNCH1(L, C, N)                                                            \
-    do {                                                                                   \
-        if (dot_partials) SMH_R2_LAUNCH2(L, C, N, true); else SMH_R2_LAUNCH2(L, C, N, false); \
+#define SMH_R2_LAUNCH1(L, C, N, R)                                                               \
+    do {                                                                                         \
+        if (dot_partials) SMH_R2_LAUNCH2(L, C, N, true, R); else SMH_R2_LAUNCH2(L, C, N, false, R); \
+    } while (0)
+    /* the narrow column forms: with the table of regular phases, the kernel that reads it */
+#define SMH_R2_LAUNCH0(L, C, N)                                                                 \
+    do {                                                                                        \
+        if (reg_len) SMH_R2_LAUNCH1(L, C, N, true); else SMH_R2_LAUNCH1(L, C, N, false);         \
     } while (0)
 #define SMH_R2_LAUNCH(L, C)                                                   \
     do {                                                                      \
         if (c12.lo8) {                                                        \
-            if constexpr (kHasCol12) SMH_R2_LAUNCH1(L, C, kCol12);            \
-        } else if (col16) SMH_R2_LAUNCH1(L, C, kCol16);                       \
-        else SMH_R2_LAUNCH1(L, C, kColU32);                                   \
+            if constexpr (kHasCol12) SMH_R2_LAUNCH0(L, C, kCol12);            \
+        } else if (col16) SMH_R2_LAUNCH0(L, C, kCol16);                       \
+        else SMH_R2_LAUNCH1(L, C, kColU32, false);                            \
     } while (0)
         switch (lanes * 16 + chunks) {
             case 1 * 16 + 1: SMH_R2_LAUNCH(1, 1); break;
@@ -622,6 +718,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
                 return fail(SMH_ERR_INVALID, "ring kernel: unsupported (lanes per row, chunks per lane) = (%d, %d)", lanes, chunks);
         }
 #undef SMH_R2_LAUNCH
+#undef SMH_R2_LAUNCH0
 #undef SMH_R2_LAUNCH1
 #undef SMH_R2_LAUNCH2
         SMH_HIP(hipGetLastError());
@@ -639,25 +736,28 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
 
 // ring_entries: what the phase plan was built for (kRingEntries; kRingEntriesWide for f32 matrices that need it).
 // dot_partials != NULL (n_blocks + 1 values): the DOT form, `y` = lhs (see launch_ring2_t).
+// reg_len (NULL: none; only for a plan whose phases ALL gather from the ring, use_ring == 1): one u32 per phase, the row length of
+// a phase whose rows are all equally long, else 0 (k_ring_regular) -- the REGK kernel then runs, in which such a phase computes its
+// row offsets instead of loading them; same chunks, same lanes, same order of FMAs.  The u32 columns have no such kernel.
 int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12,
                       const void *val, const void *x, void *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
                       const uint32_t *phase_ptr, const RingPhase *phases, unsigned ring_entries, unsigned bands,
-                      hipStream_t s, void *dot_partials, unsigned block_begin, unsigned block_end) {
+                      hipStream_t s, void *dot_partials, unsigned block_begin, unsigned block_end, const uint32_t *reg_len) {
     if (n_rows == 0) return SMH_OK;
     if (bands != 1u && bands != 4u) return fail(SMH_ERR_INVALID, "ring kernel: %u bands", bands);
     if (dtype == SMH_F64) {
         if (ring_entries != (unsigned)kRingEntries) return fail(SMH_ERR_INVALID, "f64 ring kernel: ring of %u columns", ring_entries);
         return launch_ring2_t<double, kRingEntries>(lanes, chunks, off, col, col16, c12, (const double *)val, (const double *)x,
                                                     (double *)y, n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands,
-                                                    (double *)dot_partials, s, block_begin, block_end);
+                                                    (double *)dot_partials, s, block_begin, block_end, reg_len);
     }
     if (ring_entries == (unsigned)kRingEntriesWide)
         return launch_ring2_t<float, kRingEntriesWide>(lanes, chunks, off, col, col16, c12, (const float *)val, (const float *)x,
                                                        (float *)y, n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands,
-                                                       (float *)dot_partials, s, block_begin, block_end);
+                                                       (float *)dot_partials, s, block_begin, block_end, reg_len);
     if (ring_entries != (unsigned)kRingEntries) return fail(SMH_ERR_INVALID, "ring kernel: ring of %u columns", ring_entries);
     return launch_ring2_t<float, kRingEntries>(lanes, chunks, off, col, col16, c12, (const float *)val, (const float *)x, (float *)y,
-                                               n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands, (float *)dot_partials, s, block_begin, block_end);
+                                               n_rows, nnz, padded, n_blocks, phase_ptr, phases, bands, (float *)dot_partials, s, block_begin, block_end, reg_len);
 }
 
 }  // namespace smh

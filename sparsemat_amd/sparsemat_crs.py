@@ -665,6 +665,17 @@ class SparseMatCRS:
                                       ph.ctypes.data if nph.value else None))
         return nb.value, frac.value, bool(act.value), ptr, ph
 
+    def ring_regular(self):
+        """One u32 per phase of ``ring_plan()``: the row length L of a ring phase (use_ring == 1) whose rows are all L > 0 entries
+        long, else 0.  Where every phase gathers from the ring and the ring phases stream 16-bit or 12-bit columns, the ring
+        kernel computes such a phase's row offsets instead of loading them (SMH_RING_REGULAR=0: never); results do not change."""
+        nph = C.c_size_t()
+        check(lib().smh_crs_ring_plan(self._h, None, C.byref(nph), None, None, None, None))
+        out = np.zeros(nph.value, dtype=np.uint32)
+        if nph.value:
+            check(lib().smh_crs_ring_regular(self._h, out.ctypes.data))
+        return out
+
     def max_row_len(self):
         out = C.c_uint32()
         check(lib().smh_crs_max_row_len(self._h, C.byref(out)))
