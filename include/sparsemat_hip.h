@@ -538,7 +538,8 @@ int smh_crs_spmv_dev(smh_crs *m, const void *x_dev, size_t x_len, void *y_dev, i
  * index >= rhs_len, is SMH_ERR_INDEX_RANGE (the reference panics in densevec.rs:41; rows without
  * entries never index lhs, so trailing empty rows may lie beyond lhs_len, as in the reference).
  * Computed as dot(lhs, A rhs): the dot rides the SpMV's epilogue where the kernel has one, then a
- * two-stage deterministic reduction (tolerance-level parity, like dot). */
+ * two-stage deterministic reduction (tolerance-level parity, like dot).  Rows without entries are
+ * no terms of that dot either: NaN or Inf in lhs there does not reach the result. */
 int smh_crs_inner_prod(smh_crs *m, const void *lhs_host, size_t lhs_len, const void *rhs_host,
                        size_t rhs_len, int variant, double *out);
 /* merge-path tile table (integer structure, checked bit-exact in tests): tile t starts at

@@ -130,9 +130,14 @@ __device__ __forceinline__ T block_reduce_sum(T v, T *s_w) {
 }
 
 // stage 1: partials[b] = sum over this block's strided share of x[i]*y[i]
-template <typename T, bool VEC>
+// ROWS (SparseMatrix::inner_prod through a kernel without a dot form, y = A rhs): element i is a term only where row i of the matrix
+// holds entries, rows_off[i + 1] != rows_off[i] -- the reference reads lhs[i] inside the entry loop, so what lhs holds on a row
+// without entries never reaches the sum.  Same threads, same order; with finite data the same bits (acc is never -0, the term left
+// out is +-0).
+template <typename T, bool VEC, bool ROWS = false>
 __global__ void __launch_bounds__(kBlock)
-k_dot_stage1(const T *__restrict__ x, const T *__restrict__ y, uint64_t n, T *__restrict__ partials) {
+k_dot_stage1(const T *__restrict__ x, const T *__restrict__ y, uint64_t n, T *__restrict__ partials,
+             const uint32_t *__restrict__ rows_off = nullptr) {
     __shared__ T s_w[kBlock / kWave];
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
@@ -147,11 +152,14 @@ k_dot_stage1(const T *__restrict__ x, const T *__restrict__ y, uint64_t n, T *__
             const V xx = __builtin_nontemporal_load(xv + i);
             const V yy = xv == yv ? xx : __builtin_nontemporal_load(yv + i);  // (norm_squared: one read)
 #pragma unroll
-            for (int e = 0; e < N; ++e) acc += xx[e] * yy[e];
+            for (int e = 0; e < N; ++e)
+                if (!ROWS || rows_off[i * N + e + 1] != rows_off[i * N + e]) acc += xx[e] * yy[e];
         }
-        for (uint64_t i = nv * N + tid; i < n; i += nthreads) acc += x[i] * y[i];
+        for (uint64_t i = nv * N + tid; i < n; i += nthreads)
+            if (!ROWS || rows_off[i + 1] != rows_off[i]) acc += x[i] * y[i];
     } else {
-        for (uint64_t i = tid; i < n; i += nthreads) acc += x[i] * y[i];
+        for (uint64_t i = tid; i < n; i += nthreads)
+            if (!ROWS || rows_off[i + 1] != rows_off[i]) acc += x[i] * y[i];
     }
     const T r = block_reduce_sum<T>(acc, s_w);
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
@@ -176,12 +184,17 @@ unsigned reduce_blocks(size_t n) {
 }
 
 template <typename T>
-static int launch_dot_t(const T *x, const T *y, size_t n, T *partials, T *result, hipStream_t s) {
+static int launch_dot_t(const T *x, const T *y, size_t n, T *partials, T *result, hipStream_t s, const uint32_t *rows_off) {
     const unsigned blocks = reduce_blocks(n);
-    if (aligned16(x) && aligned16(y))
-        hipLaunchKernelGGL((k_dot_stage1<T, true>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials);
+    const bool vec = aligned16(x) && aligned16(y);
+    if (rows_off && vec)
+        hipLaunchKernelGGL((k_dot_stage1<T, true, true>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials, rows_off);
+    else if (rows_off)
+        hipLaunchKernelGGL((k_dot_stage1<T, false, true>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials, rows_off);
+    else if (vec)
+        hipLaunchKernelGGL((k_dot_stage1<T, true>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials, (const uint32_t *)nullptr);
     else
-        hipLaunchKernelGGL((k_dot_stage1<T, false>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials);
+        hipLaunchKernelGGL((k_dot_stage1<T, false>), dim3(blocks), dim3(kBlock), 0, s, x, y, (uint64_t)n, partials, (const uint32_t *)nullptr);
     SMH_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_reduce_stage2<T>, dim3(1), dim3(kBlock), 0, s, partials, blocks, result);
     SMH_HIP(hipGetLastError());
@@ -219,10 +232,11 @@ int launch_fold2(int dtype, const void *in, size_t count, void *partials, void *
     return SMH_OK;
 }
 
-int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials, void *result_dev, hipStream_t s) {
+// rows_off (optional; n + 1 row offsets of a CRS matrix): only the elements whose row holds entries are terms (k_dot_stage1, ROWS)
+int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials, void *result_dev, hipStream_t s, const uint32_t *rows_off) {
     if (dtype == SMH_F64)
-        return launch_dot_t<double>((const double *)x, (const double *)y, n, (double *)partials, (double *)result_dev, s);
-    return launch_dot_t<float>((const float *)x, (const float *)y, n, (float *)partials, (float *)result_dev, s);
+        return launch_dot_t<double>((const double *)x, (const double *)y, n, (double *)partials, (double *)result_dev, s, rows_off);
+    return launch_dot_t<float>((const float *)x, (const float *)y, n, (float *)partials, (float *)result_dev, s, rows_off);
 }
 
 // ---- CRS structure statistics / validation ---------------------------------------------------

@@ -1492,9 +1492,15 @@ int smh_vec_dot(const smh_vec *x, const smh_vec *y, double *out) {
     return SMH_OK;
 }
 
-// lhs^T (A rhs) on device vectors: y = A rhs with the matrix's own kernel into the handle's y staging, then the
-// two-stage dot with lhs.  (sparsematrix.rs:161-171 sums lhs_i * a_ij * rhs_j over all entries in storage order;
-// a parallel reduction regroups that sum, so parity is tolerance-level, like dot.)
+// lhs^T (A rhs) on device vectors, by one of three routes (spmv_inner_prod, spmv_dispatch.hip):
+//   K1r   the ring kernel's DOT form: the lane that would store a row's sum adds fma(lhs[row], sum, .) to its own accumulator, a
+//         workgroup folds lanes and waves, one partial per workgroup and one for an unpadded array's last <= 3 entries, launch_fold2
+//   K1s   the CSR-stream kernels' dot epilogue with y == NULL: round(lhs[row] * sum) per thread, one partial per tile, launch_fold2
+//   else  y = A rhs by the matrix's own kernel into the handle's y staging, then launch_dot(lhs, y) over the rows that hold entries
+// sparsematrix.rs:161-171 sums lhs_i * a_ij * rhs_j over all entries in storage order; each route regroups that sum in a fixed
+// order of its own, so against the reference parity is tolerance-level, like dot -- and against the CPU model of its order
+// (tests/inner_prod_model.py) each route is bit for bit (tests/test_inner_prod_bits_gpu.py).  A row without entries is no term in
+// any of them, as in the reference, whatever lhs holds there.
 static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const void *d_rhs, size_t rhs_len, int variant,
                           double *out) {
     if (!out) return fail(SMH_ERR_INVALID, "out is NULL");

@@ -551,8 +551,9 @@ int spmv_enqueue_rows_short(::smh_crs *m, const void *x, size_t x_len, void *y, 
 // BLAS-1 (a_dev: scalar read from device memory when non-null, else `a`)
 enum class Ew { Add, Sub, Scale, Axpy, Xpby, RSubInto };
 int launch_ew(int dtype, Ew op, void *x, const void *y, size_t n, double a, const void *a_dev, hipStream_t s);
+// rows_off (n + 1 CRS row offsets): element i is a term only where rows_off[i + 1] != rows_off[i] (SparseMatrix::inner_prod)
 int launch_dot(int dtype, const void *x, const void *y, size_t n, void *partials, void *result_dev,
-               hipStream_t s);
+               hipStream_t s, const uint32_t *rows_off = nullptr);
 int launch_fold2(int dtype, const void *in, size_t count, void *partials, void *result_dev, hipStream_t s);  // *result = sum(in)
 int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
 // Sparse triangular solves (trisolve.hip).  ensure_tri_schedule: the lazy level schedule m->tri[uplo] of a square handle whose

@@ -381,6 +381,8 @@ int spmv_enqueue_rows_short(smh_crs *m, const void *x, size_t x_len, void *y, in
 // ---- lhs^T (A rhs) (smh_crs_inner_prod*) -------------------------------------------------------------------------------------------
 // The product by the matrix's own kernel on the handle's stream, folded with lhs (n_rows entries) into *res: inside the kernel where
 // it has a dot form, else y = A rhs into the handle's y staging and the two-stage dot.  scratch: kReducePartials partials.
+// In all three routes a row without entries is no term of the sum (the reference reads lhs[i] inside the entry loop), whatever lhs
+// holds there; the summation order of each route is a CPU model's bit for bit (tests/inner_prod_model.py).
 int spmv_inner_prod(smh_crs *m, const void *d_lhs, const void *d_rhs, size_t rhs_len, int variant, void *scratch, void *res) {
     const size_t vs = dtype_size(m->dtype);
     const size_t n_dot = spmv_fused_dot_partials(m, rhs_len, variant, true);
@@ -401,7 +403,7 @@ int spmv_inner_prod(smh_crs *m, const void *d_lhs, const void *d_rhs, size_t rhs
     } else {
         SMH_TRY(m->stage_y.ensure_cap(m->n_rows * vs));
         SMH_TRY(spmv_enqueue(m, d_rhs, rhs_len, m->stage_y.d.get(), variant, m->stream));
-        SMH_TRY(launch_dot(m->dtype, d_lhs, m->stage_y.d.get(), m->n_rows, scratch, res, m->stream));
+        SMH_TRY(launch_dot(m->dtype, d_lhs, m->stage_y.d.get(), m->n_rows, scratch, res, m->stream, m->d_off));  // (rows with entries only)
     }
     return SMH_OK;
 }

@@ -231,7 +231,10 @@ __device__ __forceinline__ void issue_unit(Unit<T, SB * CH> &u, const ColStream 
 }
 
 // DOT (SparseMatrix::inner_prod, sparsematrix.rs:161-171): `y` then holds lhs, nothing is stored, and every lane adds
-// lhs[row] * (A x)[row] of the rows it would have stored to its *dacc
+// lhs[row] * (A x)[row] of the rows it would have stored to its *dacc -- of the rows that hold entries: the reference reads lhs[i]
+// inside the entry loop, so what lhs holds on a row without entries (NaN, Inf) never reaches the sum.  Lane L < RU holds the
+// offsets of row base + L, the row whose sum it keeps, in u.o0 / u.o1 (load_offsets, regular_offsets): no load is added.  With
+// finite data nothing changes: dacc starts at +0 and never becomes -0, and lhs * (+0) = +-0 added to it leaves its bits.
 template <typename T, int LANES, int CH, int SB, int GM, int CF, int RING, bool DOT = false>
 __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t base, uint64_t row_end,
                                              const ColStream &cs, const T *__restrict__ valp,
@@ -298,7 +301,7 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
     }
     const uint64_t row = base + lane;
     if constexpr (DOT) {
-        if (lane < (uint32_t)(SB * RPS) && row < row_end) *dacc = r2_fma(y[row], out, *dacc);
+        if (lane < (uint32_t)(SB * RPS) && row < row_end && u.o1 != u.o0) *dacc = r2_fma(y[row], out, *dacc);
     } else {
         if (lane < (uint32_t)(SB * RPS) && row < row_end) y[row] = out;
     }

@@ -466,7 +466,10 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
 #pragma unroll
         for (int rr = 0; rr < RPT; ++rr) {
             const uint64_t r = r0 + (uint64_t)rr * kBlock + tid;
-            if (r < r1) d += dl[rr] * sum[rr];
+            // y == NULL (inner_prod): a row without entries adds nothing -- the reference reads lhs[i] inside the entry loop, so a NaN
+            // or Inf there never reaches the sum.  Finite data keep their bits (d is never -0, and +-0 added to it changes nothing);
+            // with y (the solvers' p.Ap) every row of the tile is a term as before
+            if (r < r1 && (y || o1[rr] != o0[rr])) d += dl[rr] * sum[rr];
         }
         d = wave_sum_to_lane63(d);  // (lanes by the DPP scan network, then the wavefronts in index order; K1s XD adds in the same order)
         if ((tid & (kWave - 1)) == kWave - 1) s_red[tid / kWave] = d;

@@ -250,7 +250,7 @@ k_spmv_stream_xd(const T *__restrict__ val, const T *__restrict__ x, T *__restri
     if constexpr (DOT) {  // fixed order: lanes (DPP scan network), waves (index order) -- bitwise reproducible, as K1s
         __shared__ T s_red[kBlock / kWave];
         T d = T(0);
-        if (r < n_rows) d += dl * acc;  // (as K1s: 0 + the product)
+        if (r < n_rows && (y || my_len)) d += dl * acc;  // (as K1s: 0 + the product; inner_prod, y == NULL: not of a row without entries)
         d = wave_sum_to_lane63(d);
         if (lane == kWave - 1) s_red[wave] = d;
         __syncthreads();
@@ -442,7 +442,7 @@ k_spmv_stream_xdp(const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows, u
         if (r < n_rows && (!DOT || y)) __builtin_nontemporal_store(acc, &y[r]);
         if constexpr (DOT) {  // fixed order: lanes (DPP scan network), waves (index order) -- bitwise reproducible, as K1s
             T d = T(0);
-            if (r < n_rows) d += R.dl * acc;
+            if (r < n_rows && (y || R.my_len)) d += R.dl * acc;  // (as above)
             d = wave_sum_to_lane63(d);
             if (lane == kWave - 1) s_red[par][wave] = d;
         }
