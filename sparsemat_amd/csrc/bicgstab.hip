@@ -18,7 +18,7 @@
 // Kernels: beside the two products a body is five sweeps -- partials of r^.v (2 n values); s and partials of s.s (3 n);
 // partials of t.s and t.t (2 n); x, r and partials of r.r and r^.r (7 n); p (4 n): 18 n values -- each followed (but the
 // last) by a one-workgroup kernel that folds the partials, takes the stage's decision and advances the scalars.  All scalars
-// live in device memory: a leading block in CgScalars' layout, which solve_in_batches (internal.hpp: CG's loop) polls once
+// live in device memory: a leading block in CgScalars' layout, which solve_in_batches (internal.hpp) polls once
 // per batch and whose `converged` word means STOPPED (a breakdown too), and a second block (rho, the dots, omega, the
 // breakdown code) that the host reads once after the loop.  Gate words: `active` (this body runs; dropped by the stage that
 // stops) gates every sweep after alpha; `xmode` tells the x / r sweep what is due (0 nothing, 1 x += p*alpha alone, 2 all).
@@ -26,7 +26,10 @@
 // Reductions: pcg.hip's tree everywhere -- a thread's strided run over 16-byte vectors and then its tail element, the
 // __shfl_down butterfly per wave, thread 0 over the four wave sums from the first one's, one workgroup over the partials the
 // same way -- deterministic, no float atomics.  One stream, one linear chain of launches.
+// Host side: the driver (bicgstab_t) is its allocations, its set-up launches, the body lambda and SolveRun::run (solver_host.hpp:
+// the stream of its own, the workspaces, the drain, r = b - A x); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
+#include "solver_host.hpp"
 #include "solver_tree.hpp"
 
 #include <cmath>
@@ -327,22 +330,18 @@ k_bi_beta(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rr, const 
     }
 }
 
-// b_in / x_io: n values each, in host or device memory (the copies are hipMemcpyDefault); x_io is written once, after the loop
+// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
 template <typename T>
 int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
                double *rr_out, int *breakdown_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
-    Stream own;  // the solve runs on a stream of its own
-    Scratch ws;
-    PinnedBuf h_sc;
-    int stopped = 0;
-    size_t iters = 0;
-    double rr = 0.0;
+    SolveRun run;  // (its `converged` means STOPPED here)
     int breakdown = 0;
     const unsigned grid = pcg_grid(n);
-    auto go = [&]() -> int {
-        SMH_TRY(own.create());
-        const hipStream_t s = own.get();
+    const int rc = run.run([&]() -> int {
+        SMH_TRY(run.own_stream());
+        const hipStream_t s = run.s;
+        Scratch &ws = run.ws;
         T *x = nullptr, *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *sv = nullptr, *t = nullptr, *part = nullptr;
         BiScalars<T> *sc = nullptr;
         BiMore<T> *mo = nullptr;
@@ -351,18 +350,12 @@ int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t 
         SMH_TRY(ws.alloc(&part, 2 * (size_t)kPcgBlocks));
         SMH_TRY(ws.alloc(&sc, 1));
         SMH_TRY(ws.alloc(&mo, 1));
-        SMH_TRY(h_sc.alloc(sizeof(BiScalars<T>) + sizeof(BiMore<T>), hipHostMallocDefault));
+        SMH_TRY(run.h_sc.alloc(sizeof(BiScalars<T>) + sizeof(BiMore<T>), hipHostMallocDefault));
         T *part_a = part, *part_b = part + kPcgBlocks;
-        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
-        if (n) {
-            SMH_HIP(hipMemcpyAsync(r, b_in, n * sizeof(T), hipMemcpyDefault, s));
-            SMH_HIP(hipMemcpyAsync(x, x_io, n * sizeof(T), hipMemcpyDefault, s));
-        }
-        // r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r  (before any capture: the handle's lazy workspaces exist from here on)
+        // r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r
         hipLaunchKernelGGL((k_bi_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max);
-        SMH_TRY(spmv_enqueue(m, x, n, v, variant, s));
+        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, r, x, v, s));
         if (n) {
-            SMH_TRY(launch_ew(dt, Ew::Sub, r, v, n, 0.0, nullptr, s));
             SMH_HIP(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
             SMH_HIP(hipMemcpyAsync(p, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
         }
@@ -385,55 +378,38 @@ int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t 
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(solve_in_batches(dt, s, iter_max, check_every, body, sc, h_sc.get(), &stopped, &iters, &rr));
-        BiMore<T> *h_mo = (BiMore<T> *)((char *)h_sc.get() + sizeof(BiScalars<T>));
+        SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        BiMore<T> *h_mo = (BiMore<T> *)((char *)run.h_sc.get() + sizeof(BiScalars<T>));
         SMH_HIP(hipMemcpyAsync(h_mo, mo, sizeof(BiMore<T>), hipMemcpyDeviceToHost, s));
         if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         breakdown = (int)h_mo->breakdown;
         return SMH_OK;
-    };
-    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
-    // the solve failed half way
-    const int rc = keep_error(go(), [&] {
-        if (own.get()) (void)hipStreamSynchronize(own.get());
-        (void)hipGetLastError();
-    });
-    if (rc != SMH_OK) return rc;
-    if (iters_out) *iters_out = iters;
-    if (rr_out) *rr_out = rr;
-    if (breakdown_out) *breakdown_out = breakdown;
+    }, iters_out, rr_out);
+    if (rc == SMH_OK && breakdown_out) *breakdown_out = breakdown;
     return rc;
 }
 
 int bicgstab(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
              double *rr_out, int *breakdown_out) {
-    if (check_every == 0) check_every = 8;
     if (m->dtype == SMH_F64)
         return bicgstab_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
     return bicgstab_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
 }
 
+constexpr size_t kBiCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
+
 }  // namespace
 
-// the statuses are decided here, before any launch
+// the statuses are decided here (check_solve_vec / check_solve_host, solver_host.hpp), before any launch
 extern "C" int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                       size_t *iters_out, double *rr_out, int *breakdown_out) {
-    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
-    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");                        // linearsolver.rs:30-32
-    if (m->n_rows != b->n || m->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");  // :33-36
+    SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery));
     return bicgstab(m, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
 }
 
 extern "C" int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                   int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
-    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
-    const size_t n = m->n_rows;
-    if (n != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
-    if (n && b_host == x_host_inout) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    return bicgstab(m, b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
+    return bicgstab(m, b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "crs_forms.hpp"
+#include "solver_host.hpp"
 
 namespace smh {
 
@@ -1605,22 +1606,19 @@ int smh_crs_spmv_vec(smh_crs *m, const smh_vec *x, smh_vec *y, int variant) {
 }
 
 // ---- ConjugateGradient ---------------------------------------------------------------------------------
+// The statuses are decided by check_solve_vec / check_solve_host (solver_host.hpp), before any launch.  check_every = 0 stands for
+// 4 bodies per poll here (8 in the preconditioned solvers and BiCGSTAB).
+constexpr size_t kCgCheckEvery = 4;
+
 int smh_cg_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
                      size_t check_every, size_t *iters_out, double *rr_out) {
-    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "dtype mismatch");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");           // :30-32
-    if (m->n_rows != b->n || m->n_rows != x->n)
-        return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");                            // :33-36
-    if (check_every == 0) check_every = 4;
+    SMH_TRY(check_solve_vec(m, b, x, "dtype mismatch", /*refuse_aliased*/ false, &check_every, kCgCheckEvery));
     return cg_solve(m, b, x, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 int smh_cg_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                  size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
-    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (m->n_rows != b_len || m->n_rows != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ false, /*refuse_aliased*/ false));
     smh_vec *b = nullptr, *x = nullptr;
     int rc = smh_vec_from_host((smh_dtype)m->dtype, b_len, b_host, &b);
     if (rc == SMH_OK) rc = smh_vec_from_host((smh_dtype)m->dtype, x_len, x_host_inout, &x);
@@ -1636,12 +1634,7 @@ int smh_cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, si
                       double *rr_out) {
     if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
     if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
-    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "multi-vector dtype differs from the matrix's");
-    if (b == x || b->d.get() == x->d.get()) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");           // :30-32
-    if (m->n_rows != b->n || m->n_rows != x->n || b->k != x->k)
-        return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");                            // :33-36
-    if (check_every == 0) check_every = 4;
+    SMH_TRY(check_solve_vec(m, b, x, "multi-vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kCgCheckEvery));
     return cg_solve_many(m, b, x, tol, iter_max, check_every, iters_out, rr_out);
 }
 
@@ -1649,9 +1642,7 @@ int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, v
                            size_t *iters_out, double *rr_out) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (m->n_rows != n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    SMH_TRY(check_solve_host(m, b_host, n, x_host_inout, n, /*null_vectors*/ true, /*refuse_aliased*/ false));
     smh_mvec *b = nullptr, *x = nullptr;
     int rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, b_host, &b);
     if (rc == SMH_OK) rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, x_host_inout, &x);

@@ -24,9 +24,11 @@
 // Element-wise updates round the product and the sum separately (bit-identical to the reference
 // for equal alpha/beta); the reductions are fixed trees (bitwise reproducible).
 //
-// The single-matrix driver (cg_solve, behind smh_cg_solve_vec) is at the end of the first half of this file; its loop over batches
-// of bodies -- the hipGraph, the polls -- is solve_in_batches (internal.hpp), which pcg.hip runs too.
+// The single-matrix driver (cg_solve, behind smh_cg_solve_vec) is at the end of the first half of this file: its allocations, its
+// set-up launches, the body lambda and SolveRun::run on the handle's stream (solver_host.hpp, which every device-resident solver
+// runs: the workspaces, the drain, and through solve_in_batches of internal.hpp the batches of bodies, the hipGraph, the polls).
 #include "internal.hpp"
+#include "solver_host.hpp"
 
 namespace smh {
 
@@ -349,13 +351,10 @@ void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t 
 template <typename T>
 static int cg_solve_t(smh_crs *m, const T *b, T *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out, double *rr_out) {
     const size_t n = m->n_rows;
-    hipStream_t s = m->stream;
-    Scratch ws;
-    PinnedBuf h_sc;
-    int converged = 0;
-    size_t iters = 0;
-    double rr = 0.0;
-    auto go = [&]() -> int {
+    SolveRun run(m->stream);
+    return run.run([&]() -> int {
+        const hipStream_t s = run.s;
+        Scratch &ws = run.ws;
         T *r = nullptr, *p = nullptr, *ap = nullptr, *partials = nullptr, *dot_partials = nullptr;
         CgScalars<T> *sc = nullptr, *sc2 = nullptr;  // (double-buffered within an iteration, see above)
         SMH_TRY(ws.alloc(&r, n));
@@ -367,7 +366,7 @@ static int cg_solve_t(smh_crs *m, const T *b, T *x, double tol, size_t iter_max,
         if (n_dot) SMH_TRY(ws.alloc(&dot_partials, n_dot));
         SMH_TRY(ws.alloc(&sc, 1));
         SMH_TRY(ws.alloc(&sc2, 1));
-        SMH_TRY(h_sc.alloc(sizeof(CgScalars<T>), hipHostMallocDefault));
+        SMH_TRY(run.h_sc.alloc(sizeof(CgScalars<T>), hipHostMallocDefault));
         // r = b - A x  (:38) ; p = r.clone() (:39) ; rr = r.r (:40)
         SMH_TRY(spmv_enqueue(m, x, n, r, variant, s));  // (before any capture: the handle's lazy workspaces exist from here on)
         SMH_TRY(launch_ew(m->dtype, Ew::RSubInto, r, b, n, 0.0, nullptr, s));
@@ -377,18 +376,8 @@ static int cg_solve_t(smh_crs *m, const T *b, T *x, double tol, size_t iter_max,
             SMH_TRY(spmv_enqueue(m, p, n, ap, variant, s, dot_partials));                                    // :43
             return cg_iter_tail_t<T>(sc, sc2, x, r, p, ap, n, partials, dot_partials, (uint32_t)n_dot, s);  // :45-59
         };
-        return solve_in_batches(m->dtype, s, iter_max, check_every, body, sc, h_sc.get(), &converged, &iters, &rr);
-    };
-    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
-    // the solve failed half way
-    const int rc = keep_error(go(), [&] {
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-    });
-    if (rc != SMH_OK) return rc;
-    if (iters_out) *iters_out = iters;
-    if (rr_out) *rr_out = rr;
-    return SMH_OK;
+        return run.loop(m->dtype, iter_max, check_every, body, sc);
+    }, iters_out, rr_out);
 }
 
 int cg_solve(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,

@@ -26,6 +26,7 @@
 // taken from `in` at the head of a body, so the host learns of the last column's stop with the first body AFTER it (a
 // no-op): folding every column's r.r in one workgroup for it would cost O(k) folds per body.
 #include "mvec_tree.hpp"
+#include "solver_host.hpp"
 
 namespace smh {
 
@@ -210,17 +211,14 @@ static int cg_solve_many_t(smh_crs *m, const smh_mvec *b, smh_mvec *x, double to
     const unsigned gx = (unsigned)(ngroups < 1024 ? ngroups : 1024);
     DevArray<T> r, p, ap, pap_part, rr_part;
     DevArray<CgScalars<T>> sc, sc2;
-    PinnedBuf h_sc;
+    SolveRun run(s);  // (the workspaces here are exact-size DevArrays, not run.ws; run.iters / run.rr are the summary block's [0]: unused)
     std::vector<CgScalars<T>> h_all;
     try {
         h_all.resize(ld + 1);
     } catch (...) {
         return fail(SMH_ERR_OOM, "host allocation failed");
     }
-    int converged = 0;
-    size_t iters = 0;
-    double rr = 0.0;
-    auto go = [&]() -> int {
+    const int rc = run.run([&]() -> int {
         const size_t elems = n * ld ? n * ld : 4;
         SMH_TRY(r.alloc(elems));
         SMH_TRY(p.alloc(elems));
@@ -229,7 +227,7 @@ static int cg_solve_many_t(smh_crs *m, const smh_mvec *b, smh_mvec *x, double to
         SMH_TRY(rr_part.alloc(ld * (size_t)nb));
         SMH_TRY(sc.alloc(ld + 1));
         SMH_TRY(sc2.alloc(ld + 1));
-        SMH_TRY(h_sc.alloc(sizeof(CgScalars<T>), hipHostMallocDefault));
+        SMH_TRY(run.h_sc.alloc(sizeof(CgScalars<T>), hipHostMallocDefault));
         T *xd = (T *)x->d.get();
         const T *bd = (const T *)b->d.get();
         // R = B - A X  (:38) ; P = R.clone() (:39) ; rr_c = r_c . r_c (:40).  K1m's own statuses are decided here, before any launch.
@@ -251,17 +249,12 @@ static int cg_solve_many_t(smh_crs *m, const smh_mvec *b, smh_mvec *x, double to
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(solve_in_batches(m->dtype, s, iter_max, check_every, body, sc.get(), h_sc.get(), &converged, &iters, &rr));
+        SMH_TRY(run.loop(m->dtype, iter_max, check_every, body, sc.get()));
         // the per-column scalars, once
         SMH_HIP(hipMemcpyAsync(h_all.data(), sc.get(), (ld + 1) * sizeof(CgScalars<T>), hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
-    };
-    // the stream is drained before the workspaces go back to the pool, also when the solve failed half way
-    const int rc = keep_error(go(), [&] {
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-    });
+    }, nullptr, nullptr);
     if (rc != SMH_OK) return rc;
     for (size_t c = 0; c < k; ++c) {
         iters_out[c] = (size_t)h_all[1 + c].iters;

@@ -12,13 +12,18 @@
 // (p, x, r, d in; p, x out): 10 n values per iteration beside the SpMV (the plain CG moves 8 n; the two reads of d are
 // what the preconditioner costs), p.Ap out of the SpMV epilogue when the kernel offers it.  All scalars (r.r, r.z, p.Ap,
 // alpha, beta, the stop flag, the iteration count) live in device memory as in cg.hip: the host replays a hipGraph of 8
-// bodies and polls one small block per batch (solve_in_batches, internal.hpp: CG's loop) -- no synchronisation inside an iteration.
+// bodies and polls one small block per batch (solve_in_batches, internal.hpp) -- no synchronisation inside an iteration.
 // Reductions: fixed grid, per-thread strided sums, wave butterfly, LDS across waves, one block folds the partials in
 // index order -- deterministic.
-// The second half of the file is the same recurrence preconditioned by symmetric Gauss-Seidel (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec):
-// z is a vector there, the result of two level-scheduled triangular solves (trisolve.hip); the scalars, k_pcg_alpha and the sums are these.
-// ILU(0)-PCG (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) is that half again with the solves on a factor handle (ilu.hip): TriPrecond.
+// The second half of the file is the same recurrence preconditioned by two level-scheduled triangular solves (trisolve.hip) on one
+// handle (TriPrecond), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
+// (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec) solves on the matrix itself, ILU(0) (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) on a
+// factor handle (ilu.hip).
+// Host side: both drivers (pcg_t, pcg_tri_t) are their allocations, their set-up launches, a body lambda and SolveRun::run
+// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe and the source of p.Ap are one
+// function each here (probe_diagonal, pap_source); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
+#include "solver_host.hpp"
 #include "solver_tree.hpp"
 
 #include <cmath>
@@ -211,19 +216,57 @@ k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__rest
     }
 }
 
+// ---- host side: what the Jacobi driver here and the triangular one below share ------------------------------------------------------
+// d[i] = get(i, i) of h, on s once h's own stream has finished, and the verdict: a zero or absent diagonal entry cannot be divided by
+// (name: whose refusal it is; d_bad: one word of scratch)
+template <typename T>
+int probe_diagonal(const smh_crs *h, size_t n, T *d, unsigned long long *d_bad, const char *name, hipStream_t s) {
+    SMH_HIP(hipStreamSynchronize(h->stream));  // (the handle is read on another stream than the one that wrote it)
+    unsigned long long bad = ~0ull;
+    SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
+    if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, h->d_off, h->d_col, (const T *)h->d_val, (uint64_t)n, d, d_bad);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    if (bad != ~0ull) return fail(SMH_ERR_INVALID, "%s: zero or absent diagonal entry in row %llu", name, bad);
+    return SMH_OK;
+}
+
+// Where p.Ap comes from after the product Ap = A p that was handed d_dot: out of the product's epilogue when the kernel offers it
+// (K1s: n_dot per-tile partials in d_dot; more than 1024 of them are folded by a full grid first), else a separate two-stage dot.
+// Enqueues what that takes and returns what k_pcg_alpha folds.  dot_scratch: 2 * kReducePartials + 8 values (the dot's partials,
+// its result, the first fold).
+template <typename T>
+struct PapSource {
+    const T *vals;
+    uint32_t count;
+};
+template <typename T>
+int pap_source(const T *p, const T *ap, size_t n, const T *d_dot, size_t n_dot, T *dot_scratch, hipStream_t s, PapSource<T> *out) {
+    if (d_dot && n_dot > (size_t)kReducePartials) {
+        const unsigned fb = reduce_blocks(n_dot);
+        T *fold_scratch = dot_scratch + kReducePartials + 8;
+        hipLaunchKernelGGL((k_pcg_sum_stage1<T>), dim3(fb), dim3(kBlock), 0, s, d_dot, (uint64_t)n_dot, fold_scratch);
+        *out = {fold_scratch, fb};
+    } else if (d_dot) {
+        *out = {d_dot, (uint32_t)n_dot};
+    } else {
+        if (n) SMH_TRY(launch_dot(sizeof(T) == 8 ? SMH_F64 : SMH_F32, p, ap, n, dot_scratch, dot_scratch + kReducePartials, s));
+        else SMH_HIP(hipMemsetAsync(dot_scratch + kReducePartials, 0, sizeof(T), s));
+        *out = {dot_scratch + kReducePartials, 1u};
+    }
+    return SMH_OK;
+}
+
 template <typename T>
 int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
-    Stream own;  // the solve runs on a stream of its own
-    Scratch ws;
-    PinnedBuf h_sc;
-    int converged = 0;
-    size_t iters = 0;
-    double rr = 0.0;
+    SolveRun run;
     const unsigned grid = pcg_grid(n);
-    auto go = [&]() -> int {
-        SMH_TRY(own.create());
-        const hipStream_t s = own.get();
+    return run.run([&]() -> int {
+        SMH_TRY(run.own_stream());
+        const hipStream_t s = run.s;
+        Scratch &ws = run.ws;
         T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_d = nullptr, *d_part = nullptr, *d_dot = nullptr;
         PcgScalars<T> *d_sc = nullptr;
         unsigned long long *d_bad = nullptr;
@@ -232,69 +275,35 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
         SMH_TRY(ws.alloc(&d_part, 2 * (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
         SMH_TRY(ws.alloc(&d_sc, 1));
         SMH_TRY(ws.alloc(&d_bad, 1));
-        SMH_TRY(h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
-        T *part_rr = d_part, *part_rz = d_part + kPcgBlocks, *dot_scratch = d_part + 2 * kPcgBlocks, *fold_scratch = dot_scratch + kReducePartials + 8;
-        // p.Ap: out of the SpMV epilogue when the kernel offers it (K1s), else a separate two-stage dot
+        SMH_TRY(run.h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
+        T *part_rr = d_part, *part_rz = d_part + kPcgBlocks, *dot_scratch = d_part + 2 * kPcgBlocks;
         const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
-        const uint32_t *off = m->d_off, *col = m->d_col;
-        const void *val = m->d_val;
-        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
-        // diag(A); a zero diagonal cannot be divided by
-        unsigned long long bad = ~0ull;
-        SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
-        if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, off, col, (const T *)val, (uint64_t)n, d_d, d_bad);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        if (n) {
-            SMH_HIP(hipMemcpyAsync(d_r, b_host, n * sizeof(T), hipMemcpyHostToDevice, s));
-            SMH_HIP(hipMemcpyAsync(d_x, x_host, n * sizeof(T), hipMemcpyHostToDevice, s));
-        }
-        SMH_HIP(hipStreamSynchronize(s));
-        if (bad != ~0ull) return fail(SMH_ERR_INVALID, "Jacobi preconditioner: zero or absent diagonal entry in row %llu", bad);
+        SMH_TRY(probe_diagonal(m, n, d_d, d_bad, "Jacobi preconditioner", s));
         // r = b - A x; p = r / d; rr, rz
         hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
-        SMH_TRY(spmv_enqueue(m, d_x, n, d_ap, variant, s));
-        if (n) SMH_TRY(launch_ew(dt, Ew::Sub, d_r, d_ap, n, 0.0, nullptr, s));
+        SMH_TRY(stage_residual(m, variant, b_host, x_host, n, d_r, d_x, d_ap, s));
         hipLaunchKernelGGL((k_pcg_update<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_d, (uint64_t)n, part_rr, part_rz);
         hipLaunchKernelGGL((k_pcg_beta<T, true>), dim3(1), dim3(kBlock), 0, s, d_sc, part_rr, part_rz, grid);
         hipLaunchKernelGGL((k_pcg_p<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_r, d_d, d_x, (uint64_t)n);
         SMH_HIP(hipGetLastError());
         // one loop body: SpMV (+ p.Ap), alpha, update of r + partials, stop test / beta, x and p
         auto body = [&]() -> int {
+            PapSource<T> pap;
             SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, variant, s, d_dot));
-            if (d_dot && n_dot > (size_t)kReducePartials) {
-                const unsigned fb = reduce_blocks(n_dot);
-                hipLaunchKernelGGL((k_pcg_sum_stage1<T>), dim3(fb), dim3(kBlock), 0, s, d_dot, (uint64_t)n_dot, fold_scratch);
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, fold_scratch, fb);
-            } else if (d_dot) {
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, d_dot, (uint32_t)n_dot);
-            } else {
-                if (n) SMH_TRY(launch_dot(dt, d_p, d_ap, n, dot_scratch, dot_scratch + kReducePartials, s));
-                else SMH_HIP(hipMemsetAsync(dot_scratch + kReducePartials, 0, sizeof(T), s));
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, dot_scratch + kReducePartials, 1u);
-            }
+            SMH_TRY(pap_source(d_p, d_ap, n, d_dot, n_dot, dot_scratch, s, &pap));
+            hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, pap.vals, pap.count);
             hipLaunchKernelGGL((k_pcg_update<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_d, (uint64_t)n, part_rr, part_rz);
             hipLaunchKernelGGL((k_pcg_beta<T, false>), dim3(1), dim3(kBlock), 0, s, d_sc, part_rr, part_rz, grid);
             hipLaunchKernelGGL((k_pcg_p<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_r, d_d, d_x, (uint64_t)n);
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(solve_in_batches(dt, s, iter_max, 8, body, d_sc, h_sc.get(), &converged, &iters, &rr));
+        SMH_TRY(run.loop(dt, iter_max, 8, body, d_sc));
         if (n) SMH_HIP(hipMemcpyAsync(x_host, d_x, n * sizeof(T), hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
-    };
-    // the stream is drained before the workspaces go back to the pool (which hands them straight to the next caller), also when
-    // the solve failed half way
-    const int rc = keep_error(go(), [&] {
-        if (own.get()) (void)hipStreamSynchronize(own.get());
-        (void)hipGetLastError();
-    });
-    if (rc != SMH_OK) return rc;
-    if (iters_out) *iters_out = iters;
-    if (rr_out) *rr_out = rr;
-    return rc;
+    }, iters_out, rr_out);
 }
 
 
@@ -421,22 +430,18 @@ int precond_prepare(const TriPrecond &pc) {
     return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
 }
 
-// b_in / x_io: n values each, in host or device memory (the copies are hipMemcpyDefault); x_io is written once, after the loop
+// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
 template <typename T>
 int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
               size_t *iters_out, double *rr_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
-    Stream own;  // the solve runs on a stream of its own
-    Scratch ws;
-    PinnedBuf h_sc;
-    int converged = 0;
-    size_t iters = 0;
-    double rr = 0.0;
+    SolveRun run;
     const unsigned grid = pcg_grid(n);
-    auto go = [&]() -> int {
+    return run.run([&]() -> int {
         SMH_TRY(precond_prepare(pc));
-        SMH_TRY(own.create());
-        const hipStream_t s = own.get();
+        SMH_TRY(run.own_stream());
+        const hipStream_t s = run.s;
+        Scratch &ws = run.ws;
         T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_z = nullptr, *d_w = nullptr, *d_part = nullptr, *d_dot = nullptr;
         PcgScalars<T> *d_sc = nullptr;
         unsigned long long *d_bad = nullptr;
@@ -445,29 +450,16 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
         SMH_TRY(ws.alloc(&d_part, (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
         SMH_TRY(ws.alloc(&d_sc, 1));
         SMH_TRY(ws.alloc(&d_bad, 1));
-        SMH_TRY(h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
-        T *part = d_part, *dot_scratch = d_part + kPcgBlocks, *fold_scratch = dot_scratch + kReducePartials + 8;
+        SMH_TRY(run.h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
+        T *part = d_part, *dot_scratch = d_part + kPcgBlocks;
         const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
-        SMH_HIP(hipStreamSynchronize(m->stream));  // (the matrix is read on another stream than the one that wrote it)
-        if (pc.f != m) SMH_HIP(hipStreamSynchronize(pc.f->stream));
-        // the diagonal's values are read once, here: a zero one cannot be divided by (d_w takes them and is overwritten later)
-        unsigned long long bad = ~0ull;
-        SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
-        if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, pc.f->d_off, pc.f->d_col, (const T *)pc.f->d_val, (uint64_t)n, d_w, d_bad);
-        SMH_HIP(hipGetLastError());
-        SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-        if (n) {
-            SMH_HIP(hipMemcpyAsync(d_r, b_in, n * sizeof(T), hipMemcpyDefault, s));
-            SMH_HIP(hipMemcpyAsync(d_x, x_io, n * sizeof(T), hipMemcpyDefault, s));
-        }
-        SMH_HIP(hipStreamSynchronize(s));
-        if (bad != ~0ull) return fail(SMH_ERR_INVALID, "%s: zero or absent diagonal entry in row %llu", pc.name, bad);
+        // the diagonal's values are read once, here (d_w takes them and is overwritten later)
+        SMH_TRY(probe_diagonal(pc.f, n, d_w, d_bad, pc.name, s));
         const uint32_t *active = &d_sc->active;
         // r = b - A x; z = M^-1 r; rr, rz; p = z
         hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
-        SMH_TRY(spmv_enqueue(m, d_x, n, d_ap, variant, s));
-        if (n) SMH_TRY(launch_ew(dt, Ew::Sub, d_r, d_ap, n, 0.0, nullptr, s));
+        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, d_r, d_x, d_ap, s));
         SMH_TRY(precond_apply_enqueue(pc, d_r, d_w, d_z, nullptr, s));
         hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_r, (uint64_t)n, part);
         hipLaunchKernelGGL((k_sgs_fold<T, 0>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
@@ -477,18 +469,10 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
         SMH_HIP(hipGetLastError());
         size_t spmv_nodes = 1;
         auto body = [&]() -> int {
+            PapSource<T> pap;
             SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, variant, s, d_dot));
-            if (d_dot && n_dot > (size_t)kReducePartials) {
-                const unsigned fb = reduce_blocks(n_dot);
-                hipLaunchKernelGGL((k_pcg_sum_stage1<T>), dim3(fb), dim3(kBlock), 0, s, d_dot, (uint64_t)n_dot, fold_scratch);
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, fold_scratch, fb);
-            } else if (d_dot) {
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, d_dot, (uint32_t)n_dot);
-            } else {
-                if (n) SMH_TRY(launch_dot(dt, d_p, d_ap, n, dot_scratch, dot_scratch + kReducePartials, s));
-                else SMH_HIP(hipMemsetAsync(dot_scratch + kReducePartials, 0, sizeof(T), s));
-                hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, dot_scratch + kReducePartials, 1u);
-            }
+            SMH_TRY(pap_source(d_p, d_ap, n, d_dot, n_dot, dot_scratch, s, &pap));
+            hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, pap.vals, pap.count);
             hipLaunchKernelGGL((k_sgs_update<T>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_p, d_x, (uint64_t)n, part);
             hipLaunchKernelGGL((k_sgs_fold<T, 1>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
             SMH_TRY(precond_apply_enqueue(pc, d_r, d_w, d_z, active, s));
@@ -503,31 +487,18 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
         const size_t budget = sgs_graph_nodes();
         size_t bodies = check_every;
         if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
-        SMH_TRY(solve_in_batches(dt, s, iter_max, bodies, body, d_sc, h_sc.get(), &converged, &iters, &rr, per_body <= budget));
+        SMH_TRY(run.loop(dt, iter_max, bodies, body, d_sc, per_body <= budget));
         if (n) SMH_HIP(hipMemcpyAsync(x_io, d_x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
-    };
-    const int rc = keep_error(go(), [&] {
-        if (own.get()) (void)hipStreamSynchronize(own.get());
-        (void)hipGetLastError();
-    });
-    if (rc != SMH_OK) return rc;
-    if (iters_out) *iters_out = iters;
-    if (rr_out) *rr_out = rr;
-    return rc;
+    }, iters_out, rr_out);
 }
 
 int pcg_tri(smh_crs *m, const TriPrecond &pc, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
             size_t *iters_out, double *rr_out) {
-    if (check_every == 0) check_every = 8;
     if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
     if (m->dtype == SMH_F64) return pcg_tri_t<double>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
     return pcg_tri_t<float>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
-}
-int pcg_sgs(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
-            double *rr_out) {
-    return pcg_tri(m, sgs_precond(m), b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 // z = M^-1 r by the handle's stream; r and z: n values each on the device, equal or disjoint
@@ -555,19 +526,20 @@ int precond_apply(const TriPrecond &pc, const smh_vec *r, smh_vec *z, const char
 
 }  // namespace
 
+// The entry points: the statuses are decided here (check_solve_vec / check_solve_host, solver_host.hpp), before any launch.
+// check_every = 0, and the host forms, stand for 8 bodies per poll.
+constexpr size_t kPcgCheckEvery = 8;
+constexpr const char *kVecDtype = "vector dtype differs from the matrix's";
+
 extern "C" int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                                     size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
-    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
-    const size_t n = smh_crs_n_rows(m);
-    if (n != smh_crs_n_cols(m)) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");                       // linearsolver.rs:30-32
-    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");          // :33-36
-    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
-    if (smh_crs_dtype(m) == SMH_F64)
-        return pcg_t<double>(m, (const double *)b_host, (double *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false));
+    const size_t n = m->n_rows;
+    if (m->dtype == SMH_F64) return pcg_t<double>(m, (const double *)b_host, (double *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
     return pcg_t<float>(m, (const float *)b_host, (float *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
 }
 
-// ---- the symmetric Gauss-Seidel preconditioner and its CG; the statuses are decided here, before any launch -------------------------
+// ---- the symmetric Gauss-Seidel preconditioner and its CG -----------------------------------------------------------------------------
 extern "C" int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z) {
     if (!m || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
     return precond_apply(sgs_precond(m), r, z, "sgs_apply");
@@ -575,22 +547,14 @@ extern "C" int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z) {
 
 extern "C" int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                      size_t *iters_out, double *rr_out) {
-    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
-    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");                        // linearsolver.rs:30-32
-    if (m->n_rows != b->n || m->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");  // :33-36
-    return pcg_sgs(m, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+    SMH_TRY(check_solve_vec(m, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery));
+    return pcg_tri(m, sgs_precond(m), b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 extern "C" int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                  int variant, size_t *iters_out, double *rr_out) {
-    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
-    const size_t n = m->n_rows;
-    if (n != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
-    return pcg_sgs(m, b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out);
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false));
+    return pcg_tri(m, sgs_precond(m), b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
 }
 
 // ---- ILU(0): the same recurrence and application with the solves on a factor handle (smh_crs_ilu0, ilu.hip); the product and its
@@ -600,32 +564,16 @@ extern "C" int smh_crs_ilu_apply_vec(smh_crs *f, const smh_vec *r, smh_vec *z) {
     return precond_apply(ilu_precond(f), r, z, "ilu_apply");
 }
 
-// what a and f must agree in, decided before any launch
-static int ilu_check_pair(const smh_crs *a, const smh_crs *f) {
-    if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "ILU preconditioner: the factor is not square");
-    if (f->n_rows != a->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "ILU preconditioner: the factor's dimension differs from the matrix's");
-    if (f->dtype != a->dtype) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor's dtype differs from the matrix's");
-    if (f->device != a->device) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor and the matrix live on different devices");
-    return SMH_OK;
-}
-
 extern "C" int smh_pcg_ilu_solve_vec(smh_crs *a, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                      size_t *iters_out, double *rr_out) {
-    if (!a || !f || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (b->dtype != a->dtype || x->dtype != a->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
-    if (b == x || (b->d && b->d == x->d)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    SMH_TRY(ilu_check_pair(a, f));
-    if (a->n_rows != b->n || a->n_rows != x->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    if (!f) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery, f));
     return pcg_tri(a, ilu_precond(f), b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 extern "C" int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                  int variant, size_t *iters_out, double *rr_out) {
-    if (!a || !f) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(ilu_check_pair(a, f));
-    const size_t n = a->n_rows;
-    if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (n && (!b_host || !x_host_inout)) return fail(SMH_ERR_INVALID, "NULL host vector");
-    return pcg_tri(a, ilu_precond(f), b_host, x_host_inout, n, tol, iter_max, variant, 0, iters_out, rr_out);
+    if (!f) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false, f));
+    return pcg_tri(a, ilu_precond(f), b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
 }

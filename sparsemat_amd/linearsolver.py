@@ -27,10 +27,8 @@ from .densevec import DenseVec
 from .multivec import MultiVec, pack_host
 
 
-class ConjugateGradient:
-    """``ConjugateGradient::default()`` == ``ConjugateGradient()`` (tol 1e-12, iter_max 10000,
-    linearsolver.rs:17-24).  The reference keeps both fields private; ``new(tol, iter_max)`` is the
-    documented addition (SURVEY 8b)."""
+class _DeviceSolver:
+    """What the device-resident solvers share: the settings, the results of the last solve, and the one call into the library."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
         self.tol = float(tol)
@@ -39,6 +37,30 @@ class ConjugateGradient:
         self.check_every = int(check_every)
         self.iterations = None  # loop bodies entered by the last solve
         self.r_norm_squared = None  # last r.r (as f64)
+
+    def _solve(self, vec_fn, host_fn, mat, b, x, handles=(), extra_out=()):
+        """Two ``DenseVec``s go to ``vec_fn`` (None: the solver has no such form), anything else to ``host_fn`` as an array-like b and
+        a contiguous numpy x of the matrix dtype, updated in place.  ``handles``: what the call takes after the matrix;
+        ``extra_out``: ctypes out-parameters after iters and rr.  Sets ``iterations`` and ``r_norm_squared``."""
+        iters, rr = C.c_size_t(), C.c_double()
+        out = [C.byref(iters), C.byref(rr)] + [C.byref(o) for o in extra_out]
+        var = _lib.VARIANTS[self.variant]
+        if vec_fn is not None and isinstance(b, DenseVec) and isinstance(x, DenseVec):
+            check(vec_fn(mat._h, *handles, b._h, x._h, self.tol, self.iter_max, var, self.check_every, *out))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
+                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
+            bb = np.ascontiguousarray(b, dtype=mat.dtype)
+            check(host_fn(mat._h, *handles, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None, x.size,
+                          self.tol, self.iter_max, var, *out))
+        self.iterations, self.r_norm_squared = iters.value, rr.value
+        return x
+
+
+class ConjugateGradient(_DeviceSolver):
+    """``ConjugateGradient::default()`` == ``ConjugateGradient()`` (tol 1e-12, iter_max 10000,
+    linearsolver.rs:17-24).  The reference keeps both fields private; ``new(tol, iter_max)`` is the
+    documented addition (SURVEY 8b)."""
 
     @classmethod
     def default(cls):
@@ -51,20 +73,7 @@ class ConjugateGradient:
     def solve(self, mat, b, x):
         """LinearSolver::solve(&self, mat, b, x): x is updated in place (linearsolver.rs:27-61).
         Raises SparseMatPanic("Matrix is not symmetric") / ("Matrix and vector size mismatch")."""
-        iters, rr = C.c_size_t(), C.c_double()
-        var = _lib.VARIANTS[self.variant]
-        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
-            check(lib().smh_cg_solve_vec(mat._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
-                                         C.byref(iters), C.byref(rr)))
-        else:
-            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
-                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
-            bb = np.ascontiguousarray(b, dtype=mat.dtype)
-            check(lib().smh_cg_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size,
-                                     x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var,
-                                     C.byref(iters), C.byref(rr)))
-        self.iterations, self.r_norm_squared = iters.value, rr.value
-        return x
+        return self._solve(lib().smh_cg_solve_vec, lib().smh_cg_solve, mat, b, x)
 
     def solve_many(self, mat, b, x):
         """``solve`` on k right-hand sides at once (``smh_cg_solve_many``): column c of x is ``solve(mat, b_c, x_c)`` with its
@@ -92,61 +101,31 @@ class ConjugateGradient:
         return x
 
 
-class JacobiConjugateGradient:
+class JacobiConjugateGradient(_DeviceSolver):
     """Jacobi-preconditioned CG -- an EXTENSION (the reference has no preconditioner): the
     recurrence of ``ConjugateGradient::solve`` with z = r / diag(A); same guards, stop rule and panics
     (``smh_pcg_jacobi_solve``).  Host vectors; x (numpy array of the matrix dtype) is updated in place."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto"):
-        self.tol = float(tol)
-        self.iter_max = int(iter_max)
-        self.variant = variant
-        self.iterations = None
-        self.r_norm_squared = None
+        super().__init__(tol, iter_max, variant)
+        del self.check_every  # (the library's Jacobi-PCG takes none)
 
     def solve(self, mat, b, x):
-        if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
-            raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
-        bb = np.ascontiguousarray(b, dtype=mat.dtype)
-        iters, rr = C.c_size_t(), C.c_double()
-        check(lib().smh_pcg_jacobi_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
-                                         x.size, self.tol, self.iter_max, _lib.VARIANTS[self.variant], C.byref(iters), C.byref(rr)))
-        self.iterations, self.r_norm_squared = iters.value, rr.value
-        return x
+        return self._solve(None, lib().smh_pcg_jacobi_solve, mat, b, x)
 
 
-class SGSConjugateGradient:
+class SGSConjugateGradient(_DeviceSolver):
     """CG preconditioned by symmetric Gauss-Seidel, M = (D + L) D^-1 (D + U) -- an EXTENSION: the recurrence of
     ``JacobiConjugateGradient`` with z = M^-1 r by two level-scheduled sparse triangular solves (``smh_pcg_sgs_solve*``); same
     guards, stop rule and panics, device-resident like ``ConjugateGradient``.  The number of levels -- hence of kernel launches
     per body -- follows the ordering of the matrix (``SparseMatCRS.trisolve_levels``): a red-black or multicolour numbering
     (``permute_symmetric``) has few.  x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x."""
 
-    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
-        self.tol = float(tol)
-        self.iter_max = int(iter_max)
-        self.variant = variant
-        self.check_every = int(check_every)
-        self.iterations = None
-        self.r_norm_squared = None
-
     def solve(self, mat, b, x):
-        iters, rr = C.c_size_t(), C.c_double()
-        var = _lib.VARIANTS[self.variant]
-        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
-            check(lib().smh_pcg_sgs_solve_vec(mat._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
-                                              C.byref(iters), C.byref(rr)))
-        else:
-            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
-                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
-            bb = np.ascontiguousarray(b, dtype=mat.dtype)
-            check(lib().smh_pcg_sgs_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None,
-                                          x.size, self.tol, self.iter_max, var, C.byref(iters), C.byref(rr)))
-        self.iterations, self.r_norm_squared = iters.value, rr.value
-        return x
+        return self._solve(lib().smh_pcg_sgs_solve_vec, lib().smh_pcg_sgs_solve, mat, b, x)
 
 
-class ILUConjugateGradient:
+class ILUConjugateGradient(_DeviceSolver):
     """CG preconditioned by the incomplete LU factorization without fill, M = L U (``SparseMatCRS.ilu0``) -- an EXTENSION: the
     recurrence of ``SGSConjugateGradient`` with z = U^-1 L^-1 r by a unit-lower and an upper triangular solve on the factor
     (``smh_pcg_ilu_solve*``); the product is the matrix's.  ``solve(mat, b, x, factor=None)`` factors ``mat`` itself when no factor
@@ -154,12 +133,7 @@ class ILUConjugateGradient:
     factor).  x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
-        self.tol = float(tol)
-        self.iter_max = int(iter_max)
-        self.variant = variant
-        self.check_every = int(check_every)
-        self.iterations = None
-        self.r_norm_squared = None
+        super().__init__(tol, iter_max, variant, check_every)
         self.factor = None
         self.zero_pivot = None
 
@@ -168,22 +142,10 @@ class ILUConjugateGradient:
         if factor is None:
             factor, self.zero_pivot = mat.ilu0()
         self.factor = factor
-        iters, rr = C.c_size_t(), C.c_double()
-        var = _lib.VARIANTS[self.variant]
-        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
-            check(lib().smh_pcg_ilu_solve_vec(mat._h, factor._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
-                                              C.byref(iters), C.byref(rr)))
-        else:
-            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
-                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
-            bb = np.ascontiguousarray(b, dtype=mat.dtype)
-            check(lib().smh_pcg_ilu_solve(mat._h, factor._h, bb.ctypes.data if bb.size else None, bb.size,
-                                          x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var, C.byref(iters), C.byref(rr)))
-        self.iterations, self.r_norm_squared = iters.value, rr.value
-        return x
+        return self._solve(lib().smh_pcg_ilu_solve_vec, lib().smh_pcg_ilu_solve, mat, b, x, handles=(factor._h,))
 
 
-class BiCGStab:
+class BiCGStab(_DeviceSolver):
     """BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is the
     conjugate gradient): device-resident like ``ConjugateGradient``, the same guards, panics and stop rule
     (``sqrt(f64(r.r)) < tol`` after the update of r, and on ``s.s`` at the half step), ``smh_bicgstab_solve*``.
@@ -193,31 +155,16 @@ class BiCGStab:
     3 t.t == 0: x has taken p*alpha) and ``converged`` (a stop test ended the loop: neither a breakdown nor iter_max)."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
-        self.tol = float(tol)
-        self.iter_max = int(iter_max)
-        self.variant = variant
-        self.check_every = int(check_every)
-        self.iterations = None
-        self.r_norm_squared = None
+        super().__init__(tol, iter_max, variant, check_every)
         self.breakdown = None
         self.converged = None
 
     def solve(self, mat, b, x):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
         SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
-        iters, rr, brk = C.c_size_t(), C.c_double(), C.c_int()
-        var = _lib.VARIANTS[self.variant]
-        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
-            check(lib().smh_bicgstab_solve_vec(mat._h, b._h, x._h, self.tol, self.iter_max, var, self.check_every,
-                                               C.byref(iters), C.byref(rr), C.byref(brk)))
-        else:
-            if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
-                raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
-            bb = np.ascontiguousarray(b, dtype=mat.dtype)
-            check(lib().smh_bicgstab_solve(mat._h, bb.ctypes.data if bb.size else None, bb.size,
-                                           x.ctypes.data if x.size else None, x.size, self.tol, self.iter_max, var,
-                                           C.byref(iters), C.byref(rr), C.byref(brk)))
-        self.iterations, self.r_norm_squared, self.breakdown = iters.value, rr.value, brk.value
+        brk = C.c_int()
+        self._solve(lib().smh_bicgstab_solve_vec, lib().smh_bicgstab_solve, mat, b, x, extra_out=(brk,))
+        self.breakdown = brk.value
         # every entered body that ends without a breakdown has tested the r.r it reports: under tol means that test stopped the loop
         self.converged = self.breakdown == 0 and self.iterations > 0 and math.sqrt(self.r_norm_squared) < self.tol
         return x

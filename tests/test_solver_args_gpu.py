@@ -1,0 +1,360 @@
+"""What the ten entry points of the device-resident solvers answer to arguments they refuse -- the status code and the text of
+smh_last_error -- and what ``check_every = 0`` stands for, called through ``_lib.lib()`` as test_cg_many_gpu.py's ``expect`` does.
+
+    vec form:  smh_cg_solve_vec, smh_pcg_sgs_solve_vec, smh_pcg_ilu_solve_vec, smh_bicgstab_solve_vec, smh_cg_solve_many
+    host form: smh_cg_solve, smh_pcg_jacobi_solve, smh_pcg_sgs_solve, smh_pcg_ilu_solve, smh_bicgstab_solve, smh_cg_solve_many_host
+
+The tables record what each entry point does, including where the entry points differ from one another (DESIGN.md lists those
+differences): ``smh_cg_solve_vec`` words the dtype refusal in its own way and solves with b and x in one storage, of the host
+forms only ``smh_bicgstab_solve`` refuses b == x, and ``smh_cg_solve`` leaves the NULL pointer to ``smh_vec_upload``.  Every
+refusal is decided before any launch: x, iters and rr keep what they held.  The matrices are 2 x 3, 2 x 2 and 3 x 3."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sparsemat_amd as sm
+from sparsemat_amd import _lib
+
+pytestmark = pytest.mark.gpu
+F32, F64 = np.float32, np.float64
+OK, DIM, NOT_SQUARE, INVALID = 0, _lib.SMH_ERR_DIM_MISMATCH, _lib.SMH_ERR_NOT_SQUARE, _lib.SMH_ERR_INVALID
+SYMMETRIC, SIZE, SAME, NULL_HANDLE = "Matrix is not symmetric", "Matrix and vector size mismatch", "b and x are the same storage", "NULL handle"
+VEC_DTYPE = "vector dtype differs from the matrix's"
+TOL, ITER_MAX = 1e-5, 20
+
+VEC = ["smh_cg_solve_vec", "smh_pcg_sgs_solve_vec", "smh_pcg_ilu_solve_vec", "smh_bicgstab_solve_vec", "smh_cg_solve_many"]
+HOST = ["smh_cg_solve", "smh_pcg_jacobi_solve", "smh_pcg_sgs_solve", "smh_pcg_ilu_solve", "smh_bicgstab_solve", "smh_cg_solve_many_host"]
+ILU = ["smh_pcg_ilu_solve_vec", "smh_pcg_ilu_solve"]
+TRI = ["smh_pcg_sgs_solve_vec", "smh_pcg_sgs_solve"] + ILU
+DEFAULT_CHECK_EVERY = {"smh_cg_solve_vec": 4, "smh_cg_solve_many": 4, "smh_pcg_sgs_solve_vec": 8, "smh_pcg_ilu_solve_vec": 8, "smh_bicgstab_solve_vec": 8}
+# the vec form that a host form calls or mirrors (smh_pcg_jacobi_solve has none)
+VEC_OF = {"smh_cg_solve": "smh_cg_solve_vec", "smh_pcg_sgs_solve": "smh_pcg_sgs_solve_vec", "smh_pcg_ilu_solve": "smh_pcg_ilu_solve_vec",
+          "smh_bicgstab_solve": "smh_bicgstab_solve_vec", "smh_cg_solve_many_host": "smh_cg_solve_many"}
+
+# the 3 x 3 SPD tridiagonal system and its right-hand side
+A3 = (np.array([0, 2, 5, 7], np.uint32), np.array([0, 1, 0, 1, 2, 1, 2], np.uint32), np.array([4, -1, -1, 4, -1, -1, 4], F64))
+B3 = np.array([1.0, 2.0, 3.0])
+X3 = np.linalg.solve(np.array([[4.0, -1, 0], [-1, 4, -1], [0, -1, 4]]), B3)
+
+
+def square(n, dtype=F32):
+    """n x n, tridiagonal (n = 3: A3), rows ascending, every diagonal stored"""
+    if n == 3:
+        return sm.SparseMatCRS.from_raw_parts(3, 3, A3[0], A3[1], A3[2].astype(dtype))
+    assert n == 2
+    return sm.SparseMatCRS.from_raw_parts(2, 2, [0, 2, 4], [0, 1, 0, 1], np.array([4, -1, -1, 4], dtype))
+
+
+def factor(a):
+    f, zero_pivot = a.ilu0()
+    assert zero_pivot is None
+    return f
+
+
+def rect(dtype=F32):
+    """2 x 3"""
+    return sm.SparseMatCRS.from_raw_parts(2, 3, [0, 2, 4], [0, 1, 1, 2], np.array([4, -1, 4, -1], dtype))
+
+
+def orphaned(dtype=F32):
+    """2 x 2 with an orphaned entry (the first push of a replay into a SparseMatCRS), as test_trisolve_gpu.py builds it"""
+    m = sm.SparseMatCRS.from_triplets([1, 0, 1, 0], [1, 0, 0, 1], np.ones(4, dtype), into_crs=True)
+    assert m.orphans() == 1 and m.n_rows() == m.n_cols() == 2
+    return m
+
+
+class Out:
+    """the out-parameters of a call, preset to 9: a refusal leaves them alone"""
+
+    def __init__(self):
+        self.iters, self.rr, self.brk = (C.c_size_t * 2)(9, 9), (C.c_double * 2)(9.0, 9.0), C.c_int(9)
+
+    def untouched(self):
+        return list(self.iters) == [9, 9] and list(self.rr) == [9.0, 9.0] and self.brk.value == 9
+
+
+def handle_of(obj):
+    return None if obj is None else obj._h
+
+
+def call_vec(name, m, b, x, out, f=None, check_every=0):
+    """b, x: DenseVec (MultiVec for smh_cg_solve_many), or None"""
+    L = sm.lib()
+    if name == "smh_cg_solve_many":
+        return L.smh_cg_solve_many(handle_of(m), handle_of(b), handle_of(x), TOL, ITER_MAX, check_every, out.iters, out.rr)
+    args = [handle_of(m)] + ([handle_of(f)] if name in ILU else []) + [handle_of(b), handle_of(x), TOL, ITER_MAX, _lib.VARIANTS["auto"], check_every,
+                                                                       out.iters, out.rr]
+    if name == "smh_bicgstab_solve_vec":
+        args.append(C.byref(out.brk))
+    return getattr(L, name)(*args)
+
+
+def call_host(name, m, b_ptr, b_len, x_ptr, x_len, out, f=None):
+    """b_ptr, x_ptr: addresses or None.  smh_cg_solve_many_host takes one length and k = 1: x_len is not passed"""
+    L = sm.lib()
+    if name == "smh_cg_solve_many_host":
+        return L.smh_cg_solve_many_host(handle_of(m), b_ptr, b_len, 1, x_ptr, TOL, ITER_MAX, out.iters, out.rr)
+    args = [handle_of(m)] + ([handle_of(f)] if name in ILU else []) + [b_ptr, b_len, x_ptr, x_len, TOL, ITER_MAX, _lib.VARIANTS["auto"], out.iters, out.rr]
+    if name == "smh_bicgstab_solve":
+        args.append(C.byref(out.brk))
+    return getattr(L, name)(*args)
+
+
+def vec(name, values):
+    values = np.ascontiguousarray(values)
+    return sm.MultiVec.from_vecs(values[None, :]) if name == "smh_cg_solve_many" else sm.DenseVec.from_vec(values)
+
+
+def values_of(name, v):
+    return v.to_numpy()[0] if name == "smh_cg_solve_many" else v.to_numpy()
+
+
+def refused(rc, want, what):
+    status, text = want
+    msg = sm.lib().smh_last_error().decode()
+    assert rc == status and text in msg, (what, rc, msg, want)
+
+
+# ---- the vec form -------------------------------------------------------------------------------------------------------------------
+def dtype_text(name):
+    return {"smh_cg_solve_vec": "dtype mismatch", "smh_cg_solve_many": "multi-vector dtype differs from the matrix's"}.get(name, VEC_DTYPE)
+
+
+@pytest.mark.parametrize("name", VEC)
+def test_vec_form_refusals(gpu, name):
+    a = square(3)
+    f = factor(a)
+    sentinel = np.full(3, 7.0, F32)
+    b, x = vec(name, np.ones(3, F32)), vec(name, sentinel)
+    out = Out()
+
+    def expect(rc, want, what):
+        refused(rc, want, (name, what))
+        assert np.array_equal(values_of(name, x), sentinel) and out.untouched(), (name, what)   # nothing was launched
+
+    expect(call_vec(name, None, b, x, out, f), (INVALID, NULL_HANDLE), "NULL matrix")
+    expect(call_vec(name, a, None, x, out, f), (INVALID, NULL_HANDLE), "NULL b")
+    expect(call_vec(name, a, b, None, out, f), (INVALID, NULL_HANDLE), "NULL x")
+    if name in ILU:
+        expect(call_vec(name, a, b, x, out, None), (INVALID, NULL_HANDLE), "NULL factor")
+    expect(call_vec(name, a, vec(name, np.ones(4, F32)), x, out, f), (DIM, SIZE), "b of 4")
+    expect(call_vec(name, a, vec(name, np.ones(3, F64)), x, out, f), (INVALID, dtype_text(name)), "b of the other dtype")
+    x64 = vec(name, np.full(3, 7.0, F64))
+    refused(call_vec(name, a, b, x64, out, f), (INVALID, dtype_text(name)), (name, "x of the other dtype"))
+    assert np.array_equal(values_of(name, x64), np.full(3, 7.0)) and out.untouched()
+    xs = vec(name, np.full(2, 7.0, F32))
+    refused(call_vec(name, a, b, xs, out, f), (DIM, SIZE), (name, "x of 2"))
+    assert np.array_equal(values_of(name, xs), np.full(2, 7.0, F32)) and out.untouched()
+    # 2 x 3 with vectors of 2 (the rows) and of 3 (the columns)
+    r = rect()
+    x2, b2 = vec(name, sentinel[:2]), vec(name, np.ones(2, F32))
+    for bb, xx in ((b2, x2), (b, x)):
+        refused(call_vec(name, r, bb, xx, out, square(2)), (NOT_SQUARE, SYMMETRIC), (name, "2 x 3"))
+        assert np.array_equal(values_of(name, xx)[:2], sentinel[:2]) and out.untouched()
+    if name == "smh_cg_solve_many":   # ... and its own: the column counts, the output arrays
+        expect(call_vec(name, a, sm.MultiVec.from_vecs(np.ones((2, 3), F32)), x, out), (DIM, SIZE), "k differs")
+        L = sm.lib()
+        expect(L.smh_cg_solve_many(a._h, b._h, x._h, TOL, ITER_MAX, 0, None, out.rr), (INVALID, "NULL output array"), "NULL iters")
+        expect(L.smh_cg_solve_many(a._h, b._h, x._h, TOL, ITER_MAX, 0, out.iters, None), (INVALID, "NULL output array"), "NULL rr")
+        expect(L.smh_cg_solve_many(a._h, b._h, x._h, TOL, ITER_MAX, 0, None, None), (INVALID, "NULL output array"), "NULL outputs")
+    # where more than one check fires, the first one reported.  Wrong dtype, b is x, 2 x 3, wrong length: the dtype
+    w = vec(name, np.full(4, 7.0, F64))
+    refused(call_vec(name, r, w, w, out, square(2)), (INVALID, dtype_text(name)), (name, "all four"))
+    # b is x, 2 x 3, wrong length: the same storage, but for smh_cg_solve_vec, which has no such check
+    w = vec(name, np.full(4, 7.0, F32))
+    want = (NOT_SQUARE, SYMMETRIC) if name == "smh_cg_solve_vec" else (INVALID, SAME)
+    refused(call_vec(name, r, w, w, out, square(2)), want, (name, "b is x, 2 x 3, wrong length"))
+    # 2 x 3 and a wrong length: not square
+    refused(call_vec(name, r, vec(name, np.ones(4, F32)), w, out, square(2)), (NOT_SQUARE, SYMMETRIC), (name, "2 x 3, wrong length"))
+    assert np.array_equal(values_of(name, w), np.full(4, 7.0, F32)) and out.untouched()
+    # the call that all of these refused goes through
+    assert call_vec(name, a, b, x, out, f) == OK and 0 < out.iters[0] <= ITER_MAX and out.iters[1] == 9
+
+
+@pytest.mark.parametrize("name", VEC)
+def test_vec_form_b_and_x_in_one_storage(gpu, name):
+    """One handle for both, and two handles on one device array.  smh_cg_solve_vec does not refuse: it solves (r = b - A x is
+    formed before x is first written, and b is not read again)."""
+    a = square(3)
+    f = factor(a)
+    out = Out()
+    if name == "smh_cg_solve_many":
+        x = vec(name, B3.astype(F32))
+        refused(call_vec(name, a, x, x, out), (INVALID, SAME), (name, "b is x"))
+        assert np.array_equal(values_of(name, x), B3.astype(F32)) and out.untouched()
+        return   # (a MultiVec owns its storage: no second handle on it)
+    for second_handle in (False, True):
+        x = sm.DenseVec.from_vec(B3.astype(F32))
+        b = sm.DenseVec.from_device_ptr(x.data_ptr(), 3, F32, keep=x) if second_handle else x
+        out = Out()
+        rc = call_vec(name, a, b, x, out, f)
+        if name == "smh_cg_solve_vec":
+            assert rc == OK and 0 < out.iters[0] < ITER_MAX and np.sqrt(out.rr[0]) < TOL, (rc, list(out.iters), list(out.rr))
+            assert np.allclose(x.to_numpy(), X3, rtol=0, atol=1e-5)
+        else:
+            refused(rc, (INVALID, SAME), (name, "one storage", second_handle))
+            assert np.array_equal(x.to_numpy(), B3.astype(F32)) and out.untouched()
+
+
+# ---- the host form ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", HOST)
+def test_host_form_refusals(gpu, name):
+    a = square(3)
+    f = factor(a)
+    sentinel = np.full(4, 7.0, F32)
+    x, b = sentinel.copy(), np.ones(4, F32)
+    out = Out()
+    many = name == "smh_cg_solve_many_host"
+
+    def expect(rc, want, what):
+        refused(rc, want, (name, what))
+        assert np.array_equal(x, sentinel) and out.untouched(), (name, what)   # nothing was launched, nothing copied back
+
+    bp, xp = b.ctypes.data, x.ctypes.data
+    expect(call_host(name, None, bp, 3, xp, 3, out, f), (INVALID, NULL_HANDLE), "NULL matrix")
+    if name in ILU:
+        expect(call_host(name, a, bp, 3, xp, 3, out, None), (INVALID, NULL_HANDLE), "NULL factor")
+    expect(call_host(name, a, bp, 4, xp, 4 if many else 3, out, f), (DIM, SIZE), "b of 4")
+    if not many:
+        expect(call_host(name, a, bp, 3, xp, 2, out, f), (DIM, SIZE), "x of 2")
+    for n in (2, 3):   # 2 x 3 with vectors of 2 (the rows) and of 3 (the columns)
+        expect(call_host(name, rect(), bp, n, xp, n, out, square(2)), (NOT_SQUARE, SYMMETRIC), "2 x 3")
+    # a NULL host pointer with n > 0 (smh_cg_solve has no check of its own: the upload of the vector refuses)
+    null_text = "NULL argument" if name == "smh_cg_solve" else "NULL host vector"
+    expect(call_host(name, a, None, 3, xp, 3, out, f), (INVALID, null_text), "NULL b")
+    expect(call_host(name, a, bp, 3, None, 3, out, f), (INVALID, null_text), "NULL x")
+    expect(call_host(name, a, None, 3, None, 3, out, f), (INVALID, null_text), "NULL b and x")   # (before "the same storage")
+    # where more than one check fires: not square, then the lengths, then the pointers
+    expect(call_host(name, rect(), None, 4, None, 4, out, square(2)), (NOT_SQUARE, SYMMETRIC), "2 x 3, wrong length, NULL")
+    expect(call_host(name, a, None, 4, None, 4, out, f), (DIM, SIZE), "wrong length, NULL")
+    if many:
+        L, r = sm.lib(), rect()
+        expect(L.smh_cg_solve_many_host(None, bp, 3, 1, xp, TOL, ITER_MAX, None, out.rr), (INVALID, NULL_HANDLE), "NULL matrix, NULL iters")
+        expect(L.smh_cg_solve_many_host(r._h, bp, 4, 1, xp, TOL, ITER_MAX, None, out.rr), (INVALID, "NULL output array"), "NULL iters")
+        expect(L.smh_cg_solve_many_host(a._h, bp, 3, 1, xp, TOL, ITER_MAX, out.iters, None), (INVALID, "NULL output array"), "NULL rr")
+        expect(L.smh_cg_solve_many_host(a._h, bp, 3, 0, xp, TOL, ITER_MAX, out.iters, out.rr), (INVALID, ""), "k = 0")
+    # the call that all of these refused goes through
+    assert call_host(name, a, bp, 3, xp, 3, out, f) == OK and 0 < out.iters[0] <= ITER_MAX and out.iters[1] == 9
+    assert x[3] == 7.0 and not np.array_equal(x[:3], sentinel[:3])
+
+
+@pytest.mark.parametrize("name", HOST)
+def test_host_form_b_and_x_in_one_array(gpu, name):
+    """Only smh_bicgstab_solve refuses; the others stage b and x apart and solve."""
+    a = square(3)
+    f = factor(a)
+    x = B3.astype(F32)
+    out = Out()
+    rc = call_host(name, a, x.ctypes.data, 3, x.ctypes.data, 3, out, f)
+    if name == "smh_bicgstab_solve":
+        refused(rc, (INVALID, SAME), name)
+        assert np.array_equal(x, B3.astype(F32)) and out.untouched()
+    else:
+        assert rc == OK and 0 < out.iters[0] < ITER_MAX and np.sqrt(out.rr[0]) < TOL, (name, rc, list(out.iters), list(out.rr))
+        assert np.allclose(x, X3, rtol=0, atol=1e-5)
+
+
+# ---- the preconditioner's handle ----------------------------------------------------------------------------------------------------
+def ilu_call(name, a, f, n, out):
+    """vectors of n on a and f"""
+    if name == "smh_pcg_ilu_solve_vec":
+        return call_vec(name, a, sm.DenseVec.from_vec(np.ones(n, a.dtype)), sm.DenseVec.zeros(n, a.dtype), out, f)
+    b, x = np.ones(n, a.dtype), np.zeros(n, a.dtype)
+    rc = call_host(name, a, b.ctypes.data, n, x.ctypes.data, n, out, f)
+    assert rc == OK or not x.any()
+    return rc
+
+
+@pytest.mark.parametrize("name", ILU)
+def test_ilu_pair_refusals(gpu, name):
+    """What the matrix and the factor must agree in, in the order of the checks.  (The fifth, a factor on another device, takes a
+    second GPU to build: it is checked where there is one.)"""
+    out = Out()
+    a3 = square(3)
+    cases = [("the matrix is 2 x 3", rect(), square(2), 2, (NOT_SQUARE, SYMMETRIC)),
+             ("the matrix is 2 x 3, and so is the factor", rect(), rect(), 2, (NOT_SQUARE, SYMMETRIC)),
+             ("the factor is 2 x 3", square(2), rect(), 2, (NOT_SQUARE, "ILU preconditioner: the factor is not square")),
+             ("the factor is 2 x 3 and of the other dtype", square(2), rect(F64), 2, (NOT_SQUARE, "ILU preconditioner: the factor is not square")),
+             ("the factor is 2 x 2", a3, square(2), 3, (DIM, "ILU preconditioner: the factor's dimension differs from the matrix's")),
+             ("the factor is 2 x 2 and of the other dtype", a3, square(2, F64), 3, (DIM, "ILU preconditioner: the factor's dimension differs from the matrix's")),
+             ("the factor is of the other dtype", a3, square(3, F64), 3, (INVALID, "ILU preconditioner: the factor's dtype differs from the matrix's"))]
+    for what, a, f, n, want in cases:
+        refused(ilu_call(name, a, f, n, out), want, (name, what))
+        assert out.untouched(), (name, what)
+    # the pair is checked before the vectors' lengths, after their dtype and storage (vec form)
+    refused(ilu_call(name, a3, square(2), 2, out), (DIM, "ILU preconditioner: the factor's dimension differs from the matrix's"), (name, "pair, then lengths"))
+    if name == "smh_pcg_ilu_solve_vec":
+        w = sm.DenseVec.zeros(3, F64)
+        refused(call_vec(name, a3, w, w, out, square(2)), (INVALID, VEC_DTYPE), (name, "dtype, then pair"))
+        w = sm.DenseVec.zeros(3, F32)
+        refused(call_vec(name, a3, w, w, out, square(2)), (INVALID, SAME), (name, "storage, then pair"))
+    assert out.untouched()
+    print("%s: %d device(s)" % (name, gpu))
+    if gpu >= 2:   # a factor on another device
+        L = sm.lib()
+        assert L.smh_set_device(1) == 0
+        try:
+            far = square(3)
+        finally:
+            assert L.smh_set_device(0) == 0
+        refused(ilu_call(name, a3, far, 3, out), (INVALID, "ILU preconditioner: the factor and the matrix live on different devices"), (name, "devices"))
+        assert out.untouched()
+
+
+@pytest.mark.parametrize("name", TRI)
+def test_orphaned_entry_in_the_preconditioner_handle(gpu, name):
+    """SGS solves on the matrix itself, ILU on the factor: an orphaned entry there is refused after the argument checks."""
+    out = Out()
+    who = "ILU preconditioner" if name in ILU else "SGS preconditioner"
+    m = orphaned()
+    a = square(2) if name in ILU else m
+    sentinel = np.full(2, 7.0, F32)
+    if name in VEC:
+        x = sm.DenseVec.from_vec(sentinel)
+        rc = call_vec(name, a, sm.DenseVec.from_vec(np.ones(2, F32)), x, out, m)
+        got = x.to_numpy()
+    else:
+        b, got = np.ones(2, F32), sentinel.copy()
+        rc = call_host(name, a, b.ctypes.data, 2, got.ctypes.data, 2, out, m)
+    refused(rc, (INVALID, who + ": the handle holds an orphaned entry"), name)
+    assert np.array_equal(got, sentinel) and out.untouched()
+    # ... after them: a wrong length is reported first
+    if name in VEC:
+        rc = call_vec(name, a, sm.DenseVec.from_vec(np.ones(3, F32)), sm.DenseVec.zeros(2, F32), out, m)
+    else:
+        rc = call_host(name, a, b.ctypes.data, 3, got.ctypes.data, 2, out, m)
+    refused(rc, (DIM, SIZE), (name, "length first"))
+
+
+# ---- check_every = 0 ----------------------------------------------------------------------------------------------------------------
+def solve3(name, dtype, check_every):
+    """(iterations, rr, x, breakdown) of the 3 x 3 system from x = 0, tol 1e-5, iter_max 20"""
+    a = square(3, dtype)
+    f = a.ilu0()[0] if name in ILU else None
+    out = Out()
+    if name in VEC:
+        x = vec(name, np.zeros(3, dtype))
+        assert call_vec(name, a, vec(name, B3.astype(dtype)), x, out, f, check_every) == OK, sm.lib().smh_last_error()
+        xs = values_of(name, x)
+    else:
+        b, xs = B3.astype(dtype), np.zeros(3, dtype)
+        assert call_host(name, a, b.ctypes.data, 3, xs.ctypes.data, 3, out, f) == OK, sm.lib().smh_last_error()
+    assert out.iters[1] == 9 and out.rr[1] == 9.0
+    return out.iters[0], out.rr[0], xs, out.brk.value
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("name", VEC + HOST)
+def test_check_every_zero_is_the_default(gpu, name, dtype):
+    """check_every = 0 (the host forms pass it themselves) gives what the explicit default gives -- 4 bodies per poll for CG and the
+    k-column CG, 8 for the others -- and the solve converges: a stop test ends it before iter_max, sqrt(r.r) < tol."""
+    it0, rr0, x0, brk0 = solve3(name, dtype, 0)
+    print("%s %s: %d bodies, r.r = %g" % (name, np.dtype(dtype).name, it0, rr0))
+    assert 0 < it0 < ITER_MAX and np.sqrt(rr0) < TOL and brk0 in (0, 9), (it0, rr0, brk0)
+    assert np.allclose(x0, X3, rtol=0, atol=1e-5)
+    explicit = name if name in VEC else VEC_OF.get(name)
+    if explicit is None:
+        return   # (smh_pcg_jacobi_solve: no check_every anywhere; its batches are of 8)
+    it1, rr1, x1, brk1 = solve3(explicit, dtype, DEFAULT_CHECK_EVERY[explicit])
+    assert it0 == it1 and rr0 == rr1 and np.array_equal(x0, x1) and brk0 == brk1, (it0, it1, rr0, rr1, x0, x1)
