@@ -754,4 +754,38 @@ class BiCGStab {
     int breakdown_ = 0;
 };
 
+// Restarted GMRES(m) for non-symmetric systems -- an extension, not in the reference (smh_gmres_solve*): the robust companion of
+// BiCGStab (no breakdown before the Krylov space is exhausted, no stagnation near the imaginary axis), device-resident like it, same
+// panics.  restart: 1 .. 128 (0: the library's default, 30).  breakdown(): 0 none, 1 the Krylov space is exhausted (x is updated from
+// it), 2 the residual at a cycle's start is exactly zero (sparsemat_hip.h); cycles(): how many times a v_0 was formed.
+class GMRES {
+  public:
+    GMRES() = default;
+    GMRES(double tol, size_t iter_max, size_t restart = 30) : tol_(tol), iter_max_(iter_max), restart_(restart) {}
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_gmres_solve_vec(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, restart_, SMH_SPMV_AUTO, 0, &iterations_,
+                                          &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    // host vectors, x updated in place
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_gmres_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, restart_, SMH_SPMV_AUTO,
+                                      &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    size_t iterations() const { return iterations_; }
+    double r_norm_squared() const { return r_norm_squared_; }
+    size_t cycles() const { return cycles_; }
+    int breakdown() const { return breakdown_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t iter_max_ = 10000;
+    size_t restart_ = 30;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
+    size_t cycles_ = 0;
+    int breakdown_ = 0;
+};
+
 }  // namespace sparsemat

@@ -45,7 +45,7 @@ extern "C" {
  * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
  * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
- * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec.  A caller checks smh_abi_version() ==
+ * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec.  A caller checks smh_abi_version() ==
  * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
@@ -779,6 +779,36 @@ int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_hos
 int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                            int variant, size_t check_every,
                            size_t *iters_out, double *rr_out, int *breakdown_out);
+
+/* Restarted GMRES(m) (Saad & Schultz, unpreconditioned) for non-symmetric systems -- an EXTENSION, the robust companion of
+ * smh_bicgstab_solve: it cannot break down before the Krylov space is exhausted and does not stagnate where BiCGSTAB's omega
+ * goes to zero (a spectrum near the imaginary axis); a body is ONE product and sweeps over a basis of up to m + 1 vectors of n
+ * kept on the device (so its memory is (m + 5) n values).  Device-resident like smh_bicgstab_solve: the stop is decided on the
+ * device in every body and polled every `check_every` bodies (0: default, 8), bodies enqueued past the stop are no-ops.
+ * `restart` is m, 1 <= m <= 128; 0 stands for 30.  One rounding per operation, sqrt correctly rounded, comparisons with zero exact:
+ *   set-up:  r = b - A x;  rr = r.r;  beta = sqrt(rr);  beta == 0: stop, no body entered, breakdown 2
+ *            v_0 = r / beta;  g = (beta);  j = 0;  cycles = 1
+ *   body:    w = A v_j;  h1_c = v_c.w (c <= j);  w -= v_c h1_c (c ascending);  h2_c = v_c.w;  w -= v_c h2_c;  h = h1 + h2
+ *            hn = sqrt(w.w);  the stored rotations on h;  d = sqrt(h_j h_j + hn hn);  c_j = h_j / d;  s_j = hn / d
+ *            R[0..j, j] = (h_0 .. h_{j-1}, c_j h_j + s_j hn);  g_{j+1} = (-s_j) g_j;  g_j = c_j g_j;  j += 1
+ *            v_j = w / hn (w itself when hn == 0)
+ *            the cycle ends when hn == 0 (breakdown 1: the Krylov space is exhausted, x is updated from it), |f64(g_j)| < tol
+ *            (converged), iters == iter_max, or -- none of these, which stop the solve -- j == m (restart)
+ *   cycle end:  R y = g[0..j) by back substitution;  x += v_0 y_0 + .. + v_{j-1} y_{j-1} (ascending, term by term)
+ *            r = v_0 z_0 + .. + v_j z_j with z the transposed rotations applied to g_j e_j: NO product; rr = r.r
+ *            on a restart:  beta = sqrt(rr);  beta == 0: stop, breakdown 2;  else v_0 = r / beta, g = (beta), j = 0, cycles += 1
+ * (the orders in full: csrc/gmres.hip and tests/gmres_model.py).  d is not scaled against overflow; a singular matrix gives
+ * IEEE values, not an error; non-finite data run to iter_max.  A breakdown is not an error: the call returns SMH_OK and
+ * *breakdown_out holds 0, 1 or 2.  iters_out = bodies entered, rr_out = the last rebuilt r.r (the initial residual's before the
+ * first cycle end) as f64, cycles_out = the number of times a v_0 was formed; the output pointers may be NULL.
+ * Statuses, decided on the host before any launch: smh_bicgstab_solve's, then SMH_ERR_INVALID for restart > 128.
+ * x: in x0, out the solution. */
+int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                    double tol, size_t iter_max, size_t restart, int variant,
+                    size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart,
+                        int variant, size_t check_every,
+                        size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
 
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;

@@ -105,6 +105,35 @@ impl BiCGStab {
     }
 }
 
+/// Restarted GMRES(m) for non-symmetric systems -- an extension, not in the reference (`smh_gmres_solve`): the robust companion of
+/// `BiCGStab` (no breakdown before the Krylov space is exhausted, no stagnation near the imaginary axis).  Uncompiled like the rest
+/// of this shim.
+pub struct Gmres {
+    pub tol: f64,
+    pub iter_max: usize,
+    /// 1 ..= 128 (0: the library's default, 30)
+    pub restart: usize,
+}
+
+impl Default for Gmres {
+    fn default() -> Self {
+        Gmres { tol: 1e-12, iter_max: 10_000, restart: 30 }
+    }
+}
+
+impl Gmres {
+    /// `x` is updated in place; returns (bodies entered, the last rebuilt r.r, cycles begun, breakdown code: 0 none, 1 the Krylov
+    /// space is exhausted, 2 a cycle's starting residual is exactly zero).  A breakdown ends the solve without a panic.
+    pub fn solve<T: HipValue>(&self, mat: &DeviceCrs, b: &[T], x: &mut [T]) -> (usize, f64, usize, i32) {
+        let (mut iters, mut rr, mut cycles, mut breakdown) = (0usize, 0f64, 0usize, 0 as std::os::raw::c_int);
+        check(unsafe {
+            ffi::smh_gmres_solve(mat.handle, b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void, x.len(), self.tol,
+                                 self.iter_max, self.restart, ffi::SMH_SPMV_AUTO, &mut iters, &mut rr, &mut cycles, &mut breakdown)
+        });
+        (iters, rr, cycles, breakdown as i32)
+    }
+}
+
 /// CG preconditioned by symmetric Gauss-Seidel -- an extension, not in the reference (`smh_pcg_sgs_solve`): the Jacobi
 /// recurrence with z = M^-1 r by two level-scheduled triangular solves.  Uncompiled like the rest of this shim.
 pub struct SgsConjugateGradient {

@@ -1,0 +1,502 @@
+// gmres.hip -- restarted GMRES(m) (Saad & Schultz, unpreconditioned) for non-symmetric systems, gfx950.
+//
+// An EXTENSION: the reference's only solver is ConjugateGradient (linearsolver.rs:12-61); bicgstab.hip is the library's short
+// recurrence for matrices that are not symmetric, and this is the robust one: it cannot break down before the Krylov space is
+// exhausted and it does not stagnate where BiCGSTAB's omega goes to zero (a spectrum near the imaginary axis).  The family's
+// conventions: the guards of linearsolver.rs:30-36, no stop test before the first body, one rounding per operation (p_mul / p_add /
+// p_div; sqrt is IEEE's, correctly rounded; a - b*c is add(a, -mul(b, c)); nothing is contracted), products by the matrix's own
+// kernel.  `restart` is m, 1 <= m <= 128 (kGmMaxM); 0 stands for 30.
+//   set-up:  r = b - A x;  rr = r.r;  beta = sqrt(rr)
+//            beta == 0: stop, no body entered, breakdown 2 (also when iter_max == 0)
+//            v_0 = r / beta;  g = (beta);  j = 0;  cycles = 1
+//   body (iters += 1; columns v_0 .. v_j exist):
+//      w = A v_j
+//      pass 1:  h1_c = v_c.w  (c = 0 .. j, all from the same w);  w = (..((w - v_0 h1_0) - v_1 h1_1) .. - v_j h1_j)   ascending c
+//      pass 2:  h2_c = v_c.w;  the same update with h2                                  (classical Gram-Schmidt, twice)
+//      h_c = h1_c + h2_c;  hn = sqrt(w.w)                                               (hn is h_{j+1,j})
+//      the stored rotations i = 0 .. j-1 on (h_i, h_{i+1}):  t = c_i h_i + s_i h_{i+1};  h_{i+1} = (-s_i) h_i + c_i h_{i+1};  h_i = t
+//      d = sqrt(h_j h_j + hn hn);  c_j = h_j / d;  s_j = hn / d;  R[0..j, j] = (h_0 .. h_{j-1}, c_j h_j + s_j hn)
+//      g_{j+1} = (-s_j) g_j;  g_j = c_j g_j;  j += 1
+//      v_j = w / hn  (element by element, a division), or w itself when hn == 0   -- in EVERY entered body, a cycle's last too
+//      the cycle ends when   hn == 0               (breakdown 1: the Krylov space is exhausted; x is updated from it)
+//                       or   |f64(g_j)| < tol      (converged)
+//                       or   iters == iter_max
+//                       or   j == m                (restart -- only if none of the three above holds: they stop the solve)
+//      Any of them ends the cycle; breakdown 1 is reported whenever hn == 0, also when |g_j| < tol holds with it (A = 2 I).
+//   cycle end:  R y = g[0..j) by back substitution: i descending, y_i = ((..(g_i - R_{i,i+1} y_{i+1}) - ..) - R_{i,j-1} y_{j-1}) / R_ii
+//               x = (..((x + v_0 y_0) + v_1 y_1) .. + v_{j-1} y_{j-1})
+//               z = (0, .., 0, g_j);  i = j-1 .. 0 on (z_i, z_{i+1}):  t = c_i z_i + (-s_i) z_{i+1};  z_{i+1} = s_i z_i + c_i z_{i+1};  z_i = t
+//               r = (..(v_0 z_0 + v_1 z_1) .. + v_j z_j);  rr = r.r             (the residual's coordinates in v_0 .. v_j)
+//               on a restart:  beta = sqrt(rr);  beta == 0: stop, breakdown 2;  else v_0 = r / beta, g = (beta), j = 0, cycles += 1
+// No product at a cycle end: the residual is rebuilt from the basis (CG and BiCGSTAB trust their recurrence residual too), so a
+// solve is one fixed chain of launches.  Two Gram-Schmidt passes keep max|V^T V - I| at working precision (one pass lets it grow to
+// 0.09 in f32 at m = 30: not offered).  d is NOT scaled against overflow, and a singular matrix gives IEEE values (c_j = 0 / 0), not
+// an error.  The comparisons with zero are exact and NaN compares false, so non-finite data run to iter_max (restarting on the way).
+// Outputs: iters = bodies entered; rr = the last rebuilt r.r (the initial residual's before the first cycle end); cycles = the
+// number of times a v_0 was formed; breakdown 0, 1 or 2.
+//
+// Storage: the basis is m + 1 columns of n, column-major, the column stride rounded up to 16 bytes (ld), so every column is a
+// vector that 16-byte loads sweep.  The product reads its input at a fixed address (the graph of a batch is replayed), so the
+// normalising sweep writes the new vector twice: to its column and to `vin` (n values more per body than a pointer would cost).
+// Kernels: beside the product a body at column j is  dots (j + 2 vectors read) - fold - update (j + 2 read, 1 written), twice;
+// the step (one workgroup: folds w.w, thread 0 does the rotations and the decisions and, at a cycle end, y and z); the
+// normalisation (1 read, 2 written): (4 j + 13) n values, (2 m + 11) n averaged over a full cycle.  A cycle end adds one sweep over
+// the basis that forms x and r with the partials of r.r ((j + 2) read, 2 written), its fold, and on a restart v_0 (1 read, 2 written).
+// The dots: w's 16-byte vector is loaded once per tile of kGmTile = 8 columns, one accumulator per column; every column is summed by
+// solver_tree.hpp's tree on pcg_grid(n) -- cg_model.Reducer.dot(., ., "pcg") -- so the tile width changes no bit.
+// All state is on the device: a leading block in CgScalars' layout (solve_in_batches polls it; `converged` means STOPPED) and a
+// second block (GmMore).  The kernels read the column count from it; a sweep that is not due returns at once: the Gram-Schmidt
+// sweeps when the body will not be entered (stopped, or iter_max bodies entered -- `iters` moves only in the step), the others on
+// the gate words the step and the cycle end's fold leave.  Bodies enqueued past the stop are no-ops.  No float atomics.
+#include "internal.hpp"
+#include "solver_host.hpp"
+#include "solver_tree.hpp"
+
+#include <cmath>
+
+using namespace smh;
+
+namespace {
+
+constexpr int kGmMaxM = 128;
+constexpr int kGmTile = 8;  // columns per load of w in the dots (no bit depends on it)
+constexpr size_t kGmDefaultRestart = 30;
+
+// the block the host polls through CG's reader (cg_read_scalars)
+template <typename T>
+struct GmScalars {
+    T rr, spare0_, spare1_, spare2_, spare3_;
+    uint32_t converged;  // STOPPED: converged, a breakdown
+    uint32_t spare4_, spare5_, pad_;
+    uint64_t iters;
+    uint64_t iter_max;
+    double tol;
+};
+template <typename T> constexpr bool gm_scalars_like_cg() {
+    return sizeof(GmScalars<T>) == sizeof(CgScalars<T>) && offsetof(GmScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
+           offsetof(GmScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(GmScalars<T>, iters) == offsetof(CgScalars<T>, iters);
+}
+static_assert(gm_scalars_like_cg<float>() && gm_scalars_like_cg<double>(), "GmScalars and CgScalars have drifted apart");
+
+// the solver's further state; the host reads the words before `hn` once, after the loop
+template <typename T>
+struct GmMore {
+    uint32_t j;          // columns v_0 .. v_j exist
+    uint32_t m;          // restart
+    uint32_t cycles;
+    uint32_t breakdown;  // 0 none, 1 hn == 0, 2 beta == 0
+    uint32_t do_norm;    // gate: this body's normalisation is due
+    uint32_t do_end;     // gate: a cycle end is due (the x / r sweep and its fold)
+    uint32_t do_v0;      // gate: a restart is due (v_0 = r / beta)
+    uint32_t restart;    // the cycle end that is due is a restart (not a stop)
+    T hn, beta;
+    T g[kGmMaxM + 1], c[kGmMaxM], s[kGmMaxM], h1[kGmMaxM + 1], h2[kGmMaxM + 1], y[kGmMaxM], z[kGmMaxM + 1];
+    T R[kGmMaxM * kGmMaxM];  // R_{i,k} at [k * kGmMaxM + i], i <= k
+};
+
+template <typename T> __device__ __forceinline__ T p_sqrt(T a) { return (T)sqrt((double)a); }  // (f64's sqrt rounds an f32 correctly too)
+
+template <typename T> __device__ __forceinline__ bool gm_enters(const GmScalars<T> *sc) { return !sc->converged && sc->iters < sc->iter_max; }
+
+template <typename T>
+__global__ void k_gm_init(GmScalars<T> *sc, GmMore<T> *mo, double tol, uint64_t iter_max, uint32_t m) {
+    sc->rr = sc->spare0_ = sc->spare1_ = sc->spare2_ = sc->spare3_ = T(0);
+    sc->converged = sc->spare4_ = sc->spare5_ = sc->pad_ = 0;
+    sc->iters = 0;
+    sc->iter_max = iter_max;
+    sc->tol = tol;
+    mo->j = mo->cycles = mo->breakdown = mo->do_norm = mo->do_end = mo->do_v0 = mo->restart = 0;
+    mo->m = m;
+    mo->hn = mo->beta = T(0);
+}
+
+template <typename T>
+__device__ __forceinline__ T gm_fold1(const T *__restrict__ part, unsigned n_parts) {
+    T a = T(0);
+    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
+    return block_sum1(a);  // (thread 0)
+}
+
+#define GM_SWEEP_HEAD                                  \
+    constexpr int V = 16 / sizeof(T);                  \
+    typedef T VT __attribute__((ext_vector_type(V))); \
+    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x
+#define GM_LOAD(p, q) __builtin_nontemporal_load(reinterpret_cast<const VT *>(p) + (q))
+#define GM_STORE(v, p, q) __builtin_nontemporal_store((v), reinterpret_cast<VT *>(p) + (q))
+
+// ---- the sweeps over the basis (basis: columns of stride ld, ld % V == 0) ------------------------------------------------------
+// partials of v_c.w for c = 0 .. j: part[c * kPcgBlocks + block]
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_gm_dots(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, const T *__restrict__ w,
+          uint64_t n, T *__restrict__ part) {
+    if (!gm_enters(sc)) return;  // block-uniform
+    const unsigned ncols = mo->j + 1;
+    GM_SWEEP_HEAD;
+    __shared__ T sa[kGmTile][kBlock / kWave];
+    for (unsigned c0 = 0; c0 < ncols; c0 += kGmTile) {
+        const unsigned width = ncols - c0 < (unsigned)kGmTile ? ncols - c0 : (unsigned)kGmTile;
+        const T *col0 = basis + (uint64_t)c0 * ld;
+        T acc[kGmTile];
+#pragma unroll
+        for (int t = 0; t < kGmTile; ++t) acc[t] = T(0);
+        for (uint64_t q = tid; q < nv; q += nthreads) {
+            const VT wv = GM_LOAD(w, q);
+#pragma unroll
+            for (int t = 0; t < kGmTile; ++t) {
+                if ((unsigned)t < width) {
+                    const VT vv = GM_LOAD(col0 + (uint64_t)t * ld, q);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) acc[t] = p_add(acc[t], p_mul(vv[e], wv[e]));
+                }
+            }
+        }
+        for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+            const T wi = w[i];
+#pragma unroll
+            for (int t = 0; t < kGmTile; ++t)
+                if ((unsigned)t < width) acc[t] = p_add(acc[t], p_mul(col0[(uint64_t)t * ld + i], wi));
+        }
+        // solver_tree.hpp's workgroup sum, one per column of the tile
+#pragma unroll
+        for (int t = 0; t < kGmTile; ++t) {
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) acc[t] = p_add(acc[t], (T)__shfl_down(acc[t], o, kWave));
+            if ((threadIdx.x & (kWave - 1)) == 0) sa[t][threadIdx.x / kWave] = acc[t];
+        }
+        __syncthreads();
+        if (threadIdx.x < width) {
+            T s = sa[threadIdx.x][0];
+            for (int wv = 1; wv < kBlock / kWave; ++wv) s = p_add(s, sa[threadIdx.x][wv]);
+            part[(uint64_t)(c0 + threadIdx.x) * kPcgBlocks + blockIdx.x] = s;
+        }
+        __syncthreads();  // (sa is written again by the next tile)
+    }
+}
+
+// workgroup c folds column c's partials into h1_c (PASS 1) or h2_c (PASS 2); launched on m + 1 workgroups
+template <typename T, int PASS>
+__global__ void __launch_bounds__(kBlock)
+k_gm_fold(const GmScalars<T> *__restrict__ sc, GmMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
+    if (!gm_enters(sc) || blockIdx.x > mo->j) return;
+    const T h = gm_fold1(part + (uint64_t)blockIdx.x * kPcgBlocks, n_parts);
+    if (threadIdx.x == 0) (PASS == 1 ? mo->h1 : mo->h2)[blockIdx.x] = h;
+}
+
+// w = (..((w - v_0 h_0) - v_1 h_1) .. - v_j h_j) with this pass's h; PASS 2: and the partials of w.w
+template <typename T, int PASS>
+__global__ void __launch_bounds__(kBlock)
+k_gm_update(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ w, uint64_t n,
+            T *__restrict__ part_ww) {
+    if (!gm_enters(sc)) return;
+    const unsigned ncols = mo->j + 1;
+    const T *__restrict__ h = PASS == 1 ? mo->h1 : mo->h2;
+    GM_SWEEP_HEAD;
+    T acc = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT wv = GM_LOAD(w, q);
+#pragma unroll 8
+        for (unsigned c = 0; c < ncols; ++c) {
+            const VT vv = GM_LOAD(basis + (uint64_t)c * ld, q);
+            const T hc = h[c];
+#pragma unroll
+            for (int e = 0; e < V; ++e) wv[e] = p_add(wv[e], -p_mul(vv[e], hc));
+        }
+        if (PASS == 2) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(wv[e], wv[e]));
+        }
+        GM_STORE(wv, w, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        T wi = w[i];
+        for (unsigned c = 0; c < ncols; ++c) wi = p_add(wi, -p_mul(basis[(uint64_t)c * ld + i], h[c]));
+        if (PASS == 2) acc = p_add(acc, p_mul(wi, wi));
+        w[i] = wi;
+    }
+    if (PASS == 2) {
+        const T t = block_sum1(acc);
+        if (threadIdx.x == 0) part_ww[blockIdx.x] = t;
+    }
+}
+
+// partials of r.r (set-up)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_gm_rr(const T *__restrict__ r, uint64_t n, T *__restrict__ part) {
+    GM_SWEEP_HEAD;
+    T acc = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        const VT rv = GM_LOAD(r, q);
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(rv[e], rv[e]));
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) acc = p_add(acc, p_mul(r[i], r[i]));
+    const T t = block_sum1(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// V0 false: v_j = w / hn (w itself when hn == 0), to its column and to vin.  V0 true: v_0 = r / beta, the same two places
+template <typename T, bool V0>
+__global__ void __launch_bounds__(kBlock)
+k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__restrict__ basis, uint64_t ld, T *__restrict__ vin, uint64_t n) {
+    if (!(V0 ? mo->do_v0 : mo->do_norm)) return;
+    const T d = V0 ? mo->beta : mo->hn;
+    const bool copy = !V0 && d == T(0);
+    T *__restrict__ colp = basis + (V0 ? (uint64_t)0 : (uint64_t)mo->j * ld);  // (the step has advanced j: at most m)
+    GM_SWEEP_HEAD;
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT v = GM_LOAD(src, q);
+        if (!copy) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[e] = p_div(v[e], d);
+        }
+        GM_STORE(v, colp, q);
+        GM_STORE(v, vin, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        const T v = copy ? src[i] : p_div(src[i], d);
+        colp[i] = v;
+        vin[i] = v;
+    }
+}
+
+// the cycle end: x += sum v_c y_c (c < j), r = sum v_c z_c (c <= j), the partials of r.r
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ x, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr) {
+    if (!mo->do_end) return;
+    const unsigned j = mo->j;  // >= 1
+    const T *__restrict__ y = mo->y, *__restrict__ z = mo->z;
+    GM_SWEEP_HEAD;
+    T acc = T(0);
+    for (uint64_t q = tid; q < nv; q += nthreads) {
+        VT xv = GM_LOAD(x, q);
+        VT rv;
+        {
+            const VT vv = GM_LOAD(basis, q);
+            const T y0 = y[0], z0 = z[0];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                xv[e] = p_add(xv[e], p_mul(vv[e], y0));
+                rv[e] = p_mul(vv[e], z0);
+            }
+        }
+#pragma unroll 4
+        for (unsigned c = 1; c < j; ++c) {
+            const VT vv = GM_LOAD(basis + (uint64_t)c * ld, q);
+            const T yc = y[c], zc = z[c];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                xv[e] = p_add(xv[e], p_mul(vv[e], yc));
+                rv[e] = p_add(rv[e], p_mul(vv[e], zc));
+            }
+        }
+        {
+            const VT vv = GM_LOAD(basis + (uint64_t)j * ld, q);
+            const T zj = z[j];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                rv[e] = p_add(rv[e], p_mul(vv[e], zj));
+                acc = p_add(acc, p_mul(rv[e], rv[e]));
+            }
+        }
+        GM_STORE(xv, x, q);
+        GM_STORE(rv, r, q);
+    }
+    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
+        T xi = p_add(x[i], p_mul(basis[i], y[0]));
+        T ri = p_mul(basis[i], z[0]);
+        for (unsigned c = 1; c < j; ++c) {
+            const T v = basis[(uint64_t)c * ld + i];
+            xi = p_add(xi, p_mul(v, y[c]));
+            ri = p_add(ri, p_mul(v, z[c]));
+        }
+        ri = p_add(ri, p_mul(basis[(uint64_t)j * ld + i], z[j]));
+        x[i] = xi;
+        r[i] = ri;
+        acc = p_add(acc, p_mul(ri, ri));
+    }
+    const T t = block_sum1(acc);
+    if (threadIdx.x == 0) part_rr[blockIdx.x] = t;
+}
+
+// ---- the one-workgroup kernels ----------------------------------------------------------------------------------------------------
+// rr = r.r.  SETUP: of the initial residual, and the first cycle begins.  Else: of the rebuilt one, and on a restart the next begins.
+// beta = sqrt(rr);  beta == 0: stop, breakdown 2;  else g = (beta), j = 0, cycles += 1, v_0 is due
+template <typename T, bool SETUP>
+__global__ void __launch_bounds__(kBlock) k_gm_begin(GmScalars<T> *sc, GmMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
+    if (!SETUP && !mo->do_end) return;
+    const T rr = gm_fold1(part, n_parts);
+    if (threadIdx.x == 0) {
+        sc->rr = rr;
+        mo->do_v0 = 0;
+        if (SETUP || mo->restart) {
+            const T beta = p_sqrt(rr);
+            if (beta == T(0)) {
+                mo->breakdown = 2;
+                sc->converged = 1;
+            } else {
+                mo->beta = beta;
+                mo->g[0] = beta;
+                mo->j = 0;
+                mo->cycles += 1;
+                mo->do_v0 = 1;
+            }
+        }
+    }
+}
+
+// the body's sequential part: decides whether the body counts, folds w.w, the rotations, the decisions, y and z at a cycle end
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> *mo, const T *__restrict__ part_ww, unsigned n_parts) {
+    if (!gm_enters(sc)) {  // (every thread reads before thread 0 writes: the fold below has a barrier)
+        if (threadIdx.x == 0) mo->do_norm = mo->do_end = mo->do_v0 = 0;
+        return;
+    }
+    const T ww = gm_fold1(part_ww, n_parts);
+    if (threadIdx.x != 0) return;
+    const uint64_t iters = sc->iters + 1;
+    sc->iters = iters;
+    unsigned j = mo->j;
+    T *h = mo->h1;
+    for (unsigned c = 0; c <= j; ++c) h[c] = p_add(mo->h1[c], mo->h2[c]);
+    const T hn = p_sqrt(ww);
+    for (unsigned i = 0; i < j; ++i) {
+        const T ci = mo->c[i], si = mo->s[i], a = h[i], b = h[i + 1];
+        h[i] = p_add(p_mul(ci, a), p_mul(si, b));
+        h[i + 1] = p_add(p_mul(-si, a), p_mul(ci, b));
+    }
+    const T hj = h[j];
+    const T d = p_sqrt(p_add(p_mul(hj, hj), p_mul(hn, hn)));
+    const T cj = p_div(hj, d), sj = p_div(hn, d);
+    mo->c[j] = cj;
+    mo->s[j] = sj;
+    T *Rj = mo->R + (size_t)j * kGmMaxM;
+    for (unsigned i = 0; i < j; ++i) Rj[i] = h[i];
+    Rj[j] = p_add(p_mul(cj, hj), p_mul(sj, hn));
+    const T gj = mo->g[j];
+    const T gn = p_mul(-sj, gj);
+    mo->g[j + 1] = gn;
+    mo->g[j] = p_mul(cj, gj);
+    j += 1;
+    mo->j = j;
+    mo->hn = hn;
+    mo->do_norm = 1;
+    mo->do_v0 = 0;
+    const bool exhausted = hn == T(0), conv = fabs((double)gn) < sc->tol, last = iters == sc->iter_max, full = j == mo->m;
+    const bool stop = exhausted || conv || last;
+    if (!(stop || full)) {
+        mo->do_end = 0;
+        return;
+    }
+    mo->do_end = 1;
+    mo->restart = stop ? 0 : 1;
+    if (exhausted) mo->breakdown = 1;
+    if (stop) sc->converged = 1;
+    // R y = g[0 .. j)
+    for (int i = (int)j - 1; i >= 0; --i) {
+        T a = mo->g[i];
+        for (unsigned k = i + 1; k < j; ++k) a = p_add(a, -p_mul(mo->R[(size_t)k * kGmMaxM + i], mo->y[k]));
+        mo->y[i] = p_div(a, mo->R[(size_t)i * kGmMaxM + i]);
+    }
+    // z = Omega_0^T .. Omega_{j-1}^T (g_j e_j)
+    for (unsigned i = 0; i < j; ++i) mo->z[i] = T(0);
+    mo->z[j] = gn;
+    for (int i = (int)j - 1; i >= 0; --i) {
+        const T ci = mo->c[i], si = mo->s[i], a = mo->z[i], b = mo->z[i + 1];
+        mo->z[i] = p_add(p_mul(ci, a), p_mul(-si, b));
+        mo->z[i + 1] = p_add(p_mul(si, a), p_mul(ci, b));
+    }
+}
+
+// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
+template <typename T>
+int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant, size_t check_every,
+            size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    constexpr size_t V = 16 / sizeof(T);
+    SolveRun run;  // (its `converged` means STOPPED here)
+    int breakdown = 0;
+    size_t cycles = 0;
+    const unsigned grid = pcg_grid(n);
+    const uint64_t ld = (n + V - 1) / V * V;
+    const int rc = run.run([&]() -> int {
+        SMH_TRY(run.own_stream());
+        const hipStream_t s = run.s;
+        Scratch &ws = run.ws;
+        T *x = nullptr, *r = nullptr, *w = nullptr, *vin = nullptr, *basis = nullptr, *part = nullptr, *part_ww = nullptr;
+        GmScalars<T> *sc = nullptr;
+        GmMore<T> *mo = nullptr;
+        SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&w, n)); SMH_TRY(ws.alloc(&vin, n));
+        SMH_TRY(ws.alloc(&basis, (restart + 1) * (size_t)ld));
+        SMH_TRY(ws.alloc(&part, (restart + 1) * (size_t)kPcgBlocks));
+        SMH_TRY(ws.alloc(&part_ww, (size_t)kPcgBlocks));
+        SMH_TRY(ws.alloc(&sc, 1));
+        SMH_TRY(ws.alloc(&mo, 1));
+        constexpr size_t more_head = offsetof(GmMore<T>, hn);
+        SMH_TRY(run.h_sc.alloc(sizeof(GmScalars<T>) + more_head, hipHostMallocDefault));
+        // r = b - A x (w: scratch); rr = r.r; beta; v_0
+        hipLaunchKernelGGL((k_gm_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max, (uint32_t)restart);
+        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, r, x, w, s));
+        hipLaunchKernelGGL((k_gm_rr<T>), dim3(grid), dim3(kBlock), 0, s, r, (uint64_t)n, part_ww);
+        hipLaunchKernelGGL((k_gm_begin<T, true>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
+        hipLaunchKernelGGL((k_gm_norm<T, true>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n);
+        SMH_HIP(hipGetLastError());
+        const dim3 cols((unsigned)restart + 1);
+        auto body = [&]() -> int {
+            SMH_TRY(spmv_enqueue(m, vin, n, w, variant, s));
+            hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_gm_fold<T, 1>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
+            hipLaunchKernelGGL((k_gm_update<T, 1>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_gm_fold<T, 2>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
+            hipLaunchKernelGGL((k_gm_update<T, 2>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gm_step<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
+            hipLaunchKernelGGL((k_gm_norm<T, false>), dim3(grid), dim3(kBlock), 0, s, mo, w, basis, ld, vin, (uint64_t)n);
+            hipLaunchKernelGGL((k_gm_xr<T>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gm_begin<T, false>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
+            hipLaunchKernelGGL((k_gm_norm<T, true>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n);
+            SMH_HIP(hipGetLastError());
+            return SMH_OK;
+        };
+        SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        GmMore<T> *h_mo = (GmMore<T> *)((char *)run.h_sc.get() + sizeof(GmScalars<T>));  // (its head alone)
+        SMH_HIP(hipMemcpyAsync(h_mo, mo, more_head, hipMemcpyDeviceToHost, s));
+        if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
+        SMH_HIP(hipStreamSynchronize(s));
+        breakdown = (int)h_mo->breakdown;
+        cycles = (size_t)h_mo->cycles;
+        return SMH_OK;
+    }, iters_out, rr_out);
+    if (rc == SMH_OK && breakdown_out) *breakdown_out = breakdown;
+    if (rc == SMH_OK && cycles_out) *cycles_out = cycles;
+    return rc;
+}
+
+int gmres(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant, size_t check_every,
+          size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    if (m->dtype == SMH_F64)
+        return gmres_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out,
+                               cycles_out, breakdown_out);
+    return gmres_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
+                          breakdown_out);
+}
+
+constexpr size_t kGmCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
+
+}  // namespace
+
+// the statuses are decided here (solver_host.hpp), before any launch: BiCGSTAB's, then the range of `restart`
+extern "C" int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart, int variant,
+                                   size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres(m, b->d, x->d, m->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+}
+
+extern "C" int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
+                               size_t restart, int variant, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres(m, b_host, x_host_inout, m->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out, breakdown_out);
+}

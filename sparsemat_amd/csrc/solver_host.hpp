@@ -1,4 +1,4 @@
-// solver_host.hpp -- what the host side of the device-resident solvers shares (cg.hip, cg_many.hip, pcg.hip, bicgstab.hip and their
+// solver_host.hpp -- what the host side of the device-resident solvers shares (cg.hip, cg_many.hip, pcg.hip, bicgstab.hip, gmres.hip and their
 // entry points): the argument checks of the entry points and the skeleton of a solve around solve_in_batches (internal.hpp).
 // A solver is its allocations, its set-up launches, a body lambda and SolveRun::run; the kernels are its own file's.
 #pragma once
@@ -41,7 +41,7 @@ int check_solve_vec(const smh_crs *m, const V *b, const V *x, const char *dtype_
 }
 
 // The host form.  null_vectors: the entry point refuses a NULL vector of n > 0 itself (smh_cg_solve leaves that to the upload);
-// refuse_aliased: ... and b_host == x_host (smh_bicgstab_solve alone).
+// refuse_aliased: ... and b_host == x_host (smh_bicgstab_solve and smh_gmres_solve alone).
 inline int check_solve_host(const smh_crs *m, const void *b_host, size_t b_len, const void *x_host, size_t x_len, bool null_vectors,
                             bool refuse_aliased, const smh_crs *factor = nullptr) {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
@@ -51,6 +51,13 @@ inline int check_solve_host(const smh_crs *m, const void *b_host, size_t b_len, 
     if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
     if (null_vectors && n && (!b_host || !x_host)) return fail(SMH_ERR_INVALID, "NULL host vector");
     if (refuse_aliased && n && b_host == x_host) return fail(SMH_ERR_INVALID, "b and x are the same storage");
+    return SMH_OK;
+}
+
+// GMRES's restart length, after the checks above: 0 stands for default_restart, anything above max_restart is refused
+inline int check_solve_restart(size_t *restart, size_t default_restart, size_t max_restart) {
+    if (*restart == 0) *restart = default_restart;
+    if (*restart > max_restart) return fail(SMH_ERR_INVALID, "restart is %zu: it must be at most %zu (0: the default, %zu)", *restart, max_restart, default_restart);
     return SMH_OK;
 }
 

@@ -14,6 +14,8 @@
                                solves on a factor computed on the device.
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
                                device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
+* ``GMRES``                 -- an extension for non-symmetric systems: restarted GMRES(m), the robust companion of ``BiCGStab``
+                               (``smh_gmres_solve*``); its Krylov basis stays on the device.
 """
 import math
 
@@ -38,21 +40,21 @@ class _DeviceSolver:
         self.iterations = None  # loop bodies entered by the last solve
         self.r_norm_squared = None  # last r.r (as f64)
 
-    def _solve(self, vec_fn, host_fn, mat, b, x, handles=(), extra_out=()):
+    def _solve(self, vec_fn, host_fn, mat, b, x, handles=(), extra_out=(), extra_in=()):
         """Two ``DenseVec``s go to ``vec_fn`` (None: the solver has no such form), anything else to ``host_fn`` as an array-like b and
         a contiguous numpy x of the matrix dtype, updated in place.  ``handles``: what the call takes after the matrix;
-        ``extra_out``: ctypes out-parameters after iters and rr.  Sets ``iterations`` and ``r_norm_squared``."""
+        ``extra_out``: ctypes out-parameters after iters and rr; ``extra_in``: what the call takes after iter_max.  Sets ``iterations`` and ``r_norm_squared``."""
         iters, rr = C.c_size_t(), C.c_double()
         out = [C.byref(iters), C.byref(rr)] + [C.byref(o) for o in extra_out]
         var = _lib.VARIANTS[self.variant]
         if vec_fn is not None and isinstance(b, DenseVec) and isinstance(x, DenseVec):
-            check(vec_fn(mat._h, *handles, b._h, x._h, self.tol, self.iter_max, var, self.check_every, *out))
+            check(vec_fn(mat._h, *handles, b._h, x._h, self.tol, self.iter_max, *extra_in, var, self.check_every, *out))
         else:
             if not (isinstance(x, np.ndarray) and x.dtype == mat.dtype and x.flags.c_contiguous):
                 raise TypeError("x must be a contiguous numpy array of the matrix dtype (updated in place)")
             bb = np.ascontiguousarray(b, dtype=mat.dtype)
             check(host_fn(mat._h, *handles, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None, x.size,
-                          self.tol, self.iter_max, var, *out))
+                          self.tol, self.iter_max, *extra_in, var, *out))
         self.iterations, self.r_norm_squared = iters.value, rr.value
         return x
 
@@ -167,4 +169,30 @@ class BiCGStab(_DeviceSolver):
         self.breakdown = brk.value
         # every entered body that ends without a breakdown has tested the r.r it reports: under tol means that test stopped the loop
         self.converged = self.breakdown == 0 and self.iterations > 0 and math.sqrt(self.r_norm_squared) < self.tol
+        return x
+
+
+class GMRES(_DeviceSolver):
+    """Restarted GMRES(m) (Saad & Schultz, unpreconditioned) for non-symmetric systems -- an EXTENSION, the robust companion of
+    ``BiCGStab``: it cannot break down before the Krylov space is exhausted and does not stagnate on a spectrum near the
+    imaginary axis; a body is one product and sweeps over a device-resident basis of up to ``restart`` + 1 vectors
+    (``smh_gmres_solve*``).  ``restart``: 1 .. 128 (0: the library's default, 30).  Same guards and panics as ``BiCGStab``.
+
+    After ``solve``: ``iterations`` (bodies entered), ``r_norm_squared`` (the r.r of the residual rebuilt from the basis at the
+    last cycle end -- no product is spent on it --, the initial residual's before the first; as f64), ``cycles`` (the number of
+    times a v_0 was formed) and ``breakdown`` (0 none; 1 the Krylov space is exhausted: x is updated from it; 2 the residual
+    at a cycle's start is exactly zero: x is the solution as it stands)."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, restart=30, variant="auto", check_every=0):
+        super().__init__(tol, iter_max, variant, check_every)
+        self.restart = int(restart)
+        self.cycles = None
+        self.breakdown = None
+
+    def solve(self, mat, b, x):
+        """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
+        SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
+        cycles, brk = C.c_size_t(), C.c_int()
+        self._solve(lib().smh_gmres_solve_vec, lib().smh_gmres_solve, mat, b, x, extra_out=(cycles, brk), extra_in=(self.restart,))
+        self.cycles, self.breakdown = cycles.value, brk.value
         return x
