@@ -23,9 +23,8 @@
 // breakdown code) that the host reads once after the loop.  Gate words: `active` (this body runs; dropped by the stage that
 // stops) gates every sweep after alpha; `xmode` tells the x / r sweep what is due (0 nothing, 1 x += p*alpha alone, 2 all).
 // Bodies enqueued past the stop are no-ops, so x, rr, iters and the code are the stopping body's wherever it falls in a batch.
-// Reductions: pcg.hip's tree everywhere -- a thread's strided run over 16-byte vectors and then its tail element, the
-// __shfl_down butterfly per wave, thread 0 over the four wave sums from the first one's, one workgroup over the partials the
-// same way -- deterministic, no float atomics.  One stream, one linear chain of launches.
+// Sweeps and reductions: solver_tree.hpp's everywhere -- its sweep, its workgroup sums, fold1 / fold2 over the partials --
+// deterministic, no float atomics.  One stream, one linear chain of launches.
 // Host side: the driver (bicgstab_t) is its allocations, its set-up launches, the body lambda and SolveRun::run (solver_host.hpp:
 // the stream of its own, the workspaces, the drain, r = b - A x); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
@@ -51,11 +50,7 @@ struct BiScalars {
     uint64_t iter_max;
     double tol;
 };
-template <typename T> constexpr bool bi_scalars_like_cg() {
-    return sizeof(BiScalars<T>) == sizeof(CgScalars<T>) && offsetof(BiScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
-           offsetof(BiScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(BiScalars<T>, iters) == offsetof(CgScalars<T>, iters);
-}
-static_assert(bi_scalars_like_cg<float>() && bi_scalars_like_cg<double>(), "BiScalars and CgScalars have drifted apart");
+static_assert(scalars_like_cg<BiScalars>(), "BiScalars and CgScalars have drifted apart");
 // the solver's further scalars: read by the host once, after the loop
 template <typename T>
 struct BiMore {
@@ -75,43 +70,13 @@ __global__ void k_bi_init(BiScalars<T> *sc, BiMore<T> *mo, double tol, uint64_t 
     mo->breakdown = mo->pad_ = 0;
 }
 
-// one workgroup: the sums of part_a[0..n_parts) and part_b[0..n_parts) in out2[0], out2[1] (thread 0 writes, thread 0 reads)
-template <typename T>
-__device__ __forceinline__ void fold2(const T *__restrict__ part_a, const T *__restrict__ part_b, unsigned n_parts, T *out2) {
-    T a = T(0), b = T(0);
-    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) { a = p_add(a, part_a[k]); b = p_add(b, part_b[k]); }
-    block_sums(a, b, out2, out2 + 1);  // (one block: blockIdx.x == 0)
-}
-template <typename T>
-__device__ __forceinline__ T fold1(const T *__restrict__ part, unsigned n_parts) {
-    T a = T(0);
-    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
-    return block_sum1(a);  // (thread 0)
-}
-
-// ---- the sweeps: 16 bytes per lane and array (the workspaces are pool allocations: aligned), the last n % V elements one by one --
-#define BI_SWEEP_HEAD                                  \
-    constexpr int V = 16 / sizeof(T);                  \
-    typedef T VT __attribute__((ext_vector_type(V))); \
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x
-#define BI_LOAD(p, q) __builtin_nontemporal_load(reinterpret_cast<const VT *>(p) + (q))
-#define BI_STORE(v, p, q) __builtin_nontemporal_store((v), reinterpret_cast<VT *>(p) + (q))
-
+// ---- the sweeps (solver_tree.hpp's sweep: the workspaces are pool allocations, aligned) ---------------------------------------------
 // partials of a.b (r^.v): runs when the body that follows will be entered
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
 k_bi_dot(const BiScalars<T> *__restrict__ sc, const T *__restrict__ a, const T *__restrict__ b, uint64_t n, T *__restrict__ part) {
     if (sc->converged || sc->iters >= sc->iter_max) return;  // block-uniform
-    BI_SWEEP_HEAD;
-    T acc = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        const VT av = BI_LOAD(a, q), bv = BI_LOAD(b, q);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(av[e], bv[e]));
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) acc = p_add(acc, p_mul(a[i], b[i]));
-    const T t = block_sum1(acc);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    block_partial(sweep_dot(a, b, n), part);
 }
 
 // partials of t.s and t.t in one sweep.  SETUP (t = s = r): the initial rho = r^.r and r.r, ungated
@@ -120,21 +85,15 @@ __global__ void __launch_bounds__(kBlock)
 k_bi_dot2(const BiScalars<T> *__restrict__ sc, const T *__restrict__ t, const T *__restrict__ s, uint64_t n, T *__restrict__ part_ts,
           T *__restrict__ part_tt) {
     if (!SETUP && !sc->active) return;
-    BI_SWEEP_HEAD;
     T a_ts = T(0), a_tt = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        const VT tv = BI_LOAD(t, q), sv = BI_LOAD(s, q);
+    sweep<T>(n, [&](auto at) {
+        const auto tv = at.load(t), sv = at.load(s);
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
+        for (int e = 0; e < at.width; ++e) {
             a_ts = p_add(a_ts, p_mul(tv[e], sv[e]));
             a_tt = p_add(a_tt, p_mul(tv[e], tv[e]));
         }
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        const T ti = t[i];
-        a_ts = p_add(a_ts, p_mul(ti, s[i]));
-        a_tt = p_add(a_tt, p_mul(ti, ti));
-    }
+    });
     block_sums(a_ts, a_tt, part_ts, part_tt);
 }
 
@@ -144,25 +103,18 @@ __global__ void __launch_bounds__(kBlock)
 k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__restrict__ v, T *__restrict__ s, uint64_t n, T *__restrict__ part_ss) {
     if (!sc->active) return;
     const T alpha = sc->alpha;
-    BI_SWEEP_HEAD;
     T acc = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT sv = BI_LOAD(r, q);
-        const VT vv = BI_LOAD(v, q);
+    sweep<T>(n, [&](auto at) {
+        auto sv = at.load(r);
+        const auto vv = at.load(v);
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
+        for (int e = 0; e < at.width; ++e) {
             sv[e] = p_add(sv[e], -p_mul(vv[e], alpha));
             acc = p_add(acc, p_mul(sv[e], sv[e]));
         }
-        BI_STORE(sv, s, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        const T si = p_add(r[i], -p_mul(v[i], alpha));
-        s[i] = si;
-        acc = p_add(acc, p_mul(si, si));
-    }
-    const T t = block_sum1(acc);
-    if (threadIdx.x == 0) part_ss[blockIdx.x] = t;
+        at.store(s, sv);
+    });
+    block_partial(acc, part_ss);
 }
 
 // xmode 2: x = (x + p*alpha) + s*omega; r = s - t*omega; partials of r.r and r^.r.  xmode 1 (half-step stop, breakdown 3): x += p*alpha
@@ -173,42 +125,32 @@ k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T
     const uint32_t mode = sc->xmode;  // block-uniform
     if (mode == 0) return;
     const T alpha = sc->alpha;
-    BI_SWEEP_HEAD;
     if (mode == 1) {
-        for (uint64_t q = tid; q < nv; q += nthreads) {
-            VT xv = BI_LOAD(x, q);
-            const VT pv = BI_LOAD(p, q);
+        sweep<T>(n, [&](auto at) {
+            auto xv = at.load(x);
+            const auto pv = at.load(p);
 #pragma unroll
-            for (int e = 0; e < V; ++e) xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
-            BI_STORE(xv, x, q);
-        }
-        for (uint64_t i = nv * V + tid; i < n; i += nthreads) x[i] = p_add(x[i], p_mul(p[i], alpha));
+            for (int e = 0; e < at.width; ++e) xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
+            at.store(x, xv);
+        });
         return;
     }
     const T omega = mo->omega;
     T a_rr = T(0), a_rho = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT xv = BI_LOAD(x, q);
-        const VT pv = BI_LOAD(p, q), sv = BI_LOAD(s, q), tv = BI_LOAD(t, q), hv = BI_LOAD(rhat, q);
-        VT rv;
+    sweep<T>(n, [&](auto at) {
+        auto xv = at.load(x);
+        const auto pv = at.load(p), sv = at.load(s), tv = at.load(t), hv = at.load(rhat);
+        typename decltype(at)::pack rv;
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
+        for (int e = 0; e < at.width; ++e) {
             xv[e] = p_add(p_add(xv[e], p_mul(pv[e], alpha)), p_mul(sv[e], omega));
             rv[e] = p_add(sv[e], -p_mul(tv[e], omega));
             a_rr = p_add(a_rr, p_mul(rv[e], rv[e]));
             a_rho = p_add(a_rho, p_mul(hv[e], rv[e]));
         }
-        BI_STORE(xv, x, q);
-        BI_STORE(rv, r, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        const T si = s[i];
-        x[i] = p_add(p_add(x[i], p_mul(p[i], alpha)), p_mul(si, omega));
-        const T ri = p_add(si, -p_mul(t[i], omega));
-        r[i] = ri;
-        a_rr = p_add(a_rr, p_mul(ri, ri));
-        a_rho = p_add(a_rho, p_mul(rhat[i], ri));
-    }
+        at.store(x, xv);
+        at.store(r, rv);
+    });
     block_sums(a_rr, a_rho, part_rr, part_rho);
 }
 
@@ -218,15 +160,13 @@ __global__ void __launch_bounds__(kBlock)
 k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ v, uint64_t n) {
     if (!sc->active) return;
     const T beta = sc->beta, omega = mo->omega;
-    BI_SWEEP_HEAD;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT pv = BI_LOAD(p, q);
-        const VT rv = BI_LOAD(r, q), vv = BI_LOAD(v, q);
+    sweep<T>(n, [&](auto at) {
+        auto pv = at.load(p);
+        const auto rv = at.load(r), vv = at.load(v);
 #pragma unroll
-        for (int e = 0; e < V; ++e) pv[e] = p_add(rv[e], p_mul(p_add(pv[e], -p_mul(vv[e], omega)), beta));
-        BI_STORE(pv, p, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) p[i] = p_add(r[i], p_mul(p_add(p[i], -p_mul(v[i], omega)), beta));
+        for (int e = 0; e < at.width; ++e) pv[e] = p_add(rv[e], p_mul(p_add(pv[e], -p_mul(vv[e], omega)), beta));
+        at.store(p, pv);
+    });
 }
 
 // ---- the one-workgroup kernels between the sweeps -----------------------------------------------------------------------

@@ -22,19 +22,18 @@
 // kernels are no-ops, so the host may enqueue iterations in batches and poll the flag lazily:
 // x, r, p are exactly those of the iteration in which the reference would have left its loop.
 // Element-wise updates round the product and the sum separately (bit-identical to the reference
-// for equal alpha/beta); the reductions are fixed trees (bitwise reproducible).
+// for equal alpha/beta); the reductions are fixed trees (bitwise reproducible).  The two sweeps (cg_update_body, cg_p_body) are
+// written once on solver_tree.hpp's sweep, by 16 bytes or by element as the host found the pointers aligned; the tree here
+// (cg_block_sum, cg_fold_everywhere: plain +, thread 0 from zero) is this file's own, not solver_tree.hpp's.
 //
 // The single-matrix driver (cg_solve, behind smh_cg_solve_vec) is at the end of the first half of this file: its allocations, its
 // set-up launches, the body lambda and SolveRun::run on the handle's stream (solver_host.hpp, which every device-resident solver
 // runs: the workspaces, the drain, and through solve_in_batches of internal.hpp the batches of bodies, the hipGraph, the polls).
 #include "internal.hpp"
 #include "solver_host.hpp"
+#include "solver_tree.hpp"
 
 namespace smh {
-
-template <typename T> struct CgVec;
-template <> struct CgVec<float> { typedef float type __attribute__((ext_vector_type(4))); static constexpr int N = 4; };
-template <> struct CgVec<double> { typedef double type __attribute__((ext_vector_type(2))); static constexpr int N = 2; };
 
 __device__ __forceinline__ float cg_mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ double cg_mul(double a, double b) { return __dmul_rn(a, b); }
@@ -94,37 +93,17 @@ __global__ void __launch_bounds__(kBlock) k_cg_set_rr(CgScalars<T> *sc, const T 
 // r -= round(Ap * alpha) on [0, n), partials[blockIdx.x] = this workgroup's share of r.r   (linearsolver.rs:49-51)
 template <typename T, bool VEC>
 __device__ __forceinline__ void cg_update_body(T alpha, T *__restrict__ r, const T *__restrict__ ap, uint64_t n, T *__restrict__ partials, T *s_w) {
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     T acc = T(0);
-    if constexpr (VEC) {
-        typedef typename CgVec<T>::type V;
-        constexpr int N = CgVec<T>::N;
-        const uint64_t nv = n / N;
-        V *rv = reinterpret_cast<V *>(r);
-        const V *apv = reinterpret_cast<const V *>(ap);
-        for (uint64_t i = tid; i < nv; i += nthreads) {
-            V rr = __builtin_nontemporal_load(rv + i);  // (streams far larger than the caches: the non-temporal forms move 13 % more, blas1.hip)
-            const V aa = __builtin_nontemporal_load(apv + i);
+    sweep<T, VEC ? kBy16Bytes : kByElement>(n, [&](auto at) {  // (streams far larger than the caches: the non-temporal forms move 13 % more, blas1.hip)
+        auto rr = at.load(r);
+        const auto aa = at.load(ap);
 #pragma unroll
-            for (int e = 0; e < N; ++e) {
-                rr[e] = cg_sub(rr[e], cg_mul(aa[e], alpha));  // r -= mat_p * alpha        :49
-                acc += rr[e] * rr[e];                         // r.norm_squared()          :51
-            }
-            __builtin_nontemporal_store(rr, rv + i);
+        for (int e = 0; e < at.width; ++e) {
+            rr[e] = cg_sub(rr[e], cg_mul(aa[e], alpha));  // r -= mat_p * alpha        :49
+            acc += rr[e] * rr[e];                         // r.norm_squared()          :51
         }
-        for (uint64_t i = nv * N + tid; i < n; i += nthreads) {
-            const T t = cg_sub(r[i], cg_mul(ap[i], alpha));
-            r[i] = t;
-            acc += t * t;
-        }
-    } else {
-        for (uint64_t i = tid; i < n; i += nthreads) {
-            const T t = cg_sub(r[i], cg_mul(ap[i], alpha));
-            r[i] = t;
-            acc += t * t;
-        }
-    }
+        at.store(r, rr);
+    });
     const T s = cg_block_sum<T>(acc, s_w);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
@@ -132,45 +111,27 @@ __device__ __forceinline__ void cg_update_body(T alpha, T *__restrict__ r, const
 // x += round(p * alpha) (:47) and, when `rebuild`, p = round(p * beta) + r (:58-59), on [0, n)
 template <typename T, bool VEC>
 __device__ __forceinline__ void cg_p_body(bool rebuild, T alpha, T beta, T *__restrict__ p, const T *__restrict__ r, T *__restrict__ x, uint64_t n) {
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
-    if constexpr (VEC) {
-        typedef typename CgVec<T>::type V;
-        constexpr int N = CgVec<T>::N;
-        const uint64_t nv = n / N;
-        V *pv = reinterpret_cast<V *>(p);
-        V *xv = reinterpret_cast<V *>(x);
-        const V *rv = reinterpret_cast<const V *>(r);
-        if (rebuild) {
-            for (uint64_t i = tid; i < nv; i += nthreads) {
-                V pp = __builtin_nontemporal_load(pv + i), xx = __builtin_nontemporal_load(xv + i);
-                const V rr = __builtin_nontemporal_load(rv + i);
+    constexpr SweepWidth W = VEC ? kBy16Bytes : kByElement;
+    if (rebuild) {
+        sweep<T, W>(n, [&](auto at) {
+            auto pp = at.load(p), xx = at.load(x);
+            const auto rr = at.load(r);
 #pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    xx[e] = cg_add(xx[e], cg_mul(pp[e], alpha));  // *x += p.clone() * alpha        :47
-                    pp[e] = cg_add(cg_mul(pp[e], beta), rr[e]);   // p.scale(beta); p.add(&r)       :58-59
-                }
-                __builtin_nontemporal_store(xx, xv + i);
-                __builtin_nontemporal_store(pp, pv + i);
+            for (int e = 0; e < at.width; ++e) {
+                xx[e] = cg_add(xx[e], cg_mul(pp[e], alpha));  // *x += p.clone() * alpha        :47
+                pp[e] = cg_add(cg_mul(pp[e], beta), rr[e]);   // p.scale(beta); p.add(&r)       :58-59
             }
-        } else {
-            for (uint64_t i = tid; i < nv; i += nthreads) {
-                V xx = __builtin_nontemporal_load(xv + i);
-                const V pp = __builtin_nontemporal_load(pv + i);
-#pragma unroll
-                for (int e = 0; e < N; ++e) xx[e] = cg_add(xx[e], cg_mul(pp[e], alpha));
-                __builtin_nontemporal_store(xx, xv + i);
-            }
-        }
-        for (uint64_t i = nv * N + tid; i < n; i += nthreads) {
-            x[i] = cg_add(x[i], cg_mul(p[i], alpha));
-            if (rebuild) p[i] = cg_add(cg_mul(p[i], beta), r[i]);
-        }
+            at.store(x, xx);
+            at.store(p, pp);
+        });
     } else {
-        for (uint64_t i = tid; i < n; i += nthreads) {
-            x[i] = cg_add(x[i], cg_mul(p[i], alpha));
-            if (rebuild) p[i] = cg_add(cg_mul(p[i], beta), r[i]);
-        }
+        sweep<T, W>(n, [&](auto at) {
+            auto xx = at.load(x);
+            const auto pp = at.load(p);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) xx[e] = cg_add(xx[e], cg_mul(pp[e], alpha));
+            at.store(x, xx);
+        });
     }
 }
 
@@ -287,7 +248,7 @@ static int launch_cg_update(bool vec, unsigned cap, const void *sc_in, void *sc_
 template <typename T>
 static int launch_cg_p(bool vec, uint64_t cap, const void *sc_in, void *sc_out, const T *rr_vals, uint32_t nb, T *p, const T *r, T *x, size_t n,
                        hipStream_t s) {
-    uint64_t pb = (n / CgVec<T>::N + kBlock) / kBlock;
+    uint64_t pb = (n / (16 / sizeof(T)) + kBlock) / kBlock;  // (one 16-byte vector per thread)
     if (pb > cap) pb = cap;
     if (vec)
         hipLaunchKernelGGL((k_cg_par_p<T, true>), dim3((unsigned)pb), dim3(kBlock), 0, s, (const CgScalars<T> *)sc_in, (CgScalars<T> *)sc_out, rr_vals, nb, p, r, x, (uint64_t)n);

@@ -42,7 +42,8 @@
 // the step (one workgroup: folds w.w, thread 0 does the rotations and the decisions and, at a cycle end, y and z); the
 // normalisation (1 read, 2 written): (4 j + 13) n values, (2 m + 11) n averaged over a full cycle.  A cycle end adds one sweep over
 // the basis that forms x and r with the partials of r.r ((j + 2) read, 2 written), its fold, and on a restart v_0 (1 read, 2 written).
-// The dots: w's 16-byte vector is loaded once per tile of kGmTile = 8 columns, one accumulator per column; every column is summed by
+// Every sweep is solver_tree.hpp's sweep, a column of the basis being one more array to load from.
+// The dots: w's pack is loaded once per tile of kGmTile = 8 columns, one accumulator per column; every column is summed by
 // solver_tree.hpp's tree on pcg_grid(n) -- cg_model.Reducer.dot(., ., "pcg") -- so the tile width changes no bit.
 // All state is on the device: a leading block in CgScalars' layout (solve_in_batches polls it; `converged` means STOPPED) and a
 // second block (GmMore).  The kernels read the column count from it; a sweep that is not due returns at once: the Gram-Schmidt
@@ -72,11 +73,7 @@ struct GmScalars {
     uint64_t iter_max;
     double tol;
 };
-template <typename T> constexpr bool gm_scalars_like_cg() {
-    return sizeof(GmScalars<T>) == sizeof(CgScalars<T>) && offsetof(GmScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
-           offsetof(GmScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(GmScalars<T>, iters) == offsetof(CgScalars<T>, iters);
-}
-static_assert(gm_scalars_like_cg<float>() && gm_scalars_like_cg<double>(), "GmScalars and CgScalars have drifted apart");
+static_assert(scalars_like_cg<GmScalars>(), "GmScalars and CgScalars have drifted apart");
 
 // the solver's further state; the host reads the words before `hn` once, after the loop
 template <typename T>
@@ -110,20 +107,6 @@ __global__ void k_gm_init(GmScalars<T> *sc, GmMore<T> *mo, double tol, uint64_t 
     mo->hn = mo->beta = T(0);
 }
 
-template <typename T>
-__device__ __forceinline__ T gm_fold1(const T *__restrict__ part, unsigned n_parts) {
-    T a = T(0);
-    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
-    return block_sum1(a);  // (thread 0)
-}
-
-#define GM_SWEEP_HEAD                                  \
-    constexpr int V = 16 / sizeof(T);                  \
-    typedef T VT __attribute__((ext_vector_type(V))); \
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x
-#define GM_LOAD(p, q) __builtin_nontemporal_load(reinterpret_cast<const VT *>(p) + (q))
-#define GM_STORE(v, p, q) __builtin_nontemporal_store((v), reinterpret_cast<VT *>(p) + (q))
-
 // ---- the sweeps over the basis (basis: columns of stride ld, ld % V == 0) ------------------------------------------------------
 // partials of v_c.w for c = 0 .. j: part[c * kPcgBlocks + block]
 template <typename T>
@@ -132,7 +115,6 @@ k_gm_dots(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo,
           uint64_t n, T *__restrict__ part) {
     if (!gm_enters(sc)) return;  // block-uniform
     const unsigned ncols = mo->j + 1;
-    GM_SWEEP_HEAD;
     __shared__ T sa[kGmTile][kBlock / kWave];
     for (unsigned c0 = 0; c0 < ncols; c0 += kGmTile) {
         const unsigned width = ncols - c0 < (unsigned)kGmTile ? ncols - c0 : (unsigned)kGmTile;
@@ -140,24 +122,19 @@ k_gm_dots(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo,
         T acc[kGmTile];
 #pragma unroll
         for (int t = 0; t < kGmTile; ++t) acc[t] = T(0);
-        for (uint64_t q = tid; q < nv; q += nthreads) {
-            const VT wv = GM_LOAD(w, q);
+        sweep<T>(n, [&](auto at) {
+            const auto wv = at.load(w);
 #pragma unroll
             for (int t = 0; t < kGmTile; ++t) {
                 if ((unsigned)t < width) {
-                    const VT vv = GM_LOAD(col0 + (uint64_t)t * ld, q);
+                    const auto vv = at.load(col0 + (uint64_t)t * ld);
 #pragma unroll
-                    for (int e = 0; e < V; ++e) acc[t] = p_add(acc[t], p_mul(vv[e], wv[e]));
+                    for (int e = 0; e < at.width; ++e) acc[t] = p_add(acc[t], p_mul(vv[e], wv[e]));
                 }
             }
-        }
-        for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-            const T wi = w[i];
-#pragma unroll
-            for (int t = 0; t < kGmTile; ++t)
-                if ((unsigned)t < width) acc[t] = p_add(acc[t], p_mul(col0[(uint64_t)t * ld + i], wi));
-        }
-        // solver_tree.hpp's workgroup sum, one per column of the tile
+        });
+        // solver_tree.hpp's workgroup sum written out for a tile: one accumulator per column, and thread t < width (not thread 0)
+        // sums and writes column t -- block_sum1 per column would cost a barrier each, so this stays its own
 #pragma unroll
         for (int t = 0; t < kGmTile; ++t) {
 #pragma unroll
@@ -179,7 +156,7 @@ template <typename T, int PASS>
 __global__ void __launch_bounds__(kBlock)
 k_gm_fold(const GmScalars<T> *__restrict__ sc, GmMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
     if (!gm_enters(sc) || blockIdx.x > mo->j) return;
-    const T h = gm_fold1(part + (uint64_t)blockIdx.x * kPcgBlocks, n_parts);
+    const T h = fold1(part + (uint64_t)blockIdx.x * kPcgBlocks, n_parts);
     if (threadIdx.x == 0) (PASS == 1 ? mo->h1 : mo->h2)[blockIdx.x] = h;
 }
 
@@ -191,48 +168,29 @@ k_gm_update(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ m
     if (!gm_enters(sc)) return;
     const unsigned ncols = mo->j + 1;
     const T *__restrict__ h = PASS == 1 ? mo->h1 : mo->h2;
-    GM_SWEEP_HEAD;
     T acc = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT wv = GM_LOAD(w, q);
+    sweep<T>(n, [&](auto at) {
+        auto wv = at.load(w);
 #pragma unroll 8
         for (unsigned c = 0; c < ncols; ++c) {
-            const VT vv = GM_LOAD(basis + (uint64_t)c * ld, q);
+            const auto vv = at.load(basis + (uint64_t)c * ld);
             const T hc = h[c];
 #pragma unroll
-            for (int e = 0; e < V; ++e) wv[e] = p_add(wv[e], -p_mul(vv[e], hc));
+            for (int e = 0; e < at.width; ++e) wv[e] = p_add(wv[e], -p_mul(vv[e], hc));
         }
         if (PASS == 2) {
 #pragma unroll
-            for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(wv[e], wv[e]));
+            for (int e = 0; e < at.width; ++e) acc = p_add(acc, p_mul(wv[e], wv[e]));
         }
-        GM_STORE(wv, w, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        T wi = w[i];
-        for (unsigned c = 0; c < ncols; ++c) wi = p_add(wi, -p_mul(basis[(uint64_t)c * ld + i], h[c]));
-        if (PASS == 2) acc = p_add(acc, p_mul(wi, wi));
-        w[i] = wi;
-    }
-    if (PASS == 2) {
-        const T t = block_sum1(acc);
-        if (threadIdx.x == 0) part_ww[blockIdx.x] = t;
-    }
+        at.store(w, wv);
+    });
+    if (PASS == 2) block_partial(acc, part_ww);
 }
 
 // partials of r.r (set-up)
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_gm_rr(const T *__restrict__ r, uint64_t n, T *__restrict__ part) {
-    GM_SWEEP_HEAD;
-    T acc = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        const VT rv = GM_LOAD(r, q);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc = p_add(acc, p_mul(rv[e], rv[e]));
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) acc = p_add(acc, p_mul(r[i], r[i]));
-    const T t = block_sum1(acc);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    block_partial(sweep_dot(r, r, n), part);
 }
 
 // V0 false: v_j = w / hn (w itself when hn == 0), to its column and to vin.  V0 true: v_0 = r / beta, the same two places
@@ -243,21 +201,15 @@ k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__rest
     const T d = V0 ? mo->beta : mo->hn;
     const bool copy = !V0 && d == T(0);
     T *__restrict__ colp = basis + (V0 ? (uint64_t)0 : (uint64_t)mo->j * ld);  // (the step has advanced j: at most m)
-    GM_SWEEP_HEAD;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT v = GM_LOAD(src, q);
+    sweep<T>(n, [&](auto at) {
+        auto v = at.load(src);
         if (!copy) {
 #pragma unroll
-            for (int e = 0; e < V; ++e) v[e] = p_div(v[e], d);
+            for (int e = 0; e < at.width; ++e) v[e] = p_div(v[e], d);
         }
-        GM_STORE(v, colp, q);
-        GM_STORE(v, vin, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        const T v = copy ? src[i] : p_div(src[i], d);
-        colp[i] = v;
-        vin[i] = v;
-    }
+        at.store(colp, v);
+        at.store(vin, v);
+    });
 }
 
 // the cycle end: x += sum v_c y_c (c < j), r = sum v_c z_c (c <= j), the partials of r.r
@@ -267,57 +219,42 @@ k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t 
     if (!mo->do_end) return;
     const unsigned j = mo->j;  // >= 1
     const T *__restrict__ y = mo->y, *__restrict__ z = mo->z;
-    GM_SWEEP_HEAD;
     T acc = T(0);
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT xv = GM_LOAD(x, q);
-        VT rv;
+    sweep<T>(n, [&](auto at) {
+        auto xv = at.load(x);
+        typename decltype(at)::pack rv;
         {
-            const VT vv = GM_LOAD(basis, q);
+            const auto vv = at.load(basis);
             const T y0 = y[0], z0 = z[0];
 #pragma unroll
-            for (int e = 0; e < V; ++e) {
+            for (int e = 0; e < at.width; ++e) {
                 xv[e] = p_add(xv[e], p_mul(vv[e], y0));
                 rv[e] = p_mul(vv[e], z0);
             }
         }
 #pragma unroll 4
         for (unsigned c = 1; c < j; ++c) {
-            const VT vv = GM_LOAD(basis + (uint64_t)c * ld, q);
+            const auto vv = at.load(basis + (uint64_t)c * ld);
             const T yc = y[c], zc = z[c];
 #pragma unroll
-            for (int e = 0; e < V; ++e) {
+            for (int e = 0; e < at.width; ++e) {
                 xv[e] = p_add(xv[e], p_mul(vv[e], yc));
                 rv[e] = p_add(rv[e], p_mul(vv[e], zc));
             }
         }
         {
-            const VT vv = GM_LOAD(basis + (uint64_t)j * ld, q);
+            const auto vv = at.load(basis + (uint64_t)j * ld);
             const T zj = z[j];
 #pragma unroll
-            for (int e = 0; e < V; ++e) {
+            for (int e = 0; e < at.width; ++e) {
                 rv[e] = p_add(rv[e], p_mul(vv[e], zj));
                 acc = p_add(acc, p_mul(rv[e], rv[e]));
             }
         }
-        GM_STORE(xv, x, q);
-        GM_STORE(rv, r, q);
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        T xi = p_add(x[i], p_mul(basis[i], y[0]));
-        T ri = p_mul(basis[i], z[0]);
-        for (unsigned c = 1; c < j; ++c) {
-            const T v = basis[(uint64_t)c * ld + i];
-            xi = p_add(xi, p_mul(v, y[c]));
-            ri = p_add(ri, p_mul(v, z[c]));
-        }
-        ri = p_add(ri, p_mul(basis[(uint64_t)j * ld + i], z[j]));
-        x[i] = xi;
-        r[i] = ri;
-        acc = p_add(acc, p_mul(ri, ri));
-    }
-    const T t = block_sum1(acc);
-    if (threadIdx.x == 0) part_rr[blockIdx.x] = t;
+        at.store(x, xv);
+        at.store(r, rv);
+    });
+    block_partial(acc, part_rr);
 }
 
 // ---- the one-workgroup kernels ----------------------------------------------------------------------------------------------------
@@ -326,7 +263,7 @@ k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t 
 template <typename T, bool SETUP>
 __global__ void __launch_bounds__(kBlock) k_gm_begin(GmScalars<T> *sc, GmMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
     if (!SETUP && !mo->do_end) return;
-    const T rr = gm_fold1(part, n_parts);
+    const T rr = fold1(part, n_parts);
     if (threadIdx.x == 0) {
         sc->rr = rr;
         mo->do_v0 = 0;
@@ -353,7 +290,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> 
         if (threadIdx.x == 0) mo->do_norm = mo->do_end = mo->do_v0 = 0;
         return;
     }
-    const T ww = gm_fold1(part_ww, n_parts);
+    const T ww = fold1(part_ww, n_parts);
     if (threadIdx.x != 0) return;
     const uint64_t iters = sc->iters + 1;
     sc->iters = iters;

@@ -577,6 +577,13 @@ struct CgScalars {
     uint64_t iter_max;
     double tol;
 };
+// what cg_read_scalars relies on when the host polls another solver's leading block S<T> through it: CgScalars' size, and rr,
+// converged and iters at CgScalars' offsets
+template <template <typename> class S, typename T> constexpr bool scalars_like_cg_t() {
+    return sizeof(S<T>) == sizeof(CgScalars<T>) && offsetof(S<T>, rr) == offsetof(CgScalars<T>, rr) &&
+           offsetof(S<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(S<T>, iters) == offsetof(CgScalars<T>, iters);
+}
+template <template <typename> class S> constexpr bool scalars_like_cg() { return scalars_like_cg_t<S, float>() && scalars_like_cg_t<S, double>(); }
 size_t cg_scalars_bytes(int dtype);  // cg.hip
 // host view of a copy of the scalar block after a poll (cg.hip)
 void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t *iters, double *rr);

@@ -13,8 +13,8 @@
 // what the preconditioner costs), p.Ap out of the SpMV epilogue when the kernel offers it.  All scalars (r.r, r.z, p.Ap,
 // alpha, beta, the stop flag, the iteration count) live in device memory as in cg.hip: the host replays a hipGraph of 8
 // bodies and polls one small block per batch (solve_in_batches, internal.hpp) -- no synchronisation inside an iteration.
-// Reductions: fixed grid, per-thread strided sums, wave butterfly, LDS across waves, one block folds the partials in
-// index order -- deterministic.
+// The sweeps state their arithmetic once, on solver_tree.hpp's sweep; the sums and the one-workgroup folds of their partials are
+// its tree (block_sums / block_sum1, fold1 / fold2) -- deterministic.
 // The second half of the file is the same recurrence preconditioned by two level-scheduled triangular solves (trisolve.hip) on one
 // handle (TriPrecond), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
 // (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec) solves on the matrix itself, ILU(0) (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) on a
@@ -64,12 +64,7 @@ struct PcgScalars {
     uint64_t iter_max;
     double tol;
 };
-// the host polls this block through CG's reader (cg_read_scalars): the two layouts agree in size and in what the host reads
-template <typename T> constexpr bool pcg_scalars_like_cg() {
-    return sizeof(PcgScalars<T>) == sizeof(CgScalars<T>) && offsetof(PcgScalars<T>, rr) == offsetof(CgScalars<T>, rr) &&
-           offsetof(PcgScalars<T>, converged) == offsetof(CgScalars<T>, converged) && offsetof(PcgScalars<T>, iters) == offsetof(CgScalars<T>, iters);
-}
-static_assert(pcg_scalars_like_cg<float>() && pcg_scalars_like_cg<double>(), "PcgScalars and CgScalars have drifted apart");
+static_assert(scalars_like_cg<PcgScalars>(), "PcgScalars and CgScalars have drifted apart");  // (the host polls it through CG's reader)
 
 template <typename T>
 __global__ void k_pcg_init(PcgScalars<T> *sc, double tol, uint64_t iter_max) {
@@ -83,18 +78,13 @@ __global__ void k_pcg_init(PcgScalars<T> *sc, double tol, uint64_t iter_max) {
 // out[b] = sum of block b's strided share of in[0..n): first stage of folding the SpMV epilogue's per-tile partials
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_pcg_sum_stage1(const T *__restrict__ in, uint64_t n, T *__restrict__ out) {
-    T a = T(0);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) a = p_add(a, in[i]);
-    const T t = block_sum1(a);
-    if (threadIdx.x == 0) out[blockIdx.x] = t;
+    block_partial(strided_sum(in, n, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x), out);
 }
 
 // p.Ap = fold(partials); decide whether this body runs; alpha = r.z / p.Ap
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_pcg_alpha(PcgScalars<T> *sc, const T *__restrict__ partials, uint32_t count) {
-    T a = T(0);
-    for (uint32_t i = threadIdx.x; i < count; i += kBlock) a = p_add(a, partials[i]);
-    const T pap = block_sum1(a);
+    const T pap = fold1(partials, count);
     if (threadIdx.x == 0) {
         const bool active = !sc->converged && sc->iters < sc->iter_max;
         sc->active = sc->entered = active ? 1u : 0u;
@@ -111,40 +101,27 @@ template <typename T, bool UPDATE>
 __global__ void __launch_bounds__(kBlock)
 k_pcg_update(const PcgScalars<T> *__restrict__ sc, T *__restrict__ r, const T *__restrict__ ap, const T *__restrict__ d, uint64_t n,
              T *__restrict__ part_rr, T *__restrict__ part_rz) {
-    // 16 bytes per lane and array (the buffers are hipMalloc'ed: aligned); the last n % V elements one by one
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
     T alpha = T(0);
     if (UPDATE) {
         if (!sc->active) return;  // block-uniform
         alpha = sc->alpha;
     }
     T s_rr = T(0), s_rz = T(0);
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT rv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(r) + q);
-        const VT dv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(d) + q);
+    sweep<T>(n, [&](auto at) {
+        auto rv = at.load(r);
+        const auto dv = at.load(d);
         if (UPDATE) {
-            const VT av = __builtin_nontemporal_load(reinterpret_cast<const VT *>(ap) + q);
+            const auto av = at.load(ap);
 #pragma unroll
-            for (int e = 0; e < V; ++e) rv[e] = p_add(rv[e], -p_mul(av[e], alpha));
-            __builtin_nontemporal_store(rv, reinterpret_cast<VT *>(r) + q);
+            for (int e = 0; e < at.width; ++e) rv[e] = p_add(rv[e], -p_mul(av[e], alpha));
+            at.store(r, rv);
         }
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
+        for (int e = 0; e < at.width; ++e) {
             s_rr = p_add(s_rr, p_mul(rv[e], rv[e]));
             s_rz = p_add(s_rz, p_mul(rv[e], p_div(rv[e], dv[e])));
         }
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        T ri = r[i];
-        if (UPDATE) {
-            ri = p_add(ri, -p_mul(ap[i], alpha));
-            r[i] = ri;
-        }
-        s_rr = p_add(s_rr, p_mul(ri, ri));
-        s_rz = p_add(s_rz, p_mul(ri, p_div(ri, d[i])));
-    }
+    });
     block_sums(s_rr, s_rz, part_rr, part_rz);
 }
 
@@ -153,10 +130,8 @@ template <typename T, bool FIRST>
 __global__ void __launch_bounds__(kBlock)
 k_pcg_beta(PcgScalars<T> *sc, const T *__restrict__ part_a, const T *__restrict__ part_b, unsigned n_parts) {
     if (!FIRST && !sc->active) return;
-    T a = T(0), b = T(0);
-    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) { a = p_add(a, part_a[k]); b = p_add(b, part_b[k]); }
     __shared__ T out2[2];
-    block_sums(a, b, out2, out2 + 1);  // (one block: blockIdx.x == 0; thread 0 writes)
+    fold2(part_a, part_b, n_parts, out2);
     if (threadIdx.x == 0) {
         const T rr = out2[0], rz = out2[1];
         sc->rr = rr;
@@ -177,8 +152,6 @@ k_pcg_beta(PcgScalars<T> *sc, const T *__restrict__ part_a, const T *__restrict_
 template <typename T, bool FIRST>
 __global__ void __launch_bounds__(kBlock)
 k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ d, T *__restrict__ x, uint64_t n) {
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
     T alpha = T(0), beta = T(0);
     bool rebuild = true;
     if (!FIRST) {
@@ -187,33 +160,25 @@ k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__rest
         beta = sc->beta;
         rebuild = sc->active != 0;
     }
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT pv;
+    sweep<T>(n, [&](auto at) {
+        typename decltype(at)::pack pv;
         if (!FIRST) {
-            pv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(p) + q);
-            VT xv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(x) + q);
+            pv = at.load(p);
+            auto xv = at.load(x);
 #pragma unroll
-            for (int e = 0; e < V; ++e) xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
-            __builtin_nontemporal_store(xv, reinterpret_cast<VT *>(x) + q);
+            for (int e = 0; e < at.width; ++e) xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
+            at.store(x, xv);
         }
         if (rebuild) {
-            const VT rv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(r) + q), dv = __builtin_nontemporal_load(reinterpret_cast<const VT *>(d) + q);
+            const auto rv = at.load(r), dv = at.load(d);
 #pragma unroll
-            for (int e = 0; e < V; ++e) {
+            for (int e = 0; e < at.width; ++e) {
                 const T z = p_div(rv[e], dv[e]);
                 pv[e] = FIRST ? z : p_add(p_mul(pv[e], beta), z);
             }
-            __builtin_nontemporal_store(pv, reinterpret_cast<VT *>(p) + q);
+            at.store(p, pv);
         }
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        if (!FIRST) x[i] = p_add(x[i], p_mul(p[i], alpha));
-        if (rebuild) {
-            const T z = p_div(r[i], d[i]);
-            p[i] = FIRST ? z : p_add(p_mul(p[i], beta), z);
-        }
-    }
+    });
 }
 
 // ---- host side: what the Jacobi driver here and the triangular one below share ------------------------------------------------------
@@ -315,19 +280,8 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
 template <typename T, bool ALWAYS>
 __global__ void __launch_bounds__(kBlock)
 k_sgs_dot(const PcgScalars<T> *__restrict__ sc, const T *__restrict__ x, const T *__restrict__ y, uint64_t n, T *__restrict__ part) {
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
     if (!ALWAYS && !sc->active) return;
-    T a = T(0);
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        const VT xv = *(reinterpret_cast<const VT *>(x) + q), yv = *(reinterpret_cast<const VT *>(y) + q);
-#pragma unroll
-        for (int e = 0; e < V; ++e) a = p_add(a, p_mul(xv[e], yv[e]));
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) a = p_add(a, p_mul(x[i], y[i]));
-    const T t = block_sum1(a);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
+    block_partial(sweep_dot<T, kPlain>(x, y, n), part);
 }
 
 // the entered body's r -= ap*alpha and x += p*alpha in one sweep, and the partials of the new r.r
@@ -335,32 +289,22 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock)
 k_sgs_update(const PcgScalars<T> *__restrict__ sc, T *__restrict__ r, const T *__restrict__ ap, const T *__restrict__ p, T *__restrict__ x, uint64_t n,
              T *__restrict__ part_rr) {
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
     if (!sc->active) return;  // block-uniform
     const T alpha = sc->alpha;
     T s_rr = T(0);
-    const uint64_t nv = n / V, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t q = tid; q < nv; q += nthreads) {
-        VT rv = *(reinterpret_cast<const VT *>(r) + q), xv = *(reinterpret_cast<const VT *>(x) + q);
-        const VT av = *(reinterpret_cast<const VT *>(ap) + q), pv = *(reinterpret_cast<const VT *>(p) + q);
+    sweep<T, kBy16Bytes, kPlain>(n, [&](auto at) {
+        auto rv = at.load(r), xv = at.load(x);
+        const auto av = at.load(ap), pv = at.load(p);
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
+        for (int e = 0; e < at.width; ++e) {
             rv[e] = p_add(rv[e], -p_mul(av[e], alpha));
             xv[e] = p_add(xv[e], p_mul(pv[e], alpha));
             s_rr = p_add(s_rr, p_mul(rv[e], rv[e]));
         }
-        *(reinterpret_cast<VT *>(r) + q) = rv;
-        *(reinterpret_cast<VT *>(x) + q) = xv;
-    }
-    for (uint64_t i = nv * V + tid; i < n; i += nthreads) {
-        const T ri = p_add(r[i], -p_mul(ap[i], alpha));
-        r[i] = ri;
-        x[i] = p_add(x[i], p_mul(p[i], alpha));
-        s_rr = p_add(s_rr, p_mul(ri, ri));
-    }
-    const T t = block_sum1(s_rr);
-    if (threadIdx.x == 0) part_rr[blockIdx.x] = t;
+        at.store(r, rv);
+        at.store(x, xv);
+    });
+    block_partial(s_rr, part_rr);
 }
 
 // one workgroup folds the partials.  WHAT 0: rr of the initial residual; 1: rr, then the stop test (before beta); 2: the first
@@ -368,9 +312,7 @@ k_sgs_update(const PcgScalars<T> *__restrict__ sc, T *__restrict__ r, const T *_
 template <typename T, int WHAT>
 __global__ void __launch_bounds__(kBlock) k_sgs_fold(PcgScalars<T> *sc, const T *__restrict__ part, unsigned n_parts) {
     if ((WHAT == 1 || WHAT == 3) && !sc->active) return;
-    T a = T(0);
-    for (unsigned k = threadIdx.x; k < n_parts; k += kBlock) a = p_add(a, part[k]);
-    const T v = block_sum1(a);
+    const T v = fold1(part, n_parts);
     if (threadIdx.x == 0) {
         if (WHAT == 0) {
             sc->rr = v;
@@ -394,8 +336,15 @@ template <typename T, bool FIRST>
 __global__ void __launch_bounds__(kBlock) k_sgs_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__restrict__ z, uint64_t n) {
     if (!FIRST && !sc->active) return;
     const T beta = FIRST ? T(0) : sc->beta;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        p[i] = FIRST ? z[i] : p_add(p_mul(p[i], beta), z[i]);
+    sweep<T, kByElement>(n, [&](auto at) {
+        auto pv = at.load(z);
+        if (!FIRST) {
+            const auto old = at.load(p);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) pv[e] = p_add(p_mul(old[e], beta), pv[e]);
+        }
+        at.store(p, pv);
+    });
 }
 
 // most nodes of a captured batch (a linear chain): beyond it the bodies per batch go down, and a single body beyond it runs

@@ -18,7 +18,7 @@ import trisolve_cases as tc
 import trisolve_model as tm
 from kernel_forms import env, same
 from sparsemat_amd import _lib
-from test_sgs_gpu import assert_result, device_product, is_fused
+from test_sgs_gpu import SMALL_PATHS, assert_result, check_path, device_product, is_fused, path_ids, path_system
 from util import assert_spmv_close
 
 pytestmark = pytest.mark.gpu
@@ -353,6 +353,26 @@ def test_stops_batches_and_iter_max(gpu, dtype):
     none = model(0.0, 0)
     assert_result(run_host(a, f, b, x0, 0.0, 0, "stream"), none, "iter_max 0")
     assert_result(run_vec(a, f, b, x0, 0.0, 0, "stream", 3), none, "iter_max 0, vec")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", SMALL_PATHS, ids=path_ids(SMALL_PATHS))
+def test_bits_at_every_path_size(gpu, case, dtype):
+    """tests/test_sgs_gpu.py's small path sizes (n = 3 and n = 391: no whole vector, a tail of 1 and of 3, two workgroups, a replayed
+    batch and one body more) with the ILU(0) factor.  The second trip of the grid is SGS's case alone: the kernels are the same ones."""
+    off, col, val, _, _ = path_system(*case[:4], dtype)
+    w, zp = im.ilu0(off, col, val, vector=True)
+    assert zp is None
+    plans = (tm.Plan(off, col, tm.LOWER), tm.Plan(off, col, tm.UPPER))
+    made = {}
+
+    def factor_of(a):
+        if id(a) not in made:
+            made[id(a)] = a.ilu0()[0]
+            assert same(values(made[id(a)]), w)
+        return made[id(a)]
+    check_path(case, dtype, lambda r: im.ilu_apply(off, col, w, r, plans),
+               lambda a, *args: run_host(a, factor_of(a), *args), lambda a, *args: run_vec(a, factor_of(a), *args))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -3,7 +3,8 @@ csrc/trisolve.hip) pinned BIT FOR BIT to tests/sgs_model.py in "device" mode: x,
 the four grid cases of the model's table in the natural and the red-black ordering, through the STREAM product (p.Ap out of
 its epilogue), SEQ and AUTO.  The model takes every product from the device's own product of the same variant on the same
 handle, held to the suite's parity bound against the oracle first (as tests/test_solver_kernels_gpu.py does), so no tolerance
-appears in the solver cases."""
+appears in the solver cases.  The table's grids are multiples of 4 inside one trip of the sweeps' grid: the path sizes further down
+(n = 3, 391 and 262 447) run the tails, a second workgroup and a thread's second trip, for tests/test_ilu_gpu.py too."""
 import math
 import os
 
@@ -194,6 +195,60 @@ def test_node_budget_changes_no_bit(gpu, dtype):
             assert_result(run_vec(a, b, x0, 0.0, 13, "stream", 8), want, ("budget", nodes))
             assert_result(run_vec(a, b, x0, tol, 50, "stream", 8), stopped, ("budget, stop", nodes))
             assert_result(run_host(a, b, x0, tol, 50, "stream"), stopped, ("budget, host", nodes))
+
+
+# ---- every path of the sweeps (k_sgs_dot, k_sgs_update, k_sgs_p and the fold) -------------------------------------------------
+# (nx, ny, spread, ordering, bodies).  The sweeps take 16 bytes per lane and then the last n % V rows one by one (V = 4 in f32, 2 in
+# f64), on min(ceil(n / 256), 512) workgroups.  n = 3: no whole vector in f32, one vector and one tail row in f64.  n = 391: two
+# workgroups, a tail of 3 (f32) and of 1 (f64); nine bodies are a replayed batch of 8 and one more.
+SMALL_PATHS = [(1, 3, 0.0, "natural", 2), (23, 17, 1.0, "natural", 9), (23, 17, 1.0, "red_black", 9)]
+# n = 262 447: the grid is at its cap, 131 072 threads over 131 223 f64 vectors, so threads make a second trip; the tail is 1.
+# Red-black keeps the schedules at two levels (the model solves level by level).  f32 makes a second trip only past 524 288 rows.
+BIG_PATH = (361, 727, 1.0, "red_black", 3)
+_PATHS = {}
+
+
+def path_system(nx, ny, spread, ordering, dtype):
+    """(off, col, val, b, x0) of lap2d(nx, ny) in the ordering, b and x0 random, computed once"""
+    key = nx, ny, spread, ordering, np.dtype(dtype).name
+    if key not in _PATHS:
+        off, col, val = sg.lap2d(nx, ny, dtype, seed=2, spread=spread)
+        if ordering == "red_black":
+            off, col, val = sg.permute_symmetric(off, col, val, sg.red_black(nx, ny))
+        rng = np.random.default_rng(11)
+        n = nx * ny
+        _PATHS[key] = off, col, val, rng.uniform(-1, 1, n).astype(dtype), rng.uniform(-1, 1, n).astype(dtype)
+    return _PATHS[key]
+
+
+def path_ids(cases):
+    return ["%dx%d-%s" % (c[0], c[1], c[3]) for c in cases]
+
+
+def check_path(case, dtype, precond=None, run_host=None, run_vec=None):
+    """tol = 0 from a random x0 through the STREAM product: the model's bits from the host entry and from the _vec entry with
+    check_every 3.  run_host / run_vec: (handle, b, x0, tol, iter_max, variant[, check_every]) -> (x, bodies, r.r)"""
+    nx, ny, spread, ordering, bodies = case
+    off, col, val, b, x0 = path_system(nx, ny, spread, ordering, dtype)
+    a = handle(off, col, val)
+    want = sg.sgs_pcg(off, col, val, b, x0, 0.0, bodies, fused=True, product=device_product(a, "stream", off, col, val), precond=precond)
+    assert want.iterations == bodies and np.isfinite(want.x).all() and np.isfinite(want.r_norm_squared)
+    assert_result(run_host(a, b, x0, 0.0, bodies, "stream"), want, (case, "host"))
+    assert_result(run_vec(a, b, x0, 0.0, bodies, "stream", 3), want, (case, "vec/3"))
+
+
+@pytest.mark.parametrize("dtype", [pytest.param(F32, id="f32"), pytest.param(F64, id="f64")])
+@pytest.mark.parametrize("case", SMALL_PATHS, ids=path_ids(SMALL_PATHS))
+def test_bits_at_every_path_size(gpu, case, dtype):
+    n, V = case[0] * case[1], 16 // np.dtype(dtype).itemsize
+    assert (n, n % V) in ((3, 3), (3, 1), (391, 3), (391, 1))
+    check_path(case, dtype, None, run_host, run_vec)
+
+
+def test_bits_on_a_second_trip_of_the_grid(gpu):
+    nx, ny = BIG_PATH[:2]
+    assert nx * ny // 2 > 512 * 256 and (nx * ny) % 2 == 1
+    check_path(BIG_PATH, F64, None, run_host, run_vec)
 
 
 def test_statuses(gpu):
