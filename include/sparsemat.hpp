@@ -758,20 +758,33 @@ class BiCGStab {
 // BiCGStab (no breakdown before the Krylov space is exhausted, no stagnation near the imaginary axis), device-resident like it, same
 // panics.  restart: 1 .. 128 (0: the library's default, 30).  breakdown(): 0 none, 1 the Krylov space is exhausted (x is updated from
 // it), 2 the residual at a cycle's start is exactly zero (sparsemat_hip.h); cycles(): how many times a v_0 was formed.
+// precond (smh_gmres_precond_solve*): SMH_PRECOND_NONE (the default: the calls above), _JACOBI, _SGS or _ILU -- right preconditioning,
+// A M^-1 u = b, x = M^-1 u; r_norm_squared() is then the recurrence residual's.  SMH_PRECOND_ILU takes the factor (mat.ilu0()) or,
+// in the overloads without one, factors mat first.
 class GMRES {
   public:
     GMRES() = default;
-    GMRES(double tol, size_t iter_max, size_t restart = 30) : tol_(tol), iter_max_(iter_max), restart_(restart) {}
+    GMRES(double tol, size_t iter_max, size_t restart = 30, int precond = SMH_PRECOND_NONE)
+        : tol_(tol), iter_max_(iter_max), restart_(restart), precond_(precond) {}
     template <typename T>
     void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &b, DenseVec<T> &x) {
+        if (precond_ == SMH_PRECOND_ILU) return solve(mat, mat.ilu0(), b, x);
+        if (precond_ != SMH_PRECOND_NONE) return solve_precond(mat, nullptr, b, x);
         detail::check(smh_gmres_solve_vec(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, restart_, SMH_SPMV_AUTO, 0, &iterations_,
                                           &r_norm_squared_, &cycles_, &breakdown_));
     }
     // host vectors, x updated in place
     template <typename T>
     void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
+        if (precond_ == SMH_PRECOND_ILU) return solve(mat, mat.ilu0(), b, x);
+        if (precond_ != SMH_PRECOND_NONE) return solve_precond(mat, nullptr, b, x);
         detail::check(smh_gmres_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, restart_, SMH_SPMV_AUTO,
                                       &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    // ... with the ILU(0) factor of mat (a factor with another kind is the library's SMH_ERR_INVALID)
+    template <typename T, typename V>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const V &b, V &x) {
+        solve_precond(mat, factor.handle(), b, x);
     }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }
@@ -779,9 +792,20 @@ class GMRES {
     int breakdown() const { return breakdown_; }
 
   private:
+    template <typename T>
+    void solve_precond(const SparseMatCRS<T> &mat, smh_crs *factor, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_gmres_precond_solve_vec(mat.handle(), precond_, factor, b.handle(), x.handle(), tol_, iter_max_, restart_,
+                                                  SMH_SPMV_AUTO, 0, &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    template <typename T>
+    void solve_precond(const SparseMatCRS<T> &mat, smh_crs *factor, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_gmres_precond_solve(mat.handle(), precond_, factor, b.data(), b.size(), x.data(), x.size(), tol_, iter_max_,
+                                              restart_, SMH_SPMV_AUTO, &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
     double tol_ = 1e-12;
     size_t iter_max_ = 10000;
     size_t restart_ = 30;
+    int precond_ = SMH_PRECOND_NONE;
     size_t iterations_ = 0;
     double r_norm_squared_ = 0.0;
     size_t cycles_ = 0;

@@ -45,8 +45,8 @@ extern "C" {
  * smh_crs_permute_symmetric_dev, smh_vec_permute, smh_vec_permute_dev, smh_crs_bandwidth, smh_crs_span_fraction, smh_crs_rcm,
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
  * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
- * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec.  A caller checks smh_abi_version() ==
- * SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
+ * smh_gmres_precond_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -809,6 +809,36 @@ int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_i
 int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart,
                         int variant, size_t check_every,
                         size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+
+/* Right-preconditioned GMRES(m) -- an EXTENSION: A M^-1 u = b, x = M^-1 u, inside the solver above, so the residual it minimises is
+ * the true one, b - A x, and the stop rule, rr, cycles and both breakdown codes keep their meaning.  Everything not named here is
+ * smh_gmres_solve's contract, word for word.  One rounding per operation, nothing contracted:
+ *   set-up:     unchanged (r = b - A x; M is not applied to the residual)
+ *   body:       u = M^-1 v_j;  w = A u;  both Gram-Schmidt passes, the step and v_{j+1} = w / hn unchanged
+ *   cycle end:  y unchanged;  t = (..(v_0 y_0 + v_1 y_1) .. + v_{j-1} y_{j-1})   (starts from the product, as r does)
+ *               q = M^-1 t;  x = x + q                       (one application per cycle, one add per element)
+ *               r, rr, the restart: unchanged (rebuilt from the basis; no product)
+ * precond = SMH_PRECOND_JACOBI: M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (as smh_pcg_jacobi_solve forms z);
+ * SMH_PRECOND_SGS: smh_crs_sgs_apply_vec's operations on a itself; SMH_PRECOND_ILU: smh_crs_ilu_apply_vec's on the factor handle
+ * f (smh_crs_ilu0; what its values are is the caller's business).  SMH_PRECOND_NONE forwards to smh_gmres_solve*: its bits.
+ * f is the ILU factor and NULL for every other kind: a non-NULL f with another kind, a NULL f with SMH_PRECOND_ILU and any other
+ * value of precond are SMH_ERR_INVALID.  Memory: (m + 6) n values with Jacobi, (m + 7) n with SGS and ILU.  A batch of many kernel
+ * launches (two applications per body) is replayed in smaller batches or launched plainly, which changes no bit.
+ * rr is the RECURRENCE residual's r.r: with an ill-conditioned M (triangular solves that amplify rounding) it parts from
+ * |b - A x|^2, which the caller then forms itself.
+ * Statuses, decided before any launch of the solve: smh_gmres_solve's; ILU: smh_pcg_ilu_solve's about f (n: SMH_ERR_DIM_MISMATCH;
+ * dtype, device, an orphaned entry, a zero or absent diagonal entry, the message naming the row: SMH_ERR_INVALID; a stored column
+ * >= n: SMH_ERR_INDEX_RANGE); SGS: smh_pcg_sgs_solve's about a; Jacobi: smh_pcg_jacobi_solve's about the diagonal. */
+#define SMH_PRECOND_NONE 0
+#define SMH_PRECOND_JACOBI 1
+#define SMH_PRECOND_SGS 2
+#define SMH_PRECOND_ILU 3
+int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout,
+                            size_t x_len, double tol, size_t iter_max, size_t restart, int variant,
+                            size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+int smh_gmres_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol,
+                                size_t iter_max, size_t restart, int variant, size_t check_every,
+                                size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
 
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;

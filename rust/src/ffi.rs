@@ -18,6 +18,10 @@ pub const SMH_TRI_LOWER: c_int = 0;
 pub const SMH_TRI_UPPER: c_int = 1;
 pub const SMH_DIAG_NON_UNIT: c_int = 0;
 pub const SMH_DIAG_UNIT: c_int = 1;
+pub const SMH_PRECOND_NONE: c_int = 0;
+pub const SMH_PRECOND_JACOBI: c_int = 1;
+pub const SMH_PRECOND_SGS: c_int = 2;
+pub const SMH_PRECOND_ILU: c_int = 3;
 pub const SMH_EXCHANGE_NONE: c_int = 0;
 pub const SMH_EXCHANGE_ALLGATHER: c_int = 1;
 pub const SMH_EXCHANGE_WINDOW: c_int = 2;
@@ -62,6 +66,14 @@ extern "C" {
     pub fn smh_gmres_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize, restart: usize,
                                variant: c_int, check_every: usize,
                                iters_out: *mut usize, rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    // extension: the same solver right-preconditioned (A M^-1 u = b, x = M^-1 u); precond: SMH_PRECOND_*; f: the ILU(0) factor's
+    // handle with SMH_PRECOND_ILU, null otherwise
+    pub fn smh_gmres_precond_solve(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b_host: *const c_void, b_len: usize,
+                                   x_host_inout: *mut c_void, x_len: usize, tol: c_double, iter_max: usize, restart: usize, variant: c_int,
+                                   iters_out: *mut usize, rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_gmres_precond_solve_vec(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec,
+                                       tol: c_double, iter_max: usize, restart: usize, variant: c_int, check_every: usize,
+                                       iters_out: *mut usize, rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
     // extensions (not in the reference): level-scheduled sparse triangular solves, the symmetric Gauss-Seidel preconditioner
     // M = (D + L) D^-1 (D + U) built on them, and its CG (same contract as smh_pcg_jacobi_solve)
     pub fn smh_crs_trisolve_levels(m: *mut smh_crs, uplo: c_int, n_levels_out: *mut usize, level_of_row_out: *mut u32,

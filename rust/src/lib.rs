@@ -132,6 +132,20 @@ impl Gmres {
         });
         (iters, rr, cycles, breakdown as i32)
     }
+
+    /// `solve` right-preconditioned (`smh_gmres_precond_solve`): `precond` is one of `ffi::SMH_PRECOND_*`, `factor` the ILU(0)
+    /// factor's handle with `SMH_PRECOND_ILU` and `None` otherwise.  The r.r returned is the recurrence residual's.
+    pub fn solve_preconditioned<T: HipValue>(&self, mat: &DeviceCrs, precond: std::os::raw::c_int, factor: Option<&DeviceCrs>, b: &[T],
+                                             x: &mut [T]) -> (usize, f64, usize, i32) {
+        let (mut iters, mut rr, mut cycles, mut breakdown) = (0usize, 0f64, 0usize, 0 as std::os::raw::c_int);
+        let f = factor.map_or(std::ptr::null_mut(), |f| f.handle);
+        check(unsafe {
+            ffi::smh_gmres_precond_solve(mat.handle, precond, f, b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void,
+                                         x.len(), self.tol, self.iter_max, self.restart, ffi::SMH_SPMV_AUTO, &mut iters, &mut rr,
+                                         &mut cycles, &mut breakdown)
+        });
+        (iters, rr, cycles, breakdown as i32)
+    }
 }
 
 /// CG preconditioned by symmetric Gauss-Seidel -- an extension, not in the reference (`smh_pcg_sgs_solve`): the Jacobi

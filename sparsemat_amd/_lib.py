@@ -16,6 +16,8 @@ SMH_ERR_HIP, SMH_ERR_OOM, SMH_ERR_NO_DEVICE, SMH_ERR_CAPACITY, SMH_ERR_COMM = 5,
 SMH_F32, SMH_F64 = 0, 1
 SMH_TRI_LOWER, SMH_TRI_UPPER = 0, 1
 SMH_DIAG_NON_UNIT, SMH_DIAG_UNIT = 0, 1
+SMH_PRECOND_NONE, SMH_PRECOND_JACOBI, SMH_PRECOND_SGS, SMH_PRECOND_ILU = 0, 1, 2, 3
+PRECONDS = {None: SMH_PRECOND_NONE, "jacobi": SMH_PRECOND_JACOBI, "sgs": SMH_PRECOND_SGS, "ilu": SMH_PRECOND_ILU}
 UPLO = {"lower": SMH_TRI_LOWER, "upper": SMH_TRI_UPPER}
 EXCHANGE_NONE, EXCHANGE_ALLGATHER, EXCHANGE_WINDOW, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGES = {"none": EXCHANGE_NONE, "allgather": EXCHANGE_ALLGATHER, "window": EXCHANGE_WINDOW, "halo": EXCHANGE_WINDOW, "auto": EXCHANGE_AUTO}
@@ -195,6 +197,10 @@ SIGNATURES = {
                                C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_gmres_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),
                                    C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_gmres_precond_solve": (_int, [_vp, _int, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _sz, _int, C.POINTER(_sz),
+                                       C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_gmres_precond_solve_vec": (_int, [_vp, _int, _vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),
+                                           C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_comm_unique_id": (_int, [_vp]),
     "smh_comm_create": (_int, [_vp, _int, _int, C.POINTER(_vp)]),
     "smh_comm_destroy": (_int, [_vp]),

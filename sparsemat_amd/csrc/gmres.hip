@@ -1,4 +1,4 @@
-// gmres.hip -- restarted GMRES(m) (Saad & Schultz, unpreconditioned) for non-symmetric systems, gfx950.
+// gmres.hip -- restarted GMRES(m) (Saad & Schultz), unpreconditioned and right-preconditioned, for non-symmetric systems, gfx950.
 //
 // An EXTENSION: the reference's only solver is ConjugateGradient (linearsolver.rs:12-61); bicgstab.hip is the library's short
 // recurrence for matrices that are not symmetric, and this is the robust one: it cannot break down before the Krylov space is
@@ -49,7 +49,29 @@
 // second block (GmMore).  The kernels read the column count from it; a sweep that is not due returns at once: the Gram-Schmidt
 // sweeps when the body will not be entered (stopped, or iter_max bodies entered -- `iters` moves only in the step), the others on
 // the gate words the step and the cycle end's fold leave.  Bodies enqueued past the stop are no-ops.  No float atomics.
+//
+// Right-preconditioned (smh_gmres_precond_solve*): A M^-1 u = b, x = M^-1 u, so the residual that is minimised is the true one and
+// the stop rule, rr, cycles and both codes keep their meaning.  What changes in the recurrence above:
+//   set-up:     nothing (r = b - A x; M is not applied to the residual)
+//   body:       u = M^-1 v_j;  w = A u        (both Gram-Schmidt passes, the step and v_{j+1} = w / hn as above)
+//   cycle end:  t = (..(v_0 y_0 + v_1 y_1) .. + v_{j-1} y_{j-1})   (starts from the product, as r does);  q = M^-1 t;  x = x + q
+//               (r, rr and the restart as above: rebuilt from the basis, no product)
+// The driver is instantiated per GmPrecond; kGmNone's chain of launches is the one described above, launch for launch.
+// kGmJacobi: M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe, as Jacobi-PCG forms z), and costs no
+// launch: both forms of the normalising sweep write v to its column and v / d to the product's fixed input, the cycle end's sweep
+// keeps t in registers and stores x + t / d.  One read of d each: a body at column j moves (4 j + 14) n values beside the product, a
+// cycle end and a restart's v_0 one more each; (m + 6) n values of storage.
+// kGmTri: M^-1 is two level-scheduled triangular solves on one handle (TriPrecond, precond.hpp: SGS on the matrix itself, ILU(0) on
+// a factor).  The body's chain opens with the application vin -> u (the product then reads u); the cycle end's sweep writes t where
+// w was (w is free once v_{j+1} is formed) and r with the partials of r.r, one application t -> q follows in place, then the sweep
+// x += q.  Every triangular launch takes a device gate word: the cycle end's is do_end, the body's is GmMore::enter -- "the next body
+// will be entered" -- which the set-up's and the restart's k_gm_begin and every k_gm_step leave (iters == iter_max is a stop, so
+// after a step "not stopped" says it all; the set-up compares with iter_max itself), so bodies enqueued past the stop run no solve.
+// (m + 7) n values of storage.  A captured batch holds two applications per body: pcg.hip's node budget (bodies_within_budget)
+// makes the batches smaller or drops the capture, which changes no bit.
+// rr is the RECURRENCE residual's r.r: where the solves amplify rounding it parts from |b - A x|^2.
 #include "internal.hpp"
+#include "precond.hpp"
 #include "solver_host.hpp"
 #include "solver_tree.hpp"
 
@@ -62,6 +84,9 @@ namespace {
 constexpr int kGmMaxM = 128;
 constexpr int kGmTile = 8;  // columns per load of w in the dots (no bit depends on it)
 constexpr size_t kGmDefaultRestart = 30;
+
+// how M^-1 is applied (the header's last paragraph): not at all, inside the sweeps, or by two triangular solves on a handle
+enum GmPrecond { kGmNone, kGmJacobi, kGmTri };
 
 // the block the host polls through CG's reader (cg_read_scalars)
 template <typename T>
@@ -86,6 +111,7 @@ struct GmMore {
     uint32_t do_end;     // gate: a cycle end is due (the x / r sweep and its fold)
     uint32_t do_v0;      // gate: a restart is due (v_0 = r / beta)
     uint32_t restart;    // the cycle end that is due is a restart (not a stop)
+    uint32_t enter;      // gate: the next body will be entered (the triangular solves that open it are due)
     T hn, beta;
     T g[kGmMaxM + 1], c[kGmMaxM], s[kGmMaxM], h1[kGmMaxM + 1], h2[kGmMaxM + 1], y[kGmMaxM], z[kGmMaxM + 1];
     T R[kGmMaxM * kGmMaxM];  // R_{i,k} at [k * kGmMaxM + i], i <= k
@@ -102,7 +128,7 @@ __global__ void k_gm_init(GmScalars<T> *sc, GmMore<T> *mo, double tol, uint64_t 
     sc->iters = 0;
     sc->iter_max = iter_max;
     sc->tol = tol;
-    mo->j = mo->cycles = mo->breakdown = mo->do_norm = mo->do_end = mo->do_v0 = mo->restart = 0;
+    mo->j = mo->cycles = mo->breakdown = mo->do_norm = mo->do_end = mo->do_v0 = mo->restart = mo->enter = 0;
     mo->m = m;
     mo->hn = mo->beta = T(0);
 }
@@ -193,10 +219,12 @@ __global__ void __launch_bounds__(kBlock) k_gm_rr(const T *__restrict__ r, uint6
     block_partial(sweep_dot(r, r, n), part);
 }
 
-// V0 false: v_j = w / hn (w itself when hn == 0), to its column and to vin.  V0 true: v_0 = r / beta, the same two places
-template <typename T, bool V0>
+// V0 false: v_j = w / hn (w itself when hn == 0), to its column and to vin.  V0 true: v_0 = r / beta, the same two places.
+// kGmJacobi: vin takes u = v / diag, the product's input, instead
+template <typename T, bool V0, GmPrecond P = kGmNone>
 __global__ void __launch_bounds__(kBlock)
-k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__restrict__ basis, uint64_t ld, T *__restrict__ vin, uint64_t n) {
+k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__restrict__ basis, uint64_t ld, T *__restrict__ vin, uint64_t n,
+          const T *__restrict__ diag = nullptr) {
     if (!(V0 ? mo->do_v0 : mo->do_norm)) return;
     const T d = V0 ? mo->beta : mo->hn;
     const bool copy = !V0 && d == T(0);
@@ -208,27 +236,36 @@ k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__rest
             for (int e = 0; e < at.width; ++e) v[e] = p_div(v[e], d);
         }
         at.store(colp, v);
+        if constexpr (P == kGmJacobi) {
+            const auto dv = at.load(diag);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) v[e] = p_div(v[e], dv[e]);
+        }
         at.store(vin, v);
     });
 }
 
-// the cycle end: x += sum v_c y_c (c < j), r = sum v_c z_c (c <= j), the partials of r.r
-template <typename T>
+// the cycle end: x += sum v_c y_c (c < j), r = sum v_c z_c (c <= j), the partials of r.r.  Preconditioned, the sum t starts from
+// its first product and stays out of x: kGmJacobi keeps it in registers and stores x + t / diag; kGmTri writes it to t_out (x is
+// not touched: x += M^-1 t follows)
+template <typename T, GmPrecond P = kGmNone>
 __global__ void __launch_bounds__(kBlock)
-k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ x, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr) {
+k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ x, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr,
+        const T *__restrict__ diag = nullptr, T *__restrict__ t_out = nullptr) {
     if (!mo->do_end) return;
     const unsigned j = mo->j;  // >= 1
     const T *__restrict__ y = mo->y, *__restrict__ z = mo->z;
     T acc = T(0);
     sweep<T>(n, [&](auto at) {
-        auto xv = at.load(x);
-        typename decltype(at)::pack rv;
+        typename decltype(at)::pack xv, rv;  // xv: x and its sum, or (preconditioned) t
+        if constexpr (P == kGmNone) xv = at.load(x);
         {
             const auto vv = at.load(basis);
             const T y0 = y[0], z0 = z[0];
 #pragma unroll
             for (int e = 0; e < at.width; ++e) {
-                xv[e] = p_add(xv[e], p_mul(vv[e], y0));
+                if constexpr (P == kGmNone) xv[e] = p_add(xv[e], p_mul(vv[e], y0));
+                else xv[e] = p_mul(vv[e], y0);
                 rv[e] = p_mul(vv[e], z0);
             }
         }
@@ -251,10 +288,28 @@ k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t 
                 acc = p_add(acc, p_mul(rv[e], rv[e]));
             }
         }
-        at.store(x, xv);
+        if constexpr (P == kGmJacobi) {
+            const auto x0 = at.load(x), dv = at.load(diag);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) xv[e] = p_add(x0[e], p_div(xv[e], dv[e]));
+        }
+        at.store(P == kGmTri ? t_out : x, xv);
         at.store(r, rv);
     });
     block_partial(acc, part_rr);
+}
+
+// kGmTri's last sweep of a cycle end: x = x + q, q = M^-1 t
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_gm_xadd(const GmMore<T> *__restrict__ mo, T *__restrict__ x, const T *__restrict__ q, uint64_t n) {
+    if (!mo->do_end) return;
+    sweep<T>(n, [&](auto at) {
+        auto xv = at.load(x);
+        const auto qv = at.load(q);
+#pragma unroll
+        for (int e = 0; e < at.width; ++e) xv[e] = p_add(xv[e], qv[e]);
+        at.store(x, xv);
+    });
 }
 
 // ---- the one-workgroup kernels ----------------------------------------------------------------------------------------------------
@@ -279,6 +334,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_begin(GmScalars<T> *sc, GmMore<T>
                 mo->cycles += 1;
                 mo->do_v0 = 1;
             }
+            mo->enter = gm_enters(sc) ? 1u : 0u;  // (a restart follows a step that stopped nothing: beta == 0 alone closes the gate)
         }
     }
 }
@@ -287,7 +343,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_begin(GmScalars<T> *sc, GmMore<T>
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> *mo, const T *__restrict__ part_ww, unsigned n_parts) {
     if (!gm_enters(sc)) {  // (every thread reads before thread 0 writes: the fold below has a barrier)
-        if (threadIdx.x == 0) mo->do_norm = mo->do_end = mo->do_v0 = 0;
+        if (threadIdx.x == 0) mo->do_norm = mo->do_end = mo->do_v0 = mo->enter = 0;
         return;
     }
     const T ww = fold1(part_ww, n_parts);
@@ -322,6 +378,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> 
     mo->do_v0 = 0;
     const bool exhausted = hn == T(0), conv = fabs((double)gn) < sc->tol, last = iters == sc->iter_max, full = j == mo->m;
     const bool stop = exhausted || conv || last;
+    mo->enter = stop ? 0u : 1u;  // (iters == iter_max is a stop)
     if (!(stop || full)) {
         mo->do_end = 0;
         return;
@@ -346,10 +403,11 @@ __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> 
     }
 }
 
-// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
-template <typename T>
-int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant, size_t check_every,
-            size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kGmTri's handle (else unused).
+// kGmNone's chain of launches is the unpreconditioned solver's, launch for launch.
+template <typename T, GmPrecond P>
+int gmres_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
+            size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     constexpr size_t V = 16 / sizeof(T);
     SolveRun run;  // (its `converged` means STOPPED here)
@@ -358,10 +416,12 @@ int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t ite
     const unsigned grid = pcg_grid(n);
     const uint64_t ld = (n + V - 1) / V * V;
     const int rc = run.run([&]() -> int {
+        if constexpr (P == kGmTri) SMH_TRY(precond_prepare(pc));
         SMH_TRY(run.own_stream());
         const hipStream_t s = run.s;
         Scratch &ws = run.ws;
         T *x = nullptr, *r = nullptr, *w = nullptr, *vin = nullptr, *basis = nullptr, *part = nullptr, *part_ww = nullptr;
+        T *diag = nullptr, *u = nullptr, *tw = nullptr;  // Jacobi: the diagonal.  Tri: u = M^-1 v_j and the solves' scratch
         GmScalars<T> *sc = nullptr;
         GmMore<T> *mo = nullptr;
         SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&w, n)); SMH_TRY(ws.alloc(&vin, n));
@@ -372,16 +432,32 @@ int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t ite
         SMH_TRY(ws.alloc(&mo, 1));
         constexpr size_t more_head = offsetof(GmMore<T>, hn);
         SMH_TRY(run.h_sc.alloc(sizeof(GmScalars<T>) + more_head, hipHostMallocDefault));
+        if constexpr (P != kGmNone) {
+            unsigned long long *d_bad = nullptr;
+            SMH_TRY(ws.alloc(&d_bad, 1));
+            if constexpr (P == kGmJacobi) {
+                SMH_TRY(ws.alloc(&diag, n));
+                SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
+            } else {
+                SMH_TRY(ws.alloc(&u, n)); SMH_TRY(ws.alloc(&tw, n));
+                SMH_TRY(probe_diagonal(pc.f, n, u, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+            }
+        }
         // r = b - A x (w: scratch); rr = r.r; beta; v_0
         hipLaunchKernelGGL((k_gm_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max, (uint32_t)restart);
         SMH_TRY(stage_residual(m, variant, b_in, x_io, n, r, x, w, s));
         hipLaunchKernelGGL((k_gm_rr<T>), dim3(grid), dim3(kBlock), 0, s, r, (uint64_t)n, part_ww);
         hipLaunchKernelGGL((k_gm_begin<T, true>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
-        hipLaunchKernelGGL((k_gm_norm<T, true>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n);
+        hipLaunchKernelGGL((k_gm_norm<T, true, P>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n, diag);
         SMH_HIP(hipGetLastError());
         const dim3 cols((unsigned)restart + 1);
         auto body = [&]() -> int {
-            SMH_TRY(spmv_enqueue(m, vin, n, w, variant, s));
+            if constexpr (P == kGmTri) {
+                SMH_TRY(precond_apply_enqueue(pc, vin, tw, u, &mo->enter, s));
+                SMH_TRY(spmv_enqueue(m, u, n, w, variant, s));
+            } else {
+                SMH_TRY(spmv_enqueue(m, vin, n, w, variant, s));
+            }
             hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
             hipLaunchKernelGGL((k_gm_fold<T, 1>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
             hipLaunchKernelGGL((k_gm_update<T, 1>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
@@ -389,14 +465,25 @@ int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t ite
             hipLaunchKernelGGL((k_gm_fold<T, 2>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
             hipLaunchKernelGGL((k_gm_update<T, 2>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
             hipLaunchKernelGGL((k_gm_step<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
-            hipLaunchKernelGGL((k_gm_norm<T, false>), dim3(grid), dim3(kBlock), 0, s, mo, w, basis, ld, vin, (uint64_t)n);
-            hipLaunchKernelGGL((k_gm_xr<T>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gm_norm<T, false, P>), dim3(grid), dim3(kBlock), 0, s, mo, w, basis, ld, vin, (uint64_t)n, diag);
+            hipLaunchKernelGGL((k_gm_xr<T, P>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww, diag, w);  // (w is free)
             hipLaunchKernelGGL((k_gm_begin<T, false>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
-            hipLaunchKernelGGL((k_gm_norm<T, true>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n);
+            if constexpr (P == kGmTri) {  // q = M^-1 t in place, x += q: due at a cycle end alone
+                SMH_TRY(precond_apply_enqueue(pc, w, tw, w, &mo->do_end, s));
+                hipLaunchKernelGGL((k_gm_xadd<T>), dim3(grid), dim3(kBlock), 0, s, mo, x, w, (uint64_t)n);
+            }
+            hipLaunchKernelGGL((k_gm_norm<T, true, P>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n, diag);
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        if constexpr (P == kGmTri) {
+            // the node budget of a captured batch (pcg.hip's): two applications, the product (a few nodes at most) and the chain of 12
+            bool capture = true;
+            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 1 + 3 + 12, check_every, &capture);
+            SMH_TRY(run.loop(dt, iter_max, bodies, body, sc, capture));
+        } else {
+            SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        }
         GmMore<T> *h_mo = (GmMore<T> *)((char *)run.h_sc.get() + sizeof(GmScalars<T>));  // (its head alone)
         SMH_HIP(hipMemcpyAsync(h_mo, mo, more_head, hipMemcpyDeviceToHost, s));
         if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
@@ -410,13 +497,37 @@ int gmres_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t ite
     return rc;
 }
 
-int gmres(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant, size_t check_every,
-          size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+template <typename T>
+int gmres_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
+            size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    const T *b = (const T *)b_in;
+    T *x = (T *)x_io;
+    const TriPrecond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
+    switch (precond) {
+    case SMH_PRECOND_NONE:
+        return gmres_t<T, kGmNone>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    case SMH_PRECOND_JACOBI:
+        return gmres_t<T, kGmJacobi>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    default:
+        if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+        return gmres_t<T, kGmTri>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    }
+}
+
+// precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
+int gmres(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
+          size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     if (m->dtype == SMH_F64)
-        return gmres_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out,
-                               cycles_out, breakdown_out);
-    return gmres_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
-                          breakdown_out);
+        return gmres_p<double>(m, precond, f, b_in, x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    return gmres_p<float>(m, precond, f, b_in, x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+}
+
+// what the preconditioned entry points decide about `precond` and `f` before anything else
+int check_precond(int precond, const smh_crs *f) {
+    if (precond < SMH_PRECOND_NONE || precond > SMH_PRECOND_ILU) return fail(SMH_ERR_INVALID, "precond is %d: it must be one of SMH_PRECOND_*", precond);
+    if (precond == SMH_PRECOND_ILU && !f) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (precond != SMH_PRECOND_ILU && f) return fail(SMH_ERR_INVALID, "a factor handle goes with SMH_PRECOND_ILU alone");
+    return SMH_OK;
 }
 
 constexpr size_t kGmCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
@@ -428,12 +539,37 @@ extern "C" int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, dou
                                    size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(m, b->d, x->d, m->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    return gmres(m, SMH_PRECOND_NONE, nullptr, b->d, x->d, m->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
+                 breakdown_out);
 }
 
 extern "C" int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                size_t restart, int variant, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(m, b_host, x_host_inout, m->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out, breakdown_out);
+    return gmres(m, SMH_PRECOND_NONE, nullptr, b_host, x_host_inout, m->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out,
+                 cycles_out, breakdown_out);
+}
+
+// Right-preconditioned: `precond` and `f` first, then the checks above (with ILU's factor against the matrix, as smh_pcg_ilu_solve);
+// what needs the device -- a stored column >= n, a zero or absent diagonal entry -- is decided in the driver before its first launch
+extern "C" int smh_gmres_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                                           size_t restart, int variant, size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out,
+                                           int *breakdown_out) {
+    SMH_TRY(check_precond(precond, f));
+    if (precond == SMH_PRECOND_NONE) return smh_gmres_solve_vec(a, b, x, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery, f));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres(a, precond, f, b->d, x->d, a->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+}
+
+extern "C" int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                                       double tol, size_t iter_max, size_t restart, int variant, size_t *iters_out, double *rr_out,
+                                       size_t *cycles_out, int *breakdown_out) {
+    SMH_TRY(check_precond(precond, f));
+    if (precond == SMH_PRECOND_NONE) return smh_gmres_solve(a, b_host, b_len, x_host_inout, x_len, tol, iter_max, restart, variant, iters_out, rr_out, cycles_out, breakdown_out);
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, f));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out,
+                 breakdown_out);
 }

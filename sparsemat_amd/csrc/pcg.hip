@@ -16,18 +16,19 @@
 // The sweeps state their arithmetic once, on solver_tree.hpp's sweep; the sums and the one-workgroup folds of their partials are
 // its tree (block_sums / block_sum1, fold1 / fold2) -- deterministic.
 // The second half of the file is the same recurrence preconditioned by two level-scheduled triangular solves (trisolve.hip) on one
-// handle (TriPrecond), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
+// handle (TriPrecond, precond.hpp), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
 // (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec) solves on the matrix itself, ILU(0) (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) on a
 // factor handle (ilu.hip).
 // Host side: both drivers (pcg_t, pcg_tri_t) are their allocations, their set-up launches, a body lambda and SolveRun::run
-// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe and the source of p.Ap are one
-// function each here (probe_diagonal, pap_source); the entry points' argument checks are solver_host.hpp's.
+// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe, TriPrecond and the node budget of a
+// captured batch are precond.hpp's (shared with gmres.hip), the source of p.Ap one function here (pap_source); the entry points'
+// argument checks are solver_host.hpp's.
 #include "internal.hpp"
+#include "precond.hpp"
 #include "solver_host.hpp"
 #include "solver_tree.hpp"
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 using namespace smh;
@@ -37,20 +38,6 @@ unsigned reduce_blocks(size_t n);  // blas1.hip
 }
 
 namespace {
-
-// d[i] = get(i, i); *bad = the smallest row whose diagonal entry is zero or absent (stays ~0 when there is none)
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-k_pcg_diag(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val, uint64_t n, T *__restrict__ d,
-           unsigned long long *bad) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        T v = T(0);
-        for (uint64_t q = off[i]; q < off[i + 1]; ++q)
-            if (col[q] == i) { v = val[q]; break; }
-        d[i] = v;
-        if (v == T(0)) atomicMin(bad, (unsigned long long)i);
-    }
-}
 
 // ---- device-resident scalars (like cg.hip): nothing of an iteration passes through the host ---------------------------
 template <typename T>
@@ -181,22 +168,7 @@ k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__rest
     });
 }
 
-// ---- host side: what the Jacobi driver here and the triangular one below share ------------------------------------------------------
-// d[i] = get(i, i) of h, on s once h's own stream has finished, and the verdict: a zero or absent diagonal entry cannot be divided by
-// (name: whose refusal it is; d_bad: one word of scratch)
-template <typename T>
-int probe_diagonal(const smh_crs *h, size_t n, T *d, unsigned long long *d_bad, const char *name, hipStream_t s) {
-    SMH_HIP(hipStreamSynchronize(h->stream));  // (the handle is read on another stream than the one that wrote it)
-    unsigned long long bad = ~0ull;
-    SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
-    if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, h->d_off, h->d_col, (const T *)h->d_val, (uint64_t)n, d, d_bad);
-    SMH_HIP(hipGetLastError());
-    SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-    SMH_HIP(hipStreamSynchronize(s));
-    if (bad != ~0ull) return fail(SMH_ERR_INVALID, "%s: zero or absent diagonal entry in row %llu", name, bad);
-    return SMH_OK;
-}
-
+// ---- host side: what the Jacobi driver here and the triangular one below share (the zero-diagonal probe: precond.hpp) --------------------
 // Where p.Ap comes from after the product Ap = A p that was handed d_dot: out of the product's epilogue when the kernel offers it
 // (K1s: n_dot per-tile partials in d_dot; more than 1024 of them are folded by a full grid first), else a separate two-stage dot.
 // Enqueues what that takes and returns what k_pcg_alpha folds.  dot_scratch: 2 * kReducePartials + 8 values (the dot's partials,
@@ -347,38 +319,6 @@ __global__ void __launch_bounds__(kBlock) k_sgs_p(const PcgScalars<T> *__restric
     });
 }
 
-// most nodes of a captured batch (a linear chain): beyond it the bodies per batch go down, and a single body beyond it runs
-// uncaptured.  How the bodies reach the device changes no bit.  SMH_SGS_GRAPH_NODES: tuning knob
-size_t sgs_graph_nodes() {
-    if (const char *e = getenv("SMH_SGS_GRAPH_NODES")) return (size_t)strtoull(e, nullptr, 10);
-    return 4096;
-}
-
-// A preconditioner applied by two triangular solves on one handle: z = T_upper^-1 (scale(T_lower^-1 r)).  SGS: the matrix itself,
-// both diagonals stored, the right-hand side of the upper solve scaled by the diagonal.  ILU(0): the factor handle (ilu.hip), the
-// lower solve with the unit diagonal, no scaling.
-struct TriPrecond {
-    smh_crs *f;
-    int lower_diag;
-    bool scale_rhs;
-    const char *name;
-};
-TriPrecond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
-TriPrecond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
-
-// z = M^-1 r on stream s (w: n values of scratch; z may be r; the schedules exist)
-int precond_apply_enqueue(const TriPrecond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
-    SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.lower_diag, false, r, w, active, s));
-    return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
-}
-
-// the checks of a preconditioner handle that need the device: columns, schedules, a stored diagonal in every row
-int precond_prepare(const TriPrecond &pc) {
-    SMH_TRY(columns_within_n_cols(pc.f, pc.name));
-    SMH_TRY(ensure_tri_schedule(pc.f, SMH_TRI_LOWER));
-    return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
-}
-
 // b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
 template <typename T>
 int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
@@ -432,11 +372,9 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
             return SMH_OK;
         };
         // the node budget of a captured batch: the two solves' launches, the product (a few nodes at most) and the tail of 8
-        const size_t per_body = pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size() + spmv_nodes + 3 + 8;
-        const size_t budget = sgs_graph_nodes();
-        size_t bodies = check_every;
-        if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
-        SMH_TRY(run.loop(dt, iter_max, bodies, body, d_sc, per_body <= budget));
+        bool capture = true;
+        const size_t bodies = bodies_within_budget(precond_apply_nodes(pc) + spmv_nodes + 3 + 8, check_every, &capture);
+        SMH_TRY(run.loop(dt, iter_max, bodies, body, d_sc, capture));
         if (n) SMH_HIP(hipMemcpyAsync(x_io, d_x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;

@@ -1,0 +1,86 @@
+// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS- and ILU-PCG; gmres.hip: the right-preconditioned
+// GMRES): the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle (TriPrecond) and the
+// node budget of a captured batch that holds such applications.
+#pragma once
+#include "internal.hpp"
+#include "solver_tree.hpp"
+
+#include <cstdlib>
+
+namespace smh {
+
+// d[i] = get(i, i); *bad = the smallest row whose diagonal entry is zero or absent (stays ~0 when there is none)
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_pcg_diag(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val, uint64_t n, T *__restrict__ d,
+           unsigned long long *bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        T v = T(0);
+        for (uint64_t q = off[i]; q < off[i + 1]; ++q)
+            if (col[q] == i) { v = val[q]; break; }
+        d[i] = v;
+        if (v == T(0)) atomicMin(bad, (unsigned long long)i);
+    }
+}
+
+// d[i] = get(i, i) of h, on s once h's own stream has finished, and the verdict: a zero or absent diagonal entry cannot be divided by
+// (name: whose refusal it is; d_bad: one word of scratch)
+template <typename T>
+int probe_diagonal(const smh_crs *h, size_t n, T *d, unsigned long long *d_bad, const char *name, hipStream_t s) {
+    SMH_HIP(hipStreamSynchronize(h->stream));  // (the handle is read on another stream than the one that wrote it)
+    unsigned long long bad = ~0ull;
+    SMH_HIP(hipMemcpyAsync(d_bad, &bad, sizeof bad, hipMemcpyHostToDevice, s));
+    if (n) hipLaunchKernelGGL((k_pcg_diag<T>), dim3(pcg_grid(n) * 4), dim3(kBlock), 0, s, h->d_off, h->d_col, (const T *)h->d_val, (uint64_t)n, d, d_bad);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+    SMH_HIP(hipStreamSynchronize(s));
+    if (bad != ~0ull) return fail(SMH_ERR_INVALID, "%s: zero or absent diagonal entry in row %llu", name, bad);
+    return SMH_OK;
+}
+
+// most nodes of a captured batch (a linear chain): beyond it the bodies per batch go down, and a single body beyond it runs
+// uncaptured.  How the bodies reach the device changes no bit.  SMH_SGS_GRAPH_NODES: tuning knob
+inline size_t sgs_graph_nodes() {
+    if (const char *e = getenv("SMH_SGS_GRAPH_NODES")) return (size_t)strtoull(e, nullptr, 10);
+    return 4096;
+}
+
+// A preconditioner applied by two triangular solves on one handle: z = T_upper^-1 (scale(T_lower^-1 r)).  SGS: the matrix itself,
+// both diagonals stored, the right-hand side of the upper solve scaled by the diagonal.  ILU(0): the factor handle (ilu.hip), the
+// lower solve with the unit diagonal, no scaling.
+struct TriPrecond {
+    smh_crs *f;
+    int lower_diag;
+    bool scale_rhs;
+    const char *name;
+};
+inline TriPrecond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
+inline TriPrecond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
+
+// z = M^-1 r on stream s (w: n values of scratch; z may be r; the schedules exist)
+inline int precond_apply_enqueue(const TriPrecond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
+    SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.lower_diag, false, r, w, active, s));
+    return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
+}
+
+// the launches of one application (the schedules exist)
+inline size_t precond_apply_nodes(const TriPrecond &pc) { return pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size(); }
+
+// the checks of a preconditioner handle that need the device: columns, schedules, a stored diagonal in every row
+inline int precond_prepare(const TriPrecond &pc) {
+    SMH_TRY(columns_within_n_cols(pc.f, pc.name));
+    SMH_TRY(ensure_tri_schedule(pc.f, SMH_TRI_LOWER));
+    return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
+}
+
+// The bodies of a captured batch under the node budget, per_body nodes each: check_every, fewer when that many are beyond the
+// budget, one when a single body is (*capture: whether a batch is captured at all).
+inline size_t bodies_within_budget(size_t per_body, size_t check_every, bool *capture) {
+    const size_t budget = sgs_graph_nodes();
+    size_t bodies = check_every;
+    if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
+    *capture = per_body <= budget;
+    return bodies;
+}
+
+}  // namespace smh

@@ -15,7 +15,8 @@
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
                                device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
 * ``GMRES``                 -- an extension for non-symmetric systems: restarted GMRES(m), the robust companion of ``BiCGStab``
-                               (``smh_gmres_solve*``); its Krylov basis stays on the device.
+                               (``smh_gmres_solve*``); its Krylov basis stays on the device.  ``precond="jacobi"``, ``"sgs"`` or
+                               ``"ilu"``: right-preconditioned (``smh_gmres_precond_solve*``).
 """
 import math
 
@@ -181,18 +182,41 @@ class GMRES(_DeviceSolver):
     After ``solve``: ``iterations`` (bodies entered), ``r_norm_squared`` (the r.r of the residual rebuilt from the basis at the
     last cycle end -- no product is spent on it --, the initial residual's before the first; as f64), ``cycles`` (the number of
     times a v_0 was formed) and ``breakdown`` (0 none; 1 the Krylov space is exhausted: x is updated from it; 2 the residual
-    at a cycle's start is exactly zero: x is the solution as it stands)."""
+    at a cycle's start is exactly zero: x is the solution as it stands).
 
-    def __init__(self, tol=1e-12, iter_max=10_000, restart=30, variant="auto", check_every=0):
+    ``precond``: None, "jacobi", "sgs" or "ilu" -- RIGHT preconditioning (``smh_gmres_precond_solve*``): A M^-1 u = b, x = M^-1 u,
+    so the residual GMRES minimises is the true one and the stop rule, ``r_norm_squared``, ``cycles`` and ``breakdown`` keep their
+    meaning.  M^-1 is applied once per body and once per cycle end: a division by the diagonal fused into the solver's sweeps
+    ("jacobi"), or ``SparseMatCRS.sgs_apply`` / ``ilu_apply``'s two level-scheduled triangular solves ("sgs" on the matrix, "ilu" on
+    a factor).  ``solve(mat, b, x, factor=None)`` with "ilu" factors ``mat`` itself when no factor is given (afterwards ``factor``
+    holds the one used and ``zero_pivot`` what its factorization reported, None for a passed factor).  ``r_norm_squared`` is the
+    RECURRENCE residual's: where the triangular solves amplify rounding (a matrix far from diagonally dominant) it parts from
+    |b - A x|^2 -- form that yourself when it matters."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, restart=30, variant="auto", check_every=0, precond=None):
         super().__init__(tol, iter_max, variant, check_every)
+        if precond not in _lib.PRECONDS:
+            raise ValueError('precond must be None, "jacobi", "sgs" or "ilu"')
         self.restart = int(restart)
+        self.precond = precond
         self.cycles = None
         self.breakdown = None
+        self.factor = None
+        self.zero_pivot = None
 
-    def solve(self, mat, b, x):
+    def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
         SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
         cycles, brk = C.c_size_t(), C.c_int()
-        self._solve(lib().smh_gmres_solve_vec, lib().smh_gmres_solve, mat, b, x, extra_out=(cycles, brk), extra_in=(self.restart,))
+        if self.precond is None and factor is None:
+            self._solve(lib().smh_gmres_solve_vec, lib().smh_gmres_solve, mat, b, x, extra_out=(cycles, brk), extra_in=(self.restart,))
+        else:
+            self.zero_pivot = None
+            if self.precond == "ilu" and factor is None:
+                factor, self.zero_pivot = mat.ilu0()
+            self.factor = factor
+            self._solve(lib().smh_gmres_precond_solve_vec, lib().smh_gmres_precond_solve, mat, b, x,
+                        handles=(_lib.PRECONDS[self.precond], factor._h if factor is not None else None), extra_out=(cycles, brk),
+                        extra_in=(self.restart,))
         self.cycles, self.breakdown = cycles.value, brk.value
         return x
