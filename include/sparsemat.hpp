@@ -727,28 +727,51 @@ class ILUConjugateGradient {
 // BiCGSTAB for non-symmetric systems -- an extension, not in the reference (smh_bicgstab_solve*): device-resident like
 // ConjugateGradient, same panics and stop rule.  breakdown(): 0 none, 1 rho' == 0 or omega == 0, 2 r^.v == 0, 3 t.t == 0
 // (sparsemat_hip.h); a breakdown ends the solve without a panic.
+// precond (smh_bicgstab_precond_solve*): SMH_PRECOND_NONE (the default: the calls above), _JACOBI, _SGS or _ILU -- right
+// preconditioning, A M^-1 u = b, x = M^-1 u, as GMRES below.  SMH_PRECOND_ILU takes the factor (mat.ilu0()) or, in the overloads
+// without one, factors mat first.
 class BiCGStab {
   public:
     BiCGStab() = default;
-    BiCGStab(double tol, size_t iter_max) : tol_(tol), iter_max_(iter_max) {}
+    BiCGStab(double tol, size_t iter_max, int precond = SMH_PRECOND_NONE) : tol_(tol), iter_max_(iter_max), precond_(precond) {}
     template <typename T>
     void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &b, DenseVec<T> &x) {
+        if (precond_ == SMH_PRECOND_ILU) return solve(mat, mat.ilu0(), b, x);
+        if (precond_ != SMH_PRECOND_NONE) return solve_precond(mat, nullptr, b, x);
         detail::check(smh_bicgstab_solve_vec(mat.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0, &iterations_,
                                              &r_norm_squared_, &breakdown_));
     }
     // host vectors, x updated in place
     template <typename T>
     void solve(const SparseMatCRS<T> &mat, const std::vector<T> &b, std::vector<T> &x) {
+        if (precond_ == SMH_PRECOND_ILU) return solve(mat, mat.ilu0(), b, x);
+        if (precond_ != SMH_PRECOND_NONE) return solve_precond(mat, nullptr, b, x);
         detail::check(smh_bicgstab_solve(mat.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, SMH_SPMV_AUTO,
                                          &iterations_, &r_norm_squared_, &breakdown_));
+    }
+    // ... with the ILU(0) factor of mat (a factor with another kind is the library's SMH_ERR_INVALID)
+    template <typename T, typename V>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const V &b, V &x) {
+        solve_precond(mat, factor.handle(), b, x);
     }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }
     int breakdown() const { return breakdown_; }
 
   private:
+    template <typename T>
+    void solve_precond(const SparseMatCRS<T> &mat, smh_crs *factor, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_bicgstab_precond_solve_vec(mat.handle(), precond_, factor, b.handle(), x.handle(), tol_, iter_max_,
+                                                     SMH_SPMV_AUTO, 0, &iterations_, &r_norm_squared_, &breakdown_));
+    }
+    template <typename T>
+    void solve_precond(const SparseMatCRS<T> &mat, smh_crs *factor, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_bicgstab_precond_solve(mat.handle(), precond_, factor, b.data(), b.size(), x.data(), x.size(), tol_, iter_max_,
+                                                 SMH_SPMV_AUTO, &iterations_, &r_norm_squared_, &breakdown_));
+    }
     double tol_ = 1e-12;
     size_t iter_max_ = 10000;
+    int precond_ = SMH_PRECOND_NONE;
     size_t iterations_ = 0;
     double r_norm_squared_ = 0.0;
     int breakdown_ = 0;

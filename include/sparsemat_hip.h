@@ -46,7 +46,7 @@ extern "C" {
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
  * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
  * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
- * smh_gmres_precond_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -839,6 +839,32 @@ int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_h
 int smh_gmres_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol,
                                 size_t iter_max, size_t restart, int variant, size_t check_every,
                                 size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+
+/* Right-preconditioned BiCGSTAB -- an EXTENSION: A M^-1 u = b, x = M^-1 u, inside smh_bicgstab_solve's recurrence, so the residual it
+ * carries is the true one, b - A x, and the stop rule, rr, iters and the three breakdown codes keep their meaning.  Everything not
+ * named here is smh_bicgstab_solve's contract, word for word.  One rounding per operation, nothing contracted:
+ *   set-up:  unchanged (r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r; M is not applied to the residual)
+ *   body:    p^ = M^-1 p;  v = A p^;  rv = r^.v;                 rv == 0: breakdown 2 (x untouched)
+ *            alpha = rho / rv;  s = r - v*alpha;  ss = s.s
+ *                                                             sqrt(f64(ss)) < tol: x += p^*alpha; rr = ss; converged
+ *            s^ = M^-1 s;  t = A s^;  ts = t.s;  tt = t.t;       tt == 0: x += p^*alpha; rr = ss; breakdown 3
+ *            omega = ts / tt;  x = (x + p^*alpha) + s^*omega;  r = s - t*omega;  rr = r.r;  rho' = r^.r
+ *            the stop test, breakdown 1, beta and p = r + (p - v*omega)*beta: unchanged
+ * precond and f are smh_gmres_precond_solve's: SMH_PRECOND_JACOBI divides by the first stored (i, i); SMH_PRECOND_SGS applies
+ * smh_crs_sgs_apply_vec's operations on a itself; SMH_PRECOND_ILU smh_crs_ilu_apply_vec's on the factor handle f;
+ * SMH_PRECOND_NONE forwards to smh_bicgstab_solve*: its bits.  f is the ILU factor and NULL for every other kind: a non-NULL f
+ * with another kind, a NULL f with SMH_PRECOND_ILU and any other value of precond are SMH_ERR_INVALID, decided first.  Memory:
+ * ten vectors of n against seven.  A batch of many kernel launches (two applications per body) is replayed in smaller batches or
+ * launched plainly, which changes no bit.  rr is the RECURRENCE residual's r.r, as it is in smh_bicgstab_solve.
+ * Statuses, decided before any launch of the solve: smh_bicgstab_solve's; then what smh_gmres_precond_solve decides about the
+ * preconditioner, with its codes and messages (ILU: f's n, dtype, device, an orphaned entry, a zero or absent diagonal entry, a
+ * stored column >= n; SGS: the same about a; Jacobi: a zero or absent diagonal entry of a). */
+int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout,
+                               size_t x_len, double tol, size_t iter_max, int variant,
+                               size_t *iters_out, double *rr_out, int *breakdown_out);
+int smh_bicgstab_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol,
+                                   size_t iter_max, int variant, size_t check_every,
+                                   size_t *iters_out, double *rr_out, int *breakdown_out);
 
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;

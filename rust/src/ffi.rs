@@ -74,6 +74,13 @@ extern "C" {
     pub fn smh_gmres_precond_solve_vec(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec,
                                        tol: c_double, iter_max: usize, restart: usize, variant: c_int, check_every: usize,
                                        iters_out: *mut usize, rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    // extension: BiCGSTAB right-preconditioned the same way (precond and f as above)
+    pub fn smh_bicgstab_precond_solve(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b_host: *const c_void, b_len: usize,
+                                      x_host_inout: *mut c_void, x_len: usize, tol: c_double, iter_max: usize, variant: c_int,
+                                      iters_out: *mut usize, rr_out: *mut c_double, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_bicgstab_precond_solve_vec(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec,
+                                          tol: c_double, iter_max: usize, variant: c_int, check_every: usize,
+                                          iters_out: *mut usize, rr_out: *mut c_double, breakdown_out: *mut c_int) -> c_int;
     // extensions (not in the reference): level-scheduled sparse triangular solves, the symmetric Gauss-Seidel preconditioner
     // M = (D + L) D^-1 (D + U) built on them, and its CG (same contract as smh_pcg_jacobi_solve)
     pub fn smh_crs_trisolve_levels(m: *mut smh_crs, uplo: c_int, n_levels_out: *mut usize, level_of_row_out: *mut u32,

@@ -103,6 +103,19 @@ impl BiCGStab {
         });
         (iters, rr, breakdown as i32)
     }
+
+    /// `solve` right-preconditioned (`smh_bicgstab_precond_solve`): `precond` is one of `ffi::SMH_PRECOND_*`, `factor` the ILU(0)
+    /// factor's handle with `SMH_PRECOND_ILU` and `None` otherwise.
+    pub fn solve_preconditioned<T: HipValue>(&self, mat: &DeviceCrs, precond: std::os::raw::c_int, factor: Option<&DeviceCrs>, b: &[T],
+                                             x: &mut [T]) -> (usize, f64, i32) {
+        let (mut iters, mut rr, mut breakdown) = (0usize, 0f64, 0 as std::os::raw::c_int);
+        let f = factor.map_or(std::ptr::null_mut(), |f| f.handle);
+        check(unsafe {
+            ffi::smh_bicgstab_precond_solve(mat.handle, precond, f, b.as_ptr() as *const c_void, b.len(), x.as_mut_ptr() as *mut c_void,
+                                            x.len(), self.tol, self.iter_max, ffi::SMH_SPMV_AUTO, &mut iters, &mut rr, &mut breakdown)
+        });
+        (iters, rr, breakdown as i32)
+    }
 }
 
 /// Restarted GMRES(m) for non-symmetric systems -- an extension, not in the reference (`smh_gmres_solve`): the robust companion of

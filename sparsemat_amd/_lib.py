@@ -201,6 +201,10 @@ SIGNATURES = {
                                        C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_gmres_precond_solve_vec": (_int, [_vp, _int, _vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),
                                            C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_bicgstab_precond_solve": (_int, [_vp, _int, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
+                                          C.POINTER(C.c_double), C.POINTER(_int)]),
+    "smh_bicgstab_precond_solve_vec": (_int, [_vp, _int, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
+                                              C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_comm_unique_id": (_int, [_vp]),
     "smh_comm_create": (_int, [_vp, _int, _int, C.POINTER(_vp)]),
     "smh_comm_destroy": (_int, [_vp]),

@@ -25,9 +25,30 @@
 // Bodies enqueued past the stop are no-ops, so x, rr, iters and the code are the stopping body's wherever it falls in a batch.
 // Sweeps and reductions: solver_tree.hpp's everywhere -- its sweep, its workgroup sums, fold1 / fold2 over the partials --
 // deterministic, no float atomics.  One stream, one linear chain of launches.
+//
+// Right-preconditioned (smh_bicgstab_precond_solve*): A M^-1 u = b, x = M^-1 u, so the residual the recurrence carries is the true
+// one and the stop rule, rr, iters and the three codes keep their meaning.  What changes in the recurrence above:
+//   set-up:  nothing (M is not applied to the residual)
+//   body:    p^ = M^-1 p;  v = A p^;   ...   s^ = M^-1 s;  t = A s^;   x takes p^*alpha and s^*omega (r, the dots and p as above)
+// x does not feed back, so from x0 = 0 every scalar is the unpreconditioned recurrence's on the product A o M^-1.
+// The driver and the kernels that differ are instantiated per BiPrecond; kBiNone's chain of launches is the one described above,
+// launch for launch.
+// kBiJacobi: M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe), and costs no launch in a body: the p
+// sweep writes p and p^ = p / d (4 n -> 6 n), the s sweep s and s^ = s / d (3 n -> 5 n), the x / r sweep reads p^ and s^ for x and s for
+// r (7 n -> 8 n; dividing p and s again in registers would read d for one of them: the same 8 n, and two divisions more) -- 23 n
+// values beside the two products, against 18 n.  The set-up forms p^ = r / d in one sweep of its own.  Ten vectors of storage.
+// kBiTri: M^-1 is two level-scheduled triangular solves on one handle (TriPrecond, precond.hpp: SGS on the matrix itself, ILU(0) on a
+// factor).  The body opens with the application p -> p^ and the s application s -> s^ follows the half-step stage; the products read
+// p^ and s^; the sweeps are kBiNone's but for the x / r sweep (8 n).  Every triangular launch takes a device gate word: the s
+// application `active`, the p application BiMore::enter -- "the next body will be entered" -- which the set-up leaves (iter_max == 0
+// closes it), every stage that stops and a body that is not entered clear, and the beta stage sets (iters == iter_max is a stop
+// there); so bodies enqueued past the stop run no solve.  Ten vectors of storage (p^, s^, the solves' scratch).  A captured batch
+// holds two applications per body: bodies_within_budget (precond.hpp) makes the batches smaller or drops the capture, which changes
+// no bit.
 // Host side: the driver (bicgstab_t) is its allocations, its set-up launches, the body lambda and SolveRun::run (solver_host.hpp:
 // the stream of its own, the workspaces, the drain, r = b - A x); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
+#include "precond.hpp"
 #include "solver_host.hpp"
 #include "solver_tree.hpp"
 
@@ -36,6 +57,9 @@
 using namespace smh;
 
 namespace {
+
+// how M^-1 is applied (the header's last paragraphs): not at all, inside the sweeps, or by two triangular solves on a handle
+enum BiPrecond { kBiNone, kBiJacobi, kBiTri };
 
 // ---- device-resident scalars ---------------------------------------------------------------------------------------------
 // the block the host polls through CG's reader (cg_read_scalars): rr, the stop word and the body count sit where CG's do
@@ -56,7 +80,7 @@ template <typename T>
 struct BiMore {
     T rho, rv, ss, ts, tt, omega;
     uint32_t breakdown;  // 0 none, 1 rho' == 0 or omega == 0, 2 r^.v == 0, 3 t.t == 0 (a stop with code 0 was a stop test's)
-    uint32_t pad_;
+    uint32_t enter;      // gate: the next body will be entered (kBiTri's application p -> p^ that opens it is due)
 };
 
 template <typename T>
@@ -67,7 +91,7 @@ __global__ void k_bi_init(BiScalars<T> *sc, BiMore<T> *mo, double tol, uint64_t 
     sc->iter_max = iter_max;
     sc->tol = tol;
     mo->rho = mo->rv = mo->ss = mo->ts = mo->tt = mo->omega = T(0);
-    mo->breakdown = mo->pad_ = 0;
+    mo->breakdown = mo->enter = 0;
 }
 
 // ---- the sweeps (solver_tree.hpp's sweep: the workspaces are pool allocations, aligned) ---------------------------------------------
@@ -97,10 +121,11 @@ k_bi_dot2(const BiScalars<T> *__restrict__ sc, const T *__restrict__ t, const T 
     block_sums(a_ts, a_tt, part_ts, part_tt);
 }
 
-// s = r - v*alpha; partials of s.s
-template <typename T>
+// s = r - v*alpha; partials of s.s.  kBiJacobi: and s^ = s / diag, the second product's input
+template <typename T, BiPrecond P = kBiNone>
 __global__ void __launch_bounds__(kBlock)
-k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__restrict__ v, T *__restrict__ s, uint64_t n, T *__restrict__ part_ss) {
+k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__restrict__ v, T *__restrict__ s, uint64_t n, T *__restrict__ part_ss,
+       const T *__restrict__ diag = nullptr, T *__restrict__ shat = nullptr) {
     if (!sc->active) return;
     const T alpha = sc->alpha;
     T acc = T(0);
@@ -113,15 +138,23 @@ k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__
             acc = p_add(acc, p_mul(sv[e], sv[e]));
         }
         at.store(s, sv);
+        if constexpr (P == kBiJacobi) {
+            const auto dv = at.load(diag);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) sv[e] = p_div(sv[e], dv[e]);
+            at.store(shat, sv);
+        }
     });
     block_partial(acc, part_ss);
 }
 
-// xmode 2: x = (x + p*alpha) + s*omega; r = s - t*omega; partials of r.r and r^.r.  xmode 1 (half-step stop, breakdown 3): x += p*alpha
-template <typename T>
+// xmode 2: x = (x + p*alpha) + s*omega; r = s - t*omega; partials of r.r and r^.r.  xmode 1 (half-step stop, breakdown 3): x += p*alpha.
+// PRE (preconditioned): p is p^ in both modes and x takes shat = s^ where r takes s
+template <typename T, bool PRE = false>
 __global__ void __launch_bounds__(kBlock)
 k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ x, const T *__restrict__ p, const T *__restrict__ s,
-        const T *__restrict__ t, const T *__restrict__ rhat, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr, T *__restrict__ part_rho) {
+        const T *__restrict__ t, const T *__restrict__ rhat, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr, T *__restrict__ part_rho,
+        const T *__restrict__ shat = nullptr) {
     const uint32_t mode = sc->xmode;  // block-uniform
     if (mode == 0) return;
     const T alpha = sc->alpha;
@@ -140,10 +173,12 @@ k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T
     sweep<T>(n, [&](auto at) {
         auto xv = at.load(x);
         const auto pv = at.load(p), sv = at.load(s), tv = at.load(t), hv = at.load(rhat);
-        typename decltype(at)::pack rv;
+        typename decltype(at)::pack rv, qv;  // qv: what x takes beside p (s, or s^)
+        if constexpr (PRE) qv = at.load(shat);
+        else qv = sv;
 #pragma unroll
         for (int e = 0; e < at.width; ++e) {
-            xv[e] = p_add(p_add(xv[e], p_mul(pv[e], alpha)), p_mul(sv[e], omega));
+            xv[e] = p_add(p_add(xv[e], p_mul(pv[e], alpha)), p_mul(qv[e], omega));
             rv[e] = p_add(sv[e], -p_mul(tv[e], omega));
             a_rr = p_add(a_rr, p_mul(rv[e], rv[e]));
             a_rho = p_add(a_rho, p_mul(hv[e], rv[e]));
@@ -154,10 +189,11 @@ k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T
     block_sums(a_rr, a_rho, part_rr, part_rho);
 }
 
-// p = r + (p - v*omega)*beta
-template <typename T>
+// p = r + (p - v*omega)*beta.  kBiJacobi: and p^ = p / diag, the first product's input
+template <typename T, BiPrecond P = kBiNone>
 __global__ void __launch_bounds__(kBlock)
-k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ v, uint64_t n) {
+k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ v, uint64_t n,
+       const T *__restrict__ diag = nullptr, T *__restrict__ phat = nullptr) {
     if (!sc->active) return;
     const T beta = sc->beta, omega = mo->omega;
     sweep<T>(n, [&](auto at) {
@@ -166,6 +202,24 @@ k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T 
 #pragma unroll
         for (int e = 0; e < at.width; ++e) pv[e] = p_add(rv[e], p_mul(p_add(pv[e], -p_mul(vv[e], omega)), beta));
         at.store(p, pv);
+        if constexpr (P == kBiJacobi) {
+            const auto dv = at.load(diag);
+#pragma unroll
+            for (int e = 0; e < at.width; ++e) pv[e] = p_div(pv[e], dv[e]);
+            at.store(phat, pv);
+        }
+    });
+}
+
+// kBiJacobi's set-up: p^ = p / diag (p = r)
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_bi_phat0(const T *__restrict__ p, const T *__restrict__ diag, T *__restrict__ phat, uint64_t n) {
+    sweep<T>(n, [&](auto at) {
+        auto pv = at.load(p);
+        const auto dv = at.load(diag);
+#pragma unroll
+        for (int e = 0; e < at.width; ++e) pv[e] = p_div(pv[e], dv[e]);
+        at.store(phat, pv);
     });
 }
 
@@ -179,6 +233,7 @@ k_bi_setup(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rho, cons
     if (threadIdx.x == 0) {
         mo->rho = out2[0];
         sc->rr = out2[1];
+        mo->enter = sc->iter_max ? 1u : 0u;
     }
 }
 
@@ -187,7 +242,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock) k_bi_alpha(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
     const bool active = !sc->converged && sc->iters < sc->iter_max;  // (every thread reads before thread 0 writes: the fold has a barrier)
     if (!active) {
-        if (threadIdx.x == 0) sc->active = sc->xmode = 0;
+        if (threadIdx.x == 0) sc->active = sc->xmode = mo->enter = 0;
         return;
     }
     const T rv = fold1(part, n_parts);
@@ -198,7 +253,7 @@ __global__ void __launch_bounds__(kBlock) k_bi_alpha(BiScalars<T> *sc, BiMore<T>
         if (rv == T(0)) {
             mo->breakdown = 2;
             sc->converged = 1;
-            sc->active = 0;
+            sc->active = mo->enter = 0;
         } else {
             sc->active = 1;
             sc->alpha = p_div(mo->rho, rv);
@@ -217,7 +272,7 @@ __global__ void __launch_bounds__(kBlock) k_bi_half(BiScalars<T> *sc, BiMore<T> 
             sc->rr = ss;
             sc->xmode = 1;
             sc->converged = 1;
-            sc->active = 0;
+            sc->active = mo->enter = 0;
         }
     }
 }
@@ -238,7 +293,7 @@ k_bi_omega(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_ts, const
             sc->xmode = 1;
             mo->breakdown = 3;
             sc->converged = 1;
-            sc->active = 0;
+            sc->active = mo->enter = 0;
         } else {
             mo->omega = p_div(ts, tt);
             sc->xmode = 2;
@@ -258,31 +313,36 @@ k_bi_beta(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rr, const 
         sc->rr = rr;
         if (sqrt((double)rr) < sc->tol) {
             sc->converged = 1;
-            sc->active = 0;
+            sc->active = mo->enter = 0;
         } else if (rho_new == T(0) || omega == T(0)) {
             mo->breakdown = 1;
             sc->converged = 1;
-            sc->active = 0;
+            sc->active = mo->enter = 0;
         } else {
             sc->beta = p_mul(p_div(rho_new, mo->rho), p_div(sc->alpha, omega));
             mo->rho = rho_new;
+            mo->enter = sc->iters < sc->iter_max ? 1u : 0u;  // (iters == iter_max is a stop)
         }
     }
 }
 
-// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
-template <typename T>
-int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
-               double *rr_out, int *breakdown_out) {
+// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kBiTri's handle (else unused).
+// kBiNone's chain of launches is the unpreconditioned solver's, launch for launch.
+template <typename T, BiPrecond P>
+int bicgstab_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+               size_t *iters_out, double *rr_out, int *breakdown_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    constexpr bool PRE = P != kBiNone;
     SolveRun run;  // (its `converged` means STOPPED here)
     int breakdown = 0;
     const unsigned grid = pcg_grid(n);
     const int rc = run.run([&]() -> int {
+        if constexpr (P == kBiTri) SMH_TRY(precond_prepare(pc));
         SMH_TRY(run.own_stream());
         const hipStream_t s = run.s;
         Scratch &ws = run.ws;
         T *x = nullptr, *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *sv = nullptr, *t = nullptr, *part = nullptr;
+        T *phat = nullptr, *shat = nullptr, *diag = nullptr, *tw = nullptr;  // p^ and s^; Jacobi: the diagonal.  Tri: the solves' scratch
         BiScalars<T> *sc = nullptr;
         BiMore<T> *mo = nullptr;
         SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&rhat, n)); SMH_TRY(ws.alloc(&p, n));
@@ -291,6 +351,18 @@ int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t 
         SMH_TRY(ws.alloc(&sc, 1));
         SMH_TRY(ws.alloc(&mo, 1));
         SMH_TRY(run.h_sc.alloc(sizeof(BiScalars<T>) + sizeof(BiMore<T>), hipHostMallocDefault));
+        if constexpr (PRE) {
+            unsigned long long *d_bad = nullptr;
+            SMH_TRY(ws.alloc(&d_bad, 1));
+            SMH_TRY(ws.alloc(&phat, n)); SMH_TRY(ws.alloc(&shat, n));
+            if constexpr (P == kBiJacobi) {
+                SMH_TRY(ws.alloc(&diag, n));
+                SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
+            } else {
+                SMH_TRY(ws.alloc(&tw, n));
+                SMH_TRY(probe_diagonal(pc.f, n, tw, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+            }
+        }
         T *part_a = part, *part_b = part + kPcgBlocks;
         // r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r
         hipLaunchKernelGGL((k_bi_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max);
@@ -301,24 +373,35 @@ int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t 
         }
         hipLaunchKernelGGL((k_bi_dot2<T, true>), dim3(grid), dim3(kBlock), 0, s, sc, r, r, (uint64_t)n, part_a, part_b);
         hipLaunchKernelGGL((k_bi_setup<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
+        if constexpr (P == kBiJacobi) hipLaunchKernelGGL((k_bi_phat0<T>), dim3(grid), dim3(kBlock), 0, s, p, diag, phat, (uint64_t)n);
         SMH_HIP(hipGetLastError());
+        const T *pin = PRE ? phat : p, *sin = PRE ? shat : sv;  // what the two products read
         auto body = [&]() -> int {
-            SMH_TRY(spmv_enqueue(m, p, n, v, variant, s));
+            if constexpr (P == kBiTri) SMH_TRY(precond_apply_enqueue(pc, p, tw, phat, &mo->enter, s));
+            SMH_TRY(spmv_enqueue(m, pin, n, v, variant, s));
             hipLaunchKernelGGL((k_bi_dot<T>), dim3(grid), dim3(kBlock), 0, s, sc, rhat, v, (uint64_t)n, part_a);
             hipLaunchKernelGGL((k_bi_alpha<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
-            hipLaunchKernelGGL((k_bi_s<T>), dim3(grid), dim3(kBlock), 0, s, sc, r, v, sv, (uint64_t)n, part_a);
+            hipLaunchKernelGGL((k_bi_s<T, P>), dim3(grid), dim3(kBlock), 0, s, sc, r, v, sv, (uint64_t)n, part_a, diag, shat);
             hipLaunchKernelGGL((k_bi_half<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
             SMH_HIP(hipGetLastError());
-            SMH_TRY(spmv_enqueue(m, sv, n, t, variant, s));
+            if constexpr (P == kBiTri) SMH_TRY(precond_apply_enqueue(pc, sv, tw, shat, &sc->active, s));
+            SMH_TRY(spmv_enqueue(m, sin, n, t, variant, s));
             hipLaunchKernelGGL((k_bi_dot2<T, false>), dim3(grid), dim3(kBlock), 0, s, sc, t, sv, (uint64_t)n, part_a, part_b);
             hipLaunchKernelGGL((k_bi_omega<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
-            hipLaunchKernelGGL((k_bi_xr<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, x, p, sv, t, rhat, r, (uint64_t)n, part_a, part_b);
+            hipLaunchKernelGGL((k_bi_xr<T, PRE>), dim3(grid), dim3(kBlock), 0, s, sc, mo, x, pin, sv, t, rhat, r, (uint64_t)n, part_a, part_b, shat);
             hipLaunchKernelGGL((k_bi_beta<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
-            hipLaunchKernelGGL((k_bi_p<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, p, r, v, (uint64_t)n);
+            hipLaunchKernelGGL((k_bi_p<T, P>), dim3(grid), dim3(kBlock), 0, s, sc, mo, p, r, v, (uint64_t)n, diag, phat);
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        if constexpr (P == kBiTri) {
+            // the node budget of a captured batch (pcg.hip's): two applications, two products (a few nodes each at most) and the chain of 9
+            bool capture = true;
+            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 2 * (1 + 3) + 9, check_every, &capture);
+            SMH_TRY(run.loop(dt, iter_max, bodies, body, sc, capture));
+        } else {
+            SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+        }
         BiMore<T> *h_mo = (BiMore<T> *)((char *)run.h_sc.get() + sizeof(BiScalars<T>));
         SMH_HIP(hipMemcpyAsync(h_mo, mo, sizeof(BiMore<T>), hipMemcpyDeviceToHost, s));
         if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
@@ -330,11 +413,28 @@ int bicgstab_t(smh_crs *m, const T *b_in, T *x_io, size_t n, double tol, size_t 
     return rc;
 }
 
-int bicgstab(smh_crs *m, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out,
-             double *rr_out, int *breakdown_out) {
-    if (m->dtype == SMH_F64)
-        return bicgstab_t<double>(m, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    return bicgstab_t<float>(m, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+template <typename T>
+int bicgstab_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant,
+               size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    const T *b = (const T *)b_in;
+    T *x = (T *)x_io;
+    const TriPrecond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
+    switch (precond) {
+    case SMH_PRECOND_NONE:
+        return bicgstab_t<T, kBiNone>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    case SMH_PRECOND_JACOBI:
+        return bicgstab_t<T, kBiJacobi>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    default:
+        if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+        return bicgstab_t<T, kBiTri>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    }
+}
+
+// precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
+int bicgstab(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant,
+             size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    if (m->dtype == SMH_F64) return bicgstab_p<double>(m, precond, f, b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    return bicgstab_p<float>(m, precond, f, b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
 }
 
 constexpr size_t kBiCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
@@ -345,11 +445,30 @@ constexpr size_t kBiCheckEvery = 8;  // bodies per poll that check_every = 0, an
 extern "C" int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                       size_t *iters_out, double *rr_out, int *breakdown_out) {
     SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery));
-    return bicgstab(m, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    return bicgstab(m, SMH_PRECOND_NONE, nullptr, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
 }
 
 extern "C" int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                   int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
-    return bicgstab(m, b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+    return bicgstab(m, SMH_PRECOND_NONE, nullptr, b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+}
+
+// Right-preconditioned: `precond` and `f` first (check_precond, precond.hpp: as smh_gmres_precond_solve*), then the checks above (with
+// ILU's factor against the matrix, as smh_pcg_ilu_solve); what needs the device -- a stored column >= n, a zero or absent diagonal
+// entry -- is decided in the driver before its first launch
+extern "C" int smh_bicgstab_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                                              int variant, size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    SMH_TRY(check_precond(precond, f));
+    if (precond == SMH_PRECOND_NONE) return smh_bicgstab_solve_vec(a, b, x, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery, f));
+    return bicgstab(a, precond, f, b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+}
+
+extern "C" int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                                          double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    SMH_TRY(check_precond(precond, f));
+    if (precond == SMH_PRECOND_NONE) return smh_bicgstab_solve(a, b_host, b_len, x_host_inout, x_len, tol, iter_max, variant, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, f));
+    return bicgstab(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
 }

@@ -522,14 +522,6 @@ int gmres(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, siz
     return gmres_p<float>(m, precond, f, b_in, x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
 }
 
-// what the preconditioned entry points decide about `precond` and `f` before anything else
-int check_precond(int precond, const smh_crs *f) {
-    if (precond < SMH_PRECOND_NONE || precond > SMH_PRECOND_ILU) return fail(SMH_ERR_INVALID, "precond is %d: it must be one of SMH_PRECOND_*", precond);
-    if (precond == SMH_PRECOND_ILU && !f) return fail(SMH_ERR_INVALID, "NULL handle");
-    if (precond != SMH_PRECOND_ILU && f) return fail(SMH_ERR_INVALID, "a factor handle goes with SMH_PRECOND_ILU alone");
-    return SMH_OK;
-}
-
 constexpr size_t kGmCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
 
 }  // namespace
@@ -551,7 +543,7 @@ extern "C" int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, voi
                  cycles_out, breakdown_out);
 }
 
-// Right-preconditioned: `precond` and `f` first, then the checks above (with ILU's factor against the matrix, as smh_pcg_ilu_solve);
+// Right-preconditioned: `precond` and `f` first (check_precond, precond.hpp), then the checks above (with ILU's factor against the matrix, as smh_pcg_ilu_solve);
 // what needs the device -- a stored column >= n, a zero or absent diagonal entry -- is decided in the driver before its first launch
 extern "C" int smh_gmres_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                                            size_t restart, int variant, size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out,

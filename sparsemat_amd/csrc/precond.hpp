@@ -1,5 +1,5 @@
-// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS- and ILU-PCG; gmres.hip: the right-preconditioned
-// GMRES): the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle (TriPrecond) and the
+// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS- and ILU-PCG; gmres.hip and bicgstab.hip: the right-preconditioned
+// GMRES and BiCGSTAB): what their entry points decide about `precond` and `f`, the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle (TriPrecond) and the
 // node budget of a captured batch that holds such applications.
 #pragma once
 #include "internal.hpp"
@@ -8,6 +8,15 @@
 #include <cstdlib>
 
 namespace smh {
+
+// what the preconditioned entry points (smh_gmres_precond_solve*, smh_bicgstab_precond_solve*) decide about `precond` and `f` before
+// anything else
+inline int check_precond(int precond, const smh_crs *f) {
+    if (precond < SMH_PRECOND_NONE || precond > SMH_PRECOND_ILU) return fail(SMH_ERR_INVALID, "precond is %d: it must be one of SMH_PRECOND_*", precond);
+    if (precond == SMH_PRECOND_ILU && !f) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (precond != SMH_PRECOND_ILU && f) return fail(SMH_ERR_INVALID, "a factor handle goes with SMH_PRECOND_ILU alone");
+    return SMH_OK;
+}
 
 // d[i] = get(i, i); *bad = the smallest row whose diagonal entry is zero or absent (stays ~0 when there is none)
 template <typename T>

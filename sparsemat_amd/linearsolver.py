@@ -13,7 +13,8 @@
 * ``ILUConjugateGradient``  -- an extension: CG preconditioned by ILU(0) (``SparseMatCRS.ilu0``, ``smh_pcg_ilu_solve*``): the same two
                                solves on a factor computed on the device.
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
-                               device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).
+                               device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).  ``precond="jacobi"``,
+                               ``"sgs"`` or ``"ilu"``: right-preconditioned (``smh_bicgstab_precond_solve*``).
 * ``GMRES``                 -- an extension for non-symmetric systems: restarted GMRES(m), the robust companion of ``BiCGStab``
                                (``smh_gmres_solve*``); its Krylov basis stays on the device.  ``precond="jacobi"``, ``"sgs"`` or
                                ``"ilu"``: right-preconditioned (``smh_gmres_precond_solve*``).
@@ -155,18 +156,39 @@ class BiCGStab(_DeviceSolver):
 
     After ``solve``: ``iterations`` (bodies entered), ``r_norm_squared`` (the last r.r, or s.s after a half-step stop, as
     f64), ``breakdown`` (0 none; 1 rho' == 0 or omega == 0: x keeps that body's update; 2 r^.v == 0: x untouched by that body;
-    3 t.t == 0: x has taken p*alpha) and ``converged`` (a stop test ended the loop: neither a breakdown nor iter_max)."""
+    3 t.t == 0: x has taken p*alpha) and ``converged`` (a stop test ended the loop: neither a breakdown nor iter_max).
 
-    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0):
+    ``precond``: None, "jacobi", "sgs" or "ilu" -- RIGHT preconditioning (``smh_bicgstab_precond_solve*``): A M^-1 u = b,
+    x = M^-1 u, so the residual the recurrence carries is the true one and the stop rule, ``r_norm_squared`` and ``breakdown`` keep
+    their meaning (in the lines above x takes M^-1 p and M^-1 s where it took p and s).  M^-1 is applied twice per body: a division
+    by the diagonal fused into the solver's sweeps ("jacobi"), or ``SparseMatCRS.sgs_apply`` / ``ilu_apply``'s two level-scheduled
+    triangular solves ("sgs" on the matrix, "ilu" on a factor).  ``solve(mat, b, x, factor=None)`` with "ilu" factors ``mat`` itself
+    when no factor is given (afterwards ``factor`` holds the one used and ``zero_pivot`` what its factorization reported, None for a
+    passed factor)."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0, precond=None):
         super().__init__(tol, iter_max, variant, check_every)
+        if precond not in _lib.PRECONDS:
+            raise ValueError('precond must be None, "jacobi", "sgs" or "ilu"')
+        self.precond = precond
         self.breakdown = None
         self.converged = None
+        self.factor = None
+        self.zero_pivot = None
 
-    def solve(self, mat, b, x):
+    def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
         SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
         brk = C.c_int()
-        self._solve(lib().smh_bicgstab_solve_vec, lib().smh_bicgstab_solve, mat, b, x, extra_out=(brk,))
+        if self.precond is None and factor is None:
+            self._solve(lib().smh_bicgstab_solve_vec, lib().smh_bicgstab_solve, mat, b, x, extra_out=(brk,))
+        else:
+            self.zero_pivot = None
+            if self.precond == "ilu" and factor is None:
+                factor, self.zero_pivot = mat.ilu0()
+            self.factor = factor
+            self._solve(lib().smh_bicgstab_precond_solve_vec, lib().smh_bicgstab_precond_solve, mat, b, x,
+                        handles=(_lib.PRECONDS[self.precond], factor._h if factor is not None else None), extra_out=(brk,))
         self.breakdown = brk.value
         # every entered body that ends without a breakdown has tested the r.r it reports: under tol means that test stopped the loop
         self.converged = self.breakdown == 0 and self.iterations > 0 and math.sqrt(self.r_norm_squared) < self.tol
