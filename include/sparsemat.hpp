@@ -371,6 +371,20 @@ class SparseMatCRS {
     }
     // z = U^-1 L^-1 r with this matrix an ilu0 factor; z may be r
     void ilu_apply(const DenseVec<T> &r, DenseVec<T> &z) const { detail::check(smh_crs_ilu_apply_vec(h_, r.handle(), z.handle())); }
+    // FSAI, the factorized sparse approximate inverse (an extension; smh_crs_fsai): {g, gt}, g lower triangular on the stored (i, c)
+    // of this matrix with c <= i, G^T G ~ A^-1 and diag(G A G^T) = 1 for an SPD matrix, gt its transpose -- two ordinary matrices,
+    // built in one data-parallel sweep on the device.  Rows strictly ascending (sort_rows), every diagonal stored, at most 128
+    // entries of a row on or below it; only those are read.  not_spd (optional): the first row whose last pivot is not > 0,
+    // no_zero_pivot without one -- not an error, the values are IEEE's.
+    std::pair<SparseMatCRS, SparseMatCRS> fsai(size_t *not_spd = nullptr) const {
+        SparseMatCRS g, gt;
+        detail::check(smh_crs_fsai(h_, &g.h_, &gt.h_, not_spd));
+        return {std::move(g), std::move(gt)};
+    }
+    // z = G^T (G r) with this matrix the g and gt the transpose of fsai(): two products; z may be r
+    void fsai_apply(const SparseMatCRS &gt, const DenseVec<T> &r, DenseVec<T> &z) const {
+        detail::check(smh_crs_fsai_apply_vec(h_, gt.h_, r.handle(), z.handle()));
+    }
     // {max i - j, max j - i} over the stored entries
     std::pair<uint32_t, uint32_t> bandwidth() const {
         uint32_t lo = 0, hi = 0;
@@ -713,6 +727,43 @@ class ILUConjugateGradient {
     void solve(const SparseMatCRS<T> &mat, const V &b, V &x) {
         const SparseMatCRS<T> factor = mat.ilu0();
         solve(mat, factor, b, x);
+    }
+    size_t iterations() const { return iterations_; }
+    double r_norm_squared() const { return r_norm_squared_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t iter_max_ = 10000;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
+};
+
+// CG preconditioned by the factorized sparse approximate inverse -- an extension, not in the reference (smh_pcg_fsai_solve*):
+// SGSConjugateGradient's recurrence with z = G^T (G r) by two products on the pair mat.fsai() gives; the body's product is mat's.
+// Same panics and stop rule.  The forms without a pair factor mat first and panic (SMH_ERR_INVALID) when it is not positive definite.
+class FSAIConjugateGradient {
+  public:
+    FSAIConjugateGradient() = default;
+    FSAIConjugateGradient(double tol, size_t iter_max) : tol_(tol), iter_max_(iter_max) {}
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_pcg_fsai_solve_vec(mat.handle(), g.handle(), gt.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0,
+                                             &iterations_, &r_norm_squared_));
+    }
+    // host vectors, x updated in place
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_pcg_fsai_solve(mat.handle(), g.handle(), gt.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_,
+                                         SMH_SPMV_AUTO, &iterations_, &r_norm_squared_));
+    }
+    // ... factoring mat first
+    template <typename T, typename V>
+    void solve(const SparseMatCRS<T> &mat, const V &b, V &x) {
+        size_t not_spd = SparseMatCRS<T>::no_zero_pivot;
+        const auto f = mat.fsai(&not_spd);
+        if (not_spd != SparseMatCRS<T>::no_zero_pivot)
+            throw Panic(SMH_ERR_INVALID, "FSAI: the matrix is not positive definite (row " + std::to_string(not_spd) + ")");
+        solve(mat, f.first, f.second, b, x);
     }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }

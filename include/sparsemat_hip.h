@@ -46,7 +46,8 @@ extern "C" {
  * smh_crs_rcm_dev; smh_crs_trisolve_levels, smh_crs_trisolve, smh_crs_trisolve_vec, smh_crs_sgs_apply_vec, smh_pcg_sgs_solve,
  * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
  * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
- * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec; smh_crs_fsai, smh_crs_fsai_apply_vec,
+ * smh_pcg_fsai_solve, smh_pcg_fsai_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -755,6 +756,42 @@ int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, size_t b_len, 
                       double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
 int smh_pcg_ilu_solve_vec(smh_crs *a, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                           int variant, size_t check_every, size_t *iters_out, double *rr_out);
+
+/* The factorized sparse approximate inverse (FSAI, Kolotilina and Yeremin) -- an EXTENSION: a preconditioner applied by two
+ * products, where SGS and ILU(0) take two triangular solves.  smh_crs_fsai: *g_out is a new library-owned handle of a's dtype, lower
+ * triangular, whose pattern is exactly the stored (i, c) of a with c <= i, columns ascending; *gt_out is its transpose as
+ * smh_crs_transpose(g) stores it (n = 1: a copy of g, where the one-operation transposition would leave an orphan).  For an SPD a, G^T G approximates a^-1 and diag(G a G^T) = 1.  Both are ordinary handles (mvp,
+ * get_many, clone, download; the caller destroys them).  Every operation is rounded once and nothing is fused; sqrt is IEEE's.
+ * For row i let J = (j_0 < ... < j_(m-1) = i) be its stored columns <= i and B the dense lower triangle B[p][q], q <= p: the stored
+ * entry (j_p, j_q) of row j_p, or 0 where none is stored.  Only entries on or below a's diagonal are ever read: the result is the
+ * FSAI of the symmetric matrix that a's lower triangle defines.
+ *     for k = 0 .. m-2:                                          (elimination, no pivoting)
+ *         for p = k+1 .. m-1:  l_p = B[p][k] / B[k][k]
+ *         for p = k+1 .. m-1, q = k+1 .. p:  B[p][q] = B[p][q] - l_p * B[q][k]      (B[q][k]: the value before its division)
+ *         for p = k+1 .. m-1:  B[p][k] = l_p
+ *     y_(m-1) = 1;  for p = m-2 .. 0:  s = 0;  for q = p+1 .. m-1 ascending:  s = s + B[q][p] * y_q;   y_p = -s
+ *     g = 1 / sqrt(B[m-1][m-1]);  G[i, j_p] = y_p * g
+ * The rows are independent: one sweep of lane groups, the triangle in the LDS (a long row: a workgroup, the triangle in global
+ * scratch; the same bits).  A LIMIT: a row with m > 128 is refused.
+ * Statuses, checked on the device before anything is written, in smh_crs_ilu0's order: SMH_ERR_NOT_SQUARE; SMH_ERR_INVALID for a
+ * handle that holds an orphan; SMH_ERR_INDEX_RANGE for a stored column >= n; SMH_ERR_INVALID for a row whose columns are not
+ * strictly ascending and for a row without a stored (i, i), the message naming the first such row; then SMH_ERR_INVALID for a row
+ * with m > 128, the message naming the first; SMH_ERR_INVALID for a NULL a, g_out or gt_out.  A matrix that is not SPD is not an
+ * error: *not_spd_out (may be NULL) is the smallest row whose last pivot B[m-1][m-1] is not > 0 (a NaN is not), SIZE_MAX without
+ * one, and such a row holds the IEEE values of the operations above.
+ * smh_crs_fsai_apply_vec: w = G r, z = G^T w by the handles' own products (SMH_SPMV_AUTO) on g's stream; z may be r.  Statuses
+ * as smh_crs_ilu_apply_vec's, with g in f's place (no diagonal is asked for: nothing divides); in addition g and gt differing in n
+ * SMH_ERR_DIM_MISMATCH, in dtype or device SMH_ERR_INVALID, gt not square SMH_ERR_NOT_SQUARE.
+ * smh_pcg_fsai_solve: the recurrence of smh_pcg_sgs_solve with that z: the product (by `variant`) and its p.Ap are a's, the
+ * two products of an application go through AUTO; same guards, stop rule, check_every and outputs.  Statuses as
+ * smh_pcg_ilu_solve's, decided before any launch, with g and then gt in f's place; the factors' values are the caller's business
+ * (no probe of a diagonal). */
+int smh_crs_fsai(const smh_crs *a, smh_crs **g_out, smh_crs **gt_out, size_t *not_spd_out);
+int smh_crs_fsai_apply_vec(smh_crs *g, smh_crs *gt, const smh_vec *r, smh_vec *z);
+int smh_pcg_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                       double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out);
+int smh_pcg_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                           int variant, size_t check_every, size_t *iters_out, double *rr_out);
 
 /* BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is
  * the conjugate gradient).  Device-resident like smh_cg_solve: scalars in HBM, the stop decided on the device in every

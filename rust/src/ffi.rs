@@ -102,6 +102,14 @@ extern "C" {
                              iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_pcg_ilu_solve_vec(a: *mut smh_crs, f: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize,
                                  variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    // extension: the factorized sparse approximate inverse (g lower triangular on a's lower pattern, gt its transpose; *not_spd_out:
+    // the first row whose last pivot is not > 0, usize::MAX without one), z = G^T (G r) by two products, and the CG it preconditions
+    pub fn smh_crs_fsai(a: *const smh_crs, g_out: *mut *mut smh_crs, gt_out: *mut *mut smh_crs, not_spd_out: *mut usize) -> c_int;
+    pub fn smh_crs_fsai_apply_vec(g: *mut smh_crs, gt: *mut smh_crs, r: *const smh_vec, z: *mut smh_vec) -> c_int;
+    pub fn smh_pcg_fsai_solve(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                              x_len: usize, tol: c_double, iter_max: usize, variant: c_int, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    pub fn smh_pcg_fsai_solve_vec(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double,
+                                  iter_max: usize, variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

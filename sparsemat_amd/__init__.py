@@ -14,7 +14,7 @@ from ._lib import SparseMatPanic, lib, LIB_PATH  # noqa: F401
 from .densevec import DenseVec  # noqa: F401
 from .multivec import MultiVec  # noqa: F401
 from .sparsemat_crs import SparseMatCRS, UpdatePlan  # noqa: F401
-from .linearsolver import GMRES, BiCGStab, ConjugateGradient, ILUConjugateGradient, JacobiConjugateGradient, SGSConjugateGradient  # noqa: F401
+from .linearsolver import GMRES, BiCGStab, ConjugateGradient, FSAIConjugateGradient, ILUConjugateGradient, JacobiConjugateGradient, SGSConjugateGradient  # noqa: F401
 from . import synth  # noqa: F401
 from .sparsemat_par_local import Comm, ParVec, SparseMatParLocal  # noqa: F401
 

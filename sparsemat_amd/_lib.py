@@ -189,6 +189,12 @@ SIGNATURES = {
                                  C.POINTER(C.c_double)]),
     "smh_pcg_ilu_solve_vec": (_int, [_vp, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
                                      C.POINTER(C.c_double)]),
+    "smh_crs_fsai": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
+    "smh_crs_fsai_apply_vec": (_int, [_vp, _vp, _vp, _vp]),
+    "smh_pcg_fsai_solve": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
+                                  C.POINTER(C.c_double)]),
+    "smh_pcg_fsai_solve_vec": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
+                                      C.POINTER(C.c_double)]),
     "smh_bicgstab_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                                   C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_bicgstab_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),

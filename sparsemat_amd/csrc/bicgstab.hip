@@ -37,7 +37,7 @@
 // sweep writes p and p^ = p / d (4 n -> 6 n), the s sweep s and s^ = s / d (3 n -> 5 n), the x / r sweep reads p^ and s^ for x and s for
 // r (7 n -> 8 n; dividing p and s again in registers would read d for one of them: the same 8 n, and two divisions more) -- 23 n
 // values beside the two products, against 18 n.  The set-up forms p^ = r / d in one sweep of its own.  Ten vectors of storage.
-// kBiTri: M^-1 is two level-scheduled triangular solves on one handle (TriPrecond, precond.hpp: SGS on the matrix itself, ILU(0) on a
+// kBiTri: M^-1 is two level-scheduled triangular solves on one handle (Precond, precond.hpp: SGS on the matrix itself, ILU(0) on a
 // factor).  The body opens with the application p -> p^ and the s application s -> s^ follows the half-step stage; the products read
 // p^ and s^; the sweeps are kBiNone's but for the x / r sweep (8 n).  Every triangular launch takes a device gate word: the s
 // application `active`, the p application BiMore::enter -- "the next body will be entered" -- which the set-up leaves (iter_max == 0
@@ -329,7 +329,7 @@ k_bi_beta(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rr, const 
 // b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kBiTri's handle (else unused).
 // kBiNone's chain of launches is the unpreconditioned solver's, launch for launch.
 template <typename T, BiPrecond P>
-int bicgstab_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+int bicgstab_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
                size_t *iters_out, double *rr_out, int *breakdown_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     constexpr bool PRE = P != kBiNone;
@@ -418,7 +418,7 @@ int bicgstab_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io
                size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
     const T *b = (const T *)b_in;
     T *x = (T *)x_io;
-    const TriPrecond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
+    const Precond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
     switch (precond) {
     case SMH_PRECOND_NONE:
         return bicgstab_t<T, kBiNone>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);

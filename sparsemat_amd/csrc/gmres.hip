@@ -61,7 +61,7 @@
 // launch: both forms of the normalising sweep write v to its column and v / d to the product's fixed input, the cycle end's sweep
 // keeps t in registers and stores x + t / d.  One read of d each: a body at column j moves (4 j + 14) n values beside the product, a
 // cycle end and a restart's v_0 one more each; (m + 6) n values of storage.
-// kGmTri: M^-1 is two level-scheduled triangular solves on one handle (TriPrecond, precond.hpp: SGS on the matrix itself, ILU(0) on
+// kGmTri: M^-1 is two level-scheduled triangular solves on one handle (Precond, precond.hpp: SGS on the matrix itself, ILU(0) on
 // a factor).  The body's chain opens with the application vin -> u (the product then reads u); the cycle end's sweep writes t where
 // w was (w is free once v_{j+1} is formed) and r with the partials of r.r, one application t -> q follows in place, then the sweep
 // x += q.  Every triangular launch takes a device gate word: the cycle end's is do_end, the body's is GmMore::enter -- "the next body
@@ -406,7 +406,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> 
 // b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kGmTri's handle (else unused).
 // kGmNone's chain of launches is the unpreconditioned solver's, launch for launch.
 template <typename T, GmPrecond P>
-int gmres_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
+int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
             size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     constexpr size_t V = 16 / sizeof(T);
@@ -502,7 +502,7 @@ int gmres_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, s
             size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     const T *b = (const T *)b_in;
     T *x = (T *)x_io;
-    const TriPrecond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
+    const Precond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
     switch (precond) {
     case SMH_PRECOND_NONE:
         return gmres_t<T, kGmNone>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);

@@ -194,8 +194,10 @@ template <typename T> int ilu_enqueue_t(const smh_crs *f, const TriSchedule &t, 
     return SMH_OK;
 }
 
-// the requirements on a pattern, in the order of the header's table; nothing is written
-int ilu_check(const smh_crs *a, const char *what) {
+}  // namespace
+
+// the requirements on a pattern (ilu0's, and fsai.hip's), in the order of the header's table; nothing is written
+int smh::ilu_check(const smh_crs *a, const char *what) {
     if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "%s: the matrix is not square", what);
     if (a->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", what);
     SMH_TRY(columns_within_n_cols(a, what));
@@ -212,6 +214,8 @@ int ilu_check(const smh_crs *a, const char *what) {
     if (bad[1] != ~0ull) return fail(SMH_ERR_INVALID, "%s: no diagonal entry stored in row %llu", what, bad[1]);
     return SMH_OK;
 }
+
+namespace {
 
 // f's values (a copy of A's) become the factor, by f's LOWER schedule on f's stream; the value-derived forms of f go
 int ilu_factor(smh_crs *f, size_t *zero_pivot_out) {

@@ -562,6 +562,9 @@ int launch_scale_values(int dtype, void *v, size_t n, double a, hipStream_t s);
 int ensure_tri_schedule(::smh_crs *m, int uplo);
 int tri_lanes(const ::smh_crs *m);  // lanes of the group a row gets, in the solves and in ilu.hip
 int trisolve_enqueue(::smh_crs *m, int uplo, int diag, bool scale_rhs, const void *b, void *x, const uint32_t *active, hipStream_t s);
+// what smh_crs_ilu0 and smh_crs_fsai require of a pattern (ilu.hip): square, no orphan, columns below n, rows strictly ascending, every
+// (i, i) stored -- checked on the device in that order, nothing written; what: whose refusal it is
+int ilu_check(const ::smh_crs *a, const char *what);
 
 // ---- the device-resident solvers (cg.hip, pcg.hip, par.hip) ----------------------------------------------------------------------
 // The scalar block of a solve: it lives in device memory, the kernels of cg.hip advance it, the host copies it back once per batch.

@@ -16,11 +16,12 @@
 // The sweeps state their arithmetic once, on solver_tree.hpp's sweep; the sums and the one-workgroup folds of their partials are
 // its tree (block_sums / block_sum1, fold1 / fold2) -- deterministic.
 // The second half of the file is the same recurrence preconditioned by two level-scheduled triangular solves (trisolve.hip) on one
-// handle (TriPrecond, precond.hpp), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
+// handle (Precond, precond.hpp), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
 // (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec) solves on the matrix itself, ILU(0) (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) on a
-// factor handle (ilu.hip).
+// factor handle (ilu.hip).  The same Precond holds FSAI's pair of factor handles (smh_pcg_fsai_solve*, smh_crs_fsai_apply_vec;
+// fsai.hip), whose z = G^T (G r) is two products of the handles' own kernels where the others take two solves.
 // Host side: both drivers (pcg_t, pcg_tri_t) are their allocations, their set-up launches, a body lambda and SolveRun::run
-// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe, TriPrecond and the node budget of a
+// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe, Precond and the node budget of a
 // captured batch are precond.hpp's (shared with gmres.hip), the source of p.Ap one function here (pap_source); the entry points'
 // argument checks are solver_host.hpp's.
 #include "internal.hpp"
@@ -321,7 +322,7 @@ __global__ void __launch_bounds__(kBlock) k_sgs_p(const PcgScalars<T> *__restric
 
 // b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
 template <typename T>
-int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+int pcg_tri_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
               size_t *iters_out, double *rr_out) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     SolveRun run;
@@ -343,8 +344,12 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
         T *part = d_part, *dot_scratch = d_part + kPcgBlocks;
         const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
-        // the diagonal's values are read once, here (d_w takes them and is overwritten later)
-        SMH_TRY(probe_diagonal(pc.f, n, d_w, d_bad, pc.name, s));
+        if (pc.gt) {  // (the handles are read on another stream than the ones that wrote them; nothing divides by their values)
+            SMH_HIP(hipStreamSynchronize(pc.f->stream));
+            SMH_HIP(hipStreamSynchronize(pc.gt->stream));
+        } else {  // the diagonal's values are read once, here (d_w takes them and is overwritten later)
+            SMH_TRY(probe_diagonal(pc.f, n, d_w, d_bad, pc.name, s));
+        }
         const uint32_t *active = &d_sc->active;
         // r = b - A x; z = M^-1 r; rr, rz; p = z
         hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
@@ -371,7 +376,7 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        // the node budget of a captured batch: the two solves' launches, the product (a few nodes at most) and the tail of 8
+        // the node budget of a captured batch: the application's launches, the product (a few nodes at most) and the tail of 8
         bool capture = true;
         const size_t bodies = bodies_within_budget(precond_apply_nodes(pc) + spmv_nodes + 3 + 8, check_every, &capture);
         SMH_TRY(run.loop(dt, iter_max, bodies, body, d_sc, capture));
@@ -381,25 +386,29 @@ int pcg_tri_t(smh_crs *m, const TriPrecond &pc, const T *b_in, T *x_io, size_t n
     }, iters_out, rr_out);
 }
 
-int pcg_tri(smh_crs *m, const TriPrecond &pc, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+int pcg_tri(smh_crs *m, const Precond &pc, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
             size_t *iters_out, double *rr_out) {
-    if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (pc.f->orphans || (pc.gt && pc.gt->orphans)) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
     if (m->dtype == SMH_F64) return pcg_tri_t<double>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
     return pcg_tri_t<float>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
 }
 
 // z = M^-1 r by the handle's stream; r and z: n values each on the device, equal or disjoint
-int precond_apply(const TriPrecond &pc, const smh_vec *r, smh_vec *z, const char *what) {
+int precond_apply(const Precond &pc, const smh_vec *r, smh_vec *z, const char *what) {
     smh_crs *f = pc.f;
     if (r->dtype != f->dtype || z->dtype != f->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
     if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
     if (f->n_rows != r->n || f->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (f->orphans || (pc.gt && pc.gt->orphans)) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (pc.gt) {
+        SMH_TRY(ilu_check_pair(f, pc.gt, pc.name));
+        SMH_HIP(hipStreamSynchronize(pc.gt->stream));  // (gt is read on g's stream)
+    }
     const size_t n = f->n_rows, bytes = n * dtype_size(f->dtype);
     const char *pr = (const char *)r->d, *pz = (const char *)z->d;
     if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "%s: r and z overlap in part", what);
     SMH_TRY(precond_prepare(pc));
-    if (f->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
+    if (!pc.gt && f->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
         return fail(SMH_ERR_INVALID, "%s: no diagonal entry stored in row %llu", pc.name, (unsigned long long)f->tri[SMH_TRI_LOWER].first_no_diag);
     Scratch scr;
     char *w = nullptr;
@@ -463,4 +472,29 @@ extern "C" int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, siz
     if (!f) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false, f));
     return pcg_tri(a, ilu_precond(f), b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
+}
+
+// ---- FSAI: the same recurrence with z = G^T (G r) by two products on the factor handles (smh_crs_fsai, fsai.hip), each through its
+// own AUTO kernel; variant is a's product's ----------------------------------------------------------------------------------------
+constexpr const char *kFsaiName = "FSAI preconditioner";
+
+extern "C" int smh_crs_fsai_apply_vec(smh_crs *g, smh_crs *gt, const smh_vec *r, smh_vec *z) {
+    if (!g || !gt || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
+    return precond_apply(fsai_precond(g, gt), r, z, "fsai_apply");
+}
+
+extern "C" int smh_pcg_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
+                                      size_t check_every, size_t *iters_out, double *rr_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery, g, kFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kFsaiName));
+    return pcg_tri(a, fsai_precond(g, gt), b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
+extern "C" int smh_pcg_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
+                                  size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false, g, kFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kFsaiName));
+    return pcg_tri(a, fsai_precond(g, gt), b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
 }

@@ -1,5 +1,5 @@
-// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS- and ILU-PCG; gmres.hip and bicgstab.hip: the right-preconditioned
-// GMRES and BiCGSTAB): what their entry points decide about `precond` and `f`, the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle (TriPrecond) and the
+// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS-, ILU- and FSAI-PCG; gmres.hip and bicgstab.hip: the right-preconditioned
+// GMRES and BiCGSTAB): what their entry points decide about `precond` and `f`, the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle or by two products on two (Precond) and the
 // node budget of a captured batch that holds such applications.
 #pragma once
 #include "internal.hpp"
@@ -54,30 +54,44 @@ inline size_t sgs_graph_nodes() {
     return 4096;
 }
 
-// A preconditioner applied by two triangular solves on one handle: z = T_upper^-1 (scale(T_lower^-1 r)).  SGS: the matrix itself,
-// both diagonals stored, the right-hand side of the upper solve scaled by the diagonal.  ILU(0): the factor handle (ilu.hip), the
-// lower solve with the unit diagonal, no scaling.
-struct TriPrecond {
+// A preconditioner applied by two sweeps over handles of the factor's kind, z = M^-1 r through n values of scratch w.
+// Two triangular solves on one handle (gt == nullptr), z = T_upper^-1 (scale(T_lower^-1 r)): SGS on the matrix itself, both
+// diagonals stored, the right-hand side of the upper solve scaled by the diagonal; ILU(0) on the factor handle (ilu.hip), the lower
+// solve with the unit diagonal, no scaling.  Two products on two handles (gt != nullptr), z = G^T (G r): FSAI (fsai.hip), each by the
+// handle's own AUTO kernel.
+struct Precond {
     smh_crs *f;
     int lower_diag;
     bool scale_rhs;
     const char *name;
+    smh_crs *gt = nullptr;
 };
-inline TriPrecond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
-inline TriPrecond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
+inline Precond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
+inline Precond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
+inline Precond fsai_precond(smh_crs *g, smh_crs *gt) { return {g, SMH_DIAG_NON_UNIT, false, "FSAI preconditioner", gt}; }
 
-// z = M^-1 r on stream s (w: n values of scratch; z may be r; the schedules exist)
-inline int precond_apply_enqueue(const TriPrecond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
+// z = M^-1 r on stream s (w: n values of scratch; z may be r; precond_prepare has run).  active gates the solves' launches; the
+// products run ungated, as the body's own does: past the stop they form the same z from the same r again
+inline int precond_apply_enqueue(const Precond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
+    if (pc.gt) {
+        SMH_TRY(spmv_enqueue(pc.f, r, pc.f->n_rows, w, SMH_SPMV_AUTO, s));
+        return spmv_enqueue(pc.gt, w, pc.f->n_rows, z, SMH_SPMV_AUTO, s);
+    }
     SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.lower_diag, false, r, w, active, s));
     return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
 }
 
-// the launches of one application (the schedules exist)
-inline size_t precond_apply_nodes(const TriPrecond &pc) { return pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size(); }
+// the launches of one application (precond_prepare has run); a product: a few nodes at most
+inline size_t precond_apply_nodes(const Precond &pc) {
+    if (pc.gt) return 2 * 4;
+    return pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size();
+}
 
-// the checks of a preconditioner handle that need the device: columns, schedules, a stored diagonal in every row
-inline int precond_prepare(const TriPrecond &pc) {
+// the checks of a preconditioner's handles that need the device: columns; the solves' schedules (a stored diagonal in every row is
+// the caller's to ask of them)
+inline int precond_prepare(const Precond &pc) {
     SMH_TRY(columns_within_n_cols(pc.f, pc.name));
+    if (pc.gt) return columns_within_n_cols(pc.gt, pc.name);
     SMH_TRY(ensure_tri_schedule(pc.f, SMH_TRI_LOWER));
     return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
 }

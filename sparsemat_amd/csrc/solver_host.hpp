@@ -7,13 +7,13 @@
 namespace smh {
 
 // ---- the argument checks of the entry points, decided before any launch -------------------------------------------------------------
-// what a matrix a and an ILU(0) factor f of it must agree in
-inline int ilu_check_pair(const smh_crs *a, const smh_crs *f) {
+// what a matrix a and a factor f of it (ILU(0)'s, or one of FSAI's two: name) must agree in
+inline int ilu_check_pair(const smh_crs *a, const smh_crs *f, const char *name = "ILU preconditioner") {
     if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "ILU preconditioner: the factor is not square");
-    if (f->n_rows != a->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "ILU preconditioner: the factor's dimension differs from the matrix's");
-    if (f->dtype != a->dtype) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor's dtype differs from the matrix's");
-    if (f->device != a->device) return fail(SMH_ERR_INVALID, "ILU preconditioner: the factor and the matrix live on different devices");
+    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "%s: the factor is not square", name);
+    if (f->n_rows != a->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "%s: the factor's dimension differs from the matrix's", name);
+    if (f->dtype != a->dtype) return fail(SMH_ERR_INVALID, "%s: the factor's dtype differs from the matrix's", name);
+    if (f->device != a->device) return fail(SMH_ERR_INVALID, "%s: the factor and the matrix live on different devices", name);
     return SMH_OK;
 }
 
@@ -24,15 +24,15 @@ inline bool same_columns(const smh_mvec *b, const smh_mvec *x) { return b->k == 
 
 // The _vec form (V: smh_vec, or smh_mvec for the k-column CG), in the order of the reports.  Where the entry points differ
 // ("known inconsistencies of the solvers' checks") the caller says so: the text of the dtype refusal, whether b and x
-// in one storage are refused, and how many bodies per poll check_every = 0 stands for.  factor: ILU's, checked against m where the
-// others check that m is square.
+// in one storage are refused, and how many bodies per poll check_every = 0 stands for.  factor: ILU's, or FSAI's G (factor_name says
+// whose), checked against m where the others check that m is square.
 template <typename V>
 int check_solve_vec(const smh_crs *m, const V *b, const V *x, const char *dtype_message, bool refuse_aliased, size_t *check_every,
-                    size_t default_check_every, const smh_crs *factor = nullptr) {
+                    size_t default_check_every, const smh_crs *factor = nullptr, const char *factor_name = "ILU preconditioner") {
     if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
     if (b->dtype != m->dtype || x->dtype != m->dtype) return fail(SMH_ERR_INVALID, "%s", dtype_message);
     if (refuse_aliased && same_storage(b, x)) return fail(SMH_ERR_INVALID, "b and x are the same storage");
-    if (factor) SMH_TRY(ilu_check_pair(m, factor));
+    if (factor) SMH_TRY(ilu_check_pair(m, factor, factor_name));
     else if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");  // linearsolver.rs:30-32
     if (m->n_rows != b->n || m->n_rows != x->n || !same_columns(b, x))
         return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");  // :33-36
@@ -43,10 +43,10 @@ int check_solve_vec(const smh_crs *m, const V *b, const V *x, const char *dtype_
 // The host form.  null_vectors: the entry point refuses a NULL vector of n > 0 itself (smh_cg_solve leaves that to the upload);
 // refuse_aliased: ... and b_host == x_host (smh_bicgstab_solve and smh_gmres_solve alone).
 inline int check_solve_host(const smh_crs *m, const void *b_host, size_t b_len, const void *x_host, size_t x_len, bool null_vectors,
-                            bool refuse_aliased, const smh_crs *factor = nullptr) {
+                            bool refuse_aliased, const smh_crs *factor = nullptr, const char *factor_name = "ILU preconditioner") {
     if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
     const size_t n = m->n_rows;
-    if (factor) SMH_TRY(ilu_check_pair(m, factor));
+    if (factor) SMH_TRY(ilu_check_pair(m, factor, factor_name));
     else if (n != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
     if (n != b_len || n != x_len) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
     if (null_vectors && n && (!b_host || !x_host)) return fail(SMH_ERR_INVALID, "NULL host vector");

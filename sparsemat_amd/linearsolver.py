@@ -12,6 +12,8 @@
                                triangular solves (``smh_pcg_sgs_solve*``), device-resident like ``ConjugateGradient``.
 * ``ILUConjugateGradient``  -- an extension: CG preconditioned by ILU(0) (``SparseMatCRS.ilu0``, ``smh_pcg_ilu_solve*``): the same two
                                solves on a factor computed on the device.
+* ``FSAIConjugateGradient`` -- an extension: CG preconditioned by the factorized sparse approximate inverse (``SparseMatCRS.fsai``,
+                               ``smh_pcg_fsai_solve*``): z = G^T (G r) by two products.
 * ``BiCGStab``              -- an extension for non-symmetric systems: the stabilised bi-conjugate gradient recurrence,
                                device-resident like ``ConjugateGradient`` (``smh_bicgstab_solve*``).  ``precond="jacobi"``,
                                ``"sgs"`` or ``"ilu"``: right-preconditioned (``smh_bicgstab_precond_solve*``).
@@ -147,6 +149,32 @@ class ILUConjugateGradient(_DeviceSolver):
             factor, self.zero_pivot = mat.ilu0()
         self.factor = factor
         return self._solve(lib().smh_pcg_ilu_solve_vec, lib().smh_pcg_ilu_solve, mat, b, x, handles=(factor._h,))
+
+
+class FSAIConjugateGradient(_DeviceSolver):
+    """CG preconditioned by the factorized sparse approximate inverse, M^-1 = G^T G (``SparseMatCRS.fsai``) -- an EXTENSION: the
+    recurrence of ``SGSConjugateGradient`` with z = G^T (G r) by two products on the factor handles (``smh_pcg_fsai_solve*``) -- no
+    schedule, no levels, the same cost in every ordering; the body's own product is the matrix's.  ``factor``: a pair ``(g, gt)``,
+    given here or to ``solve``; without one ``solve`` factors ``mat`` itself and raises ValueError when the factorization reports a
+    row that is not positive definite (afterwards ``factor`` holds the pair used and ``not_spd`` what its factorization reported,
+    None for a passed pair).  x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x."""
+
+    def __init__(self, tol=1e-12, iter_max=10_000, factor=None, variant="auto", check_every=0):
+        super().__init__(tol, iter_max, variant, check_every)
+        self.factor = factor
+        self.not_spd = None
+        self._given = factor
+
+    def solve(self, mat, b, x, factor=None):
+        self.not_spd = None
+        factor = factor if factor is not None else self._given
+        if factor is None:
+            g, gt, self.not_spd = mat.fsai()
+            if self.not_spd is not None:
+                raise ValueError("FSAI: the matrix is not positive definite (row %d)" % self.not_spd)
+            factor = (g, gt)
+        self.factor = factor
+        return self._solve(lib().smh_pcg_fsai_solve_vec, lib().smh_pcg_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h))
 
 
 class BiCGStab(_DeviceSolver):

@@ -273,6 +273,30 @@ class SparseMatCRS:
         check(lib().smh_crs_ilu_apply_vec(self._h, rv._h, z._h))
         return z.to_numpy()
 
+    # ---- FSAI (an extension; csrc/fsai.hip, applied through csrc/pcg.hip) --------------------------------------------------
+    def fsai(self):
+        """``(g, gt, not_spd)``: the factorized sparse approximate inverse of this square matrix on the pattern of its lower
+        triangle (``smh_crs_fsai``), one data-parallel sweep on the device.  ``g`` is lower triangular with G^T G ~ A^-1 and
+        diag(G A G^T) = 1 for an SPD matrix, ``gt`` its transpose -- two ordinary matrices; z = G^T (G r) is two products
+        (``g.fsai_apply(gt, r)``).  ``not_spd`` is None, or the first row whose last pivot is not > 0 (not an error: the values
+        are IEEE's).  Every row must be strictly ascending (``sort_rows``), store its diagonal, and hold at most 128 entries on
+        or below it; only those entries are read."""
+        g, gt, bad = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        check(lib().smh_crs_fsai(self._h, C.byref(g), C.byref(gt), C.byref(bad)))
+        return type(self)(g, self.dtype), type(self)(gt, self.dtype), (None if bad.value == self._NO_PIVOT else bad.value)
+
+    def fsai_apply(self, gt, r, out=None):
+        """z = G^T (G r) with this matrix the ``g`` and ``gt`` the transpose of ``fsai`` (``smh_crs_fsai_apply_vec``): two products.
+        A ``DenseVec`` r gives a new ``DenseVec``, or ``out`` (which may be r itself); anything else a numpy array."""
+        if isinstance(r, DenseVec):
+            z = DenseVec.zeros(r.dim(), self.dtype) if out is None else out
+            check(lib().smh_crs_fsai_apply_vec(self._h, gt._h, r._h, z._h))
+            return z
+        rv = DenseVec.from_vec(np.ascontiguousarray(r, dtype=self.dtype))
+        z = DenseVec.zeros(rv.dim(), self.dtype)
+        check(lib().smh_crs_fsai_apply_vec(self._h, gt._h, rv._h, z._h))
+        return z.to_numpy()
+
     def bandwidth(self):
         """(max i - j, max j - i) over the stored entries; (0, 0) without entries."""
         lo, hi = C.c_uint32(), C.c_uint32()
