@@ -671,6 +671,12 @@ int smh_cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, si
 int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, void *x_host_inout, double tol,
                            size_t iter_max, size_t *iters_out, double *rr_out);
 
+/* Diagnostics, per thread: how many batches this thread's last single-matrix device-resident solve (smh_cg_solve and every
+ * solver below but the k-column CG) replayed from its captured hipGraph.  0: nothing was captured -- iter_max <= check_every, a
+ * capture that did not come about, or another host thread was using the library (Threading): the bodies were
+ * launched one by one, the same bits. */
+int smh_last_solve_replays(void);
+
 /* Jacobi-preconditioned CG -- an EXTENSION (the reference has no
  * preconditioner): the recurrence of ConjugateGradient::solve with z = r / diag(A), diag_i =
  * get(i, i) (first match in storage order); same guards, statuses, stop rule (on r.r, tested

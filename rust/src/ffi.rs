@@ -160,6 +160,7 @@ extern "C" {
     pub fn smh_crs_apply_dev(m: *mut smh_crs, n_ops: usize, rows_dev: *const u32, cols_dev: *const u32,
                              values_dev: *const c_void, ops_dev: *const u8) -> c_int;
     pub fn smh_last_apply_route() -> c_int;  // 0 general, 1 values only, 2 replay: diagnostics only
+    pub fn smh_last_solve_replays() -> c_int;  // graph launches of this thread's last single-matrix solve (0: none captured): diagnostics only
     // a reusable update plan: re-assembly on a fixed pattern as one gather-and-fold pass (every operation must land on an
     // existing entry; bound to one handle in one structure; from_zero != 0 folds every targeted entry from +0)
     pub fn smh_update_plan_create(m: *const smh_crs, n_ops: usize, rows: *const u32, cols: *const u32, ops: *const u8,

@@ -76,6 +76,7 @@ SIGNATURES = {
     "smh_crs_apply": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_crs_apply_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_last_apply_route": (_int, []),
+    "smh_last_solve_replays": (_int, []),
     "smh_update_plan_create": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_update_plan_create_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "smh_update_plan_execute": (_int, [_vp, _vp, _vp, _int]),

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <thread>
 #include <vector>
 
 #include "crs_forms.hpp"
@@ -44,6 +45,7 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line) {
 }
 
 int require_device() {
+    note_thread();
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0) {
@@ -52,6 +54,42 @@ int require_device() {
     }
     return SMH_OK;
 }
+
+// host threads using the library, and captures in progress (internal.hpp: "host threads and graph capture").  Both counters
+// are sequentially consistent: of a thread that enters a capture and a thread that is counted at the same moment at least one
+// sees the other -- the first backs off, or the second waits.
+__thread bool t_thread_counted = false;
+__thread int t_solve_replays = 0;
+static std::atomic<int> g_threads{0}, g_capturing{0};
+
+void count_thread() {
+    struct Counted {
+        Counted() { g_threads.fetch_add(1); }
+        ~Counted() { g_threads.fetch_sub(1); }
+    };
+    static thread_local Counted counted;  // (leaves the count when the thread ends)
+    (void)counted;
+    t_thread_counted = true;
+    while (g_capturing.load() > 0) std::this_thread::yield();
+}
+
+bool capture_enter() {
+    note_thread();
+    g_capturing.fetch_add(1);
+    if (g_threads.load() > 1) {
+        g_capturing.fetch_sub(1);
+        return false;
+    }
+    return true;
+}
+
+void capture_leave() { g_capturing.fetch_sub(1); }
+
+}  // namespace smh
+
+extern "C" int smh_last_solve_replays(void) { return smh::t_solve_replays; }
+
+namespace smh {
 
 uint64_t next_crs_id() {
     static std::atomic<uint64_t> next{1};

@@ -19,8 +19,27 @@ void set_error(const char *fmt, ...);
 int fail(int status, const char *fmt, ...);
 int hip_fail(hipError_t e, const char *what, const char *file, int line);
 
+// ---- host threads and graph capture -------------------------------------------------------------------------------------
+// The solvers capture a batch of bodies in hipStreamCaptureModeThreadLocal on the handle's non-blocking stream.  On ROCm 7.2 that
+// does not keep other host threads out of the way: while ANY thread captures, a synchronous call on the legacy stream (hipMemcpy,
+// hipMemset) or hipDeviceSynchronize from another thread is refused (hipErrorStreamCaptureImplicit / Unsupported) and invalidates
+// the capture.  So a batch is captured only while one host thread is using the library: every thread is counted before its first
+// call into the runtime that could disturb a capture -- in SMH_HIP, in require_device(), in the hipMalloc / hipFree of this library
+// (the macros at the end of this file: a pooled free synchronises the device) and in smh_pool_trim -- and waits there, once, for a
+// capture in progress to end (a capture only records launches on the host).  A thread that has ended is counted no longer, and with
+// more than one thread counted capture_enter() says no: the bodies are then launched one by one, which gives the same bits
+// (solve_in_batches).  The count is coarse: a thread that made one call stays counted until it ends, and from then on no solve of
+// the process replays a graph; smh_last_solve_replays() tells a caller which of the two its last solve did.
+extern __thread bool t_thread_counted;
+extern __thread int t_solve_replays;  // graph launches of this thread's last solve_in_batches (smh_last_solve_replays)
+void count_thread();      // capi.hip
+inline void note_thread() { if (!t_thread_counted) count_thread(); }
+bool capture_enter();     // true: the calling thread may capture now; then capture_leave() once the capture has ended
+void capture_leave();
+
 #define SMH_HIP(call)                                                     \
     do {                                                                  \
+        ::smh::note_thread();                                             \
         hipError_t e__ = (call);                                          \
         if (e__ != hipSuccess) return ::smh::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
@@ -602,7 +621,9 @@ int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_eve
                      size_t *iters, double *rr, bool capture = true) {
     Graph graph;
     GraphExec exec;
-    if (capture && iter_max > check_every && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    t_solve_replays = 0;
+    const bool may_capture = capture && iter_max > check_every && capture_enter();  // (no: another host thread is using the library)
+    if (may_capture && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         int crc = SMH_OK;
         for (size_t i = 0; i < check_every && crc == SMH_OK; ++i) crc = body();
         const hipError_t ce = graph.end_capture(s);  // (also after a body that failed: the stream must leave capture mode)
@@ -611,6 +632,7 @@ int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_eve
     } else {
         (void)hipGetLastError();
     }
+    if (may_capture) capture_leave();
     auto poll = [&]() -> int {
         SMH_HIP(hipMemcpyAsync(h_sc, d_sc, cg_scalars_bytes(dtype), hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
@@ -625,6 +647,7 @@ int solve_in_batches(int dtype, hipStream_t s, size_t iter_max, size_t check_eve
             size_t batch = iter_max - launched < check_every ? iter_max - launched : check_every;
             if (exec.get()) {
                 SMH_HIP(hipGraphLaunch(exec.get(), s));
+                ++t_solve_replays;
                 batch = check_every;
             } else {
                 for (size_t i = 0; i < batch; ++i) SMH_TRY(body());
@@ -869,6 +892,6 @@ int cg_solve_many(::smh_crs *m, const ::smh_mvec *b, ::smh_mvec *x, double tol, 
 
 // ---- every .hip file of the library but pool.hip allocates device memory through the pool (declared at the top) ----------
 #ifndef SMH_POOL_IMPL
-#define hipMalloc(p, n) ::smh::pool_malloc((void **)(p), (n))
-#define hipFree(p) ::smh::pool_free((void *)(p))
+#define hipMalloc(p, n) (::smh::note_thread(), ::smh::pool_malloc((void **)(p), (n)))
+#define hipFree(p) (::smh::note_thread(), ::smh::pool_free((void *)(p)))
 #endif

@@ -128,6 +128,7 @@ long long pool_thread_net_bytes() { return t_net_bytes; }
 extern "C" {
 
 int smh_pool_trim(void) {
+    smh::note_thread();  // (hipFree below: internal.hpp, "host threads and graph capture")
     smh::Pool &P = smh::pool();
     int cur = 0;
     if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); return SMH_OK; }  // no device: nothing was ever kept

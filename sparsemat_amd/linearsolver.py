@@ -43,6 +43,7 @@ class _DeviceSolver:
         self.check_every = int(check_every)
         self.iterations = None  # loop bodies entered by the last solve
         self.r_norm_squared = None  # last r.r (as f64)
+        self.graph_replays = None  # batches the last solve replayed from its captured graph (0: launched one by one, _solve)
 
     def _solve(self, vec_fn, host_fn, mat, b, x, handles=(), extra_out=(), extra_in=()):
         """Two ``DenseVec``s go to ``vec_fn`` (None: the solver has no such form), anything else to ``host_fn`` as an array-like b and
@@ -59,7 +60,7 @@ class _DeviceSolver:
             bb = np.ascontiguousarray(b, dtype=mat.dtype)
             check(host_fn(mat._h, *handles, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None, x.size,
                           self.tol, self.iter_max, *extra_in, var, *out))
-        self.iterations, self.r_norm_squared = iters.value, rr.value
+        self.iterations, self.r_norm_squared, self.graph_replays = iters.value, rr.value, lib().smh_last_solve_replays()
         return x
 
 
