@@ -385,6 +385,20 @@ class SparseMatCRS {
     void fsai_apply(const SparseMatCRS &gt, const DenseVec<T> &r, DenseVec<T> &z) const {
         detail::check(smh_crs_fsai_apply_vec(h_, gt.h_, r.handle(), z.handle()));
     }
+    // The non-symmetric FSAI (an extension; smh_crs_fsai_ns): {gl, gu} with G_U G_L ~ A^-1, gl lower triangular with a unit diagonal
+    // on the stored (i, c) with c <= i, gu upper triangular on the stored (i, c) with c >= i -- two ordinary matrices; on a dense
+    // pattern G_U G_L = A^-1.  Rows strictly ascending (sort_rows), every diagonal stored, at most 128 entries of a row on or below
+    // and of a column on or above it.  singular (optional): the first row whose last pivot, in either factor's row solve, is zero or
+    // not finite, no_zero_pivot without one -- not an error, the values are IEEE's.
+    std::pair<SparseMatCRS, SparseMatCRS> fsai_ns(size_t *singular = nullptr) const {
+        SparseMatCRS gl, gu;
+        detail::check(smh_crs_fsai_ns(h_, &gl.h_, &gu.h_, singular));
+        return {std::move(gl), std::move(gu)};
+    }
+    // z = G_U (G_L r) with this matrix the gl and gu the other factor of fsai_ns(): two products; z may be r
+    void fsai_ns_apply(const SparseMatCRS &gu, const DenseVec<T> &r, DenseVec<T> &z) const {
+        detail::check(smh_crs_fsai_ns_apply_vec(h_, gu.h_, r.handle(), z.handle()));
+    }
     // {max i - j, max j - i} over the stored entries
     std::pair<uint32_t, uint32_t> bandwidth() const {
         uint32_t lo = 0, hi = 0;
@@ -805,6 +819,24 @@ class BiCGStab {
     void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const V &b, V &x) {
         solve_precond(mat, factor.handle(), b, x);
     }
+    // ... right-preconditioned by a pair of product handles, M^-1 v = gt (g v) (smh_bicgstab_fsai_solve*): mat.fsai_ns()'s {gl, gu},
+    // or mat.fsai()'s {g, gt} for a symmetric matrix; the kind given to the constructor is not looked at
+    template <typename T>
+    void solve_fsai(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_bicgstab_fsai_solve_vec(mat.handle(), g.handle(), gt.handle(), b.handle(), x.handle(), tol_, iter_max_, SMH_SPMV_AUTO, 0,
+                                                  &iterations_, &r_norm_squared_, &breakdown_));
+    }
+    template <typename T>
+    void solve_fsai(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_bicgstab_fsai_solve(mat.handle(), g.handle(), gt.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_,
+                                              SMH_SPMV_AUTO, &iterations_, &r_norm_squared_, &breakdown_));
+    }
+    // ... factoring mat through fsai_ns() first
+    template <typename T, typename V>
+    void solve_fsai(const SparseMatCRS<T> &mat, const V &b, V &x) {
+        const auto f = mat.fsai_ns();
+        solve_fsai(mat, f.first, f.second, b, x);
+    }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }
     int breakdown() const { return breakdown_; }
@@ -859,6 +891,24 @@ class GMRES {
     template <typename T, typename V>
     void solve(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &factor, const V &b, V &x) {
         solve_precond(mat, factor.handle(), b, x);
+    }
+    // ... right-preconditioned by a pair of product handles, M^-1 v = gt (g v) (smh_gmres_fsai_solve*): mat.fsai_ns()'s {gl, gu}, or
+    // mat.fsai()'s {g, gt} for a symmetric matrix; the kind given to the constructor is not looked at
+    template <typename T>
+    void solve_fsai(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const DenseVec<T> &b, DenseVec<T> &x) {
+        detail::check(smh_gmres_fsai_solve_vec(mat.handle(), g.handle(), gt.handle(), b.handle(), x.handle(), tol_, iter_max_, restart_, SMH_SPMV_AUTO,
+                                               0, &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    template <typename T>
+    void solve_fsai(const SparseMatCRS<T> &mat, const SparseMatCRS<T> &g, const SparseMatCRS<T> &gt, const std::vector<T> &b, std::vector<T> &x) {
+        detail::check(smh_gmres_fsai_solve(mat.handle(), g.handle(), gt.handle(), b.data(), b.size(), x.data(), x.size(), tol_, iter_max_, restart_,
+                                           SMH_SPMV_AUTO, &iterations_, &r_norm_squared_, &cycles_, &breakdown_));
+    }
+    // ... factoring mat through fsai_ns() first
+    template <typename T, typename V>
+    void solve_fsai(const SparseMatCRS<T> &mat, const V &b, V &x) {
+        const auto f = mat.fsai_ns();
+        solve_fsai(mat, f.first, f.second, b, x);
     }
     size_t iterations() const { return iterations_; }
     double r_norm_squared() const { return r_norm_squared_; }

@@ -47,7 +47,8 @@ extern "C" {
  * smh_pcg_sgs_solve_vec; smh_crs_color, smh_crs_color_dev; smh_crs_ilu0, smh_crs_ilu0_refactor, smh_crs_ilu_apply_vec,
  * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
  * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec; smh_crs_fsai, smh_crs_fsai_apply_vec,
- * smh_pcg_fsai_solve, smh_pcg_fsai_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_pcg_fsai_solve, smh_pcg_fsai_solve_vec; smh_crs_fsai_ns, smh_crs_fsai_ns_apply_vec, smh_gmres_fsai_solve, smh_gmres_fsai_solve_vec,
+ * smh_bicgstab_fsai_solve, smh_bicgstab_fsai_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -799,6 +800,29 @@ int smh_pcg_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, 
 int smh_pcg_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                            int variant, size_t check_every, size_t *iters_out, double *rr_out);
 
+/* The non-symmetric FSAI -- an EXTENSION: two factors, M^-1 = G_U G_L ~ a^-1, for matrices that are not symmetric.  *gl_out and *gu_out
+ * are new library-owned handles of a's dtype, ordinary ones as smh_crs_fsai's are.  Every operation is rounded once and nothing is fused.
+ * The row solve R(C, i) on a CRS matrix C with ascending rows: J = (j_0 < ... < j_(m-1) = i) the stored columns <= i of row i, B the
+ * dense m x m matrix B[p][q] = the stored entry (j_p, j_q) of C, or 0 where none is stored -- the full square, both triangles:
+ *     for k = 0 .. m-2:                                          (elimination, no pivoting)
+ *         for p = k+1 .. m-1:  l_p = B[p][k] / B[k][k]
+ *         for p = k+1 .. m-1, q = k+1 .. m-1:  B[p][q] = B[p][q] - l_p * B[k][q]
+ *         for p = k+1 .. m-1:  B[p][k] = l_p
+ *     y_(m-1) = 1;  for p = m-2 .. 0:  s = 0;  for q = p+1 .. m-1 ascending:  s = s + B[q][p] * y_q;   y_p = -s
+ *     d = B[m-1][m-1]                                            (d * the last row of B^-1 = y)
+ * G_L: row i, on J, is y of R(a, i): lower triangular with a stored unit diagonal, G_L ~ L^-1 of a = L D U.  G_U: let H hold in row i,
+ * on the stored columns <= i of row i of a^T, y / d of R(a^T, i) -- one division per entry; a^T with its rows ascending --; G_U is the
+ * transposition of H as smh_crs_transpose stores it (n = 1: a copy): upper triangular on the stored (i, c) of a with c >= i.  For a
+ * dense pattern G_U G_L = a^-1.  The rows are independent: one sweep of lane groups per factor, the square in the LDS (a group of
+ * 1, 2, 4, .. 64 lanes holds m <= 4, 5, 8, 11, 16, 22, 32; a longer row: a workgroup, the square in global scratch; the same bits).
+ * Statuses: smh_crs_fsai's in its order; then SMH_ERR_INVALID for a row with more than 128 stored entries on or below the diagonal,
+ * then for a column with more than 128 on or above it, the message naming the first ("row", "column"); nothing is made on refusal.
+ * *singular_out (may be NULL) is the smallest i for which d of either row solve is zero or not finite, SIZE_MAX without one: a
+ * result, not an error, and such rows hold the IEEE values of the operations above.
+ * smh_crs_fsai_ns_apply_vec: smh_crs_fsai_apply_vec under this pair's name: w = G_L r, z = G_U w through SMH_SPMV_AUTO; z may be r. */
+int smh_crs_fsai_ns(const smh_crs *a, smh_crs **gl_out, smh_crs **gu_out, size_t *singular_out);
+int smh_crs_fsai_ns_apply_vec(smh_crs *gl, smh_crs *gu, const smh_vec *r, smh_vec *z);
+
 /* BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is
  * the conjugate gradient).  Device-resident like smh_cg_solve: scalars in HBM, the stop decided on the device in every
  * body and polled every `check_every` bodies (0: default, 8), bodies enqueued past the stop are no-ops, so x and all
@@ -908,6 +932,33 @@ int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *
 int smh_bicgstab_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, const smh_vec *b, smh_vec *x, double tol,
                                    size_t iter_max, int variant, size_t check_every,
                                    size_t *iters_out, double *rr_out, int *breakdown_out);
+
+/* GMRES(m) and BiCGSTAB right-preconditioned by a pair of product handles -- an EXTENSION: M^-1 v = gt (g v), two products, where
+ * SGS and ILU(0) take two level-scheduled triangular solves: no schedule, no levels, the same cost in every ordering.  The pair is
+ * (G_L, G_U) of smh_crs_fsai_ns, or (G, G^T) of smh_crs_fsai for a symmetric a; what its values are is the caller's business (no
+ * diagonal is probed: nothing divides by a factor's value).  The arguments are those of smh_gmres_precond_solve* and
+ * smh_bicgstab_precond_solve* with the pair in place of `precond, f`; the recurrences are theirs, operation for operation: one
+ * application per GMRES body (u = M^-1 v_j) and one per cycle end (q = M^-1 t), two per BiCGSTAB body (p^ = M^-1 p, s^ = M^-1 s).
+ * WHICH PRODUCT FORMS WHAT.  The applications inside a body go through the handles' own kernels (SMH_SPMV_AUTO), ungated like the
+ * body's own product: in bodies enqueued past the stop they form the same vector from unchanged input again.  GMRES's cycle end forms
+ * q by two storage-order products, w' = g t and q = gt w', each one lane per row with the product rounded, then added
+ * (SMH_SPMV_SEQ's operations and bits), behind the device word that says a cycle end is due: they return at once in every body that
+ * ends no cycle, where two more AUTO products would have run, and cost, each time.  Every sweep that writes x, r or the basis is
+ * gated as before.  `variant` is a's product's.  Memory: (m + 7) n values for GMRES and ten vectors of n for BiCGSTAB, as with SGS and
+ * ILU(0); the cycle end needs no vector more.  A captured batch stays under the node budget of the triangular kinds.
+ * Statuses, decided before any launch, x left untouched: SMH_ERR_INVALID for a NULL g or gt; then smh_pcg_fsai_solve's about a, g
+ * and gt (not square; the pair's n: SMH_ERR_DIM_MISMATCH; dtype, device: SMH_ERR_INVALID), the vectors' as smh_gmres_solve* and
+ * smh_bicgstab_solve*, GMRES's restart; an orphaned entry in g or gt SMH_ERR_INVALID; a stored column >= n SMH_ERR_INDEX_RANGE. */
+int smh_gmres_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                         double tol, size_t iter_max, size_t restart, int variant,
+                         size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+int smh_gmres_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                             size_t restart, int variant, size_t check_every,
+                             size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+int smh_bicgstab_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
+                            double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out, int *breakdown_out);
+int smh_bicgstab_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
+                                int variant, size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out);
 
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;

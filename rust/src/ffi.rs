@@ -110,6 +110,22 @@ extern "C" {
                               x_len: usize, tol: c_double, iter_max: usize, variant: c_int, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
     pub fn smh_pcg_fsai_solve_vec(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double,
                                   iter_max: usize, variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double) -> c_int;
+    // extension: the non-symmetric FSAI, two factors G_U G_L ~ A^-1, and GMRES / BiCGSTAB right-preconditioned by a pair of product
+    // handles (its (gl, gu), or smh_crs_fsai's (g, gt) for a symmetric matrix)
+    pub fn smh_crs_fsai_ns(a: *const smh_crs, gl_out: *mut *mut smh_crs, gu_out: *mut *mut smh_crs, singular_out: *mut usize) -> c_int;
+    pub fn smh_crs_fsai_ns_apply_vec(gl: *mut smh_crs, gu: *mut smh_crs, r: *const smh_vec, z: *mut smh_vec) -> c_int;
+    pub fn smh_gmres_fsai_solve(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                                x_len: usize, tol: c_double, iter_max: usize, restart: usize, variant: c_int, iters_out: *mut usize,
+                                rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_gmres_fsai_solve_vec(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double,
+                                    iter_max: usize, restart: usize, variant: c_int, check_every: usize, iters_out: *mut usize,
+                                    rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_bicgstab_fsai_solve(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void,
+                                   x_len: usize, tol: c_double, iter_max: usize, variant: c_int, iters_out: *mut usize, rr_out: *mut c_double,
+                                   breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_bicgstab_fsai_solve_vec(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double,
+                                       iter_max: usize, variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double,
+                                       breakdown_out: *mut c_int) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

@@ -18,6 +18,8 @@ SMH_TRI_LOWER, SMH_TRI_UPPER = 0, 1
 SMH_DIAG_NON_UNIT, SMH_DIAG_UNIT = 0, 1
 SMH_PRECOND_NONE, SMH_PRECOND_JACOBI, SMH_PRECOND_SGS, SMH_PRECOND_ILU = 0, 1, 2, 3
 PRECONDS = {None: SMH_PRECOND_NONE, "jacobi": SMH_PRECOND_JACOBI, "sgs": SMH_PRECOND_SGS, "ilu": SMH_PRECOND_ILU}
+# the preconditioners of GMRES and BiCGStab: PRECONDS' kinds (one entry point, a code) and "fsai" (entry points of its own, a pair)
+PRECOND_NAMES = tuple(PRECONDS) + ("fsai",)
 UPLO = {"lower": SMH_TRI_LOWER, "upper": SMH_TRI_UPPER}
 EXCHANGE_NONE, EXCHANGE_ALLGATHER, EXCHANGE_WINDOW, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGES = {"none": EXCHANGE_NONE, "allgather": EXCHANGE_ALLGATHER, "window": EXCHANGE_WINDOW, "halo": EXCHANGE_WINDOW, "auto": EXCHANGE_AUTO}
@@ -196,6 +198,16 @@ SIGNATURES = {
                                   C.POINTER(C.c_double)]),
     "smh_pcg_fsai_solve_vec": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
                                       C.POINTER(C.c_double)]),
+    "smh_crs_fsai_ns": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz)]),
+    "smh_crs_fsai_ns_apply_vec": (_int, [_vp, _vp, _vp, _vp]),
+    "smh_gmres_fsai_solve": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _sz, _int, C.POINTER(_sz),
+                                    C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_gmres_fsai_solve_vec": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),
+                                        C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_bicgstab_fsai_solve": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
+                                       C.POINTER(C.c_double), C.POINTER(_int)]),
+    "smh_bicgstab_fsai_solve_vec": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
+                                           C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_bicgstab_solve": (_int, [_vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _int, C.POINTER(_sz),
                                   C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_bicgstab_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),

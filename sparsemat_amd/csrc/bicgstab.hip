@@ -45,6 +45,9 @@
 // there); so bodies enqueued past the stop run no solve.  Ten vectors of storage (p^, s^, the solves' scratch).  A captured batch
 // holds two applications per body: bodies_within_budget (precond.hpp) makes the batches smaller or drops the capture, which changes
 // no bit.
+// A pair of product handles (smh_bicgstab_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs kBiTri's chain with Precond's pair and
+// the same ten vectors.  Both applications are two products through the handles' own AUTO kernels, ungated as the body's own products
+// are: past the stop they form the same p^ and s^ from unchanged p and s again, and every sweep that writes x, r or p stays gated.
 // Host side: the driver (bicgstab_t) is its allocations, its set-up launches, the body lambda and SolveRun::run (solver_host.hpp:
 // the stream of its own, the workspaces, the drain, r = b - A x); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
@@ -360,7 +363,13 @@ int bicgstab_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, 
                 SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
             } else {
                 SMH_TRY(ws.alloc(&tw, n));
-                SMH_TRY(probe_diagonal(pc.f, n, tw, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+                if (pc.gt) {  // the forms of the handles' AUTO products, built here and not inside a capture (no set-up application would);
+                              // their streams are drained: the handles are read on another one.  Nothing divides by their values
+                    SMH_TRY(smh_crs_prepare(pc.f, SMH_SPMV_AUTO));
+                    SMH_TRY(smh_crs_prepare(pc.gt, SMH_SPMV_AUTO));
+                } else {
+                    SMH_TRY(probe_diagonal(pc.f, n, tw, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+                }
             }
         }
         T *part_a = part, *part_b = part + kPcgBlocks;
@@ -430,6 +439,16 @@ int bicgstab_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io
     }
 }
 
+// M^-1 = gt o g, a pair of product handles (fsai.hip): the driver of the triangular kinds with Precond's pair
+int bicgstab_fsai(smh_crs *m, smh_crs *g, smh_crs *gt, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
+                  size_t *iters_out, double *rr_out, int *breakdown_out) {
+    const Precond pc = fsai_precond(g, gt);
+    if (g->orphans || gt->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (m->dtype == SMH_F64)
+        return bicgstab_t<double, kBiTri>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    return bicgstab_t<float, kBiTri>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+}
+
 // precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
 int bicgstab(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant,
              size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
@@ -471,4 +490,25 @@ extern "C" int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, c
     if (precond == SMH_PRECOND_NONE) return smh_bicgstab_solve(a, b_host, b_len, x_host_inout, x_len, tol, iter_max, variant, iters_out, rr_out, breakdown_out);
     SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, f));
     return bicgstab(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+}
+
+// Right-preconditioned by a pair of product handles, M^-1 v = gt (g v): (G_L, G_U) of smh_crs_fsai_ns, or (G, G^T) of smh_crs_fsai for
+// a symmetric a.  The pair's checks are smh_pcg_fsai_solve's; nothing is probed (no operation divides by a factor's value); a stored
+// column >= n is decided in the driver before its first launch
+constexpr const char *kBiFsaiName = "FSAI preconditioner";
+
+extern "C" int smh_bicgstab_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
+                                           size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery, g, kBiFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kBiFsaiName));
+    return bicgstab_fsai(a, g, gt, b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+}
+
+extern "C" int smh_bicgstab_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
+                                       size_t iter_max, int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, g, kBiFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kBiFsaiName));
+    return bicgstab_fsai(a, g, gt, b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
 }

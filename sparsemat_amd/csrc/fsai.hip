@@ -163,7 +163,7 @@ k_fsai_long(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, 
 // lanes per row: the smallest power of two that holds the mean m (smh_crs_set_vector_lanes on a overrides it, as for ilu0)
 int fsai_lanes(const smh_crs *a, uint64_t nnz_g) {
     if (a->knobs.forced_lanes) return a->knobs.forced_lanes;
-    const double mean = a->n_rows ? (double)nnz_g / (double)a->n_rows : 0.0;
+    const double mean = a->n_rows ? (double)nnz_g / (double)a->n_rows : 0.0;  // (a factor of a's transposition has a's rows too)
     int lanes = 1;
     while (lanes < kWave && (double)lanes < mean) lanes <<= 1;
     return lanes;
@@ -219,6 +219,180 @@ int fsai_values_t(const smh_crs *a, const CrsArrays &g, uint64_t nnz_g, uint32_t
     return SMH_OK;
 }
 
+// ---- the non-symmetric FSAI (smh_crs_fsai_ns): the scheme above with B the full square ------------------------------------------------
+// M^-1 = G_U G_L ~ A^-1.  The row solve R(C, i) on a CRS matrix C with ascending rows: J as above, B the dense m x m matrix
+// B[p][q] = the stored entry (j_p, j_q) of C, 0 where none is stored -- both triangles --, every operation rounded once, nothing fused:
+//   for k = 0 .. m-2:                                          (elimination, no pivoting)
+//       for p = k+1 .. m-1:  l_p = B[p][k] / B[k][k]
+//       for p = k+1 .. m-1, q = k+1 .. m-1:  B[p][q] = B[p][q] - l_p * B[k][q]
+//       for p = k+1 .. m-1:  B[p][k] = l_p
+//   y_(m-1) = 1;  for p = m-2 .. 0:  s = 0;  for q = p+1 .. m-1 ascending:  s = s + B[q][p] * y_q;   y_p = -s
+//   d = B[m-1][m-1]                                            (d * the last row of B^-1 = y)
+// Row i of G_L is y of R(A, i): a stored unit diagonal, G_L ~ L^-1 of A = L D U.  Row i of H is y / d of R(A^T, i), one division per
+// entry, A^T with its rows ascending; G_U is the transposition of H as smh_crs_transpose stores it (n = 1: a copy).  For a dense
+// pattern G_U G_L = A^-1.  *singular = the smallest row whose d, in either solve, is zero or not finite (the values are IEEE's).
+// A step reads row k, which the step before finished, and writes rows p > k, each by the lane that owns it: one barrier per step.
+// The slice of a group of L lanes is kFsaiNsSlice * L values and holds a square of m <= 4, 5, 8, 11, 16, 22, 32 for L = 1 .. 64.
+constexpr uint32_t kFsaiNsSlice = 16;      // LDS values per lane: 32 KiB for the 256 threads of a workgroup in f64
+constexpr uint32_t kFsaiNsLongGrid = 256;  // most workgroups (and scratch squares: kFsaiMaxRow^2 values each) of the long-row kernel
+
+// row i of G_L (DIVIDE false) or of H (true) by a team that arrives together: J = gcol[0 .. m) its columns, B: room for m * m values
+template <typename T, typename Team>
+__device__ __forceinline__ void fsai_ns_row(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val,
+                                            const uint32_t *__restrict__ J, uint32_t m, uint32_t i, T *B, T *__restrict__ gval, bool divide,
+                                            unsigned long long *singular) {
+    const uint32_t t = Team::rank();
+    for (uint32_t p = t; p < m; p += Team::size) {
+        const uint32_t r0 = off[J[p]], r1 = off[J[p] + 1];
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint32_t c = J[q];
+            uint32_t lo = r0, hi = r1;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (col[mid] < c) lo = mid + 1;
+                else hi = mid;
+            }
+            B[p * m + q] = lo < r1 && col[lo] == c ? val[lo] : T(0);
+        }
+    }
+    Team::sync();
+    for (uint32_t k = 0; k + 1 < m; ++k) {
+        const T piv = B[k * m + k];
+        for (uint32_t p = k + 1 + t; p < m; p += Team::size) {
+            const T l = p_div(B[p * m + k], piv);
+            for (uint32_t q = k + 1; q < m; ++q) B[p * m + q] = p_add(B[p * m + q], -p_mul(l, B[k * m + q]));
+            B[p * m + k] = l;
+        }
+        Team::sync();  // (row k + 1 is complete before it is read)
+    }
+    if (t == 0) {
+        const T d = B[(m - 1) * m + m - 1];
+        for (uint32_t p = m - 1; p-- > 0;) {  // y_p takes the place of the pivot B[p][p]
+            T s = T(0);
+            for (uint32_t q = p + 1; q < m; ++q) s = p_add(s, p_mul(B[q * m + p], q + 1 == m ? T(1) : B[q * m + q]));
+            B[p * m + p] = -s;
+        }
+        for (uint32_t p = 0; p < m; ++p) {
+            const T y = p + 1 == m ? T(1) : B[p * m + p];
+            gval[p] = divide ? p_div(y, d) : y;
+        }
+        if (!(d != T(0) && isfinite(d))) atomicMin(singular, (unsigned long long)i);
+    }
+    Team::sync();  // (B is read before the team's next row overwrites it)
+}
+
+template <typename T, int L>
+__global__ void __launch_bounds__(kBlock)
+k_fsai_ns_rows(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val, const uint32_t *__restrict__ goff,
+               const uint32_t *__restrict__ gcol, T *__restrict__ gval, uint64_t n, uint32_t m_fit, bool divide, unsigned long long *singular) {
+    __shared__ T s_b[kFsaiNsSlice * kBlock];
+    const uint64_t i = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) / L;
+    if (i >= n) return;
+    const uint32_t g0 = goff[i], m = goff[i + 1] - g0;
+    if (m > m_fit) return;
+    fsai_ns_row<T, FsaiGroup<L>>(off, col, val, gcol + g0, m, (uint32_t)i, s_b + (size_t)(threadIdx.x / L) * kFsaiNsSlice * L, gval + g0, divide, singular);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kFsaiLongBlock)
+k_fsai_ns_long(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val, const uint32_t *__restrict__ goff,
+               const uint32_t *__restrict__ gcol, T *__restrict__ gval, const uint32_t *__restrict__ list, uint32_t n_long, T *scratch, bool divide,
+               unsigned long long *singular) {
+    T *B = scratch + (size_t)blockIdx.x * kFsaiMaxRow * kFsaiMaxRow;
+    for (uint32_t q = blockIdx.x; q < n_long; q += gridDim.x) {
+        const uint32_t i = list[q], g0 = goff[i], m = goff[i + 1] - g0;
+        fsai_ns_row<T, FsaiBlock>(off, col, val, gcol + g0, m, i, B, gval + g0, divide, singular);
+    }
+}
+
+// the longest row whose square fits the slice of a group of `lanes` lanes
+uint32_t fsai_ns_fit(int lanes) {
+    uint32_t m = 1;
+    while ((m + 1) * (m + 1) <= kFsaiNsSlice * (uint32_t)lanes) ++m;
+    return m;
+}
+
+template <typename T, int L>
+void fsai_ns_launch_rows(const smh_crs *c, const CrsArrays &g, uint64_t n, uint32_t m_fit, bool divide, unsigned long long *singular, hipStream_t s) {
+    const uint64_t blocks = (n * L + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL((k_fsai_ns_rows<T, L>), dim3((unsigned)blocks), dim3(kBlock), 0, s, c->d_off, c->d_col, (const T *)c->d_val, g.off, g.col, (T *)g.val, n,
+                       m_fit, divide, singular);
+}
+
+// the values of a factor of c (offsets and columns are there) on s; d_singular: one word, shared by both factors.  lanes_of: the handle
+// whose smh_crs_set_vector_lanes counts (a itself, also for the rows of its transposition)
+template <typename T>
+int fsai_ns_values_t(const smh_crs *c, const smh_crs *lanes_of, const CrsArrays &g, uint64_t nnz_g, uint32_t max_m, bool divide,
+                     unsigned long long *d_singular, hipStream_t s) {
+    const uint64_t n = c->n_rows;
+    const int lanes = fsai_lanes(lanes_of, nnz_g);
+    const uint32_t m_fit = fsai_ns_fit(lanes);
+    switch (lanes) {
+    case 1: fsai_ns_launch_rows<T, 1>(c, g, n, m_fit, divide, d_singular, s); break;
+    case 2: fsai_ns_launch_rows<T, 2>(c, g, n, m_fit, divide, d_singular, s); break;
+    case 4: fsai_ns_launch_rows<T, 4>(c, g, n, m_fit, divide, d_singular, s); break;
+    case 8: fsai_ns_launch_rows<T, 8>(c, g, n, m_fit, divide, d_singular, s); break;
+    case 16: fsai_ns_launch_rows<T, 16>(c, g, n, m_fit, divide, d_singular, s); break;
+    case 32: fsai_ns_launch_rows<T, 32>(c, g, n, m_fit, divide, d_singular, s); break;
+    default: fsai_ns_launch_rows<T, 64>(c, g, n, m_fit, divide, d_singular, s); break;
+    }
+    SMH_HIP(hipGetLastError());
+    if (max_m <= m_fit) return SMH_OK;
+    Scratch scr;
+    uint32_t *list = nullptr, *d_count = nullptr, n_long = 0;
+    SMH_TRY(scr.alloc(&list, n));
+    SMH_TRY(scr.alloc(&d_count, 1));
+    SMH_TRY(read_back(d_count, &n_long, 1, s, [&](uint32_t *d) -> int {
+        SMH_HIP(hipMemsetAsync(d, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_fsai_long_list, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, g.off, n, m_fit, list, d);
+        SMH_HIP(hipGetLastError());
+        return SMH_OK;
+    }));
+    const uint32_t grid = n_long < kFsaiNsLongGrid ? n_long : kFsaiNsLongGrid;
+    T *sq_scratch = nullptr;
+    SMH_TRY(scr.alloc(&sq_scratch, (size_t)grid * kFsaiMaxRow * kFsaiMaxRow));
+    hipLaunchKernelGGL((k_fsai_ns_long<T>), dim3(grid), dim3(kFsaiLongBlock), 0, s, c->d_off, c->d_col, (const T *)c->d_val, g.off, g.col, (T *)g.val, list,
+                       n_long, sq_scratch, divide, d_singular);
+    SMH_HIP(hipGetLastError());
+    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
+    return SMH_OK;
+}
+
+// count -> scan: the offsets of a factor on c's stored (i, col <= i); stats[0] = the largest m, stats[1] = the smallest row with
+// m > kFsaiMaxRow (the caller's to refuse), *nnz_g = the entries
+int fsai_ns_offsets(const smh_crs *c, CrsArrays &g, unsigned long long stats[2], uint64_t *nnz_g, hipStream_t s) {
+    const size_t n = c->n_rows;
+    SMH_TRY(g.alloc_off(n));
+    stats[0] = 0;
+    stats[1] = ~0ull;
+    SMH_TRY(read_back(stats, 2, s, [&](unsigned long long *d) -> int {
+        SMH_HIP(hipMemcpyAsync(d, stats, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fsai_count, dim3(grid_for(n + 1, kBuildGrid)), dim3(kBlock), 0, s, c->d_off, c->d_col, (uint64_t)n, g.off, d);
+        SMH_HIP(hipGetLastError());
+        return SMH_OK;
+    }));
+    if (stats[1] != ~0ull) return SMH_OK;
+    SMH_TRY(device_exclusive_scan_u32(g.off, (uint64_t)n + 1, s, nnz_g));
+    if (*nnz_g >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    return SMH_OK;
+}
+
+// emit -> the rows: the columns and values of a factor of c whose offsets are there
+int fsai_ns_fill(const smh_crs *c, const smh_crs *lanes_of, CrsArrays &g, uint64_t nnz_g, uint32_t max_m, bool divide, unsigned long long *d_singular,
+                 hipStream_t s) {
+    const size_t n = c->n_rows, vs = dtype_size(c->dtype);
+    SMH_TRY(g.alloc_entries(nnz_g, vs));
+    SMH_TRY(g.zero_padding(nnz_g, vs, s));
+    if (!n) return SMH_OK;
+    hipLaunchKernelGGL(k_fsai_emit, dim3(grid_for(n, kBuildGrid)), dim3(kBlock), 0, s, c->d_off, c->d_col, (uint64_t)n, g.off, g.col);
+    SMH_HIP(hipGetLastError());
+    if (c->dtype == SMH_F64) return fsai_ns_values_t<double>(c, lanes_of, g, nnz_g, max_m, divide, d_singular, s);
+    return fsai_ns_values_t<float>(c, lanes_of, g, nnz_g, max_m, divide, d_singular, s);
+}
+
+// a 1 x 1 matrix is its own transpose (the transposition's replay of one operation would leave an orphan and no row)
+int fsai_transpose(const smh_crs *h, smh_crs **out) { return h->nnz == 1 ? smh_crs_clone(h, out) : smh_crs_transpose(h, out); }
+
 }  // namespace
 
 extern "C" int smh_crs_fsai(const smh_crs *a, smh_crs **g_out, smh_crs **gt_out, size_t *not_spd_out) {
@@ -264,5 +438,51 @@ extern "C" int smh_crs_fsai(const smh_crs *a, smh_crs **g_out, smh_crs **gt_out,
     *g_out = gh;
     *gt_out = gth;
     if (not_spd_out) *not_spd_out = not_spd == ~0ull ? SIZE_MAX : (size_t)not_spd;
+    return SMH_OK;
+}
+
+extern "C" int smh_crs_fsai_ns(const smh_crs *a, smh_crs **gl_out, smh_crs **gu_out, size_t *singular_out) {
+    if (!a || !gl_out || !gu_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    *gl_out = *gu_out = nullptr;
+    SMH_TRY(ilu_check(a, "fsai_ns"));
+    const size_t n = a->n_rows;
+    const hipStream_t s = a->stream;
+    // A^T with its rows ascending (the library's transposition stores them descending), on a stream of its own
+    smh_crs *at = nullptr;
+    SMH_TRY(fsai_transpose(a, &at));
+    struct Drop {  // (destroying a handle leaves the last error's text alone)
+        smh_crs *h;
+        ~Drop() { (void)smh_crs_destroy(h); }
+    } drop_at{at};
+    SMH_TRY(smh_crs_sort_rows(at));
+    SMH_HIP(hipStreamSynchronize(at->stream));  // (it is read on a's stream)
+    // the patterns of both factors, and their refusals, before either's values
+    CrsArrays gl, h;
+    unsigned long long stats_l[2], stats_u[2];
+    uint64_t nnz_l = 0, nnz_u = 0;
+    SMH_TRY(fsai_ns_offsets(a, gl, stats_l, &nnz_l, s));
+    if (stats_l[1] != ~0ull)
+        return fail(SMH_ERR_INVALID, "fsai_ns: row %llu stores more than %u entries on or below the diagonal", stats_l[1], kFsaiMaxRow);
+    SMH_TRY(fsai_ns_offsets(at, h, stats_u, &nnz_u, s));
+    if (stats_u[1] != ~0ull)
+        return fail(SMH_ERR_INVALID, "fsai_ns: column %llu stores more than %u entries on or above the diagonal", stats_u[1], kFsaiMaxRow);
+    unsigned long long singular = ~0ull;
+    SMH_TRY(read_back(&singular, 1, s, [&](unsigned long long *d) -> int {
+        SMH_HIP(hipMemsetAsync(d, 0xFF, sizeof(unsigned long long), s));
+        SMH_TRY(fsai_ns_fill(a, a, gl, nnz_l, (uint32_t)stats_l[0], /*divide*/ false, d, s));
+        return fsai_ns_fill(at, a, h, nnz_u, (uint32_t)stats_u[0], /*divide*/ true, d, s);
+    }));
+    SMH_HIP(hipStreamSynchronize(s));  // (the new handles have streams of their own)
+    smh_crs *glh = nullptr, *hh = nullptr, *guh = nullptr;
+    SMH_TRY(wrap_arrays(a->dtype, nullptr, n, n, nnz_l, gl, 0, &glh));
+    int rc = wrap_arrays(a->dtype, nullptr, n, n, nnz_u, h, 0, &hh);
+    if (rc == SMH_OK) {
+        rc = fsai_transpose(hh, &guh);
+        rc = keep_error(rc, [&] { (void)smh_crs_destroy(hh); });
+    }
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)smh_crs_destroy(glh); });
+    *gl_out = glh;
+    *gu_out = guh;
+    if (singular_out) *singular_out = singular == ~0ull ? SIZE_MAX : (size_t)singular;
     return SMH_OK;
 }

@@ -70,6 +70,11 @@
 // (m + 7) n values of storage.  A captured batch holds two applications per body: pcg.hip's node budget (bodies_within_budget)
 // makes the batches smaller or drops the capture, which changes no bit.
 // rr is the RECURRENCE residual's r.r: where the solves amplify rounding it parts from |b - A x|^2.
+// A pair of product handles (smh_gmres_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs kGmTri's chain with Precond's pair, and
+// the same (m + 7) n values: no vector more.  The body's application vin -> u is two products through the handles' own AUTO kernels,
+// ungated as the body's own product is: past the stop they form the same u from the same vin again.  The cycle end's q = M^-1 t is
+// formed by two GATED storage-order products (precond.hpp's k_gated_seq on do_end: w -> tw -> w, SMH_SPMV_SEQ's bits), which return
+// at once in a body that ends no cycle -- through AUTO every body would pay a second, dead pair.  So q has SEQ's bits and u AUTO's.
 #include "internal.hpp"
 #include "precond.hpp"
 #include "solver_host.hpp"
@@ -440,7 +445,13 @@ int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, dou
                 SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
             } else {
                 SMH_TRY(ws.alloc(&u, n)); SMH_TRY(ws.alloc(&tw, n));
-                SMH_TRY(probe_diagonal(pc.f, n, u, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+                if (pc.gt) {  // the forms of the handles' AUTO products, built here and not inside a capture (no set-up application would);
+                              // their streams are drained: the handles are read on another one.  Nothing divides by their values
+                    SMH_TRY(smh_crs_prepare(pc.f, SMH_SPMV_AUTO));
+                    SMH_TRY(smh_crs_prepare(pc.gt, SMH_SPMV_AUTO));
+                } else {
+                    SMH_TRY(probe_diagonal(pc.f, n, u, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
+                }
             }
         }
         // r = b - A x (w: scratch); rr = r.r; beta; v_0
@@ -469,7 +480,7 @@ int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, dou
             hipLaunchKernelGGL((k_gm_xr<T, P>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww, diag, w);  // (w is free)
             hipLaunchKernelGGL((k_gm_begin<T, false>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
             if constexpr (P == kGmTri) {  // q = M^-1 t in place, x += q: due at a cycle end alone
-                SMH_TRY(precond_apply_enqueue(pc, w, tw, w, &mo->do_end, s));
+                SMH_TRY(precond_apply_gated_enqueue(pc, w, tw, w, &mo->do_end, s));
                 hipLaunchKernelGGL((k_gm_xadd<T>), dim3(grid), dim3(kBlock), 0, s, mo, x, w, (uint64_t)n);
             }
             hipLaunchKernelGGL((k_gm_norm<T, true, P>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n, diag);
@@ -512,6 +523,18 @@ int gmres_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, s
         if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
         return gmres_t<T, kGmTri>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
     }
+}
+
+// M^-1 = gt o g, a pair of product handles (fsai.hip): the driver of the triangular kinds with Precond's pair
+int gmres_fsai(smh_crs *m, smh_crs *g, smh_crs *gt, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
+               size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    const Precond pc = fsai_precond(g, gt);
+    if (g->orphans || gt->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    if (m->dtype == SMH_F64)
+        return gmres_t<double, kGmTri>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out,
+                                       cycles_out, breakdown_out);
+    return gmres_t<float, kGmTri>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
+                                  breakdown_out);
 }
 
 // precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
@@ -564,4 +587,29 @@ extern "C" int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, cons
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
     return gmres(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out,
                  breakdown_out);
+}
+
+// Right-preconditioned by a pair of product handles, M^-1 v = gt (g v): (G_L, G_U) of smh_crs_fsai_ns, or (G, G^T) of smh_crs_fsai for
+// a symmetric a.  The pair's checks are smh_pcg_fsai_solve's, then the restart's; nothing is probed (no operation divides by a factor's
+// value); a stored column >= n is decided in the driver before its first launch
+constexpr const char *kGmFsaiName = "FSAI preconditioner";
+
+extern "C" int smh_gmres_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart,
+                                        int variant, size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery, g, kGmFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kGmFsaiName));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres_fsai(a, g, gt, b->d, x->d, a->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+}
+
+extern "C" int smh_gmres_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
+                                    size_t iter_max, size_t restart, int variant, size_t *iters_out, double *rr_out, size_t *cycles_out,
+                                    int *breakdown_out) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, g, kGmFsaiName));
+    SMH_TRY(ilu_check_pair(a, gt, kGmFsaiName));
+    SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
+    return gmres_fsai(a, g, gt, b_host, x_host_inout, a->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out,
+                      breakdown_out);
 }

@@ -483,6 +483,9 @@ extern "C" int smh_crs_fsai_apply_vec(smh_crs *g, smh_crs *gt, const smh_vec *r,
     return precond_apply(fsai_precond(g, gt), r, z, "fsai_apply");
 }
 
+// the name the documents of the non-symmetric pair (G_L, G_U) use: w = G_L r, z = G_U w
+extern "C" int smh_crs_fsai_ns_apply_vec(smh_crs *gl, smh_crs *gu, const smh_vec *r, smh_vec *z) { return smh_crs_fsai_apply_vec(gl, gu, r, z); }
+
 extern "C" int smh_pcg_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
                                       size_t check_every, size_t *iters_out, double *rr_out) {
     if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");

@@ -81,6 +81,49 @@ inline int precond_apply_enqueue(const Precond &pc, const void *r, void *w, void
     return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
 }
 
+// y = M x in storage order when *gate != 0, nothing at all otherwise: k_spmv_seq's operations (one lane per row, the product rounded,
+// then added: SMH_SPMV_SEQ's bits) behind a device word.  For an application that is due in few bodies of a captured batch (GMRES's
+// cycle end), where the handle's own ungated product would run, and cost, in every body.  Columns < the length of x: precond_prepare
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_gated_seq(const uint32_t *__restrict__ gate, const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const T *__restrict__ val,
+            const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows) {
+    if (!*gate) return;  // block-uniform
+    for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t e = off[row + 1];
+        T sum = T(0);
+        for (uint64_t k = off[row]; k < e; ++k) sum = p_add(sum, p_mul(x[col[k]], val[k]));
+        y[row] = sum;
+    }
+}
+
+inline int gated_seq_enqueue(const smh_crs *h, const void *x, void *y, const uint32_t *gate, hipStream_t s) {
+    const size_t n = h->n_rows;
+    if (!n) return SMH_OK;
+    size_t blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 8192) blocks = 8192;
+    if (h->dtype == SMH_F64)
+        hipLaunchKernelGGL((k_gated_seq<double>), dim3((unsigned)blocks), dim3(kBlock), 0, s, gate, h->d_off, h->d_col, (const double *)h->d_val, (const double *)x,
+                           (double *)y, (uint64_t)n);
+    else
+        hipLaunchKernelGGL((k_gated_seq<float>), dim3((unsigned)blocks), dim3(kBlock), 0, s, gate, h->d_off, h->d_col, (const float *)h->d_val, (const float *)x,
+                           (float *)y, (uint64_t)n);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
+// z = M^-1 r when *gate != 0 and no work otherwise (w: n values of scratch; z may be r; gate: a device word).  The solves as above;
+// the pair by two gated storage-order products, w = G r and z = G^T w with SMH_SPMV_SEQ's bits -- not the handles' AUTO kernels
+inline int precond_apply_gated_enqueue(const Precond &pc, const void *r, void *w, void *z, const uint32_t *gate, hipStream_t s) {
+    if (!pc.gt) return precond_apply_enqueue(pc, r, w, z, gate, s);
+    // SMH_FSAI_END_GATE=0 (tuning knob, for measuring what the gate saves): the handles' own ungated products instead -- AUTO's bits
+    if (const char *e = getenv("SMH_FSAI_END_GATE")) {
+        if (atoi(e) == 0) return precond_apply_enqueue(pc, r, w, z, gate, s);
+    }
+    SMH_TRY(gated_seq_enqueue(pc.f, r, w, gate, s));
+    return gated_seq_enqueue(pc.gt, w, z, gate, s);
+}
+
 // the launches of one application (precond_prepare has run); a product: a few nodes at most
 inline size_t precond_apply_nodes(const Precond &pc) {
     if (pc.gt) return 2 * 4;

@@ -178,6 +178,16 @@ class FSAIConjugateGradient(_DeviceSolver):
         return self._solve(lib().smh_pcg_fsai_solve_vec, lib().smh_pcg_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h))
 
 
+def _fsai_pair(solver, mat, factor):
+    """The pair ``precond="fsai"`` applies: the one passed, or ``mat.fsai_ns()``'s, whose ``singular`` the solver keeps (None for a
+    passed pair)."""
+    solver.singular = None
+    if factor is None:
+        gl, gu, solver.singular = mat.fsai_ns()
+        factor = (gl, gu)
+    return factor
+
+
 class BiCGStab(_DeviceSolver):
     """BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is the
     conjugate gradient): device-resident like ``ConjugateGradient``, the same guards, panics and stop rule
@@ -193,17 +203,23 @@ class BiCGStab(_DeviceSolver):
     by the diagonal fused into the solver's sweeps ("jacobi"), or ``SparseMatCRS.sgs_apply`` / ``ilu_apply``'s two level-scheduled
     triangular solves ("sgs" on the matrix, "ilu" on a factor).  ``solve(mat, b, x, factor=None)`` with "ilu" factors ``mat`` itself
     when no factor is given (afterwards ``factor`` holds the one used and ``zero_pivot`` what its factorization reported, None for a
-    passed factor)."""
+    passed factor).
+
+    ``precond="fsai"`` (``smh_bicgstab_fsai_solve*``): M^-1 v = gt (g v) by two products on a pair of handles, ``factor=(g, gt)`` --
+    ``SparseMatCRS.fsai_ns``'s (G_L, G_U), or ``fsai``'s (G, G^T) for a symmetric matrix; no schedule, no levels, the same cost in every
+    ordering.  Without a factor ``solve`` factors ``mat`` through ``fsai_ns`` (afterwards ``factor`` holds the pair used and
+    ``singular`` what the factorization reported, None for a passed pair)."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0, precond=None):
         super().__init__(tol, iter_max, variant, check_every)
-        if precond not in _lib.PRECONDS:
-            raise ValueError('precond must be None, "jacobi", "sgs" or "ilu"')
+        if precond not in _lib.PRECOND_NAMES:
+            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
         self.precond = precond
         self.breakdown = None
         self.converged = None
         self.factor = None
         self.zero_pivot = None
+        self.singular = None
 
     def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
@@ -211,6 +227,10 @@ class BiCGStab(_DeviceSolver):
         brk = C.c_int()
         if self.precond is None and factor is None:
             self._solve(lib().smh_bicgstab_solve_vec, lib().smh_bicgstab_solve, mat, b, x, extra_out=(brk,))
+        elif self.precond == "fsai":
+            self.factor = factor = _fsai_pair(self, mat, factor)
+            self._solve(lib().smh_bicgstab_fsai_solve_vec, lib().smh_bicgstab_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h),
+                        extra_out=(brk,))
         else:
             self.zero_pivot = None
             if self.precond == "ilu" and factor is None:
@@ -242,18 +262,25 @@ class GMRES(_DeviceSolver):
     a factor).  ``solve(mat, b, x, factor=None)`` with "ilu" factors ``mat`` itself when no factor is given (afterwards ``factor``
     holds the one used and ``zero_pivot`` what its factorization reported, None for a passed factor).  ``r_norm_squared`` is the
     RECURRENCE residual's: where the triangular solves amplify rounding (a matrix far from diagonally dominant) it parts from
-    |b - A x|^2 -- form that yourself when it matters."""
+    |b - A x|^2 -- form that yourself when it matters.
+
+    ``precond="fsai"`` (``smh_gmres_fsai_solve*``): M^-1 v = gt (g v) by two products on a pair of handles, ``factor=(g, gt)`` --
+    ``SparseMatCRS.fsai_ns``'s (G_L, G_U), or ``fsai``'s (G, G^T) for a symmetric matrix.  The body's application goes through the
+    handles' own kernels; the cycle end's is formed by two storage-order products that run at a cycle end alone.  Without a factor
+    ``solve`` factors ``mat`` through ``fsai_ns`` (afterwards ``factor`` holds the pair used and ``singular`` what the factorization
+    reported, None for a passed pair)."""
 
     def __init__(self, tol=1e-12, iter_max=10_000, restart=30, variant="auto", check_every=0, precond=None):
         super().__init__(tol, iter_max, variant, check_every)
-        if precond not in _lib.PRECONDS:
-            raise ValueError('precond must be None, "jacobi", "sgs" or "ilu"')
+        if precond not in _lib.PRECOND_NAMES:
+            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
         self.restart = int(restart)
         self.precond = precond
         self.cycles = None
         self.breakdown = None
         self.factor = None
         self.zero_pivot = None
+        self.singular = None
 
     def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
@@ -261,6 +288,10 @@ class GMRES(_DeviceSolver):
         cycles, brk = C.c_size_t(), C.c_int()
         if self.precond is None and factor is None:
             self._solve(lib().smh_gmres_solve_vec, lib().smh_gmres_solve, mat, b, x, extra_out=(cycles, brk), extra_in=(self.restart,))
+        elif self.precond == "fsai":
+            self.factor = factor = _fsai_pair(self, mat, factor)
+            self._solve(lib().smh_gmres_fsai_solve_vec, lib().smh_gmres_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h),
+                        extra_out=(cycles, brk), extra_in=(self.restart,))
         else:
             self.zero_pivot = None
             if self.precond == "ilu" and factor is None:

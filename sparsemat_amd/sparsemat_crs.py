@@ -297,6 +297,30 @@ class SparseMatCRS:
         check(lib().smh_crs_fsai_apply_vec(self._h, gt._h, rv._h, z._h))
         return z.to_numpy()
 
+    def fsai_ns(self):
+        """``(gl, gu, singular)``: the non-symmetric factorized sparse approximate inverse of this square matrix
+        (``smh_crs_fsai_ns``), G_U G_L ~ A^-1 -- two ordinary matrices.  ``gl`` is lower triangular on the stored (i, c) with c <= i,
+        unit diagonal, G_L ~ L^-1 of A = L D U; ``gu`` is upper triangular on the stored (i, c) with c >= i; z = G_U (G_L r) is two
+        products (``gl.fsai_ns_apply(gu, r)``).  On a dense pattern G_U G_L = A^-1.  ``singular`` is None, or the first row whose
+        last pivot, in either factor's row solve, is zero or not finite (not an error: the values are IEEE's).  Every row must be
+        strictly ascending (``sort_rows``) and store its diagonal; a row may hold at most 128 entries on or below it and a column
+        at most 128 on or above it."""
+        gl, gu, bad = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        check(lib().smh_crs_fsai_ns(self._h, C.byref(gl), C.byref(gu), C.byref(bad)))
+        return type(self)(gl, self.dtype), type(self)(gu, self.dtype), (None if bad.value == self._NO_PIVOT else bad.value)
+
+    def fsai_ns_apply(self, gu, r, out=None):
+        """z = G_U (G_L r) with this matrix the ``gl`` and ``gu`` the other factor of ``fsai_ns`` (``smh_crs_fsai_ns_apply_vec``):
+        ``fsai_apply`` under the name of the non-symmetric pair."""
+        if isinstance(r, DenseVec):
+            z = DenseVec.zeros(r.dim(), self.dtype) if out is None else out
+            check(lib().smh_crs_fsai_ns_apply_vec(self._h, gu._h, r._h, z._h))
+            return z
+        rv = DenseVec.from_vec(np.ascontiguousarray(r, dtype=self.dtype))
+        z = DenseVec.zeros(rv.dim(), self.dtype)
+        check(lib().smh_crs_fsai_ns_apply_vec(self._h, gu._h, rv._h, z._h))
+        return z.to_numpy()
+
     def bandwidth(self):
         """(max i - j, max j - i) over the stored entries; (0, 0) without entries."""
         lo, hi = C.c_uint32(), C.c_uint32()
