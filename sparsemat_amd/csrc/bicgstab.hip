@@ -31,21 +31,21 @@
 //   set-up:  nothing (M is not applied to the residual)
 //   body:    p^ = M^-1 p;  v = A p^;   ...   s^ = M^-1 s;  t = A s^;   x takes p^*alpha and s^*omega (r, the dots and p as above)
 // x does not feed back, so from x0 = 0 every scalar is the unpreconditioned recurrence's on the product A o M^-1.
-// The driver and the kernels that differ are instantiated per BiPrecond; kBiNone's chain of launches is the one described above,
-// launch for launch.
-// kBiJacobi: M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe), and costs no launch in a body: the p
+// The driver and the kernels that differ are instantiated per PrecondShape (precond.hpp); kPcNone's chain of launches is the one
+// described above, launch for launch.
+// kPcFused (Jacobi): M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe), and costs no launch in a body: the p
 // sweep writes p and p^ = p / d (4 n -> 6 n), the s sweep s and s^ = s / d (3 n -> 5 n), the x / r sweep reads p^ and s^ for x and s for
 // r (7 n -> 8 n; dividing p and s again in registers would read d for one of them: the same 8 n, and two divisions more) -- 23 n
 // values beside the two products, against 18 n.  The set-up forms p^ = r / d in one sweep of its own.  Ten vectors of storage.
-// kBiTri: M^-1 is two level-scheduled triangular solves on one handle (Precond, precond.hpp: SGS on the matrix itself, ILU(0) on a
-// factor).  The body opens with the application p -> p^ and the s application s -> s^ follows the half-step stage; the products read
-// p^ and s^; the sweeps are kBiNone's but for the x / r sweep (8 n).  Every triangular launch takes a device gate word: the s
+// kPcLaunched: M^-1 is applied by launches of its own (Precond, precond.hpp); for SGS on the matrix itself and ILU(0) on a factor,
+// two level-scheduled triangular solves on one handle.  The body opens with the application p -> p^ and the s application s -> s^ follows the half-step stage; the products read
+// p^ and s^; the sweeps are kPcNone's but for the x / r sweep (8 n).  Every triangular launch takes a device gate word: the s
 // application `active`, the p application BiMore::enter -- "the next body will be entered" -- which the set-up leaves (iter_max == 0
 // closes it), every stage that stops and a body that is not entered clear, and the beta stage sets (iters == iter_max is a stop
 // there); so bodies enqueued past the stop run no solve.  Ten vectors of storage (p^, s^, the solves' scratch).  A captured batch
 // holds two applications per body: bodies_within_budget (precond.hpp) makes the batches smaller or drops the capture, which changes
 // no bit.
-// A pair of product handles (smh_bicgstab_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs kBiTri's chain with Precond's pair and
+// A pair of product handles (smh_bicgstab_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs the same chain with Precond's products and
 // the same ten vectors.  Both applications are two products through the handles' own AUTO kernels, ungated as the body's own products
 // are: past the stop they form the same p^ and s^ from unchanged p and s again, and every sweep that writes x, r or p stays gated.
 // Host side: the driver (bicgstab_t) is its allocations, its set-up launches, the body lambda and SolveRun::run (solver_host.hpp:
@@ -60,9 +60,6 @@
 using namespace smh;
 
 namespace {
-
-// how M^-1 is applied (the header's last paragraphs): not at all, inside the sweeps, or by two triangular solves on a handle
-enum BiPrecond { kBiNone, kBiJacobi, kBiTri };
 
 // ---- device-resident scalars ---------------------------------------------------------------------------------------------
 // the block the host polls through CG's reader (cg_read_scalars): rr, the stop word and the body count sit where CG's do
@@ -83,7 +80,7 @@ template <typename T>
 struct BiMore {
     T rho, rv, ss, ts, tt, omega;
     uint32_t breakdown;  // 0 none, 1 rho' == 0 or omega == 0, 2 r^.v == 0, 3 t.t == 0 (a stop with code 0 was a stop test's)
-    uint32_t enter;      // gate: the next body will be entered (kBiTri's application p -> p^ that opens it is due)
+    uint32_t enter;      // gate: the next body will be entered (kPcLaunched's application p -> p^ that opens it is due)
 };
 
 template <typename T>
@@ -124,8 +121,8 @@ k_bi_dot2(const BiScalars<T> *__restrict__ sc, const T *__restrict__ t, const T 
     block_sums(a_ts, a_tt, part_ts, part_tt);
 }
 
-// s = r - v*alpha; partials of s.s.  kBiJacobi: and s^ = s / diag, the second product's input
-template <typename T, BiPrecond P = kBiNone>
+// s = r - v*alpha; partials of s.s.  kPcFused: and s^ = s / diag, the second product's input
+template <typename T, PrecondShape P = kPcNone>
 __global__ void __launch_bounds__(kBlock)
 k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__restrict__ v, T *__restrict__ s, uint64_t n, T *__restrict__ part_ss,
        const T *__restrict__ diag = nullptr, T *__restrict__ shat = nullptr) {
@@ -141,7 +138,7 @@ k_bi_s(const BiScalars<T> *__restrict__ sc, const T *__restrict__ r, const T *__
             acc = p_add(acc, p_mul(sv[e], sv[e]));
         }
         at.store(s, sv);
-        if constexpr (P == kBiJacobi) {
+        if constexpr (P == kPcFused) {
             const auto dv = at.load(diag);
 #pragma unroll
             for (int e = 0; e < at.width; ++e) sv[e] = p_div(sv[e], dv[e]);
@@ -192,8 +189,8 @@ k_bi_xr(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T
     block_sums(a_rr, a_rho, part_rr, part_rho);
 }
 
-// p = r + (p - v*omega)*beta.  kBiJacobi: and p^ = p / diag, the first product's input
-template <typename T, BiPrecond P = kBiNone>
+// p = r + (p - v*omega)*beta.  kPcFused: and p^ = p / diag, the first product's input
+template <typename T, PrecondShape P = kPcNone>
 __global__ void __launch_bounds__(kBlock)
 k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T *__restrict__ p, const T *__restrict__ r, const T *__restrict__ v, uint64_t n,
        const T *__restrict__ diag = nullptr, T *__restrict__ phat = nullptr) {
@@ -205,7 +202,7 @@ k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T 
 #pragma unroll
         for (int e = 0; e < at.width; ++e) pv[e] = p_add(rv[e], p_mul(p_add(pv[e], -p_mul(vv[e], omega)), beta));
         at.store(p, pv);
-        if constexpr (P == kBiJacobi) {
+        if constexpr (P == kPcFused) {
             const auto dv = at.load(diag);
 #pragma unroll
             for (int e = 0; e < at.width; ++e) pv[e] = p_div(pv[e], dv[e]);
@@ -214,7 +211,7 @@ k_bi_p(const BiScalars<T> *__restrict__ sc, const BiMore<T> *__restrict__ mo, T 
     });
 }
 
-// kBiJacobi's set-up: p^ = p / diag (p = r)
+// kPcFused's set-up: p^ = p / diag (p = r)
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_bi_phat0(const T *__restrict__ p, const T *__restrict__ diag, T *__restrict__ phat, uint64_t n) {
     sweep<T>(n, [&](auto at) {
@@ -329,23 +326,22 @@ k_bi_beta(BiScalars<T> *sc, BiMore<T> *mo, const T *__restrict__ part_rr, const 
     }
 }
 
-// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kBiTri's handle (else unused).
-// kBiNone's chain of launches is the unpreconditioned solver's, launch for launch.
-template <typename T, BiPrecond P>
-int bicgstab_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
-               size_t *iters_out, double *rr_out, int *breakdown_out) {
+// P: precond_shape(pc).  kPcNone's chain of launches is the unpreconditioned solver's, launch for launch.
+template <typename T, PrecondShape P>
+int bicgstab_t(smh_crs *m, const Precond &pc, const SolveCall &c) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
-    constexpr bool PRE = P != kBiNone;
+    const size_t n = c.n;
+    constexpr bool PRE = P != kPcNone;
     SolveRun run;  // (its `converged` means STOPPED here)
     int breakdown = 0;
     const unsigned grid = pcg_grid(n);
     const int rc = run.run([&]() -> int {
-        if constexpr (P == kBiTri) SMH_TRY(precond_prepare(pc));
+        SMH_TRY(precond_prepare(pc));
         SMH_TRY(run.own_stream());
         const hipStream_t s = run.s;
         Scratch &ws = run.ws;
         T *x = nullptr, *r = nullptr, *rhat = nullptr, *p = nullptr, *v = nullptr, *sv = nullptr, *t = nullptr, *part = nullptr;
-        T *phat = nullptr, *shat = nullptr, *diag = nullptr, *tw = nullptr;  // p^ and s^; Jacobi: the diagonal.  Tri: the solves' scratch
+        T *phat = nullptr, *shat = nullptr, *diag = nullptr, *tw = nullptr;  // p^ and s^; fused: the diagonal.  Launched: the application's scratch
         BiScalars<T> *sc = nullptr;
         BiMore<T> *mo = nullptr;
         SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&rhat, n)); SMH_TRY(ws.alloc(&p, n));
@@ -354,47 +350,33 @@ int bicgstab_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, 
         SMH_TRY(ws.alloc(&sc, 1));
         SMH_TRY(ws.alloc(&mo, 1));
         SMH_TRY(run.h_sc.alloc(sizeof(BiScalars<T>) + sizeof(BiMore<T>), hipHostMallocDefault));
-        if constexpr (PRE) {
-            unsigned long long *d_bad = nullptr;
-            SMH_TRY(ws.alloc(&d_bad, 1));
-            SMH_TRY(ws.alloc(&phat, n)); SMH_TRY(ws.alloc(&shat, n));
-            if constexpr (P == kBiJacobi) {
-                SMH_TRY(ws.alloc(&diag, n));
-                SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
-            } else {
-                SMH_TRY(ws.alloc(&tw, n));
-                if (pc.gt) {  // the forms of the handles' AUTO products, built here and not inside a capture (no set-up application would);
-                              // their streams are drained: the handles are read on another one.  Nothing divides by their values
-                    SMH_TRY(smh_crs_prepare(pc.f, SMH_SPMV_AUTO));
-                    SMH_TRY(smh_crs_prepare(pc.gt, SMH_SPMV_AUTO));
-                } else {
-                    SMH_TRY(probe_diagonal(pc.f, n, tw, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
-                }
-            }
-        }
+        if constexpr (PRE) { SMH_TRY(ws.alloc(&phat, n)); SMH_TRY(ws.alloc(&shat, n)); }
+        if constexpr (P == kPcFused) SMH_TRY(ws.alloc(&diag, n));
+        if constexpr (P == kPcLaunched) SMH_TRY(ws.alloc(&tw, n));
+        SMH_TRY(precond_setup(pc, n, P == kPcFused ? diag : tw, ws, s));  // (tw: the solves' probe keeps no values)
         T *part_a = part, *part_b = part + kPcgBlocks;
         // r = b - A x; r^ = r; p = r; rho = r^.r; rr = r.r
-        hipLaunchKernelGGL((k_bi_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max);
-        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, r, x, v, s));
+        hipLaunchKernelGGL((k_bi_init<T>), dim3(1), dim3(1), 0, s, sc, mo, c.tol, (uint64_t)c.iter_max);
+        SMH_TRY(stage_residual(m, c.variant, (const T *)c.b, (const T *)c.x, n, r, x, v, s));
         if (n) {
             SMH_HIP(hipMemcpyAsync(rhat, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
             SMH_HIP(hipMemcpyAsync(p, r, n * sizeof(T), hipMemcpyDeviceToDevice, s));
         }
         hipLaunchKernelGGL((k_bi_dot2<T, true>), dim3(grid), dim3(kBlock), 0, s, sc, r, r, (uint64_t)n, part_a, part_b);
         hipLaunchKernelGGL((k_bi_setup<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
-        if constexpr (P == kBiJacobi) hipLaunchKernelGGL((k_bi_phat0<T>), dim3(grid), dim3(kBlock), 0, s, p, diag, phat, (uint64_t)n);
+        if constexpr (P == kPcFused) hipLaunchKernelGGL((k_bi_phat0<T>), dim3(grid), dim3(kBlock), 0, s, p, diag, phat, (uint64_t)n);
         SMH_HIP(hipGetLastError());
         const T *pin = PRE ? phat : p, *sin = PRE ? shat : sv;  // what the two products read
         auto body = [&]() -> int {
-            if constexpr (P == kBiTri) SMH_TRY(precond_apply_enqueue(pc, p, tw, phat, &mo->enter, s));
-            SMH_TRY(spmv_enqueue(m, pin, n, v, variant, s));
+            if constexpr (P == kPcLaunched) SMH_TRY(precond_apply_enqueue(pc, p, tw, phat, &mo->enter, s));
+            SMH_TRY(spmv_enqueue(m, pin, n, v, c.variant, s));
             hipLaunchKernelGGL((k_bi_dot<T>), dim3(grid), dim3(kBlock), 0, s, sc, rhat, v, (uint64_t)n, part_a);
             hipLaunchKernelGGL((k_bi_alpha<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
             hipLaunchKernelGGL((k_bi_s<T, P>), dim3(grid), dim3(kBlock), 0, s, sc, r, v, sv, (uint64_t)n, part_a, diag, shat);
             hipLaunchKernelGGL((k_bi_half<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, grid);
             SMH_HIP(hipGetLastError());
-            if constexpr (P == kBiTri) SMH_TRY(precond_apply_enqueue(pc, sv, tw, shat, &sc->active, s));
-            SMH_TRY(spmv_enqueue(m, sin, n, t, variant, s));
+            if constexpr (P == kPcLaunched) SMH_TRY(precond_apply_enqueue(pc, sv, tw, shat, &sc->active, s));
+            SMH_TRY(spmv_enqueue(m, sin, n, t, c.variant, s));
             hipLaunchKernelGGL((k_bi_dot2<T, false>), dim3(grid), dim3(kBlock), 0, s, sc, t, sv, (uint64_t)n, part_a, part_b);
             hipLaunchKernelGGL((k_bi_omega<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_a, part_b, grid);
             hipLaunchKernelGGL((k_bi_xr<T, PRE>), dim3(grid), dim3(kBlock), 0, s, sc, mo, x, pin, sv, t, rhat, r, (uint64_t)n, part_a, part_b, shat);
@@ -403,57 +385,29 @@ int bicgstab_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, 
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        if constexpr (P == kBiTri) {
-            // the node budget of a captured batch (pcg.hip's): two applications, two products (a few nodes each at most) and the chain of 9
+        if constexpr (P == kPcLaunched) {
+            // the node budget of a captured batch: two applications, two products (a few nodes each at most) and the chain of 9
             bool capture = true;
-            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 2 * (1 + 3) + 9, check_every, &capture);
-            SMH_TRY(run.loop(dt, iter_max, bodies, body, sc, capture));
+            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 2 * (1 + 3) + 9, c.check_every, &capture);
+            SMH_TRY(run.loop(dt, c.iter_max, bodies, body, sc, capture));
         } else {
-            SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+            SMH_TRY(run.loop(dt, c.iter_max, c.check_every, body, sc));
         }
         BiMore<T> *h_mo = (BiMore<T> *)((char *)run.h_sc.get() + sizeof(BiScalars<T>));
         SMH_HIP(hipMemcpyAsync(h_mo, mo, sizeof(BiMore<T>), hipMemcpyDeviceToHost, s));
-        if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
+        if (n) SMH_HIP(hipMemcpyAsync(c.x, x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         breakdown = (int)h_mo->breakdown;
         return SMH_OK;
-    }, iters_out, rr_out);
-    if (rc == SMH_OK && breakdown_out) *breakdown_out = breakdown;
+    }, c.iters_out, c.rr_out);
+    if (rc == SMH_OK && c.breakdown_out) *c.breakdown_out = breakdown;
     return rc;
 }
 
-template <typename T>
-int bicgstab_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant,
-               size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
-    const T *b = (const T *)b_in;
-    T *x = (T *)x_io;
-    const Precond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
-    switch (precond) {
-    case SMH_PRECOND_NONE:
-        return bicgstab_t<T, kBiNone>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    case SMH_PRECOND_JACOBI:
-        return bicgstab_t<T, kBiJacobi>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    default:
-        if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-        return bicgstab_t<T, kBiTri>(m, pc, b, x, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    }
-}
-
-// M^-1 = gt o g, a pair of product handles (fsai.hip): the driver of the triangular kinds with Precond's pair
-int bicgstab_fsai(smh_crs *m, smh_crs *g, smh_crs *gt, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
-                  size_t *iters_out, double *rr_out, int *breakdown_out) {
-    const Precond pc = fsai_precond(g, gt);
-    if (g->orphans || gt->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-    if (m->dtype == SMH_F64)
-        return bicgstab_t<double, kBiTri>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    return bicgstab_t<float, kBiTri>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-}
-
-// precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
-int bicgstab(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant,
-             size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
-    if (m->dtype == SMH_F64) return bicgstab_p<double>(m, precond, f, b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    return bicgstab_p<float>(m, precond, f, b_in, x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+// the handles' check, then the driver of the matrix's dtype and the preconditioner's shape
+int bicgstab(smh_crs *m, const Precond &pc, const SolveCall &c) {
+    SMH_TRY(precond_check_handles(pc));
+    return with_dtype_and_shape(m->dtype, precond_shape(pc), [&](auto t, auto shape) { return bicgstab_t<decltype(t), decltype(shape)::value>(m, pc, c); });
 }
 
 constexpr size_t kBiCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
@@ -463,14 +417,14 @@ constexpr size_t kBiCheckEvery = 8;  // bodies per poll that check_every = 0, an
 // the statuses are decided here (check_solve_vec / check_solve_host, solver_host.hpp), before any launch
 extern "C" int smh_bicgstab_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                       size_t *iters_out, double *rr_out, int *breakdown_out) {
-    SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery));
-    return bicgstab(m, SMH_PRECOND_NONE, nullptr, b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_solve_vec(m, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kBiCheckEvery));
+    return bicgstab(m, no_precond(), {b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out});
 }
 
 extern "C" int smh_bicgstab_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                   int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
-    return bicgstab(m, SMH_PRECOND_NONE, nullptr, b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+    return bicgstab(m, no_precond(), {b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out});
 }
 
 // Right-preconditioned: `precond` and `f` first (check_precond, precond.hpp: as smh_gmres_precond_solve*), then the checks above (with
@@ -480,8 +434,8 @@ extern "C" int smh_bicgstab_precond_solve_vec(smh_crs *a, int precond, smh_crs *
                                               int variant, size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
     SMH_TRY(check_precond(precond, f));
     if (precond == SMH_PRECOND_NONE) return smh_bicgstab_solve_vec(a, b, x, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
-    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery, f));
-    return bicgstab(a, precond, f, b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kBiCheckEvery, f));
+    return bicgstab(a, precond_of(precond, a, f), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out});
 }
 
 extern "C" int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
@@ -489,26 +443,20 @@ extern "C" int smh_bicgstab_precond_solve(smh_crs *a, int precond, smh_crs *f, c
     SMH_TRY(check_precond(precond, f));
     if (precond == SMH_PRECOND_NONE) return smh_bicgstab_solve(a, b_host, b_len, x_host_inout, x_len, tol, iter_max, variant, iters_out, rr_out, breakdown_out);
     SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, f));
-    return bicgstab(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+    return bicgstab(a, precond_of(precond, a, f), {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out});
 }
 
 // Right-preconditioned by a pair of product handles, M^-1 v = gt (g v): (G_L, G_U) of smh_crs_fsai_ns, or (G, G^T) of smh_crs_fsai for
 // a symmetric a.  The pair's checks are smh_pcg_fsai_solve's; nothing is probed (no operation divides by a factor's value); a stored
 // column >= n is decided in the driver before its first launch
-constexpr const char *kBiFsaiName = "FSAI preconditioner";
-
 extern "C" int smh_bicgstab_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
                                            size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kBiCheckEvery, g, kBiFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kBiFsaiName));
-    return bicgstab_fsai(a, g, gt, b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_pair_vec(a, g, gt, kFsaiName, b, x, &check_every, kBiCheckEvery));
+    return bicgstab(a, fsai_precond(g, gt), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out});
 }
 
 extern "C" int smh_bicgstab_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                                        size_t iter_max, int variant, size_t *iters_out, double *rr_out, int *breakdown_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, g, kBiFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kBiFsaiName));
-    return bicgstab_fsai(a, g, gt, b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out);
+    SMH_TRY(check_pair_host(a, g, gt, kFsaiName, b_host, b_len, x_host_inout, x_len, /*refuse_aliased*/ true));
+    return bicgstab(a, fsai_precond(g, gt), {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kBiCheckEvery, iters_out, rr_out, breakdown_out});
 }

@@ -56,21 +56,21 @@
 //   body:       u = M^-1 v_j;  w = A u        (both Gram-Schmidt passes, the step and v_{j+1} = w / hn as above)
 //   cycle end:  t = (..(v_0 y_0 + v_1 y_1) .. + v_{j-1} y_{j-1})   (starts from the product, as r does);  q = M^-1 t;  x = x + q
 //               (r, rr and the restart as above: rebuilt from the basis, no product)
-// The driver is instantiated per GmPrecond; kGmNone's chain of launches is the one described above, launch for launch.
-// kGmJacobi: M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe, as Jacobi-PCG forms z), and costs no
+// The driver is instantiated per PrecondShape (precond.hpp); kPcNone's chain of launches is the one described above, launch for launch.
+// kPcFused (Jacobi): M^-1 v is v_i / d_i, a division, d_i the first stored (i, i) (precond.hpp's probe, as Jacobi-PCG forms z), and costs no
 // launch: both forms of the normalising sweep write v to its column and v / d to the product's fixed input, the cycle end's sweep
 // keeps t in registers and stores x + t / d.  One read of d each: a body at column j moves (4 j + 14) n values beside the product, a
 // cycle end and a restart's v_0 one more each; (m + 6) n values of storage.
-// kGmTri: M^-1 is two level-scheduled triangular solves on one handle (Precond, precond.hpp: SGS on the matrix itself, ILU(0) on
-// a factor).  The body's chain opens with the application vin -> u (the product then reads u); the cycle end's sweep writes t where
+// kPcLaunched: M^-1 is applied by launches of its own (Precond, precond.hpp); for SGS on the matrix itself and ILU(0) on a factor, two
+// level-scheduled triangular solves on one handle.  The body's chain opens with the application vin -> u (the product then reads u); the cycle end's sweep writes t where
 // w was (w is free once v_{j+1} is formed) and r with the partials of r.r, one application t -> q follows in place, then the sweep
 // x += q.  Every triangular launch takes a device gate word: the cycle end's is do_end, the body's is GmMore::enter -- "the next body
 // will be entered" -- which the set-up's and the restart's k_gm_begin and every k_gm_step leave (iters == iter_max is a stop, so
 // after a step "not stopped" says it all; the set-up compares with iter_max itself), so bodies enqueued past the stop run no solve.
-// (m + 7) n values of storage.  A captured batch holds two applications per body: pcg.hip's node budget (bodies_within_budget)
+// (m + 7) n values of storage.  A captured batch holds two applications per body: the node budget (bodies_within_budget, precond.hpp)
 // makes the batches smaller or drops the capture, which changes no bit.
 // rr is the RECURRENCE residual's r.r: where the solves amplify rounding it parts from |b - A x|^2.
-// A pair of product handles (smh_gmres_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs kGmTri's chain with Precond's pair, and
+// A pair of product handles (smh_gmres_fsai_solve*: M^-1 v = gt (g v), fsai.hip's factors) runs the same chain with Precond's products, and
 // the same (m + 7) n values: no vector more.  The body's application vin -> u is two products through the handles' own AUTO kernels,
 // ungated as the body's own product is: past the stop they form the same u from the same vin again.  The cycle end's q = M^-1 t is
 // formed by two GATED storage-order products (precond.hpp's k_gated_seq on do_end: w -> tw -> w, SMH_SPMV_SEQ's bits), which return
@@ -89,9 +89,6 @@ namespace {
 constexpr int kGmMaxM = 128;
 constexpr int kGmTile = 8;  // columns per load of w in the dots (no bit depends on it)
 constexpr size_t kGmDefaultRestart = 30;
-
-// how M^-1 is applied (the header's last paragraph): not at all, inside the sweeps, or by two triangular solves on a handle
-enum GmPrecond { kGmNone, kGmJacobi, kGmTri };
 
 // the block the host polls through CG's reader (cg_read_scalars)
 template <typename T>
@@ -116,7 +113,7 @@ struct GmMore {
     uint32_t do_end;     // gate: a cycle end is due (the x / r sweep and its fold)
     uint32_t do_v0;      // gate: a restart is due (v_0 = r / beta)
     uint32_t restart;    // the cycle end that is due is a restart (not a stop)
-    uint32_t enter;      // gate: the next body will be entered (the triangular solves that open it are due)
+    uint32_t enter;      // gate: the next body will be entered (the application that opens it is due)
     T hn, beta;
     T g[kGmMaxM + 1], c[kGmMaxM], s[kGmMaxM], h1[kGmMaxM + 1], h2[kGmMaxM + 1], y[kGmMaxM], z[kGmMaxM + 1];
     T R[kGmMaxM * kGmMaxM];  // R_{i,k} at [k * kGmMaxM + i], i <= k
@@ -225,8 +222,8 @@ __global__ void __launch_bounds__(kBlock) k_gm_rr(const T *__restrict__ r, uint6
 }
 
 // V0 false: v_j = w / hn (w itself when hn == 0), to its column and to vin.  V0 true: v_0 = r / beta, the same two places.
-// kGmJacobi: vin takes u = v / diag, the product's input, instead
-template <typename T, bool V0, GmPrecond P = kGmNone>
+// kPcFused: vin takes u = v / diag, the product's input, instead
+template <typename T, bool V0, PrecondShape P = kPcNone>
 __global__ void __launch_bounds__(kBlock)
 k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__restrict__ basis, uint64_t ld, T *__restrict__ vin, uint64_t n,
           const T *__restrict__ diag = nullptr) {
@@ -241,7 +238,7 @@ k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__rest
             for (int e = 0; e < at.width; ++e) v[e] = p_div(v[e], d);
         }
         at.store(colp, v);
-        if constexpr (P == kGmJacobi) {
+        if constexpr (P == kPcFused) {
             const auto dv = at.load(diag);
 #pragma unroll
             for (int e = 0; e < at.width; ++e) v[e] = p_div(v[e], dv[e]);
@@ -251,9 +248,9 @@ k_gm_norm(const GmMore<T> *__restrict__ mo, const T *__restrict__ src, T *__rest
 }
 
 // the cycle end: x += sum v_c y_c (c < j), r = sum v_c z_c (c <= j), the partials of r.r.  Preconditioned, the sum t starts from
-// its first product and stays out of x: kGmJacobi keeps it in registers and stores x + t / diag; kGmTri writes it to t_out (x is
+// its first product and stays out of x: kPcFused keeps it in registers and stores x + t / diag; kPcLaunched writes it to t_out (x is
 // not touched: x += M^-1 t follows)
-template <typename T, GmPrecond P = kGmNone>
+template <typename T, PrecondShape P = kPcNone>
 __global__ void __launch_bounds__(kBlock)
 k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ x, T *__restrict__ r, uint64_t n, T *__restrict__ part_rr,
         const T *__restrict__ diag = nullptr, T *__restrict__ t_out = nullptr) {
@@ -263,13 +260,13 @@ k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t 
     T acc = T(0);
     sweep<T>(n, [&](auto at) {
         typename decltype(at)::pack xv, rv;  // xv: x and its sum, or (preconditioned) t
-        if constexpr (P == kGmNone) xv = at.load(x);
+        if constexpr (P == kPcNone) xv = at.load(x);
         {
             const auto vv = at.load(basis);
             const T y0 = y[0], z0 = z[0];
 #pragma unroll
             for (int e = 0; e < at.width; ++e) {
-                if constexpr (P == kGmNone) xv[e] = p_add(xv[e], p_mul(vv[e], y0));
+                if constexpr (P == kPcNone) xv[e] = p_add(xv[e], p_mul(vv[e], y0));
                 else xv[e] = p_mul(vv[e], y0);
                 rv[e] = p_mul(vv[e], z0);
             }
@@ -293,18 +290,18 @@ k_gm_xr(const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t 
                 acc = p_add(acc, p_mul(rv[e], rv[e]));
             }
         }
-        if constexpr (P == kGmJacobi) {
+        if constexpr (P == kPcFused) {
             const auto x0 = at.load(x), dv = at.load(diag);
 #pragma unroll
             for (int e = 0; e < at.width; ++e) xv[e] = p_add(x0[e], p_div(xv[e], dv[e]));
         }
-        at.store(P == kGmTri ? t_out : x, xv);
+        at.store(P == kPcLaunched ? t_out : x, xv);
         at.store(r, rv);
     });
     block_partial(acc, part_rr);
 }
 
-// kGmTri's last sweep of a cycle end: x = x + q, q = M^-1 t
+// kPcLaunched's last sweep of a cycle end: x = x + q, q = M^-1 t
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_gm_xadd(const GmMore<T> *__restrict__ mo, T *__restrict__ x, const T *__restrict__ q, uint64_t n) {
     if (!mo->do_end) return;
@@ -408,25 +405,24 @@ __global__ void __launch_bounds__(kBlock) k_gm_step(GmScalars<T> *sc, GmMore<T> 
     }
 }
 
-// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop.  pc: kGmTri's handle (else unused).
-// kGmNone's chain of launches is the unpreconditioned solver's, launch for launch.
-template <typename T, GmPrecond P>
-int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
-            size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
+// P: precond_shape(pc).  kPcNone's chain of launches is the unpreconditioned solver's, launch for launch.
+template <typename T, PrecondShape P>
+int gmres_t(smh_crs *m, const Precond &pc, const SolveCall &c) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
     constexpr size_t V = 16 / sizeof(T);
+    const size_t n = c.n, restart = c.restart;
     SolveRun run;  // (its `converged` means STOPPED here)
     int breakdown = 0;
     size_t cycles = 0;
     const unsigned grid = pcg_grid(n);
     const uint64_t ld = (n + V - 1) / V * V;
     const int rc = run.run([&]() -> int {
-        if constexpr (P == kGmTri) SMH_TRY(precond_prepare(pc));
+        SMH_TRY(precond_prepare(pc));
         SMH_TRY(run.own_stream());
         const hipStream_t s = run.s;
         Scratch &ws = run.ws;
         T *x = nullptr, *r = nullptr, *w = nullptr, *vin = nullptr, *basis = nullptr, *part = nullptr, *part_ww = nullptr;
-        T *diag = nullptr, *u = nullptr, *tw = nullptr;  // Jacobi: the diagonal.  Tri: u = M^-1 v_j and the solves' scratch
+        T *diag = nullptr, *u = nullptr, *tw = nullptr;  // fused: the diagonal.  Launched: u = M^-1 v_j and the application's scratch
         GmScalars<T> *sc = nullptr;
         GmMore<T> *mo = nullptr;
         SMH_TRY(ws.alloc(&x, n)); SMH_TRY(ws.alloc(&r, n)); SMH_TRY(ws.alloc(&w, n)); SMH_TRY(ws.alloc(&vin, n));
@@ -437,37 +433,23 @@ int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, dou
         SMH_TRY(ws.alloc(&mo, 1));
         constexpr size_t more_head = offsetof(GmMore<T>, hn);
         SMH_TRY(run.h_sc.alloc(sizeof(GmScalars<T>) + more_head, hipHostMallocDefault));
-        if constexpr (P != kGmNone) {
-            unsigned long long *d_bad = nullptr;
-            SMH_TRY(ws.alloc(&d_bad, 1));
-            if constexpr (P == kGmJacobi) {
-                SMH_TRY(ws.alloc(&diag, n));
-                SMH_TRY(probe_diagonal(m, n, diag, d_bad, "Jacobi preconditioner", s));
-            } else {
-                SMH_TRY(ws.alloc(&u, n)); SMH_TRY(ws.alloc(&tw, n));
-                if (pc.gt) {  // the forms of the handles' AUTO products, built here and not inside a capture (no set-up application would);
-                              // their streams are drained: the handles are read on another one.  Nothing divides by their values
-                    SMH_TRY(smh_crs_prepare(pc.f, SMH_SPMV_AUTO));
-                    SMH_TRY(smh_crs_prepare(pc.gt, SMH_SPMV_AUTO));
-                } else {
-                    SMH_TRY(probe_diagonal(pc.f, n, u, d_bad, pc.name, s));  // (the values are not kept: the solves read the handle's)
-                }
-            }
-        }
+        if constexpr (P == kPcFused) SMH_TRY(ws.alloc(&diag, n));
+        if constexpr (P == kPcLaunched) { SMH_TRY(ws.alloc(&u, n)); SMH_TRY(ws.alloc(&tw, n)); }
+        SMH_TRY(precond_setup(pc, n, P == kPcFused ? diag : u, ws, s));  // (u: the solves' probe keeps no values)
         // r = b - A x (w: scratch); rr = r.r; beta; v_0
-        hipLaunchKernelGGL((k_gm_init<T>), dim3(1), dim3(1), 0, s, sc, mo, tol, (uint64_t)iter_max, (uint32_t)restart);
-        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, r, x, w, s));
+        hipLaunchKernelGGL((k_gm_init<T>), dim3(1), dim3(1), 0, s, sc, mo, c.tol, (uint64_t)c.iter_max, (uint32_t)restart);
+        SMH_TRY(stage_residual(m, c.variant, (const T *)c.b, (const T *)c.x, n, r, x, w, s));
         hipLaunchKernelGGL((k_gm_rr<T>), dim3(grid), dim3(kBlock), 0, s, r, (uint64_t)n, part_ww);
         hipLaunchKernelGGL((k_gm_begin<T, true>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
         hipLaunchKernelGGL((k_gm_norm<T, true, P>), dim3(grid), dim3(kBlock), 0, s, mo, r, basis, ld, vin, (uint64_t)n, diag);
         SMH_HIP(hipGetLastError());
         const dim3 cols((unsigned)restart + 1);
         auto body = [&]() -> int {
-            if constexpr (P == kGmTri) {
+            if constexpr (P == kPcLaunched) {
                 SMH_TRY(precond_apply_enqueue(pc, vin, tw, u, &mo->enter, s));
-                SMH_TRY(spmv_enqueue(m, u, n, w, variant, s));
+                SMH_TRY(spmv_enqueue(m, u, n, w, c.variant, s));
             } else {
-                SMH_TRY(spmv_enqueue(m, vin, n, w, variant, s));
+                SMH_TRY(spmv_enqueue(m, vin, n, w, c.variant, s));
             }
             hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
             hipLaunchKernelGGL((k_gm_fold<T, 1>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
@@ -479,7 +461,7 @@ int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, dou
             hipLaunchKernelGGL((k_gm_norm<T, false, P>), dim3(grid), dim3(kBlock), 0, s, mo, w, basis, ld, vin, (uint64_t)n, diag);
             hipLaunchKernelGGL((k_gm_xr<T, P>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww, diag, w);  // (w is free)
             hipLaunchKernelGGL((k_gm_begin<T, false>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
-            if constexpr (P == kGmTri) {  // q = M^-1 t in place, x += q: due at a cycle end alone
+            if constexpr (P == kPcLaunched) {  // q = M^-1 t in place, x += q: due at a cycle end alone
                 SMH_TRY(precond_apply_gated_enqueue(pc, w, tw, w, &mo->do_end, s));
                 hipLaunchKernelGGL((k_gm_xadd<T>), dim3(grid), dim3(kBlock), 0, s, mo, x, w, (uint64_t)n);
             }
@@ -487,62 +469,31 @@ int gmres_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, dou
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        if constexpr (P == kGmTri) {
-            // the node budget of a captured batch (pcg.hip's): two applications, the product (a few nodes at most) and the chain of 12
+        if constexpr (P == kPcLaunched) {
+            // the node budget of a captured batch: two applications, the product (a few nodes at most) and the chain of 12
             bool capture = true;
-            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 1 + 3 + 12, check_every, &capture);
-            SMH_TRY(run.loop(dt, iter_max, bodies, body, sc, capture));
+            const size_t bodies = bodies_within_budget(2 * precond_apply_nodes(pc) + 1 + 3 + 12, c.check_every, &capture);
+            SMH_TRY(run.loop(dt, c.iter_max, bodies, body, sc, capture));
         } else {
-            SMH_TRY(run.loop(dt, iter_max, check_every, body, sc));
+            SMH_TRY(run.loop(dt, c.iter_max, c.check_every, body, sc));
         }
         GmMore<T> *h_mo = (GmMore<T> *)((char *)run.h_sc.get() + sizeof(GmScalars<T>));  // (its head alone)
         SMH_HIP(hipMemcpyAsync(h_mo, mo, more_head, hipMemcpyDeviceToHost, s));
-        if (n) SMH_HIP(hipMemcpyAsync(x_io, x, n * sizeof(T), hipMemcpyDefault, s));
+        if (n) SMH_HIP(hipMemcpyAsync(c.x, x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         breakdown = (int)h_mo->breakdown;
         cycles = (size_t)h_mo->cycles;
         return SMH_OK;
-    }, iters_out, rr_out);
-    if (rc == SMH_OK && breakdown_out) *breakdown_out = breakdown;
-    if (rc == SMH_OK && cycles_out) *cycles_out = cycles;
+    }, c.iters_out, c.rr_out);
+    if (rc == SMH_OK && c.breakdown_out) *c.breakdown_out = breakdown;
+    if (rc == SMH_OK && c.cycles_out) *c.cycles_out = cycles;
     return rc;
 }
 
-template <typename T>
-int gmres_p(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
-            size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
-    const T *b = (const T *)b_in;
-    T *x = (T *)x_io;
-    const Precond pc = precond == SMH_PRECOND_ILU ? ilu_precond(f) : sgs_precond(m);
-    switch (precond) {
-    case SMH_PRECOND_NONE:
-        return gmres_t<T, kGmNone>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
-    case SMH_PRECOND_JACOBI:
-        return gmres_t<T, kGmJacobi>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
-    default:
-        if (pc.f->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-        return gmres_t<T, kGmTri>(m, pc, b, x, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
-    }
-}
-
-// M^-1 = gt o g, a pair of product handles (fsai.hip): the driver of the triangular kinds with Precond's pair
-int gmres_fsai(smh_crs *m, smh_crs *g, smh_crs *gt, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
-               size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
-    const Precond pc = fsai_precond(g, gt);
-    if (g->orphans || gt->orphans) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-    if (m->dtype == SMH_F64)
-        return gmres_t<double, kGmTri>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out,
-                                       cycles_out, breakdown_out);
-    return gmres_t<float, kGmTri>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
-                                  breakdown_out);
-}
-
-// precond: SMH_PRECOND_*; f: the ILU factor's handle (else unused)
-int gmres(smh_crs *m, int precond, smh_crs *f, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, size_t restart, int variant,
-          size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
-    if (m->dtype == SMH_F64)
-        return gmres_p<double>(m, precond, f, b_in, x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
-    return gmres_p<float>(m, precond, f, b_in, x_io, n, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+// the handles' check, then the driver of the matrix's dtype and the preconditioner's shape
+int gmres(smh_crs *m, const Precond &pc, const SolveCall &c) {
+    SMH_TRY(precond_check_handles(pc));
+    return with_dtype_and_shape(m->dtype, precond_shape(pc), [&](auto t, auto shape) { return gmres_t<decltype(t), decltype(shape)::value>(m, pc, c); });
 }
 
 constexpr size_t kGmCheckEvery = 8;  // bodies per poll that check_every = 0, and the host form, stand for
@@ -552,18 +503,16 @@ constexpr size_t kGmCheckEvery = 8;  // bodies per poll that check_every = 0, an
 // the statuses are decided here (solver_host.hpp), before any launch: BiCGSTAB's, then the range of `restart`
 extern "C" int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart, int variant,
                                    size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
-    SMH_TRY(check_solve_vec(m, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery));
+    SMH_TRY(check_solve_vec(m, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kGmCheckEvery));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(m, SMH_PRECOND_NONE, nullptr, b->d, x->d, m->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out,
-                 breakdown_out);
+    return gmres(m, no_precond(), {b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }
 
 extern "C" int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                size_t restart, int variant, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(m, SMH_PRECOND_NONE, nullptr, b_host, x_host_inout, m->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out,
-                 cycles_out, breakdown_out);
+    return gmres(m, no_precond(), {b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kGmCheckEvery, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }
 
 // Right-preconditioned: `precond` and `f` first (check_precond, precond.hpp), then the checks above (with ILU's factor against the matrix, as smh_pcg_ilu_solve);
@@ -573,9 +522,9 @@ extern "C" int smh_gmres_precond_solve_vec(smh_crs *a, int precond, smh_crs *f, 
                                            int *breakdown_out) {
     SMH_TRY(check_precond(precond, f));
     if (precond == SMH_PRECOND_NONE) return smh_gmres_solve_vec(a, b, x, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
-    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery, f));
+    SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kGmCheckEvery, f));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(a, precond, f, b->d, x->d, a->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    return gmres(a, precond_of(precond, a, f), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }
 
 extern "C" int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len,
@@ -585,31 +534,25 @@ extern "C" int smh_gmres_precond_solve(smh_crs *a, int precond, smh_crs *f, cons
     if (precond == SMH_PRECOND_NONE) return smh_gmres_solve(a, b_host, b_len, x_host_inout, x_len, tol, iter_max, restart, variant, iters_out, rr_out, cycles_out, breakdown_out);
     SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, f));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres(a, precond, f, b_host, x_host_inout, a->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out,
-                 breakdown_out);
+    return gmres(a, precond_of(precond, a, f),
+                 {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kGmCheckEvery, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }
 
 // Right-preconditioned by a pair of product handles, M^-1 v = gt (g v): (G_L, G_U) of smh_crs_fsai_ns, or (G, G^T) of smh_crs_fsai for
 // a symmetric a.  The pair's checks are smh_pcg_fsai_solve's, then the restart's; nothing is probed (no operation divides by a factor's
 // value); a stored column >= n is decided in the driver before its first launch
-constexpr const char *kGmFsaiName = "FSAI preconditioner";
-
 extern "C" int smh_gmres_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart,
                                         int variant, size_t check_every, size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_vec(a, b, x, "vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kGmCheckEvery, g, kGmFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kGmFsaiName));
+    SMH_TRY(check_pair_vec(a, g, gt, kFsaiName, b, x, &check_every, kGmCheckEvery));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres_fsai(a, g, gt, b->d, x->d, a->n_rows, tol, iter_max, restart, variant, check_every, iters_out, rr_out, cycles_out, breakdown_out);
+    return gmres(a, fsai_precond(g, gt), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }
 
 extern "C" int smh_gmres_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                                     size_t iter_max, size_t restart, int variant, size_t *iters_out, double *rr_out, size_t *cycles_out,
                                     int *breakdown_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ true, g, kGmFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kGmFsaiName));
+    SMH_TRY(check_pair_host(a, g, gt, kFsaiName, b_host, b_len, x_host_inout, x_len, /*refuse_aliased*/ true));
     SMH_TRY(check_solve_restart(&restart, kGmDefaultRestart, kGmMaxM));
-    return gmres_fsai(a, g, gt, b_host, x_host_inout, a->n_rows, tol, iter_max, restart, variant, kGmCheckEvery, iters_out, rr_out, cycles_out,
-                      breakdown_out);
+    return gmres(a, fsai_precond(g, gt),
+                 {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kGmCheckEvery, iters_out, rr_out, breakdown_out, restart, cycles_out});
 }

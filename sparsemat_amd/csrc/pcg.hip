@@ -15,15 +15,15 @@
 // bodies and polls one small block per batch (solve_in_batches, internal.hpp) -- no synchronisation inside an iteration.
 // The sweeps state their arithmetic once, on solver_tree.hpp's sweep; the sums and the one-workgroup folds of their partials are
 // its tree (block_sums / block_sum1, fold1 / fold2) -- deterministic.
-// The second half of the file is the same recurrence preconditioned by two level-scheduled triangular solves (trisolve.hip) on one
-// handle (Precond, precond.hpp), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel
-// (smh_pcg_sgs_solve*, smh_crs_sgs_apply_vec) solves on the matrix itself, ILU(0) (smh_pcg_ilu_solve*, smh_crs_ilu_apply_vec) on a
-// factor handle (ilu.hip).  The same Precond holds FSAI's pair of factor handles (smh_pcg_fsai_solve*, smh_crs_fsai_apply_vec;
-// fsai.hip), whose z = G^T (G r) is two products of the handles' own kernels where the others take two solves.
-// Host side: both drivers (pcg_t, pcg_tri_t) are their allocations, their set-up launches, a body lambda and SolveRun::run
-// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); the zero-diagonal probe, Precond and the node budget of a
-// captured batch are precond.hpp's (shared with gmres.hip), the source of p.Ap one function here (pap_source); the entry points'
-// argument checks are solver_host.hpp's.
+// The second half of the file is the same recurrence with a preconditioner that is applied by launches of its own (Precond,
+// precond.hpp), where z is a vector; the scalars, k_pcg_alpha and the sums are these.  Symmetric Gauss-Seidel (smh_pcg_sgs_solve*,
+// smh_crs_sgs_apply_vec) is two level-scheduled triangular solves (trisolve.hip) on the matrix itself, ILU(0) (smh_pcg_ilu_solve*,
+// smh_crs_ilu_apply_vec) the same on a factor handle (ilu.hip), FSAI (smh_pcg_fsai_solve*, smh_crs_fsai_apply_vec; fsai.hip)
+// z = G^T (G r) by two products of a pair of factor handles' own kernels.
+// Host side: both drivers (pcg_t, pcg_launched_t) are their allocations, their set-up launches, a body lambda and SolveRun::run
+// (solver_host.hpp: the stream, the workspaces, the drain, r = b - A x); Precond, its set-up (the zero-diagonal probe) and the node
+// budget of a captured batch are precond.hpp's (shared with gmres.hip and bicgstab.hip), the source of p.Ap one function here
+// (pap_source); the entry points' argument checks are solver_host.hpp's.
 #include "internal.hpp"
 #include "precond.hpp"
 #include "solver_host.hpp"
@@ -169,7 +169,7 @@ k_pcg_p(const PcgScalars<T> *__restrict__ sc, T *__restrict__ p, const T *__rest
     });
 }
 
-// ---- host side: what the Jacobi driver here and the triangular one below share (the zero-diagonal probe: precond.hpp) --------------------
+// ---- host side: what the Jacobi driver here and the launched one below share (the preconditioner's set-up: precond.hpp) ---------------
 // Where p.Ap comes from after the product Ap = A p that was handed d_dot: out of the product's epilogue when the kernel offers it
 // (K1s: n_dot per-tile partials in d_dot; more than 1024 of them are folded by a full grid first), else a separate two-stage dot.
 // Enqueues what that takes and returns what k_pcg_alpha folds.  dot_scratch: 2 * kReducePartials + 8 values (the dot's partials,
@@ -196,9 +196,11 @@ int pap_source(const T *p, const T *ap, size_t n, const T *d_dot, size_t n_dot, 
     return SMH_OK;
 }
 
+// (c.b and c.x: host memory; batches of 8, c.check_every is not read)
 template <typename T>
-int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
+int pcg_t(smh_crs *m, const SolveCall &c) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    const size_t n = c.n;
     SolveRun run;
     const unsigned grid = pcg_grid(n);
     return run.run([&]() -> int {
@@ -207,20 +209,18 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
         Scratch &ws = run.ws;
         T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_d = nullptr, *d_part = nullptr, *d_dot = nullptr;
         PcgScalars<T> *d_sc = nullptr;
-        unsigned long long *d_bad = nullptr;
         SMH_TRY(ws.alloc(&d_x, n)); SMH_TRY(ws.alloc(&d_r, n)); SMH_TRY(ws.alloc(&d_p, n));
         SMH_TRY(ws.alloc(&d_ap, n)); SMH_TRY(ws.alloc(&d_d, n));
         SMH_TRY(ws.alloc(&d_part, 2 * (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
         SMH_TRY(ws.alloc(&d_sc, 1));
-        SMH_TRY(ws.alloc(&d_bad, 1));
+        SMH_TRY(precond_setup(jacobi_precond(m), n, d_d, ws, s));
         SMH_TRY(run.h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
         T *part_rr = d_part, *part_rz = d_part + kPcgBlocks, *dot_scratch = d_part + 2 * kPcgBlocks;
-        const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
+        const size_t n_dot = spmv_fused_dot_partials(m, n, c.variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
-        SMH_TRY(probe_diagonal(m, n, d_d, d_bad, "Jacobi preconditioner", s));
         // r = b - A x; p = r / d; rr, rz
-        hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
-        SMH_TRY(stage_residual(m, variant, b_host, x_host, n, d_r, d_x, d_ap, s));
+        hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, c.tol, (uint64_t)c.iter_max);
+        SMH_TRY(stage_residual(m, c.variant, (const T *)c.b, (const T *)c.x, n, d_r, d_x, d_ap, s));
         hipLaunchKernelGGL((k_pcg_update<T, false>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_d, (uint64_t)n, part_rr, part_rz);
         hipLaunchKernelGGL((k_pcg_beta<T, true>), dim3(1), dim3(kBlock), 0, s, d_sc, part_rr, part_rz, grid);
         hipLaunchKernelGGL((k_pcg_p<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_p, d_r, d_d, d_x, (uint64_t)n);
@@ -228,7 +228,7 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
         // one loop body: SpMV (+ p.Ap), alpha, update of r + partials, stop test / beta, x and p
         auto body = [&]() -> int {
             PapSource<T> pap;
-            SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, variant, s, d_dot));
+            SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, c.variant, s, d_dot));
             SMH_TRY(pap_source(d_p, d_ap, n, d_dot, n_dot, dot_scratch, s, &pap));
             hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, pap.vals, pap.count);
             hipLaunchKernelGGL((k_pcg_update<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_d, (uint64_t)n, part_rr, part_rz);
@@ -237,11 +237,11 @@ int pcg_t(smh_crs *m, const T *b_host, T *x_host, size_t n, double tol, size_t i
             SMH_HIP(hipGetLastError());
             return SMH_OK;
         };
-        SMH_TRY(run.loop(dt, iter_max, 8, body, d_sc));
-        if (n) SMH_HIP(hipMemcpyAsync(x_host, d_x, n * sizeof(T), hipMemcpyDeviceToHost, s));
+        SMH_TRY(run.loop(dt, c.iter_max, 8, body, d_sc));
+        if (n) SMH_HIP(hipMemcpyAsync(c.x, d_x, n * sizeof(T), hipMemcpyDeviceToHost, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
-    }, iters_out, rr_out);
+    }, c.iters_out, c.rr_out);
 }
 
 
@@ -320,11 +320,11 @@ __global__ void __launch_bounds__(kBlock) k_sgs_p(const PcgScalars<T> *__restric
     });
 }
 
-// b_in / x_io: n values each, in host or device memory; x_io is written once, after the loop
+// pc: applied by launches (kPcLaunched)
 template <typename T>
-int pcg_tri_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
-              size_t *iters_out, double *rr_out) {
+int pcg_launched_t(smh_crs *m, const Precond &pc, const SolveCall &c) {
     const int dt = sizeof(T) == 8 ? SMH_F64 : SMH_F32;
+    const size_t n = c.n;
     SolveRun run;
     const unsigned grid = pcg_grid(n);
     return run.run([&]() -> int {
@@ -334,26 +334,19 @@ int pcg_tri_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, d
         Scratch &ws = run.ws;
         T *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_ap = nullptr, *d_z = nullptr, *d_w = nullptr, *d_part = nullptr, *d_dot = nullptr;
         PcgScalars<T> *d_sc = nullptr;
-        unsigned long long *d_bad = nullptr;
         SMH_TRY(ws.alloc(&d_x, n)); SMH_TRY(ws.alloc(&d_r, n)); SMH_TRY(ws.alloc(&d_p, n));
         SMH_TRY(ws.alloc(&d_ap, n)); SMH_TRY(ws.alloc(&d_z, n)); SMH_TRY(ws.alloc(&d_w, n));
         SMH_TRY(ws.alloc(&d_part, (size_t)kPcgBlocks + 2 * (size_t)kReducePartials + 8));
         SMH_TRY(ws.alloc(&d_sc, 1));
-        SMH_TRY(ws.alloc(&d_bad, 1));
+        SMH_TRY(precond_setup(pc, n, d_w, ws, s));  // (a probed diagonal's values are read once, there: d_w is overwritten later)
         SMH_TRY(run.h_sc.alloc(sizeof(PcgScalars<T>), hipHostMallocDefault));
         T *part = d_part, *dot_scratch = d_part + kPcgBlocks;
-        const size_t n_dot = spmv_fused_dot_partials(m, n, variant);
+        const size_t n_dot = spmv_fused_dot_partials(m, n, c.variant);
         if (n_dot) SMH_TRY(ws.alloc(&d_dot, n_dot));
-        if (pc.gt) {  // (the handles are read on another stream than the ones that wrote them; nothing divides by their values)
-            SMH_HIP(hipStreamSynchronize(pc.f->stream));
-            SMH_HIP(hipStreamSynchronize(pc.gt->stream));
-        } else {  // the diagonal's values are read once, here (d_w takes them and is overwritten later)
-            SMH_TRY(probe_diagonal(pc.f, n, d_w, d_bad, pc.name, s));
-        }
         const uint32_t *active = &d_sc->active;
         // r = b - A x; z = M^-1 r; rr, rz; p = z
-        hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, tol, (uint64_t)iter_max);
-        SMH_TRY(stage_residual(m, variant, b_in, x_io, n, d_r, d_x, d_ap, s));
+        hipLaunchKernelGGL((k_pcg_init<T>), dim3(1), dim3(1), 0, s, d_sc, c.tol, (uint64_t)c.iter_max);
+        SMH_TRY(stage_residual(m, c.variant, (const T *)c.b, (const T *)c.x, n, d_r, d_x, d_ap, s));
         SMH_TRY(precond_apply_enqueue(pc, d_r, d_w, d_z, nullptr, s));
         hipLaunchKernelGGL((k_sgs_dot<T, true>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_r, (uint64_t)n, part);
         hipLaunchKernelGGL((k_sgs_fold<T, 0>), dim3(1), dim3(kBlock), 0, s, d_sc, part, grid);
@@ -364,7 +357,7 @@ int pcg_tri_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, d
         size_t spmv_nodes = 1;
         auto body = [&]() -> int {
             PapSource<T> pap;
-            SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, variant, s, d_dot));
+            SMH_TRY(spmv_enqueue(m, d_p, n, d_ap, c.variant, s, d_dot));
             SMH_TRY(pap_source(d_p, d_ap, n, d_dot, n_dot, dot_scratch, s, &pap));
             hipLaunchKernelGGL((k_pcg_alpha<T>), dim3(1), dim3(kBlock), 0, s, d_sc, pap.vals, pap.count);
             hipLaunchKernelGGL((k_sgs_update<T>), dim3(grid), dim3(kBlock), 0, s, d_sc, d_r, d_ap, d_p, d_x, (uint64_t)n, part);
@@ -378,46 +371,18 @@ int pcg_tri_t(smh_crs *m, const Precond &pc, const T *b_in, T *x_io, size_t n, d
         };
         // the node budget of a captured batch: the application's launches, the product (a few nodes at most) and the tail of 8
         bool capture = true;
-        const size_t bodies = bodies_within_budget(precond_apply_nodes(pc) + spmv_nodes + 3 + 8, check_every, &capture);
-        SMH_TRY(run.loop(dt, iter_max, bodies, body, d_sc, capture));
-        if (n) SMH_HIP(hipMemcpyAsync(x_io, d_x, n * sizeof(T), hipMemcpyDefault, s));
+        const size_t bodies = bodies_within_budget(precond_apply_nodes(pc) + spmv_nodes + 3 + 8, c.check_every, &capture);
+        SMH_TRY(run.loop(dt, c.iter_max, bodies, body, d_sc, capture));
+        if (n) SMH_HIP(hipMemcpyAsync(c.x, d_x, n * sizeof(T), hipMemcpyDefault, s));
         SMH_HIP(hipStreamSynchronize(s));
         return SMH_OK;
-    }, iters_out, rr_out);
+    }, c.iters_out, c.rr_out);
 }
 
-int pcg_tri(smh_crs *m, const Precond &pc, const void *b_in, void *x_io, size_t n, double tol, size_t iter_max, int variant, size_t check_every,
-            size_t *iters_out, double *rr_out) {
-    if (pc.f->orphans || (pc.gt && pc.gt->orphans)) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-    if (m->dtype == SMH_F64) return pcg_tri_t<double>(m, pc, (const double *)b_in, (double *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
-    return pcg_tri_t<float>(m, pc, (const float *)b_in, (float *)x_io, n, tol, iter_max, variant, check_every, iters_out, rr_out);
-}
-
-// z = M^-1 r by the handle's stream; r and z: n values each on the device, equal or disjoint
-int precond_apply(const Precond &pc, const smh_vec *r, smh_vec *z, const char *what) {
-    smh_crs *f = pc.f;
-    if (r->dtype != f->dtype || z->dtype != f->dtype) return fail(SMH_ERR_INVALID, "vector dtype differs from the matrix's");
-    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
-    if (f->n_rows != r->n || f->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
-    if (f->orphans || (pc.gt && pc.gt->orphans)) return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
-    if (pc.gt) {
-        SMH_TRY(ilu_check_pair(f, pc.gt, pc.name));
-        SMH_HIP(hipStreamSynchronize(pc.gt->stream));  // (gt is read on g's stream)
-    }
-    const size_t n = f->n_rows, bytes = n * dtype_size(f->dtype);
-    const char *pr = (const char *)r->d, *pz = (const char *)z->d;
-    if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "%s: r and z overlap in part", what);
-    SMH_TRY(precond_prepare(pc));
-    if (!pc.gt && f->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
-        return fail(SMH_ERR_INVALID, "%s: no diagonal entry stored in row %llu", pc.name, (unsigned long long)f->tri[SMH_TRI_LOWER].first_no_diag);
-    Scratch scr;
-    char *w = nullptr;
-    SMH_TRY(scr.alloc(&w, bytes));
-    const hipStream_t s = f->stream;
-    const int rc = precond_apply_enqueue(pc, r->d, w, z->d, nullptr, s);
-    if (rc != SMH_OK) return keep_error(rc, [&] { (void)hipStreamSynchronize(s); (void)hipGetLastError(); });
-    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
-    return SMH_OK;
+// the handles' check, then the driver of the matrix's dtype
+int pcg_launched(smh_crs *m, const Precond &pc, const SolveCall &c) {
+    SMH_TRY(precond_check_handles(pc));
+    return m->dtype == SMH_F64 ? pcg_launched_t<double>(m, pc, c) : pcg_launched_t<float>(m, pc, c);
 }
 
 }  // namespace
@@ -425,62 +390,59 @@ int precond_apply(const Precond &pc, const smh_vec *r, smh_vec *z, const char *w
 // The entry points: the statuses are decided here (check_solve_vec / check_solve_host, solver_host.hpp), before any launch.
 // check_every = 0, and the host forms, stand for 8 bodies per poll.
 constexpr size_t kPcgCheckEvery = 8;
-constexpr const char *kVecDtype = "vector dtype differs from the matrix's";
 
 extern "C" int smh_pcg_jacobi_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                                     size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false));
-    const size_t n = m->n_rows;
-    if (m->dtype == SMH_F64) return pcg_t<double>(m, (const double *)b_host, (double *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
-    return pcg_t<float>(m, (const float *)b_host, (float *)x_host_inout, n, tol, iter_max, variant, iters_out, rr_out);
+    const SolveCall c{b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out};
+    return m->dtype == SMH_F64 ? pcg_t<double>(m, c) : pcg_t<float>(m, c);
 }
 
 // ---- the symmetric Gauss-Seidel preconditioner and its CG -----------------------------------------------------------------------------
 extern "C" int smh_crs_sgs_apply_vec(smh_crs *m, const smh_vec *r, smh_vec *z) {
     if (!m || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
-    return precond_apply(sgs_precond(m), r, z, "sgs_apply");
+    return precond_apply_vec(sgs_precond(m), r, z, "sgs_apply");
 }
 
 extern "C" int smh_pcg_sgs_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                      size_t *iters_out, double *rr_out) {
     SMH_TRY(check_solve_vec(m, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery));
-    return pcg_tri(m, sgs_precond(m), b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return pcg_launched(m, sgs_precond(m), {b->d, x->d, m->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out});
 }
 
 extern "C" int smh_pcg_sgs_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                  int variant, size_t *iters_out, double *rr_out) {
     SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false));
-    return pcg_tri(m, sgs_precond(m), b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
+    return pcg_launched(m, sgs_precond(m), {b_host, x_host_inout, m->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out});
 }
 
 // ---- ILU(0): the same recurrence and application with the solves on a factor handle (smh_crs_ilu0, ilu.hip); the product and its
 // fused p.Ap come from a ----------------------------------------------------------------------------------------------------------
 extern "C" int smh_crs_ilu_apply_vec(smh_crs *f, const smh_vec *r, smh_vec *z) {
     if (!f || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
-    return precond_apply(ilu_precond(f), r, z, "ilu_apply");
+    return precond_apply_vec(ilu_precond(f), r, z, "ilu_apply");
 }
 
 extern "C" int smh_pcg_ilu_solve_vec(smh_crs *a, smh_crs *f, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant, size_t check_every,
                                      size_t *iters_out, double *rr_out) {
     if (!f) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery, f));
-    return pcg_tri(a, ilu_precond(f), b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+    return pcg_launched(a, ilu_precond(f), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out});
 }
 
 extern "C" int smh_pcg_ilu_solve(smh_crs *a, smh_crs *f, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t iter_max,
                                  int variant, size_t *iters_out, double *rr_out) {
     if (!f) return fail(SMH_ERR_INVALID, "NULL handle");
     SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false, f));
-    return pcg_tri(a, ilu_precond(f), b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
+    return pcg_launched(a, ilu_precond(f), {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out});
 }
 
 // ---- FSAI: the same recurrence with z = G^T (G r) by two products on the factor handles (smh_crs_fsai, fsai.hip), each through its
 // own AUTO kernel; variant is a's product's ----------------------------------------------------------------------------------------
-constexpr const char *kFsaiName = "FSAI preconditioner";
 
 extern "C" int smh_crs_fsai_apply_vec(smh_crs *g, smh_crs *gt, const smh_vec *r, smh_vec *z) {
     if (!g || !gt || !r || !z) return fail(SMH_ERR_INVALID, "NULL handle");
-    return precond_apply(fsai_precond(g, gt), r, z, "fsai_apply");
+    return precond_apply_vec(fsai_precond(g, gt), r, z, "fsai_apply");
 }
 
 // the name the documents of the non-symmetric pair (G_L, G_U) use: w = G_L r, z = G_U w
@@ -488,16 +450,12 @@ extern "C" int smh_crs_fsai_ns_apply_vec(smh_crs *gl, smh_crs *gu, const smh_vec
 
 extern "C" int smh_pcg_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
                                       size_t check_every, size_t *iters_out, double *rr_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_vec(a, b, x, kVecDtype, /*refuse_aliased*/ true, &check_every, kPcgCheckEvery, g, kFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kFsaiName));
-    return pcg_tri(a, fsai_precond(g, gt), b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out);
+    SMH_TRY(check_pair_vec(a, g, gt, kFsaiName, b, x, &check_every, kPcgCheckEvery));
+    return pcg_launched(a, fsai_precond(g, gt), {b->d, x->d, a->n_rows, tol, iter_max, variant, check_every, iters_out, rr_out});
 }
 
 extern "C" int smh_pcg_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
                                   size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
-    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
-    SMH_TRY(check_solve_host(a, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ true, /*refuse_aliased*/ false, g, kFsaiName));
-    SMH_TRY(ilu_check_pair(a, gt, kFsaiName));
-    return pcg_tri(a, fsai_precond(g, gt), b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out);
+    SMH_TRY(check_pair_host(a, g, gt, kFsaiName, b_host, b_len, x_host_inout, x_len, /*refuse_aliased*/ false));
+    return pcg_launched(a, fsai_precond(g, gt), {b_host, x_host_inout, a->n_rows, tol, iter_max, variant, kPcgCheckEvery, iters_out, rr_out});
 }

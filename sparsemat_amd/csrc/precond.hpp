@@ -1,11 +1,14 @@
-// precond.hpp -- what the preconditioned solvers share (pcg.hip: Jacobi-, SGS-, ILU- and FSAI-PCG; gmres.hip and bicgstab.hip: the right-preconditioned
-// GMRES and BiCGSTAB): what their entry points decide about `precond` and `f`, the probe of a handle's diagonal, the preconditioner applied by two triangular solves on one handle or by two products on two (Precond) and the
-// node budget of a captured batch that holds such applications.
+// precond.hpp -- the preconditioner object of the preconditioned solvers (pcg.hip: Jacobi-, SGS-, ILU- and FSAI-PCG; gmres.hip and bicgstab.hip: the
+// right-preconditioned GMRES and BiCGSTAB).  Precond says what M^-1 is -- nothing, a division by the diagonal, two triangular solves on one handle, two
+// products on two -- and everything that depends on that sits here: how a driver's template applies it (PrecondShape), the checks of its handles, its
+// set-up on the device, its application and the nodes that takes in a captured batch, whose budget is here too.
 #pragma once
 #include "internal.hpp"
+#include "solver_host.hpp"
 #include "solver_tree.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace smh {
 
@@ -49,36 +52,88 @@ int probe_diagonal(const smh_crs *h, size_t n, T *d, unsigned long long *d_bad, 
 
 // most nodes of a captured batch (a linear chain): beyond it the bodies per batch go down, and a single body beyond it runs
 // uncaptured.  How the bodies reach the device changes no bit.  SMH_SGS_GRAPH_NODES: tuning knob
-inline size_t sgs_graph_nodes() {
+inline size_t batch_node_budget() {
     if (const char *e = getenv("SMH_SGS_GRAPH_NODES")) return (size_t)strtoull(e, nullptr, 10);
     return 4096;
 }
 
-// A preconditioner applied by two sweeps over handles of the factor's kind, z = M^-1 r through n values of scratch w.
-// Two triangular solves on one handle (gt == nullptr), z = T_upper^-1 (scale(T_lower^-1 r)): SGS on the matrix itself, both
-// diagonals stored, the right-hand side of the upper solve scaled by the diagonal; ILU(0) on the factor handle (ilu.hip), the lower
-// solve with the unit diagonal, no scaling.  Two products on two handles (gt != nullptr), z = G^T (G r): FSAI (fsai.hip), each by the
-// handle's own AUTO kernel.
+// M^-1 by its kind, z = M^-1 r.
+// Diagonal: z_i = r_i / d_i, d_i the first stored (i, i) of the matrix f (Jacobi) -- a division inside the solver's own sweeps.
+// Solves: two triangular solves on the handle f through n values of scratch, z = T_upper^-1 (scale(T_lower^-1 r)): SGS on the
+// matrix itself, both diagonals stored, the right-hand side of the upper solve scaled by the diagonal; ILU(0) on the factor handle
+// (ilu.hip), the lower solve with the unit diagonal, no scaling.
+// Products: two products on two handles, z = gt (f r): FSAI's pair (fsai.hip), each by the handle's own AUTO kernel.
 struct Precond {
+    enum Kind { None, Diagonal, Solves, Products } kind;
+    const char *name;  // whose refusal a refusal is
     smh_crs *f;
-    int lower_diag;
-    bool scale_rhs;
-    const char *name;
-    smh_crs *gt = nullptr;
+    struct SolveForm {
+        int lower_diag;
+        bool scale_rhs;
+    };
+    union {  // by kind: Solves' form, Products' second handle
+        SolveForm solve;
+        smh_crs *gt;
+    };
 };
-inline Precond sgs_precond(smh_crs *m) { return {m, SMH_DIAG_NON_UNIT, true, "SGS preconditioner"}; }
-inline Precond ilu_precond(smh_crs *f) { return {f, SMH_DIAG_UNIT, false, "ILU preconditioner"}; }
-inline Precond fsai_precond(smh_crs *g, smh_crs *gt) { return {g, SMH_DIAG_NON_UNIT, false, "FSAI preconditioner", gt}; }
+constexpr const char *kFsaiName = "FSAI preconditioner";
+inline Precond no_precond() { return {Precond::None, "no preconditioner", nullptr, {}}; }
+inline Precond jacobi_precond(smh_crs *m) { return {Precond::Diagonal, "Jacobi preconditioner", m, {}}; }
+inline Precond sgs_precond(smh_crs *m) { return {Precond::Solves, "SGS preconditioner", m, {{SMH_DIAG_NON_UNIT, true}}}; }
+inline Precond ilu_precond(smh_crs *f) { return {Precond::Solves, "ILU preconditioner", f, {{SMH_DIAG_UNIT, false}}}; }
+inline Precond fsai_precond(smh_crs *g, smh_crs *gt) {
+    Precond pc{Precond::Products, kFsaiName, g, {}};
+    pc.gt = gt;
+    return pc;
+}
+// SMH_PRECOND_* on the matrix m and ILU's factor f (check_precond has passed)
+inline Precond precond_of(int precond, smh_crs *m, smh_crs *f) {
+    switch (precond) {
+    case SMH_PRECOND_JACOBI: return jacobi_precond(m);
+    case SMH_PRECOND_SGS: return sgs_precond(m);
+    case SMH_PRECOND_ILU: return ilu_precond(f);
+    default: return no_precond();
+    }
+}
+
+// How a driver's template applies M^-1: not at all, inside its own sweeps, or by launches of the preconditioner's own (solves
+// and products alike: a vector in, a vector out, n values of scratch)
+enum PrecondShape { kPcNone, kPcFused, kPcLaunched };
+inline PrecondShape precond_shape(const Precond &pc) {
+    return pc.kind == Precond::None ? kPcNone : pc.kind == Precond::Diagonal ? kPcFused : kPcLaunched;
+}
+
+// go(T(), shape) with T the type of dtype and shape an std::integral_constant of PrecondShape: where a driver template of both is
+// instantiated, all six from the one expression in go
+template <typename Go> int with_dtype_and_shape(int dtype, PrecondShape shape, Go &&go) {
+    auto typed = [&](auto t) -> int {
+        switch (shape) {
+        case kPcNone: return go(t, std::integral_constant<PrecondShape, kPcNone>());
+        case kPcFused: return go(t, std::integral_constant<PrecondShape, kPcFused>());
+        default: return go(t, std::integral_constant<PrecondShape, kPcLaunched>());
+        }
+    };
+    return dtype == SMH_F64 ? typed(double()) : typed(float());
+}
+
+// What a solver refuses of the preconditioner's handles after its entry point's argument checks: solves and products read the
+// stored entries, so an orphaned one (the first push of a replay) is refused
+inline int precond_check_handles(const Precond &pc) {
+    const bool reads = pc.kind == Precond::Solves || pc.kind == Precond::Products;
+    if (reads && (pc.f->orphans || (pc.kind == Precond::Products && pc.gt->orphans)))
+        return fail(SMH_ERR_INVALID, "%s: the handle holds an orphaned entry", pc.name);
+    return SMH_OK;
+}
 
 // z = M^-1 r on stream s (w: n values of scratch; z may be r; precond_prepare has run).  active gates the solves' launches; the
 // products run ungated, as the body's own does: past the stop they form the same z from the same r again
 inline int precond_apply_enqueue(const Precond &pc, const void *r, void *w, void *z, const uint32_t *active, hipStream_t s) {
-    if (pc.gt) {
+    if (pc.kind == Precond::Products) {
         SMH_TRY(spmv_enqueue(pc.f, r, pc.f->n_rows, w, SMH_SPMV_AUTO, s));
         return spmv_enqueue(pc.gt, w, pc.f->n_rows, z, SMH_SPMV_AUTO, s);
     }
-    SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.lower_diag, false, r, w, active, s));
-    return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.scale_rhs, w, z, active, s);
+    SMH_TRY(trisolve_enqueue(pc.f, SMH_TRI_LOWER, pc.solve.lower_diag, false, r, w, active, s));
+    return trisolve_enqueue(pc.f, SMH_TRI_UPPER, SMH_DIAG_NON_UNIT, pc.solve.scale_rhs, w, z, active, s);
 }
 
 // y = M x in storage order when *gate != 0, nothing at all otherwise: k_spmv_seq's operations (one lane per row, the product rounded,
@@ -115,7 +170,7 @@ inline int gated_seq_enqueue(const smh_crs *h, const void *x, void *y, const uin
 // z = M^-1 r when *gate != 0 and no work otherwise (w: n values of scratch; z may be r; gate: a device word).  The solves as above;
 // the pair by two gated storage-order products, w = G r and z = G^T w with SMH_SPMV_SEQ's bits -- not the handles' AUTO kernels
 inline int precond_apply_gated_enqueue(const Precond &pc, const void *r, void *w, void *z, const uint32_t *gate, hipStream_t s) {
-    if (!pc.gt) return precond_apply_enqueue(pc, r, w, z, gate, s);
+    if (pc.kind != Precond::Products) return precond_apply_enqueue(pc, r, w, z, gate, s);
     // SMH_FSAI_END_GATE=0 (tuning knob, for measuring what the gate saves): the handles' own ungated products instead -- AUTO's bits
     if (const char *e = getenv("SMH_FSAI_END_GATE")) {
         if (atoi(e) == 0) return precond_apply_enqueue(pc, r, w, z, gate, s);
@@ -126,23 +181,67 @@ inline int precond_apply_gated_enqueue(const Precond &pc, const void *r, void *w
 
 // the launches of one application (precond_prepare has run); a product: a few nodes at most
 inline size_t precond_apply_nodes(const Precond &pc) {
-    if (pc.gt) return 2 * 4;
+    if (pc.kind == Precond::Products) return 2 * 4;
     return pc.f->tri[SMH_TRI_LOWER].launches.size() + pc.f->tri[SMH_TRI_UPPER].launches.size();
 }
 
-// the checks of a preconditioner's handles that need the device: columns; the solves' schedules (a stored diagonal in every row is
-// the caller's to ask of them)
+// the checks of a preconditioner's handles that need the device, before a solve's first launch: columns; the solves' schedules (a
+// stored diagonal in every row is the caller's to ask of them).  None and Diagonal read no handle's columns: nothing
 inline int precond_prepare(const Precond &pc) {
+    if (pc.kind == Precond::None || pc.kind == Precond::Diagonal) return SMH_OK;
     SMH_TRY(columns_within_n_cols(pc.f, pc.name));
-    if (pc.gt) return columns_within_n_cols(pc.gt, pc.name);
+    if (pc.kind == Precond::Products) return columns_within_n_cols(pc.gt, pc.name);
     SMH_TRY(ensure_tri_schedule(pc.f, SMH_TRI_LOWER));
     return ensure_tri_schedule(pc.f, SMH_TRI_UPPER);
+}
+
+// What a solve does about its preconditioner on its own stream s after its allocations (ws: the run's) and before its first launch.
+// Diagonal: diag (n values) takes the matrix's diagonal and keeps it, a zero or absent entry is refused.  Solves: the same probe of
+// the handle the solves run on; the solves read the handle's values, so what diag (any n values of scratch) took is not kept.
+// Products: nothing divides by a factor's value, so nothing is probed; both handles' AUTO forms are built here, outside any capture,
+// and their streams drained (the handles are read on another stream than the ones that wrote them).
+template <typename T>
+int precond_setup(const Precond &pc, size_t n, T *diag, Scratch &ws, hipStream_t s) {
+    if (pc.kind == Precond::None) return SMH_OK;
+    unsigned long long *d_bad = nullptr;
+    SMH_TRY(ws.alloc(&d_bad, 1));
+    if (pc.kind != Precond::Products) return probe_diagonal(pc.f, n, diag, d_bad, pc.name, s);
+    SMH_TRY(smh_crs_prepare(pc.f, SMH_SPMV_AUTO));
+    return smh_crs_prepare(pc.gt, SMH_SPMV_AUTO);
+}
+
+// z = M^-1 r alone, by the handle's stream (smh_crs_{sgs,ilu,fsai}_apply_vec; what: the caller's name); r and z: n values each on
+// the device, equal or disjoint
+inline int precond_apply_vec(const Precond &pc, const smh_vec *r, smh_vec *z, const char *what) {
+    smh_crs *f = pc.f;
+    if (r->dtype != f->dtype || z->dtype != f->dtype) return fail(SMH_ERR_INVALID, "%s", kVecDtype);
+    if (f->n_rows != f->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (f->n_rows != r->n || f->n_rows != z->n) return fail(SMH_ERR_DIM_MISMATCH, "Matrix and vector size mismatch");
+    SMH_TRY(precond_check_handles(pc));
+    if (pc.kind == Precond::Products) {
+        SMH_TRY(ilu_check_pair(f, pc.gt, pc.name));
+        SMH_HIP(hipStreamSynchronize(pc.gt->stream));  // (gt is read on g's stream)
+    }
+    const size_t n = f->n_rows, bytes = n * dtype_size(f->dtype);
+    const char *pr = (const char *)r->d, *pz = (const char *)z->d;
+    if (pr != pz && pr < pz + bytes && pz < pr + bytes) return fail(SMH_ERR_INVALID, "%s: r and z overlap in part", what);
+    SMH_TRY(precond_prepare(pc));
+    if (pc.kind == Precond::Solves && f->tri[SMH_TRI_LOWER].first_no_diag != ~0ull)
+        return fail(SMH_ERR_INVALID, "%s: no diagonal entry stored in row %llu", pc.name, (unsigned long long)f->tri[SMH_TRI_LOWER].first_no_diag);
+    Scratch scr;
+    char *w = nullptr;
+    SMH_TRY(scr.alloc(&w, bytes));
+    const hipStream_t s = f->stream;
+    const int rc = precond_apply_enqueue(pc, r->d, w, z->d, nullptr, s);
+    if (rc != SMH_OK) return keep_error(rc, [&] { (void)hipStreamSynchronize(s); (void)hipGetLastError(); });
+    SMH_HIP(hipStreamSynchronize(s));  // (before the scratch goes back to the pool)
+    return SMH_OK;
 }
 
 // The bodies of a captured batch under the node budget, per_body nodes each: check_every, fewer when that many are beyond the
 // budget, one when a single body is (*capture: whether a batch is captured at all).
 inline size_t bodies_within_budget(size_t per_body, size_t check_every, bool *capture) {
-    const size_t budget = sgs_graph_nodes();
+    const size_t budget = batch_node_budget();
     size_t bodies = check_every;
     if (per_body * bodies > budget) bodies = budget / per_body ? budget / per_body : 1;
     *capture = per_body <= budget;

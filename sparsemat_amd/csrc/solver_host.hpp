@@ -7,6 +7,8 @@
 namespace smh {
 
 // ---- the argument checks of the entry points, decided before any launch -------------------------------------------------------------
+constexpr const char *kVecDtype = "vector dtype differs from the matrix's";  // (smh_cg_solve_vec and smh_cg_solve_many word it in their own ways)
+
 // what a matrix a and a factor f of it (ILU(0)'s, or one of FSAI's two: name) must agree in
 inline int ilu_check_pair(const smh_crs *a, const smh_crs *f, const char *name = "ILU preconditioner") {
     if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
@@ -54,6 +56,23 @@ inline int check_solve_host(const smh_crs *m, const void *b_host, size_t b_len, 
     return SMH_OK;
 }
 
+// A pair of factor handles in place of one (FSAI's g and gt: name): a NULL one first, as a NULL matrix; then the checks above with g
+// the factor; gt against m after everything else
+template <typename V>
+int check_pair_vec(const smh_crs *m, const smh_crs *g, const smh_crs *gt, const char *name, const V *b, const V *x, size_t *check_every,
+                   size_t default_check_every) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_vec(m, b, x, kVecDtype, /*refuse_aliased*/ true, check_every, default_check_every, g, name));
+    return ilu_check_pair(m, gt, name);
+}
+
+inline int check_pair_host(const smh_crs *m, const smh_crs *g, const smh_crs *gt, const char *name, const void *b_host, size_t b_len,
+                           const void *x_host, size_t x_len, bool refuse_aliased) {
+    if (!g || !gt) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host, x_len, /*null_vectors*/ true, refuse_aliased, g, name));
+    return ilu_check_pair(m, gt, name);
+}
+
 // GMRES's restart length, after the checks above: 0 stands for default_restart, anything above max_restart is refused
 inline int check_solve_restart(size_t *restart, size_t default_restart, size_t max_restart) {
     if (*restart == 0) *restart = default_restart;
@@ -62,6 +81,24 @@ inline int check_solve_restart(size_t *restart, size_t default_restart, size_t m
 }
 
 // ---- the skeleton of a solve --------------------------------------------------------------------------------------------------------
+// What a driver takes after the matrix and the preconditioner: an entry point fills it from its argument list, nobody else writes one
+// out.  b and x: n values each of the matrix's dtype, in host or device memory; x is the start and is written once, after the loop.
+// The out-parameters are optional and written when the solve succeeded.
+struct SolveCall {
+    const void *b;
+    void *x;
+    size_t n;
+    double tol;
+    size_t iter_max;
+    int variant;
+    size_t check_every;
+    size_t *iters_out;
+    double *rr_out;
+    int *breakdown_out = nullptr;  // BiCGSTAB and GMRES
+    size_t restart = 0;            // GMRES (check_solve_restart has passed)
+    size_t *cycles_out = nullptr;  // GMRES
+};
+
 // The stream a solve runs on -- the handle's (CG, the k-column CG) or one of its own, created on demand (the others) --, its device
 // workspaces, the pinned block that solve_in_batches polls through, and the scalar block as the last poll saw it.
 class SolveRun {

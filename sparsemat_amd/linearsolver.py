@@ -178,17 +178,45 @@ class FSAIConjugateGradient(_DeviceSolver):
         return self._solve(lib().smh_pcg_fsai_solve_vec, lib().smh_pcg_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h))
 
 
-def _fsai_pair(solver, mat, factor):
-    """The pair ``precond="fsai"`` applies: the one passed, or ``mat.fsai_ns()``'s, whose ``singular`` the solver keeps (None for a
-    passed pair)."""
-    solver.singular = None
-    if factor is None:
-        gl, gu, solver.singular = mat.fsai_ns()
-        factor = (gl, gu)
-    return factor
+class _RightPreconditioned(_DeviceSolver):
+    """What ``BiCGStab`` and ``GMRES`` share: ``precond``, and what a solve makes of it and of ``factor``."""
+
+    _entry = None  # the stem of the library's entry points: "smh_bicgstab", "smh_gmres"
+
+    def __init__(self, tol, iter_max, variant, check_every, precond):
+        super().__init__(tol, iter_max, variant, check_every)
+        if precond not in _lib.PRECOND_NAMES:
+            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
+        self.precond = precond
+        self.breakdown = None
+        self.factor = None
+        self.zero_pivot = None
+        self.singular = None
+
+    def _resolve(self, mat, factor):
+        """``(vec_fn, host_fn, handles)`` of a solve on ``mat``: the pair of entry points -- the plain one, ``_fsai_``'s or
+        ``_precond_``'s -- and what they take after the matrix.  Without a factor "ilu" factors ``mat`` through ``ilu0`` and "fsai"
+        through ``fsai_ns``; ``factor``, ``zero_pivot`` and ``singular`` are set as the classes' docstrings say."""
+        def entry(kind):
+            return getattr(lib(), "%s_%ssolve_vec" % (self._entry, kind)), getattr(lib(), "%s_%ssolve" % (self._entry, kind))
+
+        if self.precond is None and factor is None:
+            return entry("") + ((),)
+        if self.precond == "fsai":
+            self.singular = None
+            if factor is None:
+                gl, gu, self.singular = mat.fsai_ns()
+                factor = (gl, gu)
+            self.factor = factor
+            return entry("fsai_") + ((factor[0]._h, factor[1]._h),)
+        self.zero_pivot = None
+        if self.precond == "ilu" and factor is None:
+            factor, self.zero_pivot = mat.ilu0()
+        self.factor = factor
+        return entry("precond_") + ((_lib.PRECONDS[self.precond], factor._h if factor is not None else None),)
 
 
-class BiCGStab(_DeviceSolver):
+class BiCGStab(_RightPreconditioned):
     """BiCGSTAB (van der Vorst, unpreconditioned) for non-symmetric systems -- an EXTENSION (the reference's only solver is the
     conjugate gradient): device-resident like ``ConjugateGradient``, the same guards, panics and stop rule
     (``sqrt(f64(r.r)) < tol`` after the update of r, and on ``s.s`` at the half step), ``smh_bicgstab_solve*``.
@@ -210,41 +238,25 @@ class BiCGStab(_DeviceSolver):
     ordering.  Without a factor ``solve`` factors ``mat`` through ``fsai_ns`` (afterwards ``factor`` holds the pair used and
     ``singular`` what the factorization reported, None for a passed pair)."""
 
+    _entry = "smh_bicgstab"
+
     def __init__(self, tol=1e-12, iter_max=10_000, variant="auto", check_every=0, precond=None):
-        super().__init__(tol, iter_max, variant, check_every)
-        if precond not in _lib.PRECOND_NAMES:
-            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
-        self.precond = precond
-        self.breakdown = None
+        super().__init__(tol, iter_max, variant, check_every, precond)
         self.converged = None
-        self.factor = None
-        self.zero_pivot = None
-        self.singular = None
 
     def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
         SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
         brk = C.c_int()
-        if self.precond is None and factor is None:
-            self._solve(lib().smh_bicgstab_solve_vec, lib().smh_bicgstab_solve, mat, b, x, extra_out=(brk,))
-        elif self.precond == "fsai":
-            self.factor = factor = _fsai_pair(self, mat, factor)
-            self._solve(lib().smh_bicgstab_fsai_solve_vec, lib().smh_bicgstab_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h),
-                        extra_out=(brk,))
-        else:
-            self.zero_pivot = None
-            if self.precond == "ilu" and factor is None:
-                factor, self.zero_pivot = mat.ilu0()
-            self.factor = factor
-            self._solve(lib().smh_bicgstab_precond_solve_vec, lib().smh_bicgstab_precond_solve, mat, b, x,
-                        handles=(_lib.PRECONDS[self.precond], factor._h if factor is not None else None), extra_out=(brk,))
+        vec_fn, host_fn, handles = self._resolve(mat, factor)
+        self._solve(vec_fn, host_fn, mat, b, x, handles=handles, extra_out=(brk,))
         self.breakdown = brk.value
         # every entered body that ends without a breakdown has tested the r.r it reports: under tol means that test stopped the loop
         self.converged = self.breakdown == 0 and self.iterations > 0 and math.sqrt(self.r_norm_squared) < self.tol
         return x
 
 
-class GMRES(_DeviceSolver):
+class GMRES(_RightPreconditioned):
     """Restarted GMRES(m) (Saad & Schultz, unpreconditioned) for non-symmetric systems -- an EXTENSION, the robust companion of
     ``BiCGStab``: it cannot break down before the Krylov space is exhausted and does not stagnate on a spectrum near the
     imaginary axis; a body is one product and sweeps over a device-resident basis of up to ``restart`` + 1 vectors
@@ -270,35 +282,18 @@ class GMRES(_DeviceSolver):
     ``solve`` factors ``mat`` through ``fsai_ns`` (afterwards ``factor`` holds the pair used and ``singular`` what the factorization
     reported, None for a passed pair)."""
 
+    _entry = "smh_gmres"
+
     def __init__(self, tol=1e-12, iter_max=10_000, restart=30, variant="auto", check_every=0, precond=None):
-        super().__init__(tol, iter_max, variant, check_every)
-        if precond not in _lib.PRECOND_NAMES:
-            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
+        super().__init__(tol, iter_max, variant, check_every, precond)
         self.restart = int(restart)
-        self.precond = precond
         self.cycles = None
-        self.breakdown = None
-        self.factor = None
-        self.zero_pivot = None
-        self.singular = None
 
     def solve(self, mat, b, x, factor=None):
         """x is updated in place: two ``DenseVec``s, or an array-like b with a contiguous numpy x of the matrix dtype.  Raises
         SparseMatPanic("Matrix is not symmetric") for a matrix that is not square / ("Matrix and vector size mismatch")."""
         cycles, brk = C.c_size_t(), C.c_int()
-        if self.precond is None and factor is None:
-            self._solve(lib().smh_gmres_solve_vec, lib().smh_gmres_solve, mat, b, x, extra_out=(cycles, brk), extra_in=(self.restart,))
-        elif self.precond == "fsai":
-            self.factor = factor = _fsai_pair(self, mat, factor)
-            self._solve(lib().smh_gmres_fsai_solve_vec, lib().smh_gmres_fsai_solve, mat, b, x, handles=(factor[0]._h, factor[1]._h),
-                        extra_out=(cycles, brk), extra_in=(self.restart,))
-        else:
-            self.zero_pivot = None
-            if self.precond == "ilu" and factor is None:
-                factor, self.zero_pivot = mat.ilu0()
-            self.factor = factor
-            self._solve(lib().smh_gmres_precond_solve_vec, lib().smh_gmres_precond_solve, mat, b, x,
-                        handles=(_lib.PRECONDS[self.precond], factor._h if factor is not None else None), extra_out=(cycles, brk),
-                        extra_in=(self.restart,))
+        vec_fn, host_fn, handles = self._resolve(mat, factor)
+        self._solve(vec_fn, host_fn, mat, b, x, handles=handles, extra_out=(cycles, brk), extra_in=(self.restart,))
         self.cycles, self.breakdown = cycles.value, brk.value
         return x

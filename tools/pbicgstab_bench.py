@@ -17,7 +17,7 @@ At fixed work (tol 0; the difference quotient of solves of --bodies and 3 x --bo
 unpreconditioned body through smh_bicgstab_solve_vec, the same body through smh_bicgstab_precond_solve_vec's SMH_PRECOND_NONE, and the
 Jacobi body, next to the byte model's ratio: a body moves two products + 18 n values unpreconditioned and two products + 23 n with
 Jacobi.  The first figure is the one to hold beside tools/bicgstab_bench.py run on the parent commit in the same
-session: the kBiNone instantiation must cost nothing."""
+session: the unpreconditioned (kPcNone) instantiation must cost nothing."""
 import argparse
 import ctypes as C
 import os

@@ -30,6 +30,7 @@ def main():
     n = g ** 3
     a = synth.crs_laplace3d(g, g, g, np.float32)
     f, _ = a.ilu0()
+    fsai = a.fsai()[:2]   # (g, gt)
     bh, xh = np.ones(n, np.float32), np.zeros(n, np.float32)
     b, xd = sm.DenseVec.from_vec(bh), sm.DenseVec.zeros(n, np.float32)
     cases = [("cg_vec", lambda: sm.ConjugateGradient(0.0, it).solve(a, b, xd)),
@@ -37,7 +38,12 @@ def main():
              ("jacobi_host", lambda: sm.JacobiConjugateGradient(0.0, it).solve(a, bh, xh)),
              ("sgs_vec", lambda: sm.SGSConjugateGradient(0.0, it).solve(a, b, xd)),
              ("ilu_vec", lambda: sm.ILUConjugateGradient(0.0, it).solve(a, b, xd, factor=f)),
-             ("bicgstab_vec", lambda: sm.BiCGStab(0.0, it).solve(a, b, xd))]
+             ("bicgstab_vec", lambda: sm.BiCGStab(0.0, it).solve(a, b, xd)),
+             ("gmres_vec", lambda: sm.GMRES(0.0, it).solve(a, b, xd)),
+             ("fsai_pcg_vec", lambda: sm.FSAIConjugateGradient(0.0, it).solve(a, b, xd, factor=fsai))]
+    for kind, factor in (("sgs", None), ("ilu", f), ("fsai", fsai)):   # (the factors are built once, above)
+        cases.append(("gmres_" + kind, lambda kind=kind, factor=factor: sm.GMRES(0.0, it, precond=kind).solve(a, b, xd, factor=factor)))
+        cases.append(("bicgstab_" + kind, lambda kind=kind, factor=factor: sm.BiCGStab(0.0, it, precond=kind).solve(a, b, xd, factor=factor)))
     for name, fn in cases:
         for _ in range(args.warmup):
             fn()
