@@ -568,7 +568,14 @@ int smh_vec_copy(smh_vec *dst, const smh_vec *src);                            /
 int smh_vec_permute(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse);
 int smh_vec_permute_dev(smh_vec *dst, const smh_vec *src, const uint32_t *perm_dev, size_t n_perm, int inverse);
 /* Vector::add / sub / scale (densevec.rs:51-58, :60-67, :69-73; += -= *= sugar :76-96):
- * x += y, x -= y over the first y.dim() entries; SMH_ERR_DIM_MISMATCH iff x.dim() < y.dim() */
+ * x += y, x -= y over the first y.dim() entries; SMH_ERR_DIM_MISMATCH iff x.dim() < y.dim().
+ * ALIASING (handles made by smh_vec_wrap_dev can share storage; add, sub, axpy, xpby and the two element-wise smh_blas_*_dev
+ * below alike): over the y.dim() entries an operation touches, the operand that is written and the one that is read are the SAME
+ * storage (same device pointer: x.add(x) doubles x) or DISJOINT.  Byte ranges that overlap in part are refused with
+ * SMH_ERR_INVALID ("... x and y overlap in part") before anything is launched, both buffers untouched: every thread writes its own
+ * x[i] after reading y[i] and would read what another thread writes.  Entries of x behind y.dim() are neither read nor written
+ * and do not count.  The operations that only read -- smh_vec_dot, smh_vec_norm_squared, smh_vec_norm, smh_blas_dot_dev -- take
+ * any overlap. */
 int smh_vec_add(smh_vec *x, const smh_vec *y);
 int smh_vec_sub(smh_vec *x, const smh_vec *y);
 int smh_vec_scale(smh_vec *x, double a);
@@ -584,7 +591,9 @@ int smh_vec_norm(const smh_vec *x, double *out); /* vector.rs:61-63 */
 /* The same kernels on raw device pointers with DEVICE-resident scalars, asynchronous on `stream`:
  * the building blocks of the row-partitioned CG, whose scalars are all-reduced on the device.
  * dot: *result_dev = x.y (type T; scratch_dev needs smh_blas_dot_scratch_bytes()).
- * axpy: y += round(*a_dev * x) (linearsolver.rs:47,49).  xpby: p = round(*b_dev * p) + r (:58-59). */
+ * axpy: y += round(*a_dev * x) (linearsolver.rs:47,49).  xpby: p = round(*b_dev * p) + r (:58-59).
+ * SMH_ERR_INVALID: a dtype that is not SMH_F32 / SMH_F64, a NULL pointer (x, y only when n > 0), and for axpy / xpby two buffers
+ * whose n entries overlap in part (the aliasing rule above: the same pointer or disjoint). */
 int smh_blas_dot_dev(smh_dtype dtype, const void *x_dev, const void *y_dev, size_t n, void *result_dev,
                      void *scratch_dev, void *stream);
 size_t smh_blas_dot_scratch_bytes(void);

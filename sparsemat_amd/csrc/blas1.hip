@@ -10,7 +10,11 @@
 // Stage 1: <= kReducePartials blocks, per-thread strided partials in T, 64-lane __shfl_down
 // butterfly, LDS across the 4 waves, one partial per block.  Stage 2: one block folds the
 // partials in index order.  (The reference folds left to right in T; a tree in T is at least as
-// accurate, and parity is a tolerance on |sum| scaled by sum|x_i y_i| -- see tests.)
+// accurate, and parity is a tolerance on |sum| scaled by sum|x_i y_i| -- see tests.  The tree's own bits are pinned to a
+// CPU model of it, tests/blas1_model.py, through every public entry point: tests/test_blas1_bits_gpu.py.)
+//
+// Aliasing: a thread of k_ew reads y[i] and writes x[i], nothing else -- x and y are the same array or disjoint over the n
+// entries of a launch.  The entry points refuse two ranges that overlap in part (ew_check_overlap, capi.hip).
 #include "internal.hpp"
 
 namespace smh {

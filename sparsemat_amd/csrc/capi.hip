@@ -212,6 +212,16 @@ static int vec_check_pair(const smh_vec *x, const smh_vec *y) {
     return SMH_OK;
 }
 
+// The element-wise kernels (k_ew, blas1.hip) read y[i] and write x[i] in the same thread and know nothing about any other thread's
+// entries: over the n entries they touch, x and y are the same array or disjoint.  Two ranges that overlap IN PART would make thread i
+// read what thread i +- k writes -- a result that depends on scheduling -- so they are refused before anything is launched.
+static int ew_check_overlap(const void *x, const void *y, size_t n, int dtype, const char *what) {
+    const size_t bytes = n * dtype_size(dtype);
+    const char *px = (const char *)x, *py = (const char *)y;
+    if (px != py && px < py + bytes && py < px + bytes) return fail(SMH_ERR_INVALID, "%s: x and y overlap in part", what);
+    return SMH_OK;
+}
+
 // scratch for reductions of the vector API: per thread, per device
 struct ReduceBuffer { void *d = nullptr; int device = -1; };
 static thread_local ReduceBuffer g_red;
@@ -1490,19 +1500,20 @@ int smh_vec_copy(smh_vec *dst, const smh_vec *src) {
     return SMH_OK;
 }
 
-static int vec_ew(Ew op, smh_vec *x, const smh_vec *y, double a) {
+static int vec_ew(Ew op, smh_vec *x, const smh_vec *y, double a, const char *what) {
     SMH_TRY(vec_check_pair(x, y));
     // densevec.rs:52-54 / :61-63: panic iff self.dim() < rhs.dim(); zip() covers rhs.dim() entries
     if (x->n < y->n) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    SMH_TRY(ew_check_overlap(x->d, y->d, y->n, x->dtype, what));  // (the same storage, x.add(x), is legal: every thread its own entry)
     SMH_TRY(launch_ew(x->dtype, op, x->d, y->d, y->n, a, nullptr, nullptr));
     SMH_HIP(hipStreamSynchronize(nullptr));
     return SMH_OK;
 }
 
-int smh_vec_add(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Add, x, y, 0.0); }
-int smh_vec_sub(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Sub, x, y, 0.0); }
-int smh_vec_axpy(smh_vec *y, double a, const smh_vec *x) { return vec_ew(Ew::Axpy, y, x, a); }
-int smh_vec_xpby(smh_vec *p, double b, const smh_vec *r) { return vec_ew(Ew::Xpby, p, r, b); }
+int smh_vec_add(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Add, x, y, 0.0, "smh_vec_add"); }
+int smh_vec_sub(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Sub, x, y, 0.0, "smh_vec_sub"); }
+int smh_vec_axpy(smh_vec *y, double a, const smh_vec *x) { return vec_ew(Ew::Axpy, y, x, a, "smh_vec_axpy"); }
+int smh_vec_xpby(smh_vec *p, double b, const smh_vec *r) { return vec_ew(Ew::Xpby, p, r, b, "smh_vec_xpby"); }
 
 int smh_vec_scale(smh_vec *x, double a) {
     if (!x) return fail(SMH_ERR_INVALID, "NULL vector handle");
@@ -1625,12 +1636,14 @@ size_t smh_blas_dot_scratch_bytes(void) { return (size_t)(kReducePartials + 8) *
 int smh_blas_axpy_dev(smh_dtype dtype, void *y_dev, const void *a_dev, const void *x_dev, size_t n, void *stream) {
     if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
     if (!a_dev || (n && (!x_dev || !y_dev))) return fail(SMH_ERR_INVALID, "NULL device pointer");
+    SMH_TRY(ew_check_overlap(y_dev, x_dev, n, dtype, "smh_blas_axpy_dev"));
     return launch_ew(dtype, Ew::Axpy, y_dev, x_dev, n, 0.0, a_dev, (hipStream_t)stream);
 }
 
 int smh_blas_xpby_dev(smh_dtype dtype, void *p_dev, const void *b_dev, const void *r_dev, size_t n, void *stream) {
     if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
     if (!b_dev || (n && (!p_dev || !r_dev))) return fail(SMH_ERR_INVALID, "NULL device pointer");
+    SMH_TRY(ew_check_overlap(p_dev, r_dev, n, dtype, "smh_blas_xpby_dev"));
     return launch_ew(dtype, Ew::Xpby, p_dev, r_dev, n, 0.0, b_dev, (hipStream_t)stream);
 }
 
