@@ -100,6 +100,13 @@ class DenseVec {
     friend DenseVec operator*(DenseVec l, T a) { l *= a; return l; }
     friend T operator*(const DenseVec &l, const DenseVec &r) { return l.inner_prod(r); }
 
+    // an extension (smh_vec_cast): a new vector of U, converted on the device -- f64 -> f32 to nearest even, f32 -> f64 exactly
+    template <typename U> DenseVec<U> cast() const {
+        DenseVec<U> r(dim());
+        detail::check(smh_vec_cast(h_, r.handle()));
+        return r;
+    }
+
     smh_vec *handle() const { return h_; }
 
   private:
@@ -412,6 +419,14 @@ class SparseMatCRS {
         detail::check(smh_crs_clone(h_, &c.h_));
         return c;
     }
+    // an extension (smh_crs_cast): a new matrix of U with this one's dims, pattern, orphan and kernel settings, the values converted
+    // on the device -- f64 -> f32 to nearest even, f32 -> f64 exactly; U == T is clone().  overflow (optional): the finite values
+    // that became infinite
+    template <typename U> SparseMatCRS<U> cast(size_t *overflow = nullptr) const {
+        SparseMatCRS<U> c;
+        detail::check(smh_crs_cast(h_, detail::dtype_of<U>::value, &c.h_, overflow));
+        return c;
+    }
     // SparseMatrix::add / sub (sparsematrix.rs:123-143), in place: `*get_mut(i, j) += val` (-=) for every entry of rhs in
     // storage order -- new columns pushed to the start of their row, folds into the first occurrence, bit for bit.  rhs may
     // be *this.  The operators of sparsemat_ops! (:370-433): +=, -=, *= T, and +, -, * T on a clone.
@@ -513,6 +528,7 @@ class SparseMatCRS {
 
   private:
     template <typename U> friend class SparseMatIndexList;
+    template <typename U> friend class SparseMatCRS;  // (cast<U>() fills the other type's handle)
     SparseMatCRS() = default;
     // a row or column index of Index = u32: larger ones are refused, never truncated
     static uint32_t index(size_t i) {
@@ -934,6 +950,70 @@ class GMRES {
     double r_norm_squared_ = 0.0;
     size_t cycles_ = 0;
     int breakdown_ = 0;
+};
+
+// Mixed-precision iterative refinement -- an extension, not in the reference (smh_refine_solve*): an f64-accurate x of A x = b whose
+// bodies run in f32.  Each outer step forms r = b - A x in f64, scales it by a power of two, converts it to f32, solves
+// A_lo d = r_lo from d = 0 with the inner solver (SMH_INNER_CG, _BICGSTAB or _GMRES, preconditioned by SMH_PRECOND_NONE, _JACOBI -- not
+// with CG --, _SGS, _ILU or _FSAI) to inner_tol, and adds d to x in f64.  code(): 0 sqrt(r.r) < tol, 1 outer_max steps taken, 2 a
+// step did not lower r.r (it is undone).  The forms without mat_lo cast mat themselves; those without factors factor mat_lo through
+// ilu0(), and through fsai() (CG) or fsai_ns().
+class IterativeRefinement {
+  public:
+    IterativeRefinement() = default;
+    IterativeRefinement(double tol, size_t outer_max = 20, int inner = SMH_INNER_CG, int precond = SMH_PRECOND_NONE, double inner_tol = 1e-4,
+                        size_t inner_iter_max = 10000, size_t restart = 30)
+        : tol_(tol), outer_max_(outer_max), inner_(inner), precond_(precond), inner_tol_(inner_tol), inner_iter_max_(inner_iter_max), restart_(restart) {}
+    // with the f32 matrix and its f32 factors (nullptr where the kind takes none)
+    void solve(const SparseMatCRS<double> &mat, const SparseMatCRS<float> &mat_lo, const SparseMatCRS<float> *f, const SparseMatCRS<float> *f2,
+               const DenseVec<double> &b, DenseVec<double> &x) {
+        detail::check(smh_refine_solve_vec(mat.handle(), mat_lo.handle(), inner_, precond_, f ? f->handle() : nullptr, f2 ? f2->handle() : nullptr, b.handle(),
+                                           x.handle(), tol_, outer_max_, inner_tol_, inner_iter_max_, restart_, SMH_SPMV_AUTO, SMH_SPMV_AUTO, 0, &outer_iterations_,
+                                           &iterations_, &r_norm_squared_, &code_));
+    }
+    // host vectors, x updated in place
+    void solve(const SparseMatCRS<double> &mat, const SparseMatCRS<float> &mat_lo, const SparseMatCRS<float> *f, const SparseMatCRS<float> *f2,
+               const std::vector<double> &b, std::vector<double> &x) {
+        detail::check(smh_refine_solve(mat.handle(), mat_lo.handle(), inner_, precond_, f ? f->handle() : nullptr, f2 ? f2->handle() : nullptr, b.data(), b.size(),
+                                       x.data(), x.size(), tol_, outer_max_, inner_tol_, inner_iter_max_, restart_, SMH_SPMV_AUTO, SMH_SPMV_AUTO, 0,
+                                       &outer_iterations_, &iterations_, &r_norm_squared_, &code_));
+    }
+    // ... factoring mat_lo first
+    template <typename V>
+    void solve(const SparseMatCRS<double> &mat, const SparseMatCRS<float> &mat_lo, const V &b, V &x) {
+        if (precond_ == SMH_PRECOND_ILU) {
+            const SparseMatCRS<float> f = mat_lo.ilu0();
+            return solve(mat, mat_lo, &f, nullptr, b, x);
+        }
+        if (precond_ == SMH_PRECOND_FSAI) {
+            const auto f = inner_ == SMH_INNER_CG ? mat_lo.fsai() : mat_lo.fsai_ns();
+            return solve(mat, mat_lo, &f.first, &f.second, b, x);
+        }
+        solve(mat, mat_lo, nullptr, nullptr, b, x);
+    }
+    // ... casting mat first
+    template <typename V>
+    void solve(const SparseMatCRS<double> &mat, const V &b, V &x) {
+        const SparseMatCRS<float> mat_lo = mat.template cast<float>();
+        solve(mat, mat_lo, b, x);
+    }
+    size_t outer_iterations() const { return outer_iterations_; }
+    size_t iterations() const { return iterations_; }  // the inner solves' bodies in total
+    double r_norm_squared() const { return r_norm_squared_; }
+    int code() const { return code_; }
+
+  private:
+    double tol_ = 1e-12;
+    size_t outer_max_ = 20;
+    int inner_ = SMH_INNER_CG;
+    int precond_ = SMH_PRECOND_NONE;
+    double inner_tol_ = 1e-4;
+    size_t inner_iter_max_ = 10000;
+    size_t restart_ = 30;
+    size_t outer_iterations_ = 0;
+    size_t iterations_ = 0;
+    double r_norm_squared_ = 0.0;
+    int code_ = 0;
 };
 
 }  // namespace sparsemat

@@ -48,7 +48,7 @@ extern "C" {
  * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
  * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec; smh_crs_fsai, smh_crs_fsai_apply_vec,
  * smh_pcg_fsai_solve, smh_pcg_fsai_solve_vec; smh_crs_fsai_ns, smh_crs_fsai_ns_apply_vec, smh_gmres_fsai_solve, smh_gmres_fsai_solve_vec,
- * smh_bicgstab_fsai_solve, smh_bicgstab_fsai_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_bicgstab_fsai_solve, smh_bicgstab_fsai_solve_vec; smh_crs_cast, smh_vec_cast, smh_refine_solve, smh_refine_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -968,6 +968,67 @@ int smh_bicgstab_fsai_solve(smh_crs *a, smh_crs *g, smh_crs *gt, const void *b_h
                             double tol, size_t iter_max, int variant, size_t *iters_out, double *rr_out, int *breakdown_out);
 int smh_bicgstab_fsai_solve_vec(smh_crs *a, smh_crs *g, smh_crs *gt, const smh_vec *b, smh_vec *x, double tol, size_t iter_max,
                                 int variant, size_t check_every, size_t *iters_out, double *rr_out, int *breakdown_out);
+
+/* ---- mixed precision -- EXTENSIONS (the reference has one precision; csrc/refine.hip) ----
+ * smh_crs_cast: *out is a new library-owned handle with a's dims, offsets, columns, orphan and smh_crs_set_* settings, as
+ * smh_crs_clone copies them, and a's values converted on the device to `dtype`: f64 -> f32 rounds to nearest even and finite values
+ * beyond f32's range become +-Inf; f32 -> f64 is exact; NaN stays NaN, a zero keeps its sign, results that are f32 subnormals are
+ * kept.  dtype == a's: smh_crs_clone's result.  overflow_out (optional): the finite values that became infinite.  Derived forms are
+ * rebuilt lazily on the new handle.  Not under a stream capture.  SMH_ERR_INVALID for a NULL a or out, or an unknown dtype.
+ * smh_vec_cast: dst[i] = convert(src[i]) by the same rule.  SMH_ERR_INVALID for a NULL handle, SMH_ERR_DIM_MISMATCH when the dims
+ * differ; with equal dtypes it is smh_vec_copy(dst, src); with different dtypes, vectors that share storage are SMH_ERR_INVALID. */
+int smh_crs_cast(const smh_crs *a, smh_dtype dtype, smh_crs **out, size_t *overflow_out);
+int smh_vec_cast(const smh_vec *src, smh_vec *dst);
+
+/* Mixed-precision iterative refinement: an f64-accurate x of A x = b with the bodies run by the f32 solvers.  a is the f64 handle, b
+ * and x are f64; a_lo is an f32 handle of a's dimension on a's device -- normally smh_crs_cast(a, SMH_F32); what its values are is the
+ * caller's business, as with factor handles --, f_lo and f2_lo are f32 factors OF a_lo.  Each operation is rounded once, nothing is
+ * contracted:
+ *   set-up:  r = b - A x        (A x: a's product through `variant`; one subtraction per element)
+ *            rr = r.r           (f64: products rounded, then the fused solvers' tree on their grid; tests/refine_model.py)
+ *            outer = 0;  inner_iters = 0
+ *   loop:    rr == 0 or sqrt(rr) < tol:  code 0 (converged), stop
+ *            outer == outer_max:         code 1, stop
+ *            e = floor(ilogb(rr) / 2)    (on the host, from the polled rr; |r 2^-e|^2 is in [1, 4); a non-finite rr takes e = 0)
+ *            r_lo[i] = (float)(r[i] * 2^-e)          (the product is exact: one rounding, the conversion)
+ *            d_lo = 0;  the inner solver on a_lo d_lo = r_lo with tolerance inner_tol, inner_iter_max, restart, variant_lo, check_every
+ *            inner_iters += its bodies;  outer += 1
+ *            x_prev = x;  x[i] = x[i] + (double)d_lo[i] * 2^e    (the product is exact: one rounding, the addition)
+ *            r = b - A x;  rr' = r.r
+ *            not (rr' < rr):  x = x_prev;  code 2 (stalled; covers NaN), stop with the old rr
+ *            rr = rr'
+ * The inner solvers' stop rule is absolute, sqrt(rr) < tol: on the normalised residual inner_tol is a relative reduction between
+ * inner_tol / 2 and inner_tol, and r_lo . r_lo stays away from f32 underflow.  An inner breakdown is not an error: its d_lo is used
+ * and the outer test decides.  One 8-byte poll per outer step is the only host round trip of the outer loop.  Not under a stream
+ * capture.  0 stands for the default in outer_max (20), inner_tol (1e-4), inner_iter_max (10000) and restart (30).
+ * The inner solve goes through the existing entry points, bit for bit:
+ *   inner \ precond   NONE                 JACOBI    SGS                    ILU (f_lo)             FSAI (f_lo, f2_lo)
+ *   SMH_INNER_CG      smh_cg_solve_vec     refused   smh_pcg_sgs_solve_vec  smh_pcg_ilu_solve_vec  smh_pcg_fsai_solve_vec
+ *   _BICGSTAB         smh_bicgstab_precond_solve_vec (NONE forwards) ............................  smh_bicgstab_fsai_solve_vec
+ *   _GMRES            smh_gmres_precond_solve_vec ...............................................  smh_gmres_fsai_solve_vec
+ * SMH_PRECOND_FSAI is a kind of these two entry points only: f_lo = G or G_L, f2_lo = G^T or G_U.  CG with SMH_PRECOND_JACOBI is
+ * SMH_ERR_INVALID: the Jacobi-preconditioned CG has no device-vector form.
+ * Outputs (optional): outer steps, the inner solves' bodies in total, the last accepted r.r, the code.
+ * Statuses, decided before any launch, x left untouched, in this order: SMH_ERR_INVALID for a NULL a, a_lo, b or x; a not f64 or
+ * a_lo not f32; a vector that is not f64; b and x in one storage; an unknown inner or precond (and CG with Jacobi); a factor given
+ * where the kind takes none or missing where it takes one; then a_lo's dims (SMH_ERR_DIM_MISMATCH) or device (SMH_ERR_INVALID)
+ * differing from a's; SMH_ERR_NOT_SQUARE; the vectors' dims (SMH_ERR_DIM_MISMATCH); restart > 128 (SMH_ERR_INVALID).  Whatever the
+ * inner entry point refuses about a_lo and the factors comes back from the first outer step with its own code and message, x still
+ * untouched.  Memory: three f64 and two f32 vectors of n beside the inner solver's own.
+ * smh_refine_solve: the same on host arrays of b_len / x_len f64 values (x: in x0, out the result; a NULL array of a non-zero length
+ * and b_host == x_host_inout are SMH_ERR_INVALID). */
+#define SMH_INNER_CG 0
+#define SMH_INNER_BICGSTAB 1
+#define SMH_INNER_GMRES 2
+#define SMH_PRECOND_FSAI 4 /* smh_refine_solve* only */
+int smh_refine_solve_vec(smh_crs *a, smh_crs *a_lo, int inner, int precond, smh_crs *f_lo, smh_crs *f2_lo, const smh_vec *b,
+                         smh_vec *x, double tol, size_t outer_max, double inner_tol, size_t inner_iter_max, size_t restart,
+                         int variant, int variant_lo, size_t check_every,
+                         size_t *outer_out, size_t *inner_iters_out, double *rr_out, int *code_out);
+int smh_refine_solve(smh_crs *a, smh_crs *a_lo, int inner, int precond, smh_crs *f_lo, smh_crs *f2_lo, const void *b_host,
+                     size_t b_len, void *x_host_inout, size_t x_len, double tol, size_t outer_max, double inner_tol,
+                     size_t inner_iter_max, size_t restart, int variant, int variant_lo, size_t check_every,
+                     size_t *outer_out, size_t *inner_iters_out, double *rr_out, int *code_out);
 
 /* ---- SparseMatPar<SparseMatCRS<T,u32>> (sparsemat_par.rs:12-35, 86-140) over the GPUs of one node ----
  * The reference keeps n_blocks sub-matrices of R = n_rows / n_blocks rows (with_sub_matrices :20-28;

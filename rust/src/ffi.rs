@@ -22,6 +22,10 @@ pub const SMH_PRECOND_NONE: c_int = 0;
 pub const SMH_PRECOND_JACOBI: c_int = 1;
 pub const SMH_PRECOND_SGS: c_int = 2;
 pub const SMH_PRECOND_ILU: c_int = 3;
+pub const SMH_PRECOND_FSAI: c_int = 4;  // smh_refine_solve* only
+pub const SMH_INNER_CG: c_int = 0;
+pub const SMH_INNER_BICGSTAB: c_int = 1;
+pub const SMH_INNER_GMRES: c_int = 2;
 pub const SMH_EXCHANGE_NONE: c_int = 0;
 pub const SMH_EXCHANGE_ALLGATHER: c_int = 1;
 pub const SMH_EXCHANGE_WINDOW: c_int = 2;
@@ -126,6 +130,19 @@ extern "C" {
     pub fn smh_bicgstab_fsai_solve_vec(a: *mut smh_crs, g: *mut smh_crs, gt: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double,
                                        iter_max: usize, variant: c_int, check_every: usize, iters_out: *mut usize, rr_out: *mut c_double,
                                        breakdown_out: *mut c_int) -> c_int;
+    // extension: mixed precision.  A copy of a handle / a vector in the other dtype (f64 -> f32 to nearest even, f32 -> f64 exact), and
+    // iterative refinement: the residual and the update in f64, the correction by an f32 solver on a_lo (inner: SMH_INNER_*; precond:
+    // SMH_PRECOND_*, SMH_PRECOND_FSAI with the pair f_lo, f2_lo); 0 stands for the default in outer_max, inner_tol, inner_iter_max, restart
+    pub fn smh_crs_cast(a: *const smh_crs, dtype: c_int, out: *mut *mut smh_crs, overflow_out: *mut usize) -> c_int;
+    pub fn smh_vec_cast(src: *const smh_vec, dst: *mut smh_vec) -> c_int;
+    pub fn smh_refine_solve_vec(a: *mut smh_crs, a_lo: *mut smh_crs, inner: c_int, precond: c_int, f_lo: *mut smh_crs, f2_lo: *mut smh_crs,
+                                b: *const smh_vec, x: *mut smh_vec, tol: c_double, outer_max: usize, inner_tol: c_double, inner_iter_max: usize,
+                                restart: usize, variant: c_int, variant_lo: c_int, check_every: usize, outer_out: *mut usize,
+                                inner_iters_out: *mut usize, rr_out: *mut c_double, code_out: *mut c_int) -> c_int;
+    pub fn smh_refine_solve(a: *mut smh_crs, a_lo: *mut smh_crs, inner: c_int, precond: c_int, f_lo: *mut smh_crs, f2_lo: *mut smh_crs,
+                            b_host: *const c_void, b_len: usize, x_host_inout: *mut c_void, x_len: usize, tol: c_double, outer_max: usize,
+                            inner_tol: c_double, inner_iter_max: usize, restart: usize, variant: c_int, variant_lo: c_int, check_every: usize,
+                            outer_out: *mut usize, inner_iters_out: *mut usize, rr_out: *mut c_double, code_out: *mut c_int) -> c_int;
     pub fn smh_crs_inner_prod(m: *mut smh_crs, lhs_host: *const c_void, lhs_len: usize, rhs_host: *const c_void,
                               rhs_len: usize, variant: c_int, out: *mut c_double) -> c_int;
     // add_to (ops[k] == 0 / ops null) or set (ops[k] == 1) stream -> the CRS `to_crs()` would return

@@ -20,6 +20,11 @@ SMH_PRECOND_NONE, SMH_PRECOND_JACOBI, SMH_PRECOND_SGS, SMH_PRECOND_ILU = 0, 1, 2
 PRECONDS = {None: SMH_PRECOND_NONE, "jacobi": SMH_PRECOND_JACOBI, "sgs": SMH_PRECOND_SGS, "ilu": SMH_PRECOND_ILU}
 # the preconditioners of GMRES and BiCGStab: PRECONDS' kinds (one entry point, a code) and "fsai" (entry points of its own, a pair)
 PRECOND_NAMES = tuple(PRECONDS) + ("fsai",)
+# smh_refine_solve*: the inner solver, and "fsai" as a code of that entry point alone
+SMH_INNER_CG, SMH_INNER_BICGSTAB, SMH_INNER_GMRES = 0, 1, 2
+INNERS = {"cg": SMH_INNER_CG, "bicgstab": SMH_INNER_BICGSTAB, "gmres": SMH_INNER_GMRES}
+SMH_PRECOND_FSAI = 4
+REFINE_PRECONDS = dict(PRECONDS, fsai=SMH_PRECOND_FSAI)
 UPLO = {"lower": SMH_TRI_LOWER, "upper": SMH_TRI_UPPER}
 EXCHANGE_NONE, EXCHANGE_ALLGATHER, EXCHANGE_WINDOW, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGES = {"none": EXCHANGE_NONE, "allgather": EXCHANGE_ALLGATHER, "window": EXCHANGE_WINDOW, "halo": EXCHANGE_WINDOW, "auto": EXCHANGE_AUTO}
@@ -224,6 +229,12 @@ SIGNATURES = {
                                           C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_bicgstab_precond_solve_vec": (_int, [_vp, _int, _vp, _vp, _vp, C.c_double, _sz, _int, _sz, C.POINTER(_sz),
                                               C.POINTER(C.c_double), C.POINTER(_int)]),
+    "smh_crs_cast": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_sz)]),
+    "smh_vec_cast": (_int, [_vp, _vp]),
+    "smh_refine_solve": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, C.c_double, _sz, _sz, _int, _int, _sz,
+                                C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_double), C.POINTER(_int)]),
+    "smh_refine_solve_vec": (_int, [_vp, _vp, _int, _int, _vp, _vp, _vp, _vp, C.c_double, _sz, C.c_double, _sz, _sz, _int, _int, _sz,
+                                    C.POINTER(_sz), C.POINTER(_sz), C.POINTER(C.c_double), C.POINTER(_int)]),
     "smh_comm_unique_id": (_int, [_vp]),
     "smh_comm_create": (_int, [_vp, _int, _int, C.POINTER(_vp)]),
     "smh_comm_destroy": (_int, [_vp]),

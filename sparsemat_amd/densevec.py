@@ -87,6 +87,13 @@ class DenseVec:
         check(lib().smh_vec_copy(out._h, self._h))
         return out
 
+    def astype(self, dtype):
+        """A new vector of ``dtype`` (f32 or f64), converted on the device (``smh_vec_cast``, an extension): f64 -> f32 rounds to
+        nearest even (finite values beyond f32's range become +-Inf), f32 -> f64 is exact; the same dtype gives a copy."""
+        out = DenseVec.zeros(self.dim(), dtype)
+        check(lib().smh_vec_cast(self._h, out._h))
+        return out
+
     def permute(self, perm, inverse=False):
         """A new vector: ``out[i] = self[perm[i]]``, or with ``inverse`` ``out[perm[i]] = self[i]`` (an extension, see
         ``SparseMatCRS.permute``): ``x.permute(p).permute(p, inverse=True)`` is ``x``."""

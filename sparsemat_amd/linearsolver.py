@@ -20,6 +20,8 @@
 * ``GMRES``                 -- an extension for non-symmetric systems: restarted GMRES(m), the robust companion of ``BiCGStab``
                                (``smh_gmres_solve*``); its Krylov basis stays on the device.  ``precond="jacobi"``, ``"sgs"`` or
                                ``"ilu"``: right-preconditioned (``smh_gmres_precond_solve*``).
+* ``IterativeRefinement``   -- an extension: an f64 answer from f32 solves (``smh_refine_solve*``): the residual in f64, the correction
+                               by one of the solvers above on an f32 copy of the matrix, the update in f64.
 """
 import math
 
@@ -296,4 +298,56 @@ class GMRES(_RightPreconditioned):
         vec_fn, host_fn, handles = self._resolve(mat, factor)
         self._solve(vec_fn, host_fn, mat, b, x, handles=handles, extra_out=(cycles, brk), extra_in=(self.restart,))
         self.cycles, self.breakdown = cycles.value, brk.value
+        return x
+
+
+class IterativeRefinement:
+    """Mixed-precision iterative refinement -- an EXTENSION (``smh_refine_solve*``): an f64-accurate x of A x = b whose bodies run in
+    f32.  Each outer step forms r = b - A x in f64, scales it by a power of two to a norm in [1, 2), converts it to f32, solves
+    A_lo d = r_lo from d = 0 with the ``inner`` solver ("cg", "bicgstab" or "gmres", preconditioned by ``precond``: None, "jacobi" (not
+    with "cg"), "sgs", "ilu" or "fsai") to the absolute tolerance ``inner_tol`` -- a relative reduction of the residual by
+    ``inner_tol / 2`` to ``inner_tol`` -- and adds the widened, rescaled d to x in f64: one rounding per element going down and one
+    going up.  It stops when sqrt(r.r) < ``tol`` (``code`` 0), after ``outer_max`` steps (1), or when a step does not lower r.r (2:
+    the step is undone, x is the better iterate).  ``variant`` is the f64 product's, ``variant_lo`` the inner solver's.
+
+    ``solve(mat, b, x, mat_lo=None, factor=None)``: ``mat`` f64, x updated in place -- two f64 ``DenseVec``s, or an array-like b with a
+    contiguous f64 numpy x.  ``mat_lo``: the f32 matrix (None: ``mat.astype(float32)``); ``factor``: the f32 factor of ``mat_lo`` for
+    "ilu" (a matrix) or "fsai" (a pair); None factors ``mat_lo`` through ``ilu0``, and through ``fsai`` (inner "cg") or ``fsai_ns``.
+    Afterwards ``outer_iterations``, ``iterations`` (the inner solves' bodies in total), ``r_norm_squared`` (the last accepted r.r),
+    ``code``, ``mat_lo`` and ``factor`` are set."""
+
+    def __init__(self, tol=1e-12, outer_max=20, inner="cg", precond=None, inner_tol=1e-4, inner_iter_max=10_000, restart=30,
+                 variant="auto", variant_lo="auto", check_every=0):
+        if inner not in _lib.INNERS:
+            raise ValueError('inner must be "cg", "bicgstab" or "gmres"')
+        if precond not in _lib.REFINE_PRECONDS:
+            raise ValueError('precond must be None, "jacobi", "sgs", "ilu" or "fsai"')
+        self.tol, self.outer_max, self.inner, self.precond = float(tol), int(outer_max), inner, precond
+        self.inner_tol, self.inner_iter_max, self.restart = float(inner_tol), int(inner_iter_max), int(restart)
+        self.variant, self.variant_lo, self.check_every = variant, variant_lo, int(check_every)
+        self.outer_iterations = self.iterations = self.r_norm_squared = self.code = None
+        self.mat_lo = self.factor = None
+
+    def solve(self, mat, b, x, mat_lo=None, factor=None):
+        if mat_lo is None:
+            mat_lo = mat.astype(np.float32)
+        if factor is None and self.precond == "ilu":
+            factor = mat_lo.ilu0()[0]
+        elif factor is None and self.precond == "fsai":
+            factor = (mat_lo.fsai() if self.inner == "cg" else mat_lo.fsai_ns())[:2]
+        self.mat_lo, self.factor = mat_lo, factor
+        pair = factor if isinstance(factor, (tuple, list)) else (factor, None)
+        handles = [f._h if f is not None else None for f in pair]
+        outer, inner, rr, code = C.c_size_t(), C.c_size_t(), C.c_double(), C.c_int()
+        head = (mat._h, mat_lo._h, _lib.INNERS[self.inner], _lib.REFINE_PRECONDS[self.precond], handles[0], handles[1])
+        tail = (self.tol, self.outer_max, self.inner_tol, self.inner_iter_max, self.restart, _lib.VARIANTS[self.variant],
+                _lib.VARIANTS[self.variant_lo], self.check_every, C.byref(outer), C.byref(inner), C.byref(rr), C.byref(code))
+        if isinstance(b, DenseVec) and isinstance(x, DenseVec):
+            check(lib().smh_refine_solve_vec(*head, b._h, x._h, *tail))
+        else:
+            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+                raise TypeError("x must be a contiguous f64 numpy array (updated in place)")
+            bb = np.ascontiguousarray(b, dtype=np.float64)
+            check(lib().smh_refine_solve(*head, bb.ctypes.data if bb.size else None, bb.size, x.ctypes.data if x.size else None, x.size, *tail))
+        self.outer_iterations, self.iterations, self.r_norm_squared, self.code = outer.value, inner.value, rr.value, code.value
         return x

@@ -339,6 +339,16 @@ class SparseMatCRS:
         check(lib().smh_crs_clone(self._h, C.byref(h)))
         return type(self)(h, self.dtype)
 
+    def astype(self, dtype):
+        """A new library-owned matrix of ``dtype`` (f32 or f64) with this one's dims, pattern, orphan and kernel settings, its
+        values converted on the device (``smh_crs_cast``, an extension): f64 -> f32 rounds to nearest even, f32 -> f64 is exact; the
+        same dtype gives ``clone()``.  The result's ``overflow`` is the number of finite values that became infinite."""
+        h, over = C.c_void_p(), C.c_size_t()
+        check(lib().smh_crs_cast(self._h, _lib.dtype_code(dtype), C.byref(h), C.byref(over)))
+        out = type(self)(h, dtype)
+        out.overflow = over.value
+        return out
+
     def add(self, rhs):
         """SparseMatrix::add (sparsematrix.rs:123-133), in place like the reference's ``&mut self``: ``*get_mut(i, j) += val``
         for every entry of ``rhs`` in storage order -- new columns pushed to the start of their row, folds into the first
