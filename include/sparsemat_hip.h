@@ -118,7 +118,9 @@ int smh_crs_create(smh_dtype dtype, size_t n_rows, size_t n_cols, size_t nnz,
                    const uint32_t *offset_rows, const uint32_t *columns, const void *values,
                    int validate, smh_crs **out);
 /* Same, over arrays that already live in device memory (borrowed, not copied, must outlive
- * the handle; columns/values 16-byte aligned).  device = ordinal owning the pointers.   */
+ * the handle; columns/values 16-byte aligned).  device = ordinal owning the pointers.
+ * Values written in place afterwards are announced with smh_crs_update_values(m, NULL): the K1r ring's
+ * value records (smh_crs_ring_values) are derived from the values too, like the K2c copies. */
 int smh_crs_create_dev(smh_dtype dtype, size_t n_rows, size_t n_cols, size_t nnz,
                        const uint32_t *offset_rows_dev, const uint32_t *columns_dev,
                        const void *values_dev, int validate, smh_crs **out);
@@ -371,7 +373,9 @@ int smh_crs_is_sorted(const smh_crs *m, int *out);
 int smh_crs_sort_rows(smh_crs *m);
 int smh_crs_destroy(smh_crs *m);
 /* host mutated values: re-upload.  values_host == NULL: the device values (borrowed arrays of
- * smh_crs_create_dev) were changed in place -- derived copies (K2c) are rebuilt on next use */
+ * smh_crs_create_dev) were changed in place -- derived copies (K2c) are rebuilt on next use.
+ * The K1r ring's value records (smh_crs_ring_values) are derived from the values too: they are dropped here, and the next
+ * product tests the new values and builds them again or streams the value array. */
 int smh_crs_update_values(smh_crs *m, const void *values_host);
 int smh_crs_download(const smh_crs *m, uint32_t *offset_rows, uint32_t *columns, void *values);
 /* n_rows :124-126, n_cols :128-130, n_non_zero_entries :132-134 */
@@ -442,6 +446,15 @@ int smh_crs_ring_entries(smh_crs *m, uint32_t *out);
  * form, 12 bits per column (f32 on the single-window ring of 16384 columns; SMH_RING_COL12 = auto / 0 / 1).  The form changes
  * speed only, never a result. */
 int smh_crs_ring_column_form(smh_crs *m, int *form_out);
+/* what those phases stream for their VALUES under the current settings (builds the plan and the forms on first use):
+ * *form_out = 0: the value array itself; 1: 24-bit fixed-point values, four of them with the chunk's four low column bytes in one
+ * 16-byte record (4.5 instead of 5.5 bytes per entry; *exponent_out = E, every value being k * 2^E with -2^23 <= k < 2^23);
+ * -1: the matrix was tested and refused (some value is no such multiple, or is NaN, +-Inf, -0.0 or subnormal), it streams the value
+ * array.  The form is taken only together with the compact column form (form 2 above), for a matrix ALL of whose streamed values
+ * decode to their own bits -- checked value by value when the records are written -- so it changes speed only, never a result.
+ * SMH_RING_VAL24 = auto / 0 / 1: 0 = never; 1 = same as auto (it cannot force a matrix that does not qualify).  exponent_out may
+ * be NULL; it receives 0 unless *form_out is 1. */
+int smh_crs_ring_values(smh_crs *m, int *form_out, int *exponent_out);
 /* 1: one sliding window (slot = column mod ring size).  4: banded ring for rows that reference a few narrow
  * column intervals far apart (stencils): band k holds the k-th interval of the tiles, slot = k * S +
  * column mod S, S = ring size / 4.  intervals_out (optional, banded plans only): 8 u32 per 64-row tile,

@@ -111,6 +111,7 @@ SIGNATURES = {
     "smh_crs_set_ring": (_int, [_vp, _int]),
     "smh_crs_ring_entries": (_int, [_vp, _u32p]),
     "smh_crs_ring_column_form": (_int, [_vp, C.POINTER(_int)]),
+    "smh_crs_ring_values": (_int, [_vp, C.POINTER(_int), C.POINTER(_int)]),
     "smh_crs_ring_bands": (_int, [_vp, _u32p, _vp]),
     "smh_crs_ring_regular": (_int, [_vp, _vp]),
     "smh_crs_ring_plan": (_int, [_vp, _u32p, C.POINTER(_sz), C.POINTER(C.c_double), C.POINTER(_int), _vp, _vp]),

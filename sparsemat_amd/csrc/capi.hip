@@ -1144,6 +1144,7 @@ int smh_crs_scale(smh_crs *m, double a) {
     }
     // (K1s XD-V: every entry is its dictionary value times a, rounded as the entry itself is: the indices in the codes stay right)
     if (m->dict.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->dict.values.get(), 32, a, m->stream));
+    ring_values_changed(m);  // (K1r's chunk records hold the old values: the next product tests the scaled ones)
     if (m->cb.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->cb.val.get(), m->nnz, a, m->stream));
     if (m->cf.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->cf.val.get(), m->nnz, a, m->stream));
     if (m->tiled.state == Form::Ready) SMH_TRY(launch_scale_values(m->dtype, m->tiled.val.get(), (size_t)m->tiled.tot, a, m->stream));
@@ -1342,7 +1343,17 @@ int smh_crs_ring_column_form(smh_crs *m, int *form_out) {
     if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
     bool ring = false;
     SMH_TRY(vector_uses_ring(m, &ring));
-    *form_out = !ring ? 0 : m->ring.lo8.get() ? 2 : m->ring.col16.get() ? 1 : 0;
+    *form_out = !ring ? 0 : (m->ring.lo8.get() || m->ring.rec16.get()) ? 2 : m->ring.col16.get() ? 1 : 0;
+    return SMH_OK;
+}
+
+int smh_crs_ring_values(smh_crs *m, int *form_out, int *exponent_out) {
+    if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));
+    const bool rec = ring && m->ring.rec16.get();
+    *form_out = rec ? 1 : (ring && m->ring.v24 == Form::Refused) ? -1 : 0;
+    if (exponent_out) *exponent_out = rec ? m->ring.v24_exp : 0;
     return SMH_OK;
 }
 

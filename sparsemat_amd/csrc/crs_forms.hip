@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "crs_forms.hpp"
+#include "ring_val24.hpp"
 
 namespace smh {
 
@@ -341,11 +342,14 @@ static void drop_ring_col12(smh_crs *m) {
     m->ring.lo8.reset();
     m->ring.hdr.reset();
     m->ring.escapes.reset();
+    m->ring.rec16.reset();  // (the records hold the low column bytes: they go with the form, what is known about the values stays)
 }
+// (the low bytes live in lo8 or, with the 24-bit value code, in the chunk records: either one counts as "built")
 static int ensure_ring_col12(smh_crs *m, bool forced, bool *use) {
     RingPlan &r = m->ring;
     *use = forced || r.c12 == Form::Ready;
-    if (r.c12 != Form::NotTried && (!*use || r.lo8.get())) return SMH_OK;
+    if (r.c12 != Form::NotTried && (!*use || r.lo8.get() || r.rec16.get())) return SMH_OK;
+    r.rec16.reset();
     Scratch scr;
     uint32_t *jobs = nullptr;
     unsigned long long *d_counts = nullptr, h_counts[2] = {0, 0};
@@ -374,6 +378,49 @@ static int ensure_ring_col12(smh_crs *m, bool forced, bool *use) {
     return SMH_OK;
 }
 
+// K1r's chunk records with 24-bit values (ring_val24.hpp), for a handle whose compact column form is built: the counting pass gives
+// the exponent (or refuses: a value the code never holds, an exponent outside its bound), the encoder writes the records from the
+// values and lo8 and counts the values that do not come back bit for bit -- the form is taken (*use, and lo8 goes) only when there is
+// none.  Tested once per set of values (smh_crs_update_values / smh_crs_scale / a new storage order reset v24 to NotTried).
+void ring_values_changed(smh_crs *m) {
+    m->ring.rec16.reset();  // (the compact column form then has no low bytes: ensure_ring_col12 builds it again on the next use)
+    m->ring.v24 = Form::NotTried;
+    m->ring.v24_exp = 0;
+}
+static int ensure_ring_val24(smh_crs *m, bool *use) {
+    RingPlan &r = m->ring;
+    *use = r.v24 != Form::Refused;
+    if (!*use || r.rec16.get()) return SMH_OK;
+    r.v24 = Form::Refused;  // until the records are complete
+    r.v24_exp = 0;
+    *use = false;
+    Scratch scr;
+    uint32_t *jobs = nullptr;
+    unsigned long long *d_counts = nullptr, h_misses = 0;
+    uint32_t h_stats[2] = {0, 0};
+    SMH_TRY(scr.alloc(&jobs, 2 * r.n_phases));
+    SMH_TRY(scr.alloc(&d_counts, 2));
+    const float *val = (const float *)m->d_val;
+    SMH_TRY(read_back(h_stats, 2, m->stream, [&](uint32_t *d_stats) {
+        return launch_val24_count(m->d_off, val, m->nnz, r.phases.get(), r.n_phases, jobs, d_counts, d_stats, m->stream);
+    }));
+    const int E = h_stats[0] == ~0u ? 0 : (int)h_stats[0] - 1024;  // (no non-zero value: any exponent does)
+    if (h_stats[1] != 0u || !val24::exponent_ok(E)) return SMH_OK;
+    const size_t n_chunks_out = ((m->nnz + 3) >> 2) + 1;  // (as lo8)
+    DevArray<uint32_t> rec16;
+    SMH_TRY(rec16.alloc(n_chunks_out * 4));
+    SMH_TRY(read_back(d_counts, &h_misses, 1, m->stream, [&](unsigned long long *d) {
+        return launch_val24_encode(val, m->nnz, jobs, r.n_phases, n_chunks_out, r.lo8.get(), E, rec16.get(), d, m->stream);
+    }));
+    if (h_misses != 0) return SMH_OK;  // (a value of more than 24 bits: the records go, lo8 stays)
+    r.rec16 = std::move(rec16);
+    r.lo8.reset();
+    r.v24 = Form::Ready;
+    r.v24_exp = E;
+    *use = true;
+    return SMH_OK;
+}
+
 // does the VECTOR family run as K1r (LDS x-ring) for this matrix?
 int vector_uses_ring(smh_crs *m, bool *out) {
     *out = false;
@@ -393,8 +440,18 @@ int vector_uses_ring(smh_crs *m, bool *out) {
     if (const char *e = getenv("SMH_RING_COL12")) want12 = strcmp(e, "auto") == 0 ? -1 : (atoi(e) ? 1 : 0);  // tuning knob
     const bool can12 = m->dtype == SMH_F32 && m->ring.bands == 1 && m->ring.entries == (unsigned)kRingEntries && m->nnz > 0;
     bool use12 = can12 && (want12 == 1 || (want12 < 0 && want < 0 && m->ring.fraction >= 0.25));
+    // ... and with it, where the values are 24-bit fixed-point numbers (ring_val24.hpp), 16-byte chunk records instead of the low
+    // bytes AND the value array: 4.5 bytes per entry.  Exactly where the compact form is taken and the plan runs the REGK kernel (the
+    // only one with a record body); SMH_RING_VAL24=0 never, 1 = automatic: a matrix that does not qualify cannot be forced.
+    int want24 = m->knobs.use_val24;
+    if (const char *e = getenv("SMH_RING_VAL24")) want24 = strcmp(e, "auto") == 0 ? -1 : (atoi(e) ? 1 : 0);  // tuning knob
+    const char *reg_env = getenv("SMH_RING_REGULAR");  // (as launch_ring reads it)
+    const bool reg_off = reg_env && strcmp(reg_env, "auto") != 0 && atoi(reg_env) == 0;
+    bool use24 = use12 && want24 != 0 && m->ring.reg_applies && !reg_off;
+    if (!use24) m->ring.rec16.reset();  // (switched off: the low bytes come back below, lazily, as with the col12 / col16 switch)
     if (use12) SMH_TRY(ensure_ring_col12(m, want12 == 1, &use12));
     if (!use12) drop_ring_col12(m);
+    if (use12 && use24) SMH_TRY(ensure_ring_val24(m, &use24));
     // (the banded plan cannot do without: its gathers take the ring slot from that array)
     // col16 is built by the same rule as before also when the compact form is in use, although the kernel then does not read it:
     // tests/test_bench_contract_gpu.py pins `derived_bytes` to at least 2 bytes per entry.  Dropping it here (`!use12 &&`: 2 bytes
@@ -426,6 +483,9 @@ void invalidate(smh_crs *m, Changed what) {
     m->split = RowSplit();
     m->tiled = Tiled();
     if (what == Changed::Values) m->dict.state = Form::NotTried;  // (the dictionary array stays: a product in flight may still read it)
+    // K1r's chunk records are made of the values (and, like lo8, of the order inside the rows): the next product tests them again.
+    // hdr and the escapes stay: the columns did not change.
+    if (what == Changed::Values || what == Changed::Order) ring_values_changed(m);
     if (what == Changed::Order) {
         // the K1s codes and the 16-bit column array follow the storage order too; the ring plan's phases and windows stay: they
         // depend on each tile's column set, not on order

@@ -36,6 +36,8 @@ int ensure_split(::smh_crs *m);
 int vector_uses_ring(::smh_crs *m, bool *out);
 enum class Changed { Values, Order, BlockWidth };  // update_values / apply's values-only route; sort_rows; set_colblock_shift
 void invalidate(::smh_crs *m, Changed what);
+// the values changed where invalidate is not called (smh_crs_scale): K1r's chunk records go, the next product tests the new values
+void ring_values_changed(::smh_crs *m);
 // K1s configuration the STREAM variant runs with for this handle (builds the code tables on first use)
 struct StreamCfg {
     int rpt = 1;

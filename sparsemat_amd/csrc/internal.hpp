@@ -513,10 +513,15 @@ int launch_tile_span(const uint32_t *off, const uint32_t *col, size_t n_rows, si
 // c12 (optional, instead of col16; f32 on the single-window ring of kRingEntries columns): the compact form of ring_col12.hpp,
 // 1.5 bytes per column -- lo8: one byte per entry, hdr: one u16 per 4-entry chunk (both padded like col16), escapes: 2 u32 per
 // chunk the code cannot hold
+// rec16 (optional, instead of lo8; matrices whose values all fit the 24-bit code of ring_val24.hpp): one 16-byte record per chunk --
+// the four values as 24-bit integers and, in its fourth dword, the chunk's dword of lo8 -- with scale = 2^E; hdr and escapes as
+// before.  The ring phases then read neither lo8 nor the value array.
 struct RingCol12 {
     const uint8_t *lo8 = nullptr;
     const uint16_t *hdr = nullptr;
     const uint32_t *escapes = nullptr;
+    const uint32_t *rec16 = nullptr;
+    float scale = 0.0f;
 };
 int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12,
                       const void *val, const void *x, void *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
@@ -540,6 +545,14 @@ int launch_col12_count(const uint32_t *off, const uint32_t *col, size_t nnz, con
                        unsigned long long *counts, hipStream_t s);
 int launch_col12_encode(const uint32_t *col, size_t nnz, const uint32_t *jobs, size_t n_phases, size_t n_chunks_out, uint8_t *lo8,
                         uint16_t *hdr, uint32_t *escapes, unsigned long long *counts, hipStream_t s);
+// the chunk records' build (f32).  count: jobs as above (counts: 2 words of scratch for it), stats[0] = 1024 + the largest E every
+// non-zero value of the jobs' chunks is a multiple of 2^E for (~0u: there is none), stats[1] != 0: some value the code never holds.
+// encode: rec16 (n_chunks_out records of 16 bytes, all written; the fourth dword from lo8), *misses = values of the jobs' chunks
+// that do not decode to their own bits
+int launch_val24_count(const uint32_t *off, const float *val, size_t nnz, const RingPhase *phases, size_t n_phases, uint32_t *jobs,
+                       unsigned long long *counts, uint32_t *stats, hipStream_t s);
+int launch_val24_encode(const float *val, size_t nnz, const uint32_t *jobs, size_t n_phases, size_t n_chunks_out, const uint8_t *lo8, int exponent,
+                        uint32_t *rec16, unsigned long long *misses, hipStream_t s);
 // structure statistics / validation
 struct CrsStats {
     uint32_t max_row_len;
@@ -699,6 +712,12 @@ struct RingPlan {  // K1r
     DevArray<uint8_t> lo8;
     DevArray<uint16_t> hdr;
     DevArray<uint32_t> escapes;
+    // the chunk records of the 24-bit value code (ring_val24.hpp), built INSTEAD of lo8 where the compact form is in use, the plan
+    // takes the REGK kernel and every value the ring phases stream decodes to its own bits (hdr and escapes are shared).  v24:
+    // NotTried until the values have been tested (and again after they changed); Ready: they fit, with exponent v24_exp; Refused.
+    Form v24 = Form::NotTried;
+    int v24_exp = 0;
+    DevArray<uint32_t> rec16;             // 4 u32 per chunk; exists while the form is in use (then lo8 does not)
 };
 struct StreamCodes {  // K1s 16-bit column codes (Ready only when every tile has a description; Refused holds nothing)
     Form state = Form::NotTried;
@@ -813,6 +832,7 @@ struct Knobs {
     int use_stream_vdict = -1;            // -1 automatic (whenever the values allow), 0 never
     int use_col16 = -1;                   // -1 automatic (when at least a quarter of the rows are ring rows), 0 never, 1 always
     int use_col12 = -1;                   // the compact form instead: -1 automatic (where it applies, few chunks escape and use_col16 is automatic too), 0 never, 1 wherever it applies
+    int use_val24 = -1;                   // the chunk records with 24-bit values, where the compact form is in use: -1 / 1 when the values fit, 0 never
 };
 
 }  // namespace smh

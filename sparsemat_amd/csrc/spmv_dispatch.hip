@@ -1,5 +1,6 @@
 // spmv_dispatch.hip -- which kernel a product runs (AUTO's rules, with the measurements behind every threshold), which derived forms
 // that kernel runs on, and its launches.  Host-side logic only; the forms themselves are built in crs_forms.hip.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -178,10 +179,12 @@ static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *
     // loads its offsets
     const char *reg_env = getenv("SMH_RING_REGULAR");
     const bool reg_off = reg_env && strcmp(reg_env, "auto") != 0 && atoi(reg_env) == 0;
-    const uint32_t *reg_len = m->ring.reg_applies && !reg_off && (m->ring.lo8.get() || m->ring.col16.get()) ? m->ring.reg_len.get() : nullptr;
+    const uint32_t *reg_len = m->ring.reg_applies && !reg_off && (m->ring.lo8.get() || m->ring.rec16.get() || m->ring.col16.get()) ? m->ring.reg_len.get() : nullptr;
+    // the chunk records (vector_uses_ring keeps them only for a plan and a setting that pass reg_len) with 2^E, an exact power of two
+    const RingCol12 c12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get(), m->ring.rec16.get(),
+                        m->ring.rec16.get() ? ldexpf(1.0f, m->ring.v24_exp) : 0.0f};
     // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
-    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(),
-                             RingCol12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get()}, m->d_val, x, y, m->n_rows, m->nnz,
+    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(), c12, m->d_val, x, y, m->n_rows, m->nnz,
                              m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
                              m->ring.bands, s, dot_partials, b0, b1, reg_len);
 }

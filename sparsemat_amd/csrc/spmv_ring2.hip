@@ -21,6 +21,7 @@
 //   are off[row_begin] + i * L, computed where the other body loads them (phase_rows<..., REG>, in the REGK form of the kernel).
 #include "internal.hpp"
 #include "ring_col12.hpp"
+#include "ring_val24.hpp"
 
 #include <atomic>
 #include <type_traits>
@@ -96,12 +97,18 @@ __device__ __forceinline__ uint32_t lane_pos(uint32_t j, int q) {
 //            column is `column mod 16384`) -- 4 columns are then 8 bytes (f32: one load; f64: two of 4 bytes)
 //   kCol12:  ... into the byte array of the compact form (ring_col12.hpp; f32 on the 16384-slot ring), and hdrp into its u16
 //            chunk headers -- 4 columns are 4 + 2 bytes, decoded where they are used (chunk_slots)
-enum : int { kColU32 = 0, kCol16 = 1, kCol12 = 2 };
+//   kRec16:  ... into the 16-byte chunk records of ring_val24.hpp: a chunk's four VALUES as 24-bit integers (three dwords) and, in
+//            the fourth dword, what kCol12's byte array holds for the chunk; hdrp as for kCol12.  One load brings values and low
+//            column bytes, the value array is not read: 4 + 2 bytes per 4 entries less than kCol12 (f32, 16384-slot ring,
+//            matrices whose values all fit the code)
+enum : int { kColU32 = 0, kCol16 = 1, kCol12 = 2, kRec16 = 3 };
+constexpr bool has_headers(int cf) { return cf == kCol12 || cf == kRec16; }  // the forms that take ring slots from ring_col12.hpp's code
 struct ColStream {
     const void *colp;          // wave-uniform base of the phase's first chunk in the array of its form
-    const uint16_t *hdrp;      // kCol12: ... and in the chunk headers
-    const uint16_t *table;     // kCol12: the triple table (in LDS)
-    const u32x2 *escapes;      // kCol12: the side table
+    const uint16_t *hdrp;      // kCol12, kRec16: ... and in the chunk headers
+    const uint16_t *table;     // kCol12, kRec16: the triple table (in LDS)
+    const u32x2 *escapes;      // kCol12, kRec16: the side table
+    float scale;               // kRec16: 2^E, what the 24-bit integers are multiples of
 };
 template <typename T, int CF, int LANES>
 __device__ __forceinline__ void load_chunk_nb(const ColStream &cs, const T *__restrict__ valp, uint32_t pass_rel, uint32_t j,
@@ -110,7 +117,17 @@ __device__ __forceinline__ void load_chunk_nb(const ColStream &cs, const T *__re
     if constexpr (sizeof(T) == 4) {
         uint32_t rel = pass_rel + 4u * j;
         rel = rel < last_rel ? rel : last_rel;
-        if constexpr (CF == kCol12) {  // c[0]: the chunk's four low bytes (or its side-table index), c[1]: its header
+        if constexpr (CF == kRec16) {  // v[0..2]: the record's three value dwords (bits, decoded where they are used), c[0] / c[1] as kCol12
+            const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(
+                reinterpret_cast<const char *>(colp) + SMH_R2_OFF(rel, 4u)));
+            // (scalars first: __builtin_bit_cast applied to a vector's element reads the vector's first bytes, whichever element is named)
+            const uint32_t w0 = r.x, w1 = r.y, w2 = r.z;
+            c[0] = r.w;
+            c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(cs.hdrp) + (SMH_R2_OFF(rel, 1u) >> 1)));
+            v[0] = __uint_as_float(w0); v[1] = __uint_as_float(w1); v[2] = __uint_as_float(w2);
+            v[3] = 0.0f;  // (never read)
+            return;
+        } else if constexpr (CF == kCol12) {  // c[0]: the chunk's four low bytes (or its side-table index), c[1]: its header
             c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(rel, 1u)));
             c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(cs.hdrp) + (SMH_R2_OFF(rel, 1u) >> 1)));
         } else if constexpr (CF == kCol16) {  // kept packed: c[0], c[1] hold two columns each (unpacked where they are used, see chunk_slots)
@@ -130,7 +147,7 @@ __device__ __forceinline__ void load_chunk_nb(const ColStream &cs, const T *__re
         uint32_t e0 = pass_rel + 2u * j, e1 = pass_rel + 2u * LANES + 2u * j;
         e0 = e0 < last_rel + 2u ? e0 : last_rel + 2u;
         e1 = e1 < last_rel + 2u ? e1 : last_rel + 2u;
-        static_assert(CF != kCol12, "the compact column form is an f32 form");
+        static_assert(!has_headers(CF), "the compact column form and the chunk records are f32 forms");
         if constexpr (CF == kCol16) {
             c[0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(e0, 2u)));
             c[1] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(colp) + SMH_R2_OFF(e1, 2u)));
@@ -151,7 +168,7 @@ __device__ __forceinline__ void load_chunk_nb(const ColStream &cs, const T *__re
 template <int CF, int RING>
 __device__ __forceinline__ void chunk_slots(const uint32_t (&c)[4], const ColStream &cs, uint32_t (&slot)[4]) {
     constexpr uint32_t MASK = RING - 1;
-    if constexpr (CF == kCol12) {
+    if constexpr (has_headers(CF)) {
         static_assert(RING == (int)col12::kSlots, "the compact column form holds slots of the 16384-slot ring");
         col12::decode_chunk(c[1], c[0], cs.table, slot);
         const bool escaped = col12::is_escape(c[1]);
@@ -171,6 +188,19 @@ __device__ __forceinline__ void chunk_slots(const uint32_t (&c)[4], const ColStr
 }
 
 __device__ __forceinline__ float r2_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// a chunk's four values as the unit holds them: themselves, or (kRec16) the three dwords of 24-bit integers they are decoded from --
+// (float)k * 2^E gives the very bits the value array holds (ring_val24.hpp; the form is only built for matrices where it does)
+template <typename T, int CF>
+__device__ __forceinline__ void chunk_values(const T (&v)[4], const ColStream &cs, T (&a)[4]) {
+    if constexpr (CF == kRec16) {
+        static_assert(sizeof(T) == 4, "the chunk records are an f32 form");
+        val24::decode_chunk(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), cs.scale, a);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = v[q];
+    }
+}
 __device__ __forceinline__ double r2_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 template <typename T, int NCH>
@@ -257,6 +287,8 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
         for (int ch = 0; ch < CH; ++ch) {
             uint32_t slot[4];
             if constexpr (GM == 1) chunk_slots<CF, RING>(u.c[t * CH + ch], cs, slot);
+            T a[4];
+            chunk_values<T, CF>(u.v[t * CH + ch], cs, a);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint32_t rel = 4u * (uint32_t)(ch * LANES) + lane_pos<T, LANES>(j, q);
@@ -267,7 +299,7 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
                 if constexpr (GM == 1) xv = ring[slot[q]];
                 else if constexpr (GM == 2) xv = __builtin_nontemporal_load(&x[in ? u.c[t * CH + ch][q] : 0u]);
                 else xv = x[in ? u.c[t * CH + ch][q] : 0u];
-                const T f = r2_fma(u.v[t * CH + ch][q], xv, sum);
+                const T f = r2_fma(a[q], xv, sum);
                 sum = in ? f : sum;
             }
         }
@@ -278,6 +310,8 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
             load_chunk_nb<T, CF, LANES>(cs, valp, sa - kb + pass, j, last_rel, cc, vv);
             uint32_t slot[4];
             if constexpr (GM == 1) chunk_slots<CF, RING>(cc, cs, slot);
+            T a[4];
+            chunk_values<T, CF>(vv, cs, a);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool in = pass + lane_pos<T, LANES>(j, q) < len;
@@ -285,7 +319,7 @@ __device__ __forceinline__ void consume_unit(const Unit<T, SB * CH> &u, uint64_t
                 if constexpr (GM == 1) xv = ring[slot[q]];
                 else if constexpr (GM == 2) xv = __builtin_nontemporal_load(&x[in ? cc[q] : 0u]);
                 else xv = x[in ? cc[q] : 0u];
-                const T f = r2_fma(vv[q], xv, sum);
+                const T f = r2_fma(a[q], xv, sum);
                 sum = in ? f : sum;
             }
         }
@@ -328,8 +362,8 @@ __device__ __forceinline__ void phase_rows(const uint32_t *__restrict__ off, con
     kb = kb < (uint32_t)last_chunk ? kb : (uint32_t)last_chunk;
     const uint32_t last_rel = (uint32_t)last_chunk - kb;
     ColStream cs = cols;  // ... from the phase's first chunk (kb is a multiple of 4: kb / 4 chunks)
-    cs.colp = reinterpret_cast<const char *>(cols.colp) + (size_t)kb * (CF == kCol12 ? 1u : CF == kCol16 ? 2u : 4u);
-    if constexpr (CF == kCol12) cs.hdrp = cols.hdrp + (kb >> 2);
+    cs.colp = reinterpret_cast<const char *>(cols.colp) + (size_t)kb * (CF == kCol12 ? 1u : CF == kCol16 ? 2u : 4u);  // (kRec16: 16 bytes per 4 entries)
+    if constexpr (has_headers(CF)) cs.hdrp = cols.hdrp + (kb >> 2);
     const T *valp = val + kb;
     if constexpr (REG) {
         Unit<T, SB * CH> A, B;
@@ -397,12 +431,15 @@ __device__ const col12::Table k_col12_table = col12::make_table();
 // sends phase p to the body that computes its row offsets (L != 0) or to the one that loads them.  A kernel of its own and not
 // a fourth body beside the other three: the bodies' registers add up (one body of the f32 headline kernel takes 76-82 VGPRs,
 // the three of the other form all 128, a fourth spilled 92 bytes per lane), and these two take 97.
+// kRec16 exists in the REGK form alone (91 VGPRs on the headline shape, no scratch in any instantiation): the three bodies of the
+// other form spill with it in the DOT instantiations, so a plan that does not take the REGK kernel is not offered the records.
 template <typename T, int LANES, int CH, int CF, int RING, bool DOT = false, bool REGK = false>
 __global__ void __launch_bounds__((Ring2Cfg<T, RING>::kThreads), (Ring2Cfg<T, RING>::kWavesPerSimd))
 k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const uint16_t *__restrict__ col16, RingCol12 c12,
              const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, uint32_t nnz_lim, uint64_t last_chunk,
              const uint32_t *__restrict__ phase_ptr, const RingPhase *__restrict__ phases, uint32_t bands,
              T *__restrict__ dot_partials, uint32_t lb0, uint32_t lb_n, const uint32_t *__restrict__ reg_len) {
+    static_assert(CF != kRec16 || REGK, "the chunk records are streamed by the REGK form only");
     T dacc_v = T(0);
     T *dacc = DOT ? &dacc_v : nullptr;
     extern __shared__ __attribute__((aligned(16))) unsigned char ring_raw[];  // RING * sizeof(T) (kCol12: + the triple table), dynamic
@@ -420,14 +457,14 @@ k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t p0 = phase_ptr[lb], p1 = phase_ptr[lb + 1];
-    ColStream ring_cols = {CF == kCol16 ? (const void *)col16 : (const void *)col, nullptr, nullptr, nullptr};
-    const ColStream wide_cols = {col, nullptr, nullptr, nullptr};
-    if constexpr (CF == kCol12) {
+    ColStream ring_cols = {CF == kCol16 ? (const void *)col16 : (const void *)col, nullptr, nullptr, nullptr, 0.0f};
+    const ColStream wide_cols = {col, nullptr, nullptr, nullptr, 0.0f};
+    if constexpr (has_headers(CF)) {
         static_assert(kRing2Threads * sizeof(uint32_t) == sizeof(col12::Table), "one dword of the table per thread");
         uint16_t *table = reinterpret_cast<uint16_t *>(ring_raw + (size_t)RING * sizeof(T));
         reinterpret_cast<uint32_t *>(table)[threadIdx.x] = reinterpret_cast<const uint32_t *>(k_col12_table.e)[threadIdx.x];
         __syncthreads();
-        ring_cols = {c12.lo8, c12.hdr, table, reinterpret_cast<const u32x2 *>(c12.escapes)};
+        ring_cols = {CF == kRec16 ? (const void *)c12.rec16 : (const void *)c12.lo8, c12.hdr, table, reinterpret_cast<const u32x2 *>(c12.escapes), c12.scale};
     }
     for (uint32_t p = p0; p < p1; ++p) {
         const RingPhase ph = phases[p];
@@ -646,6 +683,97 @@ int launch_col12_encode(const uint32_t *col, size_t nnz, const uint32_t *jobs, s
     return SMH_OK;
 }
 
+// ---- the chunk records of the 24-bit value code (ring_val24.hpp), built once per matrix and set of values ----
+// The values of a chunk (entries past nnz count as +0, like the padding of an owned array)
+__device__ __forceinline__ void val24_chunk_values(const float *__restrict__ val, uint64_t nnz, uint64_t c, float (&v)[4]) {
+    if (4u * c + 3u < nnz) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(val + 4u * c);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = 4u * c + q < nnz ? val[4u * c + q] : 0.0f;
+    }
+}
+
+// The counting pass over the jobs' chunks (k_col12_jobs): stats[0] = min over the non-zero values of 1024 + the exponent of the
+// value's lowest set mantissa bit (from ~0u) -- the largest E all of them are multiples of 2^E for; stats[1] != 0: some value is
+// NaN, +-Inf, -0.0 or subnormal
+__global__ void __launch_bounds__(kBlock)
+k_val24_count(const float *__restrict__ val, uint64_t nnz, const u32x2 *__restrict__ jobs, uint32_t n_jobs, uint32_t *__restrict__ stats) {
+    uint32_t lowest = ~0u, bad = 0u;
+    for (uint32_t job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+        const u32x2 range = jobs[job];
+        for (uint64_t c = (uint64_t)range.x + threadIdx.x; c < range.y; c += kBlock) {
+            float v[4];
+            val24_chunk_values(val, nnz, c, v);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t bits = val24::float_bits(v[q]);
+                if (val24::never_fits(bits)) bad = 1u;
+                else if (bits != 0u) {
+                    const uint32_t e = (uint32_t)(1024 + val24::lowest_bit_exponent(bits));
+                    lowest = e < lowest ? e : lowest;
+                }
+            }
+        }
+    }
+    if (lowest != ~0u) atomicMin(&stats[0], lowest);
+    if (bad) atomicOr(&stats[1], 1u);
+}
+
+// The records of the jobs' chunks: {three dwords of 24-bit integers, the chunk's dword of lo8}.  *misses += the values that do not
+// come back bit for bit from what was written for them (they are written as 0): the form is only taken when there is none.
+__global__ void __launch_bounds__(kBlock)
+k_val24_encode(const float *__restrict__ val, uint64_t nnz, const u32x2 *__restrict__ jobs, uint32_t n_jobs, const uint32_t *__restrict__ lo,
+               int E, u32x4 *__restrict__ rec, unsigned long long *__restrict__ misses) {
+    unsigned long long mine = 0;
+    for (uint32_t job = blockIdx.x; job < n_jobs; job += gridDim.x) {
+        const u32x2 range = jobs[job];
+        for (uint64_t c = (uint64_t)range.x + threadIdx.x; c < range.y; c += kBlock) {
+            float v[4];
+            val24_chunk_values(val, nnz, c, v);
+            int32_t k[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                k[q] = 0;
+                if (!val24::encode(v[q], E, &k[q])) ++mine;
+            }
+            uint32_t w[3];
+            val24::pack(k, w);
+            rec[c] = u32x4{w[0], w[1], w[2], lo[c]};
+        }
+    }
+    if (mine) atomicAdd(misses, mine);
+}
+
+int launch_val24_count(const uint32_t *off, const float *val, size_t nnz, const RingPhase *phases, size_t n_phases, uint32_t *jobs,
+                       unsigned long long *counts, uint32_t *stats, hipStream_t s) {
+    SMH_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s));
+    SMH_HIP(hipMemsetAsync(stats, 0xFF, sizeof(uint32_t), s));
+    SMH_HIP(hipMemsetAsync(stats + 1, 0, sizeof(uint32_t), s));
+    if (n_phases == 0) return SMH_OK;
+    hipLaunchKernelGGL(k_col12_jobs, dim3((unsigned)((n_phases + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, off, phases, (uint32_t)n_phases,
+                       reinterpret_cast<u32x2 *>(jobs), counts);
+    SMH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_val24_count, dim3((unsigned)(n_phases < 8192 ? n_phases : 8192)), dim3(kBlock), 0, s, val, (uint64_t)nnz,
+                       reinterpret_cast<const u32x2 *>(jobs), (uint32_t)n_phases, stats);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
+int launch_val24_encode(const float *val, size_t nnz, const uint32_t *jobs, size_t n_phases, size_t n_chunks_out, const uint8_t *lo8, int exponent,
+                        uint32_t *rec16, unsigned long long *misses, hipStream_t s) {
+    // chunks no ring phase streams, and the padding: all zero, i.e. four values +0 over the low bytes lo8 has there
+    SMH_HIP(hipMemsetAsync(rec16, 0, n_chunks_out * 16, s));
+    SMH_HIP(hipMemsetAsync(misses, 0, sizeof(unsigned long long), s));
+    if (n_phases == 0) return SMH_OK;
+    hipLaunchKernelGGL(k_val24_encode, dim3((unsigned)(n_phases < 8192 ? n_phases : 8192)), dim3(kBlock), 0, s, val, (uint64_t)nnz,
+                       reinterpret_cast<const u32x2 *>(jobs), (uint32_t)n_phases, reinterpret_cast<const uint32_t *>(lo8), exponent,
+                       reinterpret_cast<u32x4 *>(rec16), misses);
+    SMH_HIP(hipGetLastError());
+    return SMH_OK;
+}
+
 // dot_partials != NULL: the DOT form -- `y` is lhs (read only), dot_partials[0..n_blocks] receive the blocks' shares of
 // lhs . (A x) plus, in slot n_blocks, that of an unpadded array's last partial chunk
 template <typename T, int RING>
@@ -655,7 +783,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
                           unsigned block_begin, unsigned block_end, const uint32_t *reg_len) {
     if (bands == 4u && !col16) return fail(SMH_ERR_INVALID, "banded ring plan without the 16-bit slot array");
     constexpr bool kHasCol12 = std::is_same<T, float>::value && RING == (int)col12::kSlots;  // the compact form's only instantiation
-    if (c12.lo8 && (!kHasCol12 || bands != 1u || !c12.hdr || !c12.escapes))
+    if ((c12.lo8 || c12.rec16) && (!kHasCol12 || bands != 1u || !c12.hdr || !c12.escapes))
         return fail(SMH_ERR_INVALID, "ring kernel: the compact column form is for f32 on the single-window ring of 16384 columns");
     // the plan's row ranges [lb0, lb1) (default: all of them)
     const unsigned lb0 = block_begin < n_blocks ? block_begin : n_blocks, lb1 = block_end < n_blocks ? block_end : n_blocks;
@@ -675,7 +803,7 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
         // dynamic LDS above 64 KiB must be allowed per kernel (idempotent, cheap)
 #define SMH_R2_LAUNCH2(L, C, N, D, R)                                                                                    \
     do {                                                                                                                 \
-        constexpr size_t lds_bytes = ring_bytes + ((N) == kCol12 ? sizeof(col12::Table) : 0);                            \
+        constexpr size_t lds_bytes = ring_bytes + (has_headers(N) ? sizeof(col12::Table) : 0);                           \
         /* once per (instantiation, DEVICE): function attributes are per device, and smh_par_* places blocks on       \
            several devices.  Bit d of the mask = device d has the opt-in; a second thread racing on the same bit only   \
            repeats an idempotent call.  (Set by the first launch, so never inside a later stream capture.) */          \
@@ -701,7 +829,10 @@ static int launch_ring2_t(int lanes, int chunks, const uint32_t *off, const uint
     } while (0)
 #define SMH_R2_LAUNCH(L, C)                                                   \
     do {                                                                      \
-        if (c12.lo8) {                                                        \
+        if (c12.rec16) { /* (the REGK form only: see k_spmv_ring2) */         \
+            if (!reg_len) return fail(SMH_ERR_INVALID, "ring kernel: the chunk records go with the table of regular phases"); \
+            if constexpr (kHasCol12) SMH_R2_LAUNCH1(L, C, kRec16, true);      \
+        } else if (c12.lo8) {                                                 \
             if constexpr (kHasCol12) SMH_R2_LAUNCH0(L, C, kCol12);            \
         } else if (col16) SMH_R2_LAUNCH0(L, C, kCol16);                       \
         else SMH_R2_LAUNCH1(L, C, kColU32, false);                            \

@@ -699,6 +699,14 @@ class SparseMatCRS:
         check(lib().smh_crs_ring_column_form(self._h, C.byref(out)))
         return ("u32", "col16", "col12")[out.value]
 
+    def ring_value_form(self):
+        """What K1r's ring phases stream for their values under the current settings: ("val24", E) -- 24-bit fixed-point values
+        k * 2^E in 16-byte chunk records, taken with the compact column form when every value fits --, ("plain", None) -- the value
+        array --, or ("refused", None): the value array, the matrix was tested and some value does not fit."""
+        form, exp = C.c_int(), C.c_int()
+        check(lib().smh_crs_ring_values(self._h, C.byref(form), C.byref(exp)))
+        return ("val24", exp.value) if form.value == 1 else ("refused" if form.value < 0 else "plain", None)
+
     def ring_bands(self, intervals=False):
         """1 (one sliding window) or 4 (banded ring); with ``intervals`` also the per-tile column intervals
         [n_tiles64, 4, 2] of a banded plan (None otherwise)."""
