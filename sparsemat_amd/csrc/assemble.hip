@@ -28,7 +28,7 @@
 // one segmented stable sort by column over the CRS offsets.
 // The same pipeline serves streams replayed on a SparseMatCRS itself (smh_crs_replay, transpose, prod: `reverse_rows`
 // emits every row's list backwards because push inserts at the row's start, sparsemat_crs.rs:85-87; the container's
-// first-push quirk is resolved by the caller from the first two operations, capi.hip), with two shortcuts for
+// first-push quirk is resolved by the caller from the first two operations, assemble_common), with two shortcuts for
 // transpose: `all_set` (no ops array) and `repeats_adjacent` (no (row, column) pair repeats -> the sorted operations
 // ARE the entries: k_asm_direct_emit).  Row expansion (k_expand_rows), the column tables of
 // ColumnIter::assemble_column_info (one stable sort of the entry indices by column) and append_to_row (the twin entry
@@ -38,7 +38,8 @@
 
 #include <chrono>
 
-#include "internal.hpp"
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -550,7 +551,7 @@ static int assemble_t(uint64_t n, const uint32_t *rows, const uint32_t *cols, co
 // all_set: every operation is `set` (ops ignored).  repeats_adjacent: the caller guarantees that operations on the same (row,
 // column) are neighbours in the row's list (transpose) -- streams without any repeat then skip the replay.
 // reverse_rows: every row in REVERSE order of first appearance -- the layout the same stream leaves in a SparseMatCRS, whose push
-// inserts at the start of the row (sparsemat_crs.rs:85-87); the first-push quirk is the caller's business (capi.hip).
+// inserts at the start of the row (sparsemat_crs.rs:85-87); the first-push quirk is the caller's business (assemble_common).
 int assemble_triplets(int dtype, size_t n, const uint32_t *rows, const uint32_t *cols, const void *vals, const uint8_t *ops,
                       bool reverse_rows, bool all_set, bool repeats_adjacent, size_t *n_rows_out, size_t *n_cols_out, size_t *nnz_out,
                       uint32_t **off_out, uint32_t **col_out,
@@ -644,7 +645,7 @@ k_bump_offsets(uint32_t *__restrict__ off, uint64_t first, uint64_t last) {  // 
 
 // One more entry at the END of row `row` (new arrays, the old ones are freed): the place the first-push quirk of a
 // SparseMatCRS leaves the first operation's entry in when the second operation names the same (row, column)
-// (sparsemat_crs.rs:75-81; capi.hip::assemble_common).
+// (sparsemat_crs.rs:75-81; assemble_common).
 int append_to_row(int dtype, uint32_t *off, uint32_t **col, void **val, size_t n_rows, size_t *nnz, size_t row, uint32_t column,
                   const void *value_host, hipStream_t s) {
     const size_t vs = dtype_size(dtype), n = *nnz;
@@ -711,4 +712,105 @@ int column_info(const uint32_t *off, const uint32_t *col, size_t n_rows, size_t 
     return SMH_OK;
 }
 
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+// add_to / set stream -> CRS.  `on_device`: the arrays are device pointers.
+// into_crs: the stream is replayed on a SparseMatCRS instead of a SparseMatIndexList + to_crs(): rows come out in reverse order
+// of first appearance (push prepends, sparsemat_crs.rs:85-87) and the container's first-push quirk applies (:75-81: the first push
+// leaves n_rows == 0, so the second operation never finds an entry):
+//   * second row <  first row: Vec::resize truncates offset_rows and the first entry is orphaned -- it stays in columns / values
+//     (and in n_cols) but no row reaches it; the result is the replay of operations 1.. alone.  Orphans are not materialised here;
+//   * second (row, column) == first: the first operation keeps an entry of its own, the oldest of its row (= last in storage);
+//   * a single operation: no rows at all (n_rows stays 0), one orphan.
+int assemble_common(smh_dtype dtype, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values,
+                    const uint8_t *ops, bool on_device, bool into_crs, smh_crs **out, bool transposing) {
+    // transposing: every operation is `set` (ops unused) and repeats of a (row, column) pair are neighbours in the row's list
+    if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
+    if (dtype != SMH_F32 && dtype != SMH_F64) return fail(SMH_ERR_INVALID, "unknown dtype %d", (int)dtype);
+    if (n_ops && (!rows || !cols || !values)) return fail(SMH_ERR_INVALID, "NULL operation array");
+    if (n_ops >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    SMH_TRY(require_device());
+    const size_t vs = dtype_size(dtype);
+    // the first two operations decide the SparseMatCRS quirk
+    size_t skip = 0, min_cols = 0, orphans = 0;
+    bool twin = false;
+    uint32_t r01[2] = {0, 0}, c01[2] = {0, 0};
+    double v0 = 0.0;  // (holds an f32 or an f64 bit pattern)
+    uint8_t op0 = 0;
+    auto fold_v0 = [&]() {  // push(i, j, zero) then `=` or `+=` (sparsematrix.rs:226-233)
+        if (op0) return;
+        if (dtype == SMH_F64) { double v; memcpy(&v, &v0, 8); v = 0.0 + v; memcpy(&v0, &v, 8); }
+        else { float v; memcpy(&v, &v0, 4); v = 0.0f + v; memcpy(&v0, &v, 4); }
+    };
+    if (into_crs && n_ops) {
+        const size_t k = n_ops < 2 ? n_ops : 2;
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+        SMH_HIP(hipMemcpy(r01, rows, k * sizeof(uint32_t), kind));
+        SMH_HIP(hipMemcpy(c01, cols, k * sizeof(uint32_t), kind));
+        SMH_HIP(hipMemcpy(&v0, values, vs, kind));
+        if (transposing) op0 = 1;
+        else if (ops) SMH_HIP(hipMemcpy(&op0, ops, 1, kind));
+        if (n_ops == 1) { fold_v0(); orphans = 1; }
+        else if (r01[1] < r01[0]) { skip = 1; min_cols = (size_t)c01[0] + 1; orphans = 1; }
+        else if (r01[1] == r01[0] && c01[1] == c01[0]) { skip = 1; twin = true; }
+    }
+    ArgStage st(on_device, ArgStage::kUnchecked);  // known difference, kept: no device check, no device-wide synchronisation
+    CrsArrays arrays;
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    const bool single = into_crs && n_ops == 1;
+    if (n_ops == 0 || single) {  // SparseMatCRS::new() (sparsemat_crs.rs:47-49): no rows at all
+        SMH_TRY(arrays.alloc(0, 0, vs));
+        SMH_HIP(hipMemset(arrays.off, 0, sizeof(uint32_t)));
+        n_cols = single ? (size_t)c01[0] + 1 : 0;
+    } else {
+        const void *d_rows = nullptr, *d_cols = nullptr, *d_vals = nullptr, *d_ops = nullptr;
+        SMH_TRY(st.in(rows, n_ops * sizeof(uint32_t), "rows", &d_rows));
+        SMH_TRY(st.in(cols, n_ops * sizeof(uint32_t), "cols", &d_cols));
+        SMH_TRY(st.in(values, n_ops * vs, "values", &d_vals));
+        SMH_TRY(st.in(ops, n_ops, "ops", &d_ops));
+        SMH_TRY(assemble_triplets(dtype, n_ops - skip, (const uint32_t *)d_rows + skip, (const uint32_t *)d_cols + skip, (const char *)d_vals + skip * vs,
+                                  d_ops ? (const uint8_t *)d_ops + skip : nullptr, into_crs, transposing, transposing, &n_rows, &n_cols, &nnz,
+                                  &arrays.off, &arrays.col, &arrays.val, nullptr));
+        if (min_cols > n_cols) n_cols = min_cols;
+        if (twin) {  // the first operation's own entry
+            fold_v0();
+            SMH_TRY(append_to_row(dtype, arrays.off, &arrays.col, &arrays.val, n_rows, &nnz, r01[0], c01[0], &v0, nullptr));
+        }
+    }
+    SMH_TRY(wrap_arrays(dtype, nullptr, n_rows, n_cols, nnz, arrays, 0, out));
+    (*out)->orphans = orphans;
+    if (single) {  // push(i, j, zero) then `=` or `+=`: kept on the handle so that smh_crs_apply can continue the replay; nothing else reads it
+        (*out)->has_first_op = true;
+        (*out)->first_row = r01[0];
+        (*out)->first_col = c01[0];
+        memcpy(&(*out)->first_val_bits, &v0, 8);
+    }
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_crs_assemble(smh_dtype dtype, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values,
+                     const uint8_t *ops, smh_crs **out) {
+    return assemble_common(dtype, n_ops, rows, cols, values, ops, false, false, out);
+}
+
+int smh_crs_assemble_dev(smh_dtype dtype, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev,
+                         const void *values_dev, const uint8_t *ops_dev, smh_crs **out) {
+    return assemble_common(dtype, n_ops, rows_dev, cols_dev, values_dev, ops_dev, true, false, out);
+}
+
+int smh_crs_replay(smh_dtype dtype, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values,
+                   const uint8_t *ops, smh_crs **out) {
+    return assemble_common(dtype, n_ops, rows, cols, values, ops, false, true, out);
+}
+
+int smh_crs_replay_dev(smh_dtype dtype, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev,
+                       const void *values_dev, const uint8_t *ops_dev, smh_crs **out) {
+    return assemble_common(dtype, n_ops, rows_dev, cols_dev, values_dev, ops_dev, true, true, out);
+}
+
+}  // extern "C"

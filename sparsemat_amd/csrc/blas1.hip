@@ -14,8 +14,10 @@
 // CPU model of it, tests/blas1_model.py, through every public entry point: tests/test_blas1_bits_gpu.py.)
 //
 // Aliasing: a thread of k_ew reads y[i] and writes x[i], nothing else -- x and y are the same array or disjoint over the n
-// entries of a launch.  The entry points refuse two ranges that overlap in part (ew_check_overlap, capi.hip).
-#include "internal.hpp"
+// entries of a launch.  The entry points refuse two ranges that overlap in part (ew_check_overlap, with the entry points below).
+#include <cmath>
+
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -290,4 +292,111 @@ int launch_crs_stats(const uint32_t *off, const uint32_t *col, size_t n_rows, si
     return SMH_OK;
 }
 
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+// The element-wise kernels (k_ew) read y[i] and write x[i] in the same thread and know nothing about any other thread's
+// entries: over the n entries they touch, x and y are the same array or disjoint.  Two ranges that overlap IN PART would make thread i
+// read what thread i +- k writes -- a result that depends on scheduling -- so they are refused before anything is launched.
+static int ew_check_overlap(const void *x, const void *y, size_t n, int dtype, const char *what) {
+    const size_t bytes = n * dtype_size(dtype);
+    const char *px = (const char *)x, *py = (const char *)y;
+    if (px != py && px < py + bytes && py < px + bytes) return fail(SMH_ERR_INVALID, "%s: x and y overlap in part", what);
+    return SMH_OK;
+}
+
+// scratch for reductions of the vector API: per thread, per device
+struct ReduceBuffer { void *d = nullptr; int device = -1; };
+static thread_local ReduceBuffer g_red;
+int reduce_scratch(void **out) {
+    const int dev = current_device();
+    if (!g_red.d || g_red.device != dev) {
+        // (a scratch left on another device is intentionally leaked: handles are device-bound)
+        SMH_HIP(hipMalloc(&g_red.d, (kReducePartials + 8) * sizeof(double)));
+        g_red.device = dev;
+    }
+    *out = g_red.d;
+    return SMH_OK;
+}
+
+static int vec_ew(Ew op, smh_vec *x, const smh_vec *y, double a, const char *what) {
+    SMH_TRY(vec_check_pair(x, y));
+    // densevec.rs:52-54 / :61-63: panic iff self.dim() < rhs.dim(); zip() covers rhs.dim() entries
+    if (x->n < y->n) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    SMH_TRY(ew_check_overlap(x->d, y->d, y->n, x->dtype, what));  // (the same storage, x.add(x), is legal: every thread its own entry)
+    SMH_TRY(launch_ew(x->dtype, op, x->d, y->d, y->n, a, nullptr, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_vec_add(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Add, x, y, 0.0, "smh_vec_add"); }
+int smh_vec_sub(smh_vec *x, const smh_vec *y) { return vec_ew(Ew::Sub, x, y, 0.0, "smh_vec_sub"); }
+int smh_vec_axpy(smh_vec *y, double a, const smh_vec *x) { return vec_ew(Ew::Axpy, y, x, a, "smh_vec_axpy"); }
+int smh_vec_xpby(smh_vec *p, double b, const smh_vec *r) { return vec_ew(Ew::Xpby, p, r, b, "smh_vec_xpby"); }
+
+int smh_vec_scale(smh_vec *x, double a) {
+    if (!x) return fail(SMH_ERR_INVALID, "NULL vector handle");
+    SMH_TRY(launch_ew(x->dtype, Ew::Scale, x->d, nullptr, x->n, a, nullptr, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return SMH_OK;
+}
+
+int smh_vec_dot(const smh_vec *x, const smh_vec *y, double *out) {
+    SMH_TRY(vec_check_pair(x, y));
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    const size_t n = x->n < y->n ? x->n : y->n;  // zip truncates (vector.rs:52)
+    void *scratch = nullptr;
+    SMH_TRY(reduce_scratch(&scratch));
+    char *res = (char *)scratch + kReducePartials * sizeof(double);
+    SMH_TRY(launch_dot(x->dtype, x->d, y->d, n, scratch, res, nullptr));
+    if (x->dtype == SMH_F64) {
+        double h = 0;
+        SMH_HIP(hipMemcpy(&h, res, sizeof h, hipMemcpyDeviceToHost));
+        *out = h;
+    } else {
+        float h = 0;
+        SMH_HIP(hipMemcpy(&h, res, sizeof h, hipMemcpyDeviceToHost));
+        *out = (double)h;
+    }
+    return SMH_OK;
+}
+
+int smh_vec_norm_squared(const smh_vec *x, double *out) { return smh_vec_dot(x, x, out); }
+
+int smh_vec_norm(const smh_vec *x, double *out) {
+    SMH_TRY(smh_vec_norm_squared(x, out));
+    *out = std::sqrt(*out);  // f64::sqrt(self.norm_squared().into())  vector.rs:61-63
+    return SMH_OK;
+}
+
+// ---- BLAS-1 on raw device pointers with DEVICE-resident scalars (asynchronous) ------------------------
+// Building blocks of a solver whose scalars never visit the host (the multi-GPU CG all-reduces them on
+// the device between these calls).
+int smh_blas_dot_dev(smh_dtype dtype, const void *x_dev, const void *y_dev, size_t n, void *result_dev,
+                     void *scratch_dev, void *stream) {
+    if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
+    if (!result_dev || !scratch_dev || (n && (!x_dev || !y_dev))) return fail(SMH_ERR_INVALID, "NULL device pointer");
+    return launch_dot(dtype, x_dev, y_dev, n, scratch_dev, result_dev, (hipStream_t)stream);
+}
+
+size_t smh_blas_dot_scratch_bytes(void) { return (size_t)(kReducePartials + 8) * sizeof(double); }
+
+int smh_blas_axpy_dev(smh_dtype dtype, void *y_dev, const void *a_dev, const void *x_dev, size_t n, void *stream) {
+    if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
+    if (!a_dev || (n && (!x_dev || !y_dev))) return fail(SMH_ERR_INVALID, "NULL device pointer");
+    SMH_TRY(ew_check_overlap(y_dev, x_dev, n, dtype, "smh_blas_axpy_dev"));
+    return launch_ew(dtype, Ew::Axpy, y_dev, x_dev, n, 0.0, a_dev, (hipStream_t)stream);
+}
+
+int smh_blas_xpby_dev(smh_dtype dtype, void *p_dev, const void *b_dev, const void *r_dev, size_t n, void *stream) {
+    if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
+    if (!b_dev || (n && (!p_dev || !r_dev))) return fail(SMH_ERR_INVALID, "NULL device pointer");
+    SMH_TRY(ew_check_overlap(p_dev, r_dev, n, dtype, "smh_blas_xpby_dev"));
+    return launch_ew(dtype, Ew::Xpby, p_dev, r_dev, n, 0.0, b_dev, (hipStream_t)stream);
+}
+
+}  // extern "C"

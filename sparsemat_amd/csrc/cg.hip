@@ -308,7 +308,7 @@ void cg_read_scalars(int dtype, const void *host_copy, int *converged, uint64_t 
 }
 
 // ConjugateGradient::solve (linearsolver.rs:27-61) on device vectors, on the handle's stream; the argument checks (:30-36) are the
-// entry point's (capi.hip).  check_every: bodies per poll.
+// entry point's (smh_cg_solve_vec, below).  check_every: bodies per poll.
 template <typename T>
 static int cg_solve_t(smh_crs *m, const T *b, T *x, double tol, size_t iter_max, int variant, size_t check_every, size_t *iters_out, double *rr_out) {
     const size_t n = m->n_rows;
@@ -412,3 +412,30 @@ int cg_par_p(int dtype, const void *sc_in, void *sc_out, const void *rr_vals, ui
 }
 
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+// ---- ConjugateGradient: the entry points -----------------------------------------------------------------------------------------
+// The statuses are decided by check_solve_vec / check_solve_host (solver_host.hpp), before any launch.
+int smh_cg_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, int variant,
+                     size_t check_every, size_t *iters_out, double *rr_out) {
+    SMH_TRY(check_solve_vec(m, b, x, "dtype mismatch", /*refuse_aliased*/ false, &check_every, kCgCheckEvery));
+    return cg_solve(m, b, x, tol, iter_max, variant, check_every, iters_out, rr_out);
+}
+
+int smh_cg_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_inout, size_t x_len, double tol,
+                 size_t iter_max, int variant, size_t *iters_out, double *rr_out) {
+    SMH_TRY(check_solve_host(m, b_host, b_len, x_host_inout, x_len, /*null_vectors*/ false, /*refuse_aliased*/ false));
+    smh_vec *b = nullptr, *x = nullptr;
+    int rc = smh_vec_from_host((smh_dtype)m->dtype, b_len, b_host, &b);
+    if (rc == SMH_OK) rc = smh_vec_from_host((smh_dtype)m->dtype, x_len, x_host_inout, &x);
+    if (rc == SMH_OK) rc = smh_cg_solve_vec(m, b, x, tol, iter_max, variant, 0, iters_out, rr_out);
+    if (rc == SMH_OK) rc = smh_vec_download(x, x_host_inout);
+    smh_vec_destroy(b);
+    smh_vec_destroy(x);
+    return rc;
+}
+
+}  // extern "C"

@@ -269,3 +269,33 @@ int cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, size_t
 }
 
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+// ---- the entry points: ConjugateGradient on k right-hand sides at once -------------------------------------------------------------
+int smh_cg_solve_many(smh_crs *m, const smh_mvec *b, smh_mvec *x, double tol, size_t iter_max, size_t check_every, size_t *iters_out,
+                      double *rr_out) {
+    if (!m || !b || !x) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
+    SMH_TRY(check_solve_vec(m, b, x, "multi-vector dtype differs from the matrix's", /*refuse_aliased*/ true, &check_every, kCgCheckEvery));
+    return cg_solve_many(m, b, x, tol, iter_max, check_every, iters_out, rr_out);
+}
+
+int smh_cg_solve_many_host(smh_crs *m, const void *b_host, size_t n, size_t k, void *x_host_inout, double tol, size_t iter_max,
+                           size_t *iters_out, double *rr_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (!iters_out || !rr_out) return fail(SMH_ERR_INVALID, "NULL output array");
+    SMH_TRY(check_solve_host(m, b_host, n, x_host_inout, n, /*null_vectors*/ true, /*refuse_aliased*/ false));
+    smh_mvec *b = nullptr, *x = nullptr;
+    int rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, b_host, &b);
+    if (rc == SMH_OK) rc = smh_mvec_from_host((smh_dtype)m->dtype, n, k, x_host_inout, &x);
+    if (rc == SMH_OK) rc = smh_cg_solve_many(m, b, x, tol, iter_max, 0, iters_out, rr_out);
+    if (rc == SMH_OK && n) rc = smh_mvec_download(x, x_host_inout);
+    smh_mvec_destroy(b);
+    smh_mvec_destroy(x);
+    return rc;
+}
+
+}  // extern "C"

@@ -36,7 +36,7 @@
 #include <chrono>
 #include <cstdlib>
 
-#include "internal.hpp"
+#include "arg_stage.hpp"
 
 namespace smh {
 
@@ -295,4 +295,38 @@ int color_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, 
     return SMH_OK;
 }
 
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+static int color_common(const smh_crs *m, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors_out, size_t *n_rounds_out,
+                        bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    SMH_TRY(columns_within_n_cols(m, "color"));
+    const size_t n = m->n_rows;
+    ArgStage st(on_device, m->device);
+    void *d_colors = nullptr, *d_perm = nullptr;  // (either may be NULL: that output is not wanted)
+    SMH_TRY(st.out(colors_out, n * sizeof(uint32_t), "colors_out", &d_colors));
+    SMH_TRY(st.out(perm_out, n * sizeof(uint32_t), "perm_out", &d_perm));
+    SMH_TRY(st.callers_writes_first());
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    size_t colors = 0, rounds = 0;
+    SMH_TRY(color_order(m->d_off, m->d_col, n, m->nnz, seed, (uint32_t *)d_colors, (uint32_t *)d_perm, &colors, &rounds, m->stream));
+    SMH_TRY(st.finish());
+    if (n_colors_out) *n_colors_out = colors;
+    if (n_rounds_out) *n_rounds_out = rounds;
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_crs_color(const smh_crs *m, uint32_t seed, uint32_t *colors_out, uint32_t *perm_out, size_t *n_colors_out, size_t *n_rounds_out) {
+    return color_common(m, seed, colors_out, perm_out, n_colors_out, n_rounds_out, false);
+}
+int smh_crs_color_dev(const smh_crs *m, uint32_t seed, uint32_t *colors_out_dev, uint32_t *perm_out_dev, size_t *n_colors_out, size_t *n_rounds_out) {
+    return color_common(m, seed, colors_out_dev, perm_out_dev, n_colors_out, n_rounds_out, true);
+}
+
+}  // extern "C"

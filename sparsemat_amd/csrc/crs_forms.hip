@@ -599,3 +599,258 @@ int recode_stream(smh_crs *m) {
 }
 
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+// ---- the entry points: the knobs of the derived forms and what they let a caller see ---------------------------------------------
+int smh_crs_span_fraction(smh_crs *m, double *out) {
+    if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m, false));  // the locality statistic is taken with the K1r inspector
+    *out = m->span_fraction;
+    return SMH_OK;
+}
+
+int smh_crs_tiled_layout(smh_crs *m, uint32_t *n_slices_out, uint32_t *slice_columns_out, uint32_t *rows_per_block_out, uint32_t *n_row_blocks_out,
+                         size_t *copy_entries_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(tiled_build(m));
+    if (n_slices_out) *n_slices_out = m->tiled.n_cb;
+    if (slice_columns_out) *slice_columns_out = tiled_slice_columns(m->dtype);
+    if (rows_per_block_out) *rows_per_block_out = m->tiled.R;
+    if (n_row_blocks_out) *n_row_blocks_out = m->tiled.n_rb;
+    if (copy_entries_out) *copy_entries_out = (size_t)m->tiled.tot;
+    return SMH_OK;
+}
+
+int smh_crs_tiled_products(smh_crs *m, size_t *n_products_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(tiled_build(m));
+    if (n_products_out) *n_products_out = (size_t)m->tiled.n_prod;
+    return SMH_OK;
+}
+
+int smh_crs_tiled_array(smh_crs *m, int which, void *out, size_t capacity_bytes, size_t *bytes_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(tiled_build(m));
+    return tiled_array(m, which, out, capacity_bytes, bytes_out);
+}
+
+int smh_crs_set_colblock_shift(smh_crs *m, uint32_t shift) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (shift > 31) return fail(SMH_ERR_INVALID, "column block shift must be 0 (automatic) or 1..31");
+    if (shift != m->knobs.cb_forced_shift) invalidate(m, Changed::BlockWidth);
+    m->knobs.cb_forced_shift = shift;
+    return SMH_OK;
+}
+
+int smh_crs_colblock(smh_crs *m, uint32_t *shift_out, size_t *n_blocks_out, int *rows_per_thread_out,
+                     double *span_fraction_out, uint32_t *offsets_out, uint32_t *columns_out, void *values_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(ensure_ring_plan(m, false));  // the locality statistic
+    SMH_TRY(ensure_colblock(m));
+    if (shift_out) *shift_out = m->cb.shift;
+    if (n_blocks_out) *n_blocks_out = m->cb.blocks;
+    if (rows_per_thread_out) *rows_per_thread_out = m->cb.rpt;
+    if (span_fraction_out) *span_fraction_out = m->span_fraction;
+    if (offsets_out)
+        SMH_HIP(hipMemcpy(offsets_out, m->cb.off.get(), m->cb.blocks * (m->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->cb.col.get(), m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->cb.val.get(), m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_colfused(smh_crs *m, int *fits_out, uint32_t *shift_out, size_t *n_blocks_out, uint32_t *rows_per_lane_out,
+                     size_t *n_tiles_out, uint32_t *tile_rows_out, uint32_t *segments_out, uint8_t *counts_out, uint32_t *columns_out,
+                     void *values_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(ensure_colfused(m));
+    const size_t tile_rows = (size_t)64 * m->cf.rt, n_tiles = (m->cf.state == Form::Ready) ? m->cf.tiles : 0;
+    if (fits_out) *fits_out = (m->cf.state == Form::Ready) ? 1 : 0;
+    if (shift_out) *shift_out = m->cf.shift;
+    if (n_blocks_out) *n_blocks_out = m->cf.blocks;
+    if (rows_per_lane_out) *rows_per_lane_out = m->cf.rt;
+    if (n_tiles_out) *n_tiles_out = n_tiles;
+    if (m->cf.state != Form::Ready) return SMH_OK;
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    if (tile_rows_out) SMH_HIP(hipMemcpy(tile_rows_out, m->cf.tile_row.get(), (n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (segments_out) SMH_HIP(hipMemcpy(segments_out, m->cf.seg.get(), (n_tiles * m->cf.blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (counts_out && n_tiles) SMH_HIP(hipMemcpy(counts_out, m->cf.cnt.get(), n_tiles * m->cf.blocks * tile_rows, hipMemcpyDeviceToHost));
+    if (columns_out && m->nnz) SMH_HIP(hipMemcpy(columns_out, m->cf.col.get(), m->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (values_out && m->nnz) SMH_HIP(hipMemcpy(values_out, m->cf.val.get(), m->nnz * dtype_size(m->dtype), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_colsplit(smh_crs *m, int *split_out, uint32_t *min_long_out, size_t *n_long_out, uint32_t *long_rows_out, smh_crs **long_out,
+                     smh_crs **short_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(ensure_split(m));
+    const bool split = m->split.state == Form::Ready;
+    if (split_out) *split_out = split ? 1 : 0;
+    if (min_long_out) *min_long_out = kSplitMinLong;
+    if (n_long_out) *n_long_out = split ? m->split.n_long : 0;
+    if (long_out) *long_out = split ? m->split.long_part : nullptr;
+    if (short_out) *short_out = split ? m->split.short_part : nullptr;
+    if (long_rows_out && split && m->split.n_long)
+        SMH_HIP(hipMemcpy(long_rows_out, m->split.rows.get(), m->split.n_long * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_resolved_variant(const smh_crs *m, int *variant_out, int *lanes_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (variant_out) *variant_out = resolve_variant(m, SMH_SPMV_AUTO);
+    if (lanes_out) *lanes_out = auto_lanes(m);
+    return SMH_OK;
+}
+
+int smh_crs_set_stream_xs(smh_crs *m, int mode) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic), 0 (never) or 1 (whenever the tiles allow)");
+    m->knobs.use_stream_xs = mode;
+    return recode_stream(m);
+}
+
+int smh_crs_set_stream_direct(smh_crs *m, int mode) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic), 0 (never) or 1 (whenever x is staged)");
+    m->knobs.use_stream_direct = mode;
+    return recode_stream(m);
+}
+
+int smh_crs_stream_direct(smh_crs *m, int *direct_out) {
+    if (!m || !direct_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    StreamCfg c;
+    SMH_TRY(stream_cfg(m, &c));
+    *direct_out = c.direct && c.xs != 0;
+    return SMH_OK;
+}
+
+int smh_crs_stream_value_dict(smh_crs *m, int *n_values_out, void *values_out) {
+    if (!m || !n_values_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    StreamCfg c;
+    SMH_TRY(stream_cfg(m, &c));
+    *n_values_out = c.dict ? (int)m->dict.n : 0;
+    if (c.dict && values_out) {
+        SMH_HIP(hipMemcpyAsync(values_out, m->dict.values.get(), (size_t)m->dict.n * dtype_size(m->dtype), hipMemcpyDeviceToHost, m->stream));
+        SMH_HIP(hipStreamSynchronize(m->stream));
+    }
+    return SMH_OK;
+}
+
+int smh_crs_set_stream_value_dict(smh_crs *m, int mode) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (mode < -1 || mode > 0) return fail(SMH_ERR_INVALID, "mode must be -1 (automatic: whenever the values allow) or 0 (never)");
+    m->knobs.use_stream_vdict = mode;
+    return recode_stream(m);
+}
+
+int smh_crs_stream_layout(smh_crs *m, int *coded_out, int *byte_lengths_out, int *small_tiles_out, int *xs_chunks_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    StreamCfg c;
+    SMH_TRY(stream_cfg(m, &c));
+    if (coded_out) *coded_out = c.code && c.cwin;
+    if (byte_lengths_out) *byte_lengths_out = c.len8 && c.tbase;
+    if (small_tiles_out) *small_tiles_out = c.small;
+    if (xs_chunks_out) *xs_chunks_out = c.xs;
+    return SMH_OK;
+}
+
+int smh_crs_set_vector_chunks(smh_crs *m, int chunks) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (chunks < 0 || chunks > 3) return fail(SMH_ERR_INVALID, "chunks per lane must be 0 (automatic), 1, 2 or 3");
+    m->knobs.forced_chunks = chunks;
+    return SMH_OK;
+}
+
+int smh_crs_set_ring(smh_crs *m, int mode) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (mode < -1 || mode > 1) return fail(SMH_ERR_INVALID, "ring mode must be -1 (auto), 0 (plain K1) or 1 (K1r)");
+    m->knobs.use_ring = mode;
+    return SMH_OK;
+}
+
+int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out, double *ring_fraction_out,
+                      int *active_out, uint32_t *phase_ptr_out, uint32_t *phases_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(ensure_ring_plan(m));
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));
+    if (n_blocks_out) *n_blocks_out = m->ring.blocks;
+    if (n_phases_out) *n_phases_out = m->ring.n_phases;
+    if (ring_fraction_out) *ring_fraction_out = m->ring.fraction;
+    if (active_out) *active_out = ring ? 1 : 0;
+    if (phase_ptr_out)
+        SMH_HIP(hipMemcpy(phase_ptr_out, m->ring.phase_ptr.get(), (m->ring.blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (phases_out && m->ring.n_phases)
+        SMH_HIP(hipMemcpy(phases_out, m->ring.phases.get(), m->ring.n_phases * sizeof(RingPhase), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_ring_regular(smh_crs *m, uint32_t *len_out) {
+    if (!m || !len_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m));
+    if (m->ring.n_phases)
+        SMH_HIP(hipMemcpy(len_out, m->ring.reg_len.get(), m->ring.n_phases * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_ring_column_form(smh_crs *m, int *form_out) {
+    if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));
+    *form_out = !ring ? 0 : (m->ring.lo8.get() || m->ring.rec16.get()) ? 2 : m->ring.col16.get() ? 1 : 0;
+    return SMH_OK;
+}
+
+int smh_crs_ring_values(smh_crs *m, int *form_out, int *exponent_out) {
+    if (!m || !form_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));
+    const bool rec = ring && m->ring.rec16.get();
+    *form_out = rec ? 1 : (ring && m->ring.v24 == Form::Refused) ? -1 : 0;
+    if (exponent_out) *exponent_out = rec ? m->ring.v24_exp : 0;
+    return SMH_OK;
+}
+
+int smh_crs_ring_entries(smh_crs *m, uint32_t *out) {
+    if (!m || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m));
+    *out = m->ring.entries;
+    return SMH_OK;
+}
+
+int smh_crs_ring_bands(smh_crs *m, uint32_t *bands_out, uint32_t *intervals_out) {
+    if (!m || !bands_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_ring_plan(m));
+    *bands_out = m->ring.bands;
+    if (intervals_out && m->ring.bands == 4 && m->ring.win.get())
+        SMH_HIP(hipMemcpy(intervals_out, m->ring.win.get(), ((m->n_rows + 63) / 64) * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+int smh_crs_set_vector_lanes(smh_crs *m, int lanes) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (lanes != 0 && (lanes < 1 || lanes > 64 || (lanes & (lanes - 1))))
+        return fail(SMH_ERR_INVALID, "lanes per row must be 0 or a power of two in 1..64");
+    m->knobs.forced_lanes = lanes;
+    return SMH_OK;
+}
+
+size_t smh_crs_merge_tiles(const smh_crs *m) {
+    if (!m) return 0;
+    return (size_t)(((uint64_t)m->n_rows + m->nnz + kMergeTile - 1) / kMergeTile);
+}
+
+size_t smh_crs_merge_tile_items(const smh_crs *) { return kMergeTile; }
+
+int smh_crs_merge_table(smh_crs *m, uint32_t *row_out, uint32_t *nnz_out) {
+    if (!m || !row_out || !nnz_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_TRY(ensure_merge_ws(m));
+    if (m->merge.n_tiles == 0) { row_out[0] = 0; nnz_out[0] = 0; return SMH_OK; }
+    SMH_HIP(hipMemcpy(row_out, m->merge.tile_row.get(), (m->merge.n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SMH_HIP(hipMemcpy(nnz_out, m->merge.tile_nz.get(), (m->merge.n_tiles + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SMH_OK;
+}
+
+}  // extern "C"

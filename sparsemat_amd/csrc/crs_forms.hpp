@@ -1,5 +1,7 @@
-// crs_forms.hpp -- what crosses between capi.hip (the entry points), crs_forms.hip (what a CRS handle derives, and when it goes) and
-// spmv_dispatch.hip (which kernel a product runs, and its launches).  What the kernel files and the solvers call is in internal.hpp.
+// crs_forms.hpp -- what crosses between the host sides of the library's files: capi.hip (the core of the C boundary: errors, the life
+// cycle of a handle), crs_forms.hip (what a CRS handle derives, and when it goes), spmv_dispatch.hip (which kernel a product runs,
+// and its launches) and the entry points that live with their feature's device code.  What the kernel files and the solvers call
+// is in internal.hpp.
 #pragma once
 #include "internal.hpp"
 
@@ -7,8 +9,21 @@ namespace smh {
 
 // ---- capi.hip --------------------------------------------------------------------------------------------------------------------
 void clear_error();  // (beside set_error) an error that a fallback has absorbed: its text goes
-// a fresh handle over the arrays of `arrays`, which it takes (ensure_split makes the two parts of a K2s split with it)
+inline bool valid_dtype(int dt) { return dt == SMH_F32 || dt == SMH_F64; }
+// a fresh handle over device arrays, made on the current device with the create-time inspection done.  The first form takes the
+// arrays of `arrays` (ensure_split makes the two parts of a K2s split with it); the second owns or borrows the three it is given
 int wrap_arrays(int dtype, const ::smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, CrsArrays &arrays, int validate, ::smh_crs **out);
+int wrap_arrays(int dtype, const ::smh_crs *like, size_t n_rows, size_t n_cols, size_t nnz, uint32_t *off, uint32_t *col, void *val, bool owns,
+                int validate, ::smh_crs **out);
+void replace_state(::smh_crs *a, ::smh_crs *fresh, bool keep_arrays);  // `a` takes the state of `fresh`, which goes (add_assign, apply)
+int vec_check_pair(const ::smh_vec *x, const ::smh_vec *y);            // two vector handles of one value type
+
+// ---- the entry points' helpers that other features call ----------------------------------------------------------------------------
+// assemble.hip: the add_to / set stream -> CRS behind smh_crs_assemble / replay [_dev]; transpose, add / sub and apply replay with it
+int assemble_common(smh_dtype dtype, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops,
+                    bool on_device, bool into_crs, ::smh_crs **out, bool transposing = false);
+UpdMatrix upd_view(const ::smh_crs *m);  // matupdate.hip: the handle as get / apply / the update plan see it
+int reduce_scratch(void **out);          // blas1.hip: the calling thread's scratch for reductions (dot, inner_prod) on the current device
 
 // ---- defined here: the read-back the builders and the create-time inspection share ------------------------------------------------
 // "Launch into a few device words, bring them to the host": launch(d) fills `count` elements at d (device scratch), which are

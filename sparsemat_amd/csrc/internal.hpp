@@ -905,7 +905,7 @@ struct smh_mvec {
 
 namespace smh {
 // K5m (cg_many.hip): ConjugateGradient::solve on the k columns of b and x at once; the argument checks are the entry point's
-// (capi.hip).  iters_out / rr_out: k entries each.  (The per-column BLAS-1 of smh_mvec and the column tree: mvec_tree.hpp.)
+// (smh_cg_solve_many, in the same file).  iters_out / rr_out: k entries each.  (The per-column BLAS-1 of smh_mvec and the column tree: mvec_tree.hpp.)
 int cg_solve_many(::smh_crs *m, const ::smh_mvec *b, ::smh_mvec *x, double tol, size_t iter_max, size_t check_every, size_t *iters_out,
                   double *rr_out);
 }  // namespace smh

@@ -26,7 +26,9 @@
 //     thread per run of equal columns folds it.  Cost O(nnz) passes plus the sort: it does not grow as lenA * lenB.
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "internal.hpp"
+#include <cstdlib>
+
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -366,3 +368,100 @@ int add_crs(int dtype, bool subtract, const AddOperand &a, const AddOperand &b, 
 }
 
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+// ---- the entry points: #[derive(Clone)] (sparsemat_crs.rs:8) and SparseMatrix::add / sub (sparsematrix.rs:123-143) --------------
+static thread_local int g_add_route = 2;
+int smh_last_add_route(void) { return g_add_route; }
+
+int smh_crs_clone(const smh_crs *a, smh_crs **out) {
+    if (!a || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    const size_t vs = dtype_size(a->dtype);
+    CrsArrays arrays;
+    SMH_TRY(arrays.alloc(a->n_rows, a->nnz, vs));
+    SMH_HIP(hipMemcpy(arrays.off, a->d_off, (a->n_rows + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    if (a->nnz) {
+        SMH_HIP(hipMemcpy(arrays.col, a->d_col, a->nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+        SMH_HIP(hipMemcpy(arrays.val, a->d_val, a->nnz * vs, hipMemcpyDeviceToDevice));
+    }
+    SMH_TRY(wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out));
+    (*out)->orphans = a->orphans;
+    (*out)->has_first_op = a->has_first_op;
+    (*out)->first_row = a->first_row;
+    (*out)->first_col = a->first_col;
+    (*out)->first_val_bits = a->first_val_bits;
+    return SMH_OK;
+}
+
+// a_mut != NULL: a += b in place (a_mut == a); else *out = a.clone() + b
+static int add_common(smh_crs *a_mut, const smh_crs *a, const smh_crs *b, bool subtract, smh_crs **out) {
+    if (!a || !b || (!a_mut && !out)) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (out) *out = nullptr;
+    if (a->dtype != b->dtype) return fail(SMH_ERR_INVALID, "operands differ in value type");
+    if (a->device != b->device) return fail(SMH_ERR_INVALID, "operands live on different devices");
+    if (a->n_rows == 0 && a->orphans)
+        return fail(SMH_ERR_INVALID, "add / sub: the left operand has no rows but an orphaned entry -- the reference's hidden offset_rows "
+                                     "length decides whether it comes back to life, and the handle does not keep it");
+    SMH_HIP(hipStreamSynchronize(b->stream));  // b's reads come after whatever b's stream still has to do
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    g_add_route = 2;
+    if (b->nnz == 0) {  // nothing visited: a unchanged (b's orphan is not reached by any row)
+        if (a_mut) return SMH_OK;
+        return smh_crs_clone(a, out);
+    }
+    smh_crs *fresh = nullptr;
+    if (a->n_rows == 0) {
+        // SparseMatCRS::new() (no offset_rows): the replay of b's entries as add_to operations, first-push quirk included
+        g_add_route = 0;
+        const size_t vs = dtype_size(a->dtype);
+        Scratch scr;
+        uint32_t *rows = nullptr;
+        char *neg = nullptr;
+        SMH_TRY(scr.alloc(&rows, b->nnz));
+        SMH_TRY(expand_rows(b->d_off, b->n_rows, rows, nullptr));
+        if (subtract) {  // 0 - v == 0 + (-v) in IEEE 754, signed zeros included
+            SMH_TRY(scr.alloc(&neg, (b->nnz + 4) * vs));
+            SMH_HIP(hipMemcpy(neg, b->d_val, b->nnz * vs, hipMemcpyDeviceToDevice));
+            SMH_TRY(launch_scale_values(a->dtype, neg, b->nnz, -1.0, nullptr));
+        }
+        SMH_HIP(hipStreamSynchronize(nullptr));
+        SMH_TRY(assemble_common((smh_dtype)a->dtype, b->nnz, rows, b->d_col, subtract ? (const void *)neg : b->d_val, nullptr, true, true, &fresh));
+        if (fresh->n_cols < a->n_cols) fresh->n_cols = a->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
+        fresh->knobs = a->knobs;
+        if (a_mut) replace_state(a_mut, fresh, false);
+        else *out = fresh;
+        return SMH_OK;
+    }
+    AddOperand oa, ob;
+    oa.off = a->d_off; oa.col = a->d_col; oa.val = a->d_val;
+    oa.n_rows = a->n_rows; oa.n_cols = a->n_cols; oa.nnz = a->nnz; oa.orphans = a->orphans;
+    oa.max_row_len = a->max_row_len; oa.max_col = a->max_col;
+    ob.off = b->d_off; ob.col = b->d_col; ob.val = b->d_val;
+    ob.n_rows = b->n_rows; ob.n_cols = b->n_cols; ob.nnz = b->nnz; ob.orphans = b->orphans;
+    ob.max_row_len = b->max_row_len; ob.max_col = b->max_col;
+    const bool force_general = getenv("SMH_ADD_FAST") && atoi(getenv("SMH_ADD_FAST")) == 0;
+    AddResult r;
+    SMH_TRY(add_crs(a->dtype, subtract, oa, ob, a_mut != nullptr, a == b, force_general, &r, a->stream));
+    g_add_route = r.route;
+    if (r.values_only) {  // (borrowed by the fresh handle until it has been built: a failure must not free a's arrays)
+        SMH_TRY(wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, a->d_off, a->d_col, a->d_val, false, 0, &fresh));
+        fresh->owns = a->owns;
+    } else
+        SMH_TRY(wrap_arrays(a->dtype, a, r.n_rows, r.n_cols, r.nnz, r.arrays, 0, &fresh));
+    fresh->orphans = a->orphans;
+    if (a_mut) replace_state(a_mut, fresh, r.values_only);
+    else *out = fresh;
+    return SMH_OK;
+}
+
+int smh_crs_add(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_common(nullptr, a, b, false, out); }
+int smh_crs_sub(const smh_crs *a, const smh_crs *b, smh_crs **out) { return add_common(nullptr, a, b, true, out); }
+int smh_crs_add_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, false, nullptr); }
+int smh_crs_sub_assign(smh_crs *a, const smh_crs *b) { return add_common(a, a, b, true, nullptr); }
+
+}  // extern "C"

@@ -17,9 +17,11 @@
 //     reversed (ascending set calls into a SparseMatCRS leave descending columns: push prepends, sparsemat_crs.rs:85-87),
 //     n_rows / n_cols = largest row / column with a kept sum + 1; a single kept sum leaves a matrix without rows (first
 //     push quirk :75-76), the quirk's other two forms cannot occur for ascending (i, j).
-#include "internal.hpp"
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 #include <chrono>
+#include <cstdlib>
 #include <memory>
 #include <new>
 #include <vector>
@@ -376,7 +378,7 @@ static int prod_t(const uint32_t *a_off, const uint32_t *a_col, const T *a_val, 
     return SMH_OK;
 }
 
-// Device arrays; the dimension rule of sparsematrix.rs:188-190 is the caller's (capi.hip).
+// Device arrays; the dimension rule of sparsematrix.rs:188-190 is the caller's (smh_crs_prod, below).
 int prod_crs(int dtype, const uint32_t *a_off, const uint32_t *a_col, const void *a_val, size_t a_rows, size_t a_nnz, uint32_t a_max_col,
              const uint32_t *b_off, const uint32_t *b_col, const void *b_val, size_t b_rows, size_t *n_rows_out, size_t *n_cols_out,
              size_t *nnz_out, uint32_t **off_out, uint32_t **col_out, void **val_out, hipStream_t s) {
@@ -387,4 +389,87 @@ int prod_crs(int dtype, const uint32_t *a_off, const uint32_t *a_col, const void
                          n_rows_out, n_cols_out, nnz_out, off_out, col_out, (float **)val_out, s);
 }
 
+// ---- the entry points: transpose, column_info, prod ------------------------------------------------------------------------------
+static int column_info_common(const smh_crs *m, uint32_t *rows, uint32_t *col_ptr, uint32_t *entries, bool on_device) {
+    if (!m || !rows || !col_ptr || !entries) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (m->nnz && (size_t)m->max_col >= m->n_cols)
+        return fail(SMH_ERR_INDEX_RANGE, "column %u out of range for %zu columns", m->max_col, m->n_cols);
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    ArgStage st(on_device, ArgStage::kUnchecked);  // known difference, kept: no device check, no device-wide synchronisation
+    void *d[3] = {nullptr, nullptr, nullptr};
+    SMH_TRY(st.out(rows, m->nnz * sizeof(uint32_t), "rows", &d[0]));
+    SMH_TRY(st.out(col_ptr, (m->n_cols + 1) * sizeof(uint32_t), "col_ptr", &d[1]));
+    SMH_TRY(st.out(entries, m->nnz * sizeof(uint32_t), "entries", &d[2]));
+    SMH_TRY(column_info(m->d_off, m->d_col, m->n_rows, m->n_cols, m->nnz, m->max_col, (uint32_t *)d[0], (uint32_t *)d[1], (uint32_t *)d[2], m->stream));
+    return st.finish();
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+static thread_local int g_transpose_route = 0;
+int smh_last_transpose_route(void) { return g_transpose_route; }
+
+// SparseMatrix::transpose (sparsematrix.rs:174-184) for Self = SparseMatCRS: `ret.set(j, i, val)` for every entry in row-major
+// storage order into a fresh SparseMatCRS -- the replay of assemble.hip with rows = the columns array (borrowed), columns = the
+// row of every entry, all operations `set`.
+int smh_crs_transpose(const smh_crs *a, smh_crs **out) {
+    if (!a || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    if (a->nnz == 0) return assemble_common((smh_dtype)a->dtype, 0, nullptr, nullptr, nullptr, nullptr, true, true, out);
+    g_transpose_route = 0;
+    // matrices with local structure: two bucketed passes instead of the device-wide sort (transpose_bucket.hip).  The container's first-push quirks (second target row below the first: the first entry is
+    // orphaned; a single operation) and repeated (row, column) pairs stay with the general route.
+    const bool bucketed_allowed = !(getenv("SMH_TRANSPOSE_BUCKETED") && atoi(getenv("SMH_TRANSPOSE_BUCKETED")) == 0);
+    if (bucketed_allowed && a->nnz >= 2 && a->have_stats) {
+        uint32_t c01[2] = {0, 0};
+        SMH_HIP(hipMemcpy(c01, a->d_col, sizeof c01, hipMemcpyDeviceToHost));
+        if (c01[1] >= c01[0]) {
+            CrsArrays t;
+            size_t t_rows = 0, t_cols = 0;
+            bool done = false;
+            SMH_TRY(transpose_bucketed(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, &t.off, &t.col, &t.val, &t_rows, &t_cols, &done,
+                                       nullptr));
+            if (done) {
+                SMH_TRY(wrap_arrays(a->dtype, nullptr, t_rows, t_cols, a->nnz, t, 0, out));
+                g_transpose_route = 1;
+                return SMH_OK;
+            }
+        }
+    }
+    Scratch scr;
+    uint32_t *d_rowof = nullptr;
+    SMH_TRY(scr.alloc(&d_rowof, a->nnz));
+    SMH_TRY(expand_rows(a->d_off, a->n_rows, d_rowof, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return assemble_common((smh_dtype)a->dtype, a->nnz, a->d_col, d_rowof, a->d_val, nullptr, true, true, out, true);
+}
+
+int smh_crs_column_info(const smh_crs *m, uint32_t *rows, uint32_t *col_ptr, uint32_t *entries) {
+    return column_info_common(m, rows, col_ptr, entries, false);
+}
+
+int smh_crs_column_info_dev(const smh_crs *m, uint32_t *rows_dev, uint32_t *col_ptr_dev, uint32_t *entries_dev) {
+    return column_info_common(m, rows_dev, col_ptr_dev, entries_dev, true);
+}
+
+// SparseMatrix::prod (sparsematrix.rs:186-210) for SparseMatCRS operands; Err("Dimension mismatch") of :188-190 as a status
+int smh_crs_prod(const smh_crs *a, const smh_crs *b, smh_crs **out) {
+    if (!a || !b || !out) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (a->dtype != b->dtype) return fail(SMH_ERR_INVALID, "operands differ in value type");
+    if (a->n_rows != b->n_cols || a->n_cols != b->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    if (a->nnz && (size_t)a->max_col >= a->n_cols)
+        return fail(SMH_ERR_INDEX_RANGE, "column %u out of range for %zu columns", a->max_col, a->n_cols);
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    SMH_HIP(hipStreamSynchronize(b->stream));
+    CrsArrays arrays;
+    size_t n_rows = 0, n_cols = 0, nnz = 0;
+    SMH_TRY(prod_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, a->max_col, b->d_off, b->d_col, b->d_val, b->n_rows, &n_rows, &n_cols,
+                     &nnz, &arrays.off, &arrays.col, &arrays.val, nullptr));
+    return wrap_arrays(a->dtype, nullptr, n_rows, n_cols, nnz, arrays, 0, out);
+}
+
+}  // extern "C"

@@ -22,7 +22,10 @@
 //   k_plan_long   a workgroup takes one run: it stages kPlanStage operations per round in LDS (the gathers of the next round are in
 //                 flight while the round is folded), and one lane folds each round from LDS in order -- serial, as the contract
 //                 demands, but without a global round trip per step.
-#include "internal.hpp"
+#include <new>
+
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -314,3 +317,106 @@ int plan_build(size_t n, const uint32_t *key, const uint32_t *src, const uint8_t
 }
 
 }  // namespace smh
+
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+using namespace smh;
+
+struct smh_update_plan {
+    uint64_t crs_id = 0, epoch = 0;  // the handle and the structure it was made for
+    UpdPlan plan;
+    StageBuf stage;  // the host form's upload of the values (lazy, reused)
+};
+
+static int plan_create_common(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, const uint8_t *ops, bool on_device,
+                              smh_update_plan **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
+    *out = nullptr;
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols)) return fail(SMH_ERR_INVALID, "NULL operation array");
+    if (n >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    if (m->n_rows == 0) return fail(SMH_ERR_INVALID, "update plan: the handle has no rows, so no operation has an entry to land on");
+    smh_update_plan *p = new (std::nothrow) smh_update_plan();
+    if (!p) return fail(SMH_ERR_OOM, "host allocation failed");
+    p->crs_id = m->id; p->epoch = m->epoch;
+    const int rc = [&]() -> int {
+        if (n == 0) return SMH_OK;  // a valid plan whose execute does nothing
+        ArgStage st(on_device, m->device);  // (its scratch also holds the sorted operations)
+        const void *d_rows = nullptr, *d_cols = nullptr, *d_ops = nullptr;
+        SMH_TRY(st.in(rows, n * sizeof(uint32_t), "rows", &d_rows));
+        SMH_TRY(st.in(cols, n * sizeof(uint32_t), "cols", &d_cols));
+        SMH_TRY(st.in(ops, n, "ops", &d_ops));
+        SMH_TRY(st.callers_writes_first());
+        SMH_HIP(hipStreamSynchronize(m->stream));
+        uint32_t *key = nullptr, *src = nullptr;
+        uint64_t n_absent = 0;
+        SMH_TRY(st.scratch().alloc(&key, n));
+        SMH_TRY(st.scratch().alloc(&src, n));
+        SMH_TRY(crs_plan_targets(upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, key, src, &n_absent, m->stream));
+        if (n_absent)
+            return fail(SMH_ERR_INVALID, "update plan: %llu of %llu operations have no entry to land on (smh_crs_apply creates entries; plan afterwards)",
+                        (unsigned long long)n_absent, (unsigned long long)n);
+        return plan_build(n, key, src, (const uint8_t *)d_ops, &p->plan, m->stream);
+    }();
+    if (rc != SMH_OK) return keep_error(rc, [&] { delete p; });
+    *out = p;
+    return SMH_OK;
+}
+
+static int plan_execute_common(smh_update_plan *p, smh_crs *m, const void *values, int from_zero, bool on_device) {
+    if (!p || !m) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (p->crs_id != m->id) return fail(SMH_ERR_INVALID, "update plan: made for another handle");
+    if (p->epoch != m->epoch) return fail(SMH_ERR_INVALID, "update plan: the handle's structure changed since the plan was made");
+    const size_t n = p->plan.n_ops;
+    if (n && !values) return fail(SMH_ERR_INVALID, "NULL value array");
+    if (n == 0) return SMH_OK;
+    ArgStage st(on_device, m->device);
+    const void *d_vals = values;
+    SMH_TRY(st.check(values, "values"));
+    SMH_TRY(st.callers_writes_first());
+    if (!on_device) {  // known difference, kept: the plan's own reusable staging buffer, so that repeated executes do not allocate
+        const size_t bytes = n * dtype_size(m->dtype);
+        SMH_TRY(p->stage.ensure_cap(bytes));
+        SMH_HIP(hipMemcpy(p->stage.d.get(), values, bytes, hipMemcpyHostToDevice));
+        d_vals = p->stage.d.get();
+    }
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    SMH_TRY(plan_execute(m->dtype, p->plan, d_vals, m->d_val, from_zero != 0, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    return smh_crs_update_values(m, nullptr);  // as apply's values-only route: structure-derived forms stay, value-derived ones follow
+}
+
+extern "C" {
+
+int smh_update_plan_create(const smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const uint8_t *ops, smh_update_plan **out) {
+    return plan_create_common(m, n_ops, rows, cols, ops, false, out);
+}
+int smh_update_plan_create_dev(const smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev, const uint8_t *ops_dev,
+                               smh_update_plan **out) {
+    return plan_create_common(m, n_ops, rows_dev, cols_dev, ops_dev, true, out);
+}
+
+int smh_update_plan_execute(smh_update_plan *p, smh_crs *m, const void *values, int from_zero) {
+    return plan_execute_common(p, m, values, from_zero, false);
+}
+int smh_update_plan_execute_dev(smh_update_plan *p, smh_crs *m, const void *values_dev, int from_zero) {
+    return plan_execute_common(p, m, values_dev, from_zero, true);
+}
+
+int smh_update_plan_stats(const smh_update_plan *p, size_t *n_ops, size_t *n_targets, size_t *n_live_ops, size_t *longest_run,
+                          size_t *long_run_threshold, size_t *device_bytes) {
+    if (!p) return fail(SMH_ERR_INVALID, "NULL plan");
+    if (n_ops) *n_ops = p->plan.n_ops;
+    if (n_targets) *n_targets = p->plan.n_targets;
+    if (n_live_ops) *n_live_ops = p->plan.n_live;
+    if (longest_run) *longest_run = p->plan.longest_run;
+    if (long_run_threshold) *long_run_threshold = kPlanLongRun;
+    if (device_bytes) *device_bytes = p->plan.device_bytes;
+    return SMH_OK;
+}
+
+int smh_update_plan_destroy(smh_update_plan *p) {
+    delete p;
+    return SMH_OK;
+}
+
+}  // extern "C"

@@ -25,7 +25,10 @@
 // The batched get is step 1 with the stored value (or +0) as its output.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "internal.hpp"
+#include <cstdlib>
+
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -452,4 +455,158 @@ int build_eye(int dtype, size_t dim, uint32_t *off, uint32_t *col, void *val, hi
     return SMH_OK;
 }
 
+// ---- the entry points: SparseMatrix::get / set / add_to / eye (sparsematrix.rs:91-98, 224-233; sparsemat_crs.rs:54-92, 136-150) --
+UpdMatrix upd_view(const smh_crs *m) {
+    UpdMatrix u;
+    u.off = m->d_off; u.col = m->d_col; u.val = m->d_val;
+    u.n_rows = m->n_rows; u.n_cols = m->n_cols; u.nnz = m->nnz; u.orphans = m->orphans;
+    u.max_row_len = m->max_row_len;
+    return u;
+}
+
+static int get_many_common(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols || !values_out)) return fail(SMH_ERR_INVALID, "NULL query array");
+    if (n == 0) return SMH_OK;
+    const size_t vs = dtype_size(m->dtype);
+    ArgStage st(on_device, m->device);
+    if (m->n_rows == 0) {  // find_index needs i < n_rows (sparsemat_crs.rs:54-67): every answer is zero
+        // known difference, kept: the query arrays are checked and waited for, never staged
+        SMH_TRY(st.check(rows, "rows"));
+        SMH_TRY(st.check(cols, "cols"));
+        SMH_TRY(st.check(values_out, "values_out"));
+        SMH_TRY(st.callers_writes_first());
+        SMH_HIP(hipStreamSynchronize(m->stream));
+        if (on_device) SMH_HIP(hipMemset(values_out, 0, n * vs));
+        else memset(values_out, 0, n * vs);
+        return SMH_OK;
+    }
+    const void *d_rows = nullptr, *d_cols = nullptr;
+    void *d_out = nullptr;
+    SMH_TRY(st.in(rows, n * sizeof(uint32_t), "rows", &d_rows));
+    SMH_TRY(st.in(cols, n * sizeof(uint32_t), "cols", &d_cols));
+    SMH_TRY(st.out(values_out, n * vs, "values_out", &d_out));
+    SMH_TRY(st.callers_writes_first());
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    SMH_TRY(crs_get_many(m->dtype, upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_out, m->stream));
+    return st.finish();
+}
+
+static thread_local int g_apply_route = 1;
+
+static int apply_common(smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (n && (!rows || !cols || !values)) return fail(SMH_ERR_INVALID, "NULL operation array");
+    if (n >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    if (n == 0) {  // nothing applied: m untouched
+        g_apply_route = 1;
+        return SMH_OK;
+    }
+    if (m->n_rows == 0 && m->orphans && !m->has_first_op)
+        return fail(SMH_ERR_INVALID, "apply: the handle has no rows but an orphaned entry whose operation it does not know");
+    const size_t vs = dtype_size(m->dtype);
+    ArgStage st(on_device, m->device);
+    const void *d_rows = nullptr, *d_cols = nullptr, *d_vals = nullptr, *d_ops = nullptr;
+    SMH_TRY(st.in(rows, n * sizeof(uint32_t), "rows", &d_rows));
+    SMH_TRY(st.in(cols, n * sizeof(uint32_t), "cols", &d_cols));
+    SMH_TRY(st.in(values, n * vs, "values", &d_vals));
+    SMH_TRY(st.in(ops, n, "ops", &d_ops));
+    SMH_TRY(st.callers_writes_first());
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    smh_crs *fresh = nullptr;
+    if (m->n_rows == 0) {
+        // SparseMatCRS::new(), or the state its first push leaves (sparsemat_crs.rs:75-76): the replay of (that push ++ the stream)
+        g_apply_route = 2;
+        if (!m->has_first_op) {
+            SMH_TRY(assemble_common((smh_dtype)m->dtype, n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_vals, (const uint8_t *)d_ops, true,
+                                    true, &fresh));
+        } else {
+            Scratch cat;  // that push's operation ++ the stream
+            uint32_t *c_rows = nullptr, *c_cols = nullptr;
+            char *c_vals = nullptr;
+            uint8_t *c_ops = nullptr;
+            SMH_TRY(cat.alloc(&c_rows, n + 1));
+            SMH_TRY(cat.alloc(&c_cols, n + 1));
+            SMH_TRY(cat.alloc(&c_vals, (n + 1) * vs));
+            SMH_TRY(cat.alloc(&c_ops, n + 1));
+            const uint8_t set = 1;  // the recorded value is already folded: `set` it
+            SMH_HIP(hipMemcpy(c_rows, &m->first_row, sizeof(uint32_t), hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_cols, &m->first_col, sizeof(uint32_t), hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_vals, &m->first_val_bits, vs, hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_ops, &set, 1, hipMemcpyHostToDevice));
+            SMH_HIP(hipMemcpy(c_rows + 1, d_rows, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            SMH_HIP(hipMemcpy(c_cols + 1, d_cols, n * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+            SMH_HIP(hipMemcpy(c_vals + vs, d_vals, n * vs, hipMemcpyDeviceToDevice));
+            if (d_ops) SMH_HIP(hipMemcpy(c_ops + 1, d_ops, n, hipMemcpyDeviceToDevice));
+            else SMH_HIP(hipMemset(c_ops + 1, 0, n));
+            SMH_TRY(assemble_common((smh_dtype)m->dtype, n + 1, c_rows, c_cols, c_vals, c_ops, true, true, &fresh));
+        }
+        if (fresh->n_cols < m->n_cols) fresh->n_cols = m->n_cols;  // push only raises n_cols (sparsemat_crs.rs:72-74)
+        fresh->knobs = m->knobs;
+        replace_state(m, fresh, false);
+        return SMH_OK;
+    }
+    const bool force_general = getenv("SMH_APPLY_FAST") && atoi(getenv("SMH_APPLY_FAST")) == 0;
+    UpdResult r;
+    SMH_TRY(crs_apply(m->dtype, upd_view(m), n, (const uint32_t *)d_rows, (const uint32_t *)d_cols, d_vals, (const uint8_t *)d_ops, force_general, &r,
+                      m->stream));
+    g_apply_route = r.route;
+    if (r.values_only)  // structure unchanged: every form derived from it stays, the value-derived ones are refreshed
+        return smh_crs_update_values(m, nullptr);
+    SMH_TRY(wrap_arrays(m->dtype, m, r.n_rows, r.n_cols, r.nnz, r.arrays, 0, &fresh));
+    fresh->orphans = m->orphans;
+    replace_state(m, fresh, false);
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_last_apply_route(void) { return g_apply_route; }
+
+int smh_crs_get(const smh_crs *m, size_t i, size_t j, void *value_out) {
+    if (!m || !value_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (i >= m->n_rows || j > 0xFFFFFFFFull) {  // no row i, or a column no entry can have
+        memset(value_out, 0, dtype_size(m->dtype));
+        return SMH_OK;
+    }
+    const uint32_t r = (uint32_t)i, c = (uint32_t)j;
+    return get_many_common(m, 1, &r, &c, value_out, false);
+}
+int smh_crs_get_many(const smh_crs *m, size_t n, const uint32_t *rows, const uint32_t *cols, void *values_out) {
+    return get_many_common(m, n, rows, cols, values_out, false);
+}
+int smh_crs_get_many_dev(const smh_crs *m, size_t n, const uint32_t *rows_dev, const uint32_t *cols_dev, void *values_out_dev) {
+    return get_many_common(m, n, rows_dev, cols_dev, values_out_dev, true);
+}
+
+int smh_crs_apply(smh_crs *m, size_t n_ops, const uint32_t *rows, const uint32_t *cols, const void *values, const uint8_t *ops) {
+    return apply_common(m, n_ops, rows, cols, values, ops, false);
+}
+int smh_crs_apply_dev(smh_crs *m, size_t n_ops, const uint32_t *rows_dev, const uint32_t *cols_dev, const void *values_dev, const uint8_t *ops_dev) {
+    return apply_common(m, n_ops, rows_dev, cols_dev, values_dev, ops_dev, true);
+}
+
+int smh_crs_eye(smh_dtype dtype, size_t dim, smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "NULL out pointer");
+    *out = nullptr;
+    if (!valid_dtype(dtype)) return fail(SMH_ERR_INVALID, "dtype must be SMH_F32 or SMH_F64");
+    if (dim >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);
+    SMH_TRY(require_device());
+    if (dim <= 1) {  // no rows (dim 0); the first push alone: no rows, one orphan, n_cols 1 (dim 1)
+        const uint32_t zero = 0;
+        const uint8_t set = 1;
+        const double one64 = 1.0;
+        const float one32 = 1.0f;
+        return assemble_common(dtype, dim, &zero, &zero, dtype == SMH_F64 ? (const void *)&one64 : (const void *)&one32, &set, false, true, out);
+    }
+    CrsArrays arrays;
+    SMH_TRY(arrays.alloc(dim, dim, dtype_size(dtype)));
+    SMH_TRY(build_eye(dtype, dim, arrays.off, arrays.col, arrays.val, nullptr));
+    return wrap_arrays(dtype, nullptr, dim, dim, dim, arrays, 0, out);
+}
+
+}  // extern "C"

@@ -18,7 +18,8 @@
 //                                them from its source rows, contiguous per row.  Addresses are 64-bit.
 // Byte model of the emit pass, per entry: read 4 + sizeof(T) (source column and value), write 4 + sizeof(T), plus one
 // 4-byte gather from col_perm^-1 when columns are permuted; per row 12 bytes of offsets.
-#include "internal.hpp"
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -247,4 +248,104 @@ int launch_bandwidth(const uint32_t *off, const uint32_t *col, size_t n_rows, ui
     return SMH_OK;
 }
 
+// ---- the entry points: a permutation is n u32 with perm[new] = old (EXTENSION) ---------------------------------------------------
+// One permutation argument of an entry point: checked for its length, staged (a host array goes to the device, the caller's
+// device array is checked), validated there (`inv` = its inverse afterwards).  perm == NULL: the identity, nothing to do
+// (*d_perm stays null).
+static int take_permutation(ArgStage &st, const uint32_t *perm, size_t len, size_t n, const char *what, const uint32_t **d_perm, uint32_t **inv) {
+    *d_perm = nullptr;
+    *inv = nullptr;
+    if (!perm) return SMH_OK;
+    if (len != n) return fail(SMH_ERR_DIM_MISMATCH, "%s has %zu entries, %zu expected", what, len, n);
+    if (n == 0) return SMH_OK;
+    const void *d = nullptr;
+    SMH_TRY(st.in(perm, n * sizeof(uint32_t), what, &d));
+    *d_perm = (const uint32_t *)d;
+    SMH_TRY(st.scratch().alloc(inv, n));
+    return validate_permutation(*d_perm, n, *inv, what, nullptr);
+}
+
+static int permute_common(const smh_crs *a, const uint32_t *row_perm, size_t n_row_perm, const uint32_t *col_perm, size_t n_col_perm, bool on_device,
+                          smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!a) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (a->orphans) return fail(SMH_ERR_INVALID, "a handle holding an orphaned entry cannot be permuted");
+    if (col_perm) SMH_TRY(columns_within_n_cols(a, "permute"));
+    ArgStage st(on_device, a->device);
+    SMH_TRY(st.callers_writes_first());  // known difference, kept: before the device check (take_permutation)
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    const uint32_t *d_rp = nullptr, *d_cp = nullptr;
+    uint32_t *row_inv = nullptr, *col_inv = nullptr;
+    SMH_TRY(take_permutation(st, row_perm, n_row_perm, a->n_rows, "row_perm", &d_rp, &row_inv));
+    SMH_TRY(take_permutation(st, col_perm, n_col_perm, a->n_cols, "col_perm", &d_cp, &col_inv));
+    CrsArrays arrays;
+    SMH_TRY(permute_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, d_rp, col_inv, &arrays, nullptr));
+    return wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out);
+}
+
+static int permute_symmetric_common(const smh_crs *a, const uint32_t *perm, size_t n_perm, bool on_device, smh_crs **out) {
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!a || !perm) return fail(SMH_ERR_INVALID, "NULL argument");
+    if (a->n_rows != a->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (a->orphans) return fail(SMH_ERR_INVALID, "a handle holding an orphaned entry cannot be permuted");
+    SMH_TRY(columns_within_n_cols(a, "permute_symmetric"));
+    ArgStage st(on_device, a->device);
+    SMH_TRY(st.callers_writes_first());  // known difference, kept: before the device check (take_permutation)
+    SMH_HIP(hipStreamSynchronize(a->stream));
+    const uint32_t *d_p = nullptr;
+    uint32_t *inv = nullptr;
+    SMH_TRY(take_permutation(st, perm, n_perm, a->n_rows, "perm", &d_p, &inv));  // (validated once, one inverse)
+    CrsArrays arrays;
+    SMH_TRY(permute_crs(a->dtype, a->d_off, a->d_col, a->d_val, a->n_rows, a->nnz, d_p, inv, &arrays, nullptr));
+    return wrap_arrays(a->dtype, a, a->n_rows, a->n_cols, a->nnz, arrays, 0, out);
+}
+
+static int vec_permute_common(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse, bool on_device) {
+    SMH_TRY(vec_check_pair(dst, src));
+    if (!perm && n_perm) return fail(SMH_ERR_INVALID, "perm is NULL");
+    if (dst->n != src->n) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    if (dst == src || (dst->d && dst->d == src->d)) return fail(SMH_ERR_INVALID, "a vector cannot be permuted into itself");
+    if (n_perm != src->n) return fail(SMH_ERR_DIM_MISMATCH, "perm has %zu entries, %zu expected", n_perm, src->n);
+    if (src->n == 0) return SMH_OK;
+    // known difference, kept: device-wide in BOTH forms (vectors work on the null stream; the caller's writes to a device array come first)
+    SMH_HIP(hipDeviceSynchronize());
+    ArgStage st(on_device, src->device);
+    const uint32_t *d_p = nullptr;
+    uint32_t *inv = nullptr;
+    SMH_TRY(take_permutation(st, perm, n_perm, src->n, "perm", &d_p, &inv));
+    SMH_TRY(launch_vec_permute(src->dtype, dst->d, src->d, d_p, src->n, inverse != 0, nullptr));
+    SMH_HIP(hipStreamSynchronize(nullptr));
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_crs_permute(const smh_crs *a, const uint32_t *row_perm, size_t n_row_perm, const uint32_t *col_perm, size_t n_col_perm, smh_crs **out) {
+    return permute_common(a, row_perm, n_row_perm, col_perm, n_col_perm, false, out);
+}
+int smh_crs_permute_dev(const smh_crs *a, const uint32_t *row_perm_dev, size_t n_row_perm, const uint32_t *col_perm_dev, size_t n_col_perm,
+                        smh_crs **out) {
+    return permute_common(a, row_perm_dev, n_row_perm, col_perm_dev, n_col_perm, true, out);
+}
+
+int smh_crs_permute_symmetric(const smh_crs *a, const uint32_t *perm, size_t n_perm, smh_crs **out) {
+    return permute_symmetric_common(a, perm, n_perm, false, out);
+}
+int smh_crs_permute_symmetric_dev(const smh_crs *a, const uint32_t *perm_dev, size_t n_perm, smh_crs **out) {
+    return permute_symmetric_common(a, perm_dev, n_perm, true, out);
+}
+
+int smh_vec_permute(smh_vec *dst, const smh_vec *src, const uint32_t *perm, size_t n_perm, int inverse) {
+    return vec_permute_common(dst, src, perm, n_perm, inverse, false);
+}
+int smh_vec_permute_dev(smh_vec *dst, const smh_vec *src, const uint32_t *perm_dev, size_t n_perm, int inverse) {
+    return vec_permute_common(dst, src, perm_dev, n_perm, inverse, true);
+}
+
+}  // extern "C"

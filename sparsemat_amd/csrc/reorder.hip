@@ -32,7 +32,8 @@
 // takes n rounds.  Memory: 40 bytes per stored entry during the set-up, 8 per distinct neighbour pair plus 24 per vertex after it.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "internal.hpp"
+#include "arg_stage.hpp"
+#include "crs_forms.hpp"
 
 namespace smh {
 
@@ -342,4 +343,51 @@ int rcm_order(const uint32_t *off, const uint32_t *col, size_t n, size_t nnz, ui
     return SMH_OK;
 }
 
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+static int rcm_common(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out, bool on_device) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows != m->n_cols) return fail(SMH_ERR_NOT_SQUARE, "Matrix is not symmetric");
+    if (m->n_rows && !perm_out) return fail(SMH_ERR_INVALID, "perm_out is NULL");
+    SMH_TRY(columns_within_n_cols(m, "rcm"));
+    ArgStage st(on_device, m->device);
+    void *d_perm = nullptr;
+    SMH_TRY(st.out(perm_out, m->n_rows * sizeof(uint32_t), "perm_out", &d_perm));
+    SMH_TRY(st.callers_writes_first());
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    size_t comps = 0, levels = 0;
+    SMH_TRY(rcm_order(m->d_off, m->d_col, m->n_rows, m->nnz, (uint32_t *)d_perm, &comps, &levels, m->stream));
+    SMH_TRY(st.finish());
+    if (n_components_out) *n_components_out = comps;
+    if (n_levels_out) *n_levels_out = levels;
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_crs_rcm(const smh_crs *m, uint32_t *perm_out, size_t *n_components_out, size_t *n_levels_out) {
+    return rcm_common(m, perm_out, n_components_out, n_levels_out, false);
+}
+int smh_crs_rcm_dev(const smh_crs *m, uint32_t *perm_out_dev, size_t *n_components_out, size_t *n_levels_out) {
+    return rcm_common(m, perm_out_dev, n_components_out, n_levels_out, true);
+}
+
+int smh_crs_bandwidth(const smh_crs *m, uint32_t *lower_out, uint32_t *upper_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    uint32_t h[2] = {0, 0};
+    if (m->n_rows && m->nnz) {
+        SMH_HIP(hipStreamSynchronize(m->stream));
+        Scratch scr;
+        uint32_t *d = nullptr;
+        SMH_TRY(scr.alloc(&d, 2));
+        SMH_TRY(read_back(d, h, 2, m->stream, [&](uint32_t *q) { return launch_bandwidth(m->d_off, m->d_col, m->n_rows, q, m->stream); }));
+    }
+    if (lower_out) *lower_out = h[0];
+    if (upper_out) *upper_out = h[1];
+    return SMH_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,8 @@ namespace smh {
 
 // ---- the argument checks of the entry points, decided before any launch -------------------------------------------------------------
 constexpr const char *kVecDtype = "vector dtype differs from the matrix's";  // (smh_cg_solve_vec and smh_cg_solve_many word it in their own ways)
+// check_every = 0 stands for 4 bodies per poll in smh_cg_solve* (cg.hip, cg_many.hip); 8 in the preconditioned solvers and BiCGSTAB
+constexpr size_t kCgCheckEvery = 4;
 
 // what a matrix a and a factor f of it (ILU(0)'s, or one of FSAI's two: name) must agree in
 inline int ilu_check_pair(const smh_crs *a, const smh_crs *f, const char *name = "ILU preconditioner") {

@@ -1,5 +1,6 @@
 // spmv_dispatch.hip -- which kernel a product runs (AUTO's rules, with the measurements behind every threshold), which derived forms
 // that kernel runs on, and its launches.  Host-side logic only; the forms themselves are built in crs_forms.hip.
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -411,4 +412,136 @@ int spmv_inner_prod(smh_crs *m, const void *d_lhs, const void *d_rhs, size_t rhs
     return SMH_OK;
 }
 
+// ---- the entry points: prepare, the products, inner_prod --------------------------------------------------------------------------
+// lhs^T (A rhs) on device vectors, by one of three routes (spmv_inner_prod above):
+//   K1r   the ring kernel's DOT form: the lane that would store a row's sum adds fma(lhs[row], sum, .) to its own accumulator, a
+//         workgroup folds lanes and waves, one partial per workgroup and one for an unpadded array's last <= 3 entries, launch_fold2
+//   K1s   the CSR-stream kernels' dot epilogue with y == NULL: round(lhs[row] * sum) per thread, one partial per tile, launch_fold2
+//   else  y = A rhs by the matrix's own kernel into the handle's y staging, then launch_dot(lhs, y) over the rows that hold entries
+// sparsematrix.rs:161-171 sums lhs_i * a_ij * rhs_j over all entries in storage order; each route regroups that sum in a fixed
+// order of its own, so against the reference parity is tolerance-level, like dot -- and against the CPU model of its order
+// (tests/inner_prod_model.py) each route is bit for bit (tests/test_inner_prod_bits_gpu.py).  A row without entries is no term in
+// any of them, as in the reference, whatever lhs holds there.
+static int inner_prod_dev(smh_crs *m, const void *d_lhs, size_t lhs_len, const void *d_rhs, size_t rhs_len, int variant,
+                          double *out) {
+    if (!out) return fail(SMH_ERR_INVALID, "out is NULL");
+    *out = 0.0;
+    if (m->n_rows == 0 || m->nnz == 0) return SMH_OK;
+    const size_t vs = dtype_size(m->dtype);
+    // lhs.get(i) is evaluated inside the entry loop (sparsematrix.rs:165-168): only rows that hold entries index lhs, so a
+    // short lhs is an error only if it ends before the last non-empty row (densevec.rs:41 panics there).  The kernels read
+    // lhs for every row, so a short-but-legal lhs is continued with zeros in a scratch copy.
+    Scratch scr;
+    if (lhs_len < m->n_rows) {
+        size_t lo = 0, hi = m->n_rows;  // smallest i with offset_rows[i] == nnz; rows i.. are empty
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            uint32_t off = 0;
+            SMH_HIP(hipMemcpyAsync(&off, m->d_off + mid, sizeof off, hipMemcpyDeviceToHost, m->stream));
+            SMH_HIP(hipStreamSynchronize(m->stream));
+            if ((size_t)off >= m->nnz) hi = mid; else lo = mid + 1;
+        }
+        if (lhs_len < lo)  // row lo - 1 is the last one with entries
+            return fail(SMH_ERR_INDEX_RANGE, "index out of bounds: the len is %zu but the index is %zu", lhs_len, lo - 1);
+        char *padded = nullptr;
+        SMH_TRY(scr.alloc(&padded, m->n_rows * vs));
+        SMH_HIP(hipMemsetAsync(padded, 0, m->n_rows * vs, m->stream));
+        if (lhs_len) SMH_HIP(hipMemcpyAsync(padded, d_lhs, lhs_len * vs, hipMemcpyDeviceToDevice, m->stream));
+        d_lhs = padded;
+    }
+    void *scratch = nullptr;
+    SMH_TRY(reduce_scratch(&scratch));
+    char *res = (char *)scratch + kReducePartials * sizeof(double);
+    SMH_TRY(spmv_inner_prod(m, d_lhs, d_rhs, rhs_len, variant, scratch, res));
+    double h64 = 0;
+    float h32 = 0;
+    if (m->dtype == SMH_F64) SMH_HIP(hipMemcpyAsync(&h64, res, sizeof h64, hipMemcpyDeviceToHost, m->stream));
+    else SMH_HIP(hipMemcpyAsync(&h32, res, sizeof h32, hipMemcpyDeviceToHost, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    *out = m->dtype == SMH_F64 ? h64 : (double)h32;
+    return SMH_OK;
+}
+
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+int smh_crs_prepare(smh_crs *m, int variant) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    // what the inspectors cost (smh_crs_prepare_stats): wall time of the build, device-synchronised at both ends, and the
+    // device memory it leaves allocated (pooled blocks: everything of 1 MiB and more; scratch freed inside the build nets out)
+    const auto t0 = std::chrono::steady_clock::now();
+    const long long b0 = pool_thread_net_bytes();
+    // (AUTO's plan refused by its lazy build: resolved again, as often as the first product would)
+    int rc = prepare_forms(m, variant);
+    if (rc == SMH_OK && m->stream) {
+        const hipError_t e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    }
+    m->prepare_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    m->prepare_bytes += pool_thread_net_bytes() - b0;
+    return rc;
+}
+
+int smh_crs_prepare_stats(smh_crs *m, int variant, double *prepare_ms_out, size_t *derived_bytes_out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    SMH_TRY(smh_crs_prepare(m, variant));
+    if (prepare_ms_out) *prepare_ms_out = m->create_ms + m->prepare_ms;
+    if (derived_bytes_out) *derived_bytes_out = (size_t)(m->prepare_bytes + m->create_bytes > 0 ? m->prepare_bytes + m->create_bytes : 0);
+    return SMH_OK;
+}
+
+int smh_crs_spmv_dev(smh_crs *m, const void *x_dev, size_t x_len, void *y_dev, int variant, void *stream) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows && (!y_dev || (m->nnz && !x_dev))) return fail(SMH_ERR_INVALID, "NULL device vector");
+    return spmv_enqueue(m, x_dev, x_len, y_dev, variant, (hipStream_t)stream);
+}
+
+int smh_crs_spmv(smh_crs *m, const void *x_host, size_t x_len, void *y_host, int variant) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (m->n_rows == 0) return SMH_OK;
+    if (!y_host || (x_len && !x_host)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    const size_t vs = dtype_size(m->dtype);
+    SMH_TRY(m->stage_x.ensure_cap(x_len * vs));
+    SMH_TRY(m->stage_y.ensure_cap(m->n_rows * vs));
+    if (x_len) SMH_HIP(hipMemcpyAsync(m->stage_x.d.get(), x_host, x_len * vs, hipMemcpyHostToDevice, m->stream));
+    SMH_TRY(spmv_enqueue(m, m->stage_x.d.get(), x_len, m->stage_y.d.get(), variant, m->stream));
+    SMH_HIP(hipMemcpyAsync(y_host, m->stage_y.d.get(), m->n_rows * vs, hipMemcpyDeviceToHost, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    return SMH_OK;
+}
+
+int smh_crs_spmv_vec(smh_crs *m, const smh_vec *x, smh_vec *y, int variant) {
+    if (!m || !x || !y) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (x->dtype != m->dtype || y->dtype != m->dtype) return fail(SMH_ERR_INVALID, "dtype mismatch");
+    if (y->n != m->n_rows) return fail(SMH_ERR_DIM_MISMATCH, "Dimension mismatch");
+    SMH_TRY(spmv_enqueue(m, x->d, x->n, y->d, variant, m->stream));
+    SMH_HIP(hipStreamSynchronize(m->stream));
+    return SMH_OK;
+}
+
+int smh_crs_inner_prod_vec(smh_crs *m, const smh_vec *lhs, const smh_vec *rhs, int variant, double *out) {
+    if (!m || !lhs || !rhs) return fail(SMH_ERR_INVALID, "NULL handle");
+    if (lhs->dtype != m->dtype || rhs->dtype != m->dtype) return fail(SMH_ERR_INVALID, "value types differ");
+    SMH_HIP(hipDeviceSynchronize());  // vectors may have pending work on other streams
+    return inner_prod_dev(m, lhs->d, lhs->n, rhs->d, rhs->n, variant, out);
+}
+
+int smh_crs_inner_prod(smh_crs *m, const void *lhs_host, size_t lhs_len, const void *rhs_host, size_t rhs_len, int variant,
+                       double *out) {
+    if (!m) return fail(SMH_ERR_INVALID, "NULL handle");
+    if ((lhs_len && !lhs_host) || (rhs_len && !rhs_host)) return fail(SMH_ERR_INVALID, "NULL host vector");
+    const size_t vs = dtype_size(m->dtype);
+    // rhs goes to the x staging; lhs to a scratch allocation of its own
+    SMH_TRY(m->stage_x.ensure_cap(rhs_len * vs));
+    Scratch scr;
+    char *d_lhs = nullptr;
+    SMH_TRY(scr.alloc(&d_lhs, (lhs_len ? lhs_len : 1) * vs));
+    if (rhs_len) SMH_HIP(hipMemcpyAsync(m->stage_x.d.get(), rhs_host, rhs_len * vs, hipMemcpyHostToDevice, m->stream));
+    if (lhs_len) SMH_HIP(hipMemcpyAsync(d_lhs, lhs_host, lhs_len * vs, hipMemcpyHostToDevice, m->stream));
+    return inner_prod_dev(m, d_lhs, lhs_len, m->stage_x.d.get(), rhs_len, variant, out);
+}
+
+}  // extern "C"

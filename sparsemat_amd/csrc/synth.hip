@@ -270,3 +270,59 @@ void synth_powerlaw_lengths(uint64_t seed, size_t row_begin, size_t row_end, uin
 }
 
 }  // namespace smh
+
+using namespace smh;
+
+extern "C" {
+
+// ---- the entry points: synthetic workloads -----------------------------------------------------------------------------------------
+int smh_synth_x(smh_dtype dtype, uint64_t seed, size_t begin, size_t n, void *x_dev, void *stream) {
+    SMH_TRY(require_device());
+    return synth_x(dtype, seed, begin, n, x_dev, (hipStream_t)stream);
+}
+
+int smh_synth_fixed(smh_dtype dtype, uint64_t seed, int pattern, size_t n, uint32_t k, size_t row_begin,
+                    size_t row_end, uint32_t *offset_rows_dev, uint32_t *columns_dev, void *values_dev, void *stream) {
+    SMH_TRY(require_device());
+    if (k == 0 || n < k || row_end < row_begin || row_end > n) return fail(SMH_ERR_INVALID, "bad generator arguments");
+    if ((uint64_t)(row_end - row_begin) * k >= 0xFFFFFFFFull)
+        return fail(SMH_ERR_CAPACITY, "Maximum number of %u entries reached", 0xFFFFFFFFu);  // sparsemat_crs.rs:82-84
+    return synth_fixed(dtype, seed, pattern, n, k, row_begin, row_end, offset_rows_dev, columns_dev, values_dev,
+                       (hipStream_t)stream);
+}
+
+int smh_synth_powerlaw_cdf(uint32_t kmax, double alpha, uint32_t *cdf_host) {
+    if (!cdf_host || kmax == 0) return fail(SMH_ERR_INVALID, "bad arguments");
+    synth_powerlaw_cdf(kmax, alpha, cdf_host);
+    return SMH_OK;
+}
+
+int smh_synth_powerlaw_lengths(uint64_t seed, size_t row_begin, size_t row_end, uint32_t kmax, const uint32_t *cdf_host,
+                               uint32_t *lengths_host) {
+    if (!cdf_host || !lengths_host || kmax == 0) return fail(SMH_ERR_INVALID, "bad arguments");
+    synth_powerlaw_lengths(seed, row_begin, row_end, kmax, cdf_host, lengths_host);
+    return SMH_OK;
+}
+
+int smh_synth_fill(smh_dtype dtype, uint64_t seed, size_t n_cols, size_t row_begin, size_t row_end,
+                   const uint32_t *offset_rows_dev, uint32_t *columns_dev, void *values_dev, void *stream) {
+    SMH_TRY(require_device());
+    if (n_cols == 0) return fail(SMH_ERR_INVALID, "n_cols == 0");
+    return synth_fill(dtype, seed, n_cols, row_begin, row_end, offset_rows_dev, columns_dev, values_dev,
+                      (hipStream_t)stream);
+}
+
+int smh_synth_laplace3d(smh_dtype dtype, size_t nx, size_t ny, size_t nz, size_t row_begin, size_t row_end,
+                        uint32_t *offset_rows_dev, uint32_t *columns_dev, void *values_dev, size_t *nnz_out,
+                        void *stream) {
+    if (row_end < row_begin || row_end > nx * ny * nz) return fail(SMH_ERR_INVALID, "bad row range");
+    const size_t nnz = synth_laplace3d_nnz(nx, ny, nz, row_begin, row_end);
+    if (nnz_out) *nnz_out = nnz;
+    if (!offset_rows_dev && !columns_dev && !values_dev) return SMH_OK;  // size query only (no device needed)
+    if (nnz >= 0xFFFFFFFFull) return fail(SMH_ERR_CAPACITY, "block nnz exceeds u32");
+    SMH_TRY(require_device());
+    return synth_laplace3d(dtype, nx, ny, nz, row_begin, row_end, offset_rows_dev, columns_dev, values_dev,
+                           (hipStream_t)stream);
+}
+
+}  // extern "C"

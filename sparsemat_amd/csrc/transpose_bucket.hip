@@ -1,7 +1,7 @@
 // transpose_bucket.hip -- SparseMatrix::transpose (sparsematrix.rs:174-184) without the device-wide sort, for matrices with
 // local structure (bands, stencils, block and FEM orderings): two bucketed passes instead of a radix sort over all entries.
 //
-// The general route (capi.hip: smh_crs_transpose -> assemble.hip) sorts all (target row, source row, value) triples by
+// The general route (matops.hip: smh_crs_transpose -> assemble.hip) sorts all (target row, source row, value) triples by
 // target row with a device-wide radix sort: three passes over 12-byte pairs, 8.3 of 16 ms on BASELINE C2.  Here the target
 // rows are cut into BUCKETS of 2^shift rows (256 unless the result's rows are long) and
 //   H  k_tb_hist  every 256-row source tile counts its entries per bucket in an LDS hash table and adds the counts to the

@@ -1,5 +1,5 @@
 """numpy restatement of the DenseVec kernels (K3 / K4 of sparsemat_amd/csrc/blas1.hip) as the public entry points reach them:
-smh_vec_add / sub / scale / axpy / xpby / dot / norm_squared / norm and smh_blas_dot_dev / axpy_dev / xpby_dev (capi.hip) -- test
+smh_vec_add / sub / scale / axpy / xpby / dot / norm_squared / norm and smh_blas_dot_dev / axpy_dev / xpby_dev (the same file) -- test
 infrastructure, not product code.  The reduction tree is tests/cg_model.py's (device_sum, reduce_blocks, vec_len), which the solvers'
 tests pin; what is written here is what this layer adds: which entries an operation touches, how the scalar arrives, which vector
 length a pair of buffers selects.  All arithmetic is in T with one rounding per multiply and one per add (the library is built with

@@ -1,4 +1,4 @@
-"""numpy restatement of the device-resident CG (sparsemat_amd/csrc/cg.hip, the driver in capi.hip, the reductions of
+"""numpy restatement of the device-resident CG (sparsemat_amd/csrc/cg.hip: kernels, driver and entry points; the reductions of
 blas1.hip) and of the Jacobi-preconditioned CG (pcg.hip) -- test infrastructure, not product code.
 
 Both recurrences are written once; HOW a reduction is carried out is a parameter (``mode``):

@@ -1,4 +1,4 @@
-"""The device-resident CG (K5: cg.hip, the driver in capi.hip, blas1.hip's reductions) and the Jacobi-PCG (pcg.hip) pinned
+"""The device-resident CG (K5: cg.hip with its driver and entry points, blas1.hip's reductions) and the Jacobi-PCG (pcg.hip) pinned
 BIT FOR BIT to tests/cg_model.py's restatement of their own summation order: x, r.r (as f64(T)) and the number of entered
 bodies -- at the sizes where each code path is first entered (vector tails of every length, fewer elements than lanes, a
 second workgroup, a thread's second trip, every grid cap), on unaligned vectors (the VEC=false kernels), from zero and
