@@ -28,6 +28,7 @@
 // over the stage; a row that straddles passes carries its accumulator, so the adds stay in storage order:
 // K1s is correct AND bit-exact for every matrix, the tables and the tile height only change speed.
 #include "internal.hpp"
+#include "stream_stage.hpp"
 
 namespace smh {
 
@@ -37,11 +38,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ uint32_t skew(uint32_t i) { return i + (i >> 5); }  // +1 word every 32: breaks 2^k strides
-
-__device__ __forceinline__ float st_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double st_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float st_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double st_add(double a, double b) { return __dadd_rn(a, b); }
 
 // ---- inspector: up to 4 column intervals per tile -------------------------------------------------------
 // win[8*t + 2k], win[8*t + 2k + 1] = [lo, hi) of interval k (sorted, disjoint; hi == lo: unused).  All zero:
@@ -225,10 +221,9 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
     __shared__ uint32_t s_wtot[L8 ? kBlock / kWave : 1];
     __shared__ T s_prod[CAP + CAP / 32 + 8];
     // bijective XCD-aware remap: XCD g (= blockIdx % 8) walks a contiguous run of tiles
-    const uint64_t q = n_tiles >> 3, rm = n_tiles & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
     // (n_tiles = the tiles of THIS launch, tile0 = the first of them: a launch may cover a run of the matrix's tiles only -- the
     // partitioned product multiplies a block's boundary rows before its interior ones, par.hip)
-    const uint64_t tile = tile0 + (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + idx;
+    const uint64_t tile = tile0 + stage::xcd_run(n_tiles, blockIdx.x & 7).first + (blockIdx.x >> 3);
     constexpr uint64_t TILE_ROWS = (uint64_t)kStreamRows * RPT;
     const uint64_t r0 = tile * TILE_ROWS;
     const uint64_t r1 = r0 + TILE_ROWS < n_rows ? r0 + TILE_ROWS : n_rows;
@@ -287,23 +282,15 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
     T xr[XS ? XS : 1][4];
     uint32_t xs_tot = 0;
     if constexpr (XS) {
-        const uint32_t *w = cwin + 8 * tile;  // scalar loads (the starts are cb0..cb3 already)
-        const uint32_t e0 = w[1], e1 = w[3], e2 = w[5], e3 = w[7];
-        const uint32_t al0 = cb0 & ~3u, al1 = cb1 & ~3u, al2 = cb2 & ~3u, al3 = cb3 & ~3u;
-        const uint32_t n0 = e0 > cb0 ? (e0 - al0 + 3u) >> 2 : 0u, n1 = e1 > cb1 ? (e1 - al1 + 3u) >> 2 : 0u;
-        const uint32_t n2 = e2 > cb2 ? (e2 - al2 + 3u) >> 2 : 0u, n3 = e3 > cb3 ? (e3 - al3 + 3u) >> 2 : 0u;
-        const uint32_t p1 = n0, p2 = p1 + n1, p3 = p2 + n2;
-        xs_tot = p3 + n3;  // (<= XS * kBlock chunks and inside x: checked by the host, smh_crs::stream_xs_*)
-        sb0 = cb0 & 3u; sb1 = 4u * p1 + (cb1 & 3u); sb2 = 4u * p2 + (cb2 & 3u); sb3 = 4u * p3 + (cb3 & 3u);
+        const stage::Layout lay = stage::layout(cwin + 8 * tile);  // scalar loads
+        xs_tot = lay.chunks();  // (<= XS * kBlock chunks and inside x: checked by the host, smh_crs::stream_xs_*)
+        sb0 = lay.first_entry0(); sb1 = lay.first_entry1(); sb2 = lay.first_entry2(); sb3 = lay.first_entry3();
 #pragma unroll
         for (int u = 0; u < XS; ++u) {
             const uint32_t j = tid + (uint32_t)u * kBlock;
             xr[u][0] = xr[u][1] = xr[u][2] = xr[u][3] = T(0);
             if (j < xs_tot) {
-                const uint32_t q = (uint32_t)(j >= p1) + (uint32_t)(j >= p2) + (uint32_t)(j >= p3);
-                const uint32_t pq = q == 0u ? 0u : q == 1u ? p1 : q == 2u ? p2 : p3;
-                const uint32_t al = q == 0u ? al0 : q == 1u ? al1 : q == 2u ? al2 : al3;
-                const T *g = x + ((uint64_t)al + 4u * (j - pq));
+                const T *g = x + 4ull * (uint64_t)lay.x_chunk(j);
                 if constexpr (sizeof(T) == 4) {
                     const f32x4 a = *reinterpret_cast<const f32x4 *>(g);
                     xr[u][0] = a.x; xr[u][1] = a.y; xr[u][2] = a.z; xr[u][3] = a.w;
@@ -390,7 +377,7 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
                     const uint32_t idx = ((uint32_t)(sbp >> ((cd >> 14) << 4)) & 0xFFFFu) + (cd & 16383u);
                     const T xe = s_xs[idx & (uint32_t)(kXsCap - 1)];  // (slots outside the tile carry other tiles' codes)
                     const uint32_t rel = j + (uint32_t)e - lo;  // (wraps below lo: fails the test too)
-                    s_prod[rel < span ? skew(rel) : kDump] = st_mul(xe, v[it][e]);
+                    s_prod[rel < span ? skew(rel) : kDump] = stage::mul(xe, v[it][e]);
                 }
             }
         }
@@ -405,8 +392,7 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
                 if (i >= lo && i < hi) {
                     if constexpr (C16) {
                         const uint32_t cd = (e & 1) ? (c[it][e >> 1] >> 16) : (c[it][e >> 1] & 0xFFFFu);
-                        if constexpr (XS) xv[it][e] = s_xs[decode_col(cd, sb0, sb1, sb2, sb3)];
-                        else xv[it][e] = x[decode_col(cd, cb0, cb1, cb2, cb3)];
+                        xv[it][e] = x[decode_col(cd, cb0, cb1, cb2, cb3)];
                     } else {
                         xv[it][e] = x[c[it][e]];
                     }
@@ -419,7 +405,7 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const uint32_t i = j + e;
-                if (i >= lo && i < hi) s_prod[skew(i - lo)] = st_mul(xv[it][e], v[it][e]);
+                if (i >= lo && i < hi) s_prod[skew(i - lo)] = stage::mul(xv[it][e], v[it][e]);
             }
         }
         __syncthreads();
@@ -437,12 +423,12 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
             T acc = sum[rr];
             for (; i + 4 <= iend; i += 4) {
                 const T p0 = s_prod[skew(i)], p1 = s_prod[skew(i + 1)], p2 = s_prod[skew(i + 2)], p3 = s_prod[skew(i + 3)];
-                acc = st_add(acc, p0);
-                acc = st_add(acc, p1);
-                acc = st_add(acc, p2);
-                acc = st_add(acc, p3);
+                acc = stage::add(acc, p0);
+                acc = stage::add(acc, p1);
+                acc = stage::add(acc, p2);
+                acc = stage::add(acc, p3);
             }
-            for (; i < iend; ++i) acc = st_add(acc, s_prod[skew(i)]);
+            for (; i < iend; ++i) acc = stage::add(acc, s_prod[skew(i)]);
             sum[rr] = acc;
         }
         ps = pe;
@@ -453,11 +439,11 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
         const uint64_t r = r0 + (uint64_t)rr * kBlock + tid;
 #if SMH_STREAM_NT_STORE  // A/B: y leaves with a non-temporal store (it is not read again by this kernel)
         if (r < r1 && (!DOT || y)) {  // (DOT with y == NULL: only lhs . (A x) is wanted -- SparseMatrix::inner_prod)
-            if constexpr (ACC) y[r] = st_add(y[r], sum[rr]);
+            if constexpr (ACC) y[r] = stage::add(y[r], sum[rr]);
             else __builtin_nontemporal_store(sum[rr], &y[r]);
         }
 #else
-        if (r < r1 && (!DOT || y)) y[r] = ACC ? st_add(y[r], sum[rr]) : sum[rr];
+        if (r < r1 && (!DOT || y)) y[r] = ACC ? stage::add(y[r], sum[rr]) : sum[rr];
 #endif
     }
     if constexpr (DOT) {
@@ -513,37 +499,29 @@ static int launch_stream_t(const uint32_t *off, const uint32_t *col, const T *va
             if (dot_partials) SMH_ST_LAUNCH(R, true, true, C); else SMH_ST_LAUNCH(R, false, true, C);   \
         }                                                                         \
     } while (0)
+    // column codes + byte row lengths (single-pass 256-row tiles).  Then: no tile beyond kStreamCapSmall entries (stencils: 7 x 256 =
+    // 1792) -> two chunk slots per thread instead of five: 32-34 VGPRs instead of 67-70 (f32), 46-50 instead of ~106 (f64: 4 -> 8 waves
+    // per SIMD).  Measured, one box: 400^3 f64 1.412 -> 1.330 ms; 512^3 f32 unchanged (1.503 / 1.515 ms) -- neither registers nor
+    // instruction count bound the f32 kernel: rocprofv3 shows the texture addresser busy 70 % of the time (8 gather instructions per
+    // thread and tile).  With small tiles, x staged in LDS: 2048 entries (xs == 2) or 4096 (xs == 4: wider grids)
+    const bool coded_l8 = code && cwin && len8 && tbase && single_pass;
+#define SMH_ST_L8(CAPV, P)                                                                                                                   \
+    do {                                                                                                                                     \
+        if (dot_partials)                                                                                                                    \
+            hipLaunchKernelGGL((k_spmv_stream<T, 1, true, false, false, CAPV, true, true, P>), grid, block, lds_pad, s, off, col, val, x, y, \
+                               (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);   \
+        else                                                                                                                                 \
+            hipLaunchKernelGGL((k_spmv_stream<T, 1, false, false, false, CAPV, true, true, P>), grid, block, lds_pad, s, off, col, val, x, y, \
+                               (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);   \
+    } while (0)
     if (rpt == 2) SMH_ST_PICK(2, false);
-#define SMH_ST_XS(D, P)                                                                                                                     \
-    hipLaunchKernelGGL((k_spmv_stream<T, 1, D, false, false, kStreamCapSmall, true, true, P>), grid, block, lds_pad, s, off, col, val, x, y, \
-                       (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0)
-    else if (code && cwin && len8 && tbase && single_pass && small_tiles && xs == 2) {  // ... and x staged in LDS (2048 entries)
-        if (dot_partials) SMH_ST_XS(true, 2); else SMH_ST_XS(false, 2);
+    else if (coded_l8) {
+        if (!small_tiles) SMH_ST_L8(kStreamCap, 0);
+        else if (xs == 2) SMH_ST_L8(kStreamCapSmall, 2);
+        else if (xs == 4) SMH_ST_L8(kStreamCapSmall, 4);
+        else SMH_ST_L8(kStreamCapSmall, 0);
     }
-    else if (code && cwin && len8 && tbase && single_pass && small_tiles && xs == 4) {  // ... (4096 entries: wider grids)
-        if (dot_partials) SMH_ST_XS(true, 4); else SMH_ST_XS(false, 4);
-    }
-#undef SMH_ST_XS
-    else if (code && cwin && len8 && tbase && single_pass && small_tiles) {
-        // ... and no tile beyond kStreamCapSmall entries (stencils: 7 x 256 = 1792): two chunk slots per thread instead of five.
-        // 32-34 VGPRs instead of 67-70 (f32), 46-50 instead of ~106 (f64: 4 -> 8 waves per SIMD).  Measured, one box: 400^3 f64
-        // 1.412 -> 1.330 ms; 512^3 f32 unchanged (1.503 / 1.515 ms) -- neither registers nor instruction count bound the f32
-        // kernel: rocprofv3 shows the texture addresser busy 70 % of the time (8 gather instructions per thread and tile)
-        if (dot_partials)
-            hipLaunchKernelGGL((k_spmv_stream<T, 1, true, false, false, kStreamCapSmall, true, true>), grid, block, lds_pad, s, off, col, val,
-                               x, y, (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);
-        else
-            hipLaunchKernelGGL((k_spmv_stream<T, 1, false, false, false, kStreamCapSmall, true, true>), grid, block, lds_pad, s, off, col, val,
-                               x, y, (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);
-    }
-    else if (code && cwin && len8 && tbase && single_pass) {  // column codes + byte row lengths
-        if (dot_partials)
-            hipLaunchKernelGGL((k_spmv_stream<T, 1, true, false, false, kStreamCap, true, true>), grid, block, lds_pad, s, off, col, val,
-                               x, y, (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);
-        else
-            hipLaunchKernelGGL((k_spmv_stream<T, 1, false, false, false, kStreamCap, true, true>), grid, block, lds_pad, s, off, col, val,
-                               x, y, (uint64_t)n_rows, (uint64_t)nnz, readable, n_tiles, dot_partials, code, cwin, len8, tbase, dot_lhs, tile0);
-    }
+#undef SMH_ST_L8
     else if (code && cwin) SMH_ST_PICK(1, true);  // 16-bit column codes (every tile described)
     else SMH_ST_PICK(1, false);
 #undef SMH_ST_PICK
@@ -703,18 +681,9 @@ __global__ void __launch_bounds__(kBlock)
 k_stream_xs_stats(const uint32_t *__restrict__ win, uint64_t n_tiles, uint32_t *__restrict__ out) {
     uint32_t mc = 0, me = 0;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t *w = win + 8 * t;
-        uint32_t chunks = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t a = w[2 * q], e = w[2 * q + 1];
-            if (e > a) {
-                const uint32_t al = a & ~3u, n = (e - al + 3u) >> 2;
-                chunks += n;
-                me = max(me, al + 4u * n);
-            }
-        }
-        mc = max(mc, chunks);
+        const stage::Layout lay = stage::layout(win + 8 * t);
+        mc = max(mc, lay.chunks());
+        me = max(me, lay.end());
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {

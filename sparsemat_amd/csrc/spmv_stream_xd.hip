@@ -18,7 +18,10 @@
 //     a loop); the row-length prefix sum is a DPP scan.
 // Without the skew the row sums of rows of EVEN length collide in LDS (stride 8 -> 8 lanes per bank); the handle takes this form
 // only when most rows have an odd length -- every stencil with a diagonal: 5, 7, 9, 27 points -- (crs_forms.hip, stream_cfg).
+#include <atomic>
+
 #include "internal.hpp"
+#include "stream_stage.hpp"
 
 namespace smh {
 
@@ -29,11 +32,6 @@ typedef uint32_t xd_u2 __attribute__((ext_vector_type(2)));
 typedef float xd_f4 __attribute__((ext_vector_type(4)));
 typedef double xd_d2 __attribute__((ext_vector_type(2)));
 constexpr int kXdRsrc = 0x00020000;  // dword 3 of a raw buffer descriptor on gfx9 (32-bit data format)
-
-__device__ __forceinline__ float xd_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double xd_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float xd_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double xd_add(double a, double b) { return __dadd_rn(a, b); }
 
 template <int CTRL, int ROWS> __device__ __forceinline__ uint32_t xd_dpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, false);  // lanes without a source receive 0
@@ -46,6 +44,9 @@ __device__ __forceinline__ uint32_t xd_wave_scan(uint32_t v) {
     v += xd_dpp<0x118, 0xF>(v);  // row_shr:8
     v += xd_dpp<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
     v += xd_dpp<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3
+    // (opaque from here on.  Seen as its argument + six DPP terms, `incl - my_len` of the row sums is rewritten as the sum of those
+    // terms; they then live across blocks and the six moves are no longer folded into their adds: 13 instructions, 6 registers)
+    asm("" : "+v"(v));
     return v;
 }
 
@@ -59,20 +60,195 @@ static_assert(kStreamCapSmall + 3 <= kXdSlots, "a tile's entries from an aligned
 // dictionary the kernel keeps in LDS, and the value array is not read at all: 2 bytes per entry leave HBM instead of 6 (f32) / 10
 // (f64).  The product is x times the very same bit pattern as before, the adds are in storage order: still bit for bit the
 // reference's result.  (stream_cfg in crs_forms.hip decides; k_value_dict_* below build the dictionary, exactly, or say that it does not exist.)
-template <typename T, int XS> struct XdBits {
-    static constexpr uint32_t kLow = sizeof(T) == 8 ? 3u : 2u;                 // free low bits
-    static constexpr uint32_t kIdx = XS == 4 ? 12u : 11u;                      // bits of an entry index inside the stage
-    static constexpr uint32_t kOfsMask = ((1u << (kLow + kIdx)) - 1u) & ~((1u << kLow) - 1u);
-    static constexpr uint32_t kValues = 1u << (16u - kIdx);                    // 32 / 16 dictionary entries
-    static constexpr uint32_t kHigh = 16u - (kLow + kIdx);                     // spare bits above the offset: 3 (f32, 2048-entry stage) or 2
-    __device__ static __forceinline__ uint32_t ofs(uint32_t c) { return c & kOfsMask; }
-    __device__ static __forceinline__ uint32_t vidx(uint32_t c) { return (c & ((1u << kLow) - 1u)) | ((c >> (kLow + kIdx)) << kLow); }
-    // dictionaries of at most 2^kHigh values (every stencil) keep the index in the HIGH bits alone: one shift instead of three operations
-    __device__ static __forceinline__ uint32_t vidx_high(uint32_t c) { return c >> (kLow + kIdx); }
+// (the code's bits: stream_stage.hpp.  Dictionaries small enough for the bits ABOVE the offset -- every stencil's -- keep the index
+// there alone: one shift instead of three operations, VD == 2 below.)
+
+// ---- one tile, step by step ---------------------------------------------------------------------------------------------------------
+// What a thread holds of a tile between requesting it and summing its row.  The per-tile kernel has one set and takes the steps once;
+// the persistent kernel has two and requests the next tile's while it multiplies the current one's.
+// XS: 16-byte chunks of x per thread the tile's stage holds (2 or 4); VALS: the value array is read (no dictionary)
+template <typename T, int XS, bool VALS>
+struct XdTileRegs {
+    uint32_t k0, pa, my_len, xs_tot;
+    uint64_t r0, tile;
+    T dl;
+    T xr[XS][4];
+    uint32_t xpiece[XS][2];  // f64: the two 16-byte pieces (2 entries each) of the stage this thread fills
+    xd_u2 cw[2];
+    T v[VALS ? 2 : 1][4];
+    uint32_t epos[2][2];  // f64: the entry positions (relative to pa) of the thread's two 2-entry pieces
 };
 
-// XS: 16-byte chunks of x per thread the tile's stage holds (2 or 4); VD: the codes carry value-dictionary indices (val is not read) --
-// 1: in the low and the high spare bits (up to 32 / 16 values), 2: in the high ones alone (up to 8 / 4 values)
+// step 1: everything of `tile` a thread needs, requested -- table words, row length, dot lhs, the x chunks, then the tile's entries
+template <typename T, bool DOT, int XS, bool VALS>
+__device__ __forceinline__ void xd_request(XdTileRegs<T, XS, VALS> &R, uint64_t tile, const T *__restrict__ val, const T *__restrict__ x,
+                                           uint64_t n_rows, const uint16_t *__restrict__ scode, const uint32_t *__restrict__ cwin,
+                                           const uint8_t *__restrict__ len8, const uint32_t *__restrict__ tbase, const T *__restrict__ dot_lhs) {
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
+    const uint32_t wbase = tid & ~(uint32_t)(kWave - 1);  // first thread of this wavefront
+    R.tile = tile;
+    R.r0 = tile * (uint64_t)kStreamRows;
+    const uint32_t k0 = tbase[tile], k1 = tbase[tile + 1];  // tile-uniform: scalar loads
+    R.k0 = k0;
+    R.my_len = len8[R.r0 + tid];  // (the byte array is padded to whole tiles with zeros)
+    R.dl = T(0);
+    if constexpr (DOT) R.dl = R.r0 + tid < n_rows ? dot_lhs[R.r0 + tid] : T(0);  // requested now: its latency hides behind the tile
+    // ---- the tile's intervals of x: 16-byte chunks, requested before the tile's own entries (they are needed first) ----
+    const stage::Layout lay = stage::layout(cwin + 8 * tile);  // scalar loads
+    R.xs_tot = lay.chunks();  // (<= XS * kBlock chunks, inside x: checked by the host)
+    // f64: a thread's 32 bytes (of x, of the values, of the products) are TWO 16-byte pieces, and a wavefront's lanes take piece
+    // l and piece 64 + l of its 128 -- each load / store instruction then covers 1 KiB of contiguous bytes.  With 32 contiguous
+    // bytes per lane (rounds 2-3) each of the two instructions touched every line and used half of it: what kept K1r's f64 kernel
+    // at 0.8 of its f32 rate (DESIGN.md, K1r) did the same here.  Which thread moves which piece changes no arithmetic: the
+    // products land in the same stage slots and are added in storage order as before (bit-exact).
+#pragma unroll
+    for (int u = 0; u < XS; ++u) {
+        R.xr[u][0] = R.xr[u][1] = R.xr[u][2] = R.xr[u][3] = T(0);
+        if constexpr (sizeof(T) == 4) {
+            const uint32_t j = tid + (uint32_t)u * kBlock;
+            if (j < R.xs_tot) {
+                const xd_f4 a = *reinterpret_cast<const xd_f4 *>(x + 4ull * (uint64_t)lay.x_chunk(j));
+                R.xr[u][0] = a.x; R.xr[u][1] = a.y; R.xr[u][2] = a.z; R.xr[u][3] = a.w;
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t pi = 2u * ((uint32_t)u * kBlock + wbase) + (uint32_t)h * kWave + lane;  // piece of the stage
+                const uint32_t j = pi >> 1;                                                            // its chunk
+                R.xpiece[u][h] = pi;
+                if (j < R.xs_tot) {
+                    const xd_d2 a = *reinterpret_cast<const xd_d2 *>(x + 4ull * (uint64_t)lay.x_chunk(j) + 2u * (pi & 1u));
+                    R.xr[u][2 * h] = a.x; R.xr[u][2 * h + 1] = a.y;
+                }
+            }
+        }
+    }
+    // ---- the tile's entries: two chunks per thread from the aligned start `pa`; a descriptor that ends with the tile's last
+    // entry makes every slot beyond it read as zero (code 0: the stage's first entry; value 0) ----
+    const uint32_t pa = k0 & ~3u, hi = k1 - pa;  // hi <= kXdSlots (kStreamCapSmall, checked by the host)
+    R.pa = pa;
+    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void *)(scode + pa), 0, (int)(((hi + 3u) & ~3u) * 2u), kXdRsrc);
+    __amdgpu_buffer_rsrc_t rv = rc;  // (not used without the values)
+    if constexpr (VALS) rv = __builtin_amdgcn_make_buffer_rsrc((void *)(val + pa), 0, (int)(hi * (uint32_t)sizeof(T)), kXdRsrc);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        if constexpr (VALS) R.v[it][0] = R.v[it][1] = R.v[it][2] = R.v[it][3] = T(0);
+        if constexpr (sizeof(T) == 4) {
+            const uint32_t j = 4u * tid + (uint32_t)it * (4u * kBlock);
+            R.cw[it] = __builtin_bit_cast(xd_u2, __builtin_amdgcn_raw_buffer_load_b64(rc, (int)(j * 2u), 0, 2 /* nt */));
+            if constexpr (VALS) {
+                const xd_f4 a = __builtin_bit_cast(xd_f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(j * 4u), 0, 2));
+                R.v[it][0] = a.x; R.v[it][1] = a.y; R.v[it][2] = a.z; R.v[it][3] = a.w;
+            }
+        } else {
+            const uint32_t e0p = 4u * ((uint32_t)it * kBlock + wbase) + 2u * lane, e1p = e0p + 2u * kWave;
+            R.epos[it][0] = e0p; R.epos[it][1] = e1p;
+            R.cw[it].x = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e0p * 2u), 0, 2 /* nt */);
+            R.cw[it].y = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e1p * 2u), 0, 2);
+            if constexpr (VALS) {
+                const xd_d2 a = __builtin_bit_cast(xd_d2, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(e0p * 8u), 0, 2));
+                const xd_d2 b = __builtin_bit_cast(xd_d2, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(e1p * 8u), 0, 2));
+                R.v[it][0] = a.x; R.v[it][1] = a.y; R.v[it][2] = b.x; R.v[it][3] = b.y;
+            }
+        }
+    }
+}
+
+// step 2: x into its stage
+template <typename T, int XS, bool VALS>
+__device__ __forceinline__ void xd_fill_stage(const XdTileRegs<T, XS, VALS> &R, T *s_xs) {
+#pragma unroll
+    for (int u = 0; u < XS; ++u) {
+        if constexpr (sizeof(T) == 4) {
+            const uint32_t j = threadIdx.x + (uint32_t)u * kBlock;
+            if (j < R.xs_tot) {
+                xd_f4 a; a.x = R.xr[u][0]; a.y = R.xr[u][1]; a.z = R.xr[u][2]; a.w = R.xr[u][3];
+                *reinterpret_cast<xd_f4 *>(&s_xs[4u * j]) = a;
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if ((R.xpiece[u][h] >> 1) < R.xs_tot) {
+                    xd_d2 a; a.x = R.xr[u][2 * h]; a.y = R.xr[u][2 * h + 1];
+                    *reinterpret_cast<xd_d2 *>(&s_xs[2u * R.xpiece[u][h]]) = a;
+                }
+        }
+    }
+}
+
+// step 3: products -- x from the stage by byte offset, four products per 16-byte store at the chunk's own position.
+// VD: the codes carry value-dictionary indices -- 1: in the low and the high spare bits, 2: in the high ones alone
+template <typename T, int XS, int VD, bool VALS>
+__device__ __forceinline__ void xd_products(const XdTileRegs<T, XS, VALS> &R, const T *s_xs, const T *s_dict, T *s_prod) {
+    static_assert(VALS == (VD == 0), "an entry's value comes from the value array or from the dictionary");
+    const char *xs_bytes = reinterpret_cast<const char *>(s_xs);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        T p[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t cword = (e >> 1) ? R.cw[it].y : R.cw[it].x;
+            const uint32_t code = (e & 1) ? (cword >> 16) : (cword & 0xFFFFu);
+            if constexpr (VD) {
+                // (a slot past the tile reads code 0: stage entry 0 times dictionary entry 0 -- never added to any row)
+                const uint32_t vi = VD == 2 ? stage::code_value_high(code, sizeof(T), XS) : stage::code_value(code, sizeof(T), XS);
+                p[e] = stage::mul(*reinterpret_cast<const T *>(xs_bytes + stage::code_ofs(code, sizeof(T), XS)), s_dict[vi]);
+            } else {
+                p[e] = stage::mul(*reinterpret_cast<const T *>(xs_bytes + code), R.v[it][e]);
+            }
+        }
+        if constexpr (sizeof(T) == 4) {
+            const uint32_t j = 4u * threadIdx.x + (uint32_t)it * (4u * kBlock);
+            xd_f4 a; a.x = p[0]; a.y = p[1]; a.z = p[2]; a.w = p[3];
+            *reinterpret_cast<xd_f4 *>(&s_prod[j]) = a;
+        } else {
+            xd_d2 a, b; a.x = p[0]; a.y = p[1]; b.x = p[2]; b.y = p[3];
+            *reinterpret_cast<xd_d2 *>(&s_prod[R.epos[it][0]]) = a;
+            *reinterpret_cast<xd_d2 *>(&s_prod[R.epos[it][1]]) = b;
+        }
+    }
+}
+
+// step 4: the row's sum in storage order, one rounded add per entry (reference: sum += product), and its store.  incl: the wavefront's
+// inclusive scan of the row lengths, s_wtot: the wavefronts' totals.  Returns (DOT) the wavefront's share of lhs . (A x) in lane 63 --
+// fixed order: lanes by the DPP scan network, as K1s; the caller adds the wavefronts in index order
+template <typename T, bool DOT, int XS, bool VALS>
+__device__ __forceinline__ T xd_row_sum(const XdTileRegs<T, XS, VALS> &R, uint32_t incl, uint32_t wave, const uint32_t *s_wtot, const T *s_prod,
+                                       T *__restrict__ y, uint64_t n_rows) {
+    uint32_t before = 0;  // entries of the tile in the waves before this one (wave-uniform)
+#pragma unroll
+    for (int ww = 0; ww < kBlock / kWave - 1; ++ww) before += (uint32_t)ww < wave ? s_wtot[ww] : 0u;
+    const T *pp = s_prod + ((R.k0 - R.pa) + before + (incl - R.my_len));
+    T q[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] = pp[i];
+    T acc = T(0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if ((uint32_t)i < R.my_len) acc = stage::add(acc, q[i]);
+    for (uint32_t i = 8; i < R.my_len; ++i) acc = stage::add(acc, pp[i]);
+    const uint64_t r = R.r0 + threadIdx.x;
+    if (r < n_rows && (!DOT || y)) __builtin_nontemporal_store(acc, &y[r]);  // (DOT with y == NULL: only lhs . (A x) is wanted)
+    T d = T(0);
+    if constexpr (DOT) {
+        if (r < n_rows && (y || R.my_len)) d += R.dl * acc;  // (as K1s: 0 + the product; inner_prod, y == NULL: not of a row without entries)
+        d = wave_sum_to_lane63(d);
+    }
+    return d;
+}
+
+// the wavefronts' shares of a tile's dot, added in index order by thread 0
+template <typename T>
+__device__ __forceinline__ void xd_fold_dot(const T *s_red, T *__restrict__ dot_partials, uint64_t tile) {
+    if (threadIdx.x == 0) {
+        T t = T(0);
+#pragma unroll
+        for (int ww = 0; ww < kBlock / kWave; ++ww) t += s_red[ww];
+        dot_partials[tile] = t;
+    }
+}
+
+// ---- K1s XD, one workgroup per tile: the four steps once.  VD = 0 reads the value array ---------------------------------------------
 template <typename T, bool DOT, int XS, int VD = 0>
 __global__ void __launch_bounds__(kBlock)
 k_spmv_stream_xd(const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows, uint64_t n_tiles,
@@ -89,177 +265,27 @@ k_spmv_stream_xd(const T *__restrict__ val, const T *__restrict__ x, T *__restri
     __shared__ __attribute__((aligned(16))) T s_xs[kXsCap];
     __shared__ __attribute__((aligned(16))) T s_prod[kXdSlots + 8];  // (+8: a row's eight unconditional reads may pass the tile's end)
     __shared__ uint32_t s_wtot[kBlock / kWave];
-    // bijective XCD-aware remap: XCD g (= blockIdx % 8) walks a contiguous run of the launch's tiles (as K1s)
-    const uint64_t q8 = n_tiles >> 3, rm = n_tiles & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const uint64_t tile = tile0 + (xcd < rm ? xcd * (q8 + 1) : rm * (q8 + 1) + (xcd - rm) * q8) + idx;
-    const uint64_t r0 = tile * (uint64_t)kStreamRows;
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / kWave));
-    const uint32_t k0 = tbase[tile], k1 = tbase[tile + 1];  // tile-uniform: scalar loads
-    const uint32_t my_len = len8[r0 + tid];                 // (the byte array is padded to whole tiles with zeros)
-    T dl = T(0);
-    if constexpr (DOT) dl = r0 + tid < n_rows ? dot_lhs[r0 + tid] : T(0);  // requested now: its latency hides behind the tile
-    // ---- the tile's intervals of x: 16-byte chunks, requested before the tile's own entries (they are needed first) ----
-    const uint32_t *w = cwin + 8 * tile;  // scalar loads
-    const uint32_t cb0 = w[0], e0 = w[1], cb1 = w[2], e1 = w[3], cb2 = w[4], e2 = w[5], cb3 = w[6], e3 = w[7];
-    const uint32_t al0 = cb0 & ~3u, al1 = cb1 & ~3u, al2 = cb2 & ~3u, al3 = cb3 & ~3u;
-    const uint32_t n0 = e0 > cb0 ? (e0 - al0 + 3u) >> 2 : 0u, n1 = e1 > cb1 ? (e1 - al1 + 3u) >> 2 : 0u;
-    const uint32_t n2 = e2 > cb2 ? (e2 - al2 + 3u) >> 2 : 0u, n3 = e3 > cb3 ? (e3 - al3 + 3u) >> 2 : 0u;
-    const uint32_t p1 = n0, p2 = p1 + n1, p3 = p2 + n2, xs_tot = p3 + n3;  // (<= XS * kBlock chunks, inside x: checked by the host)
-    const uint32_t d0 = al0 >> 2, d1 = (al1 >> 2) - p1, d2 = (al2 >> 2) - p2, d3 = (al3 >> 2) - p3;  // (mod 2^32; j + d_q is a chunk of x)
-    // f64: a thread's 32 bytes (of x, of the values, of the products) are TWO 16-byte pieces, and a wavefront's lanes take piece
-    // l and piece 64 + l of its 128 -- each load / store instruction then covers 1 KiB of contiguous bytes.  With 32 contiguous
-    // bytes per lane (rounds 2-3) each of the two instructions touched every line and used half of it: what kept K1r's f64 kernel
-    // at 0.8 of its f32 rate (DESIGN.md, K1r) did the same here.  Which thread moves which piece changes no arithmetic: the
-    // products land in the same stage slots and are added in storage order as before (bit-exact).
-    const uint32_t wbase = tid & ~(uint32_t)(kWave - 1);  // first thread of this wavefront
-    T xr[XS][4];
-    uint32_t xpiece[XS][2];  // f64: the two 16-byte pieces (2 entries each) of the stage this thread fills
-#pragma unroll
-    for (int u = 0; u < XS; ++u) {
-        xr[u][0] = xr[u][1] = xr[u][2] = xr[u][3] = T(0);
-        if constexpr (sizeof(T) == 4) {
-            const uint32_t j = tid + (uint32_t)u * kBlock;
-            xpiece[u][0] = xpiece[u][1] = 0;
-            if (j < xs_tot) {
-                // chunk j of the stage = chunk j + d_q of x, q = the interval j falls into (tile-uniform offsets: three selects)
-                uint32_t d = d0;
-                d = j >= p1 ? d1 : d;
-                d = j >= p2 ? d2 : d;
-                d = j >= p3 ? d3 : d;
-                const T *g = x + 4ull * (uint64_t)(j + d);
-                const xd_f4 a = *reinterpret_cast<const xd_f4 *>(g);
-                xr[u][0] = a.x; xr[u][1] = a.y; xr[u][2] = a.z; xr[u][3] = a.w;
-            }
-        } else {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t pi = 2u * ((uint32_t)u * kBlock + wbase) + (uint32_t)h * kWave + lane;  // piece of the stage
-                const uint32_t j = pi >> 1;                                                            // its chunk
-                xpiece[u][h] = pi;
-                if (j < xs_tot) {
-                    uint32_t d = d0;
-                    d = j >= p1 ? d1 : d;
-                    d = j >= p2 ? d2 : d;
-                    d = j >= p3 ? d3 : d;
-                    const xd_d2 a = *reinterpret_cast<const xd_d2 *>(x + 4ull * (uint64_t)(j + d) + 2u * (pi & 1u));
-                    xr[u][2 * h] = a.x; xr[u][2 * h + 1] = a.y;
-                }
-            }
-        }
-    }
-    // ---- the tile's entries: two chunks per thread from the aligned start `pa`; a descriptor that ends with the tile's last
-    // entry makes every slot beyond it read as zero (code 0: the stage's first entry; value 0) ----
-    const uint32_t pa = k0 & ~3u, hi = k1 - pa;  // hi <= kXdSlots (kStreamCapSmall, checked by the host)
-    const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void *)(scode + pa), 0, (int)(((hi + 3u) & ~3u) * 2u), kXdRsrc);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void *)(val + pa), 0, (int)(hi * (uint32_t)sizeof(T)), kXdRsrc);
-    xd_u2 cw[2];
-    T v[2][4];
-    uint32_t epos[2][2];  // f64: the entry positions (relative to pa) of the thread's two 2-entry pieces
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        v[it][0] = v[it][1] = v[it][2] = v[it][3] = T(0);
-        if constexpr (sizeof(T) == 4) {
-            const uint32_t j = 4u * tid + (uint32_t)it * (4u * kBlock);
-            epos[it][0] = epos[it][1] = 0;
-            cw[it] = __builtin_bit_cast(xd_u2, __builtin_amdgcn_raw_buffer_load_b64(rc, (int)(j * 2u), 0, 2 /* nt */));
-            if constexpr (!VD) {
-                const xd_f4 a = __builtin_bit_cast(xd_f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(j * 4u), 0, 2));
-                v[it][0] = a.x; v[it][1] = a.y; v[it][2] = a.z; v[it][3] = a.w;
-            }
-        } else {
-            const uint32_t e0p = 4u * ((uint32_t)it * kBlock + wbase) + 2u * lane, e1p = e0p + 2u * kWave;
-            epos[it][0] = e0p; epos[it][1] = e1p;
-            cw[it].x = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e0p * 2u), 0, 2 /* nt */);
-            cw[it].y = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e1p * 2u), 0, 2);
-            if constexpr (!VD) {
-                const xd_d2 a = __builtin_bit_cast(xd_d2, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(e0p * 8u), 0, 2));
-                const xd_d2 b = __builtin_bit_cast(xd_d2, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(e1p * 8u), 0, 2));
-                v[it][0] = a.x; v[it][1] = a.y; v[it][2] = b.x; v[it][3] = b.y;
-            }
-        }
-    }
-    // ---- row boundaries: prefix sum of the byte lengths (its cross-wave part rides on the barrier below) ----
-    const uint32_t incl = xd_wave_scan(my_len);
+    const uint64_t tile = tile0 + stage::xcd_run(n_tiles, blockIdx.x & 7).first + (blockIdx.x >> 3);
+    XdTileRegs<T, XS, VD == 0> R;
+    xd_request<T, DOT>(R, tile, val, x, n_rows, scode, cwin, len8, tbase, dot_lhs);
+    // row boundaries: prefix sum of the byte lengths (its cross-wave part rides on the barrier below)
+    const uint32_t incl = xd_wave_scan(R.my_len);
     if (lane == kWave - 1) s_wtot[wave] = incl;
-    // ---- x into its stage ----
-#pragma unroll
-    for (int u = 0; u < XS; ++u) {
-        if constexpr (sizeof(T) == 4) {
-            const uint32_t j = tid + (uint32_t)u * kBlock;
-            if (j < xs_tot) {
-                xd_f4 a; a.x = xr[u][0]; a.y = xr[u][1]; a.z = xr[u][2]; a.w = xr[u][3];
-                *reinterpret_cast<xd_f4 *>(&s_xs[4u * j]) = a;
-            }
-        } else {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                if ((xpiece[u][h] >> 1) < xs_tot) {
-                    xd_d2 a; a.x = xr[u][2 * h]; a.y = xr[u][2 * h + 1];
-                    *reinterpret_cast<xd_d2 *>(&s_xs[2u * xpiece[u][h]]) = a;
-                }
-        }
-    }
+    xd_fill_stage(R, s_xs);
     if constexpr (VD) {
         if (tid < 32u) s_dict[tid] = dict_v;
     }
     __syncthreads();
-    // ---- products: x from the stage by byte offset, four products per 16-byte store at the chunk's own position ----
-    const char *xs_bytes = reinterpret_cast<const char *>(s_xs);
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        T p[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t cword = (e >> 1) ? cw[it].y : cw[it].x;
-            const uint32_t code = (e & 1) ? (cword >> 16) : (cword & 0xFFFFu);
-            if constexpr (VD) {
-                // (a slot past the tile reads code 0: stage entry 0 times dictionary entry 0 -- never added to any row)
-                const uint32_t vi = VD == 2 ? XdBits<T, XS>::vidx_high(code) : XdBits<T, XS>::vidx(code);
-                p[e] = xd_mul(*reinterpret_cast<const T *>(xs_bytes + XdBits<T, XS>::ofs(code)), s_dict[vi]);
-            } else {
-                p[e] = xd_mul(*reinterpret_cast<const T *>(xs_bytes + code), v[it][e]);
-            }
-        }
-        if constexpr (sizeof(T) == 4) {
-            const uint32_t j = 4u * tid + (uint32_t)it * (4u * kBlock);
-            xd_f4 a; a.x = p[0]; a.y = p[1]; a.z = p[2]; a.w = p[3];
-            *reinterpret_cast<xd_f4 *>(&s_prod[j]) = a;
-        } else {
-            xd_d2 a, b; a.x = p[0]; a.y = p[1]; b.x = p[2]; b.y = p[3];
-            *reinterpret_cast<xd_d2 *>(&s_prod[epos[it][0]]) = a;
-            *reinterpret_cast<xd_d2 *>(&s_prod[epos[it][1]]) = b;
-        }
-    }
+    xd_products<T, XS, VD>(R, s_xs, s_dict, s_prod);
     __syncthreads();
-    // ---- row sums: storage order, one rounded add per entry (reference: sum += product) ----
-    uint32_t before = 0;  // entries of the tile in the waves before this one (wave-uniform)
-#pragma unroll
-    for (int ww = 0; ww < kBlock / kWave - 1; ++ww) before += (uint32_t)ww < wave ? s_wtot[ww] : 0u;
-    const T *pp = s_prod + ((k0 - pa) + before + (incl - my_len));
-    T q[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) q[i] = pp[i];
-    T acc = T(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        if ((uint32_t)i < my_len) acc = xd_add(acc, q[i]);
-    for (uint32_t i = 8; i < my_len; ++i) acc = xd_add(acc, pp[i]);
-    const uint64_t r = r0 + tid;
-    if (r < n_rows && (!DOT || y)) __builtin_nontemporal_store(acc, &y[r]);  // (DOT with y == NULL: only lhs . (A x) is wanted)
-    if constexpr (DOT) {  // fixed order: lanes (DPP scan network), waves (index order) -- bitwise reproducible, as K1s
+    const T d = xd_row_sum<T, DOT>(R, incl, wave, s_wtot, s_prod, y, n_rows);
+    if constexpr (DOT) {
         __shared__ T s_red[kBlock / kWave];
-        T d = T(0);
-        if (r < n_rows && (y || my_len)) d += dl * acc;  // (as K1s: 0 + the product; inner_prod, y == NULL: not of a row without entries)
-        d = wave_sum_to_lane63(d);
         if (lane == kWave - 1) s_red[wave] = d;
         __syncthreads();
-        if (tid == 0) {
-            T t = T(0);
-#pragma unroll
-            for (int ww = 0; ww < kBlock / kWave; ++ww) t += s_red[ww];
-            dot_partials[tile] = t;
-        }
+        xd_fold_dot(s_red, dot_partials, tile);
     }
 }
 
@@ -267,19 +293,8 @@ k_spmv_stream_xd(const T *__restrict__ val, const T *__restrict__ x, T *__restri
 // With the value array gone the kernel above is bound by LATENCY: a workgroup lives 2.85 us -- the two dependent memory round trips of
 // its tile (tile table -> codes and x chunks) -- at full occupancy (profiles/r04_k1s_value_dictionary.log).  Here a workgroup walks a
 // contiguous run of tiles and the NEXT tile's table entries, codes, x chunks and row lengths are on their way while the current tile is
-// multiplied and summed: the same loads, the same LDS stages, the same products and the same order of additions per row (bit-exact),
-// two barriers per tile as before; what a thread holds of a tile is the register set XdTileRegs, two of them alternate.
-template <typename T, int XS>
-struct XdTileRegs {
-    uint32_t k0, pa, my_len, xs_tot;
-    uint64_t r0, tile;
-    T dl;
-    T xr[XS][4];
-    uint32_t xpiece[XS][2];
-    xd_u2 cw[2];
-    uint32_t epos[2][2];
-};
-
+// multiplied and summed: the same four steps per tile (bit-exact), two barriers per tile as before; two register sets alternate.
+// Its own: the run a workgroup takes, s_wtot / s_red by tile parity, and the dot's fold deferred past the next barrier.
 template <typename T, bool DOT, int XS, int VD>
 __global__ void __launch_bounds__(kBlock)
 k_spmv_stream_xdp(const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows, uint64_t n_tiles, T *__restrict__ dot_partials,
@@ -291,165 +306,44 @@ k_spmv_stream_xdp(const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows, u
     __shared__ __attribute__((aligned(16))) T s_xs[kXsCap];
     __shared__ __attribute__((aligned(16))) T s_prod[kXdSlots + 8];
     __shared__ uint32_t s_wtot[2][kBlock / kWave];  // (by tile parity: a fast wavefront stages the next tile while a slow one still sums)
-    __shared__ T s_red[2][kBlock / kWave];          // (by tile parity too: folded one barrier later, see fold_dot)
+    __shared__ T s_red[2][kBlock / kWave];          // (by tile parity too: folded one barrier later, see below)
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / kWave));
-    const uint32_t wbase = tid & ~(uint32_t)(kWave - 1);
     if (tid < 32u) s_dict[tid] = dict[tid];
     // XCD g (= blockIdx % 8) owns a contiguous eighth of the launch's tiles, its workgroups contiguous runs of those
-    const uint64_t q8 = n_tiles >> 3, rm = n_tiles & 7, xcd = blockIdx.x & 7, wgx = gridDim.x >> 3, j_wg = blockIdx.x >> 3;
-    const uint64_t xcd_first = xcd < rm ? xcd * (q8 + 1) : rm * (q8 + 1) + (xcd - rm) * q8, xcd_count = q8 + (xcd < rm ? 1u : 0u);
-    const uint64_t per = (xcd_count + wgx - 1) / wgx;
-    const uint64_t t_begin = xcd_first + j_wg * per;
-    const uint64_t t_end = t_begin + per < xcd_first + xcd_count ? t_begin + per : xcd_first + xcd_count;
+    const stage::XcdRun mine = stage::xcd_run(n_tiles, blockIdx.x & 7);
+    const uint64_t wgx = gridDim.x >> 3, j_wg = blockIdx.x >> 3;
+    const uint64_t per = (mine.count + wgx - 1) / wgx;
+    const uint64_t t_begin = mine.first + j_wg * per;
+    const uint64_t t_end = t_begin + per < mine.first + mine.count ? t_begin + per : mine.first + mine.count;
     if (t_begin >= t_end) return;  // (whole workgroup, before any barrier)
-
-    auto load = [&](XdTileRegs<T, XS> &R, uint64_t t) {  // t: index inside the launch; everything of tile tile0 + t a thread needs, requested
-        R.tile = tile0 + t;
-        R.r0 = R.tile * (uint64_t)kStreamRows;
-        const uint32_t k0 = tbase[R.tile], k1 = tbase[R.tile + 1];
-        R.k0 = k0;
-        R.my_len = len8[R.r0 + tid];
-        R.dl = T(0);
-        if constexpr (DOT) R.dl = R.r0 + tid < n_rows ? dot_lhs[R.r0 + tid] : T(0);
-        const uint32_t *w = cwin + 8 * R.tile;
-        const uint32_t cb0 = w[0], e0 = w[1], cb1 = w[2], e1 = w[3], cb2 = w[4], e2 = w[5], cb3 = w[6], e3 = w[7];
-        const uint32_t al0 = cb0 & ~3u, al1 = cb1 & ~3u, al2 = cb2 & ~3u, al3 = cb3 & ~3u;
-        const uint32_t n0 = e0 > cb0 ? (e0 - al0 + 3u) >> 2 : 0u, n1 = e1 > cb1 ? (e1 - al1 + 3u) >> 2 : 0u;
-        const uint32_t n2 = e2 > cb2 ? (e2 - al2 + 3u) >> 2 : 0u, n3 = e3 > cb3 ? (e3 - al3 + 3u) >> 2 : 0u;
-        const uint32_t p1 = n0, p2 = p1 + n1, p3 = p2 + n2;
-        R.xs_tot = p3 + n3;
-        const uint32_t d0 = al0 >> 2, d1 = (al1 >> 2) - p1, d2 = (al2 >> 2) - p2, d3 = (al3 >> 2) - p3;
-#pragma unroll
-        for (int u = 0; u < XS; ++u) {
-            R.xr[u][0] = R.xr[u][1] = R.xr[u][2] = R.xr[u][3] = T(0);
-            if constexpr (sizeof(T) == 4) {
-                const uint32_t j = tid + (uint32_t)u * kBlock;
-                R.xpiece[u][0] = R.xpiece[u][1] = 0;
-                if (j < R.xs_tot) {
-                    uint32_t d = d0;
-                    d = j >= p1 ? d1 : d;
-                    d = j >= p2 ? d2 : d;
-                    d = j >= p3 ? d3 : d;
-                    const xd_f4 a = *reinterpret_cast<const xd_f4 *>(x + 4ull * (uint64_t)(j + d));
-                    R.xr[u][0] = a.x; R.xr[u][1] = a.y; R.xr[u][2] = a.z; R.xr[u][3] = a.w;
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const uint32_t pi = 2u * ((uint32_t)u * kBlock + wbase) + (uint32_t)h * kWave + lane;
-                    const uint32_t j = pi >> 1;
-                    R.xpiece[u][h] = pi;
-                    if (j < R.xs_tot) {
-                        uint32_t d = d0;
-                        d = j >= p1 ? d1 : d;
-                        d = j >= p2 ? d2 : d;
-                        d = j >= p3 ? d3 : d;
-                        const xd_d2 a = *reinterpret_cast<const xd_d2 *>(x + 4ull * (uint64_t)(j + d) + 2u * (pi & 1u));
-                        R.xr[u][2 * h] = a.x; R.xr[u][2 * h + 1] = a.y;
-                    }
-                }
-            }
-        }
-        const uint32_t pa = k0 & ~3u, hi = k1 - pa;
-        R.pa = pa;
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void *)(scode + pa), 0, (int)(((hi + 3u) & ~3u) * 2u), kXdRsrc);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            if constexpr (sizeof(T) == 4) {
-                const uint32_t j = 4u * tid + (uint32_t)it * (4u * kBlock);
-                R.epos[it][0] = j; R.epos[it][1] = j;
-                R.cw[it] = __builtin_bit_cast(xd_u2, __builtin_amdgcn_raw_buffer_load_b64(rc, (int)(j * 2u), 0, 2 /* nt */));
-            } else {
-                const uint32_t e0p = 4u * ((uint32_t)it * kBlock + wbase) + 2u * lane, e1p = e0p + 2u * kWave;
-                R.epos[it][0] = e0p; R.epos[it][1] = e1p;
-                R.cw[it].x = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e0p * 2u), 0, 2);
-                R.cw[it].y = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)(e1p * 2u), 0, 2);
-            }
-        }
+    typedef XdTileRegs<T, XS, false> Regs;
+    auto request = [&](Regs &R, uint64_t t) {  // t: index inside the launch
+        xd_request<T, DOT>(R, tile0 + t, (const T *)nullptr, x, n_rows, scode, cwin, len8, tbase, dot_lhs);
     };
-    // the wavefronts' shares of a tile's dot, folded in index order (as the per-tile kernel does) -- by thread 0 AFTER the next barrier the
-    // workgroup passes anyway (the first one of the following tile; a closing one after the last): a barrier of its own per tile, with
-    // one thread folding behind it while 255 wait at the next, cost the f32 solver 0.25 ms per iteration
-    auto fold_dot = [&](uint32_t par, uint64_t tile) {
-        if (tid == 0) {
-            T t = T(0);
-#pragma unroll
-            for (int ww = 0; ww < kBlock / kWave; ++ww) t += s_red[par][ww];
-            dot_partials[tile] = t;
-        }
-    };
-    // one tile with its registers R, prefetching tile t_next into N between the two barriers
-    auto tile_body = [&](XdTileRegs<T, XS> &R, XdTileRegs<T, XS> &N, uint64_t t_next, uint32_t par, bool first) {
+    // one tile with its registers R, prefetching tile t_next into N between the two barriers.  The wavefronts' shares of the PREVIOUS
+    // tile's dot are folded by thread 0 AFTER the first barrier here, which the workgroup passes anyway (a closing one after the last
+    // tile): a barrier of its own per tile, with one thread folding behind it while 255 wait at the next, cost the f32 solver 0.25 ms
+    // per iteration
+    auto tile_body = [&](Regs &R, Regs &N, uint64_t t_next, uint32_t par, bool first) {
         const uint32_t incl = xd_wave_scan(R.my_len);
         if (lane == kWave - 1) s_wtot[par][wave] = incl;
-#pragma unroll
-        for (int u = 0; u < XS; ++u) {
-            if constexpr (sizeof(T) == 4) {
-                const uint32_t j = tid + (uint32_t)u * kBlock;
-                if (j < R.xs_tot) {
-                    xd_f4 a; a.x = R.xr[u][0]; a.y = R.xr[u][1]; a.z = R.xr[u][2]; a.w = R.xr[u][3];
-                    *reinterpret_cast<xd_f4 *>(&s_xs[4u * j]) = a;
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    if ((R.xpiece[u][h] >> 1) < R.xs_tot) {
-                        xd_d2 a; a.x = R.xr[u][2 * h]; a.y = R.xr[u][2 * h + 1];
-                        *reinterpret_cast<xd_d2 *>(&s_xs[2u * R.xpiece[u][h]]) = a;
-                    }
-            }
-        }
+        xd_fill_stage(R, s_xs);
         __syncthreads();
         if constexpr (DOT) {
-            if (!first) fold_dot(par ^ 1u, R.tile - 1);  // (a workgroup's tiles are consecutive)
+            if (!first) xd_fold_dot(s_red[par ^ 1u], dot_partials, R.tile - 1);  // (a workgroup's tiles are consecutive)
         }
-        load(N, t_next);  // (always: no branch around the loads; the last tile is simply requested once more)
-        const char *xs_bytes = reinterpret_cast<const char *>(s_xs);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            T p[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t cword = (e >> 1) ? R.cw[it].y : R.cw[it].x;
-                const uint32_t code = (e & 1) ? (cword >> 16) : (cword & 0xFFFFu);
-                const uint32_t vi = VD == 2 ? XdBits<T, XS>::vidx_high(code) : XdBits<T, XS>::vidx(code);
-                p[e] = xd_mul(*reinterpret_cast<const T *>(xs_bytes + XdBits<T, XS>::ofs(code)), s_dict[vi]);
-            }
-            if constexpr (sizeof(T) == 4) {
-                xd_f4 a; a.x = p[0]; a.y = p[1]; a.z = p[2]; a.w = p[3];
-                *reinterpret_cast<xd_f4 *>(&s_prod[R.epos[it][0]]) = a;
-            } else {
-                xd_d2 a, b; a.x = p[0]; a.y = p[1]; b.x = p[2]; b.y = p[3];
-                *reinterpret_cast<xd_d2 *>(&s_prod[R.epos[it][0]]) = a;
-                *reinterpret_cast<xd_d2 *>(&s_prod[R.epos[it][1]]) = b;
-            }
-        }
+        request(N, t_next);  // (always: no branch around the loads; the last tile is simply requested once more)
+        xd_products<T, XS, VD>(R, s_xs, s_dict, s_prod);
         __syncthreads();
-        uint32_t before = 0;
-#pragma unroll
-        for (int ww = 0; ww < kBlock / kWave - 1; ++ww) before += (uint32_t)ww < wave ? s_wtot[par][ww] : 0u;
-        const T *pp = s_prod + ((R.k0 - R.pa) + before + (incl - R.my_len));
-        T q[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q[i] = pp[i];
-        T acc = T(0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if ((uint32_t)i < R.my_len) acc = xd_add(acc, q[i]);
-        for (uint32_t i = 8; i < R.my_len; ++i) acc = xd_add(acc, pp[i]);
-        const uint64_t r = R.r0 + tid;
-        if (r < n_rows && (!DOT || y)) __builtin_nontemporal_store(acc, &y[r]);
-        if constexpr (DOT) {  // fixed order: lanes (DPP scan network), waves (index order) -- bitwise reproducible, as K1s
-            T d = T(0);
-            if (r < n_rows && (y || R.my_len)) d += R.dl * acc;  // (as above)
-            d = wave_sum_to_lane63(d);
+        const T d = xd_row_sum<T, DOT>(R, incl, wave, s_wtot[par], s_prod, y, n_rows);
+        if constexpr (DOT) {
             if (lane == kWave - 1) s_red[par][wave] = d;
         }
     };
-    XdTileRegs<T, XS> A, B;
+    Regs A, B;
     const uint64_t t_last = t_end - 1;
-    load(A, t_begin);
+    request(A, t_begin);
     uint32_t last_par = 0;
     for (uint64_t t = t_begin;;) {
         tile_body(A, B, t + 1 < t_end ? t + 1 : t_last, 0u, t == t_begin);
@@ -461,32 +355,19 @@ k_spmv_stream_xdp(const T *__restrict__ x, T *__restrict__ y, uint64_t n_rows, u
     }
     if constexpr (DOT) {
         __syncthreads();
-        fold_dot(last_par, tile0 + t_last);
+        xd_fold_dot(s_red[last_par], dot_partials, tile0 + t_last);
     }
 }
 
-// stage offsets: code = BYTES from the start of the tile's LDS stage of x to x[column] -- the stage holds the tile's intervals
-// back to back, each from its 4-aligned start in whole 16-byte chunks (exactly what the kernel's fill does)
+// stage offsets: code = BYTES from the start of the tile's LDS stage of x to x[column]
 __global__ void __launch_bounds__(kBlock)
 k_stream_stage_codes(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col, const uint32_t *__restrict__ win,
                      uint64_t n_rows, uint64_t n_tiles, uint32_t elem_bytes, uint16_t *__restrict__ code) {
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const uint32_t *w = win + 8 * t;
-        const uint32_t a0 = w[0], e0 = w[1], a1 = w[2], e1 = w[3], a2 = w[4], e2 = w[5], a3 = w[6], e3 = w[7];
-        const uint32_t al0 = a0 & ~3u, al1 = a1 & ~3u, al2 = a2 & ~3u, al3 = a3 & ~3u;
-        const uint32_t n0 = e0 > a0 ? (e0 - al0 + 3u) >> 2 : 0u, n1 = e1 > a1 ? (e1 - al1 + 3u) >> 2 : 0u;
-        const uint32_t n2 = e2 > a2 ? (e2 - al2 + 3u) >> 2 : 0u;
-        const uint32_t p1 = n0, p2 = p1 + n1, p3 = p2 + n2;
+        const stage::Layout lay = stage::layout(win + 8 * t);
         const uint64_t r0 = t * kStreamRows, r1 = r0 + kStreamRows < n_rows ? r0 + kStreamRows : n_rows;
         const uint64_t k0 = off[r0], k1 = off[r1];
-        for (uint64_t k = k0 + threadIdx.x; k < k1; k += kBlock) {
-            const uint32_t c = col[k];
-            // the used intervals are a prefix of the table, sorted, disjoint, and contain every column of the tile
-            const uint32_t q = (uint32_t)(e1 > a1 && c >= a1) + (uint32_t)(e2 > a2 && c >= a2) + (uint32_t)(e3 > a3 && c >= a3);
-            const uint32_t al = q == 3u ? al3 : q == 2u ? al2 : q == 1u ? al1 : al0;
-            const uint32_t pq = q == 3u ? p3 : q == 2u ? p2 : q == 1u ? p1 : 0u;
-            code[k] = (uint16_t)((4u * pq + (c - al)) * elem_bytes);
-        }
+        for (uint64_t k = k0 + threadIdx.x; k < k1; k += kBlock) code[k] = (uint16_t)(lay.entry(col[k]) * elem_bytes);
     }
 }
 
@@ -582,8 +463,7 @@ k_value_dict_encode(const T *__restrict__ val, uint64_t nnz, const T *__restrict
         const U pat = bits[k];
         uint32_t idx = 0;
         for (uint32_t i = 0; i < n; ++i) idx = tab[i] == pat ? i : idx;  // (every pattern is in the dictionary: it was built from these values)
-        const uint32_t lowmask = (1u << low) - 1u;
-        code[k] = (uint16_t)(code[k] | (idx & lowmask) | ((idx >> low) << high_shift));
+        code[k] = (uint16_t)stage::code_pack(code[k], idx, low, high_shift);
     }
 }
 
@@ -601,14 +481,16 @@ k_stream_odd_rows(const uint8_t *__restrict__ len8, uint64_t n, unsigned long lo
 // one is first launched inside the solver's stream capture, where the runtime refuses the query (the fallback of 4 then halved f32's
 // grid: 1.74 against 1.45 ms per CG iteration until this was found); a refused query is not remembered.
 template <typename T, int XS, int VD> int xdp_resident(bool dot) {
-    static int res[2] = {0, 0};
-    if (res[0] == 0 || res[1] == 0) {
+    static std::atomic<int> res[2];  // (relaxed: every thread that asks is told the same, so whose answer stays does not matter)
+    if (res[0].load(std::memory_order_relaxed) == 0 || res[1].load(std::memory_order_relaxed) == 0) {
         int a = 0, b = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_spmv_stream_xdp<T, false, XS, VD>, kBlock, 0) == hipSuccess && a > 0) res[0] = a;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_spmv_stream_xdp<T, true, XS, VD>, kBlock, 0) == hipSuccess && b > 0) res[1] = b;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_spmv_stream_xdp<T, false, XS, VD>, kBlock, 0) == hipSuccess && a > 0)
+            res[0].store(a, std::memory_order_relaxed);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_spmv_stream_xdp<T, true, XS, VD>, kBlock, 0) == hipSuccess && b > 0)
+            res[1].store(b, std::memory_order_relaxed);
         (void)hipGetLastError();
     }
-    const int r = res[dot ? 1 : 0];
+    const int r = res[dot ? 1 : 0].load(std::memory_order_relaxed);
     return r > 0 ? r : (sizeof(T) == 8 ? 4 : 8);
 }
 
@@ -628,13 +510,14 @@ int launch_xd_t(const T *val, const T *x, T *y, size_t n_rows, T *dot_partials, 
     static const int persist_env = getenv("SMH_STREAM_PERSIST") ? atoi(getenv("SMH_STREAM_PERSIST")) : -1;  // tuning knob
     const bool persist = persist_env < 0 ? sizeof(T) == 8 : persist_env != 0;
     if (dict && persist && (xs == 2 || xs == 4)) {
-        static int cus_cache[64] = {};
+        static std::atomic<int> cus_cache[64];  // (relaxed, as xdp_resident's)
         int dev = 0;
         (void)hipGetDevice(&dev);
-        int &cus = cus_cache[dev & 63];
+        int cus = cus_cache[dev & 63].load(std::memory_order_relaxed);
         if (cus == 0) {
             hipDeviceProp_t prop;
             cus = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+            cus_cache[dev & 63].store(cus, std::memory_order_relaxed);
         }
         static const int per_cu_env = getenv("SMH_STREAM_PERSIST_WGS") ? atoi(getenv("SMH_STREAM_PERSIST_WGS")) : 0;  // tuning knob
 #define SMH_XDP(D, P, V)                                                                                                           \
@@ -731,15 +614,12 @@ int stream_value_dict(int dtype, const void *val, size_t nnz, void *dict_out, ui
 
 // code[k] |= index of val[k] in the dictionary (n entries), in the spare bits of a stage-offset code for a stage of xs * 1024 entries
 // do n dictionary entries fit the spare bits ABOVE the offset alone (the cheaper form for the kernel)?
-bool stream_value_dict_high(int dtype, uint32_t n, int xs) {
-    const uint32_t low = dtype == SMH_F64 ? 3u : 2u, high_shift = low + (xs == 4 ? 12u : 11u);
-    return n <= (1u << (16u - high_shift));
-}
+bool stream_value_dict_high(int dtype, uint32_t n, int xs) { return n <= stage::code_values_high((uint32_t)dtype_size(dtype), xs); }
 
 int launch_stream_value_codes(int dtype, const void *val, size_t nnz, const void *dict, uint32_t n, int xs, uint16_t *code, hipStream_t s) {
     if (nnz == 0) return SMH_OK;
-    const uint32_t high_shift = (dtype == SMH_F64 ? 3u : 2u) + (xs == 4 ? 12u : 11u);
-    const uint32_t low = stream_value_dict_high(dtype, n, xs) ? 0u : (dtype == SMH_F64 ? 3u : 2u);  // (low == 0: the whole index goes above the offset)
+    const uint32_t elem = (uint32_t)dtype_size(dtype), high_shift = stage::code_high_shift(elem, xs);
+    const uint32_t low = stream_value_dict_high(dtype, n, xs) ? 0u : stage::code_low_bits(elem);  // (low == 0: the whole index goes above the offset)
     uint64_t blocks = (nnz + kBlock - 1) / kBlock;
     if (blocks > 16384) blocks = 16384;
     if (dtype == SMH_F64)
@@ -751,7 +631,7 @@ int launch_stream_value_codes(int dtype, const void *val, size_t nnz, const void
 }
 
 // how many dictionary entries the spare bits of a code can name, for a stage of xs * 1024 entries
-uint32_t stream_value_dict_capacity(int xs) { return xs == 4 ? 16u : 32u; }
+uint32_t stream_value_dict_capacity(int xs) { return stage::code_values(xs); }
 
 int launch_stream_stage_codes(const uint32_t *off, const uint32_t *col, const uint32_t *win, size_t n_rows, uint32_t elem_bytes,
                               uint16_t *code, hipStream_t s) {

@@ -439,3 +439,64 @@ def test_stream_value_dictionary_rows_beyond_eight_entries(gpu, dtype):
     ip = m.inner_prod(lhs, x, variant="stream")
     m.set_stream_value_dict(0)
     assert np.array_equal(bits(m.mvp(x, variant="stream")), bits(want)) and m.inner_prod(lhs, x, variant="stream") == ip
+
+
+def _persistent_runs(n_tiles, cus, wgs_per_cu=1):
+    """tiles per workgroup of k_spmv_stream_xdp, as launch_xd_t sizes the grid and the kernel splits it: XCD g owns a contiguous eighth
+    of the tiles, its cus / 8 * wgs_per_cu workgroups (no more than ceil(n_tiles / 8)) contiguous runs of ceil(share / workgroups)"""
+    wgx = max(1, min(max(cus // 8, 1) * wgs_per_cu, (n_tiles + 7) // 8))
+    q8, rm = divmod(n_tiles, 8)
+    runs = []
+    for xcd in range(8):
+        count = q8 + (1 if xcd < rm else 0)
+        per = (count + wgx - 1) // wgx
+        runs += [max(0, min((j + 1) * per, count) - j * per) for j in range(wgx)]
+    return runs
+
+
+def test_stream_value_dictionary_persistent_runs_of_0_to_3_tiles(gpu):
+    """k_spmv_stream_xdp with ONE workgroup per CU on 5-point Laplacians of 1000 x ny, ny chosen from the device's CU count so that the
+    workgroups' runs are of 2 and 1 tiles (every workgroup busy), of 3, 1 and 0 tiles, and -- ny = 1, four tiles -- of 1 and 0 with
+    four XCDs idle: the two register sets alternate once, twice, not at all; a workgroup ends on either parity; the dot's deferred fold
+    happens after the next tile's first barrier and after the closing one.  The product bit for bit the oracle's, lhs . (A x) bit for
+    bit the K1s route of tests/inner_prod_model.py, f32 and f64.  (SMH_STREAM_PERSIST and SMH_STREAM_PERSIST_WGS are read once per
+    process: the test runs itself again in a fresh one that has them set.)"""
+    import os
+    import subprocess
+    import sys
+    if (os.environ.get("SMH_STREAM_PERSIST"), os.environ.get("SMH_STREAM_PERSIST_WGS")) != ("1", "1"):
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", os.path.abspath(__file__),
+                            "-k", "test_stream_value_dictionary_persistent_runs_of_0_to_3_tiles"],
+                           env=dict(os.environ, SMH_STREAM_PERSIST="1", SMH_STREAM_PERSIST_WGS="1"), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "1 passed" in r.stdout and "failed" not in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+        return
+    import torch
+    import inner_prod_model as ipm
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    nx = 1000
+
+    def first_ny(want, preferred):  # (preferred: the choice on 256 CUs)
+        for ny in [preferred] + list(range(1, 16 * cus)):
+            if set(_persistent_runs((nx * ny + 255) // 256, cus)) == want:
+                return ny
+        raise AssertionError("no ny gives runs of %s on %d CUs" % (sorted(want), cus))
+
+    cases = [(first_ny({1, 2}, 130), {1, 2}), (first_ny({0, 1, 3}, 180), {0, 1, 3}), (1, {0, 1})]
+    for ny, want_runs in cases:
+        n = nx * ny
+        runs = _persistent_runs((n + 255) // 256, cus)
+        assert set(runs) == want_runs and sum(runs) == (n + 255) // 256, (ny, cus, sorted(set(runs)))
+        if ny == 1:
+            assert len(runs) == 8 and runs[4:] == [0, 0, 0, 0]
+        for dtype in (np.float32, np.float64):
+            off, col, val = oracle.laplace2d(nx, ny, dtype)
+            rng = np.random.default_rng(ny)
+            x, lhs = rng.uniform(-1, 1, n).astype(dtype), rng.uniform(-1, 1, n).astype(dtype)
+            m = sm.SparseMatCRS.from_raw_parts(n, n, off, col, val)
+            m.set_stream_xs(1)
+            m.set_stream_direct(1)
+            assert m.stream_direct() and m.stream_layout()["xs_chunks"] in (2, 4) and 0 < len(m.stream_value_dict()) <= 3, (ny, dtype)
+            y = oracle.spmv(off, col, val, x)
+            assert np.array_equal(bits(m.mvp(x, variant="stream")), bits(y)), (ny, dtype)
+            got, want = np.asarray(m.inner_prod(lhs, x, variant="stream"), dtype), np.asarray(ipm.stream_route(lhs, y), dtype)
+            assert bits(got.reshape(1))[0] == bits(want.reshape(1))[0], (ny, dtype, float(got), float(want))

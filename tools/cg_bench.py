@@ -20,6 +20,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--dtype", default="f32")
     ap.add_argument("--variant", default="auto")
+    ap.add_argument("--spmv", default="vector,merge,auto", help="variants whose SpMV is timed alone before the solve")
+    ap.add_argument("--no-value-dict", action="store_true", help="K1s XD reads the value array (set_stream_value_dict(0))")
     args = ap.parse_args()
     dtype = np.float32 if args.dtype == "f32" else np.float64
     vs = np.dtype(dtype).itemsize
@@ -28,6 +30,8 @@ def main():
     t0 = time.time()
     a = synth.crs_laplace3d(g, g, g, dtype)
     nnz = a.n_non_zero_entries()
+    if args.no_value_dict:
+        a.set_stream_value_dict(0)
     print("laplace3d %d^3: n=%d nnz=%d built in %.2fs; auto=%s ring=%s" % (g, n, nnz, time.time() - t0, a.resolved_variant(),
                                                                          a.ring_plan()[1:3]), flush=True)
     ones = sm.DenseVec.from_vec(np.ones(n, dtype))
@@ -36,7 +40,8 @@ def main():
     # SpMV alone
     sm.lib().smh_device_synchronize()
     y = sm.DenseVec.zeros(n, dtype)
-    for variant in ("vector", "merge", "auto"):
+    b_spmv = nnz * (vs + 4) + (n + 1) * 4 + 2 * n * vs
+    for variant in [v for v in args.spmv.split(",") if v]:
         a.mvp_dev(ones.data_ptr(), n, y.data_ptr(), variant)
         sm.lib().smh_device_synchronize()
         t0 = time.perf_counter()
@@ -45,7 +50,6 @@ def main():
             a.mvp_dev(ones.data_ptr(), n, y.data_ptr(), variant)
         sm.lib().smh_device_synchronize()
         dt = (time.perf_counter() - t0) / reps
-        b_spmv = nnz * (vs + 4) + (n + 1) * 4 + 2 * n * vs
         print("  SpMV %-6s %.3f ms  %.0f GB/s (%.1f%% of 8 TB/s)" % (variant, dt * 1e3, b_spmv / dt / 1e9, b_spmv / dt / 8e10), flush=True)
     cg = sm.ConjugateGradient(0.0, args.iters, variant=args.variant, check_every=args.iters)
     cg.solve(a, b, x)  # warm-up (allocations, plans)
