@@ -469,6 +469,17 @@ int smh_crs_ring_plan(smh_crs *m, uint32_t *n_blocks_out, size_t *n_phases_out,
  * stream 16-bit or 12-bit columns, the ring kernel computes the row offsets of the regular phases instead of streaming them
  * (SMH_RING_REGULAR = auto / 0: 0 = every phase loads its offsets).  The table changes speed only, never a result. */
 int smh_crs_ring_regular(smh_crs *m, uint32_t *len_out);
+/* which form of the ring kernel a plain product (no inner_prod) of the VECTOR family would launch NOW, under the current settings
+ * and knobs (builds the plan and the forms on first use, like a product; the handle is not const for that reason):
+ * *form_out = 0: the kernel with the three bodies (ring gathers, two kinds of global gathers); 1: the kernel with the regular and the
+ * loading ring body (smh_crs_ring_regular); 2: the all-regular form -- f32 on the single-window ring of 16384 columns, EVERY phase
+ * that holds rows regular: the regular body alone, in workgroups of 768 threads (24 wavefronts per CU instead of 16;
+ * SMH_RING_ALLREG = auto / 0: 0 = form 1 instead); -1: the ring kernel is not in use (then the other two are 0).
+ * *threads_out = the workgroup size, *resident_per_cu_out = how many such workgroups a compute unit holds at once, as
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor answers for that instantiation with its dynamic LDS (0: a matrix without entries
+ * launches none).  inner_prod always runs form 0 or 1: the order of its sum goes with the wavefronts of a workgroup.  The form
+ * changes speed only, never a result. */
+int smh_crs_ring_launch_form(smh_crs *m, int *form_out, int *threads_out, int *resident_per_cu_out);
 
 /* K2c, the column-blocked copy (built on first use; integer structure, checked bit-exact in tests):
  * block b holds the entries with column >> shift == b, as a CSR over all rows whose offsets

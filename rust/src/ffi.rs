@@ -174,6 +174,9 @@ extern "C" {
     pub fn smh_crs_ring_regular(m: *mut smh_crs, len_out: *mut u32) -> c_int;
     // K1r: what the ring phases stream for their values -- 0 the value array, 1 24-bit fixed-point records (k * 2^exponent), -1 refused
     pub fn smh_crs_ring_values(m: *mut smh_crs, form_out: *mut c_int, exponent_out: *mut c_int) -> c_int;
+    // K1r: the form of the ring kernel a plain product would launch now -- 0 three bodies, 1 regular + loading body, 2 the all-regular form
+    // (768-thread workgroups), -1 no ring kernel --, its workgroup size and how many such workgroups a CU holds at once
+    pub fn smh_crs_ring_launch_form(m: *mut smh_crs, form_out: *mut c_int, threads_out: *mut c_int, resident_per_cu_out: *mut c_int) -> c_int;
     pub fn smh_crs_rcm(m: *const smh_crs, perm_out: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
     pub fn smh_crs_rcm_dev(m: *const smh_crs, perm_out_dev: *mut u32, n_components_out: *mut usize, n_levels_out: *mut usize) -> c_int;
     pub fn smh_crs_color(m: *const smh_crs, seed: u32, colors_out: *mut u32, perm_out: *mut u32, n_colors_out: *mut usize, n_rounds_out: *mut usize) -> c_int;

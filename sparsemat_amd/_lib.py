@@ -114,6 +114,7 @@ SIGNATURES = {
     "smh_crs_ring_values": (_int, [_vp, C.POINTER(_int), C.POINTER(_int)]),
     "smh_crs_ring_bands": (_int, [_vp, _u32p, _vp]),
     "smh_crs_ring_regular": (_int, [_vp, _vp]),
+    "smh_crs_ring_launch_form": (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
     "smh_crs_ring_plan": (_int, [_vp, _u32p, C.POINTER(_sz), C.POINTER(C.c_double), C.POINTER(_int), _vp, _vp]),
     "smh_crs_set_colblock_shift": (_int, [_vp, C.c_uint32]),
     "smh_crs_tiled_layout": (_int, [_vp, _u32p, _u32p, _u32p, _u32p, C.POINTER(_sz)]),

@@ -152,12 +152,16 @@ int ensure_ring_plan(smh_crs *m, bool with_bands) {
         SMH_TRY(read_back(p.reg_len.get(), h_reg.data(), phases.size(), m->stream, [&](uint32_t *d_reg) {
             return launch_ring_regular(m->d_off, p.phases.get(), phases.size(), d_reg, m->stream);
         }));
-        bool ring_only = true, any_regular = false;
+        // all_regular: a phase without rows (reg_len 0: k_ring_regular has no row to take L from) does not count against it -- the
+        // regular body returns for it before it reads anything (phase_rows: `base >= re`), as it does in the REGK kernel's other body
+        bool ring_only = true, any_regular = false, all_regular = true;
         for (size_t i = 0; i < phases.size(); ++i) {
             ring_only = ring_only && phases[i].use_ring == 1u;
             any_regular = any_regular || h_reg[i] != 0u;
+            all_regular = all_regular && (h_reg[i] != 0u || phases[i].row_end == phases[i].row_begin);
         }
         p.reg_applies = ring_only && any_regular;
+        p.reg_all = p.reg_applies && all_regular;
     }
     p.blocks = blocks;
     p.n_phases = phases.size();

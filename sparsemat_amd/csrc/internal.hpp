@@ -528,7 +528,22 @@ int launch_spmv_ring2(int dtype, int lanes, int chunks, const uint32_t *off, con
                       const uint32_t *phase_ptr, const RingPhase *phases, unsigned ring_entries, unsigned bands,
                       hipStream_t s, void *dot_partials = nullptr /* DOT form: y = lhs (read only), n_blocks + 1 partials of lhs . (A x) */,
                       unsigned block_begin = 0, unsigned block_end = ~0u /* the plan's row ranges [begin, end) only (default: all; not with the DOT form) */,
-                      const uint32_t *reg_len = nullptr /* RingPlan::reg_len: regular phases compute their row offsets (NULL: every phase loads them) */);
+                      const uint32_t *reg_len = nullptr /* RingPlan::reg_len: regular phases compute their row offsets (NULL: every phase loads them) */,
+                      int *resident_out = nullptr, int *threads_out = nullptr /* both: a query, nothing is enqueued -- the workgroups of the kernel
+                      this call would launch that a CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0: none) and their size */);
+// K1r's all-regular form (spmv_ring2_allreg.hip): f32, the single-window ring of kRingEntries columns, no DOT, for a plan whose phases
+// are all regular (RingPlan::reg_all) -- the REG body alone in workgroups of kRingAllregThreads threads, y bit for bit that of the
+// REGK form.  The column form is the one c12 / col16 hold (records, compact form, 16-bit columns); the other arguments and the
+// query are launch_spmv_ring2's.  ring2_allreg_has: (lanes, chunks) has the form (it is built where it needs no scratch within 80 VGPRs).
+constexpr int kRingAllregThreads = 768;
+bool ring2_allreg_has(int lanes, int chunks);
+int launch_spmv_ring2_allreg(int lanes, int chunks, const uint32_t *off, const uint32_t *col, const uint16_t *col16, const RingCol12 &c12,
+                             const float *val, const float *x, float *y, size_t n_rows, size_t nnz, bool padded, unsigned n_blocks,
+                             const uint32_t *phase_ptr, const RingPhase *phases, hipStream_t s, unsigned block_begin, unsigned block_end,
+                             const uint32_t *reg_len, int *resident_out = nullptr, int *threads_out = nullptr);
+// the <= 3 entries of an unpadded array's last partial chunk, added to their rows behind a K1r launch that covers the last rows
+int launch_ring2_tail(int dtype, const uint32_t *off, const uint32_t *col, const void *val, const void *x, void *y, size_t n_rows,
+                      uint64_t k_begin, size_t nnz, hipStream_t s);
 // reg_len[p] = L when phase p gathers from the ring (use_ring == 1), L > 0 and off[r] == off[row_begin] + (r - row_begin) * L for
 // every r in [row_begin, row_end]; else 0.  One read of the offsets.
 int launch_ring_regular(const uint32_t *off, const RingPhase *phases, size_t n_phases, uint32_t *reg_len, hipStream_t s);
@@ -703,6 +718,7 @@ struct RingPlan {  // K1r
     DevArray<RingPhase> phases;
     DevArray<uint32_t> reg_len;           // one per phase: the row length of a ring phase whose rows are all equally long, else 0 (launch_ring_regular)
     bool reg_applies = false;             // every phase gathers from the ring and some are regular: launches pass reg_len (k_spmv_ring2's REGK form)
+    bool reg_all = false;                 // ... and every phase that holds rows is regular: f32 launches without DOT take the all-regular form
     DevArray<uint32_t> win;              // banded plan: the tiles' column intervals (8 u32 per 64-row tile)
     DevArray<uint16_t> col16;             // 16-bit column array for the ring phases (built from the plan on first use; null: not used)
     // the compact column form (ring_col12.hpp), which the ring phases then stream instead of col16.  c12: NotTried until the counting pass has run; Ready: at most one

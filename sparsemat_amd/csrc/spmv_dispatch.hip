@@ -174,7 +174,10 @@ static int stream_launch(smh_crs *m, const StreamCfg &c, const void *x, size_t x
 }
 
 // one K1r launch over the plan's row ranges [b0, b1) (dot_partials: the DOT form, whole plan only -- see launch_spmv_ring2)
-static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u) {
+// resident_out, threads_out (both or neither) / form_out: a query instead of the launch -- launch_spmv_ring2's, and which form of the
+// kernel the launch would take: 0 = the three bodies, 1 = REGK, 2 = the all-regular form (smh_crs_ring_launch_form)
+static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *dot_partials = nullptr, unsigned b0 = 0, unsigned b1 = ~0u,
+                       int *resident_out = nullptr, int *threads_out = nullptr, int *form_out = nullptr) {
     // regular phases compute their row offsets from the plan's table, where it applies (RingPlan::reg_applies) and the ring phases
     // stream a narrow column form; SMH_RING_REGULAR=0 (tuning knob, read per launch like SMH_RING_COL12): no table, every phase
     // loads its offsets
@@ -185,9 +188,23 @@ static int launch_ring(smh_crs *m, const void *x, void *y, hipStream_t s, void *
     const RingCol12 c12{m->ring.lo8.get(), m->ring.hdr.get(), m->ring.escapes.get(), m->ring.rec16.get(),
                         m->ring.rec16.get() ? ldexpf(1.0f, m->ring.v24_exp) : 0.0f};
     // owned arrays are padded to a multiple of 4 entries; borrowed ones may end inside a 16-B chunk
-    return launch_spmv_ring2(m->dtype, auto_lanes(m), auto_chunks(m), m->d_off, m->d_col, m->ring.col16.get(), c12, m->d_val, x, y, m->n_rows, m->nnz,
-                             m->owns || m->nnz % 4 == 0, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
-                             m->ring.bands, s, dot_partials, b0, b1, reg_len);
+    const bool padded = m->owns || m->nnz % 4 == 0;
+    const int lanes = auto_lanes(m), chunks = auto_chunks(m);
+    // a plan whose phases are ALL regular (RingPlan::reg_all), f32 on the single-window ring of kRingEntries columns, no DOT (the
+    // order of inner_prod's sum goes with the 8 waves of a 512-thread workgroup): the all-regular form, 24 wavefronts per CU instead
+    // of 16, same y.  SMH_RING_ALLREG=0 (tuning knob, read per launch): the REGK kernel as before.
+    const char *all_env = getenv("SMH_RING_ALLREG");
+    const bool all_off = all_env && strcmp(all_env, "auto") != 0 && atoi(all_env) == 0;
+    const bool allreg = reg_len && m->ring.reg_all && !dot_partials && m->dtype == SMH_F32 && m->ring.entries == (unsigned)kRingEntries &&
+                        m->ring.bands == 1 && !all_off && ring2_allreg_has(lanes, chunks);
+    if (form_out) *form_out = allreg ? 2 : reg_len ? 1 : 0;
+    if (allreg)
+        return launch_spmv_ring2_allreg(lanes, chunks, m->d_off, m->d_col, m->ring.col16.get(), c12, (const float *)m->d_val, (const float *)x,
+                                        (float *)y, m->n_rows, m->nnz, padded, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), s,
+                                        b0, b1, reg_len, resident_out, threads_out);
+    return launch_spmv_ring2(m->dtype, lanes, chunks, m->d_off, m->d_col, m->ring.col16.get(), c12, m->d_val, x, y, m->n_rows, m->nnz,
+                             padded, m->ring.blocks, m->ring.phase_ptr.get(), m->ring.phases.get(), m->ring.entries,
+                             m->ring.bands, s, dot_partials, b0, b1, reg_len, resident_out, threads_out);
 }
 
 // Can y = A x also leave the partial sums of x.y (CG's p.Ap) in its epilogue?  Only the K1s kernel does;
@@ -491,6 +508,16 @@ int smh_crs_prepare_stats(smh_crs *m, int variant, double *prepare_ms_out, size_
     if (prepare_ms_out) *prepare_ms_out = m->create_ms + m->prepare_ms;
     if (derived_bytes_out) *derived_bytes_out = (size_t)(m->prepare_bytes + m->create_bytes > 0 ? m->prepare_bytes + m->create_bytes : 0);
     return SMH_OK;
+}
+
+int smh_crs_ring_launch_form(smh_crs *m, int *form_out, int *threads_out, int *resident_per_cu_out) {
+    if (!m || !form_out || !threads_out || !resident_per_cu_out) return fail(SMH_ERR_INVALID, "NULL argument");
+    *form_out = -1;
+    *threads_out = *resident_per_cu_out = 0;
+    bool ring = false;
+    SMH_TRY(vector_uses_ring(m, &ring));  // (builds the forms a product would)
+    if (!ring) return SMH_OK;
+    return launch_ring(m, nullptr, nullptr, nullptr, nullptr, 0, ~0u, resident_per_cu_out, threads_out, form_out);
 }
 
 int smh_crs_spmv_dev(smh_crs *m, const void *x_dev, size_t x_len, void *y_dev, int variant, void *stream) {

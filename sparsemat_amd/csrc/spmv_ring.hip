@@ -1,4 +1,4 @@
-// spmv_ring.hip -- K1r inspector and phase plan (the kernel itself is in spmv_ring2.hip).
+// spmv_ring.hip -- K1r inspector and phase plan (the kernel itself is in spmv_ring2_kernel.hpp).
 //
 // K1's limit on banded matrices is not HBM but the vector L1 / address path: every x[col] gather of a wave
 // instruction touches its own cache line (measured: 27 % of HBM peak on the stratified band vs 63 % when

@@ -112,7 +112,7 @@ k_spmv_vector(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
             if constexpr (sizeof(T) == 8) {
                 // f64 (round 4): a lane's 32 bytes of values per pass are TWO 16-byte pieces -- entries 2 lane, 2 lane + 1 and 2 LANES +
                 // 2 lane, 2 LANES + 2 lane + 1 of the pass -- so that each load instruction of the lane group covers contiguous bytes
-                // (K1r's lesson, spmv_ring2.hip lane_pos): the same slots, the same order of FMAs per lane as K1r, hence its bits.
+                // (K1r's lesson, spmv_ring2_kernel.hpp lane_pos): the same slots, the same order of FMAs per lane as K1r, hence its bits.
                 for (uint64_t kb = s & ~uint64_t(3); kb + 2u * lane < e; kb += 4u * LANES) {
                     uint32_t c[4];
                     T v[4];

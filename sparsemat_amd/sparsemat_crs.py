@@ -742,6 +742,15 @@ class SparseMatCRS:
             check(lib().smh_crs_ring_regular(self._h, out.ctypes.data))
         return out
 
+    def ring_launch_form(self):
+        """(form, threads, resident_per_cu) of the ring kernel a plain product would launch now, under the current settings and
+        knobs: form 0 = the three bodies, 1 = the regular and the loading ring body, 2 = the all-regular form (f32, every phase
+        regular: 768-thread workgroups; SMH_RING_ALLREG=0: form 1 instead), -1 = the ring kernel is not in use; the workgroup size;
+        and how many such workgroups a compute unit holds at once (the runtime's occupancy answer).  Results do not depend on it."""
+        form, threads, resident = C.c_int(), C.c_int(), C.c_int()
+        check(lib().smh_crs_ring_launch_form(self._h, C.byref(form), C.byref(threads), C.byref(resident)))
+        return form.value, threads.value, resident.value
+
     def max_row_len(self):
         out = C.c_uint32()
         check(lib().smh_crs_max_row_len(self._h, C.byref(out)))
