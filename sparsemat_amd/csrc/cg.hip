@@ -136,7 +136,7 @@ __device__ __forceinline__ void cg_p_body(bool rebuild, T alpha, T beta, T *__re
 }
 
 
-// ---- the two launches of an iteration's tail (single matrix: cg_iter_tail_t; row-partitioned: par.hip) ----------------------------
+// ---- the two launches of an iteration's tail (single matrix: cg_iter_tail_t; row-partitioned: par_cg.hip) ----------------------------
 // alpha + the x / r update in one launch, beta with the stop test + the p sweep in the other: every workgroup folds the `nb` partial
 // sums itself (the product's per-tile p.Ap partials or their first fold; the update's r.r partials; across row blocks: the blocks'
 // values) -- in exactly the order the one-workgroup kernels of rounds 1-3 folded them, so every workgroup (of every block) gets the
@@ -349,9 +349,9 @@ int cg_solve(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_m
 
 }  // namespace smh
 
-// ---- pieces of the row-partitioned solver (par.hip) ----------------------------------------------------------------
+// ---- pieces of the row-partitioned solver (par_cg.hip) ----------------------------------------------------------------
 // The same kernels as above, cut where the partitioned solver has to fold across row blocks: a block reduces its own
-// rows to ONE value (cg_fold), the blocks' values meet (peer-visible slots or an RCCL all-gather, par.hip), and every
+// rows to ONE value (cg_fold), the blocks' values meet (peer-visible slots or an RCCL all-gather: the seam of par.hpp), and every
 // block folds the same `nb` values in the same fixed tree -- so all blocks take identical alpha / beta / stop decisions
 // without a host round trip, and the result is bitwise reproducible.
 namespace smh {

@@ -589,7 +589,7 @@ size_t spmv_fused_dot_partials(::smh_crs *m, size_t x_len, int variant, bool any
 // kernel also leaves that many partial sums of x.y there (K1s epilogue; square matrices) -- CG's / PCG's p.Ap for free
 int spmv_enqueue(::smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, void *dot_partials = nullptr,
                  const void *dot_lhs = nullptr);
-// products of a run of rows (spmv_dispatch.hip; used by par.hip to multiply a block's boundary rows before / after its interior ones)
+// products of a run of rows (spmv_dispatch.hip; used by par_step.hip and par_cg.hip to multiply a block's boundary rows before / after its interior ones)
 int spmv_rows_granularity(::smh_crs *m, int variant, size_t *gran_out);
 int spmv_enqueue_rows(::smh_crs *m, const void *x, size_t x_len, void *y, int variant, hipStream_t s, size_t row0, size_t row1,
                       void *dot_partials = nullptr, const void *dot_lhs = nullptr);
@@ -613,7 +613,7 @@ int trisolve_enqueue(::smh_crs *m, int uplo, int diag, bool scale_rhs, const voi
 // (i, i) stored -- checked on the device in that order, nothing written; what: whose refusal it is
 int ilu_check(const ::smh_crs *a, const char *what);
 
-// ---- the device-resident solvers (cg.hip, pcg.hip, par.hip) ----------------------------------------------------------------------
+// ---- the device-resident solvers (cg.hip, pcg.hip, par_cg.hip) ----------------------------------------------------------------------
 // The scalar block of a solve: it lives in device memory, the kernels of cg.hip advance it, the host copies it back once per batch.
 // (pcg.hip's PcgScalars has the same layout -- asserted there -- with r.z in the place of rr_prev.)
 template <typename T>

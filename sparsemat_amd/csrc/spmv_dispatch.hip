@@ -333,7 +333,7 @@ int spmv_enqueue(smh_crs *m, const void *x, size_t x_len, void *y, int variant, 
     }
 }
 
-// ---- products of a run of rows (par.hip: a block's boundary rows before / after its interior ones) --------------------------
+// ---- products of a run of rows (par_step.hip, par_cg.hip: a block's boundary rows before / after its interior ones) --------------------------
 // The kernels whose launches decompose by rows WITHOUT changing any row's arithmetic: K1s (256-row tiles; bit-exact anyway) and
 // K1r (the plan's row ranges; a row's lanes, chunks and order do not depend on which workgroup takes it).  *gran_out = the row
 // granularity a run must respect (0: this handle's kernel for `variant` cannot be launched by parts).

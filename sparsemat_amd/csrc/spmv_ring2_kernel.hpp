@@ -486,7 +486,7 @@ k_spmv_ring2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col,
     constexpr int kRing2Threads = Ring2Cfg<T, RING>::kThreads;
     const uint32_t per_xcd = gridDim.x >> 3;
     // XCD-aware: neighbours share an L2.  A launch covers the plan's row ranges [lb0, lb0 + lb_n) (all of them, or -- the
-    // partitioned product, par.hip -- a block's boundary / interior ranges); the grid is lb_n rounded up to a multiple of 8
+    // partitioned product, par_step.hip -- a block's boundary / interior ranges); the grid is lb_n rounded up to a multiple of 8
     const uint32_t lb_rel = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     if (lb_rel >= lb_n) return;  // (whole workgroup, before any barrier)
     const uint32_t lb = lb0 + lb_rel;

@@ -222,7 +222,7 @@ k_spmv_stream(const uint32_t *__restrict__ off, const uint32_t *__restrict__ col
     __shared__ T s_prod[CAP + CAP / 32 + 8];
     // bijective XCD-aware remap: XCD g (= blockIdx % 8) walks a contiguous run of tiles
     // (n_tiles = the tiles of THIS launch, tile0 = the first of them: a launch may cover a run of the matrix's tiles only -- the
-    // partitioned product multiplies a block's boundary rows before its interior ones, par.hip)
+    // partitioned product multiplies a block's boundary rows before its interior ones, par_step.hip)
     const uint64_t tile = tile0 + stage::xcd_run(n_tiles, blockIdx.x & 7).first + (blockIdx.x >> 3);
     constexpr uint64_t TILE_ROWS = (uint64_t)kStreamRows * RPT;
     const uint64_t r0 = tile * TILE_ROWS;

@@ -235,7 +235,7 @@ def test_sparsemat_par_gloo(tmp_path, world):
 
 
 def test_library_plan_matches_the_python_plan():
-    """smh_par_plan (the plan arithmetic csrc/par.hip exchanges by: pure host code, no device needed) against the Python
+    """smh_par_plan (the plan arithmetic of csrc/par_plan.hpp that csrc/par_step.hip exchanges by: pure host code, no device needed) against the Python
     restatement the gloo tests run on, over random partitions incl. ragged last blocks, blocks without entries and
     intervals that reach across several neighbours."""
     from sparsemat_amd import sparsemat_par_local

@@ -6,9 +6,13 @@ and every CG iterate must be BIT-IDENTICAL with the overlap on and off, and equa
 import numpy as np
 import pytest
 
+import cg_model
 import oracle
+import par_cg_cases as pc
 import sparsemat_amd as sm
 from sparsemat_amd import synth
+from test_cg_bits_gpu import assert_result
+from test_par_cg_bits_gpu import adopt, solve_vec
 
 pytestmark = pytest.mark.gpu
 
@@ -215,3 +219,98 @@ def test_value_dictionary_blocks_of_many_tiles_by_runs_of_rows(gpu, dtype):
         b, xs = m.vec(host=b_host), m.vec()
         res[on] = (m.cg_solve_vec(b, xs, tol=1e-30, iter_max=12, check_every=4), xs.download())
     assert res[True][0] == res[False][0] and res[True][1].tobytes() == res[False][1].tobytes()
+
+
+@pytest.mark.parametrize("threads", [-1, 1], ids=["one-thread", "thread-per-block"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_a_failed_step_leaves_a_usable_handle(gpu, dtype, threads):
+    """Two blocks of 1024 rows (4 tiles each: both have an interior) on one device, window exchange beside the products.  x has
+    1500 entries: block 0's columns are covered and it forks, launches and begins the exchange; block 1's are not and it is refused
+    with the reference's message.  The entry point drains both streams of every block before it returns, so the very next calls
+    -- no synchronize in between -- find a handle like new: the product of a full-length x is the oracle's bit for bit, and a CG
+    solve gives the iterates of a fresh handle."""
+    n = 2048
+    off, col, val = cg_model.tridiag(n, dtype, seed=3)
+    rng = np.random.default_rng(5)
+    x_host = rng.uniform(-1, 1, n).astype(dtype)
+    b_host = oracle.spmv(off, col, val, np.ones(n, dtype))
+    want = oracle.spmv(off, col, val, x_host)
+
+    def handle():
+        m = sm.SparseMatParLocal.with_sub_matrices(2, n, n, off, col, val, device_ids=[0, 0])
+        m.set_threads(threads)
+        assert m.exchange_mode("auto")[0] == "window" and m.interior(0, "stream") == (0, 768) and m.interior(1, "stream") == (256, 1024)
+        return m
+
+    def solve(m):
+        b, xs = m.vec(host=b_host), m.vec()
+        return m.cg_solve_vec(b, xs, tol=0.0, iter_max=7, variant="stream", check_every=3), xs.download().tobytes()
+
+    fresh = solve(handle())
+    m = handle()
+    short, x, y = m.vec(n=1500, host=x_host[:1500]), m.vec(host=x_host), m.vec()
+    for _ in range(2):
+        with pytest.raises(sm.SparseMatPanic, match="index out of bounds: the len is 1500 but the index is 2047"):
+            m.mvp_dev(short, y, variant="stream", exchange="window")
+        m.mvp_dev(x, y, variant="stream", exchange="window")
+        m.synchronize()
+        assert y.download().tobytes() == want.tobytes()
+        with pytest.raises(sm.SparseMatPanic, match="index out of bounds: the len is 1500 but the index is 2047"):
+            m.mvp_dev(short, y, variant="stream", exchange="window")
+        assert solve(m) == fresh
+
+
+def _with_coupling(n, dtype, seed, i, j):
+    """cg_model.tridiag plus the symmetric pair (i, j) = (j, i) = -0.25, 0.25 more on both diagonals (still strictly diagonally
+    dominant: SPD); columns ascending"""
+    off, col, val = cg_model.tridiag(n, np.float64, seed=seed)
+    rows = np.repeat(np.arange(n), np.diff(off.astype(np.int64)))
+    col = col.astype(np.int64)
+    val = val + 0.25 * ((rows == col) & ((rows == i) | (rows == j)))
+    rows, col, val = np.concatenate([rows, [i, j]]), np.concatenate([col, [j, i]]), np.concatenate([val, [-0.25, -0.25]])
+    order = np.lexsort((col, rows))
+    out = np.zeros(n + 1, np.uint32)
+    np.cumsum(np.bincount(rows, minlength=n), out=out[1:])
+    return out, col[order].astype(np.uint32), val[order].astype(dtype)
+
+
+# cuts, the pair coupled on top of the tridiagonal matrix, does every block have an interior
+EDGES = {
+    # blocks of 256, 256 and 300 rows; (511, 811) dirties the tail tile of block 2 too: no interior anywhere, yet a window
+    "ragged-no-interior": ([0, 256, 512, 812], (511, 811), False),
+    "three-of-1024": ([0, 1024, 2048, 3072], None, True),
+    "lone": ([0, 812], None, False),
+}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("edge", list(EDGES))
+def test_phase_lists_at_the_edges(gpu, monkeypatch, dtype, edge):
+    """The steps' phase lists where parts of them are empty, against the oracle (the product) and the model of the block folds (the
+    solver), bit for bit: three blocks none of which has an interior, with a ragged tail (the overlapped step forks after the whole
+    product, nothing runs beside the exchange); three blocks of exactly 1024 rows with the overlap on (every part of every phase
+    does something); one block (no exchange, no meeting: the single-matrix solver's bits).  CG polled every 1 and every 3 bodies,
+    issued by one thread and by a thread per block; K1s with its dot epilogue and the one-thread-per-row kernel with the separate dot."""
+    monkeypatch.delenv("SMH_CG_FUSED_DOT", raising=False)
+    monkeypatch.delenv("SMH_STREAM_RPT", raising=False)
+    cuts, pair, has_interior = EDGES[edge]
+    n = cuts[-1]
+    parts = _with_coupling(n, dtype, 1, *pair) if pair else cg_model.tridiag(n, dtype, seed=1)
+    b, x0 = pc.rhs(n, dtype, 1, True)
+    x_want = oracle.spmv(*parts, b)
+    for variant, fused in (("stream", True), ("seq", False)):
+        case = pc.Case(edge, dtype, parts, b, x0, cuts, iter_max=6, fused=fused)
+        want = case.model()
+        assert want.iterations == 6
+        m = adopt(case)
+        m.set_overlap(True)
+        assert m.exchange_mode("auto")[0] == ("none" if len(cuts) == 2 else "window")
+        assert all((m.interior(k, "stream")[1] > m.interior(k, "stream")[0]) == has_interior for k in range(len(cuts) - 1))
+        for threads in (-1, 1):
+            m.set_threads(threads)
+            x, y = m.vec(host=b), m.vec()
+            m.mvp_dev(x, y, variant=variant)
+            m.synchronize()
+            assert y.download().tobytes() == x_want.tobytes(), (edge, variant, threads)
+            for check_every in (1, 3):
+                assert_result(solve_vec(m, case, variant, check_every), want, (edge, variant, threads, check_every))
