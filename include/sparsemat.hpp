@@ -952,6 +952,66 @@ class GMRES {
     int breakdown_ = 0;
 };
 
+// Thick-restart Lanczos with full reorthogonalisation -- an extension, not in the reference (smh_eigsh*): the k algebraically largest
+// (SMH_EIGSH_LARGEST) or smallest (SMH_EIGSH_SMALLEST) eigenpairs of a SYMMETRIC matrix.  Symmetry is the caller's promise, as it is
+// for ConjugateGradient: nothing checks it; a multiple eigenvalue is found once.  ncv: the columns of the basis, k + 2 .. 128 after
+// clipping to the dimension (0: min(n, max(2 k + 1, 20))); tol is used as given: pair i is converged when its estimate is at most
+// tol * max|theta|; restart_max: the restarts allowed.  After solve: values() / estimates() (k each, wanted-first; empty after
+// breakdown 2 or 3, which return nothing), n_conv() (< k: restart_max ran out, the k best pairs are returned all the same),
+// restarts(), products(), breakdown() (0; 1 the Krylov space is exhausted; 2 a zero or non-finite start; 3 non-finite data).
+// The vectors are not renormalised.
+class Lanczos {
+  public:
+    Lanczos() = default;
+    Lanczos(size_t k, int which = SMH_EIGSH_LARGEST, double tol = 1e-10, size_t ncv = 0, size_t restart_max = 1000)
+        : k_(k), ncv_(ncv), which_(which), tol_(tol), restart_max_(restart_max) {}
+    // device vectors: evecs holds k columns; the overload without it computes no vectors
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &start, MultiVec<T> &evecs) { run_vec(mat, start, evecs.handle()); }
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const DenseVec<T> &start) { run_vec(mat, start, nullptr); }
+    // host vectors: evecs becomes k vectors of n (left as it is after breakdown 2 or 3)
+    template <typename T>
+    void solve(const SparseMatCRS<T> &mat, const std::vector<T> &start, std::vector<std::vector<T>> &evecs) {
+        std::vector<T> flat(k_ * start.size());
+        begin();
+        detail::check(smh_eigsh(mat.handle(), start.data(), start.size(), k_, ncv_, which_, tol_, restart_max_, SMH_SPMV_AUTO, values_.data(),
+                                flat.data(), estimates_.data(), &n_conv_, &restarts_, &products_, &breakdown_));
+        end();
+        if (breakdown_ == 2 || breakdown_ == 3) return;
+        evecs.assign(k_, std::vector<T>());
+        for (size_t c = 0; c < k_; ++c) evecs[c].assign(flat.begin() + c * start.size(), flat.begin() + (c + 1) * start.size());
+    }
+    const std::vector<double> &values() const { return values_; }
+    const std::vector<double> &estimates() const { return estimates_; }
+    size_t n_conv() const { return n_conv_; }
+    size_t restarts() const { return restarts_; }
+    size_t products() const { return products_; }
+    int breakdown() const { return breakdown_; }
+
+  private:
+    void begin() { values_.assign(k_ ? k_ : 1, 0.0); estimates_.assign(k_ ? k_ : 1, 0.0); }
+    void end() {
+        const bool nothing = breakdown_ == 2 || breakdown_ == 3;
+        values_.resize(nothing ? 0 : k_);
+        estimates_.resize(nothing ? 0 : k_);
+    }
+    template <typename T>
+    void run_vec(const SparseMatCRS<T> &mat, const DenseVec<T> &start, smh_mvec *evecs) {
+        begin();
+        detail::check(smh_eigsh_vec(mat.handle(), start.handle(), evecs, k_, ncv_, which_, tol_, restart_max_, SMH_SPMV_AUTO, values_.data(),
+                                    estimates_.data(), &n_conv_, &restarts_, &products_, &breakdown_));
+        end();
+    }
+    size_t k_ = 6, ncv_ = 0;
+    int which_ = SMH_EIGSH_LARGEST;
+    double tol_ = 1e-10;
+    size_t restart_max_ = 1000;
+    std::vector<double> values_, estimates_;
+    size_t n_conv_ = 0, restarts_ = 0, products_ = 0;
+    int breakdown_ = 0;
+};
+
 // Mixed-precision iterative refinement -- an extension, not in the reference (smh_refine_solve*): an f64-accurate x of A x = b whose
 // bodies run in f32.  Each outer step forms r = b - A x in f64, scales it by a power of two, converts it to f32, solves
 // A_lo d = r_lo from d = 0 with the inner solver (SMH_INNER_CG, _BICGSTAB or _GMRES, preconditioned by SMH_PRECOND_NONE, _JACOBI -- not

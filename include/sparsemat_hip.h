@@ -48,7 +48,7 @@ extern "C" {
  * smh_pcg_ilu_solve, smh_pcg_ilu_solve_vec; smh_gmres_solve, smh_gmres_solve_vec; smh_gmres_precond_solve,
  * smh_gmres_precond_solve_vec; smh_bicgstab_precond_solve, smh_bicgstab_precond_solve_vec; smh_crs_fsai, smh_crs_fsai_apply_vec,
  * smh_pcg_fsai_solve, smh_pcg_fsai_solve_vec; smh_crs_fsai_ns, smh_crs_fsai_ns_apply_vec, smh_gmres_fsai_solve, smh_gmres_fsai_solve_vec,
- * smh_bicgstab_fsai_solve, smh_bicgstab_fsai_solve_vec; smh_crs_cast, smh_vec_cast, smh_refine_solve, smh_refine_solve_vec.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
+ * smh_bicgstab_fsai_solve, smh_bicgstab_fsai_solve_vec; smh_crs_cast, smh_vec_cast, smh_refine_solve, smh_refine_solve_vec; smh_eigsh, smh_eigsh_vec, smh_eigsh_last_timing.  A caller checks smh_abi_version() == SMH_ABI_VERSION once at load time (rust/src/lib.rs does). */
 #define SMH_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------------------ */
@@ -909,6 +909,40 @@ int smh_gmres_solve(smh_crs *m, const void *b_host, size_t b_len, void *x_host_i
 int smh_gmres_solve_vec(smh_crs *m, const smh_vec *b, smh_vec *x, double tol, size_t iter_max, size_t restart,
                         int variant, size_t check_every,
                         size_t *iters_out, double *rr_out, size_t *cycles_out, int *breakdown_out);
+
+/* Thick-restart Lanczos (Wu & Simon) with full reorthogonalisation -- an EXTENSION (the reference has no eigensolver): the k
+ * algebraically largest (SMH_EIGSH_LARGEST) or smallest (SMH_EIGSH_SMALLEST) eigenpairs of a SYMMETRIC matrix.  Symmetry is the
+ * caller's promise, as it is for smh_cg_solve: nothing checks it.  A multiple eigenvalue is found once (single-vector Lanczos).
+ * ncv = m, the columns of the basis: clipped to n, then k + 2 <= m <= 128 (0: the default, min(n, max(2 k + 1, 20))); whenever
+ * k + 2 > n, m = n and the first cycle is the whole space.  One rounding per operation, nothing contracted; the recurrence in full,
+ * with its orders: csrc/eigsh.hip and tests/eigsh_model.py.  In short: v_0 = start / |start|; a body at column j is w = A v_j,
+ * classical Gram-Schmidt twice against v_0 .. v_j (smh_gmres_solve's sweeps), alpha_j, beta_j = |w|, v_{j+1} = w / beta_j; a cycle of
+ * m - l bodies ends with ONE host round trip: the projected (arrowhead + tridiagonal) matrix is diagonalised in f64 by cyclic
+ * Jacobi, est_i = |beta_{m-1} Y[m-1, i]|, pair i is converged when est_i <= tol * max|theta|, n_conv is the converged prefix of the
+ * wanted order; unless n_conv == k, restarts == restart_max or m == n the basis is rotated on the device to the l = k + (m - k) / 2
+ * wanted Ritz vectors and the cycle continues at column l.  tol is used as given (0 converges only on an exact zero estimate).
+ * *breakdown_out: 0 none; 1 beta_j == 0, the Krylov space is exhausted: the min(k, j + 1) pairs that exist are returned exact (the
+ * values and estimates past them NaN, the vectors past them zero); 2 the start vector's norm is zero or not finite; 3 a non-finite
+ * alpha / beta (non-finite data).  2 and 3 return nothing: evals_out, est_out and the vectors are not written, *n_conv_out = 0.
+ * A breakdown is not an error: the call returns SMH_OK.  *n_conv_out < k with SMH_OK and breakdown 0 is an exhausted restart_max:
+ * the k best pairs are returned with their estimates.  evals_out / est_out: k values, in the wanted order; products_out: bodies
+ * entered; the vectors are not renormalised.  The output pointers may be NULL, the vectors too.
+ * evecs_host_out: k x n values (vector i at [i * n]); evecs: an smh_mvec of k columns.  Memory: (2 m + 4) n values.
+ * Statuses, decided on the host before any launch (a refused call writes nothing): a NULL handle or a NULL start of n > 0, a dtype
+ * that is not the matrix's, k == 0, k > n, ncv outside [k + 2, 128] after clipping, `which` out of range, evecs of another column
+ * count: SMH_ERR_INVALID; not square: SMH_ERR_NOT_SQUARE; start_len or a handle's dimension != n: SMH_ERR_DIM_MISMATCH. */
+#define SMH_EIGSH_LARGEST 0
+#define SMH_EIGSH_SMALLEST 1
+int smh_eigsh(smh_crs *m, const void *start_host, size_t start_len, size_t k, size_t ncv, int which, double tol,
+              size_t restart_max, int variant, double *evals_out, void *evecs_host_out, double *est_out,
+              size_t *n_conv_out, size_t *restarts_out, size_t *products_out, int *breakdown_out);
+int smh_eigsh_vec(smh_crs *m, const smh_vec *start, smh_mvec *evecs, size_t k, size_t ncv, int which, double tol,
+                  size_t restart_max, int variant, double *evals_out, double *est_out,
+                  size_t *n_conv_out, size_t *restarts_out, size_t *products_out, int *breakdown_out);
+/* A measuring aid: of this thread's last smh_eigsh*, the host step's wall time summed over its cycle ends and their number; and, only
+ * when the environment variable SMH_EIGSH_TIMING is set (the solve then waits for every rotation, which moves no bit), the wall
+ * time of the rotations, Yt's upload included, and their number (0 otherwise).  The pointers may be NULL. */
+int smh_eigsh_last_timing(double *host_step_ms_out, size_t *cycles_out, double *rotation_ms_out, size_t *rotations_out);
 
 /* Right-preconditioned GMRES(m) -- an EXTENSION: A M^-1 u = b, x = M^-1 u, inside the solver above, so the residual it minimises is
  * the true one, b - A x, and the stop rule, rr, cycles and both breakdown codes keep their meaning.  Everything not named here is

@@ -4,6 +4,7 @@ use std::os::raw::{c_char, c_double, c_int, c_void};
 
 #[repr(C)] pub struct smh_crs { _private: [u8; 0] }
 #[repr(C)] pub struct smh_vec { _private: [u8; 0] }
+#[repr(C)] pub struct smh_mvec { _private: [u8; 0] }
 #[repr(C)] pub struct smh_update_plan { _private: [u8; 0] }
 #[repr(C)] pub struct smh_par { _private: [u8; 0] }
 #[repr(C)] pub struct smh_par_vec { _private: [u8; 0] }
@@ -70,6 +71,17 @@ extern "C" {
     pub fn smh_gmres_solve_vec(m: *mut smh_crs, b: *const smh_vec, x: *mut smh_vec, tol: c_double, iter_max: usize, restart: usize,
                                variant: c_int, check_every: usize,
                                iters_out: *mut usize, rr_out: *mut c_double, cycles_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    // extension (not in the reference): thick-restart Lanczos, the k algebraically largest (which = 0) or smallest (1) eigenpairs of a
+    // SYMMETRIC matrix (the caller's promise); ncv: 0 or k + 2 ..= 128 after clipping to n; evals_out / est_out: k values; evecs: k x n
+    // host values or an smh_mvec of k columns, null for none; breakdown_out: 0 none, 1 the Krylov space is exhausted, 2 a zero or
+    // non-finite start, 3 non-finite data (2 and 3 write no pairs)
+    pub fn smh_eigsh(m: *mut smh_crs, start_host: *const c_void, start_len: usize, k: usize, ncv: usize, which: c_int, tol: c_double,
+                     restart_max: usize, variant: c_int, evals_out: *mut c_double, evecs_host_out: *mut c_void, est_out: *mut c_double,
+                     n_conv_out: *mut usize, restarts_out: *mut usize, products_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
+    pub fn smh_eigsh_last_timing(host_step_ms_out: *mut c_double, cycles_out: *mut usize, rotation_ms_out: *mut c_double, rotations_out: *mut usize) -> c_int;
+    pub fn smh_eigsh_vec(m: *mut smh_crs, start: *const smh_vec, evecs: *mut smh_mvec, k: usize, ncv: usize, which: c_int, tol: c_double,
+                         restart_max: usize, variant: c_int, evals_out: *mut c_double, est_out: *mut c_double,
+                         n_conv_out: *mut usize, restarts_out: *mut usize, products_out: *mut usize, breakdown_out: *mut c_int) -> c_int;
     // extension: the same solver right-preconditioned (A M^-1 u = b, x = M^-1 u); precond: SMH_PRECOND_*; f: the ILU(0) factor's
     // handle with SMH_PRECOND_ILU, null otherwise
     pub fn smh_gmres_precond_solve(a: *mut smh_crs, precond: c_int, f: *mut smh_crs, b_host: *const c_void, b_len: usize,

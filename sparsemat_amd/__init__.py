@@ -13,12 +13,12 @@ needs a HIP device.
 from ._lib import SparseMatPanic, lib, LIB_PATH  # noqa: F401
 from .densevec import DenseVec  # noqa: F401
 from .multivec import MultiVec  # noqa: F401
-from .sparsemat_crs import SparseMatCRS, UpdatePlan  # noqa: F401
+from .sparsemat_crs import EigshResult, SparseMatCRS, UpdatePlan  # noqa: F401
 from .linearsolver import GMRES, BiCGStab, ConjugateGradient, FSAIConjugateGradient, ILUConjugateGradient, IterativeRefinement, JacobiConjugateGradient, SGSConjugateGradient  # noqa: F401
 from . import synth  # noqa: F401
 from .sparsemat_par_local import Comm, ParVec, SparseMatParLocal  # noqa: F401
 
 SparseMatPar = SparseMatParLocal  # the reference's name (sparsemat_par.rs:12) for the ONE implementation: csrc/par.hip behind smh_par_*
 
-__all__ = ["SparseMatCRS", "UpdatePlan", "DenseVec", "MultiVec", "ConjugateGradient", "BiCGStab", "GMRES", "IterativeRefinement", "SparseMatPar", "SparseMatParLocal", "ParVec", "Comm", "SparseMatPanic", "synth",
+__all__ = ["SparseMatCRS", "UpdatePlan", "EigshResult", "DenseVec", "MultiVec", "ConjugateGradient", "BiCGStab", "GMRES", "IterativeRefinement", "SparseMatPar", "SparseMatParLocal", "ParVec", "Comm", "SparseMatPanic", "synth",
            "lib", "LIB_PATH"]

@@ -25,6 +25,9 @@ SMH_INNER_CG, SMH_INNER_BICGSTAB, SMH_INNER_GMRES = 0, 1, 2
 INNERS = {"cg": SMH_INNER_CG, "bicgstab": SMH_INNER_BICGSTAB, "gmres": SMH_INNER_GMRES}
 SMH_PRECOND_FSAI = 4
 REFINE_PRECONDS = dict(PRECONDS, fsai=SMH_PRECOND_FSAI)
+# smh_eigsh*: which end of the spectrum
+SMH_EIGSH_LARGEST, SMH_EIGSH_SMALLEST = 0, 1
+EIGSH_WHICH = {"LA": SMH_EIGSH_LARGEST, "SA": SMH_EIGSH_SMALLEST}
 UPLO = {"lower": SMH_TRI_LOWER, "upper": SMH_TRI_UPPER}
 EXCHANGE_NONE, EXCHANGE_ALLGATHER, EXCHANGE_WINDOW, EXCHANGE_AUTO = 0, 1, 2, 3
 EXCHANGES = {"none": EXCHANGE_NONE, "allgather": EXCHANGE_ALLGATHER, "window": EXCHANGE_WINDOW, "halo": EXCHANGE_WINDOW, "auto": EXCHANGE_AUTO}
@@ -223,6 +226,11 @@ SIGNATURES = {
                                C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_gmres_solve_vec": (_int, [_vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),
                                    C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_eigsh": (_int, [_vp, _vp, _sz, _sz, _sz, _int, C.c_double, _sz, _int, C.POINTER(C.c_double), _vp, C.POINTER(C.c_double),
+                         C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_int)]),
+    "smh_eigsh_last_timing": (_int, [C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(C.c_double), C.POINTER(_sz)]),
+    "smh_eigsh_vec": (_int, [_vp, _vp, _vp, _sz, _sz, _int, C.c_double, _sz, _int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                             C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_gmres_precond_solve": (_int, [_vp, _int, _vp, _vp, _sz, _vp, _sz, C.c_double, _sz, _sz, _int, C.POINTER(_sz),
                                        C.POINTER(C.c_double), C.POINTER(_sz), C.POINTER(_int)]),
     "smh_gmres_precond_solve_vec": (_int, [_vp, _int, _vp, _vp, _vp, C.c_double, _sz, _sz, _int, _sz, C.POINTER(_sz),

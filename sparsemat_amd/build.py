@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsparsemat_hip.so")
-SOURCES = ["capi.hip", "crs_forms.hip", "spmv_dispatch.hip", "spmv_vector.hip", "spmv_ring.hip", "spmv_ring2.hip", "spmv_ring2_allreg.hip", "spmv_stream.hip", "spmv_stream_xd.hip", "spmv_many.hip", "mvec.hip", "mvec_blas.hip", "cg_many.hip","spmv_colblock.hip", "spmv_colfused.hip", "spmv_colsplit.hip", "spmv_tiled.hip", "spmv_merge.hip", "blas1.hip", "cg.hip", "synth.hip", "assemble.hip", "matops.hip", "matadd.hip", "matupdate.hip", "matplan.hip", "par.hip", "par_step.hip", "par_cg.hip", "pcg.hip", "trisolve.hip", "bicgstab.hip", "gmres.hip", "pool.hip", "transpose_bucket.hip", "permute.hip", "reorder.hip", "color.hip", "ilu.hip", "fsai.hip", "refine.hip"]
-HEADERS = [os.path.join(CSRC, "internal.hpp"), os.path.join(CSRC, "crs_forms.hpp"), os.path.join(CSRC, "arg_stage.hpp"), os.path.join(CSRC, "mvec_tree.hpp"), os.path.join(CSRC, "ring_col12.hpp"), os.path.join(CSRC, "ring_val24.hpp"), os.path.join(CSRC, "spmv_ring2_kernel.hpp"), os.path.join(CSRC, "stream_stage.hpp"), os.path.join(CSRC, "solver_tree.hpp"), os.path.join(CSRC, "solver_host.hpp"), os.path.join(CSRC, "precond.hpp"), os.path.join(CSRC, "par.hpp"), os.path.join(CSRC, "par_plan.hpp"), os.path.join(CSRC, "par_issue.hpp"), os.path.join(HERE, "..", "include", "sparsemat_hip.h")]
+SOURCES = ["capi.hip", "crs_forms.hip", "spmv_dispatch.hip", "spmv_vector.hip", "spmv_ring.hip", "spmv_ring2.hip", "spmv_ring2_allreg.hip", "spmv_stream.hip", "spmv_stream_xd.hip", "spmv_many.hip", "mvec.hip", "mvec_blas.hip", "cg_many.hip","spmv_colblock.hip", "spmv_colfused.hip", "spmv_colsplit.hip", "spmv_tiled.hip", "spmv_merge.hip", "blas1.hip", "cg.hip", "synth.hip", "assemble.hip", "matops.hip", "matadd.hip", "matupdate.hip", "matplan.hip", "par.hip", "par_step.hip", "par_cg.hip", "pcg.hip", "trisolve.hip", "bicgstab.hip", "gmres.hip", "eigsh.hip", "pool.hip", "transpose_bucket.hip", "permute.hip", "reorder.hip", "color.hip", "ilu.hip", "fsai.hip", "refine.hip"]
+HEADERS = [os.path.join(CSRC, "internal.hpp"), os.path.join(CSRC, "crs_forms.hpp"), os.path.join(CSRC, "arg_stage.hpp"), os.path.join(CSRC, "mvec_tree.hpp"), os.path.join(CSRC, "ring_col12.hpp"), os.path.join(CSRC, "ring_val24.hpp"), os.path.join(CSRC, "spmv_ring2_kernel.hpp"), os.path.join(CSRC, "stream_stage.hpp"), os.path.join(CSRC, "solver_tree.hpp"), os.path.join(CSRC, "solver_host.hpp"), os.path.join(CSRC, "krylov_sweeps.hpp"), os.path.join(CSRC, "eigsh_host.hpp"), os.path.join(CSRC, "precond.hpp"), os.path.join(CSRC, "par.hpp"), os.path.join(CSRC, "par_plan.hpp"), os.path.join(CSRC, "par_issue.hpp"), os.path.join(HERE, "..", "include", "sparsemat_hip.h")]
 # -ffp-contract=off: the element-wise / SEQ kernels must round a*b and (a*b)+c separately, like the
 # reference; where an FMA is wanted (K1's accumulation) the kernels call __builtin_fma explicitly.
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -43,7 +43,7 @@
 // normalisation (1 read, 2 written): (4 j + 13) n values, (2 m + 11) n averaged over a full cycle.  A cycle end adds one sweep over
 // the basis that forms x and r with the partials of r.r ((j + 2) read, 2 written), its fold, and on a restart v_0 (1 read, 2 written).
 // Every sweep is solver_tree.hpp's sweep, a column of the basis being one more array to load from.
-// The dots: w's pack is loaded once per tile of kGmTile = 8 columns, one accumulator per column; every column is summed by
+// The dots (krylov_sweeps.hpp): w's pack is loaded once per tile of kGsTile = 8 columns, one accumulator per column; every column is summed by
 // solver_tree.hpp's tree on pcg_grid(n) -- cg_model.Reducer.dot(., ., "pcg") -- so the tile width changes no bit.
 // All state is on the device: a leading block in CgScalars' layout (solve_in_batches polls it; `converged` means STOPPED) and a
 // second block (GmMore).  The kernels read the column count from it; a sweep that is not due returns at once: the Gram-Schmidt
@@ -77,6 +77,7 @@
 // at once in a body that ends no cycle -- through AUTO every body would pay a second, dead pair.  So q has SEQ's bits and u AUTO's.
 #include "internal.hpp"
 #include "precond.hpp"
+#include "krylov_sweeps.hpp"
 #include "solver_host.hpp"
 #include "solver_tree.hpp"
 
@@ -87,7 +88,6 @@ using namespace smh;
 namespace {
 
 constexpr int kGmMaxM = 128;
-constexpr int kGmTile = 8;  // columns per load of w in the dots (no bit depends on it)
 constexpr size_t kGmDefaultRestart = 30;
 
 // the block the host polls through CG's reader (cg_read_scalars)
@@ -119,8 +119,6 @@ struct GmMore {
     T R[kGmMaxM * kGmMaxM];  // R_{i,k} at [k * kGmMaxM + i], i <= k
 };
 
-template <typename T> __device__ __forceinline__ T p_sqrt(T a) { return (T)sqrt((double)a); }  // (f64's sqrt rounds an f32 correctly too)
-
 template <typename T> __device__ __forceinline__ bool gm_enters(const GmScalars<T> *sc) { return !sc->converged && sc->iters < sc->iter_max; }
 
 template <typename T>
@@ -136,85 +134,8 @@ __global__ void k_gm_init(GmScalars<T> *sc, GmMore<T> *mo, double tol, uint64_t 
 }
 
 // ---- the sweeps over the basis (basis: columns of stride ld, ld % V == 0) ------------------------------------------------------
-// partials of v_c.w for c = 0 .. j: part[c * kPcgBlocks + block]
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-k_gm_dots(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, const T *__restrict__ w,
-          uint64_t n, T *__restrict__ part) {
-    if (!gm_enters(sc)) return;  // block-uniform
-    const unsigned ncols = mo->j + 1;
-    __shared__ T sa[kGmTile][kBlock / kWave];
-    for (unsigned c0 = 0; c0 < ncols; c0 += kGmTile) {
-        const unsigned width = ncols - c0 < (unsigned)kGmTile ? ncols - c0 : (unsigned)kGmTile;
-        const T *col0 = basis + (uint64_t)c0 * ld;
-        T acc[kGmTile];
-#pragma unroll
-        for (int t = 0; t < kGmTile; ++t) acc[t] = T(0);
-        sweep<T>(n, [&](auto at) {
-            const auto wv = at.load(w);
-#pragma unroll
-            for (int t = 0; t < kGmTile; ++t) {
-                if ((unsigned)t < width) {
-                    const auto vv = at.load(col0 + (uint64_t)t * ld);
-#pragma unroll
-                    for (int e = 0; e < at.width; ++e) acc[t] = p_add(acc[t], p_mul(vv[e], wv[e]));
-                }
-            }
-        });
-        // solver_tree.hpp's workgroup sum written out for a tile: one accumulator per column, and thread t < width (not thread 0)
-        // sums and writes column t -- block_sum1 per column would cost a barrier each, so this stays its own
-#pragma unroll
-        for (int t = 0; t < kGmTile; ++t) {
-#pragma unroll
-            for (int o = kWave / 2; o > 0; o >>= 1) acc[t] = p_add(acc[t], (T)__shfl_down(acc[t], o, kWave));
-            if ((threadIdx.x & (kWave - 1)) == 0) sa[t][threadIdx.x / kWave] = acc[t];
-        }
-        __syncthreads();
-        if (threadIdx.x < width) {
-            T s = sa[threadIdx.x][0];
-            for (int wv = 1; wv < kBlock / kWave; ++wv) s = p_add(s, sa[threadIdx.x][wv]);
-            part[(uint64_t)(c0 + threadIdx.x) * kPcgBlocks + blockIdx.x] = s;
-        }
-        __syncthreads();  // (sa is written again by the next tile)
-    }
-}
-
-// workgroup c folds column c's partials into h1_c (PASS 1) or h2_c (PASS 2); launched on m + 1 workgroups
-template <typename T, int PASS>
-__global__ void __launch_bounds__(kBlock)
-k_gm_fold(const GmScalars<T> *__restrict__ sc, GmMore<T> *mo, const T *__restrict__ part, unsigned n_parts) {
-    if (!gm_enters(sc) || blockIdx.x > mo->j) return;
-    const T h = fold1(part + (uint64_t)blockIdx.x * kPcgBlocks, n_parts);
-    if (threadIdx.x == 0) (PASS == 1 ? mo->h1 : mo->h2)[blockIdx.x] = h;
-}
-
-// w = (..((w - v_0 h_0) - v_1 h_1) .. - v_j h_j) with this pass's h; PASS 2: and the partials of w.w
-template <typename T, int PASS>
-__global__ void __launch_bounds__(kBlock)
-k_gm_update(const GmScalars<T> *__restrict__ sc, const GmMore<T> *__restrict__ mo, const T *__restrict__ basis, uint64_t ld, T *__restrict__ w, uint64_t n,
-            T *__restrict__ part_ww) {
-    if (!gm_enters(sc)) return;
-    const unsigned ncols = mo->j + 1;
-    const T *__restrict__ h = PASS == 1 ? mo->h1 : mo->h2;
-    T acc = T(0);
-    sweep<T>(n, [&](auto at) {
-        auto wv = at.load(w);
-#pragma unroll 8
-        for (unsigned c = 0; c < ncols; ++c) {
-            const auto vv = at.load(basis + (uint64_t)c * ld);
-            const T hc = h[c];
-#pragma unroll
-            for (int e = 0; e < at.width; ++e) wv[e] = p_add(wv[e], -p_mul(vv[e], hc));
-        }
-        if (PASS == 2) {
-#pragma unroll
-            for (int e = 0; e < at.width; ++e) acc = p_add(acc, p_mul(wv[e], wv[e]));
-        }
-        at.store(w, wv);
-    });
-    if (PASS == 2) block_partial(acc, part_ww);
-}
-
+// The Gram-Schmidt sweeps -- dots, folds, update -- are krylov_sweeps.hpp's (eigsh.hip runs the same ones).  Their "is due" word is
+// GmMore::enter: the set-up's and the restart's k_gm_begin and every k_gm_step leave it equal to gm_enters(sc).
 // partials of r.r (set-up)
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_gm_rr(const T *__restrict__ r, uint64_t n, T *__restrict__ part) {
@@ -451,12 +372,12 @@ int gmres_t(smh_crs *m, const Precond &pc, const SolveCall &c) {
             } else {
                 SMH_TRY(spmv_enqueue(m, vin, n, w, c.variant, s));
             }
-            hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
-            hipLaunchKernelGGL((k_gm_fold<T, 1>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
-            hipLaunchKernelGGL((k_gm_update<T, 1>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
-            hipLaunchKernelGGL((k_gm_dots<T>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part);
-            hipLaunchKernelGGL((k_gm_fold<T, 2>), cols, dim3(kBlock), 0, s, sc, mo, part, grid);
-            hipLaunchKernelGGL((k_gm_update<T, 2>), dim3(grid), dim3(kBlock), 0, s, sc, mo, basis, ld, w, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gs_dots<T>), dim3(grid), dim3(kBlock), 0, s, &mo->enter, &mo->j, basis, ld, w, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_gs_fold<T>), cols, dim3(kBlock), 0, s, &mo->enter, &mo->j, mo->h1, part, grid);
+            hipLaunchKernelGGL((k_gs_update<T, false>), dim3(grid), dim3(kBlock), 0, s, &mo->enter, &mo->j, mo->h1, basis, ld, w, (uint64_t)n, part_ww);
+            hipLaunchKernelGGL((k_gs_dots<T>), dim3(grid), dim3(kBlock), 0, s, &mo->enter, &mo->j, basis, ld, w, (uint64_t)n, part);
+            hipLaunchKernelGGL((k_gs_fold<T>), cols, dim3(kBlock), 0, s, &mo->enter, &mo->j, mo->h2, part, grid);
+            hipLaunchKernelGGL((k_gs_update<T, true>), dim3(grid), dim3(kBlock), 0, s, &mo->enter, &mo->j, mo->h2, basis, ld, w, (uint64_t)n, part_ww);
             hipLaunchKernelGGL((k_gm_step<T>), dim3(1), dim3(kBlock), 0, s, sc, mo, part_ww, grid);
             hipLaunchKernelGGL((k_gm_norm<T, false, P>), dim3(grid), dim3(kBlock), 0, s, mo, w, basis, ld, vin, (uint64_t)n, diag);
             hipLaunchKernelGGL((k_gm_xr<T, P>), dim3(grid), dim3(kBlock), 0, s, mo, basis, ld, x, r, (uint64_t)n, part_ww, diag, w);  // (w is free)

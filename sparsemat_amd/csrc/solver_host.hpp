@@ -1,4 +1,4 @@
-// solver_host.hpp -- what the host side of the device-resident solvers shares (cg.hip, cg_many.hip, pcg.hip, bicgstab.hip, gmres.hip and their
+// solver_host.hpp -- what the host side of the device-resident solvers shares (cg.hip, cg_many.hip, pcg.hip, bicgstab.hip, gmres.hip, eigsh.hip and their
 // entry points): the argument checks of the entry points and the skeleton of a solve around solve_in_batches (internal.hpp).
 // A solver is its allocations, its set-up launches, a body lambda and SolveRun::run; the kernels are its own file's.
 #pragma once

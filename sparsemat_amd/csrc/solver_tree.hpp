@@ -1,4 +1,4 @@
-// solver_tree.hpp -- what the fused solvers share.  All of them (cg.hip, pcg.hip, bicgstab.hip, gmres.hip): the sweep over [0, n)
+// solver_tree.hpp -- what the fused solvers share.  All of them (cg.hip, pcg.hip, bicgstab.hip, gmres.hip, eigsh.hip): the sweep over [0, n)
 // that their element-wise kernels are written on.  Those beside cg.hip: the explicitly rounded operations, the deterministic
 // workgroup sums, the one-workgroup folds of their partials and the grid of their sweeps.  The tree: a thread's own running sum, the
 // __shfl_down butterfly per wave, thread 0 over the four wave sums starting from the first wave's -- tests/cg_model.py restates it

@@ -26,6 +26,15 @@ def _index(i):
     return i
 
 
+class EigshResult:
+    """What ``SparseMatCRS.eigsh`` returns."""
+    __slots__ = ("values", "vectors", "estimates", "n_conv", "restarts", "products", "breakdown")
+
+    def __init__(self, values, vectors, estimates, n_conv, restarts, products, breakdown):
+        self.values, self.vectors, self.estimates = values, vectors, estimates
+        self.n_conv, self.restarts, self.products, self.breakdown = n_conv, restarts, products, breakdown
+
+
 class SparseMatCRS:
     def __init__(self, handle, dtype, keep=None):
         self._h = handle
@@ -828,6 +837,38 @@ class SparseMatCRS:
         check(lib().smh_crs_inner_prod(self._h, a.ctypes.data if a.size else None, a.size,
                                        b.ctypes.data if b.size else None, b.size, var, C.byref(out)))
         return out.value
+
+    def eigsh(self, k=6, which="LA", ncv=None, tol=0.0, maxiter=None, v0=None, return_eigenvectors=True, variant="auto"):
+        """The k algebraically largest (``which="LA"``) or smallest ("SA") eigenpairs of a SYMMETRIC matrix by thick-restart Lanczos
+        with full reorthogonalisation -- an EXTENSION (``smh_eigsh_vec``; the reference has no eigensolver).  Symmetry is the
+        caller's promise, as it is for ``ConjugateGradient``: nothing checks it.  A multiple eigenvalue is found once.
+        ``ncv``: the columns of the basis, k + 2 .. 128 after clipping to the dimension (None: min(n, max(2 k + 1, 20)));
+        ``tol``: pair i is converged when its estimate is at most tol * max|theta| (0 stands for 2^10 eps of the matrix dtype);
+        ``maxiter``: the restarts allowed (None: 1000); ``v0``: the start, a DenseVec or array-like (None:
+        ``numpy.random.default_rng(0).standard_normal(n)`` -- the library itself draws no random numbers).
+        Returns an ``EigshResult``: ``values`` (f64, wanted-first), ``vectors`` (a MultiVec of k columns, not renormalised; None
+        without ``return_eigenvectors``), ``estimates``, ``n_conv`` (the converged prefix; < k when ``maxiter`` ran out: the k
+        best pairs are returned all the same), ``restarts``, ``products`` and ``breakdown`` (0; 1: the Krylov space is exhausted,
+        the pairs that exist are exact; 2: a zero or non-finite start; 3: non-finite data -- 2 and 3 return no pairs: ``values``,
+        ``vectors`` and ``estimates`` are None)."""
+        n, k = self.n_rows(), int(k)
+        if which not in _lib.EIGSH_WHICH:
+            raise ValueError('which must be "LA" or "SA"')
+        if v0 is None:
+            v0 = np.random.default_rng(0).standard_normal(n)
+        start = v0 if isinstance(v0, DenseVec) else DenseVec.from_vec(np.ascontiguousarray(v0, dtype=self._dtype))
+        if tol == 0.0:
+            tol = 1024.0 * float(np.finfo(self._dtype).eps)
+        vectors = MultiVec.zeros(n, k, self._dtype) if return_eigenvectors and 0 < k <= n else None
+        values, estimates = np.zeros(max(k, 1), np.float64), np.zeros(max(k, 1), np.float64)
+        n_conv, restarts, products, brk = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int()
+        dp = C.POINTER(C.c_double)
+        check(lib().smh_eigsh_vec(self._h, start._h, vectors._h if vectors is not None else None, k, int(ncv or 0), _lib.EIGSH_WHICH[which],
+                                  float(tol), 1000 if maxiter is None else int(maxiter), _lib.VARIANTS[variant], values.ctypes.data_as(dp),
+                                  estimates.ctypes.data_as(dp), C.byref(n_conv), C.byref(restarts), C.byref(products), C.byref(brk)))
+        nothing = brk.value in (2, 3)
+        return EigshResult(None if nothing else values[:k], None if nothing else vectors, None if nothing else estimates[:k], n_conv.value,
+                           restarts.value, products.value, brk.value)
 
     def prepare(self, variant="auto"):
         """Build the lazily created workspaces of ``variant`` now (before capturing mvp_dev into a hipGraph)."""
